@@ -17,8 +17,9 @@ figure is kept as `consumer_only`.)
 `python3 bench.py --gpus N` without a launcher starts its own ranks: a child `python -m torch.distributed.run --nnodes 1
 --nproc-per-node N bench.py <same arguments>`, rank 0's JSON line relayed, the child's exit code returned.
 
-The timed region is a block of EXACTLY --steps steps between barrier + synchronize on both sides; the block is repeated
---blocks times (default 5) and `value` / `ms_per_step` come from the MEDIAN block (all are listed under `blocks`).
+The timed region is EXACTLY --steps steps, in --blocks blocks (default 1) between barrier + synchronize on both sides;
+`value` / `ms_per_step` come from the block with the median time per step (all are listed under `blocks`).
+`--dump-outputs DIR` writes the rows the last timed step returned as float64 .npy files (dump_rows).
 
 Prints ONE JSON line on rank 0: value = loci of all ranks / max-over-ranks time; roofline = the bytes the step's dominant kernel
 (the walk that writes the read words) has to move per launch over its mean HIP-event duration, against 8 TB/s; cpu_baseline =
@@ -45,7 +46,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 # heavy imports happen inside main(): the CPU leg's spawned workers re-import this module
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+HBM_PEAK_GBS = 8000.0          # MI355X HBM3E: 8 TB/s spec
 
 
 def parse_args(argv=None):
@@ -53,9 +54,8 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--blocks", type=int, default=25, help="timed blocks of EXACTLY --steps steps each (barrier + synchronize on both sides of "
-                                                           "every block); value = the median block.  25 blocks of 20 steps are 1.3 s of device work: a median "
-                                                           "over more blocks, and long enough for an outside observer of the GPU to see it busy")
+    ap.add_argument("--blocks", type=int, default=1, help="timed blocks the --steps steps are split into (barrier + synchronize on both sides of "
+                                                          "every block; at most one block per step); value = the block with the median time per step")
     ap.add_argument("--place", type=int, default=0,
                     help="(round 4's bench-side trials, kept for comparison) extra allocations of the read words tried by the BENCH at "
                          "set-up, each timed with the real walk, the fastest kept.  Default 0: the library places the array itself - "
@@ -78,7 +78,69 @@ def parse_args(argv=None):
                          "them in each rank's HBM (diagnostic: isolates the collective)")
     ap.add_argument("--wire", choices=("packed", "full"), default="packed",
                     help="N > 1: what travels to rank 0 - the packed wire rows (default) or the full 432-byte rows")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the rows the last of them returned (rank 0's, or what rank 0 gathered) to "
+                         "DIR/<field>.npy in float64 (finite: a floating-point field as <field> and <field>_finite): every locus, "
+                         "or a fixed seeded sample of them when that exceeds 60 MB")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+def step_blocks(steps: int, blocks: int) -> list:
+    """The timed blocks' sizes: --steps split into --blocks blocks (at most one per step, sizes differ by at most one) - together
+    EXACTLY --steps steps."""
+    n = max(1, min(blocks, steps))
+    return [steps // n + (i < steps % n) for i in range(n)]
+
+
+DUMP_BYTES = 60 << 20          # --dump-outputs: array bytes at most (64 MB in all with the .npy headers)
+DUMP_SEED = 20240              # --dump-outputs: the sample of loci when all of them do not fit
+
+
+def _row_columns(rows) -> dict:
+    """smc_row fields as arrays: a candidate's as cand_<name> ([n, 2, ...]), a 64-bit integer as its two 32-bit halves, no padding.
+    Every array is finite: a floating-point field comes as <name> (0 where the row holds NaN or an infinity, e.g. the p-value of a
+    Fisher test that was not run) and <name>_finite (1 where <name> is the row's value, else 0)."""
+    import numpy as np
+    cols = {}
+
+    def add(name, v):
+        if v.dtype.kind in "iu" and v.dtype.itemsize == 8:
+            v = v.astype(np.uint64)
+            cols[name + "_lo32"], cols[name + "_hi32"] = v & np.uint64(0xFFFFFFFF), v >> np.uint64(32)
+        elif v.dtype.kind == "f":
+            fin = np.isfinite(v)
+            cols[name], cols[name + "_finite"] = np.where(fin, v, 0.0), fin
+        else:
+            cols[name] = v
+    for f in rows.dtype.names:
+        if f == "cand":
+            for g in rows.dtype["cand"].base.names:
+                if g != "pad":
+                    add("cand_" + g, rows["cand"][g])
+        else:
+            add(f, rows[f])
+    return cols
+
+
+def dump_rows(rows, out_dir: str) -> dict:
+    """--dump-outputs: `rows` (ROW_DTYPE) as out_dir/<field>.npy in float64 (exact for every integer field, finite throughout:
+    _row_columns), with locus.npy the loci's indices in the run: every locus when they fit in DUMP_BYTES, else a sample of them
+    drawn with DUMP_SEED - the same loci for the same arguments, so that two builds can be compared file for file."""
+    import numpy as np
+    n = len(rows)
+    per_locus = 8 * (1 + sum(int(np.prod(v.shape[1:], dtype=np.int64)) for v in _row_columns(rows[:1]).values()))
+    k = min(n, DUMP_BYTES // per_locus)
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    cols = _row_columns(rows[idx])
+    cols["locus"] = idx
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in cols.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+    return {"dir": out_dir, "loci": int(k), "of": int(n), "files": len(cols), "bytes": int(k * per_locus),
+            "sample": None if k == n else "%d loci drawn with numpy default_rng(%d), sorted" % (k, DUMP_SEED)}
 
 
 def self_launch(a) -> int:
@@ -341,14 +403,15 @@ def main():
     status = run.status()
     for k in run.t:
         run.t[k] = 0
-    blocks = []
-    _lib.check(L.smc_build_set_timing(eng.ctx, min(a.steps * a.blocks, 256)), "smc_build_set_timing")
-    for _ in range(max(1, a.blocks)):
+    blocks = []                                                  # seconds per step of each block
+    sizes = step_blocks(a.steps, a.blocks)
+    _lib.check(L.smc_build_set_timing(eng.ctx, min(a.steps, 256)), "smc_build_set_timing")
+    for n_b in sizes:
         torch.cuda.synchronize()
         if use_dist:
             dist.barrier()
         t_start = time.perf_counter()
-        for _ in range(a.steps):
+        for _ in range(n_b):
             step()
         pipe.drain()
         torch.cuda.synchronize()
@@ -359,12 +422,12 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if share_gpu else dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        blocks.append(elapsed)
+        blocks.append(elapsed / n_b)
     import ctypes
     k_ms, k_n = ctypes.c_float(), ctypes.c_int32()
     _lib.check(L.smc_build_kernel_ms(eng.ctx, ctypes.byref(k_ms), ctypes.byref(k_n)), "smc_build_kernel_ms")
     L.smc_build_set_timing(eng.ctx, 0)
-    elapsed = sorted(blocks)[len(blocks) // 2]                   # the median block
+    step_s = sorted(blocks)[len(blocks) // 2]                    # the block with the median time per step
     # what rank 0 received in the last step against what every rank sent (outside the timed region): a 64-bit sum over each
     # rank's last buffer, compared with the sum over the block rank 0 holds for that rank
     gather_check = None
@@ -381,6 +444,18 @@ def main():
             gather_check = {"ranks": len(sent), "blocks_equal_what_was_sent": got_sums == sent, "bytes_per_rank": int(pipe.bufs[b_last].numel())}
             if got_sums != sent:
                 raise SystemExit("bench.py: the rows rank 0 gathered differ from what the ranks sent: %r vs %r" % (got_sums, sent))
+    # --dump-outputs: what the last timed step returned to its caller - this rank's rows, or on rank 0 the rows it gathered
+    # (packed wire rows are unpacked: the printed fields, the rest zero / NaN) - downloaded before anything else writes the buffers
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        b_last = (pipe.n - 1) % len(pipe.bufs)
+        if gather:
+            got = np.concatenate([t.cpu().numpy() for t in pipe.recv[b_last]])
+            last_rows = abi.unpack_wire(got.view(abi.WIRE_DTYPE)) if packed else got.view(abi.ROW_DTYPE)
+        else:
+            last_rows = pipe.bufs[b_last].cpu().numpy().view(abi.ROW_DTYPE)
+        dumped = dump_rows(last_rows, a.dump_outputs)
+        del last_rows
     # the locus kernels of the same planes, timed alone with one more plan (outside the timed region)
     if slot_streams is not None:
         torch.cuda.set_stream(torch.cuda.default_stream(dev))
@@ -407,9 +482,9 @@ def main():
     if rank == 0:
         n_steps = max(1, run.t["n"])
         out = {
-            "metric": "loci/sec at fixed read-depth x rpb", "value": total_loci * a.steps / elapsed,
+            "metric": "loci/sec at fixed read-depth x rpb", "value": total_loci / step_s,
             "unit": "loci/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": a.scaling,
+            "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": a.scaling,
             "vs_baseline": None, "dtype": "u8/u32 scan + f64 posterior", "data": "synthetic",
             "config": {"workload": "%s: %d loci%s x %d reads (%d UMIs x %d rpb), seed %d; as ALIGNMENTS resident in HBM: %s"
                        % (cfg.name, n_loc, "/GPU" if a.scaling == "weak" else " in total", cfg.depth, cfg.n_umi, cfg.rpb, cfg.seed,
@@ -425,15 +500,15 @@ def main():
                                                                                  "rows left in each rank's HBM (--rows resident)")),
                        "build_s": round(t_build, 1), **({"note": "SMC_BENCH_SHARE_GPU: all ranks on one GPU through gloo - a functional "
                                                                          "check of the N > 1 path, not a measurement"} if share_gpu else {})},
-            "blocks": {"n": len(blocks), "steps_each": a.steps, "ms_per_step": [round(b / a.steps * 1e3, 4) for b in blocks],
-                       "value_from": "median block", "spread_pct": round(100.0 * (max(blocks) - min(blocks)) / elapsed, 2)},
+            "blocks": {"n": len(blocks), "steps_each": sizes, "ms_per_step": [round(b * 1e3, 4) for b in blocks],
+                       "value_from": "median block", "spread_pct": round(100.0 * (max(blocks) - min(blocks)) / step_s, 2)},
             "roofline": dict(bench_fa.roofline_block(run, k_ms.value, k_n.value, a.config), **{
                 # SURVEY.md 8d's per-locus figure (16 B per pileup read + 360 B per locus) charged to the WHOLE step - what VERDICT r3
                 # holds against the north star's "40 % of the HBM roofline" (this rank's share of the step)
                 "whole_step_on_survey_8d": {
                     "bytes_per_step": 16.0 * run.reads + 360.0 * run.nl,
-                    "achieved": (16.0 * run.reads + 360.0 * run.nl) / (elapsed / a.steps) / 1e9, "unit": "GB/s",
-                    "frac": (16.0 * run.reads + 360.0 * run.nl) / (elapsed / a.steps) / 1e9 / HBM_PEAK_GBS},
+                    "achieved": (16.0 * run.reads + 360.0 * run.nl) / step_s / 1e9, "unit": "GB/s",
+                    "frac": (16.0 * run.reads + 360.0 * run.nl) / step_s / 1e9 / HBM_PEAK_GBS},
                 # the step one at a time with the read words in the other width, same process, same inputs, right after the headline
                 **({"other_read_word_width_same_run": dict(other_width, ms_per_step_one_at_a_time_this_width=serial_ms)} if other_width else {})}),
             "step_breakdown": {"slots": a.slots, "slot_choice": run.slot_choice, "ms_per_step_one_at_a_time": serial_ms, "placement": run.placement,
@@ -442,7 +517,7 @@ def main():
                                               "blocks": list(eng.alloc_log)},
                                "k_bp_emit2_ms": k_ms.value, "k_call_v2_ms": c_ms,
                                "host_ms_per_step": {k: round(v / n_steps * 1e3, 3) for k, v in run.t.items() if k != "n"},
-                               "pileup_reads_per_s": run.reads * a.steps / elapsed, "builder_status": status,
+                               "pileup_reads_per_s": run.reads / step_s, "builder_status": status,
                                "plans": bench_fa.plans_record(eng)},
             "p_value_note": "C3 has no locus that reaches filterVariants (parity.loci_filtered 0): the p-value half of the metric is "
                             "carried by from_alignments X3 / EX / C5 (the same step as the headline, variants under the reads) and by "
@@ -453,6 +528,8 @@ def main():
         }
         if gather_check is not None:
             out["gather_check"] = gather_check
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if cpu is not None:
             out["cpu_baseline"], out["cpu_baseline_c"] = cpu["python_pool"], cpu["c_port"]
             out["cpu_baseline_c_all_cores"] = cpu["c_port_all_cores"]
@@ -484,10 +561,12 @@ def main():
         # smc_plan_run_words, every row against oracle/aln_planes.c + oracle/smc_oracle.c - BASELINE's configs[4] (C5), loci that
         # reach filterVariants and its Fisher tests (X3, EX), the reference's own depth (EX) and the small batch (C2)
         out["from_alignments"] = {}
+        sizes = step_blocks(a.steps, a.blocks)        # (run_leg times equal blocks: one block when --steps does not divide evenly)
+        per_block, n_blocks = (sizes[0], len(sizes)) if len(set(sizes)) == 1 else (a.steps, 1)
         for name in ("C5", "X3", "EX", "C2"):
             torch.cuda.empty_cache()
             eng.trim()
-            o = bench_fa.run_leg(eng, name, synth.CONFIGS[name].n_loci, a.steps, a.warmup, a.blocks, nthreads,
+            o = bench_fa.run_leg(eng, name, synth.CONFIGS[name].n_loci, per_block, a.warmup, n_blocks, nthreads,
                                  parity_loci=0 if a.no_parity else -1, slots=a.slots, place=0)
             for k in ("placement", "generate_s"):
                 o.pop(k, None)
@@ -618,7 +697,7 @@ class _TensorBuf(object):
 
 
 def other_config(eng, name, a, dev, nthreads, oracle):
-    """The locus kernels alone on a single-GPU shape (resident read words, warm-up, blocks of --steps steps, median block,
+    """The locus kernels alone on a single-GPU shape (resident read words, warm-up, --steps steps in --blocks blocks, median block,
     HIP-event time of the dominant kernel, every row checked), reported as one short object."""
     cfg = synth.CONFIGS[name]
     params = synth.params_for(cfg)
@@ -627,22 +706,22 @@ def other_config(eng, name, a, dev, nthreads, oracle):
     rows = res.plan.alloc_rows()
     for _ in range(a.warmup):
         res.run(rows)
-    blocks = []
-    res.plan.set_timing(min(a.steps * a.blocks, 256))
-    for _ in range(max(1, a.blocks)):
+    blocks = []                                                  # seconds per step of each block
+    res.plan.set_timing(min(a.steps, 256))
+    for n_b in step_blocks(a.steps, a.blocks):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(a.steps):
+        for _ in range(n_b):
             res.run(rows)
         torch.cuda.synchronize()
-        blocks.append(time.perf_counter() - t0)
+        blocks.append((time.perf_counter() - t0) / n_b)
     k_ms, k_n, k_loci, k_reads = res.plan.kernel_ms()
     res.plan.set_timing(0)
-    el = sorted(blocks)[len(blocks) // 2]
+    step_s = sorted(blocks)[len(blocks) // 2]
     o = {"workload": "%s: %d loci x %d reads (%d UMIs x %d rpb), seed %d; read words resident in HBM"
                      % (name, cfg.n_loci, cfg.depth, cfg.n_umi, cfg.rpb, cfg.seed),
-         "value": cfg.n_loci * a.steps / el, "unit": "loci/s", "ms_per_step": el / a.steps * 1e3,
-         "blocks_ms_per_step": [round(b / a.steps * 1e3, 4) for b in blocks],
+         "value": cfg.n_loci / step_s, "unit": "loci/s", "ms_per_step": step_s * 1e3,
+         "blocks_ms_per_step": [round(b * 1e3, 4) for b in blocks],
          "roofline": call_roofline(res.loci, k_ms, k_n, k_loci, k_reads, "%s:%d" % (name, cfg.n_loci))}
     if oracle is not None:
         res.run(rows)

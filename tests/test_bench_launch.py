@@ -77,6 +77,44 @@ def test_the_headline_line_is_short_and_round_trips(tmp_path, capsys, monkeypatc
     assert full == json.loads(json.dumps(rec)) and json.loads(cap.err.strip().splitlines()[-1]) == full
 
 
+def test_the_timed_blocks_hold_exactly_steps_steps():
+    import bench
+    for steps, blocks in ((20, 1), (20, 25), (3, 2), (10, 4), (1, 5)):
+        sizes = bench.step_blocks(steps, blocks)
+        assert sum(sizes) == steps and len(sizes) == min(steps, blocks) and max(sizes) - min(sizes) <= 1
+
+
+def test_dump_outputs_are_float64_exact_and_a_fixed_sample_when_large(tmp_path):
+    """--dump-outputs: one float64 .npy per row field (integers exact, 64-bit masks as two halves, floating-point fields finite with
+    a mask of where the row's value is finite), every locus when they fit, else the same seeded sample of loci from run to run,
+    within the size limit."""
+    import numpy as np
+    import bench
+    from smcounter_amd import abi
+    rng = np.random.default_rng(3)
+    rows = np.frombuffer(rng.integers(0, 256, 3000 * abi.ROW_DTYPE.itemsize, dtype=np.uint8).tobytes(), abi.ROW_DTYPE).copy()
+    rows["pi"] = rng.random(rows["pi"].shape)
+    rows["cand"]["p_sb"] = np.where(rng.random(rows["cand"]["p_sb"].shape) < 0.5, np.nan, 0.25)    # (a test not run: NaN)
+    rec = bench.dump_rows(rows, str(tmp_path / "all"))
+    assert rec["loci"] == 3000 and rec["sample"] is None
+    got = {f.stem: np.load(f) for f in (tmp_path / "all").glob("*.npy")}
+    assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in got.values()) and len(got) == rec["files"]
+    ran = ~np.isnan(rows["cand"]["p_sb"])
+    assert (got["cand_p_sb_finite"] == ran).all() and (got["cand_p_sb"][ran] == 0.25).all() and (got["cand_p_sb"][~ran] == 0).all()
+    assert (got["status"] == rows["status"]).all() and (got["cand_flt"] == rows["cand"]["flt"]).all()
+    assert (got["pi"] == rows["pi"]).all() and (got["pi_finite"] == 1).all() and (got["locus"] == np.arange(3000)).all()
+    mask = got["touched_mask_lo32"].astype(np.uint64) | (got["touched_mask_hi32"].astype(np.uint64) << np.uint64(32))
+    assert (mask == rows["touched_mask"]).all()
+    big = np.resize(rows, 120000)
+    a, b = bench.dump_rows(big, str(tmp_path / "a")), bench.dump_rows(big, str(tmp_path / "b"))
+    assert a == dict(b, dir=a["dir"]) and a["loci"] < 120000
+    assert sum(f.stat().st_size for f in (tmp_path / "a").glob("*.npy")) <= 64 << 20
+    assert all(np.isfinite(np.load(f)).all() for f in (tmp_path / "a").glob("*.npy"))
+    idx = np.load(tmp_path / "a" / "locus.npy").astype(np.int64)
+    assert (np.load(tmp_path / "a" / "cvg.npy") == big["cvg"][idx]).all()
+    assert (idx == np.load(tmp_path / "b" / "locus.npy")).all()
+
+
 def test_bench_refuses_a_world_that_does_not_match():
     env = dict(os.environ, WORLD_SIZE="3", RANK="0", SMC_BENCH_DRY="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=120)

@@ -9,7 +9,7 @@ import dataclasses
 import numpy as np
 import pytest
 
-from conftest import ROOT, golden_files, load_golden
+from conftest import GOLDEN, ROOT, golden_files, load_golden
 from smcounter_amd import _lib, abi, dist, features, hpregion, py2compat, rows, synth
 from smcounter_amd.params import VcParams
 
@@ -119,11 +119,9 @@ def test_convert_to_vcf():
 def test_example_all_txt_invariants():
     """The reference's shipped example output pins the arithmetic of the derived columns and the
     number formatting: rebuild them from the integer columns of every row with
-    this repo's rounding / printing and compare as strings.  (The file is read from the reference
-    tree when present - build container - and skipped elsewhere.)"""
-    path = "/root/reference/example/example.smCounter.all.txt"
-    if not os.path.exists(path):
-        pytest.skip("reference example not available on this box")
+    this repo's rounding / printing and compare as strings.  (The file is the copy stored under
+    tests/golden/example.)"""
+    path = os.path.join(GOLDEN, "example", "example.smCounter.all.txt")
     hdr = None
     n = 0
     for line in open(path):

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 8
+#define SMC_ABI_VERSION 9
 #define SMC_MAX_ALLELES 64 /* allele ids per locus; ids 0-5 are A,T,G,C,N,'DEL' */
 
 /* error codes */
@@ -380,6 +380,24 @@ int smc_philox_marks(smc_ctx* ctx, const smc_params* prm, smc_locus* d_loci, int
                      int word_bits, uint32_t* d_umi_start, const uint64_t* d_ident, const uint32_t* d_ident_index, uint64_t seed,
                      uint32_t* d_status, void* stream);
 void smc_philox4x32_10_host(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+/* (ABI 9) In-run molecule down-sampling (ds.mt.py:23-72 without the BAM in between): the alignments of one run (smc_dev_aln[n_aln],
+ * smc_dev_locus[n_loci], as smc_build_planes takes them; the CIGAR and base pools are not touched) reduced to those of the KEPT
+ * barcodes, and the descriptors recomputed as smc_bam_alignments computes them for the down-sampled BAM:
+ *   d_aln_out[k], d_orig_index[k]   the kept alignments in file order, and each one's index in d_aln (capacity: n_aln each)
+ *   d_loc_out[n_loci]               w0 = first kept alignment with end > p; w1 = max(w0, first kept alignment with pos > p);
+ *                                   n = kept alignments with pos <= p < end; slot_off = exclusive scan of n rounded up to 4
+ *                                   (p = start0 + locus index)
+ *   d_summary[4]                    kept alignments, deepest n, total slots, 0
+ * bc_gid / pair_gid stay as they were (with gaps, in order: the builder only compares them), as do the run's n_bc / n_pair, and every
+ * kept alignment keeps its cig_off / seq_off.  Which barcodes are kept, by run-wide id g < n_ids:
+ *   d_keep_mask != NULL  bit g of d_keep_mask (uint32 words) - a set the host chose (the reference's semantics);
+ *   else                 Philox4x32-10(counter = (d_ident[g] lo, hi, 0x64734D54, 0), key = (seed lo, hi)) word 0 < floor(frac * 2^32);
+ *                        frac >= 1 keeps every barcode.  The same draw for every fraction: the kept sets are nested.
+ * The input windows d_loc are not read (may be NULL).  Asynchronous on `stream`; one scratch per context (calls of one context are
+ * to be ordered on one stream). */
+int smc_select_alignments(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0,
+                          const uint32_t* d_keep_mask, const uint64_t* d_ident, int64_t n_ids, uint64_t seed, double frac,
+                          smc_dev_aln* d_aln_out, uint32_t* d_orig_index, smc_dev_locus* d_loc_out, uint32_t* d_summary, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

@@ -355,6 +355,32 @@ def iter_raw_records(path: str):
     return bytes(hdr), records()
 
 
+def placed_barcodes(path: str) -> List[str]:
+    """The distinct barcodes (read name field -2, smCounter.py:320-325) of every record placed on a reference (tid >= 0), in order of
+    first appearance in the file: what ds.mt.py's `for read in samfile.fetch()` fills its bcDict with (ds.mt.py:38-48).  The whole
+    file is inflated at once (C), the records are walked without being parsed."""
+    import gzip
+    with open(path, "rb") as fh:
+        data = gzip.decompress(fh.read())
+    if data[:4] != b"BAM\1":
+        raise BamError("%s: not a BAM file" % path)
+    off = 8 + struct.unpack_from("<i", data, 4)[0]
+    n_ref = struct.unpack_from("<i", data, off)[0]
+    off += 4
+    for _ in range(n_ref):
+        off += 8 + struct.unpack_from("<i", data, off)[0]
+    seen = {}
+    unpack, end = struct.unpack_from, len(data)
+    while off + 4 <= end:
+        bs, tid = unpack("<ii", data, off)
+        if tid >= 0:
+            l_name = data[off + 12]
+            name = data[off + 36:off + 35 + l_name]
+            seen.setdefault(name.rsplit(b":", 2)[-2], None)
+        off += 4 + bs
+    return [b.decode() for b in seen]
+
+
 def write_raw(path: str, header: bytes, raw_records: Iterable[bytes], block: int = 60000) -> None:
     """BGZF-compress a header and raw BAM records (as `iter_raw_records` yields them) into a BAM file."""
     with open(path, "wb") as fh:

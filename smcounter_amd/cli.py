@@ -58,7 +58,57 @@ def build_parser() -> argparse.ArgumentParser:
                         "(Philox4x32-10) keyed by position and --samplerSeed - NOT the reference's sample: the rows of such loci differ "
                         "from smCounter's (another random subset of the same size); the same for every run, launch shape and GPU count")
     p.add_argument("--samplerSeed", type=int, default=0, help="seed of --sampler philox")
+    p.add_argument("--dsMT", default=None, help="in-run molecule down-sampling: comma-separated fractions f in (0, 1].  For each, the "
+                                                "run is also called as if on the BAM that ds.mt.py --pct f --seed dsSeed writes (each barcode "
+                                                "kept with probability f), at --mtDepth round(f x mtDepth); written to "
+                                                "<outPrefix>.dsMT<f>.smCounter.{all,cut}.txt and .cut.vcf.  The BAM is decoded once; the "
+                                                "drop is done on the GPU (needs the device plane builder; one process only)")
+    p.add_argument("--dsSampler", choices=("reference", "philox"), default="reference",
+                   help="which barcodes --dsMT keeps.  reference (default): exactly ds.mt.py's set - every placed read of the file, "
+                        "barcodes in Python 2 dict order, one random.random() each, kept when r <= f.  philox: on the GPU, a "
+                        "counter-based draw (Philox4x32-10) keyed by --dsSeed and a hash of the barcode text, kept when it falls below "
+                        "f - NOT the reference's sample (another random subset of about the same size; nested across fractions), "
+                        "without the pass over the whole file")
+    p.add_argument("--dsSeed", type=int, default=1234567, help="seed of --dsMT (ds.mt.py --seed)")
+    p.add_argument("--dsMtDepth", default=None, help="comma-separated --mtDepth of each --dsMT fraction; default "
+                                                     "max(1, round(f x mtDepth)) (sets that fraction's maxMT default and its threshold)")
     return p
+
+
+def ds_fractions(args):
+    """--dsMT / --dsMtDepth -> [(f, mtDepth of f, output prefix)]; [] without --dsMT."""
+    from .py2compat import py2_round
+    text = getattr(args, "dsMT", None)
+    if text in (None, ""):
+        return []
+    try:
+        fr = [float(x) for x in str(text).split(",") if x.strip()]
+    except ValueError:
+        raise SystemExit("--dsMT: comma-separated fractions in (0, 1] expected, got %r" % text)
+    if not fr or any(not (0.0 < f <= 1.0) for f in fr):
+        raise SystemExit("--dsMT: every fraction must lie in (0, 1], got %r" % text)
+    dtext = getattr(args, "dsMtDepth", None)
+    if dtext not in (None, ""):
+        try:
+            depths = [int(x) for x in str(dtext).split(",") if x.strip()]
+        except ValueError:
+            raise SystemExit("--dsMtDepth: comma-separated integers expected, got %r" % dtext)
+        if len(depths) != len(fr):
+            raise SystemExit("--dsMtDepth: %d depths for %d --dsMT fractions" % (len(depths), len(fr)))
+    else:
+        depths = [max(1, int(py2_round(f * args.mtDepth))) for f in fr]
+    return [(f, d, "%s.dsMT%g" % (args.outPrefix, f)) for f, d in zip(fr, depths)]
+
+
+def ds_rules(args, params: VcParams, fractions):
+    """The devplanes.DsRule of every --dsMT fraction (the reference's sampler: one pass over the whole file, here)."""
+    import dataclasses
+    from . import devplanes
+    plist = [dataclasses.replace(params, mtDepth=d) for _, d, _ in fractions]
+    fr = [f for f, _, _ in fractions]
+    if getattr(args, "dsSampler", "reference") == "philox":
+        return [devplanes.DsRule(f, P, kept=None, seed=int(args.dsSeed)) for f, P in zip(fr, plist)]
+    return devplanes.reference_rules(args.bamFile, fr, plist, int(args.dsSeed))
 
 
 class _EarlyEngine(object):
@@ -108,30 +158,41 @@ def call_shard(args, params: VcParams, loci, device: int, early=None):
     eng = early.get() if early is not None else (_ENGINES.pop(device, None) or Engine(device))
     output = _Rows()
     decoder = os.environ.get("SMC_BAM_DECODER", "native")
+    rules = getattr(args, "ds_rules", None) or None
     # (one process per GPU: the ranks of a node share its cores for decoding)
     # (LOCAL_WORLD_SIZE: WORLD_SIZE also counts the ranks of other nodes, which do not share these cores)
     per_node = int(os.environ.get("LOCAL_WORLD_SIZE") or os.environ.get("WORLD_SIZE", "1"))
     nthreads = bamio.host_threads(per_node)
-    if decoder == "python":                                           # readable decoder, same batches
+    if rules is None and decoder == "python":                         # readable decoder, same batches
         batches = bamio.iter_pileup_batches(bamio.BamFile(args.bamFile), ref, loci, max_reads=args.batchReads)
-    elif os.environ.get("SMC_PLANES", "device") == "host":             # planes built by the host threads, then uploaded
+    elif rules is None and os.environ.get("SMC_PLANES", "device") == "host":   # planes built by the host threads, then uploaded
         batches = bamio.iter_device_batches_native(args.bamFile, ref, loci, params, max_reads=args.batchReads,
                                                    nthreads=nthreads)
     else:
         # default: the host decodes alignments, the GPU builds the planes from them (k_build_planes) and they stay in HBM
         from . import devplanes
         # (a batch only lives in HBM here - 16 B per read - so it can be eight times the host-built default)
+        # (--dsMT: the same batches at full depth and for every fraction - the device builder only, SMC_PLANES=host or
+        # SMC_BAM_DECODER=python end with an error naming the first run)
         batches = devplanes.iter_resident_batches(args.bamFile, ref, loci, params, eng, max_reads=32 * args.batchReads,
                                                   nthreads=nthreads, all_planes=False, sampler=getattr(args, "sampler", "reference"),
-                                                  sampler_seed=getattr(args, "samplerSeed", 0))
+                                                  sampler_seed=getattr(args, "samplerSeed", 0), ds_rules=rules,
+                                                  force_host=rules is not None and (decoder == "python" or
+                                                                                    os.environ.get("SMC_PLANES", "device") == "host"))
         # (a batch ahead in a helper thread: decoding and building batch i + 1 overlaps the kernels and the strings of batch i;
         # the two threads use different staging buffers of the engine, device work is ordered by the default stream)
         if not _lib.exp_env("SMC_NO_PREFETCH"):
             batches = _prefetch(batches, depth=1)
+        ds_out = [_Rows() for _ in (rules or ())]
         for first, rb in batches:
+            if rules is not None:
+                rb, rbs = rb[0], rb[1:]
+                for rule, o, b in zip(rules, ds_out, rbs):
+                    o.add(vc.vc_resident(b, rule.params, ref, eng))
             output.add(vc.vc_resident(rb, params, ref, eng))
             _report_boundary(eng.last_rows, rb.chrom, rb.pos)
         _release_engine(eng)
+        output.ds = [o.done() for o in ds_out]
         return output.done()
     for first, pb in _prefetch(batches):
         output.add(vc.vc_batch(pb, params, ref, eng=eng))
@@ -260,11 +321,21 @@ def _main(args) -> int:
 
     params = VcParams(minBQ=args.minBQ, minMQ=args.minMQ, mtDepth=args.mtDepth, rpb=args.rpb, hpLen=args.hpLen,
                       mismatchThr=args.mismatchThr, mtDrop=args.mtDrop, maxMT=args.maxMT, primerDist=args.primerDist)
+    fractions = ds_fractions(args)
+    if fractions and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--dsMT runs in one process only (not under torch.distributed.run with more than one rank)")
+    host = [v for v, on in (("SMC_PLANES=host", os.environ.get("SMC_PLANES", "device") == "host"),
+                            ("SMC_BAM_DECODER=python", os.environ.get("SMC_BAM_DECODER", "native") == "python")) if on]
+    if fractions and host:
+        first = bedops.expand_loci(args.bedTarget)[:1]
+        raise SystemExit("--dsMT needs the device builder: the run at %s would be built on the host (%s)" %
+                         ("%s:%s" % first[0] if first else "(no targets)", host[0]))
     early = None
     if int(os.environ.get("WORLD_SIZE", "1")) == 1 and os.environ.get("SMC_BAM_DECODER", "native") != "python":
         # a single process: the GPU runtime and the context come up (~ 0.1 s) in a helper thread while the target is expanded
         early = _EarlyEngine(args.device)
     loc_list = bedops.expand_loci(args.bedTarget)
+    args.ds_rules = ds_rules(args, params, fractions) if fractions else None
     # One process per GPU when launched through torch.distributed.run: rank r calls a contiguous range of the
     # ordered locus list (loci share nothing, smCounter.py:683-685) on GPU LOCAL_RANK, rank 0 gathers the rows
     # in submission order and writes the files.
@@ -335,9 +406,15 @@ def _main(args) -> int:
         args.bedTandemRepeats if args.bedTandemRepeats and os.path.exists(args.bedTandemRepeats) else None,
         args.bedRepeatMaskerSubset if args.bedRepeatMaskerSubset and os.path.exists(args.bedRepeatMaskerSubset) else None)
     pred = getattr(output, "pred", None)                  # (single process: the printer's int(PI) per row)
+    ds_outputs = getattr(output, "ds", None) or []        # (--dsMT: the rows of every fraction)
     output = postfilter.apply_repeat_filters(output, trf, rm, pred=pred)
     threshold = writers.pi_threshold(args.mtDepth, args.threshold)
     writers.write_outputs(args.outPrefix, output, threshold, pred=pred)
+    for (f, d, prefix), o in zip(fractions, ds_outputs):
+        vc.raise_on_exception(o, loc_list)
+        o_pred = getattr(o, "pred", None)
+        o = postfilter.apply_repeat_filters(o, trf, rm, pred=o_pred)
+        writers.write_outputs(prefix, o, writers.pi_threshold(d, args.threshold), pred=o_pred)
     t1 = datetime.datetime.now()
     print("smCounter completed running at " + str(t1))
     print("smCounter total time: " + str(t1 - t0))

@@ -31,6 +31,9 @@ struct smc_ctx {
     void* bp_scratch = nullptr;
     size_t bp_bytes = 0;
     hipEvent_t bp_done_ev = nullptr;          // behind the last kernel of the last smc_build_planes: the next build, on whatever stream, waits for it (one scratch)
+    // scratch of smc_select_alignments (block counts / offsets, the blocks' largest ends, the difference array), grown on demand
+    void* sel_scratch = nullptr;
+    size_t sel_bytes = 0;
     // the segment table of a build travels from page-locked memory (a copy from pageable memory blocks the host until the stream has
     // drained): a small ring, an entry reused once the copy that read it has run (its event)
     struct SegStage { void* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
@@ -324,6 +327,7 @@ void smc_destroy(smc_ctx* c) {
     (void)hipFree(c->pcr);
     (void)hipFree(c->lfact);
     (void)hipFree(c->bp_scratch);
+    (void)hipFree(c->sel_scratch);
     {
         std::vector<smc_ctx::VmmBlock> left;
         { std::lock_guard<std::mutex> g(c->vmm_mu); left.swap(c->vmm); }
@@ -812,6 +816,49 @@ int smc_philox_marks(smc_ctx* ctx, const smc_params* prm, smc_locus* d_loci, int
 }
 // (no GPU needed) the generator itself, for known-answer tests of the binding
 void smc_philox4x32_10_host(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) { smc_philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], out); }
+
+int smc_select_alignments(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0,
+                          const uint32_t* d_keep_mask, const uint64_t* d_ident, int64_t n_ids, uint64_t seed, double frac,
+                          smc_dev_aln* d_aln_out, uint32_t* d_orig_index, smc_dev_locus* d_loc_out, uint32_t* d_summary, void* stream) {
+    if (!ctx) return fail(SMC_E_ARG, "smc_select_alignments: NULL context");
+    if (n_aln < 0 || n_loci < 0 || n_ids < 0 || n_aln >= (int64_t)0xFFFFF000 || n_loci >= (int64_t)0x7FFFFFFF ||
+        n_ids > (int64_t)0xFFFFFFFF || (!d_keep_mask && !d_ident && n_ids > 0) || !(frac >= 0.0))
+        return fail(SMC_E_ARG, "smc_select_alignments: bad argument");
+    if ((n_aln && (!d_aln || !d_aln_out || !d_orig_index)) || (n_loci && !d_loc_out) || !d_summary)
+        return fail(SMC_E_ARG, "smc_select_alignments: NULL device pointer");
+    (void)d_loc;                          // (the input windows are not needed: the decoder's rules are applied to the kept alignments)
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t n_blk = (uint32_t)((n_aln + SEL_ITEMS - 1) / SEL_ITEMS), nl = (uint32_t)n_loci;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_off = carve(4 * ((size_t)n_blk + 1)), o_max = carve(4 * ((size_t)n_blk + 1)), o_diff = carve(4 * ((size_t)nl + 1));
+    if (off > ctx->sel_bytes) {
+        HIPCHK(hipStreamSynchronize(st));
+        (void)hipFree(ctx->sel_scratch);
+        ctx->sel_scratch = nullptr; ctx->sel_bytes = 0;
+        const size_t want = off + off / 8;
+        hipError_t e = hipMalloc(&ctx->sel_scratch, want);
+        if (e != hipSuccess) return fail(SMC_E_HIP, "smc_select_alignments: " + std::to_string(want) + " bytes of scratch: " + hipGetErrorString(e));
+        ctx->sel_bytes = want;
+    }
+    char* sc = (char*)ctx->sel_scratch;
+    uint32_t* blk_off = (uint32_t*)(sc + o_off);
+    int32_t* blk_max = (int32_t*)(sc + o_max);
+    int32_t* diff = (int32_t*)(sc + o_diff);
+    SelRule R;
+    R.mask = d_keep_mask; R.ident = (const unsigned long long*)d_ident; R.seed = (unsigned long long)seed; R.n_ids = (uint32_t)n_ids;
+    R.thr = frac >= 1.0 ? (1ull << 32) : (unsigned long long)std::floor(frac * 4294967296.0);
+    if (n_blk) hipLaunchKernelGGL(k_sel_count, dim3(n_blk), dim3(SEL_BLOCK), 0, st, d_aln, (uint32_t)n_aln, R, blk_off);
+    hipLaunchKernelGGL(k_sel_offsets, dim3(1), dim3(SEL_SCAN), 0, st, blk_off, n_blk, diff, nl + 1u, d_summary);
+    if (n_blk) hipLaunchKernelGGL(k_sel_scatter, dim3(n_blk), dim3(SEL_BLOCK), 0, st, d_aln, (uint32_t)n_aln, R, (const uint32_t*)blk_off,
+                                  start0, nl, d_aln_out, d_orig_index, diff, blk_max);
+    hipLaunchKernelGGL(k_sel_loci, dim3(1), dim3(SEL_SCAN), 0, st, blk_max, n_blk, (const int32_t*)diff, nl, d_loc_out, d_summary);
+    if (nl) hipLaunchKernelGGL(k_sel_windows, dim3((nl + SEL_BLOCK / WAVE - 1) / (SEL_BLOCK / WAVE)), dim3(SEL_BLOCK), 0, st, (const smc_dev_aln*)d_aln_out,
+                               (const uint32_t*)blk_off, (const int32_t*)blk_max, n_blk, start0, nl, d_loc_out);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
 
 int smc_plan_set_timing(smc_plan* p, int slots) {
     if (!p || slots < 0) return fail(SMC_E_ARG, "smc_plan_set_timing: bad argument");

@@ -1,0 +1,233 @@
+// Included by smcounter_hip.hip (after k_philox_marks.inc: it uses smc_philox4x32_10).
+// ------------------------------------------------------------------------------------------
+// in-run molecule down-sampling: the alignments of the kept barcodes of a run, and the decoder's windows / depths over them
+// (smc_select_alignments)
+// ------------------------------------------------------------------------------------------
+// ds.mt.py:23-72 keeps every molecular barcode (with all its reads) with probability f and writes a BAM; smCounter then runs on
+// that BAM.  Here the run's alignments are already in HBM: the drop is done on them, and the descriptors are recomputed exactly as
+// smc_bam_alignments (csrc/smc_bam.cpp) would compute them for the down-sampled BAM - so the plane builder and everything after it
+// run unchanged on the result.  A barcode is all in or all out, so the kept alignments keep the file order, the ids keep their
+// order (with gaps: the builder only compares them), and the decoder's rules carry over:
+//   w0'  = first kept alignment with end > p       (= first index whose running maximum of end passes p: a monotone predicate)
+//   w1'  = max(w0', first kept alignment with pos > p)
+//   n'   = kept alignments with pos <= p < end     (a difference array over the run's positions, then a scan)
+//   slot_off' = exclusive scan of n' rounded up to 4
+// Five launches on one stream:
+//   k_sel_count    per block of SEL_ITEMS alignments: how many are kept
+//   k_sel_offsets  one workgroup: exclusive scan of the block counts (the kept total into the summary); clears the difference array
+//   k_sel_scatter  the kept alignments and their input index compacted in file order (ballot ranks, the same rounds as k_sel_count);
+//                  +1 / -1 of every kept alignment into the difference array through an LDS window; the block's largest kept end
+//   k_sel_loci     one workgroup: running maximum of the block ends, the depths by a scan of the difference array, slot_off', the
+//                  deepest locus and the slots into the summary
+//   k_sel_windows  a wavefront per locus: w0' by a 64-way search over the blocks' running end maximum, then a scan of that block's
+//                  kept ends; w1' by a 64-way search over the kept positions
+#define SEL_BLOCK 256
+#define SEL_ROUNDS 4
+#define SEL_ITEMS (SEL_BLOCK * SEL_ROUNDS)   // alignments per block (a round: SEL_BLOCK consecutive ones, one per thread)
+#define SEL_SCAN 1024                        // threads of the one-workgroup scans
+#define SEL_WIN 4096                         // LDS window of the difference array per block (positions beyond it: global atomics)
+#define SEL_DOMAIN 0x64734D54u               // counter word 2 of the down-sampling draw ("dsMT"); smc_philox_marks uses 0 there
+
+struct SelRule {
+    const uint32_t* mask;              // non-null: bit g of the mask keeps barcode g (the host's set: the reference's semantics)
+    const unsigned long long* ident;   // else: one 64-bit identity per barcode, kept iff Philox word 0 < thr
+    unsigned long long seed, thr;      // thr = floor(f * 2^32); >= 2^32: everything
+    uint32_t n_ids;                    // ids at or beyond this are not kept (never met: the decoder numbers below n_bc)
+};
+
+__device__ __forceinline__ bool sel_keep(const SelRule& R, uint32_t gid) {
+    if (gid >= R.n_ids) return false;
+    if (R.mask) return ((R.mask[gid >> 5] >> (gid & 31u)) & 1u) != 0u;
+    if (R.thr >= (1ull << 32)) return true;
+    const unsigned long long id = R.ident[gid];
+    uint32_t x[4];
+    smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SEL_DOMAIN, 0u, (uint32_t)R.seed, (uint32_t)(R.seed >> 32), x);
+    return (unsigned long long)x[0] < R.thr;
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_sel_count(const smc_dev_aln* __restrict__ aln, uint32_t n_aln, SelRule R,
+                                                         uint32_t* __restrict__ blk_cnt) {
+    __shared__ uint32_t wsum[SEL_BLOCK / WAVE];
+    const uint32_t base = blockIdx.x * (uint32_t)SEL_ITEMS;
+    uint32_t mine = 0;
+#pragma unroll
+    for (int r = 0; r < SEL_ROUNDS; ++r) {
+        const uint32_t i = base + (uint32_t)r * SEL_BLOCK + threadIdx.x;
+        if (i < n_aln && sel_keep(R, aln[i].bc_gid)) ++mine;
+    }
+    for (int o = WAVE / 2; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
+    if ((threadIdx.x & (WAVE - 1)) == 0) wsum[threadIdx.x / WAVE] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0;
+        for (int w = 0; w < SEL_BLOCK / WAVE; ++w) s += wsum[w];
+        blk_cnt[blockIdx.x] = s;
+    }
+}
+
+// one workgroup's exclusive scan (op: sum or max) of the values v[t] of its SEL_SCAN threads; -> (exclusive, total)
+template <bool MAX>
+__device__ __forceinline__ void sel_wg_scan(int64_t v, int64_t* buf, int64_t id, int64_t& excl, int64_t& total) {
+    const int t = threadIdx.x;
+    buf[t] = v;
+    __syncthreads();
+    for (int o = 1; o < SEL_SCAN; o <<= 1) {
+        const int64_t a = t >= o ? buf[t - o] : id;
+        __syncthreads();
+        buf[t] = MAX ? (a > buf[t] ? a : buf[t]) : buf[t] + a;
+        __syncthreads();
+    }
+    excl = t ? buf[t - 1] : id;
+    total = buf[SEL_SCAN - 1];
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(SEL_SCAN) void k_sel_offsets(uint32_t* __restrict__ blk_cnt, uint32_t n_blk, int32_t* __restrict__ diff,
+                                                          uint32_t n_diff, uint32_t* __restrict__ summary) {
+    __shared__ int64_t buf[SEL_SCAN];
+    const uint32_t t = threadIdx.x, per = (n_blk + SEL_SCAN - 1) / SEL_SCAN, b0 = min(n_blk, t * per), b1 = min(n_blk, b0 + per);
+    int64_t s = 0;
+    for (uint32_t b = b0; b < b1; ++b) s += blk_cnt[b];
+    int64_t excl, total;
+    sel_wg_scan<false>(s, buf, 0, excl, total);
+    for (uint32_t b = b0; b < b1; ++b) { const uint32_t c = blk_cnt[b]; blk_cnt[b] = (uint32_t)excl; excl += c; }
+    if (t == 0) { blk_cnt[n_blk] = (uint32_t)total; summary[0] = (uint32_t)total; }
+    for (uint32_t i = t; i < n_diff; i += SEL_SCAN) diff[i] = 0;
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_sel_scatter(const smc_dev_aln* __restrict__ aln, uint32_t n_aln, SelRule R,
+                                                           const uint32_t* __restrict__ blk_off, int32_t start0, uint32_t n_loci,
+                                                           smc_dev_aln* __restrict__ out, uint32_t* __restrict__ orig_index,
+                                                           int32_t* __restrict__ diff, int32_t* __restrict__ blk_maxend) {
+    __shared__ int32_t win[SEL_WIN];
+    __shared__ uint32_t wcnt[SEL_BLOCK / WAVE];
+    __shared__ int32_t wmax[SEL_BLOCK / WAVE];
+    const uint32_t t = threadIdx.x, wv = t / WAVE, base = blockIdx.x * (uint32_t)SEL_ITEMS;
+    for (uint32_t k = t; k < SEL_WIN; k += SEL_BLOCK) win[k] = 0;
+    // (the block's alignments are sorted by position: the window starts at the first one's)
+    const int32_t wbase = max(aln[base].pos, start0) - start0;
+    __syncthreads();
+    uint32_t dst = blk_off[blockIdx.x];
+    int32_t me = INT_MIN;
+    auto add = [&](int32_t x, int32_t d) {
+        const uint32_t k = (uint32_t)(x - wbase);
+        if (k < (uint32_t)SEL_WIN) atomicAdd(&win[k], d); else atomicAdd(&diff[x], d);
+    };
+#pragma unroll 1
+    for (int r = 0; r < SEL_ROUNDS; ++r) {
+        const uint32_t i = base + (uint32_t)r * SEL_BLOCK + t;
+        smc_dev_aln a;
+        bool keep = false;
+        if (i < n_aln) { a = aln[i]; keep = sel_keep(R, a.bc_gid); }
+        const unsigned long long m = __ballot(keep);
+        const uint32_t lane = t & (WAVE - 1), rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wcnt[wv] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (uint32_t w = 0; w < SEL_BLOCK / WAVE; ++w) { before += w < wv ? wcnt[w] : 0u; all += wcnt[w]; }
+        if (keep) {
+            out[dst + before + rank] = a;
+            orig_index[dst + before + rank] = i;
+            const int32_t lo = max(a.pos, start0) - start0, hi = (int32_t)min<int64_t>((int64_t)a.end, (int64_t)start0 + n_loci) - start0;
+            if (lo < hi) { add(lo, 1); add(hi, -1); }
+            me = max(me, a.end);
+        }
+        dst += all;
+        __syncthreads();                                   // (wcnt is rewritten by the next round)
+    }
+    for (int o = WAVE / 2; o > 0; o >>= 1) me = max(me, __shfl_xor(me, o));
+    if ((t & (WAVE - 1)) == 0) wmax[wv] = me;
+    __syncthreads();
+    if (t == 0) {
+        int32_t m = INT_MIN;
+        for (int w = 0; w < SEL_BLOCK / WAVE; ++w) m = max(m, wmax[w]);
+        blk_maxend[blockIdx.x] = m;
+    }
+    for (uint32_t k = t; k < SEL_WIN; k += SEL_BLOCK) {
+        const int32_t v = win[k];
+        if (v && wbase + (int32_t)k <= (int32_t)n_loci) atomicAdd(&diff[wbase + (int32_t)k], v);
+    }
+}
+
+__global__ __launch_bounds__(SEL_SCAN) void k_sel_loci(int32_t* __restrict__ blk_maxend, uint32_t n_blk, const int32_t* __restrict__ diff,
+                                                       uint32_t n_loci, smc_dev_locus* __restrict__ loc_out, uint32_t* __restrict__ summary) {
+    __shared__ int64_t buf[SEL_SCAN];
+    __shared__ uint32_t deepest;
+    const uint32_t t = threadIdx.x;
+    if (t == 0) deepest = 0u;
+    // the running maximum of the blocks' largest kept end (inclusive): what k_sel_windows searches for w0'
+    {
+        const uint32_t per = (n_blk + SEL_SCAN - 1) / SEL_SCAN, b0 = min(n_blk, t * per), b1 = min(n_blk, b0 + per);
+        int64_t m = INT_MIN;
+        for (uint32_t b = b0; b < b1; ++b) m = max(m, (int64_t)blk_maxend[b]);
+        int64_t excl, total;
+        sel_wg_scan<true>(m, buf, INT_MIN, excl, total);
+        for (uint32_t b = b0; b < b1; ++b) { excl = max(excl, (int64_t)blk_maxend[b]); blk_maxend[b] = (int32_t)excl; }
+    }
+    // depths: a scan of the difference array (each thread a stretch of loci); then the 4-aligned slots
+    const uint32_t per = (n_loci + SEL_SCAN - 1) / SEL_SCAN, l0 = min(n_loci, t * per), l1 = min(n_loci, l0 + per);
+    int64_t s = 0;
+    for (uint32_t l = l0; l < l1; ++l) s += diff[l];
+    int64_t d_before, d_total;
+    sel_wg_scan<false>(s, buf, 0, d_before, d_total);
+    int64_t depth = d_before, slots = 0;
+    uint32_t dmax = 0;
+    for (uint32_t l = l0; l < l1; ++l) { depth += diff[l]; slots += (depth + 3) / 4 * 4; dmax = max(dmax, (uint32_t)depth); }
+    int64_t so, s_total;
+    sel_wg_scan<false>(slots, buf, 0, so, s_total);
+    depth = d_before;
+    for (uint32_t l = l0; l < l1; ++l) {
+        depth += diff[l];
+        loc_out[l].slot_off = (uint32_t)so;
+        loc_out[l].n = (uint32_t)depth;
+        so += (depth + 3) / 4 * 4;
+    }
+    atomicMax(&deepest, dmax);
+    __syncthreads();
+    if (t == 0) { summary[1] = deepest; summary[2] = (uint32_t)s_total; }
+}
+
+// first index j in [lo, hi) with pred(j), pred monotone (false ... false true ... true); hi when there is none.  64 probes a step.
+template <typename P>
+__device__ __forceinline__ uint32_t sel_search(uint32_t lo, uint32_t hi, P pred) {
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+    while (hi - lo > WAVE) {
+        // probes s_k = lo + k * step (a probe at or beyond hi counts as true); the answer lies behind the last false probe and at or
+        // before the first true one
+        const uint32_t step = (hi - lo + WAVE - 1) / WAVE, s = lo + lane * step;
+        const unsigned long long m = __ballot(s >= hi || pred(s));
+        if (m == 0ull) { lo += (WAVE - 1) * step + 1; continue; }
+        const uint32_t f = (uint32_t)__ffsll((long long)m) - 1u;
+        if (f == 0) return lo;
+        const uint32_t sf = lo + f * step;
+        lo += (f - 1) * step + 1;
+        hi = min(hi, sf);
+    }
+    const uint32_t s = lo + lane;
+    const unsigned long long m = __ballot(s < hi && pred(s));
+    return m ? lo + (uint32_t)__ffsll((long long)m) - 1u : hi;
+}
+
+// a wavefront per locus: w0' = first kept alignment whose end passes p (the block by the running maximum of the blocks' ends - a
+// monotone predicate - then the first such end within that block's kept range); w1' = max(w0', first kept alignment with pos > p)
+__global__ __launch_bounds__(SEL_BLOCK) void k_sel_windows(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ blk_off,
+                                                           const int32_t* __restrict__ blk_runmax, uint32_t n_blk, int32_t start0,
+                                                           uint32_t n_loci, smc_dev_locus* __restrict__ loc_out) {
+    const uint32_t l = blockIdx.x * (SEL_BLOCK / WAVE) + threadIdx.x / WAVE;
+    if (l >= n_loci) return;
+    const int32_t p = start0 + (int32_t)l;
+    const uint32_t kept = blk_off[n_blk];
+    const uint32_t b = sel_search(0u, n_blk, [&](uint32_t j) { return blk_runmax[j] > p; });
+    uint32_t w0 = kept;
+    if (b < n_blk) {
+        // (ends are not sorted: the block's kept range is scanned in order, 64 at a time; its first end beyond p is the answer - every
+        // kept alignment of the blocks before it ends at or before p)
+        const uint32_t lane = threadIdx.x & (WAVE - 1), j1 = blk_off[b + 1];
+        for (uint32_t j0 = blk_off[b]; j0 < j1; j0 += WAVE) {
+            const unsigned long long m = __ballot(j0 + lane < j1 && out[j0 + lane].end > p);
+            if (m) { w0 = j0 + (uint32_t)__ffsll((long long)m) - 1u; break; }
+        }
+    }
+    const uint32_t w1 = sel_search(w0, kept, [&](uint32_t j) { return out[j].pos > p; });
+    if ((threadIdx.x & (WAVE - 1)) == 0) { loc_out[l].w0 = w0; loc_out[l].w1 = w1; }
+}

@@ -25,6 +25,7 @@
 //                        exact two-sided by chunked hypergeometric sums with a log-factorial table.
 //   k_pack_rows.inc      432-byte rows -> 168-byte wire rows for the multi-GPU gather.
 //   k_pack_words.inc     raw-field planes (meta, frag) -> read words, for batches a host builder made.
+//   k_select_aln.inc     the alignments of a run's kept barcodes (ds.mt.py's drop, in HBM) and the decoder's descriptors over them.
 //
 // Data layout (include/smcounter_hip.h): ONE uint32 per pileup read (allele, quality, fragment start, read
 // class - what is left of the 16 B of raw fields per read once the plane builder has digested them) and umi_start; a 32-byte
@@ -61,5 +62,6 @@
 #include "k_pack_rows.inc"     // kernel 3: rows -> 168-byte wire rows for the multi-GPU gather
 #include "k_pack_words.inc"    // kernel 4: raw-field planes -> one word per read (smc_pack_words)
 #include "k_philox_marks.inc" // the non-parity down-sampling of loci over the barcode cap, Philox4x32-10 keyed by position
+#include "k_select_aln.inc"    // in-run molecule down-sampling: the kept barcodes' alignments and their windows / depths
 #include "k_plan.inc"          // launch plan of a batch whose descriptors are in HBM (classify + fill)
 #include "host_abi.inc"        // the C ABI of include/smcounter_hip.h

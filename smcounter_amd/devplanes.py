@@ -148,8 +148,11 @@ READS_PER_BYTE = 6        # pileup reads a batch is sized for per compressed byt
 
 def iter_resident_batches(path: str, fasta, loci: Sequence[Tuple[str, str]], params, eng, max_reads: int = 128_000_000,
                           nthreads: int = 0, force_host: bool = False, all_planes: bool = True, sampler: str = "reference",
-                          sampler_seed: int = 0):
+                          sampler_seed: int = 0, ds_rules: Sequence[DsRule] = None):
     """BAM -> `ResidentBatch` chunks: same loci per chunk as bamio.iter_device_batches_native, planes built on the GPU.
+    `ds_rules` (--dsMT): every run is decoded and uploaded once and built K + 1 times - at full depth and, through
+    smc_select_alignments, for the kept barcodes of every rule (called with that rule's params); each item is then
+    (first, [full-depth batch, batch of rule 1, ...]), all of the same loci.  Every run must be one the device builder takes.
     `all_planes=False`: only what the locus kernels read - the read words and umi_start - is built and kept (a fifth of the
     device memory of a batch, a quarter of the builder's stores); the four raw-field planes (for checks) are then None.
     (Round 5 built and measured decoding run i + 1 on a helper thread - a second decoder handle, the streaming cursor handed
@@ -230,6 +233,8 @@ def iter_resident_batches(path: str, fasta, loci: Sequence[Tuple[str, str]], par
             words.word_bits = bits
             narrow = False
             uaux = [DevBuf(eng, 4 * (cap + 8192)) for _ in range(3)]      # umi_start, u_gid, u_finc
+            # (--dsMT: the same arrays for every rule - a rule's run holds at most the full run's reads)
+            ds = [_DsBatch(eng, cap, bits, all_planes) for _ in (ds_rules or ())]
             LC, chroms, poss, refs, tables = [], [], [], [], []
             total = slots = n_loc = 0
             n_dev = n_host = 0
@@ -239,16 +244,26 @@ def iter_resident_batches(path: str, fasta, loci: Sequence[Tuple[str, str]], par
                 run_ref = fasta.fetch(chrom, lo, hi).upper()
                 umi_base = slots + n_loc
                 done = None
+                if ds_rules and force_host:
+                    raise bamio.BamError(_ds_refused(chrom, lo, hi, "the planes are built on the host"))
                 if not force_host:
                     T = _TIMES if os.environ.get("SMC_DEVPLANES_TIMING") else None
                     t0 = time.perf_counter()
                     A = bam.alignments_run(chrom, lo, hi, key[3], params, nthreads, host_array=eng.pinned)
                     if T is not None:
                         T["decode"] += time.perf_counter() - t0
+                    up = upload_run(eng, A, run_ref) if ds_rules and A["nl"] else None
                     done = build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, [words] + planes, uaux, slots, umi_base, cap, max_depth,
                                      bam.allele_key, bam.barcode_name, sampler=sampler, sampler_seed=sampler_seed,
-                                     barcode_idents=bam.barcode_idents)
-                    if done == NARROW:
+                                     barcode_idents=bam.barcode_idents, uploaded=up)
+                    if ds_rules and done is None:
+                        raise bamio.BamError(_ds_refused(chrom, lo, hi, "the device builder does not take it"))
+                    if ds_rules and done != NARROW:
+                        narrow = not _ds_build_run(ds_rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_depth, bam, sampler,
+                                                   sampler_seed, n_loc)
+                    if up is not None:
+                        up.free()
+                    if done == NARROW or narrow:
                         narrow = True
                         break
                 if done is None:
@@ -293,25 +308,107 @@ def iter_resident_batches(path: str, fasta, loci: Sequence[Tuple[str, str]], par
             if narrow:
                 for b in [words] + uaux + [p for p in planes if p is not None]:
                     b.free()
+                for d in ds:
+                    d.free()
                 eng.word_bits = 32
                 eng.drop_spare_tuned()           # (the block chosen for the 16-bit words is of a size nothing asks for again: back to the runtime)
                 i = first
                 continue
             lc_all = LC[0] if len(LC) == 1 else np.concatenate(LC)
             uaux[1].free(); uaux[2].free()
-            yield first, ResidentBatch(planes=planes + [uaux[0]], words=words, n_slots=slots, n_ustart=slots + n_loc + 1,
-                                       loci=lc_all, chrom=chroms, pos=poss[0] if len(poss) == 1 else np.concatenate(poss) if poss else np.zeros(0, np.int64),
-                                       ref=refs, alleles=tables,
-                                       n_device_runs=n_dev, n_host_runs=n_host)
+            rb = ResidentBatch(planes=planes + [uaux[0]], words=words, n_slots=slots, n_ustart=slots + n_loc + 1,
+                               loci=lc_all, chrom=chroms, pos=poss[0] if len(poss) == 1 else np.concatenate(poss) if poss else np.zeros(0, np.int64),
+                               ref=refs, alleles=tables,
+                               n_device_runs=n_dev, n_host_runs=n_host)
+            if ds_rules is None:
+                yield first, rb
+            else:
+                yield first, [rb] + [d.batch(rb) for d in ds]
     finally:
         bam.close()
 
 
+class _DsBatch(object):
+    """The device arrays and host parts of one --dsMT rule's batch (iter_resident_batches)."""
+
+    def __init__(self, eng, cap, bits, all_planes):
+        from .engine import DevBuf
+        self.planes = [DevBuf(eng, 4 * cap) if all_planes else None for k in range(4)]
+        self.words = DevBuf(eng, (bits // 8) * cap, walk_output=True)
+        self.words.word_bits = bits
+        self.uaux = [DevBuf(eng, 4 * (cap + 8192)) for _ in range(3)]
+        self.LC, self.tables, self.slots = [], [], 0
+
+    def free(self):
+        for b in [self.words] + self.uaux + [p for p in self.planes if p is not None]:
+            b.free()
+
+    def batch(self, full) -> ResidentBatch:
+        self.uaux[1].free(); self.uaux[2].free()
+        lc = self.LC[0] if len(self.LC) == 1 else np.concatenate(self.LC)
+        return ResidentBatch(planes=self.planes + [self.uaux[0]], words=self.words, n_slots=self.slots, n_ustart=self.slots + len(lc) + 1,
+                             loci=lc, chrom=full.chrom, pos=full.pos, ref=full.ref, alleles=self.tables, n_device_runs=full.n_device_runs)
+
+
+def _ds_refused(chrom, lo, hi, why):
+    return "--dsMT needs the device builder: the run %s:%d-%d cannot go through it (%s)" % (chrom, lo + 1, hi, why)
+
+
+def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_depth, bam, sampler, sampler_seed, n_loc):
+    """The rules' builds of one decoded run (`up`: its arrays in HBM) behind the batch's first `n_loc` loci: select, build into each
+    rule's batch.  False: a build has no room in 16-bit read words (the batch is built again with 32-bit ones)."""
+    L = eng.L
+    nl = A["nl"]
+    res = []
+    if nl:
+        idents = bam.barcode_idents(A["n_bc"])
+        names = None
+    for rule, d in zip(rules, ds):
+        if not nl:
+            res.append((0, 0, np.zeros(0, LOCUS_DTYPE), []))
+            continue
+        if rule.kept is None:
+            sel, counts, d_orig = select_run(eng, up, A, lo, idents=idents, frac=rule.frac, seed=rule.seed)
+        else:
+            if rule.kept_idents is not None:
+                mask = np.isin(idents, rule.kept_idents)
+            else:
+                if names is None:
+                    names = [bam.barcode_name(g) for g in range(int(A["n_bc"]))]
+                mask = np.array([t in rule.kept for t in names], bool)
+            sel, counts, d_orig = select_run(eng, up, A, lo, mask=mask)
+        orig = []
+
+        def allele_key(ai, qpos, indel, d_orig=d_orig, orig=orig, kept=sel.n_aln):
+            # (the builder's alignment index counts the KEPT alignments: the decoder's records are those of the full run)
+            if not orig:
+                orig.append(d_orig.download(np.uint32, kept))
+            return bam.allele_key(int(orig[0][int(ai)]), qpos, indel)
+        w = d.words
+        done = build_run(counts, L, eng, abi.c_params(rule.params), rule.params, chrom, lo, fasta, run_ref, [w] + d.planes, d.uaux,
+                         d.slots, d.slots + n_loc, cap, max_depth, allele_key, bam.barcode_name, sampler=sampler, sampler_seed=sampler_seed,
+                         barcode_idents=bam.barcode_idents, uploaded=sel)
+        sel.free(shared=False)
+        d_orig.free()
+        if done is None:
+            raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "fraction %g: the device builder does not take it" % rule.frac))
+        if done == NARROW:
+            return False
+        res.append(done)
+    for d, (nl_k, ns_k, lc, tb) in zip(ds, res):
+        d.LC.append(lc)
+        d.tables += tb
+        d.slots += ns_k
+    return True
+
+
 def build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, planes, uaux, slot_base, umi_base, cap, max_depth,
-              allele_key, barcode_name, stream_sync=True, sampler: str = "reference", sampler_seed: int = 0, barcode_idents=None):
+              allele_key, barcode_name, stream_sync=True, sampler: str = "reference", sampler_seed: int = 0, barcode_idents=None,
+              uploaded=None):
     """smc_build_planes over one run's alignments `A` (bamio.NativeBam.alignments_run or synth.generate_alignments) into the
     batch's device arrays (`planes`: [words, meta, umi, frag, dist], any of them None).  `allele_key(ai, qpos, indel)` / `barcode_name(gid)` give the texts the host needs (indel allele
-    keys, barcode names for the reference's down-sampling)."""
+    keys, barcode names for the reference's down-sampling).  `uploaded` (RunOnDevice): the run's arrays are in HBM already (A then
+    holds only the counts and "deepest"); they stay the caller's."""
     import time
     from .engine import DevBuf
     T = _TIMES if os.environ.get("SMC_DEVPLANES_TIMING") else None
@@ -319,28 +416,32 @@ def build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, planes, uaux, sl
     nl, ns = A["nl"], A["n_slots"]
     if nl == 0:
         return 0, 0, np.zeros(0, LOCUS_DTYPE), []
-    deepest = int(A["loc"]["n"].max()) if len(A["loc"]) else 0
+    deepest = A["deepest"] if "deepest" in A else int(A["loc"]["n"].max()) if len(A["loc"]) else 0
     # (status bit 1 - an alignment flagged neither READ1 nor READ2 - no longer sends the run to the host builder: the walk's
     # exact path takes the previous pileup read's pairOrder, smCounter.py:359-362)
     if (A["status"] & ~1) != 0 or deepest > max_depth or slot_base + ns > cap or \
             umi_base + ns + nl + 1 > cap + 8192:
         return None
-    if (A["status"] & 1) and len(A["aln"]):
+    if (A["status"] & 1) and A["aln"] is not None and len(A["aln"]):
         # unflagged alignments: the walk looks back for the previous flagged pileup read of every such (read, locus) - fine for a
         # sprinkle of them, quadratic for single-end data, and a run that BEGINS with one ends in the host builder's error anyway
         unfl = (A["aln"]["oflag"] & 3) == 0
         if bool(unfl[0]) or float(unfl.mean()) > 0.25:
             return None
-    up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
-    d_aln, d_cig, d_bq, d_loc = up(A["aln"]), up(A["cig"]), up(A["bq"]), up(A["loc"])
-    d_ref = up(np.frombuffer(run_ref[:nl].encode().ljust(nl, b"\0"), np.uint8).copy())
+    if uploaded is None:
+        own = upload_run(eng, A, run_ref)
+        d_aln, d_cig, d_bq, d_loc, d_ref = own.aln, own.cig, own.bq, own.loc, own.ref
+        loc_host, n_aln = own.loc_host, own.n_aln
+    else:
+        own = None
+        d_aln, d_cig, d_bq, d_loc, d_ref = uploaded.aln, uploaded.cig, uploaded.bq, uploaded.loc, uploaded.ref
+        loc_host, n_aln = uploaded.loc_host, uploaded.n_aln
     d_loci = DevBuf(eng, nl * LOCUS_DTYPE.itemsize)
     xcap = 4 * nl + 4096
     d_x = DevBuf(eng, 20 * xcap)
     d_cnt = DevBuf(eng, 8)
-    loc_host = np.ascontiguousarray(A["loc"])          # (the windows size the sort and the launch grids: read on the host)
     bi = abi.SmcBuildIn(d_aln.data_ptr(), d_cig.data_ptr(), d_bq.data_ptr(), d_loc.data_ptr(), d_ref.data_ptr(),
-                        lo, nl, A["n_bc"], A["n_pair"], deepest, len(A["aln"]), loc_host.ctypes.data)
+                        lo, nl, A["n_bc"], A["n_pair"], deepest, n_aln, loc_host.ctypes.data if loc_host is not None else None)
     pp = [t.data_ptr() if t is not None else None for t in planes]     # [words, meta, umi, frag, dist]
     w16 = getattr(planes[0], "word_bits", 32) == 16
     if w16:                                                            # (16-bit read words: nothing but the words is written)
@@ -381,7 +482,9 @@ def build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, planes, uaux, sl
                                       ctypes.c_uint64(int(sampler_seed) & 0xFFFFFFFFFFFFFFFF), d_st.data_ptr(), ctypes.c_void_p(0)), "smc_philox_marks")
         lc = d_loci.download(LOCUS_DTYPE, nl)
         d_pos.free(); d_st.free(); d_id.free()
-    for b in (d_aln, d_cig, d_bq, d_loc, d_ref, d_loci, d_cnt):
+    if own is not None:
+        own.free()
+    for b in (d_loci, d_cnt):
         b.free()                              # (back to the engine's spare list right away, not whenever the collector gets to them)
     # allele tables: the six fixed keys + what the kernel met, in the order it numbered them
     tables = [_BASE_TABLE] * nl                 # (shared, never written: a locus that met more alleles gets its own list)
@@ -421,6 +524,136 @@ def build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, planes, uaux, sl
             uaux[0].upload(us, 4 * o)
             lc["flags"][l] |= LF_SAMPLED
     return nl, ns, lc, tables
+
+
+@dataclasses.dataclass
+class RunOnDevice:
+    """A run's alignment arrays in HBM (what smc_build_planes reads): uploaded once, built from as often as the caller likes."""
+    aln: object
+    cig: object
+    bq: object
+    loc: object
+    ref: object
+    n_aln: int
+    loc_host: object = None     # loc[] in host memory (sizes the builder's launches), or None: the library copies it back
+
+    def free(self, shared: bool = True):
+        for b in ((self.aln, self.cig, self.bq, self.loc, self.ref) if shared else (self.aln, self.loc)):
+            b.free()
+
+
+def upload_run(eng, A, run_ref: str) -> RunOnDevice:
+    from .engine import DevBuf
+    nl = A["nl"]
+    up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
+    d_ref = up(np.frombuffer(run_ref[:nl].encode().ljust(nl, b"\0"), np.uint8).copy())
+    # (the windows size the sort and the launch grids: read on the host)
+    return RunOnDevice(up(A["aln"]), up(A["cig"]), up(A["bq"]), up(A["loc"]), d_ref, len(A["aln"]), np.ascontiguousarray(A["loc"]))
+
+
+# ---- in-run molecule down-sampling (--dsMT): ds.mt.py's drop of whole barcodes, done on the run's alignments in HBM
+DS_DOMAIN = 0x64734D54         # counter word 2 of the philox draw (k_select_aln.inc: SEL_DOMAIN)
+
+
+@dataclasses.dataclass
+class DsRule:
+    """One fraction of --dsMT: which barcodes stay, and the parameters that fraction is called with (its mtDepth: its cap, its
+    threshold).  `kept`: the reference's kept set (barcode texts, tools.ds_mt semantics over the whole file); None: the device's
+    philox rule with `seed`."""
+    frac: float
+    params: object
+    kept: object = None
+    seed: int = 1234567
+    kept_idents: object = None  # (sorted FNV-1a idents of `kept` when no two barcodes of the file share one: a run's mask without texts)
+
+
+def reference_rules(path: str, fracs, params_list, seed: int):
+    """DsRules of the reference's sampler: every placed barcode of the file in first-appearance order, py2 dict order, one
+    random() each from Python 2's generator seeded with `seed`, kept when r <= f (ds.mt.py:23-72; tools.ds_mt.select_barcodes).
+    Computed once per file."""
+    from .py2compat import Py2Random, py2_dict_order
+    order = bamio.placed_barcodes(path)
+    py2 = py2_dict_order(order)
+    idents = fnv64_array(order)
+    unique = len(np.unique(idents)) == len(order)
+    rules = []
+    for f, P in zip(fracs, params_list):
+        rng = Py2Random(int(seed))
+        kept = {bc for bc in py2 if rng.random() <= f}
+        ki = np.sort(fnv64_array(sorted(kept))) if unique else None
+        rules.append(DsRule(float(f), P, kept=kept, seed=int(seed), kept_idents=ki))
+    return rules
+
+
+def fnv64_array(texts) -> np.ndarray:
+    """FNV-1a (64 bits) of every text, vectorised: what smc_bam_barcode_idents computes for a run's barcodes."""
+    b = [t.encode() for t in texts]
+    n = len(b)
+    x = np.full(n, 1469598103934665603, np.uint64)
+    if not n:
+        return x
+    lens = np.array([len(t) for t in b], np.int64)
+    m = np.zeros((n, int(lens.max()) if n else 0), np.uint8)
+    for i, t in enumerate(b):
+        m[i, :len(t)] = np.frombuffer(t, np.uint8)
+    prime = np.uint64(1099511628211)
+    with np.errstate(over="ignore"):
+        for k in range(m.shape[1]):
+            live = lens > k
+            x[live] = (x[live] ^ m[live, k].astype(np.uint64)) * prime
+    return x
+
+
+def philox_keep_host(L, idents, frac: float, seed: int) -> np.ndarray:
+    """The philox rule restated on the host (smc_philox4x32_10_host): which of these barcode identities stay at fraction `frac`."""
+    if frac >= 1.0:
+        return np.ones(len(idents), bool)
+    thr = int(np.floor(frac * 4294967296.0))
+    key = (ctypes.c_uint32 * 2)(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    out = (ctypes.c_uint32 * 4)()
+    keep = np.zeros(len(idents), bool)
+    for g, v in enumerate(np.asarray(idents, np.uint64).tolist()):
+        ctr = (ctypes.c_uint32 * 4)(v & 0xFFFFFFFF, v >> 32, DS_DOMAIN, 0)
+        L.smc_philox4x32_10_host(ctr, key, out)
+        keep[g] = out[0] < thr
+    return keep
+
+
+def select_run(eng, up: RunOnDevice, A, lo: int, mask=None, idents=None, frac: float = 1.0, seed: int = 0):
+    """smc_select_alignments: the run `up` (A: its counts) reduced to the kept barcodes' alignments -> (RunOnDevice of the kept ones,
+    sharing the pools and the reference; counts dict for build_run; device buffer of orig_index).  `mask`: bool per run-wide barcode
+    id (the host's set); else `idents` (uint64 per id) and the philox rule at `frac` / `seed`."""
+    from .engine import DevBuf
+    L = eng.L
+    nl, n = A["nl"], up.n_aln
+    n_ids = int(A["n_bc"])
+    d_out = DevBuf(eng, 36 * max(1, n) + 256)
+    d_orig = DevBuf(eng, 4 * max(1, n) + 256)
+    d_loc = DevBuf(eng, 16 * max(1, nl) + 256)
+    d_sum = DevBuf(eng, 256)
+    d_rule = None
+    if mask is not None:
+        words = np.packbits(np.asarray(mask, bool)[:n_ids], bitorder="little")
+        words = np.concatenate([words, np.zeros((-len(words)) % 4 + 4, np.uint8)]).view(np.uint32)
+        d_rule = DevBuf(eng, words.nbytes + 256).upload(words)
+        mptr, iptr = d_rule.data_ptr(), None
+        n_ids = min(n_ids, len(mask))
+    else:
+        idents = np.ascontiguousarray(idents, np.uint64)[:n_ids]
+        d_rule = DevBuf(eng, 8 * max(1, len(idents)) + 256).upload(idents if len(idents) else np.zeros(1, np.uint64))
+        mptr, iptr = None, d_rule.data_ptr()
+        n_ids = len(idents)
+    _lib.check(L.smc_select_alignments(eng.ctx, up.aln.data_ptr(), n, up.loc.data_ptr(), nl, int(lo), mptr, iptr, n_ids,
+                                       ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), float(frac), d_out.data_ptr(), d_orig.data_ptr(),
+                                       d_loc.data_ptr(), d_sum.data_ptr(), ctypes.c_void_p(0)), "smc_select_alignments")
+    kept, deepest, slots = (int(v) for v in d_sum.download(np.uint32, 3))
+    d_rule.free()
+    sel = RunOnDevice(d_out, up.cig, up.bq, d_loc, up.ref, kept, None)
+    counts = dict(nl=nl, n_slots=slots, n_bc=A["n_bc"], n_pair=A["n_pair"], status=A["status"], deepest=deepest, aln=None)
+    if A["status"] & 1:
+        # (alignments flagged neither READ1 nor READ2: the same test as build_run's on the full run, on the kept ones)
+        counts["aln"] = A["aln"][d_orig.download(np.uint32, kept)] if kept else A["aln"][:0]
+    return sel, counts, d_orig
 
 
 def _fnv64(text: str) -> int:

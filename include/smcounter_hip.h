@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 9
+#define SMC_ABI_VERSION 10
 #define SMC_MAX_ALLELES 64 /* allele ids per locus; ids 0-5 are A,T,G,C,N,'DEL' */
 
 /* error codes */
@@ -398,6 +398,23 @@ void smc_philox4x32_10_host(const uint32_t ctr[4], const uint32_t key[2], uint32
 int smc_select_alignments(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0,
                           const uint32_t* d_keep_mask, const uint64_t* d_ident, int64_t n_ids, uint64_t seed, double frac,
                           smc_dev_aln* d_aln_out, uint32_t* d_orig_index, smc_dev_locus* d_loc_out, uint32_t* d_summary, void* stream);
+/* (ABI 10) The same with the level of the keep rule's key.  SMC_SEL_KEY_BARCODE: the id g is bc_gid (smc_select_alignments exactly;
+ * n_bc / n_pair are not read).  SMC_SEL_KEY_READ: g is pair_gid - the read-level rule of ds.reads.withinMT.py:37-82, which keeps whole
+ * read names (every alignment of a kept name, none of the others); d_keep_mask is then a bit per run-wide read-name id, d_ident (the
+ * philox rule) an identity per read-name id, and n_ids counts read-name ids.  The caller makes sure a read-name id stands for one
+ * full query name of the file (smc_bam_pair_idents reports the ids that do not: pair_gid drops the name's last field).  A read name
+ * is all in or all out, so the kept alignments keep the file order and the windows / depths / slots are those above.  The ids are
+ * not: dropping a barcode's first reads can move its first appearance, and the plane builder's rows depend on the ids' order.  So at
+ * the read level the kept alignments' bc_gid and pair_gid are renumbered densely by first kept appearance (ids < n_bc / n_pair, the
+ * run's counts; the caller may keep passing those counts on to the builder) - the decoder's numbering of the down-sampled BAM.
+ * The key is read from the record the kernels load anyway; the renumbering is five launches more over the kept records and
+ * 8 bytes of scratch per id. */
+#define SMC_SEL_KEY_BARCODE 0
+#define SMC_SEL_KEY_READ 1
+int smc_select_alignments_keyed(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0,
+                                int32_t key, int64_t n_bc, int64_t n_pair, const uint32_t* d_keep_mask, const uint64_t* d_ident, int64_t n_ids,
+                                uint64_t seed, double frac, smc_dev_aln* d_aln_out, uint32_t* d_orig_index, smc_dev_locus* d_loc_out,
+                                uint32_t* d_summary, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

@@ -76,6 +76,13 @@ int smc_bam_allele_key(void* h, int64_t aln_index, int32_t qpos, int32_t indel, 
 const char* smc_bam_barcode_name(void* h, int32_t gid);
 /* FNV-1a (64 bits) of the text of every run-wide barcode id of the last smc_bam_alignments: the identities smc_philox_marks keys on. */
 int64_t smc_bam_barcode_idents(void* h, uint64_t* out, int64_t cap);
+/* FNV-1a (64 bits) of the FULL query name of every run-wide read-name id (pair_gid) of the last smc_bam_alignments (its first
+ * record's), and *shared = 1 when some id stands for two different names (pair_gid is keyed on the name without its last field,
+ * smCounter.py:319-322): what the read-level down-sampling (--dsRpb, ds.reads.withinMT.py) keys on.  Computed on the first call after
+ * a run, never while decoding.  -> the number of ids */
+int64_t smc_bam_pair_idents(void* h, uint64_t* out, int64_t cap, int32_t* shared);
+/* full query name of read-name id `gid` of the last smc_bam_alignments ("" out of range); valid until the next call */
+const char* smc_bam_pair_name(void* h, int32_t gid);
 
 /* ---------------------------------------------------------------- libsmc_rowfmt.so */
 

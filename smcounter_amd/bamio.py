@@ -381,6 +381,29 @@ def placed_barcodes(path: str) -> List[str]:
     return [b.decode() for b in seen]
 
 
+def placed_qnames(path: str) -> List[str]:
+    """The query name of every record placed on a reference (tid >= 0), in file order: what ds.reads.withinMT.py's
+    `for read in samfile.fetch()` walks (:37-44).  The whole file is inflated at once (C), the records are walked without being parsed."""
+    import gzip
+    with open(path, "rb") as fh:
+        data = gzip.decompress(fh.read())
+    if data[:4] != b"BAM\1":
+        raise BamError("%s: not a BAM file" % path)
+    off = 8 + struct.unpack_from("<i", data, 4)[0]
+    n_ref = struct.unpack_from("<i", data, off)[0]
+    off += 4
+    for _ in range(n_ref):
+        off += 8 + struct.unpack_from("<i", data, off)[0]
+    out = []
+    unpack, end = struct.unpack_from, len(data)
+    while off + 4 <= end:
+        bs, tid = unpack("<ii", data, off)
+        if tid >= 0:
+            out.append(data[off + 36:off + 35 + data[off + 12]].decode())
+        off += 4 + bs
+    return out
+
+
 def write_raw(path: str, header: bytes, raw_records: Iterable[bytes], block: int = 60000) -> None:
     """BGZF-compress a header and raw BAM records (as `iter_raw_records` yields them) into a BAM file."""
     with open(path, "wb") as fh:
@@ -592,6 +615,10 @@ def _native_lib():
         lib.smc_bam_barcode_name.restype = C.c_char_p
         lib.smc_bam_barcode_idents.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         lib.smc_bam_barcode_idents.restype = C.c_int64
+        lib.smc_bam_pair_idents.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+        lib.smc_bam_pair_idents.restype = C.c_int64
+        lib.smc_bam_pair_name.argtypes = [C.c_void_p, C.c_int32]
+        lib.smc_bam_pair_name.restype = C.c_char_p
         lib.smc_bam_span_bytes.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64]
         lib.smc_bam_span_bytes.restype = C.c_int64
         _NATIVE = lib
@@ -708,6 +735,19 @@ class NativeBam(object):
         out = np.zeros(max(1, int(n_bc)), np.uint64)
         n = self._lib.smc_bam_barcode_idents(self._h, out.ctypes.data, len(out))
         return out[:min(int(n), len(out))]
+
+    def pair_idents(self, n_pair: int):
+        """FNV-1a (64 bits) of the full query name of every read-name id of the last run (by run-wide pair id), and whether some id
+        covers two different names (the id drops the name's last field): -> (uint64 array, shared).  Computed on the first call."""
+        import ctypes as C
+        out = np.zeros(max(1, int(n_pair)), np.uint64)
+        shared = C.c_int32(0)
+        n = self._lib.smc_bam_pair_idents(self._h, out.ctypes.data, len(out), C.byref(shared))
+        return out[:min(int(n), len(out))], bool(shared.value)
+
+    def pair_name(self, gid: int) -> str:
+        """The full query name of read-name id `gid` of the last run (its first record's)."""
+        return self._lib.smc_bam_pair_name(self._h, int(gid)).decode()
 
     def planes_run(self, chrom: str, lo: int, hi: int, max_reads: int, params, refseq: str, nthreads: int, fasta,
                    arena=None, arena_off: int = 0):

@@ -72,6 +72,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dsSeed", type=int, default=1234567, help="seed of --dsMT (ds.mt.py --seed)")
     p.add_argument("--dsMtDepth", default=None, help="comma-separated --mtDepth of each --dsMT fraction; default "
                                                      "max(1, round(f x mtDepth)) (sets that fraction's maxMT default and its threshold)")
+    p.add_argument("--dsRpb", default=None, help="in-run read down-sampling within barcodes: comma-separated targets r > 0 of mean "
+                                                 "reads per barcode.  For each, the run is also called as if on the BAM that "
+                                                 "ds.reads.withinMT.py --rpb r --seed dsSeed writes (whole read names kept: a barcode's "
+                                                 "first always, every further one with the reference's probKeep), with --rpb r; written "
+                                                 "to <outPrefix>.dsRpb<r>.smCounter.{all,cut}.txt and .cut.vcf.  The kept names are the "
+                                                 "reference's exactly (one pass over the whole file, on the host); --dsSampler philox "
+                                                 "is not available here (a shape-independent rule for reads needs the whole file's "
+                                                 "first names and probKeep).  With --dsMT: each target and each fraction gets its own "
+                                                 "files from the same decode, no cross product.  Needs the device plane builder; one "
+                                                 "process only")
+    p.add_argument("--dsRpbMtDepth", default=None, help="comma-separated --mtDepth of each --dsRpb target; default --mtDepth")
     return p
 
 
@@ -98,6 +109,45 @@ def ds_fractions(args):
     else:
         depths = [max(1, int(py2_round(f * args.mtDepth))) for f in fr]
     return [(f, d, "%s.dsMT%g" % (args.outPrefix, f)) for f, d in zip(fr, depths)]
+
+
+def ds_rpb_targets(args):
+    """--dsRpb / --dsRpbMtDepth -> [(r, mtDepth of r, output prefix)]; [] without --dsRpb."""
+    text = getattr(args, "dsRpb", None)
+    if text in (None, ""):
+        return []
+    try:
+        rs = [float(x) for x in str(text).split(",") if x.strip()]
+    except ValueError:
+        raise SystemExit("--dsRpb: comma-separated reads-per-barcode targets > 0 expected, got %r" % text)
+    if not rs or any(not (r > 0.0 and r < float("inf")) for r in rs):
+        raise SystemExit("--dsRpb: every target must be a number > 0, got %r" % text)
+    dtext = getattr(args, "dsRpbMtDepth", None)
+    if dtext not in (None, ""):
+        try:
+            depths = [int(x) for x in str(dtext).split(",") if x.strip()]
+        except ValueError:
+            raise SystemExit("--dsRpbMtDepth: comma-separated integers expected, got %r" % dtext)
+        if len(depths) != len(rs):
+            raise SystemExit("--dsRpbMtDepth: %d depths for %d --dsRpb targets" % (len(depths), len(rs)))
+    else:
+        depths = [int(args.mtDepth)] * len(rs)
+    if getattr(args, "dsSampler", "reference") == "philox":
+        raise SystemExit("--dsRpb keeps the reference's read names only: --dsSampler philox is not available with it (a rule for "
+                         "reads that does not depend on how the file is cut into runs needs the whole file's first names and probKeep)")
+    return [(r, d, "%s.dsRpb%g" % (args.outPrefix, r)) for r, d in zip(rs, depths)]
+
+
+def ds_rpb_rules(args, params: VcParams, targets):
+    """The devplanes.DsRule of every --dsRpb target (the reference's read names: one pass over the whole file, here); a file without a
+    barcode of two or more reads ends the run with a message."""
+    import dataclasses
+    from . import devplanes
+    plist = [dataclasses.replace(params, mtDepth=d, rpb=r) for r, d, _ in targets]
+    try:
+        return devplanes.reference_read_rules(args.bamFile, [r for r, _, _ in targets], plist, int(args.dsSeed))
+    except ValueError as e:
+        raise SystemExit(str(e))
 
 
 def ds_rules(args, params: VcParams, fractions):
@@ -322,20 +372,35 @@ def _main(args) -> int:
     params = VcParams(minBQ=args.minBQ, minMQ=args.minMQ, mtDepth=args.mtDepth, rpb=args.rpb, hpLen=args.hpLen,
                       mismatchThr=args.mismatchThr, mtDrop=args.mtDrop, maxMT=args.maxMT, primerDist=args.primerDist)
     fractions = ds_fractions(args)
-    if fractions and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit("--dsMT runs in one process only (not under torch.distributed.run with more than one rank)")
+    targets = ds_rpb_targets(args)
+    flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets)) if on)
+    if flag and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("%s runs in one process only (not under torch.distributed.run with more than one rank)" % flag)
     host = [v for v, on in (("SMC_PLANES=host", os.environ.get("SMC_PLANES", "device") == "host"),
                             ("SMC_BAM_DECODER=python", os.environ.get("SMC_BAM_DECODER", "native") == "python")) if on]
-    if fractions and host:
+    if flag and host:
         first = bedops.expand_loci(args.bedTarget)[:1]
-        raise SystemExit("--dsMT needs the device builder: the run at %s would be built on the host (%s)" %
-                         ("%s:%s" % first[0] if first else "(no targets)", host[0]))
+        raise SystemExit("%s needs the device builder: the run at %s would be built on the host (%s)" %
+                         (flag, "%s:%s" % first[0] if first else "(no targets)", host[0]))
     early = None
     if int(os.environ.get("WORLD_SIZE", "1")) == 1 and os.environ.get("SMC_BAM_DECODER", "native") != "python":
         # a single process: the GPU runtime and the context come up (~ 0.1 s) in a helper thread while the target is expanded
         early = _EarlyEngine(args.device)
     loc_list = bedops.expand_loci(args.bedTarget)
-    args.ds_rules = ds_rules(args, params, fractions) if fractions else None
+    try:
+        rules = (ds_rules(args, params, fractions) if fractions else []) + (ds_rpb_rules(args, params, targets) if targets else [])
+    except SystemExit:
+        if early is not None:                  # (the engine the helper brings up stays with the process, as after a run)
+            try:
+                _ENGINES.setdefault(args.device, early.get())
+            except Exception:
+                pass
+        raise
+    for rule in rules:
+        if rule.level == "read":
+            print("--dsRpb %g: probKeep %.6g, %d of %d read names kept (seed %d, mtDepth %d)" %
+                  (rule.target, rule.prob_keep, len(rule.kept), rule.n_names, rule.seed, rule.params.mtDepth))
+    args.ds_rules = rules or None
     # One process per GPU when launched through torch.distributed.run: rank r calls a contiguous range of the
     # ordered locus list (loci share nothing, smCounter.py:683-685) on GPU LOCAL_RANK, rank 0 gathers the rows
     # in submission order and writes the files.
@@ -406,11 +471,11 @@ def _main(args) -> int:
         args.bedTandemRepeats if args.bedTandemRepeats and os.path.exists(args.bedTandemRepeats) else None,
         args.bedRepeatMaskerSubset if args.bedRepeatMaskerSubset and os.path.exists(args.bedRepeatMaskerSubset) else None)
     pred = getattr(output, "pred", None)                  # (single process: the printer's int(PI) per row)
-    ds_outputs = getattr(output, "ds", None) or []        # (--dsMT: the rows of every fraction)
+    ds_outputs = getattr(output, "ds", None) or []        # (--dsMT / --dsRpb: the rows of every fraction, then of every target)
     output = postfilter.apply_repeat_filters(output, trf, rm, pred=pred)
     threshold = writers.pi_threshold(args.mtDepth, args.threshold)
     writers.write_outputs(args.outPrefix, output, threshold, pred=pred)
-    for (f, d, prefix), o in zip(fractions, ds_outputs):
+    for (f, d, prefix), o in zip(fractions + targets, ds_outputs):
         vc.raise_on_exception(o, loc_list)
         o_pred = getattr(o, "pred", None)
         o = postfilter.apply_repeat_filters(o, trf, rm, pred=o_pred)

@@ -817,10 +817,15 @@ int smc_philox_marks(smc_ctx* ctx, const smc_params* prm, smc_locus* d_loci, int
 // (no GPU needed) the generator itself, for known-answer tests of the binding
 void smc_philox4x32_10_host(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) { smc_philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], out); }
 
-int smc_select_alignments(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0,
-                          const uint32_t* d_keep_mask, const uint64_t* d_ident, int64_t n_ids, uint64_t seed, double frac,
-                          smc_dev_aln* d_aln_out, uint32_t* d_orig_index, smc_dev_locus* d_loc_out, uint32_t* d_summary, void* stream) {
+int smc_select_alignments_keyed(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0,
+                                int32_t key, int64_t n_bc, int64_t n_pair, const uint32_t* d_keep_mask, const uint64_t* d_ident, int64_t n_ids,
+                                uint64_t seed, double frac, smc_dev_aln* d_aln_out, uint32_t* d_orig_index, smc_dev_locus* d_loc_out,
+                                uint32_t* d_summary, void* stream) {
     if (!ctx) return fail(SMC_E_ARG, "smc_select_alignments: NULL context");
+    if (key != SMC_SEL_KEY_BARCODE && key != SMC_SEL_KEY_READ) return fail(SMC_E_ARG, "smc_select_alignments_keyed: unknown key level");
+    const bool renum = key == SMC_SEL_KEY_READ;          // (the read level renumbers the kept ids: n_bc / n_pair size its tables)
+    if (renum && (n_bc < 0 || n_pair < 0 || n_bc + n_pair >= (int64_t)0xFFFFFFFF))
+        return fail(SMC_E_ARG, "smc_select_alignments_keyed: bad id counts");
     if (n_aln < 0 || n_loci < 0 || n_ids < 0 || n_aln >= (int64_t)0xFFFFF000 || n_loci >= (int64_t)0x7FFFFFFF ||
         n_ids > (int64_t)0xFFFFFFFF || (!d_keep_mask && !d_ident && n_ids > 0) || !(frac >= 0.0))
         return fail(SMC_E_ARG, "smc_select_alignments: bad argument");
@@ -833,6 +838,8 @@ int smc_select_alignments(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln,
     size_t off = 0;
     auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_off = carve(4 * ((size_t)n_blk + 1)), o_max = carve(4 * ((size_t)n_blk + 1)), o_diff = carve(4 * ((size_t)nl + 1));
+    const size_t n_idw = renum ? (size_t)(n_bc + n_pair) : 0;
+    const size_t o_rcnt = carve(renum ? 8 * ((size_t)n_blk + 1) : 0), o_rsum = carve(renum ? 16 : 0), o_first = carve(4 * n_idw), o_map = carve(4 * n_idw);
     if (off > ctx->sel_bytes) {
         HIPCHK(hipStreamSynchronize(st));
         (void)hipFree(ctx->sel_scratch);
@@ -849,6 +856,7 @@ int smc_select_alignments(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln,
     SelRule R;
     R.mask = d_keep_mask; R.ident = (const unsigned long long*)d_ident; R.seed = (unsigned long long)seed; R.n_ids = (uint32_t)n_ids;
     R.thr = frac >= 1.0 ? (1ull << 32) : (unsigned long long)std::floor(frac * 4294967296.0);
+    R.by_read = key == SMC_SEL_KEY_READ ? 1u : 0u;
     if (n_blk) hipLaunchKernelGGL(k_sel_count, dim3(n_blk), dim3(SEL_BLOCK), 0, st, d_aln, (uint32_t)n_aln, R, blk_off);
     hipLaunchKernelGGL(k_sel_offsets, dim3(1), dim3(SEL_SCAN), 0, st, blk_off, n_blk, diff, nl + 1u, d_summary);
     if (n_blk) hipLaunchKernelGGL(k_sel_scatter, dim3(n_blk), dim3(SEL_BLOCK), 0, st, d_aln, (uint32_t)n_aln, R, (const uint32_t*)blk_off,
@@ -856,8 +864,32 @@ int smc_select_alignments(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln,
     hipLaunchKernelGGL(k_sel_loci, dim3(1), dim3(SEL_SCAN), 0, st, blk_max, n_blk, (const int32_t*)diff, nl, d_loc_out, d_summary);
     if (nl) hipLaunchKernelGGL(k_sel_windows, dim3((nl + SEL_BLOCK / WAVE - 1) / (SEL_BLOCK / WAVE)), dim3(SEL_BLOCK), 0, st, (const smc_dev_aln*)d_aln_out,
                                (const uint32_t*)blk_off, (const int32_t*)blk_max, n_blk, start0, nl, d_loc_out);
+    if (renum && n_blk) {
+        // the kept ids renumbered by first kept appearance (k_select_aln.inc): first kept index per id, per-block counts of the firsts,
+        // their exclusive scans (barcodes, read names), the new id of every first, the kept records' ids rewritten
+        SelIds I;
+        I.first = (uint32_t*)(sc + o_first); I.map = (uint32_t*)(sc + o_map); I.n_bc = (uint32_t)n_bc; I.n_pair = (uint32_t)n_pair;
+        uint32_t* rcnt = (uint32_t*)(sc + o_rcnt);
+        uint32_t* rsum = (uint32_t*)(sc + o_rsum);
+        if (n_idw) HIPCHK(hipMemsetAsync(I.first, 0xFF, 4 * n_idw, st));
+        hipLaunchKernelGGL(k_sel_first, dim3(n_blk), dim3(SEL_BLOCK), 0, st, (const smc_dev_aln*)d_aln_out, (const uint32_t*)d_summary, I);
+        hipLaunchKernelGGL(k_sel_rcount, dim3(n_blk), dim3(SEL_BLOCK), 0, st, (const smc_dev_aln*)d_aln_out, (const uint32_t*)d_summary, I, n_blk, rcnt);
+        hipLaunchKernelGGL(k_sel_offsets, dim3(1), dim3(SEL_SCAN), 0, st, rcnt, n_blk, (int32_t*)nullptr, 0u, rsum);
+        hipLaunchKernelGGL(k_sel_offsets, dim3(1), dim3(SEL_SCAN), 0, st, rcnt + n_blk + 1, n_blk, (int32_t*)nullptr, 0u, rsum + 1);
+        hipLaunchKernelGGL(k_sel_rank, dim3(n_blk), dim3(SEL_BLOCK), 0, st, (const smc_dev_aln*)d_aln_out, (const uint32_t*)d_summary, I, n_blk,
+                           (const uint32_t*)rcnt);
+        hipLaunchKernelGGL(k_sel_regid, dim3(n_blk), dim3(SEL_BLOCK), 0, st, d_aln_out, (const uint32_t*)d_summary, I);
+    }
     HIPCHK(hipGetLastError());
     return SMC_OK;
+}
+
+// (ABI 9) the barcode-level rule
+int smc_select_alignments(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0,
+                          const uint32_t* d_keep_mask, const uint64_t* d_ident, int64_t n_ids, uint64_t seed, double frac,
+                          smc_dev_aln* d_aln_out, uint32_t* d_orig_index, smc_dev_locus* d_loc_out, uint32_t* d_summary, void* stream) {
+    return smc_select_alignments_keyed(ctx, d_aln, n_aln, d_loc, n_loci, start0, SMC_SEL_KEY_BARCODE, 0, 0, d_keep_mask, d_ident, n_ids, seed, frac,
+                                       d_aln_out, d_orig_index, d_loc_out, d_summary, stream);
 }
 
 int smc_plan_set_timing(smc_plan* p, int slots) {

@@ -7,7 +7,13 @@
 // that BAM.  Here the run's alignments are already in HBM: the drop is done on them, and the descriptors are recomputed exactly as
 // smc_bam_alignments (csrc/smc_bam.cpp) would compute them for the down-sampled BAM - so the plane builder and everything after it
 // run unchanged on the result.  A barcode is all in or all out, so the kept alignments keep the file order, the ids keep their
-// order (with gaps: the builder only compares them), and the decoder's rules carry over:
+// order (with gaps: the builder only compares them), and the decoder's rules carry over.
+// (ABI 10) The key of the rule can also be the read: ds.reads.withinMT.py keeps whole read names (all alignments of a name or none),
+// by read-name id (pair_gid) - the host makes sure no id of the run covers two names.  A read name is all in or all out, so the
+// windows and depths below carry over.  The ids do not: a barcode whose first read was dropped can come out of first-appearance
+// order, and the builder's rows are not independent of the ids' numeric order (tests/test_gpu_ds_rpb.py puts a run's ids through a
+// random bijection: the rows of two fixtures change).  So the read-level rule renumbers the kept ids by first kept appearance, as
+// the decoder numbers the down-sampled BAM's (k_sel_first / k_sel_rcount / k_sel_offsets / k_sel_rank / k_sel_regid below):
 //   w0'  = first kept alignment with end > p       (= first index whose running maximum of end passes p: a monotone predicate)
 //   w1'  = max(w0', first kept alignment with pos > p)
 //   n'   = kept alignments with pos <= p < end     (a difference array over the run's positions, then a scan)
@@ -32,8 +38,11 @@ struct SelRule {
     const uint32_t* mask;              // non-null: bit g of the mask keeps barcode g (the host's set: the reference's semantics)
     const unsigned long long* ident;   // else: one 64-bit identity per barcode, kept iff Philox word 0 < thr
     unsigned long long seed, thr;      // thr = floor(f * 2^32); >= 2^32: everything
-    uint32_t n_ids;                    // ids at or beyond this are not kept (never met: the decoder numbers below n_bc)
+    uint32_t n_ids;                    // ids at or beyond this are not kept (never met: the decoder numbers below n_bc / n_pair)
+    uint32_t by_read;                  // 0: the key is the barcode id (bc_gid); 1: the read-name id (pair_gid)
 };
+
+__device__ __forceinline__ uint32_t sel_key(const SelRule& R, const smc_dev_aln& a) { return R.by_read ? a.pair_gid : a.bc_gid; }
 
 __device__ __forceinline__ bool sel_keep(const SelRule& R, uint32_t gid) {
     if (gid >= R.n_ids) return false;
@@ -53,7 +62,7 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_sel_count(const smc_dev_aln* __re
 #pragma unroll
     for (int r = 0; r < SEL_ROUNDS; ++r) {
         const uint32_t i = base + (uint32_t)r * SEL_BLOCK + threadIdx.x;
-        if (i < n_aln && sel_keep(R, aln[i].bc_gid)) ++mine;
+        if (i < n_aln && sel_keep(R, R.by_read ? aln[i].pair_gid : aln[i].bc_gid)) ++mine;
     }
     for (int o = WAVE / 2; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
     if ((threadIdx.x & (WAVE - 1)) == 0) wsum[threadIdx.x / WAVE] = mine;
@@ -118,7 +127,7 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_sel_scatter(const smc_dev_aln* __
         const uint32_t i = base + (uint32_t)r * SEL_BLOCK + t;
         smc_dev_aln a;
         bool keep = false;
-        if (i < n_aln) { a = aln[i]; keep = sel_keep(R, a.bc_gid); }
+        if (i < n_aln) { a = aln[i]; keep = sel_keep(R, sel_key(R, a)); }
         const unsigned long long m = __ballot(keep);
         const uint32_t lane = t & (WAVE - 1), rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
         if (lane == 0) wcnt[wv] = (uint32_t)__popcll(m);
@@ -230,4 +239,102 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_sel_windows(const smc_dev_aln* __
     }
     const uint32_t w1 = sel_search(w0, kept, [&](uint32_t j) { return out[j].pos > p; });
     if ((threadIdx.x & (WAVE - 1)) == 0) { loc_out[l].w0 = w0; loc_out[l].w1 = w1; }
+}
+
+// ---- (read level) the kept ids renumbered by first kept appearance: both bc_gid and pair_gid of d_aln_out, dense from 0 in the order
+// the kept alignments first meet them - the decoder's numbering of the down-sampled BAM.  Grids cover the n_aln input alignments
+// (an upper bound of the kept ones: their count is on the device); first[] / map[] hold one word per input id (n_bc + n_pair).
+struct SelIds {
+    uint32_t* first;          // [n_bc + n_pair]: the first kept index of every id (0xFFFFFFFF: not kept); pair ids behind the barcodes'
+    uint32_t* map;            // [n_bc + n_pair]: the new id of every kept id
+    uint32_t n_bc, n_pair;
+};
+
+__device__ __forceinline__ uint32_t sel_slot(const SelIds& I, const smc_dev_aln& a, int which) {   // -> index into first / map, or ~0
+    return which == 0 ? (a.bc_gid < I.n_bc ? a.bc_gid : 0xFFFFFFFFu) : (a.pair_gid < I.n_pair ? I.n_bc + a.pair_gid : 0xFFFFFFFFu);
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_sel_first(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, SelIds I) {
+    const uint32_t kept = summary[0], base = blockIdx.x * (uint32_t)SEL_ITEMS;
+    for (int r = 0; r < SEL_ROUNDS; ++r) {
+        const uint32_t k = base + (uint32_t)r * SEL_BLOCK + threadIdx.x;
+        if (k >= kept) break;
+        const smc_dev_aln a = out[k];
+        for (int w = 0; w < 2; ++w) {
+            const uint32_t s = sel_slot(I, a, w);
+            if (s != 0xFFFFFFFFu) atomicMin(&I.first[s], k);
+        }
+    }
+}
+
+// per block: the kept alignments that are the first of their barcode (cnt[b]) / of their read name (cnt[n_blk + 1 + b])
+__global__ __launch_bounds__(SEL_BLOCK) void k_sel_rcount(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, SelIds I,
+                                                          uint32_t n_blk, uint32_t* __restrict__ cnt) {
+    __shared__ uint32_t wsum[2][SEL_BLOCK / WAVE];
+    const uint32_t kept = summary[0], base = blockIdx.x * (uint32_t)SEL_ITEMS;
+    uint32_t mine[2] = {0u, 0u};
+    for (int r = 0; r < SEL_ROUNDS; ++r) {
+        const uint32_t k = base + (uint32_t)r * SEL_BLOCK + threadIdx.x;
+        if (k >= kept) break;
+        const smc_dev_aln a = out[k];
+        for (int w = 0; w < 2; ++w) {
+            const uint32_t s = sel_slot(I, a, w);
+            if (s != 0xFFFFFFFFu && I.first[s] == k) ++mine[w];
+        }
+    }
+    for (int w = 0; w < 2; ++w) {
+        for (int o = WAVE / 2; o > 0; o >>= 1) mine[w] += __shfl_xor(mine[w], o);
+        if ((threadIdx.x & (WAVE - 1)) == 0) wsum[w][threadIdx.x / WAVE] = mine[w];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        uint32_t t = 0;
+        for (int v = 0; v < SEL_BLOCK / WAVE; ++v) t += wsum[threadIdx.x][v];
+        cnt[threadIdx.x * (n_blk + 1) + blockIdx.x] = t;
+    }
+}
+
+// per block (block offsets: the exclusive scans of k_sel_rcount's counts): the first kept alignment of every id gives it its new id
+// (ballot ranks within a round, the rounds in order - as k_sel_scatter ranks the kept alignments)
+__global__ __launch_bounds__(SEL_BLOCK) void k_sel_rank(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, SelIds I,
+                                                        uint32_t n_blk, const uint32_t* __restrict__ off) {
+    __shared__ uint32_t wcnt[2][SEL_BLOCK / WAVE];
+    const uint32_t t = threadIdx.x, wv = t / WAVE, lane = t & (WAVE - 1), kept = summary[0], base = blockIdx.x * (uint32_t)SEL_ITEMS;
+    uint32_t dst[2] = {off[blockIdx.x], off[n_blk + 1 + blockIdx.x]};
+#pragma unroll 1
+    for (int r = 0; r < SEL_ROUNDS; ++r) {
+        const uint32_t k = base + (uint32_t)r * SEL_BLOCK + t;
+        uint32_t s[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+        bool head[2] = {false, false};
+        if (k < kept) {
+            const smc_dev_aln a = out[k];
+            for (int w = 0; w < 2; ++w) { s[w] = sel_slot(I, a, w); head[w] = s[w] != 0xFFFFFFFFu && I.first[s[w]] == k; }
+        }
+        uint32_t rank[2];
+        for (int w = 0; w < 2; ++w) {
+            const unsigned long long m = __ballot(head[w]);
+            rank[w] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (lane == 0) wcnt[w][wv] = (uint32_t)__popcll(m);
+        }
+        __syncthreads();
+        for (int w = 0; w < 2; ++w) {
+            uint32_t before = 0, all = 0;
+            for (uint32_t v = 0; v < SEL_BLOCK / WAVE; ++v) { before += v < wv ? wcnt[w][v] : 0u; all += wcnt[w][v]; }
+            if (head[w]) I.map[s[w]] = dst[w] + before + rank[w];
+            dst[w] += all;
+        }
+        __syncthreads();                                   // (wcnt is rewritten by the next round)
+    }
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_sel_regid(smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, SelIds I) {
+    const uint32_t kept = summary[0], base = blockIdx.x * (uint32_t)SEL_ITEMS;
+    for (int r = 0; r < SEL_ROUNDS; ++r) {
+        const uint32_t k = base + (uint32_t)r * SEL_BLOCK + threadIdx.x;
+        if (k >= kept) break;
+        const smc_dev_aln a = out[k];
+        const uint32_t sb = sel_slot(I, a, 0), sp = sel_slot(I, a, 1);
+        if (sb != 0xFFFFFFFFu) out[k].bc_gid = I.map[sb];
+        if (sp != 0xFFFFFFFFu) out[k].pair_gid = I.map[sp];
+    }
 }

@@ -237,6 +237,10 @@ struct Bam {
     RawVec<uint64_t> it_key;           // (interning tables of collect_reads: hash, first record, the records' slots - reused, their pages stay)
     RawVec<uint32_t> it_first, it_slot;
     std::vector<std::string> d_bc_names;
+    int32_t d_n_pair = 0;              // the run's read-name ids, and (filled by smc_bam_pair_idents, only when asked) each one's first record
+    std::vector<uint32_t> d_pair_rep;
+    int32_t d_pair_shared = 0;         // (with d_pair_rep) 1: some read-name id covers two different full query names
+    std::string d_pair_text;           // (smc_bam_pair_name's answer)
 
     bool load_block(uint64_t coff) {
         if (fseeko(fh, (off_t)coff, SEEK_SET) != 0) return false;
@@ -1453,7 +1457,7 @@ int64_t smc_bam_alignments(void* h, const char* chrom, int64_t start0, int64_t e
     Bam& b = *(Bam*)h;
     b.io_threads = nthreads;
     *n_loci_done = *n_slots = 0; *status = 0;
-    b.d_reads.clear(); b.d_bc_names.clear();
+    b.d_reads.clear(); b.d_bc_names.clear(); b.d_pair_rep.clear(); b.d_n_pair = 0; b.d_pair_shared = 0;
     int n_bc = 0, n_pair = 0;
     const auto t_a0 = std::chrono::steady_clock::now();
     { const int rc = collect_reads(b, chrom, start0, end0, b.d_reads, n_bc, n_pair, &b.d_bc_names); if (rc) return rc; }
@@ -1587,6 +1591,7 @@ int64_t smc_bam_alignments(void* h, const char* chrom, int64_t start0, int64_t e
         });
     }
     *n_loci_done = nl; *n_slots = slots; *n_bc_out = n_bc; *n_pair_out = n_pair; *status = st;
+    b.d_n_pair = n_pair;
     if (exp_env("SMC_BAM_TIMING")) {
         auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         fprintf(stderr, "smc_bam_alignments: %zu alignments, %lld loci, %lld reads: collect %.1f ms, depth + sizes %.1f ms, pack %.1f ms, windows %.1f ms\n",
@@ -1629,6 +1634,49 @@ int64_t smc_bam_barcode_idents(void* h, uint64_t* out, int64_t cap) {
         out[g] = x;
     }
     return n;
+}
+
+// The full query names behind the run-wide read-name ids of the last smc_bam_alignments (for the reference's read-level down-sampling,
+// ds.reads.withinMT.py:37-44, which keys on the whole name).  A read-name id is keyed on (barcode, read id) and the read id drops the
+// name's last field (smCounter.py:319-322): one id can stand for two different names.  Nothing of this is computed while decoding - the
+// first call after a run walks the run's records once (their names are still views into the inflated records).
+static void pair_reps(Bam& b) {
+    if (!b.d_pair_rep.empty() || b.d_n_pair <= 0) return;
+    const uint32_t NONE = 0xFFFFFFFFu;
+    b.d_pair_rep.assign((size_t)b.d_n_pair, NONE);
+    b.d_pair_shared = 0;
+    for (size_t i = 0; i < b.d_reads.size(); ++i) {
+        const Aln& a = b.d_reads[i];
+        if (a.pair_gid < 0 || a.pair_gid >= b.d_n_pair) continue;
+        uint32_t& r = b.d_pair_rep[(size_t)a.pair_gid];
+        if (r == NONE) r = (uint32_t)i;
+        else if (b.d_reads[r].qname != a.qname) b.d_pair_shared = 1;
+    }
+}
+
+// FNV-1a (64 bits) of the full query name of every run-wide read-name id (its first record's); *shared = 1 when some id covers two
+// different names (the identities then do not name the reads).  -> the number of ids
+int64_t smc_bam_pair_idents(void* h, uint64_t* out, int64_t cap, int32_t* shared) {
+    Bam& b = *(Bam*)h;
+    pair_reps(b);
+    const int64_t n = (int64_t)b.d_pair_rep.size();
+    for (int64_t g = 0; g < n && g < cap; ++g) {
+        uint64_t x = 1469598103934665603ull;
+        const uint32_t r = b.d_pair_rep[(size_t)g];
+        if (r != 0xFFFFFFFFu) for (unsigned char c : b.d_reads[r].qname) { x ^= c; x *= 1099511628211ull; }
+        out[g] = x;
+    }
+    if (shared) *shared = b.d_pair_shared;
+    return n;
+}
+
+// full query name of run-wide read-name id `gid` of the last smc_bam_alignments (its first record's); valid until the next call
+const char* smc_bam_pair_name(void* h, int32_t gid) {
+    Bam& b = *(Bam*)h;
+    pair_reps(b);
+    const bool ok = gid >= 0 && (size_t)gid < b.d_pair_rep.size() && b.d_pair_rep[(size_t)gid] != 0xFFFFFFFFu;
+    b.d_pair_text = ok ? std::string(b.d_reads[b.d_pair_rep[(size_t)gid]].qname) : std::string();
+    return b.d_pair_text.c_str();
 }
 
 }  // extern "C"

@@ -25,7 +25,8 @@
 //                        exact two-sided by chunked hypergeometric sums with a log-factorial table.
 //   k_pack_rows.inc      432-byte rows -> 168-byte wire rows for the multi-GPU gather.
 //   k_pack_words.inc     raw-field planes (meta, frag) -> read words, for batches a host builder made.
-//   k_select_aln.inc     the alignments of a run's kept barcodes (ds.mt.py's drop, in HBM) and the decoder's descriptors over them.
+//   k_select_aln.inc     the alignments of a run's kept barcodes or kept read names (ds.mt.py's / ds.reads.withinMT.py's drop, in HBM)
+//                        and the decoder's descriptors over them.
 //
 // Data layout (include/smcounter_hip.h): ONE uint32 per pileup read (allele, quality, fragment start, read
 // class - what is left of the 16 B of raw fields per read once the plane builder has digested them) and umi_start; a 32-byte

@@ -153,6 +153,7 @@ def iter_resident_batches(path: str, fasta, loci: Sequence[Tuple[str, str]], par
     `ds_rules` (--dsMT): every run is decoded and uploaded once and built K + 1 times - at full depth and, through
     smc_select_alignments, for the kept barcodes of every rule (called with that rule's params); each item is then
     (first, [full-depth batch, batch of rule 1, ...]), all of the same loci.  Every run must be one the device builder takes.
+    (--dsRpb: a rule of level "read" keeps read names, by the run's read-name ids - smc_select_alignments_keyed; the same batches.)
     `all_planes=False`: only what the locus kernels read - the read words and umi_start - is built and kept (a fifth of the
     device memory of a batch, a quarter of the builder's stores); the four raw-field planes (for checks) are then None.
     (Round 5 built and measured decoding run i + 1 on a helper thread - a second decoder handle, the streaming cursor handed
@@ -245,7 +246,7 @@ def iter_resident_batches(path: str, fasta, loci: Sequence[Tuple[str, str]], par
                 umi_base = slots + n_loc
                 done = None
                 if ds_rules and force_host:
-                    raise bamio.BamError(_ds_refused(chrom, lo, hi, "the planes are built on the host"))
+                    raise bamio.BamError(_ds_refused(chrom, lo, hi, "the planes are built on the host", _ds_flag(ds_rules)))
                 if not force_host:
                     T = _TIMES if os.environ.get("SMC_DEVPLANES_TIMING") else None
                     t0 = time.perf_counter()
@@ -257,7 +258,7 @@ def iter_resident_batches(path: str, fasta, loci: Sequence[Tuple[str, str]], par
                                      bam.allele_key, bam.barcode_name, sampler=sampler, sampler_seed=sampler_seed,
                                      barcode_idents=bam.barcode_idents, uploaded=up)
                     if ds_rules and done is None:
-                        raise bamio.BamError(_ds_refused(chrom, lo, hi, "the device builder does not take it"))
+                        raise bamio.BamError(_ds_refused(chrom, lo, hi, "the device builder does not take it", _ds_flag(ds_rules)))
                     if ds_rules and done != NARROW:
                         narrow = not _ds_build_run(ds_rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_depth, bam, sampler,
                                                    sampler_seed, n_loc)
@@ -350,8 +351,12 @@ class _DsBatch(object):
                              loci=lc, chrom=full.chrom, pos=full.pos, ref=full.ref, alleles=self.tables, n_device_runs=full.n_device_runs)
 
 
-def _ds_refused(chrom, lo, hi, why):
-    return "--dsMT needs the device builder: the run %s:%d-%d cannot go through it (%s)" % (chrom, lo + 1, hi, why)
+def _ds_refused(chrom, lo, hi, why, flag="--dsMT"):
+    return "%s needs the device builder: the run %s:%d-%d cannot go through it (%s)" % (flag, chrom, lo + 1, hi, why)
+
+
+def _ds_flag(rules):
+    return " / ".join(sorted({r.flag for r in rules}, reverse=True))
 
 
 def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_depth, bam, sampler, sampler_seed, n_loc):
@@ -360,16 +365,33 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
     L = eng.L
     nl = A["nl"]
     res = []
-    if nl:
-        idents = bam.barcode_idents(A["n_bc"])
-        names = None
+    idents = names = p_idents = p_names = None
     for rule, d in zip(rules, ds):
         if not nl:
             res.append((0, 0, np.zeros(0, LOCUS_DTYPE), []))
             continue
-        if rule.kept is None:
+        if rule.level == "read":
+            # (--dsRpb: the kept read names, by read-name id - an id must stand for one full name, or the rule cannot be applied)
+            if p_idents is None:
+                p_idents, shared = bam.pair_idents(A["n_pair"])
+                if shared:
+                    raise bamio.BamError("--dsRpb: the run %s:%d-%d has a read id (read name without its last field) shared by two "
+                                         "different read names: ds.reads.withinMT.py keeps whole names, the decoder's ids cannot tell "
+                                         "them apart" % (chrom, lo + 1, lo + nl))
+            if rule.kept_idents is not None:
+                mask = np.isin(p_idents, rule.kept_idents)
+            else:
+                if p_names is None:
+                    p_names = [bam.pair_name(g) for g in range(int(A["n_pair"]))]
+                mask = np.array([t in rule.kept for t in p_names], bool)
+            sel, counts, d_orig = select_run(eng, up, A, lo, mask=mask, level="read")
+        elif rule.kept is None:
+            if idents is None:
+                idents = bam.barcode_idents(A["n_bc"])
             sel, counts, d_orig = select_run(eng, up, A, lo, idents=idents, frac=rule.frac, seed=rule.seed)
         else:
+            if idents is None:
+                idents = bam.barcode_idents(A["n_bc"])
             if rule.kept_idents is not None:
                 mask = np.isin(idents, rule.kept_idents)
             else:
@@ -377,21 +399,35 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
                     names = [bam.barcode_name(g) for g in range(int(A["n_bc"]))]
                 mask = np.array([t in rule.kept for t in names], bool)
             sel, counts, d_orig = select_run(eng, up, A, lo, mask=mask)
-        orig = []
+        got = {}
 
-        def allele_key(ai, qpos, indel, d_orig=d_orig, orig=orig, kept=sel.n_aln):
+        def orig_index(d_orig=d_orig, kept=sel.n_aln, got=got):
+            if "orig" not in got:
+                got["orig"] = d_orig.download(np.uint32, kept)
+            return got["orig"]
+
+        def allele_key(ai, qpos, indel, orig_index=orig_index):
             # (the builder's alignment index counts the KEPT alignments: the decoder's records are those of the full run)
-            if not orig:
-                orig.append(d_orig.download(np.uint32, kept))
-            return bam.allele_key(int(orig[0][int(ai)]), qpos, indel)
+            return bam.allele_key(int(orig_index()[int(ai)]), qpos, indel)
+        bc_name, bc_idents = bam.barcode_name, bam.barcode_idents
+        if rule.level == "read":
+            # (the read level renumbers the kept barcodes by first kept appearance: the texts the cap samplers need are the decoder's,
+            # by the old id of every new one - the old ids of the kept alignments in order, each at its first appearance)
+            def old_bc(orig_index=orig_index, got=got, bc=A["aln"]["bc_gid"]):
+                if "old_bc" not in got:
+                    old = bc[orig_index()]
+                    got["old_bc"] = old[np.sort(np.unique(old, return_index=True)[1])]
+                return got["old_bc"]
+            bc_name = lambda g, old_bc=old_bc: bam.barcode_name(int(old_bc()[int(g)]))
+            bc_idents = lambda n, old_bc=old_bc: bam.barcode_idents(A["n_bc"])[old_bc()]
         w = d.words
         done = build_run(counts, L, eng, abi.c_params(rule.params), rule.params, chrom, lo, fasta, run_ref, [w] + d.planes, d.uaux,
-                         d.slots, d.slots + n_loc, cap, max_depth, allele_key, bam.barcode_name, sampler=sampler, sampler_seed=sampler_seed,
-                         barcode_idents=bam.barcode_idents, uploaded=sel)
+                         d.slots, d.slots + n_loc, cap, max_depth, allele_key, bc_name, sampler=sampler, sampler_seed=sampler_seed,
+                         barcode_idents=bc_idents, uploaded=sel)
         sel.free(shared=False)
         d_orig.free()
         if done is None:
-            raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "fraction %g: the device builder does not take it" % rule.frac))
+            raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "%s: the device builder does not take it" % rule.label, rule.flag))
         if done == NARROW:
             return False
         res.append(done)
@@ -565,6 +601,20 @@ class DsRule:
     kept: object = None
     seed: int = 1234567
     kept_idents: object = None  # (sorted FNV-1a idents of `kept` when no two barcodes of the file share one: a run's mask without texts)
+    # (--dsRpb) level "read": `kept` holds full read names (ds.reads.withinMT.py), `target` the reads per barcode asked for, `prob_keep`
+    # the reference's probKeep, `n_names` the distinct read names of the file
+    level: str = "barcode"
+    target: float = None
+    prob_keep: float = None
+    n_names: int = 0
+
+    @property
+    def flag(self) -> str:
+        return "--dsRpb" if self.level == "read" else "--dsMT"
+
+    @property
+    def label(self) -> str:
+        return "target %g" % self.target if self.level == "read" else "fraction %g" % self.frac
 
 
 def reference_rules(path: str, fracs, params_list, seed: int):
@@ -585,17 +635,43 @@ def reference_rules(path: str, fracs, params_list, seed: int):
     return rules
 
 
+def reference_read_rules(path: str, targets, params_list, seed: int):
+    """DsRules of --dsRpb: for each target r the read names ds.reads.withinMT.py --rpb r --seed `seed` keeps (:22-90;
+    tools.ds_reads_within_mt): per barcode its distinct names in first-appearance order, probKeep from the whole file's counts,
+    barcodes in py2 dict order, the first name always kept, every further one when random() <= probKeep.  The names are read and
+    grouped once per file.  A file without a barcode of two or more names has no probKeep (the reference divides by zero):
+    ValueError naming the file and the target."""
+    from .py2compat import py2_dict_order
+    from .tools import ds_reads_within_mt as rw
+    per_bc, order = rw.group_reads(bamio.placed_qnames(path))
+    py2 = py2_dict_order(order)
+    names = [q for bc in order for q in per_bc[bc]]
+    idents = fnv64_array(names)
+    unique = len(np.unique(idents)) == len(names)
+    rules = []
+    for r, P in zip(targets, params_list):
+        try:
+            prob = rw.prob_keep(per_bc, r)
+        except ZeroDivisionError:
+            raise ValueError("--dsRpb %g: %s has no barcode with more than one read name, so ds.reads.withinMT.py's probKeep "
+                             "(:58) is not defined (it divides by zero)" % (r, path))
+        kept = rw.draw_reads(per_bc, py2, prob, seed)
+        ki = np.sort(idents[np.fromiter((q in kept for q in names), bool, len(names))]) if unique else None
+        rules.append(DsRule(1.0, P, kept=kept, seed=int(seed), kept_idents=ki, level="read", target=float(r), prob_keep=prob,
+                            n_names=len(names)))
+    return rules
+
+
 def fnv64_array(texts) -> np.ndarray:
-    """FNV-1a (64 bits) of every text, vectorised: what smc_bam_barcode_idents computes for a run's barcodes."""
+    """FNV-1a (64 bits) of every text, vectorised: what smc_bam_barcode_idents / smc_bam_pair_idents compute for a run's ids."""
     b = [t.encode() for t in texts]
     n = len(b)
     x = np.full(n, 1469598103934665603, np.uint64)
     if not n:
         return x
-    lens = np.array([len(t) for t in b], np.int64)
-    m = np.zeros((n, int(lens.max()) if n else 0), np.uint8)
-    for i, t in enumerate(b):
-        m[i, :len(t)] = np.frombuffer(t, np.uint8)
+    lens = np.fromiter(map(len, b), np.int64, n)
+    # (a fixed-width byte array, zero-padded - the texts hold no NUL byte - viewed as an n x width matrix)
+    m = np.array(b, dtype="S%d" % max(1, int(lens.max()))).view(np.uint8).reshape(n, -1)
     prime = np.uint64(1099511628211)
     with np.errstate(over="ignore"):
         for k in range(m.shape[1]):
@@ -619,14 +695,19 @@ def philox_keep_host(L, idents, frac: float, seed: int) -> np.ndarray:
     return keep
 
 
-def select_run(eng, up: RunOnDevice, A, lo: int, mask=None, idents=None, frac: float = 1.0, seed: int = 0):
+def select_run(eng, up: RunOnDevice, A, lo: int, mask=None, idents=None, frac: float = 1.0, seed: int = 0, level: str = "barcode"):
     """smc_select_alignments: the run `up` (A: its counts) reduced to the kept barcodes' alignments -> (RunOnDevice of the kept ones,
     sharing the pools and the reference; counts dict for build_run; device buffer of orig_index).  `mask`: bool per run-wide barcode
-    id (the host's set); else `idents` (uint64 per id) and the philox rule at `frac` / `seed`."""
+    id (the host's set); else `idents` (uint64 per id) and the philox rule at `frac` / `seed`.  level "read"
+    (smc_select_alignments_keyed, SMC_SEL_KEY_READ): the same per run-wide read-name id - whole read names kept or dropped - and the
+    kept alignments' ids renumbered by first kept appearance (the decoder's numbering of the down-sampled BAM)."""
     from .engine import DevBuf
     L = eng.L
     nl, n = A["nl"], up.n_aln
-    n_ids = int(A["n_bc"])
+    by_read = level == "read"
+    if level not in ("barcode", "read"):
+        raise ValueError("select_run: level %r" % level)
+    n_ids = int(A["n_pair"] if by_read else A["n_bc"])
     d_out = DevBuf(eng, 36 * max(1, n) + 256)
     d_orig = DevBuf(eng, 4 * max(1, n) + 256)
     d_loc = DevBuf(eng, 16 * max(1, nl) + 256)
@@ -643,9 +724,15 @@ def select_run(eng, up: RunOnDevice, A, lo: int, mask=None, idents=None, frac: f
         d_rule = DevBuf(eng, 8 * max(1, len(idents)) + 256).upload(idents if len(idents) else np.zeros(1, np.uint64))
         mptr, iptr = None, d_rule.data_ptr()
         n_ids = len(idents)
-    _lib.check(L.smc_select_alignments(eng.ctx, up.aln.data_ptr(), n, up.loc.data_ptr(), nl, int(lo), mptr, iptr, n_ids,
-                                       ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), float(frac), d_out.data_ptr(), d_orig.data_ptr(),
-                                       d_loc.data_ptr(), d_sum.data_ptr(), ctypes.c_void_p(0)), "smc_select_alignments")
+    tail = (ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), float(frac), d_out.data_ptr(), d_orig.data_ptr(), d_loc.data_ptr(),
+            d_sum.data_ptr(), ctypes.c_void_p(0))
+    if by_read:
+        _lib.check(L.smc_select_alignments_keyed(eng.ctx, up.aln.data_ptr(), n, up.loc.data_ptr(), nl, int(lo), 1, int(A["n_bc"]),
+                                                 int(A["n_pair"]), mptr, iptr, n_ids, *tail),
+                   "smc_select_alignments_keyed")
+    else:
+        _lib.check(L.smc_select_alignments(eng.ctx, up.aln.data_ptr(), n, up.loc.data_ptr(), nl, int(lo), mptr, iptr, n_ids, *tail),
+                   "smc_select_alignments")
     kept, deepest, slots = (int(v) for v in d_sum.download(np.uint32, 3))
     d_rule.free()
     sel = RunOnDevice(d_out, up.cig, up.bq, d_loc, up.ref, kept, None)

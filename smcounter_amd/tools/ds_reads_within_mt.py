@@ -16,7 +16,8 @@ from ..py2compat import Py2Random, py2_dict_order
 from .ds_mt import barcode_of
 
 
-def select_reads(qnames, rpb: float, seed: int):
+def group_reads(qnames):
+    """Per barcode the distinct read names in order of first appearance (:37-44), the barcodes in order of first appearance."""
     per_bc, seen, order = {}, set(), []
     for q in qnames:
         bc = barcode_of(q)
@@ -26,19 +27,33 @@ def select_reads(qnames, rpb: float, seed: int):
         if (bc, q) not in seen:
             seen.add((bc, q))
             per_bc[bc].append(q)
+    return per_bc, order
+
+
+def prob_keep(per_bc, rpb: float) -> float:
     one = sum(1 for v in per_bc.values() if len(v) == 1)
     multi = sum(1 for v in per_bc.values() if len(v) > 1)
     multi_reads = sum(len(v) for v in per_bc.values() if len(v) > 1)
-    prob_keep = 1.0 * (rpb - 1.0) * (one + multi) / (multi_reads - multi)      # :58 (ZeroDivisionError like the reference)
+    return 1.0 * (rpb - 1.0) * (one + multi) / (multi_reads - multi)      # :58 (ZeroDivisionError like the reference)
+
+
+def draw_reads(per_bc, py2_order, prob: float, seed: int):
+    """The kept read names: barcodes in py2 dict order (:62), the first name of each kept, every further one when random() <= prob."""
     rng = Py2Random(int(seed))
     selected = set()
-    for bc in py2_dict_order(order):
+    for bc in py2_order:
         reads = per_bc[bc]
         selected.add(reads[0])
         for rid in reads[1:]:
-            if rng.random() <= prob_keep:
+            if rng.random() <= prob:
                 selected.add(rid)
-    return selected, prob_keep
+    return selected
+
+
+def select_reads(qnames, rpb: float, seed: int):
+    per_bc, order = group_reads(qnames)
+    prob = prob_keep(per_bc, rpb)
+    return draw_reads(per_bc, py2_dict_order(order), prob, seed), prob
 
 
 def main(args) -> int:

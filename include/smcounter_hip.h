@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 10
+#define SMC_ABI_VERSION 11
 #define SMC_MAX_ALLELES 64 /* allele ids per locus; ids 0-5 are A,T,G,C,N,'DEL' */
 
 /* error codes */
@@ -415,6 +415,44 @@ int smc_select_alignments_keyed(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t 
                                 int32_t key, int64_t n_bc, int64_t n_pair, const uint32_t* d_keep_mask, const uint64_t* d_ident, int64_t n_ids,
                                 uint64_t seed, double frac, smc_dev_aln* d_aln_out, uint32_t* d_orig_index, smc_dev_locus* d_loc_out,
                                 uint32_t* d_summary, void* stream);
+/* (ABI 11) The read-level philox sampler of --dsRpb (--dsRpbSampler philox): a file-wide table of read names and barcodes that stays
+ * in HBM for the whole run (csrc/k_read_groups.inc).  Grouping as ds.reads.withinMT.py:37-58: the unit is the full read name, its
+ * barcode field -2 of the stripped name; per barcode the names counted; one / multi = barcodes with one / two or more names,
+ * multi_names = names in the latter.  A name is kept at a target when it is its barcode's first (its first record has the smallest
+ * ordinal of the barcode's records) or when word 0 of Philox4x32-10(counter = (identity lo, identity hi, 0x64735250 "dsRP", 0),
+ * key = (seed lo, seed hi)) < thr, thr = floor(probKeep * 2^32) in [0, 2^32] (the host computes probKeep from the counters).
+ *   _create   an empty table.
+ *   _add      n keys of consecutive placed records (host memory; smc_bam_name_keys writes them), the first one's ordinal in the file;
+ *             copied to the device, inserted by _finish.  Ordinals below 2^32 - 1, every record once.
+ *   _finish   sizes the two tables from the records added (power of two, load factor <= 0.5), inserts them, checks every record's
+ *             check words against its slots', groups; counts[SMC_RG_N_COUNTS] (below) back on the host.
+ *   _masks    per run: for n_ids read-name identities in HBM (smc_bam_pair_idents of the run, uploaded), n_thr <= SMC_RG_MAX_TARGETS
+ *             thresholds (host) -> d_masks[t * ceil(n_ids / 32) + (g >> 5)] bit (g & 31): id g kept at target t - the mask
+ *             smc_select_alignments_keyed takes at SMC_SEL_KEY_READ.  An identity the table does not hold sets SMC_RG_MISS.
+ *   _kept     the file-wide kept names per target (host kept[n_thr]).
+ *   _status   the SMC_RG_* bits so far (0: every key had one text).  After _finish / _masks / _kept (synchronises the device).
+ * Everything runs on the null stream except _masks (`stream`). */
+typedef struct smc_read_groups smc_read_groups;
+typedef struct smc_read_key {          /* one placed record: 24 bytes, smc_bam_name_keys' 3 words */
+    uint64_t name_id;                  /* FNV-1a 64 of the full read name */
+    uint64_t bc_id;                    /* FNV-1a 64 of its barcode */
+    uint32_t name_chk, bc_chk;         /* FNV-1a 32 of the same texts: the check words */
+} smc_read_key;
+#define SMC_RG_MAX_TARGETS 32
+#define SMC_RG_N_COUNTS 8              /* records, names, barcodes, one, multi, multi_names, first names, 0 */
+#define SMC_RG_NAME_COLLISION 1u       /* two records with one name identity and different check words (or barcodes) */
+#define SMC_RG_BARCODE_COLLISION 2u    /* two records with one barcode identity and different check words */
+#define SMC_RG_FULL 4u                 /* a probe went round a whole table */
+#define SMC_RG_MISS 8u                 /* _masks: an identity the table does not hold */
+#define SMC_RG_RESERVED 16u            /* an identity equal to 0 (the empty slot's mark) */
+int smc_read_groups_create(smc_ctx* ctx, smc_read_groups** out);
+int smc_read_groups_add(smc_read_groups* g, const smc_read_key* keys, int64_t n, int64_t first_ordinal);
+int smc_read_groups_finish(smc_read_groups* g, int64_t* counts);
+int smc_read_groups_masks(smc_read_groups* g, const uint64_t* d_idents, int64_t n_ids, uint64_t seed, const uint64_t* thr, int32_t n_thr,
+                          uint32_t* d_masks, void* stream);
+int smc_read_groups_kept(smc_read_groups* g, uint64_t seed, const uint64_t* thr, int32_t n_thr, int64_t* kept);
+int smc_read_groups_status(smc_read_groups* g, uint32_t* status);
+void smc_read_groups_destroy(smc_read_groups* g);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

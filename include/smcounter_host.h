@@ -83,6 +83,15 @@ int64_t smc_bam_barcode_idents(void* h, uint64_t* out, int64_t cap);
 int64_t smc_bam_pair_idents(void* h, uint64_t* out, int64_t cap, int32_t* shared);
 /* full query name of read-name id `gid` of the last smc_bam_alignments ("" out of range); valid until the next call */
 const char* smc_bam_pair_name(void* h, int32_t gid);
+/* The whole-file pass of the read-level philox sampler (--dsRpbSampler philox): every record placed on a reference (tid >= 0) of the
+ * file, in file order - the records ds.reads.withinMT.py:37-44 walks -, as 3 words each: FNV-1a (64 bits) of the full query name (the
+ * identity smc_bam_pair_idents gives a read-name id), FNV-1a (64 bits) of its barcode (field -2 of the stripped name split at ':'),
+ * then the two check words, name | barcode << 32: FNV-1a with 32 bits (offset basis 2166136261, prime 16777619) of the same texts.
+ * In chunks: restart != 0 starts from the first record (the last smc_bam_alignments run is dropped), every call writes the next
+ * placed records, at most `cap`, into out[3 * cap] and the ordinal of the chunk's first one into *first_ordinal.  Only the names are
+ * read; the blocks are inflated by `nthreads` threads.  -> records written, 0 at the end of the file (the pass is then closed),
+ * < 0 on an error (smc_bam_error: -3, a placed name without a barcode field). */
+int64_t smc_bam_name_keys(void* h, int32_t restart, int64_t cap, int32_t nthreads, uint64_t* out, int64_t* first_ordinal);
 
 /* ---------------------------------------------------------------- libsmc_rowfmt.so */
 

@@ -621,6 +621,8 @@ def _native_lib():
         lib.smc_bam_pair_name.restype = C.c_char_p
         lib.smc_bam_span_bytes.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64]
         lib.smc_bam_span_bytes.restype = C.c_int64
+        lib.smc_bam_name_keys.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
+        lib.smc_bam_name_keys.restype = C.c_int64
         _NATIVE = lib
     return _NATIVE
 
@@ -637,6 +639,7 @@ class NativeBam(object):
     def __init__(self, path: str):
         import ctypes as C
         self._lib = _native_lib()
+        self.path = path
         self._h = C.c_void_p()
         rc = self._lib.smc_bam_open(path.encode(), C.byref(self._h))
         if rc:
@@ -748,6 +751,24 @@ class NativeBam(object):
     def pair_name(self, gid: int) -> str:
         """The full query name of read-name id `gid` of the last run (its first record's)."""
         return self._lib.smc_bam_pair_name(self._h, int(gid)).decode()
+
+    def name_keys(self, chunk: int, nthreads: int = 0):
+        """The whole-file pass of the read-level philox sampler (smc_bam_name_keys): every placed record of the file in file order, in
+        chunks of at most `chunk` records -> yields (ordinal of the chunk's first record, uint64 array [n, 3]: name identity, barcode
+        identity, name check | barcode check << 32).  The chunk's array is reused by the next one.  Drops the last run."""
+        import ctypes as C
+        chunk = max(1, int(chunk))
+        out = np.empty((chunk, 3), np.uint64)
+        first = C.c_int64(0)
+        restart = 1
+        while True:
+            n = int(self._lib.smc_bam_name_keys(self._h, restart, chunk, int(nthreads or host_threads()), out.ctypes.data, C.byref(first)))
+            restart = 0
+            if n < 0:
+                raise BamError("%s: %s" % (self.path, self._lib.smc_bam_error(self._h).decode()))
+            if n == 0:
+                return
+            yield int(first.value), out[:n]
 
     def planes_run(self, chrom: str, lo: int, hi: int, max_reads: int, params, refseq: str, nthreads: int, fasta,
                    arena=None, arena_off: int = 0):

@@ -79,10 +79,17 @@ def build_parser() -> argparse.ArgumentParser:
                                                  "to <outPrefix>.dsRpb<r>.smCounter.{all,cut}.txt and .cut.vcf.  The kept names are the "
                                                  "reference's exactly (one pass over the whole file, on the host); --dsSampler philox "
                                                  "is not available here (a shape-independent rule for reads needs the whole file's "
-                                                 "first names and probKeep).  With --dsMT: each target and each fraction gets its own "
-                                                 "files from the same decode, no cross product.  Needs the device plane builder; one "
-                                                 "process only")
+                                                 "first names and probKeep: see --dsRpbSampler).  With --dsMT: each target and each "
+                                                 "fraction gets its own files from the same decode, no cross product.  Needs the device "
+                                                 "plane builder; one process only")
     p.add_argument("--dsRpbMtDepth", default=None, help="comma-separated --mtDepth of each --dsRpb target; default --mtDepth")
+    p.add_argument("--dsRpbSampler", choices=("reference", "philox"), default=None,
+                   help="which read names --dsRpb keeps.  reference (default): exactly ds.reads.withinMT.py's set (the names grouped "
+                        "and drawn on the host).  philox: the whole file's names grouped by barcode in a table on the GPU, probKeep "
+                        "from its counts as the reference computes it, a barcode's first name always kept and every further one when a "
+                        "counter-based draw (Philox4x32-10) keyed by --dsSeed and a hash of the full name falls below probKeep - NOT "
+                        "the reference's sample (another random subset of about the same size; nested across targets), independent "
+                        "of how the file is cut into runs.  Needs --dsRpb")
     return p
 
 
@@ -115,6 +122,8 @@ def ds_rpb_targets(args):
     """--dsRpb / --dsRpbMtDepth -> [(r, mtDepth of r, output prefix)]; [] without --dsRpb."""
     text = getattr(args, "dsRpb", None)
     if text in (None, ""):
+        if getattr(args, "dsRpbSampler", None) is not None:
+            raise SystemExit("--dsRpbSampler chooses the read names --dsRpb keeps: it needs --dsRpb")
         return []
     try:
         rs = [float(x) for x in str(text).split(",") if x.strip()]
@@ -134,18 +143,28 @@ def ds_rpb_targets(args):
         depths = [int(args.mtDepth)] * len(rs)
     if getattr(args, "dsSampler", "reference") == "philox":
         raise SystemExit("--dsRpb keeps the reference's read names only: --dsSampler philox is not available with it (a rule for "
-                         "reads that does not depend on how the file is cut into runs needs the whole file's first names and probKeep)")
+                         "reads that does not depend on how the file is cut into runs needs the whole file's first names and probKeep; "
+                         "--dsRpbSampler philox is that rule)")
     return [(r, d, "%s.dsRpb%g" % (args.outPrefix, r)) for r, d in zip(rs, depths)]
 
 
-def ds_rpb_rules(args, params: VcParams, targets):
-    """The devplanes.DsRule of every --dsRpb target (the reference's read names: one pass over the whole file, here); a file without a
-    barcode of two or more reads ends the run with a message."""
+def ds_rpb_rules(args, params: VcParams, targets, early=None):
+    """The devplanes.DsRule of every --dsRpb target: the reference's read names (one pass over the whole file, here), or with
+    --dsRpbSampler philox the file-wide table on the GPU (`early`: the engine coming up; else the process's engine); a file without a
+    barcode of two or more reads, or whose names collide in the table's hashes, ends the run with a message."""
     import dataclasses
     from . import devplanes
     plist = [dataclasses.replace(params, mtDepth=d, rpb=r) for r, d, _ in targets]
+    rs = [r for r, _, _ in targets]
     try:
-        return devplanes.reference_read_rules(args.bamFile, [r for r, _, _ in targets], plist, int(args.dsSeed))
+        if (getattr(args, "dsRpbSampler", None) or "reference") == "philox":
+            if early is not None:
+                eng = early.get()
+            else:
+                from .engine import Engine
+                eng = _ENGINES.get(args.device) or _ENGINES.setdefault(args.device, Engine(args.device))
+            return devplanes.philox_read_rules(args.bamFile, rs, plist, int(args.dsSeed), eng)
+        return devplanes.reference_read_rules(args.bamFile, rs, plist, int(args.dsSeed))
     except ValueError as e:
         raise SystemExit(str(e))
 
@@ -388,7 +407,7 @@ def _main(args) -> int:
         early = _EarlyEngine(args.device)
     loc_list = bedops.expand_loci(args.bedTarget)
     try:
-        rules = (ds_rules(args, params, fractions) if fractions else []) + (ds_rpb_rules(args, params, targets) if targets else [])
+        rules = (ds_rules(args, params, fractions) if fractions else []) + (ds_rpb_rules(args, params, targets, early) if targets else [])
     except SystemExit:
         if early is not None:                  # (the engine the helper brings up stays with the process, as after a run)
             try:
@@ -398,9 +417,18 @@ def _main(args) -> int:
         raise
     for rule in rules:
         if rule.level == "read":
-            print("--dsRpb %g: probKeep %.6g, %d of %d read names kept (seed %d, mtDepth %d)" %
-                  (rule.target, rule.prob_keep, len(rule.kept), rule.n_names, rule.seed, rule.params.mtDepth))
+            print("--dsRpb %g: sampler %s, seed %d, probKeep %.6g, %d of %d read names kept (mtDepth %d)" %
+                  (rule.target, rule.sampler, rule.seed, rule.prob_keep, len(rule.kept) if rule.kept is not None else rule.n_kept,
+                   rule.n_names, rule.params.mtDepth))
     args.ds_rules = rules or None
+    try:
+        return _run(args, params, fractions, targets, loc_list, early, t0)
+    finally:
+        from . import devplanes
+        devplanes.close_rules(rules)          # (--dsRpbSampler philox: the file-wide table in HBM, whatever happened)
+
+
+def _run(args, params, fractions, targets, loc_list, early, t0):
     # One process per GPU when launched through torch.distributed.run: rank r calls a contiguous range of the
     # ordered locus list (loci share nothing, smCounter.py:683-685) on GPU LOCAL_RANK, rank 0 gathers the rows
     # in submission order and writes the files.

@@ -892,6 +892,147 @@ int smc_select_alignments(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln,
                                        d_aln_out, d_orig_index, d_loc_out, d_summary, stream);
 }
 
+// ---- (ABI 11) the read-level philox sampler's file-wide table (k_read_groups.inc)
+struct smc_read_groups {
+    smc_ctx* ctx = nullptr;
+    struct Chunk { smc_read_key* d = nullptr; int64_t n = 0, ord0 = 0; };
+    std::vector<Chunk> chunks;          // the records added, in HBM until _finish inserts them
+    int64_t n_records = 0, next_ord = 0;
+    bool finished = false;
+    void* mem = nullptr;                // both tables, the info / count words, status, counters, kept counts
+    RgTable G{};
+    unsigned long long* d_kept = nullptr;
+    int64_t counts[SMC_RG_N_COUNTS] = {0};
+};
+
+static int rg_grid(unsigned long long n) { return (int)std::max<unsigned long long>(1, std::min<unsigned long long>((n + RG_BLOCK - 1) / RG_BLOCK, 8192)); }
+
+static int rg_thresholds(const uint64_t* thr, int32_t n_thr, RgThr& T) {
+    if (n_thr < 0 || n_thr > SMC_RG_MAX_TARGETS || (n_thr && !thr)) return fail(SMC_E_ARG, "smc_read_groups: bad thresholds");
+    memset(&T, 0, sizeof T);
+    for (int t = 0; t < n_thr; ++t) {
+        if (thr[t] > (1ull << 32)) return fail(SMC_E_ARG, "smc_read_groups: a threshold above 2^32");
+        T.t[t] = thr[t];
+    }
+    return SMC_OK;
+}
+
+int smc_read_groups_create(smc_ctx* ctx, smc_read_groups** out) {
+    if (!ctx || !out) return fail(SMC_E_ARG, "smc_read_groups_create: bad argument");
+    *out = new smc_read_groups();
+    (*out)->ctx = ctx;
+    return SMC_OK;
+}
+
+int smc_read_groups_add(smc_read_groups* g, const smc_read_key* keys, int64_t n, int64_t first_ordinal) {
+    if (!g || n < 0 || (n && !keys) || first_ordinal < 0) return fail(SMC_E_ARG, "smc_read_groups_add: bad argument");
+    if (g->finished) return fail(SMC_E_ARG, "smc_read_groups_add: the table is finished");
+    if (first_ordinal < g->next_ord) return fail(SMC_E_ARG, "smc_read_groups_add: ordinals must grow from chunk to chunk");
+    if (first_ordinal + n >= (int64_t)0xFFFFFFFF) return fail(SMC_E_ARG, "smc_read_groups_add: ordinals beyond 2^32 - 2");
+    if (!n) return SMC_OK;
+    HIPCHK(hipSetDevice(g->ctx->device));
+    smc_read_groups::Chunk c;
+    c.n = n; c.ord0 = first_ordinal;
+    HIPCHK(hipMalloc((void**)&c.d, sizeof(smc_read_key) * (size_t)n));
+    const hipError_t e = hipMemcpy(c.d, keys, sizeof(smc_read_key) * (size_t)n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(c.d); return fail(SMC_E_HIP, std::string("smc_read_groups_add: ") + hipGetErrorString(e)); }
+    g->chunks.push_back(c);
+    g->n_records += n;
+    g->next_ord = first_ordinal + n;
+    return SMC_OK;
+}
+
+int smc_read_groups_finish(smc_read_groups* g, int64_t* counts) {
+    if (!g || !counts) return fail(SMC_E_ARG, "smc_read_groups_finish: bad argument");
+    if (g->finished) return fail(SMC_E_ARG, "smc_read_groups_finish: finished already");
+    HIPCHK(hipSetDevice(g->ctx->device));
+    // capacity: a power of two >= 2 x the records (names and barcodes are each at most that many)
+    unsigned long long cap = 2;
+    while (cap < 2ull * (unsigned long long)g->n_records) cap <<= 1;
+    if (cap > (1ull << 31)) return fail(SMC_E_ARG, "smc_read_groups_finish: too many records");
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_name = carve(16 * cap), o_info = carve(4 * cap), o_bc = carve(16 * cap), o_cnt = carve(4 * cap),
+                 o_st = carve(4), o_ctr = carve(8 * RG_N_CTR), o_kept = carve(8 * SMC_RG_MAX_TARGETS);
+    HIPCHK(hipMalloc(&g->mem, off));
+    char* m = (char*)g->mem;
+    RgTable& G = g->G;
+    G.name = (RgSlot*)(m + o_name); G.name_info = (uint32_t*)(m + o_info); G.bc = (RgSlot*)(m + o_bc); G.bc_cnt = (uint32_t*)(m + o_cnt);
+    G.n_mask = G.b_mask = cap - 1;
+    G.status = (uint32_t*)(m + o_st); G.ctr = (unsigned long long*)(m + o_ctr);
+    g->d_kept = (unsigned long long*)(m + o_kept);
+    HIPCHK(hipMemsetAsync(m + o_st, 0, off - o_st, 0));
+    hipLaunchKernelGGL(k_rg_init, dim3(rg_grid(cap)), dim3(RG_BLOCK), 0, 0, G);
+    for (const auto& c : g->chunks)
+        hipLaunchKernelGGL(k_rg_insert, dim3(rg_grid(c.n)), dim3(RG_BLOCK), 0, 0, G, (const smc_read_key*)c.d, (uint32_t)c.n, (uint32_t)c.ord0);
+    for (const auto& c : g->chunks)
+        hipLaunchKernelGGL(k_rg_verify, dim3(rg_grid(c.n)), dim3(RG_BLOCK), 0, 0, G, (const smc_read_key*)c.d, (uint32_t)c.n);
+    hipLaunchKernelGGL(k_rg_link, dim3(rg_grid(cap)), dim3(RG_BLOCK), 0, 0, G);
+    hipLaunchKernelGGL(k_rg_reduce, dim3(rg_grid(cap)), dim3(RG_BLOCK), 0, 0, G);
+    HIPCHK(hipGetLastError());
+    unsigned long long ctr[RG_N_CTR];
+    HIPCHK(hipMemcpy(ctr, G.ctr, sizeof ctr, hipMemcpyDeviceToHost));
+    for (auto& c : g->chunks) (void)hipFree(c.d);
+    g->chunks.clear();
+    g->finished = true;
+    g->counts[0] = g->n_records;
+    g->counts[1] = (int64_t)ctr[RG_C_NAMES]; g->counts[2] = (int64_t)ctr[RG_C_BARCODES]; g->counts[3] = (int64_t)ctr[RG_C_ONE];
+    g->counts[4] = (int64_t)ctr[RG_C_MULTI]; g->counts[5] = (int64_t)ctr[RG_C_MULTI_NAMES]; g->counts[6] = (int64_t)ctr[RG_C_FIRST];
+    for (int k = 0; k < SMC_RG_N_COUNTS; ++k) counts[k] = g->counts[k];
+    return SMC_OK;
+}
+
+int smc_read_groups_masks(smc_read_groups* g, const uint64_t* d_idents, int64_t n_ids, uint64_t seed, const uint64_t* thr, int32_t n_thr,
+                          uint32_t* d_masks, void* stream) {
+    if (!g || n_ids < 0 || n_ids >= (int64_t)0xFFFFFF00 || (n_ids && (!d_idents || !d_masks))) return fail(SMC_E_ARG, "smc_read_groups_masks: bad argument");
+    if (!g->finished) return fail(SMC_E_ARG, "smc_read_groups_masks: the table is not finished");
+    RgThr T;
+    { const int rc = rg_thresholds(thr, n_thr, T); if (rc) return rc; }
+    if (!n_ids || !n_thr) return SMC_OK;
+    HIPCHK(hipSetDevice(g->ctx->device));
+    const uint32_t n_words = (uint32_t)((n_ids + 31) / 32);
+    hipLaunchKernelGGL(k_rg_masks, dim3((unsigned)((n_ids + RG_BLOCK - 1) / RG_BLOCK)), dim3(RG_BLOCK), 0, (hipStream_t)stream, g->G,
+                       (const unsigned long long*)d_idents, (uint32_t)n_ids, (unsigned long long)seed, T, (int)n_thr, d_masks, n_words);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
+int smc_read_groups_kept(smc_read_groups* g, uint64_t seed, const uint64_t* thr, int32_t n_thr, int64_t* kept) {
+    if (!g || (n_thr && !kept)) return fail(SMC_E_ARG, "smc_read_groups_kept: bad argument");
+    if (!g->finished) return fail(SMC_E_ARG, "smc_read_groups_kept: the table is not finished");
+    RgThr T;
+    { const int rc = rg_thresholds(thr, n_thr, T); if (rc) return rc; }
+    if (!n_thr) return SMC_OK;
+    HIPCHK(hipSetDevice(g->ctx->device));
+    HIPCHK(hipMemsetAsync(g->d_kept, 0, 8 * SMC_RG_MAX_TARGETS, 0));
+    hipLaunchKernelGGL(k_rg_kept, dim3(rg_grid(g->G.n_mask + 1)), dim3(RG_BLOCK), 0, 0, g->G, (unsigned long long)seed, T, (int)n_thr, g->d_kept);
+    HIPCHK(hipGetLastError());
+    unsigned long long k[SMC_RG_MAX_TARGETS];
+    HIPCHK(hipMemcpy(k, g->d_kept, 8 * (size_t)n_thr, hipMemcpyDeviceToHost));
+    for (int t = 0; t < n_thr; ++t) kept[t] = (int64_t)k[t];
+    return SMC_OK;
+}
+
+int smc_read_groups_status(smc_read_groups* g, uint32_t* status) {
+    if (!g || !status) return fail(SMC_E_ARG, "smc_read_groups_status: bad argument");
+    *status = 0;
+    if (!g->mem) return SMC_OK;
+    HIPCHK(hipSetDevice(g->ctx->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(status, g->G.status, 4, hipMemcpyDeviceToHost));
+    return SMC_OK;
+}
+
+void smc_read_groups_destroy(smc_read_groups* g) {
+    if (!g) return;
+    if (hipSetDevice(g->ctx->device) == hipSuccess) {
+        (void)hipDeviceSynchronize();           // (a _masks launch on another stream may still read the table)
+        for (auto& c : g->chunks) (void)hipFree(c.d);
+        if (g->mem) (void)hipFree(g->mem);
+    }
+    delete g;
+}
+
 int smc_plan_set_timing(smc_plan* p, int slots) {
     if (!p || slots < 0) return fail(SMC_E_ARG, "smc_plan_set_timing: bad argument");
     HIPCHK(hipSetDevice(p->ctx->device));

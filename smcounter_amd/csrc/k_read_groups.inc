@@ -1,0 +1,233 @@
+// Included by smcounter_hip.hip (after k_philox_marks.inc: it uses smc_philox4x32_10).
+// ------------------------------------------------------------------------------------------
+// the read-level philox sampler of --dsRpb (smc_read_groups_*): a file-wide table of read names and barcodes in HBM
+// ------------------------------------------------------------------------------------------
+// ds.reads.withinMT.py:37-58 groups the placed records of the whole file by barcode: per barcode its distinct full read names in
+// order of first appearance, probKeep from the counts (one / multi / multi_names).  The reference then draws one Python 2 random()
+// per name in dict order; this sampler keeps a name when it is its barcode's first, or when word 0 of Philox4x32-10(counter =
+// (identity lo, identity hi, RG_DOMAIN, 0), key = (seed lo, seed hi)) < thr - a draw per name, so the kept sets of two targets are
+// nested and nothing depends on how the file is cut into runs.
+// The table: two power-of-two open-addressing tables (linear probing, load factor at most 0.5, sized from the placed-record count -
+// an upper bound of both the names and the barcodes), a 16-byte slot each {identity, check word, first ordinal}; a name slot also
+// has an info word, its barcode's slot (| RG_FIRST once it is known to be the barcode's first name).  Identity 0 marks an empty slot.
+// Launches (one stream):
+//   k_rg_init     empty slots
+//   k_rg_insert   per record: the barcode slot, then the name slot - a 64-bit CAS claims an empty slot, an atomic minimum keeps
+//                 the first ordinal; the claimant writes the check word (and, for a name, its barcode slot)
+//   k_rg_verify   per record, after every insert: the slots' check words and the name's barcode slot against the record's - a
+//                 difference is a hash collision (status bits; the host refuses the file)
+//   k_rg_link     per name slot: the barcode's name count; first name iff the name's first ordinal is the barcode's
+//   k_rg_reduce   per barcode slot: barcodes, one, multi, multi_names into 64-bit counters (names and first names by k_rg_link)
+//   k_rg_masks    per run: a wave of 64 read-name ids looks up its names and writes two mask words per target (the bit layout
+//                 smc_select_alignments_keyed takes at SMC_SEL_KEY_READ)
+//   k_rg_kept     per name slot: the kept names of every target, for the run log
+// Every probe loop ends after `capacity` steps: a full table sets RG_FULL and the record is dropped (not met: load <= 0.5).
+#define RG_BLOCK 256
+#define RG_DOMAIN 0x64735250u               // counter word 2 of the read draw ("dsRP"); SEL_DOMAIN "dsMT" is the barcode draw's
+#define RG_FIRST 0x80000000u                // (name info) the barcode's first name
+#define RG_NONE 0xFFFFFFFFu
+
+struct RgSlot {
+    unsigned long long key;                 // identity (FNV-1a 64 of the text); 0: empty
+    uint32_t chk;                           // check word (FNV-1a 32 of the same text)
+    uint32_t first;                         // smallest ordinal of the records with this key
+};
+static_assert(sizeof(RgSlot) == 16, "RgSlot is one 16-byte slot");
+
+struct RgTable {
+    RgSlot* name;
+    uint32_t* name_info;                    // barcode slot of the name | RG_FIRST
+    RgSlot* bc;
+    uint32_t* bc_cnt;                       // names per barcode
+    unsigned long long n_mask, b_mask;      // capacities - 1
+    uint32_t* status;                       // SMC_RG_* bits
+    unsigned long long* ctr;                // RG_C_* counters
+};
+#define RG_C_NAMES 0
+#define RG_C_BARCODES 1
+#define RG_C_ONE 2
+#define RG_C_MULTI 3
+#define RG_C_MULTI_NAMES 4
+#define RG_C_FIRST 5
+#define RG_N_CTR 8
+
+struct RgThr { unsigned long long t[SMC_RG_MAX_TARGETS]; };   // floor(probKeep * 2^32) per target, in [0, 2^32]
+
+__device__ __forceinline__ unsigned long long rg_hash(unsigned long long x) {   // (splitmix64's finaliser: the home slot)
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// claim or find the slot of `key`, keep the smallest ordinal; *claimed: this thread wrote the key.  RG_NONE: the table is full.
+__device__ __forceinline__ uint32_t rg_claim(RgSlot* __restrict__ T, unsigned long long mask, unsigned long long key, uint32_t chk,
+                                             uint32_t ord, bool& claimed) {
+    unsigned long long h = rg_hash(key) & mask;
+    claimed = false;
+    for (unsigned long long step = 0; step <= mask; ++step) {
+        RgSlot* s = T + h;
+        unsigned long long cur = __hip_atomic_load(&s->key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == 0ull) cur = atomicCAS(&s->key, 0ull, key);
+        if (cur == 0ull) {
+            s->chk = chk;
+            claimed = true;
+            atomicMin(&s->first, ord);
+            return (uint32_t)h;
+        }
+        if (cur == key) {
+            // (records come in file order: the slot's first ordinal is almost always below this one already - no atomic then)
+            if (ord < __hip_atomic_load(&s->first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&s->first, ord);
+            return (uint32_t)h;
+        }
+        h = (h + 1) & mask;
+    }
+    return RG_NONE;
+}
+
+// the slot of `key`, or RG_NONE (read-only: after the inserts)
+__device__ __forceinline__ uint32_t rg_find(const RgSlot* __restrict__ T, unsigned long long mask, unsigned long long key) {
+    unsigned long long h = rg_hash(key) & mask;
+    for (unsigned long long step = 0; step <= mask; ++step) {
+        const unsigned long long cur = T[h].key;
+        if (cur == key) return (uint32_t)h;
+        if (cur == 0ull) return RG_NONE;
+        h = (h + 1) & mask;
+    }
+    return RG_NONE;
+}
+
+// empty slots; first ordinals at the largest value (the atomic minimum brings them down)
+__global__ __launch_bounds__(RG_BLOCK) void k_rg_init(RgTable G) {
+    for (unsigned long long s = (unsigned long long)blockIdx.x * RG_BLOCK + threadIdx.x; s <= G.n_mask; s += (unsigned long long)gridDim.x * RG_BLOCK) {
+        G.name[s] = RgSlot{0ull, 0u, RG_NONE};
+        G.name_info[s] = 0u;
+    }
+    for (unsigned long long s = (unsigned long long)blockIdx.x * RG_BLOCK + threadIdx.x; s <= G.b_mask; s += (unsigned long long)gridDim.x * RG_BLOCK) {
+        G.bc[s] = RgSlot{0ull, 0u, RG_NONE};
+        G.bc_cnt[s] = 0u;
+    }
+}
+
+__global__ __launch_bounds__(RG_BLOCK) void k_rg_insert(RgTable G, const smc_read_key* __restrict__ keys, uint32_t n, uint32_t ord0) {
+    for (uint32_t i = blockIdx.x * RG_BLOCK + threadIdx.x; i < n; i += gridDim.x * RG_BLOCK) {
+        const smc_read_key k = keys[i];
+        if (k.name_id == 0ull || k.bc_id == 0ull) { atomicOr(G.status, SMC_RG_RESERVED); continue; }
+        bool claimed;
+        const uint32_t b = rg_claim(G.bc, G.b_mask, k.bc_id, k.bc_chk, ord0 + i, claimed);
+        if (b == RG_NONE) { atomicOr(G.status, SMC_RG_FULL); continue; }
+        const uint32_t s = rg_claim(G.name, G.n_mask, k.name_id, k.name_chk, ord0 + i, claimed);
+        if (s == RG_NONE) { atomicOr(G.status, SMC_RG_FULL); continue; }
+        if (claimed) G.name_info[s] = b;
+    }
+}
+
+__global__ __launch_bounds__(RG_BLOCK) void k_rg_verify(RgTable G, const smc_read_key* __restrict__ keys, uint32_t n) {
+    for (uint32_t i = blockIdx.x * RG_BLOCK + threadIdx.x; i < n; i += gridDim.x * RG_BLOCK) {
+        const smc_read_key k = keys[i];
+        if (k.name_id == 0ull || k.bc_id == 0ull) continue;
+        const uint32_t b = rg_find(G.bc, G.b_mask, k.bc_id), s = rg_find(G.name, G.n_mask, k.name_id);
+        if (b == RG_NONE || s == RG_NONE) continue;                // (full: reported by k_rg_insert)
+        if (G.bc[b].chk != k.bc_chk) atomicOr(G.status, SMC_RG_BARCODE_COLLISION);
+        // (one name identity whose records name two barcodes: two names behind it)
+        if (G.name[s].chk != k.name_chk || G.name_info[s] != b) atomicOr(G.status, SMC_RG_NAME_COLLISION);
+    }
+}
+
+__device__ __forceinline__ unsigned long long rg_wave_sum(unsigned long long v) {
+    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
+    return v;
+}
+
+// (grid-stride loops whose bound is wave-uniform: every lane of a wave takes part in each round's ballot / reduction)
+__global__ __launch_bounds__(RG_BLOCK) void k_rg_link(RgTable G) {
+    const unsigned long long n = G.n_mask + 1, stride = (unsigned long long)gridDim.x * RG_BLOCK;
+    const int lane = threadIdx.x & (WAVE - 1);
+    unsigned long long names = 0, firsts = 0;
+    for (unsigned long long w = ((unsigned long long)blockIdx.x * RG_BLOCK + threadIdx.x) - lane; w < n; w += stride) {
+        const unsigned long long s = w + lane;
+        bool used = false, first = false;
+        if (s < n && G.name[s].key != 0ull) {
+            const uint32_t b = G.name_info[s] & ~RG_FIRST;
+            used = true;
+            atomicAdd(&G.bc_cnt[b], 1u);
+            first = G.name[s].first == G.bc[b].first;
+            G.name_info[s] = b | (first ? RG_FIRST : 0u);
+        }
+        names += used; firsts += first;
+    }
+    names = rg_wave_sum(names); firsts = rg_wave_sum(firsts);
+    if (lane == 0) {
+        if (names) atomicAdd(&G.ctr[RG_C_NAMES], names);
+        if (firsts) atomicAdd(&G.ctr[RG_C_FIRST], firsts);
+    }
+}
+
+__global__ __launch_bounds__(RG_BLOCK) void k_rg_reduce(RgTable G) {
+    const unsigned long long n = G.b_mask + 1, stride = (unsigned long long)gridDim.x * RG_BLOCK;
+    const int lane = threadIdx.x & (WAVE - 1);
+    unsigned long long bcs = 0, one = 0, multi = 0, multi_names = 0;
+    for (unsigned long long w = ((unsigned long long)blockIdx.x * RG_BLOCK + threadIdx.x) - lane; w < n; w += stride) {
+        const unsigned long long s = w + lane;
+        if (s < n && G.bc[s].key != 0ull) {
+            const uint32_t c = G.bc_cnt[s];
+            bcs += 1; one += c == 1u; multi += c >= 2u; multi_names += c >= 2u ? c : 0u;
+        }
+    }
+    bcs = rg_wave_sum(bcs); one = rg_wave_sum(one); multi = rg_wave_sum(multi); multi_names = rg_wave_sum(multi_names);
+    if (lane == 0 && bcs) {
+        atomicAdd(&G.ctr[RG_C_BARCODES], bcs);
+        if (one) atomicAdd(&G.ctr[RG_C_ONE], one);
+        if (multi) atomicAdd(&G.ctr[RG_C_MULTI], multi);
+        if (multi_names) atomicAdd(&G.ctr[RG_C_MULTI_NAMES], multi_names);
+    }
+}
+
+__device__ __forceinline__ uint32_t rg_draw(unsigned long long id, unsigned long long seed) {
+    uint32_t x[4];
+    smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), RG_DOMAIN, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+    return x[0];
+}
+
+// masks[t * n_words + (g >> 5)] bit (g & 31): read-name id g is kept at target t.  One thread per id, a wave writes two words per
+// target; n_words = ceil(n_ids / 32) (the last wave's second word only when it exists).
+__global__ __launch_bounds__(RG_BLOCK) void k_rg_masks(RgTable G, const unsigned long long* __restrict__ ident, uint32_t n_ids,
+                                                       unsigned long long seed, RgThr T, int n_thr, uint32_t* __restrict__ masks,
+                                                       uint32_t n_words) {
+    const uint32_t g = blockIdx.x * RG_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & (WAVE - 1);
+    bool found = false, first = false;
+    uint32_t u = 0;
+    if (g < n_ids) {
+        const unsigned long long id = ident[g];
+        const uint32_t s = id ? rg_find(G.name, G.n_mask, id) : RG_NONE;
+        if (s == RG_NONE) atomicOr(G.status, SMC_RG_MISS);
+        else { found = true; first = (G.name_info[s] & RG_FIRST) != 0u; u = rg_draw(id, seed); }
+    }
+    const uint32_t word = (g - lane) >> 5;             // the wave's first word
+    for (int t = 0; t < n_thr; ++t) {
+        const unsigned long long m = __ballot(found && (first || (unsigned long long)u < T.t[t]));
+        if (lane == 0) {
+            if (word < n_words) masks[(size_t)t * n_words + word] = (uint32_t)m;
+            if (word + 1 < n_words) masks[(size_t)t * n_words + word + 1] = (uint32_t)(m >> 32);
+        }
+    }
+}
+
+__global__ __launch_bounds__(RG_BLOCK) void k_rg_kept(RgTable G, unsigned long long seed, RgThr T, int n_thr, unsigned long long* __restrict__ kept) {
+    const unsigned long long n = G.n_mask + 1, stride = (unsigned long long)gridDim.x * RG_BLOCK;
+    const int lane = threadIdx.x & (WAVE - 1);
+    for (unsigned long long w = ((unsigned long long)blockIdx.x * RG_BLOCK + threadIdx.x) - lane; w < n; w += stride) {
+        const unsigned long long s = w + lane;
+        bool used = false, first = false;
+        uint32_t u = 0;
+        if (s < n && G.name[s].key != 0ull) {
+            used = true;
+            first = (G.name_info[s] & RG_FIRST) != 0u;
+            u = rg_draw(G.name[s].key, seed);
+        }
+        for (int t = 0; t < n_thr; ++t) {
+            const unsigned long long m = __ballot(used && (first || (unsigned long long)u < T.t[t]));
+            if (lane == 0 && m) atomicAdd(&kept[t], (unsigned long long)__popcll(m));
+        }
+    }
+}

@@ -200,6 +200,8 @@ struct Aln {
     uint8_t oflag;
 };
 
+struct NamePass;                       // (the whole-file pass of smc_bam_name_keys, below)
+
 struct Bam {
     FILE* fh = nullptr;
     const uint8_t* map = nullptr;      // the file, mapped (the block stream inflates straight from the page cache; nullptr: pread into `comp`)
@@ -241,6 +243,7 @@ struct Bam {
     std::vector<uint32_t> d_pair_rep;
     int32_t d_pair_shared = 0;         // (with d_pair_rep) 1: some read-name id covers two different full query names
     std::string d_pair_text;           // (smc_bam_pair_name's answer)
+    NamePass* name_pass = nullptr;     // smc_bam_name_keys' stream over the whole file, between two of its chunks
 
     bool load_block(uint64_t coff) {
         if (fseeko(fh, (off_t)coff, SEEK_SET) != 0) return false;
@@ -1056,6 +1059,52 @@ static void take_spare(Bam& b) {
     keep_larger(b.d_reads, S.reads); keep_larger(b.parsed, S.parsed);
 }
 
+// ---- the whole-file pass of the read-level philox sampler (smc_bam_name_keys): every placed record's name and barcode keys
+// The identity of a text is its FNV-1a (64 bits) - what smc_bam_barcode_idents / smc_bam_pair_idents compute; its check word a
+// second, independent hash of the same text: FNV-1a with 32 bits (offset basis 2166136261, prime 16777619).  Two texts with one
+// identity and different check words are a collision the device table reports (devplanes.check32_array restates this one).
+inline uint64_t text_ident(const char* p, size_t n) {
+    uint64_t x = 1469598103934665603ull;
+    for (size_t i = 0; i < n; ++i) { x ^= (unsigned char)p[i]; x *= 1099511628211ull; }
+    return x;
+}
+inline uint32_t text_check(const char* p, size_t n) {
+    uint32_t x = 2166136261u;
+    for (size_t i = 0; i < n; ++i) { x ^= (unsigned char)p[i]; x *= 16777619u; }
+    return x;
+}
+// the barcode of a read name: field -2 of the name stripped of white space, split at ':' (tools.ds_mt.barcode_of, ds.mt.py:43-45);
+// false: the name has no such field (the reference stops there with an IndexError)
+inline bool barcode_field(const char* p, size_t n, const char*& bp, size_t& bn) {
+    auto space = [](unsigned char c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 0x1c && c <= 0x1f); };   // (str.isspace, ASCII)
+    size_t a = 0, e = n;
+    while (a < e && space((unsigned char)p[a])) ++a;
+    while (e > a && space((unsigned char)p[e - 1])) --e;
+    size_t c1 = e;                                  // the last ':' and the one before it
+    while (c1 > a && p[c1 - 1] != ':') --c1;
+    if (c1 == a) return false;
+    --c1;
+    size_t c0 = c1;
+    while (c0 > a && p[c0 - 1] != ':') --c0;
+    bp = p + c0; bn = c1 - c0;
+    return true;
+}
+
+struct NamePass {
+    BlockStream bs;
+    int64_t ordinal = 0;                            // placed records handed out so far
+    double t_walk = 0, t_hash = 0;                  // ms, for SMC_BAM_TIMING
+    NamePass(Bam& b, int nthreads) : bs(b, b.first_record, nthreads) {}
+};
+
+static void name_pass_end(Bam& b) {
+    if (!b.name_pass) return;
+    b.name_pass->bs.data.swap(b.rec_data);         // (the stream's buffer back to the handle: its pages stay for the next run)
+    b.rec_data.n = 0;
+    delete b.name_pass;
+    b.name_pass = nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1120,6 +1169,7 @@ int smc_bam_open(const char* path, void** out) {
 void smc_bam_close(void* h) {
     Bam* b = (Bam*)h;
     if (!b) return;
+    name_pass_end(*b);
     if (b->map) munmap((void*)b->map, b->map_len);
     b->map = nullptr;
     if (b->fh) fclose(b->fh);
@@ -1677,6 +1727,86 @@ const char* smc_bam_pair_name(void* h, int32_t gid) {
     const bool ok = gid >= 0 && (size_t)gid < b.d_pair_rep.size() && b.d_pair_rep[(size_t)gid] != 0xFFFFFFFFu;
     b.d_pair_text = ok ? std::string(b.d_reads[b.d_pair_rep[(size_t)gid]].qname) : std::string();
     return b.d_pair_text.c_str();
+}
+
+// The whole-file pass of --dsRpbSampler philox (see smcounter_host.h): the BGZF blocks inflated by the pool as a run's are, the
+// records walked in order, the names of every 64 K of them hashed by the pool.  Only the name is read of a record.  Consumed bytes
+// are dropped after every 64 K records, so the pass holds that many records and one refill, never the file.
+int64_t smc_bam_name_keys(void* h, int32_t restart, int64_t cap, int32_t nthreads, uint64_t* out, int64_t* first_ordinal) {
+    Bam& b = *(Bam*)h;
+    if (cap <= 0 || !out) { b.err = "smc_bam_name_keys: bad argument"; return -1; }
+    if (restart || !b.name_pass) {
+        name_pass_end(b);
+        // (the stream takes the handle's record buffer: the last run's alignments, views into it, are dropped)
+        b.d_reads.clear(); b.d_bc_names.clear(); b.d_pair_rep.clear(); b.d_n_pair = 0; b.d_pair_shared = 0;
+        b.err.clear();
+        b.name_pass = new NamePass(b, nthreads < 1 ? 1 : nthreads);
+    }
+    NamePass& np = *b.name_pass;
+    BlockStream& bs = np.bs;
+    bs.nthreads = nthreads < 1 ? 1 : nthreads;
+    if (first_ordinal) *first_ordinal = np.ordinal;
+    const size_t PIECE = 65536;
+    std::vector<size_t> at;
+    at.reserve((size_t)std::min<int64_t>(cap, (int64_t)PIECE));
+    int64_t done = 0;
+    bool end = false;
+    while (done < cap && !end) {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (bs.pos > 0) {                           // drop what was consumed
+            const size_t keep = bs.data.size() - bs.pos;
+            memmove(bs.data.data(), bs.data.data() + bs.pos, keep);
+            bs.data.n = keep;
+            bs.pos = 0;
+            bs.blocks.clear();
+        }
+        // 1. the walk: the body offsets of the next placed records (offsets: a refill may move the buffer)
+        at.clear();
+        const size_t want = (size_t)std::min<int64_t>(cap - done, (int64_t)PIECE);
+        while (at.size() < want) {
+            size_t n = 0;
+            const uint8_t* p = bs.next_record(n);
+            if (!p) { end = true; break; }
+            if (n < 32) { b.err = "truncated BAM record"; return -2; }
+            int32_t tid; memcpy(&tid, p, 4);
+            if (tid >= 0) {
+                if (32 + (size_t)p[8] > n) { b.err = "truncated BAM record"; return -2; }
+                at.push_back((size_t)(p - bs.data.data()));
+            }
+        }
+        if (!b.err.empty()) return -2;              // (an inflate or block error ended the stream early)
+        const auto t1 = std::chrono::steady_clock::now();
+        // 2. the keys, by the pool: name identity, barcode identity, the two check words
+        const size_t nr = at.size();
+        uint64_t* o = out + 3 * done;
+        std::atomic<int> bad(0);
+        const int K = (int)std::max<size_t>(1, std::min<size_t>((size_t)bs.nthreads, nr >> 12));
+        const uint8_t* base = bs.data.data();
+        Pool::get().run(K, bs.nthreads, [&](int k) {
+            for (size_t i = nr * (size_t)k / (size_t)K; i < nr * (size_t)(k + 1) / (size_t)K; ++i) {
+                const uint8_t* p = base + at[i];
+                const char* q = (const char*)p + 32;
+                const size_t ln = p[8] ? (size_t)p[8] - 1 : 0;
+                const char* bp; size_t bn;
+                if (!barcode_field(q, ln, bp, bn)) { bad = 1; continue; }
+                o[3 * i] = text_ident(q, ln);
+                o[3 * i + 1] = text_ident(bp, bn);
+                o[3 * i + 2] = (uint64_t)text_check(q, ln) | (uint64_t)text_check(bp, bn) << 32;
+            }
+        });
+        if (bad.load()) { b.err = "a placed read name has no barcode field (field -2 of the name split at ':')"; return -3; }
+        done += (int64_t)nr;
+        np.t_walk += std::chrono::duration<double, std::milli>(t1 - t0).count();
+        np.t_hash += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    }
+    np.ordinal += done;
+    if (done == 0) {
+        if (exp_env("SMC_BAM_TIMING"))
+            fprintf(stderr, "smc_bam_name_keys: %lld placed records: read %.1f ms, inflate %.1f ms, walk %.1f ms (inflate included), keys %.1f ms\n",
+                    (long long)np.ordinal, bs.t_read, bs.t_inflate, np.t_walk, np.t_hash);
+        name_pass_end(b);
+    }
+    return done;
 }
 
 }  // extern "C"

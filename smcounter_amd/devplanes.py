@@ -327,6 +327,7 @@ def iter_resident_batches(path: str, fasta, loci: Sequence[Tuple[str, str]], par
                 yield first, [rb] + [d.batch(rb) for d in ds]
     finally:
         bam.close()
+        close_rules(ds_rules)            # (--dsRpbSampler philox: the file-wide table in HBM - on the last batch, or on an error)
 
 
 class _DsBatch(object):
@@ -366,76 +367,112 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
     nl = A["nl"]
     res = []
     idents = names = p_idents = p_names = None
-    for rule, d in zip(rules, ds):
-        if not nl:
-            res.append((0, 0, np.zeros(0, LOCUS_DTYPE), []))
-            continue
-        if rule.level == "read":
-            # (--dsRpb: the kept read names, by read-name id - an id must stand for one full name, or the rule cannot be applied)
-            if p_idents is None:
-                p_idents, shared = bam.pair_idents(A["n_pair"])
-                if shared:
-                    raise bamio.BamError("--dsRpb: the run %s:%d-%d has a read id (read name without its last field) shared by two "
-                                         "different read names: ds.reads.withinMT.py keeps whole names, the decoder's ids cannot tell "
-                                         "them apart" % (chrom, lo + 1, lo + nl))
-            if rule.kept_idents is not None:
-                mask = np.isin(p_idents, rule.kept_idents)
+    d_masks = {}                     # (philox read rules) id(table) -> (device masks of all its rules, words per mask, id(rule) -> index)
+    try:
+        for rule, d in zip(rules, ds):
+            if not nl:
+                res.append((0, 0, np.zeros(0, LOCUS_DTYPE), []))
+                continue
+            if rule.level == "read":
+                # (--dsRpb: the kept read names, by read-name id - an id must stand for one full name, or the rule cannot be applied)
+                if p_idents is None:
+                    p_idents, shared = bam.pair_idents(A["n_pair"])
+                    if shared:
+                        raise bamio.BamError("--dsRpb: the run %s:%d-%d has a read id (read name without its last field) shared by two "
+                                             "different read names: ds.reads.withinMT.py keeps whole names, the decoder's ids cannot tell "
+                                             "them apart" % (chrom, lo + 1, lo + nl))
+                if rule.groups is not None:
+                    # (--dsRpbSampler philox: the masks of every target from the file-wide table, one launch per run)
+                    if id(rule.groups) not in d_masks:
+                        d_masks[id(rule.groups)] = _run_read_masks(eng, rule.groups, [r for r in rules if r.groups is rule.groups],
+                                                                   p_idents, chrom, lo, nl)
+                    buf, n_words, index = d_masks[id(rule.groups)]
+                    sel, counts, d_orig = select_run(eng, up, A, lo, d_mask=buf.data_ptr() + 4 * n_words * index[id(rule)], level="read")
+                else:
+                    if rule.kept_idents is not None:
+                        mask = np.isin(p_idents, rule.kept_idents)
+                    else:
+                        if p_names is None:
+                            p_names = [bam.pair_name(g) for g in range(int(A["n_pair"]))]
+                        mask = np.array([t in rule.kept for t in p_names], bool)
+                    sel, counts, d_orig = select_run(eng, up, A, lo, mask=mask, level="read")
+            elif rule.kept is None:
+                if idents is None:
+                    idents = bam.barcode_idents(A["n_bc"])
+                sel, counts, d_orig = select_run(eng, up, A, lo, idents=idents, frac=rule.frac, seed=rule.seed)
             else:
-                if p_names is None:
-                    p_names = [bam.pair_name(g) for g in range(int(A["n_pair"]))]
-                mask = np.array([t in rule.kept for t in p_names], bool)
-            sel, counts, d_orig = select_run(eng, up, A, lo, mask=mask, level="read")
-        elif rule.kept is None:
-            if idents is None:
-                idents = bam.barcode_idents(A["n_bc"])
-            sel, counts, d_orig = select_run(eng, up, A, lo, idents=idents, frac=rule.frac, seed=rule.seed)
-        else:
-            if idents is None:
-                idents = bam.barcode_idents(A["n_bc"])
-            if rule.kept_idents is not None:
-                mask = np.isin(idents, rule.kept_idents)
-            else:
-                if names is None:
-                    names = [bam.barcode_name(g) for g in range(int(A["n_bc"]))]
-                mask = np.array([t in rule.kept for t in names], bool)
-            sel, counts, d_orig = select_run(eng, up, A, lo, mask=mask)
-        got = {}
+                if idents is None:
+                    idents = bam.barcode_idents(A["n_bc"])
+                if rule.kept_idents is not None:
+                    mask = np.isin(idents, rule.kept_idents)
+                else:
+                    if names is None:
+                        names = [bam.barcode_name(g) for g in range(int(A["n_bc"]))]
+                    mask = np.array([t in rule.kept for t in names], bool)
+                sel, counts, d_orig = select_run(eng, up, A, lo, mask=mask)
+            got = {}
 
-        def orig_index(d_orig=d_orig, kept=sel.n_aln, got=got):
-            if "orig" not in got:
-                got["orig"] = d_orig.download(np.uint32, kept)
-            return got["orig"]
+            def orig_index(d_orig=d_orig, kept=sel.n_aln, got=got):
+                if "orig" not in got:
+                    got["orig"] = d_orig.download(np.uint32, kept)
+                return got["orig"]
 
-        def allele_key(ai, qpos, indel, orig_index=orig_index):
-            # (the builder's alignment index counts the KEPT alignments: the decoder's records are those of the full run)
-            return bam.allele_key(int(orig_index()[int(ai)]), qpos, indel)
-        bc_name, bc_idents = bam.barcode_name, bam.barcode_idents
-        if rule.level == "read":
-            # (the read level renumbers the kept barcodes by first kept appearance: the texts the cap samplers need are the decoder's,
-            # by the old id of every new one - the old ids of the kept alignments in order, each at its first appearance)
-            def old_bc(orig_index=orig_index, got=got, bc=A["aln"]["bc_gid"]):
-                if "old_bc" not in got:
-                    old = bc[orig_index()]
-                    got["old_bc"] = old[np.sort(np.unique(old, return_index=True)[1])]
-                return got["old_bc"]
-            bc_name = lambda g, old_bc=old_bc: bam.barcode_name(int(old_bc()[int(g)]))
-            bc_idents = lambda n, old_bc=old_bc: bam.barcode_idents(A["n_bc"])[old_bc()]
-        w = d.words
-        done = build_run(counts, L, eng, abi.c_params(rule.params), rule.params, chrom, lo, fasta, run_ref, [w] + d.planes, d.uaux,
-                         d.slots, d.slots + n_loc, cap, max_depth, allele_key, bc_name, sampler=sampler, sampler_seed=sampler_seed,
-                         barcode_idents=bc_idents, uploaded=sel)
-        sel.free(shared=False)
-        d_orig.free()
-        if done is None:
-            raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "%s: the device builder does not take it" % rule.label, rule.flag))
-        if done == NARROW:
-            return False
-        res.append(done)
+            def allele_key(ai, qpos, indel, orig_index=orig_index):
+                # (the builder's alignment index counts the KEPT alignments: the decoder's records are those of the full run)
+                return bam.allele_key(int(orig_index()[int(ai)]), qpos, indel)
+            bc_name, bc_idents = bam.barcode_name, bam.barcode_idents
+            if rule.level == "read":
+                # (the read level renumbers the kept barcodes by first kept appearance: the texts the cap samplers need are the decoder's,
+                # by the old id of every new one - the old ids of the kept alignments in order, each at its first appearance)
+                def old_bc(orig_index=orig_index, got=got, bc=A["aln"]["bc_gid"]):
+                    if "old_bc" not in got:
+                        old = bc[orig_index()]
+                        got["old_bc"] = old[np.sort(np.unique(old, return_index=True)[1])]
+                    return got["old_bc"]
+                bc_name = lambda g, old_bc=old_bc: bam.barcode_name(int(old_bc()[int(g)]))
+                bc_idents = lambda n, old_bc=old_bc: bam.barcode_idents(A["n_bc"])[old_bc()]
+            w = d.words
+            done = build_run(counts, L, eng, abi.c_params(rule.params), rule.params, chrom, lo, fasta, run_ref, [w] + d.planes, d.uaux,
+                             d.slots, d.slots + n_loc, cap, max_depth, allele_key, bc_name, sampler=sampler, sampler_seed=sampler_seed,
+                             barcode_idents=bc_idents, uploaded=sel)
+            sel.free(shared=False)
+            d_orig.free()
+            if done is None:
+                raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "%s: the device builder does not take it" % rule.label, rule.flag))
+            if done == NARROW:
+                return False
+            res.append(done)
+    finally:
+        for buf, _, _ in d_masks.values():
+            buf.free()
     for d, (nl_k, ns_k, lc, tb) in zip(ds, res):
         d.LC.append(lc)
         d.tables += tb
         d.slots += ns_k
     return True
+
+
+def _run_read_masks(eng, groups, rules, p_idents, chrom, lo, nl):
+    """One launch for a run: the keep masks of every philox read rule of one table over the run's read-name identities ->
+    (device buffer, words per mask, {id(rule): index}).  An identity the table does not hold (it cannot happen) ends the run."""
+    from .engine import DevBuf
+    n = len(p_idents)
+    n_words = (n + 31) // 32
+    d_id = DevBuf(eng, 8 * max(1, n) + 256).upload(np.ascontiguousarray(p_idents, np.uint64) if n else np.zeros(1, np.uint64))
+    buf = DevBuf(eng, 4 * max(1, n_words * len(rules)) + 256)
+    try:
+        groups.masks(d_id.data_ptr(), n, rules[0].seed, [r.thr for r in rules], buf.data_ptr())
+        st = groups.status()
+    except BaseException:
+        buf.free()
+        raise
+    finally:
+        d_id.free()
+    if st & RG_MISS:
+        buf.free()
+        raise bamio.BamError("--dsRpbSampler philox: the run %s:%d-%d has a read name the file-wide table does not hold (status %#x)"
+                             % (chrom, lo + 1, lo + nl, st))
+    return buf, n_words, {id(r): k for k, r in enumerate(rules)}
 
 
 def build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, planes, uaux, slot_base, umi_base, cap, max_depth,
@@ -607,10 +644,19 @@ class DsRule:
     target: float = None
     prob_keep: float = None
     n_names: int = 0
+    # (--dsRpbSampler philox) `groups`: the file-wide ReadGroups table in HBM (kept is None), `thr` = floor(probKeep x 2^32) clamped
+    # to [0, 2^32], `n_kept` the names it keeps
+    groups: object = None
+    thr: int = None
+    n_kept: int = None
 
     @property
     def flag(self) -> str:
         return "--dsRpb" if self.level == "read" else "--dsMT"
+
+    @property
+    def sampler(self) -> str:
+        return "philox" if self.kept is None else "reference"
 
     @property
     def label(self) -> str:
@@ -662,6 +708,145 @@ def reference_read_rules(path: str, targets, params_list, seed: int):
     return rules
 
 
+RPB_DOMAIN = 0x64735250        # counter word 2 of the read-level philox draw (k_read_groups.inc: RG_DOMAIN, "dsRP")
+RG_NAME_COLLISION, RG_BARCODE_COLLISION, RG_FULL, RG_MISS, RG_RESERVED = 1, 2, 4, 8, 16      # smc_read_groups_status bits
+RG_MAX_TARGETS = 32
+NAME_KEY_CHUNK = 1 << 20       # placed records per chunk of the file pass (24 MB of keys on the host)
+
+
+class ReadGroups(object):
+    """The file-wide read-name / barcode table of --dsRpbSampler philox in HBM (smc_read_groups_*, csrc/k_read_groups.inc): records
+    added in chunks (bamio.NativeBam.name_keys), grouped by finish(), then masks per run and kept counts per target.  close() frees it
+    (idempotent)."""
+
+    COUNTS = ("records", "names", "barcodes", "one", "multi", "multi_names", "first_names")
+
+    def __init__(self, eng):
+        self.eng, self.L = eng, eng.L
+        h = ctypes.c_void_p()
+        _lib.check(self.L.smc_read_groups_create(eng.ctx, ctypes.byref(h)), "smc_read_groups_create")
+        self._h = h
+
+    def add(self, keys, first_ordinal: int):
+        """uint64 [n, 3] keys of consecutive placed records (smc_bam_name_keys' layout = smc_read_key), the first one's ordinal."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        _lib.check(self.L.smc_read_groups_add(self._h, keys.ctypes.data, len(keys), int(first_ordinal)), "smc_read_groups_add")
+
+    def finish(self) -> dict:
+        c = np.zeros(8, np.int64)
+        _lib.check(self.L.smc_read_groups_finish(self._h, c.ctypes.data), "smc_read_groups_finish")
+        return dict(zip(self.COUNTS, (int(v) for v in c)))
+
+    @staticmethod
+    def _thr(thr):
+        t = np.ascontiguousarray(thr, np.uint64)
+        if len(t) > RG_MAX_TARGETS:
+            raise ValueError("at most %d --dsRpb targets with the philox sampler" % RG_MAX_TARGETS)
+        return t
+
+    def masks(self, d_idents, n_ids: int, seed: int, thr, d_masks):
+        """Per read-name identity (device pointer, n_ids of them) a keep bit per target into d_masks: len(thr) masks of
+        ceil(n_ids / 32) words, smc_select_alignments_keyed's read-level layout."""
+        t = self._thr(thr)
+        _lib.check(self.L.smc_read_groups_masks(self._h, d_idents, int(n_ids), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                                t.ctypes.data, len(t), d_masks, ctypes.c_void_p(0)), "smc_read_groups_masks")
+
+    def kept(self, seed: int, thr) -> list:
+        t = self._thr(thr)
+        k = np.zeros(max(1, len(t)), np.int64)
+        _lib.check(self.L.smc_read_groups_kept(self._h, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), t.ctypes.data, len(t),
+                                               k.ctypes.data), "smc_read_groups_kept")
+        return [int(v) for v in k[:len(t)]]
+
+    def status(self) -> int:
+        st = ctypes.c_uint32(0)
+        _lib.check(self.L.smc_read_groups_status(self._h, ctypes.byref(st)), "smc_read_groups_status")
+        return int(st.value)
+
+    def close(self):
+        if self._h:
+            self.L.smc_read_groups_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def read_threshold(prob: float) -> int:
+    """floor(probKeep x 2^32) clamped to [0, 2^32]: probKeep >= 1 keeps every name, <= 0 only the barcodes' first names."""
+    if not prob > 0.0:
+        return 0
+    return min(1 << 32, int(np.floor(prob * 4294967296.0)))
+
+
+def philox_read_rules(path: str, targets, params_list, seed: int, eng, chunk: int = NAME_KEY_CHUNK, nthreads: int = 0):
+    """DsRules of --dsRpb --dsRpbSampler philox: the whole file's placed records streamed (bamio.NativeBam.name_keys, `chunk` records
+    at a time) into one ReadGroups table in HBM, its counters back on the host, probKeep per target from them in double exactly as
+    ds.reads.withinMT.py:58 computes it; a name is kept when it is its barcode's first or its philox draw falls below
+    floor(probKeep x 2^32) - NOT the reference's sample.  The rules share the table (rule.groups); iter_resident_batches frees it when
+    it ends.  ValueError: a hash collision (two texts behind one identity), or a file without a barcode of two or more names."""
+    groups = ReadGroups(eng)
+    try:
+        bam = bamio.NativeBam(path)
+        try:
+            for first, keys in bam.name_keys(chunk, nthreads):
+                groups.add(keys, first)
+        finally:
+            bam.close()
+        c = groups.finish()
+        st = groups.status()
+        if st:
+            what = [w for b, w in ((RG_NAME_COLLISION, "two read names share a 64-bit name identity"),
+                                   (RG_BARCODE_COLLISION, "two barcodes share a 64-bit identity"),
+                                   (RG_FULL, "the table is full"), (RG_RESERVED, "a name or barcode hashes to the reserved identity 0"))
+                    if st & b]
+            raise ValueError("--dsRpbSampler philox: %s: %s; the philox read sampler refuses the file (use --dsRpbSampler reference)"
+                             % (path, ", ".join(what) or "status %#x" % st))
+        one, multi, multi_names = c["one"], c["multi"], c["multi_names"]
+        rules = []
+        for r, P in zip(targets, params_list):
+            if multi_names == multi:
+                raise ValueError("--dsRpb %g: %s has no barcode with more than one read name, so ds.reads.withinMT.py's probKeep "
+                                 "(:58) is not defined (it divides by zero)" % (r, path))
+            prob = 1.0 * (float(r) - 1.0) * (one + multi) / (multi_names - multi)
+            rules.append(DsRule(1.0, P, kept=None, seed=int(seed), level="read", target=float(r), prob_keep=prob,
+                                n_names=c["names"], groups=groups, thr=read_threshold(prob)))
+        for rule, k in zip(rules, groups.kept(seed, [rule.thr for rule in rules])):
+            rule.n_kept = k
+        groups.counts = c
+        return rules
+    except BaseException:
+        groups.close()
+        raise
+
+
+def close_rules(rules):
+    """Free the device tables the rules hold (philox read rules); idempotent."""
+    for rule in rules or ():
+        if getattr(rule, "groups", None) is not None:
+            rule.groups.close()
+
+
+def check32_array(texts) -> np.ndarray:
+    """FNV-1a (32 bits) of every text: the check word smc_bam_name_keys writes beside each identity (smcounter_host.h)."""
+    b = [t.encode() for t in texts]
+    n = len(b)
+    x = np.full(n, 2166136261, np.uint32)
+    if not n:
+        return x
+    lens = np.fromiter(map(len, b), np.int64, n)
+    m = np.array(b, dtype="S%d" % max(1, int(lens.max()))).view(np.uint8).reshape(n, -1)
+    prime = np.uint32(16777619)
+    with np.errstate(over="ignore"):
+        for k in range(m.shape[1]):
+            live = lens > k
+            x[live] = (x[live] ^ m[live, k].astype(np.uint32)) * prime
+    return x
+
+
 def fnv64_array(texts) -> np.ndarray:
     """FNV-1a (64 bits) of every text, vectorised: what smc_bam_barcode_idents / smc_bam_pair_idents compute for a run's ids."""
     b = [t.encode() for t in texts]
@@ -695,12 +880,14 @@ def philox_keep_host(L, idents, frac: float, seed: int) -> np.ndarray:
     return keep
 
 
-def select_run(eng, up: RunOnDevice, A, lo: int, mask=None, idents=None, frac: float = 1.0, seed: int = 0, level: str = "barcode"):
+def select_run(eng, up: RunOnDevice, A, lo: int, mask=None, idents=None, frac: float = 1.0, seed: int = 0, level: str = "barcode",
+               d_mask=None):
     """smc_select_alignments: the run `up` (A: its counts) reduced to the kept barcodes' alignments -> (RunOnDevice of the kept ones,
     sharing the pools and the reference; counts dict for build_run; device buffer of orig_index).  `mask`: bool per run-wide barcode
     id (the host's set); else `idents` (uint64 per id) and the philox rule at `frac` / `seed`.  level "read"
     (smc_select_alignments_keyed, SMC_SEL_KEY_READ): the same per run-wide read-name id - whole read names kept or dropped - and the
-    kept alignments' ids renumbered by first kept appearance (the decoder's numbering of the down-sampled BAM)."""
+    kept alignments' ids renumbered by first kept appearance (the decoder's numbering of the down-sampled BAM).  `d_mask`: the mask
+    (bit per id) in HBM already (a device address: ReadGroups.masks wrote it)."""
     from .engine import DevBuf
     L = eng.L
     nl, n = A["nl"], up.n_aln
@@ -713,7 +900,9 @@ def select_run(eng, up: RunOnDevice, A, lo: int, mask=None, idents=None, frac: f
     d_loc = DevBuf(eng, 16 * max(1, nl) + 256)
     d_sum = DevBuf(eng, 256)
     d_rule = None
-    if mask is not None:
+    if d_mask is not None:
+        mptr, iptr = int(d_mask), None
+    elif mask is not None:
         words = np.packbits(np.asarray(mask, bool)[:n_ids], bitorder="little")
         words = np.concatenate([words, np.zeros((-len(words)) % 4 + 4, np.uint8)]).view(np.uint32)
         d_rule = DevBuf(eng, words.nbytes + 256).upload(words)
@@ -734,7 +923,8 @@ def select_run(eng, up: RunOnDevice, A, lo: int, mask=None, idents=None, frac: f
         _lib.check(L.smc_select_alignments(eng.ctx, up.aln.data_ptr(), n, up.loc.data_ptr(), nl, int(lo), mptr, iptr, n_ids, *tail),
                    "smc_select_alignments")
     kept, deepest, slots = (int(v) for v in d_sum.download(np.uint32, 3))
-    d_rule.free()
+    if d_rule is not None:
+        d_rule.free()
     sel = RunOnDevice(d_out, up.cig, up.bq, d_loc, up.ref, kept, None)
     counts = dict(nl=nl, n_slots=slots, n_bc=A["n_bc"], n_pair=A["n_pair"], status=A["status"], deepest=deepest, aln=None)
     if A["status"] & 1:

@@ -22,7 +22,12 @@ The timed region is EXACTLY --steps steps, in --blocks blocks (default 1) betwee
 `--dump-outputs DIR` writes the rows the last timed step returned as float64 .npy files (dump_rows).
 
 Prints ONE JSON line on rank 0: value = loci of all ranks / max-over-ranks time; roofline = the bytes the step's dominant kernel
-(the walk that writes the read words) has to move per launch over its mean HIP-event duration, against 8 TB/s; cpu_baseline =
+(the walk that writes the read words) has to move per launch over its mean HIP-event duration (HIP events of the timed steps),
+against 8 TB/s.  That is all a plain run does: set up, warm up, time the steps, --dump-outputs, the line.
+
+`--full` adds what takes runs of its own or checks the run, outside the timed region (--no-cpu-baseline, --no-parity and
+--no-other-configs leave parts of it out): gather_check (N > 1: what rank 0 received against what every rank sent);
+step_breakdown's ms_per_step_one_at_a_time and k_call_v2_ms; the same run in the other read-word width; cpu_baseline =
 CPU legs timed on a bounded sample of the same workload (rank 0, N = 1 only; inputs made before the clock starts); parity = EVERY
 row of the run against the CPU (oracle/aln_planes.c + oracle/smc_oracle.c from the same alignments), with the number of loci
 whose order-dependent fields were excused, the loci that reached filterVariants, the Fisher tests run and the largest p-value
@@ -67,9 +72,14 @@ def parse_args(argv=None):
     ap.add_argument("--config", default="C3", help="synthetic config (C2, C3, C5, C4); C3 is the metric's")
     ap.add_argument("--loci-per-gpu", type=int, default=0, help="override (default: the config's size)")
     ap.add_argument("--chunk", type=int, default=25000, help="loci generated / checked per chunk")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the every-row checks against the CPU")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip consumer_only and the C2 / C5 / X3 / EX one-liners")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the bench measures or checks: the CPU baselines, the every-row checks "
+                         "against the CPU, the other shapes and the other read-word width, the locus kernels timed alone, the step "
+                         "one at a time, the gather check (N > 1).  Default: the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the every-row checks against the CPU")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without consumer_only, the C2 / C5 / X3 / EX one-liners "
+                                                                    "and the other read-word width")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: the config's loci PER GPU (default, the driver's scaling run); strong: the config's loci in total, "
                          "sharded over the ranks (e.g. --config C4: 1 M loci; fits one MI355X too)")
@@ -324,7 +334,7 @@ def main():
     from smcounter_amd import abi, synth
     # The CPU leg runs FIRST, before this process touches the GPU: it starts worker processes.
     cpu = None
-    if world == 1 and not a.no_cpu_baseline:
+    if world == 1 and a.full and not a.no_cpu_baseline:
         cpu = cpu_leg(a)
     import torch
     import torch.distributed as dist
@@ -429,9 +439,9 @@ def main():
     L.smc_build_set_timing(eng.ctx, 0)
     step_s = sorted(blocks)[len(blocks) // 2]                    # the block with the median time per step
     # what rank 0 received in the last step against what every rank sent (outside the timed region): a 64-bit sum over each
-    # rank's last buffer, compared with the sum over the block rank 0 holds for that rank
+    # rank's last buffer, compared with the sum over the block rank 0 holds for that rank (--full)
     gather_check = None
-    if gather:
+    if gather and a.full:
         b_last = (pipe.n - 1) % len(pipe.bufs)
         csum = lambda t: t.view(torch.int32).sum(dtype=torch.int64).reshape(1)
         mine = csum(pipe.bufs[b_last])
@@ -456,26 +466,27 @@ def main():
             last_rows = pipe.bufs[b_last].cpu().numpy().view(abi.ROW_DTYPE)
         dumped = dump_rows(last_rows, a.dump_outputs)
         del last_rows
-    # the locus kernels of the same planes, timed alone with one more plan (outside the timed region)
-    if slot_streams is not None:
-        torch.cuda.set_stream(torch.cuda.default_stream(dev))
-    # one step at a time (every step on slot 0's stream): what a step takes when nothing of the next one runs beside it
-    torch.cuda.synchronize()
-    serial_ms = run.serial_ms(a.steps, rows=rows)
-    # the same run with the read words in the other width (32 bits), the same way: what the 16-bit word bought on this box
-    other_width = None
-    if world == 1 and not a.no_other_configs and not os.environ.get("SMC_BENCH_NO_WIDTH_AB"):
-        try:
-            other_width = run.measure_other_word_width(a.steps, rows=rows)
-        except Exception as e:                                       # (memory short, ...: the headline does not depend on it)
-            other_width = {"error": str(e)}
-    plan = run.step(keep_plan=True, rows=rows, slot=0)
-    torch.cuda.synchronize()
-    plan.set_timing(8)
-    for _ in range(8):
-        plan.run([run.words, run.uaux[0]], params, rows, stream=0)
-    c_ms = plan.kernel_ms()[0]
-    plan.close()
+    serial_ms = c_ms = other_width = None
+    if a.full:
+        # the locus kernels of the same planes, timed alone with one more plan (outside the timed region)
+        if slot_streams is not None:
+            torch.cuda.set_stream(torch.cuda.default_stream(dev))
+        # one step at a time (every step on slot 0's stream): what a step takes when nothing of the next one runs beside it
+        torch.cuda.synchronize()
+        serial_ms = run.serial_ms(a.steps, rows=rows)
+        # the same run with the read words in the other width (32 bits), the same way: what the 16-bit word bought on this box
+        if world == 1 and not a.no_other_configs and not os.environ.get("SMC_BENCH_NO_WIDTH_AB"):
+            try:
+                other_width = run.measure_other_word_width(a.steps, rows=rows)
+            except Exception as e:                                   # (memory short, ...: the headline does not depend on it)
+                other_width = {"error": str(e)}
+        plan = run.step(keep_plan=True, rows=rows, slot=0)
+        torch.cuda.synchronize()
+        plan.set_timing(8)
+        for _ in range(8):
+            plan.run([run.words, run.uaux[0]], params, rows, stream=0)
+        c_ms = plan.kernel_ms()[0]
+        plan.close()
     torch.cuda.synchronize()
 
     out = None
@@ -511,21 +522,23 @@ def main():
                     "frac": (16.0 * run.reads + 360.0 * run.nl) / step_s / 1e9 / HBM_PEAK_GBS},
                 # the step one at a time with the read words in the other width, same process, same inputs, right after the headline
                 **({"other_read_word_width_same_run": dict(other_width, ms_per_step_one_at_a_time_this_width=serial_ms)} if other_width else {})}),
-            "step_breakdown": {"slots": a.slots, "slot_choice": run.slot_choice, "ms_per_step_one_at_a_time": serial_ms, "placement": run.placement,
+            "step_breakdown": {"slots": a.slots, "slot_choice": run.slot_choice, "placement": run.placement,
                                # what the library's write-pattern probe saw when it chose the blocks of the read words (one per slot)
                                "allocation": {"chosen_by": "smc_mem_alloc_best (engine.DevBuf(walk_output=True))", "tries": eng.alloc_tries,
                                               "blocks": list(eng.alloc_log)},
-                               "k_bp_emit2_ms": k_ms.value, "k_call_v2_ms": c_ms,
+                               "k_bp_emit2_ms": k_ms.value,
                                "host_ms_per_step": {k: round(v / n_steps * 1e3, 3) for k, v in run.t.items() if k != "n"},
                                "pileup_reads_per_s": run.reads / step_s, "builder_status": status,
                                "plans": bench_fa.plans_record(eng)},
-            "p_value_note": "C3 has no locus that reaches filterVariants (parity.loci_filtered 0): the p-value half of the metric is "
-                            "carried by from_alignments X3 / EX / C5 (the same step as the headline, variants under the reads) and by "
-                            "other_configs X3 / EX / C5 (read words resident)",
             "host_buffers": "inputs resident in HBM when the timed region starts; handing host buffers of planes instead "
                             "(smc_call_batch_host: H2D of 8 B/read + kernels + D2H of the rows) measured 1.94 M loci/s on C3 "
                             "(DESIGN.md section 5) - PCIe-bound, never `value`",
         }
+        if a.full:
+            out["step_breakdown"].update(ms_per_step_one_at_a_time=serial_ms, k_call_v2_ms=c_ms)
+            out["p_value_note"] = ("C3 has no locus that reaches filterVariants (parity.loci_filtered 0): the p-value half of the metric "
+                                   "is carried by from_alignments X3 / EX / C5 (the same step as the headline, variants under the reads) "
+                                   "and by other_configs X3 / EX / C5 (read words resident)")
         if gather_check is not None:
             out["gather_check"] = gather_check
         if dumped is not None:
@@ -537,14 +550,14 @@ def main():
             out["cpu_baseline_object_adapter"] = cpu["object_adapter"]
             out["cpu_baseline_single_process"] = cpu["python_single"]
             out["cpu_baseline_pool_chunked"] = cpu["python_pool_chunked"]
-        if world == 1 and not a.no_parity:
+        if world == 1 and a.full and not a.no_parity:
             run.step(rows=rows, slot=0)
             torch.cuda.synchronize()
             run.rows = _TensorBuf(rows)
             out["parity"] = bench_fa.parity_full(run, nthreads, chunk=a.chunk)
     run.close()
     del rows, pipe
-    if rank == 0 and world == 1 and not a.no_other_configs:
+    if rank == 0 and world == 1 and a.full and not a.no_other_configs:
         oracle = None
         if not a.no_parity:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))

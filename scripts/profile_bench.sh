@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round profile of bench.py on the GPU box.
-#   1. rocprofv3 --kernel-trace --stats of the DRIVER'S command (bench.py --gpus 1 --steps 20 --warmup 5): per-kernel
+#   1. rocprofv3 --kernel-trace --stats of the full bench run (bench.py --gpus 1 --steps 20 --warmup 5 --full): per-kernel
 #      durations that must agree with roofline.kernel_ms of the same run (the bench line under the trace is kept too);
 #   2. HBM traffic counters in their own passes (FETCH_SIZE and WRITE_SIZE do not fit one pass; never mixed with trace
 #      domains), for C3 (the metric's config), C5 and C2, on a short run of the same batch (one block of 5 steps);
@@ -10,7 +10,7 @@ out=$1
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/$out
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/kt -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $R/$out/bench_under_trace.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/kt -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $R/$out/bench_under_trace.json 2>/dev/null
 find $R/$out/kt -name "*kernel_stats.csv" -exec cp {} $R/$out/kernel_stats.csv \;
 python3 $R/scripts/kt_summary.py $R/$out/kt > $R/$out/kernel_trace_by_grid.txt
 SHORT="--steps 5 --warmup 2 --blocks 1 --no-cpu-baseline --no-parity --no-other-configs"

@@ -115,6 +115,11 @@ def test_dump_outputs_are_float64_exact_and_a_fixed_sample_when_large(tmp_path):
     assert (idx == np.load(tmp_path / "b" / "locus.npy")).all()
 
 
+def test_the_extras_are_behind_full():
+    import bench
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+
+
 def test_bench_refuses_a_world_that_does_not_match():
     env = dict(os.environ, WORLD_SIZE="3", RANK="0", SMC_BENCH_DRY="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=120)
@@ -124,7 +129,7 @@ def test_bench_refuses_a_world_that_does_not_match():
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_rccl_runs_the_gather_path_with_one_rank():
-    """RCCL on hardware: `bench.py --gpus 1` with SMC_BENCH_FORCE_DIST=1 under a CHILD
+    """RCCL on hardware: `bench.py --gpus 1 --full` with SMC_BENCH_FORCE_DIST=1 under a CHILD
     `torch.distributed.run --nproc-per-node 1` on the `nccl` backend - init, the packed wire rows gathered to rank 0 inside every
     step, barrier, all_reduce of the block time, all_gather of the checksums - and the JSON line it prints: the rows rank 0
     received are the rows that were sent, and every row of the run equals the oracle's."""
@@ -136,7 +141,7 @@ def test_rccl_runs_the_gather_path_with_one_rank():
     env.update(SMC_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--blocks", "2",
-           "--loci-per-gpu", "20000", "--place", "0", "--no-cpu-baseline", "--no-other-configs"]
+           "--loci-per-gpu", "20000", "--place", "0", "--full", "--no-cpu-baseline", "--no-other-configs"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=850)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -160,10 +165,29 @@ def test_two_ranks_on_one_gpu_gather_what_they_sent_when_one_rank_uses_one_slot(
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(SMC_BENCH_SHARE_GPU="1", SMC_FA_ONE_SLOT_ON_RANK="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--blocks", "2",
-                        "--loci-per-gpu", "12000"], env=env, capture_output=True, text=True, timeout=850)
+                        "--loci-per-gpu", "12000", "--full"], env=env, capture_output=True, text=True, timeout=850)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
     assert len(lines) == 1 and len(lines[0]) <= 4096
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["value"] > 0
     assert d["gather_check"] == {"ranks": 2, "blocks_equal_what_was_sent": True, "bytes_per_rank": 12000 * 168}
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_a_plain_run_is_the_headline_alone():
+    """Without --full the bench sets up, warms up, times its steps and prints the line: the contract's keys and the roofline of
+    the timed steps, none of the checks and legs that take runs of their own."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--loci-per-gpu", "20000"], env=env, capture_output=True, text=True, timeout=550)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
+    line = p.stdout.rstrip().splitlines()[-1]
+    d = json.loads(line)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["roofline"]["kernel_samples"] > 0
+    for k in ("cpu_baseline", "parity", "from_alignments", "consumer_only", "other_configs", "gather_check"):
+        assert k not in d, k
+    assert "ms_per_step_one_at_a_time" not in d["step_breakdown"] and "k_call_v2_ms" not in d["step_breakdown"]

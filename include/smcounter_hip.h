@@ -453,6 +453,22 @@ int smc_read_groups_masks(smc_read_groups* g, const uint64_t* d_idents, int64_t 
 int smc_read_groups_kept(smc_read_groups* g, uint64_t seed, const uint64_t* thr, int32_t n_thr, int64_t* kept);
 int smc_read_groups_status(smc_read_groups* g, uint32_t* status);
 void smc_read_groups_destroy(smc_read_groups* g);
+/* (ABI 11, additive: three entries more, the version number unchanged) --dsGrid: the barcode rule of smc_select_alignments' philox
+ * rule and the read rule above composed, over the same finished table.  A name is kept in cell c when word 0 of
+ * Philox4x32-10(counter = (its barcode's identity lo, hi, 0x64734D54 "dsMT", 0), key = seed) < bc_thr[c] - floor(f * 2^32), 2^32 at
+ * f >= 1: the same draw and threshold as smc_select_alignments at frac f - and it is its barcode's first name or its own draw (above)
+ * < rd_thr[c].  Thresholds <= 2^32, at most SMC_RG_MAX_TARGETS of them.
+ *   _counts_frac  per fraction f < n_frac the counters of the barcodes kept at bc_thr[f] (host counts[f * SMC_RG_N_COUNTS + k], the
+ *                 layout above: records 0 (not counted per barcode), names, barcodes, one, multi, multi_names, first names (one per
+ *                 barcode), 0) - probKeep of a cell is the host's, from these.
+ *   _masks_grid   per run: _masks with a mask per cell, d_masks[c * ceil(n_ids / 32) + (g >> 5)] (`stream`; SMC_RG_MISS as _masks).
+ *   _kept_grid    the file-wide kept names per cell (host kept[n_cells]).
+ * Everything runs on the null stream except _masks_grid. */
+int smc_read_groups_counts_frac(smc_read_groups* g, uint64_t seed, const uint64_t* bc_thr, int32_t n_frac, int64_t* counts);
+int smc_read_groups_masks_grid(smc_read_groups* g, const uint64_t* d_idents, int64_t n_ids, uint64_t seed, const uint64_t* bc_thr,
+                               const uint64_t* rd_thr, int32_t n_cells, uint32_t* d_masks, void* stream);
+int smc_read_groups_kept_grid(smc_read_groups* g, uint64_t seed, const uint64_t* bc_thr, const uint64_t* rd_thr, int32_t n_cells,
+                              int64_t* kept);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

@@ -90,7 +90,18 @@ def build_parser() -> argparse.ArgumentParser:
                         "counter-based draw (Philox4x32-10) keyed by --dsSeed and a hash of the full name falls below probKeep - NOT "
                         "the reference's sample (another random subset of about the same size; nested across targets), independent "
                         "of how the file is cut into runs.  Needs --dsRpb")
+    p.add_argument("--dsGrid", action="store_true", default=False,
+                   help="the cross product of --dsMT and --dsRpb: for every fraction f and every target r the run is also called as "
+                        "if on the BAM that ds.mt.py --pct f, then ds.reads.withinMT.py --rpb r on its output (both --seed dsSeed) "
+                        "write, at --mtDepth of f (--dsMtDepth, or max(1, round(f x mtDepth))) and --rpb r; written to "
+                        "<outPrefix>.dsMT<f>.dsRpb<r>.smCounter.{all,cut}.txt and .cut.vcf, beside the files of every fraction and "
+                        "target.  From the same decode.  --dsSampler and --dsRpbSampler both reference (the two scripts' names exactly) "
+                        "or both philox (--dsSampler philox's barcodes, then --dsRpbSampler philox's rule with probKeep from the kept "
+                        "barcodes' counts); at most %d cells.  Needs --dsMT and --dsRpb" % GRID_MAX_CELLS)
     return p
+
+
+GRID_MAX_CELLS = 32          # (a launch takes at most SMC_RG_MAX_TARGETS masks; every cell holds a batch's device arrays)
 
 
 def ds_fractions(args):
@@ -141,14 +152,50 @@ def ds_rpb_targets(args):
             raise SystemExit("--dsRpbMtDepth: %d depths for %d --dsRpb targets" % (len(depths), len(rs)))
     else:
         depths = [int(args.mtDepth)] * len(rs)
-    if getattr(args, "dsSampler", "reference") == "philox":
+    if getattr(args, "dsSampler", "reference") == "philox" and not getattr(args, "dsGrid", False):
+        # (--dsGrid decides on the pair of samplers itself: ds_grid_cells)
         raise SystemExit("--dsRpb keeps the reference's read names only: --dsSampler philox is not available with it (a rule for "
                          "reads that does not depend on how the file is cut into runs needs the whole file's first names and probKeep; "
                          "--dsRpbSampler philox is that rule)")
     return [(r, d, "%s.dsRpb%g" % (args.outPrefix, r)) for r, d in zip(rs, depths)]
 
 
-def ds_rpb_rules(args, params: VcParams, targets, early=None):
+def ds_grid_cells(args):
+    """--dsGrid -> [(f, r, mtDepth of f, output prefix)] for every --dsMT fraction f and --dsRpb target r (fractions outer); [] without
+    --dsGrid.  Refused: without both --dsMT and --dsRpb, with one philox and one reference sampler, beyond GRID_MAX_CELLS cells."""
+    if not getattr(args, "dsGrid", False):
+        return []
+    fractions, targets = ds_fractions(args), ds_rpb_targets(args)
+    if not fractions or not targets:
+        raise SystemExit("--dsGrid calls every --dsMT fraction with every --dsRpb target: it needs both --dsMT and --dsRpb")
+    bs, rs = getattr(args, "dsSampler", "reference") or "reference", getattr(args, "dsRpbSampler", None) or "reference"
+    if bs != rs:
+        raise SystemExit("--dsGrid needs --dsSampler and --dsRpbSampler to be the same sampler (both reference or both philox), got "
+                         "--dsSampler %s and --dsRpbSampler %s" % (bs, rs))
+    if len(fractions) * len(targets) > GRID_MAX_CELLS:
+        raise SystemExit("--dsGrid: %d fractions x %d targets = %d cells, at most %d" % (len(fractions), len(targets),
+                                                                                          len(fractions) * len(targets), GRID_MAX_CELLS))
+    return [(f, r, d, "%s.dsMT%g.dsRpb%g" % (args.outPrefix, f, r)) for f, d, _ in fractions for r, _, _ in targets]
+
+
+def ds_grid_rules(args, params: VcParams, cells, frac_rules, rpb_rules, grouped=None):
+    """The devplanes.DsRule of every --dsGrid cell, after the fractions' and the targets' rules: the reference's names from the
+    fractions' kept barcodes and the targets' grouping (`grouped`), or with the philox samplers from the targets' file-wide table; a
+    cell whose kept barcodes have no barcode of two or more reads ends the run with a message."""
+    import dataclasses
+    from . import devplanes
+    plist = [dataclasses.replace(params, mtDepth=d, rpb=r) for _, r, d, _ in cells]
+    fr = [(f, r) for f, r, _, _ in cells]
+    try:
+        if (getattr(args, "dsRpbSampler", None) or "reference") == "philox":
+            return devplanes.philox_grid_rules(args.bamFile, fr, plist, int(args.dsSeed), rpb_rules[0].groups)
+        kept = {rule.frac: rule.kept for rule in frac_rules}
+        return devplanes.reference_grid_rules(args.bamFile, fr, plist, int(args.dsSeed), kept, grouped)
+    except ValueError as e:
+        raise SystemExit(str(e))
+
+
+def ds_rpb_rules(args, params: VcParams, targets, early=None, grouped=None):
     """The devplanes.DsRule of every --dsRpb target: the reference's read names (one pass over the whole file, here), or with
     --dsRpbSampler philox the file-wide table on the GPU (`early`: the engine coming up; else the process's engine); a file without a
     barcode of two or more reads, or whose names collide in the table's hashes, ends the run with a message."""
@@ -164,6 +211,8 @@ def ds_rpb_rules(args, params: VcParams, targets, early=None):
                 from .engine import Engine
                 eng = _ENGINES.get(args.device) or _ENGINES.setdefault(args.device, Engine(args.device))
             return devplanes.philox_read_rules(args.bamFile, rs, plist, int(args.dsSeed), eng)
+        if grouped is not None:
+            return devplanes.reference_read_rules(args.bamFile, rs, plist, int(args.dsSeed), grouped=grouped)
         return devplanes.reference_read_rules(args.bamFile, rs, plist, int(args.dsSeed))
     except ValueError as e:
         raise SystemExit(str(e))
@@ -392,6 +441,7 @@ def _main(args) -> int:
                       mismatchThr=args.mismatchThr, mtDrop=args.mtDrop, maxMT=args.maxMT, primerDist=args.primerDist)
     fractions = ds_fractions(args)
     targets = ds_rpb_targets(args)
+    cells = ds_grid_cells(args)
     flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets)) if on)
     if flag and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("%s runs in one process only (not under torch.distributed.run with more than one rank)" % flag)
@@ -406,9 +456,20 @@ def _main(args) -> int:
         # a single process: the GPU runtime and the context come up (~ 0.1 s) in a helper thread while the target is expanded
         early = _EarlyEngine(args.device)
     loc_list = bedops.expand_loci(args.bedTarget)
+    rules = []
     try:
-        rules = (ds_rules(args, params, fractions) if fractions else []) + (ds_rpb_rules(args, params, targets, early) if targets else [])
+        if cells:
+            # (--dsGrid: the reference's grouping of the names once, for the targets and the cells alike)
+            from . import devplanes
+            grouped = None if (args.dsRpbSampler or "reference") == "philox" else devplanes.group_placed_reads(args.bamFile)
+            frac_rules = ds_rules(args, params, fractions)
+            rules = frac_rules + ds_rpb_rules(args, params, targets, early, grouped=grouped)
+            rules += ds_grid_rules(args, params, cells, frac_rules, rules[len(frac_rules):], grouped)
+        else:
+            rules = (ds_rules(args, params, fractions) if fractions else []) + (ds_rpb_rules(args, params, targets, early) if targets else [])
     except SystemExit:
+        from . import devplanes
+        devplanes.close_rules(rules)          # (a refused cell: the targets' file-wide table in HBM)
         if early is not None:                  # (the engine the helper brings up stays with the process, as after a run)
             try:
                 _ENGINES.setdefault(args.device, early.get())
@@ -416,19 +477,23 @@ def _main(args) -> int:
                 pass
         raise
     for rule in rules:
-        if rule.level == "read":
+        if rule.grid:
+            print("--dsGrid fraction %g x target %g: sampler %s, seed %d, probKeep %.6g, %d of %d read names kept (mtDepth %d)" %
+                  (rule.frac, rule.target, rule.sampler, rule.seed, rule.prob_keep, len(rule.kept) if rule.kept is not None else rule.n_kept,
+                   rule.n_names, rule.params.mtDepth))
+        elif rule.level == "read":
             print("--dsRpb %g: sampler %s, seed %d, probKeep %.6g, %d of %d read names kept (mtDepth %d)" %
                   (rule.target, rule.sampler, rule.seed, rule.prob_keep, len(rule.kept) if rule.kept is not None else rule.n_kept,
                    rule.n_names, rule.params.mtDepth))
     args.ds_rules = rules or None
     try:
-        return _run(args, params, fractions, targets, loc_list, early, t0)
+        return _run(args, params, fractions, targets, loc_list, early, t0, cells)
     finally:
         from . import devplanes
         devplanes.close_rules(rules)          # (--dsRpbSampler philox: the file-wide table in HBM, whatever happened)
 
 
-def _run(args, params, fractions, targets, loc_list, early, t0):
+def _run(args, params, fractions, targets, loc_list, early, t0, cells=()):
     # One process per GPU when launched through torch.distributed.run: rank r calls a contiguous range of the
     # ordered locus list (loci share nothing, smCounter.py:683-685) on GPU LOCAL_RANK, rank 0 gathers the rows
     # in submission order and writes the files.
@@ -503,7 +568,8 @@ def _run(args, params, fractions, targets, loc_list, early, t0):
     output = postfilter.apply_repeat_filters(output, trf, rm, pred=pred)
     threshold = writers.pi_threshold(args.mtDepth, args.threshold)
     writers.write_outputs(args.outPrefix, output, threshold, pred=pred)
-    for (f, d, prefix), o in zip(fractions + targets, ds_outputs):
+    # (--dsGrid: the cells' rows after them, each at its fraction's mtDepth)
+    for (d, prefix), o in zip([(d, p) for _, d, p in fractions + targets] + [(d, p) for _, _, d, p in cells], ds_outputs):
         vc.raise_on_exception(o, loc_list)
         o_pred = getattr(o, "pred", None)
         o = postfilter.apply_repeat_filters(o, trf, rm, pred=o_pred)

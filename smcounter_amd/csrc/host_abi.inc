@@ -902,6 +902,7 @@ struct smc_read_groups {
     void* mem = nullptr;                // both tables, the info / count words, status, counters, kept counts
     RgTable G{};
     unsigned long long* d_kept = nullptr;
+    unsigned long long* d_frac = nullptr;   // (--dsGrid) RG_F_N counters per fraction
     int64_t counts[SMC_RG_N_COUNTS] = {0};
 };
 
@@ -953,7 +954,8 @@ int smc_read_groups_finish(smc_read_groups* g, int64_t* counts) {
     size_t off = 0;
     auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_name = carve(16 * cap), o_info = carve(4 * cap), o_bc = carve(16 * cap), o_cnt = carve(4 * cap),
-                 o_st = carve(4), o_ctr = carve(8 * RG_N_CTR), o_kept = carve(8 * SMC_RG_MAX_TARGETS);
+                 o_st = carve(4), o_ctr = carve(8 * RG_N_CTR), o_kept = carve(8 * SMC_RG_MAX_TARGETS),
+                 o_frac = carve(8 * RG_F_N * SMC_RG_MAX_TARGETS);
     HIPCHK(hipMalloc(&g->mem, off));
     char* m = (char*)g->mem;
     RgTable& G = g->G;
@@ -961,6 +963,7 @@ int smc_read_groups_finish(smc_read_groups* g, int64_t* counts) {
     G.n_mask = G.b_mask = cap - 1;
     G.status = (uint32_t*)(m + o_st); G.ctr = (unsigned long long*)(m + o_ctr);
     g->d_kept = (unsigned long long*)(m + o_kept);
+    g->d_frac = (unsigned long long*)(m + o_frac);
     HIPCHK(hipMemsetAsync(m + o_st, 0, off - o_st, 0));
     hipLaunchKernelGGL(k_rg_init, dim3(rg_grid(cap)), dim3(RG_BLOCK), 0, 0, G);
     for (const auto& c : g->chunks)
@@ -1010,6 +1013,77 @@ int smc_read_groups_kept(smc_read_groups* g, uint64_t seed, const uint64_t* thr,
     unsigned long long k[SMC_RG_MAX_TARGETS];
     HIPCHK(hipMemcpy(k, g->d_kept, 8 * (size_t)n_thr, hipMemcpyDeviceToHost));
     for (int t = 0; t < n_thr; ++t) kept[t] = (int64_t)k[t];
+    return SMC_OK;
+}
+
+// (--dsGrid) the cells' thresholds: bc_thr[c] (sel_keep's: floor(f * 2^32), 2^32 keeps every barcode) and rd_thr[c], each <= 2^32
+static int rg_grid_thresholds(const uint64_t* bc_thr, const uint64_t* rd_thr, int32_t n, RgGridThr& T) {
+    if (n < 0 || n > SMC_RG_MAX_TARGETS || (n && (!bc_thr || !rd_thr))) return fail(SMC_E_ARG, "smc_read_groups: bad grid thresholds");
+    memset(&T, 0, sizeof T);
+    for (int c = 0; c < n; ++c) {
+        if (bc_thr[c] > (1ull << 32) || rd_thr[c] > (1ull << 32)) return fail(SMC_E_ARG, "smc_read_groups: a threshold above 2^32");
+        T.bc[c] = bc_thr[c];
+        T.rd[c] = rd_thr[c];
+    }
+    return SMC_OK;
+}
+
+int smc_read_groups_counts_frac(smc_read_groups* g, uint64_t seed, const uint64_t* bc_thr, int32_t n_frac, int64_t* counts) {
+    if (!g || (n_frac && !counts)) return fail(SMC_E_ARG, "smc_read_groups_counts_frac: bad argument");
+    if (!g->finished) return fail(SMC_E_ARG, "smc_read_groups_counts_frac: the table is not finished");
+    RgThr F;
+    { const int rc = rg_thresholds(bc_thr, n_frac, F); if (rc) return rc; }
+    if (!n_frac) return SMC_OK;
+    HIPCHK(hipSetDevice(g->ctx->device));
+    HIPCHK(hipMemsetAsync(g->d_frac, 0, 8 * RG_F_N * SMC_RG_MAX_TARGETS, 0));
+    hipLaunchKernelGGL(k_rg_reduce_frac, dim3(std::min(rg_grid(g->G.b_mask + 1), RG_RED_GRID)), dim3(RG_BLOCK), 0, 0, g->G, (unsigned long long)seed, F, (int)n_frac,
+                       g->d_frac);
+    HIPCHK(hipGetLastError());
+    unsigned long long k[RG_F_N * SMC_RG_MAX_TARGETS];
+    HIPCHK(hipMemcpy(k, g->d_frac, 8 * RG_F_N * (size_t)n_frac, hipMemcpyDeviceToHost));
+    for (int f = 0; f < n_frac; ++f) {
+        const unsigned long long* a = k + f * RG_F_N;
+        int64_t* c = counts + (size_t)f * SMC_RG_N_COUNTS;
+        c[0] = 0;                                                          // (records: not counted per barcode)
+        c[1] = (int64_t)(a[RG_F_ONE] + a[RG_F_MULTI_NAMES]);               // names: one per single-name barcode, multi_names
+        c[2] = (int64_t)a[RG_F_BARCODES]; c[3] = (int64_t)a[RG_F_ONE]; c[4] = (int64_t)a[RG_F_MULTI]; c[5] = (int64_t)a[RG_F_MULTI_NAMES];
+        c[6] = (int64_t)a[RG_F_BARCODES];                                  // first names: one per barcode
+        c[7] = 0;
+    }
+    return SMC_OK;
+}
+
+int smc_read_groups_masks_grid(smc_read_groups* g, const uint64_t* d_idents, int64_t n_ids, uint64_t seed, const uint64_t* bc_thr,
+                               const uint64_t* rd_thr, int32_t n_cells, uint32_t* d_masks, void* stream) {
+    if (!g || n_ids < 0 || n_ids >= (int64_t)0xFFFFFF00 || (n_ids && (!d_idents || !d_masks)))
+        return fail(SMC_E_ARG, "smc_read_groups_masks_grid: bad argument");
+    if (!g->finished) return fail(SMC_E_ARG, "smc_read_groups_masks_grid: the table is not finished");
+    RgGridThr T;
+    { const int rc = rg_grid_thresholds(bc_thr, rd_thr, n_cells, T); if (rc) return rc; }
+    if (!n_ids || !n_cells) return SMC_OK;
+    HIPCHK(hipSetDevice(g->ctx->device));
+    const uint32_t n_words = (uint32_t)((n_ids + 31) / 32);
+    hipLaunchKernelGGL(k_rg_masks_grid, dim3((unsigned)((n_ids + RG_BLOCK - 1) / RG_BLOCK)), dim3(RG_BLOCK), 0, (hipStream_t)stream, g->G,
+                       (const unsigned long long*)d_idents, (uint32_t)n_ids, (unsigned long long)seed, T, (int)n_cells, d_masks, n_words);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
+int smc_read_groups_kept_grid(smc_read_groups* g, uint64_t seed, const uint64_t* bc_thr, const uint64_t* rd_thr, int32_t n_cells,
+                              int64_t* kept) {
+    if (!g || (n_cells && !kept)) return fail(SMC_E_ARG, "smc_read_groups_kept_grid: bad argument");
+    if (!g->finished) return fail(SMC_E_ARG, "smc_read_groups_kept_grid: the table is not finished");
+    RgGridThr T;
+    { const int rc = rg_grid_thresholds(bc_thr, rd_thr, n_cells, T); if (rc) return rc; }
+    if (!n_cells) return SMC_OK;
+    HIPCHK(hipSetDevice(g->ctx->device));
+    HIPCHK(hipMemsetAsync(g->d_kept, 0, 8 * SMC_RG_MAX_TARGETS, 0));
+    hipLaunchKernelGGL(k_rg_kept_grid, dim3(std::min(rg_grid(g->G.n_mask + 1), RG_RED_GRID)), dim3(RG_BLOCK), 0, 0, g->G, (unsigned long long)seed, T, (int)n_cells,
+                       g->d_kept);
+    HIPCHK(hipGetLastError());
+    unsigned long long k[SMC_RG_MAX_TARGETS];
+    HIPCHK(hipMemcpy(k, g->d_kept, 8 * (size_t)n_cells, hipMemcpyDeviceToHost));
+    for (int c = 0; c < n_cells; ++c) kept[c] = (int64_t)k[c];
     return SMC_OK;
 }
 

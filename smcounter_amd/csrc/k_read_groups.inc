@@ -1,4 +1,5 @@
-// Included by smcounter_hip.hip (after k_philox_marks.inc: it uses smc_philox4x32_10).
+// Included by smcounter_hip.hip after k_philox_marks.inc (it uses smc_philox4x32_10) and after k_select_aln.inc (the --dsGrid
+// passes below use its sel_draw, the barcode draw of --dsMT's philox rule).
 // ------------------------------------------------------------------------------------------
 // the read-level philox sampler of --dsRpb (smc_read_groups_*): a file-wide table of read names and barcodes in HBM
 // ------------------------------------------------------------------------------------------
@@ -21,6 +22,7 @@
 //   k_rg_masks    per run: a wave of 64 read-name ids looks up its names and writes two mask words per target (the bit layout
 //                 smc_select_alignments_keyed takes at SMC_SEL_KEY_READ)
 //   k_rg_kept     per name slot: the kept names of every target, for the run log
+// and, for --dsGrid (below): k_rg_reduce_frac, k_rg_masks_grid, k_rg_kept_grid.
 // Every probe loop ends after `capacity` steps: a full table sets RG_FULL and the record is dropped (not met: load <= 0.5).
 #define RG_BLOCK 256
 #define RG_DOMAIN 0x64735250u               // counter word 2 of the read draw ("dsRP"); SEL_DOMAIN "dsMT" is the barcode draw's
@@ -230,4 +232,122 @@ __global__ __launch_bounds__(RG_BLOCK) void k_rg_kept(RgTable G, unsigned long l
             if (lane == 0 && m) atomicAdd(&kept[t], (unsigned long long)__popcll(m));
         }
     }
+}
+
+// ---- --dsGrid: the barcode rule of --dsMT (--dsSampler philox) and the read rule above composed, over the same table
+// A name is kept in cell (f, r) when its barcode's draw - sel_draw (k_select_aln.inc: sel_keep's, over the barcode slot's identity) -
+// is below thr_f, and it is its barcode's first name or its own draw (rg_draw) is below the cell's read threshold.  Three launches:
+//   k_rg_reduce_frac  per barcode slot, per fraction: the kept barcodes' barcodes / one / multi / multi_names (probKeep of a cell is
+//                     computed from them on the host).  Per wave ballots and one sum, per workgroup in LDS, then one global atomic
+//                     per workgroup and counter (a per-wave atomic would be millions on a handful of lines at 32 fractions)
+//   k_rg_masks_grid   per run: k_rg_masks with the barcode draw in front (the name slot's info word gives its barcode slot)
+//   k_rg_kept_grid    per name slot: the kept names of every cell, for the run log (per workgroup in LDS as k_rg_reduce_frac)
+// The two reducing passes run on at most RG_RED_GRID workgroups (grid-stride): one global atomic per workgroup and counter.
+#define RG_F_BARCODES 0
+#define RG_F_ONE 1
+#define RG_F_MULTI 2
+#define RG_F_MULTI_NAMES 3
+#define RG_F_N 4                            // counters per fraction (names = one + multi_names)
+#define RG_RED_GRID 1024                    // workgroups of k_rg_reduce_frac / k_rg_kept_grid (4 per CU)
+
+struct RgGridThr {
+    unsigned long long bc[SMC_RG_MAX_TARGETS];   // per cell: floor(f * 2^32), 2^32 at f >= 1 (sel_keep's thr)
+    unsigned long long rd[SMC_RG_MAX_TARGETS];   // per cell: floor(probKeep * 2^32) in [0, 2^32]
+};
+
+__global__ __launch_bounds__(RG_BLOCK) void k_rg_reduce_frac(RgTable G, unsigned long long seed, RgThr F, int n_frac,
+                                                             unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long acc[SMC_RG_MAX_TARGETS * RG_F_N];
+    for (int k = threadIdx.x; k < n_frac * RG_F_N; k += RG_BLOCK) acc[k] = 0ull;
+    __syncthreads();
+    const unsigned long long n = G.b_mask + 1, stride = (unsigned long long)gridDim.x * RG_BLOCK;
+    const int lane = threadIdx.x & (WAVE - 1);
+    for (unsigned long long w = ((unsigned long long)blockIdx.x * RG_BLOCK + threadIdx.x) - lane; w < n; w += stride) {
+        const unsigned long long s = w + lane;
+        bool used = false;
+        uint32_t c = 0, u = 0;
+        if (s < n && G.bc[s].key != 0ull) {
+            used = true;
+            c = G.bc_cnt[s];
+            u = sel_draw(G.bc[s].key, seed);
+        }
+        if (__ballot(used) == 0ull) continue;                      // (wave-uniform)
+        for (int f = 0; f < n_frac; ++f) {
+            const bool kept = used && (unsigned long long)u < F.t[f];
+            const unsigned long long bcs = __ballot(kept);
+            if (bcs == 0ull) continue;                             // (wave-uniform)
+            const unsigned long long one = __ballot(kept && c == 1u), multi = __ballot(kept && c >= 2u);
+            const unsigned long long multi_names = rg_wave_sum(kept && c >= 2u ? (unsigned long long)c : 0ull);
+            if (lane == 0) {
+                unsigned long long* a = acc + f * RG_F_N;
+                atomicAdd(&a[RG_F_BARCODES], (unsigned long long)__popcll(bcs));
+                if (one) atomicAdd(&a[RG_F_ONE], (unsigned long long)__popcll(one));
+                if (multi) {
+                    atomicAdd(&a[RG_F_MULTI], (unsigned long long)__popcll(multi));
+                    atomicAdd(&a[RG_F_MULTI_NAMES], multi_names);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < n_frac * RG_F_N; k += RG_BLOCK)
+        if (acc[k]) atomicAdd(&out[k], acc[k]);
+}
+
+// masks[c * n_words + (g >> 5)] bit (g & 31): read-name id g is kept in cell c (k_rg_masks' layout, a mask per cell)
+__global__ __launch_bounds__(RG_BLOCK) void k_rg_masks_grid(RgTable G, const unsigned long long* __restrict__ ident, uint32_t n_ids,
+                                                            unsigned long long seed, RgGridThr T, int n_cells, uint32_t* __restrict__ masks,
+                                                            uint32_t n_words) {
+    const uint32_t g = blockIdx.x * RG_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & (WAVE - 1);
+    bool found = false, first = false;
+    uint32_t ub = 0, un = 0;
+    if (g < n_ids) {
+        const unsigned long long id = ident[g];
+        const uint32_t s = id ? rg_find(G.name, G.n_mask, id) : RG_NONE;
+        if (s == RG_NONE) atomicOr(G.status, SMC_RG_MISS);
+        else {
+            const uint32_t info = G.name_info[s];
+            found = true;
+            first = (info & RG_FIRST) != 0u;
+            ub = sel_draw(G.bc[info & ~RG_FIRST].key, seed);       // (the slot index is below the capacity: k_rg_insert wrote it)
+            un = rg_draw(id, seed);
+        }
+    }
+    const uint32_t word = (g - lane) >> 5;             // the wave's first word
+    for (int c = 0; c < n_cells; ++c) {
+        const unsigned long long m = __ballot(found && (unsigned long long)ub < T.bc[c] && (first || (unsigned long long)un < T.rd[c]));
+        if (lane == 0) {
+            if (word < n_words) masks[(size_t)c * n_words + word] = (uint32_t)m;
+            if (word + 1 < n_words) masks[(size_t)c * n_words + word + 1] = (uint32_t)(m >> 32);
+        }
+    }
+}
+
+__global__ __launch_bounds__(RG_BLOCK) void k_rg_kept_grid(RgTable G, unsigned long long seed, RgGridThr T, int n_cells,
+                                                           unsigned long long* __restrict__ kept) {
+    __shared__ unsigned long long acc[SMC_RG_MAX_TARGETS];
+    for (int c = threadIdx.x; c < n_cells; c += RG_BLOCK) acc[c] = 0ull;
+    __syncthreads();
+    const unsigned long long n = G.n_mask + 1, stride = (unsigned long long)gridDim.x * RG_BLOCK;
+    const int lane = threadIdx.x & (WAVE - 1);
+    for (unsigned long long w = ((unsigned long long)blockIdx.x * RG_BLOCK + threadIdx.x) - lane; w < n; w += stride) {
+        const unsigned long long s = w + lane;
+        bool used = false, first = false;
+        uint32_t ub = 0, un = 0;
+        if (s < n && G.name[s].key != 0ull) {
+            const uint32_t info = G.name_info[s];
+            used = true;
+            first = (info & RG_FIRST) != 0u;
+            ub = sel_draw(G.bc[info & ~RG_FIRST].key, seed);
+            un = rg_draw(G.name[s].key, seed);
+        }
+        for (int c = 0; c < n_cells; ++c) {
+            const unsigned long long m = __ballot(used && (unsigned long long)ub < T.bc[c] && (first || (unsigned long long)un < T.rd[c]));
+            if (lane == 0 && m) atomicAdd(&acc[c], (unsigned long long)__popcll(m));
+        }
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < n_cells; c += RG_BLOCK)
+        if (acc[c]) atomicAdd(&kept[c], acc[c]);
 }

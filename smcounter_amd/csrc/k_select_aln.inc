@@ -44,14 +44,19 @@ struct SelRule {
 
 __device__ __forceinline__ uint32_t sel_key(const SelRule& R, const smc_dev_aln& a) { return R.by_read ? a.pair_gid : a.bc_gid; }
 
+// the barcode draw of the philox rule: word 0 of Philox4x32-10(identity lo, hi, SEL_DOMAIN, 0; seed).  (Shared with --dsGrid's passes
+// over the file-wide table, k_read_groups.inc: the two cannot drift.)
+__device__ __forceinline__ uint32_t sel_draw(unsigned long long id, unsigned long long seed) {
+    uint32_t x[4];
+    smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SEL_DOMAIN, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+    return x[0];
+}
+
 __device__ __forceinline__ bool sel_keep(const SelRule& R, uint32_t gid) {
     if (gid >= R.n_ids) return false;
     if (R.mask) return ((R.mask[gid >> 5] >> (gid & 31u)) & 1u) != 0u;
     if (R.thr >= (1ull << 32)) return true;
-    const unsigned long long id = R.ident[gid];
-    uint32_t x[4];
-    smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SEL_DOMAIN, 0u, (uint32_t)R.seed, (uint32_t)(R.seed >> 32), x);
-    return (unsigned long long)x[0] < R.thr;
+    return (unsigned long long)sel_draw(R.ident[gid], R.seed) < R.thr;
 }
 
 __global__ __launch_bounds__(SEL_BLOCK) void k_sel_count(const smc_dev_aln* __restrict__ aln, uint32_t n_aln, SelRule R,

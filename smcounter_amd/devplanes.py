@@ -367,7 +367,7 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
     nl = A["nl"]
     res = []
     idents = names = p_idents = p_names = None
-    d_masks = {}                     # (philox read rules) id(table) -> (device masks of all its rules, words per mask, id(rule) -> index)
+    d_masks = {}                     # (philox read rules) (id(table), grid) -> (device masks of those rules, words per mask, id(rule) -> index)
     try:
         for rule, d in zip(rules, ds):
             if not nl:
@@ -382,11 +382,13 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
                                              "different read names: ds.reads.withinMT.py keeps whole names, the decoder's ids cannot tell "
                                              "them apart" % (chrom, lo + 1, lo + nl))
                 if rule.groups is not None:
-                    # (--dsRpbSampler philox: the masks of every target from the file-wide table, one launch per run)
-                    if id(rule.groups) not in d_masks:
-                        d_masks[id(rule.groups)] = _run_read_masks(eng, rule.groups, [r for r in rules if r.groups is rule.groups],
-                                                                   p_idents, chrom, lo, nl)
-                    buf, n_words, index = d_masks[id(rule.groups)]
+                    # (--dsRpbSampler philox: the masks of every target from the file-wide table, one launch per run; the --dsGrid
+                    # cells over the same table: one launch more)
+                    key = (id(rule.groups), rule.grid)
+                    if key not in d_masks:
+                        d_masks[key] = _run_read_masks(eng, rule.groups, [r for r in rules if r.groups is rule.groups and r.grid == rule.grid],
+                                                       p_idents, chrom, lo, nl)
+                    buf, n_words, index = d_masks[key]
                     sel, counts, d_orig = select_run(eng, up, A, lo, d_mask=buf.data_ptr() + 4 * n_words * index[id(rule)], level="read")
                 else:
                     if rule.kept_idents is not None:
@@ -454,14 +456,18 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
 
 def _run_read_masks(eng, groups, rules, p_idents, chrom, lo, nl):
     """One launch for a run: the keep masks of every philox read rule of one table over the run's read-name identities ->
-    (device buffer, words per mask, {id(rule): index}).  An identity the table does not hold (it cannot happen) ends the run."""
+    (device buffer, words per mask, {id(rule): index}).  An identity the table does not hold (it cannot happen) ends the run.
+    (--dsGrid cells - all of `rules` or none - take the composed rule: ReadGroups.masks_grid.)"""
     from .engine import DevBuf
     n = len(p_idents)
     n_words = (n + 31) // 32
     d_id = DevBuf(eng, 8 * max(1, n) + 256).upload(np.ascontiguousarray(p_idents, np.uint64) if n else np.zeros(1, np.uint64))
     buf = DevBuf(eng, 4 * max(1, n_words * len(rules)) + 256)
     try:
-        groups.masks(d_id.data_ptr(), n, rules[0].seed, [r.thr for r in rules], buf.data_ptr())
+        if rules[0].grid:
+            groups.masks_grid(d_id.data_ptr(), n, rules[0].seed, [r.bc_thr for r in rules], [r.thr for r in rules], buf.data_ptr())
+        else:
+            groups.masks(d_id.data_ptr(), n, rules[0].seed, [r.thr for r in rules], buf.data_ptr())
         st = groups.status()
     except BaseException:
         buf.free()
@@ -649,10 +655,14 @@ class DsRule:
     groups: object = None
     thr: int = None
     n_kept: int = None
+    # (--dsGrid) a cell: level "read", `frac` f and `target` r; `kept` the names of the three-step workflow (reference), or, philox,
+    # `bc_thr` = the --dsMT draw's threshold at f beside `thr`; `n_names` the names of the barcodes kept at f
+    grid: bool = False
+    bc_thr: int = None
 
     @property
     def flag(self) -> str:
-        return "--dsRpb" if self.level == "read" else "--dsMT"
+        return "--dsGrid" if self.grid else "--dsRpb" if self.level == "read" else "--dsMT"
 
     @property
     def sampler(self) -> str:
@@ -660,6 +670,8 @@ class DsRule:
 
     @property
     def label(self) -> str:
+        if self.grid:
+            return "fraction %g x target %g" % (self.frac, self.target)
         return "target %g" % self.target if self.level == "read" else "fraction %g" % self.frac
 
 
@@ -681,15 +693,22 @@ def reference_rules(path: str, fracs, params_list, seed: int):
     return rules
 
 
-def reference_read_rules(path: str, targets, params_list, seed: int):
+def group_placed_reads(path: str):
+    """The file's placed read names grouped as ds.reads.withinMT.py:37-44 groups them -> (per_bc, order): the one pass over the file
+    that --dsRpb and --dsGrid (reference sampler) share."""
+    from .tools import ds_reads_within_mt as rw
+    return rw.group_reads(bamio.placed_qnames(path))
+
+
+def reference_read_rules(path: str, targets, params_list, seed: int, grouped=None):
     """DsRules of --dsRpb: for each target r the read names ds.reads.withinMT.py --rpb r --seed `seed` keeps (:22-90;
     tools.ds_reads_within_mt): per barcode its distinct names in first-appearance order, probKeep from the whole file's counts,
     barcodes in py2 dict order, the first name always kept, every further one when random() <= probKeep.  The names are read and
-    grouped once per file.  A file without a barcode of two or more names has no probKeep (the reference divides by zero):
-    ValueError naming the file and the target."""
+    grouped once per file (`grouped`: group_placed_reads(path) done already).  A file without a barcode of two or more names has no
+    probKeep (the reference divides by zero): ValueError naming the file and the target."""
     from .py2compat import py2_dict_order
     from .tools import ds_reads_within_mt as rw
-    per_bc, order = rw.group_reads(bamio.placed_qnames(path))
+    per_bc, order = grouped if grouped is not None else group_placed_reads(path)
     py2 = py2_dict_order(order)
     names = [q for bc in order for q in per_bc[bc]]
     idents = fnv64_array(names)
@@ -705,6 +724,64 @@ def reference_read_rules(path: str, targets, params_list, seed: int):
         ki = np.sort(idents[np.fromiter((q in kept for q in names), bool, len(names))]) if unique else None
         rules.append(DsRule(1.0, P, kept=kept, seed=int(seed), kept_idents=ki, level="read", target=float(r), prob_keep=prob,
                             n_names=len(names)))
+    return rules
+
+
+def reference_grid_rules(path: str, cells, params_list, seed: int, kept_barcodes, grouped):
+    """DsRules of --dsGrid with the reference's samplers: for every cell (f, r) the read names of ds.mt.py --pct f, then
+    ds.reads.withinMT.py --rpb r on that BAM (both --seed `seed`).  The first BAM holds the kept barcodes whole, so the second script
+    sees the file's grouping restricted to them: their names, first-appearance order, py2 dict order of that order, probKeep from their
+    counts, one random() stream.  `kept_barcodes`: f -> the barcodes reference_rules keeps at f; `grouped`: group_placed_reads(path) -
+    no further pass over the file.  A cell whose kept barcodes include none of two or more names: ValueError naming f and r."""
+    from .py2compat import py2_dict_order
+    from .tools import ds_reads_within_mt as rw
+    per_bc, order = grouped
+    names = [q for bc in order for q in per_bc[bc]]
+    unique = len(np.unique(fnv64_array(names))) == len(names)
+    sub, rules = {}, []
+    for (f, r), P in zip(cells, params_list):
+        if f not in sub:
+            keep = kept_barcodes[f]
+            order_f = [bc for bc in order if bc in keep]
+            names_f = [q for bc in order_f for q in per_bc[bc]]
+            sub[f] = ({bc: per_bc[bc] for bc in order_f}, py2_dict_order(order_f), names_f, fnv64_array(names_f))
+        per_f, py2_f, names_f, idents_f = sub[f]
+        try:
+            prob = rw.prob_keep(per_f, r)
+        except ZeroDivisionError:
+            raise ValueError("--dsGrid fraction %g x target %g: no barcode kept at %g in %s has more than one read name, so "
+                             "ds.reads.withinMT.py's probKeep (:58) is not defined (it divides by zero)" % (f, r, f, path))
+        kept = rw.draw_reads(per_f, py2_f, prob, seed)
+        ki = np.sort(idents_f[np.fromiter((q in kept for q in names_f), bool, len(names_f))]) if unique else None
+        rules.append(DsRule(float(f), P, kept=kept, seed=int(seed), kept_idents=ki, level="read", target=float(r), prob_keep=prob,
+                            n_names=len(names_f), grid=True))
+    return rules
+
+
+def frac_threshold(f: float) -> int:
+    """The --dsMT philox draw's threshold at fraction f (smc_select_alignments): floor(f x 2^32), 2^32 at f >= 1."""
+    return 1 << 32 if f >= 1.0 else int(np.floor(f * 4294967296.0))
+
+
+def philox_grid_rules(path: str, cells, params_list, seed: int, groups):
+    """DsRules of --dsGrid with both philox samplers, over the --dsRpbSampler philox targets' file-wide table `groups` (one table per
+    file): a name is kept in cell (f, r) when its barcode passes the --dsMT philox draw at f and it is its barcode's first name or its
+    read draw is below floor(probKeep_fr x 2^32); probKeep_fr as ds.reads.withinMT.py:58 computes it, in double, from the counters of
+    the barcodes kept at f (ReadGroups.counts_frac) - a plain --dsRpb r --dsRpbSampler philox run on the BAM of the --dsSampler philox
+    barcodes at f.  A cell whose kept barcodes include none of two or more names: ValueError naming f and r."""
+    fr = list(dict.fromkeys(f for f, _ in cells))
+    cf = dict(zip(fr, groups.counts_frac(seed, [frac_threshold(f) for f in fr])))
+    rules = []
+    for (f, r), P in zip(cells, params_list):
+        c = cf[f]
+        if c["multi_names"] == c["multi"]:
+            raise ValueError("--dsGrid fraction %g x target %g: no barcode kept at %g in %s has more than one read name, so "
+                             "ds.reads.withinMT.py's probKeep (:58) is not defined (it divides by zero)" % (f, r, f, path))
+        prob = 1.0 * (float(r) - 1.0) * (c["one"] + c["multi"]) / (c["multi_names"] - c["multi"])
+        rules.append(DsRule(float(f), P, kept=None, seed=int(seed), level="read", target=float(r), prob_keep=prob, n_names=c["names"],
+                            groups=groups, thr=read_threshold(prob), grid=True, bc_thr=frac_threshold(f)))
+    for rule, k in zip(rules, groups.kept_grid(seed, [r.bc_thr for r in rules], [r.thr for r in rules])):
+        rule.n_kept = k
     return rules
 
 
@@ -738,10 +815,10 @@ class ReadGroups(object):
         return dict(zip(self.COUNTS, (int(v) for v in c)))
 
     @staticmethod
-    def _thr(thr):
+    def _thr(thr, what="--dsRpb targets"):
         t = np.ascontiguousarray(thr, np.uint64)
         if len(t) > RG_MAX_TARGETS:
-            raise ValueError("at most %d --dsRpb targets with the philox sampler" % RG_MAX_TARGETS)
+            raise ValueError("at most %d %s with the philox sampler" % (RG_MAX_TARGETS, what))
         return t
 
     def masks(self, d_idents, n_ids: int, seed: int, thr, d_masks):
@@ -757,6 +834,33 @@ class ReadGroups(object):
         _lib.check(self.L.smc_read_groups_kept(self._h, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), t.ctypes.data, len(t),
                                                k.ctypes.data), "smc_read_groups_kept")
         return [int(v) for v in k[:len(t)]]
+
+    def counts_frac(self, seed: int, bc_thr) -> list:
+        """(--dsGrid) Per fraction threshold (frac_threshold) the counters of the barcodes the --dsMT philox draw keeps: dicts of
+        names / barcodes / one / multi / multi_names / first_names."""
+        t = self._thr(bc_thr, "--dsMT fractions")
+        c = np.zeros((max(1, len(t)), 8), np.int64)
+        _lib.check(self.L.smc_read_groups_counts_frac(self._h, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), t.ctypes.data, len(t),
+                                                      c.ctypes.data), "smc_read_groups_counts_frac")
+        return [dict(zip(self.COUNTS[1:], (int(v) for v in row[1:7]))) for row in c[:len(t)]]
+
+    def masks_grid(self, d_idents, n_ids: int, seed: int, bc_thr, rd_thr, d_masks):
+        """(--dsGrid) masks() with a mask per cell: barcode threshold bc_thr[c] and read threshold rd_thr[c]."""
+        b, r = self._thr(bc_thr, "--dsGrid cells"), self._thr(rd_thr, "--dsGrid cells")
+        if len(b) != len(r):
+            raise ValueError("masks_grid: %d barcode thresholds, %d read thresholds" % (len(b), len(r)))
+        _lib.check(self.L.smc_read_groups_masks_grid(self._h, d_idents, int(n_ids), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                                     b.ctypes.data, r.ctypes.data, len(b), d_masks, ctypes.c_void_p(0)),
+                   "smc_read_groups_masks_grid")
+
+    def kept_grid(self, seed: int, bc_thr, rd_thr) -> list:
+        b, r = self._thr(bc_thr, "--dsGrid cells"), self._thr(rd_thr, "--dsGrid cells")
+        if len(b) != len(r):
+            raise ValueError("kept_grid: %d barcode thresholds, %d read thresholds" % (len(b), len(r)))
+        k = np.zeros(max(1, len(b)), np.int64)
+        _lib.check(self.L.smc_read_groups_kept_grid(self._h, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), b.ctypes.data, r.ctypes.data,
+                                                    len(b), k.ctypes.data), "smc_read_groups_kept_grid")
+        return [int(v) for v in k[:len(b)]]
 
     def status(self) -> int:
         st = ctypes.c_uint32(0)

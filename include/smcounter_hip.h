@@ -469,6 +469,15 @@ int smc_read_groups_masks_grid(smc_read_groups* g, const uint64_t* d_idents, int
                                const uint64_t* rd_thr, int32_t n_cells, uint32_t* d_masks, void* stream);
 int smc_read_groups_kept_grid(smc_read_groups* g, uint64_t seed, const uint64_t* bc_thr, const uint64_t* rd_thr, int32_t n_cells,
                               int64_t* kept);
+/* (ABI 11, additive: one entry more, the version number unchanged) --lod: the limit of detection by barcode depth, as the reference's
+ * mt_depths_lod.R computes it - roots[d], d = 0 .. max_depth, is the root on [0, 1] of pbinom(needed - 1, d, p) - 0.05 that R's
+ * uniroot returns (R_zeroin2, tol = DBL_EPSILON^0.25, maxit 1000), NOT yet rounded to 4 decimals (the caller rounds); 1.0 where
+ * d < 5, where the end values have the same sign (every d < needed) and where the search does not converge.  iters[d] (may be NULL):
+ * passes of the search's loop (0: none made; 1001: no convergence).  roots / iters: HOST arrays of max_depth + 1 elements; device
+ * scratch is the context's, the kernel runs on the null stream and the call returns with the values.  needed < 1, max_depth < 0 or
+ * max_depth > SMC_LOD_MAX_DEPTH: SMC_E_INPUT, nothing is launched. */
+#define SMC_LOD_MAX_DEPTH (1 << 24)
+int smc_lod_table(smc_ctx* ctx, int needed, int max_depth, double* roots, int32_t* iters);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

@@ -98,6 +98,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "target.  From the same decode.  --dsSampler and --dsRpbSampler both reference (the two scripts' names exactly) "
                         "or both philox (--dsSampler philox's barcodes, then --dsRpbSampler philox's rule with probKeep from the kept "
                         "barcodes' counts); at most %d cells.  Needs --dsMT and --dsRpb" % GRID_MAX_CELLS)
+    p.add_argument("--lod", action="store_true", default=False,
+                   help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
+                        "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
+                        "with probability 0.95), for the full-depth output and for every --dsMT fraction, --dsRpb target and "
+                        "--dsGrid cell at that output's own mtDepth: <prefix>.lod.bedgraph and <prefix>.lod.bedgraph.quantiles.txt "
+                        "beside each output's files, and <outPrefix>.lod.summary.txt, one line per output.  The table of LODs by "
+                        "depth is made on the GPU.  One process only")
+    p.add_argument("--lodDepth", choices=("UMT", "MT"), default=None,
+                   help="the barcode depth --lod reads.  UMT (default): the barcodes that vote at the locus (after --mtDrop and the "
+                        "cap), the UMT column of .smCounter.all.txt.  MT: every barcode, the MT column.  Needs --lod")
     return p
 
 
@@ -277,6 +287,11 @@ def call_shard(args, params: VcParams, loci, device: int, early=None):
     output = _Rows()
     decoder = os.environ.get("SMC_BAM_DECODER", "native")
     rules = getattr(args, "ds_rules", None) or None
+    # (--lod: three int32 columns of every output's rows, full depth first, and the tables while the engine is alive)
+    lod_cols = None
+    if getattr(args, "lod", False):
+        from . import lod as _lod
+        lod_cols = [_lod.DepthCols() for _ in range(1 + len(rules or ()))]
     # (one process per GPU: the ranks of a node share its cores for decoding)
     # (LOCAL_WORLD_SIZE: WORLD_SIZE also counts the ranks of other nodes, which do not share these cores)
     per_node = int(os.environ.get("LOCAL_WORLD_SIZE") or os.environ.get("WORLD_SIZE", "1"))
@@ -305,15 +320,25 @@ def call_shard(args, params: VcParams, loci, device: int, early=None):
         for first, rb in batches:
             if rules is not None:
                 rb, rbs = rb[0], rb[1:]
-                for rule, o, b in zip(rules, ds_out, rbs):
+                for k, (rule, o, b) in enumerate(zip(rules, ds_out, rbs)):
                     o.add(vc.vc_resident(b, rule.params, ref, eng))
+                    if lod_cols is not None:
+                        lod_cols[1 + k].add(eng.last_rows)
             output.add(vc.vc_resident(rb, params, ref, eng))
+            if lod_cols is not None:
+                lod_cols[0].add(eng.last_rows)
             _report_boundary(eng.last_rows, rb.chrom, rb.pos)
+        if lod_cols is not None:
+            output.lod = _lod.run_lods(eng, [params] + [rule.params for rule in rules or ()], lod_cols, args.lodDepth or "UMT")
         _release_engine(eng)
         output.ds = [o.done() for o in ds_out]
         return output.done()
     for first, pb in _prefetch(batches):
         output.add(vc.vc_batch(pb, params, ref, eng=eng))
+        if lod_cols is not None:
+            lod_cols[0].add(eng.last_rows)
+    if lod_cols is not None:
+        output.lod = _lod.run_lods(eng, [params], lod_cols, args.lodDepth or "UMT")
     eng.close()
     return output.done()
 
@@ -445,6 +470,11 @@ def _main(args) -> int:
     flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets)) if on)
     if flag and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("%s runs in one process only (not under torch.distributed.run with more than one rank)" % flag)
+    if getattr(args, "lodDepth", None) is not None and not getattr(args, "lod", False):
+        raise SystemExit("--lodDepth chooses the barcode depth --lod reads: it needs --lod")
+    if getattr(args, "lod", False) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--lod runs in one process only (not under torch.distributed.run with more than one rank): the writing rank "
+                         "prints from gathered wire rows after its engine is gone, and the table of LODs is made on the GPU")
     host = [v for v, on in (("SMC_PLANES=host", os.environ.get("SMC_PLANES", "device") == "host"),
                             ("SMC_BAM_DECODER=python", os.environ.get("SMC_BAM_DECODER", "native") == "python")) if on]
     if flag and host:
@@ -565,15 +595,35 @@ def _run(args, params, fractions, targets, loc_list, early, t0, cells=()):
         args.bedRepeatMaskerSubset if args.bedRepeatMaskerSubset and os.path.exists(args.bedRepeatMaskerSubset) else None)
     pred = getattr(output, "pred", None)                  # (single process: the printer's int(PI) per row)
     ds_outputs = getattr(output, "ds", None) or []        # (--dsMT / --dsRpb: the rows of every fraction, then of every target)
+    lods = getattr(output, "lod", None)                   # (--lod: per output, in the same order, what lod.run_lods made)
+    lod_entries = []
+
+    def write_lod(k, prefix, mt_depth, rpb):
+        # the LOD files of output k beside the files just written, its line in the run log and its entry for the summary
+        from . import lod as _lod
+        o = lods[k]
+        _lod.write_lod(prefix, [c for c, _ in loc_list], [p for _, p in loc_list], o["lods"])
+        print("--lod %s: %d barcodes needed (mtDepth %d), depth %s, table of %d depths, at most %d iterations" %
+              (prefix, o["needed"], mt_depth, args.lodDepth or "UMT", o["table"], o["iters"]))
+        lod_entries.append(_lod.summary_entry(prefix, mt_depth, rpb, o["needed"], o["rows"], args.lodDepth or "UMT", o["lods"]))
     output = postfilter.apply_repeat_filters(output, trf, rm, pred=pred)
     threshold = writers.pi_threshold(args.mtDepth, args.threshold)
     writers.write_outputs(args.outPrefix, output, threshold, pred=pred)
+    if lods is not None:
+        write_lod(0, args.outPrefix, args.mtDepth, args.rpb)
     # (--dsGrid: the cells' rows after them, each at its fraction's mtDepth)
-    for (d, prefix), o in zip([(d, p) for _, d, p in fractions + targets] + [(d, p) for _, _, d, p in cells], ds_outputs):
+    # (the reads per barcode an output was called with, for --lod's summary: --rpb for a fraction, r for a target or a cell)
+    rpbs = [args.rpb] * len(fractions) + [r for r, _, _ in targets] + [r for _, r, _, _ in cells]
+    for k, ((d, prefix), o) in enumerate(zip([(d, p) for _, d, p in fractions + targets] + [(d, p) for _, _, d, p in cells], ds_outputs)):
         vc.raise_on_exception(o, loc_list)
         o_pred = getattr(o, "pred", None)
         o = postfilter.apply_repeat_filters(o, trf, rm, pred=o_pred)
         writers.write_outputs(prefix, o, writers.pi_threshold(d, args.threshold), pred=o_pred)
+        if lods is not None:
+            write_lod(1 + k, prefix, d, rpbs[k])
+    if lods is not None:
+        from . import lod as _lod
+        _lod.write_summary(args.outPrefix, lod_entries)
     t1 = datetime.datetime.now()
     print("smCounter completed running at " + str(t1))
     print("smCounter total time: " + str(t1 - t0))

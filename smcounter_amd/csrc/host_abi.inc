@@ -34,6 +34,9 @@ struct smc_ctx {
     // scratch of smc_select_alignments (block counts / offsets, the blocks' largest ends, the difference array), grown on demand
     void* sel_scratch = nullptr;
     size_t sel_bytes = 0;
+    // scratch of smc_lod_table (roots, then iteration counts), grown on demand
+    void* lod_scratch = nullptr;
+    size_t lod_bytes = 0;
     // the segment table of a build travels from page-locked memory (a copy from pageable memory blocks the host until the stream has
     // drained): a small ring, an entry reused once the copy that read it has run (its event)
     struct SegStage { void* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
@@ -328,6 +331,7 @@ void smc_destroy(smc_ctx* c) {
     (void)hipFree(c->lfact);
     (void)hipFree(c->bp_scratch);
     (void)hipFree(c->sel_scratch);
+    (void)hipFree(c->lod_scratch);
     {
         std::vector<smc_ctx::VmmBlock> left;
         { std::lock_guard<std::mutex> g(c->vmm_mu); left.swap(c->vmm); }
@@ -1013,6 +1017,31 @@ int smc_read_groups_kept(smc_read_groups* g, uint64_t seed, const uint64_t* thr,
     unsigned long long k[SMC_RG_MAX_TARGETS];
     HIPCHK(hipMemcpy(k, g->d_kept, 8 * (size_t)n_thr, hipMemcpyDeviceToHost));
     for (int t = 0; t < n_thr; ++t) kept[t] = (int64_t)k[t];
+    return SMC_OK;
+}
+
+// (--lod) the table of one `needed`: k_lod_table over d = 0 .. max_depth on the null stream, the roots and the iteration counts back
+int smc_lod_table(smc_ctx* ctx, int needed, int max_depth, double* roots, int32_t* iters) {
+    if (!ctx || !roots) return fail(SMC_E_ARG, "smc_lod_table: NULL argument");
+    if (needed < 1) return fail(SMC_E_INPUT, "smc_lod_table: needed = " + std::to_string(needed) + ", at least 1 barcode expected");
+    if (max_depth < 0 || max_depth > SMC_LOD_MAX_DEPTH)
+        return fail(SMC_E_INPUT, "smc_lod_table: max_depth = " + std::to_string(max_depth) + " outside 0 .. " + std::to_string(SMC_LOD_MAX_DEPTH));
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)max_depth + 1, o_iters = (8 * n + 255) & ~(size_t)255, bytes = o_iters + 4 * n;
+    if (bytes > ctx->lod_bytes) {
+        (void)hipFree(ctx->lod_scratch);                  // (synchronises the device: no table kernel is in flight - the entry waits for its own)
+        ctx->lod_scratch = nullptr; ctx->lod_bytes = 0;
+        const size_t want = bytes + bytes / 8;
+        hipError_t e = hipMalloc(&ctx->lod_scratch, want);
+        if (e != hipSuccess) return fail(SMC_E_HIP, "smc_lod_table: " + std::to_string(want) + " bytes of scratch: " + hipGetErrorString(e));
+        ctx->lod_bytes = want;
+    }
+    double* d_roots = (double*)ctx->lod_scratch;
+    int32_t* d_iters = (int32_t*)((char*)ctx->lod_scratch + o_iters);
+    hipLaunchKernelGGL(k_lod_table, dim3((unsigned)((n + LOD_BLOCK - 1) / LOD_BLOCK)), dim3(LOD_BLOCK), 0, 0, needed, max_depth, d_roots, d_iters);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(roots, d_roots, 8 * n, hipMemcpyDeviceToHost));       // (null stream: ordered behind the kernel)
+    if (iters) HIPCHK(hipMemcpy(iters, d_iters, 4 * n, hipMemcpyDeviceToHost));
     return SMC_OK;
 }
 

@@ -175,6 +175,19 @@ class Engine(object):
             db.n_slots, us.ctypes.data, len(us), rows.ctypes.data), "smc_call_batch_host")
         return rows
 
+    # ---- --lod: the limit of detection by barcode depth (smc_lod_table, csrc/k_lod.inc)
+    def lod_table(self, needed: int, max_depth: int):
+        """(roots float64[max_depth + 1], iters int32[max_depth + 1]): per depth d the root R's uniroot finds for
+        pbinom(needed - 1, d, p) - 0.05 on [0, 1] (tools.mt_depths_lod.find_lod before its round(., 4); 1.0 where it gives up) and
+        the passes of the search's loop.  needed < 1 or max_depth outside 0 .. 2^24: SmcError, nothing is launched."""
+        needed, max_depth = int(needed), int(max_depth)
+        if not (-2 ** 31 <= needed < 2 ** 31 and -2 ** 31 <= max_depth < 2 ** 31):
+            raise _lib.SmcError("smc_lod_table: needed = %d, max_depth = %d: not 32-bit integers" % (needed, max_depth))
+        n = max(0, max_depth) + 1 if max_depth <= (1 << 24) else 1       # (refused arguments: the library looks at no buffer)
+        roots, iters = np.empty(n, np.float64), np.empty(n, np.int32)
+        _lib.check(self.L.smc_lod_table(self.ctx, needed, max_depth, roots.ctypes.data, iters.ctypes.data), "smc_lod_table")
+        return roots, iters
+
     # ---- resident path: the four planes + umi_start live in HBM (torch tensors), a plan is reused
     def upload(self, db: DeviceBatch):
         import torch

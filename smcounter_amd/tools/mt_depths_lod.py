@@ -91,6 +91,27 @@ def _fmt(x) -> str:
     return "%.15g" % x                       # R's default number formatting in write.table
 
 
+PROBS = (0.01, 0.05, 0.10, 0.50, 0.90, 0.95, 0.99)
+
+
+def write_bedgraph(path: str, rows) -> None:
+    """rows: (chrom, locL, locR, lod), the first three as text - the bedgraph, MTs column dropped (:45-48)."""
+    with open(path, "w") as fh:
+        for chrom, loc_l, loc_r, lod in rows:
+            fh.write("\t".join((chrom, loc_l, loc_r, _fmt(lod))) + "\n")
+
+
+def quantiles(lods):
+    """R's default (type 7) quantiles of the LODs at PROBS (:49)."""
+    return np.quantile(np.array(lods, float), PROBS) if len(lods) else [float("nan")] * len(PROBS)
+
+
+def write_quantiles(path: str, lods) -> None:
+    with open(path, "w") as fh:
+        for p, v in zip(PROBS, quantiles(lods)):
+            fh.write("%d%%|%s\n" % (round(p * 100), _fmt(v)))
+
+
 def main(argv) -> int:
     mean_depth, file_in, file_out = float(argv[0]), argv[1], argv[2]
     needed = barcodes_needed(mean_depth)
@@ -103,14 +124,8 @@ def main(argv) -> int:
         lod = find_lod(mts if mts not in ("NA", "") else float("nan"), needed)
         rows.append((chrom, loc_l, loc_r, lod))
         lods.append(lod)
-    with open(file_out, "w") as fh:          # bedgraph, MTs column dropped (:45-48)
-        for chrom, loc_l, loc_r, lod in rows:
-            fh.write("\t".join((chrom, loc_l, loc_r, _fmt(lod))) + "\n")
-    probs = (0.01, 0.05, 0.10, 0.50, 0.90, 0.95, 0.99)
-    q = np.quantile(np.array(lods, float), probs) if lods else [float("nan")] * 7   # R's default type 7
-    with open(file_out + ".quantiles.txt", "w") as fh:
-        for p, v in zip(probs, q):
-            fh.write("%d%%|%s\n" % (round(p * 100), _fmt(v)))
+    write_bedgraph(file_out, rows)
+    write_quantiles(file_out + ".quantiles.txt", lods)
     return 0
 
 

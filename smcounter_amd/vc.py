@@ -27,6 +27,7 @@ def vc_batch(pb, params: VcParams, refprov, eng: Optional[_engine.Engine] = None
     try:
         db = pb if isinstance(pb, features.DeviceBatch) else features.extract_features(pb, params)
         out_rows = eng.call_batch_host(db, params)
+        eng.last_rows = out_rows              # (as vc_resident leaves them: the command line's --lod reads three columns)
     finally:
         if own:
             eng.close()

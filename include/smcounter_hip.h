@@ -478,6 +478,40 @@ int smc_read_groups_kept_grid(smc_read_groups* g, uint64_t seed, const uint64_t*
  * max_depth > SMC_LOD_MAX_DEPTH: SMC_E_INPUT, nothing is launched. */
 #define SMC_LOD_MAX_DEPTH (1 << 24)
 int smc_lod_table(smc_ctx* ctx, int needed, int max_depth, double* roots, int32_t* iters);
+/* (ABI 11, additive: one entry more, the version number unchanged) --dsAF: which barcodes of a run cover / carry a listed allele.
+ * The run as smc_build_planes takes it (d_aln[n_aln], the CIGAR pool, the (letter, quality) pair pool, d_loc[n_loci], start0, n_bc:
+ * nothing of it is written); d_var[n_var]: the listed variants of the run, each a locus index and an allele key by the keys the
+ * caller uses (smCounter.py:371-460):
+ *   SMC_AF_SNV  the letter `letter` with no insertion or deletion starting behind it
+ *   SMC_AF_INS  INS|X|XS: `letter` = X, the `len` letters S at d_ins[ins_off ..] (len <= SMC_AF_MAX_INS), compared with the read's
+ *               inserted letters as the host's slice clamps them at the read's end
+ *   SMC_AF_DEL  DEL|XD|X: `letter` = X, `len` = the deleted positions (the letters D are the reference's: a deletion listed with other
+ *               letters is one no read shows - SMC_AF_NONE)
+ *   SMC_AF_NONE a key no read shows
+ * Per variant v and run-wide barcode id g < n_bc, over the pileup of v's locus (the alignments with pos <= p < end: the loc[].n reads
+ * of the plane builder, no quality or mapping filter): reads = the barcode's reads there, alt = those that show v's key.
+ *   d_covers / d_carries  [n_var][2 * ceil(n_bc / 64)] uint32 words each: bit g of v's mask - reads > 0 / 2 * alt > reads; the bits
+ *                         at and beyond n_bc are 0.  8-byte aligned.
+ *   d_counts              [n_var][n_bc][2] uint32 (reads, alt), 8-byte aligned; NULL: the counters stay in the context's scratch
+ * Enqueued on `stream`; nothing waits.  n_var > SMC_AF_MAX_VARIANTS, a locus index beyond n_loci, a kind beyond SMC_AF_NONE, a len
+ * beyond SMC_AF_MAX_INS, inserted letters beyond the n_ins bytes of d_ins: SMC_E_INPUT, nothing is launched (d_var / d_ins are DEVICE arrays: `var_host`, the same n_var records in host
+ * memory, is what is checked and what sizes the launch). */
+#define SMC_AF_SNV 0u
+#define SMC_AF_INS 1u
+#define SMC_AF_DEL 2u
+#define SMC_AF_NONE 3u
+#define SMC_AF_MAX_INS 255
+#define SMC_AF_MAX_VARIANTS 4096
+typedef struct smc_af_variant {
+    uint32_t locus;            /* index into d_loc: p = start0 + locus */
+    uint32_t kind, letter;     /* SMC_AF_*; the site's letter (the ALT of an SNV, the anchor of an insertion / deletion) */
+    uint32_t len, ins_off;     /* inserted letters (and where they start in d_ins) / deleted positions */
+    uint32_t pad[3];
+} smc_af_variant;
+int smc_allele_carriers(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, const uint8_t* d_bq,
+                        const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0, int64_t n_bc, const smc_af_variant* d_var,
+                        const smc_af_variant* var_host, int32_t n_var, const uint8_t* d_ins, int64_t n_ins, uint32_t* d_covers, uint32_t* d_carries,
+                        uint32_t* d_counts, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

@@ -41,6 +41,9 @@ DEV_ALN_DTYPE = np.dtype([("pos", "<i4"), ("end", "<i4"), ("cig_off", "<u4"), ("
                           ("pad", "<u2"), ("bc_gid", "<u4"), ("pair_gid", "<u4")])
 DEV_LOCUS_DTYPE = np.dtype([("w0", "<u4"), ("w1", "<u4"), ("slot_off", "<u4"), ("n", "<u4")])
 assert DEV_ALN_DTYPE.itemsize == 36 and DEV_LOCUS_DTYPE.itemsize == 16
+# smc_af_variant (smc_allele_carriers): a listed variant of a run
+AF_VARIANT_DTYPE = np.dtype([("locus", "<u4"), ("kind", "<u4"), ("letter", "<u4"), ("len", "<u4"), ("ins_off", "<u4"), ("pad", "<u4", (3,))])
+assert AF_VARIANT_DTYPE.itemsize == 32
 
 
 def c_params(p: VcParams) -> SmcParams:

@@ -98,6 +98,22 @@ def build_parser() -> argparse.ArgumentParser:
                         "target.  From the same decode.  --dsSampler and --dsRpbSampler both reference (the two scripts' names exactly) "
                         "or both philox (--dsSampler philox's barcodes, then --dsRpbSampler philox's rule with probKeep from the kept "
                         "barcodes' counts); at most %d cells.  Needs --dsMT and --dsRpb" % GRID_MAX_CELLS)
+    p.add_argument("--dsAF", default=None, help="in-run dilution of listed variants: comma-separated target allele fractions t in (0, 1).  "
+                                                "For each, the run is also called as if on the BAM that tools/ds_allele_fraction.py --af t "
+                                                "--seed dsSeed writes for the variants of --dsAFVariants: the barcodes that carry a listed "
+                                                "allele (more than half of their reads at the locus show it) are dropped whole, each with the "
+                                                "probability that brings its variant's barcode fraction down to t (a fraction is never raised; "
+                                                "an absent variant, or one every covering barcode carries, is left alone and reported); "
+                                                "written to <outPrefix>.dsAF<t>.smCounter.{all,cut}.txt and .cut.vcf, and, one line per "
+                                                "variant and output, <outPrefix>.dsAF.detection.txt.  The carriers are found on the GPU in a "
+                                                "pre-pass over the runs around the listed loci; the BAM is then decoded once.  Not together "
+                                                "with --dsMT, --dsRpb or --dsGrid; needs the device plane builder; one process only")
+    p.add_argument("--dsAFVariants", default=None, help="the variants --dsAF dilutes, one per line: VCF lines (CHROM POS ID REF ALT ...; a "
+                                                        ".cut.vcf of this program can be fed back) or `chrom pos ref alt`, tab-separated, "
+                                                        "pos 1-based, `#` lines skipped.  One-letter substitutions, insertions X / XS (at most "
+                                                        "%d inserted letters) and deletions XD / X; one variant per position, each a locus of "
+                                                        "--bedTarget" % AF_MAX_INS)
+    p.add_argument("--dsAFMtDepth", default=None, help="comma-separated --mtDepth of each --dsAF target; default --mtDepth")
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -111,6 +127,7 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+AF_MAX_INS = 255             # (smc_allele_carriers: SMC_AF_MAX_INS letters per listed insertion)
 GRID_MAX_CELLS = 32          # (a launch takes at most SMC_RG_MAX_TARGETS masks; every cell holds a batch's device arrays)
 
 
@@ -168,6 +185,76 @@ def ds_rpb_targets(args):
                          "reads that does not depend on how the file is cut into runs needs the whole file's first names and probKeep; "
                          "--dsRpbSampler philox is that rule)")
     return [(r, d, "%s.dsRpb%g" % (args.outPrefix, r)) for r, d in zip(rs, depths)]
+
+
+def ds_af_targets(args):
+    """--dsAF / --dsAFVariants / --dsAFMtDepth -> [(t, mtDepth of t, output prefix)]; [] without --dsAF.  Refused: one of --dsAF and
+    --dsAFVariants without the other, a target outside (0, 1), --dsAF beside --dsMT, --dsRpb or --dsGrid."""
+    from .tools import ds_allele_fraction as af
+    text, vfile = getattr(args, "dsAF", None), getattr(args, "dsAFVariants", None)
+    if text in (None, ""):
+        if vfile not in (None, ""):
+            raise SystemExit("--dsAFVariants lists the variants --dsAF dilutes: it needs --dsAF")
+        if getattr(args, "dsAFMtDepth", None) not in (None, ""):
+            raise SystemExit("--dsAFMtDepth gives the mtDepth of each --dsAF target: it needs --dsAF")
+        return []
+    if vfile in (None, ""):
+        raise SystemExit("--dsAF dilutes listed variants: it needs --dsAFVariants")
+    try:
+        ts = af.parse_targets(text, "--dsAF")
+    except ValueError as e:
+        raise SystemExit(str(e))
+    other = [f for f in ("dsMT", "dsRpb", "dsGrid") if getattr(args, f, None) not in (None, "", False)]
+    if other:
+        raise SystemExit("--dsAF cannot be combined with --%s in one run (the cross product is not built)" % other[0])
+    dtext = getattr(args, "dsAFMtDepth", None)
+    if dtext not in (None, ""):
+        try:
+            depths = [int(x) for x in str(dtext).split(",") if x.strip()]
+        except ValueError:
+            raise SystemExit("--dsAFMtDepth: comma-separated integers expected, got %r" % dtext)
+        if len(depths) != len(ts):
+            raise SystemExit("--dsAFMtDepth: %d depths for %d --dsAF targets" % (len(depths), len(ts)))
+    else:
+        depths = [int(args.mtDepth)] * len(ts)
+    return [(t, d, "%s.dsAF%g" % (args.outPrefix, t)) for t, d in zip(ts, depths)]
+
+
+def ds_af_variants(args, loc_list):
+    """The variants of --dsAFVariants, checked: the file's own refusals (tools.ds_allele_fraction.parse_variants) and every variant a
+    locus of --bedTarget."""
+    from . import dsaf
+    from .tools import ds_allele_fraction as af
+    try:
+        variants = af.parse_variants(args.dsAFVariants)
+        dsaf.check_variants(variants, loc_list)
+    except (ValueError, OSError) as e:
+        raise SystemExit(str(e))
+    return variants
+
+
+def ds_af_rules(args, params: VcParams, af_targets, variants, early):
+    """The devplanes.DsRule of every --dsAF target (the pre-pass on the GPU: devplanes.ds_af_rules) and the titration's numbers; the
+    run log gets a line per variant and target."""
+    import dataclasses
+    from . import devplanes
+    from .tools import ds_allele_fraction as af
+    plist = [dataclasses.replace(params, mtDepth=d) for _, d, _ in af_targets]
+    if early is not None:
+        eng = early.get()
+    else:
+        from .engine import Engine
+        eng = _ENGINES.get(args.device) or _ENGINES.setdefault(args.device, Engine(args.device))
+    try:
+        rules, res = devplanes.ds_af_rules(args.bamFile, fasta.FastaFile(args.refGenome), variants, [t for t, _, _ in af_targets], plist,
+                                           int(args.dsSeed), eng)
+    except (ValueError, bamio.BamError) as e:
+        raise SystemExit(str(e))
+    for r in res:
+        for v, row in zip(variants, r["rows"]):
+            print(af.report_line(v, r["target"], row))
+        print("--dsAF %g: seed %d, %d barcodes dropped" % (r["target"], int(args.dsSeed), len(r["dropped"])))
+    return rules, res
 
 
 def ds_grid_cells(args):
@@ -467,7 +554,8 @@ def _main(args) -> int:
     fractions = ds_fractions(args)
     targets = ds_rpb_targets(args)
     cells = ds_grid_cells(args)
-    flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets)) if on)
+    af_targets = ds_af_targets(args)
+    flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets), ("--dsAF", af_targets)) if on)
     if flag and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("%s runs in one process only (not under torch.distributed.run with more than one rank)" % flag)
     if getattr(args, "lodDepth", None) is not None and not getattr(args, "lod", False):
@@ -487,8 +575,14 @@ def _main(args) -> int:
         early = _EarlyEngine(args.device)
     loc_list = bedops.expand_loci(args.bedTarget)
     rules = []
+    args.ds_af = None
     try:
-        if cells:
+        if af_targets:
+            # (--dsAF: the listed variants checked, then the pre-pass over the runs around them)
+            variants = ds_af_variants(args, loc_list)
+            rules, res = ds_af_rules(args, params, af_targets, variants, early)
+            args.ds_af = (variants, res)
+        elif cells:
             # (--dsGrid: the reference's grouping of the names once, for the targets and the cells alike)
             from . import devplanes
             grouped = None if (args.dsRpbSampler or "reference") == "philox" else devplanes.group_placed_reads(args.bamFile)
@@ -517,13 +611,13 @@ def _main(args) -> int:
                    rule.n_names, rule.params.mtDepth))
     args.ds_rules = rules or None
     try:
-        return _run(args, params, fractions, targets, loc_list, early, t0, cells)
+        return _run(args, params, fractions, targets, loc_list, early, t0, cells, af_targets)
     finally:
         from . import devplanes
         devplanes.close_rules(rules)          # (--dsRpbSampler philox: the file-wide table in HBM, whatever happened)
 
 
-def _run(args, params, fractions, targets, loc_list, early, t0, cells=()):
+def _run(args, params, fractions, targets, loc_list, early, t0, cells=(), af_targets=()):
     # One process per GPU when launched through torch.distributed.run: rank r calls a contiguous range of the
     # ordered locus list (loci share nothing, smCounter.py:683-685) on GPU LOCAL_RANK, rank 0 gathers the rows
     # in submission order and writes the files.
@@ -613,8 +707,10 @@ def _run(args, params, fractions, targets, loc_list, early, t0, cells=()):
         write_lod(0, args.outPrefix, args.mtDepth, args.rpb)
     # (--dsGrid: the cells' rows after them, each at its fraction's mtDepth)
     # (the reads per barcode an output was called with, for --lod's summary: --rpb for a fraction, r for a target or a cell)
-    rpbs = [args.rpb] * len(fractions) + [r for r, _, _ in targets] + [r for _, r, _, _ in cells]
-    for k, ((d, prefix), o) in enumerate(zip([(d, p) for _, d, p in fractions + targets] + [(d, p) for _, _, d, p in cells], ds_outputs)):
+    # (--dsAF: its targets alone - it is not combined with the other three - each at its mtDepth and the run's --rpb)
+    rpbs = [args.rpb] * len(fractions) + [r for r, _, _ in targets] + [r for _, r, _, _ in cells] + [args.rpb] * len(af_targets)
+    for k, ((d, prefix), o) in enumerate(zip([(d, p) for _, d, p in fractions + targets] + [(d, p) for _, _, d, p in cells] +
+                                             [(d, p) for _, d, p in af_targets], ds_outputs)):
         vc.raise_on_exception(o, loc_list)
         o_pred = getattr(o, "pred", None)
         o = postfilter.apply_repeat_filters(o, trf, rm, pred=o_pred)
@@ -624,6 +720,13 @@ def _run(args, params, fractions, targets, loc_list, early, t0, cells=()):
     if lods is not None:
         from . import lod as _lod
         _lod.write_summary(args.outPrefix, lod_entries)
+    if af_targets:
+        # the titration on one page: every listed variant in the full-depth output and in every target's
+        from . import dsaf
+        variants, res = args.ds_af
+        outs = [(None, args.outPrefix, None, lods[0]["lods"] if lods is not None else None)] + \
+               [(t, p, r["rows"], lods[1 + k]["lods"] if lods is not None else None) for k, ((t, _, p), r) in enumerate(zip(af_targets, res))]
+        dsaf.write_detection(args.outPrefix, variants, outs, {(c, "%d" % int(q)): n for n, (c, q) in enumerate(loc_list)})
     t1 = datetime.datetime.now()
     print("smCounter completed running at " + str(t1))
     print("smCounter total time: " + str(t1 - t0))

@@ -37,6 +37,9 @@ struct smc_ctx {
     // scratch of smc_lod_table (roots, then iteration counts), grown on demand
     void* lod_scratch = nullptr;
     size_t lod_bytes = 0;
+    // scratch of smc_allele_carriers (the counters of a call that does not ask for them), grown on demand
+    void* af_scratch = nullptr;
+    size_t af_bytes = 0;
     // the segment table of a build travels from page-locked memory (a copy from pageable memory blocks the host until the stream has
     // drained): a small ring, an entry reused once the copy that read it has run (its event)
     struct SegStage { void* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
@@ -332,6 +335,7 @@ void smc_destroy(smc_ctx* c) {
     (void)hipFree(c->bp_scratch);
     (void)hipFree(c->sel_scratch);
     (void)hipFree(c->lod_scratch);
+    (void)hipFree(c->af_scratch);
     {
         std::vector<smc_ctx::VmmBlock> left;
         { std::lock_guard<std::mutex> g(c->vmm_mu); left.swap(c->vmm); }
@@ -1042,6 +1046,51 @@ int smc_lod_table(smc_ctx* ctx, int needed, int max_depth, double* roots, int32_
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(roots, d_roots, 8 * n, hipMemcpyDeviceToHost));       // (null stream: ordered behind the kernel)
     if (iters) HIPCHK(hipMemcpy(iters, d_iters, 4 * n, hipMemcpyDeviceToHost));
+    return SMC_OK;
+}
+
+// (--dsAF) the covers / carries bits of a run's listed variants: the counters zeroed, k_af_count over every variant's window, k_af_bits
+int smc_allele_carriers(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, const uint8_t* d_bq,
+                        const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0, int64_t n_bc, const smc_af_variant* d_var,
+                        const smc_af_variant* var_host, int32_t n_var, const uint8_t* d_ins, int64_t n_ins, uint32_t* d_covers, uint32_t* d_carries,
+                        uint32_t* d_counts, void* stream) {
+    if (!ctx || n_aln < 0 || n_loci < 0 || n_bc < 0 || n_var < 0 || n_ins < 0) return fail(SMC_E_ARG, "smc_allele_carriers: bad argument");
+    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, "smc_allele_carriers: " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
+    if (!n_var || !n_bc) return SMC_OK;
+    if (!d_aln || !d_cig || !d_bq || !d_loc || !d_var || !var_host || !d_covers || !d_carries) return fail(SMC_E_ARG, "smc_allele_carriers: NULL argument");
+    if (n_aln >= (int64_t)0xFFFFFF00 || n_bc >= (int64_t)0x7FFFFF00) return fail(SMC_E_ARG, "smc_allele_carriers: run too large");
+    if ((((uintptr_t)d_covers | (uintptr_t)d_carries | (uintptr_t)d_counts) & 7u) != 0) return fail(SMC_E_ARG, "smc_allele_carriers: outputs must be 8-byte aligned");
+    for (int32_t v = 0; v < n_var; ++v) {
+        const smc_af_variant& V = var_host[v];
+        if ((int64_t)V.locus >= n_loci) return fail(SMC_E_INPUT, "smc_allele_carriers: variant " + std::to_string(v) + " names locus " + std::to_string(V.locus) + " of " + std::to_string(n_loci));
+        if (V.kind > SMC_AF_NONE) return fail(SMC_E_INPUT, "smc_allele_carriers: variant " + std::to_string(v) + " has kind " + std::to_string(V.kind));
+        if (V.kind == SMC_AF_INS && (V.len > SMC_AF_MAX_INS || (int64_t)V.ins_off + V.len > n_ins || (V.len && !d_ins)))
+            return fail(SMC_E_INPUT, "smc_allele_carriers: variant " + std::to_string(v) + ": " + std::to_string(V.len) + " inserted letters at " +
+                                     std::to_string(V.ins_off) + " (at most " + std::to_string(SMC_AF_MAX_INS) + ", pool of " + std::to_string(n_ins) + ")");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t n_cnt = 2 * (size_t)n_bc * (size_t)n_var;
+    if (n_cnt >= (size_t)0xFFFFFF00) return fail(SMC_E_INPUT, "smc_allele_carriers: " + std::to_string(n_var) + " variants x " + std::to_string(n_bc) + " barcodes: too many counters for one call");
+    if (!d_counts) {
+        if (4 * n_cnt > ctx->af_bytes) {
+            (void)hipFree(ctx->af_scratch);               // (synchronises the device: no earlier call's kernels are in flight)
+            ctx->af_scratch = nullptr; ctx->af_bytes = 0;
+            const size_t want = 4 * n_cnt + n_cnt / 2 + 256;
+            hipError_t e = hipMalloc(&ctx->af_scratch, want);
+            if (e != hipSuccess) return fail(SMC_E_HIP, "smc_allele_carriers: " + std::to_string(want) + " bytes of scratch: " + hipGetErrorString(e));
+            ctx->af_bytes = want;
+        }
+        d_counts = (uint32_t*)ctx->af_scratch;
+    }
+    const uint32_t n_words64 = (uint32_t)((n_bc + 63) / 64);
+    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_cnt + 255) / 256, 4096)), dim3(256), 0, st, d_counts, (uint32_t)n_cnt);
+    if (n_aln)
+        hipLaunchKernelGGL(k_af_count, dim3((unsigned)std::min<int64_t>((n_aln + AF_BLOCK - 1) / AF_BLOCK, 64), (unsigned)n_var), dim3(AF_BLOCK), 0, st,
+                           d_aln, (uint32_t)n_aln, d_cig, d_bq, d_loc, start0, d_var, d_ins, (uint32_t)n_bc, d_counts);
+    hipLaunchKernelGGL(k_af_bits, dim3((n_words64 * WAVE + AF_BLOCK - 1) / AF_BLOCK, (unsigned)n_var), dim3(AF_BLOCK), 0, st,
+                       (const uint32_t*)d_counts, (uint32_t)n_bc, n_words64, (unsigned long long*)d_covers, (unsigned long long*)d_carries);
+    HIPCHK(hipGetLastError());
     return SMC_OK;
 }
 

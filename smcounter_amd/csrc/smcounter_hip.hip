@@ -28,6 +28,7 @@
 //   k_select_aln.inc     the alignments of a run's kept barcodes or kept read names (ds.mt.py's / ds.reads.withinMT.py's drop, in HBM)
 //                        and the decoder's descriptors over them.
 //   k_read_groups.inc    the file-wide read-name / barcode table of --dsRpbSampler philox (HBM) and each run's keep masks from it.
+//   k_allele_carriers.inc  which barcodes of a run cover / carry a listed allele (--dsAF): two counters per (variant, barcode), then bits.
 //   k_lod.inc            the limit-of-detection table of --lod: per barcode depth the root R's uniroot finds (mt_depths_lod.R), FP64.
 //
 // Data layout (include/smcounter_hip.h): ONE uint32 per pileup read (allele, quality, fragment start, read
@@ -67,6 +68,7 @@
 #include "k_philox_marks.inc" // the non-parity down-sampling of loci over the barcode cap, Philox4x32-10 keyed by position
 #include "k_select_aln.inc"    // in-run molecule down-sampling: the kept barcodes' alignments and their windows / depths
 #include "k_read_groups.inc"   // in-run read down-sampling (philox): the file-wide table of read names and barcodes
+#include "k_allele_carriers.inc" // --dsAF: which barcodes of a run cover / carry a listed allele (bp2_resolve's CIGAR rules)
 #include "k_lod.inc"           // --lod: the limit of detection per barcode depth (one lane per depth, Brent root search in FP64)
 #include "k_plan.inc"          // launch plan of a batch whose descriptors are in HBM (classify + fill)
 #include "host_abi.inc"        // the C ABI of include/smcounter_hip.h

@@ -398,6 +398,11 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
                             p_names = [bam.pair_name(g) for g in range(int(A["n_pair"]))]
                         mask = np.array([t in rule.kept for t in p_names], bool)
                     sel, counts, d_orig = select_run(eng, up, A, lo, mask=mask, level="read")
+            elif rule.dropped_idents is not None:
+                # (--dsAF: every barcode but the dropped carriers)
+                if idents is None:
+                    idents = bam.barcode_idents(A["n_bc"])
+                sel, counts, d_orig = select_run(eng, up, A, lo, mask=~np.isin(idents, rule.dropped_idents))
             elif rule.kept is None:
                 if idents is None:
                     idents = bam.barcode_idents(A["n_bc"])
@@ -659,9 +664,15 @@ class DsRule:
     # `bc_thr` = the --dsMT draw's threshold at f beside `thr`; `n_names` the names of the barcodes kept at f
     grid: bool = False
     bc_thr: int = None
+    # (--dsAF) level "barcode": `af` the target allele fraction, `dropped_idents` the sorted FNV-1a idents of the barcodes that go
+    # (every other barcode stays: ds_af_rules)
+    af: float = None
+    dropped_idents: object = None
 
     @property
     def flag(self) -> str:
+        if self.af is not None:
+            return "--dsAF"
         return "--dsGrid" if self.grid else "--dsRpb" if self.level == "read" else "--dsMT"
 
     @property
@@ -670,6 +681,8 @@ class DsRule:
 
     @property
     def label(self) -> str:
+        if self.af is not None:
+            return "allele fraction %g" % self.af
         if self.grid:
             return "fraction %g x target %g" % (self.frac, self.target)
         return "target %g" % self.target if self.level == "read" else "fraction %g" % self.frac
@@ -1035,6 +1048,127 @@ def select_run(eng, up: RunOnDevice, A, lo: int, mask=None, idents=None, frac: f
         # (alignments flagged neither READ1 nor READ2: the same test as build_run's on the full run, on the kept ones)
         counts["aln"] = A["aln"][d_orig.download(np.uint32, kept)] if kept else A["aln"][:0]
     return sel, counts, d_orig
+
+
+# ---- in-run dilution of listed variants (--dsAF): tools.ds_allele_fraction's drop of the barcodes that carry a listed allele
+AF_DOMAIN = 0x64734146         # counter word 2 of the barcode draw ("dsAF": tools.ds_allele_fraction.philox_word0)
+AF_MAX_INS = 255               # SMC_AF_MAX_INS: inserted letters of a listed insertion
+AF_RUN_LOCI = 512              # listed variants of one chromosome within this many positions share a decoded run of the pre-pass
+_AF_TIMES = {"decode": 0.0, "upload": 0.0, "kernel + download": 0.0, "barcodes of the file": 0.0}   # seconds per stage of the last ds_af_sets / ds_af_rules
+
+
+def af_run_variants(variants, chrom: str, lo: int, fasta):
+    """The listed variants (tools.ds_allele_fraction.Variant, all on `chrom`) of the run that starts at 0-based `lo` as
+    smc_allele_carriers takes them -> (abi.AF_VARIANT_DTYPE array, the pool of inserted letters).  A deletion whose deleted letters
+    are not the reference's is a key no read shows (the caller writes the reference's letters into the key, smCounter.py:394-396)."""
+    from .tools import ds_allele_fraction as af
+    var = np.zeros(len(variants), abi.AF_VARIANT_DTYPE)
+    pool = bytearray()
+    for k, v in enumerate(variants):
+        var[k]["locus"] = v.pos - 1 - lo
+        kind = v.kind
+        if kind == af.SNV:
+            letter, ln = v.alt, 0
+        elif kind == af.INS:
+            letter, ln = v.ref, len(v.alt) - 1
+            var[k]["ins_off"] = len(pool)
+            pool += v.alt[1:].encode()
+        else:
+            letter, ln = v.alt, len(v.ref) - 1
+            if fasta.fetch(chrom, v.pos, v.pos + ln).upper() != v.ref[1:]:
+                kind = af.NONE
+        var[k]["kind"], var[k]["letter"], var[k]["len"] = kind, ord(letter), ln
+    return var, np.frombuffer(bytes(pool) or b"\0", np.uint8).copy()
+
+
+def allele_carriers_run(eng, up: RunOnDevice, A, lo: int, var: np.ndarray, ins: np.ndarray, counts: bool = False):
+    """smc_allele_carriers over the run `up` (A: its counts) -> (covers, carries: bool [n_var, n_bc] by run-wide barcode id; the
+    (reads, alt) counters uint32 [n_var, n_bc, 2] when `counts`, else None)."""
+    from .engine import DevBuf
+    n_var, n_bc = len(var), int(A["n_bc"])
+    nw = 2 * ((n_bc + 63) // 64)
+    if not n_var or not n_bc:
+        z = np.zeros((n_var, n_bc), bool)
+        return z, z.copy(), (np.zeros((n_var, n_bc, 2), np.uint32) if counts else None)
+    var = np.ascontiguousarray(var, abi.AF_VARIANT_DTYPE)
+    d_var = DevBuf(eng, var.nbytes + 256).upload(var.view(np.uint8).reshape(-1))
+    d_ins = DevBuf(eng, len(ins) + 256).upload(np.ascontiguousarray(ins, np.uint8))
+    d_bits = DevBuf(eng, 2 * 4 * nw * n_var + 256)
+    d_cnt = DevBuf(eng, 8 * n_bc * n_var + 256) if counts else None
+    try:
+        _lib.check(eng.L.smc_allele_carriers(eng.ctx, up.aln.data_ptr(), up.n_aln, up.cig.data_ptr(), up.bq.data_ptr(), up.loc.data_ptr(),
+                                             int(A["nl"]), int(lo), n_bc, d_var.data_ptr(), var.ctypes.data, n_var, d_ins.data_ptr(), len(ins),
+                                             d_bits.data_ptr(), d_bits.data_ptr() + 4 * nw * n_var,
+                                             d_cnt.data_ptr() if counts else None, ctypes.c_void_p(0)), "smc_allele_carriers")
+        bits = d_bits.download(np.uint32, 2 * nw * n_var)            # (a copy on the default stream: behind the kernels)
+        cnt = d_cnt.download(np.uint32, 2 * n_bc * n_var).reshape(n_var, n_bc, 2) if counts else None
+    finally:
+        for b in (d_var, d_ins, d_bits, d_cnt):
+            if b is not None:
+                b.free()
+    b = np.unpackbits(bits.view(np.uint8), bitorder="little").reshape(2, n_var, 32 * nw)[:, :, :n_bc].astype(bool)
+    return b[0], b[1], cnt
+
+
+def ds_af_sets(path: str, fasta, variants, params, eng, nthreads: int = 0, max_reads: int = 128_000_000):
+    """The pre-pass of --dsAF: only the runs around the listed loci are decoded (variants of one chromosome within AF_RUN_LOCI
+    positions share one), uploaded and put through smc_allele_carriers; the runs' bits become file-wide identities (FNV-1a of the
+    barcode text) -> (covers, carries): per variant, in the order given, the uint64 identities of the barcodes that cover / carry it."""
+    import time
+    nthreads = nthreads or bamio.host_threads()
+    order = sorted(range(len(variants)), key=lambda k: (variants[k].chrom, variants[k].pos))
+    covers, carries = [None] * len(variants), [None] * len(variants)
+    for k in _AF_TIMES:
+        _AF_TIMES[k] = 0.0
+    bam = bamio.NativeBam(path)
+    try:
+        i = 0
+        while i < len(order):
+            v0 = variants[order[i]]
+            j = i
+            while j + 1 < len(order) and variants[order[j + 1]].chrom == v0.chrom and variants[order[j + 1]].pos - v0.pos < AF_RUN_LOCI:
+                j += 1
+            lo, hi = v0.pos - 1, variants[order[j]].pos
+            t0 = time.perf_counter()
+            A = bam.alignments_run(v0.chrom, lo, hi, max_reads, params, nthreads)
+            t1 = time.perf_counter()
+            nl = int(A["nl"])
+            if nl < 1:
+                raise bamio.BamError("--dsAF: the run %s:%d-%d of the pre-pass could not be decoded" % (v0.chrom, lo + 1, hi))
+            group = [k for k in order[i:j + 1] if variants[k].pos - 1 - lo < nl]     # (a run the decoder cut short: the rest starts the next)
+            var, ins = af_run_variants([variants[k] for k in group], v0.chrom, lo, fasta)
+            run_ref = fasta.fetch(v0.chrom, lo, lo + nl).upper()
+            up = upload_run(eng, A, run_ref)
+            t2 = time.perf_counter()
+            try:
+                cov, car, _ = allele_carriers_run(eng, up, A, lo, var, ins)
+            finally:
+                up.free()
+            idents = bam.barcode_idents(A["n_bc"])
+            for r, k in enumerate(group):
+                covers[k], carries[k] = idents[cov[r][:len(idents)]], idents[car[r][:len(idents)]]
+            t3 = time.perf_counter()
+            _AF_TIMES["decode"] += t1 - t0; _AF_TIMES["upload"] += t2 - t1; _AF_TIMES["kernel + download"] += t3 - t2
+            i += len(group)
+    finally:
+        bam.close()
+    return covers, carries
+
+
+def ds_af_rules(path: str, fasta, variants, targets, params_list, seed: int, eng, nthreads: int = 0):
+    """DsRules of --dsAF: one per target allele fraction, barcode level, a dropped-identity set (tools.ds_allele_fraction's steps 2-4
+    over the pre-pass's sets) -> (rules, titrate()'s result: per target the dropped identities and per variant N, V, a, k, N', V').
+    ValueError: two barcode texts of the file share an identity."""
+    import time
+    from .tools import ds_allele_fraction as af
+    t0 = time.perf_counter()
+    af.unique_idents(bamio.placed_barcodes(path), path)
+    t1 = time.perf_counter()
+    covers, carries = ds_af_sets(path, fasta, variants, params_list[0] if params_list else None, eng, nthreads)
+    _AF_TIMES["barcodes of the file"] = t1 - t0
+    res = af.titrate(covers, carries, targets, seed)
+    rules = [DsRule(1.0, P, seed=int(seed), af=float(t), dropped_idents=r["dropped"]) for t, P, r in zip(targets, params_list, res)]
+    return rules, res
 
 
 def _fnv64(text: str) -> int:

@@ -512,6 +512,34 @@ int smc_allele_carriers(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, c
                         const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0, int64_t n_bc, const smc_af_variant* d_var,
                         const smc_af_variant* var_host, int32_t n_var, const uint8_t* d_ins, int64_t n_ins, uint32_t* d_covers, uint32_t* d_carries,
                         uint32_t* d_counts, void* stream);
+/* (ABI 11, additive: two entries more, the version number unchanged) --dsAFReps: R replicates of the --dsAF dilution, replicate j
+ * with the seed seeds[j]; everything but the barcode draw u_j(b) = word 0 of Philox4x32-10(counter = (identity lo, identity hi,
+ * 0x64734146 "dsAF", 0), key = (seeds[j] lo, hi)) is the same in every replicate.  The CARRIER TABLE is the host's: d_car[n_car],
+ * the identities of the barcodes that carry a listed variant, ascending and unique, and d_car_thr[n_car][n_targets], per carrier
+ * and target the smallest floor(k * 2^32) among the variants it carries (in [0, 2^32]: 64-bit words).  A barcode is DROPPED in
+ * replicate j at target t when the table holds it at c and u_j >= d_car_thr[c][t]; every other barcode is kept.  `car_host` /
+ * `car_thr_host`: the same table in host memory - what is checked.
+ *   _masks   for the n_ids run-wide barcode identities of one decoded run (d_idents: smc_bam_barcode_idents, uploaded):
+ *            d_masks[(j * n_targets + t) * n_words + (g >> 5)] bit (g & 31) = id g is kept - n_reps * n_targets masks of n_words
+ *            uint32 words each, n_words >= ceil(n_ids / 32); the bits at and beyond n_ids and the words behind them are written
+ *            as 0.  Each is a mask smc_select_alignments takes as d_keep_mask.  d_draws (may be NULL): [n_reps][n_ids] the draw of
+ *            every carrier, 0 for the others (tests).
+ *   _counts  the achieved numbers, file-wide: d_cov_ident / d_cov_carry hold the covering barcodes of all n_var listed variants one
+ *            behind the other (variant v's at [cov_off[v], cov_off[v + 1]); carry != 0: the barcode carries v) ->
+ *            d_out[v][j][t][2] uint32 = (N', V'): the kept covering barcodes and the kept carriers of v.  d_cov_off: the n_var + 1
+ *            offsets in device memory, `cov_off_host` the same on the host.  d_out is zeroed by the call.
+ * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched: a table that is not strictly ascending, a threshold above
+ * 2^32, n_targets above SMC_AF_REP_MAX_TARGETS, n_reps above SMC_AF_REP_MAX_REPS, n_words below ceil(n_ids / 32),
+ * n_reps * n_targets * n_words (or n_var * n_reps * n_targets * 2) of 2^32 - 256 words or more, offsets that decrease. */
+#define SMC_AF_REP_MAX_TARGETS 32      /* (= SMC_RG_MAX_TARGETS: the masks one run's launch makes for the selection) */
+#define SMC_AF_REP_MAX_REPS 1000
+int smc_af_rep_masks(smc_ctx* ctx, const uint64_t* d_idents, int64_t n_ids, const uint64_t* d_car, const uint64_t* d_car_thr,
+                     const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets, const uint64_t* d_seeds,
+                     int32_t n_reps, uint32_t* d_masks, int64_t n_words, uint32_t* d_draws, void* stream);
+int smc_af_rep_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint8_t* d_cov_carry, const uint32_t* d_cov_off,
+                      const uint32_t* cov_off_host, int32_t n_var, const uint64_t* d_car, const uint64_t* d_car_thr,
+                      const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets, const uint64_t* d_seeds,
+                      int32_t n_reps, uint32_t* d_out, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

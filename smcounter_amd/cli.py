@@ -114,6 +114,15 @@ def build_parser() -> argparse.ArgumentParser:
                                                         "%d inserted letters) and deletions XD / X; one variant per position, each a locus of "
                                                         "--bedTarget" % AF_MAX_INS)
     p.add_argument("--dsAFMtDepth", default=None, help="comma-separated --mtDepth of each --dsAF target; default --mtDepth")
+    p.add_argument("--dsAFReps", type=int, default=None,
+                   help="replicate dilutions: R in %d .. %d.  Replicate j = 0 .. R - 1 is the dilution of --dsAF with seed (dsSeed + j) "
+                        "mod 2^64 and everything else unchanged (replicate 0 is the run's own .dsAF<t> output at the listed loci).  The "
+                        "replicates' barcode draws and achieved counts are made on the GPU from the pre-pass's carriers, and only the runs "
+                        "around the listed loci are called again, R times per target.  Every other file stays as it is; added: "
+                        "<outPrefix>.dsAF.replicates.txt, one line per listed variant, target and replicate (the line that variant has in "
+                        ".dsAF.detection.txt of a run with --dsSeed of that replicate, with REP and SEED), and "
+                        "<outPrefix>.dsAF.sensitivity.txt, one line per variant and target: replicates called, the detection rate and its "
+                        "Wilson score interval (95 %%%%), the achieved fractions, and with --lod the locus's LOD.  Needs --dsAF" % (REPS_MIN, REPS_MAX))
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -127,6 +136,7 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+REPS_MIN, REPS_MAX = 2, 1000   # (--dsAFReps: dsaf.REPS_MIN / REPS_MAX, SMC_AF_REP_MAX_REPS)
 AF_MAX_INS = 255             # (smc_allele_carriers: SMC_AF_MAX_INS letters per listed insertion)
 GRID_MAX_CELLS = 32          # (a launch takes at most SMC_RG_MAX_TARGETS masks; every cell holds a batch's device arrays)
 
@@ -220,6 +230,22 @@ def ds_af_targets(args):
     return [(t, d, "%s.dsAF%g" % (args.outPrefix, t)) for t, d in zip(ts, depths)]
 
 
+def ds_af_reps(args, af_targets):
+    """--dsAFReps -> R, or None without the flag.  Refused: without --dsAF, R outside REPS_MIN .. REPS_MAX."""
+    reps = getattr(args, "dsAFReps", None)
+    if reps in (None, ""):
+        return None
+    if not af_targets:
+        raise SystemExit("--dsAFReps replicates the dilutions of --dsAF: it needs --dsAF")
+    try:
+        reps = int(reps)
+    except ValueError:
+        raise SystemExit("--dsAFReps: an integer in %d .. %d expected, got %r" % (REPS_MIN, REPS_MAX, reps))
+    if not (REPS_MIN <= reps <= REPS_MAX):
+        raise SystemExit("--dsAFReps: the number of replicates must lie in %d .. %d, got %d" % (REPS_MIN, REPS_MAX, reps))
+    return reps
+
+
 def ds_af_variants(args, loc_list):
     """The variants of --dsAFVariants, checked: the file's own refusals (tools.ds_allele_fraction.parse_variants) and every variant a
     locus of --bedTarget."""
@@ -233,9 +259,9 @@ def ds_af_variants(args, loc_list):
     return variants
 
 
-def ds_af_rules(args, params: VcParams, af_targets, variants, early):
+def ds_af_rules(args, params: VcParams, af_targets, variants, early, keep=None):
     """The devplanes.DsRule of every --dsAF target (the pre-pass on the GPU: devplanes.ds_af_rules) and the titration's numbers; the
-    run log gets a line per variant and target."""
+    run log gets a line per variant and target.  `keep` (--dsAFReps): a dict for what the replicate stage starts from."""
     import dataclasses
     from . import devplanes
     from .tools import ds_allele_fraction as af
@@ -247,7 +273,7 @@ def ds_af_rules(args, params: VcParams, af_targets, variants, early):
         eng = _ENGINES.get(args.device) or _ENGINES.setdefault(args.device, Engine(args.device))
     try:
         rules, res = devplanes.ds_af_rules(args.bamFile, fasta.FastaFile(args.refGenome), variants, [t for t, _, _ in af_targets], plist,
-                                           int(args.dsSeed), eng)
+                                           int(args.dsSeed), eng, keep=keep)
     except (ValueError, bamio.BamError) as e:
         raise SystemExit(str(e))
     for r in res:
@@ -415,6 +441,8 @@ def call_shard(args, params: VcParams, loci, device: int, early=None):
             if lod_cols is not None:
                 lod_cols[0].add(eng.last_rows)
             _report_boundary(eng.last_rows, rb.chrom, rb.pos)
+        if getattr(args, "ds_af_keep", None) is not None:
+            output.af_reps = _ds_af_replicates(args, rules, ref, eng, loci, ds_out)
         if lod_cols is not None:
             output.lod = _lod.run_lods(eng, [params] + [rule.params for rule in rules or ()], lod_cols, args.lodDepth or "UMT")
         _release_engine(eng)
@@ -428,6 +456,24 @@ def call_shard(args, params: VcParams, loci, device: int, early=None):
         output.lod = _lod.run_lods(eng, [params], lod_cols, args.lodDepth or "UMT")
     eng.close()
     return output.done()
+
+
+def _ds_af_replicates(args, rules, ref, eng, loci, ds_out):
+    """--dsAFReps after the run's batches: devplanes.ds_af_replicates over the runs the pre-pass kept, and the check that ties it to
+    the run's own outputs - replicate 0 has the seed of the run, so its row at every listed locus must be the .dsAF<t> output's."""
+    from . import devplanes
+    variants, res = args.ds_af
+    keep, args.ds_af_keep = args.ds_af_keep, None
+    out = devplanes.ds_af_replicates(args.bamFile, ref, variants, [rule.af for rule in rules], [rule.params for rule in rules],
+                                     int(args.dsSeed), int(args.ds_af_reps), eng, keep, res, sampler=getattr(args, "sampler", "reference"),
+                                     sampler_seed=getattr(args, "samplerSeed", 0))
+    index = {(c, int(p)): n for n, (c, p) in enumerate(loci)}
+    for (k, t, j), line in out["rows"].items():
+        v = variants[k]
+        if j == 0 and line != ds_out[t][index[(v.chrom, v.pos)]]:
+            raise RuntimeError("--dsAFReps: replicate 0 of %s:%d at target %g is not the row of the run's own output:\n%s\n%s" %
+                               (v.chrom, v.pos, rules[t].af, line, ds_out[t][index[(v.chrom, v.pos)]]))
+    return out
 
 
 def call_shard_rows(args, params: VcParams, loci, device: int):
@@ -555,6 +601,7 @@ def _main(args) -> int:
     targets = ds_rpb_targets(args)
     cells = ds_grid_cells(args)
     af_targets = ds_af_targets(args)
+    args.ds_af_reps = ds_af_reps(args, af_targets)
     flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets), ("--dsAF", af_targets)) if on)
     if flag and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("%s runs in one process only (not under torch.distributed.run with more than one rank)" % flag)
@@ -575,13 +622,15 @@ def _main(args) -> int:
         early = _EarlyEngine(args.device)
     loc_list = bedops.expand_loci(args.bedTarget)
     rules = []
-    args.ds_af = None
+    args.ds_af = args.ds_af_keep = None
     try:
         if af_targets:
-            # (--dsAF: the listed variants checked, then the pre-pass over the runs around them)
+            # (--dsAF: the listed variants checked, then the pre-pass over the runs around them; --dsAFReps: its runs kept)
             variants = ds_af_variants(args, loc_list)
-            rules, res = ds_af_rules(args, params, af_targets, variants, early)
+            keep = {} if args.ds_af_reps is not None else None
+            rules, res = ds_af_rules(args, params, af_targets, variants, early, keep)
             args.ds_af = (variants, res)
+            args.ds_af_keep = keep
         elif cells:
             # (--dsGrid: the reference's grouping of the names once, for the targets and the cells alike)
             from . import devplanes
@@ -615,6 +664,8 @@ def _main(args) -> int:
     finally:
         from . import devplanes
         devplanes.close_rules(rules)          # (--dsRpbSampler philox: the file-wide table in HBM, whatever happened)
+        if args.ds_af_keep is not None:       # (--dsAFReps: the pre-pass's runs, when the run ended before the replicate stage)
+            devplanes.free_af_runs(args.ds_af_keep.get("runs"))
 
 
 def _run(args, params, fractions, targets, loc_list, early, t0, cells=(), af_targets=()):
@@ -700,6 +751,7 @@ def _run(args, params, fractions, targets, loc_list, early, t0, cells=(), af_tar
         print("--lod %s: %d barcodes needed (mtDepth %d), depth %s, table of %d depths, at most %d iterations" %
               (prefix, o["needed"], mt_depth, args.lodDepth or "UMT", o["table"], o["iters"]))
         lod_entries.append(_lod.summary_entry(prefix, mt_depth, rpb, o["needed"], o["rows"], args.lodDepth or "UMT", o["lods"]))
+    output_raw = output                                   # (--dsAFReps: the replicates' rows hang on the shard's rows)
     output = postfilter.apply_repeat_filters(output, trf, rm, pred=pred)
     threshold = writers.pi_threshold(args.mtDepth, args.threshold)
     writers.write_outputs(args.outPrefix, output, threshold, pred=pred)
@@ -726,7 +778,31 @@ def _run(args, params, fractions, targets, loc_list, early, t0, cells=(), af_tar
         variants, res = args.ds_af
         outs = [(None, args.outPrefix, None, lods[0]["lods"] if lods is not None else None)] + \
                [(t, p, r["rows"], lods[1 + k]["lods"] if lods is not None else None) for k, ((t, _, p), r) in enumerate(zip(af_targets, res))]
-        dsaf.write_detection(args.outPrefix, variants, outs, {(c, "%d" % int(q)): n for n, (c, q) in enumerate(loc_list)})
+        loc_index = {(c, "%d" % int(q)): n for n, (c, q) in enumerate(loc_list)}
+        dsaf.write_detection(args.outPrefix, variants, outs, loc_index)
+        reps = getattr(output_raw, "af_reps", None)
+        if reps is not None:
+            # (--dsAFReps: every replicate's row as its own run would print and cut it, then the rates)
+            entries = {}
+            for i, v in enumerate(variants):
+                for t, (target, d, _) in enumerate(af_targets):
+                    thr_t = writers.pi_threshold(d, args.threshold)
+                    per = []
+                    for j in range(args.ds_af_reps):
+                        row, cut = dsaf.replicate_entry(reps["rows"].get((i, t, j)), thr_t, trf, rm)
+                        per.append((int(reps["counts"][i, j, t, 0]), int(reps["counts"][i, j, t, 1]), row, cut))
+                    entries[(i, t)] = per
+                    called = sum(1 for _, _, _, cut in per if cut is not None and cut[0] == v.ref and v.alt in cut[1])
+                    print("--dsAFReps: %s:%d %s>%s at %g: called %d of %d" % (v.chrom, v.pos, v.ref, v.alt, target, called, args.ds_af_reps))
+            targets_only = [t for t, _, _ in af_targets]
+            dsaf.write_replicates(args.outPrefix, variants, targets_only, reps["seeds"], [[row["k"] for row in r["rows"]] for r in res], entries)
+            lod_vt = None
+            if lods is not None:
+                lod_vt = [[float(lods[1 + t]["lods"][loc_index[(v.chrom, "%d" % v.pos)]]) for v in variants] for t in range(len(af_targets))]
+            dsaf.write_sensitivity(args.outPrefix, variants, targets_only, entries, lod_vt)
+            tm = reps["times"]
+            print("--dsAFReps: replicate stage %.3f s (%d replicates x %d targets: %d builds in %d batches; counts %.4f s, masks %.4f s)" %
+                  (tm["stage"], args.ds_af_reps, len(af_targets), tm["builds"], tm["batches"], tm["counts"], tm["masks"]))
     t1 = datetime.datetime.now()
     print("smCounter completed running at " + str(t1))
     print("smCounter total time: " + str(t1 - t0))

@@ -1094,6 +1094,77 @@ int smc_allele_carriers(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, c
     return SMC_OK;
 }
 
+// (--dsAFReps) what both entries check of the carrier table, on its host copy
+static int afr_check_table(const char* who, const uint64_t* d_car, const uint64_t* d_car_thr, const uint64_t* car_host,
+                           const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets, const uint64_t* d_seeds, int32_t n_reps) {
+    const std::string w(who);
+    if (n_car < 0 || n_car >= (int64_t)0x7FFFFF00 || n_targets < 0 || n_reps < 0) return fail(SMC_E_ARG, w + ": bad argument");
+    if (n_targets > SMC_AF_REP_MAX_TARGETS) return fail(SMC_E_INPUT, w + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_AF_REP_MAX_TARGETS));
+    if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, w + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
+    if (n_reps && !d_seeds) return fail(SMC_E_ARG, w + ": NULL seeds");
+    if (n_car && (!d_car || !car_host || (n_targets && (!d_car_thr || !car_thr_host)))) return fail(SMC_E_ARG, w + ": NULL carrier table");
+    for (int64_t c = 1; c < n_car; ++c)
+        if (car_host[c - 1] >= car_host[c])
+            return fail(SMC_E_INPUT, w + ": the carrier table is not strictly ascending at entry " + std::to_string(c));
+    for (int64_t k = 0; k < n_car * (int64_t)n_targets; ++k)
+        if (car_thr_host[k] > (1ull << 32))
+            return fail(SMC_E_INPUT, w + ": threshold " + std::to_string(k) + " of the carrier table is above 2^32");
+    return SMC_OK;
+}
+
+int smc_af_rep_masks(smc_ctx* ctx, const uint64_t* d_idents, int64_t n_ids, const uint64_t* d_car, const uint64_t* d_car_thr,
+                     const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets, const uint64_t* d_seeds,
+                     int32_t n_reps, uint32_t* d_masks, int64_t n_words, uint32_t* d_draws, void* stream) {
+    if (!ctx || n_ids < 0 || n_ids >= (int64_t)0x7FFFFF00 || n_words < 0) return fail(SMC_E_ARG, "smc_af_rep_masks: bad argument");
+    { const int rc = afr_check_table("smc_af_rep_masks", d_car, d_car_thr, car_host, car_thr_host, n_car, n_targets, d_seeds, n_reps); if (rc) return rc; }
+    if (n_words < (n_ids + 31) / 32)
+        return fail(SMC_E_INPUT, "smc_af_rep_masks: " + std::to_string(n_words) + " words per mask for " + std::to_string(n_ids) + " ids");
+    if ((double)n_reps * (double)n_targets * (double)n_words >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, "smc_af_rep_masks: " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) + " targets x " +
+                                 std::to_string(n_words) + " words: too many mask words for one call");
+    if (!n_reps || !n_targets || !n_words) return SMC_OK;
+    if (!d_masks || (n_ids && !d_idents)) return fail(SMC_E_ARG, "smc_af_rep_masks: NULL argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    const unsigned gx = (unsigned)(((n_words + 1) / 2 * WAVE + AFR_BLOCK - 1) / AFR_BLOCK);      // (two words per wave)
+    hipLaunchKernelGGL(k_afr_masks, dim3(gx, (unsigned)std::min<int32_t>(n_reps, 64)), dim3(AFR_BLOCK), 0, (hipStream_t)stream,
+                       (const unsigned long long*)d_idents, (uint32_t)n_ids, (const unsigned long long*)d_car, (const unsigned long long*)d_car_thr,
+                       (uint32_t)n_car, (int)n_targets, (const unsigned long long*)d_seeds, (int)n_reps, d_masks, (uint32_t)n_words, d_draws);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
+int smc_af_rep_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint8_t* d_cov_carry, const uint32_t* d_cov_off,
+                      const uint32_t* cov_off_host, int32_t n_var, const uint64_t* d_car, const uint64_t* d_car_thr,
+                      const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets, const uint64_t* d_seeds,
+                      int32_t n_reps, uint32_t* d_out, void* stream) {
+    if (!ctx || n_var < 0) return fail(SMC_E_ARG, "smc_af_rep_counts: bad argument");
+    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, "smc_af_rep_counts: " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
+    { const int rc = afr_check_table("smc_af_rep_counts", d_car, d_car_thr, car_host, car_thr_host, n_car, n_targets, d_seeds, n_reps); if (rc) return rc; }
+    if ((double)n_var * (double)n_reps * (double)n_targets * 2.0 >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, "smc_af_rep_counts: " + std::to_string(n_var) + " variants x " + std::to_string(n_reps) + " replicates x " +
+                                 std::to_string(n_targets) + " targets: too many counters for one call");
+    if (!n_var || !n_reps || !n_targets) return SMC_OK;
+    if (!cov_off_host || !d_cov_off || !d_out) return fail(SMC_E_ARG, "smc_af_rep_counts: NULL argument");
+    uint32_t widest = 0;
+    for (int32_t v = 0; v < n_var; ++v) {
+        if (cov_off_host[v + 1] < cov_off_host[v]) return fail(SMC_E_INPUT, "smc_af_rep_counts: the offsets decrease at variant " + std::to_string(v));
+        widest = std::max(widest, cov_off_host[v + 1] - cov_off_host[v]);
+    }
+    if (cov_off_host[n_var] >= 0xFFFFFF00u) return fail(SMC_E_INPUT, "smc_af_rep_counts: too many covering barcodes for one call");
+    if (cov_off_host[n_var] && (!d_cov_ident || !d_cov_carry)) return fail(SMC_E_ARG, "smc_af_rep_counts: NULL covers");
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t n_out = 2 * (size_t)n_var * (size_t)n_reps * (size_t)n_targets;
+    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
+    if (widest)
+        hipLaunchKernelGGL(k_afr_counts, dim3((unsigned)std::min<uint32_t>((widest + AFR_BLOCK - 1) / AFR_BLOCK, 256u), (unsigned)n_var,
+                                              (unsigned)std::min<int32_t>(n_reps, 64)), dim3(AFR_BLOCK), 0, st,
+                           (const unsigned long long*)d_cov_ident, d_cov_carry, d_cov_off, (const unsigned long long*)d_car,
+                           (const unsigned long long*)d_car_thr, (uint32_t)n_car, (int)n_targets, (const unsigned long long*)d_seeds, (int)n_reps, d_out);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
 // (--dsGrid) the cells' thresholds: bc_thr[c] (sel_keep's: floor(f * 2^32), 2^32 keeps every barcode) and rd_thr[c], each <= 2^32
 static int rg_grid_thresholds(const uint64_t* bc_thr, const uint64_t* rd_thr, int32_t n, RgGridThr& T) {
     if (n < 0 || n > SMC_RG_MAX_TARGETS || (n && (!bc_thr || !rd_thr))) return fail(SMC_E_ARG, "smc_read_groups: bad grid thresholds");

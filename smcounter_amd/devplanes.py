@@ -1110,10 +1110,14 @@ def allele_carriers_run(eng, up: RunOnDevice, A, lo: int, var: np.ndarray, ins: 
     return b[0], b[1], cnt
 
 
-def ds_af_sets(path: str, fasta, variants, params, eng, nthreads: int = 0, max_reads: int = 128_000_000):
+def ds_af_sets(path: str, fasta, variants, params, eng, nthreads: int = 0, max_reads: int = 128_000_000, keep: list = None,
+               keep_bytes: int = None):
     """The pre-pass of --dsAF: only the runs around the listed loci are decoded (variants of one chromosome within AF_RUN_LOCI
     positions share one), uploaded and put through smc_allele_carriers; the runs' bits become file-wide identities (FNV-1a of the
-    barcode text) -> (covers, carries): per variant, in the order given, the uint64 identities of the barcodes that cover / carry it."""
+    barcode text) -> (covers, carries): per variant, in the order given, the uint64 identities of the barcodes that cover / carry it.
+    `keep` (--dsAFReps): a list that gets an AfRun per run - decoded and in HBM still, each with a decoder handle of its own (the
+    handle holds the run's records: allele keys, barcode texts), while their host arrays stay within `keep_bytes`; a run beyond
+    that is listed without its arrays and decoded again by the replicate stage."""
     import time
     nthreads = nthreads or bamio.host_threads()
     order = sorted(range(len(variants)), key=lambda k: (variants[k].chrom, variants[k].pos))
@@ -1130,7 +1134,8 @@ def ds_af_sets(path: str, fasta, variants, params, eng, nthreads: int = 0, max_r
                 j += 1
             lo, hi = v0.pos - 1, variants[order[j]].pos
             t0 = time.perf_counter()
-            A = bam.alignments_run(v0.chrom, lo, hi, max_reads, params, nthreads)
+            own = bamio.NativeBam(path) if keep is not None else None
+            A = (own or bam).alignments_run(v0.chrom, lo, hi, max_reads, params, nthreads)
             t1 = time.perf_counter()
             nl = int(A["nl"])
             if nl < 1:
@@ -1140,11 +1145,20 @@ def ds_af_sets(path: str, fasta, variants, params, eng, nthreads: int = 0, max_r
             run_ref = fasta.fetch(v0.chrom, lo, lo + nl).upper()
             up = upload_run(eng, A, run_ref)
             t2 = time.perf_counter()
+            held = False
             try:
                 cov, car, _ = allele_carriers_run(eng, up, A, lo, var, ins)
+                idents = (own or bam).barcode_idents(A["n_bc"])
+                if keep is not None:
+                    size = sum(int(A[x].nbytes) for x in ("aln", "cig", "bq", "loc"))
+                    held = size + sum(r.nbytes for r in keep) <= (AF_KEEP_BYTES if keep_bytes is None else keep_bytes)
+                    keep.append(AfRun(v0.chrom, lo, hi, list(group), nl, size if held else 0, own if held else None, A if held else None,
+                                      up if held else None, run_ref if held else None, idents if held else None))
             finally:
-                up.free()
-            idents = bam.barcode_idents(A["n_bc"])
+                if not held:
+                    up.free()
+                    if own is not None:
+                        own.close()
             for r, k in enumerate(group):
                 covers[k], carries[k] = idents[cov[r][:len(idents)]], idents[car[r][:len(idents)]]
             t3 = time.perf_counter()
@@ -1155,20 +1169,259 @@ def ds_af_sets(path: str, fasta, variants, params, eng, nthreads: int = 0, max_r
     return covers, carries
 
 
-def ds_af_rules(path: str, fasta, variants, targets, params_list, seed: int, eng, nthreads: int = 0):
+def ds_af_rules(path: str, fasta, variants, targets, params_list, seed: int, eng, nthreads: int = 0, keep: dict = None):
     """DsRules of --dsAF: one per target allele fraction, barcode level, a dropped-identity set (tools.ds_allele_fraction's steps 2-4
     over the pre-pass's sets) -> (rules, titrate()'s result: per target the dropped identities and per variant N, V, a, k, N', V').
-    ValueError: two barcode texts of the file share an identity."""
+    ValueError: two barcode texts of the file share an identity.  `keep` (--dsAFReps): a dict that gets what the replicate stage
+    starts from - "runs" (ds_af_sets' kept runs), "covers" and "carries"."""
     import time
     from .tools import ds_allele_fraction as af
     t0 = time.perf_counter()
     af.unique_idents(bamio.placed_barcodes(path), path)
     t1 = time.perf_counter()
-    covers, carries = ds_af_sets(path, fasta, variants, params_list[0] if params_list else None, eng, nthreads)
+    runs = [] if keep is not None else None
+    try:
+        covers, carries = ds_af_sets(path, fasta, variants, params_list[0] if params_list else None, eng, nthreads, keep=runs)
+    except BaseException:
+        free_af_runs(runs)
+        raise
+    if keep is not None:
+        keep.update(runs=runs, covers=covers, carries=carries)
     _AF_TIMES["barcodes of the file"] = t1 - t0
     res = af.titrate(covers, carries, targets, seed)
     rules = [DsRule(1.0, P, seed=int(seed), af=float(t), dropped_idents=r["dropped"]) for t, P, r in zip(targets, params_list, res)]
     return rules, res
+
+
+# ---- replicate dilutions (--dsAFReps): R seeds, the masks and the achieved counts on the device, only the listed runs called
+AF_KEEP_BYTES = 1 << 30        # host bytes of the pre-pass's runs that stay decoded for the replicate stage (as many again in HBM)
+AF_REP_BATCH_SLOTS = 16 << 20  # read slots of one replicate batch: as many replicates of a run as fit are called with one plan
+AF_REP_MAX_TARGETS = 32        # SMC_AF_REP_MAX_TARGETS
+
+
+@dataclasses.dataclass
+class AfRun:
+    """A run of the --dsAF pre-pass kept for the replicate stage: the listed variants it holds (`group`: their indexes) and, while
+    `A` is not None, its alignments on the host, its arrays in HBM (`up`), the decoder handle that holds its records (`bam`) and the
+    identities of its barcodes by run-wide id."""
+    chrom: str
+    lo: int
+    hi: int
+    group: list
+    nl: int
+    nbytes: int = 0
+    bam: object = None
+    A: object = None
+    up: object = None
+    run_ref: str = None
+    idents: object = None
+
+    def free(self):
+        if self.up is not None:
+            self.up.free()
+        if self.bam is not None:
+            self.bam.close()
+        self.up = self.bam = self.A = self.idents = None
+
+
+def free_af_runs(runs):
+    for r in runs or ():
+        r.free()
+
+
+class AfRepTable(object):
+    """The carrier table and the seeds of --dsAFReps in HBM (dsaf.carrier_table; csrc/k_af_reps.inc) with their host copies, and the
+    two calls over them."""
+
+    def __init__(self, eng, idents, thr, seeds):
+        from .engine import DevBuf
+        self.eng = eng
+        self.idents = np.ascontiguousarray(idents, np.uint64)
+        self.thr = np.ascontiguousarray(thr, np.uint64)              # [carriers, targets]
+        self.seeds = np.ascontiguousarray(seeds, np.uint64)
+        if self.thr.ndim != 2 or self.thr.shape[0] != len(self.idents):
+            raise ValueError("AfRepTable: %d carriers, thresholds of shape %r" % (len(self.idents), self.thr.shape))
+        self.n_targets = int(self.thr.shape[1])
+        up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.reshape(-1) if a.size else np.zeros(1, a.dtype))
+        self.d_idents, self.d_thr, self.d_seeds = up(self.idents), up(self.thr), up(self.seeds)
+
+    def _table(self):
+        return (self.d_idents.data_ptr(), self.d_thr.data_ptr(), self.idents.ctypes.data, self.thr.ctypes.data, len(self.idents),
+                self.n_targets, self.d_seeds.data_ptr(), len(self.seeds))
+
+    def masks(self, d_run_idents, n_ids: int, d_masks, n_words: int, d_draws=None):
+        """smc_af_rep_masks: len(seeds) x n_targets keep masks of `n_words` words each over a run's barcode identities (device
+        addresses), replicate-major - mask (j, t) is what select_run(d_mask=...) takes."""
+        _lib.check(self.eng.L.smc_af_rep_masks(self.eng.ctx, d_run_idents, int(n_ids), *self._table(), d_masks, int(n_words), d_draws,
+                                               ctypes.c_void_p(0)), "smc_af_rep_masks")
+
+    def counts(self, covers, carries) -> np.ndarray:
+        """smc_af_rep_counts: uint32 [V, R, T, 2] = (N', V') of every variant, replicate and target, from the identities that cover /
+        carry each variant (made unique here, as titrate() does)."""
+        from .engine import DevBuf
+        covers = [np.unique(np.asarray(c, np.uint64)) for c in covers]
+        off = np.zeros(len(covers) + 1, np.uint32)
+        off[1:] = np.cumsum([len(c) for c in covers])
+        ident = np.concatenate(covers) if covers else np.zeros(0, np.uint64)
+        carry = np.concatenate([np.isin(c, np.asarray(k, np.uint64)) for c, k in zip(covers, carries)]).astype(np.uint8) if covers \
+            else np.zeros(0, np.uint8)
+        n_out = 2 * len(covers) * len(self.seeds) * self.n_targets
+        up = lambda a: DevBuf(self.eng, a.nbytes + 256).upload(a if a.size else np.zeros(1, a.dtype))
+        bufs = [up(ident), up(carry), up(off), DevBuf(self.eng, 4 * max(1, n_out) + 256)]
+        try:
+            _lib.check(self.eng.L.smc_af_rep_counts(self.eng.ctx, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data,
+                                                    len(covers), *self._table(), bufs[3].data_ptr(), ctypes.c_void_p(0)), "smc_af_rep_counts")
+            out = bufs[3].download(np.uint32, n_out) if n_out else np.zeros(0, np.uint32)      # (the default stream: behind the kernel)
+        finally:
+            for b in bufs:
+                b.free()
+        return out.reshape(len(covers), len(self.seeds), self.n_targets, 2)
+
+    def free(self):
+        for b in (self.d_idents, self.d_thr, self.d_seeds):
+            b.free()
+
+
+def mask_words(n_ids: int) -> int:
+    """Words per keep mask as select_run pads a host mask: the bits' bytes rounded up to whole words, and one word more."""
+    return (int(n_ids) + 31) // 32 + 1
+
+
+def _af_rep_call(eng, run: AfRun, table: AfRepTable, d_masks, n_words, todo, P, fasta, variants, max_depth, sampler, sampler_seed, bits):
+    """The builds of `todo` - mask indexes (j * T + t), all of one target - of a kept run appended to one device batch, as
+    _ds_build_run appends successive runs to a _DsBatch, and the batch called with one plan -> (per mask index the listed loci's raw
+    rows, in the order of run.group), or NARROW (a build has no room in 16-bit read words)."""
+    from . import vc
+    A, up, lo, nl, chrom = run.A, run.up, run.lo, run.nl, run.chrom
+    ns_full = int(A["n_slots"])
+    cap = len(todo) * (ns_full + nl) + ns_full + nl + 64
+    d = _DsBatch(eng, cap, bits, False)
+    cp = abi.c_params(P)
+    try:
+        n_loc = 0
+        for m in todo:
+            sel, counts, d_orig = select_run(eng, up, A, lo, d_mask=d_masks.data_ptr() + 4 * n_words * m)
+            got = {}
+
+            def allele_key(ai, qpos, indel, d_orig=d_orig, kept=sel.n_aln, got=got):
+                # (the builder's alignment index counts the KEPT alignments: the decoder's records are those of the full run)
+                if "orig" not in got:
+                    got["orig"] = d_orig.download(np.uint32, kept)
+                return run.bam.allele_key(int(got["orig"][int(ai)]), qpos, indel)
+            try:
+                done = build_run(counts, eng.L, eng, cp, P, chrom, lo, fasta, run.run_ref, [d.words] + d.planes, d.uaux, d.slots,
+                                 d.slots + n_loc, cap, max_depth, allele_key, run.bam.barcode_name, sampler=sampler, sampler_seed=sampler_seed,
+                                 barcode_idents=lambda n: run.idents, uploaded=sel)
+            finally:
+                sel.free(shared=False)
+                d_orig.free()
+            if done is None:
+                raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "a replicate: the device builder does not take it", "--dsAFReps"))
+            if done == NARROW:
+                return NARROW
+            _, ns_k, lc, tb = done
+            d.LC.append(lc)
+            d.tables += tb
+            d.slots += ns_k
+            n_loc += nl
+        lc = d.LC[0] if len(d.LC) == 1 else np.concatenate(d.LC)
+        plan = eng.make_plan(lc)
+        try:
+            out_rows = plan.run_devbuf([d.words, d.uaux[0]], P)
+        finally:
+            plan.close()
+        at = [variants[k].pos - 1 - lo for k in run.group]
+        idx = np.array([b * nl + a for b in range(len(todo)) for a in at], np.int64)
+        view = vc.LocusView([chrom] * len(idx), [lo + 1 + a for _ in todo for a in at], [run.run_ref[a] if a < len(run.run_ref) else "" for _ in todo for a in at],
+                            [d.tables[i] for i in idx.tolist()])
+        text = vc._strings(out_rows[idx].copy(), view, P, fasta)
+        g = len(at)
+        return {m: list(text[b * g:(b + 1) * g]) for b, m in enumerate(todo)}
+    finally:
+        d.free()
+
+
+def ds_af_replicates(path: str, fasta, variants, targets, params_list, seed: int, n_reps: int, eng, keep: dict, res, sampler: str = "reference",
+                     sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000):
+    """The replicate stage of --dsAFReps.  Replicate j is --dsAF with seed (seed + j) mod 2^64: from the pre-pass's sets the carrier
+    table goes up once and smc_af_rep_counts gives every (N', V'); then per kept run smc_af_rep_masks makes all R x T keep masks in
+    one launch, and every (j, t) is select_run(d_mask) -> build_run -> the locus kernels, the replicates of a target appended to one
+    device batch and called with one plan per batch-full.  Replicates of a run whose masks are equal bit for bit are built once.
+    -> dict(seeds, counts: uint32 [V, R, T, 2], rows: {(variant index, target index, replicate): the raw row string at the variant's
+    locus}, times: seconds per part)."""
+    import time
+    from . import dsaf
+    from .engine import DevBuf
+    t_start = time.perf_counter()
+    T = len(targets)
+    if T > AF_REP_MAX_TARGETS:
+        raise ValueError("--dsAFReps: %d --dsAF targets, at most %d" % (T, AF_REP_MAX_TARGETS))
+    seeds = dsaf.rep_seeds(seed, n_reps)
+    idents, thr = dsaf.carrier_table(keep["carries"], [[row["thr"] for row in r["rows"]] for r in res])
+    table = AfRepTable(eng, idents, thr, seeds)
+    times = {"counts": 0.0, "masks": 0.0, "decode again": 0.0, "builds": 0, "batches": 0}
+    rows = {}
+    max_depth = eng.L.smc_build_max_depth()
+    try:
+        t0 = time.perf_counter()
+        counts = table.counts(keep["covers"], keep["carries"])
+        times["counts"] = time.perf_counter() - t0
+        for run in keep["runs"]:
+            if run.A is None:
+                # (over the byte cap of the pre-pass: decoded and uploaded again)
+                t0 = time.perf_counter()
+                run.bam = bamio.NativeBam(path)
+                run.A = run.bam.alignments_run(run.chrom, run.lo, run.hi, max_reads, params_list[0], nthreads or bamio.host_threads())
+                if int(run.A["nl"]) != run.nl:
+                    raise bamio.BamError("--dsAFReps: the run %s:%d-%d was decoded as %d loci, the pre-pass had %d" %
+                                         (run.chrom, run.lo + 1, run.hi, int(run.A["nl"]), run.nl))
+                run.run_ref = fasta.fetch(run.chrom, run.lo, run.lo + run.nl).upper()
+                run.up = upload_run(eng, run.A, run.run_ref)
+                run.idents = run.bam.barcode_idents(run.A["n_bc"])
+                times["decode again"] += time.perf_counter() - t0
+            n_bc = int(run.A["n_bc"])
+            n_words = mask_words(n_bc)
+            d_id = DevBuf(eng, 8 * max(1, n_bc) + 256).upload(np.ascontiguousarray(run.idents, np.uint64) if n_bc else np.zeros(1, np.uint64))
+            d_masks = DevBuf(eng, 4 * n_reps * T * n_words + 256)
+            try:
+                t0 = time.perf_counter()
+                table.masks(d_id.data_ptr(), n_bc, d_masks.data_ptr(), n_words)
+                host = d_masks.download(np.uint32, n_reps * T * n_words).reshape(n_reps, T, n_words)      # (behind the kernel)
+                times["masks"] += time.perf_counter() - t0
+                per_build = int(run.A["n_slots"]) + run.nl
+                room = max(1, AF_REP_BATCH_SLOTS // max(1, per_build))
+                for t in range(T):
+                    # (equal masks, equal rows: a variant that is left alone at t, or draws that drop the same carriers of this run)
+                    first = {}
+                    for j in range(n_reps):
+                        first.setdefault(host[j, t].tobytes(), j)
+                    todo = [j * T + t for j in sorted(first.values())]
+                    got = {}
+                    for b in range(0, len(todo), room):
+                        part = todo[b:b + room]
+                        bits = 16 if (eng.word_bits == 16 and 0 <= params_list[t].minBQ <= 63) else 32
+                        out = _af_rep_call(eng, run, table, d_masks, n_words, part, params_list[t], fasta, variants, max_depth, sampler,
+                                           sampler_seed, bits)
+                        if out == NARROW:
+                            eng.word_bits = 32
+                            out = _af_rep_call(eng, run, table, d_masks, n_words, part, params_list[t], fasta, variants, max_depth, sampler,
+                                               sampler_seed, 32)
+                        got.update(out)
+                        times["builds"] += len(part)
+                        times["batches"] += 1
+                    for j in range(n_reps):
+                        text = got[first[host[j, t].tobytes()] * T + t]
+                        for k, line in zip(run.group, text):
+                            rows[(k, t, j)] = line
+            finally:
+                d_id.free()
+                d_masks.free()
+            run.free()
+    finally:
+        table.free()
+        free_af_runs(keep["runs"])
+    times["stage"] = time.perf_counter() - t_start
+    return dict(seeds=seeds, counts=counts, rows=rows, times=times)
 
 
 def _fnv64(text: str) -> int:

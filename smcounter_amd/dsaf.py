@@ -3,8 +3,16 @@ titration on one page (which listed variant the caller still finds at which achi
 
 The semantics are tools/ds_allele_fraction.py's (DESIGN.md "--dsAF"); the pre-pass that finds the carriers on the GPU is
 devplanes.ds_af_rules.
+
+--dsAFReps: the carrier table the device draws the replicates' masks and counts from, and the two files that turn R x T calls into
+a detection rate with an interval - <outPrefix>.dsAF.replicates.txt and .dsAF.sensitivity.txt (the replicate stage itself is
+devplanes.ds_af_replicates).
 """
 from __future__ import annotations
+
+import math
+
+import numpy as np
 
 from .py2compat import py2_round, py2_str
 from .rows import HEADER_ALL
@@ -76,3 +84,102 @@ def check_variants(variants, loc_list) -> None:
     for v in variants:
         if (v.chrom, v.pos) not in loci:
             raise ValueError("--dsAFVariants: %s:%d %s>%s is not a locus of --bedTarget" % (v.chrom, v.pos, v.ref, v.alt))
+
+
+# ---- --dsAFReps
+REPS_MIN, REPS_MAX = 2, 1000
+REPLICATES_HEADER = DETECTION_HEADER[:5] + ("REP", "SEED") + DETECTION_HEADER[5:]
+SENSITIVITY_HEADER = ("CHROM", "POS", "REF", "ALT", "TARGET", "REPS", "CALLED", "RATE", "LO95", "HI95", "AF_MEAN", "AF_MIN", "AF_MAX",
+                      "V_MIN", "V_MAX", "PI_MEAN", "PI_MIN")
+WILSON_Z = 1.959963984540054
+
+
+def rep_seeds(seed: int, n_reps: int):
+    """The seed of every replicate: s_j = (seed + j) mod 2^64 (replicate 0 is the run's own --dsAF draw)."""
+    return [(int(seed) + j) & 0xFFFFFFFFFFFFFFFF for j in range(int(n_reps))]
+
+
+def carrier_table(carries, thr):
+    """The table the replicates are drawn from -> (idents: the sorted unique uint64 identities of the barcodes that carry at least
+    one listed variant, uint64 [C, T]: per carrier and target the smallest threshold among the variants it carries).  carries[v]: the
+    identities that carry variant v; thr[t][v]: titrate()'s threshold of v at target t (up to 2^32).  A barcode is dropped at t when
+    any variant it carries draws it out (tools/ds_allele_fraction.py step 3): u(b) >= the smallest of them."""
+    carries = [np.unique(np.asarray(c, np.uint64)) for c in carries]
+    idents = np.unique(np.concatenate(carries)) if carries else np.zeros(0, np.uint64)
+    table = np.full((len(idents), len(thr)), 1 << 32, np.uint64)
+    for t, row in enumerate(thr):
+        for c, h in zip(carries, row):
+            at = np.searchsorted(idents, c)
+            table[at, t] = np.minimum(table[at, t], np.uint64(h))
+    return idents, table
+
+
+def wilson(called: int, reps: int, z: float = WILSON_Z):
+    """The Wilson score interval of called / reps -> (lo, hi), clamped to [0, 1]."""
+    n, p = float(reps), float(called) / float(reps)
+    den = 1.0 + z * z / n
+    mid = (p + z * z / (2.0 * n)) / den
+    half = z * math.sqrt(p * (1.0 - p) / n + z * z / (4.0 * n * n)) / den
+    return max(0.0, mid - half), min(1.0, mid + half)
+
+
+def replicate_entry(row_text, threshold: int, trf, rm):
+    """One replicate's raw row at a listed locus (None: no row) as the run's files would hold it -> (the fields of its .all.txt line,
+    (REF, ALT list) of its .cut.txt line or None): the row through postfilter.apply_repeat_filters, then the writers' cut rule."""
+    from . import postfilter, writers
+    if row_text is None:
+        return None, None
+    row = list(postfilter.apply_repeat_filters([row_text], trf, rm))[0]
+    hit = writers.cut_row(row, threshold)
+    return row.split("\t"), (None if hit is None else (hit[1]["REF"], hit[1]["ALT"].split(",")))
+
+
+def replicate_line(v, target, rep: int, seed: int, n2: int, v2: int, k: float, row, cut) -> str:
+    """detection_line() of one replicate with REP and SEED behind TARGET (no LOD column)."""
+    f = detection_line(v, target, n2, v2, k, row, cut).split("\t")
+    return "\t".join(f[:5] + ["%d" % rep, "%d" % seed] + f[5:])
+
+
+def _pi(row) -> float:
+    text = row[_COL["PI"]] if row is not None and len(row) > _COL["PI"] else ""
+    try:
+        return float(text)
+    except ValueError:
+        return 0.0
+
+
+def sensitivity_line(v, target, reps, lod=None) -> str:
+    """One line of the sensitivity table: variant `v` at `target` over its replicates.  `reps`: per replicate (N', V', row fields or
+    None, cut or None) - what replicate_line() takes; `lod`: the locus's LOD in the run's own output of that target, with --lod."""
+    n = len(reps)
+    called = sum(1 for _, _, _, cut in reps if cut is not None and cut[0] == v.ref and v.alt in cut[1])
+    lo, hi = wilson(called, n)
+    afs = [float(v2) / n2 if n2 else 0.0 for n2, v2, _, _ in reps]
+    pis = [_pi(row) for _, _, row, _ in reps]
+    f = [v.chrom, "%d" % v.pos, v.ref, v.alt, target_text(target), "%d" % n, "%d" % called, frac_text(float(called) / n), frac_text(lo),
+         frac_text(hi), frac_text(sum(afs) / n), frac_text(min(afs)), frac_text(max(afs)), "%d" % min(v2 for _, v2, _, _ in reps),
+         "%d" % max(v2 for _, v2, _, _ in reps), frac_text(sum(pis) / n), frac_text(min(pis))]
+    if lod is not None:
+        f.append("%.15g" % lod)
+    return "\t".join(f)
+
+
+def write_replicates(out_prefix: str, variants, targets, seeds, ks, entries) -> None:
+    """<outPrefix>.dsAF.replicates.txt: a header, then a line per listed variant (file order), target (the order given) and replicate
+    (ascending).  ks[t][v]: the keep probability; entries[(v, t)]: per replicate (N', V', row fields or None, cut or None)."""
+    with open(out_prefix + ".dsAF.replicates.txt", "w") as fh:
+        fh.write("\t".join(REPLICATES_HEADER) + "\n")
+        for i, v in enumerate(variants):
+            for t, target in enumerate(targets):
+                for j, (n2, v2, row, cut) in enumerate(entries[(i, t)]):
+                    fh.write(replicate_line(v, target, j, seeds[j], n2, v2, ks[t][i], row, cut) + "\n")
+
+
+def write_sensitivity(out_prefix: str, variants, targets, entries, lods=None) -> None:
+    """<outPrefix>.dsAF.sensitivity.txt: a header, then a line per listed variant and target.  lods[t][v] (with --lod): the LOD of the
+    variant's locus in the run's .dsAF<t> output."""
+    with open(out_prefix + ".dsAF.sensitivity.txt", "w") as fh:
+        fh.write("\t".join(SENSITIVITY_HEADER + (("LOD",) if lods is not None else ())) + "\n")
+        for i, v in enumerate(variants):
+            for t, target in enumerate(targets):
+                fh.write(sensitivity_line(v, target, entries[(i, t)], None if lods is None else float(lods[t][i])) + "\n")

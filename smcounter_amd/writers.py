@@ -60,6 +60,21 @@ def _genotype(chrom: str, alts: List[str], vmf: str) -> str:
     return "1/1" if float(vmf) > 0.95 else "0/1"
 
 
+def cut_row(row: str, threshold: int):
+    """The cut rule of the two .cut files (smCounter.py:787-901): a row goes into .cut.txt / .cut.vcf when it has a PI (not a Zero_Coverage row), the
+    truncated PI reaches the threshold and its ALT is not 'DEL' -> (the truncated PI as text, the row's fields by column name), else
+    None."""
+    i_pi, i_alt = _COL["PI"], _COL["ALT"]
+    f = row.split("\t", i_pi + 1)                            # (most rows stop here: PI below the threshold)
+    if not f[i_pi]:
+        return None                                          # Zero_Coverage rows
+    qual = str(int(float(f[i_pi])))                          # truncated, phred-like
+    if int(qual) < threshold or f[i_alt] == "DEL":
+        return None
+    f = row.split("\t")
+    return qual, {name: f[i] for name, i in _COL.items()}
+
+
 def write_outputs(out_prefix: str, rows: List[str], threshold: int, pred=None) -> None:
     """rows: post-filtered 45-column strings in locus order.  `pred` (optional, rows.RowLines.pred): per row int(float(PI)) where
     the native printer knows it - rows below the threshold are then not split again to find that out."""
@@ -78,16 +93,11 @@ def write_outputs(out_prefix: str, rows: List[str], threshold: int, pred=None) -
         f_vcf.write("\n".join(_VCF_META) + "\n" + sample_col + "\n")
         if len(rows):
             f_all.write(getattr(rows, "text", None) or "\n".join(rows) + "\n")     # (postfilter._PassRows brings its text)
-        i_pi, i_alt = _COL["PI"], _COL["ALT"]
         for row in cut_rows:
-            f = row.split("\t", i_pi + 1)                    # (most rows stop here: PI below the threshold)
-            if not f[i_pi]:
-                continue                                     # Zero_Coverage rows
-            qual = str(int(float(f[i_pi])))                  # truncated, phred-like
-            if int(qual) < threshold or f[i_alt] == "DEL":
+            hit = cut_row(row, threshold)
+            if hit is None:
                 continue
-            f = row.split("\t")
-            g = {name: f[i] for name, i in _COL.items()}
+            qual, g = hit
             thr = str(threshold)
             info = ";".join(k + "=" + v for k, v in (
                 ("TYPE", g["TYPE"]), ("DP", g["DP"]), ("MT", g["MT"]), ("UMT", g["UMT"]), ("PI", g["PI"]),

@@ -12,12 +12,16 @@ repeat BEDs are absent the repeat flags are skipped with a note instead of faili
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import datetime
 import os
 import sys
 
-from . import _lib, bamio, bedops, fasta, postfilter, runlog, vc, writers
+import numpy as np
+
+from . import _lib, abi, bamio, bedops, devplanes, fasta, postfilter, runlog, vc, writers
 from . import dist as smcdist
+from .engine import Engine
 from .params import VcParams
 
 
@@ -141,6 +145,21 @@ AF_MAX_INS = 255             # (smc_allele_carriers: SMC_AF_MAX_INS letters per 
 GRID_MAX_CELLS = 32          # (a launch takes at most SMC_RG_MAX_TARGETS masks; every cell holds a batch's device arrays)
 
 
+def _ds_mt_depths(args, flag, n, what, default):
+    """--<flag>, the comma-separated --mtDepth of each of the n `what` -> n depths; default() without the flag (called only then:
+    tests hand these helpers namespaces that lack --mtDepth)."""
+    text = getattr(args, flag, None)
+    if text in (None, ""):
+        return default()
+    try:
+        depths = [int(x) for x in str(text).split(",") if x.strip()]
+    except ValueError:
+        raise SystemExit("--%s: comma-separated integers expected, got %r" % (flag, text))
+    if len(depths) != n:
+        raise SystemExit("--%s: %d depths for %d %s" % (flag, len(depths), n, what))
+    return depths
+
+
 def ds_fractions(args):
     """--dsMT / --dsMtDepth -> [(f, mtDepth of f, output prefix)]; [] without --dsMT."""
     from .py2compat import py2_round
@@ -153,16 +172,7 @@ def ds_fractions(args):
         raise SystemExit("--dsMT: comma-separated fractions in (0, 1] expected, got %r" % text)
     if not fr or any(not (0.0 < f <= 1.0) for f in fr):
         raise SystemExit("--dsMT: every fraction must lie in (0, 1], got %r" % text)
-    dtext = getattr(args, "dsMtDepth", None)
-    if dtext not in (None, ""):
-        try:
-            depths = [int(x) for x in str(dtext).split(",") if x.strip()]
-        except ValueError:
-            raise SystemExit("--dsMtDepth: comma-separated integers expected, got %r" % dtext)
-        if len(depths) != len(fr):
-            raise SystemExit("--dsMtDepth: %d depths for %d --dsMT fractions" % (len(depths), len(fr)))
-    else:
-        depths = [max(1, int(py2_round(f * args.mtDepth))) for f in fr]
+    depths = _ds_mt_depths(args, "dsMtDepth", len(fr), "--dsMT fractions", lambda: [max(1, int(py2_round(f * args.mtDepth))) for f in fr])
     return [(f, d, "%s.dsMT%g" % (args.outPrefix, f)) for f, d in zip(fr, depths)]
 
 
@@ -179,16 +189,7 @@ def ds_rpb_targets(args):
         raise SystemExit("--dsRpb: comma-separated reads-per-barcode targets > 0 expected, got %r" % text)
     if not rs or any(not (r > 0.0 and r < float("inf")) for r in rs):
         raise SystemExit("--dsRpb: every target must be a number > 0, got %r" % text)
-    dtext = getattr(args, "dsRpbMtDepth", None)
-    if dtext not in (None, ""):
-        try:
-            depths = [int(x) for x in str(dtext).split(",") if x.strip()]
-        except ValueError:
-            raise SystemExit("--dsRpbMtDepth: comma-separated integers expected, got %r" % dtext)
-        if len(depths) != len(rs):
-            raise SystemExit("--dsRpbMtDepth: %d depths for %d --dsRpb targets" % (len(depths), len(rs)))
-    else:
-        depths = [int(args.mtDepth)] * len(rs)
+    depths = _ds_mt_depths(args, "dsRpbMtDepth", len(rs), "--dsRpb targets", lambda: [int(args.mtDepth)] * len(rs))
     if getattr(args, "dsSampler", "reference") == "philox" and not getattr(args, "dsGrid", False):
         # (--dsGrid decides on the pair of samplers itself: ds_grid_cells)
         raise SystemExit("--dsRpb keeps the reference's read names only: --dsSampler philox is not available with it (a rule for "
@@ -217,16 +218,7 @@ def ds_af_targets(args):
     other = [f for f in ("dsMT", "dsRpb", "dsGrid") if getattr(args, f, None) not in (None, "", False)]
     if other:
         raise SystemExit("--dsAF cannot be combined with --%s in one run (the cross product is not built)" % other[0])
-    dtext = getattr(args, "dsAFMtDepth", None)
-    if dtext not in (None, ""):
-        try:
-            depths = [int(x) for x in str(dtext).split(",") if x.strip()]
-        except ValueError:
-            raise SystemExit("--dsAFMtDepth: comma-separated integers expected, got %r" % dtext)
-        if len(depths) != len(ts):
-            raise SystemExit("--dsAFMtDepth: %d depths for %d --dsAF targets" % (len(depths), len(ts)))
-    else:
-        depths = [int(args.mtDepth)] * len(ts)
+    depths = _ds_mt_depths(args, "dsAFMtDepth", len(ts), "--dsAF targets", lambda: [int(args.mtDepth)] * len(ts))
     return [(t, d, "%s.dsAF%g" % (args.outPrefix, t)) for t, d in zip(ts, depths)]
 
 
@@ -259,21 +251,50 @@ def ds_af_variants(args, loc_list):
     return variants
 
 
-def ds_af_rules(args, params: VcParams, af_targets, variants, early, keep=None):
-    """The devplanes.DsRule of every --dsAF target (the pre-pass on the GPU: devplanes.ds_af_rules) and the titration's numbers; the
-    run log gets a line per variant and target.  `keep` (--dsAFReps): a dict for what the replicate stage starts from."""
-    import dataclasses
-    from . import devplanes
-    from .tools import ds_allele_fraction as af
-    plist = [dataclasses.replace(params, mtDepth=d) for _, d, _ in af_targets]
+@dataclasses.dataclass
+class _Output:
+    """One output of a run: the prefix of its files and the VcParams it is called with (params.mtDepth and params.rpb are its depth and
+    its reads per barcode).  Output 0 of a run is the full-depth one; every other has a `rule`, once the rule makers below have run."""
+    prefix: str
+    params: VcParams
+    kind: str = "full"          # full, dsMT, dsRpb, dsGrid or dsAF
+    frac: float = None          # (dsMT, dsGrid) the fraction of the barcodes
+    target: float = None        # (dsRpb, dsGrid) the reads per barcode asked for
+    af: float = None            # (dsAF) the target allele fraction
+    rule: object = None         # the devplanes.DsRule that selects it; None: full depth
+
+
+@dataclasses.dataclass
+class _Plan:
+    """What a run is to do beyond its command line: its outputs in the order they are called, written and summarised (full depth,
+    fractions, targets, cells, allele fractions), the engine coming up, and the state of --dsAF."""
+    outputs: list
+    early: object = None
+    variants: list = None       # (--dsAF) the listed variants and titrate()'s result per target
+    res: list = None
+    reps: int = None            # (--dsAFReps) R, and what the pre-pass kept for the replicate stage (None once that has taken it)
+    keep: dict = None
+
+    @property
+    def rules(self):
+        return [o.rule for o in self.outputs if o.rule is not None]
+
+
+def _engine_of(args, early):
+    """The engine coming up in the helper thread, else the process's engine (it stays in _ENGINES; call_shard takes it out)."""
     if early is not None:
-        eng = early.get()
-    else:
-        from .engine import Engine
-        eng = _ENGINES.get(args.device) or _ENGINES.setdefault(args.device, Engine(args.device))
+        return early.get()
+    return _ENGINES.get(args.device) or _ENGINES.setdefault(args.device, Engine(args.device))
+
+
+def ds_af_rules(args, outs, variants, early, keep=None):
+    """The devplanes.DsRule of every --dsAF output (the pre-pass on the GPU: devplanes.ds_af_rules) and the titration's numbers; the
+    run log gets a line per variant and target.  `keep` (--dsAFReps): a dict for what the replicate stage starts from."""
+    from .tools import ds_allele_fraction as af
+    eng = _engine_of(args, early)
     try:
-        rules, res = devplanes.ds_af_rules(args.bamFile, fasta.FastaFile(args.refGenome), variants, [t for t, _, _ in af_targets], plist,
-                                           int(args.dsSeed), eng, keep=keep)
+        rules, res = devplanes.ds_af_rules(args.bamFile, fasta.FastaFile(args.refGenome), variants, [o.af for o in outs],
+                                           [o.params for o in outs], int(args.dsSeed), eng, keep=keep)
     except (ValueError, bamio.BamError) as e:
         raise SystemExit(str(e))
     for r in res:
@@ -301,16 +322,13 @@ def ds_grid_cells(args):
     return [(f, r, d, "%s.dsMT%g.dsRpb%g" % (args.outPrefix, f, r)) for f, d, _ in fractions for r, _, _ in targets]
 
 
-def ds_grid_rules(args, params: VcParams, cells, frac_rules, rpb_rules, grouped=None):
+def ds_grid_rules(args, outs, frac_rules, rpb_rules, grouped=None):
     """The devplanes.DsRule of every --dsGrid cell, after the fractions' and the targets' rules: the reference's names from the
     fractions' kept barcodes and the targets' grouping (`grouped`), or with the philox samplers from the targets' file-wide table; a
     cell whose kept barcodes have no barcode of two or more reads ends the run with a message."""
-    import dataclasses
-    from . import devplanes
-    plist = [dataclasses.replace(params, mtDepth=d, rpb=r) for _, r, d, _ in cells]
-    fr = [(f, r) for f, r, _, _ in cells]
+    fr, plist = [(o.frac, o.target) for o in outs], [o.params for o in outs]
     try:
-        if (getattr(args, "dsRpbSampler", None) or "reference") == "philox":
+        if args.dsRpbSampler == "philox":
             return devplanes.philox_grid_rules(args.bamFile, fr, plist, int(args.dsSeed), rpb_rules[0].groups)
         kept = {rule.frac: rule.kept for rule in frac_rules}
         return devplanes.reference_grid_rules(args.bamFile, fr, plist, int(args.dsSeed), kept, grouped)
@@ -318,36 +336,23 @@ def ds_grid_rules(args, params: VcParams, cells, frac_rules, rpb_rules, grouped=
         raise SystemExit(str(e))
 
 
-def ds_rpb_rules(args, params: VcParams, targets, early=None, grouped=None):
+def ds_rpb_rules(args, outs, early=None, grouped=None):
     """The devplanes.DsRule of every --dsRpb target: the reference's read names (one pass over the whole file, here), or with
     --dsRpbSampler philox the file-wide table on the GPU (`early`: the engine coming up; else the process's engine); a file without a
     barcode of two or more reads, or whose names collide in the table's hashes, ends the run with a message."""
-    import dataclasses
-    from . import devplanes
-    plist = [dataclasses.replace(params, mtDepth=d, rpb=r) for r, d, _ in targets]
-    rs = [r for r, _, _ in targets]
+    rs, plist = [o.target for o in outs], [o.params for o in outs]
     try:
-        if (getattr(args, "dsRpbSampler", None) or "reference") == "philox":
-            if early is not None:
-                eng = early.get()
-            else:
-                from .engine import Engine
-                eng = _ENGINES.get(args.device) or _ENGINES.setdefault(args.device, Engine(args.device))
-            return devplanes.philox_read_rules(args.bamFile, rs, plist, int(args.dsSeed), eng)
-        if grouped is not None:
-            return devplanes.reference_read_rules(args.bamFile, rs, plist, int(args.dsSeed), grouped=grouped)
-        return devplanes.reference_read_rules(args.bamFile, rs, plist, int(args.dsSeed))
+        if args.dsRpbSampler == "philox":
+            return devplanes.philox_read_rules(args.bamFile, rs, plist, int(args.dsSeed), _engine_of(args, early))
+        return devplanes.reference_read_rules(args.bamFile, rs, plist, int(args.dsSeed), grouped=grouped)
     except ValueError as e:
         raise SystemExit(str(e))
 
 
-def ds_rules(args, params: VcParams, fractions):
+def ds_rules(args, outs):
     """The devplanes.DsRule of every --dsMT fraction (the reference's sampler: one pass over the whole file, here)."""
-    import dataclasses
-    from . import devplanes
-    plist = [dataclasses.replace(params, mtDepth=d) for _, d, _ in fractions]
-    fr = [f for f, _, _ in fractions]
-    if getattr(args, "dsSampler", "reference") == "philox":
+    fr, plist = [o.frac for o in outs], [o.params for o in outs]
+    if args.dsSampler == "philox":
         return [devplanes.DsRule(f, P, kept=None, seed=int(args.dsSeed)) for f, P in zip(fr, plist)]
     return devplanes.reference_rules(args.bamFile, fr, plist, int(args.dsSeed))
 
@@ -362,8 +367,6 @@ class _EarlyEngine(object):
 
         def work():
             try:
-                from . import _lib
-                from .engine import Engine
                 _lib.load(with_torch=False)
                 self._eng = _ENGINES.pop(device, None) or Engine(device)
             except BaseException as e:
@@ -381,42 +384,47 @@ class _EarlyEngine(object):
 _ENGINES = {}          # device -> Engine kept for the process's next run (smc_create + the first allocations are ~ 0.1 s)
 
 
-def _release_engine(eng):
+def _release_engine(eng, keep=True):
     """The engine stays with the process: a second main() in the same process finds the context, its tables and its buffers
     again, and the command line does not spend 20 ms of its wall time freeing device memory the exiting process gives back
-    anyway (SMC_CLOSE_ENGINE=1: close it, as round 2 did)."""
-    if _lib.exp_env("SMC_CLOSE_ENGINE"):
-        _ENGINES.pop(eng.device, None)
-        eng.close()
-    else:
+    anyway (SMC_CLOSE_ENGINE=1: close it, as round 2 did).  `keep` False: an engine that took host-built batches is closed."""
+    if keep and not _lib.exp_env("SMC_CLOSE_ENGINE"):
         _ENGINES[eng.device] = eng
+    else:
+        _ENGINES.pop(eng.device, None)      # (nothing there after call_shard or the helper thread took the engine out)
+        eng.close()
 
 
-def call_shard(args, params: VcParams, loci, device: int, early=None):
-    """The per-locus rows (strings, smCounter.py:599) of a run of loci: BAM decode -> device batches -> kernels."""
-    from .engine import Engine
+@dataclasses.dataclass
+class _Shard:
+    """What call_shard hands back."""
+    rows: list                  # the row strings of the full-depth output
+    ds: tuple = ()              # the rows of every further output, in the plan's order
+    lod: list = None            # (--lod) per output what lod.run_lods made
+    af_reps: dict = None        # (--dsAFReps) what devplanes.ds_af_replicates made
+
+
+def call_shard(args, params: VcParams, loci, device: int, early=None, plan=None):
+    """The per-locus rows (strings, smCounter.py:599) of a run of loci, for every output of `plan` (none: the full-depth output
+    alone): BAM decode -> device batches -> kernels."""
     ref = fasta.FastaFile(args.refGenome)
     eng = early.get() if early is not None else (_ENGINES.pop(device, None) or Engine(device))
-    output = _Rows()
+    outputs = plan.outputs if plan is not None else [_Output(args.outPrefix, params)]
+    rules = [o.rule for o in outputs[1:]] or None
     decoder = os.environ.get("SMC_BAM_DECODER", "native")
-    rules = getattr(args, "ds_rules", None) or None
-    # (--lod: three int32 columns of every output's rows, full depth first, and the tables while the engine is alive)
-    lod_cols = None
-    if getattr(args, "lod", False):
-        from . import lod as _lod
-        lod_cols = [_lod.DepthCols() for _ in range(1 + len(rules or ()))]
     # (one process per GPU: the ranks of a node share its cores for decoding)
     # (LOCAL_WORLD_SIZE: WORLD_SIZE also counts the ranks of other nodes, which do not share these cores)
     per_node = int(os.environ.get("LOCAL_WORLD_SIZE") or os.environ.get("WORLD_SIZE", "1"))
     nthreads = bamio.host_threads(per_node)
+    resident = False
     if rules is None and decoder == "python":                         # readable decoder, same batches
-        batches = bamio.iter_pileup_batches(bamio.BamFile(args.bamFile), ref, loci, max_reads=args.batchReads)
+        batches = _prefetch(bamio.iter_pileup_batches(bamio.BamFile(args.bamFile), ref, loci, max_reads=args.batchReads))
     elif rules is None and os.environ.get("SMC_PLANES", "device") == "host":   # planes built by the host threads, then uploaded
-        batches = bamio.iter_device_batches_native(args.bamFile, ref, loci, params, max_reads=args.batchReads,
-                                                   nthreads=nthreads)
+        batches = _prefetch(bamio.iter_device_batches_native(args.bamFile, ref, loci, params, max_reads=args.batchReads,
+                                                             nthreads=nthreads))
     else:
         # default: the host decodes alignments, the GPU builds the planes from them (k_build_planes) and they stay in HBM
-        from . import devplanes
+        resident = True
         # (a batch only lives in HBM here - 16 B per read - so it can be eight times the host-built default)
         # (--dsMT: the same batches at full depth and for every fraction - the device builder only, SMC_PLANES=host or
         # SMC_BAM_DECODER=python end with an error naming the first run)
@@ -429,59 +437,52 @@ def call_shard(args, params: VcParams, loci, device: int, early=None):
         # the two threads use different staging buffers of the engine, device work is ordered by the default stream)
         if not _lib.exp_env("SMC_NO_PREFETCH"):
             batches = _prefetch(batches, depth=1)
-        ds_out = [_Rows() for _ in (rules or ())]
-        for first, rb in batches:
-            if rules is not None:
-                rb, rbs = rb[0], rb[1:]
-                for k, (rule, o, b) in enumerate(zip(rules, ds_out, rbs)):
-                    o.add(vc.vc_resident(b, rule.params, ref, eng))
-                    if lod_cols is not None:
-                        lod_cols[1 + k].add(eng.last_rows)
-            output.add(vc.vc_resident(rb, params, ref, eng))
+    call = vc.vc_resident if resident else vc.vc_batch
+    rows = [_Rows() for _ in outputs]
+    # (--lod: three int32 columns of every output's rows, and the tables while the engine is alive)
+    lod_cols = None
+    if getattr(args, "lod", False):
+        from . import lod as _lod
+        lod_cols = [_lod.DepthCols() for _ in outputs]
+    # (the full-depth output is called last: the boundary notes read its rows in the engine's staging memory)
+    order = list(range(1, len(outputs))) + [0]
+    for first, b in batches:
+        bs = b if rules is not None else [b]
+        for k in order:
+            rows[k].add(call(bs[k], outputs[k].params, ref, eng))
             if lod_cols is not None:
-                lod_cols[0].add(eng.last_rows)
-            _report_boundary(eng.last_rows, rb.chrom, rb.pos)
-        if getattr(args, "ds_af_keep", None) is not None:
-            output.af_reps = _ds_af_replicates(args, rules, ref, eng, loci, ds_out)
-        if lod_cols is not None:
-            output.lod = _lod.run_lods(eng, [params] + [rule.params for rule in rules or ()], lod_cols, args.lodDepth or "UMT")
-        _release_engine(eng)
-        output.ds = [o.done() for o in ds_out]
-        return output.done()
-    for first, pb in _prefetch(batches):
-        output.add(vc.vc_batch(pb, params, ref, eng=eng))
-        if lod_cols is not None:
-            lod_cols[0].add(eng.last_rows)
+                lod_cols[k].add(eng.last_rows)
+        if resident:
+            _report_boundary(eng.last_rows, bs[0].chrom, bs[0].pos)
+    shard = _Shard(rows[0].done(), [r.done() for r in rows[1:]])
+    if plan is not None and plan.keep is not None:
+        shard.af_reps = _ds_af_replicates(args, plan, ref, eng, loci, shard.ds)
     if lod_cols is not None:
-        output.lod = _lod.run_lods(eng, [params], lod_cols, args.lodDepth or "UMT")
-    eng.close()
-    return output.done()
+        shard.lod = _lod.run_lods(eng, [o.params for o in outputs], lod_cols, args.lodDepth or "UMT")
+    _release_engine(eng, keep=resident)
+    return shard
 
 
-def _ds_af_replicates(args, rules, ref, eng, loci, ds_out):
+def _ds_af_replicates(args, plan, ref, eng, loci, ds_rows):
     """--dsAFReps after the run's batches: devplanes.ds_af_replicates over the runs the pre-pass kept, and the check that ties it to
     the run's own outputs - replicate 0 has the seed of the run, so its row at every listed locus must be the .dsAF<t> output's."""
-    from . import devplanes
-    variants, res = args.ds_af
-    keep, args.ds_af_keep = args.ds_af_keep, None
-    out = devplanes.ds_af_replicates(args.bamFile, ref, variants, [rule.af for rule in rules], [rule.params for rule in rules],
-                                     int(args.dsSeed), int(args.ds_af_reps), eng, keep, res, sampler=getattr(args, "sampler", "reference"),
+    outs, variants = plan.outputs[1:], plan.variants
+    keep, plan.keep = plan.keep, None           # (the stage frees the kept runs itself, whatever happens in it)
+    out = devplanes.ds_af_replicates(args.bamFile, ref, variants, [o.af for o in outs], [o.params for o in outs], int(args.dsSeed),
+                                     plan.reps, eng, keep, plan.res, sampler=getattr(args, "sampler", "reference"),
                                      sampler_seed=getattr(args, "samplerSeed", 0))
     index = {(c, int(p)): n for n, (c, p) in enumerate(loci)}
     for (k, t, j), line in out["rows"].items():
         v = variants[k]
-        if j == 0 and line != ds_out[t][index[(v.chrom, v.pos)]]:
+        if j == 0 and line != ds_rows[t][index[(v.chrom, v.pos)]]:
             raise RuntimeError("--dsAFReps: replicate 0 of %s:%d at target %g is not the row of the run's own output:\n%s\n%s" %
-                               (v.chrom, v.pos, rules[t].af, line, ds_out[t][index[(v.chrom, v.pos)]]))
+                               (v.chrom, v.pos, outs[t].af, line, ds_rows[t][index[(v.chrom, v.pos)]]))
     return out
 
 
 def call_shard_rows(args, params: VcParams, loci, device: int):
     """A rank's share as NUMBERS: (rows abi.ROW_DTYPE[n], reference letters, allele tables) - the distributed command line
     sends these to rank 0 (packed: dist.pack_shard) which prints every row; no strings are made on the other ranks."""
-    import numpy as np
-    from . import abi, devplanes
-    from .engine import Engine
     if not len(loci):
         return np.zeros(0, abi.ROW_DTYPE), [], []
     ref = fasta.FastaFile(args.refGenome)
@@ -513,8 +514,6 @@ def _report_boundary(out_rows, chrom, pos):
     idx = _rows.pi_boundary_loci(out_rows)
     for l in idx.tolist():
         print("note: prediction index of %s:%d lies within 1e-8 of a printing boundary" % (chrom[l], int(pos[l])), file=sys.stderr)
-    import numpy as np
-    from . import abi
     for l in np.flatnonzero((out_rows["status"] & abi.ST_UNDERFLOW) != 0).tolist():
         print("note: a barcode at %s:%d has so many fragments that the posterior arithmetic left the double range; the "
               "reference's own numbers there depend on its multiplication order" % (chrom[l], int(pos[l])), file=sys.stderr)
@@ -535,7 +534,6 @@ class _Rows(list):
 
     def done(self):
         if self._parts and all(p is not None for p in self._parts):
-            import numpy as np
             self.pred = np.concatenate(self._parts)
         return self
 
@@ -597,17 +595,23 @@ def _main(args) -> int:
 
     params = VcParams(minBQ=args.minBQ, minMQ=args.minMQ, mtDepth=args.mtDepth, rpb=args.rpb, hpLen=args.hpLen,
                       mismatchThr=args.mismatchThr, mtDrop=args.mtDrop, maxMT=args.maxMT, primerDist=args.primerDist)
+    world = int(os.environ.get("WORLD_SIZE", "1"))
     fractions = ds_fractions(args)
     targets = ds_rpb_targets(args)
     cells = ds_grid_cells(args)
     af_targets = ds_af_targets(args)
-    args.ds_af_reps = ds_af_reps(args, af_targets)
+    at = lambda **kw: dataclasses.replace(params, **kw)
+    plan = _Plan([_Output(args.outPrefix, params)] +
+                 [_Output(p, at(mtDepth=d), "dsMT", frac=f) for f, d, p in fractions] +
+                 [_Output(p, at(mtDepth=d, rpb=r), "dsRpb", target=r) for r, d, p in targets] +
+                 [_Output(p, at(mtDepth=d, rpb=r), "dsGrid", frac=f, target=r) for f, r, d, p in cells] +
+                 [_Output(p, at(mtDepth=d), "dsAF", af=t) for t, d, p in af_targets], reps=ds_af_reps(args, af_targets))
     flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets), ("--dsAF", af_targets)) if on)
-    if flag and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    if flag and world > 1:
         raise SystemExit("%s runs in one process only (not under torch.distributed.run with more than one rank)" % flag)
     if getattr(args, "lodDepth", None) is not None and not getattr(args, "lod", False):
         raise SystemExit("--lodDepth chooses the barcode depth --lod reads: it needs --lod")
-    if getattr(args, "lod", False) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    if getattr(args, "lod", False) and world > 1:
         raise SystemExit("--lod runs in one process only (not under torch.distributed.run with more than one rank): the writing rank "
                          "prints from gathered wire rows after its engine is gone, and the table of LODs is made on the GPU")
     host = [v for v, on in (("SMC_PLANES=host", os.environ.get("SMC_PLANES", "device") == "host"),
@@ -616,197 +620,192 @@ def _main(args) -> int:
         first = bedops.expand_loci(args.bedTarget)[:1]
         raise SystemExit("%s needs the device builder: the run at %s would be built on the host (%s)" %
                          (flag, "%s:%s" % first[0] if first else "(no targets)", host[0]))
-    early = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and os.environ.get("SMC_BAM_DECODER", "native") != "python":
+    if world == 1 and os.environ.get("SMC_BAM_DECODER", "native") != "python":
         # a single process: the GPU runtime and the context come up (~ 0.1 s) in a helper thread while the target is expanded
-        early = _EarlyEngine(args.device)
+        plan.early = _EarlyEngine(args.device)
     loc_list = bedops.expand_loci(args.bedTarget)
-    rules = []
-    args.ds_af = args.ds_af_keep = None
     try:
-        if af_targets:
-            # (--dsAF: the listed variants checked, then the pre-pass over the runs around them; --dsAFReps: its runs kept)
-            variants = ds_af_variants(args, loc_list)
-            keep = {} if args.ds_af_reps is not None else None
-            rules, res = ds_af_rules(args, params, af_targets, variants, early, keep)
-            args.ds_af = (variants, res)
-            args.ds_af_keep = keep
-        elif cells:
-            # (--dsGrid: the reference's grouping of the names once, for the targets and the cells alike)
-            from . import devplanes
-            grouped = None if (args.dsRpbSampler or "reference") == "philox" else devplanes.group_placed_reads(args.bamFile)
-            frac_rules = ds_rules(args, params, fractions)
-            rules = frac_rules + ds_rpb_rules(args, params, targets, early, grouped=grouped)
-            rules += ds_grid_rules(args, params, cells, frac_rules, rules[len(frac_rules):], grouped)
-        else:
-            rules = (ds_rules(args, params, fractions) if fractions else []) + (ds_rpb_rules(args, params, targets, early) if targets else [])
+        _make_rules(args, plan, loc_list)
     except SystemExit:
-        from . import devplanes
-        devplanes.close_rules(rules)          # (a refused cell: the targets' file-wide table in HBM)
-        if early is not None:                  # (the engine the helper brings up stays with the process, as after a run)
+        devplanes.close_rules(plan.rules)     # (a refused cell: the targets' file-wide table in HBM)
+        if plan.early is not None:             # (the engine the helper brings up stays with the process, as after a run)
             try:
-                _ENGINES.setdefault(args.device, early.get())
+                _ENGINES.setdefault(args.device, plan.early.get())
             except Exception:
                 pass
         raise
-    for rule in rules:
-        if rule.grid:
-            print("--dsGrid fraction %g x target %g: sampler %s, seed %d, probKeep %.6g, %d of %d read names kept (mtDepth %d)" %
-                  (rule.frac, rule.target, rule.sampler, rule.seed, rule.prob_keep, len(rule.kept) if rule.kept is not None else rule.n_kept,
-                   rule.n_names, rule.params.mtDepth))
-        elif rule.level == "read":
-            print("--dsRpb %g: sampler %s, seed %d, probKeep %.6g, %d of %d read names kept (mtDepth %d)" %
-                  (rule.target, rule.sampler, rule.seed, rule.prob_keep, len(rule.kept) if rule.kept is not None else rule.n_kept,
-                   rule.n_names, rule.params.mtDepth))
-    args.ds_rules = rules or None
+    for rule in plan.rules:
+        if rule.level == "read":               # (a target or a cell)
+            print("%s: sampler %s, seed %d, probKeep %.6g, %d of %d read names kept (mtDepth %d)" %
+                  ("--dsGrid " + rule.label if rule.grid else "--dsRpb %g" % rule.target, rule.sampler, rule.seed, rule.prob_keep,
+                   len(rule.kept) if rule.kept is not None else rule.n_kept, rule.n_names, rule.params.mtDepth))
     try:
-        return _run(args, params, fractions, targets, loc_list, early, t0, cells, af_targets)
+        return _run(args, plan, loc_list, t0)
     finally:
-        from . import devplanes
-        devplanes.close_rules(rules)          # (--dsRpbSampler philox: the file-wide table in HBM, whatever happened)
-        if args.ds_af_keep is not None:       # (--dsAFReps: the pre-pass's runs, when the run ended before the replicate stage)
-            devplanes.free_af_runs(args.ds_af_keep.get("runs"))
+        devplanes.close_rules(plan.rules)     # (--dsRpbSampler philox: the file-wide table in HBM, whatever happened)
+        if plan.keep is not None:             # (--dsAFReps: the pre-pass's runs, when the run ended before the replicate stage)
+            devplanes.free_af_runs(plan.keep.get("runs"))
 
 
-def _run(args, params, fractions, targets, loc_list, early, t0, cells=(), af_targets=()):
-    # One process per GPU when launched through torch.distributed.run: rank r calls a contiguous range of the
-    # ordered locus list (loci share nothing, smCounter.py:683-685) on GPU LOCAL_RANK, rank 0 gathers the rows
-    # in submission order and writes the files.
+def _make_rules(args, plan, loc_list):
+    """The rule of every output but the first, each set on its output as soon as it is made: a refusal further on finds the device
+    tables to close there.  (--dsGrid comes with fractions and targets, --dsAF without any of the three.)"""
+    fr, rd, cell, af = ([o for o in plan.outputs if o.kind == kind] for kind in ("dsMT", "dsRpb", "dsGrid", "dsAF"))
+
+    def put(outs, rules):
+        for o, rule in zip(outs, rules):
+            o.rule = rule
+        return rules
+    # (--dsGrid: the reference's grouping of the names once, for the targets and the cells alike)
+    grouped = devplanes.group_placed_reads(args.bamFile) if cell and args.dsRpbSampler != "philox" else None
+    if fr:
+        frac_rules = put(fr, ds_rules(args, fr))
+    if rd:
+        rpb_rules = put(rd, ds_rpb_rules(args, rd, plan.early, grouped))
+    if cell:
+        put(cell, ds_grid_rules(args, cell, frac_rules, rpb_rules, grouped))
+    if af:
+        # (--dsAF: the listed variants checked, then the pre-pass over the runs around them; --dsAFReps: its runs kept)
+        variants = ds_af_variants(args, loc_list)
+        keep = {} if plan.reps is not None else None
+        rules, res = ds_af_rules(args, af, variants, plan.early, keep)
+        put(af, rules)
+        plan.variants, plan.res, plan.keep = variants, res, keep
+
+
+def _gather_ranks(args, params, loc_list, rank, local_rank, world):
+    """One process per GPU when launched through torch.distributed.run: rank r calls a contiguous range of the ordered locus list
+    (loci share nothing, smCounter.py:683-685) on GPU LOCAL_RANK, rank 0 gathers the rows in submission order -> every locus's row
+    strings there, to be written; None on the other ranks."""
+    import torch
+    import torch.distributed as tdist
+    # contiguous ranges balanced by depth, not by locus count (amplicon depth varies several-fold): the BAI's
+    # linear index gives compressed bytes per 16 kb window without decoding anything; every rank computes the
+    # same cuts
+    cuts = smcdist.shard_by_reads(bamio.locus_weights(args.bamFile, loc_list), world)
+    lo, hi = cuts[rank], cuts[rank + 1]
+    # A failing locus (or a decoder error) on one rank must not leave the others waiting in the collective
+    # until the RCCL timeout: every rank first agrees on a status, then all raise together or all gather.
+    err, payload = None, None
+    try:
+        r_rows, r_ref, r_tab = call_shard_rows(args, params, loc_list[lo:hi], local_rank)
+        if len(r_rows) != hi - lo:
+            raise RuntimeError("%d rows for %d loci" % (len(r_rows), hi - lo))
+        payload = smcdist.pack_shard(abi.pack_wire(r_rows), r_ref, r_tab)
+    except Exception as e:                       # reported by every rank below
+        err = "rank %d: %s: %s" % (rank, type(e).__name__, e)
+    try:
+        failed = [m for m in smcdist.all_gather_status(err) if m]
+        if failed:
+            raise RuntimeError("smCounter failed on %d of %d ranks: %s" % (len(failed), world, " | ".join(failed)))
+        # ONE gather of byte blocks: 168-byte wire rows + the rank's allele-string table (SURVEY.md 8e); a rank whose
+        # share is empty sends an empty table
+        t = torch.from_numpy(payload)
+        if tdist.get_backend() == "nccl":
+            t = t.to(torch.device("cuda", local_rank))
+        blocks = smcdist.gatherv_bytes(t, dst=0)
+        tdist.barrier()
+    finally:
+        if tdist.is_initialized():
+            tdist.destroy_process_group()
+    if rank != 0:
+        return None
+    wires, refs, tabs = [], [], []
+    for b in blocks:
+        w, rf, tb = smcdist.unpack_shard(b.cpu().numpy())
+        wires.append(w); refs += rf; tabs += tb
+    all_rows = abi.unpack_wire(np.concatenate(wires)) if wires else np.zeros(0, abi.ROW_DTYPE)
+    view = vc.LocusView([c for c, _ in loc_list], [int(p) for _, p in loc_list], refs, tabs)
+    output = vc._strings(all_rows, view, params, fasta.FastaFile(args.refGenome))
+    _report_boundary(all_rows, view.chrom, view.pos)
+    return output
+
+
+def _write_output(args, o, rows, loc_list, repeats, lod=None):
+    """The files of output `o` from its raw rows: the repeat flags, the three files, and (`lod`: what lod.run_lods made for it) the
+    LOD files beside them with their line in the run log -> its entry for the LOD summary, None without --lod."""
+    pred = getattr(rows, "pred", None)                    # (single process: the printer's int(PI) per row)
+    threshold = writers.pi_threshold(o.params.mtDepth, args.threshold)
+    writers.write_outputs(o.prefix, postfilter.apply_repeat_filters(rows, *repeats, pred=pred), threshold, pred=pred)
+    if lod is None:
+        return None
+    from . import lod as _lod
+    depth_col = args.lodDepth or "UMT"
+    _lod.write_lod(o.prefix, [c for c, _ in loc_list], [p for _, p in loc_list], lod["lods"])
+    print("--lod %s: %d barcodes needed (mtDepth %d), depth %s, table of %d depths, at most %d iterations" %
+          (o.prefix, lod["needed"], o.params.mtDepth, depth_col, lod["table"], lod["iters"]))
+    return _lod.summary_entry(o.prefix, o.params.mtDepth, o.params.rpb, lod["needed"], lod["rows"], depth_col, lod["lods"])
+
+
+def _af_reports(args, plan, shard, loc_list, repeats):
+    """--dsAF: the titration on one page - every listed variant in the full-depth output and in every target's - and, with
+    --dsAFReps, every replicate's row as its own run would print and cut it, then the rates."""
+    from . import dsaf
+    variants, res, af_outs, lods = plan.variants, plan.res, plan.outputs[1:], shard.lod
+    outs = [(o.af, o.prefix, r["rows"] if r else None, lods[k]["lods"] if lods is not None else None)
+            for k, (o, r) in enumerate(zip(plan.outputs, [None] + list(res)))]
+    loc_index = {(c, "%d" % int(q)): n for n, (c, q) in enumerate(loc_list)}
+    dsaf.write_detection(args.outPrefix, variants, outs, loc_index)
+    reps = shard.af_reps
+    if reps is None:
+        return
+    entries = {}
+    for i, v in enumerate(variants):
+        for t, o in enumerate(af_outs):
+            thr_t = writers.pi_threshold(o.params.mtDepth, args.threshold)
+            per = []
+            for j in range(plan.reps):
+                row, cut = dsaf.replicate_entry(reps["rows"].get((i, t, j)), thr_t, *repeats)
+                per.append((int(reps["counts"][i, j, t, 0]), int(reps["counts"][i, j, t, 1]), row, cut))
+            entries[(i, t)] = per
+            called = sum(1 for _, _, _, cut in per if cut is not None and cut[0] == v.ref and v.alt in cut[1])
+            print("--dsAFReps: %s:%d %s>%s at %g: called %d of %d" % (v.chrom, v.pos, v.ref, v.alt, o.af, called, plan.reps))
+    targets_only = [o.af for o in af_outs]
+    dsaf.write_replicates(args.outPrefix, variants, targets_only, reps["seeds"], [[row["k"] for row in r["rows"]] for r in res], entries)
+    lod_vt = None if lods is None else [[float(l["lods"][loc_index[(v.chrom, "%d" % v.pos)]]) for v in variants] for l in lods[1:]]
+    dsaf.write_sensitivity(args.outPrefix, variants, targets_only, entries, lod_vt)
+    tm = reps["times"]
+    print("--dsAFReps: replicate stage %.3f s (%d replicates x %d targets: %d builds in %d batches; counts %.4f s, masks %.4f s)" %
+          (tm["stage"], plan.reps, len(af_outs), tm["builds"], tm["batches"], tm["counts"], tm["masks"]))
+
+
+def _run(args, plan, loc_list, t0):
+    params = plan.outputs[0].params
     rank, local_rank, world = smcdist.init_from_env()
     if world == 1:
         # a single process never touches torch.distributed: bind the C ABI without importing PyTorch first
         # (about a second of start-up; the host-buffer entry point needs none of it)
-        from . import _lib
         _lib.load(with_torch=False)
-    if world > 1:
-        # contiguous ranges balanced by depth, not by locus count (amplicon depth varies several-fold): the BAI's
-        # linear index gives compressed bytes per 16 kb window without decoding anything; every rank computes the
-        # same cuts
-        cuts = smcdist.shard_by_reads(bamio.locus_weights(args.bamFile, loc_list), world)
-        lo, hi = cuts[rank], cuts[rank + 1]
+        # (the keywords only when there is something in them: a stand-in for call_shard may know neither)
+        more = {k: v for k, v in (("early", plan.early), ("plan", plan if len(plan.outputs) > 1 else None)) if v is not None}
+        shard = call_shard(args, params, loc_list, args.device, **more)
+        if not isinstance(shard, _Shard):                  # (a plain list of row strings: the full-depth output alone)
+            shard = _Shard(shard)
     else:
-        lo, hi = 0, len(loc_list)
-    if world == 1:
-        output = call_shard(args, params, loc_list[lo:hi], args.device, **({"early": early} if early is not None else {}))
-        vc.raise_on_exception(output, loc_list[lo:hi])
-    else:
-        # A failing locus (or a decoder error) on one rank must not leave the others waiting in the collective
-        # until the RCCL timeout: every rank first agrees on a status, then all raise together or all gather.
-        import torch.distributed as tdist
-        import numpy as np
-        import torch
-        from . import abi
-        err, payload = None, None
-        try:
-            r_rows, r_ref, r_tab = call_shard_rows(args, params, loc_list[lo:hi], local_rank)
-            if len(r_rows) != hi - lo:
-                raise RuntimeError("%d rows for %d loci" % (len(r_rows), hi - lo))
-            payload = smcdist.pack_shard(abi.pack_wire(r_rows), r_ref, r_tab)
-        except Exception as e:                       # reported by every rank below
-            err = "rank %d: %s: %s" % (rank, type(e).__name__, e)
-        try:
-            failed = [m for m in smcdist.all_gather_status(err) if m]
-            if failed:
-                raise RuntimeError("smCounter failed on %d of %d ranks: %s" % (len(failed), world, " | ".join(failed)))
-            # ONE gather of byte blocks: 168-byte wire rows + the rank's allele-string table; a rank whose
-            # share is empty sends an empty table
-            t = torch.from_numpy(payload)
-            if tdist.get_backend() == "nccl":
-                t = t.to(torch.device("cuda", local_rank))
-            blocks = smcdist.gatherv_bytes(t, dst=0)
-            tdist.barrier()
-        finally:
-            if tdist.is_initialized():
-                tdist.destroy_process_group()
-        if rank != 0:
-            return writers.pi_threshold(args.mtDepth, args.threshold)
-        wires, refs, tabs = [], [], []
-        for b in blocks:
-            w, rf, tb = smcdist.unpack_shard(b.cpu().numpy())
-            wires.append(w); refs += rf; tabs += tb
-        all_rows = abi.unpack_wire(np.concatenate(wires)) if wires else np.zeros(0, abi.ROW_DTYPE)
-        view = vc.LocusView([c for c, _ in loc_list], [int(p) for _, p in loc_list], refs, tabs)
-        output = vc._strings(all_rows, view, params, fasta.FastaFile(args.refGenome))
-        _report_boundary(all_rows, view.chrom, view.pos)
-        vc.raise_on_exception(output, loc_list)
-
+        rows = _gather_ranks(args, params, loc_list, rank, local_rank, world)
+        if rows is None:
+            return writers.pi_threshold(params.mtDepth, args.threshold)
+        shard = _Shard(rows)
+    vc.raise_on_exception(shard.rows, loc_list)
     print("begin variant filtering and output")
-    have_rep = [b for b in (args.bedTandemRepeats, args.bedRepeatMaskerSubset) if b and os.path.exists(b)]
-    if len(have_rep) < 2:
+    tracks = [b if b and os.path.exists(b) else None for b in (args.bedTandemRepeats, args.bedRepeatMaskerSubset)]
+    if None in tracks:
         print("note: repeat tracks not given or not found; RepT/RepS/LowC/SL flags are not applied", file=sys.stderr)
-    trf, rm = postfilter.load_repeat_regions(
-        args.bedTarget,
-        args.bedTandemRepeats if args.bedTandemRepeats and os.path.exists(args.bedTandemRepeats) else None,
-        args.bedRepeatMaskerSubset if args.bedRepeatMaskerSubset and os.path.exists(args.bedRepeatMaskerSubset) else None)
-    pred = getattr(output, "pred", None)                  # (single process: the printer's int(PI) per row)
-    ds_outputs = getattr(output, "ds", None) or []        # (--dsMT / --dsRpb: the rows of every fraction, then of every target)
-    lods = getattr(output, "lod", None)                   # (--lod: per output, in the same order, what lod.run_lods made)
+    repeats = postfilter.load_repeat_regions(args.bedTarget, *tracks)
     lod_entries = []
-
-    def write_lod(k, prefix, mt_depth, rpb):
-        # the LOD files of output k beside the files just written, its line in the run log and its entry for the summary
-        from . import lod as _lod
-        o = lods[k]
-        _lod.write_lod(prefix, [c for c, _ in loc_list], [p for _, p in loc_list], o["lods"])
-        print("--lod %s: %d barcodes needed (mtDepth %d), depth %s, table of %d depths, at most %d iterations" %
-              (prefix, o["needed"], mt_depth, args.lodDepth or "UMT", o["table"], o["iters"]))
-        lod_entries.append(_lod.summary_entry(prefix, mt_depth, rpb, o["needed"], o["rows"], args.lodDepth or "UMT", o["lods"]))
-    output_raw = output                                   # (--dsAFReps: the replicates' rows hang on the shard's rows)
-    output = postfilter.apply_repeat_filters(output, trf, rm, pred=pred)
-    threshold = writers.pi_threshold(args.mtDepth, args.threshold)
-    writers.write_outputs(args.outPrefix, output, threshold, pred=pred)
-    if lods is not None:
-        write_lod(0, args.outPrefix, args.mtDepth, args.rpb)
-    # (--dsGrid: the cells' rows after them, each at its fraction's mtDepth)
-    # (the reads per barcode an output was called with, for --lod's summary: --rpb for a fraction, r for a target or a cell)
-    # (--dsAF: its targets alone - it is not combined with the other three - each at its mtDepth and the run's --rpb)
-    rpbs = [args.rpb] * len(fractions) + [r for r, _, _ in targets] + [r for _, r, _, _ in cells] + [args.rpb] * len(af_targets)
-    for k, ((d, prefix), o) in enumerate(zip([(d, p) for _, d, p in fractions + targets] + [(d, p) for _, _, d, p in cells] +
-                                             [(d, p) for _, d, p in af_targets], ds_outputs)):
-        vc.raise_on_exception(o, loc_list)
-        o_pred = getattr(o, "pred", None)
-        o = postfilter.apply_repeat_filters(o, trf, rm, pred=o_pred)
-        writers.write_outputs(prefix, o, writers.pi_threshold(d, args.threshold), pred=o_pred)
-        if lods is not None:
-            write_lod(1 + k, prefix, d, rpbs[k])
-    if lods is not None:
+    for k, (o, rows) in enumerate(zip(plan.outputs, [shard.rows] + list(shard.ds))):
+        if k:                                              # (output 0 was looked at before this stage began)
+            vc.raise_on_exception(rows, loc_list)
+        lod_entries.append(_write_output(args, o, rows, loc_list, repeats, shard.lod[k] if shard.lod is not None else None))
+    if shard.lod is not None:
         from . import lod as _lod
         _lod.write_summary(args.outPrefix, lod_entries)
-    if af_targets:
-        # the titration on one page: every listed variant in the full-depth output and in every target's
-        from . import dsaf
-        variants, res = args.ds_af
-        outs = [(None, args.outPrefix, None, lods[0]["lods"] if lods is not None else None)] + \
-               [(t, p, r["rows"], lods[1 + k]["lods"] if lods is not None else None) for k, ((t, _, p), r) in enumerate(zip(af_targets, res))]
-        loc_index = {(c, "%d" % int(q)): n for n, (c, q) in enumerate(loc_list)}
-        dsaf.write_detection(args.outPrefix, variants, outs, loc_index)
-        reps = getattr(output_raw, "af_reps", None)
-        if reps is not None:
-            # (--dsAFReps: every replicate's row as its own run would print and cut it, then the rates)
-            entries = {}
-            for i, v in enumerate(variants):
-                for t, (target, d, _) in enumerate(af_targets):
-                    thr_t = writers.pi_threshold(d, args.threshold)
-                    per = []
-                    for j in range(args.ds_af_reps):
-                        row, cut = dsaf.replicate_entry(reps["rows"].get((i, t, j)), thr_t, trf, rm)
-                        per.append((int(reps["counts"][i, j, t, 0]), int(reps["counts"][i, j, t, 1]), row, cut))
-                    entries[(i, t)] = per
-                    called = sum(1 for _, _, _, cut in per if cut is not None and cut[0] == v.ref and v.alt in cut[1])
-                    print("--dsAFReps: %s:%d %s>%s at %g: called %d of %d" % (v.chrom, v.pos, v.ref, v.alt, target, called, args.ds_af_reps))
-            targets_only = [t for t, _, _ in af_targets]
-            dsaf.write_replicates(args.outPrefix, variants, targets_only, reps["seeds"], [[row["k"] for row in r["rows"]] for r in res], entries)
-            lod_vt = None
-            if lods is not None:
-                lod_vt = [[float(lods[1 + t]["lods"][loc_index[(v.chrom, "%d" % v.pos)]]) for v in variants] for t in range(len(af_targets))]
-            dsaf.write_sensitivity(args.outPrefix, variants, targets_only, entries, lod_vt)
-            tm = reps["times"]
-            print("--dsAFReps: replicate stage %.3f s (%d replicates x %d targets: %d builds in %d batches; counts %.4f s, masks %.4f s)" %
-                  (tm["stage"], args.ds_af_reps, len(af_targets), tm["builds"], tm["batches"], tm["counts"], tm["masks"]))
+    if plan.variants is not None:
+        _af_reports(args, plan, shard, loc_list, repeats)
     t1 = datetime.datetime.now()
     print("smCounter completed running at " + str(t1))
     print("smCounter total time: " + str(t1 - t0))
-    return threshold
+    return writers.pi_threshold(params.mtDepth, args.threshold)
 
 
 if __name__ == "__main__":

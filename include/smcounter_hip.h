@@ -540,6 +540,26 @@ int smc_af_rep_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint8_t* 
                       const uint32_t* cov_off_host, int32_t n_var, const uint64_t* d_car, const uint64_t* d_car_thr,
                       const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets, const uint64_t* d_seeds,
                       int32_t n_reps, uint32_t* d_out, void* stream);
+/* (ABI 11, additive: two entries more, the version number unchanged) --dsAFDepth: the cells (target t, barcode fraction f) of the
+ * --dsAF dilution.  A barcode is KEPT in cell (t, f) of replicate j when smc_af_rep_masks keeps it at t (the carrier table and the
+ * "dsAF" draw above, key seeds[j]) AND its depth draw d_j(b) = word 0 of Philox4x32-10(counter = (identity lo, identity hi,
+ * 0x64734D54 "dsMT", 0), key = (seeds[j] lo, hi)) - smc_select_alignments' philox rule - is below depth_thr[f].  `depth_thr`: HOST
+ * memory, n_fracs words, floor(f * 2^32) each and 2^32 at f = 1 (every barcode stays: the masks are smc_af_rep_masks').  The depth
+ * draw is made for every barcode, the "dsAF" draw for carriers only.
+ *   _masks   d_masks[((j * n_targets + t) * n_fracs + f) * n_words + (g >> 5)] bit (g & 31) = id g is kept: n_reps * n_targets *
+ *            n_fracs masks in smc_af_rep_masks' layout.  d_draws (may be NULL): [n_reps][n_ids] the depth draw of every id (tests).
+ *   _counts  d_out[v][j][t][f][2] uint32 = (N', V') of the cell, from the covering barcodes as smc_af_rep_counts takes them.
+ * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched: what smc_af_rep_masks / _counts refuse, a depth threshold
+ * above 2^32, n_targets * n_fracs above SMC_AF_DEPTH_MAX_CELLS, an output of 2^32 - 256 words or more. */
+#define SMC_AF_DEPTH_MAX_CELLS 32      /* (= SMC_RG_MAX_TARGETS) */
+int smc_af_depth_masks(smc_ctx* ctx, const uint64_t* d_idents, int64_t n_ids, const uint64_t* d_car, const uint64_t* d_car_thr,
+                       const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets,
+                       const uint64_t* depth_thr, int32_t n_fracs, const uint64_t* d_seeds, int32_t n_reps, uint32_t* d_masks,
+                       int64_t n_words, uint32_t* d_draws, void* stream);
+int smc_af_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint8_t* d_cov_carry, const uint32_t* d_cov_off,
+                        const uint32_t* cov_off_host, int32_t n_var, const uint64_t* d_car, const uint64_t* d_car_thr,
+                        const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets,
+                        const uint64_t* depth_thr, int32_t n_fracs, const uint64_t* d_seeds, int32_t n_reps, uint32_t* d_out, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

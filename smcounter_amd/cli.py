@@ -127,6 +127,18 @@ def build_parser() -> argparse.ArgumentParser:
                         ".dsAF.detection.txt of a run with --dsSeed of that replicate, with REP and SEED), and "
                         "<outPrefix>.dsAF.sensitivity.txt, one line per variant and target: replicates called, the detection rate and its "
                         "Wilson score interval (95 %%%%), the achieved fractions, and with --lod the locus's LOD.  Needs --dsAF" % (REPS_MIN, REPS_MAX))
+    p.add_argument("--dsAFDepth", default=None,
+                   help="the dilutions of --dsAF at several barcode depths: comma-separated fractions f in (0, 1].  For every target t "
+                        "and every f the run is also called on the CELL (t, f): a barcode stays when the --dsAF rule at t keeps it and "
+                        "the --dsMT --dsSampler philox draw keeps it at f (two independent draws, both keyed by --dsSeed) - the .dsMT<f> "
+                        "output of a --dsMT f --dsSampler philox run on the BAM tools/ds_allele_fraction.py --af t writes, at the "
+                        "mtDepth --dsMT f would get from that target's mtDepth (max(1, round(f x mtDepth))); written to "
+                        "<outPrefix>.dsAF<t>.dsMT<f>.smCounter.{all,cut}.txt and .cut.vcf (with --lod: its LOD files and summary line), "
+                        "and, one line per variant and cell, <outPrefix>.dsAF.depth.detection.txt.  With --dsAFReps the cells are "
+                        "replicated as the targets are: <outPrefix>.dsAF.depth.replicates.txt, .dsAF.depth.sensitivity.txt and "
+                        ".dsAF.depth.curve.txt (per variant and depth the detection rate at every target and T95, the smallest "
+                        "target found in 95 %%%% of the replicates together with every larger one).  The masks and counts of the cells "
+                        "are made on the GPU; at most %d cells.  Needs --dsAF" % GRID_MAX_CELLS)
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -238,6 +250,30 @@ def ds_af_reps(args, af_targets):
     return reps
 
 
+def ds_af_depth_cells(args, af_targets):
+    """--dsAFDepth -> (fractions, [(target index, t, f, mtDepth of the cell, output prefix)] for every --dsAF target t and every fraction
+    f, targets outer), or (None, []) without the flag.  A cell's mtDepth is what --dsMT f gets from its target's mtDepth.  Refused:
+    without --dsAF, a fraction outside (0, 1], a repeated fraction, beyond GRID_MAX_CELLS cells."""
+    from .py2compat import py2_round
+    text = getattr(args, "dsAFDepth", None)
+    if text in (None, ""):
+        return None, []
+    if not af_targets:
+        raise SystemExit("--dsAFDepth thins the barcodes of the --dsAF dilutions: it needs --dsAF")
+    try:
+        fr = [float(x) for x in str(text).split(",") if x.strip()]
+    except ValueError:
+        raise SystemExit("--dsAFDepth: comma-separated fractions in (0, 1] expected, got %r" % text)
+    if not fr or any(not (0.0 < f <= 1.0) for f in fr):
+        raise SystemExit("--dsAFDepth: every fraction must lie in (0, 1], got %r" % text)
+    if len(set("%g" % f for f in fr)) != len(fr):
+        raise SystemExit("--dsAFDepth: a fraction is listed twice (the cells' files would share a name), got %r" % text)
+    if len(af_targets) * len(fr) > GRID_MAX_CELLS:
+        raise SystemExit("--dsAFDepth: %d targets x %d fractions = %d cells, at most %d" % (len(af_targets), len(fr), len(af_targets) * len(fr),
+                                                                                             GRID_MAX_CELLS))
+    return fr, [(k, t, f, max(1, int(py2_round(f * d))), "%s.dsMT%g" % (p, f)) for k, (t, d, p) in enumerate(af_targets) for f in fr]
+
+
 def ds_af_variants(args, loc_list):
     """The variants of --dsAFVariants, checked: the file's own refusals (tools.ds_allele_fraction.parse_variants) and every variant a
     locus of --bedTarget."""
@@ -257,23 +293,25 @@ class _Output:
     its reads per barcode).  Output 0 of a run is the full-depth one; every other has a `rule`, once the rule makers below have run."""
     prefix: str
     params: VcParams
-    kind: str = "full"          # full, dsMT, dsRpb, dsGrid or dsAF
-    frac: float = None          # (dsMT, dsGrid) the fraction of the barcodes
+    kind: str = "full"          # full, dsMT, dsRpb, dsGrid, dsAF or dsAFDepth
+    frac: float = None          # (dsMT, dsGrid, dsAFDepth) the fraction of the barcodes
     target: float = None        # (dsRpb, dsGrid) the reads per barcode asked for
-    af: float = None            # (dsAF) the target allele fraction
+    af: float = None            # (dsAF, dsAFDepth) the target allele fraction
+    af_index: int = None        # (dsAFDepth) which --dsAF target the cell belongs to
     rule: object = None         # the devplanes.DsRule that selects it; None: full depth
 
 
 @dataclasses.dataclass
 class _Plan:
     """What a run is to do beyond its command line: its outputs in the order they are called, written and summarised (full depth,
-    fractions, targets, cells, allele fractions), the engine coming up, and the state of --dsAF."""
+    fractions, targets, cells, allele fractions, their cells), the engine coming up, and the state of --dsAF."""
     outputs: list
     early: object = None
     variants: list = None       # (--dsAF) the listed variants and titrate()'s result per target
     res: list = None
     reps: int = None            # (--dsAFReps) R, and what the pre-pass kept for the replicate stage (None once that has taken it)
     keep: dict = None
+    depth: dict = None          # (--dsAFDepth) "fracs", the cells' "params", and once the rules are made "rules" and "counts" [V, T, F, 2]
 
     @property
     def rules(self):
@@ -287,14 +325,16 @@ def _engine_of(args, early):
     return _ENGINES.get(args.device) or _ENGINES.setdefault(args.device, Engine(args.device))
 
 
-def ds_af_rules(args, outs, variants, early, keep=None):
+def ds_af_rules(args, outs, variants, early, keep=None, depth=None):
     """The devplanes.DsRule of every --dsAF output (the pre-pass on the GPU: devplanes.ds_af_rules) and the titration's numbers; the
-    run log gets a line per variant and target.  `keep` (--dsAFReps): a dict for what the replicate stage starts from."""
+    run log gets a line per variant and target.  `keep` (--dsAFReps): a dict for what the replicate stage starts from.  `depth`
+    (--dsAFDepth): the plan's dict; it gets the cells' rules and counts."""
     from .tools import ds_allele_fraction as af
     eng = _engine_of(args, early)
     try:
         rules, res = devplanes.ds_af_rules(args.bamFile, fasta.FastaFile(args.refGenome), variants, [o.af for o in outs],
-                                           [o.params for o in outs], int(args.dsSeed), eng, keep=keep)
+                                           [o.params for o in outs], int(args.dsSeed), eng, keep=keep,
+                                           **({"depth": depth} if depth is not None else {}))
     except (ValueError, bamio.BamError) as e:
         raise SystemExit(str(e))
     for r in res:
@@ -466,17 +506,20 @@ def call_shard(args, params: VcParams, loci, device: int, early=None, plan=None)
 def _ds_af_replicates(args, plan, ref, eng, loci, ds_rows):
     """--dsAFReps after the run's batches: devplanes.ds_af_replicates over the runs the pre-pass kept, and the check that ties it to
     the run's own outputs - replicate 0 has the seed of the run, so its row at every listed locus must be the .dsAF<t> output's."""
-    outs, variants = plan.outputs[1:], plan.variants
+    variants = plan.variants
+    # (the run's outputs behind the first: the targets, then with --dsAFDepth their cells - the order of the stage's cells)
+    outs, targets = plan.outputs[1:], [o for o in plan.outputs if o.kind == "dsAF"]
     keep, plan.keep = plan.keep, None           # (the stage frees the kept runs itself, whatever happens in it)
-    out = devplanes.ds_af_replicates(args.bamFile, ref, variants, [o.af for o in outs], [o.params for o in outs], int(args.dsSeed),
+    more = {"depth": plan.depth} if plan.depth is not None else {}
+    out = devplanes.ds_af_replicates(args.bamFile, ref, variants, [o.af for o in targets], [o.params for o in targets], int(args.dsSeed),
                                      plan.reps, eng, keep, plan.res, sampler=getattr(args, "sampler", "reference"),
-                                     sampler_seed=getattr(args, "samplerSeed", 0))
+                                     sampler_seed=getattr(args, "samplerSeed", 0), **more)
     index = {(c, int(p)): n for n, (c, p) in enumerate(loci)}
     for (k, t, j), line in out["rows"].items():
         v = variants[k]
         if j == 0 and line != ds_rows[t][index[(v.chrom, v.pos)]]:
-            raise RuntimeError("--dsAFReps: replicate 0 of %s:%d at target %g is not the row of the run's own output:\n%s\n%s" %
-                               (v.chrom, v.pos, outs[t].af, line, ds_rows[t][index[(v.chrom, v.pos)]]))
+            raise RuntimeError("--dsAFReps: replicate 0 of %s:%d in %s is not the row of the run's own output:\n%s\n%s" %
+                               (v.chrom, v.pos, outs[t].prefix, line, ds_rows[t][index[(v.chrom, v.pos)]]))
     return out
 
 
@@ -600,12 +643,17 @@ def _main(args) -> int:
     targets = ds_rpb_targets(args)
     cells = ds_grid_cells(args)
     af_targets = ds_af_targets(args)
+    af_fracs, af_cells = ds_af_depth_cells(args, af_targets)
     at = lambda **kw: dataclasses.replace(params, **kw)
     plan = _Plan([_Output(args.outPrefix, params)] +
                  [_Output(p, at(mtDepth=d), "dsMT", frac=f) for f, d, p in fractions] +
                  [_Output(p, at(mtDepth=d, rpb=r), "dsRpb", target=r) for r, d, p in targets] +
                  [_Output(p, at(mtDepth=d, rpb=r), "dsGrid", frac=f, target=r) for f, r, d, p in cells] +
-                 [_Output(p, at(mtDepth=d), "dsAF", af=t) for t, d, p in af_targets], reps=ds_af_reps(args, af_targets))
+                 [_Output(p, at(mtDepth=d), "dsAF", af=t) for t, d, p in af_targets] +
+                 [_Output(p, at(mtDepth=d), "dsAFDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in af_cells],
+                 reps=ds_af_reps(args, af_targets))
+    if af_fracs is not None:
+        plan.depth = dict(fracs=af_fracs, params=[o.params for o in plan.outputs if o.kind == "dsAFDepth"])
     flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets), ("--dsAF", af_targets)) if on)
     if flag and world > 1:
         raise SystemExit("%s runs in one process only (not under torch.distributed.run with more than one rank)" % flag)
@@ -668,8 +716,10 @@ def _make_rules(args, plan, loc_list):
         # (--dsAF: the listed variants checked, then the pre-pass over the runs around them; --dsAFReps: its runs kept)
         variants = ds_af_variants(args, loc_list)
         keep = {} if plan.reps is not None else None
-        rules, res = ds_af_rules(args, af, variants, plan.early, keep)
+        rules, res = ds_af_rules(args, af, variants, plan.early, keep, plan.depth)
         put(af, rules)
+        if plan.depth is not None:
+            put([o for o in plan.outputs if o.kind == "dsAFDepth"], plan.depth["rules"])
         plan.variants, plan.res, plan.keep = variants, res, keep
 
 
@@ -741,32 +791,54 @@ def _af_reports(args, plan, shard, loc_list, repeats):
     """--dsAF: the titration on one page - every listed variant in the full-depth output and in every target's - and, with
     --dsAFReps, every replicate's row as its own run would print and cut it, then the rates."""
     from . import dsaf
-    variants, res, af_outs, lods = plan.variants, plan.res, plan.outputs[1:], shard.lod
+    variants, res, af_outs, lods = plan.variants, plan.res, [o for o in plan.outputs if o.kind == "dsAF"], shard.lod
     outs = [(o.af, o.prefix, r["rows"] if r else None, lods[k]["lods"] if lods is not None else None)
             for k, (o, r) in enumerate(zip(plan.outputs, [None] + list(res)))]
     loc_index = {(c, "%d" % int(q)): n for n, (c, q) in enumerate(loc_list)}
     dsaf.write_detection(args.outPrefix, variants, outs, loc_index)
     reps = shard.af_reps
+    ks = [[row["k"] for row in r["rows"]] for r in res]
+    cell_outs = [o for o in plan.outputs if o.kind == "dsAFDepth"]
+    if plan.depth is not None:
+        # (--dsAFDepth: the same page over the cells; their outputs lie behind the targets')
+        cells = [(o.af_index, o.af, o.frac, o.params.mtDepth, o.prefix, lods[1 + len(af_outs) + c]["lods"] if lods is not None else None)
+                 for c, o in enumerate(cell_outs)]
+        dsaf.write_depth_detection(args.outPrefix, variants, cells, plan.depth["counts"].reshape(len(variants), len(cells), 2), ks, loc_index)
     if reps is None:
         return
-    entries = {}
-    for i, v in enumerate(variants):
-        for t, o in enumerate(af_outs):
-            thr_t = writers.pi_threshold(o.params.mtDepth, args.threshold)
-            per = []
-            for j in range(plan.reps):
-                row, cut = dsaf.replicate_entry(reps["rows"].get((i, t, j)), thr_t, *repeats)
-                per.append((int(reps["counts"][i, j, t, 0]), int(reps["counts"][i, j, t, 1]), row, cut))
-            entries[(i, t)] = per
-            called = sum(1 for _, _, _, cut in per if cut is not None and cut[0] == v.ref and v.alt in cut[1])
-            print("--dsAFReps: %s:%d %s>%s at %g: called %d of %d" % (v.chrom, v.pos, v.ref, v.alt, o.af, called, plan.reps))
+
+    def entries_of(outs, first, counts, what):
+        """Every replicate of the outputs `outs` (the stage's cells from `first` on): the row as its own run prints and cuts it."""
+        entries = {}
+        for i, v in enumerate(variants):
+            for t, o in enumerate(outs):
+                thr_t = writers.pi_threshold(o.params.mtDepth, args.threshold)
+                per = []
+                for j in range(plan.reps):
+                    row, cut = dsaf.replicate_entry(reps["rows"].get((i, first + t, j)), thr_t, *repeats)
+                    per.append((int(counts[i, j, t, 0]), int(counts[i, j, t, 1]), row, cut))
+                entries[(i, t)] = per
+                called = sum(1 for _, _, _, cut in per if cut is not None and cut[0] == v.ref and v.alt in cut[1])
+                print("--dsAFReps: %s:%d %s>%s at %s: called %d of %d" % (v.chrom, v.pos, v.ref, v.alt, what(o), called, plan.reps))
+        return entries
+    entries = entries_of(af_outs, 0, reps["counts"], lambda o: "%g" % o.af)
     targets_only = [o.af for o in af_outs]
-    dsaf.write_replicates(args.outPrefix, variants, targets_only, reps["seeds"], [[row["k"] for row in r["rows"]] for r in res], entries)
-    lod_vt = None if lods is None else [[float(l["lods"][loc_index[(v.chrom, "%d" % v.pos)]]) for v in variants] for l in lods[1:]]
+    dsaf.write_replicates(args.outPrefix, variants, targets_only, reps["seeds"], ks, entries)
+    lod_vt = None if lods is None else [[float(l["lods"][loc_index[(v.chrom, "%d" % v.pos)]]) for v in variants]
+                                        for l in lods[1:1 + len(af_outs)]]
     dsaf.write_sensitivity(args.outPrefix, variants, targets_only, entries, lod_vt)
+    if plan.depth is not None:
+        dc = reps["depth_counts"]
+        cell_entries = entries_of(cell_outs, len(af_outs), dc.reshape(dc.shape[0], dc.shape[1], len(cells), 2),
+                                  lambda o: "%g x fraction %g" % (o.af, o.frac))
+        dsaf.write_depth_replicates(args.outPrefix, variants, cells, reps["seeds"], ks, cell_entries)
+        dsaf.write_depth_sensitivity(args.outPrefix, variants, cells, cell_entries, loc_index)
+        full = [(o.params.mtDepth, lods[1 + t]["lods"] if lods is not None else None) for t, o in enumerate(af_outs)]
+        dsaf.write_depth_curve(args.outPrefix, variants, targets_only, plan.depth["fracs"], full, cells, entries, cell_entries, loc_index)
     tm = reps["times"]
-    print("--dsAFReps: replicate stage %.3f s (%d replicates x %d targets: %d builds in %d batches; counts %.4f s, masks %.4f s)" %
-          (tm["stage"], plan.reps, len(af_outs), tm["builds"], tm["batches"], tm["counts"], tm["masks"]))
+    over = "%d targets" % len(af_outs) + (" and %d cells" % len(cell_outs) if cell_outs else "")
+    print("--dsAFReps: replicate stage %.3f s (%d replicates x %s: %d builds in %d batches; counts %.4f s, masks %.4f s)" %
+          (tm["stage"], plan.reps, over, tm["builds"], tm["batches"], tm["counts"], tm["masks"]))
 
 
 def _run(args, plan, loc_list, t0):

@@ -368,6 +368,7 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
     res = []
     idents = names = p_idents = p_names = None
     d_masks = {}                     # (philox read rules) (id(table), grid) -> (device masks of those rules, words per mask, id(rule) -> index)
+    d_cells = None                   # (--dsAFDepth) (device masks of every cell of this run, words per mask)
     try:
         for rule, d in zip(rules, ds):
             if not nl:
@@ -398,6 +399,15 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
                             p_names = [bam.pair_name(g) for g in range(int(A["n_pair"]))]
                         mask = np.array([t in rule.kept for t in p_names], bool)
                     sel, counts, d_orig = select_run(eng, up, A, lo, mask=mask, level="read")
+            elif rule.depth is not None:
+                # (--dsAFDepth: the masks of every cell from the carrier table and the two draws, one launch per run.  This branch
+                # stands BEFORE the dropped_idents one on purpose: a cell's rule also carries `dropped_idents` of t and `bc_thr` of f -
+                # what the cell is, for the log and for whoever restates it on the host - but its mask is the table's)
+                if idents is None:
+                    idents = bam.barcode_idents(A["n_bc"])
+                if d_cells is None:
+                    d_cells = _run_depth_masks(eng, rule.depth, idents)
+                sel, counts, d_orig = select_run(eng, up, A, lo, d_mask=d_cells[0].data_ptr() + 4 * d_cells[1] * rule.cell)
             elif rule.dropped_idents is not None:
                 # (--dsAF: every barcode but the dropped carriers)
                 if idents is None:
@@ -452,6 +462,8 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
     finally:
         for buf, _, _ in d_masks.values():
             buf.free()
+        if d_cells is not None:
+            d_cells[0].free()
     for d, (nl_k, ns_k, lc, tb) in zip(ds, res):
         d.LC.append(lc)
         d.tables += tb
@@ -484,6 +496,24 @@ def _run_read_masks(eng, groups, rules, p_idents, chrom, lo, nl):
         raise bamio.BamError("--dsRpbSampler philox: the run %s:%d-%d has a read name the file-wide table does not hold (status %#x)"
                              % (chrom, lo + 1, lo + nl, st))
     return buf, n_words, {id(r): k for k, r in enumerate(rules)}
+
+
+def _run_depth_masks(eng, table, idents):
+    """One launch for a run: the keep masks of every --dsAFDepth cell (the table's one seed) over the run's barcode identities ->
+    (device buffer of T x F masks, words per mask)."""
+    from .engine import DevBuf
+    n = len(idents)
+    n_words = mask_words(n)
+    d_id = DevBuf(eng, 8 * max(1, n) + 256).upload(np.ascontiguousarray(idents, np.uint64) if n else np.zeros(1, np.uint64))
+    buf = DevBuf(eng, 4 * n_words * table.n_targets * table.n_fracs * len(table.seeds) + 256)
+    try:
+        table.masks(d_id.data_ptr(), n, buf.data_ptr(), n_words)
+    except BaseException:
+        buf.free()
+        raise
+    finally:
+        d_id.free()
+    return buf, n_words
 
 
 def build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, planes, uaux, slot_base, umi_base, cap, max_depth,
@@ -668,9 +698,15 @@ class DsRule:
     # (every other barcode stays: ds_af_rules)
     af: float = None
     dropped_idents: object = None
+    # (--dsAFDepth) a cell: `af` t and `frac` f; `dropped_idents` of t beside `bc_thr` = the --dsMT draw's threshold at f; `depth`: the
+    # cells' AfDepthTable in HBM (one for all cells of the run), `cell` this one's index in its masks (t x F + f)
+    depth: object = None
+    cell: int = None
 
     @property
     def flag(self) -> str:
+        if self.depth is not None:
+            return "--dsAFDepth"
         if self.af is not None:
             return "--dsAF"
         return "--dsGrid" if self.grid else "--dsRpb" if self.level == "read" else "--dsMT"
@@ -681,6 +717,8 @@ class DsRule:
 
     @property
     def label(self) -> str:
+        if self.depth is not None:
+            return "allele fraction %g x fraction %g" % (self.af, self.frac)
         if self.af is not None:
             return "allele fraction %g" % self.af
         if self.grid:
@@ -945,6 +983,9 @@ def close_rules(rules):
     for rule in rules or ():
         if getattr(rule, "groups", None) is not None:
             rule.groups.close()
+    # (--dsAFDepth: the cells of a run share ONE table - freed once)
+    for table in {id(r.depth): r.depth for r in rules or () if getattr(r, "depth", None) is not None}.values():
+        table.free()
 
 
 def check32_array(texts) -> np.ndarray:
@@ -1169,11 +1210,13 @@ def ds_af_sets(path: str, fasta, variants, params, eng, nthreads: int = 0, max_r
     return covers, carries
 
 
-def ds_af_rules(path: str, fasta, variants, targets, params_list, seed: int, eng, nthreads: int = 0, keep: dict = None):
+def ds_af_rules(path: str, fasta, variants, targets, params_list, seed: int, eng, nthreads: int = 0, keep: dict = None, depth: dict = None):
     """DsRules of --dsAF: one per target allele fraction, barcode level, a dropped-identity set (tools.ds_allele_fraction's steps 2-4
     over the pre-pass's sets) -> (rules, titrate()'s result: per target the dropped identities and per variant N, V, a, k, N', V').
     ValueError: two barcode texts of the file share an identity.  `keep` (--dsAFReps): a dict that gets what the replicate stage
-    starts from - "runs" (ds_af_sets' kept runs), "covers" and "carries"."""
+    starts from - "runs" (ds_af_sets' kept runs), "covers" and "carries".  `depth` (--dsAFDepth): a dict with "fracs" and "params" (of
+    the T x F cells, targets outer); it gets "rules" (a DsRule per cell over one AfDepthTable in HBM: close_rules frees it) and
+    "counts", uint32 [V, T, F, 2] = the achieved (N', V') of every cell (smc_af_depth_counts)."""
     import time
     from .tools import ds_allele_fraction as af
     t0 = time.perf_counter()
@@ -1190,6 +1233,20 @@ def ds_af_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     _AF_TIMES["barcodes of the file"] = t1 - t0
     res = af.titrate(covers, carries, targets, seed)
     rules = [DsRule(1.0, P, seed=int(seed), af=float(t), dropped_idents=r["dropped"]) for t, P, r in zip(targets, params_list, res)]
+    if depth is not None:
+        from . import dsaf
+        fracs = list(depth["fracs"])
+        idents, thr = dsaf.carrier_table(carries, [[row["thr"] for row in r["rows"]] for r in res])
+        table = AfDepthTable(eng, idents, thr, [int(seed) & 0xFFFFFFFFFFFFFFFF], [frac_threshold(f) for f in fracs])
+        try:
+            depth["counts"] = table.counts(covers, carries)[:, 0]
+            depth["rules"] = [DsRule(float(f), depth["params"][t * len(fracs) + k], seed=int(seed), af=float(targets[t]),
+                                     dropped_idents=res[t]["dropped"], bc_thr=frac_threshold(f), depth=table, cell=t * len(fracs) + k)
+                              for t in range(len(targets)) for k, f in enumerate(fracs)]
+        except BaseException:
+            free_af_runs(runs)
+            table.free()
+            raise
     return rules, res
 
 
@@ -1258,6 +1315,12 @@ class AfRepTable(object):
     def counts(self, covers, carries) -> np.ndarray:
         """smc_af_rep_counts: uint32 [V, R, T, 2] = (N', V') of every variant, replicate and target, from the identities that cover /
         carry each variant (made unique here, as titrate() does)."""
+        return self._counts(covers, carries, self.n_targets, lambda bufs, off, n_var: _lib.check(self.eng.L.smc_af_rep_counts(
+            self.eng.ctx, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data, n_var, *self._table(), bufs[3].data_ptr(),
+            ctypes.c_void_p(0)), "smc_af_rep_counts")).reshape(len(covers), len(self.seeds), self.n_targets, 2)
+
+    def _counts(self, covers, carries, per_rep: int, call) -> np.ndarray:
+        """The covering barcodes up, `call(bufs, offsets, n_var)`, the 2 x V x R x per_rep counters back."""
         from .engine import DevBuf
         covers = [np.unique(np.asarray(c, np.uint64)) for c in covers]
         off = np.zeros(len(covers) + 1, np.uint32)
@@ -1265,21 +1328,46 @@ class AfRepTable(object):
         ident = np.concatenate(covers) if covers else np.zeros(0, np.uint64)
         carry = np.concatenate([np.isin(c, np.asarray(k, np.uint64)) for c, k in zip(covers, carries)]).astype(np.uint8) if covers \
             else np.zeros(0, np.uint8)
-        n_out = 2 * len(covers) * len(self.seeds) * self.n_targets
+        n_out = 2 * len(covers) * len(self.seeds) * per_rep
         up = lambda a: DevBuf(self.eng, a.nbytes + 256).upload(a if a.size else np.zeros(1, a.dtype))
         bufs = [up(ident), up(carry), up(off), DevBuf(self.eng, 4 * max(1, n_out) + 256)]
         try:
-            _lib.check(self.eng.L.smc_af_rep_counts(self.eng.ctx, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data,
-                                                    len(covers), *self._table(), bufs[3].data_ptr(), ctypes.c_void_p(0)), "smc_af_rep_counts")
+            call(bufs, off, len(covers))
             out = bufs[3].download(np.uint32, n_out) if n_out else np.zeros(0, np.uint32)      # (the default stream: behind the kernel)
         finally:
             for b in bufs:
                 b.free()
-        return out.reshape(len(covers), len(self.seeds), self.n_targets, 2)
+        return out
 
     def free(self):
         for b in (self.d_idents, self.d_thr, self.d_seeds):
             b.free()
+
+
+class AfDepthTable(AfRepTable):
+    """The same table with the thresholds of the --dsAFDepth fractions (frac_threshold(f), host memory: they travel by value), and
+    the two calls of csrc/k_af_depth.inc over them."""
+
+    def __init__(self, eng, idents, thr, seeds, depth_thr):
+        super().__init__(eng, idents, thr, seeds)
+        self.depth_thr = np.ascontiguousarray(depth_thr, np.uint64)
+        self.n_fracs = len(self.depth_thr)
+
+    def _table(self):
+        t = super()._table()
+        return t[:6] + (self.depth_thr.ctypes.data, self.n_fracs) + t[6:]
+
+    def masks(self, d_run_idents, n_ids: int, d_masks, n_words: int, d_draws=None):
+        """smc_af_depth_masks: len(seeds) x n_targets x n_fracs keep masks of `n_words` words each - mask ((j x T + t) x F + f) is what
+        select_run(d_mask=...) takes.  d_draws: uint32 [len(seeds), n_ids], the depth draw of every id."""
+        _lib.check(self.eng.L.smc_af_depth_masks(self.eng.ctx, d_run_idents, int(n_ids), *self._table(), d_masks, int(n_words), d_draws,
+                                                 ctypes.c_void_p(0)), "smc_af_depth_masks")
+
+    def counts(self, covers, carries) -> np.ndarray:
+        """smc_af_depth_counts: uint32 [V, R, T, F, 2] = (N', V') of every variant, replicate and cell."""
+        return self._counts(covers, carries, self.n_targets * self.n_fracs, lambda bufs, off, n_var: _lib.check(self.eng.L.smc_af_depth_counts(
+            self.eng.ctx, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data, n_var, *self._table(), bufs[3].data_ptr(),
+            ctypes.c_void_p(0)), "smc_af_depth_counts")).reshape(len(covers), len(self.seeds), self.n_targets, self.n_fracs, 2)
 
 
 def mask_words(n_ids: int) -> int:
@@ -1288,7 +1376,8 @@ def mask_words(n_ids: int) -> int:
 
 
 def _af_rep_call(eng, run: AfRun, table: AfRepTable, d_masks, n_words, todo, P, fasta, variants, max_depth, sampler, sampler_seed, bits):
-    """The builds of `todo` - mask indexes (j * T + t), all of one target - of a kept run appended to one device batch, as
+    """The builds of `todo` - indexes of masks in `d_masks`, all of one cell (a target, or with --dsAFDepth a target x fraction: the
+    params `P` are that cell's) - of a kept run appended to one device batch, as
     _ds_build_run appends successive runs to a _DsBatch, and the batch called with one plan -> (per mask index the listed loci's raw
     rows, in the order of run.group), or NARROW (a build has no room in 16-bit read words)."""
     from . import vc
@@ -1342,13 +1431,17 @@ def _af_rep_call(eng, run: AfRun, table: AfRepTable, d_masks, n_words, todo, P, 
 
 
 def ds_af_replicates(path: str, fasta, variants, targets, params_list, seed: int, n_reps: int, eng, keep: dict, res, sampler: str = "reference",
-                     sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000):
+                     sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, depth: dict = None):
     """The replicate stage of --dsAFReps.  Replicate j is --dsAF with seed (seed + j) mod 2^64: from the pre-pass's sets the carrier
     table goes up once and smc_af_rep_counts gives every (N', V'); then per kept run smc_af_rep_masks makes all R x T keep masks in
     one launch, and every (j, t) is select_run(d_mask) -> build_run -> the locus kernels, the replicates of a target appended to one
     device batch and called with one plan per batch-full.  Replicates of a run whose masks are equal bit for bit are built once.
     -> dict(seeds, counts: uint32 [V, R, T, 2], rows: {(variant index, target index, replicate): the raw row string at the variant's
-    locus}, times: seconds per part)."""
+    locus}, times: seconds per part).
+    `depth` (--dsAFDepth: dict with "fracs" and the "params" of the T x F cells, targets outer): the stage runs over CELLS - the T
+    plain targets first, then the T x F cells, each with its own params; the cells' masks and counts come from smc_af_depth_masks /
+    _counts with the same seeds (replicate j draws both streams with s_j), behind the targets' in one device buffer.  `rows` is then
+    keyed by the cell's index (0 .. T - 1 the targets, T + t x F + f the cells) and "depth_counts" is uint32 [V, R, T, F, 2]."""
     import time
     from . import dsaf
     from .engine import DevBuf
@@ -1359,12 +1452,18 @@ def ds_af_replicates(path: str, fasta, variants, targets, params_list, seed: int
     seeds = dsaf.rep_seeds(seed, n_reps)
     idents, thr = dsaf.carrier_table(keep["carries"], [[row["thr"] for row in r["rows"]] for r in res])
     table = AfRepTable(eng, idents, thr, seeds)
+    F = len(depth["fracs"]) if depth is not None else 0
+    cell_params = list(params_list) + (list(depth["params"]) if depth is not None else [])
+    dtable = depth_counts = None
     times = {"counts": 0.0, "masks": 0.0, "decode again": 0.0, "builds": 0, "batches": 0}
     rows = {}
     max_depth = eng.L.smc_build_max_depth()
     try:
         t0 = time.perf_counter()
         counts = table.counts(keep["covers"], keep["carries"])
+        if depth is not None:
+            dtable = AfDepthTable(eng, idents, thr, seeds, [frac_threshold(f) for f in depth["fracs"]])
+            depth_counts = dtable.counts(keep["covers"], keep["carries"])
         times["counts"] = time.perf_counter() - t0
         for run in keep["runs"]:
             if run.A is None:
@@ -1382,35 +1481,41 @@ def ds_af_replicates(path: str, fasta, variants, targets, params_list, seed: int
             n_bc = int(run.A["n_bc"])
             n_words = mask_words(n_bc)
             d_id = DevBuf(eng, 8 * max(1, n_bc) + 256).upload(np.ascontiguousarray(run.idents, np.uint64) if n_bc else np.zeros(1, np.uint64))
-            d_masks = DevBuf(eng, 4 * n_reps * T * n_words + 256)
+            d_masks = DevBuf(eng, 4 * n_reps * T * (1 + F) * n_words + 256)
             try:
                 t0 = time.perf_counter()
                 table.masks(d_id.data_ptr(), n_bc, d_masks.data_ptr(), n_words)
-                host = d_masks.download(np.uint32, n_reps * T * n_words).reshape(n_reps, T, n_words)      # (behind the kernel)
+                if dtable is not None:
+                    dtable.masks(d_id.data_ptr(), n_bc, d_masks.data_ptr() + 4 * n_reps * T * n_words, n_words)
+                host = d_masks.download(np.uint32, n_reps * T * (1 + F) * n_words)                        # (behind the kernels)
+                # (per cell: the replicates' masks and their indexes in the buffer - the targets' masks first, then the cells')
+                host, host_cells = host[:n_reps * T * n_words].reshape(n_reps, T, n_words), host[n_reps * T * n_words:].reshape(n_reps, T * F, n_words)
+                of_cell = [(host[:, t], [j * T + t for j in range(n_reps)]) for t in range(T)] + \
+                          [(host_cells[:, c], [n_reps * T + j * T * F + c for j in range(n_reps)]) for c in range(T * F)]
                 times["masks"] += time.perf_counter() - t0
                 per_build = int(run.A["n_slots"]) + run.nl
                 room = max(1, AF_REP_BATCH_SLOTS // max(1, per_build))
-                for t in range(T):
+                for t, (cell_masks, index) in enumerate(of_cell):
                     # (equal masks, equal rows: a variant that is left alone at t, or draws that drop the same carriers of this run)
                     first = {}
                     for j in range(n_reps):
-                        first.setdefault(host[j, t].tobytes(), j)
-                    todo = [j * T + t for j in sorted(first.values())]
+                        first.setdefault(cell_masks[j].tobytes(), j)
+                    todo = [index[j] for j in sorted(first.values())]
                     got = {}
                     for b in range(0, len(todo), room):
                         part = todo[b:b + room]
-                        bits = 16 if (eng.word_bits == 16 and 0 <= params_list[t].minBQ <= 63) else 32
-                        out = _af_rep_call(eng, run, table, d_masks, n_words, part, params_list[t], fasta, variants, max_depth, sampler,
+                        bits = 16 if (eng.word_bits == 16 and 0 <= cell_params[t].minBQ <= 63) else 32
+                        out = _af_rep_call(eng, run, table, d_masks, n_words, part, cell_params[t], fasta, variants, max_depth, sampler,
                                            sampler_seed, bits)
                         if out == NARROW:
                             eng.word_bits = 32
-                            out = _af_rep_call(eng, run, table, d_masks, n_words, part, params_list[t], fasta, variants, max_depth, sampler,
+                            out = _af_rep_call(eng, run, table, d_masks, n_words, part, cell_params[t], fasta, variants, max_depth, sampler,
                                                sampler_seed, 32)
                         got.update(out)
                         times["builds"] += len(part)
                         times["batches"] += 1
                     for j in range(n_reps):
-                        text = got[first[host[j, t].tobytes()] * T + t]
+                        text = got[index[first[cell_masks[j].tobytes()]]]
                         for k, line in zip(run.group, text):
                             rows[(k, t, j)] = line
             finally:
@@ -1419,9 +1524,11 @@ def ds_af_replicates(path: str, fasta, variants, targets, params_list, seed: int
             run.free()
     finally:
         table.free()
+        if dtable is not None:
+            dtable.free()
         free_af_runs(keep["runs"])
     times["stage"] = time.perf_counter() - t_start
-    return dict(seeds=seeds, counts=counts, rows=rows, times=times)
+    return dict(seeds=seeds, counts=counts, rows=rows, times=times, depth_counts=depth_counts)
 
 
 def _fnv64(text: str) -> int:

@@ -7,6 +7,9 @@ devplanes.ds_af_rules.
 --dsAFReps: the carrier table the device draws the replicates' masks and counts from, and the two files that turn R x T calls into
 a detection rate with an interval - <outPrefix>.dsAF.replicates.txt and .dsAF.sensitivity.txt (the replicate stage itself is
 devplanes.ds_af_replicates).
+
+--dsAFDepth: the four <outPrefix>.dsAF.depth.* files - the same three pages over the cells (target t, barcode fraction f), and the
+curve: per listed variant and barcode depth the detection rate at every target, and the smallest target still found (t95).
 """
 from __future__ import annotations
 
@@ -183,3 +186,132 @@ def write_sensitivity(out_prefix: str, variants, targets, entries, lods=None) ->
         for i, v in enumerate(variants):
             for t, target in enumerate(targets):
                 fh.write(sensitivity_line(v, target, entries[(i, t)], None if lods is None else float(lods[t][i])) + "\n")
+
+
+# ---- --dsAFDepth
+DEPTH_DETECTION_HEADER = DETECTION_HEADER[:5] + ("FRACTION", "MTDEPTH") + DETECTION_HEADER[5:]
+DEPTH_REPLICATES_HEADER = DEPTH_DETECTION_HEADER[:7] + ("REP", "SEED") + DEPTH_DETECTION_HEADER[7:]
+DEPTH_SENSITIVITY_HEADER = SENSITIVITY_HEADER[:5] + ("FRACTION", "MTDEPTH") + SENSITIVITY_HEADER[5:] + ("N_MEAN",)
+CURVE_HEADER = ("CHROM", "POS", "REF", "ALT", "DEPTH", "MTDEPTH", "N_MEAN")
+T95_RATE = 0.95
+NA = "NA"
+
+
+def t95(targets, rates, level: float = T95_RATE):
+    """The smallest listed target whose detection rate is at least `level` TOGETHER WITH the rate of every larger listed target (a
+    rate that dips below `level` above it disqualifies it: the curve is read from the top), or None.  `targets` in any order."""
+    best = None
+    for t, r in sorted(zip(targets, rates), key=lambda x: -x[0]):
+        if not r >= level:
+            break
+        best = t
+    return best
+
+
+def _cell_fields(line: str, frac: float, mt_depth: int):
+    f = line.split("\t")
+    return f[:5] + ["%g" % frac, "%d" % mt_depth] + f[5:]
+
+
+def depth_detection_line(v, target, frac, mt_depth, n2, v2, k, row, cut, lod=None) -> str:
+    """detection_line() of variant `v` in cell (target, frac) with FRACTION and MTDEPTH behind TARGET."""
+    return "\t".join(_cell_fields(detection_line(v, target, n2, v2, k, row, cut, lod), frac, mt_depth))
+
+
+def depth_replicate_line(v, target, frac, mt_depth, rep: int, seed: int, n2, v2, k, row, cut) -> str:
+    f = _cell_fields(detection_line(v, target, n2, v2, k, row, cut), frac, mt_depth)
+    return "\t".join(f[:7] + ["%d" % rep, "%d" % seed] + f[7:])
+
+
+def _n_mean(reps) -> float:
+    return sum(float(n2) for n2, _, _, _ in reps) / len(reps)
+
+
+def _called(v, reps) -> int:
+    return sum(1 for _, _, _, cut in reps if cut is not None and cut[0] == v.ref and v.alt in cut[1])
+
+
+def depth_sensitivity_line(v, target, frac, mt_depth, reps, lod=None) -> str:
+    """sensitivity_line() of a cell with FRACTION and MTDEPTH behind TARGET and the mean N' behind PI_MIN (then LOD)."""
+    f = _cell_fields(sensitivity_line(v, target, reps), frac, mt_depth) + [frac_text(_n_mean(reps))]
+    if lod is not None:
+        f.append("%.15g" % lod)
+    return "\t".join(f)
+
+
+def curve_line(v, depth, mt_depths, targets, per_target, lod=None) -> str:
+    """One line of the curve: variant `v` at one barcode depth (`depth` None: full, else f).  `mt_depths`: the mtDepth of every target's
+    output at that depth (printed once when equal, else joined by commas); `per_target[t]`: the replicates of target targets[t] there,
+    as sensitivity_line() takes them.  RATE@ columns in ascending target order, then T95."""
+    order = sorted(range(len(targets)), key=lambda t: targets[t])
+    rates = [float(_called(v, per_target[t])) / len(per_target[t]) for t in range(len(targets))]
+    best = t95(targets, rates)
+    depths = ["%d" % d for d in mt_depths]
+    f = [v.chrom, "%d" % v.pos, v.ref, v.alt, FULL if depth is None else "%g" % depth, depths[0] if len(set(depths)) == 1 else ",".join(depths),
+         frac_text(sum(_n_mean(p) for p in per_target) / len(per_target))] + [frac_text(rates[t]) for t in order] + \
+        [NA if best is None else "%g" % best]
+    if lod is not None:
+        f.append("%.15g" % lod)
+    return "\t".join(f)
+
+
+def curve_header(targets, with_lod: bool = False):
+    return CURVE_HEADER + tuple("RATE@%g" % t for t in sorted(targets)) + ("T95",) + (("LOD",) if with_lod else ())
+
+
+def write_depth_detection(out_prefix: str, variants, cells, counts, ks, loc_index=None) -> None:
+    """<outPrefix>.dsAF.depth.detection.txt: a header, then a line per listed variant and cell (targets outer, fractions inner).
+    `cells`: per cell (target index, target, fraction, mtDepth, output prefix, that output's LODs by locus index or None);
+    counts[v][cell] = (N', V'); ks[t][v]: the keep probability."""
+    read = [read_output(c[4]) for c in cells]
+    with_lod = any(c[5] is not None for c in cells)
+    with open(out_prefix + ".dsAF.depth.detection.txt", "w") as fh:
+        fh.write("\t".join(DEPTH_DETECTION_HEADER + (("LOD",) if with_lod else ())) + "\n")
+        for i, v in enumerate(variants):
+            key = (v.chrom, "%d" % v.pos)
+            for c, ((t, target, frac, depth, _, lods), (rows, cut)) in enumerate(zip(cells, read)):
+                lod = float(lods[loc_index[key]]) if lods is not None else None
+                fh.write(depth_detection_line(v, target, frac, depth, int(counts[i][c][0]), int(counts[i][c][1]), ks[t][i], rows.get(key),
+                                              cut.get(key), lod) + "\n")
+
+
+def write_depth_replicates(out_prefix: str, variants, cells, seeds, ks, entries) -> None:
+    """<outPrefix>.dsAF.depth.replicates.txt: a line per listed variant, cell and replicate.  entries[(v, cell)]: per replicate (N', V',
+    row fields or None, cut or None)."""
+    with open(out_prefix + ".dsAF.depth.replicates.txt", "w") as fh:
+        fh.write("\t".join(DEPTH_REPLICATES_HEADER) + "\n")
+        for i, v in enumerate(variants):
+            for c, (t, target, frac, depth, _, _) in enumerate(cells):
+                for j, (n2, v2, row, cut) in enumerate(entries[(i, c)]):
+                    fh.write(depth_replicate_line(v, target, frac, depth, j, seeds[j], n2, v2, ks[t][i], row, cut) + "\n")
+
+
+def write_depth_sensitivity(out_prefix: str, variants, cells, entries, loc_index=None) -> None:
+    """<outPrefix>.dsAF.depth.sensitivity.txt: a line per listed variant and cell; LOD: the locus's in the run's own output of the cell."""
+    with_lod = any(c[5] is not None for c in cells)
+    with open(out_prefix + ".dsAF.depth.sensitivity.txt", "w") as fh:
+        fh.write("\t".join(DEPTH_SENSITIVITY_HEADER + (("LOD",) if with_lod else ())) + "\n")
+        for i, v in enumerate(variants):
+            for c, (t, target, frac, depth, _, lods) in enumerate(cells):
+                lod = float(lods[loc_index[(v.chrom, "%d" % v.pos)]]) if lods is not None else None
+                fh.write(depth_sensitivity_line(v, target, frac, depth, entries[(i, c)], lod) + "\n")
+
+
+def write_depth_curve(out_prefix: str, variants, targets, fracs, full, cells, full_entries, entries, loc_index=None) -> None:
+    """<outPrefix>.dsAF.depth.curve.txt: a line per listed variant and barcode depth - `full` (the plain targets' outputs) first, then
+    every fraction.  `full`: per target (mtDepth, the LODs of that target's .dsAF<t> output or None); full_entries[(v, t)] /
+    entries[(v, cell)]: the replicates.  LOD: the locus's theoretical one at that depth, in the output of the LARGEST listed target
+    there (the least diluted one, at the mtDepth the line shows for it) - its .dsAF<t> output on the `full` line, its cell at f."""
+    T, F = len(targets), len(fracs)
+    top = max(range(T), key=lambda t: targets[t])
+    with_lod = any(c[5] is not None for c in cells)
+    with open(out_prefix + ".dsAF.depth.curve.txt", "w") as fh:
+        fh.write("\t".join(curve_header(targets, with_lod)) + "\n")
+        for i, v in enumerate(variants):
+            at = loc_index[(v.chrom, "%d" % v.pos)] if with_lod else None
+            fh.write(curve_line(v, None, [d for d, _ in full], targets, [full_entries[(i, t)] for t in range(T)],
+                                float(full[top][1][at]) if with_lod else None) + "\n")
+            for k, f in enumerate(fracs):
+                mine = [cells[t * F + k] for t in range(T)]
+                fh.write(curve_line(v, f, [c[3] for c in mine], targets, [entries[(i, t * F + k)] for t in range(T)],
+                                    float(mine[top][5][at]) if with_lod else None) + "\n")

@@ -522,12 +522,14 @@ int smc_allele_carriers(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, c
  *   _masks   for the n_ids run-wide barcode identities of one decoded run (d_idents: smc_bam_barcode_idents, uploaded):
  *            d_masks[(j * n_targets + t) * n_words + (g >> 5)] bit (g & 31) = id g is kept - n_reps * n_targets masks of n_words
  *            uint32 words each, n_words >= ceil(n_ids / 32); the bits at and beyond n_ids and the words behind them are written
- *            as 0.  Each is a mask smc_select_alignments takes as d_keep_mask.  d_draws (may be NULL): [n_reps][n_ids] the draw of
- *            every carrier, 0 for the others (tests).
+ *            as 0.  Each is a mask smc_select_alignments takes as d_keep_mask.  d_draws (may be NULL): [n_reps][n_ids] the "dsAF"
+ *            draw u_j of every carrier, 0 for the others (tests).
  *   _counts  the achieved numbers, file-wide: d_cov_ident / d_cov_carry hold the covering barcodes of all n_var listed variants one
  *            behind the other (variant v's at [cov_off[v], cov_off[v + 1]); carry != 0: the barcode carries v) ->
  *            d_out[v][j][t][2] uint32 = (N', V'): the kept covering barcodes and the kept carriers of v.  d_cov_off: the n_var + 1
  *            offsets in device memory, `cov_off_host` the same on the host.  d_out is zeroed by the call.
+ * Both ARE the smc_af_depth_* entries below at one fraction whose threshold is 2^32 (every barcode passes the depth rule; its draw
+ * is not made): the same kernels, the same checks, the entry's own name in the messages.
  * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched: a table that is not strictly ascending, a threshold above
  * 2^32, n_targets above SMC_AF_REP_MAX_TARGETS, n_reps above SMC_AF_REP_MAX_REPS, n_words below ceil(n_ids / 32),
  * n_reps * n_targets * n_words (or n_var * n_reps * n_targets * 2) of 2^32 - 256 words or more, offsets that decrease. */
@@ -544,10 +546,12 @@ int smc_af_rep_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint8_t* 
  * --dsAF dilution.  A barcode is KEPT in cell (t, f) of replicate j when smc_af_rep_masks keeps it at t (the carrier table and the
  * "dsAF" draw above, key seeds[j]) AND its depth draw d_j(b) = word 0 of Philox4x32-10(counter = (identity lo, identity hi,
  * 0x64734D54 "dsMT", 0), key = (seeds[j] lo, hi)) - smc_select_alignments' philox rule - is below depth_thr[f].  `depth_thr`: HOST
- * memory, n_fracs words, floor(f * 2^32) each and 2^32 at f = 1 (every barcode stays: the masks are smc_af_rep_masks').  The depth
- * draw is made for every barcode, the "dsAF" draw for carriers only.
+ * memory, n_fracs words, floor(f * 2^32) each and 2^32 at f = 1 (every barcode stays: the masks and the counts are smc_af_rep_*'s,
+ * which are these entries at that one fraction).  The depth draw is made for every barcode - unless no threshold is below 2^32 and
+ * d_draws is NULL, when it decides nothing - the "dsAF" draw for carriers only.
  *   _masks   d_masks[((j * n_targets + t) * n_fracs + f) * n_words + (g >> 5)] bit (g & 31) = id g is kept: n_reps * n_targets *
- *            n_fracs masks in smc_af_rep_masks' layout.  d_draws (may be NULL): [n_reps][n_ids] the depth draw of every id (tests).
+ *            n_fracs masks in smc_af_rep_masks' layout.  d_draws (may be NULL): [n_reps][n_ids] the "dsMT" depth draw d_j of every
+ *            id - not the "dsAF" draw smc_af_rep_masks reports (tests).
  *   _counts  d_out[v][j][t][f][2] uint32 = (N', V') of the cell, from the covering barcodes as smc_af_rep_counts takes them.
  * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched: what smc_af_rep_masks / _counts refuse, a depth threshold
  * above 2^32, n_targets * n_fracs above SMC_AF_DEPTH_MAX_CELLS, an output of 2^32 - 256 words or more. */

@@ -1094,10 +1094,11 @@ int smc_allele_carriers(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, c
     return SMC_OK;
 }
 
-// (--dsAFReps) what both entries check of the carrier table, on its host copy
-static int afr_check_table(const char* who, const uint64_t* d_car, const uint64_t* d_car_thr, const uint64_t* car_host,
-                           const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets, const uint64_t* d_seeds, int32_t n_reps) {
-    const std::string w(who);
+// (--dsAFReps, --dsAFDepth) what the four entries check of the carrier table, on its host copy, and of the fractions' thresholds
+// (host memory), which go into the kernels' argument -> `with_depth`: a fraction is below 2^32, so the depth draw decides something
+static int afd_check_table(const std::string& w, const uint64_t* d_car, const uint64_t* d_car_thr, const uint64_t* car_host,
+                           const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs,
+                           const uint64_t* d_seeds, int32_t n_reps, AfdThr& D, int& with_depth) {
     if (n_car < 0 || n_car >= (int64_t)0x7FFFFF00 || n_targets < 0 || n_reps < 0) return fail(SMC_E_ARG, w + ": bad argument");
     if (n_targets > SMC_AF_REP_MAX_TARGETS) return fail(SMC_E_INPUT, w + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_AF_REP_MAX_TARGETS));
     if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, w + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
@@ -1109,123 +1110,73 @@ static int afr_check_table(const char* who, const uint64_t* d_car, const uint64_
     for (int64_t k = 0; k < n_car * (int64_t)n_targets; ++k)
         if (car_thr_host[k] > (1ull << 32))
             return fail(SMC_E_INPUT, w + ": threshold " + std::to_string(k) + " of the carrier table is above 2^32");
-    return SMC_OK;
-}
-
-int smc_af_rep_masks(smc_ctx* ctx, const uint64_t* d_idents, int64_t n_ids, const uint64_t* d_car, const uint64_t* d_car_thr,
-                     const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets, const uint64_t* d_seeds,
-                     int32_t n_reps, uint32_t* d_masks, int64_t n_words, uint32_t* d_draws, void* stream) {
-    if (!ctx || n_ids < 0 || n_ids >= (int64_t)0x7FFFFF00 || n_words < 0) return fail(SMC_E_ARG, "smc_af_rep_masks: bad argument");
-    { const int rc = afr_check_table("smc_af_rep_masks", d_car, d_car_thr, car_host, car_thr_host, n_car, n_targets, d_seeds, n_reps); if (rc) return rc; }
-    if (n_words < (n_ids + 31) / 32)
-        return fail(SMC_E_INPUT, "smc_af_rep_masks: " + std::to_string(n_words) + " words per mask for " + std::to_string(n_ids) + " ids");
-    if ((double)n_reps * (double)n_targets * (double)n_words >= (double)0xFFFFFF00u)
-        return fail(SMC_E_INPUT, "smc_af_rep_masks: " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) + " targets x " +
-                                 std::to_string(n_words) + " words: too many mask words for one call");
-    if (!n_reps || !n_targets || !n_words) return SMC_OK;
-    if (!d_masks || (n_ids && !d_idents)) return fail(SMC_E_ARG, "smc_af_rep_masks: NULL argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    const unsigned gx = (unsigned)(((n_words + 1) / 2 * WAVE + AFR_BLOCK - 1) / AFR_BLOCK);      // (two words per wave)
-    hipLaunchKernelGGL(k_afr_masks, dim3(gx, (unsigned)std::min<int32_t>(n_reps, 64)), dim3(AFR_BLOCK), 0, (hipStream_t)stream,
-                       (const unsigned long long*)d_idents, (uint32_t)n_ids, (const unsigned long long*)d_car, (const unsigned long long*)d_car_thr,
-                       (uint32_t)n_car, (int)n_targets, (const unsigned long long*)d_seeds, (int)n_reps, d_masks, (uint32_t)n_words, d_draws);
-    HIPCHK(hipGetLastError());
-    return SMC_OK;
-}
-
-int smc_af_rep_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint8_t* d_cov_carry, const uint32_t* d_cov_off,
-                      const uint32_t* cov_off_host, int32_t n_var, const uint64_t* d_car, const uint64_t* d_car_thr,
-                      const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets, const uint64_t* d_seeds,
-                      int32_t n_reps, uint32_t* d_out, void* stream) {
-    if (!ctx || n_var < 0) return fail(SMC_E_ARG, "smc_af_rep_counts: bad argument");
-    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, "smc_af_rep_counts: " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
-    { const int rc = afr_check_table("smc_af_rep_counts", d_car, d_car_thr, car_host, car_thr_host, n_car, n_targets, d_seeds, n_reps); if (rc) return rc; }
-    if ((double)n_var * (double)n_reps * (double)n_targets * 2.0 >= (double)0xFFFFFF00u)
-        return fail(SMC_E_INPUT, "smc_af_rep_counts: " + std::to_string(n_var) + " variants x " + std::to_string(n_reps) + " replicates x " +
-                                 std::to_string(n_targets) + " targets: too many counters for one call");
-    if (!n_var || !n_reps || !n_targets) return SMC_OK;
-    if (!cov_off_host || !d_cov_off || !d_out) return fail(SMC_E_ARG, "smc_af_rep_counts: NULL argument");
-    uint32_t widest = 0;
-    for (int32_t v = 0; v < n_var; ++v) {
-        if (cov_off_host[v + 1] < cov_off_host[v]) return fail(SMC_E_INPUT, "smc_af_rep_counts: the offsets decrease at variant " + std::to_string(v));
-        widest = std::max(widest, cov_off_host[v + 1] - cov_off_host[v]);
-    }
-    if (cov_off_host[n_var] >= 0xFFFFFF00u) return fail(SMC_E_INPUT, "smc_af_rep_counts: too many covering barcodes for one call");
-    if (cov_off_host[n_var] && (!d_cov_ident || !d_cov_carry)) return fail(SMC_E_ARG, "smc_af_rep_counts: NULL covers");
-    HIPCHK(hipSetDevice(ctx->device));
-    const hipStream_t st = (hipStream_t)stream;
-    const size_t n_out = 2 * (size_t)n_var * (size_t)n_reps * (size_t)n_targets;
-    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
-    if (widest)
-        hipLaunchKernelGGL(k_afr_counts, dim3((unsigned)std::min<uint32_t>((widest + AFR_BLOCK - 1) / AFR_BLOCK, 256u), (unsigned)n_var,
-                                              (unsigned)std::min<int32_t>(n_reps, 64)), dim3(AFR_BLOCK), 0, st,
-                           (const unsigned long long*)d_cov_ident, d_cov_carry, d_cov_off, (const unsigned long long*)d_car,
-                           (const unsigned long long*)d_car_thr, (uint32_t)n_car, (int)n_targets, (const unsigned long long*)d_seeds, (int)n_reps, d_out);
-    HIPCHK(hipGetLastError());
-    return SMC_OK;
-}
-
-// (--dsAFDepth) the fractions' thresholds (host memory) into the kernels' argument, and the bound on the cells
-static int afd_thresholds(const char* who, const uint64_t* depth_thr, int32_t n_targets, int32_t n_fracs, AfdThr& D) {
-    const std::string w(who);
     if (n_fracs < 0 || (n_fracs && !depth_thr)) return fail(SMC_E_ARG, w + ": bad depth thresholds");
     if ((int64_t)n_targets * (int64_t)n_fracs > SMC_AF_DEPTH_MAX_CELLS)
         return fail(SMC_E_INPUT, w + ": " + std::to_string(n_targets) + " targets x " + std::to_string(n_fracs) + " fractions, at most " +
                                  std::to_string(SMC_AF_DEPTH_MAX_CELLS) + " cells");
     memset(&D, 0, sizeof D);
+    with_depth = 0;
     for (int f = 0; f < n_fracs; ++f) {
         if (depth_thr[f] > (1ull << 32)) return fail(SMC_E_INPUT, w + ": depth threshold " + std::to_string(f) + " is above 2^32");
         D.f[f] = depth_thr[f];
+        with_depth |= depth_thr[f] < (1ull << 32);
     }
     return SMC_OK;
 }
 
-int smc_af_depth_masks(smc_ctx* ctx, const uint64_t* d_idents, int64_t n_ids, const uint64_t* d_car, const uint64_t* d_car_thr,
-                       const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets,
-                       const uint64_t* depth_thr, int32_t n_fracs, const uint64_t* d_seeds, int32_t n_reps, uint32_t* d_masks,
-                       int64_t n_words, uint32_t* d_draws, void* stream) {
-    if (!ctx || n_ids < 0 || n_ids >= (int64_t)0x7FFFFF00 || n_words < 0) return fail(SMC_E_ARG, "smc_af_depth_masks: bad argument");
-    { const int rc = afr_check_table("smc_af_depth_masks", d_car, d_car_thr, car_host, car_thr_host, n_car, n_targets, d_seeds, n_reps); if (rc) return rc; }
+// The replicate entries are the depth entries at one fraction of 2^32 (every barcode passes the depth rule): one body per call.
+// `who`: the entry, for the messages; `frac_text`: whether they name the fractions (the replicate entries have none to name).
+static const uint64_t AFR_ONE_FRACTION[1] = {1ull << 32};
+static std::string afd_fracs_text(bool frac_text, int32_t n_fracs) { return frac_text ? " x " + std::to_string(n_fracs) + " fractions" : std::string(); }
+
+static int af_cell_masks(const char* who, bool frac_text, smc_ctx* ctx, const uint64_t* d_idents, int64_t n_ids, const uint64_t* d_car,
+                         const uint64_t* d_car_thr, const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets,
+                         const uint64_t* depth_thr, int32_t n_fracs, const uint64_t* d_seeds, int32_t n_reps, uint32_t* d_masks,
+                         int64_t n_words, uint32_t* d_draws_af, uint32_t* d_draws_depth, void* stream) {
+    const std::string w(who);
+    if (!ctx || n_ids < 0 || n_ids >= (int64_t)0x7FFFFF00 || n_words < 0) return fail(SMC_E_ARG, w + ": bad argument");
     AfdThr D;
-    { const int rc = afd_thresholds("smc_af_depth_masks", depth_thr, n_targets, n_fracs, D); if (rc) return rc; }
+    int with_depth;
+    { const int rc = afd_check_table(w, d_car, d_car_thr, car_host, car_thr_host, n_car, n_targets, depth_thr, n_fracs, d_seeds, n_reps, D, with_depth); if (rc) return rc; }
     if (n_words < (n_ids + 31) / 32)
-        return fail(SMC_E_INPUT, "smc_af_depth_masks: " + std::to_string(n_words) + " words per mask for " + std::to_string(n_ids) + " ids");
+        return fail(SMC_E_INPUT, w + ": " + std::to_string(n_words) + " words per mask for " + std::to_string(n_ids) + " ids");
     if ((double)n_reps * (double)n_targets * (double)n_fracs * (double)n_words >= (double)0xFFFFFF00u)
-        return fail(SMC_E_INPUT, "smc_af_depth_masks: " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) + " targets x " +
-                                 std::to_string(n_fracs) + " fractions x " + std::to_string(n_words) + " words: too many mask words for one call");
+        return fail(SMC_E_INPUT, w + ": " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) + " targets" +
+                                 afd_fracs_text(frac_text, n_fracs) + " x " + std::to_string(n_words) + " words: too many mask words for one call");
     if (!n_reps || !n_targets || !n_fracs || !n_words) return SMC_OK;
-    if (!d_masks || (n_ids && !d_idents)) return fail(SMC_E_ARG, "smc_af_depth_masks: NULL argument");
+    if (!d_masks || (n_ids && !d_idents)) return fail(SMC_E_ARG, w + ": NULL argument");
     HIPCHK(hipSetDevice(ctx->device));
     const unsigned gx = (unsigned)(((n_words + 1) / 2 * WAVE + AFR_BLOCK - 1) / AFR_BLOCK);      // (two words per wave)
     hipLaunchKernelGGL(k_afd_masks, dim3(gx, (unsigned)std::min<int32_t>(n_reps, 64)), dim3(AFR_BLOCK), 0, (hipStream_t)stream,
                        (const unsigned long long*)d_idents, (uint32_t)n_ids, (const unsigned long long*)d_car, (const unsigned long long*)d_car_thr,
-                       (uint32_t)n_car, (int)n_targets, D, (int)n_fracs, (const unsigned long long*)d_seeds, (int)n_reps, d_masks,
-                       (uint32_t)n_words, d_draws);
+                       (uint32_t)n_car, (int)n_targets, D, (int)n_fracs, (int)(with_depth || d_draws_depth), (const unsigned long long*)d_seeds,
+                       (int)n_reps, d_masks, (uint32_t)n_words, d_draws_af, d_draws_depth);
     HIPCHK(hipGetLastError());
     return SMC_OK;
 }
 
-int smc_af_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint8_t* d_cov_carry, const uint32_t* d_cov_off,
-                        const uint32_t* cov_off_host, int32_t n_var, const uint64_t* d_car, const uint64_t* d_car_thr,
-                        const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets,
-                        const uint64_t* depth_thr, int32_t n_fracs, const uint64_t* d_seeds, int32_t n_reps, uint32_t* d_out, void* stream) {
-    if (!ctx || n_var < 0) return fail(SMC_E_ARG, "smc_af_depth_counts: bad argument");
-    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, "smc_af_depth_counts: " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
-    { const int rc = afr_check_table("smc_af_depth_counts", d_car, d_car_thr, car_host, car_thr_host, n_car, n_targets, d_seeds, n_reps); if (rc) return rc; }
+static int af_cell_counts(const char* who, bool frac_text, smc_ctx* ctx, const uint64_t* d_cov_ident, const uint8_t* d_cov_carry,
+                          const uint32_t* d_cov_off, const uint32_t* cov_off_host, int32_t n_var, const uint64_t* d_car, const uint64_t* d_car_thr,
+                          const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets, const uint64_t* depth_thr,
+                          int32_t n_fracs, const uint64_t* d_seeds, int32_t n_reps, uint32_t* d_out, void* stream) {
+    const std::string w(who);
+    if (!ctx || n_var < 0) return fail(SMC_E_ARG, w + ": bad argument");
+    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, w + ": " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
     AfdThr D;
-    { const int rc = afd_thresholds("smc_af_depth_counts", depth_thr, n_targets, n_fracs, D); if (rc) return rc; }
+    int with_depth;
+    { const int rc = afd_check_table(w, d_car, d_car_thr, car_host, car_thr_host, n_car, n_targets, depth_thr, n_fracs, d_seeds, n_reps, D, with_depth); if (rc) return rc; }
     if ((double)n_var * (double)n_reps * (double)n_targets * (double)n_fracs * 2.0 >= (double)0xFFFFFF00u)
-        return fail(SMC_E_INPUT, "smc_af_depth_counts: " + std::to_string(n_var) + " variants x " + std::to_string(n_reps) + " replicates x " +
-                                 std::to_string(n_targets) + " targets x " + std::to_string(n_fracs) + " fractions: too many counters for one call");
+        return fail(SMC_E_INPUT, w + ": " + std::to_string(n_var) + " variants x " + std::to_string(n_reps) + " replicates x " +
+                                 std::to_string(n_targets) + " targets" + afd_fracs_text(frac_text, n_fracs) + ": too many counters for one call");
     if (!n_var || !n_reps || !n_targets || !n_fracs) return SMC_OK;
-    if (!cov_off_host || !d_cov_off || !d_out) return fail(SMC_E_ARG, "smc_af_depth_counts: NULL argument");
+    if (!cov_off_host || !d_cov_off || !d_out) return fail(SMC_E_ARG, w + ": NULL argument");
     uint32_t widest = 0;
     for (int32_t v = 0; v < n_var; ++v) {
-        if (cov_off_host[v + 1] < cov_off_host[v]) return fail(SMC_E_INPUT, "smc_af_depth_counts: the offsets decrease at variant " + std::to_string(v));
+        if (cov_off_host[v + 1] < cov_off_host[v]) return fail(SMC_E_INPUT, w + ": the offsets decrease at variant " + std::to_string(v));
         widest = std::max(widest, cov_off_host[v + 1] - cov_off_host[v]);
     }
-    if (cov_off_host[n_var] >= 0xFFFFFF00u) return fail(SMC_E_INPUT, "smc_af_depth_counts: too many covering barcodes for one call");
-    if (cov_off_host[n_var] && (!d_cov_ident || !d_cov_carry)) return fail(SMC_E_ARG, "smc_af_depth_counts: NULL covers");
+    if (cov_off_host[n_var] >= 0xFFFFFF00u) return fail(SMC_E_INPUT, w + ": too many covering barcodes for one call");
+    if (cov_off_host[n_var] && (!d_cov_ident || !d_cov_carry)) return fail(SMC_E_ARG, w + ": NULL covers");
     HIPCHK(hipSetDevice(ctx->device));
     const hipStream_t st = (hipStream_t)stream;
     const size_t n_out = 2 * (size_t)n_var * (size_t)n_reps * (size_t)n_targets * (size_t)n_fracs;
@@ -1234,10 +1185,41 @@ int smc_af_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint8_t
         hipLaunchKernelGGL(k_afd_counts, dim3((unsigned)std::min<uint32_t>((widest + AFR_BLOCK - 1) / AFR_BLOCK, 256u), (unsigned)n_var,
                                               (unsigned)std::min<int32_t>(n_reps, 64)), dim3(AFR_BLOCK), 0, st,
                            (const unsigned long long*)d_cov_ident, d_cov_carry, d_cov_off, (const unsigned long long*)d_car,
-                           (const unsigned long long*)d_car_thr, (uint32_t)n_car, (int)n_targets, D, (int)n_fracs,
+                           (const unsigned long long*)d_car_thr, (uint32_t)n_car, (int)n_targets, D, (int)n_fracs, with_depth,
                            (const unsigned long long*)d_seeds, (int)n_reps, d_out);
     HIPCHK(hipGetLastError());
     return SMC_OK;
+}
+
+int smc_af_rep_masks(smc_ctx* ctx, const uint64_t* d_idents, int64_t n_ids, const uint64_t* d_car, const uint64_t* d_car_thr,
+                     const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets, const uint64_t* d_seeds,
+                     int32_t n_reps, uint32_t* d_masks, int64_t n_words, uint32_t* d_draws, void* stream) {
+    return af_cell_masks("smc_af_rep_masks", false, ctx, d_idents, n_ids, d_car, d_car_thr, car_host, car_thr_host, n_car, n_targets,
+                         AFR_ONE_FRACTION, 1, d_seeds, n_reps, d_masks, n_words, d_draws, nullptr, stream);
+}
+
+int smc_af_rep_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint8_t* d_cov_carry, const uint32_t* d_cov_off,
+                      const uint32_t* cov_off_host, int32_t n_var, const uint64_t* d_car, const uint64_t* d_car_thr,
+                      const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets, const uint64_t* d_seeds,
+                      int32_t n_reps, uint32_t* d_out, void* stream) {
+    return af_cell_counts("smc_af_rep_counts", false, ctx, d_cov_ident, d_cov_carry, d_cov_off, cov_off_host, n_var, d_car, d_car_thr,
+                          car_host, car_thr_host, n_car, n_targets, AFR_ONE_FRACTION, 1, d_seeds, n_reps, d_out, stream);
+}
+
+int smc_af_depth_masks(smc_ctx* ctx, const uint64_t* d_idents, int64_t n_ids, const uint64_t* d_car, const uint64_t* d_car_thr,
+                       const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets,
+                       const uint64_t* depth_thr, int32_t n_fracs, const uint64_t* d_seeds, int32_t n_reps, uint32_t* d_masks,
+                       int64_t n_words, uint32_t* d_draws, void* stream) {
+    return af_cell_masks("smc_af_depth_masks", true, ctx, d_idents, n_ids, d_car, d_car_thr, car_host, car_thr_host, n_car, n_targets,
+                         depth_thr, n_fracs, d_seeds, n_reps, d_masks, n_words, nullptr, d_draws, stream);
+}
+
+int smc_af_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint8_t* d_cov_carry, const uint32_t* d_cov_off,
+                        const uint32_t* cov_off_host, int32_t n_var, const uint64_t* d_car, const uint64_t* d_car_thr,
+                        const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets,
+                        const uint64_t* depth_thr, int32_t n_fracs, const uint64_t* d_seeds, int32_t n_reps, uint32_t* d_out, void* stream) {
+    return af_cell_counts("smc_af_depth_counts", true, ctx, d_cov_ident, d_cov_carry, d_cov_off, cov_off_host, n_var, d_car, d_car_thr,
+                          car_host, car_thr_host, n_car, n_targets, depth_thr, n_fracs, d_seeds, n_reps, d_out, stream);
 }
 
 // (--dsGrid) the cells' thresholds: bc_thr[c] (sel_keep's: floor(f * 2^32), 2^32 keeps every barcode) and rd_thr[c], each <= 2^32

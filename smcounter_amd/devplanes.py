@@ -699,7 +699,7 @@ class DsRule:
     af: float = None
     dropped_idents: object = None
     # (--dsAFDepth) a cell: `af` t and `frac` f; `dropped_idents` of t beside `bc_thr` = the --dsMT draw's threshold at f; `depth`: the
-    # cells' AfDepthTable in HBM (one for all cells of the run), `cell` this one's index in its masks (t x F + f)
+    # cells' AfCellTable in HBM (one for all cells of the run), `cell` this one's index in its masks (t x F + f)
     depth: object = None
     cell: int = None
 
@@ -1215,7 +1215,7 @@ def ds_af_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     over the pre-pass's sets) -> (rules, titrate()'s result: per target the dropped identities and per variant N, V, a, k, N', V').
     ValueError: two barcode texts of the file share an identity.  `keep` (--dsAFReps): a dict that gets what the replicate stage
     starts from - "runs" (ds_af_sets' kept runs), "covers" and "carries".  `depth` (--dsAFDepth): a dict with "fracs" and "params" (of
-    the T x F cells, targets outer); it gets "rules" (a DsRule per cell over one AfDepthTable in HBM: close_rules frees it) and
+    the T x F cells, targets outer); it gets "rules" (a DsRule per cell over one AfCellTable in HBM: close_rules frees it) and
     "counts", uint32 [V, T, F, 2] = the achieved (N', V') of every cell (smc_af_depth_counts)."""
     import time
     from .tools import ds_allele_fraction as af
@@ -1237,7 +1237,7 @@ def ds_af_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
         from . import dsaf
         fracs = list(depth["fracs"])
         idents, thr = dsaf.carrier_table(carries, [[row["thr"] for row in r["rows"]] for r in res])
-        table = AfDepthTable(eng, idents, thr, [int(seed) & 0xFFFFFFFFFFFFFFFF], [frac_threshold(f) for f in fracs])
+        table = AfCellTable(eng, idents, thr, [int(seed) & 0xFFFFFFFFFFFFFFFF], [frac_threshold(f) for f in fracs])
         try:
             depth["counts"] = table.counts(covers, carries)[:, 0]
             depth["rules"] = [DsRule(float(f), depth["params"][t * len(fracs) + k], seed=int(seed), af=float(targets[t]),
@@ -1286,88 +1286,73 @@ def free_af_runs(runs):
         r.free()
 
 
-class AfRepTable(object):
-    """The carrier table and the seeds of --dsAFReps in HBM (dsaf.carrier_table; csrc/k_af_reps.inc) with their host copies, and the
-    two calls over them."""
+class AfCellTable(object):
+    """The carrier table and the seeds of --dsAFReps / --dsAFDepth in HBM (dsaf.carrier_table; csrc/k_af_depth.inc) with their host
+    copies, and the two calls over them.  `depth_thr` (--dsAFDepth): the thresholds of the barcode fractions (frac_threshold(f), host
+    memory: they travel by value) - the results then have one dimension more, the fractions', behind the targets'."""
 
-    def __init__(self, eng, idents, thr, seeds):
+    def __init__(self, eng, idents, thr, seeds, depth_thr=None):
         from .engine import DevBuf
         self.eng = eng
         self.idents = np.ascontiguousarray(idents, np.uint64)
         self.thr = np.ascontiguousarray(thr, np.uint64)              # [carriers, targets]
         self.seeds = np.ascontiguousarray(seeds, np.uint64)
         if self.thr.ndim != 2 or self.thr.shape[0] != len(self.idents):
-            raise ValueError("AfRepTable: %d carriers, thresholds of shape %r" % (len(self.idents), self.thr.shape))
+            raise ValueError("AfCellTable: %d carriers, thresholds of shape %r" % (len(self.idents), self.thr.shape))
         self.n_targets = int(self.thr.shape[1])
+        self.depth_thr = None if depth_thr is None else np.ascontiguousarray(depth_thr, np.uint64)
+        self.n_fracs = None if depth_thr is None else len(self.depth_thr)
         up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.reshape(-1) if a.size else np.zeros(1, a.dtype))
         self.d_idents, self.d_thr, self.d_seeds = up(self.idents), up(self.thr), up(self.seeds)
 
-    def _table(self):
-        return (self.d_idents.data_ptr(), self.d_thr.data_ptr(), self.idents.ctypes.data, self.thr.ctypes.data, len(self.idents),
-                self.n_targets, self.d_seeds.data_ptr(), len(self.seeds))
+    def _call(self, kind: str, head: tuple, tail: tuple, depth):
+        """smc_af_rep_<kind> or, with `depth` thresholds, smc_af_depth_<kind>: `head`, the table (the thresholds behind the targets),
+        the seeds, `tail`, the default stream."""
+        name = "smc_af_%s_%s" % ("rep" if depth is None else "depth", kind)
+        args = [self.eng.ctx, *head, self.d_idents.data_ptr(), self.d_thr.data_ptr(), self.idents.ctypes.data, self.thr.ctypes.data,
+                len(self.idents), self.n_targets]
+        if depth is not None:
+            args += [depth.ctypes.data, len(depth)]
+        args += [self.d_seeds.data_ptr(), len(self.seeds), *tail, ctypes.c_void_p(0)]
+        _lib.check(getattr(self.eng.L, name)(*args), name)
 
-    def masks(self, d_run_idents, n_ids: int, d_masks, n_words: int, d_draws=None):
-        """smc_af_rep_masks: len(seeds) x n_targets keep masks of `n_words` words each over a run's barcode identities (device
-        addresses), replicate-major - mask (j, t) is what select_run(d_mask=...) takes."""
-        _lib.check(self.eng.L.smc_af_rep_masks(self.eng.ctx, d_run_idents, int(n_ids), *self._table(), d_masks, int(n_words), d_draws,
-                                               ctypes.c_void_p(0)), "smc_af_rep_masks")
+    def masks(self, d_run_idents, n_ids: int, d_masks, n_words: int, d_draws=None, plain: bool = False):
+        """smc_af_rep_masks / smc_af_depth_masks: len(seeds) x n_targets [x n_fracs] keep masks of `n_words` words each over a run's
+        barcode identities (device addresses) - mask (j x T + t) [x F + f] is what select_run(d_mask=...) takes.  d_draws: uint32
+        [len(seeds), n_ids], the AF draw of every carrier (0 for the others) or, with fractions, the depth draw of every id.
+        `plain`: the targets' masks of a table with fractions, as if it had none."""
+        self._call("masks", (d_run_idents, int(n_ids)), (d_masks, int(n_words), d_draws), None if plain else self.depth_thr)
 
-    def counts(self, covers, carries) -> np.ndarray:
-        """smc_af_rep_counts: uint32 [V, R, T, 2] = (N', V') of every variant, replicate and target, from the identities that cover /
-        carry each variant (made unique here, as titrate() does)."""
-        return self._counts(covers, carries, self.n_targets, lambda bufs, off, n_var: _lib.check(self.eng.L.smc_af_rep_counts(
-            self.eng.ctx, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data, n_var, *self._table(), bufs[3].data_ptr(),
-            ctypes.c_void_p(0)), "smc_af_rep_counts")).reshape(len(covers), len(self.seeds), self.n_targets, 2)
-
-    def _counts(self, covers, carries, per_rep: int, call) -> np.ndarray:
-        """The covering barcodes up, `call(bufs, offsets, n_var)`, the 2 x V x R x per_rep counters back."""
+    def counts(self, covers, carries, plain: bool = False) -> np.ndarray:
+        """smc_af_rep_counts / smc_af_depth_counts: uint32 [V, R, T, 2] or [V, R, T, F, 2] = (N', V') of every variant, replicate and
+        target [and fraction], from the identities that cover / carry each variant (made unique here, as titrate() does)."""
         from .engine import DevBuf
+        depth = None if plain else self.depth_thr
+        shape = (len(covers), len(self.seeds), self.n_targets) + (() if depth is None else (len(depth),)) + (2,)
         covers = [np.unique(np.asarray(c, np.uint64)) for c in covers]
         off = np.zeros(len(covers) + 1, np.uint32)
         off[1:] = np.cumsum([len(c) for c in covers])
         ident = np.concatenate(covers) if covers else np.zeros(0, np.uint64)
         carry = np.concatenate([np.isin(c, np.asarray(k, np.uint64)) for c, k in zip(covers, carries)]).astype(np.uint8) if covers \
             else np.zeros(0, np.uint8)
-        n_out = 2 * len(covers) * len(self.seeds) * per_rep
+        n_out = int(np.prod(shape))
         up = lambda a: DevBuf(self.eng, a.nbytes + 256).upload(a if a.size else np.zeros(1, a.dtype))
         bufs = [up(ident), up(carry), up(off), DevBuf(self.eng, 4 * max(1, n_out) + 256)]
         try:
-            call(bufs, off, len(covers))
+            self._call("counts", (bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data, len(covers)),
+                       (bufs[3].data_ptr(),), depth)
             out = bufs[3].download(np.uint32, n_out) if n_out else np.zeros(0, np.uint32)      # (the default stream: behind the kernel)
         finally:
             for b in bufs:
                 b.free()
-        return out
+        return out.reshape(shape)
 
     def free(self):
         for b in (self.d_idents, self.d_thr, self.d_seeds):
             b.free()
 
 
-class AfDepthTable(AfRepTable):
-    """The same table with the thresholds of the --dsAFDepth fractions (frac_threshold(f), host memory: they travel by value), and
-    the two calls of csrc/k_af_depth.inc over them."""
-
-    def __init__(self, eng, idents, thr, seeds, depth_thr):
-        super().__init__(eng, idents, thr, seeds)
-        self.depth_thr = np.ascontiguousarray(depth_thr, np.uint64)
-        self.n_fracs = len(self.depth_thr)
-
-    def _table(self):
-        t = super()._table()
-        return t[:6] + (self.depth_thr.ctypes.data, self.n_fracs) + t[6:]
-
-    def masks(self, d_run_idents, n_ids: int, d_masks, n_words: int, d_draws=None):
-        """smc_af_depth_masks: len(seeds) x n_targets x n_fracs keep masks of `n_words` words each - mask ((j x T + t) x F + f) is what
-        select_run(d_mask=...) takes.  d_draws: uint32 [len(seeds), n_ids], the depth draw of every id."""
-        _lib.check(self.eng.L.smc_af_depth_masks(self.eng.ctx, d_run_idents, int(n_ids), *self._table(), d_masks, int(n_words), d_draws,
-                                                 ctypes.c_void_p(0)), "smc_af_depth_masks")
-
-    def counts(self, covers, carries) -> np.ndarray:
-        """smc_af_depth_counts: uint32 [V, R, T, F, 2] = (N', V') of every variant, replicate and cell."""
-        return self._counts(covers, carries, self.n_targets * self.n_fracs, lambda bufs, off, n_var: _lib.check(self.eng.L.smc_af_depth_counts(
-            self.eng.ctx, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data, n_var, *self._table(), bufs[3].data_ptr(),
-            ctypes.c_void_p(0)), "smc_af_depth_counts")).reshape(len(covers), len(self.seeds), self.n_targets, self.n_fracs, 2)
+AfRepTable = AfDepthTable = AfCellTable       # (one class: what the callers wrote before there was one)
 
 
 def mask_words(n_ids: int) -> int:
@@ -1451,19 +1436,18 @@ def ds_af_replicates(path: str, fasta, variants, targets, params_list, seed: int
         raise ValueError("--dsAFReps: %d --dsAF targets, at most %d" % (T, AF_REP_MAX_TARGETS))
     seeds = dsaf.rep_seeds(seed, n_reps)
     idents, thr = dsaf.carrier_table(keep["carries"], [[row["thr"] for row in r["rows"]] for r in res])
-    table = AfRepTable(eng, idents, thr, seeds)
+    table = AfCellTable(eng, idents, thr, seeds, [frac_threshold(f) for f in depth["fracs"]] if depth is not None else None)
     F = len(depth["fracs"]) if depth is not None else 0
     cell_params = list(params_list) + (list(depth["params"]) if depth is not None else [])
-    dtable = depth_counts = None
+    depth_counts = None
     times = {"counts": 0.0, "masks": 0.0, "decode again": 0.0, "builds": 0, "batches": 0}
     rows = {}
     max_depth = eng.L.smc_build_max_depth()
     try:
         t0 = time.perf_counter()
-        counts = table.counts(keep["covers"], keep["carries"])
+        counts = table.counts(keep["covers"], keep["carries"], plain=True)
         if depth is not None:
-            dtable = AfDepthTable(eng, idents, thr, seeds, [frac_threshold(f) for f in depth["fracs"]])
-            depth_counts = dtable.counts(keep["covers"], keep["carries"])
+            depth_counts = table.counts(keep["covers"], keep["carries"])
         times["counts"] = time.perf_counter() - t0
         for run in keep["runs"]:
             if run.A is None:
@@ -1481,17 +1465,18 @@ def ds_af_replicates(path: str, fasta, variants, targets, params_list, seed: int
             n_bc = int(run.A["n_bc"])
             n_words = mask_words(n_bc)
             d_id = DevBuf(eng, 8 * max(1, n_bc) + 256).upload(np.ascontiguousarray(run.idents, np.uint64) if n_bc else np.zeros(1, np.uint64))
-            d_masks = DevBuf(eng, 4 * n_reps * T * (1 + F) * n_words + 256)
+            n_plain = n_reps * T                                       # (the targets' masks stand first in the buffer, then the cells')
+            d_masks = DevBuf(eng, 4 * (n_plain + n_reps * T * F) * n_words + 256)
             try:
                 t0 = time.perf_counter()
-                table.masks(d_id.data_ptr(), n_bc, d_masks.data_ptr(), n_words)
-                if dtable is not None:
-                    dtable.masks(d_id.data_ptr(), n_bc, d_masks.data_ptr() + 4 * n_reps * T * n_words, n_words)
-                host = d_masks.download(np.uint32, n_reps * T * (1 + F) * n_words)                        # (behind the kernels)
-                # (per cell: the replicates' masks and their indexes in the buffer - the targets' masks first, then the cells')
-                host, host_cells = host[:n_reps * T * n_words].reshape(n_reps, T, n_words), host[n_reps * T * n_words:].reshape(n_reps, T * F, n_words)
-                of_cell = [(host[:, t], [j * T + t for j in range(n_reps)]) for t in range(T)] + \
-                          [(host_cells[:, c], [n_reps * T + j * T * F + c for j in range(n_reps)]) for c in range(T * F)]
+                table.masks(d_id.data_ptr(), n_bc, d_masks.data_ptr(), n_words, plain=True)
+                if depth is not None:
+                    table.masks(d_id.data_ptr(), n_bc, d_masks.data_ptr() + 4 * n_plain * n_words, n_words)
+                host = d_masks.download(np.uint32, (n_plain + n_reps * T * F) * n_words).reshape(-1, n_words)      # (behind the kernels)
+                # (per cell: the replicates' masks and their indexes in the buffer)
+                index_of = [[j * T + t for j in range(n_reps)] for t in range(T)] + \
+                           [[n_plain + j * T * F + c for j in range(n_reps)] for c in range(T * F)]
+                of_cell = [(host[index], index) for index in index_of]
                 times["masks"] += time.perf_counter() - t0
                 per_build = int(run.A["n_slots"]) + run.nl
                 room = max(1, AF_REP_BATCH_SLOTS // max(1, per_build))
@@ -1524,8 +1509,6 @@ def ds_af_replicates(path: str, fasta, variants, targets, params_list, seed: int
             run.free()
     finally:
         table.free()
-        if dtable is not None:
-            dtable.free()
         free_af_runs(keep["runs"])
     times["stage"] = time.perf_counter() - t_start
     return dict(seeds=seeds, counts=counts, rows=rows, times=times, depth_counts=depth_counts)

@@ -188,5 +188,5 @@ def test_header_symbols_and_help():
     assert "smc_af_rep_masks" in _lib.SYMBOLS and "smc_af_rep_counts" in _lib.SYMBOLS
     L = _lib.load()
     assert L.smc_abi_version() == 11 and hasattr(L, "smc_af_rep_masks") and hasattr(L, "smc_af_rep_counts")
-    assert os.path.exists(os.path.join(ROOT, "smcounter_amd", "csrc", "k_af_reps.inc"))
+    assert os.path.exists(os.path.join(ROOT, "smcounter_amd", "csrc", "k_af_depth.inc"))
     assert "--dsAFReps" in cli.build_parser().format_help()

@@ -1,5 +1,5 @@
 """--dsAFDepth on the GPU: smc_af_depth_masks / smc_af_depth_counts against the restatement (tests/ds_af_depth_restate.py), bit for
-bit; f = 1 against smc_af_rep_masks; the device depth draw against devplanes.philox_keep_host; the command line's cells against the
+bit; f = 1 against smc_af_rep_masks and smc_af_rep_counts; the device depth draw against devplanes.philox_keep_host; the command line's cells against the
 two-step workflow they replace (tools.ds_allele_fraction, then --dsMT --dsSampler philox on its BAM), against separate runs with
 --dsSeed s_j, and its tables against what the test computes from the replicate lines."""
 import argparse
@@ -40,7 +40,8 @@ def _table(eng, covers, carries, targets, fracs, seeds):
 
 def _device(eng, run_idents, covers, carries, targets, fracs, seed, n_reps, draws=False):
     """The two calls over one run's identities -> (masks uint32 [R, T, F, n_words], counts uint32 [V, R, T, F, 2], the table's
-    identities, the depth draws, smc_af_rep_masks' masks [R, T, n_words] of the same table)."""
+    identities, the depth draws, smc_af_rep_masks' masks [R, T, n_words] and smc_af_rep_counts' counts [V, R, T, 2] of the same
+    table)."""
     tab, idents, _ = _table(eng, covers, carries, targets, fracs, dsaf.rep_seeds(seed, n_reps))
     n, cells = len(run_idents), len(targets) * len(fracs)
     n_words = devplanes.mask_words(n)
@@ -57,6 +58,7 @@ def _device(eng, run_idents, covers, carries, targets, fracs, seed, n_reps, draw
         try:
             plain_tab.masks(d_id.data_ptr(), n, d_p.data_ptr(), n_words)
             plain = d_p.download(np.uint32, n_reps * len(targets) * n_words).reshape(n_reps, len(targets), n_words)
+            plain_counts = plain_tab.counts(covers, carries)
         finally:
             plain_tab.free()
         counts = tab.counts(covers, carries)
@@ -65,14 +67,14 @@ def _device(eng, run_idents, covers, carries, targets, fracs, seed, n_reps, draw
             if b is not None:
                 b.free()
         tab.free()
-    return masks, counts, idents, u, plain
+    return masks, counts, idents, u, plain, plain_counts
 
 
 def _check(eng, run_idents, covers, carries, targets=TARGETS, fracs=FRACS, seed=SEED, n_reps=REPS):
-    """masks and counts == the restatement, bit for bit; the f = 1 masks == smc_af_rep_masks' -> (mask words compared, counters
-    compared, carriers of the table)."""
+    """masks and counts == the restatement, bit for bit; the f = 1 masks and counts == smc_af_rep_masks' and smc_af_rep_counts' ->
+    (mask words compared, counters compared, carriers of the table)."""
     keep, want = DR.restate(run_idents, covers, carries, targets, fracs, seed, n_reps)
-    masks, counts, idents, _, plain = _device(eng, run_idents, covers, carries, targets, fracs, seed, n_reps)
+    masks, counts, idents, _, plain, plain_counts = _device(eng, run_idents, covers, carries, targets, fracs, seed, n_reps)
     n_words = devplanes.mask_words(len(run_idents))
     assert masks.shape == (n_reps, len(targets), len(fracs), n_words)
     assert np.array_equal(masks, RR.pack(keep, n_words))
@@ -80,6 +82,7 @@ def _check(eng, run_idents, covers, carries, targets=TARGETS, fracs=FRACS, seed=
     ones = [k for k, f in enumerate(fracs) if f >= 1.0]
     for k in ones:
         assert np.array_equal(masks[:, :, k], plain)
+        assert plain_counts.shape == (len(covers), n_reps, len(targets), 2) and np.array_equal(counts[:, :, :, k], plain_counts)
     assert ones or fracs != FRACS
     return masks.size, counts.size, len(idents)
 

@@ -478,6 +478,19 @@ int smc_read_groups_kept_grid(smc_read_groups* g, uint64_t seed, const uint64_t*
  * max_depth > SMC_LOD_MAX_DEPTH: SMC_E_INPUT, nothing is launched. */
 #define SMC_LOD_MAX_DEPTH (1 << 24)
 int smc_lod_table(smc_ctx* ctx, int needed, int max_depth, double* roots, int32_t* iters);
+/* (ABI 11, additive: two entries more, the version number unchanged) FOR CHECKING, like smc_philox4x32_10_host: the arithmetic of
+ * the four Fisher tests of k_filter_loci on arguments of the caller's choice (the filter kernel only sees the tallies the locus
+ * kernel wrote).  Host pointers in and out, device scratch of the context, the null stream; both return with the values.
+ *   smc_fisher_tables  tables[n][4] = a b c d, rows first (scipy.stats.fisher_exact([[a, b], [c, d]])): one wavefront per table
+ *                      runs the filter kernel's own device function with the context's log-factorial table -> oddsratio[n],
+ *                      pvalue[n] (two-sided; a zero margin: NaN, 1; b * c == 0: inf).  A negative count, or a table whose counts add
+ *                      up to more than INT32_MAX (the tallies are int): SMC_E_INPUT, nothing is launched.  n == 0: nothing happens.
+ *   smc_lfact_values   out[i] = the log(v!) a Fisher test uses for v = n_values[i] >= 0: the context's table below 65536, Stirling's
+ *                      series from there on.  n_values[i] < 0: the series (the constants below 8) at ~n_values[i] whatever its size
+ *                      - what the table was filled from, so that the two can be compared at one argument.
+ * At most 2^24 tables / values per call. */
+int smc_fisher_tables(smc_ctx* ctx, const int64_t* tables, int64_t n, double* oddsratio, double* pvalue);
+int smc_lfact_values(smc_ctx* ctx, const int64_t* n_values, int64_t n, double* out);
 /* (ABI 11, additive: one entry more, the version number unchanged) --dsAF: which barcodes of a run cover / carry a listed allele.
  * The run as smc_build_planes takes it (d_aln[n_aln], the CIGAR pool, the (letter, quality) pair pool, d_loc[n_loci], start0, n_bc:
  * nothing of it is written); d_var[n_var]: the listed variants of the run, each a locus index and an allele key by the keys the

@@ -40,6 +40,9 @@ struct smc_ctx {
     // scratch of smc_allele_carriers (the counters of a call that does not ask for them), grown on demand
     void* af_scratch = nullptr;
     size_t af_bytes = 0;
+    // scratch of the checking entries smc_fisher_tables / smc_lfact_values (arguments, then results), grown on demand
+    void* chk_scratch = nullptr;
+    size_t chk_bytes = 0;
     // the segment table of a build travels from page-locked memory (a copy from pageable memory blocks the host until the stream has
     // drained): a small ring, an entry reused once the copy that read it has run (its event)
     struct SegStage { void* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
@@ -336,6 +339,7 @@ void smc_destroy(smc_ctx* c) {
     (void)hipFree(c->sel_scratch);
     (void)hipFree(c->lod_scratch);
     (void)hipFree(c->af_scratch);
+    (void)hipFree(c->chk_scratch);
     {
         std::vector<smc_ctx::VmmBlock> left;
         { std::lock_guard<std::mutex> g(c->vmm_mu); left.swap(c->vmm); }
@@ -1046,6 +1050,63 @@ int smc_lod_table(smc_ctx* ctx, int needed, int max_depth, double* roots, int32_
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(roots, d_roots, 8 * n, hipMemcpyDeviceToHost));       // (null stream: ordered behind the kernel)
     if (iters) HIPCHK(hipMemcpy(iters, d_iters, 4 * n, hipMemcpyDeviceToHost));
+    return SMC_OK;
+}
+
+// ---- checking entries: the Fisher tests' device arithmetic on arguments of the caller's choice (k_filter_loci.inc, its end)
+static int chk_scratch(smc_ctx* ctx, const char* who, size_t bytes) {
+    if (bytes <= ctx->chk_bytes) return SMC_OK;
+    (void)hipFree(ctx->chk_scratch);                      // (synchronises the device; the entries wait for their own kernels)
+    ctx->chk_scratch = nullptr; ctx->chk_bytes = 0;
+    hipError_t e = hipMalloc(&ctx->chk_scratch, bytes);
+    if (e != hipSuccess) return fail(SMC_E_HIP, std::string(who) + ": " + std::to_string(bytes) + " bytes of scratch: " + hipGetErrorString(e));
+    ctx->chk_bytes = bytes;
+    return SMC_OK;
+}
+#define SMC_CHK_MAX_N ((int64_t)1 << 24)
+int smc_fisher_tables(smc_ctx* ctx, const int64_t* tables, int64_t n, double* oddsratio, double* pvalue) {
+    if (!ctx || n < 0) return fail(SMC_E_ARG, "smc_fisher_tables: bad argument");
+    if (n == 0) return SMC_OK;
+    if (!tables || !oddsratio || !pvalue) return fail(SMC_E_ARG, "smc_fisher_tables: NULL argument");
+    if (n > SMC_CHK_MAX_N) return fail(SMC_E_ARG, "smc_fisher_tables: more than 2^24 tables in one call");
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t* T = tables + 4 * i;
+        int64_t tot = 0;
+        for (int k = 0; k < 4; ++k) {
+            if (T[k] < 0) return fail(SMC_E_INPUT, "smc_fisher_tables: table " + std::to_string(i) + " has the negative count " + std::to_string(T[k]));
+            if (T[k] > INT32_MAX || (tot += T[k]) > INT32_MAX)
+                return fail(SMC_E_INPUT, "smc_fisher_tables: the counts of table " + std::to_string(i) + " add up to more than 2^31 - 1 (the tallies are int)");
+        }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t N = (size_t)n;
+    if (int rc = chk_scratch(ctx, "smc_fisher_tables", 48 * N)) return rc;
+    long long* d_tab = (long long*)ctx->chk_scratch;
+    double* d_or = (double*)((char*)ctx->chk_scratch + 32 * N);
+    double* d_p = d_or + N;
+    HIPCHK(hipMemcpy(d_tab, tables, 32 * N, hipMemcpyHostToDevice));
+    constexpr unsigned per_block = SMC_FISHER_BLOCK / WAVE;
+    hipLaunchKernelGGL(k_fisher_tables, dim3((unsigned)((N + per_block - 1) / per_block)), dim3(SMC_FISHER_BLOCK), 0, 0, d_tab, (long long)n, ctx->lfact, d_or, d_p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(oddsratio, d_or, 8 * N, hipMemcpyDeviceToHost));      // (null stream: ordered behind the kernel)
+    HIPCHK(hipMemcpy(pvalue, d_p, 8 * N, hipMemcpyDeviceToHost));
+    return SMC_OK;
+}
+
+int smc_lfact_values(smc_ctx* ctx, const int64_t* n_values, int64_t n, double* out) {
+    if (!ctx || n < 0) return fail(SMC_E_ARG, "smc_lfact_values: bad argument");
+    if (n == 0) return SMC_OK;
+    if (!n_values || !out) return fail(SMC_E_ARG, "smc_lfact_values: NULL argument");
+    if (n > SMC_CHK_MAX_N) return fail(SMC_E_ARG, "smc_lfact_values: more than 2^24 values in one call");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t N = (size_t)n;
+    if (int rc = chk_scratch(ctx, "smc_lfact_values", 16 * N)) return rc;
+    long long* d_v = (long long*)ctx->chk_scratch;
+    double* d_out = (double*)ctx->chk_scratch + N;
+    HIPCHK(hipMemcpy(d_v, n_values, 8 * N, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_lfact_values, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, d_v, (long long)n, ctx->lfact, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, d_out, 8 * N, hipMemcpyDeviceToHost));
     return SMC_OK;
 }
 

@@ -180,3 +180,22 @@ __global__ __launch_bounds__(SMC_FLT_BLOCK) void k_filter_loci(KParams P, const 
     // filled it has finished long ago)
     if (blockIdx.x == 0 && threadIdx.x == 0) *other_count = 0u;
 }
+
+// Checking entries (smc_fisher_tables, smc_lfact_values): the device functions above on arguments a test chooses - k_filter_loci only
+// ever sees the tallies k_call_v2 wrote.  A wavefront per table, the SAME wave_fisher with the context's table; lane 0 stores.
+#define SMC_FISHER_BLOCK 256
+__global__ __launch_bounds__(SMC_FISHER_BLOCK) void k_fisher_tables(const long long* __restrict__ tables, long long n, const double* __restrict__ lft,
+                                                                    double* __restrict__ orat, double* __restrict__ pval) {
+    const long long w = (long long)blockIdx.x * (SMC_FISHER_BLOCK / WAVE) + (threadIdx.x >> 6);
+    if (w >= n) return;                                                           // (uniform over the wavefront)
+    const long long* T = tables + 4 * w;
+    double o, p;
+    wave_fisher(lft, T[0], T[1], T[2], T[3], &o, &p);
+    if ((threadIdx.x & 63) == 0) { orat[w] = o; pval[w] = p; }
+}
+// v >= 0: what a Fisher test gets for log(v!) - t_lfact; v < 0: d_lfact(~v), computed whatever the size (the table's entries against
+// the series at the same argument)
+__global__ void k_lfact_values(const long long* __restrict__ v, long long n, const double* __restrict__ lft, double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = v[i] >= 0 ? t_lfact(lft, v[i]) : d_lfact((double)~v[i]);
+}

@@ -188,6 +188,27 @@ class Engine(object):
         _lib.check(self.L.smc_lod_table(self.ctx, needed, max_depth, roots.ctypes.data, iters.ctypes.data), "smc_lod_table")
         return roots, iters
 
+    # ---- checking entries: the Fisher tests of k_filter_loci on tables of the caller's choice (smc_fisher_tables, smc_lfact_values)
+    def fisher_tables(self, tables):
+        """(oddsratio float64[n], pvalue float64[n]) of the 2 x 2 tables [[a, b], [c, d]] given as rows (a, b, c, d): the filter
+        kernel's own two-sided Fisher test, one wavefront per table.  A negative count or a total beyond 2^31 - 1: SmcError."""
+        t = np.ascontiguousarray(np.asarray(tables, np.int64).reshape(-1, 4))
+        orat, p = np.empty(len(t), np.float64), np.empty(len(t), np.float64)
+        _lib.check(self.L.smc_fisher_tables(self.ctx, t.ctypes.data, len(t), orat.ctypes.data, p.ctypes.data), "smc_fisher_tables")
+        return orat, p
+
+    def lfact_values(self, n_values, computed: bool = False):
+        """log(n!) as the Fisher tests get it (the context's table below 65536, Stirling's series beyond); `computed`: the series
+        at every n, the table left aside."""
+        v = np.ascontiguousarray(np.asarray(n_values, np.int64).ravel())
+        if (v < 0).any():
+            raise _lib.SmcError("smc_lfact_values: negative argument")
+        if computed:
+            v = ~v                                                     # (the library's code for "not from the table")
+        out = np.empty(len(v), np.float64)
+        _lib.check(self.L.smc_lfact_values(self.ctx, v.ctypes.data, len(v), out.ctypes.data), "smc_lfact_values")
+        return out
+
     # ---- resident path: the four planes + umi_start live in HBM (torch tensors), a plan is reused
     def upload(self, db: DeviceBatch):
         import torch

@@ -577,6 +577,33 @@ int smc_af_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint8_t
                         const uint32_t* cov_off_host, int32_t n_var, const uint64_t* d_car, const uint64_t* d_car_thr,
                         const uint64_t* car_host, const uint64_t* car_thr_host, int64_t n_car, int32_t n_targets,
                         const uint64_t* depth_thr, int32_t n_fracs, const uint64_t* d_seeds, int32_t n_reps, uint32_t* d_out, void* stream);
+/* (ABI 11, additive: one entry more, the version number unchanged) --spikeAF: listed SNVs planted in a run's bases, whole barcodes
+ * at a time.  The run as smc_build_planes takes it (d_aln[n_aln], the CIGAR pool, the (letter, quality) pair pool of n_pairs pairs:
+ * nothing of it is written).  d_var[n_var]: the listed variants of the run's chromosome, strictly ascending by 0-based position - ANY
+ * reference position, not only a locus of the run: an alignment that spans it is rewritten in whichever run it was decoded.
+ * d_idents[n_bc]: the identity of every run-wide barcode id (smc_bam_barcode_idents, uploaded).  d_nm / d_n_indel[n_aln]: per
+ * alignment its NM (0 when absent) and its CIGAR's inserted plus deleted length (smc_bam_run_mismatches, uploaded).
+ * Barcode b is SPIKED at variant v when word 0 of Philox4x32-10(counter = (identity lo, identity hi, 0x73704146 "spAF",
+ * (pos0 + 1) mod 2^32), key = (seed lo, seed hi)) < thr - one draw per barcode and variant.  Every alignment of a spiked barcode with
+ * pos <= pos0 < end whose allele key there is a single letter (a base, not inside a deletion, with no insertion or deletion starting
+ * behind it: the plane builder's rules) gets `alt` as that base's letter; its NM grows by 1 when the old letter was `ref`.
+ *   d_aln_out[n_aln]    the records, each with SMC_DA_MMOK recomputed as smc_bam_alignments computes it, from the new NM:
+ *                       100.0 * max(0, NM' - n_indel) / l_seq <= mismatch_thr in double, 0.0 for l_seq == 0
+ *   d_bq_out            the pair pool (2 * n_pairs bytes, copied here from d_bq) with the letters rewritten; qualities stay
+ *   d_stats[n_var][2]   uint32: records rewritten at v (one that showed `alt` already counts), records whose NM grew; zeroed here
+ * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched and nothing copied: positions not strictly ascending, a letter
+ * outside ACGT, ref equal to alt, a threshold above 2^32, more than SMC_AF_MAX_VARIANTS variants (d_var is a DEVICE array:
+ * `var_host`, the same n_var records in host memory, is what is checked). */
+typedef struct smc_spike_variant {
+    int32_t pos0;              /* 0-based reference position */
+    uint8_t ref, alt;          /* ASCII, out of A C G T */
+    uint8_t pad[2];
+    uint64_t thr;              /* floor(t * 2^32), in [0, 2^32] */
+} smc_spike_variant;
+int smc_spike_alleles(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, const uint8_t* d_bq, int64_t n_pairs,
+                      const smc_spike_variant* d_var, const smc_spike_variant* var_host, int32_t n_var, const uint64_t* d_idents,
+                      int64_t n_bc, uint64_t seed, double mismatch_thr, const int32_t* d_nm, const int32_t* d_n_indel,
+                      smc_dev_aln* d_aln_out, uint8_t* d_bq_out, uint32_t* d_stats, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

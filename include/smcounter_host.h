@@ -76,6 +76,10 @@ int smc_bam_allele_key(void* h, int64_t aln_index, int32_t qpos, int32_t indel, 
 const char* smc_bam_barcode_name(void* h, int32_t gid);
 /* FNV-1a (64 bits) of the text of every run-wide barcode id of the last smc_bam_alignments: the identities smc_philox_marks keys on. */
 int64_t smc_bam_barcode_idents(void* h, uint64_t* out, int64_t cap);
+/* NM (0 when the record has no NM tag) and the CIGAR's inserted plus deleted length of every alignment of the last
+ * smc_bam_alignments, in the order of its aln[]: the two terms of mismatchPer100b (smCounter.py:329-356), of which the packed record
+ * keeps only the SMC_DA_MMOK bit (smc_spike_alleles takes them).  Either array may be NULL.  -> the number of alignments */
+int64_t smc_bam_run_mismatches(void* h, int32_t* nm, int32_t* n_indel, int64_t cap);
 /* FNV-1a (64 bits) of the FULL query name of every run-wide read-name id (pair_gid) of the last smc_bam_alignments (its first
  * record's), and *shared = 1 when some id stands for two different names (pair_gid is keyed on the name without its last field,
  * smCounter.py:319-322): what the read-level down-sampling (--dsRpb, ds.reads.withinMT.py) keys on.  Computed on the first call after

@@ -44,6 +44,9 @@ assert DEV_ALN_DTYPE.itemsize == 36 and DEV_LOCUS_DTYPE.itemsize == 16
 # smc_af_variant (smc_allele_carriers): a listed variant of a run
 AF_VARIANT_DTYPE = np.dtype([("locus", "<u4"), ("kind", "<u4"), ("letter", "<u4"), ("len", "<u4"), ("ins_off", "<u4"), ("pad", "<u4", (3,))])
 assert AF_VARIANT_DTYPE.itemsize == 32
+# smc_spike_variant (smc_spike_alleles): a listed SNV by reference position, and its target's threshold
+SPIKE_VARIANT_DTYPE = np.dtype([("pos0", "<i4"), ("ref", "u1"), ("alt", "u1"), ("pad", "u1", (2,)), ("thr", "<u8")])
+assert SPIKE_VARIANT_DTYPE.itemsize == 16
 
 
 def c_params(p: VcParams) -> SmcParams:

@@ -615,6 +615,8 @@ def _native_lib():
         lib.smc_bam_barcode_name.restype = C.c_char_p
         lib.smc_bam_barcode_idents.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         lib.smc_bam_barcode_idents.restype = C.c_int64
+        lib.smc_bam_run_mismatches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        lib.smc_bam_run_mismatches.restype = C.c_int64
         lib.smc_bam_pair_idents.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
         lib.smc_bam_pair_idents.restype = C.c_int64
         lib.smc_bam_pair_name.argtypes = [C.c_void_p, C.c_int32]
@@ -738,6 +740,14 @@ class NativeBam(object):
         out = np.zeros(max(1, int(n_bc)), np.uint64)
         n = self._lib.smc_bam_barcode_idents(self._h, out.ctypes.data, len(out))
         return out[:min(int(n), len(out))]
+
+    def run_mismatches(self, n_aln: int):
+        """NM (0 when absent) and the CIGAR's inserted plus deleted length of every alignment of the last run, in the order of its
+        aln[] (smc_bam_run_mismatches) -> (int32 array, int32 array)."""
+        nm, n_indel = np.zeros(max(1, int(n_aln)), np.int32), np.zeros(max(1, int(n_aln)), np.int32)
+        n = self._lib.smc_bam_run_mismatches(self._h, nm.ctypes.data, n_indel.ctypes.data, len(nm))
+        n = min(int(n), len(nm))
+        return nm[:n], n_indel[:n]
 
     def pair_idents(self, n_pair: int):
         """FNV-1a (64 bits) of the full query name of every read-name id of the last run (by run-wide pair id), and whether some id

@@ -139,6 +139,21 @@ def build_parser() -> argparse.ArgumentParser:
                         ".dsAF.depth.curve.txt (per variant and depth the detection rate at every target and T95, the smallest "
                         "target found in 95 %%%% of the replicates together with every larger one).  The masks and counts of the cells "
                         "are made on the GPU; at most %d cells.  Needs --dsAF" % GRID_MAX_CELLS)
+    p.add_argument("--spikeAF", default=None,
+                   help="in-silico spike-ins: comma-separated target allele fractions t in (0, 1).  For each, the run is also called as if "
+                        "on the BAM that tools/spike_variants.py --af t --seed dsSeed writes for the SNVs of --spikeVariants: per variant "
+                        "and barcode one counter-based draw (Philox4x32-10 keyed by --dsSeed, the barcode text and the position) picks the "
+                        "barcodes that get the variant, and every read of such a barcode that shows a plain base at the position gets "
+                        "ALT there, its NM moving with it (a variant the sample carries already ends above t: reported, not corrected); "
+                        "written to <outPrefix>.spikeAF<t>.smCounter.{all,cut}.txt and .cut.vcf (with --lod: its LOD files and summary "
+                        "line), and, one line per variant and output, <outPrefix>.spikeAF.detection.txt.  The bases are rewritten on the "
+                        "GPU, in a copy of each decoded run; the BAM is decoded once after a pre-pass over the runs around the listed "
+                        "loci.  At most %d targets; not together with any --ds* down-sampling flag; needs the device plane builder; "
+                        "one process only" % SPIKE_MAX_TARGETS)
+    p.add_argument("--spikeVariants", default=None, help="the SNVs --spikeAF plants, one per line, in the format of --dsAFVariants: REF "
+                                                         "and ALT one letter each out of A, C, G, T, REF the genome's letter; one variant "
+                                                         "per position, each a locus of --bedTarget (insertions and deletions are refused)")
+    p.add_argument("--spikeMtDepth", default=None, help="comma-separated --mtDepth of each --spikeAF target; default --mtDepth")
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -154,6 +169,7 @@ def build_parser() -> argparse.ArgumentParser:
 
 REPS_MIN, REPS_MAX = 2, 1000   # (--dsAFReps: dsaf.REPS_MIN / REPS_MAX, SMC_AF_REP_MAX_REPS)
 AF_MAX_INS = 255             # (smc_allele_carriers: SMC_AF_MAX_INS letters per listed insertion)
+SPIKE_MAX_TARGETS = 32       # (--spikeAF: spike.MAX_TARGETS)
 GRID_MAX_CELLS = 32          # (a launch takes at most SMC_RG_MAX_TARGETS masks; every cell holds a batch's device arrays)
 
 
@@ -293,10 +309,10 @@ class _Output:
     its reads per barcode).  Output 0 of a run is the full-depth one; every other has a `rule`, once the rule makers below have run."""
     prefix: str
     params: VcParams
-    kind: str = "full"          # full, dsMT, dsRpb, dsGrid, dsAF or dsAFDepth
+    kind: str = "full"          # full, dsMT, dsRpb, dsGrid, dsAF, dsAFDepth or spikeAF
     frac: float = None          # (dsMT, dsGrid, dsAFDepth) the fraction of the barcodes
     target: float = None        # (dsRpb, dsGrid) the reads per barcode asked for
-    af: float = None            # (dsAF, dsAFDepth) the target allele fraction
+    af: float = None            # (dsAF, dsAFDepth, spikeAF) the target allele fraction
     af_index: int = None        # (dsAFDepth) which --dsAF target the cell belongs to
     rule: object = None         # the devplanes.DsRule that selects it; None: full depth
 
@@ -312,6 +328,7 @@ class _Plan:
     reps: int = None            # (--dsAFReps) R, and what the pre-pass kept for the replicate stage (None once that has taken it)
     keep: dict = None
     depth: dict = None          # (--dsAFDepth) "fracs", the cells' "params", and once the rules are made "rules" and "counts" [V, T, F, 2]
+    spike: dict = None          # (--spikeAF) once the rules are made: "variants", and "res", the pre-pass's numbers per target
 
     @property
     def rules(self):
@@ -341,6 +358,22 @@ def ds_af_rules(args, outs, variants, early, keep=None, depth=None):
         for v, row in zip(variants, r["rows"]):
             print(af.report_line(v, r["target"], row))
         print("--dsAF %g: seed %d, %d barcodes dropped" % (r["target"], int(args.dsSeed), len(r["dropped"])))
+    return rules, res
+
+
+def spike_rules(args, outs, variants, early):
+    """The devplanes.DsRule of every --spikeAF output (the pre-pass on the GPU: devplanes.spike_rules) and its numbers; the run log
+    gets a line per variant and target."""
+    from .tools import spike_variants as sv
+    eng = _engine_of(args, early)
+    try:
+        rules, res = devplanes.spike_rules(args.bamFile, fasta.FastaFile(args.refGenome), variants, [o.af for o in outs],
+                                           [o.params for o in outs], int(args.dsSeed), eng)
+    except (ValueError, bamio.BamError) as e:
+        raise SystemExit(str(e))
+    for r in res:
+        for v, row in zip(variants, r["rows"]):
+            print(sv.report_line(v, r["target"], row))
     return rules, res
 
 
@@ -644,17 +677,20 @@ def _main(args) -> int:
     cells = ds_grid_cells(args)
     af_targets = ds_af_targets(args)
     af_fracs, af_cells = ds_af_depth_cells(args, af_targets)
+    from . import spike as _spike
+    spike_targets = _spike.targets(args)
     at = lambda **kw: dataclasses.replace(params, **kw)
     plan = _Plan([_Output(args.outPrefix, params)] +
                  [_Output(p, at(mtDepth=d), "dsMT", frac=f) for f, d, p in fractions] +
                  [_Output(p, at(mtDepth=d, rpb=r), "dsRpb", target=r) for r, d, p in targets] +
                  [_Output(p, at(mtDepth=d, rpb=r), "dsGrid", frac=f, target=r) for f, r, d, p in cells] +
                  [_Output(p, at(mtDepth=d), "dsAF", af=t) for t, d, p in af_targets] +
-                 [_Output(p, at(mtDepth=d), "dsAFDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in af_cells],
+                 [_Output(p, at(mtDepth=d), "dsAFDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in af_cells] +
+                 [_Output(p, at(mtDepth=d), "spikeAF", af=t) for t, d, p in spike_targets],
                  reps=ds_af_reps(args, af_targets))
     if af_fracs is not None:
         plan.depth = dict(fracs=af_fracs, params=[o.params for o in plan.outputs if o.kind == "dsAFDepth"])
-    flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets), ("--dsAF", af_targets)) if on)
+    flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets), ("--dsAF", af_targets), ("--spikeAF", spike_targets)) if on)
     if flag and world > 1:
         raise SystemExit("%s runs in one process only (not under torch.distributed.run with more than one rank)" % flag)
     if getattr(args, "lodDepth", None) is not None and not getattr(args, "lod", False):
@@ -721,6 +757,14 @@ def _make_rules(args, plan, loc_list):
         if plan.depth is not None:
             put([o for o in plan.outputs if o.kind == "dsAFDepth"], plan.depth["rules"])
         plan.variants, plan.res, plan.keep = variants, res, keep
+    sp = [o for o in plan.outputs if o.kind == "spikeAF"]
+    if sp:
+        # (--spikeAF: the listed SNVs checked, then the pre-pass over the runs around them)
+        from . import spike as _spike
+        variants = _spike.variants(args, loc_list, fasta.FastaFile(args.refGenome))
+        rules, res = spike_rules(args, sp, variants, plan.early)
+        put(sp, rules)
+        plan.spike = dict(variants=variants, res=res)
 
 
 def _gather_ranks(args, params, loc_list, rank, local_rank, world):
@@ -874,6 +918,13 @@ def _run(args, plan, loc_list, t0):
         _lod.write_summary(args.outPrefix, lod_entries)
     if plan.variants is not None:
         _af_reports(args, plan, shard, loc_list, repeats)
+    if plan.spike is not None:
+        # (--spikeAF: every listed variant in the full-depth output and in every target's, on one page)
+        from . import spike as _spike
+        lods = shard.lod
+        outs = [(o.af, o.prefix, r["rows"] if r else None, lods[k]["lods"] if lods is not None else None)
+                for k, (o, r) in enumerate(zip(plan.outputs, [None] + list(plan.spike["res"])))]
+        _spike.write_detection(args.outPrefix, plan.spike["variants"], outs, {(c, "%d" % int(q)): n for n, (c, q) in enumerate(loc_list)})
     t1 = datetime.datetime.now()
     print("smCounter completed running at " + str(t1))
     print("smCounter total time: " + str(t1 - t0))

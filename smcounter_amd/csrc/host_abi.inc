@@ -1155,6 +1155,39 @@ int smc_allele_carriers(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, c
     return SMC_OK;
 }
 
+// (--spikeAF) a run's records and pair pool copied, then k_spike over the copies
+int smc_spike_alleles(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, const uint8_t* d_bq, int64_t n_pairs,
+                      const smc_spike_variant* d_var, const smc_spike_variant* var_host, int32_t n_var, const uint64_t* d_idents,
+                      int64_t n_bc, uint64_t seed, double mismatch_thr, const int32_t* d_nm, const int32_t* d_n_indel,
+                      smc_dev_aln* d_aln_out, uint8_t* d_bq_out, uint32_t* d_stats, void* stream) {
+    if (!ctx || n_aln < 0 || n_pairs < 0 || n_var < 0 || n_bc < 0) return fail(SMC_E_ARG, "smc_spike_alleles: bad argument");
+    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, "smc_spike_alleles: " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
+    if (n_var && !var_host) return fail(SMC_E_ARG, "smc_spike_alleles: NULL argument");
+    auto acgt = [](uint8_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; };
+    for (int32_t v = 0; v < n_var; ++v) {
+        const smc_spike_variant& V = var_host[v];
+        const std::string w = "smc_spike_alleles: variant " + std::to_string(v);
+        if (v && var_host[v - 1].pos0 >= V.pos0) return fail(SMC_E_INPUT, w + ": the positions are not strictly ascending");
+        if (!acgt(V.ref) || !acgt(V.alt)) return fail(SMC_E_INPUT, w + ": a letter outside ACGT");
+        if (V.ref == V.alt) return fail(SMC_E_INPUT, w + ": ref equals alt");
+        if (V.thr > (1ull << 32)) return fail(SMC_E_INPUT, w + ": a threshold above 2^32");
+    }
+    if (n_aln >= (int64_t)0xFFFFFF00 || n_bc >= (int64_t)0x7FFFFF00) return fail(SMC_E_ARG, "smc_spike_alleles: run too large");
+    if ((n_var && (!d_var || !d_stats)) || (n_aln && (!d_aln || !d_cig || !d_nm || !d_n_indel || !d_aln_out)) || (n_pairs && (!d_bq || !d_bq_out)) ||
+        (n_bc && !d_idents))
+        return fail(SMC_E_ARG, "smc_spike_alleles: NULL argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (n_pairs) HIPCHK(hipMemcpyAsync(d_bq_out, d_bq, 2 * (size_t)n_pairs, hipMemcpyDeviceToDevice, st));
+    if (n_var) hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)((2 * n_var + 255) / 256)), dim3(256), 0, st, d_stats, (uint32_t)(2 * n_var));
+    if (n_aln)
+        hipLaunchKernelGGL(k_spike, dim3((unsigned)((n_aln + SPK_BLOCK - 1) / SPK_BLOCK)), dim3(SPK_BLOCK), 0, st, d_aln, (uint32_t)n_aln, d_cig,
+                           (unsigned long long)n_pairs, d_var, (int)n_var, (const unsigned long long*)d_idents, (uint32_t)n_bc,
+                           (unsigned long long)seed, mismatch_thr, d_nm, d_n_indel, d_aln_out, d_bq_out, d_stats);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
 // (--dsAFReps, --dsAFDepth) what the four entries check of the carrier table, on its host copy, and of the fractions' thresholds
 // (host memory), which go into the kernels' argument -> `with_depth`: a fraction is below 2^32, so the depth draw decides something
 static int afd_check_table(const std::string& w, const uint64_t* d_car, const uint64_t* d_car_thr, const uint64_t* car_host,

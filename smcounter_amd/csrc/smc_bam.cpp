@@ -1686,6 +1686,20 @@ int64_t smc_bam_barcode_idents(void* h, uint64_t* out, int64_t cap) {
     return n;
 }
 
+// NM (0 when the record has no NM tag) and the CIGAR's inserted plus deleted length of every alignment of the last smc_bam_alignments,
+// in the order of its aln[] - the two terms of mismatchPer100b (smCounter.py:329-356) that the packed record only keeps as the
+// SMC_DA_MMOK bit; --spikeAF moves NM with the bases it rewrites.  -> the number of alignments
+int64_t smc_bam_run_mismatches(void* h, int32_t* nm, int32_t* n_indel, int64_t cap) {
+    Bam& b = *(Bam*)h;
+    const int64_t n = (int64_t)b.d_reads.size();
+    for (int64_t i = 0; i < n && i < cap; ++i) {
+        const Aln& a = b.d_reads[(size_t)i];
+        if (nm) nm[i] = (int32_t)a.nm;
+        if (n_indel) n_indel[i] = (int32_t)a.n_ind;
+    }
+    return n;
+}
+
 // The full query names behind the run-wide read-name ids of the last smc_bam_alignments (for the reference's read-level down-sampling,
 // ds.reads.withinMT.py:37-44, which keys on the whole name).  A read-name id is keyed on (barcode, read id) and the read id drops the
 // name's last field (smCounter.py:319-322): one id can stand for two different names.  Nothing of this is computed while decoding - the

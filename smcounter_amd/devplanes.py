@@ -366,7 +366,7 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
     L = eng.L
     nl = A["nl"]
     res = []
-    idents = names = p_idents = p_names = None
+    idents = names = p_idents = p_names = mism = None
     d_masks = {}                     # (philox read rules) (id(table), grid) -> (device masks of those rules, words per mask, id(rule) -> index)
     d_cells = None                   # (--dsAFDepth) (device masks of every cell of this run, words per mask)
     try:
@@ -374,7 +374,19 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
             if not nl:
                 res.append((0, 0, np.zeros(0, LOCUS_DTYPE), []))
                 continue
-            if rule.level == "read":
+            spiked = None
+            if rule.spike is not None:
+                # (--spikeAF: no selection - the run's records and bases copied and the listed SNVs written into the copy; a run none
+                # of whose records spans a listed position is built from the run's own arrays)
+                var = rule.spike.run_variants(chrom, A, rule.af)
+                if len(var):
+                    if idents is None:
+                        idents = bam.barcode_idents(A["n_bc"])
+                    if mism is None:
+                        mism = bam.run_mismatches(len(A["aln"]))
+                    spiked, _ = spike_run(eng, up, A, var, idents, rule.seed, rule.params.mismatchThr, mism[0], mism[1])
+                sel, counts, d_orig = spiked or up, A, None
+            elif rule.level == "read":
                 # (--dsRpb: the kept read names, by read-name id - an id must stand for one full name, or the rule cannot be applied)
                 if p_idents is None:
                     p_idents, shared = bam.pair_idents(A["n_pair"])
@@ -437,6 +449,10 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
             def allele_key(ai, qpos, indel, orig_index=orig_index):
                 # (the builder's alignment index counts the KEPT alignments: the decoder's records are those of the full run)
                 return bam.allele_key(int(orig_index()[int(ai)]), qpos, indel)
+            if d_orig is None:
+                # (--spikeAF: every alignment is there; a key beyond the six fixed ones is an insertion's, a deletion's or an odd letter's,
+                # and its site is a base the rewrite leaves alone or turns into a fixed key - the decoder's texts hold)
+                allele_key = bam.allele_key
             bc_name, bc_idents = bam.barcode_name, bam.barcode_idents
             if rule.level == "read":
                 # (the read level renumbers the kept barcodes by first kept appearance: the texts the cap samplers need are the decoder's,
@@ -452,8 +468,12 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
             done = build_run(counts, L, eng, abi.c_params(rule.params), rule.params, chrom, lo, fasta, run_ref, [w] + d.planes, d.uaux,
                              d.slots, d.slots + n_loc, cap, max_depth, allele_key, bc_name, sampler=sampler, sampler_seed=sampler_seed,
                              barcode_idents=bc_idents, uploaded=sel)
-            sel.free(shared=False)
-            d_orig.free()
+            if d_orig is None:
+                if spiked is not None:
+                    spiked.aln.free(); spiked.bq.free()
+            else:
+                sel.free(shared=False)
+                d_orig.free()
             if done is None:
                 raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "%s: the device builder does not take it" % rule.label, rule.flag))
             if done == NARROW:
@@ -702,9 +722,14 @@ class DsRule:
     # cells' AfCellTable in HBM (one for all cells of the run), `cell` this one's index in its masks (t x F + f)
     depth: object = None
     cell: int = None
+    # (--spikeAF) level "barcode", nothing dropped: `af` the target allele fraction, `spike` the SpikeSet whose listed SNVs are written
+    # into a copy of every run whose records span one (spike_run), at the threshold of `af`
+    spike: object = None
 
     @property
     def flag(self) -> str:
+        if self.spike is not None:
+            return "--spikeAF"
         if self.depth is not None:
             return "--dsAFDepth"
         if self.af is not None:
@@ -717,6 +742,8 @@ class DsRule:
 
     @property
     def label(self) -> str:
+        if self.spike is not None:
+            return "spiked allele fraction %g" % self.af
         if self.depth is not None:
             return "allele fraction %g x fraction %g" % (self.af, self.frac)
         if self.af is not None:
@@ -1248,6 +1275,132 @@ def ds_af_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
             table.free()
             raise
     return rules, res
+
+
+# ---- in-silico spike-ins (--spikeAF): tools.spike_variants' rewrite of whole barcodes' bases, on the run's arrays in HBM
+SPIKE_DOMAIN = 0x73704146      # counter word 2 of the draw ("spAF": tools.spike_variants.draw, k_spike.inc: SPK_DOMAIN)
+SPIKE_MAX_TARGETS = 32
+
+
+class SpikeSet(object):
+    """The listed SNVs of --spikeAF by chromosome, ascending by position, as smc_spike_alleles takes them (without thresholds)."""
+
+    def __init__(self, variants):
+        self.variants = list(variants)
+        self.by_chrom = {}
+        for c in sorted({v.chrom for v in self.variants}):
+            order = sorted((k for k, v in enumerate(self.variants) if v.chrom == c), key=lambda k: self.variants[k].pos)
+            var = np.zeros(len(order), abi.SPIKE_VARIANT_DTYPE)
+            for j, k in enumerate(order):
+                v = self.variants[k]
+                var[j]["pos0"], var[j]["ref"], var[j]["alt"] = v.pos - 1, ord(v.ref), ord(v.alt)
+            self.by_chrom[c] = (var, order)
+
+    def chrom_variants(self, chrom: str, t: float):
+        """-> (the chromosome's records at the threshold of target t, the index of each in the list given)."""
+        from .tools import spike_variants as sv
+        var, order = self.by_chrom.get(chrom, (np.zeros(0, abi.SPIKE_VARIANT_DTYPE), []))
+        var = var.copy()
+        var["thr"] = sv.threshold(t)
+        return var, order
+
+    def run_variants(self, chrom: str, A, t: float):
+        """The chromosome's records when an alignment of run `A` may span one of them (a position between the run's smallest start and
+        its largest end), else none: that run is built as it is."""
+        var, _ = self.chrom_variants(chrom, t)
+        if not len(var) or not len(A["aln"]):
+            return var[:0]
+        lo, hi = int(A["aln"]["pos"].min()), int(A["aln"]["end"].max())
+        return var if bool(((var["pos0"] >= lo) & (var["pos0"] < hi)).any()) else var[:0]
+
+
+def spike_run(eng, up: RunOnDevice, A, var: np.ndarray, idents, seed: int, mismatch_thr: float, nm, n_indel):
+    """smc_spike_alleles over the run `up` (A: its host arrays) -> (RunOnDevice whose aln and bq are the spiked copies - cig, loc and
+    ref are the run's own: free the two copies only -, uint32 [n_var, 2]: records rewritten / NM increments per variant)."""
+    from .engine import DevBuf
+    n, n_pairs, n_var, n_bc = up.n_aln, len(A["bq"]) // 2, len(var), int(A["n_bc"])
+    var = np.ascontiguousarray(var, abi.SPIKE_VARIANT_DTYPE)
+    up8 = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
+    idents = np.ascontiguousarray(idents, np.uint64)[:n_bc]
+    tmp = [up8(var), up8(idents), up8(np.ascontiguousarray(nm, np.int32)), up8(np.ascontiguousarray(n_indel, np.int32)),
+           DevBuf(eng, 8 * max(1, n_var) + 256)]
+    d_aln, d_bq = DevBuf(eng, 36 * max(1, n) + 256), DevBuf(eng, 2 * max(1, n_pairs) + 256)
+    try:
+        if len(nm) < n or len(n_indel) < n:
+            raise ValueError("spike_run: %d alignments, NM of %d" % (n, len(nm)))
+        _lib.check(eng.L.smc_spike_alleles(eng.ctx, up.aln.data_ptr(), n, up.cig.data_ptr(), up.bq.data_ptr(), n_pairs, tmp[0].data_ptr(),
+                                           var.ctypes.data, n_var, tmp[1].data_ptr(), len(idents), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                           float(mismatch_thr), tmp[2].data_ptr(), tmp[3].data_ptr(), d_aln.data_ptr(), d_bq.data_ptr(),
+                                           tmp[4].data_ptr(), ctypes.c_void_p(0)), "smc_spike_alleles")
+        stats = tmp[4].download(np.uint32, 2 * n_var).reshape(n_var, 2) if n_var else np.zeros((0, 2), np.uint32)   # (behind the kernel)
+    except BaseException:
+        d_aln.free(); d_bq.free()
+        raise
+    finally:
+        for b in tmp:
+            b.free()
+    return RunOnDevice(d_aln, up.cig, d_bq, up.loc, up.ref, n, up.loc_host), stats
+
+
+def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng, nthreads: int = 0, max_reads: int = 128_000_000):
+    """DsRules of --spikeAF, one per target, and the pre-pass: only the runs around the listed loci are decoded (as ds_af_sets groups
+    them); smc_allele_carriers gives N and V0 of every variant, then per target smc_spike_alleles writes the spiked copy and
+    smc_allele_carriers on it gives V1.  The kernel's statistics are checked against the host's restatement of the draws: the records
+    rewritten at v are the reads with v's key of the spiked covering barcodes in the spiked copy, and no other barcode's counters move.
+    -> (rules, per target dict(target, rows: per variant dict(N, V0, S, READS, V1))).  ValueError: two barcode texts of the file share
+    an identity."""
+    from .tools import ds_allele_fraction as af
+    from .tools import spike_variants as sv
+    af.unique_idents(bamio.placed_barcodes(path), path)
+    nthreads = nthreads or bamio.host_threads()
+    spikes = SpikeSet(variants)
+    P = params_list[0]
+    rows = [[None] * len(variants) for _ in targets]
+    order = sorted(range(len(variants)), key=lambda k: (variants[k].chrom, variants[k].pos))
+    bam = bamio.NativeBam(path)
+    try:
+        i = 0
+        while i < len(order):
+            v0 = variants[order[i]]
+            j = i
+            while j + 1 < len(order) and variants[order[j + 1]].chrom == v0.chrom and variants[order[j + 1]].pos - v0.pos < AF_RUN_LOCI:
+                j += 1
+            lo, hi = v0.pos - 1, variants[order[j]].pos
+            A = bam.alignments_run(v0.chrom, lo, hi, max_reads, P, nthreads)
+            nl = int(A["nl"])
+            if nl < 1:
+                raise bamio.BamError("--spikeAF: the run %s:%d-%d of the pre-pass could not be decoded" % (v0.chrom, lo + 1, hi))
+            group = [k for k in order[i:j + 1] if variants[k].pos - 1 - lo < nl]
+            var, ins = af_run_variants([variants[k] for k in group], v0.chrom, lo, fasta)
+            idents = bam.barcode_idents(A["n_bc"])
+            nm, n_indel = bam.run_mismatches(len(A["aln"]))
+            up = upload_run(eng, A, fasta.fetch(v0.chrom, lo, lo + nl).upper())
+            try:
+                cov, car, _ = allele_carriers_run(eng, up, A, lo, var, ins)
+                for t, target in enumerate(targets):
+                    svar, sorder = spikes.chrom_variants(v0.chrom, target)
+                    spiked, stats = spike_run(eng, up, A, svar, idents, seed, P.mismatchThr, nm, n_indel)
+                    try:
+                        cov1, car1, cnt1 = allele_carriers_run(eng, spiked, A, lo, var, ins, counts=True)
+                    finally:
+                        spiked.aln.free(); spiked.bq.free()
+                    for r, k in enumerate(group):
+                        v = variants[k]
+                        hit = sv.draw(idents, seed, v.pos) < np.uint64(sv.threshold(target))
+                        reads = int(stats[sorder.index(k), 0])
+                        if not np.array_equal(cov1[r], cov[r]) or reads != int(cnt1[r, hit[:cnt1.shape[1]], 1].sum()) or \
+                                bool((car1[r] != car[r])[~hit[:car.shape[1]]].any()):
+                            raise RuntimeError("--spikeAF %g: the kernel's statistics at %s:%d (%d records rewritten) do not agree with the "
+                                               "host's restatement of the draws" % (target, v.chrom, v.pos, reads))
+                        rows[t][k] = dict(N=int(cov[r].sum()), V0=int(car[r].sum()), S=int((hit[:cov.shape[1]] & cov[r]).sum()), READS=reads,
+                                          V1=int(car1[r].sum()))
+            finally:
+                up.free()
+            i += len(group)
+    finally:
+        bam.close()
+    rules = [DsRule(1.0, Pt, seed=int(seed), af=float(t), spike=spikes) for t, Pt in zip(targets, params_list)]
+    return rules, [dict(target=t, rows=r) for t, r in zip(targets, rows)]
 
 
 # ---- replicate dilutions (--dsAFReps): R seeds, the masks and the achieved counts on the device, only the listed runs called

@@ -604,6 +604,39 @@ int smc_spike_alleles(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, con
                       const smc_spike_variant* d_var, const smc_spike_variant* var_host, int32_t n_var, const uint64_t* d_idents,
                       int64_t n_bc, uint64_t seed, double mismatch_thr, const int32_t* d_nm, const int32_t* d_n_indel,
                       smc_dev_aln* d_aln_out, uint8_t* d_bq_out, uint32_t* d_stats, void* stream);
+/* (ABI 11, additive: two entries more, the version number unchanged) --spikeReps: R replicates of the --spikeAF spike-in, replicate
+ * j with the seed s_j; the run, the variants and the rewrite rule are smc_spike_alleles'.
+ *   smc_spike_alleles_reps   n_copies spiked copies of one run from one call.  `seeds` / `thr`: HOST memory, n_copies words each - copy
+ *            c is drawn with seeds[c] and EVERY variant at the threshold thr[c] (in [0, 2^32]; the variants' own `thr` field is not
+ *            read).  Copy c lies at d_aln_out + c * aln_stride (n_aln records), d_bq_out + c * bq_stride (2 * n_pairs bytes) and
+ *            d_stats[c][n_var][2], and is byte for byte what smc_spike_alleles writes with seeds[c] and every thr = thr[c]; the
+ *            bytes between the end of a copy and the next stride are not written, the run's own arrays are only read.  The strides
+ *            are BYTES: aln_stride a multiple of 4 and at least n_aln * sizeof(smc_dev_aln), bq_stride a multiple of 16 and at least
+ *            2 * n_pairs; d_bq and d_bq_out 16-byte aligned (the pool travels in 16-byte chunks: read once, stored to every copy,
+ *            in a launch of its own; the rewrite - a lane per alignment, a row of the grid per copy - follows on the same stream).
+ *   smc_spike_rep_counts     what every replicate achieves, with no spiked copy at all.  The covering barcodes of all n_var listed
+ *            variants stand one behind the other (variant v's at [cov_off[v], cov_off[v + 1])): d_cov_ident their identities,
+ *            d_cov_cnt[e][3] uint32 per barcode its pileup reads at the variant's position, those that show ALT before spiking
+ *            and those whose allele key there is a single letter - what the rewrite can touch (smc_allele_carriers' counters on
+ *            the run give the first two, its `alt` counter on a copy spiked at threshold 2^32 the third).  d_pos1[n_var]: the
+ *            variants' 1-based positions (counter word 3 of the draw).  d_seeds[n_reps] in device memory; `thr`: HOST memory,
+ *            n_targets words in [0, 2^32].  With hit = u_v(b; seeds[j]) < thr[t], u_v smc_spike_alleles' draw:
+ *            d_out[v][j][t][3] uint32 = (S: covering b with hit, READS: the sum of single[b] over them, V1: the b with
+ *            2 * (hit ? single[b] : alt0[b]) > reads[b]).  One draw per (b, v, j) serves every target.  d_out is zeroed by the call.
+ * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched and nothing copied: what smc_spike_alleles refuses (but for the
+ * variants' thresholds), n_copies below 1 or above SMC_SPIKE_MAX_COPIES, a threshold above 2^32, a stride smaller than a copy,
+ * n_copies * n_var * 2 (or n_var * n_reps * n_targets * 3) of 2^32 - 256 words or more, n_targets above
+ * SMC_SPIKE_REP_MAX_TARGETS, n_reps above SMC_AF_REP_MAX_REPS, offsets that decrease. */
+#define SMC_SPIKE_MAX_COPIES 64        /* (the copies' seeds and thresholds travel in the kernel's argument block) */
+#define SMC_SPIKE_REP_MAX_TARGETS 32   /* (= spike targets of one run) */
+int smc_spike_alleles_reps(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, const uint8_t* d_bq, int64_t n_pairs,
+                           const smc_spike_variant* d_var, const smc_spike_variant* var_host, int32_t n_var, const uint64_t* d_idents,
+                           int64_t n_bc, const uint64_t* seeds, const uint64_t* thr, int32_t n_copies, double mismatch_thr,
+                           const int32_t* d_nm, const int32_t* d_n_indel, uint8_t* d_aln_out, int64_t aln_stride, uint8_t* d_bq_out,
+                           int64_t bq_stride, uint32_t* d_stats, void* stream);
+int smc_spike_rep_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_cnt, const uint32_t* d_cov_off,
+                         const uint32_t* cov_off_host, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
+                         const uint64_t* thr, int32_t n_targets, uint32_t* d_out, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

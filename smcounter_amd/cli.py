@@ -154,6 +154,17 @@ def build_parser() -> argparse.ArgumentParser:
                                                          "and ALT one letter each out of A, C, G, T, REF the genome's letter; one variant "
                                                          "per position, each a locus of --bedTarget (insertions and deletions are refused)")
     p.add_argument("--spikeMtDepth", default=None, help="comma-separated --mtDepth of each --spikeAF target; default --mtDepth")
+    p.add_argument("--spikeReps", type=int, default=None,
+                   help="replicate spike-ins: R in %d .. %d.  Replicate j = 0 .. R - 1 is the spike-in of --spikeAF with seed (dsSeed + j) "
+                        "mod 2^64 and everything else unchanged (replicate 0 is the run's own .spikeAF<t> output at the listed loci).  "
+                        "What every replicate achieves (S, READS, V1) is counted on the GPU from the pre-pass's barcodes in one call, and "
+                        "only the runs around the listed loci are spiked and called again, several replicates per call.  Every other "
+                        "file stays as it is; added: <outPrefix>.spikeAF.replicates.txt, one line per listed variant, target and "
+                        "replicate (the line that variant has in .spikeAF.detection.txt of a run with --dsSeed of that replicate, with "
+                        "REP and SEED), <outPrefix>.spikeAF.sensitivity.txt, one line per variant and target: replicates called, the "
+                        "detection rate and its Wilson score interval (95 %%%%), the achieved fractions, and with --lod the locus's "
+                        "LOD, and <outPrefix>.spikeAF.curve.txt, one line per variant: the rate at every target and T95, the smallest "
+                        "target found in 95 %%%% of the replicates together with every larger one.  Needs --spikeAF" % (REPS_MIN, REPS_MAX))
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -329,6 +340,7 @@ class _Plan:
     keep: dict = None
     depth: dict = None          # (--dsAFDepth) "fracs", the cells' "params", and once the rules are made "rules" and "counts" [V, T, F, 2]
     spike: dict = None          # (--spikeAF) once the rules are made: "variants", and "res", the pre-pass's numbers per target
+    spike_reps: int = None      # (--spikeReps) R; plan.spike then holds "keep", what the pre-pass kept (None once the stage has taken it)
 
     @property
     def rules(self):
@@ -361,14 +373,14 @@ def ds_af_rules(args, outs, variants, early, keep=None, depth=None):
     return rules, res
 
 
-def spike_rules(args, outs, variants, early):
+def spike_rules(args, outs, variants, early, keep=None):
     """The devplanes.DsRule of every --spikeAF output (the pre-pass on the GPU: devplanes.spike_rules) and its numbers; the run log
-    gets a line per variant and target."""
+    gets a line per variant and target.  `keep` (--spikeReps): a dict for what the replicate stage starts from."""
     from .tools import spike_variants as sv
     eng = _engine_of(args, early)
     try:
         rules, res = devplanes.spike_rules(args.bamFile, fasta.FastaFile(args.refGenome), variants, [o.af for o in outs],
-                                           [o.params for o in outs], int(args.dsSeed), eng)
+                                           [o.params for o in outs], int(args.dsSeed), eng, **({"keep": keep} if keep is not None else {}))
     except (ValueError, bamio.BamError) as e:
         raise SystemExit(str(e))
     for r in res:
@@ -475,6 +487,7 @@ class _Shard:
     ds: tuple = ()              # the rows of every further output, in the plan's order
     lod: list = None            # (--lod) per output what lod.run_lods made
     af_reps: dict = None        # (--dsAFReps) what devplanes.ds_af_replicates made
+    spike_reps: dict = None     # (--spikeReps) what devplanes.spike_replicates made
 
 
 def call_shard(args, params: VcParams, loci, device: int, early=None, plan=None):
@@ -530,6 +543,8 @@ def call_shard(args, params: VcParams, loci, device: int, early=None, plan=None)
     shard = _Shard(rows[0].done(), [r.done() for r in rows[1:]])
     if plan is not None and plan.keep is not None:
         shard.af_reps = _ds_af_replicates(args, plan, ref, eng, loci, shard.ds)
+    if plan is not None and plan.spike is not None and plan.spike.get("keep") is not None:
+        shard.spike_reps = _spike_replicates(args, plan, ref, eng, loci, shard.ds)
     if lod_cols is not None:
         shard.lod = _lod.run_lods(eng, [o.params for o in outputs], lod_cols, args.lodDepth or "UMT")
     _release_engine(eng, keep=resident)
@@ -552,6 +567,23 @@ def _ds_af_replicates(args, plan, ref, eng, loci, ds_rows):
         v = variants[k]
         if j == 0 and line != ds_rows[t][index[(v.chrom, v.pos)]]:
             raise RuntimeError("--dsAFReps: replicate 0 of %s:%d in %s is not the row of the run's own output:\n%s\n%s" %
+                               (v.chrom, v.pos, outs[t].prefix, line, ds_rows[t][index[(v.chrom, v.pos)]]))
+    return out
+
+
+def _spike_replicates(args, plan, ref, eng, loci, ds_rows):
+    """--spikeReps after the run's batches: devplanes.spike_replicates over the runs the pre-pass kept, and the check that ties it to
+    the run's own outputs - replicate 0 has the seed of the run, so its row at every listed locus must be the .spikeAF<t> output's."""
+    variants, outs = plan.spike["variants"], plan.outputs[1:]
+    keep, plan.spike["keep"] = plan.spike["keep"], None      # (the stage frees the kept runs itself, whatever happens in it)
+    out = devplanes.spike_replicates(args.bamFile, ref, variants, [o.af for o in outs], [o.params for o in outs], int(args.dsSeed),
+                                     plan.spike_reps, eng, keep, sampler=getattr(args, "sampler", "reference"),
+                                     sampler_seed=getattr(args, "samplerSeed", 0))
+    index = {(c, int(p)): n for n, (c, p) in enumerate(loci)}
+    for (k, t, j), line in out["rows"].items():
+        v = variants[k]
+        if j == 0 and line != ds_rows[t][index[(v.chrom, v.pos)]]:
+            raise RuntimeError("--spikeReps: replicate 0 of %s:%d in %s is not the row of the run's own output:\n%s\n%s" %
                                (v.chrom, v.pos, outs[t].prefix, line, ds_rows[t][index[(v.chrom, v.pos)]]))
     return out
 
@@ -687,7 +719,7 @@ def _main(args) -> int:
                  [_Output(p, at(mtDepth=d), "dsAF", af=t) for t, d, p in af_targets] +
                  [_Output(p, at(mtDepth=d), "dsAFDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in af_cells] +
                  [_Output(p, at(mtDepth=d), "spikeAF", af=t) for t, d, p in spike_targets],
-                 reps=ds_af_reps(args, af_targets))
+                 reps=ds_af_reps(args, af_targets), spike_reps=_spike.reps(args, spike_targets))
     if af_fracs is not None:
         plan.depth = dict(fracs=af_fracs, params=[o.params for o in plan.outputs if o.kind == "dsAFDepth"])
     flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets), ("--dsAF", af_targets), ("--spikeAF", spike_targets)) if on)
@@ -729,6 +761,8 @@ def _main(args) -> int:
         devplanes.close_rules(plan.rules)     # (--dsRpbSampler philox: the file-wide table in HBM, whatever happened)
         if plan.keep is not None:             # (--dsAFReps: the pre-pass's runs, when the run ended before the replicate stage)
             devplanes.free_af_runs(plan.keep.get("runs"))
+        if plan.spike is not None and plan.spike.get("keep") is not None:     # (--spikeReps: the same)
+            devplanes.free_af_runs(plan.spike["keep"].get("runs"))
 
 
 def _make_rules(args, plan, loc_list):
@@ -762,9 +796,10 @@ def _make_rules(args, plan, loc_list):
         # (--spikeAF: the listed SNVs checked, then the pre-pass over the runs around them)
         from . import spike as _spike
         variants = _spike.variants(args, loc_list, fasta.FastaFile(args.refGenome))
-        rules, res = spike_rules(args, sp, variants, plan.early)
+        keep = {} if plan.spike_reps is not None else None
+        rules, res = spike_rules(args, sp, variants, plan.early, keep)
         put(sp, rules)
-        plan.spike = dict(variants=variants, res=res)
+        plan.spike = dict(variants=variants, res=res, keep=keep)
 
 
 def _gather_ranks(args, params, loc_list, rank, local_rank, world):
@@ -885,6 +920,32 @@ def _af_reports(args, plan, shard, loc_list, repeats):
           (tm["stage"], plan.reps, over, tm["builds"], tm["batches"], tm["counts"], tm["masks"]))
 
 
+def _spike_reports(args, plan, shard, loc_index, repeats):
+    """--spikeReps: every replicate's row as its own run would print and cut it, then the rates and the curve."""
+    from . import dsaf, spike as _spike
+    variants, res, outs, reps, lods = plan.spike["variants"], plan.spike["res"], plan.outputs[1:], shard.spike_reps, shard.lod
+    targets, R = [o.af for o in outs], plan.spike_reps
+    entries = {}
+    for i, v in enumerate(variants):
+        for t, o in enumerate(outs):
+            thr_t = writers.pi_threshold(o.params.mtDepth, args.threshold)
+            base = res[t]["rows"][i]
+            per = []
+            for j in range(R):
+                row, cut = dsaf.replicate_entry(reps["rows"].get((i, t, j)), thr_t, *repeats)
+                s, reads, v1 = (int(x) for x in reps["counts"][i, j, t])
+                per.append((dict(N=base["N"], V0=base["V0"], S=s, READS=reads, V1=v1), row, cut))
+            entries[(i, t)] = per
+            print("--spikeReps: %s:%d %s>%s at %g: called %d of %d" % (v.chrom, v.pos, v.ref, v.alt, o.af, _spike._called(v, per), R))
+    _spike.write_replicates(args.outPrefix, variants, targets, reps["seeds"], entries)
+    lod_vt = None if lods is None else [[float(l["lods"][loc_index[(v.chrom, "%d" % v.pos)]]) for v in variants] for l in lods[1:1 + len(outs)]]
+    _spike.write_sensitivity(args.outPrefix, variants, targets, entries, lod_vt)
+    _spike.write_curve(args.outPrefix, variants, targets, entries, lod_vt)
+    tm = reps["times"]
+    print("--spikeReps: replicate stage %.3f s (%d replicates x %d targets: counts call %.4f s, %d rewrite calls, %d builds in %d batches, "
+          "%.3f s)" % (tm["stage"], R, len(outs), tm["counts"], tm["rewrites"], tm["builds"], tm["batches"], tm["calls"]))
+
+
 def _run(args, plan, loc_list, t0):
     params = plan.outputs[0].params
     rank, local_rank, world = smcdist.init_from_env()
@@ -924,7 +985,10 @@ def _run(args, plan, loc_list, t0):
         lods = shard.lod
         outs = [(o.af, o.prefix, r["rows"] if r else None, lods[k]["lods"] if lods is not None else None)
                 for k, (o, r) in enumerate(zip(plan.outputs, [None] + list(plan.spike["res"])))]
-        _spike.write_detection(args.outPrefix, plan.spike["variants"], outs, {(c, "%d" % int(q)): n for n, (c, q) in enumerate(loc_list)})
+        loc_index = {(c, "%d" % int(q)): n for n, (c, q) in enumerate(loc_list)}
+        _spike.write_detection(args.outPrefix, plan.spike["variants"], outs, loc_index)
+        if shard.spike_reps is not None:
+            _spike_reports(args, plan, shard, loc_index, repeats)
     t1 = datetime.datetime.now()
     print("smCounter completed running at " + str(t1))
     print("smCounter total time: " + str(t1 - t0))

@@ -1155,27 +1155,38 @@ int smc_allele_carriers(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, c
     return SMC_OK;
 }
 
+// (--spikeAF, --spikeReps) what both rewrite entries check of the run and the listed variants, the variants on their host copy
+// (`own_thr`: the variants' own thresholds count - smc_spike_alleles_reps takes one per copy instead)
+static int spk_check(const std::string& who, smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, const uint8_t* d_bq,
+                     int64_t n_pairs, const smc_spike_variant* d_var, const smc_spike_variant* var_host, int32_t n_var, const uint64_t* d_idents,
+                     int64_t n_bc, const int32_t* d_nm, const int32_t* d_n_indel, const void* d_aln_out, const void* d_bq_out,
+                     const uint32_t* d_stats, bool own_thr) {
+    if (!ctx || n_aln < 0 || n_pairs < 0 || n_var < 0 || n_bc < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
+    if (n_var && !var_host) return fail(SMC_E_ARG, who + ": NULL argument");
+    auto acgt = [](uint8_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; };
+    for (int32_t v = 0; v < n_var; ++v) {
+        const smc_spike_variant& V = var_host[v];
+        const std::string w = who + ": variant " + std::to_string(v);
+        if (v && var_host[v - 1].pos0 >= V.pos0) return fail(SMC_E_INPUT, w + ": the positions are not strictly ascending");
+        if (!acgt(V.ref) || !acgt(V.alt)) return fail(SMC_E_INPUT, w + ": a letter outside ACGT");
+        if (V.ref == V.alt) return fail(SMC_E_INPUT, w + ": ref equals alt");
+        if (own_thr && V.thr > (1ull << 32)) return fail(SMC_E_INPUT, w + ": a threshold above 2^32");
+    }
+    if (n_aln >= (int64_t)0xFFFFFF00 || n_bc >= (int64_t)0x7FFFFF00) return fail(SMC_E_ARG, who + ": run too large");
+    if ((n_var && (!d_var || !d_stats)) || (n_aln && (!d_aln || !d_cig || !d_nm || !d_n_indel || !d_aln_out)) || (n_pairs && (!d_bq || !d_bq_out)) ||
+        (n_bc && !d_idents))
+        return fail(SMC_E_ARG, who + ": NULL argument");
+    return SMC_OK;
+}
+
 // (--spikeAF) a run's records and pair pool copied, then k_spike over the copies
 int smc_spike_alleles(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, const uint8_t* d_bq, int64_t n_pairs,
                       const smc_spike_variant* d_var, const smc_spike_variant* var_host, int32_t n_var, const uint64_t* d_idents,
                       int64_t n_bc, uint64_t seed, double mismatch_thr, const int32_t* d_nm, const int32_t* d_n_indel,
                       smc_dev_aln* d_aln_out, uint8_t* d_bq_out, uint32_t* d_stats, void* stream) {
-    if (!ctx || n_aln < 0 || n_pairs < 0 || n_var < 0 || n_bc < 0) return fail(SMC_E_ARG, "smc_spike_alleles: bad argument");
-    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, "smc_spike_alleles: " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
-    if (n_var && !var_host) return fail(SMC_E_ARG, "smc_spike_alleles: NULL argument");
-    auto acgt = [](uint8_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; };
-    for (int32_t v = 0; v < n_var; ++v) {
-        const smc_spike_variant& V = var_host[v];
-        const std::string w = "smc_spike_alleles: variant " + std::to_string(v);
-        if (v && var_host[v - 1].pos0 >= V.pos0) return fail(SMC_E_INPUT, w + ": the positions are not strictly ascending");
-        if (!acgt(V.ref) || !acgt(V.alt)) return fail(SMC_E_INPUT, w + ": a letter outside ACGT");
-        if (V.ref == V.alt) return fail(SMC_E_INPUT, w + ": ref equals alt");
-        if (V.thr > (1ull << 32)) return fail(SMC_E_INPUT, w + ": a threshold above 2^32");
-    }
-    if (n_aln >= (int64_t)0xFFFFFF00 || n_bc >= (int64_t)0x7FFFFF00) return fail(SMC_E_ARG, "smc_spike_alleles: run too large");
-    if ((n_var && (!d_var || !d_stats)) || (n_aln && (!d_aln || !d_cig || !d_nm || !d_n_indel || !d_aln_out)) || (n_pairs && (!d_bq || !d_bq_out)) ||
-        (n_bc && !d_idents))
-        return fail(SMC_E_ARG, "smc_spike_alleles: NULL argument");
+    if (int rc = spk_check("smc_spike_alleles", ctx, d_aln, n_aln, d_cig, d_bq, n_pairs, d_var, var_host, n_var, d_idents, n_bc, d_nm, d_n_indel,
+                           d_aln_out, d_bq_out, d_stats, true)) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     const hipStream_t st = (hipStream_t)stream;
     if (n_pairs) HIPCHK(hipMemcpyAsync(d_bq_out, d_bq, 2 * (size_t)n_pairs, hipMemcpyDeviceToDevice, st));
@@ -1184,6 +1195,90 @@ int smc_spike_alleles(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, con
         hipLaunchKernelGGL(k_spike, dim3((unsigned)((n_aln + SPK_BLOCK - 1) / SPK_BLOCK)), dim3(SPK_BLOCK), 0, st, d_aln, (uint32_t)n_aln, d_cig,
                            (unsigned long long)n_pairs, d_var, (int)n_var, (const unsigned long long*)d_idents, (uint32_t)n_bc,
                            (unsigned long long)seed, mismatch_thr, d_nm, d_n_indel, d_aln_out, d_bq_out, d_stats);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
+// (--spikeReps) n_copies spiked copies of a run: k_spike_pool stores the pair pool to every copy, k_spike_reps rewrites behind it
+int smc_spike_alleles_reps(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, const uint8_t* d_bq, int64_t n_pairs,
+                           const smc_spike_variant* d_var, const smc_spike_variant* var_host, int32_t n_var, const uint64_t* d_idents,
+                           int64_t n_bc, const uint64_t* seeds, const uint64_t* thr, int32_t n_copies, double mismatch_thr,
+                           const int32_t* d_nm, const int32_t* d_n_indel, uint8_t* d_aln_out, int64_t aln_stride, uint8_t* d_bq_out,
+                           int64_t bq_stride, uint32_t* d_stats, void* stream) {
+    const std::string who = "smc_spike_alleles_reps";
+    if (int rc = spk_check(who, ctx, d_aln, n_aln, d_cig, d_bq, n_pairs, d_var, var_host, n_var, d_idents, n_bc, d_nm, d_n_indel, d_aln_out,
+                           d_bq_out, d_stats, false)) return rc;
+    if (n_copies < 1 || n_copies > SMC_SPIKE_MAX_COPIES)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies, 1 .. " + std::to_string(SMC_SPIKE_MAX_COPIES) + " expected");
+    if (!seeds || !thr) return fail(SMC_E_ARG, who + ": NULL argument");
+    SpkCopies C;
+    memset(&C, 0, sizeof C);
+    for (int32_t c = 0; c < n_copies; ++c) {
+        if (thr[c] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": copy " + std::to_string(c) + ": a threshold above 2^32");
+        C.seed[c] = seeds[c]; C.thr[c] = thr[c];
+    }
+    if (aln_stride < n_aln * (int64_t)sizeof(smc_dev_aln) || bq_stride < 2 * n_pairs)
+        return fail(SMC_E_INPUT, who + ": strides of " + std::to_string(aln_stride) + " and " + std::to_string(bq_stride) + " bytes are smaller than a copy (" +
+                                 std::to_string(n_aln * (int64_t)sizeof(smc_dev_aln)) + " and " + std::to_string(2 * n_pairs) + " bytes)");
+    if ((aln_stride & 3) || (bq_stride & 15) || (((uintptr_t)d_bq | (uintptr_t)d_bq_out) & 15u) || ((uintptr_t)d_aln_out & 3u))
+        return fail(SMC_E_ARG, who + ": the record stride must be a multiple of 4 bytes, the pool stride and the pools' addresses of 16");
+    if ((double)n_copies * (double)n_var * 2.0 >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies x " + std::to_string(n_var) + " variants: too many statistics words for one call");
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (n_pairs) {
+        const size_t n_chunks = (2 * (size_t)n_pairs + 15) / 16;
+        hipLaunchKernelGGL(k_spike_pool, dim3((unsigned)std::min<size_t>((n_chunks + SPR_BLOCK - 1) / SPR_BLOCK, 2048)), dim3(SPR_BLOCK), 0, st, d_bq,
+                           2ull * (unsigned long long)n_pairs, d_bq_out, (unsigned long long)bq_stride, (int)n_copies);
+    }
+    const size_t n_st = 2 * (size_t)n_var * (size_t)n_copies;
+    if (n_st) hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_st + 255) / 256, 4096)), dim3(256), 0, st, d_stats, (uint32_t)n_st);
+    if (n_aln)
+        hipLaunchKernelGGL(k_spike_reps, dim3((unsigned)((n_aln + SPK_BLOCK - 1) / SPK_BLOCK), (unsigned)n_copies), dim3(SPK_BLOCK), 0, st, d_aln,
+                           (uint32_t)n_aln, d_cig, (unsigned long long)n_pairs, d_var, (int)n_var, (const unsigned long long*)d_idents, (uint32_t)n_bc,
+                           C, mismatch_thr, d_nm, d_n_indel, d_aln_out, (unsigned long long)aln_stride, d_bq_out, (unsigned long long)bq_stride, d_stats);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
+// (--spikeReps) (S, READS, V1) of every listed variant, replicate and target: the counters zeroed, then k_spike_counts
+int smc_spike_rep_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_cnt, const uint32_t* d_cov_off,
+                         const uint32_t* cov_off_host, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
+                         const uint64_t* thr, int32_t n_targets, uint32_t* d_out, void* stream) {
+    const std::string who = "smc_spike_rep_counts";
+    if (!ctx || n_var < 0 || n_reps < 0 || n_targets < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
+    if (n_targets > SMC_SPIKE_REP_MAX_TARGETS)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_SPIKE_REP_MAX_TARGETS));
+    if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
+    if ((n_reps && !d_seeds) || (n_targets && !thr)) return fail(SMC_E_ARG, who + ": NULL argument");
+    SpkThr T;
+    memset(&T, 0, sizeof T);
+    for (int32_t t = 0; t < n_targets; ++t) {
+        if (thr[t] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": target " + std::to_string(t) + ": a threshold above 2^32");
+        T.t[t] = thr[t];
+    }
+    if ((double)n_var * (double)n_reps * (double)n_targets * 3.0 >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants x " + std::to_string(n_reps) + " replicates x " +
+                                 std::to_string(n_targets) + " targets: too many counters for one call");
+    if (!n_var || !n_reps || !n_targets) return SMC_OK;
+    if (!cov_off_host || !d_cov_off || !d_pos1 || !d_out) return fail(SMC_E_ARG, who + ": NULL argument");
+    uint32_t widest = 0;
+    for (int32_t v = 0; v < n_var; ++v) {
+        if (cov_off_host[v + 1] < cov_off_host[v]) return fail(SMC_E_INPUT, who + ": the offsets decrease at variant " + std::to_string(v));
+        widest = std::max(widest, cov_off_host[v + 1] - cov_off_host[v]);
+    }
+    if (cov_off_host[n_var] >= 0x55555500u) return fail(SMC_E_INPUT, who + ": too many covering barcodes for one call");
+    if (cov_off_host[n_var] && (!d_cov_ident || !d_cov_cnt)) return fail(SMC_E_ARG, who + ": NULL covers");
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t n_out = 3 * (size_t)n_var * (size_t)n_reps * (size_t)n_targets;
+    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
+    if (widest)
+        hipLaunchKernelGGL(k_spike_counts, dim3((unsigned)std::min<uint32_t>((widest + SPR_BLOCK - 1) / SPR_BLOCK, 256u), (unsigned)n_var,
+                                                (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPR_BLOCK), 0, st,
+                           (const unsigned long long*)d_cov_ident, d_cov_cnt, d_cov_off, d_pos1, T, (int)n_targets,
+                           (const unsigned long long*)d_seeds, (int)n_reps, d_out);
     HIPCHK(hipGetLastError());
     return SMC_OK;
 }

@@ -1342,13 +1342,20 @@ def spike_run(eng, up: RunOnDevice, A, var: np.ndarray, idents, seed: int, misma
     return RunOnDevice(d_aln, up.cig, d_bq, up.loc, up.ref, n, up.loc_host), stats
 
 
-def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng, nthreads: int = 0, max_reads: int = 128_000_000):
+def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng, nthreads: int = 0, max_reads: int = 128_000_000,
+                keep: dict = None, keep_bytes: int = None):
     """DsRules of --spikeAF, one per target, and the pre-pass: only the runs around the listed loci are decoded (as ds_af_sets groups
     them); smc_allele_carriers gives N and V0 of every variant, then per target smc_spike_alleles writes the spiked copy and
     smc_allele_carriers on it gives V1.  The kernel's statistics are checked against the host's restatement of the draws: the records
     rewritten at v are the reads with v's key of the spiked covering barcodes in the spiked copy, and no other barcode's counters move.
     -> (rules, per target dict(target, rows: per variant dict(N, V0, S, READS, V1))).  ValueError: two barcode texts of the file share
-    an identity."""
+    an identity.
+    `keep` (--spikeReps): a dict that gets what the replicate stage starts from - "runs": an AfRun per run of the pre-pass, decoded
+    and in HBM still (each with a decoder handle of its own and its alignments' (NM, indel length) in `mism`) while their host arrays
+    stay within `keep_bytes` (AF_KEEP_BYTES), a run beyond that without its arrays; "covers": per variant the identities of the
+    barcodes that cover it; "counters": per variant uint32 [covering barcodes, 3] = (reads, alt0, single) - smc_allele_carriers'
+    counters on the run, and its `alt` counter on one copy spiked at threshold 2^32 (every read the rewrite can touch shows ALT
+    there, and no other does); "spikes": the SpikeSet."""
     from .tools import ds_allele_fraction as af
     from .tools import spike_variants as sv
     af.unique_idents(bamio.placed_barcodes(path), path)
@@ -1356,6 +1363,8 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     spikes = SpikeSet(variants)
     P = params_list[0]
     rows = [[None] * len(variants) for _ in targets]
+    if keep is not None:
+        keep.update(runs=[], covers=[None] * len(variants), counters=[None] * len(variants), spikes=spikes)
     order = sorted(range(len(variants)), key=lambda k: (variants[k].chrom, variants[k].pos))
     bam = bamio.NativeBam(path)
     try:
@@ -1366,17 +1375,22 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
             while j + 1 < len(order) and variants[order[j + 1]].chrom == v0.chrom and variants[order[j + 1]].pos - v0.pos < AF_RUN_LOCI:
                 j += 1
             lo, hi = v0.pos - 1, variants[order[j]].pos
-            A = bam.alignments_run(v0.chrom, lo, hi, max_reads, P, nthreads)
-            nl = int(A["nl"])
-            if nl < 1:
-                raise bamio.BamError("--spikeAF: the run %s:%d-%d of the pre-pass could not be decoded" % (v0.chrom, lo + 1, hi))
-            group = [k for k in order[i:j + 1] if variants[k].pos - 1 - lo < nl]
-            var, ins = af_run_variants([variants[k] for k in group], v0.chrom, lo, fasta)
-            idents = bam.barcode_idents(A["n_bc"])
-            nm, n_indel = bam.run_mismatches(len(A["aln"]))
-            up = upload_run(eng, A, fasta.fetch(v0.chrom, lo, lo + nl).upper())
+            own = bamio.NativeBam(path) if keep is not None else None
+            dec = own or bam
+            held = False
+            up = None
             try:
-                cov, car, _ = allele_carriers_run(eng, up, A, lo, var, ins)
+                A = dec.alignments_run(v0.chrom, lo, hi, max_reads, P, nthreads)
+                nl = int(A["nl"])
+                if nl < 1:
+                    raise bamio.BamError("--spikeAF: the run %s:%d-%d of the pre-pass could not be decoded" % (v0.chrom, lo + 1, hi))
+                group = [k for k in order[i:j + 1] if variants[k].pos - 1 - lo < nl]
+                var, ins = af_run_variants([variants[k] for k in group], v0.chrom, lo, fasta)
+                idents = dec.barcode_idents(A["n_bc"])
+                nm, n_indel = dec.run_mismatches(len(A["aln"]))
+                run_ref = fasta.fetch(v0.chrom, lo, lo + nl).upper()
+                up = upload_run(eng, A, run_ref)
+                cov, car, cnt0 = allele_carriers_run(eng, up, A, lo, var, ins, counts=keep is not None)
                 for t, target in enumerate(targets):
                     svar, sorder = spikes.chrom_variants(v0.chrom, target)
                     spiked, stats = spike_run(eng, up, A, svar, idents, seed, P.mismatchThr, nm, n_indel)
@@ -1394,8 +1408,35 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                                                "host's restatement of the draws" % (target, v.chrom, v.pos, reads))
                         rows[t][k] = dict(N=int(cov[r].sum()), V0=int(car[r].sum()), S=int((hit[:cov.shape[1]] & cov[r]).sum()), READS=reads,
                                           V1=int(car1[r].sum()))
+                if keep is not None:
+                    # (`single`: one copy with every barcode spiked at every listed position - thr 2^32 - then the `alt` counters)
+                    svar, _ = spikes.chrom_variants(v0.chrom, 0.5)
+                    svar["thr"] = 1 << 32
+                    spiked, _ = spike_run(eng, up, A, svar, idents, seed, P.mismatchThr, nm, n_indel)
+                    try:
+                        _, _, cnt_all = allele_carriers_run(eng, spiked, A, lo, var, ins, counts=True)
+                    finally:
+                        spiked.aln.free(); spiked.bq.free()
+                    for r, k in enumerate(group):
+                        c = cov[r][:len(idents)]
+                        keep["covers"][k] = idents[c]
+                        keep["counters"][k] = np.stack([cnt0[r, :len(idents), 0][c], cnt0[r, :len(idents), 1][c],
+                                                        cnt_all[r, :len(idents), 1][c]], axis=1).astype(np.uint32)
+                    size = sum(int(A[x].nbytes) for x in ("aln", "cig", "bq", "loc"))
+                    held = size + sum(r.nbytes for r in keep["runs"]) <= (AF_KEEP_BYTES if keep_bytes is None else keep_bytes)
+                    keep["runs"].append(AfRun(v0.chrom, lo, hi, list(group), nl, size if held else 0, own if held else None,
+                                              A if held else None, up if held else None, run_ref if held else None,
+                                              idents if held else None, (nm, n_indel) if held else None))
+            except BaseException:
+                if keep is not None:
+                    free_af_runs(keep["runs"])
+                raise
             finally:
-                up.free()
+                if not held:
+                    if up is not None:
+                        up.free()
+                    if own is not None:
+                        own.close()
             i += len(group)
     finally:
         bam.close()
@@ -1425,13 +1466,14 @@ class AfRun:
     up: object = None
     run_ref: str = None
     idents: object = None
+    mism: object = None         # (--spikeReps) the alignments' (NM, inserted plus deleted length), as the decoder gives them
 
     def free(self):
         if self.up is not None:
             self.up.free()
         if self.bam is not None:
             self.bam.close()
-        self.up = self.bam = self.A = self.idents = None
+        self.up = self.bam = self.A = self.idents = self.mism = None
 
 
 def free_af_runs(runs):
@@ -1665,6 +1707,206 @@ def ds_af_replicates(path: str, fasta, variants, targets, params_list, seed: int
         free_af_runs(keep["runs"])
     times["stage"] = time.perf_counter() - t_start
     return dict(seeds=seeds, counts=counts, rows=rows, times=times, depth_counts=depth_counts)
+
+
+# ---- replicate spike-ins (--spikeReps): R seeds, the achieved counts and B spiked copies per call on the device
+SPIKE_MAX_COPIES = 64          # SMC_SPIKE_MAX_COPIES
+SPIKE_REP_BATCH_BYTES = 1 << 30   # bytes of spiked copies (records + pair pools) one smc_spike_alleles_reps call of the stage writes
+
+
+def spike_rep_counts(eng, positions, covers, counters, seeds, thresholds) -> np.ndarray:
+    """smc_spike_rep_counts -> uint32 [V, R, T, 3] = (S, READS, V1) of every variant, replicate and target.  positions[v]: 1-based;
+    covers[v]: the uint64 identities of the barcodes that cover v; counters[v]: uint32 [len(covers[v]), 3] = (reads, alt0, single);
+    thresholds: floor(t * 2^32) per target."""
+    from .engine import DevBuf
+    n_var, seeds = len(covers), np.ascontiguousarray(seeds, np.uint64)
+    thr = np.ascontiguousarray(thresholds, np.uint64)
+    shape = (n_var, len(seeds), len(thr), 3)
+    off = np.zeros(n_var + 1, np.uint32)
+    off[1:] = np.cumsum([len(c) for c in covers])
+    ident = np.concatenate([np.asarray(c, np.uint64) for c in covers]) if n_var else np.zeros(0, np.uint64)
+    cnt = np.concatenate([np.asarray(c, np.uint32).reshape(-1, 3) for c in counters]) if n_var else np.zeros((0, 3), np.uint32)
+    if len(cnt) != len(ident):
+        raise ValueError("spike_rep_counts: %d covering barcodes, counters of %d" % (len(ident), len(cnt)))
+    pos = np.array([int(p) & 0xFFFFFFFF for p in positions], np.uint32)
+    n_out = int(np.prod(shape))
+    up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.reshape(-1) if a.size else np.zeros(1, a.dtype))
+    bufs = [up(ident), up(cnt), up(off), up(pos), up(seeds), DevBuf(eng, 4 * max(1, n_out) + 256)]
+    try:
+        _lib.check(eng.L.smc_spike_rep_counts(eng.ctx, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data,
+                                              bufs[3].data_ptr(), n_var, bufs[4].data_ptr(), len(seeds), thr.ctypes.data, len(thr),
+                                              bufs[5].data_ptr(), ctypes.c_void_p(0)), "smc_spike_rep_counts")
+        out = bufs[5].download(np.uint32, n_out) if n_out else np.zeros(0, np.uint32)          # (the default stream: behind the kernel)
+    finally:
+        for b in bufs:
+            b.free()
+    return out.reshape(shape)
+
+
+def spike_copy_strides(n_aln: int, n_pairs: int):
+    """The byte strides between the copies of one smc_spike_alleles_reps call: a copy's records / pair pool rounded up to 256 bytes."""
+    return (36 * max(1, n_aln) + 255) & ~255, (2 * max(1, n_pairs) + 255) & ~255
+
+
+def spike_run_copies(eng, up: RunOnDevice, A, var: np.ndarray, idents, seeds, thresholds, mismatch_thr: float, nm, n_indel,
+                     strides=None, fill=None):
+    """smc_spike_alleles_reps over the run `up`: copy c with seeds[c] and every variant at thresholds[c] -> (the copies' records, their
+    pair pools - two DevBufs, copy c at c x stride: free both -, (record stride, pool stride) in bytes, uint32 [copies, n_var, 2]
+    statistics).  `strides`: other than spike_copy_strides'; `fill`: a byte both outputs are filled with first (tests)."""
+    from .engine import DevBuf
+    n, n_pairs, n_var, n_bc, B = up.n_aln, len(A["bq"]) // 2, len(var), int(A["n_bc"]), len(seeds)
+    sa, sb = strides or spike_copy_strides(n, n_pairs)
+    var = np.ascontiguousarray(var, abi.SPIKE_VARIANT_DTYPE)
+    seeds, thr = np.ascontiguousarray(seeds, np.uint64), np.ascontiguousarray(thresholds, np.uint64)
+    up8 = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
+    idents = np.ascontiguousarray(idents, np.uint64)[:n_bc]
+    tmp = [up8(var), up8(idents), up8(np.ascontiguousarray(nm, np.int32)), up8(np.ascontiguousarray(n_indel, np.int32)),
+           DevBuf(eng, 8 * max(1, n_var * B) + 256)]
+    d_aln, d_bq = DevBuf(eng, sa * max(1, B) + 256), DevBuf(eng, sb * max(1, B) + 256)
+    try:
+        if len(nm) < n or len(n_indel) < n or len(thr) != B:
+            raise ValueError("spike_run_copies: %d alignments, NM of %d; %d seeds, %d thresholds" % (n, len(nm), B, len(thr)))
+        if fill is not None:
+            d_aln.upload(np.full(sa * max(1, B), fill, np.uint8)); d_bq.upload(np.full(sb * max(1, B), fill, np.uint8))
+        _lib.check(eng.L.smc_spike_alleles_reps(eng.ctx, up.aln.data_ptr(), n, up.cig.data_ptr(), up.bq.data_ptr(), n_pairs, tmp[0].data_ptr(),
+                                                var.ctypes.data, n_var, tmp[1].data_ptr(), len(idents), seeds.ctypes.data, thr.ctypes.data, B,
+                                                float(mismatch_thr), tmp[2].data_ptr(), tmp[3].data_ptr(), d_aln.data_ptr(), sa,
+                                                d_bq.data_ptr(), sb, tmp[4].data_ptr(), ctypes.c_void_p(0)), "smc_spike_alleles_reps")
+        stats = tmp[4].download(np.uint32, 2 * n_var * B).reshape(B, n_var, 2) if n_var * B else np.zeros((B, 0, 2), np.uint32)
+    except BaseException:
+        d_aln.free(); d_bq.free()
+        raise
+    finally:
+        for b in tmp:
+            b.free()
+    return d_aln, d_bq, (sa, sb), stats
+
+
+def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed, bits):
+    """`len(part_seeds)` spiked copies of a kept run at one target from one smc_spike_alleles_reps call, each built behind the other
+    into one device batch (as _af_rep_call appends its selections) and the batch called with one plan -> (per copy the listed loci's
+    raw rows, in the order of run.group), or NARROW.  var_at[g]: where variant run.group[g] stands in `svar`; want_reads[c][g]: the
+    counts call's READS of that copy and variant - the kernel's statistics must equal it."""
+    from . import vc
+    A, up, lo, nl, chrom = run.A, run.up, run.lo, run.nl, run.chrom
+    B = len(part_seeds)
+    ns_full = int(A["n_slots"])
+    cap = B * (ns_full + nl) + ns_full + nl + 64
+    d_aln, d_bq, (sa, sb), stats = spike_run_copies(eng, up, A, svar, run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
+    d = None
+    try:
+        for c in range(B):
+            for g, k in enumerate(run.group):
+                if int(stats[c, var_at[g], 0]) != int(want_reads[c][g]):
+                    v = variants[k]
+                    raise RuntimeError("--spikeReps: seed %d at %s:%d: the rewrite touched %d records, the counts call says %d" %
+                                       (int(part_seeds[c]), v.chrom, v.pos, int(stats[c, var_at[g], 0]), int(want_reads[c][g])))
+        d = _DsBatch(eng, cap, bits, False)
+        cp = abi.c_params(P)
+        n_loc = 0
+        for c in range(B):
+            copy = RunOnDevice(d_aln.view(c * sa), up.cig, d_bq.view(c * sb), up.loc, up.ref, up.n_aln, up.loc_host)
+            # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch)
+            done = build_run(A, eng.L, eng, cp, P, chrom, lo, fasta, run.run_ref, [d.words] + d.planes, d.uaux, d.slots, d.slots + n_loc, cap,
+                             max_depth, run.bam.allele_key, run.bam.barcode_name, sampler=sampler, sampler_seed=sampler_seed,
+                             barcode_idents=lambda n: run.idents, uploaded=copy)
+            if done is None:
+                raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "a replicate: the device builder does not take it", "--spikeReps"))
+            if done == NARROW:
+                return NARROW
+            _, ns_k, lc, tb = done
+            d.LC.append(lc)
+            d.tables += tb
+            d.slots += ns_k
+            n_loc += nl
+        lc = d.LC[0] if len(d.LC) == 1 else np.concatenate(d.LC)
+        plan = eng.make_plan(lc)
+        try:
+            out_rows = plan.run_devbuf([d.words, d.uaux[0]], P)
+        finally:
+            plan.close()
+        at = [variants[k].pos - 1 - lo for k in run.group]
+        idx = np.array([b * nl + a for b in range(B) for a in at], np.int64)
+        view = vc.LocusView([chrom] * len(idx), [lo + 1 + a for _ in range(B) for a in at],
+                            [run.run_ref[a] if a < len(run.run_ref) else "" for _ in range(B) for a in at], [d.tables[i] for i in idx.tolist()])
+        text = vc._strings(out_rows[idx].copy(), view, P, fasta)
+        g = len(at)
+        return [list(text[b * g:(b + 1) * g]) for b in range(B)]
+    finally:
+        d_aln.free(); d_bq.free()
+        if d is not None:
+            d.free()
+
+
+def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int, n_reps: int, eng, keep: dict, sampler: str = "reference",
+                     sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000):
+    """The replicate stage of --spikeReps.  Replicate j is --spikeAF with seed (seed + j) mod 2^64.  One smc_spike_rep_counts call
+    gives (S, READS, V1) of every variant, replicate and target from what the pre-pass kept (spike_rules' `keep`) - no spiked copy is
+    needed for them; then per kept run and target as many replicates as fit SPIKE_REP_BATCH_BYTES (and AF_REP_BATCH_SLOTS read
+    slots, and SMC_SPIKE_MAX_COPIES) are spiked by one smc_spike_alleles_reps call, built one behind the other and called with one
+    plan.  Every copy's statistics are checked against the counts call's READS.
+    -> dict(seeds, counts: uint32 [V, R, T, 3], rows: {(variant index, target index, replicate): the raw row string at the variant's
+    locus}, times: seconds per part and the numbers of rewrite calls, builds and batches)."""
+    import time
+    from . import dsaf
+    from .tools import spike_variants as sv
+    t_start = time.perf_counter()
+    T = len(targets)
+    if T > SPIKE_MAX_TARGETS:
+        raise ValueError("--spikeReps: %d --spikeAF targets, at most %d" % (T, SPIKE_MAX_TARGETS))
+    seeds = dsaf.rep_seeds(seed, n_reps)
+    thr = [sv.threshold(t) for t in targets]
+    spikes = keep["spikes"]
+    times = {"counts": 0.0, "calls": 0.0, "decode again": 0.0, "rewrites": 0, "builds": 0, "batches": 0}
+    rows = {}
+    max_depth = eng.L.smc_build_max_depth()
+    try:
+        t0 = time.perf_counter()
+        counts = spike_rep_counts(eng, [v.pos for v in variants], keep["covers"], keep["counters"], seeds, thr)
+        times["counts"] = time.perf_counter() - t0
+        for run in keep["runs"]:
+            if run.A is None:
+                # (over the byte cap of the pre-pass: decoded and uploaded again)
+                t0 = time.perf_counter()
+                run.bam = bamio.NativeBam(path)
+                run.A = run.bam.alignments_run(run.chrom, run.lo, run.hi, max_reads, params_list[0], nthreads or bamio.host_threads())
+                if int(run.A["nl"]) != run.nl:
+                    raise bamio.BamError("--spikeReps: the run %s:%d-%d was decoded as %d loci, the pre-pass had %d" %
+                                         (run.chrom, run.lo + 1, run.hi, int(run.A["nl"]), run.nl))
+                run.run_ref = fasta.fetch(run.chrom, run.lo, run.lo + run.nl).upper()
+                run.up = upload_run(eng, run.A, run.run_ref)
+                run.idents = run.bam.barcode_idents(run.A["n_bc"])
+                run.mism = run.bam.run_mismatches(len(run.A["aln"]))
+                times["decode again"] += time.perf_counter() - t0
+            svar, sorder = spikes.chrom_variants(run.chrom, targets[0])
+            var_at = [sorder.index(k) for k in run.group]
+            sa, sb = spike_copy_strides(run.up.n_aln, len(run.A["bq"]) // 2)
+            room = max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // (sa + sb), AF_REP_BATCH_SLOTS // max(1, int(run.A["n_slots"]) + run.nl)))
+            t0 = time.perf_counter()
+            for t in range(T):
+                P = params_list[t]
+                for b in range(0, n_reps, room):
+                    js = list(range(b, min(n_reps, b + room)))
+                    want = [[int(counts[k, j, t, 1]) for k in run.group] for j in js]
+                    bits = 16 if (eng.word_bits == 16 and 0 <= P.minBQ <= 63) else 32
+                    args = (eng, run, svar, var_at, [seeds[j] for j in js], thr[t], want, P, fasta, variants, max_depth, sampler, sampler_seed)
+                    out = _spike_rep_call(*args, bits)
+                    if out == NARROW:
+                        eng.word_bits = 32
+                        out = _spike_rep_call(*args, 32)
+                        times["rewrites"] += 1
+                    for j, text in zip(js, out):
+                        for k, line in zip(run.group, text):
+                            rows[(k, t, j)] = line
+                    times["rewrites"] += 1
+                    times["builds"] += len(js)
+                    times["batches"] += 1
+            times["calls"] += time.perf_counter() - t0
+            run.free()
+    finally:
+        free_af_runs(keep["runs"])
+    times["stage"] = time.perf_counter() - t_start
+    return dict(seeds=seeds, counts=counts, rows=rows, times=times)
 
 
 def _fnv64(text: str) -> int:

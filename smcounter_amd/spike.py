@@ -1,6 +1,10 @@
 """--spikeAF on the host side of a run: the command line's checks of the listed SNVs and targets, and
 <outPrefix>.spikeAF.detection.txt - which planted variant the caller finds at which achieved allele fraction, on one page.
 
+--spikeReps: the three files that turn R x T spike-ins into a detection rate with an interval and an observed limit beside the
+theoretical one - <outPrefix>.spikeAF.replicates.txt, .spikeAF.sensitivity.txt and .spikeAF.curve.txt (the replicate stage itself is
+devplanes.spike_replicates).
+
 The semantics are tools/spike_variants.py's (DESIGN.md "--spikeAF"); the rewrite on the GPU is csrc/k_spike.inc (smc_spike_alleles),
 the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the main pass are devplanes.spike_rules / spike_run.
 """
@@ -89,3 +93,107 @@ def write_detection(out_prefix: str, variants, outputs, loc_index=None) -> None:
                 r = (res_rows or outputs[1][2])[i]
                 lod = float(lods[loc_index[key]]) if lods is not None else None
                 fh.write(detection_line(v, target, r, rows.get(key), cut.get(key), lod) + "\n")
+
+
+# ---- --spikeReps
+REPS_MIN, REPS_MAX = dsaf.REPS_MIN, dsaf.REPS_MAX
+REPLICATES_HEADER = DETECTION_HEADER[:5] + ("REP", "SEED") + DETECTION_HEADER[5:]
+SENSITIVITY_HEADER = ("CHROM", "POS", "REF", "ALT", "TARGET", "REPS", "CALLED", "RATE", "LO95", "HI95", "AF_MEAN", "AF_MIN", "AF_MAX",
+                      "S_MIN", "S_MAX", "V_MIN", "V_MAX", "PI_MEAN", "PI_MIN")
+CURVE_HEADER = ("CHROM", "POS", "REF", "ALT", "N")
+
+
+def reps(args, spike_targets):
+    """--spikeReps -> R, or None without the flag.  SystemExit: without --spikeAF, R no integer or outside REPS_MIN .. REPS_MAX."""
+    r = getattr(args, "spikeReps", None)
+    if r in (None, ""):
+        return None
+    if not spike_targets:
+        raise SystemExit("--spikeReps replicates the spike-ins of --spikeAF: it needs --spikeAF")
+    try:
+        if isinstance(r, float) and r != int(r):
+            raise ValueError(r)
+        r = int(r)
+    except ValueError:
+        raise SystemExit("--spikeReps: an integer in %d .. %d expected, got %r" % (REPS_MIN, REPS_MAX, r))
+    if not (REPS_MIN <= r <= REPS_MAX):
+        raise SystemExit("--spikeReps: the number of replicates must lie in %d .. %d, got %d" % (REPS_MIN, REPS_MAX, r))
+    return r
+
+
+def replicate_line(v, target, rep: int, seed: int, r, row, cut) -> str:
+    """detection_line() of one replicate with REP and SEED behind TARGET (no LOD column).  `r`: dict(N, V0, S, READS, V1) of that
+    replicate."""
+    f = detection_line(v, target, r, row, cut).split("\t")
+    return "\t".join(f[:5] + ["%d" % rep, "%d" % seed] + f[5:])
+
+
+def _called(v, per) -> int:
+    return sum(1 for _, _, cut in per if cut is not None and cut[0] == v.ref and v.alt in cut[1])
+
+
+def sensitivity_line(v, target, per, lod=None) -> str:
+    """One line of the sensitivity table: variant `v` at `target` over its replicates.  `per`: per replicate (dict(N, V0, S, READS,
+    V1), row fields or None, cut or None) - what replicate_line() takes; a replicate without a row counts PI as 0; `lod`: the locus's
+    LOD in the run's own output of that target, with --lod."""
+    n = len(per)
+    called = _called(v, per)
+    lo, hi = dsaf.wilson(called, n)
+    afs = [float(r["V1"]) / r["N"] if r["N"] else 0.0 for r, _, _ in per]
+    pis = [dsaf._pi(row) for _, row, _ in per]
+    ss, vs = [r["S"] for r, _, _ in per], [r["V1"] for r, _, _ in per]
+    f = [v.chrom, "%d" % v.pos, v.ref, v.alt, dsaf.target_text(target), "%d" % n, "%d" % called, dsaf.frac_text(float(called) / n),
+         dsaf.frac_text(lo), dsaf.frac_text(hi), dsaf.frac_text(sum(afs) / n), dsaf.frac_text(min(afs)), dsaf.frac_text(max(afs)),
+         "%d" % min(ss), "%d" % max(ss), "%d" % min(vs), "%d" % max(vs), dsaf.frac_text(sum(pis) / n), dsaf.frac_text(min(pis))]
+    if lod is not None:
+        f.append("%.15g" % lod)
+    return "\t".join(f)
+
+
+def curve_header(targets, with_lod: bool = False):
+    return CURVE_HEADER + tuple("RATE@%g" % t for t in sorted(targets)) + ("T95",) + (("LOD",) if with_lod else ())
+
+
+def curve_line(v, n: int, targets, per_target, lod=None) -> str:
+    """One line of the curve: variant `v` with N covering barcodes; per_target[t]: the replicates of targets[t] as sensitivity_line()
+    takes them.  RATE@ columns in ascending target order, then T95 (dsaf.t95, or NA); `lod`: the theoretical limit beside it."""
+    rates = [float(_called(v, per)) / len(per) for per in per_target]
+    best = dsaf.t95(targets, rates)
+    f = [v.chrom, "%d" % v.pos, v.ref, v.alt, "%d" % n] + [dsaf.frac_text(rates[t]) for t in sorted(range(len(targets)), key=lambda t: targets[t])] + \
+        [dsaf.NA if best is None else "%g" % best]
+    if lod is not None:
+        f.append("%.15g" % lod)
+    return "\t".join(f)
+
+
+def write_replicates(out_prefix: str, variants, targets, seeds, entries) -> None:
+    """<outPrefix>.spikeAF.replicates.txt: a header, then a line per listed variant (file order), target (the order given) and
+    replicate (ascending).  entries[(v, t)]: per replicate (dict(N, V0, S, READS, V1), row fields or None, cut or None)."""
+    with open(out_prefix + ".spikeAF.replicates.txt", "w") as fh:
+        fh.write("\t".join(REPLICATES_HEADER) + "\n")
+        for i, v in enumerate(variants):
+            for t, target in enumerate(targets):
+                for j, (r, row, cut) in enumerate(entries[(i, t)]):
+                    fh.write(replicate_line(v, target, j, seeds[j], r, row, cut) + "\n")
+
+
+def write_sensitivity(out_prefix: str, variants, targets, entries, lods=None) -> None:
+    """<outPrefix>.spikeAF.sensitivity.txt: a header, then a line per listed variant and target.  lods[t][v] (with --lod): the LOD of
+    the variant's locus in the run's .spikeAF<t> output."""
+    with open(out_prefix + ".spikeAF.sensitivity.txt", "w") as fh:
+        fh.write("\t".join(SENSITIVITY_HEADER + (("LOD",) if lods is not None else ())) + "\n")
+        for i, v in enumerate(variants):
+            for t, target in enumerate(targets):
+                fh.write(sensitivity_line(v, target, entries[(i, t)], None if lods is None else float(lods[t][i])) + "\n")
+
+
+def write_curve(out_prefix: str, variants, targets, entries, lods=None) -> None:
+    """<outPrefix>.spikeAF.curve.txt: a header, then a line per listed variant - the observed limit (T95) beside, with --lod, the
+    theoretical one: the locus's LOD in the output of the LARGEST listed target."""
+    T = len(targets)
+    top = max(range(T), key=lambda t: targets[t])
+    with open(out_prefix + ".spikeAF.curve.txt", "w") as fh:
+        fh.write("\t".join(curve_header(targets, lods is not None)) + "\n")
+        for i, v in enumerate(variants):
+            fh.write(curve_line(v, entries[(i, 0)][0][0]["N"], targets, [entries[(i, t)] for t in range(T)],
+                                None if lods is None else float(lods[top][i])) + "\n")

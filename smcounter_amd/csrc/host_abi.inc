@@ -81,6 +81,20 @@ struct smc_ctx {
     int n_cu = 256; // compute units of the device
 };
 
+// A scratch buffer of the context, grown on demand: `need` bytes are used now; where it has fewer, `want` (need plus the entry's
+// margin) are allocated.  `sync`: the stream to wait for before the old block goes - the entry's earlier kernels on it may still
+// use the block; null: the entry waits for its own kernels before it returns (and hipFree synchronises the device).
+static int grow_scratch(void*& ptr, size_t& have, size_t need, size_t want, const char* who, const hipStream_t* sync) {
+    if (need <= have) return SMC_OK;
+    if (sync) { const hipStream_t st = *sync; HIPCHK(hipStreamSynchronize(st)); }
+    (void)hipFree(ptr);
+    ptr = nullptr; have = 0;
+    hipError_t e = hipMalloc(&ptr, want);
+    if (e != hipSuccess) return fail(SMC_E_HIP, std::string(who) + ": " + std::to_string(want) + " bytes of scratch: " + hipGetErrorString(e));
+    have = want;
+    return SMC_OK;
+}
+
 // size classes of the pool: powers of two up to 256 MB, multiples of 64 MB beyond (a 12 GB block is not rounded to 16)
 static size_t plan_size_class(size_t bytes) {
     if (bytes > ((size_t)256 << 20)) return (bytes + ((size_t)64 << 20) - 1) & ~(((size_t)64 << 20) - 1);
@@ -141,6 +155,9 @@ static size_t host_hdr_bytes(int a_cap) {
 static size_t whole_locus_lds(const smc_locus& L, int a_cap) {
     return host_hdr_bytes(a_cap) + 4 * (((size_t)L.n_reads + 3) / 4 + 2) + 9 * (size_t)L.n_umi + 32;
 }
+// LDS of a workgroup of a bin whose tables hold fcap flag dwords and ucap barcodes (a whole-locus class's largest locus, or the
+// deep class's chunk), in units of 256 bytes
+static size_t bin_lds_bytes(int a_cap, size_t fcap, size_t ucap) { return (host_hdr_bytes(a_cap) + 4 * fcap + 9 * ucap + 32 + 255) & ~(size_t)255; }
 
 // Workgroup size by locus size: the smallest block that still keeps the CU's SIMDs busy while the locus's reads stream
 // - small blocks pay less for the barriers between phases and for the parts one wavefront runs alone.  Thresholds
@@ -220,6 +237,124 @@ struct smc_plan {
     PlanSpec* d_spec = nullptr;
     int spec_checked = -1;            // -1: not looked at yet; else the verdict
 };
+
+// ---- making a plan: what smc_plan_create (from host descriptors), smc_plan_create_dev (classified on the device, waits for the record)
+// and smc_plan_create_dev_spec (sized from the last plan, waits for nothing) share
+// The classes' thresholds and the deep class's geometry.  (Experiments and tests: the geometry and its threshold can be overridden
+// when the plan is made - the environment is read on every call: tests switch the knobs on and off in one process.)
+static PlanCfg plan_cfg_from_env(int& deep_fcap) {
+    auto env_int = [](const char* name, int dflt) { const char* v = exp_env(name); return v && *v ? atoi(v) : dflt; };
+    PlanCfg C;
+    C.cls_reads[0] = SMC_R0; C.cls_reads[1] = SMC_R1; C.cls_reads[2] = SMC_R2; C.cls_reads[3] = SMC_R3;
+    C.deep_from = env_int("SMC_DEEP_FROM_READS", SMC_R3);                  // more reads than this: the deep class
+    // reads per locus: 2^24 (the limits are the 27-bit slot field and memory; pysam's max_depth in the reference is 10^6)
+    C.max_reads = 1 << 24;
+    deep_fcap = std::max(8, env_int("SMC_DEEP_FCAP", SMC_DEEP_FCAP));
+    C.deep_ucap = std::min(32767, std::max(1, env_int("SMC_DEEP_UCAP", SMC_DEEP_UCAP)));   // (15-bit queue entries)
+    C.deep_part_reads = std::max(64, env_int("SMC_DEEP_PART_READS", SMC_DEEP_PART_READS));
+    return C;
+}
+
+// A plan under construction and the bins being filled, one per class.  Every failure after `new smc_plan()` goes through fail():
+// the blocks the bins hold by then are handed to the plan first, so that smc_plan_destroy returns them to the pool with the plan's
+// own (ADVICE r3) - no exit leaves the plan or a pooled block behind.
+struct PlanBuild {
+    smc_plan* p;
+    Bin bins[5];
+    PlanBuild(smc_ctx* ctx, int64_t n_loci) : p(new smc_plan()) {
+        p->ctx = ctx; p->n_loci = n_loci;
+        for (int c = 0; c < 5; ++c) bins[c].cls = c;
+    }
+    int fail(int code, const std::string& msg) {
+        for (auto& b : bins) p->bins.push_back(b);
+        smc_plan_destroy(p);
+        return ::fail(code, msg);
+    }
+    // the bins that have a launch go to the plan, in class order, with their LDS sizes; a bin handed over is cleared here: fail()
+    // must not give it twice
+    void hand_over() {
+        for (auto& b : bins) {
+            if (!b.n_parts) continue;
+            b.lds_bytes = bin_lds_bytes(b.a_cap, (size_t)b.fcap, (size_t)b.ucap);
+            p->bins.push_back(std::move(b));
+            b = Bin();
+        }
+    }
+    smc_plan* commit() { hand_over(); return p; }
+};
+#define PCHK(x)                                                                                         \
+    do {                                                                                                \
+        hipError_t e_ = (x);                                                                            \
+        if (e_ != hipSuccess) return B.fail(SMC_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// a whole-locus bin of n_parts workgroups: its launch list and the loci's descriptors in launch order, sized and allocated
+static int bin_blocks(PlanBuild& B, Bin& b, size_t n_parts) {
+    smc_ctx* ctx = B.p->ctx;
+    b.n_parts = n_parts;
+    b.parts_bytes = sizeof(V2Part) * n_parts;
+    b.desc_bytes = sizeof(smc_locus) * n_parts;
+    PCHK(plan_alloc(ctx, (void**)&b.d_parts, b.parts_bytes));
+    PCHK(plan_alloc(ctx, (void**)&b.d_desc, b.desc_bytes));
+    return SMC_OK;
+}
+// the deep bin (its a_cap is set): also an accumulator per locus cut into more than one part, fdw flag dwords of scratch and the
+// workgroups' offsets into them
+static int deep_bin_blocks(PlanBuild& B, Bin& b, size_t n_parts, size_t n_acc, uint64_t fdw) {
+    smc_ctx* ctx = B.p->ctx;
+    b.acc_bytes = std::max<size_t>(1, n_acc) * v2_acc_words(b.a_cap) * 4;
+    b.flags_bytes = (size_t)fdw * 4;
+    b.foff_bytes = sizeof(int64_t) * n_parts;
+    PCHK(plan_alloc(ctx, (void**)&b.d_acc, b.acc_bytes));
+    PCHK(plan_alloc(ctx, (void**)&b.d_flags, b.flags_bytes));
+    PCHK(plan_alloc(ctx, (void**)&b.d_flags_off, b.foff_bytes));
+    return bin_blocks(B, b, n_parts);
+}
+
+// The device prologue of smc_plan_create_dev and smc_plan_create_dev_spec: the context's record and list of deep loci are there and
+// free (one of each per context: a plan made on another stream waits for the plan before it to be through with them), the record is
+// zero, and k_plan_classify sums this batch into it.
+static int plan_classify(PlanBuild& B, const smc_locus* d_loci, const PlanCfg& C, hipStream_t st) {
+    smc_plan* p = B.p;
+    smc_ctx* ctx = p->ctx;
+    const int64_t n_loci = p->n_loci;
+    if (!ctx->plan_stats) {
+        PCHK(hipMalloc(&ctx->plan_stats, sizeof(PlanStats)));
+        PCHK(hipHostMalloc(&ctx->plan_stats_host, sizeof(PlanStats), hipHostMallocDefault));
+    }
+    if (ctx->plan_deep_cap < (size_t)n_loci) {
+        PCHK(hipStreamSynchronize(st));
+        (void)hipFree(ctx->plan_deep); ctx->plan_deep = nullptr; ctx->plan_deep_cap = 0;
+        PCHK(hipMalloc(&ctx->plan_deep, sizeof(PlanDeep) * (size_t)n_loci));
+        ctx->plan_deep_cap = (size_t)n_loci;
+    }
+    PlanStats* d_st = (PlanStats*)ctx->plan_stats;
+    if (ctx->plan_fill_ev) PCHK(hipStreamWaitEvent(st, ctx->plan_fill_ev, 0));
+    if (!ctx->plan_stats_clean) PCHK(hipMemsetAsync(d_st, 0, sizeof(PlanStats), st));
+    ctx->plan_stats_clean = false;
+    hipLaunchKernelGGL(k_plan_classify, dim3((unsigned)((n_loci + PLAN_BLOCK - 1) / PLAN_BLOCK)), dim3(PLAN_BLOCK), 0, st, d_loci, (int)n_loci, C, d_st,
+                       (PlanDeep*)ctx->plan_deep, p->d_flt_list);
+    PCHK(hipGetLastError());
+    p->flt_clean = true;                                               // (k_plan_classify has zeroed both worklists' counts)
+    return SMC_OK;
+}
+// Their epilogue, in two steps (smc_plan_create_dev makes its deep class's lists between them).  Behind k_plan_fill / k_plan_fill_spec,
+// whose last workgroup zeroes the record: the event the next plan's kernels wait for.
+static int plan_fill_launched(PlanBuild& B, hipStream_t st) {
+    smc_ctx* ctx = B.p->ctx;
+    if (!ctx->plan_fill_ev) PCHK(hipEventCreateWithFlags(&ctx->plan_fill_ev, hipEventDisableTiming));
+    PCHK(hipEventRecord(ctx->plan_fill_ev, st));
+    ctx->plan_stats_clean = true;
+    return SMC_OK;
+}
+// Behind the last kernel that writes the plan's lists: the bins to the plan, and the event a plan destroyed unrun waits for.
+static int plan_lists_launched(PlanBuild& B, hipStream_t st) {
+    smc_plan* p = B.p;
+    B.hand_over();
+    PCHK(hipEventCreateWithFlags(&p->done_ev, hipEventDisableTiming));
+    PCHK(hipEventRecord(p->done_ev, st));
+    return SMC_OK;
+}
 
 // calProb's likelihoods all carry the factor rightP (smCounter.py:62-91), so the posteriors depend on the odds
 // e / (1 - e) of the fragments only: P(barcode | allele k) / rightP = pcr_no_error * prod(odds of the fragments that do not
@@ -391,61 +526,47 @@ int smc_plan_create(smc_ctx* ctx, const smc_locus* loci, int64_t n_loci, smc_pla
     if (!ctx || !out || (n_loci > 0 && !loci)) return fail(SMC_E_ARG, "smc_plan_create: NULL argument");
     if (n_loci > 0x7fffffff) return fail(SMC_E_ARG, "smc_plan_create: more than 2^31-1 loci in one batch");
     HIPCHK(hipSetDevice(ctx->device));
-    smc_plan* p = new smc_plan();
-    p->ctx = ctx;
-    p->n_loci = n_loci;
-    // reads per locus: 2^24 (the limits are the 27-bit slot field and memory; pysam's max_depth in the reference is 10^6)
-    const int max_reads = 1 << 24;
-    static const int cls_reads[4] = {SMC_R0, SMC_R1, SMC_R2, SMC_R3};
-    // (experiments and tests: the deep class's geometry and its threshold can be overridden when the plan is made)
-    auto env_int = [](const char* name, int dflt) { const char* v = exp_env(name); return v && *v ? atoi(v) : dflt; };
-    const int deep_from = env_int("SMC_DEEP_FROM_READS", SMC_R3);          // more reads than this: the deep class
-    const int deep_fcap = std::max(8, env_int("SMC_DEEP_FCAP", SMC_DEEP_FCAP));
-    const int deep_ucap = std::min(32767, std::max(1, env_int("SMC_DEEP_UCAP", SMC_DEEP_UCAP)));   // (15-bit queue entries)
-    const int deep_part_reads = std::max(64, env_int("SMC_DEEP_PART_READS", SMC_DEEP_PART_READS));
-    std::vector<Bin> bins(5);
-    for (int c = 0; c < 5; ++c) bins[c].cls = c;
+    int deep_fcap;
+    const PlanCfg C = plan_cfg_from_env(deep_fcap);
+    PlanBuild B(ctx, n_loci);
+    smc_plan* p = B.p;
     for (int64_t l = 0; l < n_loci; ++l) {
         const smc_locus& L = loci[l];
-        if (L.n_alleles > SMC_MAX_ALLELES || L.n_reads < 0 || L.n_umi < 0 || L.n_frag < 0 || L.n_reads >= max_reads) {
-            delete p;
-            return fail(SMC_E_INPUT, "smc_plan_create: locus " + std::to_string(l) +
-                                         " violates the layout contract (alleles<=64, reads<2^24)");
-        }
+        if (L.n_alleles > SMC_MAX_ALLELES || L.n_reads < 0 || L.n_umi < 0 || L.n_frag < 0 || L.n_reads >= C.max_reads)
+            return B.fail(SMC_E_INPUT, "smc_plan_create: locus " + std::to_string(l) +
+                                           " violates the layout contract (alleles<=64, reads<2^24)");
         // one parameter set per batch, and it must be stated: the planes bake minBQ / minMQ / mismatchThr / primerDist in
         const uint16_t fp = (uint16_t)(L.flags >> SMC_LF_FP_SHIFT);
-        if (fp == 0 || (l > 0 && fp != p->fp)) {
-            delete p;
-            return fail(SMC_E_INPUT, "smc_plan_create: locus " + std::to_string(l) + (fp == 0 ?
-                        " carries no parameter fingerprint (smc_locus.flags bits 1-15 = smc_param_fingerprint(...))" :
-                        " was built with different parameters than locus 0 (fingerprints differ)"));
-        }
+        if (fp == 0 || (l > 0 && fp != p->fp))
+            return B.fail(SMC_E_INPUT, "smc_plan_create: locus " + std::to_string(l) + (fp == 0 ?
+                          " carries no parameter fingerprint (smc_locus.flags bits 1-15 = smc_param_fingerprint(...))" :
+                          " was built with different parameters than locus 0 (fingerprints differ)"));
         p->fp = fp;
         p->need_quads = std::max<int64_t>(p->need_quads, (int64_t)L.read_off4 + (L.n_reads + 3) / 4);
         int a_cap = (L.n_alleles + 7) & ~7;
         if (a_cap < 8) a_cap = 8;
         int c = SMC_CLS_DEEP;
         for (int k = 0; k < 4; ++k)
-            if (L.n_reads <= cls_reads[k] && L.n_reads <= deep_from) { c = k; break; }
+            if (L.n_reads <= C.cls_reads[k] && L.n_reads <= C.deep_from) { c = k; break; }
         // (many barcodes with few reads: the per-barcode tables, not the reads, size the workgroup's LDS)
         if (c < SMC_CLS_DEEP && whole_locus_lds(L, a_cap) > 64 * 1024) c = SMC_CLS_DEEP;
-        Bin& b = bins[c];
+        Bin& b = B.bins[c];
         b.order.push_back((int)l);
         if (a_cap > b.a_cap) b.a_cap = a_cap;
         b.reads += L.n_reads;
     }
     p->flt_bytes = sizeof(uint32_t) * 2 * ((size_t)n_loci + 2);   // two worklists, each [0] = count, then locus indices (runs alternate)
-    HIPCHK(plan_alloc(ctx, (void**)&p->d_flt_list, p->flt_bytes));
+    PCHK(plan_alloc(ctx, (void**)&p->d_flt_list, p->flt_bytes));
     if (n_loci) {
         p->loci_bytes = sizeof(smc_locus) * (size_t)n_loci;
-        HIPCHK(plan_alloc(ctx, (void**)&p->d_loci, p->loci_bytes));
-        HIPCHK(hipMemcpy(p->d_loci, loci, sizeof(smc_locus) * (size_t)n_loci, hipMemcpyHostToDevice));
+        PCHK(plan_alloc(ctx, (void**)&p->d_loci, p->loci_bytes));
+        PCHK(hipMemcpy(p->d_loci, loci, sizeof(smc_locus) * (size_t)n_loci, hipMemcpyHostToDevice));
     }
-    for (auto& b : bins) {
+    int n_bins = 0;                                                // (a bin's place in the plan: classes without loci are left out)
+    for (auto& b : B.bins) {
         if (b.order.empty()) continue;
         // heaviest loci first: the tail of the launch is then made of light blocks
         std::stable_sort(b.order.begin(), b.order.end(), [&](int x, int y) { return loci[x].n_reads > loci[y].n_reads; });
-        std::vector<int64_t> foff;
         if (b.cls < SMC_CLS_DEEP) {
             int mq = 0, mu = 0;
             for (int l : b.order) {
@@ -454,46 +575,33 @@ int smc_plan_create(smc_ctx* ctx, const smc_locus* loci, int64_t n_loci, smc_pla
                 b.parts.push_back(V2Part{l, 0, 1, 0});
             }
             b.fcap = mq; b.ucap = mu > 0 ? mu : 1;
+            if (int rc = bin_blocks(B, b, b.parts.size())) return rc;
         } else {
-            b.fcap = deep_fcap; b.ucap = deep_ucap;
+            b.fcap = deep_fcap; b.ucap = C.deep_ucap;
+            std::vector<int64_t> foff;
             int n_acc = 0;
             int64_t fdw = 0;
             for (int l : b.order) {
                 const smc_locus& L = loci[l];
-                int np = (int)(((int64_t)L.n_reads + deep_part_reads - 1) / deep_part_reads);
-                np = std::max(np, (int)(((int64_t)L.n_umi * 10 + 9ll * deep_ucap - 1) / (9ll * deep_ucap)));   // (a share of <= 0.9 ucap barcodes)
-                np = std::max(1, std::min(np, std::max(1, L.n_umi)));
+                const int np = plan_deep_parts(C, L.n_reads, L.n_umi);
                 const int acc = np > 1 ? n_acc++ : 0;
                 for (int q = 0; q < np; ++q) {
                     b.parts.push_back(V2Part{l, q, np, acc});
                     foff.push_back(fdw + 2 * q);
                 }
-                fdw += ((int64_t)L.n_reads + 3) / 4 + 2 * np + 4;
+                fdw += plan_deep_fdw(L.n_reads, np);
             }
-            b.acc_bytes = (size_t)std::max(1, n_acc) * v2_acc_words(b.a_cap) * 4;
-            b.flags_bytes = (size_t)fdw * 4;
-            b.foff_bytes = sizeof(int64_t) * foff.size();
-            HIPCHK(plan_alloc(ctx, (void**)&b.d_acc, b.acc_bytes));
-            HIPCHK(plan_alloc(ctx, (void**)&b.d_flags, b.flags_bytes));
-            HIPCHK(plan_alloc(ctx, (void**)&b.d_flags_off, b.foff_bytes));
-            HIPCHK(hipMemcpy(b.d_flags_off, foff.data(), sizeof(int64_t) * foff.size(), hipMemcpyHostToDevice));
+            if (int rc = deep_bin_blocks(B, b, b.parts.size(), (size_t)n_acc, (uint64_t)fdw)) return rc;
+            PCHK(hipMemcpy(b.d_flags_off, foff.data(), sizeof(int64_t) * foff.size(), hipMemcpyHostToDevice));
         }
-        b.lds_bytes = (host_hdr_bytes(b.a_cap) + 4 * (size_t)b.fcap + 9 * (size_t)b.ucap + 32 + 255) & ~(size_t)255;
-        b.n_parts = b.parts.size();
-        b.parts_bytes = sizeof(V2Part) * b.parts.size();
-        HIPCHK(plan_alloc(ctx, (void**)&b.d_parts, b.parts_bytes));
-        HIPCHK(hipMemcpy(b.d_parts, b.parts.data(), sizeof(V2Part) * b.parts.size(), hipMemcpyHostToDevice));
-        {
-            std::vector<smc_locus> dl(b.parts.size());
-            for (size_t k = 0; k < dl.size(); ++k) dl[k] = loci[b.parts[k].li];
-            b.desc_bytes = sizeof(smc_locus) * dl.size();
-            HIPCHK(plan_alloc(ctx, (void**)&b.d_desc, b.desc_bytes));
-            HIPCHK(hipMemcpy(b.d_desc, dl.data(), b.desc_bytes, hipMemcpyHostToDevice));
-        }
-        if (b.reads > p->dom_reads) { p->dom_reads = b.reads; p->dom_loci = (int64_t)b.order.size(); p->dom_bin = (int)p->bins.size(); }
-        p->bins.push_back(b);
+        PCHK(hipMemcpy(b.d_parts, b.parts.data(), sizeof(V2Part) * b.parts.size(), hipMemcpyHostToDevice));
+        std::vector<smc_locus> dl(b.parts.size());
+        for (size_t k = 0; k < dl.size(); ++k) dl[k] = loci[b.parts[k].li];
+        PCHK(hipMemcpy(b.d_desc, dl.data(), b.desc_bytes, hipMemcpyHostToDevice));
+        if (b.reads > p->dom_reads) { p->dom_reads = b.reads; p->dom_loci = (int64_t)b.order.size(); p->dom_bin = n_bins; }
+        ++n_bins;
     }
-    *out = p;
+    *out = B.commit();
     return SMC_OK;
 }
 
@@ -505,132 +613,65 @@ int smc_plan_create_dev(smc_ctx* ctx, const smc_locus* d_loci, int64_t n_loci, v
     if (n_loci > 0x7fffffff) return fail(SMC_E_ARG, "smc_plan_create_dev: more than 2^31-1 loci in one batch");
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    smc_plan* p = new smc_plan();
-    p->ctx = ctx; p->n_loci = n_loci; p->own_loci = false; p->d_loci = const_cast<smc_locus*>(d_loci);
-    auto env_int = [](const char* name, int dflt) { const char* v = exp_env(name); return v && *v ? atoi(v) : dflt; };
-    PlanCfg C;
-    C.cls_reads[0] = SMC_R0; C.cls_reads[1] = SMC_R1; C.cls_reads[2] = SMC_R2; C.cls_reads[3] = SMC_R3;
-    C.deep_from = env_int("SMC_DEEP_FROM_READS", SMC_R3); C.max_reads = 1 << 24;
-    const int deep_fcap = std::max(8, env_int("SMC_DEEP_FCAP", SMC_DEEP_FCAP));
-    const int deep_ucap = std::min(32767, std::max(1, env_int("SMC_DEEP_UCAP", SMC_DEEP_UCAP)));
-    const int deep_part_reads = std::max(64, env_int("SMC_DEEP_PART_READS", SMC_DEEP_PART_READS));
-    C.deep_part_reads = deep_part_reads; C.deep_ucap = deep_ucap;
-    // every failure below goes through bail: the blocks the local bins hold by then are handed to the plan first, so that
-    // smc_plan_destroy returns them to the pool (ADVICE r3: the error paths used to leave them - and the plan - behind)
-    std::vector<Bin> bins(5);
-    auto bail = [&](int code, const std::string& msg) {
-        for (auto& b : bins) p->bins.push_back(b);
-        smc_plan_destroy(p);
-        return fail(code, msg);
-    };
-#define PCHK(x)                                                                                       \
-    do {                                                                                              \
-        hipError_t e_ = (x);                                                                          \
-        if (e_ != hipSuccess) return bail(SMC_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+    int deep_fcap;
+    const PlanCfg C = plan_cfg_from_env(deep_fcap);
+    PlanBuild B(ctx, n_loci);
+    smc_plan* p = B.p;
+    p->own_loci = false; p->d_loci = const_cast<smc_locus*>(d_loci);
     p->flt_bytes = sizeof(uint32_t) * 2 * ((size_t)n_loci + 2);   // two worklists, each [0] = count, then locus indices (runs alternate)
     hipError_t e = plan_alloc(ctx, (void**)&p->d_flt_list, p->flt_bytes);
-    if (e != hipSuccess) return bail(SMC_E_HIP, std::string("smc_plan_create_dev: ") + hipGetErrorString(e));
-    if (n_loci == 0) { *out = p; return SMC_OK; }
-    if (!ctx->plan_stats) {
-        PCHK(hipMalloc(&ctx->plan_stats, sizeof(PlanStats)));
-        PCHK(hipHostMalloc(&ctx->plan_stats_host, sizeof(PlanStats), hipHostMallocDefault));
-    }
-    if (ctx->plan_deep_cap < (size_t)n_loci) {
-        PCHK(hipStreamSynchronize(st));
-        (void)hipFree(ctx->plan_deep); ctx->plan_deep = nullptr; ctx->plan_deep_cap = 0;
-        PCHK(hipMalloc(&ctx->plan_deep, sizeof(PlanDeep) * (size_t)n_loci));
-        ctx->plan_deep_cap = (size_t)n_loci;
-    }
+    if (e != hipSuccess) return B.fail(SMC_E_HIP, std::string("smc_plan_create_dev: ") + hipGetErrorString(e));
+    if (n_loci == 0) { *out = B.commit(); return SMC_OK; }
+    if (int rc = plan_classify(B, d_loci, C, st)) return rc;
     PlanStats* d_st = (PlanStats*)ctx->plan_stats;
     PlanStats& S = *(PlanStats*)ctx->plan_stats_host;
-    const unsigned grid = (unsigned)((n_loci + PLAN_BLOCK - 1) / PLAN_BLOCK);
-    // (one record per context: a plan made on another stream waits for the plan before it to be through with it)
-    if (ctx->plan_fill_ev) PCHK(hipStreamWaitEvent(st, ctx->plan_fill_ev, 0));
-    if (!ctx->plan_stats_clean) PCHK(hipMemsetAsync(d_st, 0, sizeof(PlanStats), st));
-    ctx->plan_stats_clean = false;
-    hipLaunchKernelGGL(k_plan_classify, dim3(grid), dim3(PLAN_BLOCK), 0, st, d_loci, (int)n_loci, C, d_st, (PlanDeep*)ctx->plan_deep, p->d_flt_list);
-    PCHK(hipGetLastError());
     PCHK(hipMemcpyAsync(&S, d_st, sizeof(PlanStats), hipMemcpyDeviceToHost, st));
     PCHK(hipStreamSynchronize(st));
-    p->flt_clean = true;                                               // (k_plan_classify has zeroed both worklists' counts)
-    if (S.bad) return bail(SMC_E_INPUT, "smc_plan_create_dev: " + std::to_string(S.bad) + " loci violate the layout contract (alleles<=64, reads<2^24)");
+    if (S.bad) return B.fail(SMC_E_INPUT, "smc_plan_create_dev: " + std::to_string(S.bad) + " loci violate the layout contract (alleles<=64, reads<2^24)");
     if ((S.fp_or & S.fp_nor) != 0 || S.fp_or == 0)
-        return bail(SMC_E_INPUT, S.fp_or == 0 ? "smc_plan_create_dev: the loci carry no parameter fingerprint (smc_locus.flags bits 1-15)"
-                                             : "smc_plan_create_dev: loci built with different parameters in one batch (fingerprints differ)");
+        return B.fail(SMC_E_INPUT, S.fp_or == 0 ? "smc_plan_create_dev: the loci carry no parameter fingerprint (smc_locus.flags bits 1-15)"
+                                               : "smc_plan_create_dev: loci built with different parameters in one batch (fingerprints differ)");
     p->fp = (uint16_t)S.fp_or;
     p->need_quads = (int64_t)S.max_quad;
     PlanLists PL;
     memset(&PL, 0, sizeof PL);
     for (int c = 0; c < 4; ++c) {
-        Bin& b = bins[(size_t)c];
-        b.cls = c;
+        Bin& b = B.bins[c];
         if (!S.count[c]) continue;
         b.a_cap = (int)std::max<uint32_t>(8, S.maxa[c]);
         b.fcap = (int)S.maxq[c]; b.ucap = (int)std::max<uint32_t>(1, S.maxu[c]);
         b.reads = (int64_t)S.reads[c];
-        b.n_parts = S.count[c];
-        b.parts_bytes = sizeof(V2Part) * (size_t)S.count[c];
-        e = plan_alloc(ctx, (void**)&b.d_parts, b.parts_bytes);
-        if (e == hipSuccess) { b.desc_bytes = sizeof(smc_locus) * (size_t)S.count[c]; e = plan_alloc(ctx, (void**)&b.d_desc, b.desc_bytes); }
-        if (e != hipSuccess) return bail(SMC_E_HIP, std::string("smc_plan_create_dev: ") + hipGetErrorString(e));
+        if (int rc = bin_blocks(B, b, S.count[c])) return rc;
         PL.parts[c] = b.d_parts; PL.desc[c] = b.d_desc;
         uint32_t run = 0;
         for (int k = 0; k < PLAN_NB; ++k) { PL.base[c][k] = run; run += S.bucket[c][k]; }
     }
-    hipLaunchKernelGGL(k_plan_fill, dim3(grid), dim3(PLAN_BLOCK), 0, st, d_loci, (int)n_loci, C, d_st, PL);
+    hipLaunchKernelGGL(k_plan_fill, dim3((unsigned)((n_loci + PLAN_BLOCK - 1) / PLAN_BLOCK)), dim3(PLAN_BLOCK), 0, st, d_loci, (int)n_loci, C, d_st, PL);
     PCHK(hipGetLastError());
-    if (!ctx->plan_fill_ev) PCHK(hipEventCreateWithFlags(&ctx->plan_fill_ev, hipEventDisableTiming));
-    PCHK(hipEventRecord(ctx->plan_fill_ev, st));
-    ctx->plan_stats_clean = true;                                      // (its last workgroup zeroes the record)
+    if (int rc = plan_fill_launched(B, st)) return rc;
     // the deep class: its launch list is made on the device too (k_plan_deep), sized by what k_plan_classify has summed
     if (S.n_deep) {
-        Bin& b = bins[4];
-        b.cls = SMC_CLS_DEEP; b.fcap = deep_fcap; b.ucap = deep_ucap;
+        Bin& b = B.bins[SMC_CLS_DEEP];
+        b.fcap = deep_fcap; b.ucap = C.deep_ucap;
         b.a_cap = (int)std::max<uint32_t>(8, S.maxa[4]);
         b.reads = (int64_t)S.reads[4];
-        b.n_parts = S.deep_parts;
-        b.acc_bytes = (size_t)std::max<uint32_t>(1, S.deep_acc) * v2_acc_words(b.a_cap) * 4;
-        b.flags_bytes = (size_t)S.deep_fdw * 4;
-        b.foff_bytes = sizeof(int64_t) * (size_t)S.deep_parts;
-        b.parts_bytes = sizeof(V2Part) * (size_t)S.deep_parts;
-        b.desc_bytes = sizeof(smc_locus) * (size_t)S.deep_parts;
-        PCHK(plan_alloc(ctx, (void**)&b.d_acc, b.acc_bytes));
-        PCHK(plan_alloc(ctx, (void**)&b.d_flags, b.flags_bytes));
-        PCHK(plan_alloc(ctx, (void**)&b.d_flags_off, b.foff_bytes));
-        PCHK(plan_alloc(ctx, (void**)&b.d_parts, b.parts_bytes));
-        PCHK(plan_alloc(ctx, (void**)&b.d_desc, b.desc_bytes));
+        if (int rc = deep_bin_blocks(B, b, S.deep_parts, S.deep_acc, S.deep_fdw)) return rc;
         hipLaunchKernelGGL(k_plan_deep, dim3(1), dim3(1024), 0, st, (const PlanDeep*)ctx->plan_deep, S.n_deep, C, d_loci, b.d_parts, b.d_flags_off, b.d_desc);
         PCHK(hipGetLastError());
         PCHK(hipEventRecord(ctx->plan_fill_ev, st));                      // (the context's list of deep loci is free for the next plan only now)
     }
-    for (auto& b : bins) {
+    int n_bins = 0;                                                       // (a bin's place in the plan: classes without loci are left out)
+    for (const Bin& b : B.bins) {
         if (!b.n_parts) continue;
-        b.lds_bytes = (host_hdr_bytes(b.a_cap) + 4 * (size_t)b.fcap + 9 * (size_t)b.ucap + 32 + 255) & ~(size_t)255;
-        if (b.reads > p->dom_reads) { p->dom_reads = b.reads; p->dom_loci = b.cls < SMC_CLS_DEEP ? (int64_t)b.n_parts : (int64_t)S.n_deep; p->dom_bin = (int)p->bins.size(); }
-        p->bins.push_back(b);
-        b = Bin();                                                        // (handed over: bail must not give it twice)
+        if (b.reads > p->dom_reads) { p->dom_reads = b.reads; p->dom_loci = b.cls < SMC_CLS_DEEP ? (int64_t)b.n_parts : (int64_t)S.n_deep; p->dom_bin = n_bins; }
+        ++n_bins;
     }
-    PCHK(hipEventCreateWithFlags(&p->done_ev, hipEventDisableTiming));   // (k_plan_fill writes the lists: a plan destroyed unrun waits for it)
-    PCHK(hipEventRecord(p->done_ev, st));
-    *out = p;
+    if (int rc = plan_lists_launched(B, st)) return rc;                    // (k_plan_fill writes the lists: a plan destroyed unrun waits for it)
+    *out = B.commit();
     return SMC_OK;
-#undef PCHK
 }
 
 // ---- the plan without the host in the loop (k_plan.inc, second half)
-// LDS of a whole-locus workgroup of class c with these table sizes (as the bins of smc_plan_create_dev compute it)
-static size_t bin_lds_bytes(int a_cap, size_t fcap, size_t ucap) { return (host_hdr_bytes(a_cap) + 4 * fcap + 9 * ucap + 32 + 255) & ~(size_t)255; }
-static PlanCfg plan_cfg_from_env(int* deep_fcap) {
-    auto env_int = [](const char* name, int dflt) { const char* v = exp_env(name); return v && *v ? atoi(v) : dflt; };
-    PlanCfg C;
-    C.cls_reads[0] = SMC_R0; C.cls_reads[1] = SMC_R1; C.cls_reads[2] = SMC_R2; C.cls_reads[3] = SMC_R3;
-    C.deep_from = env_int("SMC_DEEP_FROM_READS", SMC_R3); C.max_reads = 1 << 24;
-    if (deep_fcap) *deep_fcap = std::max(8, env_int("SMC_DEEP_FCAP", SMC_DEEP_FCAP));
-    C.deep_ucap = std::min(32767, std::max(1, env_int("SMC_DEEP_UCAP", SMC_DEEP_UCAP)));
-    C.deep_part_reads = std::max(64, env_int("SMC_DEEP_PART_READS", SMC_DEEP_PART_READS));
-    return C;
-}
 int smc_plan_create_dev_spec(smc_ctx* ctx, const smc_params* prm, const smc_locus* d_loci, int64_t n_loci, void* stream, smc_plan** out) {
     if (!ctx || !prm || !out || (n_loci > 0 && !d_loci)) return fail(SMC_E_ARG, "smc_plan_create_dev_spec: NULL argument");
     if (n_loci > 0x7fffffff) return fail(SMC_E_ARG, "smc_plan_create_dev_spec: more than 2^31-1 loci in one batch");
@@ -647,8 +688,8 @@ int smc_plan_create_dev_spec(smc_ctx* ctx, const smc_params* prm, const smc_locu
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     const PlanStats& Hn = ctx->hint_stats;
-    int deep_fcap = SMC_DEEP_FCAP;
-    const PlanCfg C = plan_cfg_from_env(&deep_fcap);
+    int deep_fcap;
+    const PlanCfg C = plan_cfg_from_env(deep_fcap);
     // ---- what the launches are sized for: the last record, scaled to this batch's loci, with room
     PlanCaps K;
     memset(&K, 0, sizeof K);
@@ -679,96 +720,55 @@ int smc_plan_create_dev_spec(smc_ctx* ctx, const smc_params* prm, const smc_locu
         K.deep_fdw = grow(Hn.deep_fdw, 1.25, 4096);
         K.acap[4] = std::max<uint32_t>(8, Hn.maxa[4]);
     }
-    smc_plan* p = new smc_plan();
-    p->ctx = ctx; p->n_loci = n_loci; p->own_loci = false; p->d_loci = const_cast<smc_locus*>(d_loci);
+    PlanBuild B(ctx, n_loci);
+    smc_plan* p = B.p;
+    p->own_loci = false; p->d_loci = const_cast<smc_locus*>(d_loci);
     p->spec = true; p->caps = K; p->fp = (uint16_t)fp;
-    std::vector<Bin> bins(5);
-    auto bail = [&](int code, const std::string& msg) {
-        for (auto& b : bins) p->bins.push_back(b);
-        smc_plan_destroy(p);
-        return fail(code, msg);
-    };
-#define PCHK(x)                                                                                       \
-    do {                                                                                              \
-        hipError_t e_ = (x);                                                                          \
-        if (e_ != hipSuccess) return bail(SMC_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
     p->flt_bytes = sizeof(uint32_t) * 2 * ((size_t)n_loci + 2);
     PCHK(plan_alloc(ctx, (void**)&p->d_flt_list, p->flt_bytes));
     PCHK(plan_alloc(ctx, (void**)&p->d_spec, 256));
     if (!ctx->spec_host_free.empty()) { p->spec_host = ctx->spec_host_free.back(); ctx->spec_host_free.pop_back(); }
     else PCHK(hipHostMalloc(&p->spec_host, sizeof(PlanStats), hipHostMallocDefault));
     if (!ctx->d_spec_fail) { PCHK(hipMalloc((void**)&ctx->d_spec_fail, 256)); PCHK(hipMemsetAsync(ctx->d_spec_fail, 0, 256, st)); }
-    if (ctx->plan_deep_cap < (size_t)n_loci) {
-        PCHK(hipStreamSynchronize(st));
-        (void)hipFree(ctx->plan_deep); ctx->plan_deep = nullptr; ctx->plan_deep_cap = 0;
-        PCHK(hipMalloc(&ctx->plan_deep, sizeof(PlanDeep) * (size_t)n_loci));
-        ctx->plan_deep_cap = (size_t)n_loci;
-    }
-    PlanStats* d_st = (PlanStats*)ctx->plan_stats;                      // (allocated by the exact plan that came first)
-    const unsigned grid = (unsigned)((n_loci + PLAN_BLOCK - 1) / PLAN_BLOCK);
-    if (ctx->plan_fill_ev) PCHK(hipStreamWaitEvent(st, ctx->plan_fill_ev, 0));
-    if (!ctx->plan_stats_clean) PCHK(hipMemsetAsync(d_st, 0, sizeof(PlanStats), st));
-    ctx->plan_stats_clean = false;
-    hipLaunchKernelGGL(k_plan_classify, dim3(grid), dim3(PLAN_BLOCK), 0, st, d_loci, (int)n_loci, C, d_st, (PlanDeep*)ctx->plan_deep, p->d_flt_list);
-    PCHK(hipGetLastError());
+    if (int rc = plan_classify(B, d_loci, C, st)) return rc;
+    PlanStats* d_st = (PlanStats*)ctx->plan_stats;                      // (there since the exact plan that came first)
     PCHK(hipMemcpyAsync(p->spec_host, d_st, sizeof(PlanStats), hipMemcpyDeviceToHost, st));   // (for smc_plan_spec_ok; nobody waits for it here)
-    p->flt_clean = true;
     PlanLists PL;
     memset(&PL, 0, sizeof PL);
     for (int c = 0; c < 4; ++c) {
-        Bin& b = bins[(size_t)c];
-        b.cls = c;
+        Bin& b = B.bins[c];
         if (!K.count[c]) continue;
         b.a_cap = (int)K.acap[c]; b.fcap = (int)K.fcap[c]; b.ucap = (int)K.ucap[c];
         b.reads = (int64_t)((double)Hn.reads[c] * scale);
-        b.n_parts = K.count[c];
-        b.parts_bytes = sizeof(V2Part) * (size_t)K.count[c];
-        b.desc_bytes = sizeof(smc_locus) * (size_t)K.count[c];
-        PCHK(plan_alloc(ctx, (void**)&b.d_parts, b.parts_bytes));
-        PCHK(plan_alloc(ctx, (void**)&b.d_desc, b.desc_bytes));
+        if (int rc = bin_blocks(B, b, K.count[c])) return rc;
         b.d_launch_n = &p->d_spec->n[c];
         PL.parts[c] = b.d_parts; PL.desc[c] = b.d_desc;
     }
     if (K.n_deep) {
-        Bin& b = bins[4];
-        b.cls = SMC_CLS_DEEP; b.fcap = deep_fcap; b.ucap = C.deep_ucap;
+        Bin& b = B.bins[SMC_CLS_DEEP];
+        b.fcap = deep_fcap; b.ucap = C.deep_ucap;
         b.a_cap = (int)K.acap[4];
         b.reads = (int64_t)((double)Hn.reads[4] * scale);
-        b.n_parts = K.count[4];
-        b.acc_bytes = (size_t)std::max<uint32_t>(1, K.deep_acc) * v2_acc_words(b.a_cap) * 4;
-        b.flags_bytes = (size_t)K.deep_fdw * 4;
-        b.foff_bytes = sizeof(int64_t) * (size_t)K.count[4];
-        b.parts_bytes = sizeof(V2Part) * (size_t)K.count[4];
-        b.desc_bytes = sizeof(smc_locus) * (size_t)K.count[4];
-        PCHK(plan_alloc(ctx, (void**)&b.d_acc, b.acc_bytes));
-        PCHK(plan_alloc(ctx, (void**)&b.d_flags, b.flags_bytes));
-        PCHK(plan_alloc(ctx, (void**)&b.d_flags_off, b.foff_bytes));
-        PCHK(plan_alloc(ctx, (void**)&b.d_parts, b.parts_bytes));
-        PCHK(plan_alloc(ctx, (void**)&b.d_desc, b.desc_bytes));
+        if (int rc = deep_bin_blocks(B, b, K.count[4], K.deep_acc, K.deep_fdw)) return rc;
         b.d_launch_n = &p->d_spec->n[4];
         hipLaunchKernelGGL(k_plan_deep_spec, dim3(1), dim3(1024), 0, st, (const PlanDeep*)ctx->plan_deep, (const PlanStats*)d_st, K, C, d_loci, b.d_parts,
                            b.d_flags_off, b.d_desc);
         PCHK(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_plan_fill_spec, dim3(grid), dim3(PLAN_BLOCK), 0, st, d_loci, (int)n_loci, C, d_st, K, PL, p->d_spec, ctx->d_spec_fail);
+    hipLaunchKernelGGL(k_plan_fill_spec, dim3((unsigned)((n_loci + PLAN_BLOCK - 1) / PLAN_BLOCK)), dim3(PLAN_BLOCK), 0, st, d_loci, (int)n_loci, C, d_st, K, PL,
+                       p->d_spec, ctx->d_spec_fail);
     PCHK(hipGetLastError());
-    if (!ctx->plan_fill_ev) PCHK(hipEventCreateWithFlags(&ctx->plan_fill_ev, hipEventDisableTiming));
-    PCHK(hipEventRecord(ctx->plan_fill_ev, st));
-    ctx->plan_stats_clean = true;
-    for (auto& b : bins) {
+    if (int rc = plan_fill_launched(B, st)) return rc;
+    int n_bins = 0;
+    for (const Bin& b : B.bins) {
         if (!b.n_parts) continue;
-        b.lds_bytes = bin_lds_bytes(b.a_cap, (size_t)b.fcap, (size_t)b.ucap);
-        if (b.reads >= p->dom_reads) { p->dom_reads = b.reads; p->dom_loci = (int64_t)b.n_parts; p->dom_bin = (int)p->bins.size(); }
-        p->bins.push_back(b);
-        b = Bin();
+        if (b.reads >= p->dom_reads) { p->dom_reads = b.reads; p->dom_loci = (int64_t)b.n_parts; p->dom_bin = n_bins; }
+        ++n_bins;
     }
-    PCHK(hipEventCreateWithFlags(&p->done_ev, hipEventDisableTiming));
-    PCHK(hipEventRecord(p->done_ev, st));
+    if (int rc = plan_lists_launched(B, st)) return rc;
     ctx->spec_made++;
-    *out = p;
+    *out = B.commit();
     return SMC_OK;
-#undef PCHK
 }
 
 // After the plan's stream has been synchronised (the caller has waited for the rows): did the batch fit what the launches were sized
@@ -852,15 +852,7 @@ int smc_select_alignments_keyed(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t 
     const size_t o_off = carve(4 * ((size_t)n_blk + 1)), o_max = carve(4 * ((size_t)n_blk + 1)), o_diff = carve(4 * ((size_t)nl + 1));
     const size_t n_idw = renum ? (size_t)(n_bc + n_pair) : 0;
     const size_t o_rcnt = carve(renum ? 8 * ((size_t)n_blk + 1) : 0), o_rsum = carve(renum ? 16 : 0), o_first = carve(4 * n_idw), o_map = carve(4 * n_idw);
-    if (off > ctx->sel_bytes) {
-        HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(ctx->sel_scratch);
-        ctx->sel_scratch = nullptr; ctx->sel_bytes = 0;
-        const size_t want = off + off / 8;
-        hipError_t e = hipMalloc(&ctx->sel_scratch, want);
-        if (e != hipSuccess) return fail(SMC_E_HIP, "smc_select_alignments: " + std::to_string(want) + " bytes of scratch: " + hipGetErrorString(e));
-        ctx->sel_bytes = want;
-    }
+    if (int rc = grow_scratch(ctx->sel_scratch, ctx->sel_bytes, off, off + off / 8, "smc_select_alignments", &st)) return rc;
     char* sc = (char*)ctx->sel_scratch;
     uint32_t* blk_off = (uint32_t*)(sc + o_off);
     int32_t* blk_max = (int32_t*)(sc + o_max);
@@ -1036,14 +1028,8 @@ int smc_lod_table(smc_ctx* ctx, int needed, int max_depth, double* roots, int32_
         return fail(SMC_E_INPUT, "smc_lod_table: max_depth = " + std::to_string(max_depth) + " outside 0 .. " + std::to_string(SMC_LOD_MAX_DEPTH));
     HIPCHK(hipSetDevice(ctx->device));
     const size_t n = (size_t)max_depth + 1, o_iters = (8 * n + 255) & ~(size_t)255, bytes = o_iters + 4 * n;
-    if (bytes > ctx->lod_bytes) {
-        (void)hipFree(ctx->lod_scratch);                  // (synchronises the device: no table kernel is in flight - the entry waits for its own)
-        ctx->lod_scratch = nullptr; ctx->lod_bytes = 0;
-        const size_t want = bytes + bytes / 8;
-        hipError_t e = hipMalloc(&ctx->lod_scratch, want);
-        if (e != hipSuccess) return fail(SMC_E_HIP, "smc_lod_table: " + std::to_string(want) + " bytes of scratch: " + hipGetErrorString(e));
-        ctx->lod_bytes = want;
-    }
+    // (no stream to wait for: no table kernel is in flight - the entry waits for its own)
+    if (int rc = grow_scratch(ctx->lod_scratch, ctx->lod_bytes, bytes, bytes + bytes / 8, "smc_lod_table", nullptr)) return rc;
     double* d_roots = (double*)ctx->lod_scratch;
     int32_t* d_iters = (int32_t*)((char*)ctx->lod_scratch + o_iters);
     hipLaunchKernelGGL(k_lod_table, dim3((unsigned)((n + LOD_BLOCK - 1) / LOD_BLOCK)), dim3(LOD_BLOCK), 0, 0, needed, max_depth, d_roots, d_iters);
@@ -1054,15 +1040,7 @@ int smc_lod_table(smc_ctx* ctx, int needed, int max_depth, double* roots, int32_
 }
 
 // ---- checking entries: the Fisher tests' device arithmetic on arguments of the caller's choice (k_filter_loci.inc, its end)
-static int chk_scratch(smc_ctx* ctx, const char* who, size_t bytes) {
-    if (bytes <= ctx->chk_bytes) return SMC_OK;
-    (void)hipFree(ctx->chk_scratch);                      // (synchronises the device; the entries wait for their own kernels)
-    ctx->chk_scratch = nullptr; ctx->chk_bytes = 0;
-    hipError_t e = hipMalloc(&ctx->chk_scratch, bytes);
-    if (e != hipSuccess) return fail(SMC_E_HIP, std::string(who) + ": " + std::to_string(bytes) + " bytes of scratch: " + hipGetErrorString(e));
-    ctx->chk_bytes = bytes;
-    return SMC_OK;
-}
+// (their scratch grows to exactly what a call needs; the entries wait for their own kernels)
 #define SMC_CHK_MAX_N ((int64_t)1 << 24)
 int smc_fisher_tables(smc_ctx* ctx, const int64_t* tables, int64_t n, double* oddsratio, double* pvalue) {
     if (!ctx || n < 0) return fail(SMC_E_ARG, "smc_fisher_tables: bad argument");
@@ -1080,7 +1058,7 @@ int smc_fisher_tables(smc_ctx* ctx, const int64_t* tables, int64_t n, double* od
     }
     HIPCHK(hipSetDevice(ctx->device));
     const size_t N = (size_t)n;
-    if (int rc = chk_scratch(ctx, "smc_fisher_tables", 48 * N)) return rc;
+    if (int rc = grow_scratch(ctx->chk_scratch, ctx->chk_bytes, 48 * N, 48 * N, "smc_fisher_tables", nullptr)) return rc;
     long long* d_tab = (long long*)ctx->chk_scratch;
     double* d_or = (double*)((char*)ctx->chk_scratch + 32 * N);
     double* d_p = d_or + N;
@@ -1100,7 +1078,7 @@ int smc_lfact_values(smc_ctx* ctx, const int64_t* n_values, int64_t n, double* o
     if (n > SMC_CHK_MAX_N) return fail(SMC_E_ARG, "smc_lfact_values: more than 2^24 values in one call");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t N = (size_t)n;
-    if (int rc = chk_scratch(ctx, "smc_lfact_values", 16 * N)) return rc;
+    if (int rc = grow_scratch(ctx->chk_scratch, ctx->chk_bytes, 16 * N, 16 * N, "smc_lfact_values", nullptr)) return rc;
     long long* d_v = (long long*)ctx->chk_scratch;
     double* d_out = (double*)ctx->chk_scratch + N;
     HIPCHK(hipMemcpy(d_v, n_values, 8 * N, hipMemcpyHostToDevice));
@@ -1134,14 +1112,8 @@ int smc_allele_carriers(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, c
     const size_t n_cnt = 2 * (size_t)n_bc * (size_t)n_var;
     if (n_cnt >= (size_t)0xFFFFFF00) return fail(SMC_E_INPUT, "smc_allele_carriers: " + std::to_string(n_var) + " variants x " + std::to_string(n_bc) + " barcodes: too many counters for one call");
     if (!d_counts) {
-        if (4 * n_cnt > ctx->af_bytes) {
-            (void)hipFree(ctx->af_scratch);               // (synchronises the device: no earlier call's kernels are in flight)
-            ctx->af_scratch = nullptr; ctx->af_bytes = 0;
-            const size_t want = 4 * n_cnt + n_cnt / 2 + 256;
-            hipError_t e = hipMalloc(&ctx->af_scratch, want);
-            if (e != hipSuccess) return fail(SMC_E_HIP, "smc_allele_carriers: " + std::to_string(want) + " bytes of scratch: " + hipGetErrorString(e));
-            ctx->af_bytes = want;
-        }
+        // (no stream to wait for: freeing the old block synchronises the device - no earlier call's kernels are in flight)
+        if (int rc = grow_scratch(ctx->af_scratch, ctx->af_bytes, 4 * n_cnt, 4 * n_cnt + n_cnt / 2 + 256, "smc_allele_carriers", nullptr)) return rc;
         d_counts = (uint32_t*)ctx->af_scratch;
     }
     const uint32_t n_words64 = (uint32_t)((n_bc + 63) / 64);
@@ -1833,15 +1805,7 @@ static int build_planes_impl(smc_ctx* ctx, const smc_params* prm, const smc_buil
     const size_t o_xcnt = carve(4 * (size_t)n_loci), o_tcnt = carve(4 * ((size_t)n_tiles + 1)), o_tcur = carve(4 * (size_t)n_tiles), o_xn = carve(4);
     const size_t o_zend = off;
     const size_t o_xraw = carve(4 * BP_XW * (size_t)xraw_cap), o_gidx = carve(4 * ((size_t)xraw_cap + 4)), o_gidx2 = carve(4 * ((size_t)xraw_cap + 4));
-    if (off > ctx->bp_bytes) {
-        HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(ctx->bp_scratch);
-        ctx->bp_scratch = nullptr; ctx->bp_bytes = 0;
-        const size_t want = off + off / 8;
-        hipError_t e = hipMalloc(&ctx->bp_scratch, want);
-        if (e != hipSuccess) return fail(SMC_E_HIP, "smc_build_planes: " + std::to_string(want) + " bytes of scratch: " + hipGetErrorString(e));
-        ctx->bp_bytes = want;
-    }
+    if (int rc = grow_scratch(ctx->bp_scratch, ctx->bp_bytes, off, off + off / 8, "smc_build_planes", &st)) return rc;
     char* sc = (char*)ctx->bp_scratch;
     // one scratch per context: a build issued on another stream than the one before waits for that one's last kernel (ADVICE r4)
     if (ctx->bp_done_ev) HIPCHK(hipStreamWaitEvent(st, ctx->bp_done_ev, 0));

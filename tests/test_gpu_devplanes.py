@@ -586,6 +586,88 @@ def test_plans_made_without_the_host_fit_or_say_so(engine0):
         eng.close()
 
 
+def _words_batch(eng, name, n):
+    """A synthetic batch as the plans of these tests take it: (descriptors, parameters, [read words, umi_start], the host-made plan's
+    row bytes)."""
+    import torch
+    from smcounter_amd import synth
+    cfg = synth.CONFIGS[name]
+    P = synth.params_for(cfg)
+    db = synth.generate_native(cfg, 0, n, P)
+    raw = eng.upload(db)
+    ph = eng.make_plan(db.loci)
+    want = ph.download(ph.run(raw, P)).tobytes()
+    words = ph.pack_words(raw[0], raw[2], torch.empty_like(raw[0]))
+    torch.cuda.synchronize()
+    ph.close()
+    return db.loci, P, [words, raw[4]], want
+
+
+def test_the_three_plan_creators_refuse_a_bad_batch_and_leave_the_context_usable():
+    """Descriptors without a parameter fingerprint, or with two different ones: smc_plan_create, smc_plan_create_dev and
+    smc_plan_create_dev_spec (a context without a hint: the exact way) say so - and what they had taken by then goes back to the
+    context: a plan of the good batch made the same way right afterwards gives the host-made plan's row bytes."""
+    from smcounter_amd import _lib, devplanes
+    from smcounter_amd.engine import Engine
+    eng = Engine(0)                                              # (a context of its own: no hint, and its pool is what is at stake)
+    try:
+        loci, P, planes, want = _words_batch(eng, "C2", 64)
+        fp_mask = np.array(0x7FFF << features.LF_FP_SHIFT, loci["flags"].dtype)
+        no_fp = loci.copy()
+        no_fp["flags"] &= ~fp_mask
+        two_fp = loci.copy()
+        fp = (int(loci["flags"][1]) >> features.LF_FP_SHIFT) & 0x7FFF
+        two_fp["flags"][1] = (int(loci["flags"][1]) & ~int(fp_mask)) | ((fp % 0x7FFF + 1) << features.LF_FP_SHIFT)
+        assert fp != 0 and not (no_fp["flags"] & fp_mask).any()
+
+        def make(how, desc):
+            """-> (plan, what has to outlive it)"""
+            if how == "host":
+                return eng.make_plan(desc), None
+            d = devplanes.DevLoci(eng, desc)
+            try:
+                return eng.make_plan_dev(d, len(desc), spec_params=P if how == "spec" else None), d
+            except Exception:
+                d.free()
+                raise
+
+        def good_rows(how):
+            plan, d = make(how, loci)
+            got = plan.download(plan.run(planes, P)).tobytes()
+            plan.close()
+            if d is not None:
+                d.free()
+            return got
+
+        for how, bad, msg in (("host", no_fp, "no parameter fingerprint"), ("dev", no_fp, "no parameter fingerprint"),
+                              ("spec", no_fp, "no parameter fingerprint"), ("host", two_fp, "fingerprints differ"),
+                              ("dev", two_fp, "fingerprints differ")):
+            with pytest.raises(_lib.SmcError, match=msg):
+                make(how, bad)
+            assert good_rows(how) == want, (how, msg)
+    finally:
+        eng.close()
+
+
+def test_host_made_and_device_made_plans_report_the_same_shape(engine0, monkeypatch):
+    """Small loci put in the deep class with several parts each (the geometry of test_gpu_parity's deep-class test): smc_plan_create
+    and smc_plan_create_dev size the same launches and the same scratch (smc_plan_info), and the rows are byte-equal."""
+    from smcounter_amd import devplanes
+    for k, v in (("SMC_EXPERIMENTAL", "1"), ("SMC_DEEP_FROM_READS", "100"), ("SMC_DEEP_PART_READS", "64"), ("SMC_DEEP_FCAP", "16")):
+        monkeypatch.setenv(k, v)
+    loci, P, planes, want = _words_batch(engine0, "C3", 300)
+    d_loci = devplanes.DevLoci(engine0, loci)
+    p_host, p_dev = engine0.make_plan(loci), engine0.make_plan_dev(d_loci, len(loci))
+    i_host, i_dev = p_host.info(), p_dev.info()
+    r_host = p_host.download(p_host.run(planes, P)).tobytes()
+    r_dev = p_dev.download(p_dev.run(planes, P)).tobytes()
+    p_host.close(); p_dev.close(); d_loci.free()
+    print("plan.info(): host-made %r, device-made %r" % (i_host, i_dev))
+    assert i_host[0] == 2 and i_host[1] > 0                      # (one k_call_v2 launch - the deep class - and the filter kernel)
+    assert i_host == i_dev
+    assert r_host == r_dev == want
+
+
 def test_the_non_parity_sampler_on_the_device_equals_its_restatement(engine0):
     """smc_philox_marks (the Philox4x32-10 down-sampling SURVEY.md a4 allows as a non-parity mode) against oracle/smc_oracle.c's
     restatement on a batch whose loci are over the barcode cap: the same marks in umi_start, SMC_LF_SAMPLED set, and the rows of the

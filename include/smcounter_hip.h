@@ -637,6 +637,20 @@ int smc_spike_alleles_reps(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln
 int smc_spike_rep_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_cnt, const uint32_t* d_cov_off,
                          const uint32_t* cov_off_host, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
                          const uint64_t* thr, int32_t n_targets, uint32_t* d_out, void* stream);
+/* (ABI 11, additive: one entry more, the version number unchanged) --spikeDepth: the cells (target t, barcode fraction f) of the
+ * --spikeAF spike-in.  Cell (t, f) of replicate j is the spike-in at t drawn with seeds[j], of which the barcodes stay that
+ * smc_select_alignments' philox rule keeps at f with the same seed: keep = word 0 of Philox4x32-10(counter = (identity lo, identity
+ * hi, 0x64734D54 "dsMT", 0), key = (seeds[j] lo, hi)) < depth_thr[f].  `depth_thr`: HOST memory, n_fracs words, floor(f * 2^32) each
+ * and 2^32 at f = 1; the other arguments are smc_spike_rep_counts'.  With hit = u_v(b; seeds[j]) < thr[t] as there:
+ *   d_out[v][j][t][f][5] uint32 = (N': the covering b with keep, V0': those with 2 * alt0[b] > reads[b], S': those with hit, READS':
+ *   the sum of single[b] over the b with keep and hit, V1': the b with keep and 2 * (hit ? single[b] : alt0[b]) > reads[b]).
+ * Two draws per (b, v, j) serve every cell; the depth draw is not made when no threshold is below 2^32, and at one fraction of 2^32
+ * (S', READS', V1') are smc_spike_rep_counts' numbers.  d_out is zeroed by the call.
+ * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched and nothing zeroed: what smc_spike_rep_counts refuses, a depth
+ * threshold above 2^32, n_fracs below 1, n_targets * n_fracs above SMC_AF_DEPTH_MAX_CELLS, an output of 2^32 - 256 words or more. */
+int smc_spike_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_cnt, const uint32_t* d_cov_off,
+                           const uint32_t* cov_off_host, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
+                           const uint64_t* thr, int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

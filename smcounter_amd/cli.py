@@ -165,6 +165,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "detection rate and its Wilson score interval (95 %%%%), the achieved fractions, and with --lod the locus's "
                         "LOD, and <outPrefix>.spikeAF.curve.txt, one line per variant: the rate at every target and T95, the smallest "
                         "target found in 95 %%%% of the replicates together with every larger one.  Needs --spikeAF" % (REPS_MIN, REPS_MAX))
+    p.add_argument("--spikeDepth", default=None,
+                   help="the spike-ins of --spikeAF at several barcode depths: comma-separated fractions f in (0, 1].  For every target t "
+                        "and every f the run is also called on the CELL (t, f): the spike-in at t, of which a barcode stays when the "
+                        "--dsMT --dsSampler philox draw keeps it at f (two independent draws, both keyed by --dsSeed) - the .dsMT<f> "
+                        "output of a --dsMT f --dsSampler philox run on the BAM tools/spike_variants.py --af t writes, at the mtDepth "
+                        "--dsMT f would get from that target's mtDepth (max(1, round(f x mtDepth))); written to "
+                        "<outPrefix>.spikeAF<t>.dsMT<f>.smCounter.{all,cut}.txt and .cut.vcf (with --lod: its LOD files and summary line), "
+                        "and, one line per variant and cell, <outPrefix>.spikeAF.depth.detection.txt.  With --spikeReps the cells are "
+                        "replicated as the targets are: <outPrefix>.spikeAF.depth.replicates.txt, .spikeAF.depth.sensitivity.txt and "
+                        ".spikeAF.depth.curve.txt (per variant and depth the detection rate at every target and T95).  What the cells "
+                        "achieve is counted on the GPU in one call; at most %d cells.  Needs --spikeAF" % GRID_MAX_CELLS)
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -320,11 +331,11 @@ class _Output:
     its reads per barcode).  Output 0 of a run is the full-depth one; every other has a `rule`, once the rule makers below have run."""
     prefix: str
     params: VcParams
-    kind: str = "full"          # full, dsMT, dsRpb, dsGrid, dsAF, dsAFDepth or spikeAF
-    frac: float = None          # (dsMT, dsGrid, dsAFDepth) the fraction of the barcodes
+    kind: str = "full"          # full, dsMT, dsRpb, dsGrid, dsAF, dsAFDepth, spikeAF or spikeDepth
+    frac: float = None          # (dsMT, dsGrid, dsAFDepth, spikeDepth) the fraction of the barcodes
     target: float = None        # (dsRpb, dsGrid) the reads per barcode asked for
-    af: float = None            # (dsAF, dsAFDepth, spikeAF) the target allele fraction
-    af_index: int = None        # (dsAFDepth) which --dsAF target the cell belongs to
+    af: float = None            # (dsAF, dsAFDepth, spikeAF, spikeDepth) the target allele fraction
+    af_index: int = None        # (dsAFDepth, spikeDepth) which --dsAF / --spikeAF target the cell belongs to
     rule: object = None         # the devplanes.DsRule that selects it; None: full depth
 
 
@@ -341,6 +352,7 @@ class _Plan:
     depth: dict = None          # (--dsAFDepth) "fracs", the cells' "params", and once the rules are made "rules" and "counts" [V, T, F, 2]
     spike: dict = None          # (--spikeAF) once the rules are made: "variants", and "res", the pre-pass's numbers per target
     spike_reps: int = None      # (--spikeReps) R; plan.spike then holds "keep", what the pre-pass kept (None once the stage has taken it)
+    spike_depth: dict = None    # (--spikeDepth) "fracs", the cells' "params", and once the rules are made "rules" and "counts" [V][T x F]
 
     @property
     def rules(self):
@@ -373,14 +385,16 @@ def ds_af_rules(args, outs, variants, early, keep=None, depth=None):
     return rules, res
 
 
-def spike_rules(args, outs, variants, early, keep=None):
+def spike_rules(args, outs, variants, early, keep=None, depth=None):
     """The devplanes.DsRule of every --spikeAF output (the pre-pass on the GPU: devplanes.spike_rules) and its numbers; the run log
-    gets a line per variant and target.  `keep` (--spikeReps): a dict for what the replicate stage starts from."""
+    gets a line per variant and target.  `keep` (--spikeReps): a dict for what the replicate stage starts from.  `depth`
+    (--spikeDepth): the plan's dict; it gets the cells' rules and counts."""
     from .tools import spike_variants as sv
     eng = _engine_of(args, early)
+    more = {k: v for k, v in (("keep", keep), ("depth", depth)) if v is not None}
     try:
         rules, res = devplanes.spike_rules(args.bamFile, fasta.FastaFile(args.refGenome), variants, [o.af for o in outs],
-                                           [o.params for o in outs], int(args.dsSeed), eng, **({"keep": keep} if keep is not None else {}))
+                                           [o.params for o in outs], int(args.dsSeed), eng, **more)
     except (ValueError, bamio.BamError) as e:
         raise SystemExit(str(e))
     for r in res:
@@ -574,11 +588,13 @@ def _ds_af_replicates(args, plan, ref, eng, loci, ds_rows):
 def _spike_replicates(args, plan, ref, eng, loci, ds_rows):
     """--spikeReps after the run's batches: devplanes.spike_replicates over the runs the pre-pass kept, and the check that ties it to
     the run's own outputs - replicate 0 has the seed of the run, so its row at every listed locus must be the .spikeAF<t> output's."""
-    variants, outs = plan.spike["variants"], plan.outputs[1:]
+    # (the run's outputs behind the first: the targets, then with --spikeDepth their cells - the order of the stage's rows)
+    variants, outs, targets = plan.spike["variants"], plan.outputs[1:], [o for o in plan.outputs if o.kind == "spikeAF"]
     keep, plan.spike["keep"] = plan.spike["keep"], None      # (the stage frees the kept runs itself, whatever happens in it)
-    out = devplanes.spike_replicates(args.bamFile, ref, variants, [o.af for o in outs], [o.params for o in outs], int(args.dsSeed),
+    more = {"depth": plan.spike_depth} if plan.spike_depth is not None else {}
+    out = devplanes.spike_replicates(args.bamFile, ref, variants, [o.af for o in targets], [o.params for o in targets], int(args.dsSeed),
                                      plan.spike_reps, eng, keep, sampler=getattr(args, "sampler", "reference"),
-                                     sampler_seed=getattr(args, "samplerSeed", 0))
+                                     sampler_seed=getattr(args, "samplerSeed", 0), **more)
     index = {(c, int(p)): n for n, (c, p) in enumerate(loci)}
     for (k, t, j), line in out["rows"].items():
         v = variants[k]
@@ -711,6 +727,7 @@ def _main(args) -> int:
     af_fracs, af_cells = ds_af_depth_cells(args, af_targets)
     from . import spike as _spike
     spike_targets = _spike.targets(args)
+    spike_fracs, spike_cells = _spike.depth_cells(args, spike_targets)
     at = lambda **kw: dataclasses.replace(params, **kw)
     plan = _Plan([_Output(args.outPrefix, params)] +
                  [_Output(p, at(mtDepth=d), "dsMT", frac=f) for f, d, p in fractions] +
@@ -718,8 +735,11 @@ def _main(args) -> int:
                  [_Output(p, at(mtDepth=d, rpb=r), "dsGrid", frac=f, target=r) for f, r, d, p in cells] +
                  [_Output(p, at(mtDepth=d), "dsAF", af=t) for t, d, p in af_targets] +
                  [_Output(p, at(mtDepth=d), "dsAFDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in af_cells] +
-                 [_Output(p, at(mtDepth=d), "spikeAF", af=t) for t, d, p in spike_targets],
+                 [_Output(p, at(mtDepth=d), "spikeAF", af=t) for t, d, p in spike_targets] +
+                 [_Output(p, at(mtDepth=d), "spikeDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in spike_cells],
                  reps=ds_af_reps(args, af_targets), spike_reps=_spike.reps(args, spike_targets))
+    if spike_fracs is not None:
+        plan.spike_depth = dict(fracs=spike_fracs, params=[o.params for o in plan.outputs if o.kind == "spikeDepth"])
     if af_fracs is not None:
         plan.depth = dict(fracs=af_fracs, params=[o.params for o in plan.outputs if o.kind == "dsAFDepth"])
     flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets), ("--dsAF", af_targets), ("--spikeAF", spike_targets)) if on)
@@ -797,8 +817,10 @@ def _make_rules(args, plan, loc_list):
         from . import spike as _spike
         variants = _spike.variants(args, loc_list, fasta.FastaFile(args.refGenome))
         keep = {} if plan.spike_reps is not None else None
-        rules, res = spike_rules(args, sp, variants, plan.early, keep)
+        rules, res = spike_rules(args, sp, variants, plan.early, keep, plan.spike_depth)
         put(sp, rules)
+        if plan.spike_depth is not None:
+            put([o for o in plan.outputs if o.kind == "spikeDepth"], plan.spike_depth["rules"])
         plan.spike = dict(variants=variants, res=res, keep=keep)
 
 
@@ -920,10 +942,19 @@ def _af_reports(args, plan, shard, loc_list, repeats):
           (tm["stage"], plan.reps, over, tm["builds"], tm["batches"], tm["counts"], tm["masks"]))
 
 
+def _spike_cells(plan, lods):
+    """(--spikeDepth) per cell (target index, target, fraction, mtDepth, output prefix, that output's LODs or None), as spike's depth
+    pages take them; the cells' outputs lie behind the targets'."""
+    first = next(k for k, o in enumerate(plan.outputs) if o.kind == "spikeDepth")
+    return [(o.af_index, o.af, o.frac, o.params.mtDepth, o.prefix, lods[first + c]["lods"] if lods is not None else None)
+            for c, o in enumerate(plan.outputs[first:])]
+
+
 def _spike_reports(args, plan, shard, loc_index, repeats):
     """--spikeReps: every replicate's row as its own run would print and cut it, then the rates and the curve."""
     from . import dsaf, spike as _spike
-    variants, res, outs, reps, lods = plan.spike["variants"], plan.spike["res"], plan.outputs[1:], shard.spike_reps, shard.lod
+    variants, res, reps, lods = plan.spike["variants"], plan.spike["res"], shard.spike_reps, shard.lod
+    outs = [o for o in plan.outputs if o.kind == "spikeAF"]
     targets, R = [o.af for o in outs], plan.spike_reps
     entries = {}
     for i, v in enumerate(variants):
@@ -941,6 +972,24 @@ def _spike_reports(args, plan, shard, loc_index, repeats):
     lod_vt = None if lods is None else [[float(l["lods"][loc_index[(v.chrom, "%d" % v.pos)]]) for v in variants] for l in lods[1:1 + len(outs)]]
     _spike.write_sensitivity(args.outPrefix, variants, targets, entries, lod_vt)
     _spike.write_curve(args.outPrefix, variants, targets, entries, lod_vt)
+    if plan.spike_depth is not None:
+        # (--spikeDepth: the same three pages over the cells; their rows stand behind the targets' in the stage's)
+        cells, T, dc = _spike_cells(plan, lods), len(outs), reps["depth_counts"]
+        cell_entries = {}
+        for i, v in enumerate(variants):
+            for c, o in enumerate(o for o in plan.outputs if o.kind == "spikeDepth"):
+                thr_c = writers.pi_threshold(o.params.mtDepth, args.threshold)
+                per = []
+                for j in range(R):
+                    row, cut = dsaf.replicate_entry(reps["rows"].get((i, T + c, j)), thr_c, *repeats)
+                    per.append((dict(zip(("N", "V0", "S", "READS", "V1"), (int(x) for x in dc[i, j].reshape(-1, 5)[c]))), row, cut))
+                cell_entries[(i, c)] = per
+                print("--spikeReps: %s:%d %s>%s at %g x fraction %g: called %d of %d" % (v.chrom, v.pos, v.ref, v.alt, o.af, o.frac,
+                                                                                         _spike._called(v, per), R))
+        _spike.write_depth_replicates(args.outPrefix, variants, cells, reps["seeds"], cell_entries)
+        _spike.write_depth_sensitivity(args.outPrefix, variants, cells, cell_entries, loc_index)
+        full = [(o.params.mtDepth, lods[1 + t]["lods"] if lods is not None else None) for t, o in enumerate(outs)]
+        _spike.write_depth_curve(args.outPrefix, variants, targets, plan.spike_depth["fracs"], full, cells, entries, cell_entries, loc_index)
     tm = reps["times"]
     print("--spikeReps: replicate stage %.3f s (%d replicates x %d targets: counts call %.4f s, %d rewrite calls, %d builds in %d batches, "
           "%.3f s)" % (tm["stage"], R, len(outs), tm["counts"], tm["rewrites"], tm["builds"], tm["batches"], tm["calls"]))
@@ -987,6 +1036,8 @@ def _run(args, plan, loc_list, t0):
                 for k, (o, r) in enumerate(zip(plan.outputs, [None] + list(plan.spike["res"])))]
         loc_index = {(c, "%d" % int(q)): n for n, (c, q) in enumerate(loc_list)}
         _spike.write_detection(args.outPrefix, plan.spike["variants"], outs, loc_index)
+        if plan.spike_depth is not None:
+            _spike.write_depth_detection(args.outPrefix, plan.spike["variants"], _spike_cells(plan, lods), plan.spike_depth["counts"], loc_index)
         if shard.spike_reps is not None:
             _spike_reports(args, plan, shard, loc_index, repeats)
     t1 = datetime.datetime.now()

@@ -1255,6 +1255,61 @@ int smc_spike_rep_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32
     return SMC_OK;
 }
 
+// (--spikeDepth) (N', V0', S', READS', V1') of every listed variant, replicate and cell (target x barcode fraction): the counters
+// zeroed, then k_spike_depth_counts.  The checks are smc_spike_rep_counts' and, for the fractions, afd_check_table's.
+int smc_spike_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_cnt, const uint32_t* d_cov_off,
+                           const uint32_t* cov_off_host, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
+                           const uint64_t* thr, int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream) {
+    const std::string who = "smc_spike_depth_counts";
+    if (!ctx || n_var < 0 || n_reps < 0 || n_targets < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
+    if (n_targets > SMC_SPIKE_REP_MAX_TARGETS)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_SPIKE_REP_MAX_TARGETS));
+    if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
+    if (n_fracs < 1) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_fracs) + " fractions, at least 1 expected");
+    if ((n_reps && !d_seeds) || (n_targets && !thr) || !depth_thr) return fail(SMC_E_ARG, who + ": NULL argument");
+    if ((int64_t)n_targets * (int64_t)n_fracs > SMC_AF_DEPTH_MAX_CELLS)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets x " + std::to_string(n_fracs) + " fractions, at most " +
+                                 std::to_string(SMC_AF_DEPTH_MAX_CELLS) + " cells");
+    SpkThr T;
+    AfdThr D;
+    memset(&T, 0, sizeof T);
+    memset(&D, 0, sizeof D);
+    for (int32_t t = 0; t < n_targets; ++t) {
+        if (thr[t] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": target " + std::to_string(t) + ": a threshold above 2^32");
+        T.t[t] = thr[t];
+    }
+    int with_depth = 0;
+    for (int32_t f = 0; f < n_fracs; ++f) {
+        if (depth_thr[f] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": depth threshold " + std::to_string(f) + " is above 2^32");
+        D.f[f] = depth_thr[f];
+        with_depth |= depth_thr[f] < (1ull << 32);
+    }
+    if ((double)n_var * (double)n_reps * (double)n_targets * (double)n_fracs * (double)SPD_COUNTERS >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants x " + std::to_string(n_reps) + " replicates x " +
+                                 std::to_string(n_targets) + " targets x " + std::to_string(n_fracs) + " fractions: too many counters for one call");
+    if (!n_var || !n_reps || !n_targets) return SMC_OK;
+    if (!cov_off_host || !d_cov_off || !d_pos1 || !d_out) return fail(SMC_E_ARG, who + ": NULL argument");
+    uint32_t widest = 0;
+    for (int32_t v = 0; v < n_var; ++v) {
+        if (cov_off_host[v + 1] < cov_off_host[v]) return fail(SMC_E_INPUT, who + ": the offsets decrease at variant " + std::to_string(v));
+        widest = std::max(widest, cov_off_host[v + 1] - cov_off_host[v]);
+    }
+    if (cov_off_host[n_var] >= 0x55555500u) return fail(SMC_E_INPUT, who + ": too many covering barcodes for one call");
+    if (cov_off_host[n_var] && (!d_cov_ident || !d_cov_cnt)) return fail(SMC_E_ARG, who + ": NULL covers");
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t n_out = (size_t)SPD_COUNTERS * (size_t)n_var * (size_t)n_reps * (size_t)n_targets * (size_t)n_fracs;
+    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
+    if (widest)
+        hipLaunchKernelGGL(k_spike_depth_counts, dim3((unsigned)std::min<uint32_t>((widest + SPR_BLOCK - 1) / SPR_BLOCK, 256u), (unsigned)n_var,
+                                                      (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPR_BLOCK), 0, st,
+                           (const unsigned long long*)d_cov_ident, d_cov_cnt, d_cov_off, d_pos1, T, (int)n_targets, D, (int)n_fracs, with_depth,
+                           (const unsigned long long*)d_seeds, (int)n_reps, d_out);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
 // (--dsAFReps, --dsAFDepth) what the four entries check of the carrier table, on its host copy, and of the fractions' thresholds
 // (host memory), which go into the kernels' argument -> `with_depth`: a fraction is below 2^32, so the depth draw decides something
 static int afd_check_table(const std::string& w, const uint64_t* d_car, const uint64_t* d_car_thr, const uint64_t* car_host,

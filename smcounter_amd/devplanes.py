@@ -369,6 +369,13 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
     idents = names = p_idents = p_names = mism = None
     d_masks = {}                     # (philox read rules) (id(table), grid) -> (device masks of those rules, words per mask, id(rule) -> index)
     d_cells = None                   # (--dsAFDepth) (device masks of every cell of this run, words per mask)
+    # (--spikeAF, --spikeDepth) a target's spiked copy of this run (None: no record spans a listed position) and the builds that still
+    # need it - the target's own and those of its cells
+    spiked_of = {}
+    users = {}
+    for rule in rules:
+        if rule.spike is not None:
+            users[(id(rule.spike), rule.af)] = users.get((id(rule.spike), rule.af), 0) + 1
     try:
         for rule, d in zip(rules, ds):
             if not nl:
@@ -378,14 +385,25 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
             if rule.spike is not None:
                 # (--spikeAF: no selection - the run's records and bases copied and the listed SNVs written into the copy; a run none
                 # of whose records spans a listed position is built from the run's own arrays)
-                var = rule.spike.run_variants(chrom, A, rule.af)
-                if len(var):
+                key = (id(rule.spike), rule.af)
+                if key not in spiked_of:
+                    spiked_of[key] = None
+                    var = rule.spike.run_variants(chrom, A, rule.af)
+                    if len(var):
+                        if idents is None:
+                            idents = bam.barcode_idents(A["n_bc"])
+                        if mism is None:
+                            mism = bam.run_mismatches(len(A["aln"]))
+                        spiked_of[key], _ = spike_run(eng, up, A, var, idents, rule.seed, rule.params.mismatchThr, mism[0], mism[1])
+                spiked = spiked_of[key]
+                if rule.spike_cell:
+                    # (--spikeDepth: the --dsMT philox selection at f over the target's copy - the one spiked above for the target's
+                    # own build -, or over the run's own arrays where nothing was spiked)
                     if idents is None:
                         idents = bam.barcode_idents(A["n_bc"])
-                    if mism is None:
-                        mism = bam.run_mismatches(len(A["aln"]))
-                    spiked, _ = spike_run(eng, up, A, var, idents, rule.seed, rule.params.mismatchThr, mism[0], mism[1])
-                sel, counts, d_orig = spiked or up, A, None
+                    sel, counts, d_orig = select_run(eng, spiked or up, A, lo, idents=idents, frac=rule.frac, seed=rule.seed)
+                else:
+                    sel, counts, d_orig = spiked or up, A, None
             elif rule.level == "read":
                 # (--dsRpb: the kept read names, by read-name id - an id must stand for one full name, or the rule cannot be applied)
                 if p_idents is None:
@@ -468,12 +486,14 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
             done = build_run(counts, L, eng, abi.c_params(rule.params), rule.params, chrom, lo, fasta, run_ref, [w] + d.planes, d.uaux,
                              d.slots, d.slots + n_loc, cap, max_depth, allele_key, bc_name, sampler=sampler, sampler_seed=sampler_seed,
                              barcode_idents=bc_idents, uploaded=sel)
-            if d_orig is None:
-                if spiked is not None:
-                    spiked.aln.free(); spiked.bq.free()
-            else:
+            if d_orig is not None:
                 sel.free(shared=False)
                 d_orig.free()
+            if rule.spike is not None:
+                users[key] -= 1
+                if not users[key] and spiked is not None:          # (behind the last build of its target)
+                    spiked.aln.free(); spiked.bq.free()
+                    spiked_of[key] = None
             if done is None:
                 raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "%s: the device builder does not take it" % rule.label, rule.flag))
             if done == NARROW:
@@ -484,6 +504,9 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
             buf.free()
         if d_cells is not None:
             d_cells[0].free()
+        for spiked in spiked_of.values():                          # (a build that ended early: NARROW, or an error)
+            if spiked is not None:
+                spiked.aln.free(); spiked.bq.free()
     for d, (nl_k, ns_k, lc, tb) in zip(ds, res):
         d.LC.append(lc)
         d.tables += tb
@@ -724,12 +747,18 @@ class DsRule:
     cell: int = None
     # (--spikeAF) level "barcode", nothing dropped: `af` the target allele fraction, `spike` the SpikeSet whose listed SNVs are written
     # into a copy of every run whose records span one (spike_run), at the threshold of `af`
+    # (--spikeDepth) a cell: `spike` and `af` of its target beside `frac` f and `bc_thr` = the --dsMT draw's threshold at f: the spiked
+    # copy of the target, then the philox selection at f with the same `seed`
     spike: object = None
+
+    @property
+    def spike_cell(self) -> bool:
+        return self.spike is not None and self.bc_thr is not None
 
     @property
     def flag(self) -> str:
         if self.spike is not None:
-            return "--spikeAF"
+            return "--spikeDepth" if self.spike_cell else "--spikeAF"
         if self.depth is not None:
             return "--dsAFDepth"
         if self.af is not None:
@@ -742,6 +771,8 @@ class DsRule:
 
     @property
     def label(self) -> str:
+        if self.spike_cell:
+            return "spiked allele fraction %g x fraction %g" % (self.af, self.frac)
         if self.spike is not None:
             return "spiked allele fraction %g" % self.af
         if self.depth is not None:
@@ -1343,7 +1374,7 @@ def spike_run(eng, up: RunOnDevice, A, var: np.ndarray, idents, seed: int, misma
 
 
 def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng, nthreads: int = 0, max_reads: int = 128_000_000,
-                keep: dict = None, keep_bytes: int = None):
+                keep: dict = None, keep_bytes: int = None, depth: dict = None):
     """DsRules of --spikeAF, one per target, and the pre-pass: only the runs around the listed loci are decoded (as ds_af_sets groups
     them); smc_allele_carriers gives N and V0 of every variant, then per target smc_spike_alleles writes the spiked copy and
     smc_allele_carriers on it gives V1.  The kernel's statistics are checked against the host's restatement of the draws: the records
@@ -1355,7 +1386,11 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     stay within `keep_bytes` (AF_KEEP_BYTES), a run beyond that without its arrays; "covers": per variant the identities of the
     barcodes that cover it; "counters": per variant uint32 [covering barcodes, 3] = (reads, alt0, single) - smc_allele_carriers'
     counters on the run, and its `alt` counter on one copy spiked at threshold 2^32 (every read the rewrite can touch shows ALT
-    there, and no other does); "spikes": the SpikeSet."""
+    there, and no other does); "spikes": the SpikeSet.
+    `depth` (--spikeDepth: dict with "fracs" and the "params" of the T x F cells, targets outer): it gets "rules", the cells' DsRules,
+    and "counts", per variant and cell dict(N, V0, S, READS, V1) - one smc_spike_depth_counts call with this seed over the covers
+    and counters above.  Every cell's (N, V0, V1) is also counted a second way - select_run at f over the spiked copy of t (over the
+    run itself for V0), then smc_allele_carriers on the selection - and a difference raises RuntimeError."""
     from .tools import ds_allele_fraction as af
     from .tools import spike_variants as sv
     af.unique_idents(bamio.placed_barcodes(path), path)
@@ -1363,8 +1398,12 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     spikes = SpikeSet(variants)
     P = params_list[0]
     rows = [[None] * len(variants) for _ in targets]
+    want_counters = keep is not None or depth is not None
+    covers, counters = [None] * len(variants), [None] * len(variants)
     if keep is not None:
-        keep.update(runs=[], covers=[None] * len(variants), counters=[None] * len(variants), spikes=spikes)
+        keep.update(runs=[], covers=covers, counters=counters, spikes=spikes)
+    fracs = list(depth["fracs"]) if depth is not None else []
+    second = {}                      # (--spikeDepth) (variant, target index, fraction index) -> [N', V0', V1'] counted on selections
     order = sorted(range(len(variants)), key=lambda k: (variants[k].chrom, variants[k].pos))
     bam = bamio.NativeBam(path)
     try:
@@ -1390,12 +1429,30 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                 nm, n_indel = dec.run_mismatches(len(A["aln"]))
                 run_ref = fasta.fetch(v0.chrom, lo, lo + nl).upper()
                 up = upload_run(eng, A, run_ref)
-                cov, car, cnt0 = allele_carriers_run(eng, up, A, lo, var, ins, counts=keep is not None)
+                cov, car, cnt0 = allele_carriers_run(eng, up, A, lo, var, ins, counts=want_counters)
+                for f, frac in enumerate(fracs):
+                    # (V0' of the cells at f: the carriers before spiking among the barcodes the selection keeps)
+                    sel, sel_counts, d_orig = select_run(eng, up, A, lo, idents=idents, frac=frac, seed=seed)
+                    try:
+                        _, car_f, _ = allele_carriers_run(eng, sel, sel_counts, lo, var, ins)
+                    finally:
+                        sel.free(shared=False); d_orig.free()
+                    for r, k in enumerate(group):
+                        for t in range(len(targets)):
+                            second[(k, t, f)] = [None, int(car_f[r].sum()), None]
                 for t, target in enumerate(targets):
                     svar, sorder = spikes.chrom_variants(v0.chrom, target)
                     spiked, stats = spike_run(eng, up, A, svar, idents, seed, P.mismatchThr, nm, n_indel)
                     try:
                         cov1, car1, cnt1 = allele_carriers_run(eng, spiked, A, lo, var, ins, counts=True)
+                        for f, frac in enumerate(fracs):
+                            sel, sel_counts, d_orig = select_run(eng, spiked, A, lo, idents=idents, frac=frac, seed=seed)
+                            try:
+                                cov_f, car_f, _ = allele_carriers_run(eng, sel, sel_counts, lo, var, ins)
+                            finally:
+                                sel.free(shared=False); d_orig.free()
+                            for r, k in enumerate(group):
+                                second[(k, t, f)][0], second[(k, t, f)][2] = int(cov_f[r].sum()), int(car_f[r].sum())
                     finally:
                         spiked.aln.free(); spiked.bq.free()
                     for r, k in enumerate(group):
@@ -1408,7 +1465,7 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                                                "host's restatement of the draws" % (target, v.chrom, v.pos, reads))
                         rows[t][k] = dict(N=int(cov[r].sum()), V0=int(car[r].sum()), S=int((hit[:cov.shape[1]] & cov[r]).sum()), READS=reads,
                                           V1=int(car1[r].sum()))
-                if keep is not None:
+                if want_counters:
                     # (`single`: one copy with every barcode spiked at every listed position - thr 2^32 - then the `alt` counters)
                     svar, _ = spikes.chrom_variants(v0.chrom, 0.5)
                     svar["thr"] = 1 << 32
@@ -1419,9 +1476,10 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                         spiked.aln.free(); spiked.bq.free()
                     for r, k in enumerate(group):
                         c = cov[r][:len(idents)]
-                        keep["covers"][k] = idents[c]
-                        keep["counters"][k] = np.stack([cnt0[r, :len(idents), 0][c], cnt0[r, :len(idents), 1][c],
-                                                        cnt_all[r, :len(idents), 1][c]], axis=1).astype(np.uint32)
+                        covers[k] = idents[c]
+                        counters[k] = np.stack([cnt0[r, :len(idents), 0][c], cnt0[r, :len(idents), 1][c],
+                                                cnt_all[r, :len(idents), 1][c]], axis=1).astype(np.uint32)
+                if keep is not None:
                     size = sum(int(A[x].nbytes) for x in ("aln", "cig", "bq", "loc"))
                     held = size + sum(r.nbytes for r in keep["runs"]) <= (AF_KEEP_BYTES if keep_bytes is None else keep_bytes)
                     keep["runs"].append(AfRun(v0.chrom, lo, hi, list(group), nl, size if held else 0, own if held else None,
@@ -1441,6 +1499,24 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     finally:
         bam.close()
     rules = [DsRule(1.0, Pt, seed=int(seed), af=float(t), spike=spikes) for t, Pt in zip(targets, params_list)]
+    if depth is not None:
+        try:
+            got = spike_depth_counts(eng, [v.pos for v in variants], covers, counters, [int(seed) & 0xFFFFFFFFFFFFFFFF],
+                                     [sv.threshold(t) for t in targets], [frac_threshold(f) for f in fracs])[:, 0]
+            for (k, t, f), mine in second.items():
+                if [int(got[k, t, f, c]) for c in (0, 1, 4)] != mine:
+                    v = variants[k]
+                    raise RuntimeError("--spikeDepth: %s:%d at %g x fraction %g: the counts call says (N, V0, V1) = %r, the selection of the "
+                                       "spiked copy %r" % (v.chrom, v.pos, targets[t], fracs[f], [int(got[k, t, f, c]) for c in (0, 1, 4)], mine))
+        except BaseException:
+            if keep is not None:
+                free_af_runs(keep["runs"])
+            raise
+        names = ("N", "V0", "S", "READS", "V1")
+        depth["counts"] = [[dict(zip(names, (int(x) for x in got[k, t, f]))) for t in range(len(targets)) for f in range(len(fracs))]
+                           for k in range(len(variants))]
+        depth["rules"] = [DsRule(float(f), Pc, seed=int(seed), af=float(t), spike=spikes, bc_thr=frac_threshold(f))
+                          for (t, f), Pc in zip(((t, f) for t in targets for f in fracs), depth["params"])]
     return rules, [dict(target=t, rows=r) for t, r in zip(targets, rows)]
 
 
@@ -1743,6 +1819,34 @@ def spike_rep_counts(eng, positions, covers, counters, seeds, thresholds) -> np.
     return out.reshape(shape)
 
 
+def spike_depth_counts(eng, positions, covers, counters, seeds, thresholds, depth_thresholds) -> np.ndarray:
+    """smc_spike_depth_counts -> uint32 [V, R, T, F, 5] = (N', V0', S', READS', V1') of every variant, replicate and cell.  The
+    arguments are spike_rep_counts'; depth_thresholds: frac_threshold(f) per barcode fraction."""
+    from .engine import DevBuf
+    n_var, seeds = len(covers), np.ascontiguousarray(seeds, np.uint64)
+    thr, dthr = np.ascontiguousarray(thresholds, np.uint64), np.ascontiguousarray(depth_thresholds, np.uint64)
+    shape = (n_var, len(seeds), len(thr), len(dthr), 5)
+    off = np.zeros(n_var + 1, np.uint32)
+    off[1:] = np.cumsum([len(c) for c in covers])
+    ident = np.concatenate([np.asarray(c, np.uint64) for c in covers]) if n_var else np.zeros(0, np.uint64)
+    cnt = np.concatenate([np.asarray(c, np.uint32).reshape(-1, 3) for c in counters]) if n_var else np.zeros((0, 3), np.uint32)
+    if len(cnt) != len(ident):
+        raise ValueError("spike_depth_counts: %d covering barcodes, counters of %d" % (len(ident), len(cnt)))
+    pos = np.array([int(p) & 0xFFFFFFFF for p in positions], np.uint32)
+    n_out = int(np.prod(shape))
+    up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.reshape(-1) if a.size else np.zeros(1, a.dtype))
+    bufs = [up(ident), up(cnt), up(off), up(pos), up(seeds), DevBuf(eng, 4 * max(1, n_out) + 256)]
+    try:
+        _lib.check(eng.L.smc_spike_depth_counts(eng.ctx, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data,
+                                                bufs[3].data_ptr(), n_var, bufs[4].data_ptr(), len(seeds), thr.ctypes.data, len(thr),
+                                                dthr.ctypes.data, len(dthr), bufs[5].data_ptr(), ctypes.c_void_p(0)), "smc_spike_depth_counts")
+        out = bufs[5].download(np.uint32, n_out) if n_out else np.zeros(0, np.uint32)          # (the default stream: behind the kernel)
+    finally:
+        for b in bufs:
+            b.free()
+    return out.reshape(shape)
+
+
 def spike_copy_strides(n_aln: int, n_pairs: int):
     """The byte strides between the copies of one smc_spike_alleles_reps call: a copy's records / pair pool rounded up to 256 bytes."""
     return (36 * max(1, n_aln) + 255) & ~255, (2 * max(1, n_pairs) + 255) & ~255
@@ -1782,18 +1886,75 @@ def spike_run_copies(eng, up: RunOnDevice, A, var: np.ndarray, idents, seeds, th
     return d_aln, d_bq, (sa, sb), stats
 
 
-def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed, bits):
+def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed, bits,
+                    cells=()):
     """`len(part_seeds)` spiked copies of a kept run at one target from one smc_spike_alleles_reps call, each built behind the other
     into one device batch (as _af_rep_call appends its selections) and the batch called with one plan -> (per copy the listed loci's
     raw rows, in the order of run.group), or NARROW.  var_at[g]: where variant run.group[g] stands in `svar`; want_reads[c][g]: the
-    counts call's READS of that copy and variant - the kernel's statistics must equal it."""
+    counts call's READS of that copy and variant - the kernel's statistics must equal it.
+    `cells` (--spikeDepth: (fraction, params) of the target's cells): every copy is also selected at each fraction with its own seed
+    (select_run's philox rule) and built; a cell's selections share one device batch and one plan of their own, called with that
+    cell's params -> (the copies' rows, per cell the same), or NARROW."""
     from . import vc
     A, up, lo, nl, chrom = run.A, run.up, run.lo, run.nl, run.chrom
     B = len(part_seeds)
     ns_full = int(A["n_slots"])
     cap = B * (ns_full + nl) + ns_full + nl + 64
     d_aln, d_bq, (sa, sb), stats = spike_run_copies(eng, up, A, svar, run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
-    d = None
+    copies = [RunOnDevice(d_aln.view(c * sa), up.cig, d_bq.view(c * sb), up.loc, up.ref, up.n_aln, up.loc_host) for c in range(B)]
+    flag = "--spikeDepth" if cells else "--spikeReps"
+
+    def batch_rows(Pb, frac):
+        """The B copies (`frac` None) or their selections at `frac`, built into one batch and called with one plan at params `Pb`."""
+        d = _DsBatch(eng, cap, bits, False)
+        try:
+            cp = abi.c_params(Pb)
+            n_loc = 0
+            for c in range(B):
+                if frac is None:
+                    # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch)
+                    sel, counts, d_orig, allele_key = copies[c], A, None, run.bam.allele_key
+                else:
+                    sel, counts, d_orig = select_run(eng, copies[c], A, lo, idents=run.idents, frac=frac, seed=int(part_seeds[c]))
+                    got = {}
+
+                    def allele_key(ai, qpos, indel, d_orig=d_orig, kept=sel.n_aln, got=got):
+                        # (the builder's alignment index counts the KEPT alignments: the decoder's records are those of the full run)
+                        if "orig" not in got:
+                            got["orig"] = d_orig.download(np.uint32, kept)
+                        return run.bam.allele_key(int(got["orig"][int(ai)]), qpos, indel)
+                try:
+                    done = build_run(counts, eng.L, eng, cp, Pb, chrom, lo, fasta, run.run_ref, [d.words] + d.planes, d.uaux, d.slots,
+                                     d.slots + n_loc, cap, max_depth, allele_key, run.bam.barcode_name, sampler=sampler,
+                                     sampler_seed=sampler_seed, barcode_idents=lambda n: run.idents, uploaded=sel)
+                finally:
+                    if d_orig is not None:
+                        sel.free(shared=False)
+                        d_orig.free()
+                if done is None:
+                    raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "a replicate: the device builder does not take it", flag))
+                if done == NARROW:
+                    return NARROW
+                _, ns_k, lc, tb = done
+                d.LC.append(lc)
+                d.tables += tb
+                d.slots += ns_k
+                n_loc += nl
+            lc = d.LC[0] if len(d.LC) == 1 else np.concatenate(d.LC)
+            plan = eng.make_plan(lc)
+            try:
+                out_rows = plan.run_devbuf([d.words, d.uaux[0]], Pb)
+            finally:
+                plan.close()
+            at = [variants[k].pos - 1 - lo for k in run.group]
+            idx = np.array([b * nl + a for b in range(B) for a in at], np.int64)
+            view = vc.LocusView([chrom] * len(idx), [lo + 1 + a for _ in range(B) for a in at],
+                                [run.run_ref[a] if a < len(run.run_ref) else "" for _ in range(B) for a in at], [d.tables[i] for i in idx.tolist()])
+            text = vc._strings(out_rows[idx].copy(), view, Pb, fasta)
+            g = len(at)
+            return [list(text[b * g:(b + 1) * g]) for b in range(B)]
+        finally:
+            d.free()
     try:
         for c in range(B):
             for g, k in enumerate(run.group):
@@ -1801,52 +1962,32 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
                     v = variants[k]
                     raise RuntimeError("--spikeReps: seed %d at %s:%d: the rewrite touched %d records, the counts call says %d" %
                                        (int(part_seeds[c]), v.chrom, v.pos, int(stats[c, var_at[g], 0]), int(want_reads[c][g])))
-        d = _DsBatch(eng, cap, bits, False)
-        cp = abi.c_params(P)
-        n_loc = 0
-        for c in range(B):
-            copy = RunOnDevice(d_aln.view(c * sa), up.cig, d_bq.view(c * sb), up.loc, up.ref, up.n_aln, up.loc_host)
-            # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch)
-            done = build_run(A, eng.L, eng, cp, P, chrom, lo, fasta, run.run_ref, [d.words] + d.planes, d.uaux, d.slots, d.slots + n_loc, cap,
-                             max_depth, run.bam.allele_key, run.bam.barcode_name, sampler=sampler, sampler_seed=sampler_seed,
-                             barcode_idents=lambda n: run.idents, uploaded=copy)
-            if done is None:
-                raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "a replicate: the device builder does not take it", "--spikeReps"))
-            if done == NARROW:
+        full = batch_rows(P, None)
+        if full == NARROW or not cells:
+            return full
+        of_cell = []
+        for frac, Pc in cells:
+            of_cell.append(batch_rows(Pc, frac))
+            if of_cell[-1] == NARROW:
                 return NARROW
-            _, ns_k, lc, tb = done
-            d.LC.append(lc)
-            d.tables += tb
-            d.slots += ns_k
-            n_loc += nl
-        lc = d.LC[0] if len(d.LC) == 1 else np.concatenate(d.LC)
-        plan = eng.make_plan(lc)
-        try:
-            out_rows = plan.run_devbuf([d.words, d.uaux[0]], P)
-        finally:
-            plan.close()
-        at = [variants[k].pos - 1 - lo for k in run.group]
-        idx = np.array([b * nl + a for b in range(B) for a in at], np.int64)
-        view = vc.LocusView([chrom] * len(idx), [lo + 1 + a for _ in range(B) for a in at],
-                            [run.run_ref[a] if a < len(run.run_ref) else "" for _ in range(B) for a in at], [d.tables[i] for i in idx.tolist()])
-        text = vc._strings(out_rows[idx].copy(), view, P, fasta)
-        g = len(at)
-        return [list(text[b * g:(b + 1) * g]) for b in range(B)]
+        return full, of_cell
     finally:
         d_aln.free(); d_bq.free()
-        if d is not None:
-            d.free()
 
 
 def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int, n_reps: int, eng, keep: dict, sampler: str = "reference",
-                     sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000):
+                     sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, depth: dict = None):
     """The replicate stage of --spikeReps.  Replicate j is --spikeAF with seed (seed + j) mod 2^64.  One smc_spike_rep_counts call
     gives (S, READS, V1) of every variant, replicate and target from what the pre-pass kept (spike_rules' `keep`) - no spiked copy is
     needed for them; then per kept run and target as many replicates as fit SPIKE_REP_BATCH_BYTES (and AF_REP_BATCH_SLOTS read
     slots, and SMC_SPIKE_MAX_COPIES) are spiked by one smc_spike_alleles_reps call, built one behind the other and called with one
     plan.  Every copy's statistics are checked against the counts call's READS.
     -> dict(seeds, counts: uint32 [V, R, T, 3], rows: {(variant index, target index, replicate): the raw row string at the variant's
-    locus}, times: seconds per part and the numbers of rewrite calls, builds and batches)."""
+    locus}, times: seconds per part and the numbers of rewrite calls, builds and batches).
+    `depth` (--spikeDepth: dict with "fracs" and the "params" of the T x F cells, targets outer): one smc_spike_depth_counts call gives
+    "depth_counts", uint32 [V, R, T, F, 5], and every copy is also selected and built once per fraction (_spike_rep_call's `cells`):
+    `rows` then also holds (variant index, T + t x F + f, replicate).  The copies' READS are checked against the f = 1 numbers, as
+    without it."""
     import time
     from . import dsaf
     from .tools import spike_variants as sv
@@ -1863,6 +2004,11 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
     try:
         t0 = time.perf_counter()
         counts = spike_rep_counts(eng, [v.pos for v in variants], keep["covers"], keep["counters"], seeds, thr)
+        depth_counts = None
+        F = len(depth["fracs"]) if depth is not None else 0
+        if depth is not None:
+            depth_counts = spike_depth_counts(eng, [v.pos for v in variants], keep["covers"], keep["counters"], seeds, thr,
+                                              [frac_threshold(f) for f in depth["fracs"]])
         times["counts"] = time.perf_counter() - t0
         for run in keep["runs"]:
             if run.A is None:
@@ -1885,28 +2031,31 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
             t0 = time.perf_counter()
             for t in range(T):
                 P = params_list[t]
+                cells = [(depth["fracs"][f], depth["params"][t * F + f]) for f in range(F)]
                 for b in range(0, n_reps, room):
                     js = list(range(b, min(n_reps, b + room)))
                     want = [[int(counts[k, j, t, 1]) for k in run.group] for j in js]
                     bits = 16 if (eng.word_bits == 16 and 0 <= P.minBQ <= 63) else 32
                     args = (eng, run, svar, var_at, [seeds[j] for j in js], thr[t], want, P, fasta, variants, max_depth, sampler, sampler_seed)
-                    out = _spike_rep_call(*args, bits)
+                    out = _spike_rep_call(*args, bits, cells)
                     if out == NARROW:
                         eng.word_bits = 32
-                        out = _spike_rep_call(*args, 32)
+                        out = _spike_rep_call(*args, 32, cells)
                         times["rewrites"] += 1
-                    for j, text in zip(js, out):
-                        for k, line in zip(run.group, text):
-                            rows[(k, t, j)] = line
+                    full, of_cell = out if cells else (out, [])
+                    for c, part in [(t, full)] + [(T + t * F + f, part) for f, part in enumerate(of_cell)]:
+                        for j, text in zip(js, part):
+                            for k, line in zip(run.group, text):
+                                rows[(k, c, j)] = line
                     times["rewrites"] += 1
-                    times["builds"] += len(js)
-                    times["batches"] += 1
+                    times["builds"] += len(js) * (1 + F)
+                    times["batches"] += 1 + F
             times["calls"] += time.perf_counter() - t0
             run.free()
     finally:
         free_af_runs(keep["runs"])
     times["stage"] = time.perf_counter() - t_start
-    return dict(seeds=seeds, counts=counts, rows=rows, times=times)
+    return dict(seeds=seeds, counts=counts, rows=rows, times=times, depth_counts=depth_counts)
 
 
 def _fnv64(text: str) -> int:

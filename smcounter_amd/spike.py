@@ -5,6 +5,9 @@
 theoretical one - <outPrefix>.spikeAF.replicates.txt, .spikeAF.sensitivity.txt and .spikeAF.curve.txt (the replicate stage itself is
 devplanes.spike_replicates).
 
+--spikeDepth: the cells (target t, barcode fraction f) of the spike-ins - their flag, prefixes and mtDepths (depth_cells), and the four
+pages <outPrefix>.spikeAF.depth.detection.txt, .replicates.txt, .sensitivity.txt and .curve.txt, which mirror .dsAF.depth.*.
+
 The semantics are tools/spike_variants.py's (DESIGN.md "--spikeAF"); the rewrite on the GPU is csrc/k_spike.inc (smc_spike_alleles),
 the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the main pass are devplanes.spike_rules / spike_run.
 """
@@ -17,6 +20,7 @@ from .tools import spike_variants as sv
 DETECTION_HEADER = ("CHROM", "POS", "REF", "ALT", "TARGET", "N", "V0", "S", "READS", "V1", "AF", "UMT", "VMT", "VMF", "PI", "FILTER", "CALLED")
 MAX_TARGETS = 32               # (devplanes.SPIKE_MAX_TARGETS: every target holds a batch's device arrays)
 DS_FLAGS = ("dsMT", "dsRpb", "dsGrid", "dsAF", "dsAFReps", "dsAFDepth")
+MAX_CELLS = 32                 # (--spikeDepth: SMC_AF_DEPTH_MAX_CELLS; every cell holds a batch's device arrays)
 
 
 def targets(args):
@@ -197,3 +201,140 @@ def write_curve(out_prefix: str, variants, targets, entries, lods=None) -> None:
         for i, v in enumerate(variants):
             fh.write(curve_line(v, entries[(i, 0)][0][0]["N"], targets, [entries[(i, t)] for t in range(T)],
                                 None if lods is None else float(lods[top][i])) + "\n")
+
+
+# ---- --spikeDepth
+DEPTH_DETECTION_HEADER = DETECTION_HEADER[:5] + ("FRACTION", "MTDEPTH") + DETECTION_HEADER[5:]
+DEPTH_REPLICATES_HEADER = DEPTH_DETECTION_HEADER[:7] + ("REP", "SEED") + DEPTH_DETECTION_HEADER[7:]
+DEPTH_SENSITIVITY_HEADER = SENSITIVITY_HEADER[:5] + ("FRACTION", "MTDEPTH") + SENSITIVITY_HEADER[5:] + ("N_MEAN",)
+DEPTH_CURVE_HEADER = dsaf.CURVE_HEADER
+
+
+def depth_cells(args, spike_targets):
+    """--spikeDepth -> (fractions, [(target index, t, f, mtDepth of the cell, output prefix)] for every --spikeAF target t and every
+    fraction f, targets outer), or (None, []) without the flag.  A cell's mtDepth is what --dsMT f gets from its target's mtDepth.
+    SystemExit: without --spikeAF, text that is no list of numbers, a fraction outside (0, 1] or listed twice, beyond MAX_CELLS
+    cells."""
+    from .py2compat import py2_round
+    text = getattr(args, "spikeDepth", None)
+    if text in (None, ""):
+        return None, []
+    if not spike_targets:
+        raise SystemExit("--spikeDepth thins the barcodes of the --spikeAF spike-ins: it needs --spikeAF")
+    try:
+        fr = [float(x) for x in str(text).split(",") if x.strip()]
+    except ValueError:
+        raise SystemExit("--spikeDepth: comma-separated fractions in (0, 1] expected, got %r" % text)
+    if not fr or any(not (0.0 < f <= 1.0) for f in fr):
+        raise SystemExit("--spikeDepth: every fraction must lie in (0, 1], got %r" % text)
+    if len(set("%g" % f for f in fr)) != len(fr):
+        raise SystemExit("--spikeDepth: a fraction is listed twice (the cells' files would share a name), got %r" % text)
+    if len(spike_targets) * len(fr) > MAX_CELLS:
+        raise SystemExit("--spikeDepth: %d targets x %d fractions = %d cells, at most %d" % (len(spike_targets), len(fr),
+                                                                                              len(spike_targets) * len(fr), MAX_CELLS))
+    return fr, [(k, t, f, max(1, int(py2_round(f * d))), "%s.dsMT%g" % (p, f)) for k, (t, d, p) in enumerate(spike_targets) for f in fr]
+
+
+def _cell_fields(line: str, frac: float, mt_depth: int):
+    f = line.split("\t")
+    return f[:5] + ["%g" % frac, "%d" % mt_depth] + f[5:]
+
+
+def depth_detection_line(v, target, frac, mt_depth, r, row, cut, lod=None) -> str:
+    """detection_line() of variant `v` in cell (target, frac) with FRACTION and MTDEPTH behind TARGET.  `r`: the cell's achieved
+    dict(N, V0, S, READS, V1)."""
+    return "\t".join(_cell_fields(detection_line(v, target, r, row, cut, lod), frac, mt_depth))
+
+
+def depth_replicate_line(v, target, frac, mt_depth, rep: int, seed: int, r, row, cut) -> str:
+    f = _cell_fields(detection_line(v, target, r, row, cut), frac, mt_depth)
+    return "\t".join(f[:7] + ["%d" % rep, "%d" % seed] + f[7:])
+
+
+def _n_mean(per) -> float:
+    return sum(float(r["N"]) for r, _, _ in per) / len(per)
+
+
+def depth_sensitivity_line(v, target, frac, mt_depth, per, lod=None) -> str:
+    """sensitivity_line() of a cell with FRACTION and MTDEPTH behind TARGET and the mean N' behind PI_MIN (then LOD)."""
+    f = _cell_fields(sensitivity_line(v, target, per), frac, mt_depth) + [dsaf.frac_text(_n_mean(per))]
+    if lod is not None:
+        f.append("%.15g" % lod)
+    return "\t".join(f)
+
+
+def depth_curve_header(targets, with_lod: bool = False):
+    return DEPTH_CURVE_HEADER + tuple("RATE@%g" % t for t in sorted(targets)) + ("T95",) + (("LOD",) if with_lod else ())
+
+
+def depth_curve_line(v, depth, mt_depths, targets, per_target, lod=None) -> str:
+    """One line of the depth curve: variant `v` at one barcode depth (`depth` None: full, else f).  `mt_depths`: the mtDepth of every
+    target's output at that depth (printed once when equal, else joined by commas); per_target[t]: the replicates of targets[t] there.
+    RATE@ columns in ascending target order, then T95."""
+    order = sorted(range(len(targets)), key=lambda t: targets[t])
+    rates = [float(_called(v, per)) / len(per) for per in per_target]
+    best = dsaf.t95(targets, rates)
+    depths = ["%d" % d for d in mt_depths]
+    f = [v.chrom, "%d" % v.pos, v.ref, v.alt, dsaf.FULL if depth is None else "%g" % depth,
+         depths[0] if len(set(depths)) == 1 else ",".join(depths), dsaf.frac_text(sum(_n_mean(p) for p in per_target) / len(per_target))] + \
+        [dsaf.frac_text(rates[t]) for t in order] + [dsaf.NA if best is None else "%g" % best]
+    if lod is not None:
+        f.append("%.15g" % lod)
+    return "\t".join(f)
+
+
+def write_depth_detection(out_prefix: str, variants, cells, counts, loc_index=None) -> None:
+    """<outPrefix>.spikeAF.depth.detection.txt: a header, then a line per listed variant and cell (targets outer, fractions inner).
+    `cells`: per cell (target index, target, fraction, mtDepth, output prefix, that output's LODs by locus index or None);
+    counts[v][cell]: dict(N, V0, S, READS, V1), the cell's achieved numbers."""
+    read = [dsaf.read_output(c[4]) for c in cells]
+    with_lod = any(c[5] is not None for c in cells)
+    with open(out_prefix + ".spikeAF.depth.detection.txt", "w") as fh:
+        fh.write("\t".join(DEPTH_DETECTION_HEADER + (("LOD",) if with_lod else ())) + "\n")
+        for i, v in enumerate(variants):
+            key = (v.chrom, "%d" % v.pos)
+            for c, ((_, target, frac, depth, _, lods), (rows, cut)) in enumerate(zip(cells, read)):
+                lod = float(lods[loc_index[key]]) if lods is not None else None
+                fh.write(depth_detection_line(v, target, frac, depth, counts[i][c], rows.get(key), cut.get(key), lod) + "\n")
+
+
+def write_depth_replicates(out_prefix: str, variants, cells, seeds, entries) -> None:
+    """<outPrefix>.spikeAF.depth.replicates.txt: a line per listed variant, cell and replicate.  entries[(v, cell)]: per replicate
+    (dict(N, V0, S, READS, V1), row fields or None, cut or None)."""
+    with open(out_prefix + ".spikeAF.depth.replicates.txt", "w") as fh:
+        fh.write("\t".join(DEPTH_REPLICATES_HEADER) + "\n")
+        for i, v in enumerate(variants):
+            for c, (_, target, frac, depth, _, _) in enumerate(cells):
+                for j, (r, row, cut) in enumerate(entries[(i, c)]):
+                    fh.write(depth_replicate_line(v, target, frac, depth, j, seeds[j], r, row, cut) + "\n")
+
+
+def write_depth_sensitivity(out_prefix: str, variants, cells, entries, loc_index=None) -> None:
+    """<outPrefix>.spikeAF.depth.sensitivity.txt: a line per listed variant and cell; LOD: the locus's in the run's own output of the
+    cell."""
+    with_lod = any(c[5] is not None for c in cells)
+    with open(out_prefix + ".spikeAF.depth.sensitivity.txt", "w") as fh:
+        fh.write("\t".join(DEPTH_SENSITIVITY_HEADER + (("LOD",) if with_lod else ())) + "\n")
+        for i, v in enumerate(variants):
+            for c, (_, target, frac, depth, _, lods) in enumerate(cells):
+                lod = float(lods[loc_index[(v.chrom, "%d" % v.pos)]]) if lods is not None else None
+                fh.write(depth_sensitivity_line(v, target, frac, depth, entries[(i, c)], lod) + "\n")
+
+
+def write_depth_curve(out_prefix: str, variants, targets, fracs, full, cells, full_entries, entries, loc_index=None) -> None:
+    """<outPrefix>.spikeAF.depth.curve.txt: a line per listed variant and barcode depth - `full` (the targets' own outputs) first, then
+    every fraction.  `full`: per target (mtDepth, the LODs of its .spikeAF<t> output or None); full_entries[(v, t)] / entries[(v,
+    cell)]: the replicates.  LOD: the locus's theoretical one at that depth, in the output of the LARGEST listed target there."""
+    T, F = len(targets), len(fracs)
+    top = max(range(T), key=lambda t: targets[t])
+    with_lod = any(c[5] is not None for c in cells)
+    with open(out_prefix + ".spikeAF.depth.curve.txt", "w") as fh:
+        fh.write("\t".join(depth_curve_header(targets, with_lod)) + "\n")
+        for i, v in enumerate(variants):
+            at = loc_index[(v.chrom, "%d" % v.pos)] if with_lod else None
+            fh.write(depth_curve_line(v, None, [d for d, _ in full], targets, [full_entries[(i, t)] for t in range(T)],
+                                      float(full[top][1][at]) if with_lod else None) + "\n")
+            for k, f in enumerate(fracs):
+                mine = [cells[t * F + k] for t in range(T)]
+                fh.write(depth_curve_line(v, f, [c[3] for c in mine], targets, [entries[(i, t * F + k)] for t in range(T)],
+                                          float(mine[top][5][at]) if with_lod else None) + "\n")

@@ -593,11 +593,15 @@ int smc_af_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint8_t
  *   d_stats[n_var][2]   uint32: records rewritten at v (one that showed `alt` already counts), records whose NM grew; zeroed here
  * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched and nothing copied: positions not strictly ascending, a letter
  * outside ACGT, ref equal to alt, a threshold above 2^32, more than SMC_AF_MAX_VARIANTS variants (d_var is a DEVICE array:
- * `var_host`, the same n_var records in host memory, is what is checked). */
+ * `var_host`, the same n_var records in host memory, is what is checked).
+ * PHASE SETS (--spikePhase).  `lead` names, per record, the leader of its set: the member with the smallest position, var[k - lead].
+ * Record k is drawn with counter word 3 = (var[k - lead].pos0 + 1) mod 2^32 in place of its own position, so a barcode is spiked at
+ * every member of a set or at none; with lead = 0 everywhere the call is bit for bit what it was.  Also SMC_E_INPUT, nothing launched
+ * and nothing copied: var_host[k].lead > k, or a leader whose own `lead` is not 0 (smc_spike_alleles_reps refuses the same). */
 typedef struct smc_spike_variant {
     int32_t pos0;              /* 0-based reference position */
     uint8_t ref, alt;          /* ASCII, out of A C G T */
-    uint8_t pad[2];
+    uint16_t lead;             /* records back, in this array, to the leader of the variant's phase set; 0: its own leader */
     uint64_t thr;              /* floor(t * 2^32), in [0, 2^32] */
 } smc_spike_variant;
 int smc_spike_alleles(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, const uint8_t* d_bq, int64_t n_pairs,
@@ -618,8 +622,9 @@ int smc_spike_alleles(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, con
  *            variants stand one behind the other (variant v's at [cov_off[v], cov_off[v + 1])): d_cov_ident their identities,
  *            d_cov_cnt[e][3] uint32 per barcode its pileup reads at the variant's position, those that show ALT before spiking
  *            and those whose allele key there is a single letter - what the rewrite can touch (smc_allele_carriers' counters on
- *            the run give the first two, its `alt` counter on a copy spiked at threshold 2^32 the third).  d_pos1[n_var]: the
- *            variants' 1-based positions (counter word 3 of the draw).  d_seeds[n_reps] in device memory; `thr`: HOST memory,
+ *            the run give the first two, its `alt` counter on a copy spiked at threshold 2^32 the third).  d_pos1[n_var]: counter
+ *            word 3 of every variant's draw - the 1-based position of the LEADER of its phase set (its own without sets; the
+ *            same holds for smc_spike_depth_counts).  d_seeds[n_reps] in device memory; `thr`: HOST memory,
  *            n_targets words in [0, 2^32].  With hit = u_v(b; seeds[j]) < thr[t], u_v smc_spike_alleles' draw:
  *            d_out[v][j][t][3] uint32 = (S: covering b with hit, READS: the sum of single[b] over them, V1: the b with
  *            2 * (hit ? single[b] : alt0[b]) > reads[b]).  One draw per (b, v, j) serves every target.  d_out is zeroed by the call.
@@ -651,6 +656,29 @@ int smc_spike_rep_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32
 int smc_spike_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_cnt, const uint32_t* d_cov_off,
                            const uint32_t* cov_off_host, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
                            const uint64_t* thr, int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream);
+/* (ABI 11, additive: one entry more, the version number unchanged) --spikePhase: the JOINT numbers of phase sets - groups of listed
+ * SNVs of one chromosome that share one draw (smc_spike_variant.lead), so that a barcode carries the whole haplotype or nothing of
+ * it.  Per set g its M_g = set_m_host[g] members (1 .. SMC_SPIKE_PHASE_MAX_MEMBERS) and its JOINT barcodes, those that cover every
+ * member: d_joint_ident holds the identities of all n_sets sets one behind the other, set g's at [joint_off[g], joint_off[g + 1])
+ * (d_joint_off in device memory, `joint_off_host` the same on the host, which is what is checked).  d_joint_cnt: uint32, per set a
+ * block of (joint barcodes of g) rows of 3 * M_g words that starts at word d_cnt_off[g] - row e of set g holds, member after member,
+ * (reads, alt0, single) of that barcode at that member's position, as smc_spike_rep_counts takes them per variant.  d_set_m /
+ * d_cnt_off[n_sets]: device copies of set_m_host and of the word offsets.  d_pos1[n_sets]: counter word 3 of the set's draw, the
+ * leader's 1-based position.  d_seeds, `thr`, `depth_thr`: as smc_spike_depth_counts takes them.  With hit = u(b; seeds[j]) <
+ * thr[t] and keep = the "dsMT" draw of b with seeds[j] < depth_thr[f] - ONE spike draw per (barcode, set, replicate), the depth draw
+ * only when some depth threshold is below 2^32:
+ *   d_out[g][j][t][f][4] uint32 = (N_ALL': the joint b with keep, V0_ALL': those that carry EVERY member before spiking - 2 *
+ *   alt0 > reads at each -, S_ALL': those with keep and hit, V1_ALL': those with keep and 2 * (hit ? single : alt0) > reads at
+ *   every member).  At M_g = 1 these are columns (N', V0', S', V1') of smc_spike_depth_counts.  d_out is zeroed by the call.
+ * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched and nothing zeroed: a set with M_g outside 1 ..
+ * SMC_SPIKE_PHASE_MAX_MEMBERS, offsets that decrease, n_targets * n_fracs above SMC_AF_DEPTH_MAX_CELLS, a threshold above 2^32 on
+ * either axis, n_fracs below 1, n_reps above SMC_AF_REP_MAX_REPS, more than SMC_AF_MAX_VARIANTS sets, an output of 2^32 - 256
+ * words or more. */
+#define SMC_SPIKE_PHASE_MAX_MEMBERS 8
+int smc_spike_phase_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, const uint32_t* d_joint_cnt, const uint32_t* d_joint_off,
+                           const uint32_t* joint_off_host, const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_cnt_off,
+                           const uint32_t* d_pos1, int32_t n_sets, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
+                           int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

@@ -44,8 +44,10 @@ assert DEV_ALN_DTYPE.itemsize == 36 and DEV_LOCUS_DTYPE.itemsize == 16
 # smc_af_variant (smc_allele_carriers): a listed variant of a run
 AF_VARIANT_DTYPE = np.dtype([("locus", "<u4"), ("kind", "<u4"), ("letter", "<u4"), ("len", "<u4"), ("ins_off", "<u4"), ("pad", "<u4", (3,))])
 assert AF_VARIANT_DTYPE.itemsize == 32
-# smc_spike_variant (smc_spike_alleles): a listed SNV by reference position, and its target's threshold
-SPIKE_VARIANT_DTYPE = np.dtype([("pos0", "<i4"), ("ref", "u1"), ("alt", "u1"), ("pad", "u1", (2,)), ("thr", "<u8")])
+# smc_spike_variant (smc_spike_alleles): a listed SNV by reference position, the records back to the leader of its phase set (0: its
+# own leader), and its target's threshold
+SPIKE_VARIANT_DTYPE = np.dtype([("pos0", "<i4"), ("ref", "u1"), ("alt", "u1"), ("lead", "<u2"), ("thr", "<u8")])
+SPIKE_PHASE_MAX_MEMBERS = 8    # SMC_SPIKE_PHASE_MAX_MEMBERS
 assert SPIKE_VARIANT_DTYPE.itemsize == 16
 
 

@@ -165,6 +165,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "detection rate and its Wilson score interval (95 %%%%), the achieved fractions, and with --lod the locus's "
                         "LOD, and <outPrefix>.spikeAF.curve.txt, one line per variant: the rate at every target and T95, the smallest "
                         "target found in 95 %%%% of the replicates together with every larger one.  Needs --spikeAF" % (REPS_MIN, REPS_MAX))
+    p.add_argument("--spikePhase", action="store_true", default=False,
+                   help="plant MNVs and same-molecule variant sets: --spikeVariants may then hold MNV lines (REF and ALT of one length, 2 "
+                        "to 8 letters: one member SNV per letter that differs) and, on VCF lines, PS=<name> entries in column 8 (the "
+                        "lines of one chromosome with one name are one set, at most 8 members).  The members of a set share one draw "
+                        "per barcode - that of the member with the smallest position - so a barcode is spiked at all of them or at "
+                        "none, as tools/spike_variants.py --phased does it.  Added when a set has two members or more: "
+                        "<outPrefix>.spikeAF.phase.txt, one line per set and output with the barcodes that cover every member (N_ALL), "
+                        "carry every member before (V0_ALL) and after spiking (V1_ALL), are spiked (S_ALL), and whether every member "
+                        "was called (CALLED_ALL); with --spikeReps <outPrefix>.spikeAF.phase.replicates.txt and "
+                        ".spikeAF.phase.sensitivity.txt.  Without the flag an MNV line is refused and PS= is not read.  Needs --spikeAF")
     p.add_argument("--spikeDepth", default=None,
                    help="the spike-ins of --spikeAF at several barcode depths: comma-separated fractions f in (0, 1].  For every target t "
                         "and every f the run is also called on the CELL (t, f): the spike-in at t, of which a barcode stays when the "
@@ -353,6 +363,7 @@ class _Plan:
     spike: dict = None          # (--spikeAF) once the rules are made: "variants", and "res", the pre-pass's numbers per target
     spike_reps: int = None      # (--spikeReps) R; plan.spike then holds "keep", what the pre-pass kept (None once the stage has taken it)
     spike_depth: dict = None    # (--spikeDepth) "fracs", the cells' "params", and once the rules are made "rules" and "counts" [V][T x F]
+    spike_phase: bool = False   # (--spikePhase) plan.spike then holds "phase": None, or devplanes.spike_rules' dict of the sets of two members or more
 
     @property
     def rules(self):
@@ -385,13 +396,14 @@ def ds_af_rules(args, outs, variants, early, keep=None, depth=None):
     return rules, res
 
 
-def spike_rules(args, outs, variants, early, keep=None, depth=None):
+def spike_rules(args, outs, variants, early, keep=None, depth=None, phase=None):
     """The devplanes.DsRule of every --spikeAF output (the pre-pass on the GPU: devplanes.spike_rules) and its numbers; the run log
     gets a line per variant and target.  `keep` (--spikeReps): a dict for what the replicate stage starts from.  `depth`
-    (--spikeDepth): the plan's dict; it gets the cells' rules and counts."""
+    (--spikeDepth): the plan's dict; it gets the cells' rules and counts.  `phase` (--spikePhase): a dict with the "sets" of two
+    members or more; it gets their joint barcodes and counts."""
     from .tools import spike_variants as sv
     eng = _engine_of(args, early)
-    more = {k: v for k, v in (("keep", keep), ("depth", depth)) if v is not None}
+    more = {k: v for k, v in (("keep", keep), ("depth", depth), ("phase", phase)) if v is not None}
     try:
         rules, res = devplanes.spike_rules(args.bamFile, fasta.FastaFile(args.refGenome), variants, [o.af for o in outs],
                                            [o.params for o in outs], int(args.dsSeed), eng, **more)
@@ -400,6 +412,11 @@ def spike_rules(args, outs, variants, early, keep=None, depth=None):
     for r in res:
         for v, row in zip(variants, r["rows"]):
             print(sv.report_line(v, r["target"], row))
+    if phase is not None:
+        for ps, per in zip(phase["sets"], phase["counts"]):
+            for o, c in zip(outs, per):
+                print("--spikePhase %g: set %s (%d members) N_ALL %d, V0_ALL %d, S_ALL %d, V1_ALL %d" %
+                      (o.af, ps.name, len(ps.members), c["N_ALL"], c["V0_ALL"], c["S_ALL"], c["V1_ALL"]))
     return rules, res
 
 
@@ -592,6 +609,8 @@ def _spike_replicates(args, plan, ref, eng, loci, ds_rows):
     variants, outs, targets = plan.spike["variants"], plan.outputs[1:], [o for o in plan.outputs if o.kind == "spikeAF"]
     keep, plan.spike["keep"] = plan.spike["keep"], None      # (the stage frees the kept runs itself, whatever happens in it)
     more = {"depth": plan.spike_depth} if plan.spike_depth is not None else {}
+    if plan.spike.get("phase") is not None:
+        more["phase"] = plan.spike["phase"]
     out = devplanes.spike_replicates(args.bamFile, ref, variants, [o.af for o in targets], [o.params for o in targets], int(args.dsSeed),
                                      plan.spike_reps, eng, keep, sampler=getattr(args, "sampler", "reference"),
                                      sampler_seed=getattr(args, "samplerSeed", 0), **more)
@@ -737,7 +756,7 @@ def _main(args) -> int:
                  [_Output(p, at(mtDepth=d), "dsAFDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in af_cells] +
                  [_Output(p, at(mtDepth=d), "spikeAF", af=t) for t, d, p in spike_targets] +
                  [_Output(p, at(mtDepth=d), "spikeDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in spike_cells],
-                 reps=ds_af_reps(args, af_targets), spike_reps=_spike.reps(args, spike_targets))
+                 reps=ds_af_reps(args, af_targets), spike_reps=_spike.reps(args, spike_targets), spike_phase=_spike.phase(args, spike_targets))
     if spike_fracs is not None:
         plan.spike_depth = dict(fracs=spike_fracs, params=[o.params for o in plan.outputs if o.kind == "spikeDepth"])
     if af_fracs is not None:
@@ -817,11 +836,14 @@ def _make_rules(args, plan, loc_list):
         from . import spike as _spike
         variants = _spike.variants(args, loc_list, fasta.FastaFile(args.refGenome))
         keep = {} if plan.spike_reps is not None else None
-        rules, res = spike_rules(args, sp, variants, plan.early, keep, plan.spike_depth)
+        from .tools import spike_variants as sv
+        psets = sv.phase_sets(variants) if plan.spike_phase else []
+        phase = dict(sets=psets) if psets else None
+        rules, res = spike_rules(args, sp, variants, plan.early, keep, plan.spike_depth, phase)
         put(sp, rules)
         if plan.spike_depth is not None:
             put([o for o in plan.outputs if o.kind == "spikeDepth"], plan.spike_depth["rules"])
-        plan.spike = dict(variants=variants, res=res, keep=keep)
+        plan.spike = dict(variants=variants, res=res, keep=keep, phase=phase)
 
 
 def _gather_ranks(args, params, loc_list, rank, local_rank, world):
@@ -990,6 +1012,25 @@ def _spike_reports(args, plan, shard, loc_index, repeats):
         _spike.write_depth_sensitivity(args.outPrefix, variants, cells, cell_entries, loc_index)
         full = [(o.params.mtDepth, lods[1 + t]["lods"] if lods is not None else None) for t, o in enumerate(outs)]
         _spike.write_depth_curve(args.outPrefix, variants, targets, plan.spike_depth["fracs"], full, cells, entries, cell_entries, loc_index)
+    phase = plan.spike.get("phase")
+    if phase is not None:
+        # (--spikePhase: a set is called in a replicate when every member is; the joint counts are the stage's own call's)
+        F = len(plan.spike_depth["fracs"]) if plan.spike_depth is not None else 0
+        p_outs = [(o.af, None, o.params.mtDepth) for o in outs] + \
+                 [(o.af, o.frac, o.params.mtDepth) for o in plan.outputs if o.kind == "spikeDepth"]
+        p_entries = {}
+        for g, ps in enumerate(phase["sets"]):
+            for c in range(len(p_outs)):
+                t, f = (c, None) if c < len(outs) else divmod(c - len(outs), F)
+                per = []
+                for j in range(R):
+                    got = reps["phase_counts"][g, j, t] if f is None else reps["phase_depth_counts"][g, j, t, f]
+                    of = [(entries[(i, t)] if f is None else cell_entries[(i, c - len(outs))])[j] for i in ps.members]
+                    per.append((dict(zip(_spike.PHASE_NAMES, (int(x) for x in got))),
+                                int(all(_spike._called(variants[i], [e]) for i, e in zip(ps.members, of)))))
+                p_entries[(g, c)] = per
+        _spike.write_phase_replicates(args.outPrefix, variants, phase["sets"], p_outs, reps["seeds"], p_entries)
+        _spike.write_phase_sensitivity(args.outPrefix, variants, phase["sets"], p_outs, p_entries)
     tm = reps["times"]
     print("--spikeReps: replicate stage %.3f s (%d replicates x %d targets: counts call %.4f s, %d rewrite calls, %d builds in %d batches, "
           "%.3f s)" % (tm["stage"], R, len(outs), tm["counts"], tm["rewrites"], tm["builds"], tm["batches"], tm["calls"]))
@@ -1038,6 +1079,16 @@ def _run(args, plan, loc_list, t0):
         _spike.write_detection(args.outPrefix, plan.spike["variants"], outs, loc_index)
         if plan.spike_depth is not None:
             _spike.write_depth_detection(args.outPrefix, plan.spike["variants"], _spike_cells(plan, lods), plan.spike_depth["counts"], loc_index)
+        phase = plan.spike.get("phase")
+        if phase is not None:
+            # (--spikePhase: every set in the full-depth output - nothing spiked there -, in every target's and in every cell's)
+            sp = [o for o in plan.outputs if o.kind == "spikeAF"]
+            full = [dict(c[0], S_ALL=0, V1_ALL=c[0]["V0_ALL"]) for c in phase["counts"]]
+            p_outs = [(None, None, params.mtDepth, plan.outputs[0].prefix, full)] + \
+                     [(o.af, None, o.params.mtDepth, o.prefix, [c[t] for c in phase["counts"]]) for t, o in enumerate(sp)] + \
+                     [(o.af, o.frac, o.params.mtDepth, o.prefix, [c[k] for c in phase["depth_counts"]])
+                      for k, o in enumerate(o for o in plan.outputs if o.kind == "spikeDepth")]
+            _spike.write_phase(args.outPrefix, plan.spike["variants"], phase["sets"], p_outs)
         if shard.spike_reps is not None:
             _spike_reports(args, plan, shard, loc_index, repeats)
     t1 = datetime.datetime.now()

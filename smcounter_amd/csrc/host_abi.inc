@@ -1144,6 +1144,8 @@ static int spk_check(const std::string& who, smc_ctx* ctx, const smc_dev_aln* d_
         if (!acgt(V.ref) || !acgt(V.alt)) return fail(SMC_E_INPUT, w + ": a letter outside ACGT");
         if (V.ref == V.alt) return fail(SMC_E_INPUT, w + ": ref equals alt");
         if (own_thr && V.thr > (1ull << 32)) return fail(SMC_E_INPUT, w + ": a threshold above 2^32");
+        if ((int32_t)V.lead > v) return fail(SMC_E_INPUT, w + ": lead " + std::to_string(V.lead) + " points in front of the array");
+        if (V.lead && var_host[v - (int32_t)V.lead].lead) return fail(SMC_E_INPUT, w + ": its leader has a lead of its own");
     }
     if (n_aln >= (int64_t)0xFFFFFF00 || n_bc >= (int64_t)0x7FFFFF00) return fail(SMC_E_ARG, who + ": run too large");
     if ((n_var && (!d_var || !d_stats)) || (n_aln && (!d_aln || !d_cig || !d_nm || !d_n_indel || !d_aln_out)) || (n_pairs && (!d_bq || !d_bq_out)) ||
@@ -1306,6 +1308,68 @@ int smc_spike_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint
                                                       (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPR_BLOCK), 0, st,
                            (const unsigned long long*)d_cov_ident, d_cov_cnt, d_cov_off, d_pos1, T, (int)n_targets, D, (int)n_fracs, with_depth,
                            (const unsigned long long*)d_seeds, (int)n_reps, d_out);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
+// (--spikePhase) (N_ALL', V0_ALL', S_ALL', V1_ALL') of every phase set, replicate and cell: the counters zeroed, then
+// k_spike_phase_counts.  Everything is checked on the host copies before anything is enqueued.
+int smc_spike_phase_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, const uint32_t* d_joint_cnt, const uint32_t* d_joint_off,
+                           const uint32_t* joint_off_host, const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_cnt_off,
+                           const uint32_t* d_pos1, int32_t n_sets, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
+                           int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream) {
+    const std::string who = "smc_spike_phase_counts";
+    if (!ctx || n_sets < 0 || n_reps < 0 || n_targets < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_sets > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_sets) + " sets, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
+    if (n_targets > SMC_SPIKE_REP_MAX_TARGETS)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_SPIKE_REP_MAX_TARGETS));
+    if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
+    if (n_fracs < 1) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_fracs) + " fractions, at least 1 expected");
+    if ((n_reps && !d_seeds) || (n_targets && !thr) || !depth_thr) return fail(SMC_E_ARG, who + ": NULL argument");
+    if ((int64_t)n_targets * (int64_t)n_fracs > SMC_AF_DEPTH_MAX_CELLS)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets x " + std::to_string(n_fracs) + " fractions, at most " +
+                                 std::to_string(SMC_AF_DEPTH_MAX_CELLS) + " cells");
+    SpkThr T;
+    AfdThr D;
+    memset(&T, 0, sizeof T);
+    memset(&D, 0, sizeof D);
+    for (int32_t t = 0; t < n_targets; ++t) {
+        if (thr[t] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": target " + std::to_string(t) + ": a threshold above 2^32");
+        T.t[t] = thr[t];
+    }
+    int with_depth = 0;
+    for (int32_t f = 0; f < n_fracs; ++f) {
+        if (depth_thr[f] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": depth threshold " + std::to_string(f) + " is above 2^32");
+        D.f[f] = depth_thr[f];
+        with_depth |= depth_thr[f] < (1ull << 32);
+    }
+    if ((double)n_sets * (double)n_reps * (double)n_targets * (double)n_fracs * (double)SPP_COUNTERS >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_sets) + " sets x " + std::to_string(n_reps) + " replicates x " +
+                                 std::to_string(n_targets) + " targets x " + std::to_string(n_fracs) + " fractions: too many counters for one call");
+    if (!n_sets || !n_reps || !n_targets) return SMC_OK;
+    if (!joint_off_host || !d_joint_off || !set_m_host || !d_set_m || !d_cnt_off || !d_pos1 || !d_out) return fail(SMC_E_ARG, who + ": NULL argument");
+    uint32_t widest = 0;
+    double cnt_words = 0.0;
+    for (int32_t g = 0; g < n_sets; ++g) {
+        if (set_m_host[g] < 1 || set_m_host[g] > SMC_SPIKE_PHASE_MAX_MEMBERS)
+            return fail(SMC_E_INPUT, who + ": set " + std::to_string(g) + " has " + std::to_string(set_m_host[g]) + " members, 1 .. " +
+                                     std::to_string(SMC_SPIKE_PHASE_MAX_MEMBERS) + " expected");
+        if (joint_off_host[g + 1] < joint_off_host[g]) return fail(SMC_E_INPUT, who + ": the offsets decrease at set " + std::to_string(g));
+        widest = std::max(widest, joint_off_host[g + 1] - joint_off_host[g]);
+        cnt_words += 3.0 * (double)set_m_host[g] * (double)(joint_off_host[g + 1] - joint_off_host[g]);
+    }
+    if (joint_off_host[n_sets] >= 0x55555500u || cnt_words >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": too many joint barcodes for one call");
+    if (joint_off_host[n_sets] && (!d_joint_ident || !d_joint_cnt)) return fail(SMC_E_ARG, who + ": NULL joint barcodes");
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t n_out = (size_t)SPP_COUNTERS * (size_t)n_sets * (size_t)n_reps * (size_t)n_targets * (size_t)n_fracs;
+    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
+    if (widest)
+        hipLaunchKernelGGL(k_spike_phase_counts, dim3((unsigned)std::min<uint32_t>((widest + SPR_BLOCK - 1) / SPR_BLOCK, 256u), (unsigned)n_sets,
+                                                      (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPR_BLOCK), 0, st,
+                           (const unsigned long long*)d_joint_ident, d_joint_cnt, d_joint_off, d_set_m, d_cnt_off, d_pos1, T, (int)n_targets, D,
+                           (int)n_fracs, with_depth, (const unsigned long long*)d_seeds, (int)n_reps, d_out);
     HIPCHK(hipGetLastError());
     return SMC_OK;
 }

@@ -8,7 +8,9 @@
 // lane each) and per listed variant v whose 0-based position lies in the alignment's [pos, end) (the variants are sorted by
 // position: a binary search for the first, then along the array):
 //   draw     u_v(b) = word 0 of Philox4x32-10(counter = (identity lo, identity hi, "spAF", (pos0 + 1) mod 2^32), key = seed lo, hi)
-//            of the alignment's barcode b; b is spiked at v when u_v(b) < thr_v (thr in [0, 2^32])
+//            of the alignment's barcode b; b is spiked at v when u_v(b) < thr_v (thr in [0, 2^32]).  --spikePhase: a member of a phase
+//            set (V.lead != 0) draws with the position of its set's leader, var[k - V.lead] - one load more, for such records only
+//            (the host checked lead <= k); every member of a set then makes the same draw: all of them are hit or none
 //   column   bp2_resolve at pos0; the record is rewritten when its allele key there is a single letter: a base (not inside a
 //            deletion) with no insertion or deletion starting behind it
 //   store    ALT into the letter byte of that base (the quality byte next to it stays); NM + 1 when the old letter was REF
@@ -36,7 +38,7 @@ __global__ __launch_bounds__(SPK_BLOCK) void k_spike(const smc_dev_aln* __restri
             const smc_spike_variant V = var[k];
             if (V.pos0 >= a.end) break;
             uint32_t x[4];
-            smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, (uint32_t)V.pos0 + 1u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+            smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, (uint32_t)(V.lead ? var[k - (int)V.lead].pos0 : V.pos0) + 1u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
             if (!((unsigned long long)x[0] < V.thr)) continue;
             const BpRes r = bp2_resolve(cig + a.cig_off, (int)a.n_cig, a.pos, V.pos0, (int)a.l_seq);
             if (r.isdel || r.indel != 0 || r.qpos < 0 || r.qpos >= (int)a.l_seq) continue;

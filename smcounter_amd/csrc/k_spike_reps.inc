@@ -10,7 +10,8 @@
 //                  every copy complete.
 //   k_spike_reps   k_spike with blockIdx.y = copy: a lane per alignment, the copy's seed and threshold from the argument block (at most
 //                  SMC_SPIKE_MAX_COPIES of each travel by value), one draw per (lane, variant in span, copy), bp2_resolve only behind a
-//                  draw that hits, SMC_DA_MMOK recomputed for every alignment of every copy.
+//                  draw that hits, SMC_DA_MMOK recomputed for every alignment of every copy.  A member of a phase set draws with its
+//                  leader's position, as in k_spike.
 //   k_spike_counts a lane per covering barcode of a listed variant (blockIdx.y = variant, blockIdx.z strides over the replicates): ONE
 //                  Philox per (barcode, variant, replicate), compared against all T thresholds; per target the three sums over the
 //                  wavefront (ballot + popcount for S and V1, a DPP sum for READS), the workgroup's four wavefronts added in LDS, then
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(SPK_BLOCK) void k_spike_reps(const smc_dev_aln* __r
             const smc_spike_variant V = var[k];                  // (V.thr is not read: the copy's threshold holds for every variant)
             if (V.pos0 >= a.end) break;
             uint32_t x[4];
-            smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, (uint32_t)V.pos0 + 1u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+            smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, (uint32_t)(V.lead ? var[k - (int)V.lead].pos0 : V.pos0) + 1u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
             if (!((unsigned long long)x[0] < thr)) continue;
             const BpRes r = bp2_resolve(cig + a.cig_off, (int)a.n_cig, a.pos, V.pos0, (int)a.l_seq);
             if (r.isdel || r.indel != 0 || r.qpos < 0 || r.qpos >= (int)a.l_seq) continue;

@@ -78,6 +78,7 @@
 #include "k_spike.inc"         // --spikeAF: listed SNVs written into a copy of a run's bases, NM and the mismatch bit with them
 #include "k_spike_reps.inc"    // --spikeReps: B spiked copies of a run per call; (S, READS, V1) per variant, replicate and target without a copy
 #include "k_spike_depth.inc"   // --spikeDepth: (N', V0', S', READS', V1') per variant, replicate and cell (spike target x barcode fraction)
+#include "k_spike_phase.inc"   // --spikePhase: (N_ALL', V0_ALL', S_ALL', V1_ALL') per phase set, replicate and cell: the molecules that carry a whole haplotype
 #include "k_lod.inc"           // --lod: the limit of detection per barcode depth (one lane per depth, Brent root search in FP64)
 #include "k_plan.inc"          // launch plan of a batch whose descriptors are in HBM (classify + fill)
 #include "host_abi.inc"        // the C ABI of include/smcounter_hip.h

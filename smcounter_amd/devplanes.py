@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes
 import dataclasses
+import functools
 import os
 from typing import List, Sequence, Tuple
 
@@ -1314,9 +1315,13 @@ SPIKE_MAX_TARGETS = 32
 
 
 class SpikeSet(object):
-    """The listed SNVs of --spikeAF by chromosome, ascending by position, as smc_spike_alleles takes them (without thresholds)."""
+    """The listed SNVs of --spikeAF by chromosome, ascending by position, as smc_spike_alleles takes them (without thresholds).  With
+    phase sets (tools.spike_variants.PhasedVariants: --spikePhase) every record's `lead` says how far back its set's leader stands;
+    lead_pos[k]: the leader's 1-based position of variant k of the list given - counter word 3 of its draw, its own without sets."""
 
     def __init__(self, variants):
+        from .tools import spike_variants as sv
+        self.lead_pos = sv.leaders(variants)
         self.variants = list(variants)
         self.by_chrom = {}
         for c in sorted({v.chrom for v in self.variants}):
@@ -1325,6 +1330,8 @@ class SpikeSet(object):
             for j, k in enumerate(order):
                 v = self.variants[k]
                 var[j]["pos0"], var[j]["ref"], var[j]["alt"] = v.pos - 1, ord(v.ref), ord(v.alt)
+                # (the leader has the set's smallest position: it stands in front, on the same chromosome)
+                var[j]["lead"] = j - next(i for i, m in enumerate(order) if self.variants[m].pos == self.lead_pos[k])
             self.by_chrom[c] = (var, order)
 
     def chrom_variants(self, chrom: str, t: float):
@@ -1374,7 +1381,7 @@ def spike_run(eng, up: RunOnDevice, A, var: np.ndarray, idents, seed: int, misma
 
 
 def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng, nthreads: int = 0, max_reads: int = 128_000_000,
-                keep: dict = None, keep_bytes: int = None, depth: dict = None):
+                keep: dict = None, keep_bytes: int = None, depth: dict = None, phase: dict = None):
     """DsRules of --spikeAF, one per target, and the pre-pass: only the runs around the listed loci are decoded (as ds_af_sets groups
     them); smc_allele_carriers gives N and V0 of every variant, then per target smc_spike_alleles writes the spiked copy and
     smc_allele_carriers on it gives V1.  The kernel's statistics are checked against the host's restatement of the draws: the records
@@ -1390,7 +1397,14 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     `depth` (--spikeDepth: dict with "fracs" and the "params" of the T x F cells, targets outer): it gets "rules", the cells' DsRules,
     and "counts", per variant and cell dict(N, V0, S, READS, V1) - one smc_spike_depth_counts call with this seed over the covers
     and counters above.  Every cell's (N, V0, V1) is also counted a second way - select_run at f over the spiked copy of t (over the
-    run itself for V0), then smc_allele_carriers on the selection - and a difference raises RuntimeError."""
+    run itself for V0), then smc_allele_carriers on the selection - and a difference raises RuntimeError.
+    `phase` (--spikePhase: dict with "sets", the tools.spike_variants.PhaseSets of two members or more): every member of a set is
+    drawn with its leader's position (SpikeSet.lead_pos) in the rewrite, in the host's restatement of the draws and in the counts
+    calls.  The dict gets "joint" (per set the identities of the barcodes that cover every member and their counters, spike_joint),
+    "counts", per set and target dict(N_ALL, V0_ALL, S_ALL, V1_ALL) from one smc_spike_phase_counts call with this seed, and with
+    `depth` "depth_counts", the same per cell from a second call.  (N_ALL, V0_ALL, V1_ALL) of every target is also counted a second
+    way - the AND over the members of smc_allele_carriers' cover and carrier bits, on the run and on the spiked copy of that target
+    - and a difference raises RuntimeError."""
     from .tools import ds_allele_fraction as af
     from .tools import spike_variants as sv
     af.unique_idents(bamio.placed_barcodes(path), path)
@@ -1398,7 +1412,9 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     spikes = SpikeSet(variants)
     P = params_list[0]
     rows = [[None] * len(variants) for _ in targets]
-    want_counters = keep is not None or depth is not None
+    psets = list(phase["sets"]) if phase is not None else []
+    want_counters = keep is not None or depth is not None or bool(psets)
+    bits = {}                        # (--spikePhase) variant -> (identities that cover it, that carry it before, per target after)
     covers, counters = [None] * len(variants), [None] * len(variants)
     if keep is not None:
         keep.update(runs=[], covers=covers, counters=counters, spikes=spikes)
@@ -1457,7 +1473,10 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                         spiked.aln.free(); spiked.bq.free()
                     for r, k in enumerate(group):
                         v = variants[k]
-                        hit = sv.draw(idents, seed, v.pos) < np.uint64(sv.threshold(target))
+                        hit = sv.draw(idents, seed, spikes.lead_pos[k]) < np.uint64(sv.threshold(target))
+                        if psets:
+                            b = bits.setdefault(k, (idents[cov[r][:len(idents)]], idents[car[r][:len(idents)]], [None] * len(targets)))
+                            b[2][t] = idents[car1[r][:len(idents)]]
                         reads = int(stats[sorder.index(k), 0])
                         if not np.array_equal(cov1[r], cov[r]) or reads != int(cnt1[r, hit[:cnt1.shape[1]], 1].sum()) or \
                                 bool((car1[r] != car[r])[~hit[:car.shape[1]]].any()):
@@ -1501,7 +1520,7 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     rules = [DsRule(1.0, Pt, seed=int(seed), af=float(t), spike=spikes) for t, Pt in zip(targets, params_list)]
     if depth is not None:
         try:
-            got = spike_depth_counts(eng, [v.pos for v in variants], covers, counters, [int(seed) & 0xFFFFFFFFFFFFFFFF],
+            got = spike_depth_counts(eng, spikes.lead_pos, covers, counters, [int(seed) & 0xFFFFFFFFFFFFFFFF],
                                      [sv.threshold(t) for t in targets], [frac_threshold(f) for f in fracs])[:, 0]
             for (k, t, f), mine in second.items():
                 if [int(got[k, t, f, c]) for c in (0, 1, 4)] != mine:
@@ -1517,6 +1536,31 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                            for k in range(len(variants))]
         depth["rules"] = [DsRule(float(f), Pc, seed=int(seed), af=float(t), spike=spikes, bc_thr=frac_threshold(f))
                           for (t, f), Pc in zip(((t, f) for t in targets for f in fracs), depth["params"])]
+    if psets:
+        try:
+            joint = spike_joint(psets, covers, counters)
+            lead = [spikes.lead_pos[s.members[0]] for s in psets]
+            s0, thr = [int(seed) & 0xFFFFFFFFFFFFFFFF], [sv.threshold(t) for t in targets]
+            got = spike_phase_counts(eng, lead, joint, s0, thr, [1 << 32])[:, 0, :, 0]
+            both = lambda sets: len(functools.reduce(np.intersect1d, sets))
+            for g, ps in enumerate(psets):
+                for t in range(len(targets)):
+                    mine = [both([bits[k][0] for k in ps.members]), both([bits[k][1] for k in ps.members]),
+                            both([bits[k][2][t] for k in ps.members])]
+                    if [int(got[g, t, c]) for c in (0, 1, 3)] != mine:
+                        raise RuntimeError("--spikePhase: set %s at %g: the counts call says (N_ALL, V0_ALL, V1_ALL) = %r, the carrier bits of "
+                                           "the spiked copy %r" % (ps.name, targets[t], [int(got[g, t, c]) for c in (0, 1, 3)], mine))
+            names = ("N_ALL", "V0_ALL", "S_ALL", "V1_ALL")
+            phase["joint"] = joint
+            phase["counts"] = [[dict(zip(names, (int(x) for x in got[g, t]))) for t in range(len(targets))] for g in range(len(psets))]
+            if depth is not None:
+                cells = spike_phase_counts(eng, lead, joint, s0, thr, [frac_threshold(f) for f in fracs])[:, 0]
+                phase["depth_counts"] = [[dict(zip(names, (int(x) for x in cells[g, t, f]))) for t in range(len(targets))
+                                          for f in range(len(fracs))] for g in range(len(psets))]
+        except BaseException:
+            if keep is not None:
+                free_af_runs(keep["runs"])
+            raise
     return rules, [dict(target=t, rows=r) for t, r in zip(targets, rows)]
 
 
@@ -1847,6 +1891,59 @@ def spike_depth_counts(eng, positions, covers, counters, seeds, thresholds, dept
     return out.reshape(shape)
 
 
+def spike_joint(sets, covers, counters):
+    """Per phase set (tools.spike_variants.PhaseSet) -> (uint64 [n]: the identities of the barcodes that cover EVERY member, ascending;
+    uint32 [n, M, 3]: their (reads, alt0, single) at each member, in the set's order).  covers[v] / counters[v]: per listed variant
+    its covering identities and their counters, as spike_rep_counts takes them."""
+    out = []
+    for s in sets:
+        ids = [np.asarray(covers[k], np.uint64) for k in s.members]
+        both = np.unique(functools.reduce(np.intersect1d, ids))
+        cnt = np.zeros((len(both), len(s.members), 3), np.uint32)
+        for m, (k, x) in enumerate(zip(s.members, ids)):
+            order = np.argsort(x, kind="stable")
+            at = order[np.searchsorted(x[order], both)] if len(both) else np.zeros(0, np.int64)
+            cnt[:, m] = np.asarray(counters[k], np.uint32).reshape(-1, 3)[at]
+        out.append((both, cnt))
+    return out
+
+
+def spike_phase_counts(eng, lead_positions, joint, seeds, thresholds, depth_thresholds) -> np.ndarray:
+    """smc_spike_phase_counts -> uint32 [G, R, T, F, 4] = (N_ALL', V0_ALL', S_ALL', V1_ALL') of every phase set, replicate and cell.
+    lead_positions[g]: the 1-based position of the set's leader; joint[g]: (uint64 [n_g] identities of the barcodes that cover every
+    member, uint32 [n_g, M_g, 3] their (reads, alt0, single) per member) - spike_joint's; the rest as spike_depth_counts takes it."""
+    from .engine import DevBuf
+    G, seeds = len(joint), np.ascontiguousarray(seeds, np.uint64)
+    thr, dthr = np.ascontiguousarray(thresholds, np.uint64), np.ascontiguousarray(depth_thresholds, np.uint64)
+    shape = (G, len(seeds), len(thr), len(dthr), 4)
+    cnts = [np.ascontiguousarray(c, np.uint32) for _, c in joint]
+    for (ids, _), c in zip(joint, cnts):
+        if c.ndim != 3 or c.shape[0] != len(ids) or c.shape[2] != 3:
+            raise ValueError("spike_phase_counts: %d joint barcodes, counters of shape %r" % (len(ids), c.shape))
+    off = np.zeros(G + 1, np.uint32)
+    off[1:] = np.cumsum([len(ids) for ids, _ in joint])
+    set_m = np.array([c.shape[1] for c in cnts], np.uint32)
+    cnt_off = np.zeros(G, np.uint32)
+    if G > 1:
+        cnt_off[1:] = np.cumsum([c.size for c in cnts])[:-1]
+    ident = np.concatenate([np.asarray(ids, np.uint64) for ids, _ in joint]) if G else np.zeros(0, np.uint64)
+    cnt = np.concatenate([c.reshape(-1) for c in cnts]) if G else np.zeros(0, np.uint32)
+    pos = np.array([int(p) & 0xFFFFFFFF for p in lead_positions], np.uint32)
+    n_out = int(np.prod(shape))
+    up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.reshape(-1) if a.size else np.zeros(1, a.dtype))
+    bufs = [up(ident), up(cnt), up(off), up(set_m), up(cnt_off), up(pos), up(seeds), DevBuf(eng, 4 * max(1, n_out) + 256)]
+    try:
+        _lib.check(eng.L.smc_spike_phase_counts(eng.ctx, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data,
+                                                bufs[3].data_ptr(), set_m.ctypes.data, bufs[4].data_ptr(), bufs[5].data_ptr(), G,
+                                                bufs[6].data_ptr(), len(seeds), thr.ctypes.data, len(thr), dthr.ctypes.data, len(dthr),
+                                                bufs[7].data_ptr(), ctypes.c_void_p(0)), "smc_spike_phase_counts")
+        out = bufs[7].download(np.uint32, n_out) if n_out else np.zeros(0, np.uint32)          # (the default stream: behind the kernel)
+    finally:
+        for b in bufs:
+            b.free()
+    return out.reshape(shape)
+
+
 def spike_copy_strides(n_aln: int, n_pairs: int):
     """The byte strides between the copies of one smc_spike_alleles_reps call: a copy's records / pair pool rounded up to 256 bytes."""
     return (36 * max(1, n_aln) + 255) & ~255, (2 * max(1, n_pairs) + 255) & ~255
@@ -1976,7 +2073,7 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
 
 
 def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int, n_reps: int, eng, keep: dict, sampler: str = "reference",
-                     sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, depth: dict = None):
+                     sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, depth: dict = None, phase: dict = None):
     """The replicate stage of --spikeReps.  Replicate j is --spikeAF with seed (seed + j) mod 2^64.  One smc_spike_rep_counts call
     gives (S, READS, V1) of every variant, replicate and target from what the pre-pass kept (spike_rules' `keep`) - no spiked copy is
     needed for them; then per kept run and target as many replicates as fit SPIKE_REP_BATCH_BYTES (and AF_REP_BATCH_SLOTS read
@@ -1987,7 +2084,10 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
     `depth` (--spikeDepth: dict with "fracs" and the "params" of the T x F cells, targets outer): one smc_spike_depth_counts call gives
     "depth_counts", uint32 [V, R, T, F, 5], and every copy is also selected and built once per fraction (_spike_rep_call's `cells`):
     `rows` then also holds (variant index, T + t x F + f, replicate).  The copies' READS are checked against the f = 1 numbers, as
-    without it."""
+    without it.
+    `phase` (--spikePhase: spike_rules' dict): the draws are the sets' (SpikeSet.lead_pos), and the result gets "phase_counts", uint32
+    [G, R, T, 4] = (N_ALL, V0_ALL, S_ALL, V1_ALL) of every set, replicate and target from one smc_spike_phase_counts call, with
+    `depth` also "phase_depth_counts", uint32 [G, R, T, F, 4], from a second."""
     import time
     from . import dsaf
     from .tools import spike_variants as sv
@@ -2003,12 +2103,18 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
     max_depth = eng.L.smc_build_max_depth()
     try:
         t0 = time.perf_counter()
-        counts = spike_rep_counts(eng, [v.pos for v in variants], keep["covers"], keep["counters"], seeds, thr)
+        counts = spike_rep_counts(eng, spikes.lead_pos, keep["covers"], keep["counters"], seeds, thr)
         depth_counts = None
         F = len(depth["fracs"]) if depth is not None else 0
         if depth is not None:
-            depth_counts = spike_depth_counts(eng, [v.pos for v in variants], keep["covers"], keep["counters"], seeds, thr,
+            depth_counts = spike_depth_counts(eng, spikes.lead_pos, keep["covers"], keep["counters"], seeds, thr,
                                               [frac_threshold(f) for f in depth["fracs"]])
+        phase_counts = phase_depth_counts = None
+        if phase is not None and phase.get("joint"):
+            lead = [spikes.lead_pos[s.members[0]] for s in phase["sets"]]
+            phase_counts = spike_phase_counts(eng, lead, phase["joint"], seeds, thr, [1 << 32])[:, :, :, 0]
+            if depth is not None:
+                phase_depth_counts = spike_phase_counts(eng, lead, phase["joint"], seeds, thr, [frac_threshold(f) for f in depth["fracs"]])
         times["counts"] = time.perf_counter() - t0
         for run in keep["runs"]:
             if run.A is None:
@@ -2055,7 +2161,8 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
     finally:
         free_af_runs(keep["runs"])
     times["stage"] = time.perf_counter() - t_start
-    return dict(seeds=seeds, counts=counts, rows=rows, times=times, depth_counts=depth_counts)
+    return dict(seeds=seeds, counts=counts, rows=rows, times=times, depth_counts=depth_counts, phase_counts=phase_counts,
+                phase_depth_counts=phase_depth_counts)
 
 
 def _fnv64(text: str) -> int:

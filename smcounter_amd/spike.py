@@ -8,6 +8,10 @@ devplanes.spike_replicates).
 --spikeDepth: the cells (target t, barcode fraction f) of the spike-ins - their flag, prefixes and mtDepths (depth_cells), and the four
 pages <outPrefix>.spikeAF.depth.detection.txt, .replicates.txt, .sensitivity.txt and .curve.txt, which mirror .dsAF.depth.*.
 
+--spikePhase: MNV lines and PS= entries of the variants file are phase sets, whose members share one draw (phase); the joint pages
+<outPrefix>.spikeAF.phase.txt, .phase.replicates.txt and .phase.sensitivity.txt say how many molecules carry a whole set and whether
+all of it was called.
+
 The semantics are tools/spike_variants.py's (DESIGN.md "--spikeAF"); the rewrite on the GPU is csrc/k_spike.inc (smc_spike_alleles),
 the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the main pass are devplanes.spike_rules / spike_run.
 """
@@ -60,10 +64,10 @@ def targets(args):
 
 
 def variants(args, loc_list, fasta):
-    """The variants of --spikeVariants, checked: the file's refusals (tools.spike_variants.parse_variants: SNVs only), REF the
-    genome's letter, every variant a locus of --bedTarget."""
+    """The variants of --spikeVariants, checked: the file's refusals (tools.spike_variants.parse_variants: SNVs only, with
+    --spikePhase MNV lines and PS= sets as well), REF the genome's letter, every variant a locus of --bedTarget."""
     try:
-        out = sv.parse_variants(args.spikeVariants, "--spikeVariants")
+        out = sv.parse_variants(args.spikeVariants, "--spikeVariants", phased=bool(getattr(args, "spikePhase", False)))
         sv.check_reference(out, fasta, "--spikeVariants")
         loci = set((c, int(p)) for c, p in loc_list)
         for v in out:
@@ -338,3 +342,95 @@ def write_depth_curve(out_prefix: str, variants, targets, fracs, full, cells, fu
                 mine = [cells[t * F + k] for t in range(T)]
                 fh.write(depth_curve_line(v, f, [c[3] for c in mine], targets, [entries[(i, t * F + k)] for t in range(T)],
                                           float(mine[top][5][at]) if with_lod else None) + "\n")
+
+
+# ---- --spikePhase
+PHASE_HEADER = ("SET", "CHROM", "POSITIONS", "REFS", "ALTS", "TARGET", "FRACTION", "MTDEPTH", "N_ALL", "V0_ALL", "S_ALL", "V1_ALL", "AF_ALL",
+                "CALLED_ALL")
+PHASE_REPLICATES_HEADER = PHASE_HEADER[:8] + ("REP", "SEED") + PHASE_HEADER[8:]
+PHASE_SENSITIVITY_HEADER = PHASE_HEADER[:8] + ("REPS", "CALLED_ALL", "RATE", "LO95", "HI95", "AF_MEAN", "AF_MIN", "AF_MAX")
+PHASE_NAMES = ("N_ALL", "V0_ALL", "S_ALL", "V1_ALL")
+
+
+def phase(args, spike_targets) -> bool:
+    """--spikePhase -> whether the variants file is read for phase sets.  SystemExit: without --spikeAF."""
+    if not getattr(args, "spikePhase", False):
+        return False
+    if not spike_targets:
+        raise SystemExit("--spikePhase plants the phase sets of --spikeVariants together: it needs --spikeAF")
+    return True
+
+
+def _af_all(r) -> float:
+    return float(r["V1_ALL"]) / r["N_ALL"] if r["N_ALL"] else 0.0
+
+
+def _set_fields(pset, variants, target, frac, mt_depth):
+    vs = [variants[k] for k in pset.members]
+    return [pset.name, pset.chrom, ",".join("%d" % v.pos for v in vs), ",".join(v.ref for v in vs), ",".join(v.alt for v in vs),
+            dsaf.target_text(target), dsaf.FULL if frac is None else "%g" % frac, "%d" % mt_depth]
+
+
+def called_all(pset, variants, cut) -> int:
+    """1 when `cut` ((chrom, pos text) -> (REF, ALT list) of an output's .cut.txt) has every member of the set with its ALT."""
+    for k in pset.members:
+        v = variants[k]
+        c = cut.get((v.chrom, "%d" % v.pos))
+        if c is None or c[0] != v.ref or v.alt not in c[1]:
+            return 0
+    return 1
+
+
+def phase_line(pset, variants, target, frac, mt_depth, r, called: int) -> str:
+    """One line of the phase page: set `pset` in one output.  `target` None: the full-depth output; `frac` None: no --spikeDepth
+    cell; `r`: dict(N_ALL, V0_ALL, S_ALL, V1_ALL) of the joint barcodes there."""
+    return "\t".join(_set_fields(pset, variants, target, frac, mt_depth) + ["%d" % r[n] for n in PHASE_NAMES] +
+                     [dsaf.frac_text(_af_all(r)), "%d" % called])
+
+
+def phase_replicate_line(pset, variants, target, frac, mt_depth, rep: int, seed: int, r, called: int) -> str:
+    f = phase_line(pset, variants, target, frac, mt_depth, r, called).split("\t")
+    return "\t".join(f[:8] + ["%d" % rep, "%d" % seed] + f[8:])
+
+
+def phase_sensitivity_line(pset, variants, target, frac, mt_depth, per) -> str:
+    """One line of the phase sensitivity table; `per`: per replicate (dict(N_ALL, V0_ALL, S_ALL, V1_ALL), CALLED_ALL)."""
+    n = len(per)
+    called = sum(c for _, c in per)
+    lo, hi = dsaf.wilson(called, n)
+    afs = [_af_all(r) for r, _ in per]
+    return "\t".join(_set_fields(pset, variants, target, frac, mt_depth) +
+                     ["%d" % n, "%d" % called, dsaf.frac_text(float(called) / n), dsaf.frac_text(lo), dsaf.frac_text(hi),
+                      dsaf.frac_text(sum(afs) / n), dsaf.frac_text(min(afs)), dsaf.frac_text(max(afs))])
+
+
+def write_phase(out_prefix: str, variants, sets, outputs) -> None:
+    """<outPrefix>.spikeAF.phase.txt: a header, then for every set a line per output - full depth first, then the targets, then the
+    --spikeDepth cells.  `outputs`: per output (target or None, fraction or None, mtDepth, prefix, per set dict(N_ALL, V0_ALL, S_ALL,
+    V1_ALL))."""
+    cuts = [dsaf.read_output(o[3])[1] for o in outputs]
+    with open(out_prefix + ".spikeAF.phase.txt", "w") as fh:
+        fh.write("\t".join(PHASE_HEADER) + "\n")
+        for g, pset in enumerate(sets):
+            for (target, frac, depth, _, rows), cut in zip(outputs, cuts):
+                fh.write(phase_line(pset, variants, target, frac, depth, rows[g], called_all(pset, variants, cut)) + "\n")
+
+
+def write_phase_replicates(out_prefix: str, variants, sets, outputs, seeds, entries) -> None:
+    """<outPrefix>.spikeAF.phase.replicates.txt: a line per set, output (targets, then cells: (target, fraction or None, mtDepth)) and
+    replicate.  entries[(set, output)]: per replicate (dict(N_ALL, V0_ALL, S_ALL, V1_ALL), CALLED_ALL)."""
+    with open(out_prefix + ".spikeAF.phase.replicates.txt", "w") as fh:
+        fh.write("\t".join(PHASE_REPLICATES_HEADER) + "\n")
+        for g, pset in enumerate(sets):
+            for c, (target, frac, depth) in enumerate(outputs):
+                for j, (r, called) in enumerate(entries[(g, c)]):
+                    fh.write(phase_replicate_line(pset, variants, target, frac, depth, j, seeds[j], r, called) + "\n")
+
+
+def write_phase_sensitivity(out_prefix: str, variants, sets, outputs, entries) -> None:
+    """<outPrefix>.spikeAF.phase.sensitivity.txt: a line per set and output; the arguments are write_phase_replicates'."""
+    with open(out_prefix + ".spikeAF.phase.sensitivity.txt", "w") as fh:
+        fh.write("\t".join(PHASE_SENSITIVITY_HEADER) + "\n")
+        for g, pset in enumerate(sets):
+            for c, (target, frac, depth) in enumerate(outputs):
+                fh.write(phase_sensitivity_line(pset, variants, target, frac, depth, entries[(g, c)]) + "\n")

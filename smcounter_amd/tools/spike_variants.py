@@ -10,6 +10,9 @@ every target, the files of a plain run on the BAM this writes.
   2. one draw per barcode b (field -2 of the read name) and variant v at 1-based position P: u_v(b) = word 0 of Philox4x32-10(counter =
      (ident lo, ident hi, 0x73704146 "spAF", P mod 2^32), key = seed lo, hi), ident = the 64-bit FNV-1a of the barcode text.  b is
      spiked at v for target t when u_v(b) < floor(t 2^32).  Neighbouring variants draw independently; the spiked sets are nested over t.
+     --phased: the members of a PHASE SET - the SNVs of one MNV line, or the lines that share a PS=<name> entry - all draw with P0,
+     the smallest position of the set, in place of their own P: a barcode is spiked at every member or at none, and a read that
+     showed REF at two members gets NM + 2.  A variant of no set is a set of one: its draw is the one above.
   3. rewrite: every record of a spiked barcode in the pileup of P (pos <= p < end) whose allele key there is a single letter - a base,
      not inside a deletion, with no insertion or deletion starting behind it (smCounter.py:371-460) - gets ALT at that query position.
      Qualities, CIGAR and flags stay.  NM moves with the base, because the caller's incCond reads it (smCounter.py:329-356): + 1 when
@@ -39,9 +42,122 @@ _NM_FMT = {ord("c"): "<b", ord("C"): "<B", ord("s"): "<h", ord("S"): "<H", ord("
 _FIXED = {ord("A"): 1, ord("c"): 1, ord("C"): 1, ord("s"): 2, ord("S"): 2, ord("i"): 4, ord("I"): 4, ord("f"): 4}
 
 
-def parse_variants(path: str, flag: str = "--variants"):
+PHASE_MAX_MEMBERS = 8           # SMC_SPIKE_PHASE_MAX_MEMBERS: members of a phase set, and letters of an MNV line
+PhaseSet = collections.namedtuple("PhaseSet", "name chrom members")     # members: indexes into the variant list, ascending by position
+
+
+class PhasedVariants(list):
+    """parse_variants(phased=True): the member SNVs in file order (an MNV line's members where the line stands), with `sets` - the
+    PhaseSets listed, those of one member too, in the order their first line stands in the file - and `mnvs`, per MNV line (chrom,
+    pos, REF, line number) for check_reference."""
+
+    def __init__(self, variants=(), sets=(), mnvs=()):
+        list.__init__(self, variants)
+        self.sets, self.mnvs = list(sets), list(mnvs)
+
+
+def leaders(variants):
+    """Per variant the 1-based position of its phase set's leader (the member with the smallest position) - counter word 3 of its
+    draw.  A variant of no listed set is a set of one: its own position, today's draw."""
+    out = [v.pos for v in variants]
+    for s in getattr(variants, "sets", ()):
+        for k in s.members:
+            out[k] = variants[s.members[0]].pos
+    return out
+
+
+def phase_sets(variants):
+    """The listed sets with two members or more: what the phase pages report."""
+    return [s for s in getattr(variants, "sets", ()) if len(s.members) >= 2]
+
+
+def _parse_phased(path: str, flag: str):
+    """--spikePhase's reading of the file: ds_allele_fraction.parse_variants' line shapes and refusals, and
+      an MNV line   REF and ALT of one length L, 2 <= L <= PHASE_MAX_MEMBERS, letters out of ACGT: one member SNV per offset where they
+                    differ (at least one), all in one set named chrom:pos;
+      PS=<name>     a `;`-separated entry of column 8 of a VCF-shaped line: the lines of one chromosome with one name are one set (an
+                    MNV line with the entry joins it with all its members).
+    One variant per position over all members; at most PHASE_MAX_MEMBERS members per set; a name on one chromosome only."""
+    out, seen, mnvs = [], set(), []
+    sets, order = {}, []                                         # set key -> [name, chrom, members], and the keys in file order
+    with open(path) as fh:
+        for n, line in enumerate(fh, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip() or line.startswith("#"):
+                continue
+            f = line.split("\t")
+            where = "%s line %d" % (path, n)
+            if len(f) >= 5:
+                chrom, pos, ref, alt = f[0], f[1], f[3], f[4]
+            elif len(f) == 4:
+                chrom, pos, ref, alt = f
+            else:
+                raise ValueError("%s: %d tab-separated columns; VCF (CHROM POS ID REF ALT ...) or `chrom pos ref alt` expected" % (where, len(f)))
+            try:
+                pos = int(pos)
+            except ValueError:
+                raise ValueError("%s: position %r is not an integer" % (where, pos))
+            if pos < 1:
+                raise ValueError("%s: position %d, 1-based positions expected" % (where, pos))
+            ref, alt = ref.upper(), alt.upper()
+            if "," in alt:
+                raise ValueError("%s: ALT %r lists more than one allele (multi-allelic lines are not taken)" % (where, alt))
+            ps = [x[3:] for x in f[7].split(";") if x.startswith("PS=")] if len(f) >= 8 else []
+            if len(ps) > 1 or (ps and not ps[0]):
+                raise ValueError("%s: one PS=<name> entry with a name expected, got %r" % (where, f[7]))
+            if len(ref) == len(alt) and len(ref) >= 2:
+                if len(ref) > PHASE_MAX_MEMBERS:
+                    raise ValueError("%s: %s: an MNV of %d letters, at most %d are taken" % (flag, where, len(ref), PHASE_MAX_MEMBERS))
+                if any(c not in LETTERS for c in ref + alt):
+                    raise ValueError("%s: %s: %s:%d %s>%s: REF and ALT must be made of A, C, G, T" % (flag, where, chrom, pos, ref, alt))
+                members = [(pos + o, r, a) for o, (r, a) in enumerate(zip(ref, alt)) if r != a]
+                if not members:
+                    raise ValueError("%s: %s: %s:%d %s>%s: REF and ALT of the MNV do not differ in any letter" % (flag, where, chrom, pos, ref, alt))
+                mnvs.append((chrom, pos, ref, n))
+                key = ("PS", ps[0]) if ps else ("MNV", chrom, pos)
+                name = ps[0] if ps else "%s:%d" % (chrom, pos)
+            else:
+                ka = af.allele_key(ref, alt)
+                if ka is None:
+                    if len(ref) != len(alt):
+                        raise ValueError("%s: %s: REF %r / ALT %r have different lengths and are neither an insertion (X / XS) nor a "
+                                         "deletion (XD / X)" % (flag, where, ref, alt))
+                    raise ValueError("%s: REF %r / ALT %r is neither a substitution of one letter, an insertion (X / XS) nor a "
+                                     "deletion (XD / X)" % (where, ref, alt))
+                if ka[1] != af.SNV:
+                    raise ValueError("%s: %s:%d %s>%s is an insertion or a deletion; only one-letter substitutions can be spiked (an indel "
+                                     "means rewriting CIGARs)" % (flag, chrom, pos, ref, alt))
+                if ref not in LETTERS or alt not in LETTERS:
+                    raise ValueError("%s: %s:%d %s>%s: REF and ALT must be one of A, C, G, T" % (flag, chrom, pos, ref, alt))
+                members = [(pos, ref, alt)]
+                key, name = (("PS", ps[0]), ps[0]) if ps else (None, None)
+            for q, r, a in members:
+                if (chrom, q) in seen:
+                    raise ValueError("%s: %s:%d is listed twice (one variant per position)" % (where, chrom, q))
+                seen.add((chrom, q))
+            if key is not None:
+                if key not in sets:
+                    sets[key] = [name, chrom, []]
+                    order.append(key)
+                if sets[key][1] != chrom:
+                    raise ValueError("%s: %s: the phase set PS=%s is listed on %s and on %s (a set lies on one chromosome)" %
+                                     (flag, where, name, sets[key][1], chrom))
+                sets[key][2] += list(range(len(out), len(out) + len(members)))
+                if len(sets[key][2]) > PHASE_MAX_MEMBERS:
+                    raise ValueError("%s: %s: the phase set %s has %d members, at most %d" % (flag, where, name, len(sets[key][2]), PHASE_MAX_MEMBERS))
+            out += [af.Variant(chrom, q, r, a, a, af.SNV) for q, r, a in members]
+    if not out:
+        raise ValueError("%s lists no variant" % path)
+    return PhasedVariants(out, [PhaseSet(sets[k][0], sets[k][1], tuple(sorted(sets[k][2], key=lambda i: out[i].pos))) for k in order], mnvs)
+
+
+def parse_variants(path: str, flag: str = "--variants", phased: bool = False):
     """The variants of a spike-in file, in file order: ds_allele_fraction.parse_variants' format and refusals, and only one-letter
-    substitutions out of A, C, G, T (an insertion or a deletion would mean rewriting CIGARs).  ValueError names the variant refused."""
+    substitutions out of A, C, G, T (an insertion or a deletion would mean rewriting CIGARs).  ValueError names the variant refused.
+    `phased` (--spikePhase / --phased): MNV lines and PS= entries make phase sets (_parse_phased) -> PhasedVariants; without it an
+    MNV line is refused as ever and PS= entries are not read."""
+    if phased:
+        return _parse_phased(path, flag)
     out = af.parse_variants(path)
     for v in out:
         if v.kind != af.SNV:
@@ -58,6 +174,10 @@ def check_reference(variants, fasta, flag: str = "--variants") -> None:
         letter = fasta.fetch(v.chrom, v.pos - 1, v.pos).upper()
         if letter != v.ref:
             raise ValueError("%s: %s:%d %s>%s: the reference genome has %r there, not %s" % (flag, v.chrom, v.pos, v.ref, v.alt, letter, v.ref))
+    for chrom, pos, ref, n in getattr(variants, "mnvs", ()):     # (an MNV line: its letters that do not change too)
+        letters = fasta.fetch(chrom, pos - 1, pos - 1 + len(ref)).upper()
+        if letters != ref:
+            raise ValueError("%s: line %d: %s:%d REF %s: the reference genome has %r there" % (flag, n, chrom, pos, ref, letters))
 
 
 def threshold(t: float) -> int:
@@ -141,9 +261,11 @@ def rewrite_record(raw: bytes, edits, nm_new) -> bytes:
 
 
 class Plan(object):
-    """The listed variants by chromosome, sorted by position, with the seed and the target's threshold: which of them a record spans."""
+    """The listed variants by chromosome, sorted by position, with the seed and the target's threshold: which of them a record spans.
+    A member of a phase set (parse_variants(phased=True)) draws with its leader's position."""
 
     def __init__(self, variants, t: float, seed: int):
+        self.lead_pos = leaders(variants)
         self.variants, self.t, self.seed, self.thr = list(variants), float(t), int(seed), threshold(t)
         self.by_chrom = collections.defaultdict(list)
         for k, v in enumerate(self.variants):
@@ -163,7 +285,7 @@ class Plan(object):
     def is_spiked(self, k: int, ident: int) -> bool:
         key = (k, ident)
         if key not in self._u:
-            self._u[key] = spiked(ident, self.seed, self.variants[k].pos, self.thr)
+            self._u[key] = spiked(ident, self.seed, self.lead_pos[k], self.thr)
         return self._u[key]
 
 
@@ -234,7 +356,7 @@ def main(args):
     if args.runPath:
         os.chdir(args.runPath)
     try:
-        variants = parse_variants(args.variants)
+        variants = parse_variants(args.variants, phased=bool(getattr(args, "phased", False)))
         targets = af.parse_targets(args.af)
         if len(targets) != 1:
             raise ValueError("--af: one target allele fraction per output BAM, got %r" % args.af)
@@ -258,6 +380,8 @@ def build_parser():
     parser.add_argument("--af", default=None, required=True, help="target allele fraction in (0, 1)")
     parser.add_argument("--seed", type=int, default=1234567, help="Seed of the barcode draws")
     parser.add_argument("--refGenome", default=None, help="indexed FASTA: REF of every listed variant must be its letter there")
+    parser.add_argument("--phased", action="store_true", help="read MNV lines (REF and ALT of one length, 2 to 8 letters) and PS=<name> "
+                        "entries of VCF column 8 as phase sets: the members of a set are planted on the same barcodes")
     return parser
 
 

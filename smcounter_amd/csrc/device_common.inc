@@ -9,6 +9,8 @@ struct KParams {
     int lite_from;   // reference-allele fragments from which a barcode's other alleles get no sequencing-error term (k_call_v2, general path)
     int use_alt;     // k_call_v2: one-allele barcodes of the locus's major OTHER allele are scored from the table too (0: SMC_NO_ALT)
     int tallies_later;   // k_call_v2 leaves the filter-only tallies of the loci it queues to k_filter_tallies (batches with loci of the deep class)
+    int simple_to;   // k_call_v2: fragment count from which no barcode takes a shortcut that never forms rightP (the per-count table, `lite`):
+                     // <= SMC_SIMPLE_N, lower where rightP can leave the normal double range before that (host_abi.inc, simple_to_for)
 };
 
 // header of the per-block LDS image; the tables follow it
@@ -150,6 +152,8 @@ typedef unsigned long long lmask;
 // (smCounter.py:83-96) and   post(allele) = (pne + pcr(0)) / (pne + pcr(0) + 3 pcr(nf)),  post(pad) = pcr(nf) / (same)
 // with pcr(c) = 10^(-6 (c + .5) / (nf + 2))  (:79-81, |uniqBase| = 4).  The two -log10(1 - post) values are
 // tabulated once per context for nf < SMC_SIMPLE_N by the device code below; larger barcodes take the general path.
+// (The cancellation holds while rightP is a normal double: where minBQ is so low that rightP can underflow below SMC_SIMPLE_N
+// fragments, KParams.simple_to sends such barcodes to the general path too, which follows the products down and flags the row.)
 #define SMC_SIMPLE_N 4096
 __global__ void k_simple_table(double* __restrict__ out, int n) {
     const int nf = blockIdx.x * blockDim.x + threadIdx.x;

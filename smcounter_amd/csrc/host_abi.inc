@@ -371,6 +371,19 @@ static int lite_from_for(int min_bq) {
     return (int)std::ceil(24.0 / -std::log10(rho)) + 1;
 }
 
+// The per-count table and `lite` never form rightP: right while the reference's rightP is a normal double (it cancels), wrong
+// once it is not - the reference's posteriors are then denormal rounding, the general path follows them down and flags the row
+// (SMC_ST_UNDERFLOW).  A fragment contributes a factor 1 - e >= 1 - max(0.1, e(minBQ)) (an unpaired fragment 0.1, a merged pair its
+// smaller quality, >= minBQ), so rightP >= 2^-1000 while nf <= 1000 ln 2 / -ln(1 - e): barcodes from that count on (less one, for
+// the rounding of the products) take the general path.  At minBQ >= 9 that is beyond SMC_SIMPLE_N (0.9^n: n = 6,578) and nothing
+// changes; at minBQ 3 it is 995.
+static int simple_to_for(int min_bq) {
+    const double e = std::max(0.1, std::pow(10.0, -0.1 * (double)(min_bq < 0 ? 0 : min_bq)));
+    if (!(e < 1.0)) return 1;                                         // (minBQ 0: a merged pair of quality 0 makes rightP 0)
+    const double lim = std::floor(1000.0 * std::log(2.0) / -std::log1p(-e)) - 1.0;
+    return (int)std::min((double)SMC_SIMPLE_N, std::max(1.0, lim));
+}
+
 template <int BLOCK, bool W16>
 static hipError_t launch_bin(const Bin& b, const KParams& kp, const smc_plan* p, uint32_t* flt_list, const uint32_t* words, const uint32_t* umi_start,
                              smc_row* rows, hipStream_t st) {
@@ -1663,7 +1676,7 @@ static int plan_run_words_impl(smc_plan* p, const smc_params* prm, const uint32_
     for (const Bin& b : p->bins) deep_bins |= b.cls >= SMC_CLS_DEEP;
     if (const char* v = exp_env("SMC_TALLIES_LATER")) deep_bins = atoi(v) != 0;          // (measurements: 1 always, 0 never)
     KParams kp{prm->min_bq, prm->min_mq, prm->mt_drop, prm->primer_dist, prm->ds, prm->smt, lite_from_for(prm->min_bq), exp_env("SMC_NO_ALT") ? 0 : 1,
-               deep_bins ? 1 : 0};
+               deep_bins ? 1 : 0, simple_to_for(prm->min_bq)};
     // Two filter worklists, taken in turn: this run's k_filter_loci zeroes the OTHER list's count (the run before has long
     // finished with it) - no memset per run, a tenth of a 10,000-locus batch's time (C2).  Both counts are zeroed here before a
     // plan's first run (its blocks come from the context's pool; smc_plan_create_dev has k_plan_classify do it) and after a run

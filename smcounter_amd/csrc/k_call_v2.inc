@@ -733,18 +733,19 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BLOCK == 
                     }
                     continue;
                 }
-                if (ALT_OK && ca == nf && nf < SMC_SIMPLE_N && nf > 0) {          // every live fragment shows the major other allele (ca > 0 only where has_alt)
+                if (ALT_OK && ca == nf && nf < P.simple_to && nf > 0) {          // every live fragment shows the major other allele (ca > 0 only where has_alt)
                     bcinfo[k] = (uint16_t)(0x8000 | nf);
                     continue;
                 }
-                if (!(refa < 64u && cr == nf && nf < SMC_SIMPLE_N)) {
+                if (!(refa < 64u && cr == nf && nf < P.simple_to)) {
                     // bit 15: enough reference fragments that the other alleles' sequencing-error terms vanish (`lite`, below)
                     // (not for a barcode of thousands of fragments OF ANY ALLELE - the gate is on nf, not on cr: there the reference's
-                    // products underflow - rightP = 0.9^n leaves the double range near n = 6,700 - and the full walk follows them down)
-                    worklist[atomicAdd(&H->misc[M_NCOMPLEX], 1u)] = (uint16_t)(k | (refa < 64u && cr >= P.lite_from && nf < SMC_SIMPLE_N ? 0x8000 : 0));
+                    // products underflow - rightP = 0.9^n leaves the double range near n = 6,700, with merged pairs of a quality below
+                    // 9 earlier: P.simple_to - and the full walk follows them down)
+                    worklist[atomicAdd(&H->misc[M_NCOMPLEX], 1u)] = (uint16_t)(k | (refa < 64u && cr >= P.lite_from && nf < P.simple_to ? 0x8000 : 0));
                     continue;
                 }
-                bcinfo[k] = (uint16_t)nf;                              // (< SMC_SIMPLE_N = 4096)
+                bcinfo[k] = (uint16_t)nf;                              // (< P.simple_to <= SMC_SIMPLE_N = 4096)
             }
             // (nb1, the wave's keys of bcDict, is summed over the wavefront further down, packed with the other small counts)
             __syncthreads();                                           // the queue of the general path is complete

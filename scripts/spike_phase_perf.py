@@ -6,7 +6,7 @@ repetitions of
 (a) device synchronised around it, one smc_spike_phase_counts call over all (set, replicate, target, fraction) beside one
     smc_spike_depth_counts call over all (variant, replicate, target, fraction), both with their uploads and the copy back;
 (b) one smc_spike_alleles_reps call of 16 copies on the pre-pass's run with the set's `lead` filled, beside the same call with lead =
-    0 everywhere (k_spike_reps makes one more load per record of a set);
+    0 everywhere (k_spike_rewrite makes one more load per record of a set);
 (c) a run with --spikeAF and --spikePhase beside the same run without --spikePhase.
 
 usage: spike_phase_perf.py [n_loci] [n_umi] [rpb] [reps] [out.json]   -> one JSON line (also written to out.json when given)"""

@@ -1167,26 +1167,30 @@ static int spk_check(const std::string& who, smc_ctx* ctx, const smc_dev_aln* d_
     return SMC_OK;
 }
 
-// (--spikeAF) a run's records and pair pool copied, then k_spike over the copies
+// (--spikeAF) a run's records and pair pool copied, then k_spike_rewrite over the one copy, every variant at its own threshold
 int smc_spike_alleles(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, const uint8_t* d_bq, int64_t n_pairs,
                       const smc_spike_variant* d_var, const smc_spike_variant* var_host, int32_t n_var, const uint64_t* d_idents,
                       int64_t n_bc, uint64_t seed, double mismatch_thr, const int32_t* d_nm, const int32_t* d_n_indel,
                       smc_dev_aln* d_aln_out, uint8_t* d_bq_out, uint32_t* d_stats, void* stream) {
     if (int rc = spk_check("smc_spike_alleles", ctx, d_aln, n_aln, d_cig, d_bq, n_pairs, d_var, var_host, n_var, d_idents, n_bc, d_nm, d_n_indel,
                            d_aln_out, d_bq_out, d_stats, true)) return rc;
+    SpkCopies C;
+    memset(&C, 0, sizeof C);
+    C.seed[0] = seed;
     HIPCHK(hipSetDevice(ctx->device));
     const hipStream_t st = (hipStream_t)stream;
     if (n_pairs) HIPCHK(hipMemcpyAsync(d_bq_out, d_bq, 2 * (size_t)n_pairs, hipMemcpyDeviceToDevice, st));
     if (n_var) hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)((2 * n_var + 255) / 256)), dim3(256), 0, st, d_stats, (uint32_t)(2 * n_var));
     if (n_aln)
-        hipLaunchKernelGGL(k_spike, dim3((unsigned)((n_aln + SPK_BLOCK - 1) / SPK_BLOCK)), dim3(SPK_BLOCK), 0, st, d_aln, (uint32_t)n_aln, d_cig,
-                           (unsigned long long)n_pairs, d_var, (int)n_var, (const unsigned long long*)d_idents, (uint32_t)n_bc,
-                           (unsigned long long)seed, mismatch_thr, d_nm, d_n_indel, d_aln_out, d_bq_out, d_stats);
+        hipLaunchKernelGGL(k_spike_rewrite, dim3((unsigned)((n_aln + SPK_BLOCK - 1) / SPK_BLOCK)), dim3(SPK_BLOCK), 0, st, d_aln, (uint32_t)n_aln,
+                           d_cig, (unsigned long long)n_pairs, d_var, (int)n_var, (const unsigned long long*)d_idents, (uint32_t)n_bc, C, 1,
+                           mismatch_thr, d_nm, d_n_indel, (uint8_t*)d_aln_out, 0ull, d_bq_out, 0ull, d_stats);
     HIPCHK(hipGetLastError());
     return SMC_OK;
 }
 
-// (--spikeReps) n_copies spiked copies of a run: k_spike_pool stores the pair pool to every copy, k_spike_reps rewrites behind it
+// (--spikeReps) n_copies spiked copies of a run: k_spike_pool stores the pair pool to every copy, k_spike_rewrite rewrites behind it,
+// every variant at the copy's threshold
 int smc_spike_alleles_reps(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, const uint8_t* d_bq, int64_t n_pairs,
                            const smc_spike_variant* d_var, const smc_spike_variant* var_host, int32_t n_var, const uint64_t* d_idents,
                            int64_t n_bc, const uint64_t* seeds, const uint64_t* thr, int32_t n_copies, double mismatch_thr,
@@ -1221,69 +1225,32 @@ int smc_spike_alleles_reps(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln
     const size_t n_st = 2 * (size_t)n_var * (size_t)n_copies;
     if (n_st) hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_st + 255) / 256, 4096)), dim3(256), 0, st, d_stats, (uint32_t)n_st);
     if (n_aln)
-        hipLaunchKernelGGL(k_spike_reps, dim3((unsigned)((n_aln + SPK_BLOCK - 1) / SPK_BLOCK), (unsigned)n_copies), dim3(SPK_BLOCK), 0, st, d_aln,
+        hipLaunchKernelGGL(k_spike_rewrite, dim3((unsigned)((n_aln + SPK_BLOCK - 1) / SPK_BLOCK), (unsigned)n_copies), dim3(SPK_BLOCK), 0, st, d_aln,
                            (uint32_t)n_aln, d_cig, (unsigned long long)n_pairs, d_var, (int)n_var, (const unsigned long long*)d_idents, (uint32_t)n_bc,
-                           C, mismatch_thr, d_nm, d_n_indel, d_aln_out, (unsigned long long)aln_stride, d_bq_out, (unsigned long long)bq_stride, d_stats);
+                           C, 0, mismatch_thr, d_nm, d_n_indel, d_aln_out, (unsigned long long)aln_stride, d_bq_out, (unsigned long long)bq_stride, d_stats);
     HIPCHK(hipGetLastError());
     return SMC_OK;
 }
 
-// (--spikeReps) (S, READS, V1) of every listed variant, replicate and target: the counters zeroed, then k_spike_counts
-int smc_spike_rep_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_cnt, const uint32_t* d_cov_off,
-                         const uint32_t* cov_off_host, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
-                         const uint64_t* thr, int32_t n_targets, uint32_t* d_out, void* stream) {
-    const std::string who = "smc_spike_rep_counts";
-    if (!ctx || n_var < 0 || n_reps < 0 || n_targets < 0) return fail(SMC_E_ARG, who + ": bad argument");
-    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
+// (--spikeReps, --spikeDepth, --spikePhase) what the three counts entries check, on the host copies and before anything is enqueued,
+// then the counters zeroed and k_spike_cells.  A row is a listed variant, or with `sets` a phase set of set_m_host[g] members whose
+// counters start at d_cnt_off[g].  Without `has_fracs` (smc_spike_rep_counts) the cells are those of one fraction that keeps every
+// barcode.  `want`: k_spike_cells' mask of the counters the entry stores.
+static int spk_cell_counts(const std::string& who, smc_ctx* ctx, const uint64_t* d_ident, const uint32_t* d_cnt, const uint32_t* d_off,
+                           const uint32_t* off_host, bool sets, const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_cnt_off,
+                           const uint32_t* d_pos1, int32_t n_rows, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
+                           int32_t n_targets, bool has_fracs, const uint64_t* depth_thr, int32_t n_fracs, uint32_t want, uint32_t* d_out,
+                           void* stream) {
+    const std::string rows = sets ? " sets" : " variants", row = sets ? "set " : "variant ";
+    const int n_want = __builtin_popcount(want);
+    if (!ctx || n_rows < 0 || n_reps < 0 || n_targets < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_rows > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_rows) + rows + ", at most " + std::to_string(SMC_AF_MAX_VARIANTS));
     if (n_targets > SMC_SPIKE_REP_MAX_TARGETS)
         return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_SPIKE_REP_MAX_TARGETS));
     if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
-    if ((n_reps && !d_seeds) || (n_targets && !thr)) return fail(SMC_E_ARG, who + ": NULL argument");
-    SpkThr T;
-    memset(&T, 0, sizeof T);
-    for (int32_t t = 0; t < n_targets; ++t) {
-        if (thr[t] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": target " + std::to_string(t) + ": a threshold above 2^32");
-        T.t[t] = thr[t];
-    }
-    if ((double)n_var * (double)n_reps * (double)n_targets * 3.0 >= (double)0xFFFFFF00u)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants x " + std::to_string(n_reps) + " replicates x " +
-                                 std::to_string(n_targets) + " targets: too many counters for one call");
-    if (!n_var || !n_reps || !n_targets) return SMC_OK;
-    if (!cov_off_host || !d_cov_off || !d_pos1 || !d_out) return fail(SMC_E_ARG, who + ": NULL argument");
-    uint32_t widest = 0;
-    for (int32_t v = 0; v < n_var; ++v) {
-        if (cov_off_host[v + 1] < cov_off_host[v]) return fail(SMC_E_INPUT, who + ": the offsets decrease at variant " + std::to_string(v));
-        widest = std::max(widest, cov_off_host[v + 1] - cov_off_host[v]);
-    }
-    if (cov_off_host[n_var] >= 0x55555500u) return fail(SMC_E_INPUT, who + ": too many covering barcodes for one call");
-    if (cov_off_host[n_var] && (!d_cov_ident || !d_cov_cnt)) return fail(SMC_E_ARG, who + ": NULL covers");
-    HIPCHK(hipSetDevice(ctx->device));
-    const hipStream_t st = (hipStream_t)stream;
-    const size_t n_out = 3 * (size_t)n_var * (size_t)n_reps * (size_t)n_targets;
-    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
-    if (widest)
-        hipLaunchKernelGGL(k_spike_counts, dim3((unsigned)std::min<uint32_t>((widest + SPR_BLOCK - 1) / SPR_BLOCK, 256u), (unsigned)n_var,
-                                                (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPR_BLOCK), 0, st,
-                           (const unsigned long long*)d_cov_ident, d_cov_cnt, d_cov_off, d_pos1, T, (int)n_targets,
-                           (const unsigned long long*)d_seeds, (int)n_reps, d_out);
-    HIPCHK(hipGetLastError());
-    return SMC_OK;
-}
-
-// (--spikeDepth) (N', V0', S', READS', V1') of every listed variant, replicate and cell (target x barcode fraction): the counters
-// zeroed, then k_spike_depth_counts.  The checks are smc_spike_rep_counts' and, for the fractions, afd_check_table's.
-int smc_spike_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_cnt, const uint32_t* d_cov_off,
-                           const uint32_t* cov_off_host, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
-                           const uint64_t* thr, int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream) {
-    const std::string who = "smc_spike_depth_counts";
-    if (!ctx || n_var < 0 || n_reps < 0 || n_targets < 0) return fail(SMC_E_ARG, who + ": bad argument");
-    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
-    if (n_targets > SMC_SPIKE_REP_MAX_TARGETS)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_SPIKE_REP_MAX_TARGETS));
-    if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
-    if (n_fracs < 1) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_fracs) + " fractions, at least 1 expected");
-    if ((n_reps && !d_seeds) || (n_targets && !thr) || !depth_thr) return fail(SMC_E_ARG, who + ": NULL argument");
-    if ((int64_t)n_targets * (int64_t)n_fracs > SMC_AF_DEPTH_MAX_CELLS)
+    if (has_fracs && n_fracs < 1) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_fracs) + " fractions, at least 1 expected");
+    if ((n_reps && !d_seeds) || (n_targets && !thr) || (has_fracs && !depth_thr)) return fail(SMC_E_ARG, who + ": NULL argument");
+    if (has_fracs && (int64_t)n_targets * (int64_t)n_fracs > SMC_AF_DEPTH_MAX_CELLS)
         return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets x " + std::to_string(n_fracs) + " fractions, at most " +
                                  std::to_string(SMC_AF_DEPTH_MAX_CELLS) + " cells");
     SpkThr T;
@@ -1295,96 +1262,68 @@ int smc_spike_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint
         T.t[t] = thr[t];
     }
     int with_depth = 0;
-    for (int32_t f = 0; f < n_fracs; ++f) {
+    if (!has_fracs) { n_fracs = 1; D.f[0] = 1ull << 32; }
+    for (int32_t f = 0; has_fracs && f < n_fracs; ++f) {
         if (depth_thr[f] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": depth threshold " + std::to_string(f) + " is above 2^32");
-        D.f[f] = depth_thr[f];
+        if (f < SMC_AF_DEPTH_MAX_CELLS) D.f[f] = depth_thr[f];     // (more of them pass the cells' limit only without a target: nothing is launched)
         with_depth |= depth_thr[f] < (1ull << 32);
     }
-    if ((double)n_var * (double)n_reps * (double)n_targets * (double)n_fracs * (double)SPD_COUNTERS >= (double)0xFFFFFF00u)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants x " + std::to_string(n_reps) + " replicates x " +
-                                 std::to_string(n_targets) + " targets x " + std::to_string(n_fracs) + " fractions: too many counters for one call");
-    if (!n_var || !n_reps || !n_targets) return SMC_OK;
-    if (!cov_off_host || !d_cov_off || !d_pos1 || !d_out) return fail(SMC_E_ARG, who + ": NULL argument");
+    if ((double)n_rows * (double)n_reps * (double)n_targets * (double)n_fracs * (double)n_want >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_rows) + rows + " x " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) +
+                                 " targets" + (has_fracs ? " x " + std::to_string(n_fracs) + " fractions" : "") + ": too many counters for one call");
+    if (!n_rows || !n_reps || !n_targets) return SMC_OK;
+    if (!off_host || !d_off || !d_pos1 || !d_out || (sets && (!set_m_host || !d_set_m || !d_cnt_off))) return fail(SMC_E_ARG, who + ": NULL argument");
     uint32_t widest = 0;
-    for (int32_t v = 0; v < n_var; ++v) {
-        if (cov_off_host[v + 1] < cov_off_host[v]) return fail(SMC_E_INPUT, who + ": the offsets decrease at variant " + std::to_string(v));
-        widest = std::max(widest, cov_off_host[v + 1] - cov_off_host[v]);
+    double cnt_words = 0.0;
+    for (int32_t g = 0; g < n_rows; ++g) {
+        const uint32_t m = sets ? set_m_host[g] : 1u;
+        if (m < 1 || m > SMC_SPIKE_PHASE_MAX_MEMBERS)
+            return fail(SMC_E_INPUT, who + ": set " + std::to_string(g) + " has " + std::to_string(m) + " members, 1 .. " +
+                                     std::to_string(SMC_SPIKE_PHASE_MAX_MEMBERS) + " expected");
+        if (off_host[g + 1] < off_host[g]) return fail(SMC_E_INPUT, who + ": the offsets decrease at " + row + std::to_string(g));
+        widest = std::max(widest, off_host[g + 1] - off_host[g]);
+        cnt_words += 3.0 * (double)m * (double)(off_host[g + 1] - off_host[g]);
     }
-    if (cov_off_host[n_var] >= 0x55555500u) return fail(SMC_E_INPUT, who + ": too many covering barcodes for one call");
-    if (cov_off_host[n_var] && (!d_cov_ident || !d_cov_cnt)) return fail(SMC_E_ARG, who + ": NULL covers");
+    // (without sets cnt_words is 3 * off_host[n_rows], below 2^32 - 256 with the first limit)
+    if (off_host[n_rows] >= 0x55555500u || cnt_words >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": too many " + (sets ? "joint" : "covering") + " barcodes for one call");
+    if (off_host[n_rows] && (!d_ident || !d_cnt)) return fail(SMC_E_ARG, who + (sets ? ": NULL joint barcodes" : ": NULL covers"));
     HIPCHK(hipSetDevice(ctx->device));
     const hipStream_t st = (hipStream_t)stream;
-    const size_t n_out = (size_t)SPD_COUNTERS * (size_t)n_var * (size_t)n_reps * (size_t)n_targets * (size_t)n_fracs;
+    const size_t n_out = (size_t)n_want * (size_t)n_rows * (size_t)n_reps * (size_t)n_targets * (size_t)n_fracs;
     hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
     if (widest)
-        hipLaunchKernelGGL(k_spike_depth_counts, dim3((unsigned)std::min<uint32_t>((widest + SPR_BLOCK - 1) / SPR_BLOCK, 256u), (unsigned)n_var,
-                                                      (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPR_BLOCK), 0, st,
-                           (const unsigned long long*)d_cov_ident, d_cov_cnt, d_cov_off, d_pos1, T, (int)n_targets, D, (int)n_fracs, with_depth,
-                           (const unsigned long long*)d_seeds, (int)n_reps, d_out);
+        hipLaunchKernelGGL(k_spike_cells, dim3((unsigned)std::min<uint32_t>((widest + SPR_BLOCK - 1) / SPR_BLOCK, 256u), (unsigned)n_rows,
+                                               (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPR_BLOCK), 0, st,
+                           (const unsigned long long*)d_ident, d_cnt, d_off, sets ? d_set_m : nullptr, sets ? d_cnt_off : nullptr, d_pos1, T,
+                           (int)n_targets, D, (int)n_fracs, with_depth, (const unsigned long long*)d_seeds, (int)n_reps, want, d_out);
     HIPCHK(hipGetLastError());
     return SMC_OK;
 }
 
-// (--spikePhase) (N_ALL', V0_ALL', S_ALL', V1_ALL') of every phase set, replicate and cell: the counters zeroed, then
-// k_spike_phase_counts.  Everything is checked on the host copies before anything is enqueued.
+// (--spikeReps) (S, READS, V1) of every listed variant, replicate and target
+int smc_spike_rep_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_cnt, const uint32_t* d_cov_off,
+                         const uint32_t* cov_off_host, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
+                         const uint64_t* thr, int32_t n_targets, uint32_t* d_out, void* stream) {
+    return spk_cell_counts("smc_spike_rep_counts", ctx, d_cov_ident, d_cov_cnt, d_cov_off, cov_off_host, false, nullptr, nullptr, nullptr, d_pos1,
+                           n_var, d_seeds, n_reps, thr, n_targets, false, nullptr, 1, 0x1Cu, d_out, stream);
+}
+
+// (--spikeDepth) (N', V0', S', READS', V1') of every listed variant, replicate and cell (target x barcode fraction)
+int smc_spike_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_cnt, const uint32_t* d_cov_off,
+                           const uint32_t* cov_off_host, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
+                           const uint64_t* thr, int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream) {
+    return spk_cell_counts("smc_spike_depth_counts", ctx, d_cov_ident, d_cov_cnt, d_cov_off, cov_off_host, false, nullptr, nullptr, nullptr,
+                           d_pos1, n_var, d_seeds, n_reps, thr, n_targets, true, depth_thr, n_fracs, 0x1Fu, d_out, stream);
+}
+
+// (--spikePhase) (N_ALL', V0_ALL', S_ALL', V1_ALL') of every phase set, replicate and cell
 int smc_spike_phase_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, const uint32_t* d_joint_cnt, const uint32_t* d_joint_off,
                            const uint32_t* joint_off_host, const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_cnt_off,
                            const uint32_t* d_pos1, int32_t n_sets, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
                            int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream) {
-    const std::string who = "smc_spike_phase_counts";
-    if (!ctx || n_sets < 0 || n_reps < 0 || n_targets < 0) return fail(SMC_E_ARG, who + ": bad argument");
-    if (n_sets > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_sets) + " sets, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
-    if (n_targets > SMC_SPIKE_REP_MAX_TARGETS)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_SPIKE_REP_MAX_TARGETS));
-    if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
-    if (n_fracs < 1) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_fracs) + " fractions, at least 1 expected");
-    if ((n_reps && !d_seeds) || (n_targets && !thr) || !depth_thr) return fail(SMC_E_ARG, who + ": NULL argument");
-    if ((int64_t)n_targets * (int64_t)n_fracs > SMC_AF_DEPTH_MAX_CELLS)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets x " + std::to_string(n_fracs) + " fractions, at most " +
-                                 std::to_string(SMC_AF_DEPTH_MAX_CELLS) + " cells");
-    SpkThr T;
-    AfdThr D;
-    memset(&T, 0, sizeof T);
-    memset(&D, 0, sizeof D);
-    for (int32_t t = 0; t < n_targets; ++t) {
-        if (thr[t] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": target " + std::to_string(t) + ": a threshold above 2^32");
-        T.t[t] = thr[t];
-    }
-    int with_depth = 0;
-    for (int32_t f = 0; f < n_fracs; ++f) {
-        if (depth_thr[f] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": depth threshold " + std::to_string(f) + " is above 2^32");
-        D.f[f] = depth_thr[f];
-        with_depth |= depth_thr[f] < (1ull << 32);
-    }
-    if ((double)n_sets * (double)n_reps * (double)n_targets * (double)n_fracs * (double)SPP_COUNTERS >= (double)0xFFFFFF00u)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_sets) + " sets x " + std::to_string(n_reps) + " replicates x " +
-                                 std::to_string(n_targets) + " targets x " + std::to_string(n_fracs) + " fractions: too many counters for one call");
-    if (!n_sets || !n_reps || !n_targets) return SMC_OK;
-    if (!joint_off_host || !d_joint_off || !set_m_host || !d_set_m || !d_cnt_off || !d_pos1 || !d_out) return fail(SMC_E_ARG, who + ": NULL argument");
-    uint32_t widest = 0;
-    double cnt_words = 0.0;
-    for (int32_t g = 0; g < n_sets; ++g) {
-        if (set_m_host[g] < 1 || set_m_host[g] > SMC_SPIKE_PHASE_MAX_MEMBERS)
-            return fail(SMC_E_INPUT, who + ": set " + std::to_string(g) + " has " + std::to_string(set_m_host[g]) + " members, 1 .. " +
-                                     std::to_string(SMC_SPIKE_PHASE_MAX_MEMBERS) + " expected");
-        if (joint_off_host[g + 1] < joint_off_host[g]) return fail(SMC_E_INPUT, who + ": the offsets decrease at set " + std::to_string(g));
-        widest = std::max(widest, joint_off_host[g + 1] - joint_off_host[g]);
-        cnt_words += 3.0 * (double)set_m_host[g] * (double)(joint_off_host[g + 1] - joint_off_host[g]);
-    }
-    if (joint_off_host[n_sets] >= 0x55555500u || cnt_words >= (double)0xFFFFFF00u)
-        return fail(SMC_E_INPUT, who + ": too many joint barcodes for one call");
-    if (joint_off_host[n_sets] && (!d_joint_ident || !d_joint_cnt)) return fail(SMC_E_ARG, who + ": NULL joint barcodes");
-    HIPCHK(hipSetDevice(ctx->device));
-    const hipStream_t st = (hipStream_t)stream;
-    const size_t n_out = (size_t)SPP_COUNTERS * (size_t)n_sets * (size_t)n_reps * (size_t)n_targets * (size_t)n_fracs;
-    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
-    if (widest)
-        hipLaunchKernelGGL(k_spike_phase_counts, dim3((unsigned)std::min<uint32_t>((widest + SPR_BLOCK - 1) / SPR_BLOCK, 256u), (unsigned)n_sets,
-                                                      (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPR_BLOCK), 0, st,
-                           (const unsigned long long*)d_joint_ident, d_joint_cnt, d_joint_off, d_set_m, d_cnt_off, d_pos1, T, (int)n_targets, D,
-                           (int)n_fracs, with_depth, (const unsigned long long*)d_seeds, (int)n_reps, d_out);
-    HIPCHK(hipGetLastError());
-    return SMC_OK;
+    return spk_cell_counts("smc_spike_phase_counts", ctx, d_joint_ident, d_joint_cnt, d_joint_off, joint_off_host, true, d_set_m, set_m_host,
+                           d_cnt_off, d_pos1, n_sets, d_seeds, n_reps, thr, n_targets, true, depth_thr, n_fracs, 0x17u, d_out, stream);
 }
 
 // (--dsAFReps, --dsAFDepth) what the four entries check of the carrier table, on its host copy, and of the fractions' thresholds

@@ -32,8 +32,10 @@
 //   k_af_depth.inc       --dsAFReps, --dsAFDepth: the keep masks of R replicate dilutions per run and their achieved counts, from the
 //                        carrier table, per cell (target x barcode fraction): the --dsAF draw and the --dsMT philox draw.  The
 //                        replicates without depths are the cells of one fraction that keeps every barcode.
-//   k_spike.inc          --spikeAF: listed SNVs planted in a copy of a run's bases for the barcodes a per-variant draw picks, each
-//                        record's mismatch count and SMC_DA_MMOK bit moved with the base.
+//   k_spike.inc          --spikeAF, --spikeReps: listed SNVs planted in one or several copies of a run's bases for the barcodes a
+//                        per-variant draw picks, each record's mismatch count and SMC_DA_MMOK bit moved with the base.
+//   k_spike_cells.inc    --spikeReps, --spikeDepth, --spikePhase: what R replicate spike-ins achieve per listed variant or phase set and
+//                        cell (spike target x barcode fraction), from the covering barcodes' counters alone: no spiked copy is made.
 //   k_lod.inc            the limit-of-detection table of --lod: per barcode depth the root R's uniroot finds (mt_depths_lod.R), FP64.
 //
 // Data layout (include/smcounter_hip.h): ONE uint32 per pileup read (allele, quality, fragment start, read
@@ -75,10 +77,8 @@
 #include "k_read_groups.inc"   // in-run read down-sampling (philox): the file-wide table of read names and barcodes
 #include "k_allele_carriers.inc" // --dsAF: which barcodes of a run cover / carry a listed allele (bp2_resolve's CIGAR rules)
 #include "k_af_depth.inc"      // --dsAFReps, --dsAFDepth: R x T x F keep masks per run and the achieved (N', V') per variant, replicate and cell
-#include "k_spike.inc"         // --spikeAF: listed SNVs written into a copy of a run's bases, NM and the mismatch bit with them
-#include "k_spike_reps.inc"    // --spikeReps: B spiked copies of a run per call; (S, READS, V1) per variant, replicate and target without a copy
-#include "k_spike_depth.inc"   // --spikeDepth: (N', V0', S', READS', V1') per variant, replicate and cell (spike target x barcode fraction)
-#include "k_spike_phase.inc"   // --spikePhase: (N_ALL', V0_ALL', S_ALL', V1_ALL') per phase set, replicate and cell: the molecules that carry a whole haplotype
+#include "k_spike.inc"         // --spikeAF, --spikeReps: listed SNVs written into one or B copies of a run's bases, NM and the mismatch bit with them
+#include "k_spike_cells.inc"   // --spikeReps, --spikeDepth, --spikePhase: the achieved counts per variant or phase set, replicate and cell, without a copy
 #include "k_lod.inc"           // --lod: the limit of detection per barcode depth (one lane per depth, Brent root search in FP64)
 #include "k_plan.inc"          // launch plan of a batch whose descriptors are in HBM (classify + fill)
 #include "host_abi.inc"        // the C ABI of include/smcounter_hip.h

@@ -1834,61 +1834,56 @@ SPIKE_MAX_COPIES = 64          # SMC_SPIKE_MAX_COPIES
 SPIKE_REP_BATCH_BYTES = 1 << 30   # bytes of spiked copies (records + pair pools) one smc_spike_alleles_reps call of the stage writes
 
 
-def spike_rep_counts(eng, positions, covers, counters, seeds, thresholds) -> np.ndarray:
-    """smc_spike_rep_counts -> uint32 [V, R, T, 3] = (S, READS, V1) of every variant, replicate and target.  positions[v]: 1-based;
-    covers[v]: the uint64 identities of the barcodes that cover v; counters[v]: uint32 [len(covers[v]), 3] = (reads, alt0, single);
-    thresholds: floor(t * 2^32) per target."""
+def _spike_counts_call(eng, name: str, arrays, shape, call) -> np.ndarray:
+    """The device side of the three counts wrappers below: `arrays` go up, call(their device addresses, the output's) runs the entry
+    `name` on the default stream, the uint32 counters of `shape` come down, and everything is freed."""
     from .engine import DevBuf
-    n_var, seeds = len(covers), np.ascontiguousarray(seeds, np.uint64)
-    thr = np.ascontiguousarray(thresholds, np.uint64)
-    shape = (n_var, len(seeds), len(thr), 3)
+    n_out = int(np.prod(shape))
+    up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.reshape(-1) if a.size else np.zeros(1, a.dtype))
+    bufs = [up(a) for a in arrays] + [DevBuf(eng, 4 * max(1, n_out) + 256)]
+    try:
+        _lib.check(call([b.data_ptr() for b in bufs[:-1]], bufs[-1].data_ptr()), name)
+        out = bufs[-1].download(np.uint32, n_out) if n_out else np.zeros(0, np.uint32)         # (the default stream: behind the kernel)
+    finally:
+        for b in bufs:
+            b.free()
+    return out.reshape(shape)
+
+
+def _spike_flat_covers(who: str, positions, covers, counters):
+    """The variants' covers as the counts entries take them -> (identities, counters [n, 3], offsets [V + 1], positions)."""
+    n_var = len(covers)
     off = np.zeros(n_var + 1, np.uint32)
     off[1:] = np.cumsum([len(c) for c in covers])
     ident = np.concatenate([np.asarray(c, np.uint64) for c in covers]) if n_var else np.zeros(0, np.uint64)
     cnt = np.concatenate([np.asarray(c, np.uint32).reshape(-1, 3) for c in counters]) if n_var else np.zeros((0, 3), np.uint32)
     if len(cnt) != len(ident):
-        raise ValueError("spike_rep_counts: %d covering barcodes, counters of %d" % (len(ident), len(cnt)))
-    pos = np.array([int(p) & 0xFFFFFFFF for p in positions], np.uint32)
-    n_out = int(np.prod(shape))
-    up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.reshape(-1) if a.size else np.zeros(1, a.dtype))
-    bufs = [up(ident), up(cnt), up(off), up(pos), up(seeds), DevBuf(eng, 4 * max(1, n_out) + 256)]
-    try:
-        _lib.check(eng.L.smc_spike_rep_counts(eng.ctx, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data,
-                                              bufs[3].data_ptr(), n_var, bufs[4].data_ptr(), len(seeds), thr.ctypes.data, len(thr),
-                                              bufs[5].data_ptr(), ctypes.c_void_p(0)), "smc_spike_rep_counts")
-        out = bufs[5].download(np.uint32, n_out) if n_out else np.zeros(0, np.uint32)          # (the default stream: behind the kernel)
-    finally:
-        for b in bufs:
-            b.free()
-    return out.reshape(shape)
+        raise ValueError("%s: %d covering barcodes, counters of %d" % (who, len(ident), len(cnt)))
+    return ident, cnt, off, np.array([int(p) & 0xFFFFFFFF for p in positions], np.uint32)
+
+
+def spike_rep_counts(eng, positions, covers, counters, seeds, thresholds) -> np.ndarray:
+    """smc_spike_rep_counts -> uint32 [V, R, T, 3] = (S, READS, V1) of every variant, replicate and target.  positions[v]: 1-based;
+    covers[v]: the uint64 identities of the barcodes that cover v; counters[v]: uint32 [len(covers[v]), 3] = (reads, alt0, single);
+    thresholds: floor(t * 2^32) per target."""
+    ident, cnt, off, pos = _spike_flat_covers("spike_rep_counts", positions, covers, counters)
+    seeds, thr = np.ascontiguousarray(seeds, np.uint64), np.ascontiguousarray(thresholds, np.uint64)
+    return _spike_counts_call(
+        eng, "smc_spike_rep_counts", [ident, cnt, off, pos, seeds], (len(covers), len(seeds), len(thr), 3),
+        lambda d, d_out: eng.L.smc_spike_rep_counts(eng.ctx, d[0], d[1], d[2], off.ctypes.data, d[3], len(covers), d[4], len(seeds),
+                                                    thr.ctypes.data, len(thr), d_out, ctypes.c_void_p(0)))
 
 
 def spike_depth_counts(eng, positions, covers, counters, seeds, thresholds, depth_thresholds) -> np.ndarray:
     """smc_spike_depth_counts -> uint32 [V, R, T, F, 5] = (N', V0', S', READS', V1') of every variant, replicate and cell.  The
     arguments are spike_rep_counts'; depth_thresholds: frac_threshold(f) per barcode fraction."""
-    from .engine import DevBuf
-    n_var, seeds = len(covers), np.ascontiguousarray(seeds, np.uint64)
+    ident, cnt, off, pos = _spike_flat_covers("spike_depth_counts", positions, covers, counters)
+    seeds = np.ascontiguousarray(seeds, np.uint64)
     thr, dthr = np.ascontiguousarray(thresholds, np.uint64), np.ascontiguousarray(depth_thresholds, np.uint64)
-    shape = (n_var, len(seeds), len(thr), len(dthr), 5)
-    off = np.zeros(n_var + 1, np.uint32)
-    off[1:] = np.cumsum([len(c) for c in covers])
-    ident = np.concatenate([np.asarray(c, np.uint64) for c in covers]) if n_var else np.zeros(0, np.uint64)
-    cnt = np.concatenate([np.asarray(c, np.uint32).reshape(-1, 3) for c in counters]) if n_var else np.zeros((0, 3), np.uint32)
-    if len(cnt) != len(ident):
-        raise ValueError("spike_depth_counts: %d covering barcodes, counters of %d" % (len(ident), len(cnt)))
-    pos = np.array([int(p) & 0xFFFFFFFF for p in positions], np.uint32)
-    n_out = int(np.prod(shape))
-    up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.reshape(-1) if a.size else np.zeros(1, a.dtype))
-    bufs = [up(ident), up(cnt), up(off), up(pos), up(seeds), DevBuf(eng, 4 * max(1, n_out) + 256)]
-    try:
-        _lib.check(eng.L.smc_spike_depth_counts(eng.ctx, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data,
-                                                bufs[3].data_ptr(), n_var, bufs[4].data_ptr(), len(seeds), thr.ctypes.data, len(thr),
-                                                dthr.ctypes.data, len(dthr), bufs[5].data_ptr(), ctypes.c_void_p(0)), "smc_spike_depth_counts")
-        out = bufs[5].download(np.uint32, n_out) if n_out else np.zeros(0, np.uint32)          # (the default stream: behind the kernel)
-    finally:
-        for b in bufs:
-            b.free()
-    return out.reshape(shape)
+    return _spike_counts_call(
+        eng, "smc_spike_depth_counts", [ident, cnt, off, pos, seeds], (len(covers), len(seeds), len(thr), len(dthr), 5),
+        lambda d, d_out: eng.L.smc_spike_depth_counts(eng.ctx, d[0], d[1], d[2], off.ctypes.data, d[3], len(covers), d[4], len(seeds),
+                                                      thr.ctypes.data, len(thr), dthr.ctypes.data, len(dthr), d_out, ctypes.c_void_p(0)))
 
 
 def spike_joint(sets, covers, counters):
@@ -1912,10 +1907,8 @@ def spike_phase_counts(eng, lead_positions, joint, seeds, thresholds, depth_thre
     """smc_spike_phase_counts -> uint32 [G, R, T, F, 4] = (N_ALL', V0_ALL', S_ALL', V1_ALL') of every phase set, replicate and cell.
     lead_positions[g]: the 1-based position of the set's leader; joint[g]: (uint64 [n_g] identities of the barcodes that cover every
     member, uint32 [n_g, M_g, 3] their (reads, alt0, single) per member) - spike_joint's; the rest as spike_depth_counts takes it."""
-    from .engine import DevBuf
     G, seeds = len(joint), np.ascontiguousarray(seeds, np.uint64)
     thr, dthr = np.ascontiguousarray(thresholds, np.uint64), np.ascontiguousarray(depth_thresholds, np.uint64)
-    shape = (G, len(seeds), len(thr), len(dthr), 4)
     cnts = [np.ascontiguousarray(c, np.uint32) for _, c in joint]
     for (ids, _), c in zip(joint, cnts):
         if c.ndim != 3 or c.shape[0] != len(ids) or c.shape[2] != 3:
@@ -1929,19 +1922,11 @@ def spike_phase_counts(eng, lead_positions, joint, seeds, thresholds, depth_thre
     ident = np.concatenate([np.asarray(ids, np.uint64) for ids, _ in joint]) if G else np.zeros(0, np.uint64)
     cnt = np.concatenate([c.reshape(-1) for c in cnts]) if G else np.zeros(0, np.uint32)
     pos = np.array([int(p) & 0xFFFFFFFF for p in lead_positions], np.uint32)
-    n_out = int(np.prod(shape))
-    up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.reshape(-1) if a.size else np.zeros(1, a.dtype))
-    bufs = [up(ident), up(cnt), up(off), up(set_m), up(cnt_off), up(pos), up(seeds), DevBuf(eng, 4 * max(1, n_out) + 256)]
-    try:
-        _lib.check(eng.L.smc_spike_phase_counts(eng.ctx, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data,
-                                                bufs[3].data_ptr(), set_m.ctypes.data, bufs[4].data_ptr(), bufs[5].data_ptr(), G,
-                                                bufs[6].data_ptr(), len(seeds), thr.ctypes.data, len(thr), dthr.ctypes.data, len(dthr),
-                                                bufs[7].data_ptr(), ctypes.c_void_p(0)), "smc_spike_phase_counts")
-        out = bufs[7].download(np.uint32, n_out) if n_out else np.zeros(0, np.uint32)          # (the default stream: behind the kernel)
-    finally:
-        for b in bufs:
-            b.free()
-    return out.reshape(shape)
+    return _spike_counts_call(
+        eng, "smc_spike_phase_counts", [ident, cnt, off, set_m, cnt_off, pos, seeds], (G, len(seeds), len(thr), len(dthr), 4),
+        lambda d, d_out: eng.L.smc_spike_phase_counts(eng.ctx, d[0], d[1], d[2], off.ctypes.data, d[3], set_m.ctypes.data, d[4], d[5], G,
+                                                      d[6], len(seeds), thr.ctypes.data, len(thr), dthr.ctypes.data, len(dthr), d_out,
+                                                      ctypes.c_void_p(0)))
 
 
 def spike_copy_strides(n_aln: int, n_pairs: int):

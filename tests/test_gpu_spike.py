@@ -42,12 +42,19 @@ def _inputs(name, tmp):
     return bam, fa, loci, P, None
 
 
-def _run_kernel(eng, nat, A, chrom, variants, thr, seed, P):
-    """smc_spike_alleles over run `A` for `variants` (all on `chrom`) at one threshold -> (aln_out, bq_out, stats); the run's own
-    arrays in HBM must come back as they went up."""
+def _svar(variants, thr):
+    """The variants as the entries take them, sorted by position; thr: one threshold for all, or one per variant in that order."""
     var = np.zeros(len(variants), abi.SPIKE_VARIANT_DTYPE)
     for k, v in enumerate(sorted(variants, key=lambda v: v.pos)):
-        var[k]["pos0"], var[k]["ref"], var[k]["alt"], var[k]["thr"] = v.pos - 1, ord(v.ref), ord(v.alt), thr
+        var[k]["pos0"], var[k]["ref"], var[k]["alt"] = v.pos - 1, ord(v.ref), ord(v.alt)
+        var[k]["thr"] = thr if isinstance(thr, int) else thr[k]
+    return var
+
+
+def _run_kernel(eng, nat, A, chrom, variants, thr, seed, P):
+    """smc_spike_alleles over run `A` for `variants` (all on `chrom`) at one threshold, or one per variant -> (aln_out, bq_out, stats);
+    the run's own arrays in HBM must come back as they went up."""
+    var = _svar(variants, thr)
     idents = nat.barcode_idents(A["n_bc"])
     nm, n_indel = nat.run_mismatches(len(A["aln"]))
     up = devplanes.upload_run(eng, A, "A" * A["nl"])
@@ -137,6 +144,48 @@ def test_thresholds_zero_and_all(engine0, tmp_path):
             q = sv.base_at(a, v.pos) if a.pos < v.pos <= a.end else None
             if q is not None:
                 assert chr(bq[2 * (int(A["aln"]["seq_off"][i]) + q)]) == v.alt
+    nat.close(); py.close()
+
+
+def test_own_thresholds_are_per_variant_and_the_copies_ignore_them(engine0, tmp_path):
+    """P1 at threshold 0 and P2 - the `first` reads cover both - at 2^32 in ONE smc_spike_alleles call: P2 alone is written.  The same
+    array through smc_spike_alleles_reps: the copy's threshold holds for both variants, the array's own are not read."""
+    bam_path, fa, loci, P, variants = SR.make_case(str(tmp_path))
+    vs, own = variants[:2], [0, 1 << 32]
+    nat, py = bamio.NativeBam(bam_path), bamio.BamFile(bam_path)
+    (chrom, lo, hi), = ds_restate.stretches(loci)
+    A = nat.alignments_run(chrom, lo, hi, ds_restate.BIG, P, 2)
+    recs = py.fetch(chrom, lo, hi)
+    assert any(a.pos < vs[0].pos and vs[1].pos <= a.end for a in recs)
+    n, nb = len(A["aln"]), len(A["bq"])
+    # the single call: the restatement of P2 alone at t = 1
+    records, stats = SR.restate(bam_path, fa, vs[1:], 1.0, SEED, P.mismatchThr)
+    want_aln, want_bq = _expected(A, recs, records)
+    aln, bq, st = _run_kernel(engine0, nat, A, chrom, vs, own, SEED, P)
+    assert st.tolist() == [[0, 0], [stats[0]["READS"], stats[0]["NMINC"]]] and stats[0]["READS"] > 0
+    assert bq.tobytes() == want_bq.tobytes() and aln.tobytes() == want_aln.tobytes()
+    column = {2 * (int(A["aln"]["seq_off"][i]) + sv.base_at(a, vs[1].pos)) for i, a in enumerate(recs)
+              if a.pos < vs[1].pos <= a.end and sv.base_at(a, vs[1].pos) is not None}
+    changed = np.flatnonzero(bq != A["bq"]).tolist()
+    assert changed and set(changed) <= column
+    # one copy at 2^32: both variants, the restatement of both at t = 1; one copy at 0: the input
+    records, stats = SR.restate(bam_path, fa, vs, 1.0, SEED, P.mismatchThr)
+    both_aln, both_bq = _expected(A, recs, records)
+    assert all(x["READS"] > 0 for x in stats)
+    idents, (nm, n_indel) = nat.barcode_idents(A["n_bc"]), nat.run_mismatches(n)
+    up = devplanes.upload_run(engine0, A, "A" * A["nl"])
+    try:
+        for thr, w_aln, w_bq, w_st in ((1 << 32, both_aln, both_bq, [[x["READS"], x["NMINC"]] for x in stats]),
+                                       (0, A["aln"], A["bq"], [[0, 0], [0, 0]])):
+            d_aln, d_bq, _, got = devplanes.spike_run_copies(engine0, up, A, _svar(vs, own), idents, [SEED], [thr], P.mismatchThr, nm, n_indel)
+            try:
+                c_aln, c_bq = d_aln.download(np.uint8, 36 * n), d_bq.download(np.uint8, nb)
+            finally:
+                d_aln.free(); d_bq.free()
+            assert got.tolist() == [w_st]
+            assert c_bq.tobytes() == w_bq.tobytes() and c_aln.tobytes() == w_aln.tobytes()
+    finally:
+        up.free()
     nat.close(); py.close()
 
 

@@ -238,6 +238,37 @@ def test_one_member_equals_the_depth_counts_columns(engine0):
     assert np.array_equal(got, depth[..., [0, 1, 2, 4]]) and got.any()
 
 
+def test_the_three_entries_on_the_same_made_covers(engine0):
+    """Rows of 0, 1, 63, 64, 65 and 257 barcodes - the wavefront's and the workgroup's edges - through all three entries: the depth
+    entry gives the five quantities of the restatement, the replicate entry its columns (S, READS, V1) at the fraction that keeps
+    every barcode, the phase entry with one member the columns (N, V0, S, V1), and with three members the restatement's conjunction."""
+    counters = TD._made_counters([0, 1, 63, 64, 65, 257])
+    pos, seeds = [7, 11, 5000, 5001, 1 << 20, (1 << 32) - 1], PR.seeds(SEED, 3)
+    thr, dthr = [PR.threshold(0.4), ONE], [ONE, 1 << 31]
+    idents, cnts = [PR.idents(names) for names, _ in counters], [c for _, c in counters]
+    five = DS.counts_from(counters, pos, thr, dthr, seeds)
+    assert five.shape == (6, 3, 2, 2, 5) and not five[0].any() and all(five[v].any() for v in range(1, 6))
+    depth = devplanes.spike_depth_counts(engine0, pos, idents, cnts, seeds, thr, dthr)
+    assert np.array_equal(depth, five), np.argwhere(depth != five)[:5]
+    reps = devplanes.spike_rep_counts(engine0, pos, idents, cnts, seeds, thr)
+    assert reps.shape == (6, 3, 2, 3) and np.array_equal(reps, five[:, :, :, 0][..., [2, 3, 4]])
+    one = _device(engine0, [(names, c.reshape(-1, 1, 3)) for names, c in counters], pos, seeds, thr, dthr)
+    assert one.shape == (6, 3, 2, 2, 4) and np.array_equal(one, five[..., [0, 1, 2, 4]])
+    # three members: a sure carrier, the made counters, and a carrier that every fourth barcode is only when hit
+    sure, when_hit = np.array([3, 2, 3], np.uint32), np.array([4, 1, 3], np.uint32)
+    joint = []
+    for names, c in counters:
+        cnt = np.stack([np.tile(sure, (len(c), 1)), c, np.tile(sure, (len(c), 1))], axis=1)
+        cnt[1::4, 2] = when_hit
+        joint.append((names, cnt))
+    fails = np.concatenate([(2 * cnt[:, :, 1].astype(np.int64) <= cnt[:, :, 0]).sum(axis=1) for _, cnt in joint])
+    assert (fails == 1).any() and (fails == 0).any() and (fails == 2).any()
+    want = PH.counts_from(joint, pos, thr, dthr, seeds)
+    got = _device(engine0, joint, pos, seeds, thr, dthr)
+    assert got.shape == (6, 3, 2, 2, 4) and np.array_equal(got, want), np.argwhere(got != want)[:5]
+    assert np.array_equal(got[..., [0, 2]], one[..., [0, 2]]) and (got[..., 1] <= one[..., 1]).all() and (got[..., 1] < one[..., 1]).any()
+
+
 def test_eight_members_and_a_set_nobody_covers_between_two_that_are(engine0):
     joint = _made_joint([70, 0, 130], [8, 3, 2])                                          # (offsets 0, 70, 70, 200; rows of 24, 9 and 6 words)
     lead, seeds = [11, 5000, 1 << 20], PR.seeds(SEED, 2)

@@ -608,6 +608,50 @@ int smc_spike_alleles(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, con
                       const smc_spike_variant* d_var, const smc_spike_variant* var_host, int32_t n_var, const uint64_t* d_idents,
                       int64_t n_bc, uint64_t seed, double mismatch_thr, const int32_t* d_nm, const int32_t* d_n_indel,
                       smc_dev_aln* d_aln_out, uint8_t* d_bq_out, uint32_t* d_stats, void* stream);
+/* (ABI 11, additive: one entry more, the version number unchanged) --spikeIndels: listed insertions and deletions, and SNVs beside
+ * them, planted in a copy of a run.  The run, d_idents, d_nm / d_n_indel, the seed and the draw (counter word 3 = (pos0 + 1) mod 2^32)
+ * are smc_spike_alleles'; n_cig_words: the words of the CIGAR pool.  d_var[n_var]: strictly ascending by pos0, footprints disjoint.
+ *   SMC_AF_SNV  ref / alt as smc_spike_variant has them, len 0: smc_spike_alleles' rule
+ *   SMC_AF_INS  pos0 the anchor, ref = alt = the anchor's letter, the `len` inserted letters at d_ins[ins_off ..]; footprint [pos0, pos0 + 1]
+ *   SMC_AF_DEL  pos0 the anchor, ref = alt = the anchor's letter, `len` deleted positions; footprint [pos0, pos0 + len + 1]
+ * A record of a spiked barcode takes an insertion / a deletion when the whole footprint lies inside ONE M / = / X operation of its
+ * ORIGINAL CIGAR and inside its l_seq bases, and l_seq (+ len, an insertion) and n_cig + 2 stay <= 65535 - counted over the variants
+ * taken before it, in ascending position.  M(n) becomes M(a) I(len) M(n - a) / M(a) D(len) M(n - a - len), the operation's type kept;
+ * inserted letters take the anchor's quality; l_seq and qalen move by len, NM and n_indel grow by len; pos, end, left_sp, flags, mapq
+ * and the ids stay.  Such a record is RELOCATED: its pairs and CIGAR words are written behind the run's own, the relocated records in
+ * alignment order, densely; its SNVs (resolved on the original CIGAR) are written on the way.  Every other record takes the SNV rule
+ * in place.  Outputs, all DEVICE memory:
+ *   d_aln_out[n_aln]                 the records (seq_off, cig_off, n_cig, l_seq, qalen of a relocated one new; SMC_DA_MMOK of every
+ *                                    record from NM', n_indel' and the new l_seq, as smc_bam_alignments computes it)
+ *   d_bq_out (2 * cap_pairs bytes)   the run's 2 * n_pairs bytes, then the relocated records' pairs.  For smc_build_planes allocate
+ *                                    128 bytes more, as for any pair pool
+ *   d_cig_out (cap_cig words)        the run's n_cig_words, then the relocated records' operations
+ *   d_nm_out / d_n_indel_out[n_aln]  NM' and n_indel'
+ *   d_stats[n_var][2]                uint32: records rewritten at v, records whose NM grew at v (every one, for an insertion / a deletion)
+ *   d_totals[3]                      uint64: pairs and CIGAR words the copy needs, the run's own included; [2] bit 1 = more than
+ *                                    cap_pairs / cap_cig (both below 2^32).  Nothing beyond the capacities is written: a record that
+ *                                    does not fit is stored as the run has it, and the copy is not to be used
+ * An upper bound of the capacities from the host's arrays: n_pairs + over the alignments that span a listed insertion / deletion
+ * l_seq + the `len` of the insertions they span, n_cig_words + over the same alignments n_cig + 2 per such variant.
+ * Three launches behind the copies, enqueued on `stream`; nothing waits for the host, no workgroup waits for another; the offsets are
+ * a sum in a fixed order: two calls give the same bytes.  SMC_E_INPUT, nothing launched and nothing copied: what smc_spike_alleles
+ * refuses, a kind beyond SMC_AF_DEL, a len outside 1 .. SMC_AF_MAX_INS (0 for an SNV), ref != alt for an insertion / a deletion,
+ * inserted letters beyond the n_ins bytes of d_ins, overlapping footprints, capacities below the run's own or of 2^32 or more. */
+typedef struct smc_spike_indel_variant {
+    int32_t pos0;              /* 0-based reference position: of the SNV, of the anchor */
+    uint8_t kind;              /* SMC_AF_SNV, SMC_AF_INS, SMC_AF_DEL */
+    uint8_t ref, alt;          /* ASCII, out of A C G T; an insertion / a deletion: the anchor's letter in both */
+    uint8_t pad;
+    uint32_t len;              /* inserted letters / deleted positions; 0 for an SNV */
+    uint32_t ins_off;          /* where the inserted letters start in d_ins */
+    uint64_t thr;              /* floor(t * 2^32), in [0, 2^32] */
+} smc_spike_indel_variant;
+int smc_spike_indels(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words, const uint8_t* d_bq,
+                     int64_t n_pairs, const smc_spike_indel_variant* d_var, const smc_spike_indel_variant* var_host, int32_t n_var,
+                     const uint8_t* d_ins, int64_t n_ins, const uint64_t* d_idents, int64_t n_bc, uint64_t seed, double mismatch_thr,
+                     const int32_t* d_nm, const int32_t* d_n_indel, int64_t cap_pairs, int64_t cap_cig, smc_dev_aln* d_aln_out,
+                     uint8_t* d_bq_out, uint32_t* d_cig_out, int32_t* d_nm_out, int32_t* d_n_indel_out, uint32_t* d_stats,
+                     uint64_t* d_totals, void* stream);
 /* (ABI 11, additive: two entries more, the version number unchanged) --spikeReps: R replicates of the --spikeAF spike-in, replicate
  * j with the seed s_j; the run, the variants and the rewrite rule are smc_spike_alleles'.
  *   smc_spike_alleles_reps   n_copies spiked copies of one run from one call.  `seeds` / `thr`: HOST memory, n_copies words each - copy

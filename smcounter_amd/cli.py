@@ -175,6 +175,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "carry every member before (V0_ALL) and after spiking (V1_ALL), are spiked (S_ALL), and whether every member "
                         "was called (CALLED_ALL); with --spikeReps <outPrefix>.spikeAF.phase.replicates.txt and "
                         ".spikeAF.phase.sensitivity.txt.  Without the flag an MNV line is refused and PS= is not read.  Needs --spikeAF")
+    p.add_argument("--spikeIndels", action="store_true", default=False,
+                   help="plant insertions and deletions too: --spikeVariants may then hold, beside SNVs, insertions (REF X, ALT XS) and "
+                        "deletions (REF XD, ALT X) of 1 to 255 letters out of ACGT, REF the genome's letters, no two footprints (the anchor "
+                        "to the position behind the indel) overlapping.  A record of a spiked barcode takes the indel when the whole "
+                        "footprint lies in one aligned operation of its CIGAR - SEQ, QUAL, CIGAR and NM are rewritten on the GPU, as "
+                        "tools/spike_variants.py --indels does it; every other record is left alone.  The outputs are --spikeAF's, V0 "
+                        "and V1 of .spikeAF.detection.txt by the variant's INS / DEL key.  Not with --spikeReps, --spikeDepth or "
+                        "--spikePhase.  Without the flag an indel line is refused.  Needs --spikeAF")
     p.add_argument("--spikeDepth", default=None,
                    help="the spike-ins of --spikeAF at several barcode depths: comma-separated fractions f in (0, 1].  For every target t "
                         "and every f the run is also called on the CELL (t, f): the spike-in at t, of which a barcode stays when the "
@@ -747,6 +755,7 @@ def _main(args) -> int:
     from . import spike as _spike
     spike_targets = _spike.targets(args)
     spike_fracs, spike_cells = _spike.depth_cells(args, spike_targets)
+    _spike.indels(args, spike_targets)
     at = lambda **kw: dataclasses.replace(params, **kw)
     plan = _Plan([_Output(args.outPrefix, params)] +
                  [_Output(p, at(mtDepth=d), "dsMT", frac=f) for f, d, p in fractions] +

@@ -40,6 +40,9 @@ struct smc_ctx {
     // scratch of smc_allele_carriers (the counters of a call that does not ask for them), grown on demand
     void* af_scratch = nullptr;
     size_t af_bytes = 0;
+    // scratch of smc_spike_indels (per alignment the relocated sizes, per workgroup their sums), grown on demand
+    void* spi_scratch = nullptr;
+    size_t spi_bytes = 0;
     // scratch of the checking entries smc_fisher_tables / smc_lfact_values (arguments, then results), grown on demand
     void* chk_scratch = nullptr;
     size_t chk_bytes = 0;
@@ -487,6 +490,7 @@ void smc_destroy(smc_ctx* c) {
     (void)hipFree(c->sel_scratch);
     (void)hipFree(c->lod_scratch);
     (void)hipFree(c->af_scratch);
+    (void)hipFree(c->spi_scratch);
     (void)hipFree(c->chk_scratch);
     {
         std::vector<smc_ctx::VmmBlock> left;
@@ -1185,6 +1189,69 @@ int smc_spike_alleles(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, con
         hipLaunchKernelGGL(k_spike_rewrite, dim3((unsigned)((n_aln + SPK_BLOCK - 1) / SPK_BLOCK)), dim3(SPK_BLOCK), 0, st, d_aln, (uint32_t)n_aln,
                            d_cig, (unsigned long long)n_pairs, d_var, (int)n_var, (const unsigned long long*)d_idents, (uint32_t)n_bc, C, 1,
                            mismatch_thr, d_nm, d_n_indel, (uint8_t*)d_aln_out, 0ull, d_bq_out, 0ull, d_stats);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
+// (--spikeIndels) the run's records, pair pool and CIGAR pool copied; k_spi_count -> k_spi_scan -> k_spi_scatter behind the copies
+int smc_spike_indels(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words, const uint8_t* d_bq,
+                     int64_t n_pairs, const smc_spike_indel_variant* d_var, const smc_spike_indel_variant* var_host, int32_t n_var,
+                     const uint8_t* d_ins, int64_t n_ins, const uint64_t* d_idents, int64_t n_bc, uint64_t seed, double mismatch_thr,
+                     const int32_t* d_nm, const int32_t* d_n_indel, int64_t cap_pairs, int64_t cap_cig, smc_dev_aln* d_aln_out,
+                     uint8_t* d_bq_out, uint32_t* d_cig_out, int32_t* d_nm_out, int32_t* d_n_indel_out, uint32_t* d_stats,
+                     uint64_t* d_totals, void* stream) {
+    const std::string who = "smc_spike_indels";
+    if (!ctx || n_aln < 0 || n_pairs < 0 || n_cig_words < 0 || n_var < 0 || n_bc < 0 || n_ins < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
+    if (n_var && !var_host) return fail(SMC_E_ARG, who + ": NULL argument");
+    auto acgt = [](uint8_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; };
+    auto fp_end = [](const smc_spike_indel_variant& V) {        // the last position of the footprint
+        return (int64_t)V.pos0 + (V.kind == SMC_AF_SNV ? 0 : V.kind == SMC_AF_INS ? 1 : (int64_t)V.len + 1);
+    };
+    for (int32_t v = 0; v < n_var; ++v) {
+        const smc_spike_indel_variant& V = var_host[v];
+        const std::string w = who + ": variant " + std::to_string(v);
+        if (V.kind > SMC_AF_DEL) return fail(SMC_E_INPUT, w + " has kind " + std::to_string(V.kind));
+        if (v && var_host[v - 1].pos0 >= V.pos0) return fail(SMC_E_INPUT, w + ": the positions are not strictly ascending");
+        if (!acgt(V.ref) || !acgt(V.alt)) return fail(SMC_E_INPUT, w + ": a letter outside ACGT");
+        if (V.kind == SMC_AF_SNV ? V.ref == V.alt : V.ref != V.alt)
+            return fail(SMC_E_INPUT, w + (V.kind == SMC_AF_SNV ? ": ref equals alt" : ": the anchor of an insertion / a deletion stands in ref and alt"));
+        if (V.kind == SMC_AF_SNV ? V.len != 0 : (V.len < 1 || V.len > SMC_AF_MAX_INS))
+            return fail(SMC_E_INPUT, w + ": a length of " + std::to_string(V.len) + " (1 .. " + std::to_string(SMC_AF_MAX_INS) + " for an insertion / a deletion, 0 for an SNV)");
+        if (V.kind == SMC_AF_INS && ((int64_t)V.ins_off + V.len > n_ins || !d_ins))
+            return fail(SMC_E_INPUT, w + ": " + std::to_string(V.len) + " inserted letters at " + std::to_string(V.ins_off) + " (pool of " + std::to_string(n_ins) + ")");
+        if (V.thr > (1ull << 32)) return fail(SMC_E_INPUT, w + ": a threshold above 2^32");
+        if (v && fp_end(var_host[v - 1]) >= (int64_t)V.pos0) return fail(SMC_E_INPUT, w + ": its footprint overlaps that of the variant before it");
+    }
+    if (n_aln >= (int64_t)0xFFFFFF00 || n_bc >= (int64_t)0x7FFFFF00) return fail(SMC_E_ARG, who + ": run too large");
+    if (cap_pairs < n_pairs || cap_cig < n_cig_words || cap_pairs > (int64_t)0xFFFFFFFF || cap_cig > (int64_t)0xFFFFFFFF)
+        return fail(SMC_E_INPUT, who + ": capacities of " + std::to_string(cap_pairs) + " pairs / " + std::to_string(cap_cig) + " CIGAR words for a run of " +
+                                 std::to_string(n_pairs) + " / " + std::to_string(n_cig_words) + " (at least the run's, below 2^32)");
+    if ((n_var && (!d_var || !d_stats)) || (n_aln && (!d_aln || !d_cig || !d_nm || !d_n_indel || !d_aln_out || !d_nm_out || !d_n_indel_out)) ||
+        (n_pairs && (!d_bq || !d_bq_out)) || (n_cig_words && (!d_cig || !d_cig_out)) || (n_bc && !d_idents) || !d_totals)
+        return fail(SMC_E_ARG, who + ": NULL argument");
+    if (((uintptr_t)d_totals & 7u) != 0) return fail(SMC_E_ARG, who + ": d_totals must be 8-byte aligned");
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t nb = ((size_t)n_aln + SPI_BLOCK - 1) / SPI_BLOCK;
+    const size_t cnt_bytes = (8 * (size_t)n_aln + 15) & ~(size_t)15, need = cnt_bytes + 16 * std::max<size_t>(nb, 1);
+    if (int rc = grow_scratch(ctx->spi_scratch, ctx->spi_bytes, need, need + need / 8, "smc_spike_indels", &st)) return rc;
+    uint32_t* const cnt = (uint32_t*)ctx->spi_scratch;
+    unsigned long long* const bsum = (unsigned long long*)((uint8_t*)ctx->spi_scratch + cnt_bytes);
+    if (n_pairs) HIPCHK(hipMemcpyAsync(d_bq_out, d_bq, 2 * (size_t)n_pairs, hipMemcpyDeviceToDevice, st));
+    if (n_cig_words) HIPCHK(hipMemcpyAsync(d_cig_out, d_cig, 4 * (size_t)n_cig_words, hipMemcpyDeviceToDevice, st));
+    if (n_var) hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)((2 * n_var + 255) / 256)), dim3(256), 0, st, d_stats, (uint32_t)(2 * n_var));
+    if (n_aln)
+        hipLaunchKernelGGL(k_spi_count, dim3((unsigned)nb), dim3(SPI_BLOCK), 0, st, d_aln, (uint32_t)n_aln, d_cig, (unsigned long long)n_pairs,
+                           (unsigned long long)n_cig_words, d_var, (int)n_var, (const unsigned long long*)d_idents, (uint32_t)n_bc,
+                           (unsigned long long)seed, cnt, bsum);
+    hipLaunchKernelGGL(k_spi_scan, dim3(1), dim3(SPI_BLOCK), 0, st, bsum, (uint32_t)nb, (unsigned long long)n_pairs, (unsigned long long)n_cig_words,
+                       (unsigned long long)cap_pairs, (unsigned long long)cap_cig, (unsigned long long*)d_totals);
+    if (n_aln)
+        hipLaunchKernelGGL(k_spi_scatter, dim3((unsigned)nb), dim3(SPI_BLOCK), 0, st, d_aln, (uint32_t)n_aln, d_cig, d_bq, (unsigned long long)n_pairs,
+                           (unsigned long long)n_cig_words, d_var, (int)n_var, d_ins, (const unsigned long long*)d_idents, (uint32_t)n_bc,
+                           (unsigned long long)seed, mismatch_thr, d_nm, d_n_indel, (const uint32_t*)cnt, (const unsigned long long*)bsum,
+                           (unsigned long long)cap_pairs, (unsigned long long)cap_cig, d_aln_out, d_bq_out, d_cig_out, d_nm_out, d_n_indel_out, d_stats);
     HIPCHK(hipGetLastError());
     return SMC_OK;
 }

@@ -78,6 +78,7 @@
 #include "k_allele_carriers.inc" // --dsAF: which barcodes of a run cover / carry a listed allele (bp2_resolve's CIGAR rules)
 #include "k_af_depth.inc"      // --dsAFReps, --dsAFDepth: R x T x F keep masks per run and the achieved (N', V') per variant, replicate and cell
 #include "k_spike.inc"         // --spikeAF, --spikeReps: listed SNVs written into one or B copies of a run's bases, NM and the mismatch bit with them
+#include "k_spike_indel.inc"   // --spikeIndels: listed insertions / deletions planted in a copy of a run: count, scan, scatter of the relocated records
 #include "k_spike_cells.inc"   // --spikeReps, --spikeDepth, --spikePhase: the achieved counts per variant or phase set, replicate and cell, without a copy
 #include "k_lod.inc"           // --lod: the limit of detection per barcode depth (one lane per depth, Brent root search in FP64)
 #include "k_plan.inc"          // launch plan of a batch whose descriptors are in HBM (classify + fill)

@@ -395,7 +395,8 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
                             idents = bam.barcode_idents(A["n_bc"])
                         if mism is None:
                             mism = bam.run_mismatches(len(A["aln"]))
-                        spiked_of[key], _ = spike_run(eng, up, A, var, idents, rule.seed, rule.params.mismatchThr, mism[0], mism[1])
+                        spiked_of[key], _ = spike_copy(eng, up, A, rule.spike, chrom, var, idents, rule.seed, rule.params.mismatchThr,
+                                                       mism[0], mism[1])
                 spiked = spiked_of[key]
                 if rule.spike_cell:
                     # (--spikeDepth: the --dsMT philox selection at f over the target's copy - the one spiked above for the target's
@@ -472,6 +473,9 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
                 # (--spikeAF: every alignment is there; a key beyond the six fixed ones is an insertion's, a deletion's or an odd letter's,
                 # and its site is a base the rewrite leaves alone or turns into a fixed key - the decoder's texts hold)
                 allele_key = bam.allele_key
+                if spiked is not None and spiked.cig is not up.cig:
+                    # (--spikeIndels: a relocated record has another query layout - its texts come from the copy)
+                    allele_key = copy_allele_key(spiked, A, bam.allele_key)
             bc_name, bc_idents = bam.barcode_name, bam.barcode_idents
             if rule.level == "read":
                 # (the read level renumbers the kept barcodes by first kept appearance: the texts the cap samplers need are the decoder's,
@@ -493,7 +497,7 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
             if rule.spike is not None:
                 users[key] -= 1
                 if not users[key] and spiked is not None:          # (behind the last build of its target)
-                    spiked.aln.free(); spiked.bq.free()
+                    free_spiked(spiked, up)
                     spiked_of[key] = None
             if done is None:
                 raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "%s: the device builder does not take it" % rule.label, rule.flag))
@@ -507,7 +511,7 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
             d_cells[0].free()
         for spiked in spiked_of.values():                          # (a build that ended early: NARROW, or an error)
             if spiked is not None:
-                spiked.aln.free(); spiked.bq.free()
+                free_spiked(spiked, up)
     for d, (nl_k, ns_k, lc, tb) in zip(ds, res):
         d.LC.append(lc)
         d.tables += tb
@@ -694,6 +698,7 @@ class RunOnDevice:
     ref: object
     n_aln: int
     loc_host: object = None     # loc[] in host memory (sizes the builder's launches), or None: the library copies it back
+    pairs_used: int = None      # (a copy smc_spike_indels wrote) the pairs of its pool: the run's own, then the relocated records'
 
     def free(self, shared: bool = True):
         for b in ((self.aln, self.cig, self.bq, self.loc, self.ref) if shared else (self.aln, self.loc)):
@@ -1320,12 +1325,20 @@ class SpikeSet(object):
     lead_pos[k]: the leader's 1-based position of variant k of the list given - counter word 3 of its draw, its own without sets."""
 
     def __init__(self, variants):
+        from .tools import ds_allele_fraction as af
         from .tools import spike_variants as sv
         self.lead_pos = sv.leaders(variants)
         self.variants = list(variants)
-        self.by_chrom = {}
+        # (--spikeIndels) a list that holds an insertion or a deletion: the records are smc_spike_indels' (no phase sets beside them),
+        # ins[chrom] the pool of inserted letters
+        self.indels = any(v.kind != af.SNV for v in self.variants)
+        self.by_chrom, self.ins = {}, {}
         for c in sorted({v.chrom for v in self.variants}):
             order = sorted((k for k, v in enumerate(self.variants) if v.chrom == c), key=lambda k: self.variants[k].pos)
+            if self.indels:
+                var, self.ins[c], _ = spike_indel_variants([self.variants[k] for k in order], 0)
+                self.by_chrom[c] = (var, order)
+                continue
             var = np.zeros(len(order), abi.SPIKE_VARIANT_DTYPE)
             for j, k in enumerate(order):
                 v = self.variants[k]
@@ -1337,7 +1350,7 @@ class SpikeSet(object):
     def chrom_variants(self, chrom: str, t: float):
         """-> (the chromosome's records at the threshold of target t, the index of each in the list given)."""
         from .tools import spike_variants as sv
-        var, order = self.by_chrom.get(chrom, (np.zeros(0, abi.SPIKE_VARIANT_DTYPE), []))
+        var, order = self.by_chrom.get(chrom, (np.zeros(0, abi.SPIKE_INDEL_VARIANT_DTYPE if self.indels else abi.SPIKE_VARIANT_DTYPE), []))
         var = var.copy()
         var["thr"] = sv.threshold(t)
         return var, order
@@ -1378,6 +1391,164 @@ def spike_run(eng, up: RunOnDevice, A, var: np.ndarray, idents, seed: int, misma
         for b in tmp:
             b.free()
     return RunOnDevice(d_aln, up.cig, d_bq, up.loc, up.ref, n, up.loc_host), stats
+
+
+def spike_indel_variants(variants, thr):
+    """Listed variants of one chromosome (tools.ds_allele_fraction.Variant: SNVs, insertions, deletions) as smc_spike_indels takes
+    them, ascending by position -> (abi.SPIKE_INDEL_VARIANT_DTYPE array, the pool of inserted letters, the index of each record in the
+    list given).  `thr`: one threshold for all, or one per variant of the list given."""
+    from .tools import ds_allele_fraction as af
+    order = sorted(range(len(variants)), key=lambda k: variants[k].pos)
+    var = np.zeros(len(order), abi.SPIKE_INDEL_VARIANT_DTYPE)
+    pool = bytearray()
+    for j, k in enumerate(order):
+        v = variants[k]
+        var[j]["pos0"], var[j]["kind"], var[j]["thr"] = v.pos - 1, v.kind, thr if isinstance(thr, int) else thr[k]
+        if v.kind == af.SNV:
+            var[j]["ref"], var[j]["alt"] = ord(v.ref), ord(v.alt)
+        else:
+            var[j]["ref"] = var[j]["alt"] = ord(v.ref[0])
+            var[j]["len"] = len(v.alt) - 1 if v.kind == af.INS else len(v.ref) - 1
+            if v.kind == af.INS:
+                var[j]["ins_off"] = len(pool)
+                pool += v.alt[1:].encode()
+    return var, np.frombuffer(bytes(pool) or b"\0", np.uint8).copy(), order
+
+
+def spike_indel_caps(A, var):
+    """Upper bounds of the pools of a copy smc_spike_indels writes, from the run's host arrays: for every alignment that spans a listed
+    insertion / deletion its l_seq + the inserted letters it spans, and its n_cig + 2 per such variant -> (cap_pairs, cap_cig)."""
+    aln = A["aln"]
+    indel = var[var["kind"] != 0]
+    n_pairs, n_cig = len(A["bq"]) // 2, len(A["cig"])
+    if not len(indel) or not len(aln):
+        return n_pairs, n_cig
+    first, last = np.searchsorted(indel["pos0"], aln["pos"], "left"), np.searchsorted(indel["pos0"], aln["end"], "left")
+    s = np.concatenate([[0], np.cumsum(np.where(indel["kind"] == 1, indel["len"], 0).astype(np.int64))])
+    hit = last > first
+    return (n_pairs + int((aln["l_seq"].astype(np.int64) + s[last] - s[first])[hit].sum()),
+            n_cig + int((aln["n_cig"].astype(np.int64) + 2 * (last - first))[hit].sum()))
+
+
+def spike_indel_run(eng, up: RunOnDevice, A, var: np.ndarray, ins: np.ndarray, idents, seed: int, mismatch_thr: float, nm, n_indel,
+                    caps=None, mism: bool = True):
+    """smc_spike_indels over the run `up` (A: its host arrays) -> (RunOnDevice whose aln, cig and bq are the spiked copies - loc and
+    ref are the run's own: free the three copies only -, uint32 [n_var, 2] statistics, uint64 [3] totals, NM' and n_indel' per
+    alignment).  `caps`: (cap_pairs, cap_cig), spike_indel_caps' bounds without it.  SmcError when the copy did not fit them."""
+    from .engine import DevBuf
+    n, n_pairs, n_cw, n_var, n_bc = up.n_aln, len(A["bq"]) // 2, len(A["cig"]), len(var), int(A["n_bc"])
+    var = np.ascontiguousarray(var, abi.SPIKE_INDEL_VARIANT_DTYPE)
+    cap_pairs, cap_cig = caps if caps is not None else spike_indel_caps(A, var)
+    up8 = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
+    idents = np.ascontiguousarray(idents, np.uint64)[:n_bc]
+    ins = np.ascontiguousarray(ins, np.uint8)
+    tmp = [up8(var), up8(idents), up8(np.ascontiguousarray(nm, np.int32)), up8(np.ascontiguousarray(n_indel, np.int32)), up8(ins),
+           DevBuf(eng, 8 * max(1, n_var) + 256), DevBuf(eng, 24 + 256), DevBuf(eng, 4 * max(1, n) + 256), DevBuf(eng, 4 * max(1, n) + 256)]
+    d_aln, d_bq, d_cig = DevBuf(eng, 36 * max(1, n) + 256), DevBuf(eng, 2 * max(1, cap_pairs) + 256), DevBuf(eng, 4 * max(1, cap_cig) + 256)
+    try:
+        if len(nm) < n or len(n_indel) < n:
+            raise ValueError("spike_indel_run: %d alignments, NM of %d" % (n, len(nm)))
+        _lib.check(eng.L.smc_spike_indels(eng.ctx, up.aln.data_ptr(), n, up.cig.data_ptr(), n_cw, up.bq.data_ptr(), n_pairs, tmp[0].data_ptr(),
+                                          var.ctypes.data, n_var, tmp[4].data_ptr(), len(ins), tmp[1].data_ptr(), len(idents),
+                                          ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), float(mismatch_thr), tmp[2].data_ptr(),
+                                          tmp[3].data_ptr(), cap_pairs, cap_cig, d_aln.data_ptr(), d_bq.data_ptr(), d_cig.data_ptr(),
+                                          tmp[7].data_ptr(), tmp[8].data_ptr(), tmp[5].data_ptr(), tmp[6].data_ptr(), ctypes.c_void_p(0)),
+                   "smc_spike_indels")
+        stats = tmp[5].download(np.uint32, 2 * n_var).reshape(n_var, 2) if n_var else np.zeros((0, 2), np.uint32)   # (behind the kernels)
+        totals = tmp[6].download(np.uint64, 3)
+        nm_out, n_indel_out = (tmp[7].download(np.int32, n), tmp[8].download(np.int32, n)) if mism else (None, None)
+        if caps is None and int(totals[2]):
+            raise _lib.SmcError("smc_spike_indels: the copy needs %d pairs / %d CIGAR words, more than the bounds %d / %d" %
+                                (int(totals[0]), int(totals[1]), cap_pairs, cap_cig))
+    except BaseException:
+        d_aln.free(); d_bq.free(); d_cig.free()
+        raise
+    finally:
+        for b in tmp:
+            b.free()
+    return RunOnDevice(d_aln, d_cig, d_bq, up.loc, up.ref, n, up.loc_host, pairs_used=int(totals[0])), stats, totals, nm_out, n_indel_out
+
+
+def spike_indel_reads(A, v, hit) -> int:
+    """The records of run `A` (host arrays) that the listed insertion / deletion `v` rewrites when the barcodes `hit` (bool by run-wide
+    barcode id) are spiked: the whole footprint inside one M / = / X operation and inside l_seq, n_cig + 2 and l_seq (+ s) within 16
+    bits.  (The limits are taken per variant, not over the variants a record took before: the difference needs a CIGAR of more than
+    32,000 operations.)"""
+    from .tools import ds_allele_fraction as af
+    aln, cig = A["aln"], A["cig"]
+    p = v.pos - 1
+    n = len(v.alt) - 1 if v.kind == af.INS else len(v.ref) - 1
+    fp = 1 if v.kind == af.INS else n + 1
+    gid = aln["bc_gid"]
+    ok = (aln["pos"] <= p) & (p < aln["end"]) & (gid < len(hit))
+    ok[ok] = hit[gid[ok]]
+    ok &= (aln["n_cig"].astype(np.int64) + 2 <= 65535) & ((v.kind != af.INS) | (aln["l_seq"].astype(np.int64) + n <= 65535))
+    # (a CIGAR of one aligned operation - nearly every record: no walk)
+    w0 = cig[np.minimum(aln["cig_off"], max(0, len(cig) - 1))] if len(cig) else np.zeros(len(aln), np.uint32)
+    plain = ok & (aln["n_cig"] == 1) & np.isin(w0 & 15, (0, 7, 8))
+    d0 = p - aln["pos"].astype(np.int64)
+    count = int((plain & (d0 + fp < (w0 >> 4).astype(np.int64)) & (d0 + fp < aln["l_seq"].astype(np.int64))).sum())
+    for i in np.flatnonzero(ok & ~plain).tolist():
+        a = aln[i]
+        x, y = int(a["pos"]), 0
+        for w in cig[int(a["cig_off"]):int(a["cig_off"]) + int(a["n_cig"])].tolist():
+            op, l = w & 15, w >> 4
+            if op in (0, 7, 8):
+                if x <= p < x + l:
+                    count += p - x + fp < l and y + p - x + fp < int(a["l_seq"])
+                    break
+                x += l
+                y += l
+            elif op in (2, 3):
+                if x <= p < x + l:
+                    break
+                x += l
+            elif op in (1, 4):
+                y += l
+    return count
+
+
+def spike_copy(eng, up: RunOnDevice, A, spikes: SpikeSet, chrom: str, var: np.ndarray, idents, seed: int, mismatch_thr: float, nm, n_indel):
+    """The spiked copy of run `up` for the records `var` of `spikes` on `chrom`: spike_run, or spike_indel_run when the set holds an
+    insertion or a deletion -> (RunOnDevice, statistics); free the copy with free_spiked."""
+    if spikes.indels:
+        return spike_indel_run(eng, up, A, var, spikes.ins[chrom], idents, seed, mismatch_thr, nm, n_indel, mism=False)[:2]
+    return spike_run(eng, up, A, var, idents, seed, mismatch_thr, nm, n_indel)
+
+
+def free_spiked(spiked: RunOnDevice, up: RunOnDevice) -> None:
+    """The arrays of a spiked copy of `up` that are its own: aln and bq, and the CIGAR pool of a copy smc_spike_indels wrote."""
+    spiked.aln.free(); spiked.bq.free()
+    if spiked.cig is not up.cig:
+        spiked.cig.free()
+
+
+def copy_allele_key(spiked: RunOnDevice, A, decoder_key):
+    """`allele_key` for a copy smc_spike_indels wrote of run `A`: a relocated record's texts come from the copy - smc_bam_allele_key's
+    rules (csrc/smc_bam.cpp) over its records and the pairs behind the run's own, downloaded once, when the first such key is asked
+    for -, every other record keeps the decoder's answer (its site is a base the rewrite leaves alone or turns into a fixed key)."""
+    n_pairs = len(A["bq"]) // 2
+    got = {}
+
+    def key(ai, qpos, indel):
+        if "aln" not in got:
+            got["aln"] = spiked.aln.download(abi.DEV_ALN_DTYPE, spiked.n_aln)
+        a = got["aln"][int(ai)]
+        so, ls, qpos, indel = int(a["seq_off"]), int(a["l_seq"]), int(qpos), int(indel)
+        if so < n_pairs:
+            return decoder_key(ai, qpos, indel)
+        if "bq" not in got:
+            got["bq"] = spiked.bq.download(np.uint8, 2 * (spiked.pairs_used - n_pairs), 2 * n_pairs)
+        letters = got["bq"][2 * (so - n_pairs):2 * (so - n_pairs + ls):2]
+        if not (0 <= qpos < ls):
+            raise bamio.BamError("allele key of alignment %d at query position %d of %d" % (ai, qpos, ls))
+        site = chr(letters[qpos])
+        if indel > 0:
+            return "INS|%s|%s%s" % (site, site, letters[qpos + 1:qpos + 1 + indel].tobytes().decode())
+        if indel < 0:
+            return "D%d|%s" % (-indel, site)
+        return site
+    return key
 
 
 def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng, nthreads: int = 0, max_reads: int = 128_000_000,
@@ -1458,7 +1629,7 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                             second[(k, t, f)] = [None, int(car_f[r].sum()), None]
                 for t, target in enumerate(targets):
                     svar, sorder = spikes.chrom_variants(v0.chrom, target)
-                    spiked, stats = spike_run(eng, up, A, svar, idents, seed, P.mismatchThr, nm, n_indel)
+                    spiked, stats = spike_copy(eng, up, A, spikes, v0.chrom, svar, idents, seed, P.mismatchThr, nm, n_indel)
                     try:
                         cov1, car1, cnt1 = allele_carriers_run(eng, spiked, A, lo, var, ins, counts=True)
                         for f, frac in enumerate(fracs):
@@ -1470,7 +1641,7 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                             for r, k in enumerate(group):
                                 second[(k, t, f)][0], second[(k, t, f)][2] = int(cov_f[r].sum()), int(car_f[r].sum())
                     finally:
-                        spiked.aln.free(); spiked.bq.free()
+                        free_spiked(spiked, up)
                     for r, k in enumerate(group):
                         v = variants[k]
                         hit = sv.draw(idents, seed, spikes.lead_pos[k]) < np.uint64(sv.threshold(target))
@@ -1478,7 +1649,13 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                             b = bits.setdefault(k, (idents[cov[r][:len(idents)]], idents[car[r][:len(idents)]], [None] * len(targets)))
                             b[2][t] = idents[car1[r][:len(idents)]]
                         reads = int(stats[sorder.index(k), 0])
-                        if not np.array_equal(cov1[r], cov[r]) or reads != int(cnt1[r, hit[:cnt1.shape[1]], 1].sum()) or \
+                        if v.kind == af.SNV:
+                            shown = int(cnt1[r, hit[:cnt1.shape[1]], 1].sum())
+                        else:
+                            # (an insertion / a deletion: the eligible records of the spiked barcodes, restated from the host's arrays -
+                            # a read that shows it already, or whose anchor holds another letter, moves the `alt` counters otherwise)
+                            shown = spike_indel_reads(A, v, hit)
+                        if not np.array_equal(cov1[r], cov[r]) or reads != shown or \
                                 bool((car1[r] != car[r])[~hit[:car.shape[1]]].any()):
                             raise RuntimeError("--spikeAF %g: the kernel's statistics at %s:%d (%d records rewritten) do not agree with the "
                                                "host's restatement of the draws" % (target, v.chrom, v.pos, reads))

@@ -12,6 +12,9 @@ pages <outPrefix>.spikeAF.depth.detection.txt, .replicates.txt, .sensitivity.txt
 <outPrefix>.spikeAF.phase.txt, .phase.replicates.txt and .phase.sensitivity.txt say how many molecules carry a whole set and whether
 all of it was called.
 
+--spikeIndels: the variants file may hold insertions and deletions too (indels; tools.spike_variants --indels is the rule); the
+outputs and the detection page are --spikeAF's, V0 and V1 by the variant's INS / DEL key.
+
 The semantics are tools/spike_variants.py's (DESIGN.md "--spikeAF"); the rewrite on the GPU is csrc/k_spike.inc (smc_spike_alleles),
 the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the main pass are devplanes.spike_rules / spike_run.
 """
@@ -65,9 +68,11 @@ def targets(args):
 
 def variants(args, loc_list, fasta):
     """The variants of --spikeVariants, checked: the file's refusals (tools.spike_variants.parse_variants: SNVs only, with
-    --spikePhase MNV lines and PS= sets as well), REF the genome's letter, every variant a locus of --bedTarget."""
+    --spikePhase MNV lines and PS= sets as well, with --spikeIndels insertions and deletions whose footprints do not overlap), REF
+    the genome's letters, every variant a locus of --bedTarget."""
     try:
-        out = sv.parse_variants(args.spikeVariants, "--spikeVariants", phased=bool(getattr(args, "spikePhase", False)))
+        out = sv.parse_variants(args.spikeVariants, "--spikeVariants", phased=bool(getattr(args, "spikePhase", False)),
+                                indels=bool(getattr(args, "spikeIndels", False)))
         sv.check_reference(out, fasta, "--spikeVariants")
         loci = set((c, int(p)) for c, p in loc_list)
         for v in out:
@@ -101,6 +106,21 @@ def write_detection(out_prefix: str, variants, outputs, loc_index=None) -> None:
                 r = (res_rows or outputs[1][2])[i]
                 lod = float(lods[loc_index[key]]) if lods is not None else None
                 fh.write(detection_line(v, target, r, rows.get(key), cut.get(key), lod) + "\n")
+
+
+# ---- --spikeIndels
+def indels(args, spike_targets) -> bool:
+    """--spikeIndels -> whether --spikeVariants may hold insertions and deletions.  SystemExit: without --spikeAF; beside --spikeReps,
+    --spikeDepth or --spikePhase (what a replicate's or a cell's counters mean for an indel is not built)."""
+    if not getattr(args, "spikeIndels", False):
+        return False
+    if not spike_targets:
+        raise SystemExit("--spikeIndels lets --spikeVariants hold insertions and deletions for --spikeAF to plant: it needs --spikeAF")
+    for flag in ("spikeReps", "spikeDepth", "spikePhase"):
+        if getattr(args, flag, None) not in (None, "", False):
+            raise SystemExit("--spikeIndels cannot be combined with --%s in one run (replicates, depths and phase sets of indel spike-ins "
+                             "are not built)" % flag)
+    return True
 
 
 # ---- --spikeReps

@@ -21,6 +21,23 @@ every target, the files of a plain run on the BAM this writes.
   4. reported per variant: N covering barcodes, V0 carriers before (ds_allele_fraction's rule: more than half of the barcode's reads at
      the locus show ALT), S covering barcodes spiked, READS records rewritten (one that showed ALT already counts), V1 carriers after,
      AF = V1 / N.  Where the variant is present already the achieved fraction exceeds t: reported, not corrected.
+
+--indels (a run's --spikeIndels): the file may hold insertions (REF = X, ALT = XS) and deletions (REF = XD, ALT = X) too, 1 to 255
+letters S / D out of ACGT, REF the genome's letters.
+  footprint  the reference interval a variant needs: [P, P] (SNV), [P, P + 1] (insertion), [P, P + d + 1] (deletion of d).  A file whose
+             footprints overlap is refused by line.
+  draw       as above, with the variant's own P.
+  eligible   a record of a spiked barcode is rewritten at an insertion / a deletion when the whole footprint lies inside ONE M / = / X
+             operation of the record's ORIGINAL CIGAR (so the anchor is a base, nothing starts behind it and an aligned base follows
+             the indel) and inside its l_seq bases, and l_seq (+ |S|) and n_cig + 2 stay <= 65535 - counted over the variants taken
+             before it, in ascending position.  Every other record is left alone: one that ends inside the footprint, one in a
+             deletion there, one with an indel of its own there.  (A real molecule would give such a read a clip or mismatches: not
+             modelled.)  SNVs keep rule 3, on the original CIGAR.
+  rewrite    insertion: S behind the anchor's base, every letter with the anchor's quality; M(n) -> M(a) I(s) M(n - a).  Deletion:
+             the d bases behind the anchor go; M(n) -> M(a) D(d) M(n - a - d).  A = or X operation is split the same way.  pos, the
+             reference span (so the bin), flags and mapq stay; NM grows by s / d; MD is left as it is.
+  reported   V0 / V1 by the variant's INS|X|XS / DEL|XD|X key (ds_allele_fraction.read_key; a rewritten read whose anchor holds
+             another letter than X shows another key and is no carrier), READS the records rewritten.
 """
 from __future__ import annotations
 
@@ -151,27 +168,59 @@ def _parse_phased(path: str, flag: str):
     return PhasedVariants(out, [PhaseSet(sets[k][0], sets[k][1], tuple(sorted(sets[k][2], key=lambda i: out[i].pos))) for k in order], mnvs)
 
 
-def parse_variants(path: str, flag: str = "--variants", phased: bool = False):
+def footprint(v):
+    """The reference interval variant `v` needs, 1-based and closed: [P, P] (SNV), [P, P + 1] (insertion), [P, P + d + 1] (deletion)."""
+    return v.pos, v.pos + (0 if v.kind == af.SNV else 1 if v.kind == af.INS else len(v.ref))
+
+
+def _lines_of(path: str):
+    """(chrom, pos) -> line number of the file's variant lines (ds_allele_fraction.parse_variants has taken every one)."""
+    out = {}
+    with open(path) as fh:
+        for n, line in enumerate(fh, 1):
+            line = line.rstrip("\r\n")
+            if line.strip() and not line.startswith("#"):
+                f = line.split("\t")
+                out[(f[0], int(f[1]))] = n
+    return out
+
+
+def parse_variants(path: str, flag: str = "--variants", phased: bool = False, indels: bool = False):
     """The variants of a spike-in file, in file order: ds_allele_fraction.parse_variants' format and refusals, and only one-letter
     substitutions out of A, C, G, T (an insertion or a deletion would mean rewriting CIGARs).  ValueError names the variant refused.
     `phased` (--spikePhase / --phased): MNV lines and PS= entries make phase sets (_parse_phased) -> PhasedVariants; without it an
-    MNV line is refused as ever and PS= entries are not read."""
+    MNV line is refused as ever and PS= entries are not read.
+    `indels` (--spikeIndels / --indels): insertions X / XS and deletions XD / X of 1 to MAX_INS letters out of A, C, G, T are taken
+    too; footprints (footprint()) that overlap are refused by line."""
     if phased:
+        if indels:
+            raise ValueError("%s: phase sets of insertions and deletions are not built" % flag)
         return _parse_phased(path, flag)
     out = af.parse_variants(path)
     for v in out:
-        if v.kind != af.SNV:
+        if v.kind != af.SNV and not indels:
             raise ValueError("%s: %s:%d %s>%s is an insertion or a deletion; only one-letter substitutions can be spiked (an indel "
                              "means rewriting CIGARs)" % (flag, v.chrom, v.pos, v.ref, v.alt))
-        if v.ref not in LETTERS or v.alt not in LETTERS:
-            raise ValueError("%s: %s:%d %s>%s: REF and ALT must be one of A, C, G, T" % (flag, v.chrom, v.pos, v.ref, v.alt))
+        if any(c not in LETTERS for c in v.ref + v.alt):
+            raise ValueError("%s: %s:%d %s>%s: REF and ALT must be %s A, C, G, T" % (flag, v.chrom, v.pos, v.ref, v.alt,
+                                                                                  "one of" if v.kind == af.SNV else "made of"))
+        if v.kind == af.DEL and len(v.ref) - 1 > af.MAX_INS:
+            raise ValueError("%s: %s:%d: a deletion of %d letters, at most %d are taken" % (flag, v.chrom, v.pos, len(v.ref) - 1, af.MAX_INS))
+    if indels:
+        lines = _lines_of(path)
+        order = sorted(out, key=lambda v: (v.chrom, v.pos))
+        for u, v in zip(order, order[1:]):
+            if u.chrom == v.chrom and footprint(u)[1] >= v.pos:
+                raise ValueError("%s: %s line %d: %s:%d %s>%s lies in the footprint %d-%d of %s:%d %s>%s (line %d)" % (
+                    flag, path, lines[(v.chrom, v.pos)], v.chrom, v.pos, v.ref, v.alt, footprint(u)[0], footprint(u)[1], u.chrom, u.pos,
+                    u.ref, u.alt, lines[(u.chrom, u.pos)]))
     return out
 
 
 def check_reference(variants, fasta, flag: str = "--variants") -> None:
-    """REF of every variant must be the genome's upper-cased letter at its position."""
+    """REF of every variant must be the genome's upper-cased letter(s) at its position."""
     for v in variants:
-        letter = fasta.fetch(v.chrom, v.pos - 1, v.pos).upper()
+        letter = fasta.fetch(v.chrom, v.pos - 1, v.pos - 1 + len(v.ref)).upper()
         if letter != v.ref:
             raise ValueError("%s: %s:%d %s>%s: the reference genome has %r there, not %s" % (flag, v.chrom, v.pos, v.ref, v.alt, letter, v.ref))
     for chrom, pos, ref, n in getattr(variants, "mnvs", ()):     # (an MNV line: its letters that do not change too)
@@ -310,6 +359,121 @@ def spike_record(plan: Plan, a, chrom: str, ident: int, counts=None):
     return edits, inc
 
 
+MAX16 = 65535                   # l_seq and n_cig of a record are 16-bit fields of the device's records (and n_cig of the BAM's)
+
+
+def anchor_in_match(a, pos0: int, fp: int):
+    """-> (operation index, the anchor's offset in it, its query position) when the 0-based positions pos0 .. pos0 + fp all lie in ONE
+    M / = / X operation of alignment `a` and their bases inside its l_seq, else None."""
+    x, y = a.pos, 0
+    for ci, (op, l) in enumerate(a.cigar):
+        if op in (0, 7, 8):
+            if x <= pos0 < x + l:
+                d0 = pos0 - x
+                return (ci, d0, y + d0) if d0 + fp < l and y + d0 + fp < a.l_seq else None
+            x += l
+            y += l
+        elif op in (1, 4):
+            y += l
+        elif op in (2, 3):
+            if x <= pos0 < x + l:
+                return None
+            x += l
+    return None
+
+
+def spike_record_indels(plan: Plan, a, chrom: str, ident: int, counts=None, fasta=None):
+    """spike_record() for a list that holds insertions / deletions -> (actions, NM increments, relocated).  actions, ascending by
+    position: ("snv", query position, ALT) | ("ins", operation index, offset of the anchor in it, its query position, S) | ("del",
+    ..., d); every one resolved against the ORIGINAL CIGAR.  `relocated`: the record takes an insertion or a deletion."""
+    actions, inc, n_cig, l_seq = [], 0, len(a.cigar), a.l_seq
+    for k in plan.spanned(chrom, a.pos, a.end):
+        v = plan.variants[k]
+        hit = plan.is_spiked(k, ident)
+        if v.kind == af.SNV:
+            q = base_at(a, v.pos)
+            shows, ok = q is not None and a.seq[q] == v.alt, q is not None
+        else:
+            n = len(v.alt) - 1 if v.kind == af.INS else len(v.ref) - 1
+            at = anchor_in_match(a, v.pos - 1, 1 if v.kind == af.INS else n + 1)
+            ok = at is not None and n_cig + 2 <= MAX16 and (v.kind != af.INS or l_seq + n <= MAX16)
+            shows = af.read_key(a, v.pos, chrom, fasta) == af.variant_key(v, fasta)
+        if counts is not None:
+            c = counts[k].setdefault(ident, [0, 0, 0, 0])
+            c[0] += 1
+            c[1] += shows
+            # (a read that shows a listed insertion already is not eligible for it; a rewritten read whose anchor holds another letter
+            # than X shows another key than the variant's)
+            c[2] += (ok and (v.kind == af.SNV or a.seq[at[2]] == v.ref[0])) or shows if hit else shows
+            c[3] += hit and ok
+        if not (hit and ok):
+            continue
+        if v.kind == af.SNV:
+            actions.append(("snv", q, v.alt))
+            inc += a.seq[q] == v.ref
+        else:
+            actions.append(("ins", at[0], at[1], at[2], v.alt[1:]) if v.kind == af.INS else ("del", at[0], at[1], at[2], n))
+            inc += n
+            n_cig += 2
+            l_seq += n if v.kind == af.INS else -n
+    return actions, inc, any(x[0] != "snv" for x in actions)
+
+
+def apply_actions(a, actions):
+    """The CIGAR [(op, len)], SEQ and QUAL (bytes) of alignment `a` after `actions` (spike_record_indels)."""
+    seq, qual = list(a.seq), list(bytes(a.qual))
+    cigar = [list(c) for c in a.cigar]
+    for act in reversed(actions):                        # from the back: what stands in front keeps its indexes
+        if act[0] == "snv":
+            seq[act[1]] = act[2]
+            continue
+        kind, ci, d0, qa, x = act
+        op, l = cigar[ci]
+        if kind == "ins":
+            cigar[ci:ci + 1] = [[op, d0 + 1], [1, len(x)], [op, l - d0 - 1]]
+            seq[qa + 1:qa + 1] = list(x)
+            qual[qa + 1:qa + 1] = [qual[qa]] * len(x)
+        else:
+            cigar[ci:ci + 1] = [[op, d0 + 1], [2, x], [op, l - d0 - 1 - x]]
+            del seq[qa + 1:qa + 1 + x]
+            del qual[qa + 1:qa + 1 + x]
+    return [tuple(c) for c in cigar], "".join(seq), bytes(qual)
+
+
+def _set_nm(body: bytearray, o_aux: int, nm_new: int) -> None:
+    """NM of the record `body` (tags from o_aux) set to nm_new: in place where the tag is there and the value fits its type, else the
+    tag is taken out and added at the end with the smallest unsigned type that holds it."""
+    at = _nm_tag(bytes(body[o_aux:]))
+    if at is not None:
+        i, typ = at
+        try:
+            struct.pack_into(_NM_FMT[typ], body, o_aux + i + 3, nm_new)
+            return
+        except struct.error:
+            del body[o_aux + i:o_aux + i + 3 + _FIXED[typ]]
+    body += b"NM" + (b"C" + struct.pack("<B", nm_new) if nm_new < 256 else b"S" + struct.pack("<H", nm_new) if nm_new < 65536
+                     else b"I" + struct.pack("<I", nm_new))
+
+
+def rebuild_record(raw: bytes, cigar, seq: str, qual: bytes, nm_new: int) -> bytes:
+    """A raw record with its CIGAR, SEQ, QUAL, l_seq and n_cig replaced and NM set; the fixed fields (the bin too: the reference span
+    has not moved), the name and the other tags stay."""
+    body = raw[4:]
+    l_name, n_cig, l_seq = body[8], struct.unpack_from("<H", body, 12)[0], struct.unpack_from("<i", body, 16)[0]
+    o_aux = 32 + l_name + 4 * n_cig + (l_seq + 1) // 2 + l_seq
+    packed = bytearray((len(seq) + 1) // 2)
+    for i, ch in enumerate(seq):
+        packed[i >> 1] |= _NIBBLE[ch] << (4 if i % 2 == 0 else 0)
+    head = bytearray(body[:32 + l_name])
+    struct.pack_into("<H", head, 12, len(cigar))
+    struct.pack_into("<i", head, 16, len(seq))
+    out = head + b"".join(struct.pack("<I", (l << 4) | op) for op, l in cigar) + packed + bytearray(qual)
+    o_new = len(out)
+    out += body[o_aux:]
+    _set_nm(out, o_new, nm_new)
+    return struct.pack("<i", len(out)) + bytes(out)
+
+
 def report_rows(plan: Plan, counts):
     """Step 4 from the counters of spike_record -> per variant dict(N, V0, S, READS, V1)."""
     rows = []
@@ -324,8 +488,9 @@ def report_line(v, t: float, row) -> str:
         t, v.chrom, v.pos, v.ref, v.alt, row["N"], row["V0"], row["S"], row["READS"], row["V1"], float(row["V1"]) / row["N"] if row["N"] else 0.0)
 
 
-def spike_file(in_bam: str, out_bam: str, variants, t: float, seed: int):
-    """Steps 2-4 over a file -> per variant dict(N, V0, S, READS, V1); writes out_bam (None: only the numbers)."""
+def spike_file(in_bam: str, out_bam: str, variants, t: float, seed: int, fasta=None):
+    """Steps 2-4 over a file -> per variant dict(N, V0, S, READS, V1); writes out_bam (None: only the numbers).  `fasta`: names a
+    read's deleted letters when a deletion is listed (without one a deletion is compared by its length)."""
     ids = af.unique_idents(bamio.placed_barcodes(in_bam), in_bam)
     plan = Plan(variants, t, seed)
     counts = [dict() for _ in variants]
@@ -333,6 +498,7 @@ def spike_file(in_bam: str, out_bam: str, variants, t: float, seed: int):
     refs = [name for name, _ in probe.refs]
     probe.close()
     header, recs = bamio.iter_raw_records(in_bam)
+    with_indels = any(v.kind != af.SNV for v in variants)
 
     def out():
         for tid, q, raw in recs:
@@ -340,8 +506,16 @@ def spike_file(in_bam: str, out_bam: str, variants, t: float, seed: int):
                 a = bamio._parse_record(raw[4:])
                 bc = af.barcode_of(q)
                 if not (a.flag & 0x4) and a.cigar and bc is not None and plan.spanned(refs[tid], a.pos, a.end):
-                    edits, inc = spike_record(plan, a, refs[tid], ids.get(bc, af.fnv64(bc)), counts)
-                    if edits:
+                    ident = ids.get(bc, af.fnv64(bc))
+                    relocated = False
+                    if with_indels:
+                        actions, inc, relocated = spike_record_indels(plan, a, refs[tid], ident, counts, fasta)
+                        edits = [(x[1], x[2]) for x in actions]
+                    else:
+                        edits, inc = spike_record(plan, a, refs[tid], ident, counts)
+                    if relocated:
+                        raw = rebuild_record(raw, *apply_actions(a, actions), nm_new=a.nm + inc)
+                    elif edits:
                         raw = rewrite_record(raw, edits, a.nm + inc if inc else None)
             yield raw
     if out_bam is None:
@@ -356,16 +530,18 @@ def main(args):
     if args.runPath:
         os.chdir(args.runPath)
     try:
-        variants = parse_variants(args.variants, phased=bool(getattr(args, "phased", False)))
+        variants = parse_variants(args.variants, phased=bool(getattr(args, "phased", False)), indels=bool(getattr(args, "indels", False)))
         targets = af.parse_targets(args.af)
         if len(targets) != 1:
             raise ValueError("--af: one target allele fraction per output BAM, got %r" % args.af)
+        genome = None
         if args.refGenome:
             from .. import fasta as _fasta
-            check_reference(variants, _fasta.FastaFile(args.refGenome))
+            genome = _fasta.FastaFile(args.refGenome)
+            check_reference(variants, genome)
     except ValueError as e:
         raise SystemExit(str(e))
-    rows = spike_file(args.inBam, args.outBam, variants, targets[0], args.seed)
+    rows = spike_file(args.inBam, args.outBam, variants, targets[0], args.seed, genome)
     for v, row in zip(variants, rows):
         print(report_line(v, targets[0], row))
     return rows
@@ -382,6 +558,8 @@ def build_parser():
     parser.add_argument("--refGenome", default=None, help="indexed FASTA: REF of every listed variant must be its letter there")
     parser.add_argument("--phased", action="store_true", help="read MNV lines (REF and ALT of one length, 2 to 8 letters) and PS=<name> "
                         "entries of VCF column 8 as phase sets: the members of a set are planted on the same barcodes")
+    parser.add_argument("--indels", action="store_true", help="take insertions (REF X, ALT XS) and deletions (REF XD, ALT X) of 1 to 255 "
+                        "letters too: the records that hold the whole footprint in one aligned operation get the new SEQ, QUAL and CIGAR")
     return parser
 
 

@@ -723,6 +723,47 @@ int smc_spike_phase_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, const ui
                            const uint32_t* joint_off_host, const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_cnt_off,
                            const uint32_t* d_pos1, int32_t n_sets, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
                            int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream);
+/* (ABI 11, additive: three entries more, the version number unchanged) --spikeIndelReps / --spikeIndelDepth: replicates and barcode
+ * depths of the --spikeIndels spike-in.
+ *   smc_spike_indels_reps    n_copies copies (1 .. SMC_SPIKE_MAX_COPIES) of one run from one call.  `seeds` / `thr`: HOST memory, n_copies
+ *            words each - copy c is drawn with seeds[c] and EVERY variant at thr[c] (in [0, 2^32]; the variants' own `thr` is not
+ *            read).  Copy c is byte for byte what smc_spike_indels writes with seeds[c] and every thr = thr[c]: its records at
+ *            d_aln_out + c * aln_stride, its pair pool at d_bq_out + c * bq_stride (up to its totals[0] pairs), its CIGAR pool at
+ *            d_cig_out + c * cig_stride (up to its totals[1] words), d_nm_out[c][n_aln], d_n_indel_out[c][n_aln],
+ *            d_stats[c][n_var][2] and d_totals[c][3].  cap_pairs / cap_cig hold for every copy; nothing beyond a copy's capacity
+ *            is written, the bytes between a copy's end and the next stride are not written, the run's arrays are only read.  A
+ *            copy that needs more sets its own totals[c][2] and leaves the records that do not fit as the run has them; the other
+ *            copies are not affected.  The strides are BYTES: aln_stride a multiple of 4 and at least n_aln * sizeof(smc_dev_aln),
+ *            bq_stride / cig_stride multiples of 16 and at least 2 * cap_pairs / 4 * cap_cig; d_bq, d_cig, d_bq_out and d_cig_out
+ *            16-byte aligned (both pools travel in 16-byte chunks: read once, stored to every copy, before the scatter).  The
+ *            three launches of smc_spike_indels with a row of the grid per copy, one scan workgroup per copy; nothing waits for
+ *            the host.
+ *   smc_spike_indel_touch    d_out[v][n_bc] uint32 (zeroed by the call): per listed insertion / deletion v and barcode of the run
+ *            the records that take v when the barcode is spiked - smc_spike_indels' eligibility (the same device code), every
+ *            variant taken as hit.  An SNV's row stays 0.  Whether a record takes v depends on no other variant's draw as long as
+ *            the 16-bit limits of l_seq and n_cig cannot bind: the caller makes sure of that (n_cig + 2 k <= 65535 and l_seq + the
+ *            inserted letters <= 65535 for a record that spans k listed indels).  A record that points beyond the pools, or has
+ *            bc_gid >= n_bc, counts nowhere.  The variants' thresholds and inserted letters are not read.
+ *   smc_spike_indel_counts   smc_spike_rep_counts (depth_thr NULL: d_out[v][j][t][3]) or smc_spike_depth_counts (d_out[v][j][t][f][5])
+ *            from FOUR counters per covering barcode, d_cov_cnt[e][4] = (reads, alt0, alt1, touch): alt1 the reads that show ALT
+ *            when the barcode is hit (smc_allele_carriers' `alt` on a copy spiked at threshold 2^32), touch the records the rewrite
+ *            changes then (an SNV: alt1; an insertion / a deletion: smc_spike_indel_touch).  V1 takes 2 * (hit ? alt1 : alt0) >
+ *            reads, READS sums touch.  With alt1 = touch = single the numbers are those of the two entries named.
+ * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched and nothing copied: what smc_spike_indels (but for the variants'
+ * thresholds) and smc_spike_alleles_reps / smc_spike_rep_counts / smc_spike_depth_counts refuse, each for the entry that combines
+ * them; n_var * n_bc of 2^32 - 256 counters or more. */
+int smc_spike_indels_reps(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words, const uint8_t* d_bq,
+                          int64_t n_pairs, const smc_spike_indel_variant* d_var, const smc_spike_indel_variant* var_host, int32_t n_var,
+                          const uint8_t* d_ins, int64_t n_ins, const uint64_t* d_idents, int64_t n_bc, const uint64_t* seeds, const uint64_t* thr,
+                          int32_t n_copies, double mismatch_thr, const int32_t* d_nm, const int32_t* d_n_indel, int64_t cap_pairs,
+                          int64_t cap_cig, uint8_t* d_aln_out, int64_t aln_stride, uint8_t* d_bq_out, int64_t bq_stride, uint8_t* d_cig_out,
+                          int64_t cig_stride, int32_t* d_nm_out, int32_t* d_n_indel_out, uint32_t* d_stats, uint64_t* d_totals, void* stream);
+int smc_spike_indel_touch(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words, int64_t n_pairs,
+                          const smc_spike_indel_variant* d_var, const smc_spike_indel_variant* var_host, int32_t n_var, int64_t n_bc,
+                          uint32_t* d_out, void* stream);
+int smc_spike_indel_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_cnt, const uint32_t* d_cov_off,
+                           const uint32_t* cov_off_host, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
+                           const uint64_t* thr, int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

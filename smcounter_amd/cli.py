@@ -183,6 +183,20 @@ def build_parser() -> argparse.ArgumentParser:
                         "tools/spike_variants.py --indels does it; every other record is left alone.  The outputs are --spikeAF's, V0 "
                         "and V1 of .spikeAF.detection.txt by the variant's INS / DEL key.  Not with --spikeReps, --spikeDepth or "
                         "--spikePhase.  Without the flag an indel line is refused.  Needs --spikeAF")
+    p.add_argument("--spikeIndelReps", type=int, default=None,
+                   help="--spikeIndels and --spikeReps R in one: --spikeVariants may hold SNVs, insertions and deletions (the rules of "
+                        "--spikeIndels), and replicate j = 0 .. R - 1 is that spike-in with seed (dsSeed + j) mod 2^64 - a plain run on the "
+                        "BAM tools/spike_variants.py --indels --af t --seed (dsSeed + j) writes.  The run writes what --spikeIndels writes "
+                        "and <outPrefix>.spikeAF.replicates.txt, .spikeAF.sensitivity.txt and .spikeAF.curve.txt as --spikeReps does.  Per "
+                        "covering barcode four numbers are counted once on the GPU (its reads, those that show ALT, those that show it when "
+                        "the barcode is spiked, the records the rewrite changes then); several replicates' copies are written by one "
+                        "call.  Refused: a run with a record whose CIGAR or length could pass 65535 through the listed indels; beside "
+                        "--spikeIndels, --spikeReps, --spikeDepth or --spikePhase.  R in %d .. %d.  Needs --spikeAF" % (REPS_MIN, REPS_MAX))
+    p.add_argument("--spikeIndelDepth", default=None,
+                   help="--spikeDepth on the --spikeIndels spike-in: comma-separated barcode fractions f in (0, 1]; cells, files "
+                        "(<outPrefix>.spikeAF<t>.dsMT<f>.*, .spikeAF.depth.detection.txt, with --spikeIndelReps .spikeAF.depth.replicates / "
+                        ".sensitivity / .curve.txt), mtDepths and the limit of %d cells are --spikeDepth's.  Implies the rules of "
+                        "--spikeIndels.  Needs --spikeAF" % GRID_MAX_CELLS)
     p.add_argument("--spikeDepth", default=None,
                    help="the spike-ins of --spikeAF at several barcode depths: comma-separated fractions f in (0, 1].  For every target t "
                         "and every f the run is also called on the CELL (t, f): the spike-in at t, of which a barcode stays when the "
@@ -371,6 +385,7 @@ class _Plan:
     spike: dict = None          # (--spikeAF) once the rules are made: "variants", and "res", the pre-pass's numbers per target
     spike_reps: int = None      # (--spikeReps) R; plan.spike then holds "keep", what the pre-pass kept (None once the stage has taken it)
     spike_depth: dict = None    # (--spikeDepth) "fracs", the cells' "params", and once the rules are made "rules" and "counts" [V][T x F]
+    spike_indel_counters: bool = False   # (--spikeIndelReps, --spikeIndelDepth) the spike-ins are --spikeIndels', four counters per covering barcode
     spike_phase: bool = False   # (--spikePhase) plan.spike then holds "phase": None, or devplanes.spike_rules' dict of the sets of two members or more
 
     @property
@@ -404,7 +419,7 @@ def ds_af_rules(args, outs, variants, early, keep=None, depth=None):
     return rules, res
 
 
-def spike_rules(args, outs, variants, early, keep=None, depth=None, phase=None):
+def spike_rules(args, outs, variants, early, keep=None, depth=None, phase=None, indel_counters=False):
     """The devplanes.DsRule of every --spikeAF output (the pre-pass on the GPU: devplanes.spike_rules) and its numbers; the run log
     gets a line per variant and target.  `keep` (--spikeReps): a dict for what the replicate stage starts from.  `depth`
     (--spikeDepth): the plan's dict; it gets the cells' rules and counts.  `phase` (--spikePhase): a dict with the "sets" of two
@@ -412,6 +427,8 @@ def spike_rules(args, outs, variants, early, keep=None, depth=None, phase=None):
     from .tools import spike_variants as sv
     eng = _engine_of(args, early)
     more = {k: v for k, v in (("keep", keep), ("depth", depth), ("phase", phase)) if v is not None}
+    if indel_counters:
+        more["indel_counters"] = True
     try:
         rules, res = devplanes.spike_rules(args.bamFile, fasta.FastaFile(args.refGenome), variants, [o.af for o in outs],
                                            [o.params for o in outs], int(args.dsSeed), eng, **more)
@@ -754,7 +771,8 @@ def _main(args) -> int:
     af_fracs, af_cells = ds_af_depth_cells(args, af_targets)
     from . import spike as _spike
     spike_targets = _spike.targets(args)
-    spike_fracs, spike_cells = _spike.depth_cells(args, spike_targets)
+    indel_reps, indel_depth = _spike.indel_flags(args, spike_targets)
+    spike_fracs, spike_cells = _spike.depth_cells(args, spike_targets, "spikeIndelDepth" if indel_depth is not None else "spikeDepth")
     _spike.indels(args, spike_targets)
     at = lambda **kw: dataclasses.replace(params, **kw)
     plan = _Plan([_Output(args.outPrefix, params)] +
@@ -765,7 +783,8 @@ def _main(args) -> int:
                  [_Output(p, at(mtDepth=d), "dsAFDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in af_cells] +
                  [_Output(p, at(mtDepth=d), "spikeAF", af=t) for t, d, p in spike_targets] +
                  [_Output(p, at(mtDepth=d), "spikeDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in spike_cells],
-                 reps=ds_af_reps(args, af_targets), spike_reps=_spike.reps(args, spike_targets), spike_phase=_spike.phase(args, spike_targets))
+                 reps=ds_af_reps(args, af_targets), spike_reps=indel_reps if indel_reps is not None else _spike.reps(args, spike_targets),
+                 spike_phase=_spike.phase(args, spike_targets), spike_indel_counters=indel_reps is not None or indel_depth is not None)
     if spike_fracs is not None:
         plan.spike_depth = dict(fracs=spike_fracs, params=[o.params for o in plan.outputs if o.kind == "spikeDepth"])
     if af_fracs is not None:
@@ -843,12 +862,12 @@ def _make_rules(args, plan, loc_list):
     if sp:
         # (--spikeAF: the listed SNVs checked, then the pre-pass over the runs around them)
         from . import spike as _spike
-        variants = _spike.variants(args, loc_list, fasta.FastaFile(args.refGenome))
+        variants = _spike.variants(args, loc_list, fasta.FastaFile(args.refGenome), indels=plan.spike_indel_counters)
         keep = {} if plan.spike_reps is not None else None
         from .tools import spike_variants as sv
         psets = sv.phase_sets(variants) if plan.spike_phase else []
         phase = dict(sets=psets) if psets else None
-        rules, res = spike_rules(args, sp, variants, plan.early, keep, plan.spike_depth, phase)
+        rules, res = spike_rules(args, sp, variants, plan.early, keep, plan.spike_depth, phase, plan.spike_indel_counters)
         put(sp, rules)
         if plan.spike_depth is not None:
             put([o for o in plan.outputs if o.kind == "spikeDepth"], plan.spike_depth["rules"])

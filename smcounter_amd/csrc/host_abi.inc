@@ -1193,15 +1193,10 @@ int smc_spike_alleles(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, con
     return SMC_OK;
 }
 
-// (--spikeIndels) the run's records, pair pool and CIGAR pool copied; k_spi_count -> k_spi_scan -> k_spi_scatter behind the copies
-int smc_spike_indels(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words, const uint8_t* d_bq,
-                     int64_t n_pairs, const smc_spike_indel_variant* d_var, const smc_spike_indel_variant* var_host, int32_t n_var,
-                     const uint8_t* d_ins, int64_t n_ins, const uint64_t* d_idents, int64_t n_bc, uint64_t seed, double mismatch_thr,
-                     const int32_t* d_nm, const int32_t* d_n_indel, int64_t cap_pairs, int64_t cap_cig, smc_dev_aln* d_aln_out,
-                     uint8_t* d_bq_out, uint32_t* d_cig_out, int32_t* d_nm_out, int32_t* d_n_indel_out, uint32_t* d_stats,
-                     uint64_t* d_totals, void* stream) {
-    const std::string who = "smc_spike_indels";
-    if (!ctx || n_aln < 0 || n_pairs < 0 || n_cig_words < 0 || n_var < 0 || n_bc < 0 || n_ins < 0) return fail(SMC_E_ARG, who + ": bad argument");
+// (--spikeIndels, --spikeIndelReps) what the entries check of the listed variants, on their host copy.  `own_thr`: the variants' own
+// thresholds count; `d_ins` / `n_ins`: the pool of inserted letters, not looked at without `with_ins` (smc_spike_indel_touch)
+static int spi_check_variants(const std::string& who, const smc_spike_indel_variant* var_host, int32_t n_var, const uint8_t* d_ins, int64_t n_ins,
+                              bool with_ins, bool own_thr) {
     if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
     if (n_var && !var_host) return fail(SMC_E_ARG, who + ": NULL argument");
     auto acgt = [](uint8_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; };
@@ -1218,11 +1213,25 @@ int smc_spike_indels(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, cons
             return fail(SMC_E_INPUT, w + (V.kind == SMC_AF_SNV ? ": ref equals alt" : ": the anchor of an insertion / a deletion stands in ref and alt"));
         if (V.kind == SMC_AF_SNV ? V.len != 0 : (V.len < 1 || V.len > SMC_AF_MAX_INS))
             return fail(SMC_E_INPUT, w + ": a length of " + std::to_string(V.len) + " (1 .. " + std::to_string(SMC_AF_MAX_INS) + " for an insertion / a deletion, 0 for an SNV)");
-        if (V.kind == SMC_AF_INS && ((int64_t)V.ins_off + V.len > n_ins || !d_ins))
+        if (with_ins && V.kind == SMC_AF_INS && ((int64_t)V.ins_off + V.len > n_ins || !d_ins))
             return fail(SMC_E_INPUT, w + ": " + std::to_string(V.len) + " inserted letters at " + std::to_string(V.ins_off) + " (pool of " + std::to_string(n_ins) + ")");
-        if (V.thr > (1ull << 32)) return fail(SMC_E_INPUT, w + ": a threshold above 2^32");
+        if (own_thr && V.thr > (1ull << 32)) return fail(SMC_E_INPUT, w + ": a threshold above 2^32");
         if (v && fp_end(var_host[v - 1]) >= (int64_t)V.pos0) return fail(SMC_E_INPUT, w + ": its footprint overlaps that of the variant before it");
     }
+    return SMC_OK;
+}
+
+// (--spikeIndels, --spikeIndelReps) the body of both rewrite entries: n_copies copies at byte strides (one copy, `own_thr`, strides 0:
+// smc_spike_indels).  The pools reach the copies - hipMemcpyAsync for one, k_spike_pool for several -, then k_spi_count -> k_spi_scan ->
+// k_spi_scatter with a row of the grid (a workgroup of the scan) per copy.
+static int spi_copies(const std::string& who, smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words,
+                      const uint8_t* d_bq, int64_t n_pairs, const smc_spike_indel_variant* d_var, const smc_spike_indel_variant* var_host,
+                      int32_t n_var, const uint8_t* d_ins, int64_t n_ins, const uint64_t* d_idents, int64_t n_bc, const SpkCopies& C,
+                      int32_t n_copies, bool own_thr, double mismatch_thr, const int32_t* d_nm, const int32_t* d_n_indel, int64_t cap_pairs,
+                      int64_t cap_cig, uint8_t* d_aln_out, int64_t aln_stride, uint8_t* d_bq_out, int64_t bq_stride, uint8_t* d_cig_out,
+                      int64_t cig_stride, int32_t* d_nm_out, int32_t* d_n_indel_out, uint32_t* d_stats, uint64_t* d_totals, void* stream) {
+    if (!ctx || n_aln < 0 || n_pairs < 0 || n_cig_words < 0 || n_var < 0 || n_bc < 0 || n_ins < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (int rc = spi_check_variants(who, var_host, n_var, d_ins, n_ins, true, own_thr)) return rc;
     if (n_aln >= (int64_t)0xFFFFFF00 || n_bc >= (int64_t)0x7FFFFF00) return fail(SMC_E_ARG, who + ": run too large");
     if (cap_pairs < n_pairs || cap_cig < n_cig_words || cap_pairs > (int64_t)0xFFFFFFFF || cap_cig > (int64_t)0xFFFFFFFF)
         return fail(SMC_E_INPUT, who + ": capacities of " + std::to_string(cap_pairs) + " pairs / " + std::to_string(cap_cig) + " CIGAR words for a run of " +
@@ -1234,24 +1243,107 @@ int smc_spike_indels(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, cons
     HIPCHK(hipSetDevice(ctx->device));
     const hipStream_t st = (hipStream_t)stream;
     const size_t nb = ((size_t)n_aln + SPI_BLOCK - 1) / SPI_BLOCK;
-    const size_t cnt_bytes = (8 * (size_t)n_aln + 15) & ~(size_t)15, need = cnt_bytes + 16 * std::max<size_t>(nb, 1);
-    if (int rc = grow_scratch(ctx->spi_scratch, ctx->spi_bytes, need, need + need / 8, "smc_spike_indels", &st)) return rc;
+    const size_t cnt_bytes = (8 * (size_t)n_aln * (size_t)n_copies + 15) & ~(size_t)15, need = cnt_bytes + 16 * std::max<size_t>(nb, 1) * (size_t)n_copies;
+    if (int rc = grow_scratch(ctx->spi_scratch, ctx->spi_bytes, need, need + need / 8, who.c_str(), &st)) return rc;
     uint32_t* const cnt = (uint32_t*)ctx->spi_scratch;
     unsigned long long* const bsum = (unsigned long long*)((uint8_t*)ctx->spi_scratch + cnt_bytes);
-    if (n_pairs) HIPCHK(hipMemcpyAsync(d_bq_out, d_bq, 2 * (size_t)n_pairs, hipMemcpyDeviceToDevice, st));
-    if (n_cig_words) HIPCHK(hipMemcpyAsync(d_cig_out, d_cig, 4 * (size_t)n_cig_words, hipMemcpyDeviceToDevice, st));
-    if (n_var) hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)((2 * n_var + 255) / 256)), dim3(256), 0, st, d_stats, (uint32_t)(2 * n_var));
+    if (n_copies == 1) {
+        if (n_pairs) HIPCHK(hipMemcpyAsync(d_bq_out, d_bq, 2 * (size_t)n_pairs, hipMemcpyDeviceToDevice, st));
+        if (n_cig_words) HIPCHK(hipMemcpyAsync(d_cig_out, d_cig, 4 * (size_t)n_cig_words, hipMemcpyDeviceToDevice, st));
+    } else {
+        // (each pool read once and stored to every copy in 16-byte chunks, before the scatter appends behind it)
+        auto pool = [&](const uint8_t* src, size_t n_bytes, uint8_t* dst, int64_t stride) {
+            if (!n_bytes) return;
+            hipLaunchKernelGGL(k_spike_pool, dim3((unsigned)std::min<size_t>(((n_bytes + 15) / 16 + SPR_BLOCK - 1) / SPR_BLOCK, 2048)), dim3(SPR_BLOCK), 0, st,
+                               src, (unsigned long long)n_bytes, dst, (unsigned long long)stride, (int)n_copies);
+        };
+        pool(d_bq, 2 * (size_t)n_pairs, d_bq_out, bq_stride);
+        pool((const uint8_t*)d_cig, 4 * (size_t)n_cig_words, d_cig_out, cig_stride);
+    }
+    const size_t n_st = 2 * (size_t)n_var * (size_t)n_copies;
+    if (n_st) hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_st + 255) / 256, 4096)), dim3(256), 0, st, d_stats, (uint32_t)n_st);
     if (n_aln)
-        hipLaunchKernelGGL(k_spi_count, dim3((unsigned)nb), dim3(SPI_BLOCK), 0, st, d_aln, (uint32_t)n_aln, d_cig, (unsigned long long)n_pairs,
-                           (unsigned long long)n_cig_words, d_var, (int)n_var, (const unsigned long long*)d_idents, (uint32_t)n_bc,
-                           (unsigned long long)seed, cnt, bsum);
-    hipLaunchKernelGGL(k_spi_scan, dim3(1), dim3(SPI_BLOCK), 0, st, bsum, (uint32_t)nb, (unsigned long long)n_pairs, (unsigned long long)n_cig_words,
-                       (unsigned long long)cap_pairs, (unsigned long long)cap_cig, (unsigned long long*)d_totals);
+        hipLaunchKernelGGL(k_spi_count, dim3((unsigned)nb, (unsigned)n_copies), dim3(SPI_BLOCK), 0, st, d_aln, (uint32_t)n_aln, d_cig,
+                           (unsigned long long)n_pairs, (unsigned long long)n_cig_words, d_var, (int)n_var, (const unsigned long long*)d_idents,
+                           (uint32_t)n_bc, C, own_thr ? 1 : 0, cnt, bsum);
+    hipLaunchKernelGGL(k_spi_scan, dim3((unsigned)n_copies), dim3(SPI_BLOCK), 0, st, bsum, (uint32_t)nb, (unsigned long long)n_pairs,
+                       (unsigned long long)n_cig_words, (unsigned long long)cap_pairs, (unsigned long long)cap_cig, (unsigned long long*)d_totals);
     if (n_aln)
-        hipLaunchKernelGGL(k_spi_scatter, dim3((unsigned)nb), dim3(SPI_BLOCK), 0, st, d_aln, (uint32_t)n_aln, d_cig, d_bq, (unsigned long long)n_pairs,
-                           (unsigned long long)n_cig_words, d_var, (int)n_var, d_ins, (const unsigned long long*)d_idents, (uint32_t)n_bc,
-                           (unsigned long long)seed, mismatch_thr, d_nm, d_n_indel, (const uint32_t*)cnt, (const unsigned long long*)bsum,
-                           (unsigned long long)cap_pairs, (unsigned long long)cap_cig, d_aln_out, d_bq_out, d_cig_out, d_nm_out, d_n_indel_out, d_stats);
+        hipLaunchKernelGGL(k_spi_scatter, dim3((unsigned)nb, (unsigned)n_copies), dim3(SPI_BLOCK), 0, st, d_aln, (uint32_t)n_aln, d_cig, d_bq,
+                           (unsigned long long)n_pairs, (unsigned long long)n_cig_words, d_var, (int)n_var, d_ins, (const unsigned long long*)d_idents,
+                           (uint32_t)n_bc, C, own_thr ? 1 : 0, mismatch_thr, d_nm, d_n_indel, (const uint32_t*)cnt, (const unsigned long long*)bsum,
+                           (unsigned long long)cap_pairs, (unsigned long long)cap_cig, d_aln_out, (unsigned long long)aln_stride, d_bq_out,
+                           (unsigned long long)bq_stride, d_cig_out, (unsigned long long)cig_stride, d_nm_out, d_n_indel_out, d_stats);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
+// (--spikeIndels) the run's records, pair pool and CIGAR pool copied; k_spi_count -> k_spi_scan -> k_spi_scatter behind the copies
+int smc_spike_indels(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words, const uint8_t* d_bq,
+                     int64_t n_pairs, const smc_spike_indel_variant* d_var, const smc_spike_indel_variant* var_host, int32_t n_var,
+                     const uint8_t* d_ins, int64_t n_ins, const uint64_t* d_idents, int64_t n_bc, uint64_t seed, double mismatch_thr,
+                     const int32_t* d_nm, const int32_t* d_n_indel, int64_t cap_pairs, int64_t cap_cig, smc_dev_aln* d_aln_out,
+                     uint8_t* d_bq_out, uint32_t* d_cig_out, int32_t* d_nm_out, int32_t* d_n_indel_out, uint32_t* d_stats,
+                     uint64_t* d_totals, void* stream) {
+    SpkCopies C;
+    memset(&C, 0, sizeof C);
+    C.seed[0] = seed;
+    return spi_copies("smc_spike_indels", ctx, d_aln, n_aln, d_cig, n_cig_words, d_bq, n_pairs, d_var, var_host, n_var, d_ins, n_ins, d_idents, n_bc,
+                      C, 1, true, mismatch_thr, d_nm, d_n_indel, cap_pairs, cap_cig, (uint8_t*)d_aln_out, 0, d_bq_out, 0, (uint8_t*)d_cig_out, 0,
+                      d_nm_out, d_n_indel_out, d_stats, d_totals, stream);
+}
+
+// (--spikeIndelReps) n_copies copies of smc_spike_indels from one call, every variant at the copy's threshold
+int smc_spike_indels_reps(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words, const uint8_t* d_bq,
+                          int64_t n_pairs, const smc_spike_indel_variant* d_var, const smc_spike_indel_variant* var_host, int32_t n_var,
+                          const uint8_t* d_ins, int64_t n_ins, const uint64_t* d_idents, int64_t n_bc, const uint64_t* seeds, const uint64_t* thr,
+                          int32_t n_copies, double mismatch_thr, const int32_t* d_nm, const int32_t* d_n_indel, int64_t cap_pairs,
+                          int64_t cap_cig, uint8_t* d_aln_out, int64_t aln_stride, uint8_t* d_bq_out, int64_t bq_stride, uint8_t* d_cig_out,
+                          int64_t cig_stride, int32_t* d_nm_out, int32_t* d_n_indel_out, uint32_t* d_stats, uint64_t* d_totals, void* stream) {
+    const std::string who = "smc_spike_indels_reps";
+    if (n_copies < 1 || n_copies > SMC_SPIKE_MAX_COPIES)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies, 1 .. " + std::to_string(SMC_SPIKE_MAX_COPIES) + " expected");
+    if (!seeds || !thr) return fail(SMC_E_ARG, who + ": NULL argument");
+    SpkCopies C;
+    memset(&C, 0, sizeof C);
+    for (int32_t c = 0; c < n_copies; ++c) {
+        if (thr[c] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": copy " + std::to_string(c) + ": a threshold above 2^32");
+        C.seed[c] = seeds[c]; C.thr[c] = thr[c];
+    }
+    if (n_aln < 0 || cap_pairs < 0 || cap_cig < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (aln_stride < n_aln * (int64_t)sizeof(smc_dev_aln) || bq_stride < 2 * cap_pairs || cig_stride < 4 * cap_cig)
+        return fail(SMC_E_INPUT, who + ": strides of " + std::to_string(aln_stride) + ", " + std::to_string(bq_stride) + " and " + std::to_string(cig_stride) +
+                                 " bytes are smaller than a copy (" + std::to_string(n_aln * (int64_t)sizeof(smc_dev_aln)) + ", " +
+                                 std::to_string(2 * cap_pairs) + " and " + std::to_string(4 * cap_cig) + " bytes)");
+    if ((aln_stride & 3) || (bq_stride & 15) || (cig_stride & 15) ||
+        (((uintptr_t)d_bq | (uintptr_t)d_bq_out | (uintptr_t)d_cig | (uintptr_t)d_cig_out) & 15u) || ((uintptr_t)d_aln_out & 3u))
+        return fail(SMC_E_ARG, who + ": the record stride must be a multiple of 4 bytes, the pools' strides and addresses of 16");
+    if ((double)n_copies * (double)n_var * 2.0 >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies x " + std::to_string(n_var) + " variants: too many statistics words for one call");
+    return spi_copies(who, ctx, d_aln, n_aln, d_cig, n_cig_words, d_bq, n_pairs, d_var, var_host, n_var, d_ins, n_ins, d_idents, n_bc, C, n_copies,
+                      false, mismatch_thr, d_nm, d_n_indel, cap_pairs, cap_cig, d_aln_out, aln_stride, d_bq_out, bq_stride, d_cig_out, cig_stride,
+                      d_nm_out, d_n_indel_out, d_stats, d_totals, stream);
+}
+
+// (--spikeIndelReps) per listed insertion / deletion and barcode of the run the records the rewrite changes when the barcode is spiked
+int smc_spike_indel_touch(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words, int64_t n_pairs,
+                          const smc_spike_indel_variant* d_var, const smc_spike_indel_variant* var_host, int32_t n_var, int64_t n_bc,
+                          uint32_t* d_out, void* stream) {
+    const std::string who = "smc_spike_indel_touch";
+    if (!ctx || n_aln < 0 || n_pairs < 0 || n_cig_words < 0 || n_var < 0 || n_bc < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (int rc = spi_check_variants(who, var_host, n_var, nullptr, 0, false, false)) return rc;
+    if (n_aln >= (int64_t)0xFFFFFF00 || n_bc >= (int64_t)0x7FFFFF00) return fail(SMC_E_ARG, who + ": run too large");
+    if ((double)n_var * (double)n_bc >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants x " + std::to_string(n_bc) + " barcodes: too many counters for one call");
+    const size_t n_out = (size_t)n_var * (size_t)n_bc;
+    if (!n_out) return SMC_OK;
+    if (!d_var || !d_out || (n_aln && (!d_aln || !d_cig))) return fail(SMC_E_ARG, who + ": NULL argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
+    if (n_aln)
+        hipLaunchKernelGGL(k_spi_touch, dim3((unsigned)(((size_t)n_aln + SPI_BLOCK - 1) / SPI_BLOCK)), dim3(SPI_BLOCK), 0, st, d_aln, (uint32_t)n_aln, d_cig,
+                           (unsigned long long)n_pairs, (unsigned long long)n_cig_words, d_var, (int)n_var, (uint32_t)n_bc, d_out);
     HIPCHK(hipGetLastError());
     return SMC_OK;
 }
@@ -1307,7 +1399,7 @@ static int spk_cell_counts(const std::string& who, smc_ctx* ctx, const uint64_t*
                            const uint32_t* off_host, bool sets, const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_cnt_off,
                            const uint32_t* d_pos1, int32_t n_rows, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
                            int32_t n_targets, bool has_fracs, const uint64_t* depth_thr, int32_t n_fracs, uint32_t want, uint32_t* d_out,
-                           void* stream) {
+                           void* stream, uint32_t cs = 3, uint32_t i_alt1 = 2, uint32_t i_touch = 2) {
     const std::string rows = sets ? " sets" : " variants", row = sets ? "set " : "variant ";
     const int n_want = __builtin_popcount(want);
     if (!ctx || n_rows < 0 || n_reps < 0 || n_targets < 0) return fail(SMC_E_ARG, who + ": bad argument");
@@ -1349,9 +1441,9 @@ static int spk_cell_counts(const std::string& who, smc_ctx* ctx, const uint64_t*
                                      std::to_string(SMC_SPIKE_PHASE_MAX_MEMBERS) + " expected");
         if (off_host[g + 1] < off_host[g]) return fail(SMC_E_INPUT, who + ": the offsets decrease at " + row + std::to_string(g));
         widest = std::max(widest, off_host[g + 1] - off_host[g]);
-        cnt_words += 3.0 * (double)m * (double)(off_host[g + 1] - off_host[g]);
+        cnt_words += (double)cs * (double)m * (double)(off_host[g + 1] - off_host[g]);
     }
-    // (without sets cnt_words is 3 * off_host[n_rows], below 2^32 - 256 with the first limit)
+    // (without sets and with three counters cnt_words is 3 * off_host[n_rows], below 2^32 - 256 with the first limit)
     if (off_host[n_rows] >= 0x55555500u || cnt_words >= (double)0xFFFFFF00u)
         return fail(SMC_E_INPUT, who + ": too many " + (sets ? "joint" : "covering") + " barcodes for one call");
     if (off_host[n_rows] && (!d_ident || !d_cnt)) return fail(SMC_E_ARG, who + (sets ? ": NULL joint barcodes" : ": NULL covers"));
@@ -1362,7 +1454,7 @@ static int spk_cell_counts(const std::string& who, smc_ctx* ctx, const uint64_t*
     if (widest)
         hipLaunchKernelGGL(k_spike_cells, dim3((unsigned)std::min<uint32_t>((widest + SPR_BLOCK - 1) / SPR_BLOCK, 256u), (unsigned)n_rows,
                                                (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPR_BLOCK), 0, st,
-                           (const unsigned long long*)d_ident, d_cnt, d_off, sets ? d_set_m : nullptr, sets ? d_cnt_off : nullptr, d_pos1, T,
+                           (const unsigned long long*)d_ident, d_cnt, cs, i_alt1, i_touch, d_off, sets ? d_set_m : nullptr, sets ? d_cnt_off : nullptr, d_pos1, T,
                            (int)n_targets, D, (int)n_fracs, with_depth, (const unsigned long long*)d_seeds, (int)n_reps, want, d_out);
     HIPCHK(hipGetLastError());
     return SMC_OK;
@@ -1382,6 +1474,17 @@ int smc_spike_depth_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint
                            const uint64_t* thr, int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream) {
     return spk_cell_counts("smc_spike_depth_counts", ctx, d_cov_ident, d_cov_cnt, d_cov_off, cov_off_host, false, nullptr, nullptr, nullptr,
                            d_pos1, n_var, d_seeds, n_reps, thr, n_targets, true, depth_thr, n_fracs, 0x1Fu, d_out, stream);
+}
+
+// (--spikeIndelReps, --spikeIndelDepth) smc_spike_rep_counts' numbers (depth_thr NULL) or smc_spike_depth_counts' from FOUR counters per
+// covering barcode, (reads, alt0, alt1, touch): k_spike_cells with stride 4, car1 from column 2 and READS' from column 3
+int smc_spike_indel_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_cnt, const uint32_t* d_cov_off,
+                           const uint32_t* cov_off_host, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
+                           const uint64_t* thr, int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream) {
+    const bool cells = depth_thr != nullptr;
+    return spk_cell_counts("smc_spike_indel_counts", ctx, d_cov_ident, d_cov_cnt, d_cov_off, cov_off_host, false, nullptr, nullptr, nullptr,
+                           d_pos1, n_var, d_seeds, n_reps, thr, n_targets, cells, depth_thr, cells ? n_fracs : 1, cells ? 0x1Fu : 0x1Cu, d_out,
+                           stream, 4, 2, 3);
 }
 
 // (--spikePhase) (N_ALL', V0_ALL', S_ALL', V1_ALL') of every phase set, replicate and cell

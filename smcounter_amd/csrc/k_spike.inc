@@ -11,6 +11,7 @@
 //                     is 1 KiB of consecutive bytes), the bytes behind the last whole chunk by one lane, one at a time, so that nothing
 //                     beyond a copy's 2 * n_pairs bytes is written.  A launch of its own: the rewrite behind it, on the same stream, finds
 //                     every copy complete.  (smc_spike_alleles copies its one pool with hipMemcpyAsync: no alignment asked of it.)
+//                     smc_spike_indels_reps (k_spike_indel.inc) sends the pair pool AND the CIGAR pool through it, one launch each.
 //   k_spike_rewrite   blockIdx.y = copy c, a lane per alignment; the copies' seeds and thresholds come by value (at most
 //                     SMC_SPIKE_MAX_COPIES of each).  Per listed variant v whose 0-based position lies in the alignment's [pos, end) (the
 //                     variants are sorted by position: a binary search for the first, then along the array):

@@ -27,6 +27,12 @@
 //                  workgroup's four wavefronts added in LDS, then one atomic add per workgroup, replicate, cell and WANTED counter that
 //                  is not 0.  `want` (uniform): bit k = counter k of (N', V0', S', READS', V1') is stored, the stored ones one behind
 //                  the other in that order - 0b11100 for the replicates, 0b11111 for the depths, 0b10111 for the phase sets.
+// --spikeIndelReps, --spikeIndelDepth (smc_spike_indel_counts): for an insertion or a deletion `single` is two numbers - the reads
+// that show ALT when the barcode is hit (`alt1`: those that show it already, and the rewritten ones whose anchor letter is REF's) and
+// the records the rewrite changes (`touch`: an eligible record whose anchor holds another letter is rewritten, and shows another key).
+// The host then gives FOUR numbers per barcode, (reads, alt0, alt1, touch), and the kernel takes the row's stride `cs` and the two
+// columns as uniform arguments: car1 from column `i_alt1`, READS' from column `i_touch`.  cs = 3 with both columns 2 is the kernel of
+// the three entries above.
 // Once per run / once per file: not on the per-locus hot path.
 #define SPC_COUNTERS 5
 static_assert(SMC_SPIKE_REP_MAX_TARGETS <= SMC_AF_DEPTH_MAX_CELLS && SPC_COUNTERS * SMC_AF_DEPTH_MAX_CELLS <= SPR_BLOCK,
@@ -41,9 +47,10 @@ __device__ __forceinline__ uint32_t spd_hits(const SpkThr& T, uint32_t u, int n_
 
 // out[((g * n_reps + j) * n_tgt * n_frac + t * n_frac + f) * popcount(want) + k] += the k-th wanted counter of row g (zeroed before
 // the launch); n_tgt * n_frac <= SMC_AF_DEPTH_MAX_CELLS.  Row g: barcodes [off[g], off[g + 1]) of `ident`, M = set_m[g] members (1 ..
-// SMC_SPIKE_PHASE_MAX_MEMBERS, checked by the host; 1 when set_m is NULL), counters cnt[base + (e - off[g]) * 3 * M + 3 * m + {0, 1, 2}]
-// = (reads, alt0, single) with base = cnt_off[g], or 3 * off[g] when cnt_off is NULL (every row has one member).
+// SMC_SPIKE_PHASE_MAX_MEMBERS, checked by the host; 1 when set_m is NULL), counters cnt[base + (e - off[g]) * cs * M + cs * m + {0, 1,
+// i_alt1, i_touch}] = (reads, alt0, alt1, touch) with base = cnt_off[g], or cs * off[g] when cnt_off is NULL (every row has one member).
 __global__ __launch_bounds__(SPR_BLOCK) void k_spike_cells(const unsigned long long* __restrict__ ident, const uint32_t* __restrict__ cnt,
+                                                           uint32_t cs, uint32_t i_alt1, uint32_t i_touch,
                                                            const uint32_t* __restrict__ off, const uint32_t* __restrict__ set_m,
                                                            const uint32_t* __restrict__ cnt_off, const uint32_t* __restrict__ pos1, SpkThr T,
                                                            int n_tgt, AfdThr D, int n_frac, int with_depth,
@@ -52,7 +59,7 @@ __global__ __launch_bounds__(SPR_BLOCK) void k_spike_cells(const unsigned long l
     __shared__ uint32_t part[SPR_BLOCK / WAVE][SMC_AF_DEPTH_MAX_CELLS][SPC_COUNTERS];
     const uint32_t g = blockIdx.y;
     const uint32_t e0 = off[g], e1 = off[g + 1], pos = pos1[g], M = set_m ? set_m[g] : 1u;
-    const uint32_t* const cnt_g = cnt + (cnt_off ? (size_t)cnt_off[g] : 3 * (size_t)e0);
+    const uint32_t* const cnt_g = cnt + (cnt_off ? (size_t)cnt_off[g] : (size_t)cs * e0);
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const int n_cells = n_tgt * n_frac, n_want = __popc(want);
     const uint32_t stride = gridDim.x * SPR_BLOCK;
@@ -64,13 +71,13 @@ __global__ __launch_bounds__(SPR_BLOCK) void k_spike_cells(const unsigned long l
         bool car0 = live, car1 = live;                                                 // carries EVERY member before / when hit
         if (live) {
             id = ident[e];
-            const uint32_t* const row = cnt_g + (size_t)(e - e0) * 3u * M;
+            const uint32_t* const row = cnt_g + (size_t)(e - e0) * cs * M;
             for (uint32_t m = 0; m < M; ++m) {
-                const unsigned long long reads = row[3 * m], alt0 = row[3 * m + 1], sgl = row[3 * m + 2];
+                const unsigned long long reads = row[cs * m], alt0 = row[cs * m + 1], sgl = row[cs * m + i_alt1];
                 car0 = car0 && 2ull * alt0 > reads;
                 car1 = car1 && 2ull * sgl > reads;
             }
-            if (M == 1u) single = row[2];
+            if (M == 1u) single = row[i_touch];
         }
         for (int j = blockIdx.z; j < n_reps; j += gridDim.z) {
             const unsigned long long seed = seeds[j];

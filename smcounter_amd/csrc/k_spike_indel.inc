@@ -1,6 +1,8 @@
 // Included by smcounter_hip.hip (after k_spike.inc: SPK_DOMAIN, the SNV rule it restates; after k_bp_emit2.inc: bp2_resolve).
 // ------------------------------------------------------------------------------------------
-// --spikeIndels: listed insertions and deletions (and SNVs beside them) planted in a copy of a run (smc_spike_indels)
+// --spikeIndels: listed insertions and deletions (and SNVs beside them) planted in a copy of a run (smc_spike_indels);
+// --spikeIndelReps: several such copies from one call (smc_spike_indels_reps), and the records each listed indel can touch
+// (smc_spike_indel_touch)
 // ------------------------------------------------------------------------------------------
 // An indel changes a record's length, CIGAR and query layout: the records that take one are RELOCATED - their pairs and CIGAR words
 // written anew behind the run's own, in alignment order, densely - and every other record goes through k_spike_rewrite's rule in
@@ -13,11 +15,20 @@
 //                   workgroup.  A relocated record walks its CIGAR and its variants once more (spi_walk<true>) and stores operations
 //                   and pairs; the others take the SNV rule in place.  Every record, nm_out, n_indel_out; stats by atomics.
 // The scan is a sum of integers in a fixed tree: the offsets are the same in every call.
+// SEVERAL COPIES (smc_spike_indels_reps): blockIdx.y = copy c in all three kernels - its seed and threshold come by value (SpkCopies,
+// every variant at the copy's threshold unless `own_thr`), its cnt[] / bsum[] / totals[] / statistics stand one copy behind the
+// other, its outputs at byte strides.  The run's two pools reach every copy by k_spike_pool (read once, stored n_copies times in
+// 16-byte chunks) before the scatter appends to them.  One copy with own_thr is smc_spike_indels.
+//   k_spi_touch     a lane per alignment: spi_walk<false, true> - no draw, every listed insertion / deletion taken as hit - adds 1 to
+//                   out[v][bc_gid] for every one the record is eligible for: the records the rewrite changes at v when the barcode is
+//                   spiked.  The eligibility is spi_walk's own lines, not a restatement.
 // Eligible (the specification is tools/spike_variants.py): the variant's footprint - the anchor and the position behind it (an
 // insertion), the anchor, the d deleted positions and the one behind them (a deletion) - inside ONE M / = / X operation of the
 // ORIGINAL CIGAR, its query positions inside l_seq; the record's l_seq and n_cig, as the variants before it left them, still in 16
 // bits.  Variants are taken in ascending position; their footprints are disjoint (the host checked), so a split operation's rest
-// holds the next one whole or not at all.
+// holds the next one whole or not at all.  For the same reason whether a record takes variant v depends on no other variant's draw,
+// but for the two 16-bit limits, which count what the variants before it added: the host of --spikeIndelReps refuses a run in which
+// they could bind (devplanes.spike_indel_limits), and then k_spi_touch's numbers hold for every draw.
 #define SPI_BLOCK 256
 #define SPI_MAX16 65535u
 static_assert(sizeof(smc_spike_indel_variant) == 24, "abi.SPIKE_INDEL_VARIANT_DTYPE");
@@ -41,12 +52,16 @@ struct SpiRes { uint32_t l_seq, n_cig; int nm_inc, indel_inc; };
 
 // One record against its variants var[lo ..] (those with pos0 < a.end).  EMIT false: only the indel kinds are drawn, nothing is stored
 // -> whether any hit is eligible, R.l_seq / R.n_cig the record's new sizes.  EMIT true: the SNVs are drawn too, the operations go to
-// oc[], the pairs to op[] (the caller made sure that R.n_cig words and R.l_seq pairs fit), stats[] counts.
-template <bool EMIT>
+// oc[], the pairs to op[] (the caller made sure that R.n_cig words and R.l_seq pairs fit), stats[] counts.  A variant's threshold is
+// its own with `own_thr`, else `thr_c`.  TOUCH (with EMIT false): nothing is drawn - every insertion / deletion counts as hit - and
+// stats[k * touch_stride] counts every one the record is eligible for.
+template <bool EMIT, bool TOUCH = false>
 __device__ __forceinline__ bool spi_walk(const smc_dev_aln& a, const uint32_t* __restrict__ cg, const uint8_t* __restrict__ src,
                                          const smc_spike_indel_variant* __restrict__ var, int lo, int n_var, const uint8_t* __restrict__ ins,
-                                         unsigned long long id, unsigned long long seed, uint32_t* __restrict__ oc, uint8_t* __restrict__ op,
-                                         uint32_t* __restrict__ stats, SpiRes& R) {
+                                         unsigned long long id, unsigned long long seed, unsigned long long thr_c, int own_thr,
+                                         uint32_t* __restrict__ oc, uint8_t* __restrict__ op, uint32_t* __restrict__ stats, size_t touch_stride,
+                                         SpiRes& R) {
+    static_assert(!(EMIT && TOUCH), "spi_walk: TOUCH counts, it stores no record");
     const int n_cig = (int)a.n_cig, l_seq = (int)a.l_seq;
     int ci = 0, x = a.pos, y = 0, used = 0;                      // operation ci starts at reference x, query y; `used` of it are out already
     int yq = 0;                                                  // pairs [0, yq) of the record are dealt with
@@ -72,9 +87,11 @@ __device__ __forceinline__ bool spi_walk(const smc_dev_aln& a, const uint32_t* _
         const smc_spike_indel_variant V = var[k];
         if (V.pos0 >= a.end) break;
         if (!EMIT && V.kind == SMC_AF_SNV) continue;
-        uint32_t u[4];
-        smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, (uint32_t)V.pos0 + 1u, (uint32_t)seed, (uint32_t)(seed >> 32), u);
-        if (!((unsigned long long)u[0] < V.thr)) continue;
+        if (!TOUCH) {
+            uint32_t u[4];
+            smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, (uint32_t)V.pos0 + 1u, (uint32_t)seed, (uint32_t)(seed >> 32), u);
+            if (!((unsigned long long)u[0] < (own_thr ? V.thr : thr_c))) continue;
+        }
         if (V.kind == SMC_AF_SNV) {                              // k_spike_rewrite's rule, on the original CIGAR
             const BpRes r = bp2_resolve(cg, n_cig, a.pos, V.pos0, l_seq);
             if (r.isdel || r.indel != 0 || r.qpos < yq || r.qpos >= l_seq) continue;
@@ -104,6 +121,7 @@ __device__ __forceinline__ bool spi_walk(const smc_dev_aln& a, const uint32_t* _
         if (d0 < used || (long long)d0 + fp >= (long long)len || qa + fp >= l_seq || qa < yq) continue;
         if (cur_c + 2u > SPI_MAX16 || (V.kind == SMC_AF_INS && cur_l + (uint32_t)n > SPI_MAX16)) continue;
         any = true;
+        if (TOUCH) atomicAdd(&stats[(size_t)k * touch_stride], 1u);
         cur_c += 2u;
         const int head = d0 - used + 1;
         if (EMIT) { oc[oci] = (uint32_t)head << 4 | (uint32_t)o; oc[oci + 1] = (uint32_t)n << 4 | (V.kind == SMC_AF_INS ? 1u : 2u); }
@@ -135,23 +153,31 @@ __device__ __forceinline__ int spi_first(const smc_spike_indel_variant* __restri
     return lo;
 }
 
-// cnt[i] / cnt[n_aln + i]: the new l_seq / n_cig of a record that is relocated, else 0; bsum[2 b], bsum[2 b + 1]: workgroup b's sums
+// (a record that points beyond the pools, or whose barcode id is none of the run's, is left where it is and counts nowhere)
+__device__ __forceinline__ bool spi_in_run(const smc_dev_aln& a, int lo, const smc_spike_indel_variant* __restrict__ var, int n_var, uint32_t n_bc,
+                                           unsigned long long n_pairs, unsigned long long n_cig_words) {
+    return a.bc_gid < n_bc && lo < n_var && var[lo].pos0 < a.end && (unsigned long long)a.seq_off + a.l_seq <= n_pairs &&
+           (unsigned long long)a.cig_off + a.n_cig <= n_cig_words;
+}
+
+// copy c = blockIdx.y.  cnt_c[i] / cnt_c[n_aln + i]: the new l_seq / n_cig of a record that is relocated, else 0; bsum_c[2 b],
+// bsum_c[2 b + 1]: workgroup b's sums; cnt_c = cnt + 2 c n_aln, bsum_c = bsum + 2 c gridDim.x
 __global__ __launch_bounds__(SPI_BLOCK) void k_spi_count(const smc_dev_aln* __restrict__ aln, uint32_t n_aln, const uint32_t* __restrict__ cig,
                                                          unsigned long long n_pairs, unsigned long long n_cig_words,
                                                          const smc_spike_indel_variant* __restrict__ var, int n_var,
-                                                         const unsigned long long* __restrict__ ident, uint32_t n_bc, unsigned long long seed,
+                                                         const unsigned long long* __restrict__ ident, uint32_t n_bc, SpkCopies C, int own_thr,
                                                          uint32_t* __restrict__ cnt, unsigned long long* __restrict__ bsum) {
     __shared__ uint32_t lds[SPI_BLOCK / 64];
-    const uint32_t i = blockIdx.x * SPI_BLOCK + threadIdx.x;
+    const uint32_t i = blockIdx.x * SPI_BLOCK + threadIdx.x, c = blockIdx.y;
+    cnt += 2ull * c * n_aln; bsum += 2ull * c * gridDim.x;
     uint32_t np = 0, nc = 0;
     if (i < n_aln) {
         const smc_dev_aln a = aln[i];
         const int lo = spi_first(var, n_var, a.pos);
-        // (a record that points beyond the pools is left where it is)
-        if (a.bc_gid < n_bc && lo < n_var && var[lo].pos0 < a.end && (unsigned long long)a.seq_off + a.l_seq <= n_pairs &&
-            (unsigned long long)a.cig_off + a.n_cig <= n_cig_words) {
+        if (spi_in_run(a, lo, var, n_var, n_bc, n_pairs, n_cig_words)) {
             SpiRes R;
-            if (spi_walk<false>(a, cig + a.cig_off, nullptr, var, lo, n_var, nullptr, ident[a.bc_gid], seed, nullptr, nullptr, nullptr, R)) {
+            if (spi_walk<false>(a, cig + a.cig_off, nullptr, var, lo, n_var, nullptr, ident[a.bc_gid], C.seed[c], C.thr[c], own_thr, nullptr, nullptr,
+                                nullptr, 0, R)) {
                 np = R.l_seq; nc = R.n_cig;
             }
         }
@@ -163,12 +189,13 @@ __global__ __launch_bounds__(SPI_BLOCK) void k_spi_count(const smc_dev_aln* __re
     if (threadIdx.x == 0) { bsum[2ull * blockIdx.x] = tp; bsum[2ull * blockIdx.x + 1] = tc; }
 }
 
-// one workgroup: bsum[] -> its exclusive scan, in place; totals[0] / [1] = pairs / CIGAR words the copy needs, the run's own included,
-// totals[2] bit 1 = more than the capacities
+// one workgroup per copy (blockIdx.x = c): bsum_c[] -> its exclusive scan, in place; totals[3 c + 0] / [1] = pairs / CIGAR words the
+// copy needs, the run's own included, totals[3 c + 2] bit 1 = more than the capacities
 __global__ __launch_bounds__(SPI_BLOCK) void k_spi_scan(unsigned long long* __restrict__ bsum, uint32_t n_blocks, unsigned long long n_pairs,
                                                         unsigned long long n_cig_words, unsigned long long cap_pairs, unsigned long long cap_cig,
                                                         unsigned long long* __restrict__ totals) {
     __shared__ unsigned long long lds[SPI_BLOCK / 64];
+    bsum += 2ull * blockIdx.x * n_blocks; totals += 3ull * blockIdx.x;
     unsigned long long carry_p = 0, carry_c = 0;
     for (uint32_t b0 = 0; b0 < n_blocks; b0 += SPI_BLOCK) {
         const uint32_t b = b0 + threadIdx.x;
@@ -187,14 +214,21 @@ __global__ __launch_bounds__(SPI_BLOCK) void k_spi_scan(unsigned long long* __re
 __global__ __launch_bounds__(SPI_BLOCK) void k_spi_scatter(const smc_dev_aln* __restrict__ aln, uint32_t n_aln, const uint32_t* __restrict__ cig,
                                                            const uint8_t* __restrict__ bq, unsigned long long n_pairs, unsigned long long n_cig_words,
                                                            const smc_spike_indel_variant* __restrict__ var, int n_var, const uint8_t* __restrict__ ins,
-                                                           const unsigned long long* __restrict__ ident, uint32_t n_bc, unsigned long long seed,
+                                                           const unsigned long long* __restrict__ ident, uint32_t n_bc, SpkCopies C, int own_thr,
                                                            double mismatch_thr, const int32_t* __restrict__ nm, const int32_t* __restrict__ n_indel,
                                                            const uint32_t* __restrict__ cnt, const unsigned long long* __restrict__ bsum,
-                                                           unsigned long long cap_pairs, unsigned long long cap_cig, smc_dev_aln* __restrict__ aln_out,
-                                                           uint8_t* __restrict__ bq_out, uint32_t* __restrict__ cig_out, int32_t* __restrict__ nm_out,
+                                                           unsigned long long cap_pairs, unsigned long long cap_cig, uint8_t* __restrict__ aln_out_b,
+                                                           unsigned long long aln_stride, uint8_t* __restrict__ bq_out, unsigned long long bq_stride,
+                                                           uint8_t* __restrict__ cig_out_b, unsigned long long cig_stride, int32_t* __restrict__ nm_out,
                                                            int32_t* __restrict__ n_indel_out, uint32_t* __restrict__ stats) {
     __shared__ uint32_t lds[SPI_BLOCK / 64];
-    const uint32_t i = blockIdx.x * SPI_BLOCK + threadIdx.x;
+    const uint32_t i = blockIdx.x * SPI_BLOCK + threadIdx.x, c = blockIdx.y;
+    // copy c: its scratch, its outputs (the pools at byte strides, NM' / n_indel' / statistics one copy behind the other)
+    const unsigned long long seed = C.seed[c], thr_c = C.thr[c];
+    cnt += 2ull * c * n_aln; bsum += 2ull * c * gridDim.x;
+    smc_dev_aln* const aln_out = reinterpret_cast<smc_dev_aln*>(aln_out_b + c * aln_stride);
+    uint32_t* const cig_out = reinterpret_cast<uint32_t*>(cig_out_b + c * cig_stride);
+    bq_out += c * bq_stride; nm_out += (size_t)c * n_aln; n_indel_out += (size_t)c * n_aln; stats += 2ull * c * (unsigned long long)n_var;
     const bool valid = i < n_aln;
     const uint32_t np = valid ? cnt[i] : 0u, nc = valid ? cnt[(size_t)n_aln + i] : 0u;
     uint32_t tp, tc;
@@ -208,8 +242,8 @@ __global__ __launch_bounds__(SPI_BLOCK) void k_spi_scatter(const smc_dev_aln* __
         // (nothing beyond the capacities is written: such a record stays as the run has it, and totals[2] says so)
         if (off_p + np <= cap_pairs && off_c + nc <= cap_cig && off_p + np <= 0xFFFFFFFFull && off_c + nc <= 0xFFFFFFFFull) {
             SpiRes R;
-            spi_walk<true>(a, cig + a.cig_off, bq + 2ull * a.seq_off, var, lo, n_var, ins, ident[a.bc_gid], seed, cig_out + off_c, bq_out + 2ull * off_p,
-                           stats, R);
+            spi_walk<true>(a, cig + a.cig_off, bq + 2ull * a.seq_off, var, lo, n_var, ins, ident[a.bc_gid], seed, thr_c, own_thr, cig_out + off_c,
+                           bq_out + 2ull * off_p, stats, 0, R);
             new_nm += R.nm_inc; new_indel += R.indel_inc;
             a.qalen = (uint16_t)((int)a.qalen + (int)R.l_seq - (int)a.l_seq);
             a.l_seq = (uint16_t)R.l_seq; a.n_cig = (uint16_t)R.n_cig;
@@ -223,7 +257,7 @@ __global__ __launch_bounds__(SPI_BLOCK) void k_spi_scatter(const smc_dev_aln* __
             if (V.kind != SMC_AF_SNV) continue;
             uint32_t u[4];
             smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, (uint32_t)V.pos0 + 1u, (uint32_t)seed, (uint32_t)(seed >> 32), u);
-            if (!((unsigned long long)u[0] < V.thr)) continue;
+            if (!((unsigned long long)u[0] < (own_thr ? V.thr : thr_c))) continue;
             const BpRes r = bp2_resolve(cig + a.cig_off, (int)a.n_cig, a.pos, V.pos0, (int)a.l_seq);
             if (r.isdel || r.indel != 0 || r.qpos < 0 || r.qpos >= (int)a.l_seq) continue;
             const unsigned long long at = (unsigned long long)a.seq_off + (unsigned long long)r.qpos;
@@ -240,4 +274,19 @@ __global__ __launch_bounds__(SPI_BLOCK) void k_spi_scatter(const smc_dev_aln* __
     a.oflag = (uint8_t)((a.oflag & ~SMC_DA_MMOK) | (mm100 <= mismatch_thr ? SMC_DA_MMOK : 0u));
     aln_out[i] = a;
     nm_out[i] = (int32_t)new_nm; n_indel_out[i] = (int32_t)new_indel;
+}
+
+// out[v * n_bc + b] += the records of barcode b that take the listed insertion / deletion v when b is spiked (zeroed before the launch;
+// an SNV's row stays 0).  Bounds as in k_spi_count.
+__global__ __launch_bounds__(SPI_BLOCK) void k_spi_touch(const smc_dev_aln* __restrict__ aln, uint32_t n_aln, const uint32_t* __restrict__ cig,
+                                                         unsigned long long n_pairs, unsigned long long n_cig_words,
+                                                         const smc_spike_indel_variant* __restrict__ var, int n_var, uint32_t n_bc,
+                                                         uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * SPI_BLOCK + threadIdx.x;
+    if (i >= n_aln) return;
+    const smc_dev_aln a = aln[i];
+    const int lo = spi_first(var, n_var, a.pos);
+    if (!spi_in_run(a, lo, var, n_var, n_bc, n_pairs, n_cig_words)) return;
+    SpiRes R;
+    spi_walk<false, true>(a, cig + a.cig_off, nullptr, var, lo, n_var, nullptr, 0ull, 0ull, 0ull, 0, nullptr, nullptr, out + a.bc_gid, (size_t)n_bc, R);
 }

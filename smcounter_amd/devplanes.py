@@ -476,6 +476,10 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
                 if spiked is not None and spiked.cig is not up.cig:
                     # (--spikeIndels: a relocated record has another query layout - its texts come from the copy)
                     allele_key = copy_allele_key(spiked, A, bam.allele_key)
+            elif spiked is not None and spiked.cig is not up.cig:
+                # (--spikeIndelDepth: a cell of such a copy - the kept alignment's index in the copy, then the copy's texts)
+                def allele_key(ai, qpos, indel, orig_index=orig_index, key=copy_allele_key(spiked, A, bam.allele_key)):
+                    return key(int(orig_index()[int(ai)]), qpos, indel)
             bc_name, bc_idents = bam.barcode_name, bam.barcode_idents
             if rule.level == "read":
                 # (the read level renumbers the kept barcodes by first kept appearance: the texts the cap samplers need are the decoder's,
@@ -1324,14 +1328,15 @@ class SpikeSet(object):
     phase sets (tools.spike_variants.PhasedVariants: --spikePhase) every record's `lead` says how far back its set's leader stands;
     lead_pos[k]: the leader's 1-based position of variant k of the list given - counter word 3 of its draw, its own without sets."""
 
-    def __init__(self, variants):
+    def __init__(self, variants, indels: bool = False):
         from .tools import ds_allele_fraction as af
         from .tools import spike_variants as sv
         self.lead_pos = sv.leaders(variants)
         self.variants = list(variants)
         # (--spikeIndels) a list that holds an insertion or a deletion: the records are smc_spike_indels' (no phase sets beside them),
         # ins[chrom] the pool of inserted letters
-        self.indels = any(v.kind != af.SNV for v in self.variants)
+        # (--spikeIndelReps, --spikeIndelDepth: `indels` - smc_spike_indels' records whatever the list holds)
+        self.indels = bool(indels) or any(v.kind != af.SNV for v in self.variants)
         self.by_chrom, self.ins = {}, {}
         for c in sorted({v.chrom for v in self.variants}):
             order = sorted((k for k, v in enumerate(self.variants) if v.chrom == c), key=lambda k: self.variants[k].pos)
@@ -1428,6 +1433,38 @@ def spike_indel_caps(A, var):
     hit = last > first
     return (n_pairs + int((aln["l_seq"].astype(np.int64) + s[last] - s[first])[hit].sum()),
             n_cig + int((aln["n_cig"].astype(np.int64) + 2 * (last - first))[hit].sum()))
+
+
+def spike_indel_limits(A, var):
+    """The first alignment of run `A` (host arrays) at which the 16-bit limits of smc_spike_indels' walk COULD bind - it spans k listed
+    insertions / deletions with s inserted letters in all and n_cig + 2 k > 65535 or l_seq + s > 65535 -, or None.  Without such a
+    record whether a record takes a listed variant depends on no other variant's draw (--spikeIndelReps counts on that)."""
+    aln = A["aln"]
+    indel = var[var["kind"] != 0]
+    if not len(indel) or not len(aln):
+        return None
+    first, last = np.searchsorted(indel["pos0"], aln["pos"], "left"), np.searchsorted(indel["pos0"], aln["end"], "left")
+    s = np.concatenate([[0], np.cumsum(np.where(indel["kind"] == 1, indel["len"], 0).astype(np.int64))])
+    bad = np.flatnonzero((aln["n_cig"].astype(np.int64) + 2 * (last - first) > 65535) | (aln["l_seq"].astype(np.int64) + s[last] - s[first] > 65535))
+    return int(bad[0]) if len(bad) else None
+
+
+def spike_indel_touch(eng, up: RunOnDevice, A, var: np.ndarray) -> np.ndarray:
+    """smc_spike_indel_touch over the run `up` (A: its host arrays) -> uint32 [n_var, n_bc]: per record of `var` and run-wide barcode
+    id the records that take the insertion / deletion when the barcode is spiked (0 throughout for an SNV)."""
+    from .engine import DevBuf
+    n_var, n_bc = len(var), int(A["n_bc"])
+    if not n_var or not n_bc:
+        return np.zeros((n_var, n_bc), np.uint32)
+    var = np.ascontiguousarray(var, abi.SPIKE_INDEL_VARIANT_DTYPE)
+    d_var, d_out = DevBuf(eng, var.nbytes + 256).upload(var.view(np.uint8).reshape(-1)), DevBuf(eng, 4 * n_var * n_bc + 256)
+    try:
+        _lib.check(eng.L.smc_spike_indel_touch(eng.ctx, up.aln.data_ptr(), up.n_aln, up.cig.data_ptr(), len(A["cig"]), len(A["bq"]) // 2,
+                                               d_var.data_ptr(), var.ctypes.data, n_var, n_bc, d_out.data_ptr(), ctypes.c_void_p(0)),
+                   "smc_spike_indel_touch")
+        return d_out.download(np.uint32, n_var * n_bc).reshape(n_var, n_bc)      # (the default stream: behind the kernel)
+    finally:
+        d_var.free(); d_out.free()
 
 
 def spike_indel_run(eng, up: RunOnDevice, A, var: np.ndarray, ins: np.ndarray, idents, seed: int, mismatch_thr: float, nm, n_indel,
@@ -1552,7 +1589,7 @@ def copy_allele_key(spiked: RunOnDevice, A, decoder_key):
 
 
 def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng, nthreads: int = 0, max_reads: int = 128_000_000,
-                keep: dict = None, keep_bytes: int = None, depth: dict = None, phase: dict = None):
+                keep: dict = None, keep_bytes: int = None, depth: dict = None, phase: dict = None, indel_counters: bool = False):
     """DsRules of --spikeAF, one per target, and the pre-pass: only the runs around the listed loci are decoded (as ds_af_sets groups
     them); smc_allele_carriers gives N and V0 of every variant, then per target smc_spike_alleles writes the spiked copy and
     smc_allele_carriers on it gives V1.  The kernel's statistics are checked against the host's restatement of the draws: the records
@@ -1575,12 +1612,20 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     "counts", per set and target dict(N_ALL, V0_ALL, S_ALL, V1_ALL) from one smc_spike_phase_counts call with this seed, and with
     `depth` "depth_counts", the same per cell from a second call.  (N_ALL, V0_ALL, V1_ALL) of every target is also counted a second
     way - the AND over the members of smc_allele_carriers' cover and carrier bits, on the run and on the spiked copy of that target
-    - and a difference raises RuntimeError."""
+    - and a difference raises RuntimeError.
+    `indel_counters` (--spikeIndelReps, --spikeIndelDepth): the spike-ins are smc_spike_indels' whatever the list holds, and the
+    counters are FOUR per covering barcode, uint32 [covering barcodes, 4] = (reads, alt0, alt1, touch): alt1 the `alt` counter on the
+    copy spiked at threshold 2^32 - for an insertion / a deletion alt0 plus the eligible records whose anchor letter is REF's -, touch
+    the records the rewrite changes when the barcode is hit - alt1 for an SNV, smc_spike_indel_touch's for an insertion / a deletion.
+    The cells' counts then come from smc_spike_indel_counts.  ValueError, before anything is spiked: a run with a record at which the
+    16-bit limits of the rewrite could bind (spike_indel_limits) - the counters would depend on the other variants' draws."""
     from .tools import ds_allele_fraction as af
     from .tools import spike_variants as sv
     af.unique_idents(bamio.placed_barcodes(path), path)
     nthreads = nthreads or bamio.host_threads()
-    spikes = SpikeSet(variants)
+    spikes = SpikeSet(variants, indels=indel_counters)
+    if indel_counters and phase is not None:
+        raise ValueError("--spikeIndelReps / --spikeIndelDepth: phase sets of indel spike-ins are not built")
     P = params_list[0]
     rows = [[None] * len(variants) for _ in targets]
     psets = list(phase["sets"]) if phase is not None else []
@@ -1612,6 +1657,13 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                     raise bamio.BamError("--spikeAF: the run %s:%d-%d of the pre-pass could not be decoded" % (v0.chrom, lo + 1, hi))
                 group = [k for k in order[i:j + 1] if variants[k].pos - 1 - lo < nl]
                 var, ins = af_run_variants([variants[k] for k in group], v0.chrom, lo, fasta)
+                if indel_counters:
+                    bad = spike_indel_limits(A, spikes.chrom_variants(v0.chrom, 0.5)[0])
+                    if bad is not None:
+                        a = A["aln"][bad]
+                        raise ValueError("--spikeIndelReps / --spikeIndelDepth: the record at %s:%d (l_seq %d, %d CIGAR operations) spans listed "
+                                         "indels that could take l_seq or the CIGAR beyond 65535: whether it takes one would depend on the "
+                                         "draws of the others" % (v0.chrom, int(a["pos"]) + 1, int(a["l_seq"]), int(a["n_cig"])))
                 idents = dec.barcode_idents(A["n_bc"])
                 nm, n_indel = dec.run_mismatches(len(A["aln"]))
                 run_ref = fasta.fetch(v0.chrom, lo, lo + nl).upper()
@@ -1663,18 +1715,22 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                                           V1=int(car1[r].sum()))
                 if want_counters:
                     # (`single`: one copy with every barcode spiked at every listed position - thr 2^32 - then the `alt` counters)
-                    svar, _ = spikes.chrom_variants(v0.chrom, 0.5)
+                    svar, sorder = spikes.chrom_variants(v0.chrom, 0.5)
                     svar["thr"] = 1 << 32
-                    spiked, _ = spike_run(eng, up, A, svar, idents, seed, P.mismatchThr, nm, n_indel)
+                    spiked, _ = spike_copy(eng, up, A, spikes, v0.chrom, svar, idents, seed, P.mismatchThr, nm, n_indel)
                     try:
                         _, _, cnt_all = allele_carriers_run(eng, spiked, A, lo, var, ins, counts=True)
                     finally:
-                        spiked.aln.free(); spiked.bq.free()
+                        free_spiked(spiked, up)
+                    touch = spike_indel_touch(eng, up, A, svar) if indel_counters else None
                     for r, k in enumerate(group):
                         c = cov[r][:len(idents)]
                         covers[k] = idents[c]
-                        counters[k] = np.stack([cnt0[r, :len(idents), 0][c], cnt0[r, :len(idents), 1][c],
-                                                cnt_all[r, :len(idents), 1][c]], axis=1).astype(np.uint32)
+                        cols = [cnt0[r, :len(idents), 0][c], cnt0[r, :len(idents), 1][c], cnt_all[r, :len(idents), 1][c]]
+                        if indel_counters:
+                            # (what the rewrite changes: an SNV's single-letter reads - all of which then show ALT -, an indel's eligible records)
+                            cols.append(cols[2] if variants[k].kind == af.SNV else touch[sorder.index(k), :len(idents)][c])
+                        counters[k] = np.stack(cols, axis=1).astype(np.uint32)
                 if keep is not None:
                     size = sum(int(A[x].nbytes) for x in ("aln", "cig", "bq", "loc"))
                     held = size + sum(r.nbytes for r in keep["runs"]) <= (AF_KEEP_BYTES if keep_bytes is None else keep_bytes)
@@ -1697,8 +1753,9 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     rules = [DsRule(1.0, Pt, seed=int(seed), af=float(t), spike=spikes) for t, Pt in zip(targets, params_list)]
     if depth is not None:
         try:
-            got = spike_depth_counts(eng, spikes.lead_pos, covers, counters, [int(seed) & 0xFFFFFFFFFFFFFFFF],
-                                     [sv.threshold(t) for t in targets], [frac_threshold(f) for f in fracs])[:, 0]
+            got = (spike_indel_counts if indel_counters else spike_depth_counts)(
+                eng, spikes.lead_pos, covers, counters, [int(seed) & 0xFFFFFFFFFFFFFFFF], [sv.threshold(t) for t in targets],
+                [frac_threshold(f) for f in fracs])[:, 0]
             for (k, t, f), mine in second.items():
                 if [int(got[k, t, f, c]) for c in (0, 1, 4)] != mine:
                     v = variants[k]
@@ -2027,13 +2084,15 @@ def _spike_counts_call(eng, name: str, arrays, shape, call) -> np.ndarray:
     return out.reshape(shape)
 
 
-def _spike_flat_covers(who: str, positions, covers, counters):
-    """The variants' covers as the counts entries take them -> (identities, counters [n, 3], offsets [V + 1], positions)."""
+def _spike_flat_covers(who: str, positions, covers, counters, width: int = 3):
+    """The variants' covers as the counts entries take them -> (identities, counters [n, width], offsets [V + 1], positions)."""
     n_var = len(covers)
     off = np.zeros(n_var + 1, np.uint32)
     off[1:] = np.cumsum([len(c) for c in covers])
     ident = np.concatenate([np.asarray(c, np.uint64) for c in covers]) if n_var else np.zeros(0, np.uint64)
-    cnt = np.concatenate([np.asarray(c, np.uint32).reshape(-1, 3) for c in counters]) if n_var else np.zeros((0, 3), np.uint32)
+    if any(np.asarray(c).size != width * len(x) for c, x in zip(counters, covers)):
+        raise ValueError("%s: %d counters per covering barcode expected" % (who, width))
+    cnt = np.concatenate([np.asarray(c, np.uint32).reshape(-1, width) for c in counters]) if n_var else np.zeros((0, width), np.uint32)
     if len(cnt) != len(ident):
         raise ValueError("%s: %d covering barcodes, counters of %d" % (who, len(ident), len(cnt)))
     return ident, cnt, off, np.array([int(p) & 0xFFFFFFFF for p in positions], np.uint32)
@@ -2061,6 +2120,20 @@ def spike_depth_counts(eng, positions, covers, counters, seeds, thresholds, dept
         eng, "smc_spike_depth_counts", [ident, cnt, off, pos, seeds], (len(covers), len(seeds), len(thr), len(dthr), 5),
         lambda d, d_out: eng.L.smc_spike_depth_counts(eng.ctx, d[0], d[1], d[2], off.ctypes.data, d[3], len(covers), d[4], len(seeds),
                                                       thr.ctypes.data, len(thr), dthr.ctypes.data, len(dthr), d_out, ctypes.c_void_p(0)))
+
+
+def spike_indel_counts(eng, positions, covers, counters, seeds, thresholds, depth_thresholds=None) -> np.ndarray:
+    """smc_spike_indel_counts -> spike_rep_counts' uint32 [V, R, T, 3] (`depth_thresholds` None) or spike_depth_counts' [V, R, T, F, 5]
+    from counters[v]: uint32 [len(covers[v]), 4] = (reads, alt0, alt1, touch).  The other arguments are theirs."""
+    ident, cnt, off, pos = _spike_flat_covers("spike_indel_counts", positions, covers, counters, 4)
+    seeds, thr = np.ascontiguousarray(seeds, np.uint64), np.ascontiguousarray(thresholds, np.uint64)
+    dthr = None if depth_thresholds is None else np.ascontiguousarray(depth_thresholds, np.uint64)
+    shape = (len(covers), len(seeds), len(thr)) + ((3,) if dthr is None else (len(dthr), 5))
+    return _spike_counts_call(
+        eng, "smc_spike_indel_counts", [ident, cnt, off, pos, seeds], shape,
+        lambda d, d_out: eng.L.smc_spike_indel_counts(eng.ctx, d[0], d[1], d[2], off.ctypes.data, d[3], len(covers), d[4], len(seeds),
+                                                      thr.ctypes.data, len(thr), None if dthr is None else dthr.ctypes.data,
+                                                      0 if dthr is None else len(dthr), d_out, ctypes.c_void_p(0)))
 
 
 def spike_joint(sets, covers, counters):
@@ -2145,23 +2218,119 @@ def spike_run_copies(eng, up: RunOnDevice, A, var: np.ndarray, idents, seeds, th
     return d_aln, d_bq, (sa, sb), stats
 
 
+class _BufView(object):
+    """A stretch of a DevBuf that reads like a buffer of its own (data_ptr, download); the owner frees the allocation."""
+
+    def __init__(self, buf, offset_bytes: int):
+        self.buf, self.off, self.word_bits = buf, int(offset_bytes), 32
+
+    def data_ptr(self) -> int:
+        return self.buf.data_ptr() + self.off
+
+    def download(self, dtype, count: int, offset_bytes: int = 0):
+        return self.buf.download(dtype, count, self.off + offset_bytes)
+
+    def free(self):
+        pass
+
+
+def spike_indel_copy_strides(n_aln: int, cap_pairs: int, cap_cig: int):
+    """The byte strides between the copies of one smc_spike_indels_reps call: a copy's records, its pair pool (128 bytes more, as
+    smc_build_planes wants behind any pair pool) and its CIGAR pool at their capacities, each rounded up to 256 bytes."""
+    return (36 * max(1, n_aln) + 255) & ~255, (2 * max(1, cap_pairs) + 128 + 255) & ~255, (4 * max(1, cap_cig) + 255) & ~255
+
+
+def spike_indel_run_copies(eng, up: RunOnDevice, A, var: np.ndarray, ins: np.ndarray, idents, seeds, thresholds, mismatch_thr: float, nm, n_indel,
+                           caps=None, strides=None, fill=None, mism: bool = False):
+    """smc_spike_indels_reps over the run `up`: copy c with seeds[c] and every variant at thresholds[c] -> dict(aln, bq, cig: three
+    DevBufs, copy c at c x its stride - free all three -, strides: (records, pair pool, CIGAR pool) in bytes, caps, stats: uint32
+    [copies, n_var, 2], totals: uint64 [copies, 3], nm / n_indel: int32 [copies, n_aln] with `mism`).  `caps`: (cap_pairs, cap_cig),
+    spike_indel_caps' bounds without it; `strides`: other than spike_indel_copy_strides'; `fill`: a byte the three outputs are
+    filled with first (tests).  One download of all totals; SmcError when a copy did not fit spike_indel_caps' bounds."""
+    from .engine import DevBuf
+    n, n_pairs, n_cw, n_var, n_bc, B = up.n_aln, len(A["bq"]) // 2, len(A["cig"]), len(var), int(A["n_bc"]), len(seeds)
+    var = np.ascontiguousarray(var, abi.SPIKE_INDEL_VARIANT_DTYPE)
+    cap_pairs, cap_cig = caps if caps is not None else spike_indel_caps(A, var)
+    sa, sb, sc = strides or spike_indel_copy_strides(n, cap_pairs, cap_cig)
+    seeds, thr = np.ascontiguousarray(seeds, np.uint64), np.ascontiguousarray(thresholds, np.uint64)
+    up8 = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
+    idents = np.ascontiguousarray(idents, np.uint64)[:n_bc]
+    ins = np.ascontiguousarray(ins, np.uint8)
+    nB = max(1, B)
+    tmp = [up8(var), up8(idents), up8(np.ascontiguousarray(nm, np.int32)), up8(np.ascontiguousarray(n_indel, np.int32)), up8(ins),
+           DevBuf(eng, 8 * max(1, n_var) * nB + 256), DevBuf(eng, 24 * nB + 256), DevBuf(eng, 4 * max(1, n) * nB + 256),
+           DevBuf(eng, 4 * max(1, n) * nB + 256)]
+    out = [DevBuf(eng, sa * nB + 256), DevBuf(eng, sb * nB + 256), DevBuf(eng, sc * nB + 256)]
+    try:
+        if len(nm) < n or len(n_indel) < n or len(thr) != B:
+            raise ValueError("spike_indel_run_copies: %d alignments, NM of %d; %d seeds, %d thresholds" % (n, len(nm), B, len(thr)))
+        if fill is not None:
+            for b, st in zip(out, (sa, sb, sc)):
+                b.upload(np.full(st * nB, fill, np.uint8))
+        _lib.check(eng.L.smc_spike_indels_reps(eng.ctx, up.aln.data_ptr(), n, up.cig.data_ptr(), n_cw, up.bq.data_ptr(), n_pairs, tmp[0].data_ptr(),
+                                               var.ctypes.data, n_var, tmp[4].data_ptr(), len(ins), tmp[1].data_ptr(), len(idents),
+                                               seeds.ctypes.data, thr.ctypes.data, B, float(mismatch_thr), tmp[2].data_ptr(), tmp[3].data_ptr(),
+                                               cap_pairs, cap_cig, out[0].data_ptr(), sa, out[1].data_ptr(), sb, out[2].data_ptr(), sc,
+                                               tmp[7].data_ptr(), tmp[8].data_ptr(), tmp[5].data_ptr(), tmp[6].data_ptr(), ctypes.c_void_p(0)),
+                   "smc_spike_indels_reps")
+        totals = tmp[6].download(np.uint64, 3 * B).reshape(B, 3)                     # (the default stream: behind the kernels)
+        stats = tmp[5].download(np.uint32, 2 * n_var * B).reshape(B, n_var, 2) if n_var * B else np.zeros((B, 0, 2), np.uint32)
+        nm_out, n_indel_out = (tmp[7].download(np.int32, n * B).reshape(B, n), tmp[8].download(np.int32, n * B).reshape(B, n)) if mism and n \
+            else (None, None)
+        if caps is None and totals[:, 2].any():
+            c = int(np.flatnonzero(totals[:, 2])[0])
+            raise _lib.SmcError("smc_spike_indels_reps: copy %d needs %d pairs / %d CIGAR words, more than the bounds %d / %d" %
+                                (c, int(totals[c, 0]), int(totals[c, 1]), cap_pairs, cap_cig))
+    except BaseException:
+        for b in out:
+            b.free()
+        raise
+    finally:
+        for b in tmp:
+            b.free()
+    return dict(aln=out[0], bq=out[1], cig=out[2], strides=(sa, sb, sc), caps=(cap_pairs, cap_cig), stats=stats, totals=totals, nm=nm_out,
+                n_indel=n_indel_out)
+
+
 def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed, bits,
-                    cells=()):
+                    cells=(), indel: dict = None):
     """`len(part_seeds)` spiked copies of a kept run at one target from one smc_spike_alleles_reps call, each built behind the other
     into one device batch (as _af_rep_call appends its selections) and the batch called with one plan -> (per copy the listed loci's
     raw rows, in the order of run.group), or NARROW.  var_at[g]: where variant run.group[g] stands in `svar`; want_reads[c][g]: the
     counts call's READS of that copy and variant - the kernel's statistics must equal it.
     `cells` (--spikeDepth: (fraction, params) of the target's cells): every copy is also selected at each fraction with its own seed
     (select_run's philox rule) and built; a cell's selections share one device batch and one plan of their own, called with that
-    cell's params -> (the copies' rows, per cell the same), or NARROW."""
+    cell's params -> (the copies' rows, per cell the same), or NARROW.
+    `indel` (--spikeIndelReps: dict(ins: the chromosome's pool of inserted letters, want: per copy and variant of run.group the counts
+    call's (N, V1), want_cells: per cell the same (N', V1'))): the copies come from one smc_spike_indels_reps call, each with records,
+    CIGAR pool and pair pool of its own; a relocated record's allele texts come from the copy (copy_allele_key); and beside READS every
+    copy's N and V1 - smc_allele_carriers on the copy, on its selection for a cell - must equal the counts call's."""
     from . import vc
     A, up, lo, nl, chrom = run.A, run.up, run.lo, run.nl, run.chrom
     B = len(part_seeds)
     ns_full = int(A["n_slots"])
     cap = B * (ns_full + nl) + ns_full + nl + 64
-    d_aln, d_bq, (sa, sb), stats = spike_run_copies(eng, up, A, svar, run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
-    copies = [RunOnDevice(d_aln.view(c * sa), up.cig, d_bq.view(c * sb), up.loc, up.ref, up.n_aln, up.loc_host) for c in range(B)]
+    if indel is None:
+        d_aln, d_bq, (sa, sb), stats = spike_run_copies(eng, up, A, svar, run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
+        copies = [RunOnDevice(d_aln.view(c * sa), up.cig, d_bq.view(c * sb), up.loc, up.ref, up.n_aln, up.loc_host) for c in range(B)]
+        owned = [d_aln, d_bq]
+    else:
+        made = spike_indel_run_copies(eng, up, A, svar, indel["ins"], run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
+        (sa, sb, sc), stats, owned = made["strides"], made["stats"], [made["aln"], made["bq"], made["cig"]]
+        copies = [RunOnDevice(_BufView(made["aln"], c * sa), _BufView(made["cig"], c * sc), _BufView(made["bq"], c * sb), up.loc, up.ref, up.n_aln,
+                              up.loc_host, pairs_used=int(made["totals"][c, 0])) for c in range(B)]
+        af_var, af_ins = af_run_variants([variants[k] for k in run.group], chrom, lo, fasta)
     flag = "--spikeDepth" if cells else "--spikeReps"
+
+    def check_carriers(c, sel, counts, want, what):
+        """(N, V1) of every variant of the run on copy c (or its selection) by smc_allele_carriers against the counts call's."""
+        cov, car, _ = allele_carriers_run(eng, sel, counts, lo, af_var, af_ins)
+        for g, k in enumerate(run.group):
+            mine = (int(cov[g].sum()), int(car[g].sum()))
+            if mine != tuple(int(x) for x in want[g]):
+                v = variants[k]
+                raise RuntimeError("--spikeIndelReps: seed %d at %s:%d%s: the copy holds (N, V1) = %r, the counts call says %r" %
+                                   (int(part_seeds[c]), v.chrom, v.pos, what, mine, tuple(int(x) for x in want[g])))
 
     def batch_rows(Pb, frac):
         """The B copies (`frac` None) or their selections at `frac`, built into one batch and called with one plan at params `Pb`."""
@@ -2173,6 +2342,9 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
                 if frac is None:
                     # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch)
                     sel, counts, d_orig, allele_key = copies[c], A, None, run.bam.allele_key
+                    if indel is not None:
+                        allele_key = copy_allele_key(copies[c], A, run.bam.allele_key)
+                        check_carriers(c, sel, counts, indel["want"][c], "")
                 else:
                     sel, counts, d_orig = select_run(eng, copies[c], A, lo, idents=run.idents, frac=frac, seed=int(part_seeds[c]))
                     got = {}
@@ -2182,6 +2354,16 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
                         if "orig" not in got:
                             got["orig"] = d_orig.download(np.uint32, kept)
                         return run.bam.allele_key(int(got["orig"][int(ai)]), qpos, indel)
+                    if indel is not None:
+                        def allele_key(ai, qpos, indel_len, d_orig=d_orig, kept=sel.n_aln, got=got, key=copy_allele_key(copies[c], A, run.bam.allele_key)):
+                            if "orig" not in got:
+                                got["orig"] = d_orig.download(np.uint32, kept)
+                            return key(int(got["orig"][int(ai)]), qpos, indel_len)
+                        try:
+                            check_carriers(c, sel, counts, indel["want_cells"][cell_at[frac]][c], " x fraction %g" % frac)
+                        except BaseException:
+                            sel.free(shared=False); d_orig.free()
+                            raise
                 try:
                     done = build_run(counts, eng.L, eng, cp, Pb, chrom, lo, fasta, run.run_ref, [d.words] + d.planes, d.uaux, d.slots,
                                      d.slots + n_loc, cap, max_depth, allele_key, run.bam.barcode_name, sampler=sampler,
@@ -2214,6 +2396,7 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
             return [list(text[b * g:(b + 1) * g]) for b in range(B)]
         finally:
             d.free()
+    cell_at = {frac: f for f, (frac, _) in enumerate(cells)}
     try:
         for c in range(B):
             for g, k in enumerate(run.group):
@@ -2231,7 +2414,8 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
                 return NARROW
         return full, of_cell
     finally:
-        d_aln.free(); d_bq.free()
+        for b in owned:
+            b.free()
 
 
 def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int, n_reps: int, eng, keep: dict, sampler: str = "reference",
@@ -2265,12 +2449,14 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
     max_depth = eng.L.smc_build_max_depth()
     try:
         t0 = time.perf_counter()
-        counts = spike_rep_counts(eng, spikes.lead_pos, keep["covers"], keep["counters"], seeds, thr)
+        # (--spikeIndelReps: four counters per covering barcode - the stride-4 entry)
+        four = bool(keep["counters"]) and np.asarray(keep["counters"][0]).ndim == 2 and np.asarray(keep["counters"][0]).shape[1] == 4
+        counts = (spike_indel_counts if four else spike_rep_counts)(eng, spikes.lead_pos, keep["covers"], keep["counters"], seeds, thr)
         depth_counts = None
         F = len(depth["fracs"]) if depth is not None else 0
         if depth is not None:
-            depth_counts = spike_depth_counts(eng, spikes.lead_pos, keep["covers"], keep["counters"], seeds, thr,
-                                              [frac_threshold(f) for f in depth["fracs"]])
+            depth_counts = (spike_indel_counts if four else spike_depth_counts)(eng, spikes.lead_pos, keep["covers"], keep["counters"], seeds, thr,
+                                                                                [frac_threshold(f) for f in depth["fracs"]])
         phase_counts = phase_depth_counts = None
         if phase is not None and phase.get("joint"):
             lead = [spikes.lead_pos[s.members[0]] for s in phase["sets"]]
@@ -2294,8 +2480,12 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
                 times["decode again"] += time.perf_counter() - t0
             svar, sorder = spikes.chrom_variants(run.chrom, targets[0])
             var_at = [sorder.index(k) for k in run.group]
-            sa, sb = spike_copy_strides(run.up.n_aln, len(run.A["bq"]) // 2)
-            room = max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // (sa + sb), AF_REP_BATCH_SLOTS // max(1, int(run.A["n_slots"]) + run.nl)))
+            if four:
+                # (a copy: records, both pools at their capacities, and the call's scratch of 8 bytes per alignment)
+                per_copy = sum(spike_indel_copy_strides(run.up.n_aln, *spike_indel_caps(run.A, svar))) + 8 * run.up.n_aln
+            else:
+                per_copy = sum(spike_copy_strides(run.up.n_aln, len(run.A["bq"]) // 2))
+            room = max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per_copy, AF_REP_BATCH_SLOTS // max(1, int(run.A["n_slots"]) + run.nl)))
             t0 = time.perf_counter()
             for t in range(T):
                 P = params_list[t]
@@ -2305,10 +2495,16 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
                     want = [[int(counts[k, j, t, 1]) for k in run.group] for j in js]
                     bits = 16 if (eng.word_bits == 16 and 0 <= P.minBQ <= 63) else 32
                     args = (eng, run, svar, var_at, [seeds[j] for j in js], thr[t], want, P, fasta, variants, max_depth, sampler, sampler_seed)
-                    out = _spike_rep_call(*args, bits, cells)
+                    indel = None
+                    if four:
+                        n_cov = [len(keep["covers"][k]) for k in run.group]
+                        indel = dict(ins=spikes.ins[run.chrom], want=[[(n, int(counts[k, j, t, 2])) for k, n in zip(run.group, n_cov)] for j in js],
+                                     want_cells=[[[(int(depth_counts[k, j, t, f, 0]), int(depth_counts[k, j, t, f, 4])) for k in run.group]
+                                                  for j in js] for f in range(F)])
+                    out = _spike_rep_call(*args, bits, cells, indel)
                     if out == NARROW:
                         eng.word_bits = 32
-                        out = _spike_rep_call(*args, 32, cells)
+                        out = _spike_rep_call(*args, 32, cells, indel)
                         times["rewrites"] += 1
                     full, of_cell = out if cells else (out, [])
                     for c, part in [(t, full)] + [(T + t * F + f, part) for f, part in enumerate(of_cell)]:

@@ -15,6 +15,9 @@ all of it was called.
 --spikeIndels: the variants file may hold insertions and deletions too (indels; tools.spike_variants --indels is the rule); the
 outputs and the detection page are --spikeAF's, V0 and V1 by the variant's INS / DEL key.
 
+--spikeIndelReps / --spikeIndelDepth: --spikeReps and --spikeDepth on the --spikeIndels spike-in (indel_flags); the pages are those
+of --spikeReps / --spikeDepth, from the same writers.
+
 The semantics are tools/spike_variants.py's (DESIGN.md "--spikeAF"); the rewrite on the GPU is csrc/k_spike.inc (smc_spike_alleles),
 the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the main pass are devplanes.spike_rules / spike_run.
 """
@@ -66,13 +69,13 @@ def targets(args):
     return [(t, d, "%s.spikeAF%g" % (args.outPrefix, t)) for t, d in zip(ts, depths)]
 
 
-def variants(args, loc_list, fasta):
+def variants(args, loc_list, fasta, indels: bool = False):
     """The variants of --spikeVariants, checked: the file's refusals (tools.spike_variants.parse_variants: SNVs only, with
-    --spikePhase MNV lines and PS= sets as well, with --spikeIndels insertions and deletions whose footprints do not overlap), REF
-    the genome's letters, every variant a locus of --bedTarget."""
+    --spikePhase MNV lines and PS= sets as well, with --spikeIndels - or `indels`: --spikeIndelReps, --spikeIndelDepth - insertions and
+    deletions whose footprints do not overlap), REF the genome's letters, every variant a locus of --bedTarget."""
     try:
         out = sv.parse_variants(args.spikeVariants, "--spikeVariants", phased=bool(getattr(args, "spikePhase", False)),
-                                indels=bool(getattr(args, "spikeIndels", False)))
+                                indels=bool(indels) or bool(getattr(args, "spikeIndels", False)))
         sv.check_reference(out, fasta, "--spikeVariants")
         loci = set((c, int(p)) for c, p in loc_list)
         for v in out:
@@ -123,6 +126,33 @@ def indels(args, spike_targets) -> bool:
     return True
 
 
+# ---- --spikeIndelReps, --spikeIndelDepth
+def indel_flags(args, spike_targets):
+    """--spikeIndelReps / --spikeIndelDepth -> (R or None, the fractions' text or None).  SystemExit: beside --spikeIndels, --spikeReps,
+    --spikeDepth (the flag that covers it is named) or --spikePhase; --spikeIndelReps without --spikeAF and --spikeVariants,
+    --spikeIndelDepth without --spikeAF; R no integer or outside REPS_MIN .. REPS_MAX.  (The fractions are depth_cells' to check.)"""
+    r, text = getattr(args, "spikeIndelReps", None), getattr(args, "spikeIndelDepth", None)
+    r, text = (None if r in (None, "") else r), (None if text in (None, "") else text)
+    if r is None and text is None:
+        return None, None
+    mine = "--spikeIndelReps" if r is not None else "--spikeIndelDepth"
+    if getattr(args, "spikeIndels", False):
+        raise SystemExit("%s implies the rules of --spikeIndels: leave --spikeIndels out" % mine)
+    if getattr(args, "spikeReps", None) not in (None, ""):
+        raise SystemExit("%s cannot be combined with --spikeReps in one run: --spikeIndelReps R replicates the spike-ins itself" % mine)
+    if getattr(args, "spikeDepth", None) not in (None, ""):
+        raise SystemExit("%s cannot be combined with --spikeDepth in one run: --spikeIndelDepth takes the barcode fractions" % mine)
+    if getattr(args, "spikePhase", False):
+        raise SystemExit("%s cannot be combined with --spikePhase in one run (phase sets of indel spike-ins are not built)" % mine)
+    if not spike_targets:
+        raise SystemExit("--spikeIndelReps replicates the spike-ins of --spikeAF, insertions and deletions among them: it needs --spikeAF "
+                         "and --spikeVariants" if r is not None else
+                         "--spikeIndelDepth thins the barcodes of the --spikeAF spike-ins, insertions and deletions among them: it needs --spikeAF")
+    if r is not None:
+        r = reps(args, spike_targets, "spikeIndelReps")
+    return r, text
+
+
 # ---- --spikeReps
 REPS_MIN, REPS_MAX = dsaf.REPS_MIN, dsaf.REPS_MAX
 REPLICATES_HEADER = DETECTION_HEADER[:5] + ("REP", "SEED") + DETECTION_HEADER[5:]
@@ -131,21 +161,22 @@ SENSITIVITY_HEADER = ("CHROM", "POS", "REF", "ALT", "TARGET", "REPS", "CALLED", 
 CURVE_HEADER = ("CHROM", "POS", "REF", "ALT", "N")
 
 
-def reps(args, spike_targets):
-    """--spikeReps -> R, or None without the flag.  SystemExit: without --spikeAF, R no integer or outside REPS_MIN .. REPS_MAX."""
-    r = getattr(args, "spikeReps", None)
+def reps(args, spike_targets, flag: str = "spikeReps"):
+    """--spikeReps -> R, or None without the flag.  SystemExit: without --spikeAF, R no integer or outside REPS_MIN .. REPS_MAX.
+    `flag`: the flag read and named ("spikeIndelReps")."""
+    r = getattr(args, flag, None)
     if r in (None, ""):
         return None
     if not spike_targets:
-        raise SystemExit("--spikeReps replicates the spike-ins of --spikeAF: it needs --spikeAF")
+        raise SystemExit("--%s replicates the spike-ins of --spikeAF: it needs --spikeAF" % flag)
     try:
         if isinstance(r, float) and r != int(r):
             raise ValueError(r)
         r = int(r)
     except ValueError:
-        raise SystemExit("--spikeReps: an integer in %d .. %d expected, got %r" % (REPS_MIN, REPS_MAX, r))
+        raise SystemExit("--%s: an integer in %d .. %d expected, got %r" % (flag, REPS_MIN, REPS_MAX, r))
     if not (REPS_MIN <= r <= REPS_MAX):
-        raise SystemExit("--spikeReps: the number of replicates must lie in %d .. %d, got %d" % (REPS_MIN, REPS_MAX, r))
+        raise SystemExit("--%s: the number of replicates must lie in %d .. %d, got %d" % (flag, REPS_MIN, REPS_MAX, r))
     return r
 
 
@@ -234,28 +265,28 @@ DEPTH_SENSITIVITY_HEADER = SENSITIVITY_HEADER[:5] + ("FRACTION", "MTDEPTH") + SE
 DEPTH_CURVE_HEADER = dsaf.CURVE_HEADER
 
 
-def depth_cells(args, spike_targets):
+def depth_cells(args, spike_targets, flag: str = "spikeDepth"):
     """--spikeDepth -> (fractions, [(target index, t, f, mtDepth of the cell, output prefix)] for every --spikeAF target t and every
     fraction f, targets outer), or (None, []) without the flag.  A cell's mtDepth is what --dsMT f gets from its target's mtDepth.
     SystemExit: without --spikeAF, text that is no list of numbers, a fraction outside (0, 1] or listed twice, beyond MAX_CELLS
-    cells."""
+    cells.  `flag`: the flag read and named ("spikeIndelDepth")."""
     from .py2compat import py2_round
-    text = getattr(args, "spikeDepth", None)
+    text = getattr(args, flag, None)
     if text in (None, ""):
         return None, []
     if not spike_targets:
-        raise SystemExit("--spikeDepth thins the barcodes of the --spikeAF spike-ins: it needs --spikeAF")
+        raise SystemExit("--%s thins the barcodes of the --spikeAF spike-ins: it needs --spikeAF" % flag)
     try:
         fr = [float(x) for x in str(text).split(",") if x.strip()]
     except ValueError:
-        raise SystemExit("--spikeDepth: comma-separated fractions in (0, 1] expected, got %r" % text)
+        raise SystemExit("--%s: comma-separated fractions in (0, 1] expected, got %r" % (flag, text))
     if not fr or any(not (0.0 < f <= 1.0) for f in fr):
-        raise SystemExit("--spikeDepth: every fraction must lie in (0, 1], got %r" % text)
+        raise SystemExit("--%s: every fraction must lie in (0, 1], got %r" % (flag, text))
     if len(set("%g" % f for f in fr)) != len(fr):
-        raise SystemExit("--spikeDepth: a fraction is listed twice (the cells' files would share a name), got %r" % text)
+        raise SystemExit("--%s: a fraction is listed twice (the cells' files would share a name), got %r" % (flag, text))
     if len(spike_targets) * len(fr) > MAX_CELLS:
-        raise SystemExit("--spikeDepth: %d targets x %d fractions = %d cells, at most %d" % (len(spike_targets), len(fr),
-                                                                                              len(spike_targets) * len(fr), MAX_CELLS))
+        raise SystemExit("--%s: %d targets x %d fractions = %d cells, at most %d" % (flag, len(spike_targets), len(fr),
+                                                                                      len(spike_targets) * len(fr), MAX_CELLS))
     return fr, [(k, t, f, max(1, int(py2_round(f * d))), "%s.dsMT%g" % (p, f)) for k, (t, d, p) in enumerate(spike_targets) for f in fr]
 
 

@@ -636,13 +636,21 @@ int smc_spike_alleles(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, con
  * Three launches behind the copies, enqueued on `stream`; nothing waits for the host, no workgroup waits for another; the offsets are
  * a sum in a fixed order: two calls give the same bytes.  SMC_E_INPUT, nothing launched and nothing copied: what smc_spike_alleles
  * refuses, a kind beyond SMC_AF_DEL, a len outside 1 .. SMC_AF_MAX_INS (0 for an SNV), ref != alt for an insertion / a deletion,
- * inserted letters beyond the n_ins bytes of d_ins, overlapping footprints, capacities below the run's own or of 2^32 or more. */
+ * inserted letters beyond the n_ins bytes of d_ins, overlapping footprints, capacities below the run's own or of 2^32 or more.
+ * PHASE SETS (--spikeIndelPhase).  `lead` is smc_spike_variant's: records back, in this position-sorted array, to the leader of the
+ * record's set - the member with the smallest position, an SNV's or an anchor's.  Record k, of whatever kind, is drawn with counter
+ * word 3 = (var[k - lead].pos0 + 1) mod 2^32 in place of its own position: a barcode is spiked at every member or at none, and every
+ * member is then applied under its own rule above.  A record between two members that is no member (lead 0) draws on its own.  With
+ * lead = 0 everywhere the call is bit for bit what it was (the field is the upper half of what was a 32-bit `len` <= 255).  Also
+ * SMC_E_INPUT, nothing launched and nothing copied: var_host[k].lead > k, or a leader whose own `lead` is not 0
+ * (smc_spike_indels_reps refuses the same; smc_spike_indel_touch makes no draw and does not read the field). */
 typedef struct smc_spike_indel_variant {
     int32_t pos0;              /* 0-based reference position: of the SNV, of the anchor */
     uint8_t kind;              /* SMC_AF_SNV, SMC_AF_INS, SMC_AF_DEL */
     uint8_t ref, alt;          /* ASCII, out of A C G T; an insertion / a deletion: the anchor's letter in both */
     uint8_t pad;
-    uint32_t len;              /* inserted letters / deleted positions; 0 for an SNV */
+    uint16_t len;              /* inserted letters / deleted positions (1 .. SMC_AF_MAX_INS); 0 for an SNV */
+    uint16_t lead;             /* records back, in this array, to the leader of the variant's phase set; 0: its own leader */
     uint32_t ins_off;          /* where the inserted letters start in d_ins */
     uint64_t thr;              /* floor(t * 2^32), in [0, 2^32] */
 } smc_spike_indel_variant;
@@ -764,6 +772,16 @@ int smc_spike_indel_touch(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln,
 int smc_spike_indel_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_cnt, const uint32_t* d_cov_off,
                            const uint32_t* cov_off_host, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
                            const uint64_t* thr, int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream);
+/* (ABI 11, additive: one entry more, the version number unchanged) --spikeIndelPhase: the joint numbers of phase sets whose members
+ * may be insertions and deletions.  smc_spike_phase_counts on rows of 4 * M_g words per joint barcode: per member (reads, alt0, alt1,
+ * touch), the columns of smc_spike_indel_counts - d_joint_cnt holds, per set, a block of (joint barcodes of g) rows of 4 * M_g words
+ * from word d_cnt_off[g].  V1_ALL' takes 2 * (hit ? alt1 : alt0) > reads at EVERY member; `touch` is not read (no READS' of a set).
+ * Every other argument, d_out[g][j][t][f][4] and every refusal are smc_spike_phase_counts'; with alt1 = touch = single the numbers
+ * are its numbers word for word, at M_g = 1 columns (N', V0', S', V1') of smc_spike_indel_counts. */
+int smc_spike_indel_phase_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, const uint32_t* d_joint_cnt, const uint32_t* d_joint_off,
+                                 const uint32_t* joint_off_host, const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_cnt_off,
+                                 const uint32_t* d_pos1, int32_t n_sets, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
+                                 int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

@@ -50,8 +50,8 @@ SPIKE_VARIANT_DTYPE = np.dtype([("pos0", "<i4"), ("ref", "u1"), ("alt", "u1"), (
 SPIKE_PHASE_MAX_MEMBERS = 8    # SMC_SPIKE_PHASE_MAX_MEMBERS
 assert SPIKE_VARIANT_DTYPE.itemsize == 16
 # smc_spike_indel_variant (smc_spike_indels): an SNV, an insertion or a deletion by the reference position of its base / anchor
-SPIKE_INDEL_VARIANT_DTYPE = np.dtype([("pos0", "<i4"), ("kind", "u1"), ("ref", "u1"), ("alt", "u1"), ("pad", "u1"), ("len", "<u4"),
-                                      ("ins_off", "<u4"), ("thr", "<u8")])
+SPIKE_INDEL_VARIANT_DTYPE = np.dtype([("pos0", "<i4"), ("kind", "u1"), ("ref", "u1"), ("alt", "u1"), ("pad", "u1"), ("len", "<u2"),
+                                      ("lead", "<u2"), ("ins_off", "<u4"), ("thr", "<u8")])
 assert SPIKE_INDEL_VARIANT_DTYPE.itemsize == 24
 
 

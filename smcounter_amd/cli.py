@@ -182,7 +182,7 @@ def build_parser() -> argparse.ArgumentParser:
                         "footprint lies in one aligned operation of its CIGAR - SEQ, QUAL, CIGAR and NM are rewritten on the GPU, as "
                         "tools/spike_variants.py --indels does it; every other record is left alone.  The outputs are --spikeAF's, V0 "
                         "and V1 of .spikeAF.detection.txt by the variant's INS / DEL key.  Not with --spikeReps, --spikeDepth or "
-                        "--spikePhase.  Without the flag an indel line is refused.  Needs --spikeAF")
+                        "--spikePhase (--spikeIndelReps, --spikeIndelDepth and --spikeIndelPhase cover them).  Without the flag an indel line is refused.  Needs --spikeAF")
     p.add_argument("--spikeIndelReps", type=int, default=None,
                    help="--spikeIndels and --spikeReps R in one: --spikeVariants may hold SNVs, insertions and deletions (the rules of "
                         "--spikeIndels), and replicate j = 0 .. R - 1 is that spike-in with seed (dsSeed + j) mod 2^64 - a plain run on the "
@@ -197,6 +197,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "(<outPrefix>.spikeAF<t>.dsMT<f>.*, .spikeAF.depth.detection.txt, with --spikeIndelReps .spikeAF.depth.replicates / "
                         ".sensitivity / .curve.txt), mtDepths and the limit of %d cells are --spikeDepth's.  Implies the rules of "
                         "--spikeIndels.  Needs --spikeAF" % GRID_MAX_CELLS)
+    p.add_argument("--spikeIndelPhase", action="store_true", default=False,
+                   help="--spikePhase under the rules of --spikeIndels: a phase set of --spikeVariants (an MNV line, or the lines of one "
+                        "chromosome that share a PS=<name> entry of VCF column 8 - on insertion and deletion lines too) may hold SNVs, "
+                        "insertions and deletions, at most 8 members; the footprints of ALL listed variants must be disjoint.  Every "
+                        "member is drawn with the position of the set's leader (the smallest position, an SNV's or an anchor's), so a "
+                        "barcode is spiked at every member or at none, and each member is then applied under its own rule, as "
+                        "tools/spike_variants.py --phased --indels does it.  Writes what --spikeIndels writes and, when a set has two "
+                        "members or more, <outPrefix>.spikeAF.phase.txt; beside --spikeIndelReps and / or --spikeIndelDepth also their "
+                        "pages, the cells' lines and .spikeAF.phase.replicates.txt / .phase.sensitivity.txt.  Not with --spikeIndels, "
+                        "--spikePhase (it implies both), --spikeReps or --spikeDepth (use --spikeIndelReps / --spikeIndelDepth).  Needs "
+                        "--spikeAF")
     p.add_argument("--spikeDepth", default=None,
                    help="the spike-ins of --spikeAF at several barcode depths: comma-separated fractions f in (0, 1].  For every target t "
                         "and every f the run is also called on the CELL (t, f): the spike-in at t, of which a barcode stays when the "
@@ -385,8 +396,8 @@ class _Plan:
     spike: dict = None          # (--spikeAF) once the rules are made: "variants", and "res", the pre-pass's numbers per target
     spike_reps: int = None      # (--spikeReps) R; plan.spike then holds "keep", what the pre-pass kept (None once the stage has taken it)
     spike_depth: dict = None    # (--spikeDepth) "fracs", the cells' "params", and once the rules are made "rules" and "counts" [V][T x F]
-    spike_indel_counters: bool = False   # (--spikeIndelReps, --spikeIndelDepth) the spike-ins are --spikeIndels', four counters per covering barcode
-    spike_phase: bool = False   # (--spikePhase) plan.spike then holds "phase": None, or devplanes.spike_rules' dict of the sets of two members or more
+    spike_indel_counters: bool = False   # (--spikeIndelReps, --spikeIndelDepth, --spikeIndelPhase) the spike-ins are --spikeIndels', four counters per covering barcode
+    spike_phase: bool = False   # (--spikePhase, --spikeIndelPhase) plan.spike then holds "phase": None, or devplanes.spike_rules' dict of the sets of two members or more
 
     @property
     def rules(self):
@@ -440,8 +451,8 @@ def spike_rules(args, outs, variants, early, keep=None, depth=None, phase=None, 
     if phase is not None:
         for ps, per in zip(phase["sets"], phase["counts"]):
             for o, c in zip(outs, per):
-                print("--spikePhase %g: set %s (%d members) N_ALL %d, V0_ALL %d, S_ALL %d, V1_ALL %d" %
-                      (o.af, ps.name, len(ps.members), c["N_ALL"], c["V0_ALL"], c["S_ALL"], c["V1_ALL"]))
+                print("%s %g: set %s (%d members) N_ALL %d, V0_ALL %d, S_ALL %d, V1_ALL %d" %
+                      ("--spikeIndelPhase" if getattr(args, "spikeIndelPhase", False) else "--spikePhase", o.af, ps.name, len(ps.members), c["N_ALL"], c["V0_ALL"], c["S_ALL"], c["V1_ALL"]))
     return rules, res
 
 
@@ -771,6 +782,7 @@ def _main(args) -> int:
     af_fracs, af_cells = ds_af_depth_cells(args, af_targets)
     from . import spike as _spike
     spike_targets = _spike.targets(args)
+    indel_phase = _spike.indel_phase(args, spike_targets)
     indel_reps, indel_depth = _spike.indel_flags(args, spike_targets)
     spike_fracs, spike_cells = _spike.depth_cells(args, spike_targets, "spikeIndelDepth" if indel_depth is not None else "spikeDepth")
     _spike.indels(args, spike_targets)
@@ -784,7 +796,8 @@ def _main(args) -> int:
                  [_Output(p, at(mtDepth=d), "spikeAF", af=t) for t, d, p in spike_targets] +
                  [_Output(p, at(mtDepth=d), "spikeDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in spike_cells],
                  reps=ds_af_reps(args, af_targets), spike_reps=indel_reps if indel_reps is not None else _spike.reps(args, spike_targets),
-                 spike_phase=_spike.phase(args, spike_targets), spike_indel_counters=indel_reps is not None or indel_depth is not None)
+                 spike_phase=_spike.phase(args, spike_targets) or indel_phase,
+                 spike_indel_counters=indel_reps is not None or indel_depth is not None or indel_phase)
     if spike_fracs is not None:
         plan.spike_depth = dict(fracs=spike_fracs, params=[o.params for o in plan.outputs if o.kind == "spikeDepth"])
     if af_fracs is not None:

@@ -1194,9 +1194,10 @@ int smc_spike_alleles(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, con
 }
 
 // (--spikeIndels, --spikeIndelReps) what the entries check of the listed variants, on their host copy.  `own_thr`: the variants' own
-// thresholds count; `d_ins` / `n_ins`: the pool of inserted letters, not looked at without `with_ins` (smc_spike_indel_touch)
+// thresholds count; `d_ins` / `n_ins`: the pool of inserted letters, not looked at without `with_ins` (smc_spike_indel_touch);
+// `with_lead`: the entry draws, so `lead` must point at a leader inside the array (smc_spike_indel_touch does not read it)
 static int spi_check_variants(const std::string& who, const smc_spike_indel_variant* var_host, int32_t n_var, const uint8_t* d_ins, int64_t n_ins,
-                              bool with_ins, bool own_thr) {
+                              bool with_ins, bool own_thr, bool with_lead) {
     if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
     if (n_var && !var_host) return fail(SMC_E_ARG, who + ": NULL argument");
     auto acgt = [](uint8_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; };
@@ -1217,6 +1218,10 @@ static int spi_check_variants(const std::string& who, const smc_spike_indel_vari
             return fail(SMC_E_INPUT, w + ": " + std::to_string(V.len) + " inserted letters at " + std::to_string(V.ins_off) + " (pool of " + std::to_string(n_ins) + ")");
         if (own_thr && V.thr > (1ull << 32)) return fail(SMC_E_INPUT, w + ": a threshold above 2^32");
         if (v && fp_end(var_host[v - 1]) >= (int64_t)V.pos0) return fail(SMC_E_INPUT, w + ": its footprint overlaps that of the variant before it");
+        if (with_lead) {                                         // (--spikeIndelPhase: spk_check's two lines)
+            if ((int32_t)V.lead > v) return fail(SMC_E_INPUT, w + ": lead " + std::to_string(V.lead) + " points in front of the array");
+            if (V.lead && var_host[v - (int32_t)V.lead].lead) return fail(SMC_E_INPUT, w + ": its leader has a lead of its own");
+        }
     }
     return SMC_OK;
 }
@@ -1231,7 +1236,7 @@ static int spi_copies(const std::string& who, smc_ctx* ctx, const smc_dev_aln* d
                       int64_t cap_cig, uint8_t* d_aln_out, int64_t aln_stride, uint8_t* d_bq_out, int64_t bq_stride, uint8_t* d_cig_out,
                       int64_t cig_stride, int32_t* d_nm_out, int32_t* d_n_indel_out, uint32_t* d_stats, uint64_t* d_totals, void* stream) {
     if (!ctx || n_aln < 0 || n_pairs < 0 || n_cig_words < 0 || n_var < 0 || n_bc < 0 || n_ins < 0) return fail(SMC_E_ARG, who + ": bad argument");
-    if (int rc = spi_check_variants(who, var_host, n_var, d_ins, n_ins, true, own_thr)) return rc;
+    if (int rc = spi_check_variants(who, var_host, n_var, d_ins, n_ins, true, own_thr, true)) return rc;
     if (n_aln >= (int64_t)0xFFFFFF00 || n_bc >= (int64_t)0x7FFFFF00) return fail(SMC_E_ARG, who + ": run too large");
     if (cap_pairs < n_pairs || cap_cig < n_cig_words || cap_pairs > (int64_t)0xFFFFFFFF || cap_cig > (int64_t)0xFFFFFFFF)
         return fail(SMC_E_INPUT, who + ": capacities of " + std::to_string(cap_pairs) + " pairs / " + std::to_string(cap_cig) + " CIGAR words for a run of " +
@@ -1331,7 +1336,7 @@ int smc_spike_indel_touch(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln,
                           uint32_t* d_out, void* stream) {
     const std::string who = "smc_spike_indel_touch";
     if (!ctx || n_aln < 0 || n_pairs < 0 || n_cig_words < 0 || n_var < 0 || n_bc < 0) return fail(SMC_E_ARG, who + ": bad argument");
-    if (int rc = spi_check_variants(who, var_host, n_var, nullptr, 0, false, false)) return rc;
+    if (int rc = spi_check_variants(who, var_host, n_var, nullptr, 0, false, false, false)) return rc;
     if (n_aln >= (int64_t)0xFFFFFF00 || n_bc >= (int64_t)0x7FFFFF00) return fail(SMC_E_ARG, who + ": run too large");
     if ((double)n_var * (double)n_bc >= (double)0xFFFFFF00u)
         return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants x " + std::to_string(n_bc) + " barcodes: too many counters for one call");
@@ -1494,6 +1499,16 @@ int smc_spike_phase_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, const ui
                            int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream) {
     return spk_cell_counts("smc_spike_phase_counts", ctx, d_joint_ident, d_joint_cnt, d_joint_off, joint_off_host, true, d_set_m, set_m_host,
                            d_cnt_off, d_pos1, n_sets, d_seeds, n_reps, thr, n_targets, true, depth_thr, n_fracs, 0x17u, d_out, stream);
+}
+
+// (--spikeIndelPhase) smc_spike_phase_counts' numbers from FOUR counters per joint barcode and member, (reads, alt0, alt1, touch):
+// k_spike_cells with stride 4 and car1 from column 2 (READS' is not wanted: column 3 is not read for a set)
+int smc_spike_indel_phase_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, const uint32_t* d_joint_cnt, const uint32_t* d_joint_off,
+                                 const uint32_t* joint_off_host, const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_cnt_off,
+                                 const uint32_t* d_pos1, int32_t n_sets, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
+                                 int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream) {
+    return spk_cell_counts("smc_spike_indel_phase_counts", ctx, d_joint_ident, d_joint_cnt, d_joint_off, joint_off_host, true, d_set_m, set_m_host,
+                           d_cnt_off, d_pos1, n_sets, d_seeds, n_reps, thr, n_targets, true, depth_thr, n_fracs, 0x17u, d_out, stream, 4, 2, 3);
 }
 
 // (--dsAFReps, --dsAFDepth) what the four entries check of the carrier table, on its host copy, and of the fractions' thresholds

@@ -29,6 +29,10 @@
 // holds the next one whole or not at all.  For the same reason whether a record takes variant v depends on no other variant's draw,
 // but for the two 16-bit limits, which count what the variants before it added: the host of --spikeIndelReps refuses a run in which
 // they could bind (devplanes.spike_indel_limits), and then k_spi_touch's numbers hold for every draw.
+// --spikeIndelPhase: a member of a phase set (V.lead != 0) draws with the position of its set's leader, var[k - V.lead], in both draw
+// sites (spi_walk, the in-place SNV loop of k_spi_scatter) - k_spike_rewrite's rule: one load more, for such records only; the leader
+// may stand in front of the record's first variant `lo`, the host checked lead <= k.  Every member of a set then makes the same draw
+// and is applied under its own rule; what a record is eligible for does not depend on it.  k_spi_touch draws nothing.
 #define SPI_BLOCK 256
 #define SPI_MAX16 65535u
 static_assert(sizeof(smc_spike_indel_variant) == 24, "abi.SPIKE_INDEL_VARIANT_DTYPE");
@@ -89,7 +93,8 @@ __device__ __forceinline__ bool spi_walk(const smc_dev_aln& a, const uint32_t* _
         if (!EMIT && V.kind == SMC_AF_SNV) continue;
         if (!TOUCH) {
             uint32_t u[4];
-            smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, (uint32_t)V.pos0 + 1u, (uint32_t)seed, (uint32_t)(seed >> 32), u);
+            smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, (uint32_t)(V.lead ? var[k - (int)V.lead].pos0 : V.pos0) + 1u,
+                              (uint32_t)seed, (uint32_t)(seed >> 32), u);
             if (!((unsigned long long)u[0] < (own_thr ? V.thr : thr_c))) continue;
         }
         if (V.kind == SMC_AF_SNV) {                              // k_spike_rewrite's rule, on the original CIGAR
@@ -256,7 +261,8 @@ __global__ __launch_bounds__(SPI_BLOCK) void k_spi_scatter(const smc_dev_aln* __
             if (V.pos0 >= a.end) break;
             if (V.kind != SMC_AF_SNV) continue;
             uint32_t u[4];
-            smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, (uint32_t)V.pos0 + 1u, (uint32_t)seed, (uint32_t)(seed >> 32), u);
+            smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, (uint32_t)(V.lead ? var[k - (int)V.lead].pos0 : V.pos0) + 1u,
+                              (uint32_t)seed, (uint32_t)(seed >> 32), u);
             if (!((unsigned long long)u[0] < (own_thr ? V.thr : thr_c))) continue;
             const BpRes r = bp2_resolve(cig + a.cig_off, (int)a.n_cig, a.pos, V.pos0, (int)a.l_seq);
             if (r.isdel || r.indel != 0 || r.qpos < 0 || r.qpos >= (int)a.l_seq) continue;

@@ -1333,23 +1333,29 @@ class SpikeSet(object):
         from .tools import spike_variants as sv
         self.lead_pos = sv.leaders(variants)
         self.variants = list(variants)
-        # (--spikeIndels) a list that holds an insertion or a deletion: the records are smc_spike_indels' (no phase sets beside them),
-        # ins[chrom] the pool of inserted letters
+        # (--spikeIndels) a list that holds an insertion or a deletion: the records are smc_spike_indels' (with --spikeIndelPhase their
+        # `lead` too), ins[chrom] the pool of inserted letters
         # (--spikeIndelReps, --spikeIndelDepth: `indels` - smc_spike_indels' records whatever the list holds)
         self.indels = bool(indels) or any(v.kind != af.SNV for v in self.variants)
         self.by_chrom, self.ins = {}, {}
         for c in sorted({v.chrom for v in self.variants}):
             order = sorted((k for k, v in enumerate(self.variants) if v.chrom == c), key=lambda k: self.variants[k].pos)
+            # (the leader has the set's smallest position: it stands in front, on the same chromosome; `lead` is a 16-bit field of
+            # both records)
+            at = {self.variants[k].pos: j for j, k in enumerate(order)}
+            lead = [j - at[self.lead_pos[k]] for j, k in enumerate(order)]
+            far = next((j for j, x in enumerate(lead) if x > 0xFFFF), None)
+            if far is not None:
+                raise ValueError("%s:%d: its phase set's leader stands %d records in front, beyond the field's 65535" %
+                                 (c, self.variants[order[far]].pos, lead[far]))
             if self.indels:
                 var, self.ins[c], _ = spike_indel_variants([self.variants[k] for k in order], 0)
-                self.by_chrom[c] = (var, order)
-                continue
-            var = np.zeros(len(order), abi.SPIKE_VARIANT_DTYPE)
-            for j, k in enumerate(order):
-                v = self.variants[k]
-                var[j]["pos0"], var[j]["ref"], var[j]["alt"] = v.pos - 1, ord(v.ref), ord(v.alt)
-                # (the leader has the set's smallest position: it stands in front, on the same chromosome)
-                var[j]["lead"] = j - next(i for i, m in enumerate(order) if self.variants[m].pos == self.lead_pos[k])
+            else:
+                var = np.zeros(len(order), abi.SPIKE_VARIANT_DTYPE)
+                for j, k in enumerate(order):
+                    v = self.variants[k]
+                    var[j]["pos0"], var[j]["ref"], var[j]["alt"] = v.pos - 1, ord(v.ref), ord(v.alt)
+            var["lead"] = lead
             self.by_chrom[c] = (var, order)
 
     def chrom_variants(self, chrom: str, t: float):
@@ -1617,15 +1623,16 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     counters are FOUR per covering barcode, uint32 [covering barcodes, 4] = (reads, alt0, alt1, touch): alt1 the `alt` counter on the
     copy spiked at threshold 2^32 - for an insertion / a deletion alt0 plus the eligible records whose anchor letter is REF's -, touch
     the records the rewrite changes when the barcode is hit - alt1 for an SNV, smc_spike_indel_touch's for an insertion / a deletion.
-    The cells' counts then come from smc_spike_indel_counts.  ValueError, before anything is spiked: a run with a record at which the
+    The cells' counts then come from smc_spike_indel_counts, and with `phase` (--spikeIndelPhase: the members of a set may be
+    insertions and deletions, every record of SpikeSet carries its `lead`) the joint rows hold four counters per member and the joint
+    numbers come from smc_spike_indel_phase_counts; the second count is the same AND of smc_allele_carriers' bits, INS / DEL keys
+    included.  ValueError, before anything is spiked: a run with a record at which the
     16-bit limits of the rewrite could bind (spike_indel_limits) - the counters would depend on the other variants' draws."""
     from .tools import ds_allele_fraction as af
     from .tools import spike_variants as sv
     af.unique_idents(bamio.placed_barcodes(path), path)
     nthreads = nthreads or bamio.host_threads()
     spikes = SpikeSet(variants, indels=indel_counters)
-    if indel_counters and phase is not None:
-        raise ValueError("--spikeIndelReps / --spikeIndelDepth: phase sets of indel spike-ins are not built")
     P = params_list[0]
     rows = [[None] * len(variants) for _ in targets]
     psets = list(phase["sets"]) if phase is not None else []
@@ -1775,7 +1782,9 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
             joint = spike_joint(psets, covers, counters)
             lead = [spikes.lead_pos[s.members[0]] for s in psets]
             s0, thr = [int(seed) & 0xFFFFFFFFFFFFFFFF], [sv.threshold(t) for t in targets]
-            got = spike_phase_counts(eng, lead, joint, s0, thr, [1 << 32])[:, 0, :, 0]
+            # (--spikeIndelPhase: four counters per member - smc_spike_indel_phase_counts)
+            phase_counts = spike_indel_phase_counts if indel_counters else spike_phase_counts
+            got = phase_counts(eng, lead, joint, s0, thr, [1 << 32])[:, 0, :, 0]
             both = lambda sets: len(functools.reduce(np.intersect1d, sets))
             for g, ps in enumerate(psets):
                 for t in range(len(targets)):
@@ -1788,7 +1797,7 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
             phase["joint"] = joint
             phase["counts"] = [[dict(zip(names, (int(x) for x in got[g, t]))) for t in range(len(targets))] for g in range(len(psets))]
             if depth is not None:
-                cells = spike_phase_counts(eng, lead, joint, s0, thr, [frac_threshold(f) for f in fracs])[:, 0]
+                cells = phase_counts(eng, lead, joint, s0, thr, [frac_threshold(f) for f in fracs])[:, 0]
                 phase["depth_counts"] = [[dict(zip(names, (int(x) for x in cells[g, t, f]))) for t in range(len(targets))
                                           for f in range(len(fracs))] for g in range(len(psets))]
         except BaseException:
@@ -2139,30 +2148,31 @@ def spike_indel_counts(eng, positions, covers, counters, seeds, thresholds, dept
 def spike_joint(sets, covers, counters):
     """Per phase set (tools.spike_variants.PhaseSet) -> (uint64 [n]: the identities of the barcodes that cover EVERY member, ascending;
     uint32 [n, M, 3]: their (reads, alt0, single) at each member, in the set's order).  covers[v] / counters[v]: per listed variant
-    its covering identities and their counters, as spike_rep_counts takes them."""
+    its covering identities and their counters, as spike_rep_counts takes them - or, with four counters per covering barcode
+    (spike_indel_counts': reads, alt0, alt1, touch), uint32 [n, M, 4]."""
     out = []
     for s in sets:
         ids = [np.asarray(covers[k], np.uint64) for k in s.members]
         both = np.unique(functools.reduce(np.intersect1d, ids))
-        cnt = np.zeros((len(both), len(s.members), 3), np.uint32)
+        first = np.asarray(counters[s.members[0]])
+        width = int(first.shape[1]) if first.ndim == 2 else 3
+        cnt = np.zeros((len(both), len(s.members), width), np.uint32)
         for m, (k, x) in enumerate(zip(s.members, ids)):
             order = np.argsort(x, kind="stable")
             at = order[np.searchsorted(x[order], both)] if len(both) else np.zeros(0, np.int64)
-            cnt[:, m] = np.asarray(counters[k], np.uint32).reshape(-1, 3)[at]
+            cnt[:, m] = np.asarray(counters[k], np.uint32).reshape(-1, width)[at]
         out.append((both, cnt))
     return out
 
 
-def spike_phase_counts(eng, lead_positions, joint, seeds, thresholds, depth_thresholds) -> np.ndarray:
-    """smc_spike_phase_counts -> uint32 [G, R, T, F, 4] = (N_ALL', V0_ALL', S_ALL', V1_ALL') of every phase set, replicate and cell.
-    lead_positions[g]: the 1-based position of the set's leader; joint[g]: (uint64 [n_g] identities of the barcodes that cover every
-    member, uint32 [n_g, M_g, 3] their (reads, alt0, single) per member) - spike_joint's; the rest as spike_depth_counts takes it."""
+def _spike_joint_counts(eng, who: str, entry, width: int, lead_positions, joint, seeds, thresholds, depth_thresholds) -> np.ndarray:
+    """The two wrappers below: the joint rows of `width` counters per member flattened as both entries take them, then `entry`."""
     G, seeds = len(joint), np.ascontiguousarray(seeds, np.uint64)
     thr, dthr = np.ascontiguousarray(thresholds, np.uint64), np.ascontiguousarray(depth_thresholds, np.uint64)
     cnts = [np.ascontiguousarray(c, np.uint32) for _, c in joint]
     for (ids, _), c in zip(joint, cnts):
-        if c.ndim != 3 or c.shape[0] != len(ids) or c.shape[2] != 3:
-            raise ValueError("spike_phase_counts: %d joint barcodes, counters of shape %r" % (len(ids), c.shape))
+        if c.ndim != 3 or c.shape[0] != len(ids) or c.shape[2] != width:
+            raise ValueError("%s: %d joint barcodes, counters of shape %r (%d per member expected)" % (who, len(ids), c.shape, width))
     off = np.zeros(G + 1, np.uint32)
     off[1:] = np.cumsum([len(ids) for ids, _ in joint])
     set_m = np.array([c.shape[1] for c in cnts], np.uint32)
@@ -2173,10 +2183,24 @@ def spike_phase_counts(eng, lead_positions, joint, seeds, thresholds, depth_thre
     cnt = np.concatenate([c.reshape(-1) for c in cnts]) if G else np.zeros(0, np.uint32)
     pos = np.array([int(p) & 0xFFFFFFFF for p in lead_positions], np.uint32)
     return _spike_counts_call(
-        eng, "smc_spike_phase_counts", [ident, cnt, off, set_m, cnt_off, pos, seeds], (G, len(seeds), len(thr), len(dthr), 4),
-        lambda d, d_out: eng.L.smc_spike_phase_counts(eng.ctx, d[0], d[1], d[2], off.ctypes.data, d[3], set_m.ctypes.data, d[4], d[5], G,
-                                                      d[6], len(seeds), thr.ctypes.data, len(thr), dthr.ctypes.data, len(dthr), d_out,
-                                                      ctypes.c_void_p(0)))
+        eng, "smc_" + who, [ident, cnt, off, set_m, cnt_off, pos, seeds], (G, len(seeds), len(thr), len(dthr), 4),
+        lambda d, d_out: entry(eng.ctx, d[0], d[1], d[2], off.ctypes.data, d[3], set_m.ctypes.data, d[4], d[5], G, d[6], len(seeds),
+                               thr.ctypes.data, len(thr), dthr.ctypes.data, len(dthr), d_out, ctypes.c_void_p(0)))
+
+
+def spike_phase_counts(eng, lead_positions, joint, seeds, thresholds, depth_thresholds) -> np.ndarray:
+    """smc_spike_phase_counts -> uint32 [G, R, T, F, 4] = (N_ALL', V0_ALL', S_ALL', V1_ALL') of every phase set, replicate and cell.
+    lead_positions[g]: the 1-based position of the set's leader; joint[g]: (uint64 [n_g] identities of the barcodes that cover every
+    member, uint32 [n_g, M_g, 3] their (reads, alt0, single) per member) - spike_joint's; the rest as spike_depth_counts takes it."""
+    return _spike_joint_counts(eng, "spike_phase_counts", eng.L.smc_spike_phase_counts, 3, lead_positions, joint, seeds, thresholds,
+                               depth_thresholds)
+
+
+def spike_indel_phase_counts(eng, lead_positions, joint, seeds, thresholds, depth_thresholds) -> np.ndarray:
+    """smc_spike_indel_phase_counts -> spike_phase_counts' uint32 [G, R, T, F, 4] from joint[g]'s uint32 [n_g, M_g, 4] = (reads, alt0,
+    alt1, touch) per member - spike_joint's over spike_indel_counts' counters."""
+    return _spike_joint_counts(eng, "spike_indel_phase_counts", eng.L.smc_spike_indel_phase_counts, 4, lead_positions, joint, seeds,
+                               thresholds, depth_thresholds)
 
 
 def spike_copy_strides(n_aln: int, n_pairs: int):
@@ -2433,7 +2457,8 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
     without it.
     `phase` (--spikePhase: spike_rules' dict): the draws are the sets' (SpikeSet.lead_pos), and the result gets "phase_counts", uint32
     [G, R, T, 4] = (N_ALL, V0_ALL, S_ALL, V1_ALL) of every set, replicate and target from one smc_spike_phase_counts call, with
-    `depth` also "phase_depth_counts", uint32 [G, R, T, F, 4], from a second."""
+    `depth` also "phase_depth_counts", uint32 [G, R, T, F, 4], from a second (--spikeIndelPhase: smc_spike_indel_phase_counts, the
+    joint rows then hold four counters per member)."""
     import time
     from . import dsaf
     from .tools import spike_variants as sv
@@ -2460,9 +2485,10 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
         phase_counts = phase_depth_counts = None
         if phase is not None and phase.get("joint"):
             lead = [spikes.lead_pos[s.members[0]] for s in phase["sets"]]
-            phase_counts = spike_phase_counts(eng, lead, phase["joint"], seeds, thr, [1 << 32])[:, :, :, 0]
+            joint_counts = spike_indel_phase_counts if four else spike_phase_counts
+            phase_counts = joint_counts(eng, lead, phase["joint"], seeds, thr, [1 << 32])[:, :, :, 0]
             if depth is not None:
-                phase_depth_counts = spike_phase_counts(eng, lead, phase["joint"], seeds, thr, [frac_threshold(f) for f in depth["fracs"]])
+                phase_depth_counts = joint_counts(eng, lead, phase["joint"], seeds, thr, [frac_threshold(f) for f in depth["fracs"]])
         times["counts"] = time.perf_counter() - t0
         for run in keep["runs"]:
             if run.A is None:

@@ -18,6 +18,9 @@ outputs and the detection page are --spikeAF's, V0 and V1 by the variant's INS /
 --spikeIndelReps / --spikeIndelDepth: --spikeReps and --spikeDepth on the --spikeIndels spike-in (indel_flags); the pages are those
 of --spikeReps / --spikeDepth, from the same writers.
 
+--spikeIndelPhase: phase sets whose members may be insertions and deletions (indel_phase; tools.spike_variants --phased --indels is
+the rule): the variants file is read as --spikePhase reads it, under the rules of --spikeIndels; the pages are --spikePhase's.
+
 The semantics are tools/spike_variants.py's (DESIGN.md "--spikeAF"); the rewrite on the GPU is csrc/k_spike.inc (smc_spike_alleles),
 the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the main pass are devplanes.spike_rules / spike_run.
 """
@@ -72,10 +75,11 @@ def targets(args):
 def variants(args, loc_list, fasta, indels: bool = False):
     """The variants of --spikeVariants, checked: the file's refusals (tools.spike_variants.parse_variants: SNVs only, with
     --spikePhase MNV lines and PS= sets as well, with --spikeIndels - or `indels`: --spikeIndelReps, --spikeIndelDepth - insertions and
-    deletions whose footprints do not overlap), REF the genome's letters, every variant a locus of --bedTarget."""
+    deletions whose footprints do not overlap, with --spikeIndelPhase both), REF the genome's letters, every variant a locus of --bedTarget."""
     try:
-        out = sv.parse_variants(args.spikeVariants, "--spikeVariants", phased=bool(getattr(args, "spikePhase", False)),
-                                indels=bool(indels) or bool(getattr(args, "spikeIndels", False)))
+        both = bool(getattr(args, "spikeIndelPhase", False))
+        out = sv.parse_variants(args.spikeVariants, "--spikeVariants", phased=both or bool(getattr(args, "spikePhase", False)),
+                                indels=both or bool(indels) or bool(getattr(args, "spikeIndels", False)))
         sv.check_reference(out, fasta, "--spikeVariants")
         loci = set((c, int(p)) for c, p in loc_list)
         for v in out:
@@ -151,6 +155,27 @@ def indel_flags(args, spike_targets):
     if r is not None:
         r = reps(args, spike_targets, "spikeIndelReps")
     return r, text
+
+
+# ---- --spikeIndelPhase
+def indel_phase(args, spike_targets) -> bool:
+    """--spikeIndelPhase -> whether --spikeVariants is read for phase sets whose members may be insertions and deletions.  SystemExit,
+    each naming the flag to use instead: beside --spikeIndels or --spikePhase (it implies both), beside --spikeReps or --spikeDepth
+    (--spikeIndelReps / --spikeIndelDepth stand beside it); without --spikeAF."""
+    if not getattr(args, "spikeIndelPhase", False):
+        return False
+    if getattr(args, "spikeIndels", False):
+        raise SystemExit("--spikeIndelPhase implies the rules of --spikeIndels: leave --spikeIndels out")
+    if getattr(args, "spikePhase", False):
+        raise SystemExit("--spikeIndelPhase reads --spikeVariants as --spikePhase does: leave --spikePhase out")
+    if getattr(args, "spikeReps", None) not in (None, ""):
+        raise SystemExit("--spikeIndelPhase cannot be combined with --spikeReps in one run: use --spikeIndelReps R beside it")
+    if getattr(args, "spikeDepth", None) not in (None, ""):
+        raise SystemExit("--spikeIndelPhase cannot be combined with --spikeDepth in one run: use --spikeIndelDepth beside it")
+    if not spike_targets:
+        raise SystemExit("--spikeIndelPhase plants the phase sets of --spikeVariants, insertions and deletions among their members: it "
+                         "needs --spikeAF and --spikeVariants")
+    return True
 
 
 # ---- --spikeReps
@@ -423,7 +448,9 @@ def _set_fields(pset, variants, target, frac, mt_depth):
 
 
 def called_all(pset, variants, cut) -> int:
-    """1 when `cut` ((chrom, pos text) -> (REF, ALT list) of an output's .cut.txt) has every member of the set with its ALT."""
+    """1 when `cut` ((chrom, pos text) -> (REF, ALT list) of an output's .cut.txt) has every member of the set with its ALT - per
+    member the comparison of the detection page's CALLED (dsaf.detection_line), whatever its kind: an insertion's or a deletion's line
+    stands at its anchor with the listed REF and ALT texts."""
     for k in pset.members:
         v = variants[k]
         c = cut.get((v.chrom, "%d" % v.pos))

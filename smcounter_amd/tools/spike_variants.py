@@ -38,6 +38,13 @@ letters S / D out of ACGT, REF the genome's letters.
              reference span (so the bin), flags and mapq stay; NM grows by s / d; MD is left as it is.
   reported   V0 / V1 by the variant's INS|X|XS / DEL|XD|X key (ds_allele_fraction.read_key; a rewritten read whose anchor holds
              another letter than X shows another key and is no carrier), READS the records rewritten.
+
+--phased --indels (a run's --spikeIndelPhase): PS=<name> may stand on an insertion's or a deletion's line too, so a phase set may
+hold SNVs, an MNV line's members, insertions and deletions together (at most 8 members; the footprints of ALL listed variants
+disjoint).  The leader is the member with the smallest position - an SNV's or an anchor's -, every member draws with the leader's P0,
+and each is then applied under its OWN rule above, on the record's original CIGAR: a barcode is spiked at every member or at none,
+but a record may take some members and not others (one that ends inside a deletion's footprint takes the SNV in front of it only).
+NM accumulates per record: a 3-letter deletion and an SNV that showed REF give NM + 4.  A variant of no set draws as ever.
 """
 from __future__ import annotations
 
@@ -88,14 +95,18 @@ def phase_sets(variants):
     return [s for s in getattr(variants, "sets", ()) if len(s.members) >= 2]
 
 
-def _parse_phased(path: str, flag: str):
+def _parse_phased(path: str, flag: str, indels: bool = False):
     """--spikePhase's reading of the file: ds_allele_fraction.parse_variants' line shapes and refusals, and
       an MNV line   REF and ALT of one length L, 2 <= L <= PHASE_MAX_MEMBERS, letters out of ACGT: one member SNV per offset where they
                     differ (at least one), all in one set named chrom:pos;
       PS=<name>     a `;`-separated entry of column 8 of a VCF-shaped line: the lines of one chromosome with one name are one set (an
                     MNV line with the entry joins it with all its members).
-    One variant per position over all members; at most PHASE_MAX_MEMBERS members per set; a name on one chromosome only."""
+    One variant per position over all members; at most PHASE_MAX_MEMBERS members per set; a name on one chromosome only.
+    `indels` (--spikeIndelPhase / --phased --indels): a line may be an insertion X / XS or a deletion XD / X of 1 to MAX_INS letters
+    out of ACGT too, and its PS= entry makes it a member like any other; the footprints (footprint()) of ALL listed variants, members
+    or not, must be disjoint - refused by line, with parse_variants(indels=True)'s message."""
     out, seen, mnvs = [], set(), []
+    line_of = {}                                                 # (chrom, pos) of a listed variant -> its line number
     sets, order = {}, []                                         # set key -> [name, chrom, members], and the keys in file order
     with open(path) as fh:
         for n, line in enumerate(fh, 1):
@@ -141,17 +152,26 @@ def _parse_phased(path: str, flag: str):
                                          "deletion (XD / X)" % (flag, where, ref, alt))
                     raise ValueError("%s: REF %r / ALT %r is neither a substitution of one letter, an insertion (X / XS) nor a "
                                      "deletion (XD / X)" % (where, ref, alt))
-                if ka[1] != af.SNV:
+                if ka[1] != af.SNV and not indels:
                     raise ValueError("%s: %s:%d %s>%s is an insertion or a deletion; only one-letter substitutions can be spiked (an indel "
                                      "means rewriting CIGARs)" % (flag, chrom, pos, ref, alt))
-                if ref not in LETTERS or alt not in LETTERS:
-                    raise ValueError("%s: %s:%d %s>%s: REF and ALT must be one of A, C, G, T" % (flag, chrom, pos, ref, alt))
+                if ka[1] == af.SNV:
+                    if ref not in LETTERS or alt not in LETTERS:
+                        raise ValueError("%s: %s:%d %s>%s: REF and ALT must be one of A, C, G, T" % (flag, chrom, pos, ref, alt))
+                else:                                            # (parse_variants(indels=True)'s refusals of an indel line)
+                    if ka[1] == af.INS and len(alt) - 1 > af.MAX_INS:
+                        raise ValueError("%s: an insertion of %d letters, at most %d are taken" % (where, len(alt) - 1, af.MAX_INS))
+                    if any(c not in LETTERS for c in ref + alt):
+                        raise ValueError("%s: %s:%d %s>%s: REF and ALT must be made of A, C, G, T" % (flag, chrom, pos, ref, alt))
+                    if ka[1] == af.DEL and len(ref) - 1 > af.MAX_INS:
+                        raise ValueError("%s: %s:%d: a deletion of %d letters, at most %d are taken" % (flag, chrom, pos, len(ref) - 1, af.MAX_INS))
                 members = [(pos, ref, alt)]
                 key, name = (("PS", ps[0]), ps[0]) if ps else (None, None)
             for q, r, a in members:
                 if (chrom, q) in seen:
                     raise ValueError("%s: %s:%d is listed twice (one variant per position)" % (where, chrom, q))
                 seen.add((chrom, q))
+                line_of[(chrom, q)] = n
             if key is not None:
                 if key not in sets:
                     sets[key] = [name, chrom, []]
@@ -162,9 +182,11 @@ def _parse_phased(path: str, flag: str):
                 sets[key][2] += list(range(len(out), len(out) + len(members)))
                 if len(sets[key][2]) > PHASE_MAX_MEMBERS:
                     raise ValueError("%s: %s: the phase set %s has %d members, at most %d" % (flag, where, name, len(sets[key][2]), PHASE_MAX_MEMBERS))
-            out += [af.Variant(chrom, q, r, a, a, af.SNV) for q, r, a in members]
+            out += [af.Variant(chrom, q, r, a, *af.allele_key(r, a)) for q, r, a in members]
     if not out:
         raise ValueError("%s lists no variant" % path)
+    if indels:
+        _check_footprints(out, flag, path, line_of)
     return PhasedVariants(out, [PhaseSet(sets[k][0], sets[k][1], tuple(sorted(sets[k][2], key=lambda i: out[i].pos))) for k in order], mnvs)
 
 
@@ -185,17 +207,26 @@ def _lines_of(path: str):
     return out
 
 
+def _check_footprints(variants, flag: str, path: str, lines) -> None:
+    """ValueError, by line, when the footprints of two listed variants of one chromosome overlap.  lines[(chrom, pos)]: line numbers."""
+    order = sorted(variants, key=lambda v: (v.chrom, v.pos))
+    for u, v in zip(order, order[1:]):
+        if u.chrom == v.chrom and footprint(u)[1] >= v.pos:
+            raise ValueError("%s: %s line %d: %s:%d %s>%s lies in the footprint %d-%d of %s:%d %s>%s (line %d)" % (
+                flag, path, lines[(v.chrom, v.pos)], v.chrom, v.pos, v.ref, v.alt, footprint(u)[0], footprint(u)[1], u.chrom, u.pos,
+                u.ref, u.alt, lines[(u.chrom, u.pos)]))
+
+
 def parse_variants(path: str, flag: str = "--variants", phased: bool = False, indels: bool = False):
     """The variants of a spike-in file, in file order: ds_allele_fraction.parse_variants' format and refusals, and only one-letter
     substitutions out of A, C, G, T (an insertion or a deletion would mean rewriting CIGARs).  ValueError names the variant refused.
     `phased` (--spikePhase / --phased): MNV lines and PS= entries make phase sets (_parse_phased) -> PhasedVariants; without it an
     MNV line is refused as ever and PS= entries are not read.
     `indels` (--spikeIndels / --indels): insertions X / XS and deletions XD / X of 1 to MAX_INS letters out of A, C, G, T are taken
-    too; footprints (footprint()) that overlap are refused by line."""
+    too; footprints (footprint()) that overlap are refused by line.
+    Both (--spikeIndelPhase / --phased --indels): phase sets whose members may be insertions and deletions -> PhasedVariants."""
     if phased:
-        if indels:
-            raise ValueError("%s: phase sets of insertions and deletions are not built" % flag)
-        return _parse_phased(path, flag)
+        return _parse_phased(path, flag, indels)
     out = af.parse_variants(path)
     for v in out:
         if v.kind != af.SNV and not indels:
@@ -207,13 +238,7 @@ def parse_variants(path: str, flag: str = "--variants", phased: bool = False, in
         if v.kind == af.DEL and len(v.ref) - 1 > af.MAX_INS:
             raise ValueError("%s: %s:%d: a deletion of %d letters, at most %d are taken" % (flag, v.chrom, v.pos, len(v.ref) - 1, af.MAX_INS))
     if indels:
-        lines = _lines_of(path)
-        order = sorted(out, key=lambda v: (v.chrom, v.pos))
-        for u, v in zip(order, order[1:]):
-            if u.chrom == v.chrom and footprint(u)[1] >= v.pos:
-                raise ValueError("%s: %s line %d: %s:%d %s>%s lies in the footprint %d-%d of %s:%d %s>%s (line %d)" % (
-                    flag, path, lines[(v.chrom, v.pos)], v.chrom, v.pos, v.ref, v.alt, footprint(u)[0], footprint(u)[1], u.chrom, u.pos,
-                    u.ref, u.alt, lines[(u.chrom, u.pos)]))
+        _check_footprints(out, flag, path, _lines_of(path))
     return out
 
 

@@ -782,6 +782,44 @@ int smc_spike_indel_phase_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, co
                                  const uint32_t* joint_off_host, const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_cnt_off,
                                  const uint32_t* d_pos1, int32_t n_sets, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
                                  int32_t n_targets, const uint64_t* depth_thr, int32_t n_fracs, uint32_t* d_out, void* stream);
+/* (ABI 11, additive: two entries more, the version number unchanged) --spikeRpb: the cells (spike target t, reads-per-barcode target
+ * r) of the --spikeAF spike-in.  Cell (t, r) of replicate j is the spike-in at t drawn with seeds[j], of which the records stay that
+ * smc_read_groups_masks keeps with the same seed at r: a record whose read name is the first of its barcode, file-wide, or whose
+ * read draw - word 0 of Philox4x32-10(counter = (name identity lo, name identity hi, 0x64735250 "dsRP", 0), key = (seeds[j] lo, hi)) -
+ * is below read_thr[r] = floor(probKeep_r * 2^32).  Thinning reads changes a barcode's counters per r and per seed, so they are
+ * counted per record:
+ *   smc_spike_read_bits   for the run as smc_spike_indel_touch takes it (d_bq: its pair pool of n_pairs pairs; d_loc[n_loci], start0:
+ *            as smc_allele_carriers takes them) and its listed SNVs d_var[n_var] (smc_allele_carriers' records, kind SMC_AF_SNV, `letter`
+ *            the ALT): d_out[v][n_aln] uint8, one byte per alignment - bit 0: the record is in the window [w0, w1) of v's locus and
+ *            covers its position p (pos <= p < end); bit 1: it shows ALT there as it is (smc_allele_carriers' rule); bit 2: its allele
+ *            key there is a single letter (a base, not inside a deletion, no insertion or deletion starting behind it, inside l_seq
+ *            and the pools) - exactly the records smc_spike_alleles rewrites when the barcode is spiked.  Every byte of d_out is
+ *            written (0 for a record outside the window); plain stores, no atomics.  Summed per barcode the three bits are
+ *            smc_spike_rep_counts' (reads, alt0, single).
+ *   smc_spike_rpb_counts  the covering barcodes of all n_var variants one behind the other as smc_spike_rep_counts takes them
+ *            (d_cov_ident, d_cov_off / cov_off_host); per covering barcode e its covering records [rec_off[e], rec_off[e + 1]) of
+ *            d_rec_name (the read-name identity: smc_bam_pair_idents of the record's pair_gid) and d_rec_flag (uint8: bit 0 = the
+ *            name is its barcode's first, file-wide; bits 1 and 2 = bits 1 and 2 of smc_spike_read_bits) - d_rec_off: the
+ *            cov_off_host[n_var] + 1 offsets in device memory, rec_off_host the same on the host; n_rec records.  d_pos1, d_seeds,
+ *            `thr`: smc_spike_rep_counts'; `read_thr`: HOST memory, n_read_thr words in [0, 2^32].  A record is KEPT at r when flag
+ *            bit 0 is set or its read draw is below read_thr[r]; with (reads_r, alt_r, single_r) of a barcode over its kept records,
+ *            hit = u_v(b; seeds[j]) < thr[t], there = reads_r > 0:
+ *            d_out[v][j][t][r][5] uint32 = (N': the b with there, V0': those with 2 * alt_r > reads_r, S': those with hit, READS':
+ *            the sum of single_r over the b with there and hit, V1': the b with there and 2 * (hit ? single_r : alt_r) > reads_r).
+ *            One spike draw per (b, v, j) and one read draw per (record, j) serve every cell; at one read threshold of 2^32 the
+ *            numbers are smc_spike_depth_counts' at one depth threshold of 2^32.  d_out is zeroed by the call; integer atomics
+ *            only: two calls give the same words.
+ * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched and nothing zeroed: more than SMC_AF_MAX_VARIANTS variants, a
+ * locus index beyond n_loci, a kind that is not SMC_AF_SNV (smc_spike_read_bits); what smc_spike_depth_counts refuses, a read
+ * threshold above 2^32, n_read_thr below 1, n_targets * n_read_thr above SMC_AF_DEPTH_MAX_CELLS, record offsets that decrease or end
+ * beyond n_rec (smc_spike_rpb_counts). */
+int smc_spike_read_bits(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words, const uint8_t* d_bq,
+                        int64_t n_pairs, const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0, const smc_af_variant* d_var,
+                        const smc_af_variant* var_host, int32_t n_var, uint8_t* d_out, void* stream);
+int smc_spike_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_off, const uint32_t* cov_off_host,
+                         const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
+                         int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
+                         int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

@@ -219,6 +219,19 @@ def build_parser() -> argparse.ArgumentParser:
                         "replicated as the targets are: <outPrefix>.spikeAF.depth.replicates.txt, .spikeAF.depth.sensitivity.txt and "
                         ".spikeAF.depth.curve.txt (per variant and depth the detection rate at every target and T95).  What the cells "
                         "achieve is counted on the GPU in one call; at most %d cells.  Needs --spikeAF" % GRID_MAX_CELLS)
+    p.add_argument("--spikeRpb", default=None,
+                   help="the spike-ins of --spikeAF at several reads-per-barcode targets: comma-separated r > 0.  For every target t and "
+                        "every r the run is also called on the CELL (t, r): the spike-in at t, then the --dsRpb r --dsRpbSampler philox "
+                        "thinning with the same --dsSeed (two independent draws: one per barcode and position, one per read name) - the "
+                        ".dsRpb<r> output of a --dsRpb r --dsRpbSampler philox run on the BAM tools/spike_variants.py --af t writes, at "
+                        "that target's mtDepth and --rpb r; written to <outPrefix>.spikeAF<t>.dsRpb<r>.smCounter.{all,cut}.txt and "
+                        ".cut.vcf (with --lod: its LOD files and summary line), and, one line per variant and cell, "
+                        "<outPrefix>.spikeAF.rpb.detection.txt with the counts over the reads the cell keeps.  The file-wide table of "
+                        "read names is built once; what the cells achieve is counted per read on the GPU in one call; at most %d "
+                        "cells.  With --spikeReps the cells are replicated as the targets are, replicate j drawing both streams with "
+                        "seed (dsSeed + j) mod 2^64: <outPrefix>.spikeAF.rpb.replicates.txt, .spikeAF.rpb.sensitivity.txt and "
+                        ".spikeAF.rpb.curve.txt (per variant and r the detection rate at every target and T95).  SNV lists only; not "
+                        "with --spikeDepth, --spikePhase or the --spikeIndel* flags.  Needs --spikeAF" % GRID_MAX_CELLS)
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -374,11 +387,11 @@ class _Output:
     its reads per barcode).  Output 0 of a run is the full-depth one; every other has a `rule`, once the rule makers below have run."""
     prefix: str
     params: VcParams
-    kind: str = "full"          # full, dsMT, dsRpb, dsGrid, dsAF, dsAFDepth, spikeAF or spikeDepth
+    kind: str = "full"          # full, dsMT, dsRpb, dsGrid, dsAF, dsAFDepth, spikeAF, spikeDepth or spikeRpb
     frac: float = None          # (dsMT, dsGrid, dsAFDepth, spikeDepth) the fraction of the barcodes
-    target: float = None        # (dsRpb, dsGrid) the reads per barcode asked for
-    af: float = None            # (dsAF, dsAFDepth, spikeAF, spikeDepth) the target allele fraction
-    af_index: int = None        # (dsAFDepth, spikeDepth) which --dsAF / --spikeAF target the cell belongs to
+    target: float = None        # (dsRpb, dsGrid, spikeRpb) the reads per barcode asked for
+    af: float = None            # (dsAF, dsAFDepth, spikeAF, spikeDepth, spikeRpb) the target allele fraction
+    af_index: int = None        # (dsAFDepth, spikeDepth, spikeRpb) which --dsAF / --spikeAF target the cell belongs to
     rule: object = None         # the devplanes.DsRule that selects it; None: full depth
 
 
@@ -396,6 +409,7 @@ class _Plan:
     spike: dict = None          # (--spikeAF) once the rules are made: "variants", and "res", the pre-pass's numbers per target
     spike_reps: int = None      # (--spikeReps) R; plan.spike then holds "keep", what the pre-pass kept (None once the stage has taken it)
     spike_depth: dict = None    # (--spikeDepth) "fracs", the cells' "params", and once the rules are made "rules" and "counts" [V][T x F]
+    spike_rpb: dict = None      # (--spikeRpb) "targets", the cells' "params", and once the rules are made "rules" and "counts" [V][T x Rr]
     spike_indel_counters: bool = False   # (--spikeIndelReps, --spikeIndelDepth, --spikeIndelPhase) the spike-ins are --spikeIndels', four counters per covering barcode
     spike_phase: bool = False   # (--spikePhase, --spikeIndelPhase) plan.spike then holds "phase": None, or devplanes.spike_rules' dict of the sets of two members or more
 
@@ -430,14 +444,14 @@ def ds_af_rules(args, outs, variants, early, keep=None, depth=None):
     return rules, res
 
 
-def spike_rules(args, outs, variants, early, keep=None, depth=None, phase=None, indel_counters=False):
+def spike_rules(args, outs, variants, early, keep=None, depth=None, phase=None, indel_counters=False, rpb=None):
     """The devplanes.DsRule of every --spikeAF output (the pre-pass on the GPU: devplanes.spike_rules) and its numbers; the run log
     gets a line per variant and target.  `keep` (--spikeReps): a dict for what the replicate stage starts from.  `depth`
     (--spikeDepth): the plan's dict; it gets the cells' rules and counts.  `phase` (--spikePhase): a dict with the "sets" of two
-    members or more; it gets their joint barcodes and counts."""
+    members or more; it gets their joint barcodes and counts.  `rpb` (--spikeRpb): the plan's dict; it gets the cells' rules and counts."""
     from .tools import spike_variants as sv
     eng = _engine_of(args, early)
-    more = {k: v for k, v in (("keep", keep), ("depth", depth), ("phase", phase)) if v is not None}
+    more = {k: v for k, v in (("keep", keep), ("depth", depth), ("phase", phase), ("rpb", rpb)) if v is not None}
     if indel_counters:
         more["indel_counters"] = True
     try:
@@ -584,6 +598,9 @@ def call_shard(args, params: VcParams, loci, device: int, early=None, plan=None)
         batches = devplanes.iter_resident_batches(args.bamFile, ref, loci, params, eng, max_reads=32 * args.batchReads,
                                                   nthreads=nthreads, all_planes=False, sampler=getattr(args, "sampler", "reference"),
                                                   sampler_seed=getattr(args, "samplerSeed", 0), ds_rules=rules,
+                                                  # (--spikeRpb: the replicate stage reads the cells' file-wide table behind the last
+                                                  # batch - main() owns the plan's tables and closes them whatever happens)
+                                                  close_tables=plan is None or plan.spike_rpb is None,
                                                   force_host=rules is not None and (decoder == "python" or
                                                                                     os.environ.get("SMC_PLANES", "device") == "host"))
         # (a batch ahead in a helper thread: decoding and building batch i + 1 overlaps the kernels and the strings of batch i;
@@ -647,6 +664,8 @@ def _spike_replicates(args, plan, ref, eng, loci, ds_rows):
     more = {"depth": plan.spike_depth} if plan.spike_depth is not None else {}
     if plan.spike.get("phase") is not None:
         more["phase"] = plan.spike["phase"]
+    if plan.spike_rpb is not None:
+        more["rpb"] = plan.spike_rpb
     out = devplanes.spike_replicates(args.bamFile, ref, variants, [o.af for o in targets], [o.params for o in targets], int(args.dsSeed),
                                      plan.spike_reps, eng, keep, sampler=getattr(args, "sampler", "reference"),
                                      sampler_seed=getattr(args, "samplerSeed", 0), **more)
@@ -786,6 +805,7 @@ def _main(args) -> int:
     indel_reps, indel_depth = _spike.indel_flags(args, spike_targets)
     spike_fracs, spike_cells = _spike.depth_cells(args, spike_targets, "spikeIndelDepth" if indel_depth is not None else "spikeDepth")
     _spike.indels(args, spike_targets)
+    spike_rpbs, spike_rpb_cells = _spike.rpb_cells(args, spike_targets)
     at = lambda **kw: dataclasses.replace(params, **kw)
     plan = _Plan([_Output(args.outPrefix, params)] +
                  [_Output(p, at(mtDepth=d), "dsMT", frac=f) for f, d, p in fractions] +
@@ -794,12 +814,15 @@ def _main(args) -> int:
                  [_Output(p, at(mtDepth=d), "dsAF", af=t) for t, d, p in af_targets] +
                  [_Output(p, at(mtDepth=d), "dsAFDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in af_cells] +
                  [_Output(p, at(mtDepth=d), "spikeAF", af=t) for t, d, p in spike_targets] +
-                 [_Output(p, at(mtDepth=d), "spikeDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in spike_cells],
+                 [_Output(p, at(mtDepth=d), "spikeDepth", frac=f, af=t, af_index=k) for k, t, f, d, p in spike_cells] +
+                 [_Output(p, at(mtDepth=d, rpb=r), "spikeRpb", target=r, af=t, af_index=k) for k, t, r, d, p in spike_rpb_cells],
                  reps=ds_af_reps(args, af_targets), spike_reps=indel_reps if indel_reps is not None else _spike.reps(args, spike_targets),
                  spike_phase=_spike.phase(args, spike_targets) or indel_phase,
                  spike_indel_counters=indel_reps is not None or indel_depth is not None or indel_phase)
     if spike_fracs is not None:
         plan.spike_depth = dict(fracs=spike_fracs, params=[o.params for o in plan.outputs if o.kind == "spikeDepth"])
+    if spike_rpbs is not None:
+        plan.spike_rpb = dict(targets=spike_rpbs, params=[o.params for o in plan.outputs if o.kind == "spikeRpb"])
     if af_fracs is not None:
         plan.depth = dict(fracs=af_fracs, params=[o.params for o in plan.outputs if o.kind == "dsAFDepth"])
     flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets), ("--dsAF", af_targets), ("--spikeAF", spike_targets)) if on)
@@ -832,6 +855,10 @@ def _main(args) -> int:
         raise
     for rule in plan.rules:
         if rule.level == "read":               # (a target or a cell)
+            if rule.spike_rpb_cell:
+                print("--spikeRpb %s: sampler %s, seed %d, probKeep %.6g, threshold %d, %d of %d read names kept (mtDepth %d)" %
+                      (rule.label, rule.sampler, rule.seed, rule.prob_keep, rule.thr, rule.n_kept, rule.n_names, rule.params.mtDepth))
+                continue
             print("%s: sampler %s, seed %d, probKeep %.6g, %d of %d read names kept (mtDepth %d)" %
                   ("--dsGrid " + rule.label if rule.grid else "--dsRpb %g" % rule.target, rule.sampler, rule.seed, rule.prob_keep,
                    len(rule.kept) if rule.kept is not None else rule.n_kept, rule.n_names, rule.params.mtDepth))
@@ -880,8 +907,10 @@ def _make_rules(args, plan, loc_list):
         from .tools import spike_variants as sv
         psets = sv.phase_sets(variants) if plan.spike_phase else []
         phase = dict(sets=psets) if psets else None
-        rules, res = spike_rules(args, sp, variants, plan.early, keep, plan.spike_depth, phase, plan.spike_indel_counters)
+        rules, res = spike_rules(args, sp, variants, plan.early, keep, plan.spike_depth, phase, plan.spike_indel_counters, plan.spike_rpb)
         put(sp, rules)
+        if plan.spike_rpb is not None:
+            put([o for o in plan.outputs if o.kind == "spikeRpb"], plan.spike_rpb["rules"])
         if plan.spike_depth is not None:
             put([o for o in plan.outputs if o.kind == "spikeDepth"], plan.spike_depth["rules"])
         plan.spike = dict(variants=variants, res=res, keep=keep, phase=phase)
@@ -1005,12 +1034,11 @@ def _af_reports(args, plan, shard, loc_list, repeats):
           (tm["stage"], plan.reps, over, tm["builds"], tm["batches"], tm["counts"], tm["masks"]))
 
 
-def _spike_cells(plan, lods):
-    """(--spikeDepth) per cell (target index, target, fraction, mtDepth, output prefix, that output's LODs or None), as spike's depth
-    pages take them; the cells' outputs lie behind the targets'."""
-    first = next(k for k, o in enumerate(plan.outputs) if o.kind == "spikeDepth")
-    return [(o.af_index, o.af, o.frac, o.params.mtDepth, o.prefix, lods[first + c]["lods"] if lods is not None else None)
-            for c, o in enumerate(plan.outputs[first:])]
+def _spike_cells(plan, lods, kind="spikeDepth"):
+    """(--spikeDepth; `kind` "spikeRpb": --spikeRpb) per cell (target index, target, fraction or reads-per-barcode target, mtDepth,
+    output prefix, that output's LODs or None), as spike's depth pages take them; the cells' outputs lie behind the targets'."""
+    return [(o.af_index, o.af, o.frac if kind == "spikeDepth" else o.target, o.params.mtDepth, o.prefix,
+             lods[k]["lods"] if lods is not None else None) for k, o in enumerate(plan.outputs) if o.kind == kind]
 
 
 def _spike_reports(args, plan, shard, loc_index, repeats):
@@ -1035,24 +1063,29 @@ def _spike_reports(args, plan, shard, loc_index, repeats):
     lod_vt = None if lods is None else [[float(l["lods"][loc_index[(v.chrom, "%d" % v.pos)]]) for v in variants] for l in lods[1:1 + len(outs)]]
     _spike.write_sensitivity(args.outPrefix, variants, targets, entries, lod_vt)
     _spike.write_curve(args.outPrefix, variants, targets, entries, lod_vt)
-    if plan.spike_depth is not None:
-        # (--spikeDepth: the same three pages over the cells; their rows stand behind the targets' in the stage's)
-        cells, T, dc = _spike_cells(plan, lods), len(outs), reps["depth_counts"]
+    cell_entries = None
+    for kind, info, axis in (("spikeDepth", plan.spike_depth, _spike.DEPTH_AXIS), ("spikeRpb", plan.spike_rpb, _spike.RPB_AXIS)):
+        if info is None:
+            continue
+        # (--spikeDepth, --spikeRpb: the same three pages over the cells; their rows stand behind the targets' in the stage's)
+        depth = kind == "spikeDepth"
+        cells, T, dc = _spike_cells(plan, lods, kind), len(outs), reps["depth_counts" if depth else "rpb_counts"]
         cell_entries = {}
         for i, v in enumerate(variants):
-            for c, o in enumerate(o for o in plan.outputs if o.kind == "spikeDepth"):
+            for c, o in enumerate(o for o in plan.outputs if o.kind == kind):
                 thr_c = writers.pi_threshold(o.params.mtDepth, args.threshold)
                 per = []
                 for j in range(R):
                     row, cut = dsaf.replicate_entry(reps["rows"].get((i, T + c, j)), thr_c, *repeats)
                     per.append((dict(zip(("N", "V0", "S", "READS", "V1"), (int(x) for x in dc[i, j].reshape(-1, 5)[c]))), row, cut))
                 cell_entries[(i, c)] = per
-                print("--spikeReps: %s:%d %s>%s at %g x fraction %g: called %d of %d" % (v.chrom, v.pos, v.ref, v.alt, o.af, o.frac,
-                                                                                         _spike._called(v, per), R))
-        _spike.write_depth_replicates(args.outPrefix, variants, cells, reps["seeds"], cell_entries)
-        _spike.write_depth_sensitivity(args.outPrefix, variants, cells, cell_entries, loc_index)
+                print("--spikeReps: %s:%d %s>%s at %g x %s %g: called %d of %d" % (v.chrom, v.pos, v.ref, v.alt, o.af, "fraction" if depth else "target",
+                                                                                   o.frac if depth else o.target, _spike._called(v, per), R))
+        _spike.write_depth_replicates(args.outPrefix, variants, cells, reps["seeds"], cell_entries, axis)
+        _spike.write_depth_sensitivity(args.outPrefix, variants, cells, cell_entries, loc_index, axis)
         full = [(o.params.mtDepth, lods[1 + t]["lods"] if lods is not None else None) for t, o in enumerate(outs)]
-        _spike.write_depth_curve(args.outPrefix, variants, targets, plan.spike_depth["fracs"], full, cells, entries, cell_entries, loc_index)
+        _spike.write_depth_curve(args.outPrefix, variants, targets, info["fracs"] if depth else info["targets"], full, cells, entries, cell_entries,
+                                 loc_index, axis)
     phase = plan.spike.get("phase")
     if phase is not None:
         # (--spikePhase: a set is called in a replicate when every member is; the joint counts are the stage's own call's)
@@ -1120,6 +1153,9 @@ def _run(args, plan, loc_list, t0):
         _spike.write_detection(args.outPrefix, plan.spike["variants"], outs, loc_index)
         if plan.spike_depth is not None:
             _spike.write_depth_detection(args.outPrefix, plan.spike["variants"], _spike_cells(plan, lods), plan.spike_depth["counts"], loc_index)
+        if plan.spike_rpb is not None:
+            _spike.write_depth_detection(args.outPrefix, plan.spike["variants"], _spike_cells(plan, lods, "spikeRpb"),
+                                         plan.spike_rpb["counts"], loc_index, _spike.RPB_AXIS)
         phase = plan.spike.get("phase")
         if phase is not None:
             # (--spikePhase: every set in the full-depth output - nothing spiked there -, in every target's and in every cell's)

@@ -1511,6 +1511,94 @@ int smc_spike_indel_phase_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, co
                            d_cnt_off, d_pos1, n_sets, d_seeds, n_reps, thr, n_targets, true, depth_thr, n_fracs, 0x17u, d_out, stream, 4, 2, 3);
 }
 
+// (--spikeRpb) per listed SNV of a run and alignment one byte: covers / shows ALT / single-letter key.  One launch, every byte written
+int smc_spike_read_bits(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words, const uint8_t* d_bq,
+                        int64_t n_pairs, const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0, const smc_af_variant* d_var,
+                        const smc_af_variant* var_host, int32_t n_var, uint8_t* d_out, void* stream) {
+    const std::string who = "smc_spike_read_bits";
+    if (!ctx || n_aln < 0 || n_cig_words < 0 || n_pairs < 0 || n_loci < 0 || n_var < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
+    if (n_var && !var_host) return fail(SMC_E_ARG, who + ": NULL argument");
+    for (int32_t v = 0; v < n_var; ++v) {
+        const smc_af_variant& V = var_host[v];
+        if ((int64_t)V.locus >= n_loci)
+            return fail(SMC_E_INPUT, who + ": variant " + std::to_string(v) + " names locus " + std::to_string(V.locus) + " of " + std::to_string(n_loci));
+        if (V.kind != SMC_AF_SNV) return fail(SMC_E_INPUT, who + ": variant " + std::to_string(v) + " has kind " + std::to_string(V.kind) + ", an SNV expected");
+    }
+    if (n_aln >= (int64_t)0xFFFFFF00) return fail(SMC_E_ARG, who + ": run too large");
+    if (!n_var || !n_aln) return SMC_OK;
+    if (!d_aln || !d_cig || !d_bq || !d_loc || !d_var || !d_out) return fail(SMC_E_ARG, who + ": NULL argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_spr_bits, dim3((unsigned)std::min<int64_t>((n_aln + SPB_BLOCK - 1) / SPB_BLOCK, 1024), (unsigned)n_var), dim3(SPB_BLOCK), 0,
+                       (hipStream_t)stream, d_aln, (uint32_t)n_aln, d_cig, (unsigned long long)n_cig_words, d_bq, (unsigned long long)n_pairs, d_loc,
+                       start0, d_var, d_out);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
+// (--spikeRpb) (N', V0', S', READS', V1') of every listed SNV, replicate and cell (spike target x read threshold), from the covering
+// barcodes' records: everything checked on the host copies before anything is enqueued, then the counters zeroed and k_spr_counts
+int smc_spike_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_off, const uint32_t* cov_off_host,
+                         const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
+                         int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
+                         int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out, void* stream) {
+    const std::string who = "smc_spike_rpb_counts";
+    if (!ctx || n_var < 0 || n_reps < 0 || n_targets < 0 || n_rec < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
+    if (n_targets > SMC_SPIKE_REP_MAX_TARGETS)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_SPIKE_REP_MAX_TARGETS));
+    if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
+    if (n_read_thr < 1) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_read_thr) + " read thresholds, at least 1 expected");
+    if ((n_reps && !d_seeds) || (n_targets && !thr) || !read_thr) return fail(SMC_E_ARG, who + ": NULL argument");
+    if ((int64_t)n_targets * (int64_t)n_read_thr > SMC_AF_DEPTH_MAX_CELLS)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets x " + std::to_string(n_read_thr) + " read thresholds, at most " +
+                                 std::to_string(SMC_AF_DEPTH_MAX_CELLS) + " cells");
+    SpkThr T;
+    RgThr Q;
+    memset(&T, 0, sizeof T);
+    memset(&Q, 0, sizeof Q);
+    for (int32_t t = 0; t < n_targets; ++t) {
+        if (thr[t] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": target " + std::to_string(t) + ": a threshold above 2^32");
+        T.t[t] = thr[t];
+    }
+    for (int32_t r = 0; r < n_read_thr; ++r) {
+        if (read_thr[r] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": read threshold " + std::to_string(r) + " is above 2^32");
+        if (r < SMC_RG_MAX_TARGETS) Q.t[r] = read_thr[r];         // (more of them pass the cells' limit only without a target: nothing is launched)
+    }
+    if ((double)n_var * (double)n_reps * (double)n_targets * (double)n_read_thr * (double)SPC_COUNTERS >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants x " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) +
+                                 " targets x " + std::to_string(n_read_thr) + " read thresholds: too many counters for one call");
+    if (n_rec >= (int64_t)0xFFFFFF00) return fail(SMC_E_INPUT, who + ": too many covering records for one call");
+    if (!n_var || !n_reps || !n_targets) return SMC_OK;
+    if (!cov_off_host || !d_cov_off || !d_pos1 || !d_out) return fail(SMC_E_ARG, who + ": NULL argument");
+    uint32_t widest = 0;
+    for (int32_t g = 0; g < n_var; ++g) {
+        if (cov_off_host[g + 1] < cov_off_host[g]) return fail(SMC_E_INPUT, who + ": the offsets decrease at variant " + std::to_string(g));
+        widest = std::max(widest, cov_off_host[g + 1] - cov_off_host[g]);
+    }
+    const uint32_t n_cov = cov_off_host[n_var];
+    if (n_cov >= 0x55555500u) return fail(SMC_E_INPUT, who + ": too many covering barcodes for one call");
+    if (n_cov) {
+        if (!d_cov_ident || !d_rec_off || !rec_off_host) return fail(SMC_E_ARG, who + ": NULL covers");
+        for (uint32_t e = 0; e < n_cov; ++e)
+            if (rec_off_host[e + 1] < rec_off_host[e]) return fail(SMC_E_INPUT, who + ": the record offsets decrease at covering barcode " + std::to_string(e));
+        if ((int64_t)rec_off_host[n_cov] > n_rec)
+            return fail(SMC_E_INPUT, who + ": the record offsets end at " + std::to_string(rec_off_host[n_cov]) + ", beyond the " + std::to_string(n_rec) + " records");
+        if (n_rec && (!d_rec_name || !d_rec_flag)) return fail(SMC_E_ARG, who + ": NULL records");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t n_out = (size_t)SPC_COUNTERS * (size_t)n_var * (size_t)n_reps * (size_t)n_targets * (size_t)n_read_thr;
+    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
+    if (widest)
+        hipLaunchKernelGGL(n_read_thr <= 8 ? k_spr_counts<8> : k_spr_counts<SMC_RG_MAX_TARGETS>, dim3((unsigned)std::min<uint32_t>((widest + SPB_BLOCK - 1) / SPB_BLOCK, 256u), (unsigned)n_var,
+                                              (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPB_BLOCK), 0, st,
+                           (const unsigned long long*)d_cov_ident, d_cov_off, d_rec_off, (const unsigned long long*)d_rec_name, d_rec_flag,
+                           (uint32_t)n_rec, d_pos1, T, (int)n_targets, Q, (int)n_read_thr, (const unsigned long long*)d_seeds, (int)n_reps, d_out);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
 // (--dsAFReps, --dsAFDepth) what the four entries check of the carrier table, on its host copy, and of the fractions' thresholds
 // (host memory), which go into the kernels' argument -> `with_depth`: a fraction is below 2^32, so the depth draw decides something
 static int afd_check_table(const std::string& w, const uint64_t* d_car, const uint64_t* d_car_thr, const uint64_t* car_host,

@@ -1,0 +1,149 @@
+// Included by smcounter_hip.hip (after k_spike_cells.inc: SPC_COUNTERS, spd_hits and the spike draw's domain; after k_read_groups.inc:
+// rg_draw, the read draw k_rg_masks makes; after k_allele_carriers.inc: af_shows).
+// ------------------------------------------------------------------------------------------
+// --spikeRpb: what every cell (spike target t, reads-per-barcode target r) of R replicate spike-ins achieves per listed SNV, counted
+// PER READ (smc_spike_read_bits, smc_spike_rpb_counts)
+// ------------------------------------------------------------------------------------------
+// A cell is the --spikeAF spike-in at t, then the --dsRpb philox thinning at r, both drawn with the key s_j, each a stream of its own:
+//   the spike rule at t   hit  = u(b) = k_spike_rewrite's draw (domain "spAF", counter word 3 the variant's 1-based position) < thr[t],
+//                         one draw per barcode;
+//   the read rule at r    kept = the record's name is the first of its barcode, file-wide, or rg_draw(name) - k_rg_masks' draw,
+//                         domain "dsRP" - < rthr[r] = floor(probKeep_r * 2^32): one draw per read name.
+// k_spike_cells decides whole barcodes from three counters the run fixes.  Thinning reads moves those counters per r and per seed: it
+// can flip a barcode's majority and can take a barcode out of the locus altogether.  So the counters are made here, per replicate,
+// from one FLAG BYTE per covering record:
+//   k_spr_bits    (smc_spike_read_bits) a lane per alignment, a row of workgroups per listed SNV: bit 0 the record covers the
+//                 position, bit 1 it shows ALT as it is (af_shows), bit 2 its allele key there is a single letter - the records
+//                 k_spike_rewrite touches.  A plain byte store per alignment, 0 outside the locus's window: no atomics.
+//   k_spr_counts  (smc_spike_rpb_counts) a lane per covering barcode of a variant (blockIdx.y = variant, blockIdx.z strides over the
+//                 replicates).  The lane walks the barcode's records (a CSR segment: name identity and flag byte, bit 0 = first name,
+//                 bits 1 / 2 = alt / single from k_spr_bits): ONE philox per record and replicate, its compares against the Rr read
+//                 thresholds one bit set; per r the lane keeps (reads_r, alt_r, single_r) over the kept records.  Then per barcode
+//                 and r:  N' = reads_r > 0,  car0 = 2 alt_r > reads_r,  car1 = 2 single_r > reads_r,  and per cell (t, r)
+//                   V0' = N' && car0    S' = N' && hit    READS' = single_r over N' && hit    V1' = N' && (hit ? car1 : car0)
+//                 reduced as k_spike_cells reduces: ballots + popcounts and a DPP sum for READS', the workgroup's wavefronts added in
+//                 LDS, one integer atomic add per workgroup, replicate, cell and counter that is not 0 - two calls give the same words.
+// The per-r counters are indexed by unrolled loops only (they stay in registers: 3 x MAXR of them, so the kernel is compiled for MAXR =
+// 8 - what a run asks for - and for MAXR = 32, the most the cells' limit admits; n_rr <= MAXR).  Once per run / once per file: not on
+// the per-locus hot path.
+#define SPB_BLOCK 256
+#define SPB_COVERS 1u
+#define SPB_ALT 2u
+#define SPB_SINGLE 4u
+#define SPB_FIRST 1u                         // (a record's flag byte for k_spr_counts) first name of its barcode, file-wide
+
+// out[v * n_aln + i]: the three bits of alignment i at variant v (an SNV: var[v].letter its ALT); every byte of the row is written.
+// Against k_af_count on MALFORMED records: a record is counted here whatever its bc_gid (the host groups the bytes by barcode, and
+// takes the covering barcodes from smc_allele_carriers' bits), and one whose CIGAR or bases lie beyond the pools covers but shows
+// nothing, as k_spike_rewrite treats it - k_af_count skips the first and reads the second.  The two then disagree, and the host,
+// which compares the bytes' sums per barcode with the pre-pass's counters for every run, ends the run: no wrong number is printed.
+__global__ __launch_bounds__(SPB_BLOCK) void k_spr_bits(const smc_dev_aln* __restrict__ aln, uint32_t n_aln, const uint32_t* __restrict__ cig,
+                                                        unsigned long long n_cig_words, const uint8_t* __restrict__ bq,
+                                                        unsigned long long n_pairs, const smc_dev_locus* __restrict__ loc, int32_t start0,
+                                                        const smc_af_variant* __restrict__ var, uint8_t* __restrict__ out) {
+    const smc_af_variant V = var[blockIdx.y];
+    const smc_dev_locus L = loc[V.locus];
+    const uint32_t w1 = min(L.w1, n_aln);
+    const int p = start0 + (int)V.locus;
+    uint8_t* const o = out + (size_t)n_aln * blockIdx.y;
+    for (uint32_t i = blockIdx.x * SPB_BLOCK + threadIdx.x; i < n_aln; i += gridDim.x * SPB_BLOCK) {
+        uint32_t b = 0u;
+        if (i >= L.w0 && i < w1) {
+            const smc_dev_aln a = aln[i];
+            // (a record that points beyond a pool covers, and shows nothing: k_spike_rewrite leaves it alone as well)
+            if (a.pos <= p && p < a.end) {
+                b = SPB_COVERS;
+                if ((unsigned long long)a.cig_off + a.n_cig <= n_cig_words) {
+                    const BpRes r = bp2_resolve(cig + a.cig_off, (int)a.n_cig, a.pos, p, (int)a.l_seq);
+                    if (!r.isdel && r.indel == 0 && r.qpos >= 0 && r.qpos < (int)a.l_seq &&
+                        (unsigned long long)a.seq_off + (unsigned long long)r.qpos < n_pairs) {
+                        b |= SPB_SINGLE;
+                        if (af_shows(V, a, cig, bq, nullptr, p)) b |= SPB_ALT;
+                    }
+                }
+            }
+        }
+        o[i] = (uint8_t)b;
+    }
+}
+
+// out[(((g * n_reps + j) * n_tgt + t) * n_rr + r) * 5 + k] += counter k of (N', V0', S', READS', V1') (zeroed before the launch); n_tgt *
+// n_rr <= SMC_AF_DEPTH_MAX_CELLS.  Variant g: barcodes [off[g], off[g + 1]) of `ident`; barcode e: records [rec_off[e], rec_off[e + 1])
+// of rec_name / rec_flag, clamped to n_rec.  n_rr <= MAXR (the host picks the instance).
+template <int MAXR>
+__global__ __launch_bounds__(SPB_BLOCK) void k_spr_counts(const unsigned long long* __restrict__ ident, const uint32_t* __restrict__ off,
+                                                          const uint32_t* __restrict__ rec_off, const unsigned long long* __restrict__ rec_name,
+                                                          const uint8_t* __restrict__ rec_flag, uint32_t n_rec,
+                                                          const uint32_t* __restrict__ pos1, SpkThr T, int n_tgt, RgThr Q, int n_rr,
+                                                          const unsigned long long* __restrict__ seeds, int n_reps, uint32_t* __restrict__ out) {
+    __shared__ uint32_t part[SPB_BLOCK / WAVE][SMC_AF_DEPTH_MAX_CELLS][SPC_COUNTERS];
+    const uint32_t g = blockIdx.y;
+    const uint32_t e0 = off[g], e1 = off[g + 1], pos = pos1[g];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    const int n_cells = n_tgt * n_rr;
+    const uint32_t every = n_rr >= 32 ? 0xFFFFFFFFu : (1u << n_rr) - 1u;
+    const uint32_t stride = gridDim.x * SPB_BLOCK;
+    for (uint32_t base = e0 + blockIdx.x * SPB_BLOCK; base < e1; base += stride) {     // (whole workgroups: the barriers below)
+        const uint32_t e = base + threadIdx.x;
+        unsigned long long id = 0;
+        uint32_t r0 = 0, r1 = 0;                                                       // (a lane beyond the row: no records, N' = 0 everywhere)
+        if (e < e1) {
+            id = ident[e];
+            r0 = min(rec_off[e], n_rec);
+            r1 = min(rec_off[e + 1], n_rec);
+        }
+        for (int j = blockIdx.z; j < n_reps; j += gridDim.z) {
+            const unsigned long long seed = seeds[j];
+            uint32_t x[4];
+            smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, pos, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+            const uint32_t k_hit = spd_hits(T, x[0], n_tgt);
+            uint32_t reads[MAXR], alt[MAXR], sgl[MAXR];
+#pragma unroll
+            for (int r = 0; r < MAXR; ++r) reads[r] = alt[r] = sgl[r] = 0u;
+            for (uint32_t i = r0; i < r1; ++i) {
+                const uint32_t fl = rec_flag[i];
+                uint32_t kept = every;
+                if (!(fl & SPB_FIRST)) {
+                    const uint32_t u = rg_draw(rec_name[i], seed);
+                    kept = 0u;
+                    for (int r = 0; r < n_rr; ++r) kept |= (uint32_t)((unsigned long long)u < Q.t[r]) << r;
+                }
+                const uint32_t is_alt = (fl >> 1) & 1u, is_sgl = (fl >> 2) & 1u;
+#pragma unroll
+                for (int r = 0; r < MAXR; ++r) {
+                    const uint32_t k = (kept >> r) & 1u;
+                    reads[r] += k; alt[r] += k & is_alt; sgl[r] += k & is_sgl;
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < MAXR; ++r) {
+                if (r < n_rr) {                                                        // (uniform)
+                    const bool there = reads[r] > 0u;
+                    const bool car0 = 2ull * alt[r] > (unsigned long long)reads[r], car1 = 2ull * sgl[r] > (unsigned long long)reads[r];
+                    const unsigned long long m_n = __ballot(there), m_v0 = __ballot(there && car0);
+                    for (int t = 0; t < n_tgt; ++t) {
+                        const bool hit = ((k_hit >> t) & 1u) != 0u;
+                        const unsigned long long m_s = __ballot(there && hit), m_v1 = __ballot(there && (hit ? car1 : car0));
+                        // (a run holds fewer than 2^32 - 256 alignments: no wrap that matters)
+                        const int rd = wave_add((int)((there && hit) ? sgl[r] : 0u));
+                        if (lane == 0) {
+                            uint32_t* const p = part[wave][t * n_rr + r];
+                            p[0] = (uint32_t)__popcll(m_n); p[1] = (uint32_t)__popcll(m_v0); p[2] = (uint32_t)__popcll(m_s);
+                            p[3] = (uint32_t)rd; p[4] = (uint32_t)__popcll(m_v1);
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            if ((int)threadIdx.x < SPC_COUNTERS * n_cells) {                           // (5 * 32 = 160 < SPB_BLOCK)
+                const int c = threadIdx.x / SPC_COUNTERS, q = threadIdx.x % SPC_COUNTERS;
+                uint32_t sum = 0;
+                for (int w = 0; w < SPB_BLOCK / WAVE; ++w) sum += part[w][c][q];
+                if (sum) atomicAdd(&out[(((size_t)g * n_reps + j) * n_cells + c) * SPC_COUNTERS + q], sum);
+            }
+            __syncthreads();
+        }
+    }
+}
+static_assert(SMC_RG_MAX_TARGETS == SMC_AF_DEPTH_MAX_CELLS && SPC_COUNTERS * SMC_AF_DEPTH_MAX_CELLS <= SPB_BLOCK,
+              "k_spr_counts: a bit per read threshold, a lane per cell and counter");

@@ -36,6 +36,8 @@
 //                        per-variant draw picks, each record's mismatch count and SMC_DA_MMOK bit moved with the base.
 //   k_spike_cells.inc    --spikeReps, --spikeDepth, --spikePhase: what R replicate spike-ins achieve per listed variant or phase set and
 //                        cell (spike target x barcode fraction), from the covering barcodes' counters alone: no spiked copy is made.
+//   k_spike_rpb.inc      --spikeRpb: the same counts per cell (spike target x reads-per-barcode target), made per READ - thinning reads
+//                        moves a barcode's counters - from a flag byte per covering record and one read draw per record and replicate.
 //   k_lod.inc            the limit-of-detection table of --lod: per barcode depth the root R's uniroot finds (mt_depths_lod.R), FP64.
 //
 // Data layout (include/smcounter_hip.h): ONE uint32 per pileup read (allele, quality, fragment start, read
@@ -80,6 +82,7 @@
 #include "k_spike.inc"         // --spikeAF, --spikeReps: listed SNVs written into one or B copies of a run's bases, NM and the mismatch bit with them
 #include "k_spike_indel.inc"   // --spikeIndels: listed insertions / deletions planted in a copy of a run: count, scan, scatter of the relocated records
 #include "k_spike_cells.inc"   // --spikeReps, --spikeDepth, --spikePhase: the achieved counts per variant or phase set, replicate and cell, without a copy
+#include "k_spike_rpb.inc"     // --spikeRpb: a flag byte per record and listed SNV; the achieved counts per variant, replicate and cell (target x read threshold)
 #include "k_lod.inc"           // --lod: the limit of detection per barcode depth (one lane per depth, Brent root search in FP64)
 #include "k_plan.inc"          // launch plan of a batch whose descriptors are in HBM (classify + fill)
 #include "host_abi.inc"        // the C ABI of include/smcounter_hip.h

@@ -149,7 +149,7 @@ READS_PER_BYTE = 6        # pileup reads a batch is sized for per compressed byt
 
 def iter_resident_batches(path: str, fasta, loci: Sequence[Tuple[str, str]], params, eng, max_reads: int = 128_000_000,
                           nthreads: int = 0, force_host: bool = False, all_planes: bool = True, sampler: str = "reference",
-                          sampler_seed: int = 0, ds_rules: Sequence[DsRule] = None):
+                          sampler_seed: int = 0, ds_rules: Sequence[DsRule] = None, close_tables: bool = True):
     """BAM -> `ResidentBatch` chunks: same loci per chunk as bamio.iter_device_batches_native, planes built on the GPU.
     `ds_rules` (--dsMT): every run is decoded and uploaded once and built K + 1 times - at full depth and, through
     smc_select_alignments, for the kept barcodes of every rule (called with that rule's params); each item is then
@@ -328,7 +328,11 @@ def iter_resident_batches(path: str, fasta, loci: Sequence[Tuple[str, str]], par
                 yield first, [rb] + [d.batch(rb) for d in ds]
     finally:
         bam.close()
-        close_rules(ds_rules)            # (--dsRpbSampler philox: the file-wide table in HBM - on the last batch, or on an error)
+        # (--dsRpbSampler philox: the file-wide table in HBM - on the last batch, or on an error; `close_tables` False: the caller owns
+        # the rules' tables and closes them itself - the command line, whose replicate stage of --spikeRpb reads the table behind the
+        # last batch)
+        if close_tables:
+            close_rules(ds_rules)
 
 
 class _DsBatch(object):
@@ -377,6 +381,29 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
     for rule in rules:
         if rule.spike is not None:
             users[(id(rule.spike), rule.af)] = users.get((id(rule.spike), rule.af), 0) + 1
+
+    def read_idents(rule):
+        # (--dsRpb, --spikeRpb: the kept read names, by read-name id - an id must stand for one full name, or the rule cannot be applied)
+        nonlocal p_idents
+        if p_idents is None:
+            p_idents = pair_idents_or_refuse(bam, A, "--spikeRpb" if rule.spike_rpb_cell else "--dsRpb", chrom, lo, nl)
+        return p_idents
+
+    def read_mask(rule):
+        # (--dsRpbSampler philox: the masks of every target from the file-wide table, one launch per run; the --dsGrid cells over
+        # the same table: one launch more) -> the device address of the rule's mask
+        # (--spikeRpb: the T cells of one r keep the same names - one mask serves them)
+        key = (id(rule.groups), rule.grid)
+        same = lambda r: (r.thr, r.bc_thr)
+        if key not in d_masks:
+            first = {}
+            for r in rules:
+                if r.groups is rule.groups and r.grid == rule.grid:
+                    first.setdefault(same(r), r)
+            buf, n_words, index = _run_read_masks(eng, rule.groups, list(first.values()), read_idents(rule), chrom, lo, nl)
+            d_masks[key] = (buf, n_words, {k: index[id(r)] for k, r in first.items()})
+        buf, n_words, index = d_masks[key]
+        return buf.data_ptr() + 4 * n_words * index[same(rule)]
     try:
         for rule, d in zip(rules, ds):
             if not nl:
@@ -398,7 +425,11 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
                         spiked_of[key], _ = spike_copy(eng, up, A, rule.spike, chrom, var, idents, rule.seed, rule.params.mismatchThr,
                                                        mism[0], mism[1])
                 spiked = spiked_of[key]
-                if rule.spike_cell:
+                if rule.spike_rpb_cell:
+                    # (--spikeRpb: the philox read selection at r over the target's copy, or over the run's own arrays where nothing
+                    # was spiked - the masks of every cell of the table from one launch: spiking changes no name)
+                    sel, counts, d_orig = select_run(eng, spiked or up, A, lo, d_mask=read_mask(rule), level="read")
+                elif rule.spike_cell:
                     # (--spikeDepth: the --dsMT philox selection at f over the target's copy - the one spiked above for the target's
                     # own build -, or over the run's own arrays where nothing was spiked)
                     if idents is None:
@@ -407,23 +438,10 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
                 else:
                     sel, counts, d_orig = spiked or up, A, None
             elif rule.level == "read":
-                # (--dsRpb: the kept read names, by read-name id - an id must stand for one full name, or the rule cannot be applied)
-                if p_idents is None:
-                    p_idents, shared = bam.pair_idents(A["n_pair"])
-                    if shared:
-                        raise bamio.BamError("--dsRpb: the run %s:%d-%d has a read id (read name without its last field) shared by two "
-                                             "different read names: ds.reads.withinMT.py keeps whole names, the decoder's ids cannot tell "
-                                             "them apart" % (chrom, lo + 1, lo + nl))
                 if rule.groups is not None:
-                    # (--dsRpbSampler philox: the masks of every target from the file-wide table, one launch per run; the --dsGrid
-                    # cells over the same table: one launch more)
-                    key = (id(rule.groups), rule.grid)
-                    if key not in d_masks:
-                        d_masks[key] = _run_read_masks(eng, rule.groups, [r for r in rules if r.groups is rule.groups and r.grid == rule.grid],
-                                                       p_idents, chrom, lo, nl)
-                    buf, n_words, index = d_masks[key]
-                    sel, counts, d_orig = select_run(eng, up, A, lo, d_mask=buf.data_ptr() + 4 * n_words * index[id(rule)], level="read")
+                    sel, counts, d_orig = select_run(eng, up, A, lo, d_mask=read_mask(rule), level="read")
                 else:
+                    read_idents(rule)
                     if rule.kept_idents is not None:
                         mask = np.isin(p_idents, rule.kept_idents)
                     else:
@@ -521,6 +539,17 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
         d.tables += tb
         d.slots += ns_k
     return True
+
+
+def pair_idents_or_refuse(bam, A, flag: str, chrom: str, lo: int, nl: int) -> np.ndarray:
+    """The identity of every read-name id of the run `A` that `bam` decoded last (bamio.NativeBam.pair_idents).  BamError: a read id
+    stands for two different read names - a rule that keeps whole names (`flag`: --dsRpb, --spikeRpb) cannot be applied by id."""
+    p_idents, shared = bam.pair_idents(A["n_pair"])
+    if shared:
+        raise bamio.BamError("%s: the run %s:%d-%d has a read id (read name without its last field) shared by two "
+                             "different read names: ds.reads.withinMT.py keeps whole names, the decoder's ids cannot tell "
+                             "them apart" % (flag, chrom, lo + 1, lo + nl))
+    return p_idents
 
 
 def _run_read_masks(eng, groups, rules, p_idents, chrom, lo, nl):
@@ -759,6 +788,9 @@ class DsRule:
     # into a copy of every run whose records span one (spike_run), at the threshold of `af`
     # (--spikeDepth) a cell: `spike` and `af` of its target beside `frac` f and `bc_thr` = the --dsMT draw's threshold at f: the spiked
     # copy of the target, then the philox selection at f with the same `seed`
+    # (--spikeRpb) a cell: `spike` and `af` of its target beside level "read", `target` r, `prob_keep`, `groups` (the file-wide table of
+    # the UNSPIKED file: spiking changes no name) and `thr`: the spiked copy of the target, then the philox read selection at r with the
+    # same `seed`
     spike: object = None
 
     @property
@@ -766,7 +798,13 @@ class DsRule:
         return self.spike is not None and self.bc_thr is not None
 
     @property
+    def spike_rpb_cell(self) -> bool:
+        return self.spike is not None and self.level == "read"
+
+    @property
     def flag(self) -> str:
+        if self.spike_rpb_cell:
+            return "--spikeRpb"
         if self.spike is not None:
             return "--spikeDepth" if self.spike_cell else "--spikeAF"
         if self.depth is not None:
@@ -781,6 +819,8 @@ class DsRule:
 
     @property
     def label(self) -> str:
+        if self.spike_rpb_cell:
+            return "spiked allele fraction %g x target %g" % (self.af, self.target)
         if self.spike_cell:
             return "spiked allele fraction %g x fraction %g" % (self.af, self.frac)
         if self.spike is not None:
@@ -1005,12 +1045,14 @@ def read_threshold(prob: float) -> int:
     return min(1 << 32, int(np.floor(prob * 4294967296.0)))
 
 
-def philox_read_rules(path: str, targets, params_list, seed: int, eng, chunk: int = NAME_KEY_CHUNK, nthreads: int = 0):
+def philox_read_rules(path: str, targets, params_list, seed: int, eng, chunk: int = NAME_KEY_CHUNK, nthreads: int = 0, flag: str = None):
     """DsRules of --dsRpb --dsRpbSampler philox: the whole file's placed records streamed (bamio.NativeBam.name_keys, `chunk` records
     at a time) into one ReadGroups table in HBM, its counters back on the host, probKeep per target from them in double exactly as
     ds.reads.withinMT.py:58 computes it; a name is kept when it is its barcode's first or its philox draw falls below
     floor(probKeep x 2^32) - NOT the reference's sample.  The rules share the table (rule.groups); iter_resident_batches frees it when
-    it ends.  ValueError: a hash collision (two texts behind one identity), or a file without a barcode of two or more names."""
+    it ends.  ValueError: a hash collision (two texts behind one identity), or a file without a barcode of two or more names.
+    `flag` (--spikeRpb): the flag the refusals name in place of --dsRpb / --dsRpbSampler philox - its cells have this sampler only, so
+    the advice to use the reference sampler is left out."""
     groups = ReadGroups(eng)
     try:
         bam = bamio.NativeBam(path)
@@ -1026,14 +1068,15 @@ def philox_read_rules(path: str, targets, params_list, seed: int, eng, chunk: in
                                    (RG_BARCODE_COLLISION, "two barcodes share a 64-bit identity"),
                                    (RG_FULL, "the table is full"), (RG_RESERVED, "a name or barcode hashes to the reserved identity 0"))
                     if st & b]
-            raise ValueError("--dsRpbSampler philox: %s: %s; the philox read sampler refuses the file (use --dsRpbSampler reference)"
-                             % (path, ", ".join(what) or "status %#x" % st))
+            raise ValueError("%s: %s: %s; the philox read sampler refuses the file%s"
+                             % (flag or "--dsRpbSampler philox", path, ", ".join(what) or "status %#x" % st,
+                                "" if flag else " (use --dsRpbSampler reference)"))
         one, multi, multi_names = c["one"], c["multi"], c["multi_names"]
         rules = []
         for r, P in zip(targets, params_list):
             if multi_names == multi:
-                raise ValueError("--dsRpb %g: %s has no barcode with more than one read name, so ds.reads.withinMT.py's probKeep "
-                                 "(:58) is not defined (it divides by zero)" % (r, path))
+                raise ValueError("%s %g: %s has no barcode with more than one read name, so ds.reads.withinMT.py's probKeep "
+                                 "(:58) is not defined (it divides by zero)" % (flag or "--dsRpb", r, path))
             prob = 1.0 * (float(r) - 1.0) * (one + multi) / (multi_names - multi)
             rules.append(DsRule(1.0, P, kept=None, seed=int(seed), level="read", target=float(r), prob_keep=prob,
                                 n_names=c["names"], groups=groups, thr=read_threshold(prob)))
@@ -1595,7 +1638,8 @@ def copy_allele_key(spiked: RunOnDevice, A, decoder_key):
 
 
 def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng, nthreads: int = 0, max_reads: int = 128_000_000,
-                keep: dict = None, keep_bytes: int = None, depth: dict = None, phase: dict = None, indel_counters: bool = False):
+                keep: dict = None, keep_bytes: int = None, depth: dict = None, phase: dict = None, indel_counters: bool = False,
+                rpb: dict = None):
     """DsRules of --spikeAF, one per target, and the pre-pass: only the runs around the listed loci are decoded (as ds_af_sets groups
     them); smc_allele_carriers gives N and V0 of every variant, then per target smc_spike_alleles writes the spiked copy and
     smc_allele_carriers on it gives V1.  The kernel's statistics are checked against the host's restatement of the draws: the records
@@ -1627,16 +1671,50 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     insertions and deletions, every record of SpikeSet carries its `lead`) the joint rows hold four counters per member and the joint
     numbers come from smc_spike_indel_phase_counts; the second count is the same AND of smc_allele_carriers' bits, INS / DEL keys
     included.  ValueError, before anything is spiked: a run with a record at which the
-    16-bit limits of the rewrite could bind (spike_indel_limits) - the counters would depend on the other variants' draws."""
+    16-bit limits of the rewrite could bind (spike_indel_limits) - the counters would depend on the other variants' draws.
+    `rpb` (--spikeRpb: dict with "targets", the reads-per-barcode targets, and the "params" of the T x Rr cells, targets outer; SNV
+    lists only): philox_read_rules builds the file-wide table of the UNSPIKED file once; per run of the pre-pass smc_spike_read_bits
+    gives a flag byte per record and listed SNV, the first names come from the table at threshold 0 and the covering records of every
+    variant become a CSR (spike_rpb_records) - kept in keep["records"] for the replicate stage; one smc_spike_rpb_counts call with
+    this seed gives "counts", per variant and cell dict(N, V0, S, READS, V1) over the reads the cell keeps, and "rules" gets the
+    cells' DsRules (level "read" over the shared table).  Every cell's (N, V0, V1) is also counted a second way - select_run by
+    read mask over the spiked copy of t (over the run itself for V0), then smc_allele_carriers on the selection - and a difference
+    raises RuntimeError.  ValueError / BamError: what --dsRpbSampler philox refuses."""
     from .tools import ds_allele_fraction as af
     from .tools import spike_variants as sv
     af.unique_idents(bamio.placed_barcodes(path), path)
     nthreads = nthreads or bamio.host_threads()
+    if rpb is not None:
+        if depth is not None or phase is not None or indel_counters or any(v.kind != af.SNV for v in variants):
+            raise ValueError("--spikeRpb: cells of barcode depths, phase sets or indel spike-ins are not built")
+        # (the file-wide table of the UNSPIKED file serves every cell and replicate: spiking changes no name, barcode or record count)
+        read_rules = philox_read_rules(path, list(rpb["targets"]), [params_list[0]] * len(rpb["targets"]), seed, eng, nthreads=nthreads,
+                                       flag="--spikeRpb")
+        try:
+            return _spike_rules(path=path, fasta=fasta, variants=variants, targets=targets, params_list=params_list, seed=seed, eng=eng,
+                                nthreads=nthreads, max_reads=max_reads, keep=keep, keep_bytes=keep_bytes, depth=depth, phase=phase,
+                                indel_counters=indel_counters, rpb=rpb, read_rules=read_rules)
+        except BaseException:
+            close_rules(read_rules)
+            raise
+    return _spike_rules(path=path, fasta=fasta, variants=variants, targets=targets, params_list=params_list, seed=seed, eng=eng,
+                        nthreads=nthreads, max_reads=max_reads, keep=keep, keep_bytes=keep_bytes, depth=depth, phase=phase,
+                        indel_counters=indel_counters, rpb=None, read_rules=None)
+
+
+def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthreads, max_reads, keep, keep_bytes, depth, phase,
+                 indel_counters, rpb, read_rules):
+    """spike_rules' body; `read_rules` (--spikeRpb): philox_read_rules' rules of the reads-per-barcode targets, whose table the caller
+    closes when this raises."""
+    from .tools import ds_allele_fraction as af
+    from .tools import spike_variants as sv
     spikes = SpikeSet(variants, indels=indel_counters)
     P = params_list[0]
     rows = [[None] * len(variants) for _ in targets]
     psets = list(phase["sets"]) if phase is not None else []
-    want_counters = keep is not None or depth is not None or bool(psets)
+    want_counters = keep is not None or depth is not None or bool(psets) or rpb is not None
+    records = [None] * len(variants)                   # (--spikeRpb) per variant spike_rpb_records' CSR of its covering records
+    second_rpb = {}                                    # (--spikeRpb) (variant, target index, r index) -> [N', V0', V1'] counted on selections
     bits = {}                        # (--spikePhase) variant -> (identities that cover it, that carry it before, per target after)
     covers, counters = [None] * len(variants), [None] * len(variants)
     if keep is not None:
@@ -1656,7 +1734,7 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
             own = bamio.NativeBam(path) if keep is not None else None
             dec = own or bam
             held = False
-            up = None
+            up = read_masks = None                     # (--spikeRpb: read_masks, _run_read_masks' of this run while the second count needs them)
             try:
                 A = dec.alignments_run(v0.chrom, lo, hi, max_reads, P, nthreads)
                 nl = int(A["nl"])
@@ -1686,11 +1764,36 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                     for r, k in enumerate(group):
                         for t in range(len(targets)):
                             second[(k, t, f)] = [None, int(car_f[r].sum()), None]
+                if rpb is not None:
+                    p_idents = pair_idents_or_refuse(dec, A, "--spikeRpb", v0.chrom, lo, nl)
+                    read_masks = _run_read_masks(eng, read_rules[0].groups, read_rules, p_idents, v0.chrom, lo, nl)
+
+                def read_selected(run, r):
+                    # (the cells' second count: the read selection at r over `run`, then smc_allele_carriers on it -> (N', carriers) per variant)
+                    sel, sel_counts, d_orig = select_run(eng, run, A, lo, d_mask=read_masks[0].data_ptr() + 4 * read_masks[1] * r, level="read")
+                    try:
+                        cov_r, car_r, _ = allele_carriers_run(eng, sel, sel_counts, lo, var, ins)
+                    finally:
+                        sel.free(shared=False); d_orig.free()
+                    return cov_r.sum(axis=1), car_r.sum(axis=1)
+                for r in range(len(read_rules or ())):
+                    n_r, car_r = read_selected(up, r)
+                    for x, k in enumerate(group):
+                        for t in range(len(targets)):
+                            second_rpb[(k, t, r)] = [int(n_r[x]), int(car_r[x]), None]
                 for t, target in enumerate(targets):
                     svar, sorder = spikes.chrom_variants(v0.chrom, target)
                     spiked, stats = spike_copy(eng, up, A, spikes, v0.chrom, svar, idents, seed, P.mismatchThr, nm, n_indel)
                     try:
                         cov1, car1, cnt1 = allele_carriers_run(eng, spiked, A, lo, var, ins, counts=True)
+                        for r in range(len(read_rules or ())):
+                            n_r, car_r = read_selected(spiked, r)
+                            for x, k in enumerate(group):
+                                if second_rpb[(k, t, r)][0] != int(n_r[x]):
+                                    raise RuntimeError("--spikeRpb: %s:%d at %g x target %g: the read selection keeps %d covering barcodes of "
+                                                       "the run and %d of its spiked copy" % (variants[k].chrom, variants[k].pos, target,
+                                                                                             rpb["targets"][r], second_rpb[(k, t, r)][0], int(n_r[x])))
+                                second_rpb[(k, t, r)][2] = int(car_r[x])
                         for f, frac in enumerate(fracs):
                             sel, sel_counts, d_orig = select_run(eng, spiked, A, lo, idents=idents, frac=frac, seed=seed)
                             try:
@@ -1738,6 +1841,22 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                             # (what the rewrite changes: an SNV's single-letter reads - all of which then show ALT -, an indel's eligible records)
                             cols.append(cols[2] if variants[k].kind == af.SNV else touch[sorder.index(k), :len(idents)][c])
                         counters[k] = np.stack(cols, axis=1).astype(np.uint32)
+                if rpb is not None:
+                    # (a flag byte per record and listed SNV, the first names from the table at threshold 0 - the first mask of a launch
+                    # with that one threshold -, then the CSR of every variant's covering records)
+                    read_masks[0].free()
+                    read_masks = None
+                    read_bits = spike_read_bits(eng, up, A, lo, var)
+                    first = run_first_names(eng, read_rules[0].groups, p_idents, v0.chrom, lo, nl)
+                    for r, k in enumerate(group):
+                        gids = np.flatnonzero(cov[r][:len(idents)])
+                        records[k] = spike_rpb_records(A, read_bits[r], gids, p_idents, first)
+                        sums = np.stack([np.add.reduceat(((records[k][2] >> s) & 1).astype(np.int64), records[k][0][:-1].astype(np.int64))
+                                         if len(gids) else np.zeros(0, np.int64) for s in (1, 2)], axis=1)
+                        if not np.array_equal(np.diff(records[k][0].astype(np.int64)), counters[k][:, 0]) or \
+                                not np.array_equal(sums, counters[k][:, 1:3]):
+                            raise RuntimeError("--spikeRpb: %s:%d: the records' bits do not sum to the pre-pass's counters" %
+                                               (variants[k].chrom, variants[k].pos))
                 if keep is not None:
                     size = sum(int(A[x].nbytes) for x in ("aln", "cig", "bq", "loc"))
                     held = size + sum(r.nbytes for r in keep["runs"]) <= (AF_KEEP_BYTES if keep_bytes is None else keep_bytes)
@@ -1749,6 +1868,8 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                     free_af_runs(keep["runs"])
                 raise
             finally:
+                if read_masks is not None:
+                    read_masks[0].free()
                 if not held:
                     if up is not None:
                         up.free()
@@ -1758,6 +1879,28 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     finally:
         bam.close()
     rules = [DsRule(1.0, Pt, seed=int(seed), af=float(t), spike=spikes) for t, Pt in zip(targets, params_list)]
+    if rpb is not None:
+        try:
+            rthr = [r.thr for r in read_rules]
+            got = spike_rpb_counts(eng, spikes.lead_pos, covers, records, [int(seed) & 0xFFFFFFFFFFFFFFFF], [sv.threshold(t) for t in targets],
+                                   rthr)[:, 0]
+            for (k, t, r), mine in second_rpb.items():
+                if [int(got[k, t, r, c]) for c in (0, 1, 4)] != mine:
+                    v = variants[k]
+                    raise RuntimeError("--spikeRpb: %s:%d at %g x target %g: the counts call says (N, V0, V1) = %r, the selection of the "
+                                       "spiked copy %r" % (v.chrom, v.pos, targets[t], rpb["targets"][r],
+                                                           [int(got[k, t, r, c]) for c in (0, 1, 4)], mine))
+        except BaseException:
+            if keep is not None:
+                free_af_runs(keep["runs"])
+            raise
+        names = ("N", "V0", "S", "READS", "V1")
+        rpb["counts"] = [[dict(zip(names, (int(x) for x in got[k, t, r]))) for t in range(len(targets)) for r in range(len(read_rules))]
+                         for k in range(len(variants))]
+        rpb["rules"] = [dataclasses.replace(read_rules[r], params=Pc, af=float(t), spike=spikes)
+                        for (t, r), Pc in zip(((t, r) for t in targets for r in range(len(read_rules))), rpb["params"])]
+        if keep is not None:
+            keep["records"] = records
     if depth is not None:
         try:
             got = (spike_indel_counts if indel_counters else spike_depth_counts)(
@@ -2145,6 +2288,89 @@ def spike_indel_counts(eng, positions, covers, counters, seeds, thresholds, dept
                                                       0 if dthr is None else len(dthr), d_out, ctypes.c_void_p(0)))
 
 
+SPB_COVERS, SPB_ALT, SPB_SINGLE, SPB_FIRST = 1, 2, 4, 1      # k_spike_rpb.inc: smc_spike_read_bits' bits; bit 0 of a record's flag byte
+
+
+def spike_read_bits(eng, up: RunOnDevice, A, lo: int, var: np.ndarray) -> np.ndarray:
+    """smc_spike_read_bits over the run `up` (A: its host arrays) -> uint8 [n_var, n_aln]: per listed SNV (af_run_variants' records) and
+    alignment bit 0 = the record covers the position, bit 1 = it shows ALT as it is, bit 2 = its allele key there is a single letter."""
+    from .engine import DevBuf
+    n_var, n = len(var), up.n_aln
+    if not n_var or not n:
+        return np.zeros((n_var, n), np.uint8)
+    var = np.ascontiguousarray(var, abi.AF_VARIANT_DTYPE)
+    d_var = DevBuf(eng, var.nbytes + 256).upload(var.view(np.uint8).reshape(-1))
+    d_out = DevBuf(eng, n_var * n + 256)
+    try:
+        _lib.check(eng.L.smc_spike_read_bits(eng.ctx, up.aln.data_ptr(), n, up.cig.data_ptr(), len(A["cig"]), up.bq.data_ptr(), len(A["bq"]) // 2,
+                                             up.loc.data_ptr(), int(A["nl"]), int(lo), d_var.data_ptr(), var.ctypes.data, n_var,
+                                             d_out.data_ptr(), ctypes.c_void_p(0)), "smc_spike_read_bits")
+        return d_out.download(np.uint8, n_var * n).reshape(n_var, n)                      # (the default stream: behind the kernel)
+    finally:
+        d_var.free(); d_out.free()
+
+
+def spike_rpb_records(A, bits: np.ndarray, gids: np.ndarray, p_idents: np.ndarray, first: np.ndarray):
+    """The CSR smc_spike_rpb_counts takes for ONE listed variant of run `A`: `bits` its row of spike_read_bits, `gids` the run-wide ids
+    of its covering barcodes (ascending), `p_idents` the identity of every read-name id of the run, `first` (bool per read-name id)
+    whether the name is its barcode's first, file-wide -> (uint32 [len(gids) + 1] offsets, uint64 name identities, uint8 flags), a
+    barcode's records in file order."""
+    aln = A["aln"]
+    idx = np.flatnonzero(bits & SPB_COVERS)
+    bc = aln["bc_gid"][idx].astype(np.int64)
+    idx = idx[np.argsort(bc, kind="stable")]
+    per = np.bincount(bc, minlength=int(A["n_bc"]))
+    gids = np.asarray(gids, np.int64)
+    if int(per[gids].sum()) != len(idx):
+        raise ValueError("spike_rpb_records: %d covering records, %d of them in the %d covering barcodes" % (len(idx), int(per[gids].sum()), len(gids)))
+    off = np.zeros(len(gids) + 1, np.uint32)
+    off[1:] = np.cumsum(per[gids])
+    pair = aln["pair_gid"][idx]
+    flag = (bits[idx] & (SPB_ALT | SPB_SINGLE)) | np.where(np.asarray(first, bool)[pair], SPB_FIRST, 0).astype(np.uint8)
+    return off, np.ascontiguousarray(np.asarray(p_idents, np.uint64)[pair]), flag.astype(np.uint8)
+
+
+def run_first_names(eng, groups: ReadGroups, p_idents, chrom: str = "?", lo: int = 0, nl: int = 0) -> np.ndarray:
+    """bool per read-name id of a run (`p_idents`: their identities): the name is its barcode's first in the file - the names
+    ReadGroups.masks keeps at threshold 0, where no draw passes (the seed does not matter)."""
+    rule = DsRule(1.0, None, seed=0, level="read", groups=groups, thr=0)
+    buf, n_words, _ = _run_read_masks(eng, groups, [rule], p_idents, chrom, lo, nl)
+    try:
+        words = buf.download(np.uint32, max(1, n_words))
+    finally:
+        buf.free()
+    return np.unpackbits(words.view(np.uint8), bitorder="little")[:len(p_idents)].astype(bool)
+
+
+def spike_rpb_counts(eng, positions, covers, records, seeds, thresholds, read_thresholds) -> np.ndarray:
+    """smc_spike_rpb_counts -> uint32 [V, R, T, Rr, 5] = (N', V0', S', READS', V1') of every variant, replicate and cell.  positions,
+    covers, seeds, thresholds: spike_rep_counts'; records[v]: spike_rpb_records' (offsets [len(covers[v]) + 1], name identities, flag
+    bytes) of variant v; read_thresholds: read_threshold(probKeep) per reads-per-barcode target."""
+    n_var = len(covers)
+    off = np.zeros(n_var + 1, np.uint32)
+    off[1:] = np.cumsum([len(c) for c in covers])
+    ident = np.concatenate([np.asarray(c, np.uint64) for c in covers]) if n_var else np.zeros(0, np.uint64)
+    rec_off, base = [np.zeros(1, np.int64)], 0
+    for v, (c, (o, names, flags)) in enumerate(zip(covers, records)):
+        o = np.asarray(o, np.int64)
+        if len(o) != len(c) + 1 or len(names) != len(flags) or (len(o) and (int(o[0]) != 0 or int(o[-1]) != len(names))):
+            raise ValueError("spike_rpb_counts: variant %d: %d covering barcodes, %d offsets over %d names and %d flags" %
+                             (v, len(c), len(o), len(names), len(flags)))
+        rec_off.append(o[1:] + base)
+        base += len(names)
+    rec_off = np.concatenate(rec_off).astype(np.uint32)
+    name = np.concatenate([np.asarray(r[1], np.uint64) for r in records]) if n_var else np.zeros(0, np.uint64)
+    flag = np.concatenate([np.asarray(r[2], np.uint8) for r in records]) if n_var else np.zeros(0, np.uint8)
+    pos = np.array([int(p) & 0xFFFFFFFF for p in positions], np.uint32)
+    seeds = np.ascontiguousarray(seeds, np.uint64)
+    thr, rthr = np.ascontiguousarray(thresholds, np.uint64), np.ascontiguousarray(read_thresholds, np.uint64)
+    return _spike_counts_call(
+        eng, "smc_spike_rpb_counts", [ident, off, rec_off, name, flag, pos, seeds], (n_var, len(seeds), len(thr), len(rthr), 5),
+        lambda d, d_out: eng.L.smc_spike_rpb_counts(eng.ctx, d[0], d[1], off.ctypes.data, d[2], rec_off.ctypes.data, d[3], d[4], len(name),
+                                                    d[5], n_var, d[6], len(seeds), thr.ctypes.data, len(thr), rthr.ctypes.data, len(rthr),
+                                                    d_out, ctypes.c_void_p(0)))
+
+
 def spike_joint(sets, covers, counters):
     """Per phase set (tools.spike_variants.PhaseSet) -> (uint64 [n]: the identities of the barcodes that cover EVERY member, ascending;
     uint32 [n, M, 3]: their (reads, alt0, single) at each member, in the set's order).  covers[v] / counters[v]: per listed variant
@@ -2317,7 +2543,7 @@ def spike_indel_run_copies(eng, up: RunOnDevice, A, var: np.ndarray, ins: np.nda
 
 
 def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed, bits,
-                    cells=(), indel: dict = None):
+                    cells=(), indel: dict = None, read_cells: dict = None):
     """`len(part_seeds)` spiked copies of a kept run at one target from one smc_spike_alleles_reps call, each built behind the other
     into one device batch (as _af_rep_call appends its selections) and the batch called with one plan -> (per copy the listed loci's
     raw rows, in the order of run.group), or NARROW.  var_at[g]: where variant run.group[g] stands in `svar`; want_reads[c][g]: the
@@ -2328,7 +2554,11 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
     `indel` (--spikeIndelReps: dict(ins: the chromosome's pool of inserted letters, want: per copy and variant of run.group the counts
     call's (N, V1), want_cells: per cell the same (N', V1'))): the copies come from one smc_spike_indels_reps call, each with records,
     CIGAR pool and pair pool of its own; a relocated record's allele texts come from the copy (copy_allele_key); and beside READS every
-    copy's N and V1 - smc_allele_carriers on the copy, on its selection for a cell - must equal the counts call's."""
+    copy's N and V1 - smc_allele_carriers on the copy, on its selection for a cell - must equal the counts call's.
+    `read_cells` (--spikeRpb: dict(params: the VcParams of the target's cells, one per reads-per-barcode target, masks: per copy the
+    address of its first keep mask - ReadGroups.masks with the copy's seed, one mask per target -, n_words: words per mask)): every
+    copy is also selected per r by read name (select_run, level "read") and built; a cell's selections share one batch and one plan
+    -> (the copies' rows, per cell the same), or NARROW."""
     from . import vc
     A, up, lo, nl, chrom = run.A, run.up, run.lo, run.nl, run.chrom
     B = len(part_seeds)
@@ -2344,7 +2574,7 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
         copies = [RunOnDevice(_BufView(made["aln"], c * sa), _BufView(made["cig"], c * sc), _BufView(made["bq"], c * sb), up.loc, up.ref, up.n_aln,
                               up.loc_host, pairs_used=int(made["totals"][c, 0])) for c in range(B)]
         af_var, af_ins = af_run_variants([variants[k] for k in run.group], chrom, lo, fasta)
-    flag = "--spikeDepth" if cells else "--spikeReps"
+    flag = "--spikeRpb" if read_cells else "--spikeDepth" if cells else "--spikeReps"
 
     def check_carriers(c, sel, counts, want, what):
         """(N, V1) of every variant of the run on copy c (or its selection) by smc_allele_carriers against the counts call's."""
@@ -2356,14 +2586,37 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
                 raise RuntimeError("--spikeIndelReps: seed %d at %s:%d%s: the copy holds (N, V1) = %r, the counts call says %r" %
                                    (int(part_seeds[c]), v.chrom, v.pos, what, mine, tuple(int(x) for x in want[g])))
 
-    def batch_rows(Pb, frac):
-        """The B copies (`frac` None) or their selections at `frac`, built into one batch and called with one plan at params `Pb`."""
+    def batch_rows(Pb, frac, read=None):
+        """The B copies (`frac` None) or their selections at `frac` - `read` r: by read name at the r-th reads-per-barcode target -, built
+        into one batch and called with one plan at params `Pb`."""
         d = _DsBatch(eng, cap, bits, False)
         try:
             cp = abi.c_params(Pb)
             n_loc = 0
             for c in range(B):
-                if frac is None:
+                bc_name, bc_idents = run.bam.barcode_name, lambda n: run.idents
+                if read is not None:
+                    sel, counts, d_orig = select_run(eng, copies[c], A, lo, d_mask=read_cells["masks"][c] + 4 * read_cells["n_words"] * read,
+                                                     level="read")
+                    got = {}
+
+                    def orig_index(d_orig=d_orig, kept=sel.n_aln, got=got):
+                        if "orig" not in got:
+                            got["orig"] = d_orig.download(np.uint32, kept)
+                        return got["orig"]
+
+                    def allele_key(ai, qpos, indel, orig_index=orig_index):
+                        return run.bam.allele_key(int(orig_index()[int(ai)]), qpos, indel)
+
+                    def old_bc(orig_index=orig_index, got=got, bc=A["aln"]["bc_gid"]):
+                        # (the read level renumbers the kept barcodes by first kept appearance: as the main pass maps them back)
+                        if "old_bc" not in got:
+                            old = bc[orig_index()]
+                            got["old_bc"] = old[np.sort(np.unique(old, return_index=True)[1])]
+                        return got["old_bc"]
+                    bc_name = lambda g, old_bc=old_bc: run.bam.barcode_name(int(old_bc()[int(g)]))
+                    bc_idents = lambda n, old_bc=old_bc: run.idents[old_bc()]
+                elif frac is None:
                     # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch)
                     sel, counts, d_orig, allele_key = copies[c], A, None, run.bam.allele_key
                     if indel is not None:
@@ -2390,8 +2643,8 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
                             raise
                 try:
                     done = build_run(counts, eng.L, eng, cp, Pb, chrom, lo, fasta, run.run_ref, [d.words] + d.planes, d.uaux, d.slots,
-                                     d.slots + n_loc, cap, max_depth, allele_key, run.bam.barcode_name, sampler=sampler,
-                                     sampler_seed=sampler_seed, barcode_idents=lambda n: run.idents, uploaded=sel)
+                                     d.slots + n_loc, cap, max_depth, allele_key, bc_name, sampler=sampler,
+                                     sampler_seed=sampler_seed, barcode_idents=bc_idents, uploaded=sel)
                 finally:
                     if d_orig is not None:
                         sel.free(shared=False)
@@ -2429,11 +2682,15 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
                     raise RuntimeError("--spikeReps: seed %d at %s:%d: the rewrite touched %d records, the counts call says %d" %
                                        (int(part_seeds[c]), v.chrom, v.pos, int(stats[c, var_at[g], 0]), int(want_reads[c][g])))
         full = batch_rows(P, None)
-        if full == NARROW or not cells:
+        if full == NARROW or not (cells or read_cells):
             return full
         of_cell = []
         for frac, Pc in cells:
             of_cell.append(batch_rows(Pc, frac))
+            if of_cell[-1] == NARROW:
+                return NARROW
+        for r, Pc in enumerate(read_cells["params"] if read_cells else ()):
+            of_cell.append(batch_rows(Pc, None, r))
             if of_cell[-1] == NARROW:
                 return NARROW
         return full, of_cell
@@ -2443,7 +2700,8 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
 
 
 def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int, n_reps: int, eng, keep: dict, sampler: str = "reference",
-                     sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, depth: dict = None, phase: dict = None):
+                     sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, depth: dict = None, phase: dict = None,
+                     rpb: dict = None):
     """The replicate stage of --spikeReps.  Replicate j is --spikeAF with seed (seed + j) mod 2^64.  One smc_spike_rep_counts call
     gives (S, READS, V1) of every variant, replicate and target from what the pre-pass kept (spike_rules' `keep`) - no spiked copy is
     needed for them; then per kept run and target as many replicates as fit SPIKE_REP_BATCH_BYTES (and AF_REP_BATCH_SLOTS read
@@ -2458,7 +2716,11 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
     `phase` (--spikePhase: spike_rules' dict): the draws are the sets' (SpikeSet.lead_pos), and the result gets "phase_counts", uint32
     [G, R, T, 4] = (N_ALL, V0_ALL, S_ALL, V1_ALL) of every set, replicate and target from one smc_spike_phase_counts call, with
     `depth` also "phase_depth_counts", uint32 [G, R, T, F, 4], from a second (--spikeIndelPhase: smc_spike_indel_phase_counts, the
-    joint rows then hold four counters per member)."""
+    joint rows then hold four counters per member).
+    `rpb` (--spikeRpb: spike_rules' dict with "targets", the "params" of the T x Rr cells and their "rules"): one smc_spike_rpb_counts
+    call with all R seeds over the records the pre-pass kept (keep["records"]) gives "rpb_counts", uint32 [V, R, T, Rr, 5]; every copy
+    is also selected per r with the keep masks of ITS seed - one ReadGroups.masks call per seed and run - and built
+    (_spike_rep_call's `read_cells`): `rows` then also holds (variant index, T + t x Rr + r, replicate)."""
     import time
     from . import dsaf
     from .tools import spike_variants as sv
@@ -2489,6 +2751,11 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
             phase_counts = joint_counts(eng, lead, phase["joint"], seeds, thr, [1 << 32])[:, :, :, 0]
             if depth is not None:
                 phase_depth_counts = joint_counts(eng, lead, phase["joint"], seeds, thr, [frac_threshold(f) for f in depth["fracs"]])
+        rpb_counts, read_rules = None, []
+        if rpb is not None:
+            F = len(rpb["targets"])
+            read_rules = rpb["rules"][:F]
+            rpb_counts = spike_rpb_counts(eng, spikes.lead_pos, keep["covers"], keep["records"], seeds, thr, [r.thr for r in read_rules])
         times["counts"] = time.perf_counter() - t0
         for run in keep["runs"]:
             if run.A is None:
@@ -2513,40 +2780,67 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
                 per_copy = sum(spike_copy_strides(run.up.n_aln, len(run.A["bq"]) // 2))
             room = max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per_copy, AF_REP_BATCH_SLOTS // max(1, int(run.A["n_slots"]) + run.nl)))
             t0 = time.perf_counter()
-            for t in range(T):
-                P = params_list[t]
-                cells = [(depth["fracs"][f], depth["params"][t * F + f]) for f in range(F)]
-                for b in range(0, n_reps, room):
-                    js = list(range(b, min(n_reps, b + room)))
-                    want = [[int(counts[k, j, t, 1]) for k in run.group] for j in js]
-                    bits = 16 if (eng.word_bits == 16 and 0 <= P.minBQ <= 63) else 32
-                    args = (eng, run, svar, var_at, [seeds[j] for j in js], thr[t], want, P, fasta, variants, max_depth, sampler, sampler_seed)
-                    indel = None
-                    if four:
-                        n_cov = [len(keep["covers"][k]) for k in run.group]
-                        indel = dict(ins=spikes.ins[run.chrom], want=[[(n, int(counts[k, j, t, 2])) for k, n in zip(run.group, n_cov)] for j in js],
-                                     want_cells=[[[(int(depth_counts[k, j, t, f, 0]), int(depth_counts[k, j, t, f, 4])) for k in run.group]
-                                                  for j in js] for f in range(F)])
-                    out = _spike_rep_call(*args, bits, cells, indel)
-                    if out == NARROW:
-                        eng.word_bits = 32
-                        out = _spike_rep_call(*args, 32, cells, indel)
-                        times["rewrites"] += 1
-                    full, of_cell = out if cells else (out, [])
-                    for c, part in [(t, full)] + [(T + t * F + f, part) for f, part in enumerate(of_cell)]:
-                        for j, text in zip(js, part):
-                            for k, line in zip(run.group, text):
-                                rows[(k, c, j)] = line
-                    times["rewrites"] += 1
-                    times["builds"] += len(js) * (1 + F)
-                    times["batches"] += 1 + F
+            seed_masks = {}
+            try:
+                if rpb is not None:
+                    # (the keep masks of every reads-per-barcode target, per seed: one launch each over the run's read-name identities)
+                    p_idents = pair_idents_or_refuse(run.bam, run.A, "--spikeRpb", run.chrom, run.lo, run.nl)
+                    for j in range(n_reps):
+                        seed_masks[j] = _run_read_masks(eng, read_rules[0].groups, [dataclasses.replace(r, seed=seeds[j]) for r in read_rules],
+                                                        p_idents, run.chrom, run.lo, run.nl)
+                _spike_rep_targets(eng=eng, run=run, svar=svar, var_at=var_at, seeds=seeds, thr=thr, counts=counts, depth_counts=depth_counts,
+                                   params_list=params_list, fasta=fasta, variants=variants, max_depth=max_depth, sampler=sampler,
+                                   sampler_seed=sampler_seed, depth=depth, rpb=rpb, seed_masks=seed_masks, keep=keep, spikes=spikes,
+                                   four=four, room=room, n_reps=n_reps, rows=rows, times=times)
+            finally:
+                for buf, _, _ in seed_masks.values():
+                    buf.free()
             times["calls"] += time.perf_counter() - t0
             run.free()
     finally:
         free_af_runs(keep["runs"])
     times["stage"] = time.perf_counter() - t_start
     return dict(seeds=seeds, counts=counts, rows=rows, times=times, depth_counts=depth_counts, phase_counts=phase_counts,
-                phase_depth_counts=phase_depth_counts)
+                phase_depth_counts=phase_depth_counts, rpb_counts=rpb_counts)
+
+
+def _spike_rep_targets(*, eng, run, svar, var_at, seeds, thr, counts, depth_counts, params_list, fasta, variants, max_depth, sampler,
+                       sampler_seed, depth, rpb, seed_masks, keep, spikes, four, room, n_reps, rows, times):
+    """spike_replicates' calls for one kept run: per target as many replicates per _spike_rep_call as `room` allows; `rows` and `times`
+    are filled.  seed_masks[j] (--spikeRpb): _run_read_masks' of replicate j."""
+    T = len(params_list)
+    F = len(depth["fracs"]) if depth is not None else len(rpb["targets"]) if rpb is not None else 0
+    for t in range(T):
+        P = params_list[t]
+        cells = [(depth["fracs"][f], depth["params"][t * F + f]) for f in range(F)] if depth is not None else []
+        for b in range(0, n_reps, room):
+            js = list(range(b, min(n_reps, b + room)))
+            want = [[int(counts[k, j, t, 1]) for k in run.group] for j in js]
+            bits = 16 if (eng.word_bits == 16 and 0 <= P.minBQ <= 63) else 32
+            args = (eng, run, svar, var_at, [seeds[j] for j in js], thr[t], want, P, fasta, variants, max_depth, sampler, sampler_seed)
+            indel = None
+            if four:
+                n_cov = [len(keep["covers"][k]) for k in run.group]
+                indel = dict(ins=spikes.ins[run.chrom], want=[[(n, int(counts[k, j, t, 2])) for k, n in zip(run.group, n_cov)] for j in js],
+                             want_cells=[[[(int(depth_counts[k, j, t, f, 0]), int(depth_counts[k, j, t, f, 4])) for k in run.group]
+                                          for j in js] for f in range(F)])
+            read_cells = None
+            if rpb is not None:
+                read_cells = dict(params=rpb["params"][t * F:(t + 1) * F], masks=[seed_masks[j][0].data_ptr() for j in js],
+                                  n_words=seed_masks[js[0]][1])
+            out = _spike_rep_call(*args, bits, cells, indel, read_cells)
+            if out == NARROW:
+                eng.word_bits = 32
+                out = _spike_rep_call(*args, 32, cells, indel, read_cells)
+                times["rewrites"] += 1
+            full, of_cell = out if (cells or read_cells) else (out, [])
+            for c, part in [(t, full)] + [(T + t * F + f, part) for f, part in enumerate(of_cell)]:
+                for j, text in zip(js, part):
+                    for k, line in zip(run.group, text):
+                        rows[(k, c, j)] = line
+            times["rewrites"] += 1
+            times["builds"] += len(js) * (1 + F)
+            times["batches"] += 1 + F
 
 
 def _fnv64(text: str) -> int:

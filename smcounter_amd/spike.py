@@ -21,6 +21,10 @@ of --spikeReps / --spikeDepth, from the same writers.
 --spikeIndelPhase: phase sets whose members may be insertions and deletions (indel_phase; tools.spike_variants --phased --indels is
 the rule): the variants file is read as --spikePhase reads it, under the rules of --spikeIndels; the pages are --spikePhase's.
 
+--spikeRpb: the cells (target t, reads-per-barcode target r) of the spike-ins - the flag, the cells' prefixes and mtDepths (rpb_cells) -
+and the pages <outPrefix>.spikeAF.rpb.detection.txt, .replicates.txt, .sensitivity.txt and .curve.txt from the depth pages' writers,
+with RPB as their axis column (RPB_AXIS).
+
 The semantics are tools/spike_variants.py's (DESIGN.md "--spikeAF"); the rewrite on the GPU is csrc/k_spike.inc (smc_spike_alleles),
 the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the main pass are devplanes.spike_rules / spike_run.
 """
@@ -283,10 +287,28 @@ def write_curve(out_prefix: str, variants, targets, entries, lods=None) -> None:
                                 None if lods is None else float(lods[top][i])) + "\n")
 
 
-# ---- --spikeDepth
-DEPTH_DETECTION_HEADER = DETECTION_HEADER[:5] + ("FRACTION", "MTDEPTH") + DETECTION_HEADER[5:]
-DEPTH_REPLICATES_HEADER = DEPTH_DETECTION_HEADER[:7] + ("REP", "SEED") + DEPTH_DETECTION_HEADER[7:]
-DEPTH_SENSITIVITY_HEADER = SENSITIVITY_HEADER[:5] + ("FRACTION", "MTDEPTH") + SENSITIVITY_HEADER[5:] + ("N_MEAN",)
+# ---- --spikeDepth (and, with another axis, --spikeRpb)
+# the cells' second axis on the pages below: (the pages' infix, the axis column's name); the column's text is "%g" of the cell's value
+DEPTH_AXIS = ("depth", "FRACTION")
+RPB_AXIS = ("rpb", "RPB")
+
+
+def cell_detection_header(axis=DEPTH_AXIS):
+    return DETECTION_HEADER[:5] + (axis[1], "MTDEPTH") + DETECTION_HEADER[5:]
+
+
+def cell_replicates_header(axis=DEPTH_AXIS):
+    h = cell_detection_header(axis)
+    return h[:7] + ("REP", "SEED") + h[7:]
+
+
+def cell_sensitivity_header(axis=DEPTH_AXIS):
+    return SENSITIVITY_HEADER[:5] + (axis[1], "MTDEPTH") + SENSITIVITY_HEADER[5:] + ("N_MEAN",)
+
+
+DEPTH_DETECTION_HEADER = cell_detection_header()
+DEPTH_REPLICATES_HEADER = cell_replicates_header()
+DEPTH_SENSITIVITY_HEADER = cell_sensitivity_header()
 DEPTH_CURVE_HEADER = dsaf.CURVE_HEADER
 
 
@@ -343,8 +365,10 @@ def depth_sensitivity_line(v, target, frac, mt_depth, per, lod=None) -> str:
     return "\t".join(f)
 
 
-def depth_curve_header(targets, with_lod: bool = False):
-    return DEPTH_CURVE_HEADER + tuple("RATE@%g" % t for t in sorted(targets)) + ("T95",) + (("LOD",) if with_lod else ())
+def depth_curve_header(targets, with_lod: bool = False, axis=DEPTH_AXIS):
+    # (the curve's axis column is DEPTH for the barcode fractions - dsaf.CURVE_HEADER - and the axis's own name otherwise)
+    head = DEPTH_CURVE_HEADER if axis is DEPTH_AXIS else DEPTH_CURVE_HEADER[:4] + (axis[1],) + DEPTH_CURVE_HEADER[5:]
+    return head + tuple("RATE@%g" % t for t in sorted(targets)) + ("T95",) + (("LOD",) if with_lod else ())
 
 
 def depth_curve_line(v, depth, mt_depths, targets, per_target, lod=None) -> str:
@@ -363,14 +387,15 @@ def depth_curve_line(v, depth, mt_depths, targets, per_target, lod=None) -> str:
     return "\t".join(f)
 
 
-def write_depth_detection(out_prefix: str, variants, cells, counts, loc_index=None) -> None:
+def write_depth_detection(out_prefix: str, variants, cells, counts, loc_index=None, axis=DEPTH_AXIS) -> None:
     """<outPrefix>.spikeAF.depth.detection.txt: a header, then a line per listed variant and cell (targets outer, fractions inner).
     `cells`: per cell (target index, target, fraction, mtDepth, output prefix, that output's LODs by locus index or None);
-    counts[v][cell]: dict(N, V0, S, READS, V1), the cell's achieved numbers."""
+    counts[v][cell]: dict(N, V0, S, READS, V1), the cell's achieved numbers.  `axis` (RPB_AXIS: --spikeRpb): the page is
+    .spikeAF.<axis[0]>.detection.txt, the cells' third field stands under the column axis[1]."""
     read = [dsaf.read_output(c[4]) for c in cells]
     with_lod = any(c[5] is not None for c in cells)
-    with open(out_prefix + ".spikeAF.depth.detection.txt", "w") as fh:
-        fh.write("\t".join(DEPTH_DETECTION_HEADER + (("LOD",) if with_lod else ())) + "\n")
+    with open("%s.spikeAF.%s.detection.txt" % (out_prefix, axis[0]), "w") as fh:
+        fh.write("\t".join(cell_detection_header(axis) + (("LOD",) if with_lod else ())) + "\n")
         for i, v in enumerate(variants):
             key = (v.chrom, "%d" % v.pos)
             for c, ((_, target, frac, depth, _, lods), (rows, cut)) in enumerate(zip(cells, read)):
@@ -378,38 +403,38 @@ def write_depth_detection(out_prefix: str, variants, cells, counts, loc_index=No
                 fh.write(depth_detection_line(v, target, frac, depth, counts[i][c], rows.get(key), cut.get(key), lod) + "\n")
 
 
-def write_depth_replicates(out_prefix: str, variants, cells, seeds, entries) -> None:
+def write_depth_replicates(out_prefix: str, variants, cells, seeds, entries, axis=DEPTH_AXIS) -> None:
     """<outPrefix>.spikeAF.depth.replicates.txt: a line per listed variant, cell and replicate.  entries[(v, cell)]: per replicate
     (dict(N, V0, S, READS, V1), row fields or None, cut or None)."""
-    with open(out_prefix + ".spikeAF.depth.replicates.txt", "w") as fh:
-        fh.write("\t".join(DEPTH_REPLICATES_HEADER) + "\n")
+    with open("%s.spikeAF.%s.replicates.txt" % (out_prefix, axis[0]), "w") as fh:
+        fh.write("\t".join(cell_replicates_header(axis)) + "\n")
         for i, v in enumerate(variants):
             for c, (_, target, frac, depth, _, _) in enumerate(cells):
                 for j, (r, row, cut) in enumerate(entries[(i, c)]):
                     fh.write(depth_replicate_line(v, target, frac, depth, j, seeds[j], r, row, cut) + "\n")
 
 
-def write_depth_sensitivity(out_prefix: str, variants, cells, entries, loc_index=None) -> None:
+def write_depth_sensitivity(out_prefix: str, variants, cells, entries, loc_index=None, axis=DEPTH_AXIS) -> None:
     """<outPrefix>.spikeAF.depth.sensitivity.txt: a line per listed variant and cell; LOD: the locus's in the run's own output of the
     cell."""
     with_lod = any(c[5] is not None for c in cells)
-    with open(out_prefix + ".spikeAF.depth.sensitivity.txt", "w") as fh:
-        fh.write("\t".join(DEPTH_SENSITIVITY_HEADER + (("LOD",) if with_lod else ())) + "\n")
+    with open("%s.spikeAF.%s.sensitivity.txt" % (out_prefix, axis[0]), "w") as fh:
+        fh.write("\t".join(cell_sensitivity_header(axis) + (("LOD",) if with_lod else ())) + "\n")
         for i, v in enumerate(variants):
             for c, (_, target, frac, depth, _, lods) in enumerate(cells):
                 lod = float(lods[loc_index[(v.chrom, "%d" % v.pos)]]) if lods is not None else None
                 fh.write(depth_sensitivity_line(v, target, frac, depth, entries[(i, c)], lod) + "\n")
 
 
-def write_depth_curve(out_prefix: str, variants, targets, fracs, full, cells, full_entries, entries, loc_index=None) -> None:
+def write_depth_curve(out_prefix: str, variants, targets, fracs, full, cells, full_entries, entries, loc_index=None, axis=DEPTH_AXIS) -> None:
     """<outPrefix>.spikeAF.depth.curve.txt: a line per listed variant and barcode depth - `full` (the targets' own outputs) first, then
     every fraction.  `full`: per target (mtDepth, the LODs of its .spikeAF<t> output or None); full_entries[(v, t)] / entries[(v,
     cell)]: the replicates.  LOD: the locus's theoretical one at that depth, in the output of the LARGEST listed target there."""
     T, F = len(targets), len(fracs)
     top = max(range(T), key=lambda t: targets[t])
     with_lod = any(c[5] is not None for c in cells)
-    with open(out_prefix + ".spikeAF.depth.curve.txt", "w") as fh:
-        fh.write("\t".join(depth_curve_header(targets, with_lod)) + "\n")
+    with open("%s.spikeAF.%s.curve.txt" % (out_prefix, axis[0]), "w") as fh:
+        fh.write("\t".join(depth_curve_header(targets, with_lod, axis)) + "\n")
         for i, v in enumerate(variants):
             at = loc_index[(v.chrom, "%d" % v.pos)] if with_lod else None
             fh.write(depth_curve_line(v, None, [d for d, _ in full], targets, [full_entries[(i, t)] for t in range(T)],
@@ -418,6 +443,37 @@ def write_depth_curve(out_prefix: str, variants, targets, fracs, full, cells, fu
                 mine = [cells[t * F + k] for t in range(T)]
                 fh.write(depth_curve_line(v, f, [c[3] for c in mine], targets, [entries[(i, t * F + k)] for t in range(T)],
                                           float(mine[top][5][at]) if with_lod else None) + "\n")
+
+
+# ---- --spikeRpb
+RPB_NOT_WITH = ("spikeDepth", "spikePhase", "spikeIndels", "spikeIndelReps", "spikeIndelDepth", "spikeIndelPhase")
+
+
+def rpb_cells(args, spike_targets):
+    """--spikeRpb -> (reads-per-barcode targets, [(target index, t, r, mtDepth of the cell, output prefix)] for every --spikeAF target t
+    and every r, targets outer), or (None, []) without the flag.  A cell is called at its target's mtDepth (and at --rpb r).
+    SystemExit: without --spikeAF, text that is no list of numbers, a target <= 0 or listed twice, beyond MAX_CELLS cells, beside a
+    flag of RPB_NOT_WITH (the combination is not built)."""
+    text = getattr(args, "spikeRpb", None)
+    if text in (None, ""):
+        return None, []
+    if not spike_targets:
+        raise SystemExit("--spikeRpb thins the reads of the --spikeAF spike-ins: it needs --spikeAF")
+    for flag in RPB_NOT_WITH:
+        if getattr(args, flag, None) not in (None, "", False):
+            raise SystemExit("--spikeRpb cannot be combined with --%s in one run (the combination is not built)" % flag)
+    try:
+        rs = [float(x) for x in str(text).split(",") if x.strip()]
+    except ValueError:
+        raise SystemExit("--spikeRpb: comma-separated reads-per-barcode targets > 0 expected, got %r" % text)
+    if not rs or any(not (r > 0.0 and r < float("inf")) for r in rs):
+        raise SystemExit("--spikeRpb: every target must be a number > 0, got %r" % text)
+    if len(set("%g" % r for r in rs)) != len(rs):
+        raise SystemExit("--spikeRpb: a target is listed twice (the cells' files would share a name), got %r" % text)
+    if len(spike_targets) * len(rs) > MAX_CELLS:
+        raise SystemExit("--spikeRpb: %d targets x %d reads-per-barcode targets = %d cells, at most %d" %
+                         (len(spike_targets), len(rs), len(spike_targets) * len(rs), MAX_CELLS))
+    return rs, [(k, t, r, d, "%s.dsRpb%g" % (p, r)) for k, (t, d, p) in enumerate(spike_targets) for r in rs]
 
 
 # ---- --spikePhase

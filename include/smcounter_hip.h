@@ -820,6 +820,41 @@ int smc_spike_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32
                          const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
                          int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
                          int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out, void* stream);
+/* (ABI 11, additive: two entries more, the version number unchanged) --spikeIndelRpb: the cells (spike target t, reads-per-barcode
+ * target r) of the --spikeIndels spike-in.  The cell, the two draws and the kept records are smc_spike_rpb_counts'; what a record
+ * contributes is FOUR bits, because for an insertion or a deletion the records that show the key when the barcode is hit (alt1) and the
+ * records the rewrite changes then (touch) are two sets (smc_spike_indel_counts).
+ *   smc_spike_indel_read_bits   the run, d_loc[n_loci] and start0 as smc_spike_read_bits takes them; d_var[n_var] / d_ins[n_ins]: the
+ *            listed variants of the run as smc_spike_indel_touch takes them (SNVs, insertions, deletions; strictly ascending by pos0,
+ *            footprints disjoint; `thr` and `lead` are not read), each a locus of the run: 0 <= pos0 - start0 < n_loci.
+ *            d_out[v][n_aln] uint8, every byte written (0 for a record outside the window of v's locus):
+ *              bit 0  the record is in the window and covers the position - an indel's anchor: pos <= pos0 < end
+ *              bit 1  alt0: it shows the variant's key there as it is (smc_allele_carriers' rule, INS / DEL keys included)
+ *              bit 2  alt1: it shows the key when its barcode is spiked - an SNV: the single-letter bit of smc_spike_read_bits; an
+ *                     insertion / a deletion: touched and the anchor's letter is `ref`, or not touched and bit 1
+ *              bit 3  touch: the rewrite changes it when its barcode is spiked - an SNV: bit 2; an insertion / a deletion:
+ *                     smc_spike_indels' eligibility (the same device code as smc_spike_indel_touch, the 16-bit limits included)
+ *            A record whose CIGAR words or pairs lie beyond the pools covers and shows nothing; bc_gid is not read.  Summed per
+ *            barcode the four bits are smc_spike_indel_counts' (reads, alt0, alt1, touch).  Plain stores, no atomics.
+ *   smc_spike_indel_rpb_counts  smc_spike_rpb_counts' arguments; d_rec_flag: bit 0 = first name, bits 1 / 2 / 3 = bits 1 / 2 / 3 above.
+ *            With (reads_r, alt0_r, alt1_r, touch_r) of a barcode over its kept records, hit and there as in smc_spike_rpb_counts:
+ *            d_out[v][j][t][r][5] uint32 = (N': the b with there, V0': those with 2 * alt0_r > reads_r, S': those with hit, READS':
+ *            the sum of touch_r over the b with there and hit, V1': the b with there and 2 * (hit ? alt1_r : alt0_r) > reads_r).
+ *            With bit 3 = bit 2 in every flag the words are smc_spike_rpb_counts'; at one read threshold of 2^32 they are
+ *            smc_spike_indel_counts' at one depth threshold of 2^32.  The same kernel body as smc_spike_rpb_counts; integer atomics
+ *            only: two calls give the same words.  d_pos1: the variant's own 1-based position (no phase sets under this axis).
+ * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched and nothing zeroed: what smc_spike_indel_touch refuses (a kind
+ * beyond SMC_AF_DEL, positions not strictly ascending, letters, lengths, overlapping footprints), inserted letters beyond d_ins, a
+ * position that is no locus of the run (smc_spike_indel_read_bits); what smc_spike_rpb_counts refuses (smc_spike_indel_rpb_counts). */
+int smc_spike_indel_read_bits(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words,
+                              const uint8_t* d_bq, int64_t n_pairs, const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0,
+                              const smc_spike_indel_variant* d_var, const smc_spike_indel_variant* var_host, int32_t n_var,
+                              const uint8_t* d_ins, int64_t n_ins, uint8_t* d_out, void* stream);
+int smc_spike_indel_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_off, const uint32_t* cov_off_host,
+                               const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
+                               int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
+                               const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out,
+                               void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

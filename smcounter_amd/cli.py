@@ -232,6 +232,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "seed (dsSeed + j) mod 2^64: <outPrefix>.spikeAF.rpb.replicates.txt, .spikeAF.rpb.sensitivity.txt and "
                         ".spikeAF.rpb.curve.txt (per variant and r the detection rate at every target and T95).  SNV lists only; not "
                         "with --spikeDepth, --spikePhase or the --spikeIndel* flags.  Needs --spikeAF" % GRID_MAX_CELLS)
+    p.add_argument("--spikeIndelRpb", default=None,
+                   help="--spikeRpb on the --spikeIndels spike-in: comma-separated reads-per-barcode targets r > 0; --spikeVariants may "
+                        "hold SNVs, insertions and deletions (the rules of --spikeIndels).  Cell (t, r) is the .dsRpb<r> output of a "
+                        "--dsRpb r --dsRpbSampler philox run on the BAM tools/spike_variants.py --indels --af t writes, both with "
+                        "--dsSeed; cells, files (<outPrefix>.spikeAF<t>.dsRpb<r>.*, .spikeAF.rpb.detection.txt, with --spikeIndelReps "
+                        ".spikeAF.rpb.replicates / .sensitivity / .curve.txt) and limits (%d cells) are --spikeRpb's; V0 and V1 are "
+                        "counted by the variant's INS / DEL key over the reads the cell keeps, READS is the kept records the rewrite "
+                        "changed.  Not with --spikeRpb, --spikeIndels, --spikeReps, --spikeDepth or --spikePhase; --spikeIndelDepth and "
+                        "--spikeIndelPhase beside it are not built.  Needs --spikeAF" % GRID_MAX_CELLS)
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -409,8 +418,8 @@ class _Plan:
     spike: dict = None          # (--spikeAF) once the rules are made: "variants", and "res", the pre-pass's numbers per target
     spike_reps: int = None      # (--spikeReps) R; plan.spike then holds "keep", what the pre-pass kept (None once the stage has taken it)
     spike_depth: dict = None    # (--spikeDepth) "fracs", the cells' "params", and once the rules are made "rules" and "counts" [V][T x F]
-    spike_rpb: dict = None      # (--spikeRpb) "targets", the cells' "params", and once the rules are made "rules" and "counts" [V][T x Rr]
-    spike_indel_counters: bool = False   # (--spikeIndelReps, --spikeIndelDepth, --spikeIndelPhase) the spike-ins are --spikeIndels', four counters per covering barcode
+    spike_rpb: dict = None      # (--spikeRpb, --spikeIndelRpb) "targets", the cells' "params", and once the rules are made "rules" and "counts" [V][T x Rr]
+    spike_indel_counters: bool = False   # (--spikeIndelReps, --spikeIndelDepth, --spikeIndelPhase, --spikeIndelRpb) the spike-ins are --spikeIndels', four counters per covering barcode
     spike_phase: bool = False   # (--spikePhase, --spikeIndelPhase) plan.spike then holds "phase": None, or devplanes.spike_rules' dict of the sets of two members or more
 
     @property
@@ -806,6 +815,11 @@ def _main(args) -> int:
     spike_fracs, spike_cells = _spike.depth_cells(args, spike_targets, "spikeIndelDepth" if indel_depth is not None else "spikeDepth")
     _spike.indels(args, spike_targets)
     spike_rpbs, spike_rpb_cells = _spike.rpb_cells(args, spike_targets)
+    indel_rpb = False
+    if spike_rpbs is None:
+        # (--spikeIndelRpb: the same cells and outputs, the spike-ins --spikeIndels')
+        spike_rpbs, spike_rpb_cells = _spike.indel_rpb_cells(args, spike_targets)
+        indel_rpb = spike_rpbs is not None
     at = lambda **kw: dataclasses.replace(params, **kw)
     plan = _Plan([_Output(args.outPrefix, params)] +
                  [_Output(p, at(mtDepth=d), "dsMT", frac=f) for f, d, p in fractions] +
@@ -818,7 +832,7 @@ def _main(args) -> int:
                  [_Output(p, at(mtDepth=d, rpb=r), "spikeRpb", target=r, af=t, af_index=k) for k, t, r, d, p in spike_rpb_cells],
                  reps=ds_af_reps(args, af_targets), spike_reps=indel_reps if indel_reps is not None else _spike.reps(args, spike_targets),
                  spike_phase=_spike.phase(args, spike_targets) or indel_phase,
-                 spike_indel_counters=indel_reps is not None or indel_depth is not None or indel_phase)
+                 spike_indel_counters=indel_reps is not None or indel_depth is not None or indel_phase or indel_rpb)
     if spike_fracs is not None:
         plan.spike_depth = dict(fracs=spike_fracs, params=[o.params for o in plan.outputs if o.kind == "spikeDepth"])
     if spike_rpbs is not None:
@@ -856,8 +870,8 @@ def _main(args) -> int:
     for rule in plan.rules:
         if rule.level == "read":               # (a target or a cell)
             if rule.spike_rpb_cell:
-                print("--spikeRpb %s: sampler %s, seed %d, probKeep %.6g, threshold %d, %d of %d read names kept (mtDepth %d)" %
-                      (rule.label, rule.sampler, rule.seed, rule.prob_keep, rule.thr, rule.n_kept, rule.n_names, rule.params.mtDepth))
+                print("%s %s: sampler %s, seed %d, probKeep %.6g, threshold %d, %d of %d read names kept (mtDepth %d)" %
+                      (rule.flag, rule.label, rule.sampler, rule.seed, rule.prob_keep, rule.thr, rule.n_kept, rule.n_names, rule.params.mtDepth))
                 continue
             print("%s: sampler %s, seed %d, probKeep %.6g, %d of %d read names kept (mtDepth %d)" %
                   ("--dsGrid " + rule.label if rule.grid else "--dsRpb %g" % rule.target, rule.sampler, rule.seed, rule.prob_keep,

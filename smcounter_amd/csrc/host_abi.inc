@@ -1536,13 +1536,14 @@ int smc_spike_read_bits(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, c
     return SMC_OK;
 }
 
-// (--spikeRpb) (N', V0', S', READS', V1') of every listed SNV, replicate and cell (spike target x read threshold), from the covering
-// barcodes' records: everything checked on the host copies before anything is enqueued, then the counters zeroed and k_spr_counts
-int smc_spike_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_off, const uint32_t* cov_off_host,
-                         const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
-                         int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
-                         int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out, void* stream) {
-    const std::string who = "smc_spike_rpb_counts";
+// (--spikeRpb, --spikeIndelRpb) (N', V0', S', READS', V1') of every listed variant, replicate and cell (spike target x read threshold),
+// from the covering barcodes' records: everything checked on the host copies before anything is enqueued, then the counters zeroed and
+// k_spr_counts - with `four` the instance that reads alt1 and touch from flag bits 2 and 3, else the one in which bit 2 is both
+static int spr_cell_counts(const std::string& who, bool four, smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_off,
+                           const uint32_t* cov_off_host, const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name,
+                           const uint8_t* d_rec_flag, int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds,
+                           int32_t n_reps, const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr,
+                           uint32_t* d_out, void* stream) {
     if (!ctx || n_var < 0 || n_reps < 0 || n_targets < 0 || n_rec < 0) return fail(SMC_E_ARG, who + ": bad argument");
     if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
     if (n_targets > SMC_SPIKE_REP_MAX_TARGETS)
@@ -1590,11 +1591,57 @@ int smc_spike_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32
     const hipStream_t st = (hipStream_t)stream;
     const size_t n_out = (size_t)SPC_COUNTERS * (size_t)n_var * (size_t)n_reps * (size_t)n_targets * (size_t)n_read_thr;
     hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
+    const auto kernel = four ? (n_read_thr <= 8 ? k_spr_counts<8, true> : k_spr_counts<SMC_RG_MAX_TARGETS, true>)
+                             : (n_read_thr <= 8 ? k_spr_counts<8, false> : k_spr_counts<SMC_RG_MAX_TARGETS, false>);
     if (widest)
-        hipLaunchKernelGGL(n_read_thr <= 8 ? k_spr_counts<8> : k_spr_counts<SMC_RG_MAX_TARGETS>, dim3((unsigned)std::min<uint32_t>((widest + SPB_BLOCK - 1) / SPB_BLOCK, 256u), (unsigned)n_var,
+        hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<uint32_t>((widest + SPB_BLOCK - 1) / SPB_BLOCK, 256u), (unsigned)n_var,
                                               (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPB_BLOCK), 0, st,
                            (const unsigned long long*)d_cov_ident, d_cov_off, d_rec_off, (const unsigned long long*)d_rec_name, d_rec_flag,
                            (uint32_t)n_rec, d_pos1, T, (int)n_targets, Q, (int)n_read_thr, (const unsigned long long*)d_seeds, (int)n_reps, d_out);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
+int smc_spike_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_off, const uint32_t* cov_off_host,
+                         const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
+                         int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
+                         int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out, void* stream) {
+    return spr_cell_counts("smc_spike_rpb_counts", false, ctx, d_cov_ident, d_cov_off, cov_off_host, d_rec_off, rec_off_host, d_rec_name, d_rec_flag,
+                           n_rec, d_pos1, n_var, d_seeds, n_reps, thr, n_targets, read_thr, n_read_thr, d_out, stream);
+}
+
+// (--spikeIndelRpb) the same from FOUR bits per record: flag bit 2 = alt1, bit 3 = touch (smc_spike_indel_read_bits' bits 2 and 3)
+int smc_spike_indel_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_off, const uint32_t* cov_off_host,
+                               const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
+                               int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
+                               const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out,
+                               void* stream) {
+    return spr_cell_counts("smc_spike_indel_rpb_counts", true, ctx, d_cov_ident, d_cov_off, cov_off_host, d_rec_off, rec_off_host, d_rec_name,
+                           d_rec_flag, n_rec, d_pos1, n_var, d_seeds, n_reps, thr, n_targets, read_thr, n_read_thr, d_out, stream);
+}
+
+// (--spikeIndelRpb) per listed variant of a run - an SNV, an insertion, a deletion - and alignment one byte: covers / shows the key /
+// alt1 / touch.  One launch, every byte written
+int smc_spike_indel_read_bits(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words,
+                              const uint8_t* d_bq, int64_t n_pairs, const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0,
+                              const smc_spike_indel_variant* d_var, const smc_spike_indel_variant* var_host, int32_t n_var,
+                              const uint8_t* d_ins, int64_t n_ins, uint8_t* d_out, void* stream) {
+    const std::string who = "smc_spike_indel_read_bits";
+    if (!ctx || n_aln < 0 || n_cig_words < 0 || n_pairs < 0 || n_loci < 0 || n_var < 0 || n_ins < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    // (kinds, ascending positions, letters, lengths, the inserted letters inside the pool, disjoint footprints; no draw: thr and lead are not read)
+    if (int rc = spi_check_variants(who, var_host, n_var, d_ins, n_ins, true, false, false)) return rc;
+    for (int32_t v = 0; v < n_var; ++v) {
+        const int64_t locus = (int64_t)var_host[v].pos0 - (int64_t)start0;
+        if (locus < 0 || locus >= n_loci)
+            return fail(SMC_E_INPUT, who + ": variant " + std::to_string(v) + " names locus " + std::to_string(locus) + " of " + std::to_string(n_loci));
+    }
+    if (n_aln >= (int64_t)0xFFFFFF00) return fail(SMC_E_ARG, who + ": run too large");
+    if (!n_var || !n_aln) return SMC_OK;
+    if (!d_aln || !d_cig || !d_bq || !d_loc || !d_var || !d_out) return fail(SMC_E_ARG, who + ": NULL argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_spr_indel_bits, dim3((unsigned)std::min<int64_t>((n_aln + SPB_BLOCK - 1) / SPB_BLOCK, 1024), (unsigned)n_var), dim3(SPB_BLOCK), 0,
+                       (hipStream_t)stream, d_aln, (uint32_t)n_aln, d_cig, (unsigned long long)n_cig_words, d_bq, (unsigned long long)n_pairs, d_loc,
+                       start0, d_var, (int)n_var, d_ins, d_out);
     HIPCHK(hipGetLastError());
     return SMC_OK;
 }

@@ -19,7 +19,7 @@
 // every variant at the copy's threshold unless `own_thr`), its cnt[] / bsum[] / totals[] / statistics stand one copy behind the
 // other, its outputs at byte strides.  The run's two pools reach every copy by k_spike_pool (read once, stored n_copies times in
 // 16-byte chunks) before the scatter appends to them.  One copy with own_thr is smc_spike_indels.
-//   k_spi_touch     a lane per alignment: spi_walk<false, true> - no draw, every listed insertion / deletion taken as hit - adds 1 to
+//   k_spi_touch     a lane per alignment: spi_walk<false, SPI_TOUCH_SUM> - no draw, every listed insertion / deletion taken as hit - adds 1 to
 //                   out[v][bc_gid] for every one the record is eligible for: the records the rewrite changes at v when the barcode is
 //                   spiked.  The eligibility is spi_walk's own lines, not a restatement.
 // Eligible (the specification is tools/spike_variants.py): the variant's footprint - the anchor and the position behind it (an
@@ -52,14 +52,18 @@ __device__ __forceinline__ T spi_block_excl(T v, T* lds, T& total) {
     return pre + inc - v;
 }
 
-struct SpiRes { uint32_t l_seq, n_cig; int nm_inc, indel_inc; };
+struct SpiRes { uint32_t l_seq, n_cig; int nm_inc, indel_inc; int want; bool took; };
+// what spi_walk does beside (or in place of) drawing: count the eligible records per barcode, or answer for ONE variant of one record
+#define SPI_TOUCH_SUM 1
+#define SPI_TOUCH_ONE 2
 
 // One record against its variants var[lo ..] (those with pos0 < a.end).  EMIT false: only the indel kinds are drawn, nothing is stored
 // -> whether any hit is eligible, R.l_seq / R.n_cig the record's new sizes.  EMIT true: the SNVs are drawn too, the operations go to
 // oc[], the pairs to op[] (the caller made sure that R.n_cig words and R.l_seq pairs fit), stats[] counts.  A variant's threshold is
 // its own with `own_thr`, else `thr_c`.  TOUCH (with EMIT false): nothing is drawn - every insertion / deletion counts as hit - and
-// stats[k * touch_stride] counts every one the record is eligible for.
-template <bool EMIT, bool TOUCH = false>
+// SPI_TOUCH_SUM: stats[k * touch_stride] counts every one the record is eligible for; SPI_TOUCH_ONE (--spikeIndelRpb, per record):
+// nothing is stored, R.took says whether the record is eligible for variant R.want (an index into var[], set by the caller).
+template <bool EMIT, int TOUCH = 0>
 __device__ __forceinline__ bool spi_walk(const smc_dev_aln& a, const uint32_t* __restrict__ cg, const uint8_t* __restrict__ src,
                                          const smc_spike_indel_variant* __restrict__ var, int lo, int n_var, const uint8_t* __restrict__ ins,
                                          unsigned long long id, unsigned long long seed, unsigned long long thr_c, int own_thr,
@@ -71,7 +75,7 @@ __device__ __forceinline__ bool spi_walk(const smc_dev_aln& a, const uint32_t* _
     int yq = 0;                                                  // pairs [0, yq) of the record are dealt with
     uint32_t oci = 0, oq = 0, cur_l = (uint32_t)l_seq, cur_c = (uint32_t)n_cig;
     bool any = false;
-    R.nm_inc = 0; R.indel_inc = 0;
+    R.nm_inc = 0; R.indel_inc = 0; R.took = false;
     auto copy_to = [&](int q_end) {                              // pairs [yq, q_end) as they are
         q_end = min(q_end, l_seq);
         if (EMIT) for (int q = yq; q < q_end; ++q) *(uint16_t*)(op + 2ull * (oq + (uint32_t)(q - yq))) = *(const uint16_t*)(src + 2ull * q);
@@ -126,7 +130,8 @@ __device__ __forceinline__ bool spi_walk(const smc_dev_aln& a, const uint32_t* _
         if (d0 < used || (long long)d0 + fp >= (long long)len || qa + fp >= l_seq || qa < yq) continue;
         if (cur_c + 2u > SPI_MAX16 || (V.kind == SMC_AF_INS && cur_l + (uint32_t)n > SPI_MAX16)) continue;
         any = true;
-        if (TOUCH) atomicAdd(&stats[(size_t)k * touch_stride], 1u);
+        if (TOUCH == SPI_TOUCH_SUM) atomicAdd(&stats[(size_t)k * touch_stride], 1u);
+        if (TOUCH == SPI_TOUCH_ONE && k == R.want) R.took = true;
         cur_c += 2u;
         const int head = d0 - used + 1;
         if (EMIT) { oc[oci] = (uint32_t)head << 4 | (uint32_t)o; oc[oci + 1] = (uint32_t)n << 4 | (V.kind == SMC_AF_INS ? 1u : 2u); }
@@ -294,5 +299,5 @@ __global__ __launch_bounds__(SPI_BLOCK) void k_spi_touch(const smc_dev_aln* __re
     const int lo = spi_first(var, n_var, a.pos);
     if (!spi_in_run(a, lo, var, n_var, n_bc, n_pairs, n_cig_words)) return;
     SpiRes R;
-    spi_walk<false, true>(a, cig + a.cig_off, nullptr, var, lo, n_var, nullptr, 0ull, 0ull, 0ull, 0, nullptr, nullptr, out + a.bc_gid, (size_t)n_bc, R);
+    spi_walk<false, SPI_TOUCH_SUM>(a, cig + a.cig_off, nullptr, var, lo, n_var, nullptr, 0ull, 0ull, 0ull, 0, nullptr, nullptr, out + a.bc_gid, (size_t)n_bc, R);
 }

@@ -1,5 +1,5 @@
 // Included by smcounter_hip.hip (after k_spike_cells.inc: SPC_COUNTERS, spd_hits and the spike draw's domain; after k_read_groups.inc:
-// rg_draw, the read draw k_rg_masks makes; after k_allele_carriers.inc: af_shows).
+// rg_draw, the read draw k_rg_masks makes; after k_allele_carriers.inc: af_shows; after k_spike_indel.inc: spi_walk, spi_first).
 // ------------------------------------------------------------------------------------------
 // --spikeRpb: what every cell (spike target t, reads-per-barcode target r) of R replicate spike-ins achieves per listed SNV, counted
 // PER READ (smc_spike_read_bits, smc_spike_rpb_counts)
@@ -26,11 +26,33 @@
 // The per-r counters are indexed by unrolled loops only (they stay in registers: 3 x MAXR of them, so the kernel is compiled for MAXR =
 // 8 - what a run asks for - and for MAXR = 32, the most the cells' limit admits; n_rr <= MAXR).  Once per run / once per file: not on
 // the per-locus hot path.
+// --spikeIndelRpb (smc_spike_indel_read_bits, smc_spike_indel_rpb_counts): for an insertion or a deletion `single` is two numbers, as
+// in k_spike_cells - alt1, the records that show the key when the barcode is hit, and touch, the records the rewrite changes then.
+//   k_spr_indel_bits  k_spr_bits over smc_spike_indel_variant records: bits 0 / 1 as there (af_shows with the INS / DEL key), bit 2 =
+//                 alt1, bit 3 = touch.  An SNV's bits 2 and 3 are both k_spr_bits' bit 2 (spr_snv_bits, shared); an indel's touch is
+//                 spi_walk<false, SPI_TOUCH_ONE> - the rewrite's own eligibility lines, the 16-bit limits included -, its alt1 a
+//                 touched record whose anchor letter is REF's first, or an untouched one that shows the key already.
+//   k_spr_counts<MAXR, true>  the SAME body with a fourth per-r counter: car1 from alt1_r (flag bit 2), READS' from touch_r (flag bit
+//                 3).  The SNV entry is the instance <MAXR, false>, in which touch IS alt1 - no fourth array exists there and its
+//                 code is what it was.
 #define SPB_BLOCK 256
 #define SPB_COVERS 1u
 #define SPB_ALT 2u
 #define SPB_SINGLE 4u
+#define SPB_ALT1 4u                          // (k_spr_indel_bits: the same bit as SPB_SINGLE - an SNV's alt1 is its single-letter bit)
+#define SPB_TOUCH 8u
 #define SPB_FIRST 1u                         // (a record's flag byte for k_spr_counts) first name of its barcode, file-wide
+
+// bits 1 and 2 of a record that covers the SNV V at p: shows ALT as it is, the allele key a single letter
+// (a record that points beyond a pool covers, and shows nothing: k_spike_rewrite leaves it alone as well)
+__device__ __forceinline__ uint32_t spr_snv_bits(const smc_af_variant& V, const smc_dev_aln& a, const uint32_t* __restrict__ cig,
+                                                 unsigned long long n_cig_words, const uint8_t* __restrict__ bq, unsigned long long n_pairs, int p) {
+    if ((unsigned long long)a.cig_off + a.n_cig > n_cig_words) return 0u;
+    const BpRes r = bp2_resolve(cig + a.cig_off, (int)a.n_cig, a.pos, p, (int)a.l_seq);
+    if (r.isdel || r.indel != 0 || r.qpos < 0 || r.qpos >= (int)a.l_seq || (unsigned long long)a.seq_off + (unsigned long long)r.qpos >= n_pairs)
+        return 0u;
+    return SPB_SINGLE | (af_shows(V, a, cig, bq, nullptr, p) ? SPB_ALT : 0u);
+}
 
 // out[v * n_aln + i]: the three bits of alignment i at variant v (an SNV: var[v].letter its ALT); every byte of the row is written.
 // Against k_af_count on MALFORMED records: a record is counted here whatever its bc_gid (the host groups the bytes by barcode, and
@@ -50,16 +72,50 @@ __global__ __launch_bounds__(SPB_BLOCK) void k_spr_bits(const smc_dev_aln* __res
         uint32_t b = 0u;
         if (i >= L.w0 && i < w1) {
             const smc_dev_aln a = aln[i];
-            // (a record that points beyond a pool covers, and shows nothing: k_spike_rewrite leaves it alone as well)
+            if (a.pos <= p && p < a.end) b = SPB_COVERS | spr_snv_bits(V, a, cig, n_cig_words, bq, n_pairs, p);
+        }
+        o[i] = (uint8_t)b;
+    }
+}
+
+// out[v * n_aln + i]: the four bits of alignment i at variant v of `var` (SNVs, insertions, deletions, ascending by position: what
+// smc_spike_indel_touch takes); every byte of the row is written, 0 outside the window of v's locus (var[v].pos0 - start0; the host
+// checked that it is one of the run's).  Malformed records as in k_spr_bits: whatever its bc_gid a record counts, and one whose CIGAR
+// words or whose l_seq pairs lie beyond the pools covers and shows nothing (spi_in_run's bounds: k_spi_count leaves it where it is).
+__global__ __launch_bounds__(SPB_BLOCK) void k_spr_indel_bits(const smc_dev_aln* __restrict__ aln, uint32_t n_aln, const uint32_t* __restrict__ cig,
+                                                              unsigned long long n_cig_words, const uint8_t* __restrict__ bq,
+                                                              unsigned long long n_pairs, const smc_dev_locus* __restrict__ loc, int32_t start0,
+                                                              const smc_spike_indel_variant* __restrict__ var, int n_var,
+                                                              const uint8_t* __restrict__ ins, uint8_t* __restrict__ out) {
+    const smc_spike_indel_variant S = var[blockIdx.y];
+    const int p = S.pos0;
+    smc_af_variant V;                                            // (af_shows' record: the key's letter is the ALT of an SNV, the anchor's else)
+    V.locus = (uint32_t)(p - start0); V.kind = S.kind; V.letter = S.kind == SMC_AF_SNV ? S.alt : S.ref; V.len = S.len; V.ins_off = S.ins_off;
+    const smc_dev_locus L = loc[V.locus];
+    const uint32_t w1 = min(L.w1, n_aln);
+    uint8_t* const o = out + (size_t)n_aln * blockIdx.y;
+    for (uint32_t i = blockIdx.x * SPB_BLOCK + threadIdx.x; i < n_aln; i += gridDim.x * SPB_BLOCK) {
+        uint32_t b = 0u;
+        if (i >= L.w0 && i < w1) {
+            const smc_dev_aln a = aln[i];
             if (a.pos <= p && p < a.end) {
                 b = SPB_COVERS;
-                if ((unsigned long long)a.cig_off + a.n_cig <= n_cig_words) {
-                    const BpRes r = bp2_resolve(cig + a.cig_off, (int)a.n_cig, a.pos, p, (int)a.l_seq);
-                    if (!r.isdel && r.indel == 0 && r.qpos >= 0 && r.qpos < (int)a.l_seq &&
-                        (unsigned long long)a.seq_off + (unsigned long long)r.qpos < n_pairs) {
-                        b |= SPB_SINGLE;
-                        if (af_shows(V, a, cig, bq, nullptr, p)) b |= SPB_ALT;
+                if (S.kind == SMC_AF_SNV) {
+                    b |= spr_snv_bits(V, a, cig, n_cig_words, bq, n_pairs, p);
+                    if (b & SPB_SINGLE) b |= SPB_TOUCH;              // (an SNV: the rewrite changes the single-letter records, which then show ALT)
+                } else if ((unsigned long long)a.cig_off + a.n_cig <= n_cig_words && (unsigned long long)a.seq_off + a.l_seq <= n_pairs) {
+                    const bool shows = af_shows(V, a, cig, bq, ins, p);
+                    SpiRes R;
+                    R.want = (int)blockIdx.y;
+                    spi_walk<false, SPI_TOUCH_ONE>(a, cig + a.cig_off, nullptr, var, spi_first(var, n_var, a.pos), n_var, nullptr, 0ull, 0ull, 0ull, 0,
+                                                   nullptr, nullptr, nullptr, 0, R);
+                    bool alt1 = shows;
+                    if (R.took) {
+                        // (eligible: the anchor is a base of an M / = / X operation inside l_seq - bp2_resolve's qpos is its query position)
+                        const BpRes r = bp2_resolve(cig + a.cig_off, (int)a.n_cig, a.pos, p, (int)a.l_seq);
+                        alt1 = r.qpos >= 0 && r.qpos < (int)a.l_seq && bq[2ull * ((unsigned long long)a.seq_off + (unsigned long long)r.qpos)] == S.ref;
                     }
+                    b |= (shows ? SPB_ALT : 0u) | (alt1 ? SPB_ALT1 : 0u) | (R.took ? SPB_TOUCH : 0u);
                 }
             }
         }
@@ -69,8 +125,9 @@ __global__ __launch_bounds__(SPB_BLOCK) void k_spr_bits(const smc_dev_aln* __res
 
 // out[(((g * n_reps + j) * n_tgt + t) * n_rr + r) * 5 + k] += counter k of (N', V0', S', READS', V1') (zeroed before the launch); n_tgt *
 // n_rr <= SMC_AF_DEPTH_MAX_CELLS.  Variant g: barcodes [off[g], off[g + 1]) of `ident`; barcode e: records [rec_off[e], rec_off[e + 1])
-// of rec_name / rec_flag, clamped to n_rec.  n_rr <= MAXR (the host picks the instance).
-template <int MAXR>
+// of rec_name / rec_flag, clamped to n_rec.  n_rr <= MAXR (the host picks the instance).  FOUR (smc_spike_indel_rpb_counts): flag bit 2
+// is alt1 and bit 3 touch, a per-r counter each; without it bit 2 is both (`single`) and bit 3 is not read.
+template <int MAXR, bool FOUR>
 __global__ __launch_bounds__(SPB_BLOCK) void k_spr_counts(const unsigned long long* __restrict__ ident, const uint32_t* __restrict__ off,
                                                           const uint32_t* __restrict__ rec_off, const unsigned long long* __restrict__ rec_name,
                                                           const uint8_t* __restrict__ rec_flag, uint32_t n_rec,
@@ -97,9 +154,9 @@ __global__ __launch_bounds__(SPB_BLOCK) void k_spr_counts(const unsigned long lo
             uint32_t x[4];
             smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, pos, (uint32_t)seed, (uint32_t)(seed >> 32), x);
             const uint32_t k_hit = spd_hits(T, x[0], n_tgt);
-            uint32_t reads[MAXR], alt[MAXR], sgl[MAXR];
+            uint32_t reads[MAXR], alt[MAXR], sgl[MAXR], tch[FOUR ? MAXR : 1];
 #pragma unroll
-            for (int r = 0; r < MAXR; ++r) reads[r] = alt[r] = sgl[r] = 0u;
+            for (int r = 0; r < MAXR; ++r) { reads[r] = alt[r] = sgl[r] = 0u; if (FOUR) tch[r] = 0u; }
             for (uint32_t i = r0; i < r1; ++i) {
                 const uint32_t fl = rec_flag[i];
                 uint32_t kept = every;
@@ -108,11 +165,12 @@ __global__ __launch_bounds__(SPB_BLOCK) void k_spr_counts(const unsigned long lo
                     kept = 0u;
                     for (int r = 0; r < n_rr; ++r) kept |= (uint32_t)((unsigned long long)u < Q.t[r]) << r;
                 }
-                const uint32_t is_alt = (fl >> 1) & 1u, is_sgl = (fl >> 2) & 1u;
+                const uint32_t is_alt = (fl >> 1) & 1u, is_sgl = (fl >> 2) & 1u, is_tch = (fl >> 3) & 1u;
 #pragma unroll
                 for (int r = 0; r < MAXR; ++r) {
                     const uint32_t k = (kept >> r) & 1u;
                     reads[r] += k; alt[r] += k & is_alt; sgl[r] += k & is_sgl;
+                    if (FOUR) tch[r] += k & is_tch;
                 }
             }
 #pragma unroll
@@ -125,7 +183,7 @@ __global__ __launch_bounds__(SPB_BLOCK) void k_spr_counts(const unsigned long lo
                         const bool hit = ((k_hit >> t) & 1u) != 0u;
                         const unsigned long long m_s = __ballot(there && hit), m_v1 = __ballot(there && (hit ? car1 : car0));
                         // (a run holds fewer than 2^32 - 256 alignments: no wrap that matters)
-                        const int rd = wave_add((int)((there && hit) ? sgl[r] : 0u));
+                        const int rd = wave_add((int)((there && hit) ? (FOUR ? tch[r] : sgl[r]) : 0u));
                         if (lane == 0) {
                             uint32_t* const p = part[wave][t * n_rr + r];
                             p[0] = (uint32_t)__popcll(m_n); p[1] = (uint32_t)__popcll(m_v0); p[2] = (uint32_t)__popcll(m_s);

@@ -386,7 +386,7 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
         # (--dsRpb, --spikeRpb: the kept read names, by read-name id - an id must stand for one full name, or the rule cannot be applied)
         nonlocal p_idents
         if p_idents is None:
-            p_idents = pair_idents_or_refuse(bam, A, "--spikeRpb" if rule.spike_rpb_cell else "--dsRpb", chrom, lo, nl)
+            p_idents = pair_idents_or_refuse(bam, A, rule.flag if rule.spike_rpb_cell else "--dsRpb", chrom, lo, nl)
         return p_idents
 
     def read_mask(rule):
@@ -804,7 +804,7 @@ class DsRule:
     @property
     def flag(self) -> str:
         if self.spike_rpb_cell:
-            return "--spikeRpb"
+            return "--spikeIndelRpb" if getattr(self.spike, "indels", False) else "--spikeRpb"
         if self.spike is not None:
             return "--spikeDepth" if self.spike_cell else "--spikeAF"
         if self.depth is not None:
@@ -1679,17 +1679,23 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     this seed gives "counts", per variant and cell dict(N, V0, S, READS, V1) over the reads the cell keeps, and "rules" gets the
     cells' DsRules (level "read" over the shared table).  Every cell's (N, V0, V1) is also counted a second way - select_run by
     read mask over the spiked copy of t (over the run itself for V0), then smc_allele_carriers on the selection - and a difference
-    raises RuntimeError.  ValueError / BamError: what --dsRpbSampler philox refuses."""
+    raises RuntimeError.  ValueError / BamError: what --dsRpbSampler philox refuses.
+    `rpb` with `indel_counters` (--spikeIndelRpb): the list may hold insertions and deletions.  The flag byte per record comes from
+    smc_spike_indel_read_bits - bits 1 / 2 / 3 = alt0 / alt1 / touch -, its per-barcode sums must equal the four counters above, and the
+    counts come from smc_spike_indel_rpb_counts.  The second count is the same: an indel copy has pools of its own, but its records
+    stand in the run's order and number, so the read mask selects the same records and select_run hands on the copy's pools."""
     from .tools import ds_allele_fraction as af
     from .tools import spike_variants as sv
     af.unique_idents(bamio.placed_barcodes(path), path)
     nthreads = nthreads or bamio.host_threads()
     if rpb is not None:
-        if depth is not None or phase is not None or indel_counters or any(v.kind != af.SNV for v in variants):
+        # (--spikeIndelRpb - `indel_counters` - lifts the indel part; an indel in the list without it is --spikeRpb's to refuse)
+        if depth is not None or phase is not None or (not indel_counters and any(v.kind != af.SNV for v in variants)):
             raise ValueError("--spikeRpb: cells of barcode depths, phase sets or indel spike-ins are not built")
-        # (the file-wide table of the UNSPIKED file serves every cell and replicate: spiking changes no name, barcode or record count)
+        # (the file-wide table of the UNSPIKED file serves every cell and replicate: spiking changes no name, barcode or record count -
+        # an indel rewrite changes a record's length and CIGAR only)
         read_rules = philox_read_rules(path, list(rpb["targets"]), [params_list[0]] * len(rpb["targets"]), seed, eng, nthreads=nthreads,
-                                       flag="--spikeRpb")
+                                       flag="--spikeIndelRpb" if indel_counters else "--spikeRpb")
         try:
             return _spike_rules(path=path, fasta=fasta, variants=variants, targets=targets, params_list=params_list, seed=seed, eng=eng,
                                 nthreads=nthreads, max_reads=max_reads, keep=keep, keep_bytes=keep_bytes, depth=depth, phase=phase,
@@ -1709,6 +1715,7 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
     from .tools import ds_allele_fraction as af
     from .tools import spike_variants as sv
     spikes = SpikeSet(variants, indels=indel_counters)
+    rpb_flag = "--spikeIndelRpb" if indel_counters else "--spikeRpb"
     P = params_list[0]
     rows = [[None] * len(variants) for _ in targets]
     psets = list(phase["sets"]) if phase is not None else []
@@ -1746,9 +1753,10 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                     bad = spike_indel_limits(A, spikes.chrom_variants(v0.chrom, 0.5)[0])
                     if bad is not None:
                         a = A["aln"][bad]
-                        raise ValueError("--spikeIndelReps / --spikeIndelDepth: the record at %s:%d (l_seq %d, %d CIGAR operations) spans listed "
+                        raise ValueError("%s: the record at %s:%d (l_seq %d, %d CIGAR operations) spans listed "
                                          "indels that could take l_seq or the CIGAR beyond 65535: whether it takes one would depend on the "
-                                         "draws of the others" % (v0.chrom, int(a["pos"]) + 1, int(a["l_seq"]), int(a["n_cig"])))
+                                         "draws of the others" % ("--spikeIndelRpb" if rpb is not None else "--spikeIndelReps / --spikeIndelDepth",
+                                                                  v0.chrom, int(a["pos"]) + 1, int(a["l_seq"]), int(a["n_cig"])))
                 idents = dec.barcode_idents(A["n_bc"])
                 nm, n_indel = dec.run_mismatches(len(A["aln"]))
                 run_ref = fasta.fetch(v0.chrom, lo, lo + nl).upper()
@@ -1765,7 +1773,7 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                         for t in range(len(targets)):
                             second[(k, t, f)] = [None, int(car_f[r].sum()), None]
                 if rpb is not None:
-                    p_idents = pair_idents_or_refuse(dec, A, "--spikeRpb", v0.chrom, lo, nl)
+                    p_idents = pair_idents_or_refuse(dec, A, rpb_flag, v0.chrom, lo, nl)
                     read_masks = _run_read_masks(eng, read_rules[0].groups, read_rules, p_idents, v0.chrom, lo, nl)
 
                 def read_selected(run, r):
@@ -1790,8 +1798,8 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                             n_r, car_r = read_selected(spiked, r)
                             for x, k in enumerate(group):
                                 if second_rpb[(k, t, r)][0] != int(n_r[x]):
-                                    raise RuntimeError("--spikeRpb: %s:%d at %g x target %g: the read selection keeps %d covering barcodes of "
-                                                       "the run and %d of its spiked copy" % (variants[k].chrom, variants[k].pos, target,
+                                    raise RuntimeError("%s: %s:%d at %g x target %g: the read selection keeps %d covering barcodes of "
+                                                       "the run and %d of its spiked copy" % (rpb_flag, variants[k].chrom, variants[k].pos, target,
                                                                                              rpb["targets"][r], second_rpb[(k, t, r)][0], int(n_r[x])))
                                 second_rpb[(k, t, r)][2] = int(car_r[x])
                         for f, frac in enumerate(fracs):
@@ -1846,17 +1854,23 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                     # with that one threshold -, then the CSR of every variant's covering records)
                     read_masks[0].free()
                     read_masks = None
-                    read_bits = spike_read_bits(eng, up, A, lo, var)
+                    if indel_counters:
+                        # (--spikeIndelRpb: the group's records of the chromosome's list - ascending, as the group is; the inserted
+                        # letters stay where the chromosome's pool has them)
+                        read_bits = spike_indel_read_bits(eng, up, A, lo, svar[[sorder.index(k) for k in group]], spikes.ins[v0.chrom])
+                    else:
+                        read_bits = spike_read_bits(eng, up, A, lo, var)
                     first = run_first_names(eng, read_rules[0].groups, p_idents, v0.chrom, lo, nl)
+                    shifts = (1, 2, 3) if indel_counters else (1, 2)
                     for r, k in enumerate(group):
                         gids = np.flatnonzero(cov[r][:len(idents)])
                         records[k] = spike_rpb_records(A, read_bits[r], gids, p_idents, first)
                         sums = np.stack([np.add.reduceat(((records[k][2] >> s) & 1).astype(np.int64), records[k][0][:-1].astype(np.int64))
-                                         if len(gids) else np.zeros(0, np.int64) for s in (1, 2)], axis=1)
+                                         if len(gids) else np.zeros(0, np.int64) for s in shifts], axis=1)
                         if not np.array_equal(np.diff(records[k][0].astype(np.int64)), counters[k][:, 0]) or \
-                                not np.array_equal(sums, counters[k][:, 1:3]):
-                            raise RuntimeError("--spikeRpb: %s:%d: the records' bits do not sum to the pre-pass's counters" %
-                                               (variants[k].chrom, variants[k].pos))
+                                not np.array_equal(sums, counters[k][:, 1:1 + len(shifts)]):
+                            raise RuntimeError("%s: %s:%d: the records' bits do not sum to the pre-pass's counters" %
+                                               (rpb_flag, variants[k].chrom, variants[k].pos))
                 if keep is not None:
                     size = sum(int(A[x].nbytes) for x in ("aln", "cig", "bq", "loc"))
                     held = size + sum(r.nbytes for r in keep["runs"]) <= (AF_KEEP_BYTES if keep_bytes is None else keep_bytes)
@@ -1883,12 +1897,12 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
         try:
             rthr = [r.thr for r in read_rules]
             got = spike_rpb_counts(eng, spikes.lead_pos, covers, records, [int(seed) & 0xFFFFFFFFFFFFFFFF], [sv.threshold(t) for t in targets],
-                                   rthr)[:, 0]
+                                   rthr, four=indel_counters)[:, 0]
             for (k, t, r), mine in second_rpb.items():
                 if [int(got[k, t, r, c]) for c in (0, 1, 4)] != mine:
                     v = variants[k]
-                    raise RuntimeError("--spikeRpb: %s:%d at %g x target %g: the counts call says (N, V0, V1) = %r, the selection of the "
-                                       "spiked copy %r" % (v.chrom, v.pos, targets[t], rpb["targets"][r],
+                    raise RuntimeError("%s: %s:%d at %g x target %g: the counts call says (N, V0, V1) = %r, the selection of the "
+                                       "spiked copy %r" % (rpb_flag, v.chrom, v.pos, targets[t], rpb["targets"][r],
                                                            [int(got[k, t, r, c]) for c in (0, 1, 4)], mine))
         except BaseException:
             if keep is not None:
@@ -2289,6 +2303,7 @@ def spike_indel_counts(eng, positions, covers, counters, seeds, thresholds, dept
 
 
 SPB_COVERS, SPB_ALT, SPB_SINGLE, SPB_FIRST = 1, 2, 4, 1      # k_spike_rpb.inc: smc_spike_read_bits' bits; bit 0 of a record's flag byte
+SPB_ALT1, SPB_TOUCH = 4, 8                                   # smc_spike_indel_read_bits' bits 2 and 3 (an SNV list's bytes have no bit 3)
 
 
 def spike_read_bits(eng, up: RunOnDevice, A, lo: int, var: np.ndarray) -> np.ndarray:
@@ -2310,11 +2325,35 @@ def spike_read_bits(eng, up: RunOnDevice, A, lo: int, var: np.ndarray) -> np.nda
         d_var.free(); d_out.free()
 
 
+def spike_indel_read_bits(eng, up: RunOnDevice, A, lo: int, var: np.ndarray, ins: np.ndarray) -> np.ndarray:
+    """smc_spike_indel_read_bits over the run `up` (A: its host arrays) -> uint8 [n_var, n_aln]: per listed variant (`var`: smc_spike_indels'
+    records of the run's listed loci, ascending; `ins`: the pool their insertions point into) and alignment bit 0 = the record covers
+    the position, bit 1 = it shows the key as it is, bit 2 = it shows it when its barcode is spiked, bit 3 = the rewrite changes it then."""
+    from .engine import DevBuf
+    n_var, n = len(var), up.n_aln
+    if not n_var or not n:
+        return np.zeros((n_var, n), np.uint8)
+    var = np.ascontiguousarray(var, abi.SPIKE_INDEL_VARIANT_DTYPE)
+    ins = np.ascontiguousarray(ins, np.uint8)
+    d_var = DevBuf(eng, var.nbytes + 256).upload(var.view(np.uint8).reshape(-1))
+    d_ins = DevBuf(eng, ins.nbytes + 256).upload(ins if ins.nbytes else np.zeros(4, np.uint8))
+    d_out = DevBuf(eng, n_var * n + 256)
+    try:
+        _lib.check(eng.L.smc_spike_indel_read_bits(eng.ctx, up.aln.data_ptr(), n, up.cig.data_ptr(), len(A["cig"]), up.bq.data_ptr(),
+                                                   len(A["bq"]) // 2, up.loc.data_ptr(), int(A["nl"]), int(lo), d_var.data_ptr(), var.ctypes.data,
+                                                   n_var, d_ins.data_ptr(), len(ins), d_out.data_ptr(), ctypes.c_void_p(0)),
+                   "smc_spike_indel_read_bits")
+        return d_out.download(np.uint8, n_var * n).reshape(n_var, n)                      # (the default stream: behind the kernel)
+    finally:
+        d_var.free(); d_ins.free(); d_out.free()
+
+
 def spike_rpb_records(A, bits: np.ndarray, gids: np.ndarray, p_idents: np.ndarray, first: np.ndarray):
     """The CSR smc_spike_rpb_counts takes for ONE listed variant of run `A`: `bits` its row of spike_read_bits, `gids` the run-wide ids
     of its covering barcodes (ascending), `p_idents` the identity of every read-name id of the run, `first` (bool per read-name id)
     whether the name is its barcode's first, file-wide -> (uint32 [len(gids) + 1] offsets, uint64 name identities, uint8 flags), a
-    barcode's records in file order."""
+    barcode's records in file order.  A flag carries bits 1 .. 3 of the record's byte (spike_indel_read_bits': alt0, alt1, touch; bit 3
+    of spike_read_bits' bytes is 0)."""
     aln = A["aln"]
     idx = np.flatnonzero(bits & SPB_COVERS)
     bc = aln["bc_gid"][idx].astype(np.int64)
@@ -2326,7 +2365,7 @@ def spike_rpb_records(A, bits: np.ndarray, gids: np.ndarray, p_idents: np.ndarra
     off = np.zeros(len(gids) + 1, np.uint32)
     off[1:] = np.cumsum(per[gids])
     pair = aln["pair_gid"][idx]
-    flag = (bits[idx] & (SPB_ALT | SPB_SINGLE)) | np.where(np.asarray(first, bool)[pair], SPB_FIRST, 0).astype(np.uint8)
+    flag = (bits[idx] & (SPB_ALT | SPB_SINGLE | SPB_TOUCH)) | np.where(np.asarray(first, bool)[pair], SPB_FIRST, 0).astype(np.uint8)
     return off, np.ascontiguousarray(np.asarray(p_idents, np.uint64)[pair]), flag.astype(np.uint8)
 
 
@@ -2342,10 +2381,11 @@ def run_first_names(eng, groups: ReadGroups, p_idents, chrom: str = "?", lo: int
     return np.unpackbits(words.view(np.uint8), bitorder="little")[:len(p_idents)].astype(bool)
 
 
-def spike_rpb_counts(eng, positions, covers, records, seeds, thresholds, read_thresholds) -> np.ndarray:
+def spike_rpb_counts(eng, positions, covers, records, seeds, thresholds, read_thresholds, four: bool = False) -> np.ndarray:
     """smc_spike_rpb_counts -> uint32 [V, R, T, Rr, 5] = (N', V0', S', READS', V1') of every variant, replicate and cell.  positions,
     covers, seeds, thresholds: spike_rep_counts'; records[v]: spike_rpb_records' (offsets [len(covers[v]) + 1], name identities, flag
-    bytes) of variant v; read_thresholds: read_threshold(probKeep) per reads-per-barcode target."""
+    bytes) of variant v; read_thresholds: read_threshold(probKeep) per reads-per-barcode target.  `four` (--spikeIndelRpb):
+    smc_spike_indel_rpb_counts - the flags' bits 2 and 3 are alt1 and touch."""
     n_var = len(covers)
     off = np.zeros(n_var + 1, np.uint32)
     off[1:] = np.cumsum([len(c) for c in covers])
@@ -2364,9 +2404,10 @@ def spike_rpb_counts(eng, positions, covers, records, seeds, thresholds, read_th
     pos = np.array([int(p) & 0xFFFFFFFF for p in positions], np.uint32)
     seeds = np.ascontiguousarray(seeds, np.uint64)
     thr, rthr = np.ascontiguousarray(thresholds, np.uint64), np.ascontiguousarray(read_thresholds, np.uint64)
+    entry = "smc_spike_indel_rpb_counts" if four else "smc_spike_rpb_counts"
     return _spike_counts_call(
-        eng, "smc_spike_rpb_counts", [ident, off, rec_off, name, flag, pos, seeds], (n_var, len(seeds), len(thr), len(rthr), 5),
-        lambda d, d_out: eng.L.smc_spike_rpb_counts(eng.ctx, d[0], d[1], off.ctypes.data, d[2], rec_off.ctypes.data, d[3], d[4], len(name),
+        eng, entry, [ident, off, rec_off, name, flag, pos, seeds], (n_var, len(seeds), len(thr), len(rthr), 5),
+        lambda d, d_out: getattr(eng.L, entry)(eng.ctx, d[0], d[1], off.ctypes.data, d[2], rec_off.ctypes.data, d[3], d[4], len(name),
                                                     d[5], n_var, d[6], len(seeds), thr.ctypes.data, len(thr), rthr.ctypes.data, len(rthr),
                                                     d_out, ctypes.c_void_p(0)))
 
@@ -2558,7 +2599,8 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
     `read_cells` (--spikeRpb: dict(params: the VcParams of the target's cells, one per reads-per-barcode target, masks: per copy the
     address of its first keep mask - ReadGroups.masks with the copy's seed, one mask per target -, n_words: words per mask)): every
     copy is also selected per r by read name (select_run, level "read") and built; a cell's selections share one batch and one plan
-    -> (the copies' rows, per cell the same), or NARROW."""
+    -> (the copies' rows, per cell the same), or NARROW.  With `indel` (--spikeIndelRpb) want_cells holds the cells' (N', V1') per
+    reads-per-barcode target, and `read_cells` their "targets" for the message."""
     from . import vc
     A, up, lo, nl, chrom = run.A, run.up, run.lo, run.nl, run.chrom
     B = len(part_seeds)
@@ -2574,7 +2616,7 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
         copies = [RunOnDevice(_BufView(made["aln"], c * sa), _BufView(made["cig"], c * sc), _BufView(made["bq"], c * sb), up.loc, up.ref, up.n_aln,
                               up.loc_host, pairs_used=int(made["totals"][c, 0])) for c in range(B)]
         af_var, af_ins = af_run_variants([variants[k] for k in run.group], chrom, lo, fasta)
-    flag = "--spikeRpb" if read_cells else "--spikeDepth" if cells else "--spikeReps"
+    flag = ("--spikeIndelRpb" if indel is not None else "--spikeRpb") if read_cells else "--spikeDepth" if cells else "--spikeReps"
 
     def check_carriers(c, sel, counts, want, what):
         """(N, V1) of every variant of the run on copy c (or its selection) by smc_allele_carriers against the counts call's."""
@@ -2605,8 +2647,10 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
                             got["orig"] = d_orig.download(np.uint32, kept)
                         return got["orig"]
 
-                    def allele_key(ai, qpos, indel, orig_index=orig_index):
-                        return run.bam.allele_key(int(orig_index()[int(ai)]), qpos, indel)
+                    def allele_key(ai, qpos, indel_len, orig_index=orig_index,
+                                   key=run.bam.allele_key if indel is None else copy_allele_key(copies[c], A, run.bam.allele_key)):
+                        # (--spikeIndelRpb: a relocated record's texts come from the copy, by the kept alignment's index in it)
+                        return key(int(orig_index()[int(ai)]), qpos, indel_len)
 
                     def old_bc(orig_index=orig_index, got=got, bc=A["aln"]["bc_gid"]):
                         # (the read level renumbers the kept barcodes by first kept appearance: as the main pass maps them back)
@@ -2616,6 +2660,12 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
                         return got["old_bc"]
                     bc_name = lambda g, old_bc=old_bc: run.bam.barcode_name(int(old_bc()[int(g)]))
                     bc_idents = lambda n, old_bc=old_bc: run.idents[old_bc()]
+                    if indel is not None:
+                        try:
+                            check_carriers(c, sel, counts, indel["want_cells"][read][c], " x target %g" % read_cells["targets"][read])
+                        except BaseException:
+                            sel.free(shared=False); d_orig.free()
+                            raise
                 elif frac is None:
                     # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch)
                     sel, counts, d_orig, allele_key = copies[c], A, None, run.bam.allele_key
@@ -2720,7 +2770,9 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
     `rpb` (--spikeRpb: spike_rules' dict with "targets", the "params" of the T x Rr cells and their "rules"): one smc_spike_rpb_counts
     call with all R seeds over the records the pre-pass kept (keep["records"]) gives "rpb_counts", uint32 [V, R, T, Rr, 5]; every copy
     is also selected per r with the keep masks of ITS seed - one ReadGroups.masks call per seed and run - and built
-    (_spike_rep_call's `read_cells`): `rows` then also holds (variant index, T + t x Rr + r, replicate)."""
+    (_spike_rep_call's `read_cells`): `rows` then also holds (variant index, T + t x Rr + r, replicate).  With four counters
+    (--spikeIndelRpb) the counts come from smc_spike_indel_rpb_counts and the copies from smc_spike_indels_reps; beside READS every copy's
+    (N, V1), and every cell's (N', V1') on its selection, must equal the counts calls'."""
     import time
     from . import dsaf
     from .tools import spike_variants as sv
@@ -2755,7 +2807,7 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
         if rpb is not None:
             F = len(rpb["targets"])
             read_rules = rpb["rules"][:F]
-            rpb_counts = spike_rpb_counts(eng, spikes.lead_pos, keep["covers"], keep["records"], seeds, thr, [r.thr for r in read_rules])
+            rpb_counts = spike_rpb_counts(eng, spikes.lead_pos, keep["covers"], keep["records"], seeds, thr, [r.thr for r in read_rules], four=four)
         times["counts"] = time.perf_counter() - t0
         for run in keep["runs"]:
             if run.A is None:
@@ -2784,11 +2836,12 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
             try:
                 if rpb is not None:
                     # (the keep masks of every reads-per-barcode target, per seed: one launch each over the run's read-name identities)
-                    p_idents = pair_idents_or_refuse(run.bam, run.A, "--spikeRpb", run.chrom, run.lo, run.nl)
+                    p_idents = pair_idents_or_refuse(run.bam, run.A, read_rules[0].flag, run.chrom, run.lo, run.nl)
                     for j in range(n_reps):
                         seed_masks[j] = _run_read_masks(eng, read_rules[0].groups, [dataclasses.replace(r, seed=seeds[j]) for r in read_rules],
                                                         p_idents, run.chrom, run.lo, run.nl)
                 _spike_rep_targets(eng=eng, run=run, svar=svar, var_at=var_at, seeds=seeds, thr=thr, counts=counts, depth_counts=depth_counts,
+                                   rpb_counts=rpb_counts,
                                    params_list=params_list, fasta=fasta, variants=variants, max_depth=max_depth, sampler=sampler,
                                    sampler_seed=sampler_seed, depth=depth, rpb=rpb, seed_masks=seed_masks, keep=keep, spikes=spikes,
                                    four=four, room=room, n_reps=n_reps, rows=rows, times=times)
@@ -2804,12 +2857,13 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
                 phase_depth_counts=phase_depth_counts, rpb_counts=rpb_counts)
 
 
-def _spike_rep_targets(*, eng, run, svar, var_at, seeds, thr, counts, depth_counts, params_list, fasta, variants, max_depth, sampler,
+def _spike_rep_targets(*, eng, run, svar, var_at, seeds, thr, counts, depth_counts, rpb_counts, params_list, fasta, variants, max_depth, sampler,
                        sampler_seed, depth, rpb, seed_masks, keep, spikes, four, room, n_reps, rows, times):
     """spike_replicates' calls for one kept run: per target as many replicates per _spike_rep_call as `room` allows; `rows` and `times`
     are filled.  seed_masks[j] (--spikeRpb): _run_read_masks' of replicate j."""
     T = len(params_list)
     F = len(depth["fracs"]) if depth is not None else len(rpb["targets"]) if rpb is not None else 0
+    cell_counts = depth_counts if depth is not None else rpb_counts      # (the cells' [V, R, T, F or Rr, 5])
     for t in range(T):
         P = params_list[t]
         cells = [(depth["fracs"][f], depth["params"][t * F + f]) for f in range(F)] if depth is not None else []
@@ -2822,12 +2876,12 @@ def _spike_rep_targets(*, eng, run, svar, var_at, seeds, thr, counts, depth_coun
             if four:
                 n_cov = [len(keep["covers"][k]) for k in run.group]
                 indel = dict(ins=spikes.ins[run.chrom], want=[[(n, int(counts[k, j, t, 2])) for k, n in zip(run.group, n_cov)] for j in js],
-                             want_cells=[[[(int(depth_counts[k, j, t, f, 0]), int(depth_counts[k, j, t, f, 4])) for k in run.group]
+                             want_cells=[[[(int(cell_counts[k, j, t, f, 0]), int(cell_counts[k, j, t, f, 4])) for k in run.group]
                                           for j in js] for f in range(F)])
             read_cells = None
             if rpb is not None:
                 read_cells = dict(params=rpb["params"][t * F:(t + 1) * F], masks=[seed_masks[j][0].data_ptr() for j in js],
-                                  n_words=seed_masks[js[0]][1])
+                                  n_words=seed_masks[js[0]][1], targets=list(rpb["targets"]))
             out = _spike_rep_call(*args, bits, cells, indel, read_cells)
             if out == NARROW:
                 eng.word_bits = 32

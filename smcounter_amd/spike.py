@@ -25,6 +25,9 @@ the rule): the variants file is read as --spikePhase reads it, under the rules o
 and the pages <outPrefix>.spikeAF.rpb.detection.txt, .replicates.txt, .sensitivity.txt and .curve.txt from the depth pages' writers,
 with RPB as their axis column (RPB_AXIS).
 
+--spikeIndelRpb: --spikeRpb on the --spikeIndels spike-in (indel_flags refuses what does not go with it, indel_rpb_cells makes the cells
+as rpb_cells does); the outputs' kind, the pages and their writers are --spikeRpb's.
+
 The semantics are tools/spike_variants.py's (DESIGN.md "--spikeAF"); the rewrite on the GPU is csrc/k_spike.inc (smc_spike_alleles),
 the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the main pass are devplanes.spike_rules / spike_run.
 """
@@ -136,14 +139,23 @@ def indels(args, spike_targets) -> bool:
 
 # ---- --spikeIndelReps, --spikeIndelDepth
 def indel_flags(args, spike_targets):
-    """--spikeIndelReps / --spikeIndelDepth -> (R or None, the fractions' text or None).  SystemExit: beside --spikeIndels, --spikeReps,
+    """--spikeIndelReps / --spikeIndelDepth -> (R or None, the fractions' text or None); --spikeIndelRpb is checked here with them - its
+    text is indel_rpb_cells' to read: beside --spikeRpb (--spikeIndelRpb takes the targets), beside --spikeIndelDepth or
+    --spikeIndelPhase (not built), without --spikeAF, and what follows for all three.  SystemExit: beside --spikeIndels, --spikeReps,
     --spikeDepth (the flag that covers it is named) or --spikePhase; --spikeIndelReps without --spikeAF and --spikeVariants,
     --spikeIndelDepth without --spikeAF; R no integer or outside REPS_MIN .. REPS_MAX.  (The fractions are depth_cells' to check.)"""
-    r, text = getattr(args, "spikeIndelReps", None), getattr(args, "spikeIndelDepth", None)
-    r, text = (None if r in (None, "") else r), (None if text in (None, "") else text)
-    if r is None and text is None:
+    r, text, rp = getattr(args, "spikeIndelReps", None), getattr(args, "spikeIndelDepth", None), getattr(args, "spikeIndelRpb", None)
+    r, text, rp = (None if r in (None, "") else r), (None if text in (None, "") else text), (None if rp in (None, "") else rp)
+    if r is None and text is None and rp is None:
         return None, None
-    mine = "--spikeIndelReps" if r is not None else "--spikeIndelDepth"
+    mine = "--spikeIndelReps" if r is not None else "--spikeIndelDepth" if text is not None else "--spikeIndelRpb"
+    if rp is not None:
+        # (--spikeIndelRpb: the reads-per-barcode targets are indel_rpb_cells' to check)
+        if getattr(args, "spikeRpb", None) not in (None, ""):
+            raise SystemExit("--spikeIndelRpb cannot be combined with --spikeRpb in one run: --spikeIndelRpb takes the targets")
+        for flag in ("spikeIndelDepth", "spikeIndelPhase"):
+            if getattr(args, flag, None) not in (None, "", False):
+                raise SystemExit("--spikeIndelRpb cannot be combined with --%s in one run (the combination is not built)" % flag)
     if getattr(args, "spikeIndels", False):
         raise SystemExit("%s implies the rules of --spikeIndels: leave --spikeIndels out" % mine)
     if getattr(args, "spikeReps", None) not in (None, ""):
@@ -155,6 +167,8 @@ def indel_flags(args, spike_targets):
     if not spike_targets:
         raise SystemExit("--spikeIndelReps replicates the spike-ins of --spikeAF, insertions and deletions among them: it needs --spikeAF "
                          "and --spikeVariants" if r is not None else
+                         "--spikeIndelRpb thins the reads of the --spikeAF spike-ins, insertions and deletions among them: it needs --spikeAF"
+                         if text is None else
                          "--spikeIndelDepth thins the barcodes of the --spikeAF spike-ins, insertions and deletions among them: it needs --spikeAF")
     if r is not None:
         r = reps(args, spike_targets, "spikeIndelReps")
@@ -462,18 +476,36 @@ def rpb_cells(args, spike_targets):
     for flag in RPB_NOT_WITH:
         if getattr(args, flag, None) not in (None, "", False):
             raise SystemExit("--spikeRpb cannot be combined with --%s in one run (the combination is not built)" % flag)
+    return _rpb_cells(text, spike_targets, "spikeRpb")
+
+
+def _rpb_cells(text, spike_targets, flag: str):
+    """The reads-per-barcode targets of `text` and the cells they make with the --spikeAF targets; `flag`: the flag named."""
     try:
         rs = [float(x) for x in str(text).split(",") if x.strip()]
     except ValueError:
-        raise SystemExit("--spikeRpb: comma-separated reads-per-barcode targets > 0 expected, got %r" % text)
+        raise SystemExit("--%s: comma-separated reads-per-barcode targets > 0 expected, got %r" % (flag, text))
     if not rs or any(not (r > 0.0 and r < float("inf")) for r in rs):
-        raise SystemExit("--spikeRpb: every target must be a number > 0, got %r" % text)
+        raise SystemExit("--%s: every target must be a number > 0, got %r" % (flag, text))
     if len(set("%g" % r for r in rs)) != len(rs):
-        raise SystemExit("--spikeRpb: a target is listed twice (the cells' files would share a name), got %r" % text)
+        raise SystemExit("--%s: a target is listed twice (the cells' files would share a name), got %r" % (flag, text))
     if len(spike_targets) * len(rs) > MAX_CELLS:
-        raise SystemExit("--spikeRpb: %d targets x %d reads-per-barcode targets = %d cells, at most %d" %
-                         (len(spike_targets), len(rs), len(spike_targets) * len(rs), MAX_CELLS))
+        raise SystemExit("--%s: %d targets x %d reads-per-barcode targets = %d cells, at most %d" %
+                         (flag, len(spike_targets), len(rs), len(spike_targets) * len(rs), MAX_CELLS))
     return rs, [(k, t, r, d, "%s.dsRpb%g" % (p, r)) for k, (t, d, p) in enumerate(spike_targets) for r in rs]
+
+
+# ---- --spikeIndelRpb
+def indel_rpb_cells(args, spike_targets):
+    """--spikeIndelRpb -> rpb_cells' (reads-per-barcode targets, cells), or (None, []) without the flag.  What the flag does not go
+    with is indel_flags' to refuse (call it first); SystemExit here: without --spikeAF, text that is no list of numbers, a target <= 0
+    or listed twice, beyond MAX_CELLS cells."""
+    text = getattr(args, "spikeIndelRpb", None)
+    if text in (None, ""):
+        return None, []
+    if not spike_targets:
+        raise SystemExit("--spikeIndelRpb thins the reads of the --spikeAF spike-ins, insertions and deletions among them: it needs --spikeAF")
+    return _rpb_cells(text, spike_targets, "spikeIndelRpb")
 
 
 # ---- --spikePhase

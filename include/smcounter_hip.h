@@ -855,6 +855,37 @@ int smc_spike_indel_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const 
                                int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
                                const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out,
                                void* stream);
+/* (ABI 11, additive: one entry more, the version number unchanged) --spikePhaseRpb: the JOINT numbers of phase sets in the cells
+ * (spike target t, reads-per-barcode target r).  Thinning reads can take a barcode out of one member's pileup, or flip its majority
+ * at one member only, so the joint numbers are counted per record.  Per set g its M_g = set_m_host[g] members (1 ..
+ * SMC_SPIKE_PHASE_MAX_MEMBERS; d_set_m the device copy) and its joint barcodes - the identities that cover every member in the
+ * unthinned run, ascending, as smc_spike_phase_counts takes them (d_joint_ident, d_joint_off / joint_off_host): a barcode that is
+ * not joint unthinned cannot become joint.  Per (joint barcode e of g, member m) ONE segment of covering records, segment
+ * seg_base[g] + (e - joint_off[g]) * M_g + m: its records are [rec_off[s], rec_off[s + 1]) of d_rec_name / d_rec_flag as
+ * smc_spike_indel_rpb_counts takes them (bit 0 = first name, bit 1 = alt0, bit 2 = alt1; bit 3 is not read: a set has no READS').
+ * d_seg_base / seg_base_host[n_sets]: the running sums of M_g * (joint barcodes of g), from 0 - the segments lie set after set;
+ * d_rec_off / rec_off_host: the n_seg + 1 offsets, n_seg the sum over all sets; n_rec records.  A record that spans several
+ * members appears in each of their segments.  d_pos1[n_sets]: the leader's 1-based position, counter word 3 of the set's draw.
+ * d_seeds, `thr`, `read_thr`: as smc_spike_rpb_counts takes them.  An SNV-only list passes smc_spike_read_bits' bytes, whose bit 2
+ * (single) is an SNV's alt1.  With hit = u(b; seeds[j]) < thr[t] - ONE spike draw per (barcode, set, replicate) -, a record KEPT
+ * at r when flag bit 0 is set or its read draw with seeds[j] is below read_thr[r], and (reads, alt0, alt1) of a barcode at member m
+ * over the kept records of its segment:
+ *   d_out[g][j][t][r][4] uint32 = (N_ALL': the joint b with reads > 0 at EVERY member, V0_ALL': those of N_ALL' with 2 * alt0 >
+ *   reads at every member, S_ALL': those of N_ALL' with hit, V1_ALL': those of N_ALL' with 2 * (hit ? alt1 : alt0) > reads at every
+ *   member).  At M_g = 1 these are columns (N', V0', S', V1') of smc_spike_indel_rpb_counts; at one read threshold of 2^32 they are
+ *   smc_spike_indel_phase_counts' at one depth threshold of 2^32.  d_out is zeroed by the call; integer atomics only: two calls
+ *   give the same words.
+ * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched and nothing zeroed: a set with M_g outside 1 ..
+ * SMC_SPIKE_PHASE_MAX_MEMBERS, joint or record offsets that decrease, record offsets that end beyond n_rec, segment bases that
+ * are not the running sums, a threshold above 2^32 on either axis, n_read_thr below 1, n_targets * n_read_thr above
+ * SMC_AF_DEPTH_MAX_CELLS, n_reps above SMC_AF_REP_MAX_REPS, more than SMC_AF_MAX_VARIANTS sets, an output of 2^32 - 256 words or
+ * more. */
+int smc_spike_phase_rpb_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, const uint32_t* d_joint_off, const uint32_t* joint_off_host,
+                               const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_seg_base, const uint32_t* seg_base_host,
+                               const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
+                               int64_t n_rec, const uint32_t* d_pos1, int32_t n_sets, const uint64_t* d_seeds, int32_t n_reps,
+                               const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out,
+                               void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

@@ -241,6 +241,20 @@ def build_parser() -> argparse.ArgumentParser:
                         "counted by the variant's INS / DEL key over the reads the cell keeps, READS is the kept records the rewrite "
                         "changed.  Not with --spikeRpb, --spikeIndels, --spikeReps, --spikeDepth or --spikePhase; --spikeIndelDepth and "
                         "--spikeIndelPhase beside it are not built.  Needs --spikeAF" % GRID_MAX_CELLS)
+    p.add_argument("--spikePhaseRpb", default=None,
+                   help="phase sets at reads-per-barcode targets: comma-separated r > 0.  --spikeVariants is read under the rules of "
+                        "--spikeIndelPhase (SNVs, MNV lines, insertions and deletions; PS=<name> sets of at most 8 members; all "
+                        "footprints disjoint), and cell (t, r) is that spike-in at t - every member of a set drawn with its leader's "
+                        "position - then the --dsRpb r --dsRpbSampler philox thinning with the same --dsSeed: the .dsRpb<r> output of a "
+                        "--dsRpb r --dsRpbSampler philox run on the BAM tools/spike_variants.py --phased --indels --af t writes.  Writes "
+                        "what --spikeIndelRpb and --spikeIndelPhase write and, when a set has two members or more, "
+                        "<outPrefix>.spikeAF.rpb.phase.txt: per set and cell the barcodes that keep a read at every member (N_ALL), carry "
+                        "every member before (V0_ALL) and after spiking (V1_ALL) over the kept reads, are spiked (S_ALL), and whether "
+                        "every member was called in the cell (CALLED_ALL); with --spikeIndelReps R also "
+                        "<outPrefix>.spikeAF.rpb.phase.replicates.txt and .rpb.phase.sensitivity.txt.  The joint numbers are counted "
+                        "per read on the GPU in one call; at most %d cells.  Not with --spikeRpb, --spikeIndelRpb (this flag takes the "
+                        "targets), --spikeIndels, --spikePhase, --spikeIndelPhase (implied), --spikeReps (use --spikeIndelReps), "
+                        "--spikeDepth or --spikeIndelDepth (not built).  Needs --spikeAF" % GRID_MAX_CELLS)
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -418,9 +432,9 @@ class _Plan:
     spike: dict = None          # (--spikeAF) once the rules are made: "variants", and "res", the pre-pass's numbers per target
     spike_reps: int = None      # (--spikeReps) R; plan.spike then holds "keep", what the pre-pass kept (None once the stage has taken it)
     spike_depth: dict = None    # (--spikeDepth) "fracs", the cells' "params", and once the rules are made "rules" and "counts" [V][T x F]
-    spike_rpb: dict = None      # (--spikeRpb, --spikeIndelRpb) "targets", the cells' "params", and once the rules are made "rules" and "counts" [V][T x Rr]
-    spike_indel_counters: bool = False   # (--spikeIndelReps, --spikeIndelDepth, --spikeIndelPhase, --spikeIndelRpb) the spike-ins are --spikeIndels', four counters per covering barcode
-    spike_phase: bool = False   # (--spikePhase, --spikeIndelPhase) plan.spike then holds "phase": None, or devplanes.spike_rules' dict of the sets of two members or more
+    spike_rpb: dict = None      # (--spikeRpb, --spikeIndelRpb, --spikePhaseRpb: then also "flag") "targets", the cells' "params", and once the rules are made "rules" and "counts" [V][T x Rr]
+    spike_indel_counters: bool = False   # (--spikeIndelReps, --spikeIndelDepth, --spikeIndelPhase, --spikeIndelRpb, --spikePhaseRpb) the spike-ins are --spikeIndels', four counters per covering barcode
+    spike_phase: bool = False   # (--spikePhase, --spikeIndelPhase, --spikePhaseRpb) plan.spike then holds "phase": None, or devplanes.spike_rules' dict of the sets of two members or more
 
     @property
     def rules(self):
@@ -475,7 +489,14 @@ def spike_rules(args, outs, variants, early, keep=None, depth=None, phase=None, 
         for ps, per in zip(phase["sets"], phase["counts"]):
             for o, c in zip(outs, per):
                 print("%s %g: set %s (%d members) N_ALL %d, V0_ALL %d, S_ALL %d, V1_ALL %d" %
-                      ("--spikeIndelPhase" if getattr(args, "spikeIndelPhase", False) else "--spikePhase", o.af, ps.name, len(ps.members), c["N_ALL"], c["V0_ALL"], c["S_ALL"], c["V1_ALL"]))
+                      ("--spikeIndelPhase" if getattr(args, "spikeIndelPhase", False) else "--spikePhaseRpb" if rpb is not None else "--spikePhase",
+                       o.af, ps.name, len(ps.members), c["N_ALL"], c["V0_ALL"], c["S_ALL"], c["V1_ALL"]))
+        if phase.get("rpb_counts") is not None:
+            # (--spikePhaseRpb: the joint numbers over the reads each cell keeps)
+            for ps, per in zip(phase["sets"], phase["rpb_counts"]):
+                for (t, r), c in zip(((o.af, r) for o in outs for r in rpb["targets"]), per):
+                    print("--spikePhaseRpb %g x target %g: set %s (%d members) N_ALL %d, V0_ALL %d, S_ALL %d, V1_ALL %d" %
+                          (t, r, ps.name, len(ps.members), c["N_ALL"], c["V0_ALL"], c["S_ALL"], c["V1_ALL"]))
     return rules, res
 
 
@@ -810,6 +831,8 @@ def _main(args) -> int:
     af_fracs, af_cells = ds_af_depth_cells(args, af_targets)
     from . import spike as _spike
     spike_targets = _spike.targets(args)
+    # (--spikePhaseRpb first: its refusals name the flag to use beside it)
+    phase_rpbs, phase_rpb_cells = _spike.phase_rpb_cells(args, spike_targets)
     indel_phase = _spike.indel_phase(args, spike_targets)
     indel_reps, indel_depth = _spike.indel_flags(args, spike_targets)
     spike_fracs, spike_cells = _spike.depth_cells(args, spike_targets, "spikeIndelDepth" if indel_depth is not None else "spikeDepth")
@@ -820,6 +843,9 @@ def _main(args) -> int:
         # (--spikeIndelRpb: the same cells and outputs, the spike-ins --spikeIndels')
         spike_rpbs, spike_rpb_cells = _spike.indel_rpb_cells(args, spike_targets)
         indel_rpb = spike_rpbs is not None
+    if phase_rpbs is not None:
+        # (--spikePhaseRpb: --spikeIndelRpb's cells and outputs under the rules of --spikeIndelPhase)
+        spike_rpbs, spike_rpb_cells, indel_rpb, indel_phase = phase_rpbs, phase_rpb_cells, True, True
     at = lambda **kw: dataclasses.replace(params, **kw)
     plan = _Plan([_Output(args.outPrefix, params)] +
                  [_Output(p, at(mtDepth=d), "dsMT", frac=f) for f, d, p in fractions] +
@@ -837,6 +863,8 @@ def _main(args) -> int:
         plan.spike_depth = dict(fracs=spike_fracs, params=[o.params for o in plan.outputs if o.kind == "spikeDepth"])
     if spike_rpbs is not None:
         plan.spike_rpb = dict(targets=spike_rpbs, params=[o.params for o in plan.outputs if o.kind == "spikeRpb"])
+        if phase_rpbs is not None:
+            plan.spike_rpb["flag"] = "--spikePhaseRpb"
     if af_fracs is not None:
         plan.depth = dict(fracs=af_fracs, params=[o.params for o in plan.outputs if o.kind == "dsAFDepth"])
     flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets), ("--dsAF", af_targets), ("--spikeAF", spike_targets)) if on)
@@ -1119,6 +1147,24 @@ def _spike_reports(args, plan, shard, loc_index, repeats):
                 p_entries[(g, c)] = per
         _spike.write_phase_replicates(args.outPrefix, variants, phase["sets"], p_outs, reps["seeds"], p_entries)
         _spike.write_phase_sensitivity(args.outPrefix, variants, phase["sets"], p_outs, p_entries)
+        if reps.get("phase_rpb_counts") is not None:
+            # (--spikePhaseRpb: the same two pages over the cells (t, r); replicate 0 is the run's own cell)
+            r_outs = [(o.af, o.target, o.params.mtDepth) for o in plan.outputs if o.kind == "spikeRpb"]
+            Rr = len(plan.spike_rpb["targets"])
+            r_entries = {}
+            for g, ps in enumerate(phase["sets"]):
+                for c in range(len(r_outs)):
+                    t, r = divmod(c, Rr)
+                    per = []
+                    for j in range(R):
+                        got = dict(zip(_spike.PHASE_NAMES, (int(x) for x in reps["phase_rpb_counts"][g, j, t, r])))
+                        per.append((got, int(all(_spike._called(variants[i], [cell_entries[(i, c)][j]]) for i in ps.members))))
+                    if per[0][0] != phase["rpb_counts"][g][c]:
+                        raise RuntimeError("--spikePhaseRpb: set %s at %g x target %g: replicate 0 holds %r, the run's own cell %r" %
+                                           (ps.name, r_outs[c][0], r_outs[c][1], per[0][0], phase["rpb_counts"][g][c]))
+                    r_entries[(g, c)] = per
+            _spike.write_phase_replicates(args.outPrefix, variants, phase["sets"], r_outs, reps["seeds"], r_entries, _spike.RPB_AXIS)
+            _spike.write_phase_sensitivity(args.outPrefix, variants, phase["sets"], r_outs, r_entries, _spike.RPB_AXIS)
     tm = reps["times"]
     print("--spikeReps: replicate stage %.3f s (%d replicates x %d targets: counts call %.4f s, %d rewrite calls, %d builds in %d batches, "
           "%.3f s)" % (tm["stage"], R, len(outs), tm["counts"], tm["rewrites"], tm["builds"], tm["batches"], tm["calls"]))
@@ -1180,6 +1226,11 @@ def _run(args, plan, loc_list, t0):
                      [(o.af, o.frac, o.params.mtDepth, o.prefix, [c[k] for c in phase["depth_counts"]])
                       for k, o in enumerate(o for o in plan.outputs if o.kind == "spikeDepth")]
             _spike.write_phase(args.outPrefix, plan.spike["variants"], phase["sets"], p_outs)
+            if phase.get("rpb_counts") is not None:
+                # (--spikePhaseRpb: every set in every cell (t, r), counted over the reads the cell keeps)
+                r_outs = [(o.af, o.target, o.params.mtDepth, o.prefix, [c[k] for c in phase["rpb_counts"]])
+                          for k, o in enumerate(o for o in plan.outputs if o.kind == "spikeRpb")]
+                _spike.write_phase(args.outPrefix, plan.spike["variants"], phase["sets"], r_outs, _spike.RPB_AXIS)
         if shard.spike_reps is not None:
             _spike_reports(args, plan, shard, loc_index, repeats)
     t1 = datetime.datetime.now()

@@ -1620,6 +1620,84 @@ int smc_spike_indel_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const 
                            d_rec_flag, n_rec, d_pos1, n_var, d_seeds, n_reps, thr, n_targets, read_thr, n_read_thr, d_out, stream);
 }
 
+// (--spikePhaseRpb) (N_ALL', V0_ALL', S_ALL', V1_ALL') of every phase set, replicate and cell (spike target x read threshold), from the
+// records of every (joint barcode, member): everything checked on the host copies before anything is enqueued - the segment bases are
+// the running sums of (joint barcodes x members), so no lane reads an offset beyond the n_seg + 1 there are -, then the counters
+// zeroed and k_spr_phase_counts
+int smc_spike_phase_rpb_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, const uint32_t* d_joint_off, const uint32_t* joint_off_host,
+                               const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_seg_base, const uint32_t* seg_base_host,
+                               const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
+                               int64_t n_rec, const uint32_t* d_pos1, int32_t n_sets, const uint64_t* d_seeds, int32_t n_reps,
+                               const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out,
+                               void* stream) {
+    const std::string who = "smc_spike_phase_rpb_counts";
+    if (!ctx || n_sets < 0 || n_reps < 0 || n_targets < 0 || n_rec < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_sets > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_sets) + " sets, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
+    if (n_targets > SMC_SPIKE_REP_MAX_TARGETS)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_SPIKE_REP_MAX_TARGETS));
+    if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
+    if (n_read_thr < 1) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_read_thr) + " read thresholds, at least 1 expected");
+    if ((n_reps && !d_seeds) || (n_targets && !thr) || !read_thr) return fail(SMC_E_ARG, who + ": NULL argument");
+    if ((int64_t)n_targets * (int64_t)n_read_thr > SMC_AF_DEPTH_MAX_CELLS)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets x " + std::to_string(n_read_thr) + " read thresholds, at most " +
+                                 std::to_string(SMC_AF_DEPTH_MAX_CELLS) + " cells");
+    SpkThr T;
+    RgThr Q;
+    memset(&T, 0, sizeof T);
+    memset(&Q, 0, sizeof Q);
+    for (int32_t t = 0; t < n_targets; ++t) {
+        if (thr[t] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": target " + std::to_string(t) + ": a threshold above 2^32");
+        T.t[t] = thr[t];
+    }
+    for (int32_t r = 0; r < n_read_thr; ++r) {
+        if (read_thr[r] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": read threshold " + std::to_string(r) + " is above 2^32");
+        if (r < SMC_RG_MAX_TARGETS) Q.t[r] = read_thr[r];         // (more of them pass the cells' limit only without a target: nothing is launched)
+    }
+    if ((double)n_sets * (double)n_reps * (double)n_targets * (double)n_read_thr * (double)SPP_COUNTERS >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_sets) + " sets x " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) +
+                                 " targets x " + std::to_string(n_read_thr) + " read thresholds: too many counters for one call");
+    if (n_rec >= (int64_t)0xFFFFFF00) return fail(SMC_E_INPUT, who + ": too many covering records for one call");
+    if (!n_sets || !n_reps || !n_targets) return SMC_OK;
+    if (!joint_off_host || !d_joint_off || !set_m_host || !d_set_m || !seg_base_host || !d_seg_base || !d_pos1 || !d_out)
+        return fail(SMC_E_ARG, who + ": NULL argument");
+    uint32_t widest = 0;
+    uint64_t n_seg = 0;
+    for (int32_t g = 0; g < n_sets; ++g) {
+        const uint32_t m = set_m_host[g];
+        if (m < 1 || m > SMC_SPIKE_PHASE_MAX_MEMBERS)
+            return fail(SMC_E_INPUT, who + ": set " + std::to_string(g) + " has " + std::to_string(m) + " members, 1 .. " +
+                                     std::to_string(SMC_SPIKE_PHASE_MAX_MEMBERS) + " expected");
+        if (joint_off_host[g + 1] < joint_off_host[g]) return fail(SMC_E_INPUT, who + ": the offsets decrease at set " + std::to_string(g));
+        if ((uint64_t)seg_base_host[g] != n_seg)
+            return fail(SMC_E_INPUT, who + ": the segments of set " + std::to_string(g) + " start at " + std::to_string(seg_base_host[g]) + ", " +
+                                     std::to_string(n_seg) + " expected");
+        widest = std::max(widest, joint_off_host[g + 1] - joint_off_host[g]);
+        n_seg += (uint64_t)m * (uint64_t)(joint_off_host[g + 1] - joint_off_host[g]);
+    }
+    if (joint_off_host[n_sets] >= 0x55555500u || n_seg >= 0xFFFFFF00ull) return fail(SMC_E_INPUT, who + ": too many joint barcodes for one call");
+    if (n_seg) {
+        if (!d_joint_ident || !d_rec_off || !rec_off_host) return fail(SMC_E_ARG, who + ": NULL joint barcodes");
+        for (uint64_t s = 0; s < n_seg; ++s)
+            if (rec_off_host[s + 1] < rec_off_host[s]) return fail(SMC_E_INPUT, who + ": the record offsets decrease at segment " + std::to_string(s));
+        if ((int64_t)rec_off_host[n_seg] > n_rec)
+            return fail(SMC_E_INPUT, who + ": the record offsets end at " + std::to_string(rec_off_host[n_seg]) + ", beyond the " + std::to_string(n_rec) + " records");
+        if (n_rec && (!d_rec_name || !d_rec_flag)) return fail(SMC_E_ARG, who + ": NULL records");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t n_out = (size_t)SPP_COUNTERS * (size_t)n_sets * (size_t)n_reps * (size_t)n_targets * (size_t)n_read_thr;
+    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
+    const auto kernel = n_read_thr <= 8 ? k_spr_phase_counts<8> : k_spr_phase_counts<SMC_RG_MAX_TARGETS>;
+    if (widest)
+        hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<uint32_t>((widest + SPB_BLOCK - 1) / SPB_BLOCK, 256u), (unsigned)n_sets,
+                                        (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPB_BLOCK), 0, st,
+                           (const unsigned long long*)d_joint_ident, d_joint_off, d_set_m, d_seg_base, d_rec_off, (const unsigned long long*)d_rec_name,
+                           d_rec_flag, (uint32_t)n_rec, d_pos1, T, (int)n_targets, Q, (int)n_read_thr, (const unsigned long long*)d_seeds, (int)n_reps,
+                           d_out);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
 // (--spikeIndelRpb) per listed variant of a run - an SNV, an insertion, a deletion - and alignment one byte: covers / shows the key /
 // alt1 / touch.  One launch, every byte written
 int smc_spike_indel_read_bits(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, const uint32_t* d_cig, int64_t n_cig_words,

@@ -205,3 +205,102 @@ __global__ __launch_bounds__(SPB_BLOCK) void k_spr_counts(const unsigned long lo
 }
 static_assert(SMC_RG_MAX_TARGETS == SMC_AF_DEPTH_MAX_CELLS && SPC_COUNTERS * SMC_AF_DEPTH_MAX_CELLS <= SPB_BLOCK,
               "k_spr_counts: a bit per read threshold, a lane per cell and counter");
+
+// --spikePhaseRpb (smc_spike_phase_rpb_counts): the JOINT numbers of phase sets under read thinning.  A set's barcode counts when it
+// keeps a read at EVERY member and carries it when it does so at EVERY member; thinning can take it out of one member's pileup, or flip
+// its majority at one member only, so the joint numbers cannot be had from the members' own cells: they are made per record as well.
+//   k_spr_phase_counts  k_spr_counts' shape: a lane per JOINT barcode of a set (blockIdx.y = set, blockIdx.z strides over the
+//                 replicates), ONE spike draw per (barcode, set, replicate) with the leader's position.  The lane walks its M_g members
+//                 one after the other, each a CSR segment of covering records (segment seg_base[g] + (e - off[g]) * M_g + m); per
+//                 member the 3 x MAXR counters (reads_r, alt0_r, alt1_r) of k_spr_counts, which it then folds into three bit sets
+//                 over r - there, car0, car1 - and ANDs into the running all-members sets: registers do not grow with M_g.  Per r and
+//                 t four ballots + popcounts, the wavefronts added in LDS, one integer atomic add per workgroup, replicate, cell and
+//                 counter that is not 0.  Flag bit 3 (touch) is not read: a set has no READS'.
+// A record that spans several members is a record of each of their segments, and its read draw is made once per member.
+#define SPP_COUNTERS 4
+// out[(((g * n_reps + j) * n_tgt + t) * n_rr + r) * 4 + k] += counter k of (N_ALL', V0_ALL', S_ALL', V1_ALL') (zeroed before the launch).
+// Set g: joint barcodes [off[g], off[g + 1]) of `ident`, set_m[g] members (1 .. SMC_SPIKE_PHASE_MAX_MEMBERS: the host checked), its
+// segments from seg_base[g]; segment s: records [rec_off[s], rec_off[s + 1]) clamped to n_rec.  n_rr <= MAXR.
+template <int MAXR>
+__global__ __launch_bounds__(SPB_BLOCK) void k_spr_phase_counts(const unsigned long long* __restrict__ ident, const uint32_t* __restrict__ off,
+                                                                const uint32_t* __restrict__ set_m, const uint32_t* __restrict__ seg_base,
+                                                                const uint32_t* __restrict__ rec_off, const unsigned long long* __restrict__ rec_name,
+                                                                const uint8_t* __restrict__ rec_flag, uint32_t n_rec,
+                                                                const uint32_t* __restrict__ pos1, SpkThr T, int n_tgt, RgThr Q, int n_rr,
+                                                                const unsigned long long* __restrict__ seeds, int n_reps, uint32_t* __restrict__ out) {
+    __shared__ uint32_t part[SPB_BLOCK / WAVE][SMC_AF_DEPTH_MAX_CELLS][SPP_COUNTERS];
+    const uint32_t g = blockIdx.y;
+    const uint32_t e0 = off[g], e1 = off[g + 1], pos = pos1[g], n_mem = set_m[g], s_base = seg_base[g];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    const int n_cells = n_tgt * n_rr;
+    const uint32_t every = n_rr >= 32 ? 0xFFFFFFFFu : (1u << n_rr) - 1u;
+    const uint32_t stride = gridDim.x * SPB_BLOCK;
+    for (uint32_t base = e0 + blockIdx.x * SPB_BLOCK; base < e1; base += stride) {     // (whole workgroups: the barriers below)
+        const uint32_t e = base + threadIdx.x;
+        const bool in_row = e < e1;
+        const unsigned long long id = in_row ? ident[e] : 0ull;
+        const uint32_t s0 = s_base + (e - e0) * n_mem;                                 // (read only in_row)
+        for (int j = blockIdx.z; j < n_reps; j += gridDim.z) {
+            const unsigned long long seed = seeds[j];
+            uint32_t x[4];
+            smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, pos, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+            const uint32_t k_hit = spd_hits(T, x[0], n_tgt);
+            uint32_t all_there = in_row ? every : 0u, all_c0 = every, all_c1 = every;  // (a lane beyond the row: N_ALL' = 0 everywhere)
+            for (uint32_t m = 0; m < n_mem; ++m) {                                     // (uniform bound; a lane beyond the row walks nothing)
+                uint32_t r0 = 0, r1 = 0;
+                if (in_row) {
+                    r0 = min(rec_off[s0 + m], n_rec);
+                    r1 = min(rec_off[s0 + m + 1], n_rec);
+                }
+                uint32_t reads[MAXR], alt[MAXR], sgl[MAXR];
+#pragma unroll
+                for (int r = 0; r < MAXR; ++r) reads[r] = alt[r] = sgl[r] = 0u;
+                for (uint32_t i = r0; i < r1; ++i) {
+                    const uint32_t fl = rec_flag[i];
+                    uint32_t kept = every;
+                    if (!(fl & SPB_FIRST)) {
+                        const uint32_t u = rg_draw(rec_name[i], seed);
+                        kept = 0u;
+                        for (int r = 0; r < n_rr; ++r) kept |= (uint32_t)((unsigned long long)u < Q.t[r]) << r;
+                    }
+                    const uint32_t is_alt = (fl >> 1) & 1u, is_sgl = (fl >> 2) & 1u;
+#pragma unroll
+                    for (int r = 0; r < MAXR; ++r) {
+                        const uint32_t k = (kept >> r) & 1u;
+                        reads[r] += k; alt[r] += k & is_alt; sgl[r] += k & is_sgl;
+                    }
+                }
+                uint32_t there = 0u, c0 = 0u, c1 = 0u;
+#pragma unroll
+                for (int r = 0; r < MAXR; ++r) {
+                    there |= (uint32_t)(reads[r] > 0u) << r;
+                    c0 |= (uint32_t)(2ull * alt[r] > (unsigned long long)reads[r]) << r;
+                    c1 |= (uint32_t)(2ull * sgl[r] > (unsigned long long)reads[r]) << r;
+                }
+                all_there &= there; all_c0 &= c0; all_c1 &= c1;
+            }
+            for (int r = 0; r < n_rr; ++r) {                                           // (uniform)
+                const bool there = ((all_there >> r) & 1u) != 0u;
+                const bool car0 = ((all_c0 >> r) & 1u) != 0u, car1 = ((all_c1 >> r) & 1u) != 0u;
+                const unsigned long long m_n = __ballot(there), m_v0 = __ballot(there && car0);
+                for (int t = 0; t < n_tgt; ++t) {
+                    const bool hit = ((k_hit >> t) & 1u) != 0u;
+                    const unsigned long long m_s = __ballot(there && hit), m_v1 = __ballot(there && (hit ? car1 : car0));
+                    if (lane == 0) {
+                        uint32_t* const p = part[wave][t * n_rr + r];
+                        p[0] = (uint32_t)__popcll(m_n); p[1] = (uint32_t)__popcll(m_v0); p[2] = (uint32_t)__popcll(m_s);
+                        p[3] = (uint32_t)__popcll(m_v1);
+                    }
+                }
+            }
+            __syncthreads();
+            if ((int)threadIdx.x < SPP_COUNTERS * n_cells) {                           // (4 * 32 = 128 < SPB_BLOCK)
+                const int c = threadIdx.x / SPP_COUNTERS, q = threadIdx.x % SPP_COUNTERS;
+                uint32_t sum = 0;
+                for (int w = 0; w < SPB_BLOCK / WAVE; ++w) sum += part[w][c][q];
+                if (sum) atomicAdd(&out[(((size_t)g * n_reps + j) * n_cells + c) * SPP_COUNTERS + q], sum);
+            }
+            __syncthreads();
+        }
+    }
+}

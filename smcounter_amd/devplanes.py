@@ -804,7 +804,8 @@ class DsRule:
     @property
     def flag(self) -> str:
         if self.spike_rpb_cell:
-            return "--spikeIndelRpb" if getattr(self.spike, "indels", False) else "--spikeRpb"
+            # (--spikePhaseRpb's cells are --spikeIndelRpb's under another flag: the SpikeSet carries its name)
+            return getattr(self.spike, "rpb_flag", None) or ("--spikeIndelRpb" if getattr(self.spike, "indels", False) else "--spikeRpb")
         if self.spike is not None:
             return "--spikeDepth" if self.spike_cell else "--spikeAF"
         if self.depth is not None:
@@ -1683,19 +1684,28 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     `rpb` with `indel_counters` (--spikeIndelRpb): the list may hold insertions and deletions.  The flag byte per record comes from
     smc_spike_indel_read_bits - bits 1 / 2 / 3 = alt0 / alt1 / touch -, its per-barcode sums must equal the four counters above, and the
     counts come from smc_spike_indel_rpb_counts.  The second count is the same: an indel copy has pools of its own, but its records
-    stand in the run's order and number, so the read mask selects the same records and select_run hands on the copy's pools."""
+    stand in the run's order and number, so the read mask selects the same records and select_run hands on the copy's pools.
+    `rpb` with "flag" "--spikePhaseRpb", `indel_counters` and `phase` (--spikePhaseRpb): phase sets on the reads-per-barcode axis.  The
+    per-variant counts are drawn with the leaders' positions; the covering records of every (joint barcode, member) become one CSR
+    (spike_joint_records, kept in phase["joint_records"]) and one smc_spike_phase_rpb_counts call with this seed gives
+    phase["rpb_counts"], per set and cell dict(N_ALL, V0_ALL, S_ALL, V1_ALL) over the reads the cell keeps.  They are counted a second
+    way as well: the read selections hand back smc_allele_carriers' cover and carrier bits as identities, and per set and cell the AND
+    over the members - on the selection of the spiked copy of t for N_ALL' and V1_ALL', on that of the run itself for V0_ALL' - must
+    give the same numbers, else RuntimeError naming set and cell.  The refusals and DsRule.flag name --spikePhaseRpb."""
     from .tools import ds_allele_fraction as af
     from .tools import spike_variants as sv
     af.unique_idents(bamio.placed_barcodes(path), path)
     nthreads = nthreads or bamio.host_threads()
     if rpb is not None:
         # (--spikeIndelRpb - `indel_counters` - lifts the indel part; an indel in the list without it is --spikeRpb's to refuse)
-        if depth is not None or phase is not None or (not indel_counters and any(v.kind != af.SNV for v in variants)):
+        # (--spikePhaseRpb - rpb["flag"], with `indel_counters` - lifts the phase part as well)
+        phase_rpb = indel_counters and rpb.get("flag") == "--spikePhaseRpb"
+        if depth is not None or (phase is not None and not phase_rpb) or (not indel_counters and any(v.kind != af.SNV for v in variants)):
             raise ValueError("--spikeRpb: cells of barcode depths, phase sets or indel spike-ins are not built")
         # (the file-wide table of the UNSPIKED file serves every cell and replicate: spiking changes no name, barcode or record count -
         # an indel rewrite changes a record's length and CIGAR only)
         read_rules = philox_read_rules(path, list(rpb["targets"]), [params_list[0]] * len(rpb["targets"]), seed, eng, nthreads=nthreads,
-                                       flag="--spikeIndelRpb" if indel_counters else "--spikeRpb")
+                                       flag=rpb.get("flag") or ("--spikeIndelRpb" if indel_counters else "--spikeRpb"))
         try:
             return _spike_rules(path=path, fasta=fasta, variants=variants, targets=targets, params_list=params_list, seed=seed, eng=eng,
                                 nthreads=nthreads, max_reads=max_reads, keep=keep, keep_bytes=keep_bytes, depth=depth, phase=phase,
@@ -1715,7 +1725,8 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
     from .tools import ds_allele_fraction as af
     from .tools import spike_variants as sv
     spikes = SpikeSet(variants, indels=indel_counters)
-    rpb_flag = "--spikeIndelRpb" if indel_counters else "--spikeRpb"
+    spikes.rpb_flag = (rpb or {}).get("flag")          # (--spikePhaseRpb: the flag DsRule.flag names for the cells)
+    rpb_flag = (rpb or {}).get("flag") or ("--spikeIndelRpb" if indel_counters else "--spikeRpb")
     P = params_list[0]
     rows = [[None] * len(variants) for _ in targets]
     psets = list(phase["sets"]) if phase is not None else []
@@ -1723,6 +1734,8 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
     records = [None] * len(variants)                   # (--spikeRpb) per variant spike_rpb_records' CSR of its covering records
     second_rpb = {}                                    # (--spikeRpb) (variant, target index, r index) -> [N', V0', V1'] counted on selections
     bits = {}                        # (--spikePhase) variant -> (identities that cover it, that carry it before, per target after)
+    rbits = {}                       # (--spikePhaseRpb) (variant, r index) -> [identities that carry it before on the selection at r, per target
+    #                                  (identities that cover it, that carry it) on the selection of the spiked copy]
     covers, counters = [None] * len(variants), [None] * len(variants)
     if keep is not None:
         keep.update(runs=[], covers=covers, counters=counters, spikes=spikes)
@@ -1755,7 +1768,7 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                         a = A["aln"][bad]
                         raise ValueError("%s: the record at %s:%d (l_seq %d, %d CIGAR operations) spans listed "
                                          "indels that could take l_seq or the CIGAR beyond 65535: whether it takes one would depend on the "
-                                         "draws of the others" % ("--spikeIndelRpb" if rpb is not None else "--spikeIndelReps / --spikeIndelDepth",
+                                         "draws of the others" % (rpb_flag if rpb is not None else "--spikeIndelReps / --spikeIndelDepth",
                                                                   v0.chrom, int(a["pos"]) + 1, int(a["l_seq"]), int(a["n_cig"])))
                 idents = dec.barcode_idents(A["n_bc"])
                 nm, n_indel = dec.run_mismatches(len(A["aln"]))
@@ -1781,22 +1794,35 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                     sel, sel_counts, d_orig = select_run(eng, run, A, lo, d_mask=read_masks[0].data_ptr() + 4 * read_masks[1] * r, level="read")
                     try:
                         cov_r, car_r, _ = allele_carriers_run(eng, sel, sel_counts, lo, var, ins)
+                        who = None
+                        if psets and rpb is not None:
+                            # (--spikePhaseRpb: the bits as identities - a read selection renumbers the kept records' barcode ids by
+                            # first kept appearance, so each new id is traced back through the kept records' places in the run)
+                            orig = d_orig.download(np.uint32, sel.n_aln) if sel.n_aln else np.zeros(0, np.uint32)
+                            new = sel.aln.download(np.uint8, 36 * sel.n_aln).view(abi.DEV_ALN_DTYPE)["bc_gid"] if sel.n_aln else orig
+                            of_new = np.zeros(cov_r.shape[1], np.uint64)
+                            of_new[new.astype(np.int64)] = idents[A["aln"]["bc_gid"][orig].astype(np.int64)]
+                            who = [(of_new[cov_r[x]], of_new[car_r[x]]) for x in range(len(group))]
                     finally:
                         sel.free(shared=False); d_orig.free()
-                    return cov_r.sum(axis=1), car_r.sum(axis=1)
+                    return cov_r.sum(axis=1), car_r.sum(axis=1), who
                 for r in range(len(read_rules or ())):
-                    n_r, car_r = read_selected(up, r)
+                    n_r, car_r, who = read_selected(up, r)
                     for x, k in enumerate(group):
                         for t in range(len(targets)):
                             second_rpb[(k, t, r)] = [int(n_r[x]), int(car_r[x]), None]
+                        if who is not None:
+                            rbits[(k, r)] = [who[x][1], [None] * len(targets)]
                 for t, target in enumerate(targets):
                     svar, sorder = spikes.chrom_variants(v0.chrom, target)
                     spiked, stats = spike_copy(eng, up, A, spikes, v0.chrom, svar, idents, seed, P.mismatchThr, nm, n_indel)
                     try:
                         cov1, car1, cnt1 = allele_carriers_run(eng, spiked, A, lo, var, ins, counts=True)
                         for r in range(len(read_rules or ())):
-                            n_r, car_r = read_selected(spiked, r)
+                            n_r, car_r, who = read_selected(spiked, r)
                             for x, k in enumerate(group):
+                                if who is not None:
+                                    rbits[(k, r)][1][t] = who[x]
                                 if second_rpb[(k, t, r)][0] != int(n_r[x]):
                                     raise RuntimeError("%s: %s:%d at %g x target %g: the read selection keeps %d covering barcodes of "
                                                        "the run and %d of its spiked copy" % (rpb_flag, variants[k].chrom, variants[k].pos, target,
@@ -1957,6 +1983,25 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                 cells = phase_counts(eng, lead, joint, s0, thr, [frac_threshold(f) for f in fracs])[:, 0]
                 phase["depth_counts"] = [[dict(zip(names, (int(x) for x in cells[g, t, f]))) for t in range(len(targets))
                                           for f in range(len(fracs))] for g in range(len(psets))]
+            if rpb is not None:
+                # (--spikePhaseRpb: the joint numbers over the reads each cell keeps, counted per record - and a second time as the
+                # AND over the members of the selections' bits: on the spiked copy of t for N_ALL' and V1_ALL', on the run for V0_ALL')
+                joint_records = spike_joint_records(psets, covers, records)
+                cells = spike_phase_rpb_counts(eng, lead, [len(ps.members) for ps in psets], joint_records, s0, thr,
+                                               [r.thr for r in read_rules])[:, 0]
+                for g, ps in enumerate(psets):
+                    for t in range(len(targets)):
+                        for r in range(len(read_rules)):
+                            n_all = functools.reduce(np.intersect1d, [rbits[(k, r)][1][t][0] for k in ps.members])
+                            mine = [len(n_all), len(functools.reduce(np.intersect1d, [n_all] + [rbits[(k, r)][0] for k in ps.members])),
+                                    both([rbits[(k, r)][1][t][1] for k in ps.members])]
+                            if [int(cells[g, t, r, c]) for c in (0, 1, 3)] != mine:
+                                raise RuntimeError("%s: set %s at %g x target %g: the counts call says (N_ALL, V0_ALL, V1_ALL) = %r, the "
+                                                   "selection of the spiked copy %r" % (rpb_flag, ps.name, targets[t], rpb["targets"][r],
+                                                                                        [int(cells[g, t, r, c]) for c in (0, 1, 3)], mine))
+                phase["joint_records"] = joint_records
+                phase["rpb_counts"] = [[dict(zip(names, (int(x) for x in cells[g, t, r]))) for t in range(len(targets))
+                                        for r in range(len(read_rules))] for g in range(len(psets))]
         except BaseException:
             if keep is not None:
                 free_af_runs(keep["runs"])
@@ -2470,6 +2515,76 @@ def spike_indel_phase_counts(eng, lead_positions, joint, seeds, thresholds, dept
                                thresholds, depth_thresholds)
 
 
+def spike_joint_records(sets, covers, records):
+    """Per phase set -> (uint64 [n]: the identities of the barcodes that cover EVERY member, ascending - spike_joint's first array;
+    uint32 [n * M + 1]: the offsets of the (joint barcode, member) segments, barcode-major and the members in the set's order; uint64
+    name identities; uint8 flag bytes) - what spike_phase_rpb_counts takes.  covers[v]: per listed variant its covering identities;
+    records[v]: its spike_rpb_records CSR over them.  The members of one set may lie in different runs of the pre-pass: they are joined
+    by identity.  A record that spans several members stands in the segment of each."""
+    out = []
+    for s in sets:
+        ids = [np.asarray(covers[k], np.uint64) for k in s.members]
+        both = np.unique(functools.reduce(np.intersect1d, ids))
+        n, M = len(both), len(s.members)
+        start, length = np.zeros((n, M), np.int64), np.zeros((n, M), np.int64)
+        base, pools = 0, []
+        for m, (k, x) in enumerate(zip(s.members, ids)):
+            o, names, flags = records[k]
+            o = np.asarray(o, np.int64)
+            if len(o) != len(x) + 1 or len(names) != len(flags):
+                raise ValueError("spike_joint_records: set %s, member %d: %d covering barcodes, %d offsets over %d names and %d flags" %
+                                 (s.name, m, len(x), len(o), len(names), len(flags)))
+            order = np.argsort(x, kind="stable")
+            at = order[np.searchsorted(x[order], both)] if n else np.zeros(0, np.int64)
+            start[:, m], length[:, m] = o[at] + base, o[at + 1] - o[at]
+            base += len(names)
+            pools.append((np.asarray(names, np.uint64), np.asarray(flags, np.uint8)))
+        off = np.zeros(n * M + 1, np.int64)
+        off[1:] = np.cumsum(length.reshape(-1))
+        # (every segment's records, segment after segment: the index of record i of segment s is start[s] + i)
+        take = np.repeat(start.reshape(-1) - off[:-1], length.reshape(-1)) + np.arange(int(off[-1]), dtype=np.int64)
+        name = np.concatenate([p[0] for p in pools])[take] if int(off[-1]) else np.zeros(0, np.uint64)
+        flag = np.concatenate([p[1] for p in pools])[take] if int(off[-1]) else np.zeros(0, np.uint8)
+        out.append((both, off.astype(np.uint32), np.ascontiguousarray(name), np.ascontiguousarray(flag)))
+    return out
+
+
+def spike_phase_rpb_counts(eng, lead_positions, set_members, joint_records, seeds, thresholds, read_thresholds) -> np.ndarray:
+    """smc_spike_phase_rpb_counts -> uint32 [G, R, T, Rr, 4] = (N_ALL', V0_ALL', S_ALL', V1_ALL') of every phase set, replicate and cell
+    (spike target x reads-per-barcode target), counted over the reads each cell keeps.  lead_positions[g]: the 1-based position of the
+    set's leader; set_members[g]: M_g; joint_records[g]: spike_joint_records' (joint identities [n_g], segment offsets [n_g * M_g + 1],
+    name identities, flag bytes); seeds, thresholds, read_thresholds: spike_rpb_counts'."""
+    G = len(joint_records)
+    set_m = np.array([int(m) for m in set_members], np.uint32)
+    off = np.zeros(G + 1, np.uint32)
+    off[1:] = np.cumsum([len(j[0]) for j in joint_records])
+    seg_base = np.zeros(G, np.uint32)
+    rec_off, base, n_seg = [np.zeros(1, np.int64)], 0, 0
+    for g, (ids, o, names, flags) in enumerate(joint_records):
+        o = np.asarray(o, np.int64)
+        if len(o) != len(ids) * int(set_m[g]) + 1 or len(names) != len(flags) or int(o[0]) != 0 or int(o[-1]) != len(names):
+            raise ValueError("spike_phase_rpb_counts: set %d: %d joint barcodes of %d members, %d offsets over %d names and %d flags" %
+                             (g, len(ids), int(set_m[g]), len(o), len(names), len(flags)))
+        seg_base[g] = n_seg
+        rec_off.append(o[1:] + base)
+        base += len(names)
+        n_seg += len(o) - 1
+    rec_off = np.concatenate(rec_off).astype(np.uint32)
+    ident = np.concatenate([np.asarray(j[0], np.uint64) for j in joint_records]) if G else np.zeros(0, np.uint64)
+    name = np.concatenate([np.asarray(j[2], np.uint64) for j in joint_records]) if G else np.zeros(0, np.uint64)
+    flag = np.concatenate([np.asarray(j[3], np.uint8) for j in joint_records]) if G else np.zeros(0, np.uint8)
+    pos = np.array([int(p) & 0xFFFFFFFF for p in lead_positions], np.uint32)
+    seeds = np.ascontiguousarray(seeds, np.uint64)
+    thr, rthr = np.ascontiguousarray(thresholds, np.uint64), np.ascontiguousarray(read_thresholds, np.uint64)
+    return _spike_counts_call(
+        eng, "smc_spike_phase_rpb_counts", [ident, off, set_m, seg_base, rec_off, name, flag, pos, seeds],
+        (G, len(seeds), len(thr), len(rthr), 4),
+        lambda d, d_out: eng.L.smc_spike_phase_rpb_counts(eng.ctx, d[0], d[1], off.ctypes.data, d[2], set_m.ctypes.data, d[3],
+                                                          seg_base.ctypes.data, d[4], rec_off.ctypes.data, d[5], d[6], len(name), d[7], G,
+                                                          d[8], len(seeds), thr.ctypes.data, len(thr), rthr.ctypes.data, len(rthr), d_out,
+                                                          ctypes.c_void_p(0)))
+
+
 def spike_copy_strides(n_aln: int, n_pairs: int):
     """The byte strides between the copies of one smc_spike_alleles_reps call: a copy's records / pair pool rounded up to 256 bytes."""
     return (36 * max(1, n_aln) + 255) & ~255, (2 * max(1, n_pairs) + 255) & ~255
@@ -2616,11 +2731,19 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
         copies = [RunOnDevice(_BufView(made["aln"], c * sa), _BufView(made["cig"], c * sc), _BufView(made["bq"], c * sb), up.loc, up.ref, up.n_aln,
                               up.loc_host, pairs_used=int(made["totals"][c, 0])) for c in range(B)]
         af_var, af_ins = af_run_variants([variants[k] for k in run.group], chrom, lo, fasta)
-    flag = ("--spikeIndelRpb" if indel is not None else "--spikeRpb") if read_cells else "--spikeDepth" if cells else "--spikeReps"
+    flag = (read_cells.get("flag") or ("--spikeIndelRpb" if indel is not None else "--spikeRpb")) if read_cells else \
+        "--spikeDepth" if cells else "--spikeReps"
 
-    def check_carriers(c, sel, counts, want, what):
-        """(N, V1) of every variant of the run on copy c (or its selection) by smc_allele_carriers against the counts call's."""
+    def check_carriers(c, sel, counts, want, what, read=None, idents_of=None):
+        """(N, V1) of every variant of the run on copy c (or its selection) by smc_allele_carriers against the counts call's.  With
+        indel["bits"] (--spikePhaseRpb) the cover and carrier bits of the sets' members on the selection at `read` are kept as
+        identities - idents_of(): the identity of every barcode id of the selection -, key (variant, copy, read)."""
         cov, car, _ = allele_carriers_run(eng, sel, counts, lo, af_var, af_ins)
+        if idents_of is not None and indel.get("bits") is not None:
+            ids = idents_of()
+            for g, k in enumerate(run.group):
+                if k in indel["members"]:
+                    indel["bits"][(k, c, read)] = (ids[cov[g][:len(ids)]], ids[car[g][:len(ids)]])
         for g, k in enumerate(run.group):
             mine = (int(cov[g].sum()), int(car[g].sum()))
             if mine != tuple(int(x) for x in want[g]):
@@ -2662,7 +2785,8 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
                     bc_idents = lambda n, old_bc=old_bc: run.idents[old_bc()]
                     if indel is not None:
                         try:
-                            check_carriers(c, sel, counts, indel["want_cells"][read][c], " x target %g" % read_cells["targets"][read])
+                            check_carriers(c, sel, counts, indel["want_cells"][read][c], " x target %g" % read_cells["targets"][read],
+                                           read, lambda old_bc=old_bc: run.idents[old_bc()])
                         except BaseException:
                             sel.free(shared=False); d_orig.free()
                             raise
@@ -2772,7 +2896,10 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
     is also selected per r with the keep masks of ITS seed - one ReadGroups.masks call per seed and run - and built
     (_spike_rep_call's `read_cells`): `rows` then also holds (variant index, T + t x Rr + r, replicate).  With four counters
     (--spikeIndelRpb) the counts come from smc_spike_indel_rpb_counts and the copies from smc_spike_indels_reps; beside READS every copy's
-    (N, V1), and every cell's (N', V1') on its selection, must equal the counts calls'."""
+    (N, V1), and every cell's (N', V1') on its selection, must equal the counts calls'.
+    `rpb` with `phase` (--spikePhaseRpb: phase["joint_records"] from the pre-pass): one smc_spike_phase_rpb_counts call with all R
+    seeds gives "phase_rpb_counts", uint32 [G, R, T, Rr, 4]; per copy and cell the AND over a set's members of the selection's cover and
+    carrier bits must give its (N_ALL', V1_ALL') (_check_joint_bits)."""
     import time
     from . import dsaf
     from .tools import spike_variants as sv
@@ -2796,7 +2923,7 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
         if depth is not None:
             depth_counts = (spike_indel_counts if four else spike_depth_counts)(eng, spikes.lead_pos, keep["covers"], keep["counters"], seeds, thr,
                                                                                 [frac_threshold(f) for f in depth["fracs"]])
-        phase_counts = phase_depth_counts = None
+        phase_counts = phase_depth_counts = phase_rpb_counts = joint_bits = None
         if phase is not None and phase.get("joint"):
             lead = [spikes.lead_pos[s.members[0]] for s in phase["sets"]]
             joint_counts = spike_indel_phase_counts if four else spike_phase_counts
@@ -2808,6 +2935,12 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
             F = len(rpb["targets"])
             read_rules = rpb["rules"][:F]
             rpb_counts = spike_rpb_counts(eng, spikes.lead_pos, keep["covers"], keep["records"], seeds, thr, [r.thr for r in read_rules], four=four)
+            if phase is not None and phase.get("joint_records"):
+                # (--spikePhaseRpb: one call with all R seeds over the (joint barcode, member) records of the pre-pass)
+                phase_rpb_counts = spike_phase_rpb_counts(eng, [spikes.lead_pos[s.members[0]] for s in phase["sets"]],
+                                                          [len(s.members) for s in phase["sets"]], phase["joint_records"], seeds, thr,
+                                                          [r.thr for r in read_rules])
+                joint_bits, seen = {}, set()
         times["counts"] = time.perf_counter() - t0
         for run in keep["runs"]:
             if run.A is None:
@@ -2844,7 +2977,11 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
                                    rpb_counts=rpb_counts,
                                    params_list=params_list, fasta=fasta, variants=variants, max_depth=max_depth, sampler=sampler,
                                    sampler_seed=sampler_seed, depth=depth, rpb=rpb, seed_masks=seed_masks, keep=keep, spikes=spikes,
-                                   four=four, room=room, n_reps=n_reps, rows=rows, times=times)
+                                   four=four, room=room, n_reps=n_reps, rows=rows, times=times, joint_bits=joint_bits,
+                                   members={k for s in phase["sets"] for k in s.members} if joint_bits is not None else ())
+                if joint_bits is not None:
+                    seen.update(run.group)
+                    _check_joint_bits(phase["sets"], seen, joint_bits, phase_rpb_counts, seeds, targets, rpb["targets"], read_rules[0].flag)
             finally:
                 for buf, _, _ in seed_masks.values():
                     buf.free()
@@ -2854,11 +2991,29 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
         free_af_runs(keep["runs"])
     times["stage"] = time.perf_counter() - t_start
     return dict(seeds=seeds, counts=counts, rows=rows, times=times, depth_counts=depth_counts, phase_counts=phase_counts,
-                phase_depth_counts=phase_depth_counts, rpb_counts=rpb_counts)
+                phase_depth_counts=phase_depth_counts, rpb_counts=rpb_counts, phase_rpb_counts=phase_rpb_counts)
+
+
+def _check_joint_bits(sets, seen, joint_bits, counts, seeds, targets, rpb_targets, flag):
+    """(--spikePhaseRpb) Every set whose members' runs are all done (`seen`: the variants so far): per copy and cell the AND over the
+    members of the selection's cover / carrier identities (joint_bits[(variant, target, r, replicate)], dropped here) against (N_ALL',
+    V1_ALL') of the counts call, uint32 [G, R, T, Rr, 4].  A difference raises RuntimeError."""
+    for g, ps in enumerate(sets):
+        if not all(k in seen for k in ps.members) or (ps.members[0], 0, 0, 0) not in joint_bits:
+            continue
+        for t in range(len(targets)):
+            for r in range(len(rpb_targets)):
+                for j in range(len(seeds)):
+                    got = [joint_bits.pop((k, t, r, j)) for k in ps.members]
+                    mine = [len(functools.reduce(np.intersect1d, [x[c] for x in got])) for c in (0, 1)]
+                    if mine != [int(counts[g, j, t, r, c]) for c in (0, 3)]:
+                        raise RuntimeError("%s: set %s, seed %d at %g x target %g: the copy's selection holds (N_ALL, V1_ALL) = %r, the counts "
+                                           "call says %r" % (flag, ps.name, int(seeds[j]), targets[t], rpb_targets[r], mine,
+                                                             [int(counts[g, j, t, r, c]) for c in (0, 3)]))
 
 
 def _spike_rep_targets(*, eng, run, svar, var_at, seeds, thr, counts, depth_counts, rpb_counts, params_list, fasta, variants, max_depth, sampler,
-                       sampler_seed, depth, rpb, seed_masks, keep, spikes, four, room, n_reps, rows, times):
+                       sampler_seed, depth, rpb, seed_masks, keep, spikes, four, room, n_reps, rows, times, joint_bits=None, members=()):
     """spike_replicates' calls for one kept run: per target as many replicates per _spike_rep_call as `room` allows; `rows` and `times`
     are filled.  seed_masks[j] (--spikeRpb): _run_read_masks' of replicate j."""
     T = len(params_list)
@@ -2877,17 +3032,21 @@ def _spike_rep_targets(*, eng, run, svar, var_at, seeds, thr, counts, depth_coun
                 n_cov = [len(keep["covers"][k]) for k in run.group]
                 indel = dict(ins=spikes.ins[run.chrom], want=[[(n, int(counts[k, j, t, 2])) for k, n in zip(run.group, n_cov)] for j in js],
                              want_cells=[[[(int(cell_counts[k, j, t, f, 0]), int(cell_counts[k, j, t, f, 4])) for k in run.group]
-                                          for j in js] for f in range(F)])
+                                          for j in js] for f in range(F)],
+                             bits={} if joint_bits is not None else None, members=members)
             read_cells = None
             if rpb is not None:
                 read_cells = dict(params=rpb["params"][t * F:(t + 1) * F], masks=[seed_masks[j][0].data_ptr() for j in js],
-                                  n_words=seed_masks[js[0]][1], targets=list(rpb["targets"]))
+                                  n_words=seed_masks[js[0]][1], targets=list(rpb["targets"]), flag=rpb.get("flag"))
             out = _spike_rep_call(*args, bits, cells, indel, read_cells)
             if out == NARROW:
                 eng.word_bits = 32
                 out = _spike_rep_call(*args, 32, cells, indel, read_cells)
                 times["rewrites"] += 1
             full, of_cell = out if (cells or read_cells) else (out, [])
+            if joint_bits is not None:
+                for (k, c, r), val in indel["bits"].items():
+                    joint_bits[(k, t, r, js[c])] = val
             for c, part in [(t, full)] + [(T + t * F + f, part) for f, part in enumerate(of_cell)]:
                 for j, text in zip(js, part):
                     for k, line in zip(run.group, text):

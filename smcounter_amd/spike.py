@@ -28,6 +28,10 @@ with RPB as their axis column (RPB_AXIS).
 --spikeIndelRpb: --spikeRpb on the --spikeIndels spike-in (indel_flags refuses what does not go with it, indel_rpb_cells makes the cells
 as rpb_cells does); the outputs' kind, the pages and their writers are --spikeRpb's.
 
+--spikePhaseRpb: phase sets on the reads-per-barcode axis (phase_rpb_cells: the flag's refusals and --spikeRpb's cells); the run
+writes what --spikeIndelRpb and --spikeIndelPhase write and, with RPB as the phase pages' axis column, <outPrefix>.spikeAF.rpb.phase.txt,
+.rpb.phase.replicates.txt and .rpb.phase.sensitivity.txt - the joint numbers over the reads each cell keeps.
+
 The semantics are tools/spike_variants.py's (DESIGN.md "--spikeAF"); the rewrite on the GPU is csrc/k_spike.inc (smc_spike_alleles),
 the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the main pass are devplanes.spike_rules / spike_run.
 """
@@ -84,7 +88,7 @@ def variants(args, loc_list, fasta, indels: bool = False):
     --spikePhase MNV lines and PS= sets as well, with --spikeIndels - or `indels`: --spikeIndelReps, --spikeIndelDepth - insertions and
     deletions whose footprints do not overlap, with --spikeIndelPhase both), REF the genome's letters, every variant a locus of --bedTarget."""
     try:
-        both = bool(getattr(args, "spikeIndelPhase", False))
+        both = bool(getattr(args, "spikeIndelPhase", False)) or getattr(args, "spikePhaseRpb", None) not in (None, "")
         out = sv.parse_variants(args.spikeVariants, "--spikeVariants", phased=both or bool(getattr(args, "spikePhase", False)),
                                 indels=both or bool(indels) or bool(getattr(args, "spikeIndels", False)))
         sv.check_reference(out, fasta, "--spikeVariants")
@@ -508,12 +512,60 @@ def indel_rpb_cells(args, spike_targets):
     return _rpb_cells(text, spike_targets, "spikeIndelRpb")
 
 
+# ---- --spikePhaseRpb
+def phase_rpb_cells(args, spike_targets):
+    """--spikePhaseRpb -> rpb_cells' (reads-per-barcode targets, cells), or (None, []) without the flag.  The flag implies the rules of
+    --spikeIndelPhase (and so of --spikeIndels and --spikePhase) and takes the targets as --spikeIndelRpb does.  SystemExit, each naming
+    the flag to use instead where there is one: beside --spikeRpb or --spikeIndelRpb (this flag takes the targets), beside
+    --spikeIndels, --spikePhase or --spikeIndelPhase (implied), beside --spikeReps (--spikeIndelReps), beside --spikeDepth or
+    --spikeIndelDepth (not built); without --spikeAF; text that is no list of numbers, a target <= 0 or listed twice, beyond MAX_CELLS
+    cells."""
+    text = getattr(args, "spikePhaseRpb", None)
+    if text in (None, ""):
+        return None, []
+    for flag in ("spikeRpb", "spikeIndelRpb"):
+        if getattr(args, flag, None) not in (None, ""):
+            raise SystemExit("--spikePhaseRpb cannot be combined with --%s in one run: --spikePhaseRpb takes the targets" % flag)
+    for flag in ("spikeIndels", "spikePhase", "spikeIndelPhase"):
+        if getattr(args, flag, False):
+            raise SystemExit("--spikePhaseRpb implies the rules of --%s: leave --%s out" % (flag, flag))
+    if getattr(args, "spikeReps", None) not in (None, ""):
+        raise SystemExit("--spikePhaseRpb cannot be combined with --spikeReps in one run: use --spikeIndelReps R beside it")
+    for flag in ("spikeDepth", "spikeIndelDepth"):
+        if getattr(args, flag, None) not in (None, ""):
+            raise SystemExit("--spikePhaseRpb cannot be combined with --%s in one run (phase sets in cells of barcode depths and "
+                             "reads-per-barcode targets are not built)" % flag)
+    if not spike_targets:
+        raise SystemExit("--spikePhaseRpb thins the reads of the --spikeAF spike-ins, phase sets among them: it needs --spikeAF and "
+                         "--spikeVariants")
+    return _rpb_cells(text, spike_targets, "spikePhaseRpb")
+
+
 # ---- --spikePhase
-PHASE_HEADER = ("SET", "CHROM", "POSITIONS", "REFS", "ALTS", "TARGET", "FRACTION", "MTDEPTH", "N_ALL", "V0_ALL", "S_ALL", "V1_ALL", "AF_ALL",
-                "CALLED_ALL")
-PHASE_REPLICATES_HEADER = PHASE_HEADER[:8] + ("REP", "SEED") + PHASE_HEADER[8:]
-PHASE_SENSITIVITY_HEADER = PHASE_HEADER[:8] + ("REPS", "CALLED_ALL", "RATE", "LO95", "HI95", "AF_MEAN", "AF_MIN", "AF_MAX")
 PHASE_NAMES = ("N_ALL", "V0_ALL", "S_ALL", "V1_ALL")
+
+
+def phase_header(axis=DEPTH_AXIS):
+    return ("SET", "CHROM", "POSITIONS", "REFS", "ALTS", "TARGET", axis[1], "MTDEPTH") + PHASE_NAMES + ("AF_ALL", "CALLED_ALL")
+
+
+def phase_replicates_header(axis=DEPTH_AXIS):
+    h = phase_header(axis)
+    return h[:8] + ("REP", "SEED") + h[8:]
+
+
+def phase_sensitivity_header(axis=DEPTH_AXIS):
+    return phase_header(axis)[:8] + ("REPS", "CALLED_ALL", "RATE", "LO95", "HI95", "AF_MEAN", "AF_MIN", "AF_MAX")
+
+
+PHASE_HEADER = phase_header()
+PHASE_REPLICATES_HEADER = phase_replicates_header()
+PHASE_SENSITIVITY_HEADER = phase_sensitivity_header()
+
+
+def _phase_page(out_prefix: str, axis, page: str) -> str:
+    # (the barcode fractions' pages are .spikeAF.phase<page>; another axis puts its infix in front: .spikeAF.rpb.phase<page>)
+    return "%s.spikeAF.%sphase%s.txt" % (out_prefix, "" if axis is DEPTH_AXIS else axis[0] + ".", page)
 
 
 def phase(args, spike_targets) -> bool:
@@ -570,33 +622,34 @@ def phase_sensitivity_line(pset, variants, target, frac, mt_depth, per) -> str:
                       dsaf.frac_text(sum(afs) / n), dsaf.frac_text(min(afs)), dsaf.frac_text(max(afs))])
 
 
-def write_phase(out_prefix: str, variants, sets, outputs) -> None:
+def write_phase(out_prefix: str, variants, sets, outputs, axis=DEPTH_AXIS) -> None:
     """<outPrefix>.spikeAF.phase.txt: a header, then for every set a line per output - full depth first, then the targets, then the
     --spikeDepth cells.  `outputs`: per output (target or None, fraction or None, mtDepth, prefix, per set dict(N_ALL, V0_ALL, S_ALL,
-    V1_ALL))."""
+    V1_ALL)).  `axis` (RPB_AXIS: --spikePhaseRpb): the page is .spikeAF.<axis[0]>.phase.txt, the outputs are the cells and their
+    second field - the reads-per-barcode target - stands under the column axis[1]."""
     cuts = [dsaf.read_output(o[3])[1] for o in outputs]
-    with open(out_prefix + ".spikeAF.phase.txt", "w") as fh:
-        fh.write("\t".join(PHASE_HEADER) + "\n")
+    with open(_phase_page(out_prefix, axis, ""), "w") as fh:
+        fh.write("\t".join(phase_header(axis)) + "\n")
         for g, pset in enumerate(sets):
             for (target, frac, depth, _, rows), cut in zip(outputs, cuts):
                 fh.write(phase_line(pset, variants, target, frac, depth, rows[g], called_all(pset, variants, cut)) + "\n")
 
 
-def write_phase_replicates(out_prefix: str, variants, sets, outputs, seeds, entries) -> None:
+def write_phase_replicates(out_prefix: str, variants, sets, outputs, seeds, entries, axis=DEPTH_AXIS) -> None:
     """<outPrefix>.spikeAF.phase.replicates.txt: a line per set, output (targets, then cells: (target, fraction or None, mtDepth)) and
-    replicate.  entries[(set, output)]: per replicate (dict(N_ALL, V0_ALL, S_ALL, V1_ALL), CALLED_ALL)."""
-    with open(out_prefix + ".spikeAF.phase.replicates.txt", "w") as fh:
-        fh.write("\t".join(PHASE_REPLICATES_HEADER) + "\n")
+    replicate.  entries[(set, output)]: per replicate (dict(N_ALL, V0_ALL, S_ALL, V1_ALL), CALLED_ALL).  `axis`: write_phase's."""
+    with open(_phase_page(out_prefix, axis, ".replicates"), "w") as fh:
+        fh.write("\t".join(phase_replicates_header(axis)) + "\n")
         for g, pset in enumerate(sets):
             for c, (target, frac, depth) in enumerate(outputs):
                 for j, (r, called) in enumerate(entries[(g, c)]):
                     fh.write(phase_replicate_line(pset, variants, target, frac, depth, j, seeds[j], r, called) + "\n")
 
 
-def write_phase_sensitivity(out_prefix: str, variants, sets, outputs, entries) -> None:
+def write_phase_sensitivity(out_prefix: str, variants, sets, outputs, entries, axis=DEPTH_AXIS) -> None:
     """<outPrefix>.spikeAF.phase.sensitivity.txt: a line per set and output; the arguments are write_phase_replicates'."""
-    with open(out_prefix + ".spikeAF.phase.sensitivity.txt", "w") as fh:
-        fh.write("\t".join(PHASE_SENSITIVITY_HEADER) + "\n")
+    with open(_phase_page(out_prefix, axis, ".sensitivity"), "w") as fh:
+        fh.write("\t".join(phase_sensitivity_header(axis)) + "\n")
         for g, pset in enumerate(sets):
             for c, (target, frac, depth) in enumerate(outputs):
                 fh.write(phase_sensitivity_line(pset, variants, target, frac, depth, entries[(g, c)]) + "\n")

@@ -886,6 +886,36 @@ int smc_spike_phase_rpb_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, cons
                                int64_t n_rec, const uint32_t* d_pos1, int32_t n_sets, const uint64_t* d_seeds, int32_t n_reps,
                                const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out,
                                void* stream);
+
+/* (ABI 11, additive: one entry more, the version number unchanged) --spikeScan: one verdict per (copy, listed locus) of a called
+ * batch whose rows stay in HBM.  d_rows: n_copies x n_loci rows as a plan wrote them, copy c's locus l at c * n_loci + l.  d_listed /
+ * listed_host[n_listed]: the loci a pass planted an SNV at - `offset` the locus within a copy (below n_loci), `alt` the fixed allele
+ * id of the planted letter (A, T, G, C = 0 .. 3).  `thr`: the truncated-PI threshold of the .cut files (writers.pi_threshold).
+ *   d_out[c * n_listed + g] = { pi: cand[0].pi unrounded, vmt: cand[0].vmt, mt_verdict: the verdict in bits 30 - 31 above
+ *   min(used_mt, SMC_SCAN_MT_MASK) }.  With lo = thr - 0.005 - 1e-6 and hi = thr - 0.005 + 1e-6 in double:
+ *     SMC_SCAN_CALLED  status 0, not bi-allelic, cand[0].allele == alt and cand[0].pi > hi
+ *     SMC_SCAN_NOT     status 0, not bi-allelic, and cand[0].allele != alt or cand[0].pi < lo
+ *     SMC_SCAN_HOST    the rest: a bi-allelic row, a status that is not 0, a PI in [lo, hi] or NaN - the host prints and cuts the row
+ *   d_host_list[0 .. *d_n_host): the indices c * n_listed + g of the SMC_SCAN_HOST records, each once, in no fixed order (room for
+ *   n_copies * n_listed words); *d_n_host is zeroed by the call.  Nothing else is written.
+ * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched: an offset that is not below n_loci, an alt above 3, n_copies
+ * above 65535, n_copies * n_listed or n_copies * n_loci of 2^31 or more, a `thr` that is not finite. */
+typedef struct smc_scan_locus {
+    uint32_t offset;
+    uint32_t alt;
+} smc_scan_locus;
+typedef struct smc_scan_verdict {      /* 16 bytes */
+    double pi;
+    int32_t vmt;
+    uint32_t mt_verdict;
+} smc_scan_verdict;
+#define SMC_SCAN_NOT 0u
+#define SMC_SCAN_CALLED 1u
+#define SMC_SCAN_HOST 2u
+#define SMC_SCAN_MT_MASK 0x3FFFFFFFu
+int smc_scan_detect(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64_t n_loci, const smc_scan_locus* d_listed,
+                    const smc_scan_locus* listed_host, int32_t n_listed, double thr, smc_scan_verdict* d_out, uint32_t* d_host_list,
+                    uint32_t* d_n_host, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

@@ -53,6 +53,12 @@ assert SPIKE_VARIANT_DTYPE.itemsize == 16
 SPIKE_INDEL_VARIANT_DTYPE = np.dtype([("pos0", "<i4"), ("kind", "u1"), ("ref", "u1"), ("alt", "u1"), ("pad", "u1"), ("len", "<u2"),
                                       ("lead", "<u2"), ("ins_off", "<u4"), ("thr", "<u8")])
 assert SPIKE_INDEL_VARIANT_DTYPE.itemsize == 24
+# smc_scan_locus / smc_scan_verdict (smc_scan_detect): a listed locus of a called batch, and what the kernel says of it per copy - the
+# verdict in bits 30 - 31 of mt_verdict above the used MT
+SCAN_LOCUS_DTYPE = np.dtype([("offset", "<u4"), ("alt", "<u4")])
+SCAN_VERDICT_DTYPE = np.dtype([("pi", "<f8"), ("vmt", "<i4"), ("mt_verdict", "<u4")])
+assert SCAN_LOCUS_DTYPE.itemsize == 8 and SCAN_VERDICT_DTYPE.itemsize == 16
+SCAN_NOT, SCAN_CALLED, SCAN_HOST, SCAN_MT_MASK = 0, 1, 2, 0x3FFFFFFF
 
 
 def c_params(p: VcParams) -> SmcParams:

@@ -12,6 +12,7 @@ repeat BEDs are absent the repeat flags are skipped with a note instead of faili
 from __future__ import annotations
 
 import argparse
+import collections
 import dataclasses
 import datetime
 import os
@@ -255,6 +256,26 @@ def build_parser() -> argparse.ArgumentParser:
                         "per read on the GPU in one call; at most %d cells.  Not with --spikeRpb, --spikeIndelRpb (this flag takes the "
                         "targets), --spikeIndels, --spikePhase, --spikeIndelPhase (implied), --spikeReps (use --spikeIndelReps), "
                         "--spikeDepth or --spikeIndelDepth (not built).  Needs --spikeAF" % GRID_MAX_CELLS)
+    p.add_argument("--spikeScan", default=None,
+                   help="a measured detection-rate map of the whole target: comma-separated target allele fractions t in (0, 1).  One "
+                        "SNV, REF>ALT by --spikeScanAlt, is planted at every locus of --bedTarget whose genome letter is A, C, G or T, in "
+                        "passes: pass k holds the loci with pos mod --spikeScanStride == k, and is by definition the run --spikeAF "
+                        "<targets> --spikeVariants <the pass's list> --spikeReps R --dsSeed s (tools/spike_scan_lists.py writes the "
+                        "lists).  Every run of the file is decoded once; the replicates' rows stay on the GPU, which says per replicate "
+                        "and locus whether the SNV was called (smc_scan_detect) - only rows it cannot decide come to the host.  Writes "
+                        "<outPrefix>.spikeScan.sensitivity.txt (a line per locus and target: .spikeAF.sensitivity.txt's without the PI "
+                        "columns), .spikeScan.curve.txt (the rate at every target and T95), <outPrefix>.spikeScan<t>.rate.bedgraph per "
+                        "target and .spikeScan.t95.bedgraph (1 where no listed target reaches 0.95) beside --lod's theoretical bedgraph; "
+                        "no .spikeAF<t> output is written and the full-depth files stay as they are.  The cost grows with stride x R x "
+                        "targets whole-panel builds.  Needs --spikeScanReps; not with any other --spike* or --ds* flag but --dsSeed; "
+                        "one process only")
+    p.add_argument("--spikeScanReps", default=None, help="R, the replicates of every --spikeScan pass: an integer in %d .. %d; replicate j "
+                                                         "has seed (dsSeed + j) mod 2^64" % (REPS_MIN, REPS_MAX))
+    p.add_argument("--spikeScanStride", default=None, help="S, an integer >= 1 (default 256): two SNVs of a --spikeScan pass are at least "
+                                                           "S positions apart.  A smaller S means fewer passes and more reads shared "
+                                                           "between a pass's spike-ins")
+    p.add_argument("--spikeScanAlt", default=None, help="the ALT of --spikeScan: transition (default: A>G, G>A, C>T, T>C), transversion "
+                                                        "(A>C, C>A, G>T, T>G) or complement (A>T, T>A, C>G, G>C)")
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -271,6 +292,7 @@ def build_parser() -> argparse.ArgumentParser:
 REPS_MIN, REPS_MAX = 2, 1000   # (--dsAFReps: dsaf.REPS_MIN / REPS_MAX, SMC_AF_REP_MAX_REPS)
 AF_MAX_INS = 255             # (smc_allele_carriers: SMC_AF_MAX_INS letters per listed insertion)
 SPIKE_MAX_TARGETS = 32       # (--spikeAF: spike.MAX_TARGETS)
+SCAN_MAX_PASS_VARIANTS = 4096   # (--spikeScan: SMC_AF_MAX_VARIANTS, the variants of one chromosome a rewrite call takes)
 GRID_MAX_CELLS = 32          # (a launch takes at most SMC_RG_MAX_TARGETS masks; every cell holds a batch's device arrays)
 
 
@@ -434,6 +456,7 @@ class _Plan:
     spike_depth: dict = None    # (--spikeDepth) "fracs", the cells' "params", and once the rules are made "rules" and "counts" [V][T x F]
     spike_rpb: dict = None      # (--spikeRpb, --spikeIndelRpb, --spikePhaseRpb: then also "flag") "targets", the cells' "params", and once the rules are made "rules" and "counts" [V][T x Rr]
     spike_indel_counters: bool = False   # (--spikeIndelReps, --spikeIndelDepth, --spikeIndelPhase, --spikeIndelRpb, --spikePhaseRpb) the spike-ins are --spikeIndels', four counters per covering barcode
+    scan: dict = None           # (--spikeScan) spike.scan's dict; once the rules are made also "variants", "loci" and "passes"
     spike_phase: bool = False   # (--spikePhase, --spikeIndelPhase, --spikePhaseRpb) plan.spike then holds "phase": None, or devplanes.spike_rules' dict of the sets of two members or more
 
     @property
@@ -599,6 +622,7 @@ class _Shard:
     lod: list = None            # (--lod) per output what lod.run_lods made
     af_reps: dict = None        # (--dsAFReps) what devplanes.ds_af_replicates made
     spike_reps: dict = None     # (--spikeReps) what devplanes.spike_replicates made
+    scan: dict = None           # (--spikeScan) what devplanes.spike_scan made
 
 
 def call_shard(args, params: VcParams, loci, device: int, early=None, plan=None):
@@ -659,6 +683,8 @@ def call_shard(args, params: VcParams, loci, device: int, early=None, plan=None)
         shard.af_reps = _ds_af_replicates(args, plan, ref, eng, loci, shard.ds)
     if plan is not None and plan.spike is not None and plan.spike.get("keep") is not None:
         shard.spike_reps = _spike_replicates(args, plan, ref, eng, loci, shard.ds)
+    if plan is not None and plan.scan is not None:
+        shard.scan = _spike_scan(args, plan, ref, eng, params)
     if lod_cols is not None:
         shard.lod = _lod.run_lods(eng, [o.params for o in outputs], lod_cols, args.lodDepth or "UMT")
     _release_engine(eng, keep=resident)
@@ -705,6 +731,28 @@ def _spike_replicates(args, plan, ref, eng, loci, ds_rows):
         if j == 0 and line != ds_rows[t][index[(v.chrom, v.pos)]]:
             raise RuntimeError("--spikeReps: replicate 0 of %s:%d in %s is not the row of the run's own output:\n%s\n%s" %
                                (v.chrom, v.pos, outs[t].prefix, line, ds_rows[t][index[(v.chrom, v.pos)]]))
+    return out
+
+
+def _repeat_tracks(args):
+    """The two repeat tracks of the command line as postfilter.load_repeat_regions takes them: None for one not given or not found."""
+    return [b if b and os.path.exists(b) else None for b in (args.bedTandemRepeats, args.bedRepeatMaskerSubset)]
+
+
+def _spike_scan(args, plan, ref, eng, params):
+    """--spikeScan after the run's batches: devplanes.spike_scan over every run of the file, and a line per pass in the run log."""
+    scan = plan.scan
+    threshold = writers.pi_threshold(params.mtDepth, args.threshold)
+    repeats = postfilter.load_repeat_regions(args.bedTarget, *_repeat_tracks(args))
+    try:
+        out = devplanes.spike_scan(args.bamFile, ref, scan["variants"], scan["passes"], scan["targets"], params, int(args.dsSeed), scan["reps"],
+                                   eng, threshold, repeats, sampler=getattr(args, "sampler", "reference"),
+                                   sampler_seed=getattr(args, "samplerSeed", 0))
+    except (ValueError, bamio.BamError) as e:
+        raise SystemExit(str(e))
+    for (k, _), st in zip(scan["passes"], out["passes"]):
+        print("--spikeScan pass %d: %d variants, %d copies, %d builds, %d verdicts decided by the host, %.3f s" %
+              (k, st["variants"], st["copies"], st["builds"], st["host"], st["seconds"]))
     return out
 
 
@@ -824,12 +872,14 @@ def _main(args) -> int:
     params = VcParams(minBQ=args.minBQ, minMQ=args.minMQ, mtDepth=args.mtDepth, rpb=args.rpb, hpLen=args.hpLen,
                       mismatchThr=args.mismatchThr, mtDrop=args.mtDrop, maxMT=args.maxMT, primerDist=args.primerDist)
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    from . import spike as _spike
+    # (--spikeScan first: it stands alone, and its refusals name what it cannot stand beside)
+    scan = _spike.scan(args)
     fractions = ds_fractions(args)
     targets = ds_rpb_targets(args)
     cells = ds_grid_cells(args)
     af_targets = ds_af_targets(args)
     af_fracs, af_cells = ds_af_depth_cells(args, af_targets)
-    from . import spike as _spike
     spike_targets = _spike.targets(args)
     # (--spikePhaseRpb first: its refusals name the flag to use beside it)
     phase_rpbs, phase_rpb_cells = _spike.phase_rpb_cells(args, spike_targets)
@@ -865,9 +915,11 @@ def _main(args) -> int:
         plan.spike_rpb = dict(targets=spike_rpbs, params=[o.params for o in plan.outputs if o.kind == "spikeRpb"])
         if phase_rpbs is not None:
             plan.spike_rpb["flag"] = "--spikePhaseRpb"
+    plan.scan = scan
     if af_fracs is not None:
         plan.depth = dict(fracs=af_fracs, params=[o.params for o in plan.outputs if o.kind == "dsAFDepth"])
-    flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets), ("--dsAF", af_targets), ("--spikeAF", spike_targets)) if on)
+    flag = " / ".join(f for f, on in (("--dsMT", fractions), ("--dsRpb", targets), ("--dsAF", af_targets), ("--spikeAF", spike_targets),
+                                      ("--spikeScan", scan)) if on)
     if flag and world > 1:
         raise SystemExit("%s runs in one process only (not under torch.distributed.run with more than one rank)" % flag)
     if getattr(args, "lodDepth", None) is not None and not getattr(args, "lod", False):
@@ -956,6 +1008,32 @@ def _make_rules(args, plan, loc_list):
         if plan.spike_depth is not None:
             put([o for o in plan.outputs if o.kind == "spikeDepth"], plan.spike_depth["rules"])
         plan.spike = dict(variants=variants, res=res, keep=keep, phase=phase)
+    if plan.scan is not None:
+        # (--spikeScan: the scan's SNV of every locus and the passes, by the tool's own functions; two barcode texts with one
+        # identity are refused here, as --spikeAF's pre-pass refuses them)
+        from .tools import ds_allele_fraction as af, spike_scan_lists as lists
+        try:
+            af.unique_idents(bamio.placed_barcodes(args.bamFile), args.bamFile)
+            variants, skipped = lists.scan_variants(loc_list, fasta.FastaFile(args.refGenome), plan.scan["alt"])
+            passes = lists.scan_passes(variants, plan.scan["stride"])
+        except (ValueError, OSError, bamio.BamError) as e:
+            raise SystemExit(str(e))
+        for k, members in passes:
+            # (the rewrite takes a pass's whole list of a chromosome: smc_spike_alleles_reps' limit)
+            chrom, n = collections.Counter(variants[i].chrom for i in members).most_common(1)[0]
+            if n > SCAN_MAX_PASS_VARIANTS:
+                raise SystemExit("--spikeScan: pass %d holds %d loci of %s, at most %d (a larger --spikeScanStride makes more and smaller "
+                                 "passes)" % (k, n, chrom, SCAN_MAX_PASS_VARIANTS))
+        index = {(v.chrom, v.pos): i for i, v in enumerate(variants)}
+        seen, loci = set(), []
+        for c, q in loc_list:
+            if (c, int(q)) not in seen:
+                seen.add((c, int(q)))
+                loci.append((c, int(q), index.get((c, int(q)))))
+        plan.scan.update(variants=variants, skipped=skipped, passes=passes, loci=loci, loc_list=loc_list)
+        print("--spikeScan: %d loci in %d passes of stride %d (%s), %d skipped for a letter that is not A, C, G or T; %d replicates x %d "
+              "targets" % (len(variants), len(passes), plan.scan["stride"], plan.scan["alt"], len(skipped), plan.scan["reps"],
+                           len(plan.scan["targets"])))
 
 
 def _gather_ranks(args, params, loc_list, rank, local_rank, world):
@@ -1170,6 +1248,32 @@ def _spike_reports(args, plan, shard, loc_index, repeats):
           "%.3f s)" % (tm["stage"], R, len(outs), tm["counts"], tm["rewrites"], tm["builds"], tm["batches"], tm["calls"]))
 
 
+def _scan_reports(args, plan, shard):
+    """--spikeScan: the two pages and the bedgraphs from the stage's verdicts and counts, and the closing line of the run log."""
+    from . import spike as _spike
+    scan, out = plan.scan, shard.scan
+    variants, targets, R = scan["variants"], scan["targets"], scan["reps"]
+    entries = {}
+    for i, v in enumerate(variants):
+        n, v0 = out["base"][i]
+        for t in range(len(targets)):
+            entries[(i, t)] = [_spike.scan_entry(v, dict(N=n, V0=v0, S=int(s), READS=int(reads), V1=int(v1)), bool(out["called"][i, t, j]))
+                               for j, (s, reads, v1) in enumerate(out["counts"][i, :, t].tolist())]
+    lods = None
+    if shard.lod is not None:
+        # (--lod: the full-depth output's LOD at the locus - the scan has no output of its own per target)
+        at, first = {}, shard.lod[0]["lods"]
+        for n, (c, q) in enumerate(scan["loc_list"]):
+            at.setdefault((c, int(q)), n)
+        lods = [float(first[at[(v.chrom, v.pos)]]) for v in variants]
+    _spike.write_scan(args.outPrefix, scan["loci"], variants, targets, entries, lods)
+    tm = out["times"]
+    print("--spikeScan: %d loci x %d targets x %d replicates in %d passes: %d runs decoded once each (%.3f s), %d copies built and "
+          "called, %d of %d verdicts decided by the host, stage %.3f s" %
+          (len(variants), len(targets), R, len(scan["passes"]), tm["runs"], tm["decode"], sum(st["builds"] for st in out["passes"]),
+           sum(st["host"] for st in out["passes"]), len(variants) * len(targets) * R, tm["stage"]))
+
+
 def _run(args, plan, loc_list, t0):
     params = plan.outputs[0].params
     rank, local_rank, world = smcdist.init_from_env()
@@ -1178,7 +1282,8 @@ def _run(args, plan, loc_list, t0):
         # (about a second of start-up; the host-buffer entry point needs none of it)
         _lib.load(with_torch=False)
         # (the keywords only when there is something in them: a stand-in for call_shard may know neither)
-        more = {k: v for k, v in (("early", plan.early), ("plan", plan if len(plan.outputs) > 1 else None)) if v is not None}
+        more = {k: v for k, v in (("early", plan.early), ("plan", plan if len(plan.outputs) > 1 or plan.scan is not None else None))
+                if v is not None}
         shard = call_shard(args, params, loc_list, args.device, **more)
         if not isinstance(shard, _Shard):                  # (a plain list of row strings: the full-depth output alone)
             shard = _Shard(shard)
@@ -1189,7 +1294,7 @@ def _run(args, plan, loc_list, t0):
         shard = _Shard(rows)
     vc.raise_on_exception(shard.rows, loc_list)
     print("begin variant filtering and output")
-    tracks = [b if b and os.path.exists(b) else None for b in (args.bedTandemRepeats, args.bedRepeatMaskerSubset)]
+    tracks = _repeat_tracks(args)
     if None in tracks:
         print("note: repeat tracks not given or not found; RepT/RepS/LowC/SL flags are not applied", file=sys.stderr)
     repeats = postfilter.load_repeat_regions(args.bedTarget, *tracks)
@@ -1233,6 +1338,8 @@ def _run(args, plan, loc_list, t0):
                 _spike.write_phase(args.outPrefix, plan.spike["variants"], phase["sets"], r_outs, _spike.RPB_AXIS)
         if shard.spike_reps is not None:
             _spike_reports(args, plan, shard, loc_index, repeats)
+    if shard.scan is not None:
+        _scan_reports(args, plan, shard)
     t1 = datetime.datetime.now()
     print("smCounter completed running at " + str(t1))
     print("smCounter total time: " + str(t1 - t0))

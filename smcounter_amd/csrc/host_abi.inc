@@ -1536,6 +1536,40 @@ int smc_spike_read_bits(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln, c
     return SMC_OK;
 }
 
+// (--spikeScan) one verdict per (copy, listed locus) of a called batch: everything checked on the host copy before anything is
+// enqueued, then the cursor zeroed and one launch (none for an empty list or no copy)
+int smc_scan_detect(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64_t n_loci, const smc_scan_locus* d_listed,
+                    const smc_scan_locus* listed_host, int32_t n_listed, double thr, smc_scan_verdict* d_out, uint32_t* d_host_list,
+                    uint32_t* d_n_host, void* stream) {
+    const std::string who = "smc_scan_detect";
+    static_assert(sizeof(smc_scan_verdict) == 16 && sizeof(smc_scan_locus) == 8, "smc_scan_detect's records");
+    if (!ctx || n_copies < 0 || n_loci < 0 || n_listed < 0 || !d_n_host) return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_listed && !listed_host) return fail(SMC_E_ARG, who + ": NULL argument");
+    if (!std::isfinite(thr)) return fail(SMC_E_INPUT, who + ": a threshold that is not finite");
+    if (n_copies > 65535) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies, at most 65535");
+    if ((int64_t)n_copies * (int64_t)n_listed >= (1ll << 31) || (int64_t)n_copies * n_loci >= (1ll << 31))
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies of " + std::to_string(n_loci) + " loci, " +
+                                 std::to_string(n_listed) + " listed: 2^31 records or rows, or more");
+    for (int32_t g = 0; g < n_listed; ++g) {
+        if ((int64_t)listed_host[g].offset >= n_loci)
+            return fail(SMC_E_INPUT, who + ": listed locus " + std::to_string(g) + " names offset " + std::to_string(listed_host[g].offset) +
+                                     " of " + std::to_string(n_loci));
+        if (listed_host[g].alt > 3u)
+            return fail(SMC_E_INPUT, who + ": listed locus " + std::to_string(g) + " has allele id " + std::to_string(listed_host[g].alt) +
+                                     ", one of 0 .. 3 expected");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemsetAsync(d_n_host, 0, sizeof(uint32_t), (hipStream_t)stream));
+    if (!n_listed || !n_copies) return SMC_OK;
+    if (!d_rows || !d_listed || !d_out || !d_host_list) return fail(SMC_E_ARG, who + ": NULL argument");
+    const double edge = thr - 0.005;
+    hipLaunchKernelGGL(k_scan_detect, dim3((unsigned)std::min<int64_t>(((int64_t)n_listed + SCD_BLOCK - 1) / SCD_BLOCK, 1024), (unsigned)n_copies),
+                       dim3(SCD_BLOCK), 0, (hipStream_t)stream, d_rows, (uint32_t)n_loci, d_listed, (uint32_t)n_listed, edge - 1e-6, edge + 1e-6,
+                       d_out, d_host_list, d_n_host);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
 // (--spikeRpb, --spikeIndelRpb) (N', V0', S', READS', V1') of every listed variant, replicate and cell (spike target x read threshold),
 // from the covering barcodes' records: everything checked on the host copies before anything is enqueued, then the counters zeroed and
 // k_spr_counts - with `four` the instance that reads alt1 and touch from flag bits 2 and 3, else the one in which bit 2 is both

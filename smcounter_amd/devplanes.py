@@ -3056,6 +3056,246 @@ def _spike_rep_targets(*, eng, run, svar, var_at, seeds, thr, counts, depth_coun
             times["batches"] += 1 + F
 
 
+# ---- --spikeScan: a measured detection rate at every locus of the target; the called batches' rows stay in HBM
+SCAN_ALT_ID = {"A": 0, "T": 1, "G": 2, "C": 3}      # (pileup.BASE_ALLELES: the fixed allele ids smc_scan_detect compares cand[0] with)
+
+
+def scan_detect(eng, d_rows, n_copies: int, n_loci: int, listed, threshold):
+    """smc_scan_detect over the rows of a called batch in HBM (`d_rows`: n_copies x n_loci rows, e.g. Plan.run_into_devbuf's) ->
+    (abi.SCAN_VERDICT_DTYPE [n_copies, G], the indices copy x G + listed locus of the records the host has to decide, ascending - the
+    kernel appends them in no fixed order).  listed: abi.SCAN_LOCUS_DTYPE [G]; threshold: the truncated-PI cut of the .cut files."""
+    from .engine import DevBuf
+    listed = np.ascontiguousarray(listed, abi.SCAN_LOCUS_DTYPE)
+    B, G = int(n_copies), len(listed)
+    n = B * G
+    bufs = [DevBuf(eng, listed.nbytes + 256).upload(listed.view(np.uint8).reshape(-1) if G else np.zeros(4, np.uint8)),
+            DevBuf(eng, 16 * max(1, n) + 256), DevBuf(eng, 4 * max(1, n) + 256), DevBuf(eng, 256)]
+    try:
+        _lib.check(eng.L.smc_scan_detect(eng.ctx, d_rows.data_ptr() if d_rows is not None else None, B, int(n_loci), bufs[0].data_ptr(),
+                                         listed.ctypes.data, G, float(threshold), bufs[1].data_ptr(), bufs[2].data_ptr(), bufs[3].data_ptr(),
+                                         ctypes.c_void_p(0)), "smc_scan_detect")
+        n_host = int(bufs[3].download(np.uint32, 1)[0])              # (the default stream: behind the kernel)
+        rec = bufs[1].download(abi.SCAN_VERDICT_DTYPE, n) if n else np.zeros(0, abi.SCAN_VERDICT_DTYPE)
+        if n_host > n:
+            raise _lib.SmcError("smc_scan_detect: %d records for the host out of %d" % (n_host, n))
+        todo = np.sort(bufs[2].download(np.uint32, n_host)) if n_host else np.zeros(0, np.uint32)
+    finally:
+        for b in bufs:
+            b.free()
+    return rec.reshape(B, G), todo
+
+
+def scan_called_host(text, v, threshold: int, repeats) -> bool:
+    """Was `v` called in the raw row `text`, the way the replicate pages decide it: the row through the repeat filters and the .cut
+    rule (dsaf.replicate_entry), then REF and ALT compared (spike._called)."""
+    from . import dsaf, spike as _spike
+    row, cut = dsaf.replicate_entry(text, threshold, *repeats)
+    return bool(_spike._called(v, [(None, row, cut)]))
+
+
+def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed,
+               bits, threshold, repeats, check0):
+    """`len(part_seeds)` spiked copies of the run at one target from one smc_spike_alleles_reps call, each built behind the other into
+    one device batch and the batch called with one plan - _spike_rep_call's way - but the rows stay in HBM: smc_scan_detect gives a
+    verdict per (copy, listed locus), and only the rows it leaves to the host come down, one by one, to be printed and cut the
+    existing way.  run.group: the pass's variants of this run; listed: their abi.SCAN_LOCUS_DTYPE records; check0: the copy that is
+    replicate 0 (or None) - its listed rows come down as well, and a device verdict of CALLED or NOT that the host's decision does
+    not share ends the run.  -> (bool [copies, listed]: called, the number of verdicts the host decided), or NARROW."""
+    from . import vc
+    A, up, lo, nl, chrom = run.A, run.up, run.lo, run.nl, run.chrom
+    B, G = len(part_seeds), len(run.group)
+    ns_full = int(A["n_slots"])
+    cap = B * (ns_full + nl) + ns_full + nl + 64
+    d_aln, d_bq, (sa, sb), stats = spike_run_copies(eng, up, A, svar, run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
+    d = d_rows = plan = None
+    try:
+        for c in range(B):
+            for g, k in enumerate(run.group):
+                if int(stats[c, var_at[g], 0]) != int(want_reads[c][g]):
+                    v = variants[k]
+                    raise RuntimeError("--spikeScan: seed %d at %s:%d: the rewrite touched %d records, the counts call says %d" %
+                                       (int(part_seeds[c]), v.chrom, v.pos, int(stats[c, var_at[g], 0]), int(want_reads[c][g])))
+        d = _DsBatch(eng, cap, bits, False)
+        cp = abi.c_params(P)
+        n_loc = 0
+        for c in range(B):
+            copy = RunOnDevice(d_aln.view(c * sa), up.cig, d_bq.view(c * sb), up.loc, up.ref, up.n_aln, up.loc_host)
+            # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch)
+            done = build_run(A, eng.L, eng, cp, P, chrom, lo, fasta, run.run_ref, [d.words] + d.planes, d.uaux, d.slots, d.slots + n_loc, cap,
+                             max_depth, run.bam.allele_key, run.bam.barcode_name, sampler=sampler, sampler_seed=sampler_seed,
+                             barcode_idents=lambda n: run.idents, uploaded=copy)
+            if done is None:
+                raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "a replicate: the device builder does not take it", "--spikeScan"))
+            if done == NARROW:
+                return NARROW
+            _, ns_k, lc, tb = done
+            d.LC.append(lc)
+            d.tables += tb
+            d.slots += ns_k
+            n_loc += nl
+        plan = eng.make_plan(d.LC[0] if len(d.LC) == 1 else np.concatenate(d.LC))
+        d_rows = plan.run_into_devbuf([d.words, d.uaux[0]], P)
+        rec, todo = scan_detect(eng, d_rows, B, nl, listed, threshold)       # (its downloads wait for the plan's kernels)
+        verdict = (rec["mt_verdict"] >> 30).astype(np.int64)
+        called = verdict == abi.SCAN_CALLED
+        theirs = set(int(x) for x in todo)
+        if theirs != set(int(x) for x in np.flatnonzero(verdict.reshape(-1) == abi.SCAN_HOST)):
+            raise RuntimeError("--spikeScan: %s:%d-%d: the list of the records for the host is not that of the HOST verdicts" % (chrom, lo + 1, lo + nl))
+        mine = sorted(theirs | (set(check0 * G + g for g in range(G)) if check0 is not None else set()))
+        if mine:
+            at = [int(listed["offset"][i % G]) for i in mine]
+            got = np.empty(len(mine), abi.ROW_DTYPE)
+            for n, (i, a) in enumerate(zip(mine, at)):
+                d_rows.download(abi.ROW_DTYPE, 1, ((i // G) * nl + a) * abi.ROW_DTYPE.itemsize, out=got[n:n + 1])
+            view = vc.LocusView([chrom] * len(mine), [lo + 1 + a for a in at], [run.run_ref[a] if a < len(run.run_ref) else "" for a in at],
+                                [d.tables[(i // G) * nl + a] for i, a in zip(mine, at)])
+            text = vc._strings(got, view, P, fasta)
+            for i, line in zip(mine, text):
+                v = variants[run.group[i % G]]
+                if line.startswith(vc.EXC_PREFIX):
+                    raise RuntimeError("--spikeScan: %s:%d: the row of seed %d could not be printed:\n%s" % (v.chrom, v.pos, int(part_seeds[i // G]), line))
+                host = scan_called_host(line, v, threshold, repeats)
+                if i in theirs:
+                    called[i // G, i % G] = host
+                elif host != bool(called[i // G, i % G]):
+                    raise RuntimeError("--spikeScan: replicate 0 of %s:%d %s>%s: smc_scan_detect says %s (PI %.17g, threshold %d), the row as "
+                                       "the run would print and cut it says %s:\n%s" %
+                                       (v.chrom, v.pos, v.ref, v.alt, "CALLED" if called[i // G, i % G] else "NOT", float(rec[i // G, i % G]["pi"]),
+                                        threshold, "called" if host else "not called", line))
+        return called, len(theirs)
+    finally:
+        if plan is not None:
+            plan.close()
+        for b in (d_rows, d, d_aln, d_bq):
+            if b is not None:
+                b.free()
+
+
+def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n_reps: int, eng, threshold: int, repeats,
+               sampler: str = "reference", sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000):
+    """The stage of --spikeScan.  variants: the scan's SNV at every scanned locus (tools.spike_scan_lists.scan_variants); passes: [(k,
+    the indices of pass k)] (scan_passes).  A pass is the run --spikeAF <targets> --spikeVariants <its list> --spikeReps n_reps --dsSeed
+    seed: replicate j has seed (seed + j) mod 2^64, and the draws, the rewrite, NM and the thresholds are that run's.
+    The scanned loci are cut into runs as the pre-pass cuts listed variants (AF_RUN_LOCI); every run is decoded and uploaded ONCE and
+    kept as an AfRun while its passes are made.  Per pass with a locus in the run: the pre-pass's counters of its variants
+    (smc_allele_carriers with counts on the run, and on one copy spiked at threshold 2^32 with the pass's list), one
+    smc_spike_rep_counts call for (S, READS, V1) of every variant, replicate and target, then per target as many copies per
+    smc_spike_alleles_reps call as spike_replicates' room rule allows, each built behind the last and the batch called with one plan
+    (_scan_call).  The rewrite takes the pass's whole list of the chromosome: a variant is rewritten in whichever run decodes a read
+    that spans it.  No batch of rows is downloaded.
+    -> dict(seeds, base: per variant (N, V0), counts: uint32 [V, R, T, 3] = (S, READS, V1), called: bool [V, T, R], passes: per pass
+    of `passes` dict(variants, copies, builds, host, seconds), times: dict(stage, runs, decode))."""
+    import time
+    from . import dsaf
+    from .tools import spike_variants as sv
+    t_start = time.perf_counter()
+    T, R, V = len(targets), int(n_reps), len(variants)
+    if T > SPIKE_MAX_TARGETS:
+        raise ValueError("--spikeScan: %d targets, at most %d" % (T, SPIKE_MAX_TARGETS))
+    seeds = dsaf.rep_seeds(seed, R)
+    thr = [sv.threshold(t) for t in targets]
+    P = params
+    nthreads = nthreads or bamio.host_threads()
+    max_depth = eng.L.smc_build_max_depth()
+    pass_at = np.full(V, -1, np.int64)          # variant -> its pass's index in `passes`
+    local = np.zeros(V, np.int64)               # ... and its place in that pass's list
+    for p, (_, members) in enumerate(passes):
+        pass_at[members] = p
+        local[members] = np.arange(len(members))
+    spikes = [SpikeSet([variants[i] for i in members]) for _, members in passes]
+    base, counts, called = [None] * V, np.zeros((V, R, T, 3), np.uint32), np.zeros((V, T, R), bool)
+    stats = [dict(variants=0, copies=0, builds=0, host=0, seconds=0.0) for _ in passes]
+    times = {"decode": 0.0, "runs": 0}
+    order = sorted(range(V), key=lambda k: (variants[k].chrom, variants[k].pos))
+    i = 0
+    while i < len(order):
+        v0 = variants[order[i]]
+        j = i
+        while j + 1 < len(order) and variants[order[j + 1]].chrom == v0.chrom and variants[order[j + 1]].pos - v0.pos < AF_RUN_LOCI:
+            j += 1
+        lo, hi = v0.pos - 1, variants[order[j]].pos
+        t0 = time.perf_counter()
+        run = AfRun(v0.chrom, lo, hi, [], 0, bam=bamio.NativeBam(path))
+        try:
+            A = run.bam.alignments_run(v0.chrom, lo, hi, max_reads, P, nthreads)
+            nl = int(A["nl"])
+            if nl < 1:
+                raise bamio.BamError("--spikeScan: the run %s:%d-%d could not be decoded" % (v0.chrom, lo + 1, hi))
+            inside = [k for k in order[i:j + 1] if variants[k].pos - 1 - lo < nl]
+            run.A, run.nl = A, nl
+            run.run_ref = fasta.fetch(v0.chrom, lo, lo + nl).upper()
+            run.idents = run.bam.barcode_idents(A["n_bc"])
+            run.mism = run.bam.run_mismatches(len(A["aln"]))
+            run.up = upload_run(eng, A, run.run_ref)
+            times["decode"] += time.perf_counter() - t0
+            times["runs"] += 1
+            per_copy = sum(spike_copy_strides(run.up.n_aln, len(A["bq"]) // 2))
+            room = max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per_copy, AF_REP_BATCH_SLOTS // max(1, int(A["n_slots"]) + nl)))
+            for p in sorted({int(pass_at[k]) for k in inside}):
+                t0 = time.perf_counter()
+                run.group = [k for k in inside if pass_at[k] == p]
+                _scan_pass(eng, run, spikes[p], [int(local[k]) for k in run.group], variants, seeds, thr, P, fasta, max_depth, sampler,
+                           sampler_seed, threshold, repeats, room, base, counts, called, stats[p])
+                stats[p]["variants"] += len(run.group)
+                stats[p]["seconds"] += time.perf_counter() - t0
+        finally:
+            run.free()
+        i += len(inside)
+    times["stage"] = time.perf_counter() - t_start
+    return dict(seeds=seeds, base=base, counts=counts, called=called, passes=stats, times=times)
+
+
+def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr, P, fasta, max_depth, sampler, sampler_seed, threshold,
+               repeats, room, base, counts, called, stat):
+    """spike_scan's work for one pass in one run: run.group are the pass's variants there (indices into `variants`), members[g] the
+    place of run.group[g] in the pass's list (`spikes`).  base, counts, called and stat are filled."""
+    A, up, lo, chrom = run.A, run.up, run.lo, run.chrom
+    idents, (nm, n_indel) = run.idents, run.mism
+    group = run.group
+    var, ins = af_run_variants([variants[k] for k in group], chrom, lo, fasta)
+    cov, car, cnt0 = allele_carriers_run(eng, up, A, lo, var, ins, counts=True)
+    # (`single`: one copy with every barcode spiked at every position of the pass's list - thr 2^32 - then the `alt` counters)
+    svar, sorder = spikes.chrom_variants(chrom, 0.5)
+    svar["thr"] = 1 << 32
+    spiked, _ = spike_copy(eng, up, A, spikes, chrom, svar, idents, seeds[0], P.mismatchThr, nm, n_indel)
+    try:
+        _, _, cnt_all = allele_carriers_run(eng, spiked, A, lo, var, ins, counts=True)
+    finally:
+        free_spiked(spiked, up)
+    covers, counters = [], []
+    for g, k in enumerate(group):
+        c = cov[g][:len(idents)]
+        covers.append(idents[c])
+        counters.append(np.stack([cnt0[g, :len(idents), 0][c], cnt0[g, :len(idents), 1][c], cnt_all[g, :len(idents), 1][c]], axis=1).astype(np.uint32))
+        base[k] = (int(cov[g].sum()), int(car[g].sum()))
+    mine = spike_rep_counts(eng, [spikes.lead_pos[m] for m in members], covers, counters, seeds, thr)       # [G, R, T, 3]
+    at_of = {m: n for n, m in enumerate(sorder)}
+    var_at = [at_of[m] for m in members]
+    listed = np.zeros(len(group), abi.SCAN_LOCUS_DTYPE)
+    for g, k in enumerate(group):
+        counts[k] = mine[g]
+        listed[g] = (variants[k].pos - 1 - lo, SCAN_ALT_ID[variants[k].alt])
+    R = len(seeds)
+    for t in range(len(thr)):
+        for b in range(0, R, room):
+            js = list(range(b, min(R, b + room)))
+            want = [[int(mine[g, j, t, 1]) for g in range(len(group))] for j in js]
+            bits = 16 if (eng.word_bits == 16 and 0 <= P.minBQ <= 63) else 32
+            args = (eng, run, svar, var_at, listed, [seeds[j] for j in js], thr[t], want, P, fasta, variants, max_depth, sampler, sampler_seed)
+            tail = (threshold, repeats, js.index(0) if 0 in js else None)
+            out = _scan_call(*args, bits, *tail)
+            if out == NARROW:
+                eng.word_bits = 32
+                out = _scan_call(*args, 32, *tail)
+            yes, n_host = out
+            for c, j in enumerate(js):
+                for g, k in enumerate(group):
+                    called[k, t, j] = yes[c, g]
+            stat["copies"] += len(js)
+            stat["builds"] += len(js)
+            stat["host"] += n_host
+
+
 def _fnv64(text: str) -> int:
     """FNV-1a, 64 bits, of a barcode's text (as smc_bam_barcode_idents computes it natively)."""
     x = 1469598103934665603

@@ -328,6 +328,17 @@ class Plan(object):
         rows.free()
         return out
 
+    def run_into_devbuf(self, planes, params: VcParams) -> DevBuf:
+        """run_devbuf without the download: the rows stay in HBM, in a DevBuf the caller frees.  Enqueued on the default stream - what
+        reads the rows there (smc_scan_detect, a DevBuf.download of some of them) is ordered behind the kernels."""
+        rows = DevBuf(self.eng, self.n_loci * abi.ROW_DTYPE.itemsize)
+        try:
+            self.run(planes, params, rows, stream=0)
+        except BaseException:
+            rows.free()
+            raise
+        return rows
+
     def alloc_wire(self):
         """Device buffer for the packed wire rows of this plan's loci (abi.WIRE_DTYPE, 168 B per locus)."""
         import torch

@@ -32,6 +32,11 @@ as rpb_cells does); the outputs' kind, the pages and their writers are --spikeRp
 writes what --spikeIndelRpb and --spikeIndelPhase write and, with RPB as the phase pages' axis column, <outPrefix>.spikeAF.rpb.phase.txt,
 .rpb.phase.replicates.txt and .rpb.phase.sensitivity.txt - the joint numbers over the reads each cell keeps.
 
+--spikeScan: one SNV at every locus of the target, planted in passes (tools.spike_scan_lists is the rule; scan reads the flags and
+refuses what does not go with them); the pages <outPrefix>.spikeScan.sensitivity.txt and .curve.txt and the bedgraphs
+<outPrefix>.spikeScan<t>.rate.bedgraph and .spikeScan.t95.bedgraph (write_scan) from the verdicts of devplanes.spike_scan, which keeps
+the called rows on the GPU (smc_scan_detect).
+
 The semantics are tools/spike_variants.py's (DESIGN.md "--spikeAF"); the rewrite on the GPU is csrc/k_spike.inc (smc_spike_alleles),
 the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the main pass are devplanes.spike_rules / spike_run.
 """
@@ -653,3 +658,109 @@ def write_phase_sensitivity(out_prefix: str, variants, sets, outputs, entries, a
         for g, pset in enumerate(sets):
             for c, (target, frac, depth) in enumerate(outputs):
                 fh.write(phase_sensitivity_line(pset, variants, target, frac, depth, entries[(g, c)]) + "\n")
+
+
+# ---- --spikeScan
+SCAN_FLAGS = ("spikeScan", "spikeScanReps", "spikeScanStride", "spikeScanAlt")
+SCAN_NOT_WITH = ("spikeAF", "spikeVariants", "spikeMtDepth", "spikeReps", "spikePhase", "spikeIndels", "spikeIndelReps", "spikeIndelDepth",
+                 "spikeIndelPhase", "spikeDepth", "spikeRpb", "spikeIndelRpb", "spikePhaseRpb")
+SCAN_NOT_WITH_DS = DS_FLAGS + ("dsMtDepth", "dsRpbMtDepth", "dsAFVariants", "dsAFMtDepth")
+SCAN_SENSITIVITY_HEADER = tuple(c for c in SENSITIVITY_HEADER if c not in ("PI_MEAN", "PI_MIN"))
+
+
+def _scan_int(text, flag: str, lo: int, hi, what: str) -> int:
+    try:
+        if isinstance(text, float) and text != int(text):
+            raise ValueError(text)
+        n = int(str(text).strip()) if not isinstance(text, (int, float)) else int(text)
+    except ValueError:
+        raise SystemExit("--%s: an integer %s expected, got %r" % (flag, what, text))
+    if n < lo or (hi is not None and n > hi):
+        raise SystemExit("--%s: an integer %s expected, got %d" % (flag, what, n))
+    return n
+
+
+def scan(args):
+    """--spikeScan / --spikeScanReps / --spikeScanStride / --spikeScanAlt -> dict(targets, reps, stride, alt), or None without
+    --spikeScan.  SystemExit: a helper flag without --spikeScan, --spikeScan without --spikeScanReps, any other --spike* flag or a
+    down-sampling flag beside it, a target outside (0, 1) or listed twice, more than MAX_TARGETS, R outside REPS_MIN .. REPS_MAX or no
+    integer, a stride below 1 or no integer, an unknown ALT rule."""
+    from .tools import spike_scan_lists as lists
+    text, r, stride, alt = (getattr(args, f, None) for f in SCAN_FLAGS)
+    given = lambda x: x not in (None, "", False)
+    if not given(text):
+        for flag, value in zip(SCAN_FLAGS[1:], (r, stride, alt)):
+            if given(value):
+                raise SystemExit("--%s belongs to --spikeScan: it needs --spikeScan" % flag)
+        return None
+    for flag in SCAN_NOT_WITH:
+        if given(getattr(args, flag, None)):
+            raise SystemExit("--spikeScan cannot be combined with --%s in one run: the scan plants its own SNV at every locus of "
+                             "--bedTarget (a pass of it is the --spikeAF --spikeReps run of tools/spike_scan_lists.py's list)" % flag)
+    for flag in SCAN_NOT_WITH_DS:
+        if given(getattr(args, flag, None)):
+            raise SystemExit("--spikeScan cannot be combined with --%s in one run (a scan of a down-sampled file is not built)" % flag)
+    if not given(r):
+        raise SystemExit("--spikeScan measures a detection rate over replicates: it needs --spikeScanReps")
+    try:
+        ts = af.parse_targets(text, "--spikeScan")
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if len(set("%g" % t for t in ts)) != len(ts):
+        raise SystemExit("--spikeScan: a target is listed twice (the targets' files would share a name), got %r" % text)
+    if len(ts) > MAX_TARGETS:
+        raise SystemExit("--spikeScan: %d targets, at most %d" % (len(ts), MAX_TARGETS))
+    r = _scan_int(r, "spikeScanReps", REPS_MIN, REPS_MAX, "in %d .. %d" % (REPS_MIN, REPS_MAX))
+    stride = lists.DEFAULT_STRIDE if not given(stride) else _scan_int(stride, "spikeScanStride", 1, None, ">= 1")
+    alt = lists.DEFAULT_ALT if not given(alt) else str(alt)
+    if alt not in lists.ALT_RULES:
+        raise SystemExit("--spikeScanAlt: one of %s expected, got %r" % (", ".join(sorted(lists.ALT_RULES)), alt))
+    return dict(targets=ts, reps=r, stride=stride, alt=alt)
+
+
+def scan_entry(v, r, called: bool):
+    """One replicate of the scan as sensitivity_line() and curve_line() take it: `r` dict(N, V0, S, READS, V1); no row is kept - a
+    verdict stands where the .cut line would."""
+    return r, None, ((v.ref, [v.alt]) if called else None)
+
+
+def scan_sensitivity_line(v, target, per, lod=None) -> str:
+    """sensitivity_line() without PI_MEAN and PI_MIN (the scan keeps no row); `lod`: the locus's LOD in the FULL-DEPTH output."""
+    f = sensitivity_line(v, target, per).split("\t")[:len(SCAN_SENSITIVITY_HEADER)]
+    if lod is not None:
+        f.append("%.15g" % lod)
+    return "\t".join(f)
+
+
+def write_scan(out_prefix: str, loci, variants, targets, entries, lods=None) -> None:
+    """The pages of --spikeScan.  `loci`: every locus of the target in order as (chrom, pos, index into `variants` or None for a locus
+    skipped for its letter); entries[(i, t)]: the replicates of variant i at targets[t] (scan_entry); lods[i]: the full-depth
+    output's LOD at variant i, with --lod.
+      <outPrefix>.spikeScan.sensitivity.txt    a line per scanned locus and target (scan_sensitivity_line)
+      <outPrefix>.spikeScan.curve.txt          curve_line per scanned locus
+      <outPrefix>.spikeScan<t>.rate.bedgraph   chrom, pos - 1, pos, RATE of that target - the page's text - per scanned locus
+      <outPrefix>.spikeScan.t95.bedgraph       chrom, pos - 1, pos, T95 - 1 where it is NA, as --lod writes "not detectable", and 1 at
+                                               a skipped locus"""
+    T = len(targets)
+    rates, t95s = [[] for _ in range(T)], []
+    i_rate, i_t95 = SCAN_SENSITIVITY_HEADER.index("RATE"), len(CURVE_HEADER) + T
+    with open(out_prefix + ".spikeScan.sensitivity.txt", "w") as fs, open(out_prefix + ".spikeScan.curve.txt", "w") as fc:
+        fs.write("\t".join(SCAN_SENSITIVITY_HEADER + (("LOD",) if lods is not None else ())) + "\n")
+        fc.write("\t".join(curve_header(targets, lods is not None)) + "\n")
+        for i, v in enumerate(variants):
+            lod = None if lods is None else float(lods[i])
+            for t, target in enumerate(targets):
+                line = scan_sensitivity_line(v, target, entries[(i, t)], lod)
+                rates[t].append(line.split("\t")[i_rate])
+                fs.write(line + "\n")
+            line = curve_line(v, entries[(i, 0)][0][0]["N"], targets, [entries[(i, t)] for t in range(T)], lod)
+            t95s.append(line.split("\t")[i_t95])
+            fc.write(line + "\n")
+    for t, target in enumerate(targets):
+        with open("%s.spikeScan%g.rate.bedgraph" % (out_prefix, target), "w") as fh:
+            for chrom, pos, i in loci:
+                if i is not None:
+                    fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), rates[t][i]))
+    with open(out_prefix + ".spikeScan.t95.bedgraph", "w") as fh:
+        for chrom, pos, i in loci:
+            fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "1" if i is None or t95s[i] == dsaf.NA else t95s[i]))

@@ -1396,6 +1396,30 @@ int smc_spike_alleles_reps(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln
     return SMC_OK;
 }
 
+// What spk_cell_counts and spr_cell_counts check first, the axes both have: rows (`rows`: " variants" or " sets"), spike targets,
+// replicates, and with `has_second` a second axis of the cells (`second`: " fractions" or " read thresholds"; second_thr its thresholds) -
+// the limits, the NULL seeds and thresholds, then T filled from thr.  `bad`: what else makes the call a bad argument.
+static int spk_axes(const std::string& who, const smc_ctx* ctx, bool bad, const std::string& rows, int32_t n_rows, const uint64_t* d_seeds,
+                    int32_t n_reps, const uint64_t* thr, int32_t n_targets, bool has_second, const char* second, const uint64_t* second_thr,
+                    int32_t n_second, SpkThr& T) {
+    if (!ctx || n_rows < 0 || n_reps < 0 || n_targets < 0 || bad) return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_rows > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_rows) + rows + ", at most " + std::to_string(SMC_AF_MAX_VARIANTS));
+    if (n_targets > SMC_SPIKE_REP_MAX_TARGETS)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_SPIKE_REP_MAX_TARGETS));
+    if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
+    if (has_second && n_second < 1) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_second) + second + ", at least 1 expected");
+    if ((n_reps && !d_seeds) || (n_targets && !thr) || (has_second && !second_thr)) return fail(SMC_E_ARG, who + ": NULL argument");
+    if (has_second && (int64_t)n_targets * (int64_t)n_second > SMC_AF_DEPTH_MAX_CELLS)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets x " + std::to_string(n_second) + second + ", at most " +
+                                 std::to_string(SMC_AF_DEPTH_MAX_CELLS) + " cells");
+    memset(&T, 0, sizeof T);
+    for (int32_t t = 0; t < n_targets; ++t) {
+        if (thr[t] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": target " + std::to_string(t) + ": a threshold above 2^32");
+        T.t[t] = thr[t];
+    }
+    return SMC_OK;
+}
+
 // (--spikeReps, --spikeDepth, --spikePhase) what the three counts entries check, on the host copies and before anything is enqueued,
 // then the counters zeroed and k_spike_cells.  A row is a listed variant, or with `sets` a phase set of set_m_host[g] members whose
 // counters start at d_cnt_off[g].  Without `has_fracs` (smc_spike_rep_counts) the cells are those of one fraction that keeps every
@@ -1407,24 +1431,10 @@ static int spk_cell_counts(const std::string& who, smc_ctx* ctx, const uint64_t*
                            void* stream, uint32_t cs = 3, uint32_t i_alt1 = 2, uint32_t i_touch = 2) {
     const std::string rows = sets ? " sets" : " variants", row = sets ? "set " : "variant ";
     const int n_want = __builtin_popcount(want);
-    if (!ctx || n_rows < 0 || n_reps < 0 || n_targets < 0) return fail(SMC_E_ARG, who + ": bad argument");
-    if (n_rows > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_rows) + rows + ", at most " + std::to_string(SMC_AF_MAX_VARIANTS));
-    if (n_targets > SMC_SPIKE_REP_MAX_TARGETS)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_SPIKE_REP_MAX_TARGETS));
-    if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
-    if (has_fracs && n_fracs < 1) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_fracs) + " fractions, at least 1 expected");
-    if ((n_reps && !d_seeds) || (n_targets && !thr) || (has_fracs && !depth_thr)) return fail(SMC_E_ARG, who + ": NULL argument");
-    if (has_fracs && (int64_t)n_targets * (int64_t)n_fracs > SMC_AF_DEPTH_MAX_CELLS)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets x " + std::to_string(n_fracs) + " fractions, at most " +
-                                 std::to_string(SMC_AF_DEPTH_MAX_CELLS) + " cells");
     SpkThr T;
+    if (int rc = spk_axes(who, ctx, false, rows, n_rows, d_seeds, n_reps, thr, n_targets, has_fracs, " fractions", depth_thr, n_fracs, T)) return rc;
     AfdThr D;
-    memset(&T, 0, sizeof T);
     memset(&D, 0, sizeof D);
-    for (int32_t t = 0; t < n_targets; ++t) {
-        if (thr[t] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": target " + std::to_string(t) + ": a threshold above 2^32");
-        T.t[t] = thr[t];
-    }
     int with_depth = 0;
     if (!has_fracs) { n_fracs = 1; D.f[0] = 1ull << 32; }
     for (int32_t f = 0; has_fracs && f < n_fracs; ++f) {
@@ -1570,78 +1580,87 @@ int smc_scan_detect(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64
     return SMC_OK;
 }
 
-// (--spikeRpb, --spikeIndelRpb) (N', V0', S', READS', V1') of every listed variant, replicate and cell (spike target x read threshold),
-// from the covering barcodes' records: everything checked on the host copies before anything is enqueued, then the counters zeroed and
-// k_spr_counts - with `four` the instance that reads alt1 and touch from flag bits 2 and 3, else the one in which bit 2 is both
-static int spr_cell_counts(const std::string& who, bool four, smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_off,
-                           const uint32_t* cov_off_host, const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name,
-                           const uint8_t* d_rec_flag, int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds,
+// (--spikeRpb, --spikeIndelRpb, --spikePhaseRpb) what the three counts entries check, on the host copies and before anything is
+// enqueued, then the counters zeroed and k_spr_counts.  A row is a listed variant: (N', V0', S', READS', V1') per replicate and cell
+// (spike target x read threshold) from the records of its covering barcodes, segment e the records of barcode e - with `four` the
+// instance that reads alt1 and touch from flag bits 2 and 3, else the one in which bit 2 is both.  Or with `sets` a phase set of
+// set_m_host[g] members: (N_ALL', V0_ALL', S_ALL', V1_ALL') from the records of every (joint barcode, member); the segment bases are
+// the running sums of (joint barcodes x members), so no lane reads an offset beyond the n_seg + 1 there are.
+static int spr_cell_counts(const std::string& who, bool four, bool sets, smc_ctx* ctx, const uint64_t* d_ident, const uint32_t* d_off,
+                           const uint32_t* off_host, const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_seg_base,
+                           const uint32_t* seg_base_host, const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name,
+                           const uint8_t* d_rec_flag, int64_t n_rec, const uint32_t* d_pos1, int32_t n_rows, const uint64_t* d_seeds,
                            int32_t n_reps, const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr,
                            uint32_t* d_out, void* stream) {
-    if (!ctx || n_var < 0 || n_reps < 0 || n_targets < 0 || n_rec < 0) return fail(SMC_E_ARG, who + ": bad argument");
-    if (n_var > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
-    if (n_targets > SMC_SPIKE_REP_MAX_TARGETS)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_SPIKE_REP_MAX_TARGETS));
-    if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
-    if (n_read_thr < 1) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_read_thr) + " read thresholds, at least 1 expected");
-    if ((n_reps && !d_seeds) || (n_targets && !thr) || !read_thr) return fail(SMC_E_ARG, who + ": NULL argument");
-    if ((int64_t)n_targets * (int64_t)n_read_thr > SMC_AF_DEPTH_MAX_CELLS)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets x " + std::to_string(n_read_thr) + " read thresholds, at most " +
-                                 std::to_string(SMC_AF_DEPTH_MAX_CELLS) + " cells");
+    const std::string rows = sets ? " sets" : " variants", row = sets ? "set " : "variant ";
+    const size_t n_counters = sets ? SPP_COUNTERS : SPC_COUNTERS;
     SpkThr T;
+    if (int rc = spk_axes(who, ctx, n_rec < 0, rows, n_rows, d_seeds, n_reps, thr, n_targets, true, " read thresholds", read_thr, n_read_thr, T)) return rc;
     RgThr Q;
-    memset(&T, 0, sizeof T);
     memset(&Q, 0, sizeof Q);
-    for (int32_t t = 0; t < n_targets; ++t) {
-        if (thr[t] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": target " + std::to_string(t) + ": a threshold above 2^32");
-        T.t[t] = thr[t];
-    }
     for (int32_t r = 0; r < n_read_thr; ++r) {
         if (read_thr[r] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": read threshold " + std::to_string(r) + " is above 2^32");
         if (r < SMC_RG_MAX_TARGETS) Q.t[r] = read_thr[r];         // (more of them pass the cells' limit only without a target: nothing is launched)
     }
-    if ((double)n_var * (double)n_reps * (double)n_targets * (double)n_read_thr * (double)SPC_COUNTERS >= (double)0xFFFFFF00u)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants x " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) +
+    if ((double)n_rows * (double)n_reps * (double)n_targets * (double)n_read_thr * (double)n_counters >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_rows) + rows + " x " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) +
                                  " targets x " + std::to_string(n_read_thr) + " read thresholds: too many counters for one call");
     if (n_rec >= (int64_t)0xFFFFFF00) return fail(SMC_E_INPUT, who + ": too many covering records for one call");
-    if (!n_var || !n_reps || !n_targets) return SMC_OK;
-    if (!cov_off_host || !d_cov_off || !d_pos1 || !d_out) return fail(SMC_E_ARG, who + ": NULL argument");
+    if (!n_rows || !n_reps || !n_targets) return SMC_OK;
+    if (!off_host || !d_off || !d_pos1 || !d_out || (sets && (!set_m_host || !d_set_m || !seg_base_host || !d_seg_base)))
+        return fail(SMC_E_ARG, who + ": NULL argument");
     uint32_t widest = 0;
-    for (int32_t g = 0; g < n_var; ++g) {
-        if (cov_off_host[g + 1] < cov_off_host[g]) return fail(SMC_E_INPUT, who + ": the offsets decrease at variant " + std::to_string(g));
-        widest = std::max(widest, cov_off_host[g + 1] - cov_off_host[g]);
+    uint64_t n_seg = 0;
+    for (int32_t g = 0; g < n_rows; ++g) {
+        const uint32_t m = sets ? set_m_host[g] : 1u;
+        if (m < 1 || m > SMC_SPIKE_PHASE_MAX_MEMBERS)
+            return fail(SMC_E_INPUT, who + ": set " + std::to_string(g) + " has " + std::to_string(m) + " members, 1 .. " +
+                                     std::to_string(SMC_SPIKE_PHASE_MAX_MEMBERS) + " expected");
+        if (off_host[g + 1] < off_host[g]) return fail(SMC_E_INPUT, who + ": the offsets decrease at " + row + std::to_string(g));
+        if (sets && (uint64_t)seg_base_host[g] != n_seg)
+            return fail(SMC_E_INPUT, who + ": the segments of set " + std::to_string(g) + " start at " + std::to_string(seg_base_host[g]) + ", " +
+                                     std::to_string(n_seg) + " expected");
+        widest = std::max(widest, off_host[g + 1] - off_host[g]);
+        n_seg += (uint64_t)m * (uint64_t)(off_host[g + 1] - off_host[g]);
     }
-    const uint32_t n_cov = cov_off_host[n_var];
-    if (n_cov >= 0x55555500u) return fail(SMC_E_INPUT, who + ": too many covering barcodes for one call");
-    if (n_cov) {
-        if (!d_cov_ident || !d_rec_off || !rec_off_host) return fail(SMC_E_ARG, who + ": NULL covers");
-        for (uint32_t e = 0; e < n_cov; ++e)
-            if (rec_off_host[e + 1] < rec_off_host[e]) return fail(SMC_E_INPUT, who + ": the record offsets decrease at covering barcode " + std::to_string(e));
-        if ((int64_t)rec_off_host[n_cov] > n_rec)
-            return fail(SMC_E_INPUT, who + ": the record offsets end at " + std::to_string(rec_off_host[n_cov]) + ", beyond the " + std::to_string(n_rec) + " records");
+    if (!sets) n_seg = off_host[n_rows];                           // (a variant's segment is its barcode's index in the covers, whatever off_host[0] is)
+    if (off_host[n_rows] >= 0x55555500u || n_seg >= 0xFFFFFF00ull)
+        return fail(SMC_E_INPUT, who + ": too many " + (sets ? "joint" : "covering") + " barcodes for one call");
+    if (n_seg) {
+        if (!d_ident || !d_rec_off || !rec_off_host) return fail(SMC_E_ARG, who + (sets ? ": NULL joint barcodes" : ": NULL covers"));
+        for (uint64_t s = 0; s < n_seg; ++s)
+            if (rec_off_host[s + 1] < rec_off_host[s])
+                return fail(SMC_E_INPUT, who + ": the record offsets decrease at " + (sets ? "segment " : "covering barcode ") + std::to_string(s));
+        if ((int64_t)rec_off_host[n_seg] > n_rec)
+            return fail(SMC_E_INPUT, who + ": the record offsets end at " + std::to_string(rec_off_host[n_seg]) + ", beyond the " + std::to_string(n_rec) + " records");
         if (n_rec && (!d_rec_name || !d_rec_flag)) return fail(SMC_E_ARG, who + ": NULL records");
     }
     HIPCHK(hipSetDevice(ctx->device));
     const hipStream_t st = (hipStream_t)stream;
-    const size_t n_out = (size_t)SPC_COUNTERS * (size_t)n_var * (size_t)n_reps * (size_t)n_targets * (size_t)n_read_thr;
+    const size_t n_out = n_counters * (size_t)n_rows * (size_t)n_reps * (size_t)n_targets * (size_t)n_read_thr;
     hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
-    const auto kernel = four ? (n_read_thr <= 8 ? k_spr_counts<8, true> : k_spr_counts<SMC_RG_MAX_TARGETS, true>)
-                             : (n_read_thr <= 8 ? k_spr_counts<8, false> : k_spr_counts<SMC_RG_MAX_TARGETS, false>);
+    const bool few = n_read_thr <= 8;
+    const auto kernel = sets   ? (few ? k_spr_counts<8, false, true> : k_spr_counts<SMC_RG_MAX_TARGETS, false, true>)
+                        : four ? (few ? k_spr_counts<8, true, false> : k_spr_counts<SMC_RG_MAX_TARGETS, true, false>)
+                               : (few ? k_spr_counts<8, false, false> : k_spr_counts<SMC_RG_MAX_TARGETS, false, false>);
     if (widest)
-        hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<uint32_t>((widest + SPB_BLOCK - 1) / SPB_BLOCK, 256u), (unsigned)n_var,
-                                              (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPB_BLOCK), 0, st,
-                           (const unsigned long long*)d_cov_ident, d_cov_off, d_rec_off, (const unsigned long long*)d_rec_name, d_rec_flag,
-                           (uint32_t)n_rec, d_pos1, T, (int)n_targets, Q, (int)n_read_thr, (const unsigned long long*)d_seeds, (int)n_reps, d_out);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<uint32_t>((widest + SPB_BLOCK - 1) / SPB_BLOCK, 256u), (unsigned)n_rows,
+                                        (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPB_BLOCK), 0, st,
+                           (const unsigned long long*)d_ident, d_off, sets ? d_set_m : nullptr, sets ? d_seg_base : nullptr, d_rec_off,
+                           (const unsigned long long*)d_rec_name, d_rec_flag, (uint32_t)n_rec, d_pos1, T, (int)n_targets, Q, (int)n_read_thr,
+                           (const unsigned long long*)d_seeds, (int)n_reps, d_out);
     HIPCHK(hipGetLastError());
     return SMC_OK;
 }
 
+// (--spikeRpb) flag bit 2 of a record is `single`
 int smc_spike_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_off, const uint32_t* cov_off_host,
                          const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
                          int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
                          int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out, void* stream) {
-    return spr_cell_counts("smc_spike_rpb_counts", false, ctx, d_cov_ident, d_cov_off, cov_off_host, d_rec_off, rec_off_host, d_rec_name, d_rec_flag,
-                           n_rec, d_pos1, n_var, d_seeds, n_reps, thr, n_targets, read_thr, n_read_thr, d_out, stream);
+    return spr_cell_counts("smc_spike_rpb_counts", false, false, ctx, d_cov_ident, d_cov_off, cov_off_host, nullptr, nullptr, nullptr, nullptr,
+                           d_rec_off, rec_off_host, d_rec_name, d_rec_flag, n_rec, d_pos1, n_var, d_seeds, n_reps, thr, n_targets, read_thr,
+                           n_read_thr, d_out, stream);
 }
 
 // (--spikeIndelRpb) the same from FOUR bits per record: flag bit 2 = alt1, bit 3 = touch (smc_spike_indel_read_bits' bits 2 and 3)
@@ -1650,86 +1669,21 @@ int smc_spike_indel_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const 
                                int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps,
                                const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out,
                                void* stream) {
-    return spr_cell_counts("smc_spike_indel_rpb_counts", true, ctx, d_cov_ident, d_cov_off, cov_off_host, d_rec_off, rec_off_host, d_rec_name,
-                           d_rec_flag, n_rec, d_pos1, n_var, d_seeds, n_reps, thr, n_targets, read_thr, n_read_thr, d_out, stream);
+    return spr_cell_counts("smc_spike_indel_rpb_counts", true, false, ctx, d_cov_ident, d_cov_off, cov_off_host, nullptr, nullptr, nullptr,
+                           nullptr, d_rec_off, rec_off_host, d_rec_name, d_rec_flag, n_rec, d_pos1, n_var, d_seeds, n_reps, thr, n_targets,
+                           read_thr, n_read_thr, d_out, stream);
 }
 
-// (--spikePhaseRpb) (N_ALL', V0_ALL', S_ALL', V1_ALL') of every phase set, replicate and cell (spike target x read threshold), from the
-// records of every (joint barcode, member): everything checked on the host copies before anything is enqueued - the segment bases are
-// the running sums of (joint barcodes x members), so no lane reads an offset beyond the n_seg + 1 there are -, then the counters
-// zeroed and k_spr_phase_counts
+// (--spikePhaseRpb) the joint numbers of every phase set
 int smc_spike_phase_rpb_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, const uint32_t* d_joint_off, const uint32_t* joint_off_host,
                                const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_seg_base, const uint32_t* seg_base_host,
                                const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
                                int64_t n_rec, const uint32_t* d_pos1, int32_t n_sets, const uint64_t* d_seeds, int32_t n_reps,
                                const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out,
                                void* stream) {
-    const std::string who = "smc_spike_phase_rpb_counts";
-    if (!ctx || n_sets < 0 || n_reps < 0 || n_targets < 0 || n_rec < 0) return fail(SMC_E_ARG, who + ": bad argument");
-    if (n_sets > SMC_AF_MAX_VARIANTS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_sets) + " sets, at most " + std::to_string(SMC_AF_MAX_VARIANTS));
-    if (n_targets > SMC_SPIKE_REP_MAX_TARGETS)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets, at most " + std::to_string(SMC_SPIKE_REP_MAX_TARGETS));
-    if (n_reps > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_reps) + " replicates, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
-    if (n_read_thr < 1) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_read_thr) + " read thresholds, at least 1 expected");
-    if ((n_reps && !d_seeds) || (n_targets && !thr) || !read_thr) return fail(SMC_E_ARG, who + ": NULL argument");
-    if ((int64_t)n_targets * (int64_t)n_read_thr > SMC_AF_DEPTH_MAX_CELLS)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_targets) + " targets x " + std::to_string(n_read_thr) + " read thresholds, at most " +
-                                 std::to_string(SMC_AF_DEPTH_MAX_CELLS) + " cells");
-    SpkThr T;
-    RgThr Q;
-    memset(&T, 0, sizeof T);
-    memset(&Q, 0, sizeof Q);
-    for (int32_t t = 0; t < n_targets; ++t) {
-        if (thr[t] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": target " + std::to_string(t) + ": a threshold above 2^32");
-        T.t[t] = thr[t];
-    }
-    for (int32_t r = 0; r < n_read_thr; ++r) {
-        if (read_thr[r] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": read threshold " + std::to_string(r) + " is above 2^32");
-        if (r < SMC_RG_MAX_TARGETS) Q.t[r] = read_thr[r];         // (more of them pass the cells' limit only without a target: nothing is launched)
-    }
-    if ((double)n_sets * (double)n_reps * (double)n_targets * (double)n_read_thr * (double)SPP_COUNTERS >= (double)0xFFFFFF00u)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_sets) + " sets x " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) +
-                                 " targets x " + std::to_string(n_read_thr) + " read thresholds: too many counters for one call");
-    if (n_rec >= (int64_t)0xFFFFFF00) return fail(SMC_E_INPUT, who + ": too many covering records for one call");
-    if (!n_sets || !n_reps || !n_targets) return SMC_OK;
-    if (!joint_off_host || !d_joint_off || !set_m_host || !d_set_m || !seg_base_host || !d_seg_base || !d_pos1 || !d_out)
-        return fail(SMC_E_ARG, who + ": NULL argument");
-    uint32_t widest = 0;
-    uint64_t n_seg = 0;
-    for (int32_t g = 0; g < n_sets; ++g) {
-        const uint32_t m = set_m_host[g];
-        if (m < 1 || m > SMC_SPIKE_PHASE_MAX_MEMBERS)
-            return fail(SMC_E_INPUT, who + ": set " + std::to_string(g) + " has " + std::to_string(m) + " members, 1 .. " +
-                                     std::to_string(SMC_SPIKE_PHASE_MAX_MEMBERS) + " expected");
-        if (joint_off_host[g + 1] < joint_off_host[g]) return fail(SMC_E_INPUT, who + ": the offsets decrease at set " + std::to_string(g));
-        if ((uint64_t)seg_base_host[g] != n_seg)
-            return fail(SMC_E_INPUT, who + ": the segments of set " + std::to_string(g) + " start at " + std::to_string(seg_base_host[g]) + ", " +
-                                     std::to_string(n_seg) + " expected");
-        widest = std::max(widest, joint_off_host[g + 1] - joint_off_host[g]);
-        n_seg += (uint64_t)m * (uint64_t)(joint_off_host[g + 1] - joint_off_host[g]);
-    }
-    if (joint_off_host[n_sets] >= 0x55555500u || n_seg >= 0xFFFFFF00ull) return fail(SMC_E_INPUT, who + ": too many joint barcodes for one call");
-    if (n_seg) {
-        if (!d_joint_ident || !d_rec_off || !rec_off_host) return fail(SMC_E_ARG, who + ": NULL joint barcodes");
-        for (uint64_t s = 0; s < n_seg; ++s)
-            if (rec_off_host[s + 1] < rec_off_host[s]) return fail(SMC_E_INPUT, who + ": the record offsets decrease at segment " + std::to_string(s));
-        if ((int64_t)rec_off_host[n_seg] > n_rec)
-            return fail(SMC_E_INPUT, who + ": the record offsets end at " + std::to_string(rec_off_host[n_seg]) + ", beyond the " + std::to_string(n_rec) + " records");
-        if (n_rec && (!d_rec_name || !d_rec_flag)) return fail(SMC_E_ARG, who + ": NULL records");
-    }
-    HIPCHK(hipSetDevice(ctx->device));
-    const hipStream_t st = (hipStream_t)stream;
-    const size_t n_out = (size_t)SPP_COUNTERS * (size_t)n_sets * (size_t)n_reps * (size_t)n_targets * (size_t)n_read_thr;
-    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
-    const auto kernel = n_read_thr <= 8 ? k_spr_phase_counts<8> : k_spr_phase_counts<SMC_RG_MAX_TARGETS>;
-    if (widest)
-        hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<uint32_t>((widest + SPB_BLOCK - 1) / SPB_BLOCK, 256u), (unsigned)n_sets,
-                                        (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPB_BLOCK), 0, st,
-                           (const unsigned long long*)d_joint_ident, d_joint_off, d_set_m, d_seg_base, d_rec_off, (const unsigned long long*)d_rec_name,
-                           d_rec_flag, (uint32_t)n_rec, d_pos1, T, (int)n_targets, Q, (int)n_read_thr, (const unsigned long long*)d_seeds, (int)n_reps,
-                           d_out);
-    HIPCHK(hipGetLastError());
-    return SMC_OK;
+    return spr_cell_counts("smc_spike_phase_rpb_counts", false, true, ctx, d_joint_ident, d_joint_off, joint_off_host, d_set_m, set_m_host,
+                           d_seg_base, seg_base_host, d_rec_off, rec_off_host, d_rec_name, d_rec_flag, n_rec, d_pos1, n_sets, d_seeds, n_reps,
+                           thr, n_targets, read_thr, n_read_thr, d_out, stream);
 }
 
 // (--spikeIndelRpb) per listed variant of a run - an SNV, an insertion, a deletion - and alignment one byte: covers / shows the key /

@@ -15,11 +15,12 @@
 //   k_spr_bits    (smc_spike_read_bits) a lane per alignment, a row of workgroups per listed SNV: bit 0 the record covers the
 //                 position, bit 1 it shows ALT as it is (af_shows), bit 2 its allele key there is a single letter - the records
 //                 k_spike_rewrite touches.  A plain byte store per alignment, 0 outside the locus's window: no atomics.
-//   k_spr_counts  (smc_spike_rpb_counts) a lane per covering barcode of a variant (blockIdx.y = variant, blockIdx.z strides over the
-//                 replicates).  The lane walks the barcode's records (a CSR segment: name identity and flag byte, bit 0 = first name,
-//                 bits 1 / 2 = alt / single from k_spr_bits): ONE philox per record and replicate, its compares against the Rr read
-//                 thresholds one bit set; per r the lane keeps (reads_r, alt_r, single_r) over the kept records.  Then per barcode
-//                 and r:  N' = reads_r > 0,  car0 = 2 alt_r > reads_r,  car1 = 2 single_r > reads_r,  and per cell (t, r)
+//   k_spr_counts  (smc_spike_rpb_counts, smc_spike_indel_rpb_counts, smc_spike_phase_rpb_counts) ONE body, <MAXR, FOUR, SETS>: a lane
+//                 per barcode of a row (blockIdx.y = row, blockIdx.z strides over the replicates), one spike draw per (barcode, row,
+//                 replicate).  The lane walks a CSR segment of records (name identity and flag byte, bit 0 = first name, bits 1 / 2 =
+//                 alt / single from k_spr_bits): ONE philox per record and replicate, its compares against the Rr read thresholds one
+//                 bit set; per r the lane keeps (reads_r, alt_r, single_r) over the kept records.  Then per barcode and r:
+//                 N' = reads_r > 0,  car0 = 2 alt_r > reads_r,  car1 = 2 single_r > reads_r,  and per cell (t, r)
 //                   V0' = N' && car0    S' = N' && hit    READS' = single_r over N' && hit    V1' = N' && (hit ? car1 : car0)
 //                 reduced as k_spike_cells reduces: ballots + popcounts and a DPP sum for READS', the workgroup's wavefronts added in
 //                 LDS, one integer atomic add per workgroup, replicate, cell and counter that is not 0 - two calls give the same words.
@@ -32,9 +33,18 @@
 //                 alt1, bit 3 = touch.  An SNV's bits 2 and 3 are both k_spr_bits' bit 2 (spr_snv_bits, shared); an indel's touch is
 //                 spi_walk<false, SPI_TOUCH_ONE> - the rewrite's own eligibility lines, the 16-bit limits included -, its alt1 a
 //                 touched record whose anchor letter is REF's first, or an untouched one that shows the key already.
-//   k_spr_counts<MAXR, true>  the SAME body with a fourth per-r counter: car1 from alt1_r (flag bit 2), READS' from touch_r (flag bit
-//                 3).  The SNV entry is the instance <MAXR, false>, in which touch IS alt1 - no fourth array exists there and its
-//                 code is what it was.
+//   FOUR          a fourth per-r counter: car1 from alt1_r (flag bit 2), READS' from touch_r (flag bit 3).  Without it touch IS alt1
+//                 and no fourth array exists.
+// --spikePhaseRpb (smc_spike_phase_rpb_counts): the JOINT numbers of phase sets under read thinning.  A set's barcode counts when it
+// keeps a read at EVERY member and carries it when it does so at EVERY member; thinning can take it out of one member's pileup, or flip
+// its majority at one member only, so the joint numbers cannot be had from the members' own cells: they are made per record as well.
+//   SETS          a row is a phase set, a lane one of its JOINT barcodes, the spike draw made with the leader's position.  The lane
+//                 walks its M_g members one after the other (segment seg_base[g] + (e - off[g]) * M_g + m), folds each member's
+//                 3 x MAXR counters into three bit sets over r - there, car0, car1 - and ANDs them into the running all-members
+//                 sets: registers do not grow with M_g.  Four counters per cell, (N_ALL', V0_ALL', S_ALL', V1_ALL'): a set has no
+//                 READS', so flag bit 3 is not read and there is no <MAXR, true, true>.  A record that spans several members is a
+//                 record of each of their segments, and its read draw is made once per member.  Without SETS a row is a listed
+//                 variant - a set of one member whose segments are its covering barcodes - and its bit sets are never formed.
 #define SPB_BLOCK 256
 #define SPB_COVERS 1u
 #define SPB_ALT 2u
@@ -123,114 +133,35 @@ __global__ __launch_bounds__(SPB_BLOCK) void k_spr_indel_bits(const smc_dev_aln*
     }
 }
 
-// out[(((g * n_reps + j) * n_tgt + t) * n_rr + r) * 5 + k] += counter k of (N', V0', S', READS', V1') (zeroed before the launch); n_tgt *
-// n_rr <= SMC_AF_DEPTH_MAX_CELLS.  Variant g: barcodes [off[g], off[g + 1]) of `ident`; barcode e: records [rec_off[e], rec_off[e + 1])
-// of rec_name / rec_flag, clamped to n_rec.  n_rr <= MAXR (the host picks the instance).  FOUR (smc_spike_indel_rpb_counts): flag bit 2
-// is alt1 and bit 3 touch, a per-r counter each; without it bit 2 is both (`single`) and bit 3 is not read.
-template <int MAXR, bool FOUR>
+// records [r0, r1) of segment s, clamped to the n_rec there are
+__device__ __forceinline__ void spr_segment(const uint32_t* __restrict__ rec_off, uint32_t s, uint32_t n_rec, uint32_t& r0, uint32_t& r1) {
+    r0 = min(rec_off[s], n_rec);
+    r1 = min(rec_off[s + 1], n_rec);
+}
+
+#define SPP_COUNTERS 4
+// Without SETS  out[(((g * n_reps + j) * n_tgt + t) * n_rr + r) * 5 + k] += counter k of (N', V0', S', READS', V1'),
+// with SETS     out[(((g * n_reps + j) * n_tgt + t) * n_rr + r) * 4 + k] += counter k of (N_ALL', V0_ALL', S_ALL', V1_ALL')
+// (zeroed before the launch); n_tgt * n_rr <= SMC_AF_DEPTH_MAX_CELLS, n_rr <= MAXR (the host picks the instance).  Row g: barcodes
+// [off[g], off[g + 1]) of `ident`; segment s: records [rec_off[s], rec_off[s + 1]) of rec_name / rec_flag, clamped to n_rec.  A listed
+// variant is a set of ONE member whose segments are its covering barcodes (segment e for barcode e: set_m and seg_base are not read);
+// with SETS row g has set_m[g] members (1 .. SMC_SPIKE_PHASE_MAX_MEMBERS: the host checked) and its segments start at seg_base[g].
+// FOUR (smc_spike_indel_rpb_counts): flag bit 2 is alt1 and bit 3 touch, a per-r counter each; without it bit 2 is both (`single`) and
+// bit 3 is not read - a set has no READS', so it never reads it.
+template <int MAXR, bool FOUR, bool SETS>
 __global__ __launch_bounds__(SPB_BLOCK) void k_spr_counts(const unsigned long long* __restrict__ ident, const uint32_t* __restrict__ off,
+                                                          const uint32_t* __restrict__ set_m, const uint32_t* __restrict__ seg_base,
                                                           const uint32_t* __restrict__ rec_off, const unsigned long long* __restrict__ rec_name,
                                                           const uint8_t* __restrict__ rec_flag, uint32_t n_rec,
                                                           const uint32_t* __restrict__ pos1, SpkThr T, int n_tgt, RgThr Q, int n_rr,
                                                           const unsigned long long* __restrict__ seeds, int n_reps, uint32_t* __restrict__ out) {
-    __shared__ uint32_t part[SPB_BLOCK / WAVE][SMC_AF_DEPTH_MAX_CELLS][SPC_COUNTERS];
+    static_assert(!(FOUR && SETS), "k_spr_counts: a set never reads flag bit 3");
+    constexpr int NC = SETS ? SPP_COUNTERS : SPC_COUNTERS;
+    constexpr int TAIL = SETS ? 1 : MAXR;                  // (the cells' tail unrolled over the per-r arrays; a set's reads bit r of three words: a loop)
+    __shared__ uint32_t part[SPB_BLOCK / WAVE][SMC_AF_DEPTH_MAX_CELLS][NC];
     const uint32_t g = blockIdx.y;
     const uint32_t e0 = off[g], e1 = off[g + 1], pos = pos1[g];
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    const int n_cells = n_tgt * n_rr;
-    const uint32_t every = n_rr >= 32 ? 0xFFFFFFFFu : (1u << n_rr) - 1u;
-    const uint32_t stride = gridDim.x * SPB_BLOCK;
-    for (uint32_t base = e0 + blockIdx.x * SPB_BLOCK; base < e1; base += stride) {     // (whole workgroups: the barriers below)
-        const uint32_t e = base + threadIdx.x;
-        unsigned long long id = 0;
-        uint32_t r0 = 0, r1 = 0;                                                       // (a lane beyond the row: no records, N' = 0 everywhere)
-        if (e < e1) {
-            id = ident[e];
-            r0 = min(rec_off[e], n_rec);
-            r1 = min(rec_off[e + 1], n_rec);
-        }
-        for (int j = blockIdx.z; j < n_reps; j += gridDim.z) {
-            const unsigned long long seed = seeds[j];
-            uint32_t x[4];
-            smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, pos, (uint32_t)seed, (uint32_t)(seed >> 32), x);
-            const uint32_t k_hit = spd_hits(T, x[0], n_tgt);
-            uint32_t reads[MAXR], alt[MAXR], sgl[MAXR], tch[FOUR ? MAXR : 1];
-#pragma unroll
-            for (int r = 0; r < MAXR; ++r) { reads[r] = alt[r] = sgl[r] = 0u; if (FOUR) tch[r] = 0u; }
-            for (uint32_t i = r0; i < r1; ++i) {
-                const uint32_t fl = rec_flag[i];
-                uint32_t kept = every;
-                if (!(fl & SPB_FIRST)) {
-                    const uint32_t u = rg_draw(rec_name[i], seed);
-                    kept = 0u;
-                    for (int r = 0; r < n_rr; ++r) kept |= (uint32_t)((unsigned long long)u < Q.t[r]) << r;
-                }
-                const uint32_t is_alt = (fl >> 1) & 1u, is_sgl = (fl >> 2) & 1u, is_tch = (fl >> 3) & 1u;
-#pragma unroll
-                for (int r = 0; r < MAXR; ++r) {
-                    const uint32_t k = (kept >> r) & 1u;
-                    reads[r] += k; alt[r] += k & is_alt; sgl[r] += k & is_sgl;
-                    if (FOUR) tch[r] += k & is_tch;
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < MAXR; ++r) {
-                if (r < n_rr) {                                                        // (uniform)
-                    const bool there = reads[r] > 0u;
-                    const bool car0 = 2ull * alt[r] > (unsigned long long)reads[r], car1 = 2ull * sgl[r] > (unsigned long long)reads[r];
-                    const unsigned long long m_n = __ballot(there), m_v0 = __ballot(there && car0);
-                    for (int t = 0; t < n_tgt; ++t) {
-                        const bool hit = ((k_hit >> t) & 1u) != 0u;
-                        const unsigned long long m_s = __ballot(there && hit), m_v1 = __ballot(there && (hit ? car1 : car0));
-                        // (a run holds fewer than 2^32 - 256 alignments: no wrap that matters)
-                        const int rd = wave_add((int)((there && hit) ? (FOUR ? tch[r] : sgl[r]) : 0u));
-                        if (lane == 0) {
-                            uint32_t* const p = part[wave][t * n_rr + r];
-                            p[0] = (uint32_t)__popcll(m_n); p[1] = (uint32_t)__popcll(m_v0); p[2] = (uint32_t)__popcll(m_s);
-                            p[3] = (uint32_t)rd; p[4] = (uint32_t)__popcll(m_v1);
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            if ((int)threadIdx.x < SPC_COUNTERS * n_cells) {                           // (5 * 32 = 160 < SPB_BLOCK)
-                const int c = threadIdx.x / SPC_COUNTERS, q = threadIdx.x % SPC_COUNTERS;
-                uint32_t sum = 0;
-                for (int w = 0; w < SPB_BLOCK / WAVE; ++w) sum += part[w][c][q];
-                if (sum) atomicAdd(&out[(((size_t)g * n_reps + j) * n_cells + c) * SPC_COUNTERS + q], sum);
-            }
-            __syncthreads();
-        }
-    }
-}
-static_assert(SMC_RG_MAX_TARGETS == SMC_AF_DEPTH_MAX_CELLS && SPC_COUNTERS * SMC_AF_DEPTH_MAX_CELLS <= SPB_BLOCK,
-              "k_spr_counts: a bit per read threshold, a lane per cell and counter");
-
-// --spikePhaseRpb (smc_spike_phase_rpb_counts): the JOINT numbers of phase sets under read thinning.  A set's barcode counts when it
-// keeps a read at EVERY member and carries it when it does so at EVERY member; thinning can take it out of one member's pileup, or flip
-// its majority at one member only, so the joint numbers cannot be had from the members' own cells: they are made per record as well.
-//   k_spr_phase_counts  k_spr_counts' shape: a lane per JOINT barcode of a set (blockIdx.y = set, blockIdx.z strides over the
-//                 replicates), ONE spike draw per (barcode, set, replicate) with the leader's position.  The lane walks its M_g members
-//                 one after the other, each a CSR segment of covering records (segment seg_base[g] + (e - off[g]) * M_g + m); per
-//                 member the 3 x MAXR counters (reads_r, alt0_r, alt1_r) of k_spr_counts, which it then folds into three bit sets
-//                 over r - there, car0, car1 - and ANDs into the running all-members sets: registers do not grow with M_g.  Per r and
-//                 t four ballots + popcounts, the wavefronts added in LDS, one integer atomic add per workgroup, replicate, cell and
-//                 counter that is not 0.  Flag bit 3 (touch) is not read: a set has no READS'.
-// A record that spans several members is a record of each of their segments, and its read draw is made once per member.
-#define SPP_COUNTERS 4
-// out[(((g * n_reps + j) * n_tgt + t) * n_rr + r) * 4 + k] += counter k of (N_ALL', V0_ALL', S_ALL', V1_ALL') (zeroed before the launch).
-// Set g: joint barcodes [off[g], off[g + 1]) of `ident`, set_m[g] members (1 .. SMC_SPIKE_PHASE_MAX_MEMBERS: the host checked), its
-// segments from seg_base[g]; segment s: records [rec_off[s], rec_off[s + 1]) clamped to n_rec.  n_rr <= MAXR.
-template <int MAXR>
-__global__ __launch_bounds__(SPB_BLOCK) void k_spr_phase_counts(const unsigned long long* __restrict__ ident, const uint32_t* __restrict__ off,
-                                                                const uint32_t* __restrict__ set_m, const uint32_t* __restrict__ seg_base,
-                                                                const uint32_t* __restrict__ rec_off, const unsigned long long* __restrict__ rec_name,
-                                                                const uint8_t* __restrict__ rec_flag, uint32_t n_rec,
-                                                                const uint32_t* __restrict__ pos1, SpkThr T, int n_tgt, RgThr Q, int n_rr,
-                                                                const unsigned long long* __restrict__ seeds, int n_reps, uint32_t* __restrict__ out) {
-    __shared__ uint32_t part[SPB_BLOCK / WAVE][SMC_AF_DEPTH_MAX_CELLS][SPP_COUNTERS];
-    const uint32_t g = blockIdx.y;
-    const uint32_t e0 = off[g], e1 = off[g + 1], pos = pos1[g], n_mem = set_m[g], s_base = seg_base[g];
+    const uint32_t n_mem = SETS ? set_m[g] : 1u, s_base = SETS ? seg_base[g] : 0u;
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const int n_cells = n_tgt * n_rr;
     const uint32_t every = n_rr >= 32 ? 0xFFFFFFFFu : (1u << n_rr) - 1u;
@@ -239,22 +170,20 @@ __global__ __launch_bounds__(SPB_BLOCK) void k_spr_phase_counts(const unsigned l
         const uint32_t e = base + threadIdx.x;
         const bool in_row = e < e1;
         const unsigned long long id = in_row ? ident[e] : 0ull;
-        const uint32_t s0 = s_base + (e - e0) * n_mem;                                 // (read only in_row)
+        const uint32_t s0 = s_base + (e - e0) * n_mem;                                 // (SETS, read only in_row)
+        uint32_t r0 = 0, r1 = 0;                                                       // (a lane beyond the row: no records, N' = 0 everywhere)
+        if (!SETS && in_row) spr_segment(rec_off, e, n_rec, r0, r1);                   // (the variant's one segment, the same for every replicate)
         for (int j = blockIdx.z; j < n_reps; j += gridDim.z) {
             const unsigned long long seed = seeds[j];
             uint32_t x[4];
             smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, pos, (uint32_t)seed, (uint32_t)(seed >> 32), x);
             const uint32_t k_hit = spd_hits(T, x[0], n_tgt);
-            uint32_t all_there = in_row ? every : 0u, all_c0 = every, all_c1 = every;  // (a lane beyond the row: N_ALL' = 0 everywhere)
-            for (uint32_t m = 0; m < n_mem; ++m) {                                     // (uniform bound; a lane beyond the row walks nothing)
-                uint32_t r0 = 0, r1 = 0;
-                if (in_row) {
-                    r0 = min(rec_off[s0 + m], n_rec);
-                    r1 = min(rec_off[s0 + m + 1], n_rec);
-                }
-                uint32_t reads[MAXR], alt[MAXR], sgl[MAXR];
+            uint32_t reads[MAXR], alt[MAXR], sgl[MAXR], tch[FOUR ? MAXR : 1];
+            uint32_t all_there = in_row ? every : 0u, all_c0 = every, all_c1 = every;  // (SETS; a lane beyond the row: N_ALL' = 0 everywhere)
+            for (uint32_t m = 0; m < n_mem; ++m) {                                     // (uniform bound; once without SETS)
+                if (SETS && in_row) spr_segment(rec_off, s0 + m, n_rec, r0, r1);
 #pragma unroll
-                for (int r = 0; r < MAXR; ++r) reads[r] = alt[r] = sgl[r] = 0u;
+                for (int r = 0; r < MAXR; ++r) { reads[r] = alt[r] = sgl[r] = 0u; if (FOUR) tch[r] = 0u; }
                 for (uint32_t i = r0; i < r1; ++i) {
                     const uint32_t fl = rec_flag[i];
                     uint32_t kept = every;
@@ -263,44 +192,56 @@ __global__ __launch_bounds__(SPB_BLOCK) void k_spr_phase_counts(const unsigned l
                         kept = 0u;
                         for (int r = 0; r < n_rr; ++r) kept |= (uint32_t)((unsigned long long)u < Q.t[r]) << r;
                     }
-                    const uint32_t is_alt = (fl >> 1) & 1u, is_sgl = (fl >> 2) & 1u;
+                    const uint32_t is_alt = (fl >> 1) & 1u, is_sgl = (fl >> 2) & 1u, is_tch = (fl >> 3) & 1u;
 #pragma unroll
                     for (int r = 0; r < MAXR; ++r) {
                         const uint32_t k = (kept >> r) & 1u;
                         reads[r] += k; alt[r] += k & is_alt; sgl[r] += k & is_sgl;
+                        if (FOUR) tch[r] += k & is_tch;
                     }
                 }
-                uint32_t there = 0u, c0 = 0u, c1 = 0u;
+                if (SETS) {                                                            // (the member's counters fold into three bit sets over r)
+                    uint32_t there = 0u, c0 = 0u, c1 = 0u;
 #pragma unroll
-                for (int r = 0; r < MAXR; ++r) {
-                    there |= (uint32_t)(reads[r] > 0u) << r;
-                    c0 |= (uint32_t)(2ull * alt[r] > (unsigned long long)reads[r]) << r;
-                    c1 |= (uint32_t)(2ull * sgl[r] > (unsigned long long)reads[r]) << r;
+                    for (int r = 0; r < MAXR; ++r) {
+                        there |= (uint32_t)(reads[r] > 0u) << r;
+                        c0 |= (uint32_t)(2ull * alt[r] > (unsigned long long)reads[r]) << r;
+                        c1 |= (uint32_t)(2ull * sgl[r] > (unsigned long long)reads[r]) << r;
+                    }
+                    all_there &= there; all_c0 &= c0; all_c1 &= c1;
                 }
-                all_there &= there; all_c0 &= c0; all_c1 &= c1;
             }
-            for (int r = 0; r < n_rr; ++r) {                                           // (uniform)
-                const bool there = ((all_there >> r) & 1u) != 0u;
-                const bool car0 = ((all_c0 >> r) & 1u) != 0u, car1 = ((all_c1 >> r) & 1u) != 0u;
-                const unsigned long long m_n = __ballot(there), m_v0 = __ballot(there && car0);
-                for (int t = 0; t < n_tgt; ++t) {
-                    const bool hit = ((k_hit >> t) & 1u) != 0u;
-                    const unsigned long long m_s = __ballot(there && hit), m_v1 = __ballot(there && (hit ? car1 : car0));
-                    if (lane == 0) {
-                        uint32_t* const p = part[wave][t * n_rr + r];
-                        p[0] = (uint32_t)__popcll(m_n); p[1] = (uint32_t)__popcll(m_v0); p[2] = (uint32_t)__popcll(m_s);
-                        p[3] = (uint32_t)__popcll(m_v1);
+#pragma unroll TAIL
+            for (int r = 0; r < (SETS ? n_rr : MAXR); ++r) {
+                if (r < n_rr) {                                                        // (uniform)
+                    const bool there = SETS ? ((all_there >> r) & 1u) != 0u : reads[r] > 0u;
+                    const bool car0 = SETS ? ((all_c0 >> r) & 1u) != 0u : 2ull * alt[r] > (unsigned long long)reads[r];
+                    const bool car1 = SETS ? ((all_c1 >> r) & 1u) != 0u : 2ull * sgl[r] > (unsigned long long)reads[r];
+                    const unsigned long long m_n = __ballot(there), m_v0 = __ballot(there && car0);
+                    for (int t = 0; t < n_tgt; ++t) {
+                        const bool hit = ((k_hit >> t) & 1u) != 0u;
+                        const unsigned long long m_s = __ballot(there && hit), m_v1 = __ballot(there && (hit ? car1 : car0));
+                        int rd = 0;                                                    // (a run holds fewer than 2^32 - 256 alignments: no wrap that matters)
+                        if (!SETS) rd = wave_add((int)((there && hit) ? (FOUR ? tch[r] : sgl[r]) : 0u));
+                        if (lane == 0) {
+                            uint32_t* const p = part[wave][t * n_rr + r];
+                            p[0] = (uint32_t)__popcll(m_n); p[1] = (uint32_t)__popcll(m_v0); p[2] = (uint32_t)__popcll(m_s);
+                            if (!SETS) p[3] = (uint32_t)rd;
+                            p[NC - 1] = (uint32_t)__popcll(m_v1);
+                        }
                     }
                 }
             }
             __syncthreads();
-            if ((int)threadIdx.x < SPP_COUNTERS * n_cells) {                           // (4 * 32 = 128 < SPB_BLOCK)
-                const int c = threadIdx.x / SPP_COUNTERS, q = threadIdx.x % SPP_COUNTERS;
+            if ((int)threadIdx.x < NC * n_cells) {                                     // (5 * 32 = 160 < SPB_BLOCK)
+                const int c = threadIdx.x / NC, q = threadIdx.x % NC;
                 uint32_t sum = 0;
                 for (int w = 0; w < SPB_BLOCK / WAVE; ++w) sum += part[w][c][q];
-                if (sum) atomicAdd(&out[(((size_t)g * n_reps + j) * n_cells + c) * SPP_COUNTERS + q], sum);
+                if (sum) atomicAdd(&out[(((size_t)g * n_reps + j) * n_cells + c) * NC + q], sum);
             }
             __syncthreads();
         }
     }
 }
+static_assert(SMC_RG_MAX_TARGETS == SMC_AF_DEPTH_MAX_CELLS && SPP_COUNTERS <= SPC_COUNTERS && SPC_COUNTERS * SMC_AF_DEPTH_MAX_CELLS <= SPB_BLOCK,
+              "k_spr_counts: a bit per read threshold, a lane per cell and counter");

@@ -2426,6 +2426,20 @@ def run_first_names(eng, groups: ReadGroups, p_idents, chrom: str = "?", lo: int
     return np.unpackbits(words.view(np.uint8), bitorder="little")[:len(p_idents)].astype(bool)
 
 
+def _spike_rpb_flat(csrs, n_segs, head):
+    """The record CSRs of the rows of one counts call, one after the other: csrs[g] = (offsets over n_segs[g] segments, name identities,
+    flag bytes) -> (uint32 offsets over every segment, uint64 names, uint8 flags).  head(g): how a ValueError names row g."""
+    rec_off, base = [np.zeros(1, np.int64)], 0
+    for g, ((o, names, flags), n) in enumerate(zip(csrs, n_segs)):
+        o = np.asarray(o, np.int64)
+        if len(o) != n + 1 or len(names) != len(flags) or int(o[0]) != 0 or int(o[-1]) != len(names):
+            raise ValueError("%s, %d offsets over %d names and %d flags" % (head(g), len(o), len(names), len(flags)))
+        rec_off.append(o[1:] + base)
+        base += len(names)
+    cat = lambda k, dtype: np.concatenate([np.asarray(c[k], dtype) for c in csrs]) if len(csrs) else np.zeros(0, dtype)
+    return np.concatenate(rec_off).astype(np.uint32), cat(1, np.uint64), cat(2, np.uint8)
+
+
 def spike_rpb_counts(eng, positions, covers, records, seeds, thresholds, read_thresholds, four: bool = False) -> np.ndarray:
     """smc_spike_rpb_counts -> uint32 [V, R, T, Rr, 5] = (N', V0', S', READS', V1') of every variant, replicate and cell.  positions,
     covers, seeds, thresholds: spike_rep_counts'; records[v]: spike_rpb_records' (offsets [len(covers[v]) + 1], name identities, flag
@@ -2435,17 +2449,8 @@ def spike_rpb_counts(eng, positions, covers, records, seeds, thresholds, read_th
     off = np.zeros(n_var + 1, np.uint32)
     off[1:] = np.cumsum([len(c) for c in covers])
     ident = np.concatenate([np.asarray(c, np.uint64) for c in covers]) if n_var else np.zeros(0, np.uint64)
-    rec_off, base = [np.zeros(1, np.int64)], 0
-    for v, (c, (o, names, flags)) in enumerate(zip(covers, records)):
-        o = np.asarray(o, np.int64)
-        if len(o) != len(c) + 1 or len(names) != len(flags) or (len(o) and (int(o[0]) != 0 or int(o[-1]) != len(names))):
-            raise ValueError("spike_rpb_counts: variant %d: %d covering barcodes, %d offsets over %d names and %d flags" %
-                             (v, len(c), len(o), len(names), len(flags)))
-        rec_off.append(o[1:] + base)
-        base += len(names)
-    rec_off = np.concatenate(rec_off).astype(np.uint32)
-    name = np.concatenate([np.asarray(r[1], np.uint64) for r in records]) if n_var else np.zeros(0, np.uint64)
-    flag = np.concatenate([np.asarray(r[2], np.uint8) for r in records]) if n_var else np.zeros(0, np.uint8)
+    rec_off, name, flag = _spike_rpb_flat(records, [len(c) for c in covers],
+                                          lambda v: "spike_rpb_counts: variant %d: %d covering barcodes" % (v, len(covers[v])))
     pos = np.array([int(p) & 0xFFFFFFFF for p in positions], np.uint32)
     seeds = np.ascontiguousarray(seeds, np.uint64)
     thr, rthr = np.ascontiguousarray(thresholds, np.uint64), np.ascontiguousarray(read_thresholds, np.uint64)
@@ -2457,6 +2462,15 @@ def spike_rpb_counts(eng, positions, covers, records, seeds, thresholds, read_th
                                                     d_out, ctypes.c_void_p(0)))
 
 
+def _spike_joint_index(s, covers):
+    """Phase set `s` -> (uint64 [n]: the identities of the barcodes that cover EVERY member, ascending; per member, in the set's order,
+    int64 [n]: where each of them stands in covers[member])."""
+    ids = [np.asarray(covers[k], np.uint64) for k in s.members]
+    both = np.unique(functools.reduce(np.intersect1d, ids))
+    orders = [np.argsort(x, kind="stable") for x in ids]
+    return both, [o[np.searchsorted(x[o], both)] if len(both) else np.zeros(0, np.int64) for x, o in zip(ids, orders)]
+
+
 def spike_joint(sets, covers, counters):
     """Per phase set (tools.spike_variants.PhaseSet) -> (uint64 [n]: the identities of the barcodes that cover EVERY member, ascending;
     uint32 [n, M, 3]: their (reads, alt0, single) at each member, in the set's order).  covers[v] / counters[v]: per listed variant
@@ -2464,15 +2478,12 @@ def spike_joint(sets, covers, counters):
     (spike_indel_counts': reads, alt0, alt1, touch), uint32 [n, M, 4]."""
     out = []
     for s in sets:
-        ids = [np.asarray(covers[k], np.uint64) for k in s.members]
-        both = np.unique(functools.reduce(np.intersect1d, ids))
+        both, at = _spike_joint_index(s, covers)
         first = np.asarray(counters[s.members[0]])
         width = int(first.shape[1]) if first.ndim == 2 else 3
         cnt = np.zeros((len(both), len(s.members), width), np.uint32)
-        for m, (k, x) in enumerate(zip(s.members, ids)):
-            order = np.argsort(x, kind="stable")
-            at = order[np.searchsorted(x[order], both)] if len(both) else np.zeros(0, np.int64)
-            cnt[:, m] = np.asarray(counters[k], np.uint32).reshape(-1, width)[at]
+        for m, k in enumerate(s.members):
+            cnt[:, m] = np.asarray(counters[k], np.uint32).reshape(-1, width)[at[m]]
         out.append((both, cnt))
     return out
 
@@ -2523,20 +2534,17 @@ def spike_joint_records(sets, covers, records):
     by identity.  A record that spans several members stands in the segment of each."""
     out = []
     for s in sets:
-        ids = [np.asarray(covers[k], np.uint64) for k in s.members]
-        both = np.unique(functools.reduce(np.intersect1d, ids))
+        both, at = _spike_joint_index(s, covers)
         n, M = len(both), len(s.members)
         start, length = np.zeros((n, M), np.int64), np.zeros((n, M), np.int64)
         base, pools = 0, []
-        for m, (k, x) in enumerate(zip(s.members, ids)):
+        for m, k in enumerate(s.members):
             o, names, flags = records[k]
             o = np.asarray(o, np.int64)
-            if len(o) != len(x) + 1 or len(names) != len(flags):
+            if len(o) != len(covers[k]) + 1 or len(names) != len(flags):
                 raise ValueError("spike_joint_records: set %s, member %d: %d covering barcodes, %d offsets over %d names and %d flags" %
-                                 (s.name, m, len(x), len(o), len(names), len(flags)))
-            order = np.argsort(x, kind="stable")
-            at = order[np.searchsorted(x[order], both)] if n else np.zeros(0, np.int64)
-            start[:, m], length[:, m] = o[at] + base, o[at + 1] - o[at]
+                                 (s.name, m, len(covers[k]), len(o), len(names), len(flags)))
+            start[:, m], length[:, m] = o[at[m]] + base, o[at[m] + 1] - o[at[m]]
             base += len(names)
             pools.append((np.asarray(names, np.uint64), np.asarray(flags, np.uint8)))
         off = np.zeros(n * M + 1, np.int64)
@@ -2558,21 +2566,12 @@ def spike_phase_rpb_counts(eng, lead_positions, set_members, joint_records, seed
     set_m = np.array([int(m) for m in set_members], np.uint32)
     off = np.zeros(G + 1, np.uint32)
     off[1:] = np.cumsum([len(j[0]) for j in joint_records])
-    seg_base = np.zeros(G, np.uint32)
-    rec_off, base, n_seg = [np.zeros(1, np.int64)], 0, 0
-    for g, (ids, o, names, flags) in enumerate(joint_records):
-        o = np.asarray(o, np.int64)
-        if len(o) != len(ids) * int(set_m[g]) + 1 or len(names) != len(flags) or int(o[0]) != 0 or int(o[-1]) != len(names):
-            raise ValueError("spike_phase_rpb_counts: set %d: %d joint barcodes of %d members, %d offsets over %d names and %d flags" %
-                             (g, len(ids), int(set_m[g]), len(o), len(names), len(flags)))
-        seg_base[g] = n_seg
-        rec_off.append(o[1:] + base)
-        base += len(names)
-        n_seg += len(o) - 1
-    rec_off = np.concatenate(rec_off).astype(np.uint32)
+    n_segs = [len(j[0]) * int(m) for j, m in zip(joint_records, set_m)]
+    seg_base = np.cumsum([0] + n_segs)[:-1].astype(np.uint32)
+    rec_off, name, flag = _spike_rpb_flat(
+        [j[1:] for j in joint_records], n_segs,
+        lambda g: "spike_phase_rpb_counts: set %d: %d joint barcodes of %d members" % (g, len(joint_records[g][0]), int(set_m[g])))
     ident = np.concatenate([np.asarray(j[0], np.uint64) for j in joint_records]) if G else np.zeros(0, np.uint64)
-    name = np.concatenate([np.asarray(j[2], np.uint64) for j in joint_records]) if G else np.zeros(0, np.uint64)
-    flag = np.concatenate([np.asarray(j[3], np.uint8) for j in joint_records]) if G else np.zeros(0, np.uint8)
     pos = np.array([int(p) & 0xFFFFFFFF for p in lead_positions], np.uint32)
     seeds = np.ascontiguousarray(seeds, np.uint64)
     thr, rthr = np.ascontiguousarray(thresholds, np.uint64), np.ascontiguousarray(read_thresholds, np.uint64)

@@ -2,6 +2,7 @@
 the synthetic case and bam_cigars through the device's own path (the read bits entry, spike_rpb_records, spike_joint_records) and on
 made-up record lists for the kernel's edges; its two equivalences against smc_spike_indel_rpb_counts and smc_spike_indel_phase_counts on
 the device; an SNV-only list fed with smc_spike_read_bits' bytes; the refusals."""
+import collections
 import os
 import sys
 
@@ -251,6 +252,29 @@ def test_one_replicate_the_ends_of_both_axes_and_the_two_equivalences(engine0):
         counters.append(np.stack([np.diff(off.astype(np.int64))] + sums, axis=1).astype(np.uint32))
     whole = devplanes.spike_indel_phase_counts(eng, lead, devplanes.spike_joint(sets, covers, counters), PR.seeds(SEED, 3), thr, [ONE])
     assert np.array_equal(got[:, :, :, 3:], whole) and whole[1].any()
+
+
+@pytest.mark.parametrize("n_rthr", (4, 9))
+def test_a_set_of_one_member_is_a_listed_variant_in_both_instances(engine0, n_rthr):
+    """The two faces of k_spr_counts where they overlap: a set of one member through smc_spike_phase_rpb_counts against the same rows
+    as listed variants through smc_spike_indel_rpb_counts (four-bit flags) and smc_spike_rpb_counts (flags without bit 3), both against
+    the restatement.  The middle row is one nobody covers; 4 read thresholds take the instance of 8, 9 the wide one."""
+    eng = engine0
+    rows = _made([(1, 210, 0), (1, 0, 0), (1, 33, 0)], seed=13)
+    assert [len({r.barcode for r in s[0]}) for s in rows] == [210, 0, 33]
+    per = [n for s in rows for n in collections.Counter(r.barcode for r in s[0]).values()]
+    assert min(per) == 1 and 1 < max(per) <= 5                                            # (1 .. 5 records per barcode)
+    lead, seeds, thr = [1000, 2000, 3000], PR.seeds(SEED, 3), [PR.threshold(t) for t in (0.2, 0.6)]
+    rthr = [PR.threshold(k / float(n_rthr - 1)) for k in range(n_rthr - 1)] + [ONE]
+    want = ZR.counts_from(rows, lead, thr, rthr, seeds)
+    assert want.shape == (3, 3, 2, n_rthr, 4) and want[0].any() and not want[1].any() and want[2].any()
+    for bit3 in (True, False):
+        got, joint, (sets, covers, records) = _device(eng, rows, lead, seeds, thr, rthr, bit3=bit3)
+        assert [len(j[0]) for j in joint] == [210, 0, 33] and all(len(s.members) == 1 for s in sets)
+        listed = devplanes.spike_rpb_counts(eng, lead, covers, records, seeds, thr, rthr, four=bit3)
+        assert listed.shape == (3, 3, 2, n_rthr, 5) and listed[..., 3].any()              # (READS': the input is not empty)
+        assert np.array_equal(got, listed[..., [0, 1, 2, 4]])
+        assert np.array_equal(got, want) and np.array_equal(listed[..., [0, 1, 2, 4]], want)
 
 
 def test_an_snv_only_list_with_the_bytes_of_smc_spike_read_bits(engine0):

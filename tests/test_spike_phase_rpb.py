@@ -132,7 +132,9 @@ def test_the_entry_is_declared_and_exported():
     assert L.smc_abi_version() == 11 and hasattr(L, "smc_spike_phase_rpb_counts")
     assert len(L.smc_spike_phase_rpb_counts.argtypes) == 23 and len(L.smc_spike_indel_rpb_counts.argtypes) == 19
     kernels = open(os.path.join(ROOT, "smcounter_amd", "csrc", "k_spike_rpb.inc")).read()
-    assert len(re.findall(r"void k_spr_phase_counts\(", kernels)) == 1 and "asm" not in kernels
+    # ONE counts kernel body serves the listed variants and the sets
+    assert len(re.findall(r"void k_spr_counts\(", kernels)) == 1 and "k_spr_counts<SMC_RG_MAX_TARGETS, false, true>" in open(
+        os.path.join(ROOT, "smcounter_amd", "csrc", "host_abi.inc")).read() and "asm" not in kernels
 
 
 # ---- the writers with the RPB axis

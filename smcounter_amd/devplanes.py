@@ -316,10 +316,9 @@ def iter_resident_batches(path: str, fasta, loci: Sequence[Tuple[str, str]], par
                 eng.drop_spare_tuned()           # (the block chosen for the 16-bit words is of a size nothing asks for again: back to the runtime)
                 i = first
                 continue
-            lc_all = LC[0] if len(LC) == 1 else np.concatenate(LC)
             uaux[1].free(); uaux[2].free()
             rb = ResidentBatch(planes=planes + [uaux[0]], words=words, n_slots=slots, n_ustart=slots + n_loc + 1,
-                               loci=lc_all, chrom=chroms, pos=poss[0] if len(poss) == 1 else np.concatenate(poss) if poss else np.zeros(0, np.int64),
+                               loci=_all_loci(LC), chrom=chroms, pos=poss[0] if len(poss) == 1 else np.concatenate(poss) if poss else np.zeros(0, np.int64),
                                ref=refs, alleles=tables,
                                n_device_runs=n_dev, n_host_runs=n_host)
             if ds_rules is None:
@@ -335,8 +334,14 @@ def iter_resident_batches(path: str, fasta, loci: Sequence[Tuple[str, str]], par
             close_rules(ds_rules)
 
 
+def _all_loci(LC):
+    """The descriptors of a batch from those of its builds, in order."""
+    return LC[0] if len(LC) == 1 else np.concatenate(LC)
+
+
 class _DsBatch(object):
-    """The device arrays and host parts of one --dsMT rule's batch (iter_resident_batches)."""
+    """The device arrays and host parts of one --dsMT rule's batch (iter_resident_batches), or of the copies of one kept run that a
+    replicate stage calls together (_build_copies)."""
 
     def __init__(self, eng, cap, bits, all_planes):
         from .engine import DevBuf
@@ -350,9 +355,19 @@ class _DsBatch(object):
         for b in [self.words] + self.uaux + [p for p in self.planes if p is not None]:
             b.free()
 
+    def add(self, done):
+        """What build_run answered for a build into these arrays at `slots`: the next one stands behind it."""
+        _, ns, lc, tb = done
+        self.LC.append(lc)
+        self.tables += tb
+        self.slots += ns
+
+    def loci(self) -> np.ndarray:
+        return _all_loci(self.LC)
+
     def batch(self, full) -> ResidentBatch:
         self.uaux[1].free(); self.uaux[2].free()
-        lc = self.LC[0] if len(self.LC) == 1 else np.concatenate(self.LC)
+        lc = self.loci()
         return ResidentBatch(planes=self.planes + [self.uaux[0]], words=self.words, n_slots=self.slots, n_ustart=self.slots + len(lc) + 1,
                              loci=lc, chrom=full.chrom, pos=full.pos, ref=full.ref, alleles=self.tables, n_device_runs=full.n_device_runs)
 
@@ -363,6 +378,62 @@ def _ds_refused(chrom, lo, hi, why, flag="--dsMT"):
 
 def _ds_flag(rules):
     return " / ".join(sorted({r.flag for r in rules}, reverse=True))
+
+
+class _KeptRun(object):
+    """What build_run needs of one build of a decoded run `A`: the arrays in HBM with their counts - the run's own, a spiked copy's
+    (`run`, A, None) or a selection of either (select_run's `sel, counts, d_orig`) - and the three callbacks that take the build's
+    numbering back to the decoder's (`key`, `name`, `idents`: its allele_key, barcode_name and barcode_idents).
+    A kept alignment's index is not the decoder's: with a selection a key is asked for at orig_index of it.  `copy` (a copy
+    smc_spike_indels wrote, or the one a selection was made of): a relocated record's texts come from the copy (copy_allele_key).
+    `by_read` (select_run at level "read"): the selection renumbers the barcodes by first kept appearance, so new id g is old id
+    old_bc()[g] - the old ids of the kept alignments in order, each at its first appearance; a barcode-level selection keeps the ids.
+    idents() is therefore what scattering the decoder's identities of the kept alignments' old ids to their new ids gives
+    (tests/test_host_logic.py pins the two against each other).  orig_index comes down once, when first asked for.
+    -> allele_key(ai, qpos, indel), barcode_name(g), barcode_idents(n): build_run's callbacks; old_bc(), idents()."""
+
+    def __init__(self, run: RunOnDevice, counts, d_orig, A, key, name, idents, copy: RunOnDevice = None, by_read: bool = False):
+        self.run, self.counts, self.A, self.d_orig, self.by_read = run, counts, A, d_orig, by_read
+        self._key = key if copy is None else copy_allele_key(copy, A, key)
+        self._name, self._idents = name, idents
+        self._orig = self._old_bc = None
+        # (what build_run is handed: where nothing is renumbered, the decoder's own - no call in between)
+        self.allele_key = self._key if d_orig is None else self._kept_key
+        self.barcode_name, self.barcode_idents = (self._old_name, lambda n: self.idents()) if by_read else (name, idents)
+
+    def orig_index(self) -> np.ndarray:
+        """The place in the run of every kept alignment."""
+        if self._orig is None:
+            self._orig = self.d_orig.download(np.uint32, self.run.n_aln) if self.run.n_aln else np.zeros(0, np.uint32)
+        return self._orig
+
+    def _kept_key(self, ai, qpos, indel):
+        # (the builder's alignment index counts the KEPT alignments: the decoder's records, and a copy's, are those of the full run)
+        return self._key(int(self.orig_index()[int(ai)]), qpos, indel)
+
+    def old_bc(self) -> np.ndarray:
+        """The decoder's barcode id of every barcode id of this build."""
+        if self._old_bc is None:
+            if self.by_read:
+                old = self.A["aln"]["bc_gid"][self.orig_index()]
+                self._old_bc = old[np.sort(np.unique(old, return_index=True)[1])]
+            else:
+                self._old_bc = np.arange(int(self.A["n_bc"]))
+        return self._old_bc
+
+    def _old_name(self, g):
+        return self._name(int(self.old_bc()[int(g)]))
+
+    def idents(self) -> np.ndarray:
+        """The identity of every barcode id of this build."""
+        ids = self._idents(self.A["n_bc"])
+        return ids[self.old_bc()] if self.by_read else ids
+
+    def free(self):
+        """A selection's own arrays; the run's and a copy's stay their owner's."""
+        if self.d_orig is not None:
+            self.run.free(shared=False)
+            self.d_orig.free()
 
 
 def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_depth, bam, sampler, sampler_seed, n_loc):
@@ -477,45 +548,18 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
                         names = [bam.barcode_name(g) for g in range(int(A["n_bc"]))]
                     mask = np.array([t in rule.kept for t in names], bool)
                 sel, counts, d_orig = select_run(eng, up, A, lo, mask=mask)
-            got = {}
-
-            def orig_index(d_orig=d_orig, kept=sel.n_aln, got=got):
-                if "orig" not in got:
-                    got["orig"] = d_orig.download(np.uint32, kept)
-                return got["orig"]
-
-            def allele_key(ai, qpos, indel, orig_index=orig_index):
-                # (the builder's alignment index counts the KEPT alignments: the decoder's records are those of the full run)
-                return bam.allele_key(int(orig_index()[int(ai)]), qpos, indel)
-            if d_orig is None:
-                # (--spikeAF: every alignment is there; a key beyond the six fixed ones is an insertion's, a deletion's or an odd letter's,
-                # and its site is a base the rewrite leaves alone or turns into a fixed key - the decoder's texts hold)
-                allele_key = bam.allele_key
-                if spiked is not None and spiked.cig is not up.cig:
-                    # (--spikeIndels: a relocated record has another query layout - its texts come from the copy)
-                    allele_key = copy_allele_key(spiked, A, bam.allele_key)
-            elif spiked is not None and spiked.cig is not up.cig:
-                # (--spikeIndelDepth: a cell of such a copy - the kept alignment's index in the copy, then the copy's texts)
-                def allele_key(ai, qpos, indel, orig_index=orig_index, key=copy_allele_key(spiked, A, bam.allele_key)):
-                    return key(int(orig_index()[int(ai)]), qpos, indel)
-            bc_name, bc_idents = bam.barcode_name, bam.barcode_idents
-            if rule.level == "read":
-                # (the read level renumbers the kept barcodes by first kept appearance: the texts the cap samplers need are the decoder's,
-                # by the old id of every new one - the old ids of the kept alignments in order, each at its first appearance)
-                def old_bc(orig_index=orig_index, got=got, bc=A["aln"]["bc_gid"]):
-                    if "old_bc" not in got:
-                        old = bc[orig_index()]
-                        got["old_bc"] = old[np.sort(np.unique(old, return_index=True)[1])]
-                    return got["old_bc"]
-                bc_name = lambda g, old_bc=old_bc: bam.barcode_name(int(old_bc()[int(g)]))
-                bc_idents = lambda n, old_bc=old_bc: bam.barcode_idents(A["n_bc"])[old_bc()]
+            # (--spikeAF: every alignment is there; a key beyond the six fixed ones is an insertion's, a deletion's or an odd letter's, and
+            # its site is a base the rewrite leaves alone or turns into a fixed key - the decoder's texts hold.  --spikeIndels: a relocated
+            # record has another query layout - its texts come from the copy; --spikeIndelDepth: a cell of such a copy - the kept
+            # alignment's index in the copy, then the copy's texts)
+            # (the read level: the texts the cap samplers need are the decoder's, by the old id of every new one)
+            kept = _KeptRun(sel, counts, d_orig, A, bam.allele_key, bam.barcode_name, bam.barcode_idents,
+                            copy=spiked if spiked is not None and spiked.cig is not up.cig else None, by_read=rule.level == "read")
             w = d.words
             done = build_run(counts, L, eng, abi.c_params(rule.params), rule.params, chrom, lo, fasta, run_ref, [w] + d.planes, d.uaux,
-                             d.slots, d.slots + n_loc, cap, max_depth, allele_key, bc_name, sampler=sampler, sampler_seed=sampler_seed,
-                             barcode_idents=bc_idents, uploaded=sel)
-            if d_orig is not None:
-                sel.free(shared=False)
-                d_orig.free()
+                             d.slots, d.slots + n_loc, cap, max_depth, kept.allele_key, kept.barcode_name, sampler=sampler,
+                             sampler_seed=sampler_seed, barcode_idents=kept.barcode_idents, uploaded=sel)
+            kept.free()
             if rule.spike is not None:
                 users[key] -= 1
                 if not users[key] and spiked is not None:          # (behind the last build of its target)
@@ -534,10 +578,8 @@ def _ds_build_run(rules, ds, A, up, eng, chrom, lo, fasta, run_ref, cap, max_dep
         for spiked in spiked_of.values():                          # (a build that ended early: NARROW, or an error)
             if spiked is not None:
                 free_spiked(spiked, up)
-    for d, (nl_k, ns_k, lc, tb) in zip(ds, res):
-        d.LC.append(lc)
-        d.tables += tb
-        d.slots += ns_k
+    for d, done in zip(ds, res):
+        d.add(done)
     return True
 
 
@@ -1610,6 +1652,36 @@ def free_spiked(spiked: RunOnDevice, up: RunOnDevice) -> None:
         spiked.cig.free()
 
 
+def _spike_single_counters(eng, up: RunOnDevice, A, lo: int, spikes: SpikeSet, chrom: str, members, var, ins, idents, seed: int, P, nm, n_indel,
+                           cov, cnt0, four: bool):
+    """The counters the counts calls of the spike family start from, for the variants `members` (indexes into the list `spikes` was
+    made of; `var`, `ins`: af_run_variants' records of them; `cov`, `cnt0`: smc_allele_carriers' cover bits and counters of them on
+    the run `up`).  `single`: one copy with every barcode spiked at every position of the chromosome's list - thr 2^32 - then the
+    `alt` counters on it.  -> (the chromosome's records at that threshold, the index of each in the list, per member the identities
+    of the barcodes that cover it, per member uint32 [covering barcodes, 3] = (reads, alt0, single)).  `four`: a fourth column, what
+    the rewrite changes: an SNV's single-letter reads - all of which then show ALT -, an indel's eligible records
+    (smc_spike_indel_touch)."""
+    from .tools import ds_allele_fraction as af
+    svar, sorder = spikes.chrom_variants(chrom, 0.5)
+    svar["thr"] = 1 << 32
+    spiked, _ = spike_copy(eng, up, A, spikes, chrom, svar, idents, seed, P.mismatchThr, nm, n_indel)
+    try:
+        _, _, cnt_all = allele_carriers_run(eng, spiked, A, lo, var, ins, counts=True)
+    finally:
+        free_spiked(spiked, up)
+    touch = spike_indel_touch(eng, up, A, svar) if four else None
+    at_of = {m: n for n, m in enumerate(sorder)}
+    covers, counters = [], []
+    for r, m in enumerate(members):
+        c = cov[r][:len(idents)]
+        covers.append(idents[c])
+        cols = [cnt0[r, :len(idents), 0][c], cnt0[r, :len(idents), 1][c], cnt_all[r, :len(idents), 1][c]]
+        if four:
+            cols.append(cols[2] if spikes.variants[m].kind == af.SNV else touch[at_of[m], :len(idents)][c])
+        counters.append(np.stack(cols, axis=1).astype(np.uint32))
+    return svar, sorder, covers, counters
+
+
 def copy_allele_key(spiked: RunOnDevice, A, decoder_key):
     """`allele_key` for a copy smc_spike_indels wrote of run `A`: a relocated record's texts come from the copy - smc_bam_allele_key's
     rules (csrc/smc_bam.cpp) over its records and the pairs behind the run's own, downloaded once, when the first such key is asked
@@ -1791,20 +1863,18 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
 
                 def read_selected(run, r):
                     # (the cells' second count: the read selection at r over `run`, then smc_allele_carriers on it -> (N', carriers) per variant)
-                    sel, sel_counts, d_orig = select_run(eng, run, A, lo, d_mask=read_masks[0].data_ptr() + 4 * read_masks[1] * r, level="read")
+                    kept = _KeptRun(*select_run(eng, run, A, lo, d_mask=read_masks[0].data_ptr() + 4 * read_masks[1] * r, level="read"), A=A,
+                                    key=dec.allele_key, name=dec.barcode_name, idents=lambda n: idents, by_read=True)
                     try:
-                        cov_r, car_r, _ = allele_carriers_run(eng, sel, sel_counts, lo, var, ins)
+                        cov_r, car_r, _ = allele_carriers_run(eng, kept.run, kept.counts, lo, var, ins)
                         who = None
                         if psets and rpb is not None:
                             # (--spikePhaseRpb: the bits as identities - a read selection renumbers the kept records' barcode ids by
                             # first kept appearance, so each new id is traced back through the kept records' places in the run)
-                            orig = d_orig.download(np.uint32, sel.n_aln) if sel.n_aln else np.zeros(0, np.uint32)
-                            new = sel.aln.download(np.uint8, 36 * sel.n_aln).view(abi.DEV_ALN_DTYPE)["bc_gid"] if sel.n_aln else orig
-                            of_new = np.zeros(cov_r.shape[1], np.uint64)
-                            of_new[new.astype(np.int64)] = idents[A["aln"]["bc_gid"][orig].astype(np.int64)]
-                            who = [(of_new[cov_r[x]], of_new[car_r[x]]) for x in range(len(group))]
+                            ids = kept.idents()
+                            who = [(ids[cov_r[x][:len(ids)]], ids[car_r[x][:len(ids)]]) for x in range(len(group))]
                     finally:
-                        sel.free(shared=False); d_orig.free()
+                        kept.free()
                     return cov_r.sum(axis=1), car_r.sum(axis=1), who
                 for r in range(len(read_rules or ())):
                     n_r, car_r, who = read_selected(up, r)
@@ -1858,23 +1928,10 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                         rows[t][k] = dict(N=int(cov[r].sum()), V0=int(car[r].sum()), S=int((hit[:cov.shape[1]] & cov[r]).sum()), READS=reads,
                                           V1=int(car1[r].sum()))
                 if want_counters:
-                    # (`single`: one copy with every barcode spiked at every listed position - thr 2^32 - then the `alt` counters)
-                    svar, sorder = spikes.chrom_variants(v0.chrom, 0.5)
-                    svar["thr"] = 1 << 32
-                    spiked, _ = spike_copy(eng, up, A, spikes, v0.chrom, svar, idents, seed, P.mismatchThr, nm, n_indel)
-                    try:
-                        _, _, cnt_all = allele_carriers_run(eng, spiked, A, lo, var, ins, counts=True)
-                    finally:
-                        free_spiked(spiked, up)
-                    touch = spike_indel_touch(eng, up, A, svar) if indel_counters else None
+                    svar, sorder, covers_g, counters_g = _spike_single_counters(eng, up, A, lo, spikes, v0.chrom, group, var, ins, idents, seed, P,
+                                                                                nm, n_indel, cov, cnt0, indel_counters)
                     for r, k in enumerate(group):
-                        c = cov[r][:len(idents)]
-                        covers[k] = idents[c]
-                        cols = [cnt0[r, :len(idents), 0][c], cnt0[r, :len(idents), 1][c], cnt_all[r, :len(idents), 1][c]]
-                        if indel_counters:
-                            # (what the rewrite changes: an SNV's single-letter reads - all of which then show ALT -, an indel's eligible records)
-                            cols.append(cols[2] if variants[k].kind == af.SNV else touch[sorder.index(k), :len(idents)][c])
-                        counters[k] = np.stack(cols, axis=1).astype(np.uint32)
+                        covers[k], counters[k] = covers_g[r], counters_g[r]
                 if rpb is not None:
                     # (a flag byte per record and listed SNV, the first names from the table at threshold 0 - the first mask of a launch
                     # with that one threshold -, then the CSR of every variant's covering records)
@@ -2120,59 +2177,86 @@ def mask_words(n_ids: int) -> int:
     return (int(n_ids) + 31) // 32 + 1
 
 
-def _af_rep_call(eng, run: AfRun, table: AfRepTable, d_masks, n_words, todo, P, fasta, variants, max_depth, sampler, sampler_seed, bits):
-    """The builds of `todo` - indexes of masks in `d_masks`, all of one cell (a target, or with --dsAFDepth a target x fraction: the
-    params `P` are that cell's) - of a kept run appended to one device batch, as
-    _ds_build_run appends successive runs to a _DsBatch, and the batch called with one plan -> (per mask index the listed loci's raw
-    rows, in the order of run.group), or NARROW (a build has no room in 16-bit read words)."""
-    from . import vc
-    A, up, lo, nl, chrom = run.A, run.up, run.lo, run.nl, run.chrom
-    ns_full = int(A["n_slots"])
-    cap = len(todo) * (ns_full + nl) + ns_full + nl + 64
+def _narrow_retry(eng, P, call):
+    """call(bits): with 16-bit read words while the engine builds them and the params' minBQ fits, and when that answers NARROW (a build
+    has no room in them) once more with 32 - as every batch of the file from there on."""
+    out = call(16 if (eng.word_bits == 16 and 0 <= P.minBQ <= 63) else 32)
+    if out == NARROW:
+        eng.word_bits = 32
+        out = call(32)
+    return out
+
+
+def _build_copies(eng, run: AfRun, n_copies: int, kept_runs, P, bits, flag, fasta, max_depth, sampler, sampler_seed):
+    """The builds of a replicate stage's batch: `kept_runs` - an iterable of `n_copies` _KeptRun over the kept run `run`, its selections
+    or its spiked copies, each made when the loop asks for it and freed behind its build - built one behind the other into one
+    _DsBatch with the cell's params `P`, as _ds_build_run appends successive runs to a rule's -> the batch (the caller frees it), or
+    NARROW (a build has no room in 16-bit read words).  BamError naming `flag`: a build the device builder does not take."""
+    lo, nl = run.lo, run.nl
+    ns_full = int(run.A["n_slots"])
+    cap = n_copies * (ns_full + nl) + ns_full + nl + 64
     d = _DsBatch(eng, cap, bits, False)
     cp = abi.c_params(P)
     try:
         n_loc = 0
-        for m in todo:
-            sel, counts, d_orig = select_run(eng, up, A, lo, d_mask=d_masks.data_ptr() + 4 * n_words * m)
-            got = {}
-
-            def allele_key(ai, qpos, indel, d_orig=d_orig, kept=sel.n_aln, got=got):
-                # (the builder's alignment index counts the KEPT alignments: the decoder's records are those of the full run)
-                if "orig" not in got:
-                    got["orig"] = d_orig.download(np.uint32, kept)
-                return run.bam.allele_key(int(got["orig"][int(ai)]), qpos, indel)
+        for kept in kept_runs:
             try:
-                done = build_run(counts, eng.L, eng, cp, P, chrom, lo, fasta, run.run_ref, [d.words] + d.planes, d.uaux, d.slots,
-                                 d.slots + n_loc, cap, max_depth, allele_key, run.bam.barcode_name, sampler=sampler, sampler_seed=sampler_seed,
-                                 barcode_idents=lambda n: run.idents, uploaded=sel)
+                done = build_run(kept.counts, eng.L, eng, cp, P, run.chrom, lo, fasta, run.run_ref, [d.words] + d.planes, d.uaux, d.slots,
+                                 d.slots + n_loc, cap, max_depth, kept.allele_key, kept.barcode_name, sampler=sampler, sampler_seed=sampler_seed,
+                                 barcode_idents=kept.barcode_idents, uploaded=kept.run)
             finally:
-                sel.free(shared=False)
-                d_orig.free()
+                kept.free()
             if done is None:
-                raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "a replicate: the device builder does not take it", "--dsAFReps"))
+                raise bamio.BamError(_ds_refused(run.chrom, lo, lo + nl, "a replicate: the device builder does not take it", flag))
             if done == NARROW:
+                d.free()
                 return NARROW
-            _, ns_k, lc, tb = done
-            d.LC.append(lc)
-            d.tables += tb
-            d.slots += ns_k
+            d.add(done)
             n_loc += nl
-        lc = d.LC[0] if len(d.LC) == 1 else np.concatenate(d.LC)
-        plan = eng.make_plan(lc)
+        return d
+    except BaseException:
+        d.free()
+        raise
+
+
+def _listed_rows(d: _DsBatch, out_rows, run: AfRun, at, n_copies: int, P, fasta):
+    """The raw row strings of the loci at offsets `at` of the run in every one of the `n_copies` builds of batch `d`, whose called rows
+    `out_rows` are -> per copy the listed loci's text, in the order of `at`."""
+    from . import vc
+    lo, nl = run.lo, run.nl
+    idx = np.array([b * nl + a for b in range(n_copies) for a in at], np.int64)
+    view = vc.LocusView([run.chrom] * len(idx), [lo + 1 + a for _ in range(n_copies) for a in at],
+                        [run.run_ref[a] if a < len(run.run_ref) else "" for _ in range(n_copies) for a in at], [d.tables[i] for i in idx.tolist()])
+    text = vc._strings(out_rows[idx].copy(), view, P, fasta)
+    g = len(at)
+    return [list(text[b * g:(b + 1) * g]) for b in range(n_copies)]
+
+
+def _copy_rows(eng, run: AfRun, variants, n_copies: int, kept_runs, P, bits, flag, fasta, max_depth, sampler, sampler_seed):
+    """_build_copies, the batch called with one plan, and of its rows those of the variants of run.group (indexes into `variants`) ->
+    per copy the listed loci's raw rows, in the order of run.group, or NARROW."""
+    d = _build_copies(eng, run, n_copies, kept_runs, P, bits, flag, fasta, max_depth, sampler, sampler_seed)
+    if d == NARROW:
+        return NARROW
+    try:
+        plan = eng.make_plan(d.loci())
         try:
             out_rows = plan.run_devbuf([d.words, d.uaux[0]], P)
         finally:
             plan.close()
-        at = [variants[k].pos - 1 - lo for k in run.group]
-        idx = np.array([b * nl + a for b in range(len(todo)) for a in at], np.int64)
-        view = vc.LocusView([chrom] * len(idx), [lo + 1 + a for _ in todo for a in at], [run.run_ref[a] if a < len(run.run_ref) else "" for _ in todo for a in at],
-                            [d.tables[i] for i in idx.tolist()])
-        text = vc._strings(out_rows[idx].copy(), view, P, fasta)
-        g = len(at)
-        return {m: list(text[b * g:(b + 1) * g]) for b, m in enumerate(todo)}
+        return _listed_rows(d, out_rows, run, [variants[k].pos - 1 - run.lo for k in run.group], n_copies, P, fasta)
     finally:
         d.free()
+
+
+def _af_rep_call(eng, run: AfRun, table: AfRepTable, d_masks, n_words, todo, P, fasta, variants, max_depth, sampler, sampler_seed, bits):
+    """The builds of `todo` - indexes of masks in `d_masks`, all of one cell (a target, or with --dsAFDepth a target x fraction: the
+    params `P` are that cell's) - of a kept run appended to one device batch (_build_copies) and the batch called with one plan ->
+    (per mask index the listed loci's raw rows, in the order of run.group), or NARROW (a build has no room in 16-bit read words)."""
+    kept_runs = (_KeptRun(*select_run(eng, run.up, run.A, run.lo, d_mask=d_masks.data_ptr() + 4 * n_words * m), run.A, run.bam.allele_key,
+                          run.bam.barcode_name, lambda n: run.idents) for m in todo)
+    text = _copy_rows(eng, run, variants, len(todo), kept_runs, P, bits, "--dsAFReps", fasta, max_depth, sampler, sampler_seed)
+    return NARROW if text == NARROW else dict(zip(todo, text))
 
 
 def ds_af_replicates(path: str, fasta, variants, targets, params_list, seed: int, n_reps: int, eng, keep: dict, res, sampler: str = "reference",
@@ -2249,14 +2333,8 @@ def ds_af_replicates(path: str, fasta, variants, targets, params_list, seed: int
                     got = {}
                     for b in range(0, len(todo), room):
                         part = todo[b:b + room]
-                        bits = 16 if (eng.word_bits == 16 and 0 <= cell_params[t].minBQ <= 63) else 32
-                        out = _af_rep_call(eng, run, table, d_masks, n_words, part, cell_params[t], fasta, variants, max_depth, sampler,
-                                           sampler_seed, bits)
-                        if out == NARROW:
-                            eng.word_bits = 32
-                            out = _af_rep_call(eng, run, table, d_masks, n_words, part, cell_params[t], fasta, variants, max_depth, sampler,
-                                               sampler_seed, 32)
-                        got.update(out)
+                        got.update(_narrow_retry(eng, cell_params[t], lambda bits: _af_rep_call(
+                            eng, run, table, d_masks, n_words, part, cell_params[t], fasta, variants, max_depth, sampler, sampler_seed, bits)))
                         times["builds"] += len(part)
                         times["batches"] += 1
                     for j in range(n_reps):
@@ -2715,11 +2793,8 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
     copy is also selected per r by read name (select_run, level "read") and built; a cell's selections share one batch and one plan
     -> (the copies' rows, per cell the same), or NARROW.  With `indel` (--spikeIndelRpb) want_cells holds the cells' (N', V1') per
     reads-per-barcode target, and `read_cells` their "targets" for the message."""
-    from . import vc
-    A, up, lo, nl, chrom = run.A, run.up, run.lo, run.nl, run.chrom
+    A, up, lo, chrom = run.A, run.up, run.lo, run.chrom
     B = len(part_seeds)
-    ns_full = int(A["n_slots"])
-    cap = B * (ns_full + nl) + ns_full + nl + 64
     if indel is None:
         d_aln, d_bq, (sa, sb), stats = spike_run_copies(eng, up, A, svar, run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
         copies = [RunOnDevice(d_aln.view(c * sa), up.cig, d_bq.view(c * sb), up.loc, up.ref, up.n_aln, up.loc_host) for c in range(B)]
@@ -2733,13 +2808,13 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
     flag = (read_cells.get("flag") or ("--spikeIndelRpb" if indel is not None else "--spikeRpb")) if read_cells else \
         "--spikeDepth" if cells else "--spikeReps"
 
-    def check_carriers(c, sel, counts, want, what, read=None, idents_of=None):
+    def check_carriers(c, kept, want, what, read=None):
         """(N, V1) of every variant of the run on copy c (or its selection) by smc_allele_carriers against the counts call's.  With
         indel["bits"] (--spikePhaseRpb) the cover and carrier bits of the sets' members on the selection at `read` are kept as
-        identities - idents_of(): the identity of every barcode id of the selection -, key (variant, copy, read)."""
-        cov, car, _ = allele_carriers_run(eng, sel, counts, lo, af_var, af_ins)
-        if idents_of is not None and indel.get("bits") is not None:
-            ids = idents_of()
+        identities - kept.idents(): the identity of every barcode id of the selection -, key (variant, copy, read)."""
+        cov, car, _ = allele_carriers_run(eng, kept.run, kept.counts, lo, af_var, af_ins)
+        if read is not None and indel.get("bits") is not None:
+            ids = kept.idents()
             for g, k in enumerate(run.group):
                 if k in indel["members"]:
                     indel["bits"][(k, c, read)] = (ids[cov[g][:len(ids)]], ids[car[g][:len(ids)]])
@@ -2750,102 +2825,31 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
                 raise RuntimeError("--spikeIndelReps: seed %d at %s:%d%s: the copy holds (N, V1) = %r, the counts call says %r" %
                                    (int(part_seeds[c]), v.chrom, v.pos, what, mine, tuple(int(x) for x in want[g])))
 
-    def batch_rows(Pb, frac, read=None):
-        """The B copies (`frac` None) or their selections at `frac` - `read` r: by read name at the r-th reads-per-barcode target -, built
-        into one batch and called with one plan at params `Pb`."""
-        d = _DsBatch(eng, cap, bits, False)
-        try:
-            cp = abi.c_params(Pb)
-            n_loc = 0
-            for c in range(B):
-                bc_name, bc_idents = run.bam.barcode_name, lambda n: run.idents
-                if read is not None:
-                    sel, counts, d_orig = select_run(eng, copies[c], A, lo, d_mask=read_cells["masks"][c] + 4 * read_cells["n_words"] * read,
-                                                     level="read")
-                    got = {}
-
-                    def orig_index(d_orig=d_orig, kept=sel.n_aln, got=got):
-                        if "orig" not in got:
-                            got["orig"] = d_orig.download(np.uint32, kept)
-                        return got["orig"]
-
-                    def allele_key(ai, qpos, indel_len, orig_index=orig_index,
-                                   key=run.bam.allele_key if indel is None else copy_allele_key(copies[c], A, run.bam.allele_key)):
-                        # (--spikeIndelRpb: a relocated record's texts come from the copy, by the kept alignment's index in it)
-                        return key(int(orig_index()[int(ai)]), qpos, indel_len)
-
-                    def old_bc(orig_index=orig_index, got=got, bc=A["aln"]["bc_gid"]):
-                        # (the read level renumbers the kept barcodes by first kept appearance: as the main pass maps them back)
-                        if "old_bc" not in got:
-                            old = bc[orig_index()]
-                            got["old_bc"] = old[np.sort(np.unique(old, return_index=True)[1])]
-                        return got["old_bc"]
-                    bc_name = lambda g, old_bc=old_bc: run.bam.barcode_name(int(old_bc()[int(g)]))
-                    bc_idents = lambda n, old_bc=old_bc: run.idents[old_bc()]
-                    if indel is not None:
-                        try:
-                            check_carriers(c, sel, counts, indel["want_cells"][read][c], " x target %g" % read_cells["targets"][read],
-                                           read, lambda old_bc=old_bc: run.idents[old_bc()])
-                        except BaseException:
-                            sel.free(shared=False); d_orig.free()
-                            raise
-                elif frac is None:
-                    # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch)
-                    sel, counts, d_orig, allele_key = copies[c], A, None, run.bam.allele_key
-                    if indel is not None:
-                        allele_key = copy_allele_key(copies[c], A, run.bam.allele_key)
-                        check_carriers(c, sel, counts, indel["want"][c], "")
-                else:
-                    sel, counts, d_orig = select_run(eng, copies[c], A, lo, idents=run.idents, frac=frac, seed=int(part_seeds[c]))
-                    got = {}
-
-                    def allele_key(ai, qpos, indel, d_orig=d_orig, kept=sel.n_aln, got=got):
-                        # (the builder's alignment index counts the KEPT alignments: the decoder's records are those of the full run)
-                        if "orig" not in got:
-                            got["orig"] = d_orig.download(np.uint32, kept)
-                        return run.bam.allele_key(int(got["orig"][int(ai)]), qpos, indel)
-                    if indel is not None:
-                        def allele_key(ai, qpos, indel_len, d_orig=d_orig, kept=sel.n_aln, got=got, key=copy_allele_key(copies[c], A, run.bam.allele_key)):
-                            if "orig" not in got:
-                                got["orig"] = d_orig.download(np.uint32, kept)
-                            return key(int(got["orig"][int(ai)]), qpos, indel_len)
-                        try:
-                            check_carriers(c, sel, counts, indel["want_cells"][cell_at[frac]][c], " x fraction %g" % frac)
-                        except BaseException:
-                            sel.free(shared=False); d_orig.free()
-                            raise
+    def kept_copies(frac, read):
+        """The B copies (`frac` None) or their selections at `frac` - `read` r: by read name at the r-th reads-per-barcode target -, with
+        `indel` each checked against the counts call's (N, V1) before it is handed on."""
+        for c in range(B):
+            if read is not None:
+                picked = select_run(eng, copies[c], A, lo, d_mask=read_cells["masks"][c] + 4 * read_cells["n_words"] * read, level="read")
+                cell, what = read, " x target %g" % read_cells["targets"][read]
+            elif frac is None:
+                picked, cell, what = (copies[c], A, None), None, ""
+            else:
+                picked = select_run(eng, copies[c], A, lo, idents=run.idents, frac=frac, seed=int(part_seeds[c]))
+                cell, what = cell_at[frac], " x fraction %g" % frac
+            kept = _KeptRun(*picked, A, run.bam.allele_key, run.bam.barcode_name, lambda n: run.idents,
+                            copy=copies[c] if indel is not None else None, by_read=read is not None)
+            if indel is not None:
                 try:
-                    done = build_run(counts, eng.L, eng, cp, Pb, chrom, lo, fasta, run.run_ref, [d.words] + d.planes, d.uaux, d.slots,
-                                     d.slots + n_loc, cap, max_depth, allele_key, bc_name, sampler=sampler,
-                                     sampler_seed=sampler_seed, barcode_idents=bc_idents, uploaded=sel)
-                finally:
-                    if d_orig is not None:
-                        sel.free(shared=False)
-                        d_orig.free()
-                if done is None:
-                    raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "a replicate: the device builder does not take it", flag))
-                if done == NARROW:
-                    return NARROW
-                _, ns_k, lc, tb = done
-                d.LC.append(lc)
-                d.tables += tb
-                d.slots += ns_k
-                n_loc += nl
-            lc = d.LC[0] if len(d.LC) == 1 else np.concatenate(d.LC)
-            plan = eng.make_plan(lc)
-            try:
-                out_rows = plan.run_devbuf([d.words, d.uaux[0]], Pb)
-            finally:
-                plan.close()
-            at = [variants[k].pos - 1 - lo for k in run.group]
-            idx = np.array([b * nl + a for b in range(B) for a in at], np.int64)
-            view = vc.LocusView([chrom] * len(idx), [lo + 1 + a for _ in range(B) for a in at],
-                                [run.run_ref[a] if a < len(run.run_ref) else "" for _ in range(B) for a in at], [d.tables[i] for i in idx.tolist()])
-            text = vc._strings(out_rows[idx].copy(), view, Pb, fasta)
-            g = len(at)
-            return [list(text[b * g:(b + 1) * g]) for b in range(B)]
-        finally:
-            d.free()
+                    check_carriers(c, kept, indel["want"][c] if cell is None else indel["want_cells"][cell][c], what, read)
+                except BaseException:
+                    kept.free()
+                    raise
+            yield kept
+
+    def batch_rows(Pb, frac, read=None):
+        """kept_copies built into one batch and called with one plan at params `Pb`."""
+        return _copy_rows(eng, run, variants, B, kept_copies(frac, read), Pb, bits, flag, fasta, max_depth, sampler, sampler_seed)
     cell_at = {frac: f for f, (frac, _) in enumerate(cells)}
     try:
         for c in range(B):
@@ -3024,7 +3028,6 @@ def _spike_rep_targets(*, eng, run, svar, var_at, seeds, thr, counts, depth_coun
         for b in range(0, n_reps, room):
             js = list(range(b, min(n_reps, b + room)))
             want = [[int(counts[k, j, t, 1]) for k in run.group] for j in js]
-            bits = 16 if (eng.word_bits == 16 and 0 <= P.minBQ <= 63) else 32
             args = (eng, run, svar, var_at, [seeds[j] for j in js], thr[t], want, P, fasta, variants, max_depth, sampler, sampler_seed)
             indel = None
             if four:
@@ -3037,11 +3040,10 @@ def _spike_rep_targets(*, eng, run, svar, var_at, seeds, thr, counts, depth_coun
             if rpb is not None:
                 read_cells = dict(params=rpb["params"][t * F:(t + 1) * F], masks=[seed_masks[j][0].data_ptr() for j in js],
                                   n_words=seed_masks[js[0]][1], targets=list(rpb["targets"]), flag=rpb.get("flag"))
-            out = _spike_rep_call(*args, bits, cells, indel, read_cells)
-            if out == NARROW:
-                eng.word_bits = 32
-                out = _spike_rep_call(*args, 32, cells, indel, read_cells)
-                times["rewrites"] += 1
+            def call(bits):
+                times["rewrites"] += 1                                 # (a call that answers NARROW has spiked its copies too)
+                return _spike_rep_call(*args, bits, cells, indel, read_cells)
+            out = _narrow_retry(eng, P, call)
             full, of_cell = out if (cells or read_cells) else (out, [])
             if joint_bits is not None:
                 for (k, c, r), val in indel["bits"].items():
@@ -3050,7 +3052,6 @@ def _spike_rep_targets(*, eng, run, svar, var_at, seeds, thr, counts, depth_coun
                 for j, text in zip(js, part):
                     for k, line in zip(run.group, text):
                         rows[(k, c, j)] = line
-            times["rewrites"] += 1
             times["builds"] += len(js) * (1 + F)
             times["batches"] += 1 + F
 
@@ -3103,8 +3104,6 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
     from . import vc
     A, up, lo, nl, chrom = run.A, run.up, run.lo, run.nl, run.chrom
     B, G = len(part_seeds), len(run.group)
-    ns_full = int(A["n_slots"])
-    cap = B * (ns_full + nl) + ns_full + nl + 64
     d_aln, d_bq, (sa, sb), stats = spike_run_copies(eng, up, A, svar, run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
     d = d_rows = plan = None
     try:
@@ -3114,25 +3113,14 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
                     v = variants[k]
                     raise RuntimeError("--spikeScan: seed %d at %s:%d: the rewrite touched %d records, the counts call says %d" %
                                        (int(part_seeds[c]), v.chrom, v.pos, int(stats[c, var_at[g], 0]), int(want_reads[c][g])))
-        d = _DsBatch(eng, cap, bits, False)
-        cp = abi.c_params(P)
-        n_loc = 0
-        for c in range(B):
-            copy = RunOnDevice(d_aln.view(c * sa), up.cig, d_bq.view(c * sb), up.loc, up.ref, up.n_aln, up.loc_host)
-            # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch)
-            done = build_run(A, eng.L, eng, cp, P, chrom, lo, fasta, run.run_ref, [d.words] + d.planes, d.uaux, d.slots, d.slots + n_loc, cap,
-                             max_depth, run.bam.allele_key, run.bam.barcode_name, sampler=sampler, sampler_seed=sampler_seed,
-                             barcode_idents=lambda n: run.idents, uploaded=copy)
-            if done is None:
-                raise bamio.BamError(_ds_refused(chrom, lo, lo + nl, "a replicate: the device builder does not take it", "--spikeScan"))
-            if done == NARROW:
-                return NARROW
-            _, ns_k, lc, tb = done
-            d.LC.append(lc)
-            d.tables += tb
-            d.slots += ns_k
-            n_loc += nl
-        plan = eng.make_plan(d.LC[0] if len(d.LC) == 1 else np.concatenate(d.LC))
+        # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch)
+        copies = (_KeptRun(RunOnDevice(d_aln.view(c * sa), up.cig, d_bq.view(c * sb), up.loc, up.ref, up.n_aln, up.loc_host), A, None, A,
+                           run.bam.allele_key, run.bam.barcode_name, lambda n: run.idents) for c in range(B))
+        built = _build_copies(eng, run, B, copies, P, bits, "--spikeScan", fasta, max_depth, sampler, sampler_seed)
+        if built == NARROW:
+            return NARROW
+        d = built
+        plan = eng.make_plan(d.loci())
         d_rows = plan.run_into_devbuf([d.words, d.uaux[0]], P)
         rec, todo = scan_detect(eng, d_rows, B, nl, listed, threshold)       # (its downloads wait for the plan's kernels)
         verdict = (rec["mt_verdict"] >> 30).astype(np.int64)
@@ -3253,19 +3241,9 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
     group = run.group
     var, ins = af_run_variants([variants[k] for k in group], chrom, lo, fasta)
     cov, car, cnt0 = allele_carriers_run(eng, up, A, lo, var, ins, counts=True)
-    # (`single`: one copy with every barcode spiked at every position of the pass's list - thr 2^32 - then the `alt` counters)
-    svar, sorder = spikes.chrom_variants(chrom, 0.5)
-    svar["thr"] = 1 << 32
-    spiked, _ = spike_copy(eng, up, A, spikes, chrom, svar, idents, seeds[0], P.mismatchThr, nm, n_indel)
-    try:
-        _, _, cnt_all = allele_carriers_run(eng, spiked, A, lo, var, ins, counts=True)
-    finally:
-        free_spiked(spiked, up)
-    covers, counters = [], []
+    svar, sorder, covers, counters = _spike_single_counters(eng, up, A, lo, spikes, chrom, members, var, ins, idents, seeds[0], P, nm, n_indel,
+                                                            cov, cnt0, False)
     for g, k in enumerate(group):
-        c = cov[g][:len(idents)]
-        covers.append(idents[c])
-        counters.append(np.stack([cnt0[g, :len(idents), 0][c], cnt0[g, :len(idents), 1][c], cnt_all[g, :len(idents), 1][c]], axis=1).astype(np.uint32))
         base[k] = (int(cov[g].sum()), int(car[g].sum()))
     mine = spike_rep_counts(eng, [spikes.lead_pos[m] for m in members], covers, counters, seeds, thr)       # [G, R, T, 3]
     at_of = {m: n for n, m in enumerate(sorder)}
@@ -3279,14 +3257,9 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
         for b in range(0, R, room):
             js = list(range(b, min(R, b + room)))
             want = [[int(mine[g, j, t, 1]) for g in range(len(group))] for j in js]
-            bits = 16 if (eng.word_bits == 16 and 0 <= P.minBQ <= 63) else 32
             args = (eng, run, svar, var_at, listed, [seeds[j] for j in js], thr[t], want, P, fasta, variants, max_depth, sampler, sampler_seed)
             tail = (threshold, repeats, js.index(0) if 0 in js else None)
-            out = _scan_call(*args, bits, *tail)
-            if out == NARROW:
-                eng.word_bits = 32
-                out = _scan_call(*args, 32, *tail)
-            yes, n_host = out
+            yes, n_host = _narrow_retry(eng, P, lambda bits: _scan_call(*args, bits, *tail))
             for c, j in enumerate(js):
                 for g, k in enumerate(group):
                     called[k, t, j] = yes[c, g]

@@ -221,6 +221,42 @@ def test_refusals_launch_nothing(engine0):
         b.free()
 
 
+def test_replicate_stage_builds_again_with_32_bit_words(engine0, tmp_path):
+    """The hand-made BAM with one base quality of 70 under the first listed position: the 16-bit builder has no room for it, so the
+    stage's first call answers NARROW, the engine goes over to 32-bit words and the call is made again - one rewrite more than a
+    stage that starts at 32 bits, and the same rows."""
+    from smcounter_amd import fasta
+    from smcounter_amd.tools import ds_allele_fraction as af
+    bam, fa, loci, P, variants = SR.make_case(str(tmp_path))
+    variants = [af.Variant(v.chrom, v.pos, v.ref, v.alt, v.alt, af.SNV) for v in variants]
+    recs = [dict(tid=0, pos=pos, qname=qname, flag=flag, mapq=60, cigar=list(cigar), seq=seq, qual=list(qual), nm=nm if has_nm else None)
+            for qname, flag, pos, cigar, seq, qual, nm, has_nm in SR.file_records(bam)]
+    first = next(r for r in recs if r["qname"].startswith("mfirst"))          # (P1 is its first aligned base)
+    assert first["pos"] == SR.P1 - 1 and first["cigar"][0] == (SR.M, 30) and max(first["qual"]) <= 63
+    first["qual"][0] = 70
+    bam = str(tmp_path / "q70.bam")
+    bamio.write_bam(bam, [(SR.CASE_CHROM, 400)], recs, block=8000)
+    bamio.write_bai(bam)
+    assert 0 <= P.minBQ <= 63
+
+    def stage(bits):
+        keep = {}
+        devplanes.spike_rules(bam, fasta.FastaFile(fa), variants, [0.5], [P], SEED, engine0, keep=keep)
+        engine0.word_bits = bits
+        out = devplanes.spike_replicates(bam, fasta.FastaFile(fa), variants, [0.5], [P], SEED, 2, engine0, keep)
+        return out, engine0.word_bits
+    old = engine0.word_bits
+    try:
+        narrow, bits_after = stage(16)
+        wide, _ = stage(32)
+    finally:
+        engine0.word_bits = old
+    assert bits_after == 32
+    assert len(narrow["rows"]) == len(variants) * 2 and narrow["rows"] == wide["rows"]
+    assert narrow["times"]["rewrites"] == wide["times"]["rewrites"] + 1 == 2
+    assert narrow["times"]["builds"] == wide["times"]["builds"] and narrow["times"]["batches"] == wide["times"]["batches"]
+
+
 def _lines(path):
     return [l.split("\t") for l in open(path).read().splitlines()]
 

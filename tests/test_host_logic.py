@@ -713,3 +713,81 @@ def test_16_bit_builder_refuses_a_min_bq_it_has_no_room_for():
     rc = L.smc_build_planes_w16(None, ctypes.byref(cp), None, 0, 0, dummy, None, None, None, None, None, 0, None, None)
     assert rc != 0 and b"minBQ 64" in L.smc_last_error()
     assert L.smc_build_planes_w16(None, ctypes.byref(cp), None, 0, 0, None, None, None, None, None, None, 0, None, None) != 0     # no words array
+
+
+class _CountedBuf(object):
+    """A stand-in for a device buffer: what download hands back, and how often it and free were called."""
+
+    def __init__(self, data=None):
+        self.data, self.downloads, self.freed = data, 0, 0
+
+    def download(self, dtype, count, offset_bytes=0):
+        self.downloads += 1
+        return np.asarray(self.data, dtype)[:count].copy()
+
+    def free(self):
+        self.freed += 1
+
+
+def _kept_run_case(orig, by_read, copy=None):
+    """Eight alignments over three barcodes, `orig` the places of the kept ones -> (the adapter, its buffers, the keys the decoder was
+    asked for, A, the decoder's identities)."""
+    from smcounter_amd import devplanes
+    A = dict(aln=np.zeros(8, abi.DEV_ALN_DTYPE), n_bc=3, bq=np.zeros(2 * 64, np.uint8))
+    A["aln"]["bc_gid"] = [0, 1, 2, 0, 1, 2, 2, 1]
+    idents = np.array([0xA0, 0xB1, 0xC2], np.uint64)
+    asked = []
+
+    def key(ai, qpos, indel):
+        asked.append((ai, qpos, indel))
+        return "K%d" % ai
+    bufs = dict(aln=_CountedBuf(), cig=_CountedBuf(), bq=_CountedBuf(), loc=_CountedBuf(), ref=_CountedBuf(),
+                orig=_CountedBuf(np.array(orig, np.uint32)))
+    sel = devplanes.RunOnDevice(bufs["aln"], bufs["cig"], bufs["bq"], bufs["loc"], bufs["ref"], len(orig))
+    kept = devplanes._KeptRun(sel, dict(nl=1), bufs["orig"], A, key, lambda g: "name%d" % g, lambda n: idents[:n], copy=copy, by_read=by_read)
+    return kept, bufs, asked, A, idents
+
+
+def test_kept_run_maps_a_selections_numbering_back_to_the_decoders():
+    """devplanes._KeptRun with stand-in buffers: orig_index comes down once and only when asked for; a key is asked for at the original
+    index; a read-level selection's barcode ids are the old ones by first kept appearance - and idents() is what the scatter of
+    spike_rules' second count (written out here as it stood) gives; a barcode-level selection keeps the ids; free() frees what the
+    selection owns."""
+    from smcounter_amd import devplanes
+    # read level: the first kept alignment belongs to the highest old barcode id - all three kept, then only two
+    for orig, new, old_bc in (([2, 3, 4, 7], [0, 1, 2, 2], [2, 0, 1]), ([5, 6, 0], [0, 0, 1], [2, 0])):
+        kept, bufs, asked, A, idents = _kept_run_case(orig, True)
+        assert bufs["orig"].downloads == 0                                            # nothing asked for, nothing copied
+        assert [kept.allele_key(i, 7 + i, -i) for i in range(len(orig))] == ["K%d" % o for o in orig]
+        assert asked == [(o, 7 + i, -i) for i, o in enumerate(orig)] and all(type(a[0]) is int for a in asked)
+        assert kept.old_bc().tolist() == old_bc
+        assert [kept.barcode_name(g) for g in range(len(old_bc))] == ["name%d" % o for o in old_bc]
+        assert kept.barcode_name(np.uint32(0)) == "name2"
+        assert kept.barcode_idents(3).tolist() == idents[old_bc].tolist() == kept.idents().tolist()
+        assert bufs["orig"].downloads == 1                                            # ... however many were asked for
+        # the parent's scatter: every new id gets the identity of the old id of a kept alignment that carries it
+        orig_a, new_a = np.array(orig, np.uint32), np.array(new, np.uint32)
+        of_new = np.zeros(A["n_bc"], np.uint64)
+        of_new[new_a.astype(np.int64)] = idents[A["aln"]["bc_gid"][orig_a].astype(np.int64)]
+        n = len(kept.idents())
+        assert n == len(old_bc) and of_new[:n].tolist() == kept.idents().tolist() and not of_new[n:].any()
+        kept.free()
+        assert [bufs[x].freed for x in ("aln", "loc", "orig", "cig", "bq", "ref")] == [1, 1, 1, 0, 0, 0]
+    # barcode level: the same kept alignments, the decoder's ids
+    kept, bufs, asked, A, idents = _kept_run_case([2, 3, 4, 7], False)
+    assert kept.old_bc().tolist() == [0, 1, 2] and kept.barcode_name(2) == "name2"
+    assert kept.barcode_idents(3).tolist() == idents.tolist() == kept.idents().tolist()
+    assert bufs["orig"].downloads == 0
+    assert kept.allele_key(1, 0, 0) == "K3" and kept.allele_key(3, 0, 0) == "K7" and bufs["orig"].downloads == 1
+    # no selection (the run itself, or a spiked copy): the decoder's index, nothing to copy and nothing to free
+    kept, bufs, asked, A, idents = _kept_run_case([], False)
+    kept = devplanes._KeptRun(kept.run, A, None, A, lambda ai, q, i: "K%d" % ai, lambda g: "name%d" % g, lambda n: idents[:n])
+    assert kept.allele_key(5, 0, 0) == "K5" and kept.barcode_name(1) == "name1" and kept.idents().tolist() == idents.tolist()
+    kept.free()
+    assert not any(b.freed or b.downloads for b in bufs.values())
+    # a selection of an indel copy: the copy's key, at the kept alignment's index in the copy (a record that was not relocated - its
+    # pairs stand in the run's own pool - keeps the decoder's answer)
+    copy = devplanes.RunOnDevice(_CountedBuf(np.zeros(8, abi.DEV_ALN_DTYPE)), None, _CountedBuf(), None, None, 8)
+    kept, bufs, asked, A, idents = _kept_run_case([6, 1], False, copy=copy)
+    assert kept.allele_key(0, 4, 2) == "K6" and kept.allele_key(1, 4, 2) == "K1" and asked == [(6, 4, 2), (1, 4, 2)]
+    assert copy.aln.downloads == 1 and copy.bq.downloads == 0 and bufs["orig"].downloads == 1

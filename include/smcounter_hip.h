@@ -916,6 +916,40 @@ typedef struct smc_scan_verdict {      /* 16 bytes */
 int smc_scan_detect(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64_t n_loci, const smc_scan_locus* d_listed,
                     const smc_scan_locus* listed_host, int32_t n_listed, double thr, smc_scan_verdict* d_out, uint32_t* d_host_list,
                     uint32_t* d_n_host, void* stream);
+/* (ABI 11, additive: one entry more, the version number unchanged) --spikeScanIndel: smc_scan_detect for lists whose members are
+ * allele KEYS.  An insertion's or a deletion's allele id is numbered per locus and per build (6 and up, in the order the builder met
+ * the keys), so the id to compare cand[0].allele with is resolved per copy from that build's extras list.
+ *   d_rows, n_copies, n_loci   as smc_scan_detect takes them.
+ *   d_var / var_host[n_listed] the listed variants as smc_allele_carriers takes them, `locus` ascending (equal loci may follow one
+ *                              another); d_ins[n_ins]: the pool of inserted letters.
+ *   d_aln, d_cig, d_bq         the copies' records, CIGAR words and (letter, quality) pairs: copy c's array at base + c * its BYTE
+ *                              stride, as smc_spike_indels_reps lays them out; a stride of 0: every copy shares the array.  n_aln
+ *                              records per copy; cap_pairs: the pairs of a copy's pool that may be read.  (The CIGAR words are not
+ *                              read: an extras entry holds the query position and the indel the builder's walk resolved.)
+ *   d_x, x_stride              the builds' extras lists, copy c's at d_x + c * x_stride WORDS: entries of five words (locus, allele id,
+ *                              alignment, query position, indel) as smc_build_planes leaves them; d_xcount[c * xcount_stride]: copy
+ *                              c's number of entries, clipped to xcap in the kernel.
+ *   d_alt_id[c * n_listed + g] out: an SNV's fixed id (A, T, G, C = 0 .. 3); for an insertion / a deletion the allele id of the one
+ *                              entry of copy c at that locus whose alignment shows the key by smc_allele_carriers' rule on the copy's
+ *                              own record - the anchor letter the variant's; a deletion: indel == -len; an insertion: the inserted
+ *                              letters, clamped at the read's end, the pool's -; SMC_SCAN_ID_NONE when no entry does (and for
+ *                              SMC_AF_NONE); SMC_SCAN_ID_HOST when two entries do, or when an entry of the locus names a record
+ *                              that cannot be read (an alignment beyond n_aln, a query position beyond l_seq, pairs beyond cap_pairs).
+ *   d_out, d_host_list, d_n_host  exactly smc_scan_detect's, by its rule with cand[0].allele == d_alt_id[..] and the same lo / hi:
+ *                              SMC_SCAN_ID_NONE gives SMC_SCAN_NOT on a row with status 0 that is not bi-allelic, SMC_SCAN_ID_HOST
+ *                              gives SMC_SCAN_HOST.
+ * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched: what smc_scan_detect refuses; a `locus` that is not below
+ * n_loci or stands behind a larger one; a kind beyond SMC_AF_NONE; an SNV whose letter is not A, C, G or T; an insertion / a deletion
+ * with a len of 0 or above SMC_AF_MAX_INS; inserted letters beyond the pool; a byte stride that does not keep its array aligned (a
+ * multiple of 4 for records and CIGAR words, of 2 for pairs) or is negative. */
+#define SMC_SCAN_ID_NONE 0xFFFFFFFFu
+#define SMC_SCAN_ID_HOST 0xFFFFFFFEu
+int smc_scan_detect_keys(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64_t n_loci, const smc_af_variant* d_var,
+                         const smc_af_variant* var_host, int32_t n_listed, const uint8_t* d_ins, int64_t n_ins, const smc_dev_aln* d_aln,
+                         int64_t aln_stride, const uint32_t* d_cig, int64_t cig_stride, const uint8_t* d_bq, int64_t bq_stride, int64_t n_aln,
+                         int64_t cap_pairs, const uint32_t* d_x, int64_t x_stride, const uint32_t* d_xcount, int64_t xcount_stride,
+                         int64_t xcap, double thr, uint32_t* d_alt_id, smc_scan_verdict* d_out, uint32_t* d_host_list, uint32_t* d_n_host,
+                         void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

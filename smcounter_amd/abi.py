@@ -59,6 +59,8 @@ SCAN_LOCUS_DTYPE = np.dtype([("offset", "<u4"), ("alt", "<u4")])
 SCAN_VERDICT_DTYPE = np.dtype([("pi", "<f8"), ("vmt", "<i4"), ("mt_verdict", "<u4")])
 assert SCAN_LOCUS_DTYPE.itemsize == 8 and SCAN_VERDICT_DTYPE.itemsize == 16
 SCAN_NOT, SCAN_CALLED, SCAN_HOST, SCAN_MT_MASK = 0, 1, 2, 0x3FFFFFFF
+# (smc_scan_detect_keys) what d_alt_id holds where no extras entry of the copy shows the listed key / where the host has to look
+SCAN_ID_NONE, SCAN_ID_HOST = 0xFFFFFFFF, 0xFFFFFFFE
 
 
 def c_params(p: VcParams) -> SmcParams:

@@ -276,6 +276,16 @@ def build_parser() -> argparse.ArgumentParser:
                                                            "between a pass's spike-ins")
     p.add_argument("--spikeScanAlt", default=None, help="the ALT of --spikeScan: transition (default: A>G, G>A, C>T, T>C), transversion "
                                                         "(A>C, C>A, G>T, T>G) or complement (A>T, T>A, C>G, G>C)")
+    p.add_argument("--spikeScanIndel", default=None,
+                   help="--spikeScan with an indel instead of the SNV: del<d> plants the deletion of the d letters behind every locus P "
+                        "(REF genome[P .. P+d], ALT genome[P]), dup<s> the tandem duplication of the next s (REF genome[P], ALT genome[P] + "
+                        "genome[P+1 .. P+s]); d, s in 1 .. 255.  A locus is skipped when a letter of P .. P+d (P .. P+s) is not A, C, G or T "
+                        "or lies past the chromosome's end.  A pass is by definition the run --spikeAF <targets> --spikeVariants <the "
+                        "pass's list> --spikeIndelReps R --dsSeed s (tools/spike_scan_lists.py --indel writes the lists); the footprints "
+                        "of a pass must be disjoint: --spikeScanStride >= d + 2 for a deletion, >= 2 for a duplication.  The allele id "
+                        "of the planted key is resolved per replicate on the GPU from the build's own list of allele keys "
+                        "(smc_scan_detect_keys); the files are --spikeScan's, REF and ALT the indel's texts at its anchor.  Needs "
+                        "--spikeScan; not with --spikeScanAlt")
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -747,7 +757,7 @@ def _spike_scan(args, plan, ref, eng, params):
     try:
         out = devplanes.spike_scan(args.bamFile, ref, scan["variants"], scan["passes"], scan["targets"], params, int(args.dsSeed), scan["reps"],
                                    eng, threshold, repeats, sampler=getattr(args, "sampler", "reference"),
-                                   sampler_seed=getattr(args, "samplerSeed", 0))
+                                   sampler_seed=getattr(args, "samplerSeed", 0), indel="indel" in scan)
     except (ValueError, bamio.BamError) as e:
         raise SystemExit(str(e))
     for (k, _), st in zip(scan["passes"], out["passes"]):
@@ -1014,12 +1024,15 @@ def _make_rules(args, plan, loc_list):
         from .tools import ds_allele_fraction as af, spike_scan_lists as lists
         try:
             af.unique_idents(bamio.placed_barcodes(args.bamFile), args.bamFile)
-            variants, skipped = lists.scan_variants(loc_list, fasta.FastaFile(args.refGenome), plan.scan["alt"])
+            if "indel" in plan.scan:
+                variants, skipped = lists.scan_indels(loc_list, fasta.FastaFile(args.refGenome), plan.scan["indel"])
+            else:
+                variants, skipped = lists.scan_variants(loc_list, fasta.FastaFile(args.refGenome), plan.scan["alt"])
             passes = lists.scan_passes(variants, plan.scan["stride"])
         except (ValueError, OSError, bamio.BamError) as e:
             raise SystemExit(str(e))
         for k, members in passes:
-            # (the rewrite takes a pass's whole list of a chromosome: smc_spike_alleles_reps' limit)
+            # (the rewrite takes a pass's whole list of a chromosome: smc_spike_alleles_reps' limit, and smc_spike_indels_reps')
             chrom, n = collections.Counter(variants[i].chrom for i in members).most_common(1)[0]
             if n > SCAN_MAX_PASS_VARIANTS:
                 raise SystemExit("--spikeScan: pass %d holds %d loci of %s, at most %d (a larger --spikeScanStride makes more and smaller "
@@ -1031,9 +1044,15 @@ def _make_rules(args, plan, loc_list):
                 seen.add((c, int(q)))
                 loci.append((c, int(q), index.get((c, int(q)))))
         plan.scan.update(variants=variants, skipped=skipped, passes=passes, loci=loci, loc_list=loc_list)
-        print("--spikeScan: %d loci in %d passes of stride %d (%s), %d skipped for a letter that is not A, C, G or T; %d replicates x %d "
-              "targets" % (len(variants), len(passes), plan.scan["stride"], plan.scan["alt"], len(skipped), plan.scan["reps"],
-                           len(plan.scan["targets"])))
+        if "indel" in plan.scan:
+            print("--spikeScan: %d loci in %d passes of stride %d (--spikeScanIndel %s%d), %d skipped for a letter inside the footprint "
+                  "that is not A, C, G or T or lies past the chromosome's end; %d replicates x %d targets" %
+                  ((len(variants), len(passes), plan.scan["stride"]) + plan.scan["indel"] + (len(skipped), plan.scan["reps"],
+                                                                                              len(plan.scan["targets"]))))
+        else:
+            print("--spikeScan: %d loci in %d passes of stride %d (%s), %d skipped for a letter that is not A, C, G or T; %d replicates x %d "
+                  "targets" % (len(variants), len(passes), plan.scan["stride"], plan.scan["alt"], len(skipped), plan.scan["reps"],
+                               len(plan.scan["targets"])))
 
 
 def _gather_ranks(args, params, loc_list, rank, local_rank, world):

@@ -1580,6 +1580,74 @@ int smc_scan_detect(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64
     return SMC_OK;
 }
 
+// (--spikeScanIndel) smc_scan_detect for lists whose members are allele keys: the same checks, and those of the listed records, of the
+// strides and of the pool, on the host copies before anything is enqueued; then the cursor zeroed and three launches (none for an
+// empty list or no copy)
+int smc_scan_detect_keys(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64_t n_loci, const smc_af_variant* d_var,
+                         const smc_af_variant* var_host, int32_t n_listed, const uint8_t* d_ins, int64_t n_ins, const smc_dev_aln* d_aln,
+                         int64_t aln_stride, const uint32_t* d_cig, int64_t cig_stride, const uint8_t* d_bq, int64_t bq_stride, int64_t n_aln,
+                         int64_t cap_pairs, const uint32_t* d_x, int64_t x_stride, const uint32_t* d_xcount, int64_t xcount_stride,
+                         int64_t xcap, double thr, uint32_t* d_alt_id, smc_scan_verdict* d_out, uint32_t* d_host_list, uint32_t* d_n_host,
+                         void* stream) {
+    const std::string who = "smc_scan_detect_keys";
+    if (!ctx || n_copies < 0 || n_loci < 0 || n_listed < 0 || n_ins < 0 || n_aln < 0 || cap_pairs < 0 || xcap < 0 || !d_n_host)
+        return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_listed && !var_host) return fail(SMC_E_ARG, who + ": NULL argument");
+    if (!std::isfinite(thr)) return fail(SMC_E_INPUT, who + ": a threshold that is not finite");
+    if (n_copies > 65535) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies, at most 65535");
+    if ((int64_t)n_copies * (int64_t)n_listed >= (1ll << 31) || (int64_t)n_copies * n_loci >= (1ll << 31))
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies of " + std::to_string(n_loci) + " loci, " +
+                                 std::to_string(n_listed) + " listed: 2^31 records or rows, or more");
+    if (n_aln >= (int64_t)0xFFFFFF00 || xcap >= (1ll << 31)) return fail(SMC_E_INPUT, who + ": run too large");
+    // (a byte stride keeps its array aligned: records and CIGAR words 4 bytes, pairs 2; 0: the copies share the array)
+    if (aln_stride < 0 || aln_stride % 4 || cig_stride < 0 || cig_stride % 4 || bq_stride < 0 || bq_stride % 2 || x_stride < 0 || xcount_stride < 0)
+        return fail(SMC_E_INPUT, who + ": strides of " + std::to_string(aln_stride) + " / " + std::to_string(cig_stride) + " / " +
+                                 std::to_string(bq_stride) + " bytes: multiples of 4 / 4 / 2 expected, none negative");
+    bool keys = false;
+    for (int32_t g = 0; g < n_listed; ++g) {
+        const smc_af_variant& V = var_host[g];
+        const std::string w = who + ": listed variant " + std::to_string(g);
+        if ((int64_t)V.locus >= n_loci) return fail(SMC_E_INPUT, w + " names locus " + std::to_string(V.locus) + " of " + std::to_string(n_loci));
+        if (g && V.locus < var_host[g - 1].locus) return fail(SMC_E_INPUT, w + ": locus " + std::to_string(V.locus) + " behind " +
+                                                                           std::to_string(var_host[g - 1].locus) + ", ascending expected");
+        if (V.kind > SMC_AF_NONE) return fail(SMC_E_INPUT, w + " has kind " + std::to_string(V.kind));
+        if (V.kind == SMC_AF_SNV && V.letter != 'A' && V.letter != 'T' && V.letter != 'G' && V.letter != 'C')
+            return fail(SMC_E_INPUT, w + ": an SNV to letter " + std::to_string(V.letter) + ", one of A, C, G, T expected");
+        if (V.kind == SMC_AF_INS || V.kind == SMC_AF_DEL) {
+            keys = true;
+            if (V.len < 1 || V.len > SMC_AF_MAX_INS)
+                return fail(SMC_E_INPUT, w + ": a length of " + std::to_string(V.len) + ", 1 .. " + std::to_string(SMC_AF_MAX_INS) + " expected");
+            if (V.kind == SMC_AF_INS && ((int64_t)V.ins_off + V.len > n_ins || !d_ins))
+                return fail(SMC_E_INPUT, w + ": " + std::to_string(V.len) + " inserted letters at " + std::to_string(V.ins_off) +
+                                         " of a pool of " + std::to_string(n_ins));
+        }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemsetAsync(d_n_host, 0, sizeof(uint32_t), (hipStream_t)stream));
+    if (!n_listed || !n_copies) return SMC_OK;
+    if (!d_rows || !d_var || !d_alt_id || !d_out || !d_host_list) return fail(SMC_E_ARG, who + ": NULL argument");
+    if (keys && xcap && (!d_aln || !d_bq || !d_x || !d_xcount)) return fail(SMC_E_ARG, who + ": NULL argument");
+    const unsigned gx = (unsigned)std::min<int64_t>(((int64_t)n_listed + SCD_BLOCK - 1) / SCD_BLOCK, 1024);
+    hipLaunchKernelGGL(k_sdk_init, dim3(gx, (unsigned)n_copies), dim3(SCD_BLOCK), 0, (hipStream_t)stream, d_var, (uint32_t)n_listed, d_alt_id);
+    if (keys && xcap) {
+        (void)d_cig;                    // (an entry holds the query position and the indel the walk resolved: no CIGAR is read)
+        SdkCopies C;
+        C.aln = (const uint8_t*)d_aln; C.aln_stride = (unsigned long long)aln_stride;
+        C.bq = d_bq; C.bq_stride = (unsigned long long)bq_stride;
+        C.n_aln = (uint32_t)n_aln; C.cap_pairs = (unsigned long long)cap_pairs;
+        C.x = d_x; C.x_stride = (unsigned long long)x_stride;
+        C.xcount = d_xcount; C.xcount_stride = (unsigned long long)xcount_stride;
+        C.xcap = (uint32_t)xcap;
+        hipLaunchKernelGGL(k_sdk_resolve, dim3((unsigned)std::min<int64_t>((xcap + SCD_BLOCK - 1) / SCD_BLOCK, 1024), (unsigned)n_copies),
+                           dim3(SCD_BLOCK), 0, (hipStream_t)stream, C, d_var, (uint32_t)n_listed, d_ins, d_alt_id);
+    }
+    const double edge = thr - 0.005;
+    hipLaunchKernelGGL(k_sdk_detect, dim3(gx, (unsigned)n_copies), dim3(SCD_BLOCK), 0, (hipStream_t)stream, d_rows, (uint32_t)n_loci, d_var,
+                       (uint32_t)n_listed, d_alt_id, edge - 1e-6, edge + 1e-6, d_out, d_host_list, d_n_host);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
 // (--spikeRpb, --spikeIndelRpb, --spikePhaseRpb) what the three counts entries check, on the host copies and before anything is
 // enqueued, then the counters zeroed and k_spr_counts.  A row is a listed variant: (N', V0', S', READS', V1') per replicate and cell
 // (spike target x read threshold) from the records of its covering barcodes, segment e the records of barcode e - with `four` the

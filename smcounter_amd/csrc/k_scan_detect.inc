@@ -48,3 +48,116 @@ __global__ __launch_bounds__(SCD_BLOCK) void k_scan_detect(const smc_row* __rest
         if (v == SMC_SCAN_HOST) host_list[atomicAdd(n_host, 1u)] = idx;       // (at most n_copies * n_listed appends: the list's size)
     }
 }
+
+// ------------------------------------------------------------------------------------------
+// --spikeScanIndel: the same verdict when the planted variant is an allele KEY (smc_scan_detect_keys)
+// ------------------------------------------------------------------------------------------
+// An insertion's or a deletion's allele id is not fixed: the builder numbers the keys a locus meets 6 and up, per build, in the order
+// it meets them, and leaves one extras entry (locus, allele id, alignment, query position, indel) per such key - the alignment is the
+// one whose text the host would print as the key (smc_bam_allele_key).  A pass's copies are built one behind the other, each leaving
+// its extras list in a region of its own; per called batch
+//   k_sdk_init     a lane per (copy = blockIdx.y, listed variant): an SNV's id is its letter's fixed id, a key's SMC_SCAN_ID_NONE;
+//   k_sdk_resolve  a lane per extras entry of copy blockIdx.y (the count clipped to xcap): the listed variants of the entry's locus by
+//                  a lower-bound search over the ascending `locus` fields, then af_shows' rule on the COPY's record and pairs - the
+//                  anchor letter the variant's; a deletion: indel == -len; an insertion: the inserted letters, clamped at the read's
+//                  end as the host's slice clamps them, the pool's.  (The entry holds the query position and the indel the walk
+//                  resolved: the CIGAR is not walked again.)  A match puts the entry's id into the slot by compare-and-swap; a slot
+//                  that was taken already - two entries show the key: must not happen -, or an entry whose record cannot be read
+//                  (an alignment beyond n_aln, a query position beyond l_seq, pairs beyond cap_pairs), gets SMC_SCAN_ID_HOST, which
+//                  nothing replaces: the slot's end state does not depend on the order of the lanes;
+//   k_sdk_detect   k_scan_detect with cand[0].allele == the slot's id: SMC_SCAN_ID_NONE - nobody shows the key in that copy - is NOT
+//                  on a row that is otherwise decidable, SMC_SCAN_ID_HOST is HOST.
+// Three launches behind one another on the stream, once per called batch; the extras of a copy are a few entries per locus next to an
+// indel and none elsewhere, so the resolve pass is a few thousand lanes.  A lane per entry (not a lane per (copy, listed variant) that
+// walks the copy's list): the lists are unsorted, and a walk per listed variant would read every list G times.
+struct SdkCopies {
+    const uint8_t* aln; unsigned long long aln_stride;          // copy c's records at aln + c * aln_stride (bytes)
+    const uint8_t* bq; unsigned long long bq_stride;            // ... its (letter, quality) pairs
+    uint32_t n_aln; unsigned long long cap_pairs;
+    const uint32_t* x; unsigned long long x_stride;             // ... its extras entries at x + c * x_stride (words)
+    const uint32_t* xcount; unsigned long long xcount_stride;   // ... their number at xcount[c * xcount_stride]
+    uint32_t xcap;
+};
+
+__device__ __forceinline__ uint32_t sdk_letter_id(uint32_t letter) {                 // (pileup.BASE_ALLELES: A, T, G, C = 0 .. 3)
+    return letter == 'A' ? 0u : letter == 'T' ? 1u : letter == 'G' ? 2u : 3u;
+}
+
+__global__ __launch_bounds__(SCD_BLOCK) void k_sdk_init(const smc_af_variant* __restrict__ var, uint32_t n_listed, uint32_t* __restrict__ alt_id) {
+    const uint32_t c = blockIdx.y;
+    for (uint32_t g = blockIdx.x * SCD_BLOCK + threadIdx.x; g < n_listed; g += gridDim.x * SCD_BLOCK) {
+        const smc_af_variant V = var[g];
+        alt_id[(size_t)c * n_listed + g] = V.kind == SMC_AF_SNV ? sdk_letter_id(V.letter) : SMC_SCAN_ID_NONE;
+    }
+}
+
+__global__ __launch_bounds__(SCD_BLOCK) void k_sdk_resolve(SdkCopies C, const smc_af_variant* __restrict__ var, uint32_t n_listed,
+                                                           const uint8_t* __restrict__ ins, uint32_t* __restrict__ alt_id) {
+    const uint32_t c = blockIdx.y;
+    const uint32_t n = min(C.xcount[(size_t)c * C.xcount_stride], C.xcap);
+    const uint32_t* const x = C.x + (size_t)c * C.x_stride;
+    const smc_dev_aln* const aln = (const smc_dev_aln*)(C.aln + (size_t)c * C.aln_stride);
+    const uint8_t* const bq = C.bq + (size_t)c * C.bq_stride;
+    for (uint32_t e = blockIdx.x * SCD_BLOCK + threadIdx.x; e < n; e += gridDim.x * SCD_BLOCK) {
+        const uint32_t l = x[5ull * e], aid = x[5ull * e + 1], ai = x[5ull * e + 2], qpos = x[5ull * e + 3];
+        const int32_t indel = (int32_t)x[5ull * e + 4];
+        uint32_t g = 0, hi = n_listed;
+        while (g < hi) {
+            const uint32_t mid = g + (hi - g) / 2;
+            if (var[mid].locus < l) g = mid + 1; else hi = mid;
+        }
+        for (; g < n_listed; ++g) {
+            const smc_af_variant V = var[g];
+            if (V.locus != l) break;
+            if (V.kind != SMC_AF_INS && V.kind != SMC_AF_DEL) continue;
+            uint32_t* const slot = alt_id + (size_t)c * n_listed + g;
+            bool bad = ai >= C.n_aln, shows = false;
+            if (!bad) {
+                const smc_dev_aln a = aln[ai];
+                bad = qpos >= (uint32_t)a.l_seq || (unsigned long long)a.seq_off + a.l_seq > C.cap_pairs;
+                if (!bad) {
+                    const uint8_t* const s = bq + 2ull * a.seq_off;                   // (the letter of base k: byte 2k)
+                    if ((uint32_t)s[2ull * qpos] == V.letter) {
+                        if (V.kind == SMC_AF_DEL) {
+                            shows = indel < 0 && (0u - (uint32_t)indel) == V.len;
+                        } else if (indel > 0) {
+                            // the inserted letters as the host's slice clamps them: query [qpos + 1, min(l_seq, qpos + 1 + indel))
+                            const uint32_t k_max = min((uint32_t)a.l_seq - (qpos + 1u), (uint32_t)indel);
+                            shows = k_max == V.len;
+                            for (uint32_t k = 0; shows && k < k_max; ++k) shows = s[2ull * (qpos + 1u + k)] == ins[V.ins_off + k];
+                        }
+                    }
+                }
+            }
+            if (bad) atomicExch(slot, SMC_SCAN_ID_HOST);
+            else if (shows && atomicCAS(slot, SMC_SCAN_ID_NONE, aid) != SMC_SCAN_ID_NONE) atomicExch(slot, SMC_SCAN_ID_HOST);
+        }
+    }
+}
+
+__global__ __launch_bounds__(SCD_BLOCK) void k_sdk_detect(const smc_row* __restrict__ rows, uint32_t n_loci,
+                                                          const smc_af_variant* __restrict__ var, uint32_t n_listed,
+                                                          const uint32_t* __restrict__ alt_id, double lo, double hi,
+                                                          smc_scan_verdict* __restrict__ out, uint32_t* __restrict__ host_list,
+                                                          uint32_t* __restrict__ n_host) {
+    const uint32_t c = blockIdx.y;
+    for (uint32_t g = blockIdx.x * SCD_BLOCK + threadIdx.x; g < n_listed; g += gridDim.x * SCD_BLOCK) {
+        const uint32_t idx = c * n_listed + g;
+        const uint32_t id = alt_id[idx];
+        const smc_row* const r = rows + ((size_t)c * n_loci + var[g].locus);  // (the host checked locus < n_loci on its copy)
+        const int32_t status = r->status, bi = r->biallelic, used = r->used_mt;
+        const int32_t allele = r->cand[0].allele, vmt = r->cand[0].vmt;
+        const double pi = r->cand[0].pi;
+        uint32_t v = SMC_SCAN_HOST;
+        if (id != SMC_SCAN_ID_HOST && status == 0 && bi == 0) {
+            if (id == SMC_SCAN_ID_NONE || (uint32_t)allele != id || pi < lo) v = SMC_SCAN_NOT;
+            else if (pi > hi) v = SMC_SCAN_CALLED;
+        }
+        smc_scan_verdict rec;
+        rec.pi = pi;
+        rec.vmt = vmt;
+        rec.mt_verdict = (v << 30) | (uint32_t)min(max(used, 0), (int32_t)SMC_SCAN_MT_MASK);
+        out[idx] = rec;
+        if (v == SMC_SCAN_HOST) host_list[atomicAdd(n_host, 1u)] = idx;       // (at most n_copies * n_listed appends: the list's size)
+    }
+}

@@ -641,11 +641,13 @@ def _run_depth_masks(eng, table, idents):
 
 def build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, planes, uaux, slot_base, umi_base, cap, max_depth,
               allele_key, barcode_name, stream_sync=True, sampler: str = "reference", sampler_seed: int = 0, barcode_idents=None,
-              uploaded=None):
+              uploaded=None, extras: "BuildExtras" = None):
     """smc_build_planes over one run's alignments `A` (bamio.NativeBam.alignments_run or synth.generate_alignments) into the
     batch's device arrays (`planes`: [words, meta, umi, frag, dist], any of them None).  `allele_key(ai, qpos, indel)` / `barcode_name(gid)` give the texts the host needs (indel allele
     keys, barcode names for the reference's down-sampling).  `uploaded` (RunOnDevice): the run's arrays are in HBM already (A then
-    holds only the counts and "deepest"); they stay the caller's."""
+    holds only the counts and "deepest"); they stay the caller's.  `extras` (BuildExtras, off by default): the build's extras list
+    and its count stay in the caller's device regions, extras.n gets the count, and no per-locus table is made - the answer's tables
+    are [] (extras_table makes the one of a locus when it is asked for)."""
     import time
     from .engine import DevBuf
     T = _TIMES if os.environ.get("SMC_DEVPLANES_TIMING") else None
@@ -674,9 +676,8 @@ def build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, planes, uaux, sl
         d_aln, d_cig, d_bq, d_loc, d_ref = uploaded.aln, uploaded.cig, uploaded.bq, uploaded.loc, uploaded.ref
         loc_host, n_aln = uploaded.loc_host, uploaded.n_aln
     d_loci = DevBuf(eng, nl * LOCUS_DTYPE.itemsize)
-    xcap = 4 * nl + 4096
-    d_x = DevBuf(eng, 20 * xcap)
-    d_cnt = DevBuf(eng, 8)
+    xcap = build_xcap(nl)
+    d_x, d_cnt = (DevBuf(eng, 20 * xcap), DevBuf(eng, 8)) if extras is None else (extras.x, extras.cnt)
     bi = abi.SmcBuildIn(d_aln.data_ptr(), d_cig.data_ptr(), d_bq.data_ptr(), d_loc.data_ptr(), d_ref.data_ptr(),
                         lo, nl, A["n_bc"], A["n_pair"], deepest, n_aln, loc_host.ctypes.data if loc_host is not None else None)
     pp = [t.data_ptr() if t is not None else None for t in planes]     # [words, meta, umi, frag, dist]
@@ -721,25 +722,17 @@ def build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, planes, uaux, sl
         d_pos.free(); d_st.free(); d_id.free()
     if own is not None:
         own.free()
-    for b in (d_loci, d_cnt):
+    for b in (d_loci,) + ((d_cnt,) if extras is None else ()):
         b.free()                              # (back to the engine's spare list right away, not whenever the collector gets to them)
-    # allele tables: the six fixed keys + what the kernel met, in the order it numbered them
-    tables = [_BASE_TABLE] * nl                 # (shared, never written: a locus that met more alleles gets its own list)
     nx = int(cnt[0])
-    if nx:
-        xl = d_x.download(np.uint32, 5 * nx).reshape(nx, 5)
-        xl = xl[np.lexsort((xl[:, 1], xl[:, 0]))]
-        for l, aid, ai, qpos, indel in xl.tolist():
-            key = allele_key(ai, qpos, np.int32(np.uint32(indel)))
-            if key[0] == "D" and len(key) > 1:        # "D<len>|<site>" -> DEL|site+deleted|site (smCounter.py:392-396)
-                ln, site = key[1:].split("|")
-                pos1 = lo + l + 1
-                key = "DEL|" + site + fasta.fetch(chrom, pos1, pos1 + int(ln)).upper() + "|" + site
-            if tables[l] is _BASE_TABLE:
-                tables[l] = list(BASE_ALLELES)
-            assert aid == len(tables[l]), (l, aid, len(tables[l]))
-            tables[l].append(key)
-    d_x.free()
+    if extras is not None:
+        extras.n, tables = nx, []
+    else:
+        # allele tables: the six fixed keys + what the kernel met, in the order it numbered them
+        tables = [_BASE_TABLE] * nl             # (shared, never written: a locus that met more alleles gets its own list)
+        if nx:
+            _extras_into_tables(tables, d_x.download(np.uint32, 5 * nx).reshape(nx, 5), allele_key, chrom, lo, fasta)
+        d_x.free()
     # the reference's down-sampling (smCounter.py:496-498) on loci over the barcode cap: barcode texts by first included read
     over = np.nonzero((lc["n_umi"] > params.ds) & ((lc["flags"] & LF_SAMPLED) == 0))[0] if params.ds > 0 else []
     if len(over):
@@ -761,6 +754,43 @@ def build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, planes, uaux, sl
             uaux[0].upload(us, 4 * o)
             lc["flags"][l] |= LF_SAMPLED
     return nl, ns, lc, tables
+
+
+def build_xcap(nl: int) -> int:
+    """The extras entries build_run gives a build of `nl` loci room for (20 bytes each)."""
+    return 4 * int(nl) + 4096
+
+
+@dataclasses.dataclass
+class BuildExtras:
+    """Where build_run leaves a build's extras list instead of making tables of it: `x`, a device region of 20 * build_xcap(nl) bytes,
+    and `cnt`, one of 8 bytes (the count, then the builder's status word); both stay the caller's.  `n`: the count, once built."""
+    x: object
+    cnt: object
+    n: int = None
+
+
+def _extras_into_tables(tables, xl: np.ndarray, allele_key, chrom: str, lo: int, fasta) -> None:
+    """The extras entries `xl` ([n, 5]: locus, allele id, alignment, query position, indel) appended to the allele tables of their
+    loci, in the order the kernel numbered them; a locus that still shares _BASE_TABLE gets a list of its own."""
+    xl = xl[np.lexsort((xl[:, 1], xl[:, 0]))]
+    for l, aid, ai, qpos, indel in xl.tolist():
+        key = allele_key(ai, qpos, np.int32(np.uint32(indel)))
+        if key[0] == "D" and len(key) > 1:        # "D<len>|<site>" -> DEL|site+deleted|site (smCounter.py:392-396)
+            ln, site = key[1:].split("|")
+            pos1 = lo + l + 1
+            key = "DEL|" + site + fasta.fetch(chrom, pos1, pos1 + int(ln)).upper() + "|" + site
+        if tables[l] is _BASE_TABLE:
+            tables[l] = list(BASE_ALLELES)
+        assert aid == len(tables[l]), (l, aid, len(tables[l]))
+        tables[l].append(key)
+
+
+def extras_table(xl: np.ndarray, locus: int, allele_key, chrom: str, lo: int, fasta):
+    """The allele table of one locus of a build from the build's extras entries `xl` (a BuildExtras region downloaded: [n, 5])."""
+    tables = {locus: _BASE_TABLE}
+    _extras_into_tables(tables, xl[xl[:, 0] == locus], allele_key, chrom, lo, fasta)
+    return tables[locus]
 
 
 @dataclasses.dataclass
@@ -2187,11 +2217,12 @@ def _narrow_retry(eng, P, call):
     return out
 
 
-def _build_copies(eng, run: AfRun, n_copies: int, kept_runs, P, bits, flag, fasta, max_depth, sampler, sampler_seed):
+def _build_copies(eng, run: AfRun, n_copies: int, kept_runs, P, bits, flag, fasta, max_depth, sampler, sampler_seed, extras=None):
     """The builds of a replicate stage's batch: `kept_runs` - an iterable of `n_copies` _KeptRun over the kept run `run`, its selections
     or its spiked copies, each made when the loop asks for it and freed behind its build - built one behind the other into one
     _DsBatch with the cell's params `P`, as _ds_build_run appends successive runs to a rule's -> the batch (the caller frees it), or
-    NARROW (a build has no room in 16-bit read words).  BamError naming `flag`: a build the device builder does not take."""
+    NARROW (a build has no room in 16-bit read words).  BamError naming `flag`: a build the device builder does not take.
+    `extras`: per copy the BuildExtras its build leaves its extras list in - the batch then has no tables."""
     lo, nl = run.lo, run.nl
     ns_full = int(run.A["n_slots"])
     cap = n_copies * (ns_full + nl) + ns_full + nl + 64
@@ -2199,11 +2230,11 @@ def _build_copies(eng, run: AfRun, n_copies: int, kept_runs, P, bits, flag, fast
     cp = abi.c_params(P)
     try:
         n_loc = 0
-        for kept in kept_runs:
+        for c, kept in enumerate(kept_runs):
             try:
                 done = build_run(kept.counts, eng.L, eng, cp, P, run.chrom, lo, fasta, run.run_ref, [d.words] + d.planes, d.uaux, d.slots,
                                  d.slots + n_loc, cap, max_depth, kept.allele_key, kept.barcode_name, sampler=sampler, sampler_seed=sampler_seed,
-                                 barcode_idents=kept.barcode_idents, uploaded=kept.run)
+                                 barcode_idents=kept.barcode_idents, uploaded=kept.run, extras=extras[c] if extras is not None else None)
             finally:
                 kept.free()
             if done is None:
@@ -3085,6 +3116,40 @@ def scan_detect(eng, d_rows, n_copies: int, n_loci: int, listed, threshold):
     return rec.reshape(B, G), todo
 
 
+def scan_detect_keys(eng, d_rows, n_copies: int, n_loci: int, var, ins, copies: dict, extras: dict, threshold):
+    """smc_scan_detect_keys over the rows of a called batch in HBM -> scan_detect's pair and the resolved ids, uint32 [n_copies, G]
+    (abi.SCAN_ID_NONE: no extras entry of the copy shows the key; abi.SCAN_ID_HOST: the host has to look).  var, ins:
+    af_run_variants' records of the listed variants, `locus` ascending, and their pool of inserted letters.  copies: dict(aln, cig,
+    bq: device addresses of copy 0's arrays, strides: the three byte strides - 0: shared -, n_aln, cap_pairs: the pairs of a copy's
+    pool).  extras: dict(x, cnt: device addresses of copy 0's extras list and of its count, x_stride, cnt_stride: in words, xcap)."""
+    from .engine import DevBuf
+    var = np.ascontiguousarray(var, abi.AF_VARIANT_DTYPE)
+    ins = np.ascontiguousarray(ins, np.uint8)
+    B, G = int(n_copies), len(var)
+    n = B * G
+    up8 = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
+    bufs = [up8(var), up8(ins), DevBuf(eng, 4 * max(1, n) + 256), DevBuf(eng, 16 * max(1, n) + 256), DevBuf(eng, 4 * max(1, n) + 256),
+            DevBuf(eng, 256)]
+    sa, sb, sc = copies["strides"]
+    try:
+        _lib.check(eng.L.smc_scan_detect_keys(eng.ctx, d_rows.data_ptr() if d_rows is not None else None, B, int(n_loci), bufs[0].data_ptr(),
+                                              var.ctypes.data, G, bufs[1].data_ptr(), len(ins), copies["aln"], int(sa), copies["cig"],
+                                              int(sc), copies["bq"], int(sb), int(copies["n_aln"]), int(copies["cap_pairs"]), extras["x"],
+                                              int(extras["x_stride"]), extras["cnt"], int(extras["cnt_stride"]), int(extras["xcap"]),
+                                              float(threshold), bufs[2].data_ptr(), bufs[3].data_ptr(), bufs[4].data_ptr(),
+                                              bufs[5].data_ptr(), ctypes.c_void_p(0)), "smc_scan_detect_keys")
+        n_host = int(bufs[5].download(np.uint32, 1)[0])              # (the default stream: behind the kernels)
+        rec = bufs[3].download(abi.SCAN_VERDICT_DTYPE, n) if n else np.zeros(0, abi.SCAN_VERDICT_DTYPE)
+        ids = bufs[2].download(np.uint32, n) if n else np.zeros(0, np.uint32)
+        if n_host > n:
+            raise _lib.SmcError("smc_scan_detect_keys: %d records for the host out of %d" % (n_host, n))
+        todo = np.sort(bufs[4].download(np.uint32, n_host)) if n_host else np.zeros(0, np.uint32)
+    finally:
+        for b in bufs:
+            b.free()
+    return rec.reshape(B, G), todo, ids.reshape(B, G)
+
+
 def scan_called_host(text, v, threshold: int, repeats) -> bool:
     """Was `v` called in the raw row `text`, the way the replicate pages decide it: the row through the repeat filters and the .cut
     rule (dsaf.replicate_entry), then REF and ALT compared (spike._called)."""
@@ -3094,40 +3159,89 @@ def scan_called_host(text, v, threshold: int, repeats) -> bool:
 
 
 def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed,
-               bits, threshold, repeats, check0):
+               bits, threshold, repeats, check0, indel: dict = None):
     """`len(part_seeds)` spiked copies of the run at one target from one smc_spike_alleles_reps call, each built behind the other into
     one device batch and the batch called with one plan - _spike_rep_call's way - but the rows stay in HBM: smc_scan_detect gives a
     verdict per (copy, listed locus), and only the rows it leaves to the host come down, one by one, to be printed and cut the
     existing way.  run.group: the pass's variants of this run; listed: their abi.SCAN_LOCUS_DTYPE records; check0: the copy that is
     replicate 0 (or None) - its listed rows come down as well, and a device verdict of CALLED or NOT that the host's decision does
-    not share ends the run.  -> (bool [copies, listed]: called, the number of verdicts the host decided), or NARROW."""
+    not share ends the run.  -> (bool [copies, listed]: called, the number of verdicts the host decided), or NARROW.
+    `indel` (--spikeScanIndel: dict(ins: the chromosome's pool of inserted letters, var, var_ins: af_run_variants' records of
+    run.group - they stand where `listed` does -, want: per copy and variant the counts call's (N, V1))): the copies come from one
+    smc_spike_indels_reps call; every build leaves its extras list in HBM and makes no table (BuildExtras); smc_scan_detect_keys
+    resolves the key's allele id per copy from them; replicate 0's (N, V1) by smc_allele_carriers on the copy must be the counts
+    call's; and the table of a row that comes down is made from its copy's extras, the texts through copy_allele_key on the copy,
+    which is alive until this call returns."""
     from . import vc
+    from .engine import DevBuf
     A, up, lo, nl, chrom = run.A, run.up, run.lo, run.nl, run.chrom
     B, G = len(part_seeds), len(run.group)
-    d_aln, d_bq, (sa, sb), stats = spike_run_copies(eng, up, A, svar, run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
+    flag, entry = ("--spikeScan", "smc_scan_detect") if indel is None else ("--spikeScanIndel", "smc_scan_detect_keys")
+    extras = None
+    if indel is None:
+        d_aln, d_bq, (sa, sb), stats = spike_run_copies(eng, up, A, svar, run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
+        owned = [d_aln, d_bq]
+        runs = [RunOnDevice(d_aln.view(c * sa), up.cig, d_bq.view(c * sb), up.loc, up.ref, up.n_aln, up.loc_host) for c in range(B)]
+    else:
+        made = spike_indel_run_copies(eng, up, A, svar, indel["ins"], run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1],
+                                      caps=indel.get("caps"))
+        (sa, sb, sc), stats, owned = made["strides"], made["stats"], [made["aln"], made["bq"], made["cig"]]
+        if made["totals"][:, 2].any():
+            for b in owned:
+                b.free()
+            raise _lib.SmcError("smc_spike_indels_reps: a copy of %s:%d-%d did not fit spike_indel_caps' bounds" % (chrom, lo + 1, lo + nl))
+        runs = [RunOnDevice(_BufView(made["aln"], c * sa), _BufView(made["cig"], c * sc), _BufView(made["bq"], c * sb), up.loc, up.ref, up.n_aln,
+                            up.loc_host, pairs_used=int(made["totals"][c, 0])) for c in range(B)]
+        xcap = build_xcap(nl)
+        owned += [DevBuf(eng, 20 * xcap * B + 256), DevBuf(eng, 8 * B + 256)]
+        extras = [BuildExtras(_BufView(owned[3], 20 * xcap * c), _BufView(owned[4], 8 * c)) for c in range(B)]
     d = d_rows = plan = None
     try:
         for c in range(B):
             for g, k in enumerate(run.group):
                 if int(stats[c, var_at[g], 0]) != int(want_reads[c][g]):
                     v = variants[k]
-                    raise RuntimeError("--spikeScan: seed %d at %s:%d: the rewrite touched %d records, the counts call says %d" %
-                                       (int(part_seeds[c]), v.chrom, v.pos, int(stats[c, var_at[g], 0]), int(want_reads[c][g])))
-        # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch)
-        copies = (_KeptRun(RunOnDevice(d_aln.view(c * sa), up.cig, d_bq.view(c * sb), up.loc, up.ref, up.n_aln, up.loc_host), A, None, A,
-                           run.bam.allele_key, run.bam.barcode_name, lambda n: run.idents) for c in range(B))
-        built = _build_copies(eng, run, B, copies, P, bits, "--spikeScan", fasta, max_depth, sampler, sampler_seed)
+                    raise RuntimeError("%s: seed %d at %s:%d: the rewrite touched %d records, the counts call says %d" %
+                                       (flag, int(part_seeds[c]), v.chrom, v.pos, int(stats[c, var_at[g], 0]), int(want_reads[c][g])))
+        if indel is not None and check0 is not None:
+            cov, car, _ = allele_carriers_run(eng, runs[check0], A, lo, indel["var"], indel["var_ins"])
+            for g, k in enumerate(run.group):
+                mine, want = (int(cov[g].sum()), int(car[g].sum())), tuple(int(x) for x in indel["want"][check0][g])
+                if mine != want:
+                    v = variants[k]
+                    raise RuntimeError("%s: seed %d at %s:%d: the copy holds (N, V1) = %r, the counts call says %r" %
+                                       (flag, int(part_seeds[check0]), v.chrom, v.pos, mine, want))
+        # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch; a record the indel rewrite
+        # relocated has its texts in the copy - no table is made of those builds here)
+        copies = (_KeptRun(runs[c], A, None, A, run.bam.allele_key, run.bam.barcode_name, lambda n: run.idents) for c in range(B))
+        built = _build_copies(eng, run, B, copies, P, bits, flag, fasta, max_depth, sampler, sampler_seed, extras)
         if built == NARROW:
             return NARROW
         d = built
         plan = eng.make_plan(d.loci())
         d_rows = plan.run_into_devbuf([d.words, d.uaux[0]], P)
-        rec, todo = scan_detect(eng, d_rows, B, nl, listed, threshold)       # (its downloads wait for the plan's kernels)
+        if indel is None:
+            rec, todo = scan_detect(eng, d_rows, B, nl, listed, threshold)       # (its downloads wait for the plan's kernels)
+            table_of = lambda c, a: d.tables[c * nl + a]
+        else:
+            rec, todo, _ = scan_detect_keys(
+                eng, d_rows, B, nl, indel["var"], indel["var_ins"],
+                dict(aln=made["aln"].data_ptr(), cig=made["cig"].data_ptr(), bq=made["bq"].data_ptr(), strides=(sa, sb, sc), n_aln=up.n_aln,
+                     cap_pairs=made["caps"][0]),
+                dict(x=owned[3].data_ptr(), cnt=owned[4].data_ptr(), x_stride=5 * xcap, cnt_stride=2, xcap=xcap), threshold)
+            lists, keys = {}, {}
+
+            def table_of(c, a):
+                if c not in lists:
+                    n_x = min(int(extras[c].n), xcap)
+                    lists[c] = extras[c].x.download(np.uint32, 5 * n_x).reshape(n_x, 5) if n_x else np.zeros((0, 5), np.uint32)
+                    keys[c] = copy_allele_key(runs[c], A, run.bam.allele_key)
+                return extras_table(lists[c], a, keys[c], chrom, lo, fasta)
         verdict = (rec["mt_verdict"] >> 30).astype(np.int64)
         called = verdict == abi.SCAN_CALLED
         theirs = set(int(x) for x in todo)
         if theirs != set(int(x) for x in np.flatnonzero(verdict.reshape(-1) == abi.SCAN_HOST)):
-            raise RuntimeError("--spikeScan: %s:%d-%d: the list of the records for the host is not that of the HOST verdicts" % (chrom, lo + 1, lo + nl))
+            raise RuntimeError("%s: %s:%d-%d: the list of the records for the host is not that of the HOST verdicts" % (flag, chrom, lo + 1, lo + nl))
         mine = sorted(theirs | (set(check0 * G + g for g in range(G)) if check0 is not None else set()))
         if mine:
             at = [int(listed["offset"][i % G]) for i in mine]
@@ -3135,31 +3249,33 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
             for n, (i, a) in enumerate(zip(mine, at)):
                 d_rows.download(abi.ROW_DTYPE, 1, ((i // G) * nl + a) * abi.ROW_DTYPE.itemsize, out=got[n:n + 1])
             view = vc.LocusView([chrom] * len(mine), [lo + 1 + a for a in at], [run.run_ref[a] if a < len(run.run_ref) else "" for a in at],
-                                [d.tables[(i // G) * nl + a] for i, a in zip(mine, at)])
+                                [table_of(i // G, a) for i, a in zip(mine, at)])
             text = vc._strings(got, view, P, fasta)
             for i, line in zip(mine, text):
                 v = variants[run.group[i % G]]
                 if line.startswith(vc.EXC_PREFIX):
-                    raise RuntimeError("--spikeScan: %s:%d: the row of seed %d could not be printed:\n%s" % (v.chrom, v.pos, int(part_seeds[i // G]), line))
+                    raise RuntimeError("%s: %s:%d: the row of seed %d could not be printed:\n%s" % (flag, v.chrom, v.pos, int(part_seeds[i // G]), line))
                 host = scan_called_host(line, v, threshold, repeats)
                 if i in theirs:
                     called[i // G, i % G] = host
                 elif host != bool(called[i // G, i % G]):
-                    raise RuntimeError("--spikeScan: replicate 0 of %s:%d %s>%s: smc_scan_detect says %s (PI %.17g, threshold %d), the row as "
+                    who = "replicate 0 of" if indel is None else "seed %d at" % int(part_seeds[i // G])
+                    raise RuntimeError("%s: %s %s:%d %s>%s: %s says %s (PI %.17g, threshold %d), the row as "
                                        "the run would print and cut it says %s:\n%s" %
-                                       (v.chrom, v.pos, v.ref, v.alt, "CALLED" if called[i // G, i % G] else "NOT", float(rec[i // G, i % G]["pi"]),
+                                       (flag, who, v.chrom, v.pos, v.ref, v.alt, entry,
+                                        "CALLED" if called[i // G, i % G] else "NOT", float(rec[i // G, i % G]["pi"]),
                                         threshold, "called" if host else "not called", line))
         return called, len(theirs)
     finally:
         if plan is not None:
             plan.close()
-        for b in (d_rows, d, d_aln, d_bq):
+        for b in [d_rows, d] + owned:
             if b is not None:
                 b.free()
 
 
 def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n_reps: int, eng, threshold: int, repeats,
-               sampler: str = "reference", sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000):
+               sampler: str = "reference", sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, indel: bool = False):
     """The stage of --spikeScan.  variants: the scan's SNV at every scanned locus (tools.spike_scan_lists.scan_variants); passes: [(k,
     the indices of pass k)] (scan_passes).  A pass is the run --spikeAF <targets> --spikeVariants <its list> --spikeReps n_reps --dsSeed
     seed: replicate j has seed (seed + j) mod 2^64, and the draws, the rewrite, NM and the thresholds are that run's.
@@ -3170,6 +3286,12 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     smc_spike_alleles_reps call as spike_replicates' room rule allows, each built behind the last and the batch called with one plan
     (_scan_call).  The rewrite takes the pass's whole list of the chromosome: a variant is rewritten in whichever run decodes a read
     that spans it.  No batch of rows is downloaded.
+    `indel` (--spikeScanIndel: `variants` are the scan's insertion or deletion at every locus, tools.spike_scan_lists.scan_indels): a
+    pass is the run --spikeAF <targets> --spikeVariants <its list> --spikeIndelReps n_reps.  The counters are the four of
+    _spike_single_counters, the counts come from one smc_spike_indel_counts call, the copies from smc_spike_indels_reps - sized by
+    spike_indel_caps and spike_indel_copy_strides under the same room rule -, and the verdicts from smc_scan_detect_keys (_scan_call's
+    `indel`).  ValueError before anything is spiked: a run with a record at which the rewrite's 16-bit limits could bind
+    (spike_indel_limits).
     -> dict(seeds, base: per variant (N, V0), counts: uint32 [V, R, T, 3] = (S, READS, V1), called: bool [V, T, R], passes: per pass
     of `passes` dict(variants, copies, builds, host, seconds), times: dict(stage, runs, decode))."""
     import time
@@ -3189,7 +3311,7 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     for p, (_, members) in enumerate(passes):
         pass_at[members] = p
         local[members] = np.arange(len(members))
-    spikes = [SpikeSet([variants[i] for i in members]) for _, members in passes]
+    spikes = [SpikeSet([variants[i] for i in members], indels=indel) for _, members in passes]
     base, counts, called = [None] * V, np.zeros((V, R, T, 3), np.uint32), np.zeros((V, T, R), bool)
     stats = [dict(variants=0, copies=0, builds=0, host=0, seconds=0.0) for _ in passes]
     times = {"decode": 0.0, "runs": 0}
@@ -3217,12 +3339,25 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
             times["decode"] += time.perf_counter() - t0
             times["runs"] += 1
             per_copy = sum(spike_copy_strides(run.up.n_aln, len(A["bq"]) // 2))
-            room = max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per_copy, AF_REP_BATCH_SLOTS // max(1, int(A["n_slots"]) + nl)))
-            for p in sorted({int(pass_at[k]) for k in inside}):
+            in_run = sorted({int(pass_at[k]) for k in inside})
+            for p in in_run if indel else ():
+                bad = spike_indel_limits(A, spikes[p].chrom_variants(v0.chrom, 0.5)[0])
+                if bad is not None:
+                    a = A["aln"][bad]
+                    raise ValueError("%s: the record at %s:%d (l_seq %d, %d CIGAR operations) spans listed "
+                                     "indels that could take l_seq or the CIGAR beyond 65535: whether it takes one would depend on the "
+                                     "draws of the others" % ("--spikeScanIndel", v0.chrom, int(a["pos"]) + 1, int(a["l_seq"]), int(a["n_cig"])))
+            for p in in_run:
                 t0 = time.perf_counter()
                 run.group = [k for k in inside if pass_at[k] == p]
+                caps = None
+                if indel:
+                    # (a copy: records, both pools at their capacities, and the call's scratch of 8 bytes per alignment - spike_replicates')
+                    caps = spike_indel_caps(A, spikes[p].chrom_variants(v0.chrom, 0.5)[0])
+                    per_copy = sum(spike_indel_copy_strides(run.up.n_aln, *caps)) + 8 * run.up.n_aln
+                room = max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per_copy, AF_REP_BATCH_SLOTS // max(1, int(A["n_slots"]) + nl)))
                 _scan_pass(eng, run, spikes[p], [int(local[k]) for k in run.group], variants, seeds, thr, P, fasta, max_depth, sampler,
-                           sampler_seed, threshold, repeats, room, base, counts, called, stats[p])
+                           sampler_seed, threshold, repeats, room, base, counts, called, stats[p], caps)
                 stats[p]["variants"] += len(run.group)
                 stats[p]["seconds"] += time.perf_counter() - t0
         finally:
@@ -3233,25 +3368,28 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
 
 
 def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr, P, fasta, max_depth, sampler, sampler_seed, threshold,
-               repeats, room, base, counts, called, stat):
+               repeats, room, base, counts, called, stat, caps=None):
     """spike_scan's work for one pass in one run: run.group are the pass's variants there (indices into `variants`), members[g] the
-    place of run.group[g] in the pass's list (`spikes`).  base, counts, called and stat are filled."""
+    place of run.group[g] in the pass's list (`spikes`).  base, counts, called and stat are filled.  `caps` (--spikeScanIndel:
+    spike_indel_caps of the pass's list on the run): the indel branch."""
     A, up, lo, chrom = run.A, run.up, run.lo, run.chrom
     idents, (nm, n_indel) = run.idents, run.mism
     group = run.group
     var, ins = af_run_variants([variants[k] for k in group], chrom, lo, fasta)
     cov, car, cnt0 = allele_carriers_run(eng, up, A, lo, var, ins, counts=True)
     svar, sorder, covers, counters = _spike_single_counters(eng, up, A, lo, spikes, chrom, members, var, ins, idents, seeds[0], P, nm, n_indel,
-                                                            cov, cnt0, False)
+                                                            cov, cnt0, caps is not None)
     for g, k in enumerate(group):
         base[k] = (int(cov[g].sum()), int(car[g].sum()))
-    mine = spike_rep_counts(eng, [spikes.lead_pos[m] for m in members], covers, counters, seeds, thr)       # [G, R, T, 3]
+    mine = (spike_rep_counts if caps is None else spike_indel_counts)(eng, [spikes.lead_pos[m] for m in members], covers, counters, seeds,
+                                                                     thr)       # [G, R, T, 3]
     at_of = {m: n for n, m in enumerate(sorder)}
     var_at = [at_of[m] for m in members]
     listed = np.zeros(len(group), abi.SCAN_LOCUS_DTYPE)
     for g, k in enumerate(group):
         counts[k] = mine[g]
-        listed[g] = (variants[k].pos - 1 - lo, SCAN_ALT_ID[variants[k].alt])
+        # (--spikeScanIndel: a key has no fixed id - smc_scan_detect_keys takes `var`, and of `listed` only the offsets are read)
+        listed[g] = (variants[k].pos - 1 - lo, SCAN_ALT_ID[variants[k].alt] if caps is None else 0)
     R = len(seeds)
     for t in range(len(thr)):
         for b in range(0, R, room):
@@ -3259,6 +3397,9 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
             want = [[int(mine[g, j, t, 1]) for g in range(len(group))] for j in js]
             args = (eng, run, svar, var_at, listed, [seeds[j] for j in js], thr[t], want, P, fasta, variants, max_depth, sampler, sampler_seed)
             tail = (threshold, repeats, js.index(0) if 0 in js else None)
+            if caps is not None:
+                tail += (dict(ins=spikes.ins[chrom], caps=caps, var=var, var_ins=ins,
+                              want=[[(len(covers[g]), int(mine[g, j, t, 2])) for g in range(len(group))] for j in js]),)
             yes, n_host = _narrow_retry(eng, P, lambda bits: _scan_call(*args, bits, *tail))
             for c, j in enumerate(js):
                 for g, k in enumerate(group):

@@ -37,6 +37,10 @@ refuses what does not go with them); the pages <outPrefix>.spikeScan.sensitivity
 <outPrefix>.spikeScan<t>.rate.bedgraph and .spikeScan.t95.bedgraph (write_scan) from the verdicts of devplanes.spike_scan, which keeps
 the called rows on the GPU (smc_scan_detect).
 
+--spikeScanIndel: the scan with one deletion (del<d>) or one tandem duplication (dup<s>) at every locus instead of the SNV (scan reads
+and refuses the flag; tools.spike_scan_lists.scan_indels is the rule); the files and their writers are --spikeScan's, REF and ALT the
+indel's texts at its anchor, the verdicts from smc_scan_detect_keys.
+
 The semantics are tools/spike_variants.py's (DESIGN.md "--spikeAF"); the rewrite on the GPU is csrc/k_spike.inc (smc_spike_alleles),
 the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the main pass are devplanes.spike_rules / spike_run.
 """
@@ -684,15 +688,21 @@ def scan(args):
     """--spikeScan / --spikeScanReps / --spikeScanStride / --spikeScanAlt -> dict(targets, reps, stride, alt), or None without
     --spikeScan.  SystemExit: a helper flag without --spikeScan, --spikeScan without --spikeScanReps, any other --spike* flag or a
     down-sampling flag beside it, a target outside (0, 1) or listed twice, more than MAX_TARGETS, R outside REPS_MIN .. REPS_MAX or no
-    integer, a stride below 1 or no integer, an unknown ALT rule."""
+    integer, a stride below 1 or no integer, an unknown ALT rule.
+    --spikeScanIndel adds "indel": ("del" or "dup", the length) to the dict.  SystemExit: the flag without --spikeScan or beside
+    --spikeScanAlt, a rule that is neither del<d> nor dup<s> with a length in 1 .. 255, a stride below the footprint's."""
     from .tools import spike_scan_lists as lists
     text, r, stride, alt = (getattr(args, f, None) for f in SCAN_FLAGS)
+    indel = getattr(args, "spikeScanIndel", None)
     given = lambda x: x not in (None, "", False)
     if not given(text):
-        for flag, value in zip(SCAN_FLAGS[1:], (r, stride, alt)):
+        for flag, value in zip(SCAN_FLAGS[1:] + ("spikeScanIndel",), (r, stride, alt, indel)):
             if given(value):
                 raise SystemExit("--%s belongs to --spikeScan: it needs --spikeScan" % flag)
         return None
+    if given(indel) and given(alt):
+        raise SystemExit("--spikeScanIndel cannot be combined with --spikeScanAlt: the scan plants an insertion or a deletion OR an SNV at "
+                         "every locus, not both")
     for flag in SCAN_NOT_WITH:
         if given(getattr(args, flag, None)):
             raise SystemExit("--spikeScan cannot be combined with --%s in one run: the scan plants its own SNV at every locus of "
@@ -715,7 +725,14 @@ def scan(args):
     alt = lists.DEFAULT_ALT if not given(alt) else str(alt)
     if alt not in lists.ALT_RULES:
         raise SystemExit("--spikeScanAlt: one of %s expected, got %r" % (", ".join(sorted(lists.ALT_RULES)), alt))
-    return dict(targets=ts, reps=r, stride=stride, alt=alt)
+    out = dict(targets=ts, reps=r, stride=stride, alt=alt)
+    if given(indel):
+        try:
+            out["indel"] = lists.parse_indel_rule(indel)
+            lists.check_indel_stride(out["indel"], stride)
+        except ValueError as e:
+            raise SystemExit(str(e))
+    return out
 
 
 def scan_entry(v, r, called: bool):

@@ -13,6 +13,17 @@ flags that exist; the command line makes its passes with scan_passes() below.
   <outPrefix>.pass<k>.txt   `chrom pos ref alt`, tab-separated, in locus order - one file per pass that holds a locus
   <outPrefix>.passes.txt    a header, one line `k variants file` per such pass, and a last line `#skipped n`: the loci whose genome
                             letter is not A, C, G or T (nothing is planted there)
+
+--spikeScanIndel del<d>|dup<s> (--indel here) plants one deletion or one tandem duplication instead of the SNV at every locus P:
+  del<d>   REF = genome[P .. P+d], ALT = genome[P]: the d letters behind the anchor go;
+  dup<s>   REF = genome[P], ALT = genome[P] + genome[P+1 .. P+s]: the next s letters once more, a homopolymer's expansion inside a run;
+d, s in 1 .. 255.  A locus is skipped when a letter of P .. P+d (P .. P+s) is not A, C, G or T or lies past the chromosome's end.  The
+footprints are --spikeIndels' (spike_variants.footprint: [P, P+d+1] / [P, P+1]) and must be disjoint within a pass: S >= d + 2 for a
+deletion, S >= 2 for a duplication (indel_min_stride).  A pass is then the run
+
+    --spikeAF <targets> --spikeVariants <outPrefix>.pass<k>.txt --spikeIndelReps R --dsSeed s
+
+and every list written parses under spike_variants.parse_variants(..., indels=True).
 """
 from __future__ import annotations
 
@@ -60,6 +71,56 @@ def scan_variants(loc_list, fasta, alt: str = DEFAULT_ALT):
     return out, skipped
 
 
+def parse_indel_rule(text, flag: str = "--spikeScanIndel"):
+    """`del<d>` / `dup<s>` -> ("del" or "dup", the length).  ValueError: anything else, or a length outside 1 .. 255."""
+    t = str(text).strip()
+    if t[:3] in ("del", "dup") and t[3:].isdigit() and len(t) <= 9 and 1 <= int(t[3:]) <= af.MAX_INS:
+        return t[:3], int(t[3:])
+    raise ValueError("%s: del<d> or dup<s> with a length in 1 .. %d expected, got %r" % (flag, af.MAX_INS, text))
+
+
+def indel_min_stride(rule) -> int:
+    """The smallest stride at which the footprints of a pass are disjoint: d + 2 for del<d>, 2 for dup<s>."""
+    kind, n = rule
+    return n + 2 if kind == "del" else 2
+
+
+def check_indel_stride(rule, stride: int, flag: str = "--spikeScanStride") -> None:
+    """ValueError: a stride below indel_min_stride - two footprints of a pass would overlap."""
+    if int(stride) < indel_min_stride(rule):
+        raise ValueError("%s: a stride of %d with %s%d: the footprints of a pass would overlap, the smallest stride allowed is %d" %
+                         (flag, int(stride), rule[0], rule[1], indel_min_stride(rule)))
+
+
+def scan_indels(loc_list, fasta, rule):
+    """scan_variants for --spikeScanIndel: the deletion or duplication of `rule` (parse_indel_rule's pair) anchored at every locus ->
+    (variants in locus order, the (chrom, pos) skipped: a letter of the anchor and the n positions behind it that is not A, C, G or T,
+    or the chromosome ends before them)."""
+    kind, n = rule
+    out, skipped, seen = [], [], set()
+    i, m = 0, len(loc_list)
+    while i < m:
+        chrom, p0 = loc_list[i][0], int(loc_list[i][1])
+        j = i
+        while j + 1 < m and loc_list[j + 1][0] == chrom and int(loc_list[j + 1][1]) == p0 + (j + 1 - i):
+            j += 1
+        letters = fasta.fetch(chrom, p0 - 1, p0 + (j - i) + n).upper()     # (clipped at the chromosome's end: then the tail is short)
+        for x in range(j - i + 1):
+            pos = p0 + x
+            if (chrom, pos) in seen:
+                continue
+            seen.add((chrom, pos))
+            w = letters[x:x + n + 1]
+            if len(w) != n + 1 or any(c not in "ACGT" for c in w):
+                skipped.append((chrom, pos))
+                continue
+            ref, alt = (w, w[0]) if kind == "del" else (w[0], w)
+            key, k = af.allele_key(ref, alt)
+            out.append(af.Variant(chrom, pos, ref, alt, key, k))
+        i = j + 1
+    return out, skipped
+
+
 def scan_passes(variants, stride: int):
     """-> [(k, the indices into `variants` of pass k, in the order given)] for every k in 0 .. stride - 1 that holds a locus."""
     stride = int(stride)
@@ -92,14 +153,25 @@ def main(args):
     if args.runPath:
         os.chdir(args.runPath)
     from .. import bedops, fasta as _fasta
+    indel = getattr(args, "indel", None)
     try:
-        variants, skipped = scan_variants(bedops.expand_loci(args.bedTarget), _fasta.FastaFile(args.refGenome), args.alt)
+        loc_list, fa = bedops.expand_loci(args.bedTarget), _fasta.FastaFile(args.refGenome)
+        if indel in (None, ""):
+            variants, skipped = scan_variants(loc_list, fa, args.alt)
+        else:
+            rule = parse_indel_rule(indel, "--indel")
+            check_indel_stride(rule, args.stride, "--stride")
+            variants, skipped = scan_indels(loc_list, fa, rule)
         passes = scan_passes(variants, args.stride)
     except (ValueError, OSError) as e:
         raise SystemExit(str(e))
     names = write_lists(args.outPrefix, variants, passes, len(skipped))
-    print("%d loci in %d passes of stride %d (%s), %d skipped for a letter that is not A, C, G or T" %
-          (len(variants), len(passes), args.stride, args.alt, len(skipped)))
+    if indel in (None, ""):
+        print("%d loci in %d passes of stride %d (%s), %d skipped for a letter that is not A, C, G or T" %
+              (len(variants), len(passes), args.stride, args.alt, len(skipped)))
+    else:
+        print("%d loci in %d passes of stride %d (%s), %d skipped for a letter inside the footprint that is not A, C, G or T or lies past "
+              "the chromosome's end" % (len(variants), len(passes), args.stride, indel, len(skipped)))
     return names
 
 
@@ -111,6 +183,8 @@ def build_parser():
     parser.add_argument("--stride", type=int, default=DEFAULT_STRIDE, help="S: pass k holds the loci with pos mod S == k")
     parser.add_argument("--alt", default=DEFAULT_ALT, help="the ALT rule: transition (A>G, G>A, C>T, T>C), transversion (A>C, C>A, G>T, "
                         "T>G) or complement (A>T, T>A, C>G, G>C)")
+    parser.add_argument("--indel", default=None, help="del<d> or dup<s>, d, s in 1 .. 255: the lists of --spikeScanIndel - a deletion of the "
+                        "d letters behind every locus, or a tandem duplication of the next s - for --spikeIndelReps; --alt is not read")
     parser.add_argument("--outPrefix", default=None, required=True, help="prefix of the files written")
     return parser
 

@@ -810,10 +810,15 @@ class RunOnDevice:
             b.free()
 
 
-def upload_run(eng, A, run_ref: str) -> RunOnDevice:
+def _up8(eng, a: np.ndarray):
+    """A DevBuf of its own that holds the bytes of the contiguous array `a` (four zero bytes for an empty one)."""
     from .engine import DevBuf
+    return DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
+
+
+def upload_run(eng, A, run_ref: str) -> RunOnDevice:
     nl = A["nl"]
-    up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
+    up = functools.partial(_up8, eng)
     d_ref = up(np.frombuffer(run_ref[:nl].encode().ljust(nl, b"\0"), np.uint8).copy())
     # (the windows size the sort and the launch grids: read on the host)
     return RunOnDevice(up(A["aln"]), up(A["cig"]), up(A["bq"]), up(A["loc"]), d_ref, len(A["aln"]), np.ascontiguousarray(A["loc"]))
@@ -1306,6 +1311,19 @@ def af_run_variants(variants, chrom: str, lo: int, fasta):
     return var, np.frombuffer(bytes(pool) or b"\0", np.uint8).copy()
 
 
+def _listed_spans(variants, order):
+    """Listed variants cut into the spans that are decoded as one run each: from the first not yet taken (`order`: the indexes into
+    `variants` by chromosome and position) those of its chromosome less than AF_RUN_LOCI positions on -> a generator of (chrom, lo, hi,
+    the span's indexes).  The caller answers each with send(n), the variants its run holds - one cut short: the rest starts the next."""
+    i = 0
+    while i < len(order):
+        v0, j = variants[order[i]], i
+        while j + 1 < len(order) and variants[order[j + 1]].chrom == v0.chrom and variants[order[j + 1]].pos - v0.pos < AF_RUN_LOCI:
+            j += 1
+        i += yield v0.chrom, v0.pos - 1, variants[order[j]].pos, order[i:j + 1]
+        yield                                          # (what send() returns; the loop's next step resumes here)
+
+
 def allele_carriers_run(eng, up: RunOnDevice, A, lo: int, var: np.ndarray, ins: np.ndarray, counts: bool = False):
     """smc_allele_carriers over the run `up` (A: its counts) -> (covers, carries: bool [n_var, n_bc] by run-wide barcode id; the
     (reads, alt) counters uint32 [n_var, n_bc, 2] when `counts`, else None)."""
@@ -1351,23 +1369,18 @@ def ds_af_sets(path: str, fasta, variants, params, eng, nthreads: int = 0, max_r
         _AF_TIMES[k] = 0.0
     bam = bamio.NativeBam(path)
     try:
-        i = 0
-        while i < len(order):
-            v0 = variants[order[i]]
-            j = i
-            while j + 1 < len(order) and variants[order[j + 1]].chrom == v0.chrom and variants[order[j + 1]].pos - v0.pos < AF_RUN_LOCI:
-                j += 1
-            lo, hi = v0.pos - 1, variants[order[j]].pos
+        spans = _listed_spans(variants, order)
+        for chrom, lo, hi, span in spans:
             t0 = time.perf_counter()
             own = bamio.NativeBam(path) if keep is not None else None
-            A = (own or bam).alignments_run(v0.chrom, lo, hi, max_reads, params, nthreads)
+            A = (own or bam).alignments_run(chrom, lo, hi, max_reads, params, nthreads)
             t1 = time.perf_counter()
             nl = int(A["nl"])
             if nl < 1:
-                raise bamio.BamError("--dsAF: the run %s:%d-%d of the pre-pass could not be decoded" % (v0.chrom, lo + 1, hi))
-            group = [k for k in order[i:j + 1] if variants[k].pos - 1 - lo < nl]     # (a run the decoder cut short: the rest starts the next)
-            var, ins = af_run_variants([variants[k] for k in group], v0.chrom, lo, fasta)
-            run_ref = fasta.fetch(v0.chrom, lo, lo + nl).upper()
+                raise bamio.BamError("--dsAF: the run %s:%d-%d of the pre-pass could not be decoded" % (chrom, lo + 1, hi))
+            group = [k for k in span if variants[k].pos - 1 - lo < nl]
+            var, ins = af_run_variants([variants[k] for k in group], chrom, lo, fasta)
+            run_ref = fasta.fetch(chrom, lo, lo + nl).upper()
             up = upload_run(eng, A, run_ref)
             t2 = time.perf_counter()
             held = False
@@ -1377,7 +1390,7 @@ def ds_af_sets(path: str, fasta, variants, params, eng, nthreads: int = 0, max_r
                 if keep is not None:
                     size = sum(int(A[x].nbytes) for x in ("aln", "cig", "bq", "loc"))
                     held = size + sum(r.nbytes for r in keep) <= (AF_KEEP_BYTES if keep_bytes is None else keep_bytes)
-                    keep.append(AfRun(v0.chrom, lo, hi, list(group), nl, size if held else 0, own if held else None, A if held else None,
+                    keep.append(AfRun(chrom, lo, hi, list(group), nl, size if held else 0, own if held else None, A if held else None,
                                       up if held else None, run_ref if held else None, idents if held else None))
             finally:
                 if not held:
@@ -1388,7 +1401,7 @@ def ds_af_sets(path: str, fasta, variants, params, eng, nthreads: int = 0, max_r
                 covers[k], carries[k] = idents[cov[r][:len(idents)]], idents[car[r][:len(idents)]]
             t3 = time.perf_counter()
             _AF_TIMES["decode"] += t1 - t0; _AF_TIMES["upload"] += t2 - t1; _AF_TIMES["kernel + download"] += t3 - t2
-            i += len(group)
+            spans.send(len(group))
     finally:
         bam.close()
     return covers, carries
@@ -1492,20 +1505,28 @@ class SpikeSet(object):
         return var if bool(((var["pos0"] >= lo) & (var["pos0"] < hi)).any()) else var[:0]
 
 
+def _spike_inputs(eng, who: str, up: RunOnDevice, A, var, dtype, idents, nm, n_indel, copies=None):
+    """What the four rewrite wrappers start with: the records as `dtype` and the identities of the run's barcodes, both contiguous, and
+    these two, NM and the indel lengths per alignment in HBM -> (var, idents, the four DevBufs: free them).  ValueError naming `who`:
+    NM or the indel lengths of fewer alignments than the run's or, with copies = (seeds, thresholds), not one threshold per seed."""
+    n = up.n_aln
+    if len(nm) < n or len(n_indel) < n or (copies is not None and len(copies[1]) != len(copies[0])):
+        raise ValueError("%s: %d alignments, NM of %d" % (who, n, len(nm)) +
+                         ("; %d seeds, %d thresholds" % (len(copies[0]), len(copies[1])) if copies is not None else ""))
+    var = np.ascontiguousarray(var, dtype)
+    idents = np.ascontiguousarray(idents, np.uint64)[:int(A["n_bc"])]
+    return var, idents, [_up8(eng, a) for a in (var, idents, np.ascontiguousarray(nm, np.int32), np.ascontiguousarray(n_indel, np.int32))]
+
+
 def spike_run(eng, up: RunOnDevice, A, var: np.ndarray, idents, seed: int, mismatch_thr: float, nm, n_indel):
     """smc_spike_alleles over the run `up` (A: its host arrays) -> (RunOnDevice whose aln and bq are the spiked copies - cig, loc and
     ref are the run's own: free the two copies only -, uint32 [n_var, 2]: records rewritten / NM increments per variant)."""
     from .engine import DevBuf
-    n, n_pairs, n_var, n_bc = up.n_aln, len(A["bq"]) // 2, len(var), int(A["n_bc"])
-    var = np.ascontiguousarray(var, abi.SPIKE_VARIANT_DTYPE)
-    up8 = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
-    idents = np.ascontiguousarray(idents, np.uint64)[:n_bc]
-    tmp = [up8(var), up8(idents), up8(np.ascontiguousarray(nm, np.int32)), up8(np.ascontiguousarray(n_indel, np.int32)),
-           DevBuf(eng, 8 * max(1, n_var) + 256)]
+    n, n_pairs, n_var = up.n_aln, len(A["bq"]) // 2, len(var)
+    var, idents, tmp = _spike_inputs(eng, "spike_run", up, A, var, abi.SPIKE_VARIANT_DTYPE, idents, nm, n_indel)
+    tmp.append(DevBuf(eng, 8 * max(1, n_var) + 256))
     d_aln, d_bq = DevBuf(eng, 36 * max(1, n) + 256), DevBuf(eng, 2 * max(1, n_pairs) + 256)
     try:
-        if len(nm) < n or len(n_indel) < n:
-            raise ValueError("spike_run: %d alignments, NM of %d" % (n, len(nm)))
         _lib.check(eng.L.smc_spike_alleles(eng.ctx, up.aln.data_ptr(), n, up.cig.data_ptr(), up.bq.data_ptr(), n_pairs, tmp[0].data_ptr(),
                                            var.ctypes.data, n_var, tmp[1].data_ptr(), len(idents), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
                                            float(mismatch_thr), tmp[2].data_ptr(), tmp[3].data_ptr(), d_aln.data_ptr(), d_bq.data_ptr(),
@@ -1571,6 +1592,16 @@ def spike_indel_limits(A, var):
     return int(bad[0]) if len(bad) else None
 
 
+def _refuse_indel_limits(A, var, flag: str, chrom: str) -> None:
+    """ValueError naming `flag`, before anything is spiked: run `A` of `chrom` has a record at which spike_indel_limits' limits could bind."""
+    bad = spike_indel_limits(A, var)
+    if bad is not None:
+        a = A["aln"][bad]
+        raise ValueError("%s: the record at %s:%d (l_seq %d, %d CIGAR operations) spans listed indels that could take l_seq or the CIGAR "
+                         "beyond 65535: whether it takes one would depend on the draws of the others" %
+                         (flag, chrom, int(a["pos"]) + 1, int(a["l_seq"]), int(a["n_cig"])))
+
+
 def spike_indel_touch(eng, up: RunOnDevice, A, var: np.ndarray) -> np.ndarray:
     """smc_spike_indel_touch over the run `up` (A: its host arrays) -> uint32 [n_var, n_bc]: per record of `var` and run-wide barcode
     id the records that take the insertion / deletion when the barcode is spiked (0 throughout for an SNV)."""
@@ -1595,18 +1626,14 @@ def spike_indel_run(eng, up: RunOnDevice, A, var: np.ndarray, ins: np.ndarray, i
     ref are the run's own: free the three copies only -, uint32 [n_var, 2] statistics, uint64 [3] totals, NM' and n_indel' per
     alignment).  `caps`: (cap_pairs, cap_cig), spike_indel_caps' bounds without it.  SmcError when the copy did not fit them."""
     from .engine import DevBuf
-    n, n_pairs, n_cw, n_var, n_bc = up.n_aln, len(A["bq"]) // 2, len(A["cig"]), len(var), int(A["n_bc"])
-    var = np.ascontiguousarray(var, abi.SPIKE_INDEL_VARIANT_DTYPE)
+    n, n_pairs, n_cw, n_var = up.n_aln, len(A["bq"]) // 2, len(A["cig"]), len(var)
+    var, idents, tmp = _spike_inputs(eng, "spike_indel_run", up, A, var, abi.SPIKE_INDEL_VARIANT_DTYPE, idents, nm, n_indel)
     cap_pairs, cap_cig = caps if caps is not None else spike_indel_caps(A, var)
-    up8 = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
-    idents = np.ascontiguousarray(idents, np.uint64)[:n_bc]
     ins = np.ascontiguousarray(ins, np.uint8)
-    tmp = [up8(var), up8(idents), up8(np.ascontiguousarray(nm, np.int32)), up8(np.ascontiguousarray(n_indel, np.int32)), up8(ins),
-           DevBuf(eng, 8 * max(1, n_var) + 256), DevBuf(eng, 24 + 256), DevBuf(eng, 4 * max(1, n) + 256), DevBuf(eng, 4 * max(1, n) + 256)]
+    tmp += [_up8(eng, ins), DevBuf(eng, 8 * max(1, n_var) + 256), DevBuf(eng, 24 + 256), DevBuf(eng, 4 * max(1, n) + 256),
+            DevBuf(eng, 4 * max(1, n) + 256)]
     d_aln, d_bq, d_cig = DevBuf(eng, 36 * max(1, n) + 256), DevBuf(eng, 2 * max(1, cap_pairs) + 256), DevBuf(eng, 4 * max(1, cap_cig) + 256)
     try:
-        if len(nm) < n or len(n_indel) < n:
-            raise ValueError("spike_indel_run: %d alignments, NM of %d" % (n, len(nm)))
         _lib.check(eng.L.smc_spike_indels(eng.ctx, up.aln.data_ptr(), n, up.cig.data_ptr(), n_cw, up.bq.data_ptr(), n_pairs, tmp[0].data_ptr(),
                                           var.ctypes.data, n_var, tmp[4].data_ptr(), len(ins), tmp[1].data_ptr(), len(idents),
                                           ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), float(mismatch_thr), tmp[2].data_ptr(),
@@ -1846,35 +1873,25 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
     order = sorted(range(len(variants)), key=lambda k: (variants[k].chrom, variants[k].pos))
     bam = bamio.NativeBam(path)
     try:
-        i = 0
-        while i < len(order):
-            v0 = variants[order[i]]
-            j = i
-            while j + 1 < len(order) and variants[order[j + 1]].chrom == v0.chrom and variants[order[j + 1]].pos - v0.pos < AF_RUN_LOCI:
-                j += 1
-            lo, hi = v0.pos - 1, variants[order[j]].pos
+        spans = _listed_spans(variants, order)
+        for chrom, lo, hi, span in spans:
             own = bamio.NativeBam(path) if keep is not None else None
             dec = own or bam
             held = False
             up = read_masks = None                     # (--spikeRpb: read_masks, _run_read_masks' of this run while the second count needs them)
             try:
-                A = dec.alignments_run(v0.chrom, lo, hi, max_reads, P, nthreads)
+                A = dec.alignments_run(chrom, lo, hi, max_reads, P, nthreads)
                 nl = int(A["nl"])
                 if nl < 1:
-                    raise bamio.BamError("--spikeAF: the run %s:%d-%d of the pre-pass could not be decoded" % (v0.chrom, lo + 1, hi))
-                group = [k for k in order[i:j + 1] if variants[k].pos - 1 - lo < nl]
-                var, ins = af_run_variants([variants[k] for k in group], v0.chrom, lo, fasta)
+                    raise bamio.BamError("--spikeAF: the run %s:%d-%d of the pre-pass could not be decoded" % (chrom, lo + 1, hi))
+                group = [k for k in span if variants[k].pos - 1 - lo < nl]
+                var, ins = af_run_variants([variants[k] for k in group], chrom, lo, fasta)
                 if indel_counters:
-                    bad = spike_indel_limits(A, spikes.chrom_variants(v0.chrom, 0.5)[0])
-                    if bad is not None:
-                        a = A["aln"][bad]
-                        raise ValueError("%s: the record at %s:%d (l_seq %d, %d CIGAR operations) spans listed "
-                                         "indels that could take l_seq or the CIGAR beyond 65535: whether it takes one would depend on the "
-                                         "draws of the others" % (rpb_flag if rpb is not None else "--spikeIndelReps / --spikeIndelDepth",
-                                                                  v0.chrom, int(a["pos"]) + 1, int(a["l_seq"]), int(a["n_cig"])))
+                    _refuse_indel_limits(A, spikes.chrom_variants(chrom, 0.5)[0],
+                                         rpb_flag if rpb is not None else "--spikeIndelReps / --spikeIndelDepth", chrom)
                 idents = dec.barcode_idents(A["n_bc"])
                 nm, n_indel = dec.run_mismatches(len(A["aln"]))
-                run_ref = fasta.fetch(v0.chrom, lo, lo + nl).upper()
+                run_ref = fasta.fetch(chrom, lo, lo + nl).upper()
                 up = upload_run(eng, A, run_ref)
                 cov, car, cnt0 = allele_carriers_run(eng, up, A, lo, var, ins, counts=want_counters)
                 for f, frac in enumerate(fracs):
@@ -1888,8 +1905,8 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                         for t in range(len(targets)):
                             second[(k, t, f)] = [None, int(car_f[r].sum()), None]
                 if rpb is not None:
-                    p_idents = pair_idents_or_refuse(dec, A, rpb_flag, v0.chrom, lo, nl)
-                    read_masks = _run_read_masks(eng, read_rules[0].groups, read_rules, p_idents, v0.chrom, lo, nl)
+                    p_idents = pair_idents_or_refuse(dec, A, rpb_flag, chrom, lo, nl)
+                    read_masks = _run_read_masks(eng, read_rules[0].groups, read_rules, p_idents, chrom, lo, nl)
 
                 def read_selected(run, r):
                     # (the cells' second count: the read selection at r over `run`, then smc_allele_carriers on it -> (N', carriers) per variant)
@@ -1914,8 +1931,8 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                         if who is not None:
                             rbits[(k, r)] = [who[x][1], [None] * len(targets)]
                 for t, target in enumerate(targets):
-                    svar, sorder = spikes.chrom_variants(v0.chrom, target)
-                    spiked, stats = spike_copy(eng, up, A, spikes, v0.chrom, svar, idents, seed, P.mismatchThr, nm, n_indel)
+                    svar, sorder = spikes.chrom_variants(chrom, target)
+                    spiked, stats = spike_copy(eng, up, A, spikes, chrom, svar, idents, seed, P.mismatchThr, nm, n_indel)
                     try:
                         cov1, car1, cnt1 = allele_carriers_run(eng, spiked, A, lo, var, ins, counts=True)
                         for r in range(len(read_rules or ())):
@@ -1958,7 +1975,7 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                         rows[t][k] = dict(N=int(cov[r].sum()), V0=int(car[r].sum()), S=int((hit[:cov.shape[1]] & cov[r]).sum()), READS=reads,
                                           V1=int(car1[r].sum()))
                 if want_counters:
-                    svar, sorder, covers_g, counters_g = _spike_single_counters(eng, up, A, lo, spikes, v0.chrom, group, var, ins, idents, seed, P,
+                    svar, sorder, covers_g, counters_g = _spike_single_counters(eng, up, A, lo, spikes, chrom, group, var, ins, idents, seed, P,
                                                                                 nm, n_indel, cov, cnt0, indel_counters)
                     for r, k in enumerate(group):
                         covers[k], counters[k] = covers_g[r], counters_g[r]
@@ -1970,10 +1987,10 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                     if indel_counters:
                         # (--spikeIndelRpb: the group's records of the chromosome's list - ascending, as the group is; the inserted
                         # letters stay where the chromosome's pool has them)
-                        read_bits = spike_indel_read_bits(eng, up, A, lo, svar[[sorder.index(k) for k in group]], spikes.ins[v0.chrom])
+                        read_bits = spike_indel_read_bits(eng, up, A, lo, svar[[sorder.index(k) for k in group]], spikes.ins[chrom])
                     else:
                         read_bits = spike_read_bits(eng, up, A, lo, var)
-                    first = run_first_names(eng, read_rules[0].groups, p_idents, v0.chrom, lo, nl)
+                    first = run_first_names(eng, read_rules[0].groups, p_idents, chrom, lo, nl)
                     shifts = (1, 2, 3) if indel_counters else (1, 2)
                     for r, k in enumerate(group):
                         gids = np.flatnonzero(cov[r][:len(idents)])
@@ -1987,7 +2004,7 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                 if keep is not None:
                     size = sum(int(A[x].nbytes) for x in ("aln", "cig", "bq", "loc"))
                     held = size + sum(r.nbytes for r in keep["runs"]) <= (AF_KEEP_BYTES if keep_bytes is None else keep_bytes)
-                    keep["runs"].append(AfRun(v0.chrom, lo, hi, list(group), nl, size if held else 0, own if held else None,
+                    keep["runs"].append(AfRun(chrom, lo, hi, list(group), nl, size if held else 0, own if held else None,
                                               A if held else None, up if held else None, run_ref if held else None,
                                               idents if held else None, (nm, n_indel) if held else None))
             except BaseException:
@@ -2002,7 +2019,7 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                         up.free()
                     if own is not None:
                         own.close()
-            i += len(group)
+            spans.send(len(group))
     finally:
         bam.close()
     rules = [DsRule(1.0, Pt, seed=int(seed), af=float(t), spike=spikes) for t, Pt in zip(targets, params_list)]
@@ -2120,6 +2137,22 @@ class AfRun:
     idents: object = None
     mism: object = None         # (--spikeReps) the alignments' (NM, inserted plus deleted length), as the decoder gives them
 
+    def load(self, path: str, fasta, eng, params, max_reads: int, nthreads: int, mism: bool = False) -> int:
+        """Decode the run with a handle of its own, upload it and fill the fields above (`mism`: that one too) -> the loci the decoder
+        gave.  Fewer than one, or not the `nl` this run already has (the pre-pass's): nothing but the decode is done and the caller
+        refuses; a run without `nl` gets the decoder's.  free() takes back whatever a load that failed has made."""
+        self.bam = bamio.NativeBam(path)
+        self.A = self.bam.alignments_run(self.chrom, self.lo, self.hi, max_reads, params, nthreads or bamio.host_threads())
+        nl = int(self.A["nl"])
+        if nl < 1 or self.nl not in (0, nl):
+            return nl
+        self.nl = nl
+        self.run_ref = fasta.fetch(self.chrom, self.lo, self.lo + nl).upper()
+        self.up = upload_run(eng, self.A, self.run_ref)
+        self.idents = self.bam.barcode_idents(self.A["n_bc"])
+        self.mism = self.bam.run_mismatches(len(self.A["aln"])) if mism else None
+        return nl
+
     def free(self):
         if self.up is not None:
             self.up.free()
@@ -2139,7 +2172,6 @@ class AfCellTable(object):
     memory: they travel by value) - the results then have one dimension more, the fractions', behind the targets'."""
 
     def __init__(self, eng, idents, thr, seeds, depth_thr=None):
-        from .engine import DevBuf
         self.eng = eng
         self.idents = np.ascontiguousarray(idents, np.uint64)
         self.thr = np.ascontiguousarray(thr, np.uint64)              # [carriers, targets]
@@ -2149,8 +2181,7 @@ class AfCellTable(object):
         self.n_targets = int(self.thr.shape[1])
         self.depth_thr = None if depth_thr is None else np.ascontiguousarray(depth_thr, np.uint64)
         self.n_fracs = None if depth_thr is None else len(self.depth_thr)
-        up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.reshape(-1) if a.size else np.zeros(1, a.dtype))
-        self.d_idents, self.d_thr, self.d_seeds = up(self.idents), up(self.thr), up(self.seeds)
+        self.d_idents, self.d_thr, self.d_seeds = _up8(eng, self.idents), _up8(eng, self.thr), _up8(eng, self.seeds)
 
     def _call(self, kind: str, head: tuple, tail: tuple, depth):
         """smc_af_rep_<kind> or, with `depth` thresholds, smc_af_depth_<kind>: `head`, the table (the thresholds behind the targets),
@@ -2183,8 +2214,7 @@ class AfCellTable(object):
         carry = np.concatenate([np.isin(c, np.asarray(k, np.uint64)) for c, k in zip(covers, carries)]).astype(np.uint8) if covers \
             else np.zeros(0, np.uint8)
         n_out = int(np.prod(shape))
-        up = lambda a: DevBuf(self.eng, a.nbytes + 256).upload(a if a.size else np.zeros(1, a.dtype))
-        bufs = [up(ident), up(carry), up(off), DevBuf(self.eng, 4 * max(1, n_out) + 256)]
+        bufs = [_up8(self.eng, a) for a in (ident, carry, off)] + [DevBuf(self.eng, 4 * max(1, n_out) + 256)]
         try:
             self._call("counts", (bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), off.ctypes.data, len(covers)),
                        (bufs[3].data_ptr(),), depth)
@@ -2280,7 +2310,7 @@ def _copy_rows(eng, run: AfRun, variants, n_copies: int, kept_runs, P, bits, fla
         d.free()
 
 
-def _af_rep_call(eng, run: AfRun, table: AfRepTable, d_masks, n_words, todo, P, fasta, variants, max_depth, sampler, sampler_seed, bits):
+def _af_rep_call(eng, run: AfRun, table: AfCellTable, d_masks, n_words, todo, P, fasta, variants, max_depth, sampler, sampler_seed, bits):
     """The builds of `todo` - indexes of masks in `d_masks`, all of one cell (a target, or with --dsAFDepth a target x fraction: the
     params `P` are that cell's) - of a kept run appended to one device batch (_build_copies) and the batch called with one plan ->
     (per mask index the listed loci's raw rows, in the order of run.group), or NARROW (a build has no room in 16-bit read words)."""
@@ -2328,14 +2358,10 @@ def ds_af_replicates(path: str, fasta, variants, targets, params_list, seed: int
             if run.A is None:
                 # (over the byte cap of the pre-pass: decoded and uploaded again)
                 t0 = time.perf_counter()
-                run.bam = bamio.NativeBam(path)
-                run.A = run.bam.alignments_run(run.chrom, run.lo, run.hi, max_reads, params_list[0], nthreads or bamio.host_threads())
-                if int(run.A["nl"]) != run.nl:
+                nl = run.load(path, fasta, eng, params_list[0], max_reads, nthreads)
+                if nl != run.nl:
                     raise bamio.BamError("--dsAFReps: the run %s:%d-%d was decoded as %d loci, the pre-pass had %d" %
-                                         (run.chrom, run.lo + 1, run.hi, int(run.A["nl"]), run.nl))
-                run.run_ref = fasta.fetch(run.chrom, run.lo, run.lo + run.nl).upper()
-                run.up = upload_run(eng, run.A, run.run_ref)
-                run.idents = run.bam.barcode_idents(run.A["n_bc"])
+                                         (run.chrom, run.lo + 1, run.hi, nl, run.nl))
                 times["decode again"] += time.perf_counter() - t0
             n_bc = int(run.A["n_bc"])
             n_words = mask_words(n_bc)
@@ -2393,8 +2419,7 @@ def _spike_counts_call(eng, name: str, arrays, shape, call) -> np.ndarray:
     `name` on the default stream, the uint32 counters of `shape` come down, and everything is freed."""
     from .engine import DevBuf
     n_out = int(np.prod(shape))
-    up = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.reshape(-1) if a.size else np.zeros(1, a.dtype))
-    bufs = [up(a) for a in arrays] + [DevBuf(eng, 4 * max(1, n_out) + 256)]
+    bufs = [_up8(eng, a) for a in arrays] + [DevBuf(eng, 4 * max(1, n_out) + 256)]
     try:
         _lib.check(call([b.data_ptr() for b in bufs[:-1]], bufs[-1].data_ptr()), name)
         out = bufs[-1].download(np.uint32, n_out) if n_out else np.zeros(0, np.uint32)         # (the default stream: behind the kernel)
@@ -2704,18 +2729,13 @@ def spike_run_copies(eng, up: RunOnDevice, A, var: np.ndarray, idents, seeds, th
     pair pools - two DevBufs, copy c at c x stride: free both -, (record stride, pool stride) in bytes, uint32 [copies, n_var, 2]
     statistics).  `strides`: other than spike_copy_strides'; `fill`: a byte both outputs are filled with first (tests)."""
     from .engine import DevBuf
-    n, n_pairs, n_var, n_bc, B = up.n_aln, len(A["bq"]) // 2, len(var), int(A["n_bc"]), len(seeds)
+    n, n_pairs, n_var, B = up.n_aln, len(A["bq"]) // 2, len(var), len(seeds)
     sa, sb = strides or spike_copy_strides(n, n_pairs)
-    var = np.ascontiguousarray(var, abi.SPIKE_VARIANT_DTYPE)
     seeds, thr = np.ascontiguousarray(seeds, np.uint64), np.ascontiguousarray(thresholds, np.uint64)
-    up8 = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
-    idents = np.ascontiguousarray(idents, np.uint64)[:n_bc]
-    tmp = [up8(var), up8(idents), up8(np.ascontiguousarray(nm, np.int32)), up8(np.ascontiguousarray(n_indel, np.int32)),
-           DevBuf(eng, 8 * max(1, n_var * B) + 256)]
+    var, idents, tmp = _spike_inputs(eng, "spike_run_copies", up, A, var, abi.SPIKE_VARIANT_DTYPE, idents, nm, n_indel, (seeds, thr))
+    tmp.append(DevBuf(eng, 8 * max(1, n_var * B) + 256))
     d_aln, d_bq = DevBuf(eng, sa * max(1, B) + 256), DevBuf(eng, sb * max(1, B) + 256)
     try:
-        if len(nm) < n or len(n_indel) < n or len(thr) != B:
-            raise ValueError("spike_run_copies: %d alignments, NM of %d; %d seeds, %d thresholds" % (n, len(nm), B, len(thr)))
         if fill is not None:
             d_aln.upload(np.full(sa * max(1, B), fill, np.uint8)); d_bq.upload(np.full(sb * max(1, B), fill, np.uint8))
         _lib.check(eng.L.smc_spike_alleles_reps(eng.ctx, up.aln.data_ptr(), n, up.cig.data_ptr(), up.bq.data_ptr(), n_pairs, tmp[0].data_ptr(),
@@ -2762,22 +2782,17 @@ def spike_indel_run_copies(eng, up: RunOnDevice, A, var: np.ndarray, ins: np.nda
     spike_indel_caps' bounds without it; `strides`: other than spike_indel_copy_strides'; `fill`: a byte the three outputs are
     filled with first (tests).  One download of all totals; SmcError when a copy did not fit spike_indel_caps' bounds."""
     from .engine import DevBuf
-    n, n_pairs, n_cw, n_var, n_bc, B = up.n_aln, len(A["bq"]) // 2, len(A["cig"]), len(var), int(A["n_bc"]), len(seeds)
-    var = np.ascontiguousarray(var, abi.SPIKE_INDEL_VARIANT_DTYPE)
+    n, n_pairs, n_cw, n_var, B = up.n_aln, len(A["bq"]) // 2, len(A["cig"]), len(var), len(seeds)
+    seeds, thr = np.ascontiguousarray(seeds, np.uint64), np.ascontiguousarray(thresholds, np.uint64)
+    var, idents, tmp = _spike_inputs(eng, "spike_indel_run_copies", up, A, var, abi.SPIKE_INDEL_VARIANT_DTYPE, idents, nm, n_indel, (seeds, thr))
     cap_pairs, cap_cig = caps if caps is not None else spike_indel_caps(A, var)
     sa, sb, sc = strides or spike_indel_copy_strides(n, cap_pairs, cap_cig)
-    seeds, thr = np.ascontiguousarray(seeds, np.uint64), np.ascontiguousarray(thresholds, np.uint64)
-    up8 = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
-    idents = np.ascontiguousarray(idents, np.uint64)[:n_bc]
     ins = np.ascontiguousarray(ins, np.uint8)
     nB = max(1, B)
-    tmp = [up8(var), up8(idents), up8(np.ascontiguousarray(nm, np.int32)), up8(np.ascontiguousarray(n_indel, np.int32)), up8(ins),
-           DevBuf(eng, 8 * max(1, n_var) * nB + 256), DevBuf(eng, 24 * nB + 256), DevBuf(eng, 4 * max(1, n) * nB + 256),
-           DevBuf(eng, 4 * max(1, n) * nB + 256)]
+    tmp += [_up8(eng, ins), DevBuf(eng, 8 * max(1, n_var) * nB + 256), DevBuf(eng, 24 * nB + 256), DevBuf(eng, 4 * max(1, n) * nB + 256),
+            DevBuf(eng, 4 * max(1, n) * nB + 256)]
     out = [DevBuf(eng, sa * nB + 256), DevBuf(eng, sb * nB + 256), DevBuf(eng, sc * nB + 256)]
     try:
-        if len(nm) < n or len(n_indel) < n or len(thr) != B:
-            raise ValueError("spike_indel_run_copies: %d alignments, NM of %d; %d seeds, %d thresholds" % (n, len(nm), B, len(thr)))
         if fill is not None:
             for b, st in zip(out, (sa, sb, sc)):
                 b.upload(np.full(st * nB, fill, np.uint8))
@@ -2806,73 +2821,117 @@ def spike_indel_run_copies(eng, up: RunOnDevice, A, var: np.ndarray, ins: np.nda
                 n_indel=n_indel_out)
 
 
+class _SpikedCopies(object):
+    """The spiked copies of the kept run `run` at one threshold, copy c with seeds[c], from one spike_run_copies call or, with `ins` (the
+    chromosome's pool of inserted letters; `caps`: spike_indel_run_copies'), one spike_indel_run_copies call, whose buffers this owns
+    until free().  runs[c]: copy c as a RunOnDevice - records and pair pool at c x their strides, the run's CIGAR pool or an indel copy's
+    own at c x its stride with pairs_used from totals[c, 0], the run's loc and ref.  stats, strides, caps, totals: the call's."""
+
+    def __init__(self, eng, run: AfRun, svar, seeds, thr: int, P, ins=None, caps=None):
+        up, B = run.up, len(seeds)
+        self.eng, self.run, self.seeds = eng, run, seeds
+        args = (run.idents, seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
+        if ins is None:
+            aln, bq, self.strides, self.stats = spike_run_copies(eng, up, run.A, svar, *args)
+            self.owned, self.caps, self.totals = [aln, bq], None, None
+            cig, pairs = [up.cig] * B, [None] * B
+        else:
+            made = spike_indel_run_copies(eng, up, run.A, svar, ins, *args, caps=caps)
+            aln, bq, self.strides, self.stats, self.caps, self.totals = (made[x] for x in ("aln", "bq", "strides", "stats", "caps", "totals"))
+            self.owned = [aln, bq, made["cig"]]
+            cig, pairs = [_BufView(made["cig"], c * self.strides[2]) for c in range(B)], [int(x) for x in self.totals[:, 0]]
+        self.runs = [RunOnDevice(_BufView(aln, c * self.strides[0]), cig[c], _BufView(bq, c * self.strides[1]), up.loc, up.ref, up.n_aln,
+                                 up.loc_host, pairs_used=pairs[c]) for c in range(B)]
+
+    def addresses(self) -> dict:
+        """scan_detect_keys' `copies` (indel copies)."""
+        aln, bq, cig = (b.data_ptr() for b in self.owned)
+        return dict(aln=aln, cig=cig, bq=bq, strides=self.strides, n_aln=self.run.up.n_aln, cap_pairs=self.caps[0])
+
+    def check_reads(self, var_at, want_reads, variants, flag: str) -> None:
+        """The rewrite's READS of every copy and variant of run.group (var_at[g]: where run.group[g] stands in the records) against the
+        counts call's want_reads[c][g].  A difference raises RuntimeError naming `flag`."""
+        for c, seed in enumerate(self.seeds):
+            for g, k in enumerate(self.run.group):
+                if int(self.stats[c, var_at[g], 0]) != int(want_reads[c][g]):
+                    v = variants[k]
+                    raise RuntimeError("%s: seed %d at %s:%d: the rewrite touched %d records, the counts call says %d" %
+                                       (flag, int(seed), v.chrom, v.pos, int(self.stats[c, var_at[g], 0]), int(want_reads[c][g])))
+
+    def check_carriers(self, c: int, on: RunOnDevice, counts, want, var, ins, variants, flag: str, what: str = ""):
+        """(N, V1) of every variant of run.group (var, ins: af_run_variants' of them) by smc_allele_carriers on copy c or a selection of it
+        (`on`, `counts`) against the counts call's want[g] -> (covers, carries).  A difference: RuntimeError naming `flag` and the cell `what`."""
+        cov, car, _ = allele_carriers_run(self.eng, on, counts, self.run.lo, var, ins)
+        for g, k in enumerate(self.run.group):
+            mine, theirs = (int(cov[g].sum()), int(car[g].sum())), tuple(int(x) for x in want[g])
+            if mine != theirs:
+                v = variants[k]
+                raise RuntimeError("%s: seed %d at %s:%d%s: the copy holds (N, V1) = %r, the counts call says %r" %
+                                   (flag, int(self.seeds[c]), v.chrom, v.pos, what, mine, theirs))
+        return cov, car
+
+    def free(self):
+        for b in self.owned:
+            b.free()
+
+
+def _copy_room(run: AfRun, svar, four: bool):
+    """How many spiked copies of the kept run one rewrite call makes: as many as fit SPIKE_REP_BATCH_BYTES - a copy is its records and
+    pair pool or, with `four` counters, records, both pools at their capacities and the call's scratch of 8 bytes per alignment -,
+    AF_REP_BATCH_SLOTS read slots and SMC_SPIKE_MAX_COPIES, and at least one -> (copies, spike_indel_caps of `svar` on the run or None)."""
+    n, caps = run.up.n_aln, spike_indel_caps(run.A, svar) if four else None
+    per_copy = sum(spike_indel_copy_strides(n, *caps)) + 8 * n if four else sum(spike_copy_strides(n, len(run.A["bq"]) // 2))
+    return max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per_copy, AF_REP_BATCH_SLOTS // max(1, int(run.A["n_slots"]) + run.nl))), caps
+
+
 def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed, bits,
                     cells=(), indel: dict = None, read_cells: dict = None):
-    """`len(part_seeds)` spiked copies of a kept run at one target from one smc_spike_alleles_reps call, each built behind the other
-    into one device batch (as _af_rep_call appends its selections) and the batch called with one plan -> (per copy the listed loci's
-    raw rows, in the order of run.group), or NARROW.  var_at[g]: where variant run.group[g] stands in `svar`; want_reads[c][g]: the
-    counts call's READS of that copy and variant - the kernel's statistics must equal it.
+    """The _SpikedCopies of a kept run at one target, one per seed of `part_seeds`, each built behind the other into one device batch
+    (as _af_rep_call appends its selections) and the batch called with one plan -> (per copy the listed loci's raw rows, in the order
+    of run.group), or NARROW.  var_at, want_reads: check_reads'.
     `cells` (--spikeDepth: (fraction, params) of the target's cells): every copy is also selected at each fraction with its own seed
     (select_run's philox rule) and built; a cell's selections share one device batch and one plan of their own, called with that
     cell's params -> (the copies' rows, per cell the same), or NARROW.
-    `indel` (--spikeIndelReps: dict(ins: the chromosome's pool of inserted letters, want: per copy and variant of run.group the counts
-    call's (N, V1), want_cells: per cell the same (N', V1'))): the copies come from one smc_spike_indels_reps call, each with records,
-    CIGAR pool and pair pool of its own; a relocated record's allele texts come from the copy (copy_allele_key); and beside READS every
-    copy's N and V1 - smc_allele_carriers on the copy, on its selection for a cell - must equal the counts call's.
+    `indel` (--spikeIndelReps: dict(ins: _SpikedCopies', want: per copy and variant of run.group the counts call's (N, V1), want_cells:
+    per cell the same (N', V1'))): a relocated record's allele texts come from the copy (copy_allele_key); and beside READS every
+    copy's N and V1 - on the copy, on its selection for a cell - must equal the counts call's.
     `read_cells` (--spikeRpb: dict(params: the VcParams of the target's cells, one per reads-per-barcode target, masks: per copy the
     address of its first keep mask - ReadGroups.masks with the copy's seed, one mask per target -, n_words: words per mask)): every
     copy is also selected per r by read name (select_run, level "read") and built; a cell's selections share one batch and one plan
     -> (the copies' rows, per cell the same), or NARROW.  With `indel` (--spikeIndelRpb) want_cells holds the cells' (N', V1') per
     reads-per-barcode target, and `read_cells` their "targets" for the message."""
-    A, up, lo, chrom = run.A, run.up, run.lo, run.chrom
-    B = len(part_seeds)
-    if indel is None:
-        d_aln, d_bq, (sa, sb), stats = spike_run_copies(eng, up, A, svar, run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
-        copies = [RunOnDevice(d_aln.view(c * sa), up.cig, d_bq.view(c * sb), up.loc, up.ref, up.n_aln, up.loc_host) for c in range(B)]
-        owned = [d_aln, d_bq]
-    else:
-        made = spike_indel_run_copies(eng, up, A, svar, indel["ins"], run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
-        (sa, sb, sc), stats, owned = made["strides"], made["stats"], [made["aln"], made["bq"], made["cig"]]
-        copies = [RunOnDevice(_BufView(made["aln"], c * sa), _BufView(made["cig"], c * sc), _BufView(made["bq"], c * sb), up.loc, up.ref, up.n_aln,
-                              up.loc_host, pairs_used=int(made["totals"][c, 0])) for c in range(B)]
-        af_var, af_ins = af_run_variants([variants[k] for k in run.group], chrom, lo, fasta)
+    A, lo, B = run.A, run.lo, len(part_seeds)
+    if indel is not None:
+        af_var, af_ins = af_run_variants([variants[k] for k in run.group], run.chrom, lo, fasta)
     flag = (read_cells.get("flag") or ("--spikeIndelRpb" if indel is not None else "--spikeRpb")) if read_cells else \
         "--spikeDepth" if cells else "--spikeReps"
-
-    def check_carriers(c, kept, want, what, read=None):
-        """(N, V1) of every variant of the run on copy c (or its selection) by smc_allele_carriers against the counts call's.  With
-        indel["bits"] (--spikePhaseRpb) the cover and carrier bits of the sets' members on the selection at `read` are kept as
-        identities - kept.idents(): the identity of every barcode id of the selection -, key (variant, copy, read)."""
-        cov, car, _ = allele_carriers_run(eng, kept.run, kept.counts, lo, af_var, af_ins)
-        if read is not None and indel.get("bits") is not None:
-            ids = kept.idents()
-            for g, k in enumerate(run.group):
-                if k in indel["members"]:
-                    indel["bits"][(k, c, read)] = (ids[cov[g][:len(ids)]], ids[car[g][:len(ids)]])
-        for g, k in enumerate(run.group):
-            mine = (int(cov[g].sum()), int(car[g].sum()))
-            if mine != tuple(int(x) for x in want[g]):
-                v = variants[k]
-                raise RuntimeError("--spikeIndelReps: seed %d at %s:%d%s: the copy holds (N, V1) = %r, the counts call says %r" %
-                                   (int(part_seeds[c]), v.chrom, v.pos, what, mine, tuple(int(x) for x in want[g])))
+    copies = _SpikedCopies(eng, run, svar, part_seeds, thr, P, indel["ins"] if indel is not None else None)
 
     def kept_copies(frac, read):
         """The B copies (`frac` None) or their selections at `frac` - `read` r: by read name at the r-th reads-per-barcode target -, with
-        `indel` each checked against the counts call's (N, V1) before it is handed on."""
-        for c in range(B):
+        `indel` each checked against the counts call's (N, V1) before it is handed on.  With indel["bits"] (--spikePhaseRpb) the cover
+        and carrier bits of the sets' members on the selection at `read` are kept as identities - kept.idents(): the identity of every
+        barcode id of the selection -, key (variant, copy, read)."""
+        for c, copy in enumerate(copies.runs):
             if read is not None:
-                picked = select_run(eng, copies[c], A, lo, d_mask=read_cells["masks"][c] + 4 * read_cells["n_words"] * read, level="read")
+                picked = select_run(eng, copy, A, lo, d_mask=read_cells["masks"][c] + 4 * read_cells["n_words"] * read, level="read")
                 cell, what = read, " x target %g" % read_cells["targets"][read]
             elif frac is None:
-                picked, cell, what = (copies[c], A, None), None, ""
+                picked, cell, what = (copy, A, None), None, ""
             else:
-                picked = select_run(eng, copies[c], A, lo, idents=run.idents, frac=frac, seed=int(part_seeds[c]))
+                picked = select_run(eng, copy, A, lo, idents=run.idents, frac=frac, seed=int(part_seeds[c]))
                 cell, what = cell_at[frac], " x fraction %g" % frac
             kept = _KeptRun(*picked, A, run.bam.allele_key, run.bam.barcode_name, lambda n: run.idents,
-                            copy=copies[c] if indel is not None else None, by_read=read is not None)
+                            copy=copy if indel is not None else None, by_read=read is not None)
             if indel is not None:
                 try:
-                    check_carriers(c, kept, indel["want"][c] if cell is None else indel["want_cells"][cell][c], what, read)
+                    cov, car = copies.check_carriers(c, kept.run, kept.counts, indel["want"][c] if cell is None else indel["want_cells"][cell][c],
+                                                     af_var, af_ins, variants, "--spikeIndelReps", what)
+                    if read is not None and indel.get("bits") is not None:
+                        ids = kept.idents()
+                        for g, k in enumerate(run.group):
+                            if k in indel["members"]:
+                                indel["bits"][(k, c, read)] = (ids[cov[g][:len(ids)]], ids[car[g][:len(ids)]])
                 except BaseException:
                     kept.free()
                     raise
@@ -2883,12 +2942,7 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
         return _copy_rows(eng, run, variants, B, kept_copies(frac, read), Pb, bits, flag, fasta, max_depth, sampler, sampler_seed)
     cell_at = {frac: f for f, (frac, _) in enumerate(cells)}
     try:
-        for c in range(B):
-            for g, k in enumerate(run.group):
-                if int(stats[c, var_at[g], 0]) != int(want_reads[c][g]):
-                    v = variants[k]
-                    raise RuntimeError("--spikeReps: seed %d at %s:%d: the rewrite touched %d records, the counts call says %d" %
-                                       (int(part_seeds[c]), v.chrom, v.pos, int(stats[c, var_at[g], 0]), int(want_reads[c][g])))
+        copies.check_reads(var_at, want_reads, variants, "--spikeReps")      # (the message names --spikeReps whichever flag is in force)
         full = batch_rows(P, None)
         if full == NARROW or not (cells or read_cells):
             return full
@@ -2903,8 +2957,7 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
                 return NARROW
         return full, of_cell
     finally:
-        for b in owned:
-            b.free()
+        copies.free()
 
 
 def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int, n_reps: int, eng, keep: dict, sampler: str = "reference",
@@ -2912,9 +2965,8 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
                      rpb: dict = None):
     """The replicate stage of --spikeReps.  Replicate j is --spikeAF with seed (seed + j) mod 2^64.  One smc_spike_rep_counts call
     gives (S, READS, V1) of every variant, replicate and target from what the pre-pass kept (spike_rules' `keep`) - no spiked copy is
-    needed for them; then per kept run and target as many replicates as fit SPIKE_REP_BATCH_BYTES (and AF_REP_BATCH_SLOTS read
-    slots, and SMC_SPIKE_MAX_COPIES) are spiked by one smc_spike_alleles_reps call, built one behind the other and called with one
-    plan.  Every copy's statistics are checked against the counts call's READS.
+    needed for them; then per kept run and target as many replicates as _copy_room allows are spiked by one smc_spike_alleles_reps
+    call, built one behind the other and called with one plan.  Every copy's statistics are checked against the counts call's READS.
     -> dict(seeds, counts: uint32 [V, R, T, 3], rows: {(variant index, target index, replicate): the raw row string at the variant's
     locus}, times: seconds per part and the numbers of rewrite calls, builds and batches).
     `depth` (--spikeDepth: dict with "fracs" and the "params" of the T x F cells, targets outer): one smc_spike_depth_counts call gives
@@ -2980,24 +3032,14 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
             if run.A is None:
                 # (over the byte cap of the pre-pass: decoded and uploaded again)
                 t0 = time.perf_counter()
-                run.bam = bamio.NativeBam(path)
-                run.A = run.bam.alignments_run(run.chrom, run.lo, run.hi, max_reads, params_list[0], nthreads or bamio.host_threads())
-                if int(run.A["nl"]) != run.nl:
+                nl = run.load(path, fasta, eng, params_list[0], max_reads, nthreads, mism=True)
+                if nl != run.nl:
                     raise bamio.BamError("--spikeReps: the run %s:%d-%d was decoded as %d loci, the pre-pass had %d" %
-                                         (run.chrom, run.lo + 1, run.hi, int(run.A["nl"]), run.nl))
-                run.run_ref = fasta.fetch(run.chrom, run.lo, run.lo + run.nl).upper()
-                run.up = upload_run(eng, run.A, run.run_ref)
-                run.idents = run.bam.barcode_idents(run.A["n_bc"])
-                run.mism = run.bam.run_mismatches(len(run.A["aln"]))
+                                         (run.chrom, run.lo + 1, run.hi, nl, run.nl))
                 times["decode again"] += time.perf_counter() - t0
             svar, sorder = spikes.chrom_variants(run.chrom, targets[0])
             var_at = [sorder.index(k) for k in run.group]
-            if four:
-                # (a copy: records, both pools at their capacities, and the call's scratch of 8 bytes per alignment)
-                per_copy = sum(spike_indel_copy_strides(run.up.n_aln, *spike_indel_caps(run.A, svar))) + 8 * run.up.n_aln
-            else:
-                per_copy = sum(spike_copy_strides(run.up.n_aln, len(run.A["bq"]) // 2))
-            room = max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per_copy, AF_REP_BATCH_SLOTS // max(1, int(run.A["n_slots"]) + run.nl)))
+            room, _ = _copy_room(run, svar, four)
             t0 = time.perf_counter()
             seed_masks = {}
             try:
@@ -3127,8 +3169,7 @@ def scan_detect_keys(eng, d_rows, n_copies: int, n_loci: int, var, ins, copies: 
     ins = np.ascontiguousarray(ins, np.uint8)
     B, G = int(n_copies), len(var)
     n = B * G
-    up8 = lambda a: DevBuf(eng, a.nbytes + 256).upload(a.view(np.uint8).reshape(-1) if a.nbytes else np.zeros(4, np.uint8))
-    bufs = [up8(var), up8(ins), DevBuf(eng, 4 * max(1, n) + 256), DevBuf(eng, 16 * max(1, n) + 256), DevBuf(eng, 4 * max(1, n) + 256),
+    bufs = [_up8(eng, var), _up8(eng, ins), DevBuf(eng, 4 * max(1, n) + 256), DevBuf(eng, 16 * max(1, n) + 256), DevBuf(eng, 4 * max(1, n) + 256),
             DevBuf(eng, 256)]
     sa, sb, sc = copies["strides"]
     try:
@@ -3160,61 +3201,39 @@ def scan_called_host(text, v, threshold: int, repeats) -> bool:
 
 def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed,
                bits, threshold, repeats, check0, indel: dict = None):
-    """`len(part_seeds)` spiked copies of the run at one target from one smc_spike_alleles_reps call, each built behind the other into
-    one device batch and the batch called with one plan - _spike_rep_call's way - but the rows stay in HBM: smc_scan_detect gives a
-    verdict per (copy, listed locus), and only the rows it leaves to the host come down, one by one, to be printed and cut the
-    existing way.  run.group: the pass's variants of this run; listed: their abi.SCAN_LOCUS_DTYPE records; check0: the copy that is
-    replicate 0 (or None) - its listed rows come down as well, and a device verdict of CALLED or NOT that the host's decision does
-    not share ends the run.  -> (bool [copies, listed]: called, the number of verdicts the host decided), or NARROW.
-    `indel` (--spikeScanIndel: dict(ins: the chromosome's pool of inserted letters, var, var_ins: af_run_variants' records of
-    run.group - they stand where `listed` does -, want: per copy and variant the counts call's (N, V1))): the copies come from one
-    smc_spike_indels_reps call; every build leaves its extras list in HBM and makes no table (BuildExtras); smc_scan_detect_keys
-    resolves the key's allele id per copy from them; replicate 0's (N, V1) by smc_allele_carriers on the copy must be the counts
-    call's; and the table of a row that comes down is made from its copy's extras, the texts through copy_allele_key on the copy,
-    which is alive until this call returns."""
+    """The _SpikedCopies of the run at one target, one per seed of `part_seeds`, each built behind the other into one device batch and
+    the batch called with one plan - _spike_rep_call's way - but the rows stay in HBM: smc_scan_detect gives a verdict per (copy,
+    listed locus), and only the rows it leaves to the host come down, one by one, to be printed and cut the existing way.  run.group:
+    the pass's variants of this run; listed: their abi.SCAN_LOCUS_DTYPE records; check0: the copy that is replicate 0 (or None) - its
+    listed rows come down as well, and a device verdict of CALLED or NOT that the host's decision does not share ends the run.
+    -> (bool [copies, listed]: called, the number of verdicts the host decided), or NARROW.
+    `indel` (--spikeScanIndel: dict(ins, caps: _SpikedCopies' - SmcError when a copy did not fit the caps -, var, var_ins:
+    af_run_variants' records of run.group - they stand where `listed` does -, want: per copy and variant the counts call's (N, V1))):
+    every build leaves its extras list in HBM and makes no table (BuildExtras); smc_scan_detect_keys resolves the key's allele id per
+    copy from them; replicate 0's (N, V1) on the copy must be the counts call's; and the table of a row that comes down is made from
+    its copy's extras, the texts through copy_allele_key on the copy, which is alive until this call returns."""
     from . import vc
     from .engine import DevBuf
-    A, up, lo, nl, chrom = run.A, run.up, run.lo, run.nl, run.chrom
+    A, lo, nl, chrom = run.A, run.lo, run.nl, run.chrom
     B, G = len(part_seeds), len(run.group)
     flag, entry = ("--spikeScan", "smc_scan_detect") if indel is None else ("--spikeScanIndel", "smc_scan_detect_keys")
-    extras = None
-    if indel is None:
-        d_aln, d_bq, (sa, sb), stats = spike_run_copies(eng, up, A, svar, run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1])
-        owned = [d_aln, d_bq]
-        runs = [RunOnDevice(d_aln.view(c * sa), up.cig, d_bq.view(c * sb), up.loc, up.ref, up.n_aln, up.loc_host) for c in range(B)]
-    else:
-        made = spike_indel_run_copies(eng, up, A, svar, indel["ins"], run.idents, part_seeds, [thr] * B, P.mismatchThr, run.mism[0], run.mism[1],
-                                      caps=indel.get("caps"))
-        (sa, sb, sc), stats, owned = made["strides"], made["stats"], [made["aln"], made["bq"], made["cig"]]
-        if made["totals"][:, 2].any():
-            for b in owned:
-                b.free()
-            raise _lib.SmcError("smc_spike_indels_reps: a copy of %s:%d-%d did not fit spike_indel_caps' bounds" % (chrom, lo + 1, lo + nl))
-        runs = [RunOnDevice(_BufView(made["aln"], c * sa), _BufView(made["cig"], c * sc), _BufView(made["bq"], c * sb), up.loc, up.ref, up.n_aln,
-                            up.loc_host, pairs_used=int(made["totals"][c, 0])) for c in range(B)]
-        xcap = build_xcap(nl)
-        owned += [DevBuf(eng, 20 * xcap * B + 256), DevBuf(eng, 8 * B + 256)]
-        extras = [BuildExtras(_BufView(owned[3], 20 * xcap * c), _BufView(owned[4], 8 * c)) for c in range(B)]
+    copies = _SpikedCopies(eng, run, svar, part_seeds, thr, P, *((indel["ins"], indel.get("caps")) if indel is not None else ()))
+    runs, extras, xbufs = copies.runs, None, []
     d = d_rows = plan = None
     try:
-        for c in range(B):
-            for g, k in enumerate(run.group):
-                if int(stats[c, var_at[g], 0]) != int(want_reads[c][g]):
-                    v = variants[k]
-                    raise RuntimeError("%s: seed %d at %s:%d: the rewrite touched %d records, the counts call says %d" %
-                                       (flag, int(part_seeds[c]), v.chrom, v.pos, int(stats[c, var_at[g], 0]), int(want_reads[c][g])))
-        if indel is not None and check0 is not None:
-            cov, car, _ = allele_carriers_run(eng, runs[check0], A, lo, indel["var"], indel["var_ins"])
-            for g, k in enumerate(run.group):
-                mine, want = (int(cov[g].sum()), int(car[g].sum())), tuple(int(x) for x in indel["want"][check0][g])
-                if mine != want:
-                    v = variants[k]
-                    raise RuntimeError("%s: seed %d at %s:%d: the copy holds (N, V1) = %r, the counts call says %r" %
-                                       (flag, int(part_seeds[check0]), v.chrom, v.pos, mine, want))
+        if indel is not None and copies.totals[:, 2].any():
+            raise _lib.SmcError("smc_spike_indels_reps: a copy of %s:%d-%d did not fit spike_indel_caps' bounds" % (chrom, lo + 1, lo + nl))
+        copies.check_reads(var_at, want_reads, variants, flag)
+        if indel is not None:
+            if check0 is not None:
+                copies.check_carriers(check0, runs[check0], A, indel["want"][check0], indel["var"], indel["var_ins"], variants, flag)
+            xcap = build_xcap(nl)
+            xbufs += [DevBuf(eng, 20 * xcap * B + 256), DevBuf(eng, 8 * B + 256)]
+            extras = [BuildExtras(_BufView(xbufs[0], 20 * xcap * c), _BufView(xbufs[1], 8 * c)) for c in range(B)]
         # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch; a record the indel rewrite
         # relocated has its texts in the copy - no table is made of those builds here)
-        copies = (_KeptRun(runs[c], A, None, A, run.bam.allele_key, run.bam.barcode_name, lambda n: run.idents) for c in range(B))
-        built = _build_copies(eng, run, B, copies, P, bits, flag, fasta, max_depth, sampler, sampler_seed, extras)
+        kept = (_KeptRun(runs[c], A, None, A, run.bam.allele_key, run.bam.barcode_name, lambda n: run.idents) for c in range(B))
+        built = _build_copies(eng, run, B, kept, P, bits, flag, fasta, max_depth, sampler, sampler_seed, extras)
         if built == NARROW:
             return NARROW
         d = built
@@ -3225,10 +3244,8 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
             table_of = lambda c, a: d.tables[c * nl + a]
         else:
             rec, todo, _ = scan_detect_keys(
-                eng, d_rows, B, nl, indel["var"], indel["var_ins"],
-                dict(aln=made["aln"].data_ptr(), cig=made["cig"].data_ptr(), bq=made["bq"].data_ptr(), strides=(sa, sb, sc), n_aln=up.n_aln,
-                     cap_pairs=made["caps"][0]),
-                dict(x=owned[3].data_ptr(), cnt=owned[4].data_ptr(), x_stride=5 * xcap, cnt_stride=2, xcap=xcap), threshold)
+                eng, d_rows, B, nl, indel["var"], indel["var_ins"], copies.addresses(),
+                dict(x=xbufs[0].data_ptr(), cnt=xbufs[1].data_ptr(), x_stride=5 * xcap, cnt_stride=2, xcap=xcap), threshold)
             lists, keys = {}, {}
 
             def table_of(c, a):
@@ -3269,9 +3286,10 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
     finally:
         if plan is not None:
             plan.close()
-        for b in [d_rows, d] + owned:
+        for b in [d_rows, d] + xbufs:
             if b is not None:
                 b.free()
+        copies.free()
 
 
 def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n_reps: int, eng, threshold: int, repeats,
@@ -3283,15 +3301,14 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     kept as an AfRun while its passes are made.  Per pass with a locus in the run: the pre-pass's counters of its variants
     (smc_allele_carriers with counts on the run, and on one copy spiked at threshold 2^32 with the pass's list), one
     smc_spike_rep_counts call for (S, READS, V1) of every variant, replicate and target, then per target as many copies per
-    smc_spike_alleles_reps call as spike_replicates' room rule allows, each built behind the last and the batch called with one plan
+    smc_spike_alleles_reps call as _copy_room allows, each built behind the last and the batch called with one plan
     (_scan_call).  The rewrite takes the pass's whole list of the chromosome: a variant is rewritten in whichever run decodes a read
     that spans it.  No batch of rows is downloaded.
     `indel` (--spikeScanIndel: `variants` are the scan's insertion or deletion at every locus, tools.spike_scan_lists.scan_indels): a
     pass is the run --spikeAF <targets> --spikeVariants <its list> --spikeIndelReps n_reps.  The counters are the four of
-    _spike_single_counters, the counts come from one smc_spike_indel_counts call, the copies from smc_spike_indels_reps - sized by
-    spike_indel_caps and spike_indel_copy_strides under the same room rule -, and the verdicts from smc_scan_detect_keys (_scan_call's
-    `indel`).  ValueError before anything is spiked: a run with a record at which the rewrite's 16-bit limits could bind
-    (spike_indel_limits).
+    _spike_single_counters, the counts come from one smc_spike_indel_counts call, the copies from smc_spike_indels_reps under the same
+    room rule, and the verdicts from smc_scan_detect_keys (_scan_call's `indel`).  ValueError before anything is spiked: a run with a
+    record at which the rewrite's 16-bit limits could bind (_refuse_indel_limits).
     -> dict(seeds, base: per variant (N, V0), counts: uint32 [V, R, T, 3] = (S, READS, V1), called: bool [V, T, R], passes: per pass
     of `passes` dict(variants, copies, builds, host, seconds), times: dict(stage, runs, decode))."""
     import time
@@ -3316,53 +3333,31 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     stats = [dict(variants=0, copies=0, builds=0, host=0, seconds=0.0) for _ in passes]
     times = {"decode": 0.0, "runs": 0}
     order = sorted(range(V), key=lambda k: (variants[k].chrom, variants[k].pos))
-    i = 0
-    while i < len(order):
-        v0 = variants[order[i]]
-        j = i
-        while j + 1 < len(order) and variants[order[j + 1]].chrom == v0.chrom and variants[order[j + 1]].pos - v0.pos < AF_RUN_LOCI:
-            j += 1
-        lo, hi = v0.pos - 1, variants[order[j]].pos
+    spans = _listed_spans(variants, order)
+    for chrom, lo, hi, span in spans:
         t0 = time.perf_counter()
-        run = AfRun(v0.chrom, lo, hi, [], 0, bam=bamio.NativeBam(path))
+        run = AfRun(chrom, lo, hi, [], 0)
         try:
-            A = run.bam.alignments_run(v0.chrom, lo, hi, max_reads, P, nthreads)
-            nl = int(A["nl"])
+            nl = run.load(path, fasta, eng, P, max_reads, nthreads, mism=True)
             if nl < 1:
-                raise bamio.BamError("--spikeScan: the run %s:%d-%d could not be decoded" % (v0.chrom, lo + 1, hi))
-            inside = [k for k in order[i:j + 1] if variants[k].pos - 1 - lo < nl]
-            run.A, run.nl = A, nl
-            run.run_ref = fasta.fetch(v0.chrom, lo, lo + nl).upper()
-            run.idents = run.bam.barcode_idents(A["n_bc"])
-            run.mism = run.bam.run_mismatches(len(A["aln"]))
-            run.up = upload_run(eng, A, run.run_ref)
+                raise bamio.BamError("--spikeScan: the run %s:%d-%d could not be decoded" % (chrom, lo + 1, hi))
+            inside = [k for k in span if variants[k].pos - 1 - lo < nl]
             times["decode"] += time.perf_counter() - t0
             times["runs"] += 1
-            per_copy = sum(spike_copy_strides(run.up.n_aln, len(A["bq"]) // 2))
             in_run = sorted({int(pass_at[k]) for k in inside})
             for p in in_run if indel else ():
-                bad = spike_indel_limits(A, spikes[p].chrom_variants(v0.chrom, 0.5)[0])
-                if bad is not None:
-                    a = A["aln"][bad]
-                    raise ValueError("%s: the record at %s:%d (l_seq %d, %d CIGAR operations) spans listed "
-                                     "indels that could take l_seq or the CIGAR beyond 65535: whether it takes one would depend on the "
-                                     "draws of the others" % ("--spikeScanIndel", v0.chrom, int(a["pos"]) + 1, int(a["l_seq"]), int(a["n_cig"])))
+                _refuse_indel_limits(run.A, spikes[p].chrom_variants(chrom, 0.5)[0], "--spikeScanIndel", chrom)
             for p in in_run:
                 t0 = time.perf_counter()
                 run.group = [k for k in inside if pass_at[k] == p]
-                caps = None
-                if indel:
-                    # (a copy: records, both pools at their capacities, and the call's scratch of 8 bytes per alignment - spike_replicates')
-                    caps = spike_indel_caps(A, spikes[p].chrom_variants(v0.chrom, 0.5)[0])
-                    per_copy = sum(spike_indel_copy_strides(run.up.n_aln, *caps)) + 8 * run.up.n_aln
-                room = max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per_copy, AF_REP_BATCH_SLOTS // max(1, int(A["n_slots"]) + nl)))
+                room, caps = _copy_room(run, spikes[p].chrom_variants(chrom, 0.5)[0] if indel else None, indel)
                 _scan_pass(eng, run, spikes[p], [int(local[k]) for k in run.group], variants, seeds, thr, P, fasta, max_depth, sampler,
                            sampler_seed, threshold, repeats, room, base, counts, called, stats[p], caps)
                 stats[p]["variants"] += len(run.group)
                 stats[p]["seconds"] += time.perf_counter() - t0
         finally:
             run.free()
-        i += len(inside)
+        spans.send(len(inside))
     times["stage"] = time.perf_counter() - t_start
     return dict(seeds=seeds, base=base, counts=counts, called=called, passes=stats, times=times)
 

@@ -718,8 +718,11 @@ def test_16_bit_builder_refuses_a_min_bq_it_has_no_room_for():
 class _CountedBuf(object):
     """A stand-in for a device buffer: what download hands back, and how often it and free were called."""
 
-    def __init__(self, data=None):
-        self.data, self.downloads, self.freed = data, 0, 0
+    def __init__(self, data=None, ptr=0):
+        self.data, self.downloads, self.freed, self.ptr = data, 0, 0, ptr
+
+    def data_ptr(self):
+        return self.ptr
 
     def download(self, dtype, count, offset_bytes=0):
         self.downloads += 1
@@ -791,3 +794,180 @@ def test_kept_run_maps_a_selections_numbering_back_to_the_decoders():
     kept, bufs, asked, A, idents = _kept_run_case([6, 1], False, copy=copy)
     assert kept.allele_key(0, 4, 2) == "K6" and kept.allele_key(1, 4, 2) == "K1" and asked == [(6, 4, 2), (1, 4, 2)]
     assert copy.aln.downloads == 1 and copy.bq.downloads == 0 and bufs["orig"].downloads == 1
+
+
+def _copies_case(monkeypatch, stats=None, totals=None):
+    """A kept run of 8 alignments with the listed variants 1 and 0 (records 2 and 0 of three), three seeds, and spike_run_copies /
+    spike_indel_run_copies patched to hand back counted stand-ins -> (devplanes, the run, its own buffers, the stand-ins, what the
+    patched calls were given, the further arguments of the two calls: svar, var_at, seeds, thr, P, variants)."""
+    from types import SimpleNamespace as NS
+    from smcounter_amd import devplanes
+    own = [_CountedBuf(ptr=0x100 * (k + 1)) for k in range(5)]
+    run = devplanes.AfRun("chr1", 100, 140, [1, 0], 40, bam=NS(allele_key=lambda ai, q, i: "K%d" % ai, barcode_name=lambda g: "name%d" % g, close=lambda: None),
+                          A=dict(n_bc=3, nl=40, n_slots=100, bq=np.zeros(2 * 64, np.uint8)), up=devplanes.RunOnDevice(*own, 8, "loc on the host"),
+                          run_ref="A" * 40, idents=np.arange(3, dtype=np.uint64), mism=("NM", "INDEL"))
+    made = dict(aln=_CountedBuf(ptr=0x10000), bq=_CountedBuf(ptr=0x20000), cig=_CountedBuf(ptr=0x30000))
+    stats = np.array([[[5, 0], [0, 0], [7, 0]]] * 3, np.uint32) if stats is None else stats          # READS 5 at record 0, 7 at record 2
+    totals = np.array([[70, 9, 0], [80, 9, 0], [90, 9, 0]], np.uint64) if totals is None else totals
+    given = []
+    monkeypatch.setattr(devplanes, "spike_run_copies", lambda *a, **k: (given.append((a, k)), (made["aln"], made["bq"], (512, 256), stats))[1])
+    monkeypatch.setattr(devplanes, "spike_indel_run_copies",
+                        lambda *a, caps=None: (given.append((a, dict(caps=caps))), dict(made, strides=(512, 256, 768), caps=caps or (99, 33),
+                                                                                      stats=stats, totals=totals, nm=None, n_indel=None))[1])
+    variants = [NS(chrom="chr1", pos=121, ref="A", alt="T"), NS(chrom="chr1", pos=131, ref="A", alt="T")]
+    return devplanes, run, own, made, given, ("svar", [2, 0], [11, 12, 13], 1 << 20, VcParams(), variants)
+
+
+def test_spiked_copies_are_views_at_the_strides_of_the_buffers_they_own(monkeypatch):
+    """devplanes._SpikedCopies with stand-in buffers, B = 3: copy c reads its records and pair pool at c x their strides; an SNV copy
+    shares the run's CIGAR pool (the object itself), an indel copy has its own at c x its stride and pairs_used from totals[c, 0]; loc
+    and ref are the run's; the rewrite is given the run, every seed and one threshold per seed; free() frees what the call returned,
+    once, and nothing of the run."""
+    devplanes, run, own, made, given, (svar, var_at, seeds, thr, P, variants) = _copies_case(monkeypatch)
+    copies = devplanes._SpikedCopies("eng", run, svar, seeds, thr, P)
+    assert given == [(("eng", run.up, run.A, svar, run.idents, seeds, [thr] * 3, P.mismatchThr, "NM", "INDEL"), {})]
+    assert copies.stats.shape == (3, 3, 2) and copies.strides == (512, 256) and copies.caps is None and copies.totals is None
+    for c, r in enumerate(copies.runs):
+        assert (r.aln.data_ptr(), r.bq.data_ptr()) == (0x10000 + 512 * c, 0x20000 + 256 * c) and r.aln.word_bits == 32
+        assert r.cig is run.up.cig and r.loc is run.up.loc and r.ref is run.up.ref
+        assert (r.n_aln, r.loc_host, r.pairs_used) == (8, "loc on the host", None)
+    copies.free()
+    assert [made[x].freed for x in ("aln", "bq", "cig")] == [1, 1, 0] and not any(b.freed for b in own)
+    # the indel rewrite
+    devplanes, run, own, made, given, _ = _copies_case(monkeypatch)
+    copies = devplanes._SpikedCopies("eng", run, svar, seeds, thr, P, "ins", (120, 40))
+    assert given == [(("eng", run.up, run.A, svar, "ins", run.idents, seeds, [thr] * 3, P.mismatchThr, "NM", "INDEL"), dict(caps=(120, 40)))]
+    assert copies.strides == (512, 256, 768) and copies.caps == (120, 40)
+    for c, r in enumerate(copies.runs):
+        assert (r.aln.data_ptr(), r.bq.data_ptr(), r.cig.data_ptr()) == (0x10000 + 512 * c, 0x20000 + 256 * c, 0x30000 + 768 * c)
+        assert r.cig is not run.up.cig and r.loc is run.up.loc and r.ref is run.up.ref and r.pairs_used == [70, 80, 90][c]
+    assert copies.addresses() == dict(aln=0x10000, cig=0x30000, bq=0x20000, strides=(512, 256, 768), n_aln=8, cap_pairs=120)
+    copies.free()
+    assert [made[x].freed for x in ("aln", "bq", "cig")] == [1, 1, 1] and not any(b.freed for b in own)
+
+
+def test_the_two_spike_calls_free_their_copies_once_on_every_way_out(monkeypatch):
+    """_spike_rep_call and _scan_call over devplanes._SpikedCopies with stand-in buffers: a READS or an (N, V1) that is not the counts
+    call's raises RuntimeError with the text each stage had before there was one class (written out here); a consumer that answers
+    NARROW, and the scan's own refusal of a copy that did not fit the caps it passed, end the call too - and on each way out every buffer
+    the rewrite returned is freed exactly once, the run's own never."""
+    import functools
+    case = functools.partial(_copies_case, monkeypatch)
+
+    def freed_once(made, own, indel):
+        return [made[x].freed for x in ("aln", "bq", "cig")] == [1, 1, int(indel)] and not any(b.freed for b in own)
+    good = [[7, 5]] * 3                                              # READS per copy of variants 1, 0: records 2, 0
+    bad = [[7, 5], [7, 6], [7, 5]]
+    listed = np.zeros(2, abi.SCAN_LOCUS_DTYPE)
+    # READS: the replicate stage names --spikeReps whichever flag is in force, the scan its own
+    devplanes, run, own, made, _, (svar, var_at, seeds, thr, P, variants) = case()
+    rep = lambda want, *tail: devplanes._spike_rep_call("eng", run, svar, var_at, seeds, thr, want, P, None, variants, 0, "reference", 0, 32, *tail)
+    scan = lambda want, check0, *tail: devplanes._scan_call("eng", run, svar, var_at, listed, seeds, thr, want, P, None, variants, 0, "reference",
+                                                            0, 32, 0, (), check0, *tail)
+    with pytest.raises(RuntimeError) as e:
+        rep(bad, [(0.5, P)])
+    assert str(e.value) == "--spikeReps: seed 12 at chr1:121: the rewrite touched 5 records, the counts call says 6"
+    assert freed_once(made, own, False)
+    devplanes, run, own, made, _, _ = case()
+    with pytest.raises(RuntimeError) as e:
+        scan(bad, None)
+    assert str(e.value) == "--spikeScan: seed 12 at chr1:121: the rewrite touched 5 records, the counts call says 6"
+    assert freed_once(made, own, False)
+    # (N, V1): smc_allele_carriers on the copy says (2, 1) of both variants
+    two_one = (np.array([[1, 1, 0]] * 2, bool), np.array([[0, 1, 0]] * 2, bool), None)
+    monkeypatch.setattr(devplanes, "allele_carriers_run", lambda *a, **k: two_one)
+    monkeypatch.setattr(devplanes, "af_run_variants", lambda *a: ("var", "ins"))
+    want = [[(2, 1), (2, 1)], [(2, 1), (2, 2)], [(2, 1), (2, 1)]]
+    devplanes, run, own, made, _, _ = case()
+    monkeypatch.setattr(devplanes, "_copy_rows", lambda eng, run, variants, n, kept_runs, *a: [kept.free() for kept in kept_runs])
+    with pytest.raises(RuntimeError) as e:
+        rep(good, (), dict(ins="ins", want=want, want_cells=[]))
+    assert str(e.value) == "--spikeIndelReps: seed 12 at chr1:121: the copy holds (N, V1) = (2, 1), the counts call says (2, 2)"
+    assert freed_once(made, own, True)
+    devplanes, run, own, made, _, _ = case()
+    copies = devplanes._SpikedCopies("eng", run, svar, seeds, thr, P, "ins")
+    with pytest.raises(RuntimeError) as e:
+        copies.check_carriers(1, copies.runs[1], run.A, want[1], "var", "ins", variants, "--spikeIndelReps", " x fraction 0.5")
+    assert str(e.value) == "--spikeIndelReps: seed 12 at chr1:121 x fraction 0.5: the copy holds (N, V1) = (2, 1), the counts call says (2, 2)"
+    devplanes, run, own, made, _, _ = case()
+    with pytest.raises(RuntimeError) as e:
+        scan(good, 1, dict(ins="ins", caps=(120, 40), var="var", var_ins="ins", want=want))
+    assert str(e.value) == "--spikeScanIndel: seed 12 at chr1:121: the copy holds (N, V1) = (2, 1), the counts call says (2, 2)"
+    assert freed_once(made, own, True)
+    # NARROW from the consumer
+    devplanes, run, own, made, _, _ = case()
+    monkeypatch.setattr(devplanes, "_copy_rows", lambda *a: devplanes.NARROW)
+    assert rep(good, (), dict(ins="ins", want=[[(2, 1)] * 2] * 3, want_cells=[])) == devplanes.NARROW and freed_once(made, own, True)
+    devplanes, run, own, made, _, _ = case()
+    monkeypatch.setattr(devplanes, "_build_copies", lambda *a: devplanes.NARROW)
+    assert scan(good, None) == devplanes.NARROW and freed_once(made, own, False)
+    # a copy that did not fit the caps the scan passed: its own refusal (spike_indel_run_copies raises only without caps)
+    devplanes, run, own, made, given, _ = case(totals=np.array([[70, 9, 0], [800, 9, 1], [90, 9, 0]], np.uint64))
+    with pytest.raises(_lib.SmcError) as e:
+        scan(good, None, dict(ins="ins", caps=(120, 40), var="var", var_ins="ins", want=want))
+    assert str(e.value) == "smc_spike_indels_reps: a copy of chr1:101-140 did not fit spike_indel_caps' bounds"
+    assert given[0][1] == dict(caps=(120, 40)) and freed_once(made, own, True)
+
+
+def test_copy_room_is_the_least_of_its_three_limits(monkeypatch):
+    """devplanes._copy_room against its formula - max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per copy, AF_REP_BATCH_SLOTS //
+    (n_slots + nl))) - on runs where each limit binds in turn, for the SNV rewrite's copies and the indel rewrite's, whose caps it
+    hands back."""
+    from types import SimpleNamespace as NS
+    from smcounter_amd import devplanes
+    M, BYTES, SLOTS = devplanes.SPIKE_MAX_COPIES, devplanes.SPIKE_REP_BATCH_BYTES, devplanes.AF_REP_BATCH_SLOTS
+    assert (M, BYTES, SLOTS) == (64, 1 << 30, 16 << 20)
+
+    def run_of(n_aln, n_pairs, n_slots, nl=40):
+        return NS(up=NS(n_aln=n_aln), A=dict(bq=range(2 * n_pairs), n_slots=n_slots), nl=nl)
+    seen = []
+    monkeypatch.setattr(devplanes, "spike_indel_caps", lambda A, svar: (seen.append(svar), caps)[1])
+    #                    n_aln      n_pairs     n_slots     caps                      the room, and the limit that gives it
+    for n, n_pairs, n_slots, caps, room in ((8, 64, 100, None, M),
+                                            (1_000_000, 50_000_000, 100, None, BYTES // (36_000_000 + 100_000_000)),
+                                            (8, 64, 4_000_000, None, SLOTS // 4_000_040),
+                                            (8, 64, 100, (70, 12), M),
+                                            (1_000_000, 64, 100, (100_000_000, 10_000_000), BYTES // (36_000_000 + 200_000_256 + 40_000_000 + 8_000_000)),
+                                            (8, 64, 4_000_000, (70, 12), SLOTS // 4_000_040),
+                                            (8, 64, 100, (1 << 30, 12), 1)):
+        four = caps is not None
+        per_copy = sum(devplanes.spike_indel_copy_strides(n, *caps)) + 8 * n if four else sum(devplanes.spike_copy_strides(n, n_pairs))
+        limits = (M, BYTES // per_copy, SLOTS // (n_slots + 40))
+        assert devplanes._copy_room(run_of(n, n_pairs, n_slots), "svar", four) == (max(1, min(limits)), caps)
+        assert max(1, min(limits)) == room and sorted(limits)[0] < sorted(limits)[1]          # one limit binds, the one this row is for
+    assert 1 < BYTES // (36_000_000 + 100_000_000) < M and 1 < SLOTS // 4_000_040 < M and seen == ["svar"] * 4
+
+
+def test_listed_spans_cut_as_the_three_loops_did():
+    """devplanes._listed_spans against the loop of ds_af_sets, _spike_rules and spike_scan as it stood in each (restated here): two
+    chromosomes, a variant AF_RUN_LOCI - 1 positions behind its span's first (inside) and one AF_RUN_LOCI behind (the next span), and
+    a consumer that takes fewer variants than it is offered - a run the decoder cut short: the rest starts the next span."""
+    from types import SimpleNamespace as NS
+    from smcounter_amd import devplanes
+    W = devplanes.AF_RUN_LOCI
+    variants = [NS(chrom=c, pos=p) for c, p in (("chr2", 60), ("chr1", 100 + W), ("chr1", 100), ("chr2", 50), ("chr1", 99 + W), ("chr2", 70),
+                                                ("chr1", 700 + W), ("chr1", 101 + W))]
+    order = sorted(range(len(variants)), key=lambda k: (variants[k].chrom, variants[k].pos))
+    take = lambda span: max(1, len(span) - 1) if variants[span[0]].chrom == "chr2" else len(span)
+
+    def parents():
+        i = 0
+        while i < len(order):
+            v0 = variants[order[i]]
+            j = i
+            while j + 1 < len(order) and variants[order[j + 1]].chrom == v0.chrom and variants[order[j + 1]].pos - v0.pos < W:
+                j += 1
+            lo, hi = v0.pos - 1, variants[order[j]].pos
+            group = order[i:j + 1][:take(order[i:j + 1])]
+            yield v0.chrom, lo, hi, order[i:j + 1], group
+            i += len(group)
+    mine = []
+    spans = devplanes._listed_spans(variants, order)
+    for chrom, lo, hi, span in spans:
+        mine.append((chrom, lo, hi, span, span[:take(span)]))
+        spans.send(take(span))
+    assert mine == list(parents())
+    assert [(c, lo, hi, [variants[k].pos for k in g]) for c, lo, hi, _, g in mine] == [
+        ("chr1", 99, 99 + W, [100, 99 + W]), ("chr1", 99 + W, 101 + W, [100 + W, 101 + W]), ("chr1", 699 + W, 700 + W, [700 + W]),
+        ("chr2", 49, 70, [50, 60]), ("chr2", 69, 70, [70])]
+    assert list(devplanes._listed_spans(variants, [])) == []

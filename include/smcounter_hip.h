@@ -415,6 +415,27 @@ int smc_select_alignments_keyed(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t 
                                 int32_t key, int64_t n_bc, int64_t n_pair, const uint32_t* d_keep_mask, const uint64_t* d_ident, int64_t n_ids,
                                 uint64_t seed, double frac, smc_dev_aln* d_aln_out, uint32_t* d_orig_index, smc_dev_locus* d_loc_out,
                                 uint32_t* d_summary, void* stream);
+/* (ABI 11, additive: one entry more, the version number unchanged) The philox selections of n_copies copies of a run at n_fracs
+ * fractions in one call - what n_copies x n_fracs smc_select_alignments calls give, without their launches, allocations and downloads.
+ * Copy c's records stand at d_aln + c x aln_stride_bytes (0: the copies share the records; else a positive multiple of 4) and are drawn
+ * with seeds[c]; a barcode's draw serves every fraction, so the kept sets of a copy are nested in the fraction.  `seeds` (n_copies) and
+ * `fracs` (n_fracs doubles, each in (0, 1]) are HOST arrays, read before the call returns.  Selection s = f x n_copies + c, fractions
+ * outer - the selections of one fraction lie at a constant stride:
+ *   d_aln_out + s x n_aln, d_orig_index + s x n_aln   the kept records in file order and their indices in the copy
+ *   d_loc_out + s x n_loci                            the n_loci descriptors
+ *   d_summary + 4 x s                                 kept alignments, deepest n, total slots (the fourth word is not written)
+ * For every (c, f) the first `kept` records, their indices, all descriptors and the three summary words are byte for byte what
+ * smc_select_alignments writes for copy c's records with d_keep_mask = NULL, the same d_ident, seeds[c] and fracs[f] (the same
+ * threshold floor(f x 2^32), 2^32 at f = 1: everything); nothing is written behind the kept records.  d_ident must hold n_ids
+ * identities (it is read at f = 1 too).  SMC_E_INPUT, nothing launched: n_copies or n_fracs below 1, more than SMC_SEL_MAX_SELECTIONS
+ * selections, a fraction outside (0, 1], a negative stride or one that is no multiple of 4, a NULL output.  Asynchronous on `stream`;
+ * the scratch is the context's, once per selection (4 bytes per locus and 8 per 1024 alignments each), shared with smc_select_alignments:
+ * calls of one context are to be ordered on one stream. */
+#define SMC_SEL_MAX_SELECTIONS 2048
+int smc_select_alignments_copies(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t aln_stride_bytes, int32_t n_copies, int64_t n_aln,
+                                 const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0, const uint64_t* d_ident, int64_t n_ids,
+                                 const uint64_t* seeds, const double* fracs, int32_t n_fracs, smc_dev_aln* d_aln_out, uint32_t* d_orig_index,
+                                 smc_dev_locus* d_loc_out, uint32_t* d_summary, void* stream);
 /* (ABI 11) The read-level philox sampler of --dsRpb (--dsRpbSampler philox): a file-wide table of read names and barcodes that stays
  * in HBM for the whole run (csrc/k_read_groups.inc).  Grouping as ds.reads.withinMT.py:37-58: the unit is the full read name, its
  * barcode field -2 of the stripped name; per barcode the names counted; one / multi = barcodes with one / two or more names,

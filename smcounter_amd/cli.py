@@ -286,6 +286,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "of the planted key is resolved per replicate on the GPU from the build's own list of allele keys "
                         "(smc_scan_detect_keys); the files are --spikeScan's, REF and ALT the indel's texts at its anchor.  Needs "
                         "--spikeScan; not with --spikeScanAlt")
+    p.add_argument("--spikeScanDepth", default=None,
+                   help="f1,f2,...: --spikeScan (and --spikeScanIndel) also at these barcode fractions, each in (0, 1] and none listed "
+                        "twice.  A pass is then by definition its run with --spikeDepth <fractions> (--spikeIndelDepth) beside "
+                        "--spikeReps: the same draws, and a cell's mtDepth max(1, round(f x mtDepth)) with its own threshold.  The "
+                        "copies of a batch are selected at every fraction by one smc_select_alignments_copies call.  Writes "
+                        "<outPrefix>.spikeScan.depth.sensitivity.txt, .spikeScan.depth.curve.txt, .spikeScan.depth.need.txt (F95: the "
+                        "smallest depth with a rate of 0.95 at it and above), <outPrefix>.spikeScan<t>.dsMT<f>.rate.bedgraph, "
+                        ".spikeScan.dsMT<f>.t95.bedgraph and .spikeScan<t>.f95.bedgraph (2 where full depth fails); targets x "
+                        "fractions at most %d.  With --lod these pages carry no LOD column.  Needs --spikeScan" % GRID_MAX_CELLS)
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -751,13 +760,18 @@ def _repeat_tracks(args):
 
 def _spike_scan(args, plan, ref, eng, params):
     """--spikeScan after the run's batches: devplanes.spike_scan over every run of the file, and a line per pass in the run log."""
+    from . import spike as _spike
     scan = plan.scan
     threshold = writers.pi_threshold(params.mtDepth, args.threshold)
     repeats = postfilter.load_repeat_regions(args.bedTarget, *_repeat_tracks(args))
+    depth = None
+    if "fracs" in scan:
+        cells = [dataclasses.replace(params, mtDepth=_spike.scan_depth_mt(params.mtDepth, f)) for f in scan["fracs"]]
+        depth = dict(fracs=scan["fracs"], params=cells, thresholds=[writers.pi_threshold(c.mtDepth, args.threshold) for c in cells])
     try:
         out = devplanes.spike_scan(args.bamFile, ref, scan["variants"], scan["passes"], scan["targets"], params, int(args.dsSeed), scan["reps"],
                                    eng, threshold, repeats, sampler=getattr(args, "sampler", "reference"),
-                                   sampler_seed=getattr(args, "samplerSeed", 0), indel="indel" in scan)
+                                   sampler_seed=getattr(args, "samplerSeed", 0), indel="indel" in scan, depth=depth)
     except (ValueError, bamio.BamError) as e:
         raise SystemExit(str(e))
     for (k, _), st in zip(scan["passes"], out["passes"]):
@@ -1290,7 +1304,19 @@ def _scan_reports(args, plan, shard):
     print("--spikeScan: %d loci x %d targets x %d replicates in %d passes: %d runs decoded once each (%.3f s), %d copies built and "
           "called, %d of %d verdicts decided by the host, stage %.3f s" %
           (len(variants), len(targets), R, len(scan["passes"]), tm["runs"], tm["decode"], sum(st["builds"] for st in out["passes"]),
-           sum(st["host"] for st in out["passes"]), len(variants) * len(targets) * R, tm["stage"]))
+           sum(st["host"] for st in out["passes"]), len(variants) * len(targets) * R * (1 + len(scan.get("fracs", ()))), tm["stage"]))
+    if "fracs" in scan:
+        fracs = scan["fracs"]
+        cells = {}
+        for i, v in enumerate(variants):
+            for t in range(len(targets)):
+                for f in range(len(fracs)):
+                    cells[(i, t, f)] = [_spike.scan_entry(v, dict(N=int(n), V0=int(v0), S=int(s), READS=int(reads), V1=int(v1)),
+                                                          bool(out["depth_called"][i, t, f, j]))
+                                        for j, (n, v0, s, reads, v1) in enumerate(out["depth_counts"][i, :, t, f].tolist())]
+        _spike.write_scan_depth(args.outPrefix, scan["loci"], variants, targets, fracs, plan.outputs[0].params.mtDepth, entries, cells)
+        print("--spikeScanDepth: fractions %s: %d cells per pass, %d select_copies calls" %
+              (",".join("%g" % f for f in fracs), len(targets) * len(fracs), sum(st["selects"] for st in out["passes"])))
 
 
 def _run(args, plan, loc_list, t0):

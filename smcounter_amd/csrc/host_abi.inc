@@ -913,6 +913,72 @@ int smc_select_alignments(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t n_aln,
                                        d_aln_out, d_orig_index, d_loc_out, d_summary, stream);
 }
 
+// (ABI 11, additive) the philox selections of n_copies copies of a run at n_fracs fractions: the five stages of the single call with
+// the selection as a grid dimension (k_select_aln.inc), the scratch once per selection.  Nothing waits.
+int smc_select_alignments_copies(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t aln_stride_bytes, int32_t n_copies, int64_t n_aln,
+                                 const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0, const uint64_t* d_ident, int64_t n_ids,
+                                 const uint64_t* seeds, const double* fracs, int32_t n_fracs, smc_dev_aln* d_aln_out, uint32_t* d_orig_index,
+                                 smc_dev_locus* d_loc_out, uint32_t* d_summary, void* stream) {
+    const std::string who = "smc_select_alignments_copies";
+    if (!ctx) return fail(SMC_E_ARG, who + ": NULL context");
+    if (n_aln < 0 || n_loci < 0 || n_ids < 0 || n_aln >= (int64_t)0xFFFFF000 || n_loci >= (int64_t)0x7FFFFFFF || n_ids > (int64_t)0xFFFFFFFF ||
+        (!d_ident && n_ids > 0) || (n_aln && !d_aln))
+        return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_copies < 1 || n_fracs < 1 || (int64_t)n_copies * (int64_t)n_fracs > SMC_SEL_MAX_SELECTIONS)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies x " + std::to_string(n_fracs) + " fractions, 1 .. " +
+                                 std::to_string(SMC_SEL_MAX_SELECTIONS) + " selections expected");
+    if (!seeds || !fracs) return fail(SMC_E_ARG, who + ": NULL argument");
+    for (int32_t f = 0; f < n_fracs; ++f)
+        if (!(fracs[f] > 0.0 && fracs[f] <= 1.0))
+            return fail(SMC_E_INPUT, who + ": fraction " + std::to_string(f) + " is " + std::to_string(fracs[f]) + ", not in (0, 1]");
+    if (aln_stride_bytes < 0 || (aln_stride_bytes & 3))
+        return fail(SMC_E_INPUT, who + ": a record stride of " + std::to_string(aln_stride_bytes) + " bytes (0 or a positive multiple of 4 expected)");
+    if (!d_aln_out || !d_orig_index || !d_loc_out || !d_summary) return fail(SMC_E_INPUT, who + ": NULL output");
+    (void)d_loc;                          // (as the single call: the input windows are not needed)
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t n_blk = (uint32_t)((n_aln + SEL_ITEMS - 1) / SEL_ITEMS), nl = (uint32_t)n_loci;
+    const uint32_t C = (uint32_t)n_copies, F = (uint32_t)n_fracs, S = C * F;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_off = carve(4 * ((size_t)n_blk + 1) * S), o_max = carve(4 * ((size_t)n_blk + 1) * S), o_diff = carve(4 * ((size_t)nl + 1) * S);
+    if (int rc = grow_scratch(ctx->sel_scratch, ctx->sel_bytes, off, off + off / 8, who.c_str(), &st)) return rc;
+    char* sc = (char*)ctx->sel_scratch;
+    uint32_t* blk_off = (uint32_t*)(sc + o_off);
+    int32_t* blk_max = (int32_t*)(sc + o_max);
+    int32_t* diff = (int32_t*)(sc + o_diff);
+    // the two record stages: a launch per group of SEL_CP_COPIES copies x SEL_CP_FRACS fractions (one launch for a usual batch)
+    auto records = [&](bool scatter) {
+        for (uint32_t c0 = 0; c0 < C; c0 += SEL_CP_COPIES)
+            for (uint32_t f0 = 0; f0 < F; f0 += SEL_CP_FRACS) {
+                SelCopies K;
+                memset(&K, 0, sizeof K);
+                const uint32_t nc = std::min<uint32_t>(SEL_CP_COPIES, C - c0);
+                K.c0 = c0; K.f0 = f0; K.n_f = std::min<uint32_t>(SEL_CP_FRACS, F - f0); K.n_copies = C;
+                for (uint32_t c = 0; c < nc; ++c) K.seed[c] = (unsigned long long)seeds[c0 + c];
+                // (the single call's conversion)
+                for (uint32_t f = 0; f < K.n_f; ++f)
+                    K.thr[f] = fracs[f0 + f] >= 1.0 ? (1ull << 32) : (unsigned long long)std::floor(fracs[f0 + f] * 4294967296.0);
+                if (!scatter)
+                    hipLaunchKernelGGL(k_selc_count, dim3(n_blk, nc), dim3(SEL_BLOCK), 0, st, (const char*)d_aln, (unsigned long long)aln_stride_bytes,
+                                       (uint32_t)n_aln, (const unsigned long long*)d_ident, (uint32_t)n_ids, K, n_blk, blk_off);
+                else
+                    hipLaunchKernelGGL(k_selc_scatter, dim3(n_blk, nc), dim3(SEL_BLOCK), 0, st, (const char*)d_aln, (unsigned long long)aln_stride_bytes,
+                                       (uint32_t)n_aln, (const unsigned long long*)d_ident, (uint32_t)n_ids, K, n_blk, (const uint32_t*)blk_off, start0,
+                                       nl, d_aln_out, d_orig_index, diff, blk_max);
+            }
+    };
+    if (n_blk) records(false);
+    hipLaunchKernelGGL(k_selc_offsets, dim3(S), dim3(SEL_SCAN), 0, st, blk_off, n_blk, diff, nl + 1u, d_summary);
+    if (n_blk) records(true);
+    hipLaunchKernelGGL(k_selc_loci, dim3(S), dim3(SEL_SCAN), 0, st, blk_max, n_blk, (const int32_t*)diff, nl, d_loc_out, d_summary);
+    if (nl) hipLaunchKernelGGL(k_selc_windows, dim3((nl + SEL_BLOCK / WAVE - 1) / (SEL_BLOCK / WAVE), S), dim3(SEL_BLOCK), 0, st,
+                               (const smc_dev_aln*)d_aln_out, (uint32_t)n_aln, (const uint32_t*)blk_off, (const int32_t*)blk_max, n_blk, start0,
+                               nl, d_loc_out);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
 // ---- (ABI 11) the read-level philox sampler's file-wide table (k_read_groups.inc)
 struct smc_read_groups {
     smc_ctx* ctx = nullptr;

@@ -96,8 +96,9 @@ __device__ __forceinline__ void sel_wg_scan(int64_t v, int64_t* buf, int64_t id,
     __syncthreads();
 }
 
-__global__ __launch_bounds__(SEL_SCAN) void k_sel_offsets(uint32_t* __restrict__ blk_cnt, uint32_t n_blk, int32_t* __restrict__ diff,
-                                                          uint32_t n_diff, uint32_t* __restrict__ summary) {
+// (the stage's work for one selection: k_sel_offsets, and k_selc_offsets per selection of a batch)
+__device__ __forceinline__ void sel_offsets_body(uint32_t* __restrict__ blk_cnt, uint32_t n_blk, int32_t* __restrict__ diff, uint32_t n_diff,
+                                                 uint32_t* __restrict__ summary) {
     __shared__ int64_t buf[SEL_SCAN];
     const uint32_t t = threadIdx.x, per = (n_blk + SEL_SCAN - 1) / SEL_SCAN, b0 = min(n_blk, t * per), b1 = min(n_blk, b0 + per);
     int64_t s = 0;
@@ -107,6 +108,11 @@ __global__ __launch_bounds__(SEL_SCAN) void k_sel_offsets(uint32_t* __restrict__
     for (uint32_t b = b0; b < b1; ++b) { const uint32_t c = blk_cnt[b]; blk_cnt[b] = (uint32_t)excl; excl += c; }
     if (t == 0) { blk_cnt[n_blk] = (uint32_t)total; summary[0] = (uint32_t)total; }
     for (uint32_t i = t; i < n_diff; i += SEL_SCAN) diff[i] = 0;
+}
+
+__global__ __launch_bounds__(SEL_SCAN) void k_sel_offsets(uint32_t* __restrict__ blk_cnt, uint32_t n_blk, int32_t* __restrict__ diff,
+                                                          uint32_t n_diff, uint32_t* __restrict__ summary) {
+    sel_offsets_body(blk_cnt, n_blk, diff, n_diff, summary);
 }
 
 __global__ __launch_bounds__(SEL_BLOCK) void k_sel_scatter(const smc_dev_aln* __restrict__ aln, uint32_t n_aln, SelRule R,
@@ -163,8 +169,8 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_sel_scatter(const smc_dev_aln* __
     }
 }
 
-__global__ __launch_bounds__(SEL_SCAN) void k_sel_loci(int32_t* __restrict__ blk_maxend, uint32_t n_blk, const int32_t* __restrict__ diff,
-                                                       uint32_t n_loci, smc_dev_locus* __restrict__ loc_out, uint32_t* __restrict__ summary) {
+__device__ __forceinline__ void sel_loci_body(int32_t* __restrict__ blk_maxend, uint32_t n_blk, const int32_t* __restrict__ diff,
+                                              uint32_t n_loci, smc_dev_locus* __restrict__ loc_out, uint32_t* __restrict__ summary) {
     __shared__ int64_t buf[SEL_SCAN];
     __shared__ uint32_t deepest;
     const uint32_t t = threadIdx.x;
@@ -201,6 +207,11 @@ __global__ __launch_bounds__(SEL_SCAN) void k_sel_loci(int32_t* __restrict__ blk
     if (t == 0) { summary[1] = deepest; summary[2] = (uint32_t)s_total; }
 }
 
+__global__ __launch_bounds__(SEL_SCAN) void k_sel_loci(int32_t* __restrict__ blk_maxend, uint32_t n_blk, const int32_t* __restrict__ diff,
+                                                       uint32_t n_loci, smc_dev_locus* __restrict__ loc_out, uint32_t* __restrict__ summary) {
+    sel_loci_body(blk_maxend, n_blk, diff, n_loci, loc_out, summary);
+}
+
 // first index j in [lo, hi) with pred(j), pred monotone (false ... false true ... true); hi when there is none.  64 probes a step.
 template <typename P>
 __device__ __forceinline__ uint32_t sel_search(uint32_t lo, uint32_t hi, P pred) {
@@ -224,9 +235,9 @@ __device__ __forceinline__ uint32_t sel_search(uint32_t lo, uint32_t hi, P pred)
 
 // a wavefront per locus: w0' = first kept alignment whose end passes p (the block by the running maximum of the blocks' ends - a
 // monotone predicate - then the first such end within that block's kept range); w1' = max(w0', first kept alignment with pos > p)
-__global__ __launch_bounds__(SEL_BLOCK) void k_sel_windows(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ blk_off,
-                                                           const int32_t* __restrict__ blk_runmax, uint32_t n_blk, int32_t start0,
-                                                           uint32_t n_loci, smc_dev_locus* __restrict__ loc_out) {
+__device__ __forceinline__ void sel_windows_body(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ blk_off,
+                                                 const int32_t* __restrict__ blk_runmax, uint32_t n_blk, int32_t start0, uint32_t n_loci,
+                                                 smc_dev_locus* __restrict__ loc_out) {
     const uint32_t l = blockIdx.x * (SEL_BLOCK / WAVE) + threadIdx.x / WAVE;
     if (l >= n_loci) return;
     const int32_t p = start0 + (int32_t)l;
@@ -244,6 +255,12 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_sel_windows(const smc_dev_aln* __
     }
     const uint32_t w1 = sel_search(w0, kept, [&](uint32_t j) { return out[j].pos > p; });
     if ((threadIdx.x & (WAVE - 1)) == 0) { loc_out[l].w0 = w0; loc_out[l].w1 = w1; }
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_sel_windows(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ blk_off,
+                                                           const int32_t* __restrict__ blk_runmax, uint32_t n_blk, int32_t start0,
+                                                           uint32_t n_loci, smc_dev_locus* __restrict__ loc_out) {
+    sel_windows_body(out, blk_off, blk_runmax, n_blk, start0, n_loci, loc_out);
 }
 
 // ---- (read level) the kept ids renumbered by first kept appearance: both bc_gid and pair_gid of d_aln_out, dense from 0 in the order
@@ -342,4 +359,149 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_sel_regid(smc_dev_aln* __restrict
         if (sb != 0xFFFFFFFFu) out[k].bc_gid = I.map[sb];
         if (sp != 0xFFFFFFFFu) out[k].pair_gid = I.map[sp];
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// the philox selections of several copies of a run at several fractions in one call (smc_select_alignments_copies)
+// ------------------------------------------------------------------------------------------
+// --spikeScanDepth and its kin select every spiked copy of a run at every listed fraction: n_copies x n_fracs single calls, each five
+// launches and a download.  The draw of a barcode depends on (identity, seed) alone, so one draw per (alignment, copy) serves every
+// fraction.  The same five stages, the selection s = fraction x n_copies + copy a grid dimension, every array of the single call
+// (block counts / offsets, block end maxima, difference array, outputs, summary) once per selection:
+//   k_selc_count    grid (blocks, copies): one draw per alignment, a ballot per fraction, the kept counts of the block per fraction
+//   k_selc_offsets  a workgroup per selection: k_sel_offsets' work
+//   k_selc_scatter  grid (blocks, copies): the draws kept in registers; per fraction k_sel_scatter's rounds, the one LDS window of
+//                   the difference array zeroed and flushed per fraction
+//   k_selc_loci     a workgroup per selection: k_sel_loci's work
+//   k_selc_windows  grid (loci / 4, selections): k_sel_windows' work
+// Seeds and thresholds travel in the launch's arguments, SEL_CP_COPIES x SEL_CP_FRACS of them: a larger batch takes several launches
+// of the two record stages (a draw is then made once per group of SEL_CP_FRACS fractions).
+#define SEL_CP_COPIES 32
+#define SEL_CP_FRACS 32
+
+struct SelCopies {
+    unsigned long long seed[SEL_CP_COPIES];   // of copies c0 .. c0 + gridDim.y - 1
+    unsigned long long thr[SEL_CP_FRACS];     // of fractions f0 .. f0 + n_f - 1: floor(f * 2^32), 2^32: everything
+    uint32_t c0, f0, n_f;
+    uint32_t n_copies;                        // of the whole call: selection s = f * n_copies + c
+};
+
+// the copy's record i of a block round, whether it can be kept at all (a barcode id the table holds) and its barcode's draw
+__device__ __forceinline__ bool selc_draw(const smc_dev_aln* __restrict__ aln, uint32_t i, uint32_t n_aln,
+                                          const unsigned long long* __restrict__ ident, uint32_t n_ids, unsigned long long seed, uint32_t& draw) {
+    draw = 0u;
+    if (i >= n_aln) return false;
+    const uint32_t g = aln[i].bc_gid;
+    if (g >= n_ids) return false;
+    draw = sel_draw(ident[g], seed);
+    return true;
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_selc_count(const char* __restrict__ aln_base, unsigned long long aln_stride, uint32_t n_aln,
+                                                          const unsigned long long* __restrict__ ident, uint32_t n_ids, SelCopies K,
+                                                          uint32_t n_blk, uint32_t* __restrict__ blk_cnt_all) {
+    __shared__ uint32_t cnt[SEL_CP_FRACS];
+    const uint32_t t = threadIdx.x, c = K.c0 + blockIdx.y, base = blockIdx.x * (uint32_t)SEL_ITEMS;
+    const smc_dev_aln* aln = (const smc_dev_aln*)(aln_base + (size_t)c * aln_stride);
+    if (t < SEL_CP_FRACS) cnt[t] = 0u;
+    __syncthreads();
+#pragma unroll 1
+    for (int r = 0; r < SEL_ROUNDS; ++r) {
+        uint32_t draw;
+        const bool ok = selc_draw(aln, base + (uint32_t)r * SEL_BLOCK + t, n_aln, ident, n_ids, K.seed[blockIdx.y], draw);
+        for (uint32_t f = 0; f < K.n_f; ++f) {
+            const unsigned long long m = __ballot(ok && (unsigned long long)draw < K.thr[f]);
+            if ((t & (WAVE - 1)) == 0 && m) atomicAdd(&cnt[f], (uint32_t)__popcll(m));
+        }
+    }
+    __syncthreads();
+    if (t < K.n_f) blk_cnt_all[((size_t)(K.f0 + t) * K.n_copies + c) * (n_blk + 1u) + blockIdx.x] = cnt[t];
+}
+
+__global__ __launch_bounds__(SEL_SCAN) void k_selc_offsets(uint32_t* __restrict__ blk_cnt_all, uint32_t n_blk, int32_t* __restrict__ diff_all,
+                                                           uint32_t n_diff, uint32_t* __restrict__ summary) {
+    const size_t s = blockIdx.x;
+    sel_offsets_body(blk_cnt_all + s * (n_blk + 1u), n_blk, diff_all + s * n_diff, n_diff, summary + 4 * s);
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_selc_scatter(const char* __restrict__ aln_base, unsigned long long aln_stride, uint32_t n_aln,
+                                                            const unsigned long long* __restrict__ ident, uint32_t n_ids, SelCopies K,
+                                                            uint32_t n_blk, const uint32_t* __restrict__ blk_off_all, int32_t start0,
+                                                            uint32_t n_loci, smc_dev_aln* __restrict__ out_all, uint32_t* __restrict__ orig_all,
+                                                            int32_t* __restrict__ diff_all, int32_t* __restrict__ blk_maxend_all) {
+    __shared__ int32_t win[SEL_WIN];
+    __shared__ uint32_t wcnt[SEL_BLOCK / WAVE];
+    __shared__ int32_t wmax[SEL_BLOCK / WAVE];
+    const uint32_t t = threadIdx.x, wv = t / WAVE, lane = t & (WAVE - 1), c = K.c0 + blockIdx.y, base = blockIdx.x * (uint32_t)SEL_ITEMS;
+    const smc_dev_aln* aln = (const smc_dev_aln*)(aln_base + (size_t)c * aln_stride);
+    uint32_t draw[SEL_ROUNDS];
+    bool ok[SEL_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < SEL_ROUNDS; ++r) ok[r] = selc_draw(aln, base + (uint32_t)r * SEL_BLOCK + t, n_aln, ident, n_ids, K.seed[blockIdx.y], draw[r]);
+    // (the block's alignments are sorted by position: the window starts at the first one's)
+    const int32_t wbase = max(aln[base].pos, start0) - start0;
+#pragma unroll 1
+    for (uint32_t f = 0; f < K.n_f; ++f) {
+        const size_t s = (size_t)(K.f0 + f) * K.n_copies + c;
+        const unsigned long long thr = K.thr[f];
+        smc_dev_aln* out = out_all + s * n_aln;
+        uint32_t* orig_index = orig_all + s * n_aln;
+        int32_t* diff = diff_all + s * ((size_t)n_loci + 1u);
+        for (uint32_t k = t; k < SEL_WIN; k += SEL_BLOCK) win[k] = 0;
+        __syncthreads();
+        uint32_t dst = blk_off_all[s * (n_blk + 1u) + blockIdx.x];
+        int32_t me = INT_MIN;
+        auto add = [&](int32_t x, int32_t d) {
+            const uint32_t k = (uint32_t)(x - wbase);
+            if (k < (uint32_t)SEL_WIN) atomicAdd(&win[k], d); else atomicAdd(&diff[x], d);
+        };
+#pragma unroll
+        for (int r = 0; r < SEL_ROUNDS; ++r) {
+            const uint32_t i = base + (uint32_t)r * SEL_BLOCK + t;
+            const bool keep = ok[r] && (unsigned long long)draw[r] < thr;
+            const unsigned long long m = __ballot(keep);
+            const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (lane == 0) wcnt[wv] = (uint32_t)__popcll(m);
+            __syncthreads();
+            uint32_t before = 0, all = 0;
+            for (uint32_t w = 0; w < SEL_BLOCK / WAVE; ++w) { before += w < wv ? wcnt[w] : 0u; all += wcnt[w]; }
+            if (keep) {
+                const smc_dev_aln a = aln[i];
+                out[dst + before + rank] = a;
+                orig_index[dst + before + rank] = i;
+                const int32_t lo = max(a.pos, start0) - start0, hi = (int32_t)min<int64_t>((int64_t)a.end, (int64_t)start0 + n_loci) - start0;
+                if (lo < hi) { add(lo, 1); add(hi, -1); }
+                me = max(me, a.end);
+            }
+            dst += all;
+            __syncthreads();                               // (wcnt is rewritten by the next round)
+        }
+        for (int o = WAVE / 2; o > 0; o >>= 1) me = max(me, __shfl_xor(me, o));
+        if (lane == 0) wmax[wv] = me;
+        __syncthreads();
+        if (t == 0) {
+            int32_t m = INT_MIN;
+            for (int w = 0; w < SEL_BLOCK / WAVE; ++w) m = max(m, wmax[w]);
+            blk_maxend_all[s * (n_blk + 1u) + blockIdx.x] = m;
+        }
+        for (uint32_t k = t; k < SEL_WIN; k += SEL_BLOCK) {
+            const int32_t v = win[k];
+            if (v && wbase + (int32_t)k <= (int32_t)n_loci) atomicAdd(&diff[wbase + (int32_t)k], v);
+        }
+        __syncthreads();                                   // (win and wmax are rewritten by the next fraction)
+    }
+}
+
+__global__ __launch_bounds__(SEL_SCAN) void k_selc_loci(int32_t* __restrict__ blk_maxend_all, uint32_t n_blk, const int32_t* __restrict__ diff_all,
+                                                        uint32_t n_loci, smc_dev_locus* __restrict__ loc_out, uint32_t* __restrict__ summary) {
+    const size_t s = blockIdx.x;
+    sel_loci_body(blk_maxend_all + s * (n_blk + 1u), n_blk, diff_all + s * ((size_t)n_loci + 1u), n_loci, loc_out + s * n_loci, summary + 4 * s);
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_selc_windows(const smc_dev_aln* __restrict__ out_all, uint32_t n_aln,
+                                                            const uint32_t* __restrict__ blk_off_all, const int32_t* __restrict__ blk_runmax_all,
+                                                            uint32_t n_blk, int32_t start0, uint32_t n_loci, smc_dev_locus* __restrict__ loc_out) {
+    const size_t s = blockIdx.y;
+    sel_windows_body(out_all + s * n_aln, blk_off_all + s * (n_blk + 1u), blk_runmax_all + s * (n_blk + 1u), n_blk, start0, n_loci,
+                     loc_out + s * n_loci);
 }

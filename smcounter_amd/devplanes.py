@@ -1280,6 +1280,74 @@ def select_run(eng, up: RunOnDevice, A, lo: int, mask=None, idents=None, frac: f
     return sel, counts, d_orig
 
 
+SEL_MAX_SELECTIONS = 2048      # SMC_SEL_MAX_SELECTIONS
+
+
+class CopySelections(object):
+    """What select_copies returns: of[f][c] = select_run's triple (RunOnDevice of the kept alignments, counts dict for build_run, the
+    orig_index) for copy c at fracs[f] - views over the four buffers this owns until free(): the records, orig_index and descriptors
+    of selection s = f x copies + c at s x n_aln / s x n_aln / s x nl entries, and the summaries (`summary`: uint32 [F, B, 3] = kept,
+    deepest, slots, on the host).  The B selections of one fraction lie at the constant strides `strides` (records, orig_index,
+    descriptors; bytes), so they can be handed on as one batch."""
+
+    def __init__(self, bufs, of, summary, strides):
+        self.bufs, self.of, self.summary, self.strides = bufs, of, summary, strides
+
+    def free(self):
+        for b in self.bufs:
+            b.free()
+        self.bufs = []
+
+
+def select_copies(eng, runs, A, lo: int, idents, seeds, fracs) -> CopySelections:
+    """smc_select_alignments_copies: the philox selections of the B copies `runs` of one run (RunOnDevices of equal n_aln whose records
+    stand at a constant stride - _SpikedCopies.runs - or are the same array; A: the run's counts) at every fraction of `fracs`, copy c
+    drawn with seeds[c] -> CopySelections.  Every selection is what select_run(eng, runs[c], A, lo, idents=idents, frac=fracs[f],
+    seed=seeds[c]) gives; one call and ONE download (the summaries) in place of B x F of each."""
+    from .engine import DevBuf
+    B, F = len(runs), len(fracs)
+    if B < 1 or F < 1 or B * F > SEL_MAX_SELECTIONS or len(seeds) != B:
+        raise ValueError("select_copies: %d copies (%d seeds) x %d fractions; 1 .. %d selections" % (B, len(seeds), F, SEL_MAX_SELECTIONS))
+    n, nl, S = runs[0].n_aln, int(A["nl"]), B * F
+    base = runs[0].aln.data_ptr()
+    stride = runs[1].aln.data_ptr() - base if B > 1 else 0
+    if any(r.n_aln != n or r.aln.data_ptr() != base + c * stride for c, r in enumerate(runs)):
+        raise ValueError("select_copies: the copies' records do not stand at one stride, or differ in length")
+    idents = np.ascontiguousarray(idents, np.uint64)[:int(A["n_bc"])]
+    seeds = np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], np.uint64)
+    fr = np.ascontiguousarray(fracs, np.float64)
+    sa, so, sl = 36 * n, 4 * n, 16 * nl
+    bufs = [DevBuf(eng, max(1, sa) * S + 256), DevBuf(eng, max(1, so) * S + 256), DevBuf(eng, max(1, sl) * S + 256), DevBuf(eng, 16 * S + 256)]
+    d_id = DevBuf(eng, 8 * max(1, len(idents)) + 256).upload(idents if len(idents) else np.zeros(1, np.uint64))
+    try:
+        _lib.check(eng.L.smc_select_alignments_copies(eng.ctx, base, int(stride), B, n, None, nl, int(lo), d_id.data_ptr(), len(idents),
+                                                      seeds.ctypes.data, fr.ctypes.data, F, bufs[0].data_ptr(), bufs[1].data_ptr(),
+                                                      bufs[2].data_ptr(), bufs[3].data_ptr(), ctypes.c_void_p(0)),
+                   "smc_select_alignments_copies")
+        summary = bufs[3].download(np.uint32, 4 * S).reshape(F, B, 4)[:, :, :3].copy()     # (the default stream: behind the kernels)
+        of = []
+        for f in range(F):
+            of.append([])
+            for c, up in enumerate(runs):
+                s = f * B + c
+                kept, deepest, slots = (int(v) for v in summary[f, c])
+                d_orig = _BufView(bufs[1], s * so)
+                sel = RunOnDevice(_BufView(bufs[0], s * sa), up.cig, up.bq, _BufView(bufs[2], s * sl), up.ref, kept, None,
+                                  pairs_used=up.pairs_used)
+                counts = dict(nl=nl, n_slots=slots, n_bc=A["n_bc"], n_pair=A["n_pair"], status=A["status"], deepest=deepest, aln=None)
+                if A["status"] & 1:
+                    # (select_run's gather: alignments flagged neither READ1 nor READ2)
+                    counts["aln"] = A["aln"][d_orig.download(np.uint32, kept)] if kept else A["aln"][:0]
+                of[f].append((sel, counts, d_orig))
+    except BaseException:
+        for b in bufs:
+            b.free()
+        raise
+    finally:
+        d_id.free()
+    return CopySelections(bufs, of, summary, (sa, so, sl))
+
+
 # ---- in-run dilution of listed variants (--dsAF): tools.ds_allele_fraction's drop of the barcodes that carry a listed allele
 AF_DOMAIN = 0x64734146         # counter word 2 of the barcode draw ("dsAF": tools.ds_allele_fraction.philox_word0)
 AF_MAX_INS = 255               # SMC_AF_MAX_INS: inserted letters of a listed insertion
@@ -2875,13 +2943,17 @@ class _SpikedCopies(object):
             b.free()
 
 
-def _copy_room(run: AfRun, svar, four: bool):
+def _copy_room(run: AfRun, svar, four: bool, n_selections: int = 0):
     """How many spiked copies of the kept run one rewrite call makes: as many as fit SPIKE_REP_BATCH_BYTES - a copy is its records and
     pair pool or, with `four` counters, records, both pools at their capacities and the call's scratch of 8 bytes per alignment -,
-    AF_REP_BATCH_SLOTS read slots and SMC_SPIKE_MAX_COPIES, and at least one -> (copies, spike_indel_caps of `svar` on the run or None)."""
+    AF_REP_BATCH_SLOTS read slots and SMC_SPIKE_MAX_COPIES, and at least one -> (copies, spike_indel_caps of `svar` on the run or None).
+    `n_selections` (--spikeScanDepth: the fractions): a copy also has that many selections alive beside it (select_copies: records,
+    orig_index and descriptors at their capacities), and copies x selections stays within SEL_MAX_SELECTIONS."""
     n, caps = run.up.n_aln, spike_indel_caps(run.A, svar) if four else None
     per_copy = sum(spike_indel_copy_strides(n, *caps)) + 8 * n if four else sum(spike_copy_strides(n, len(run.A["bq"]) // 2))
-    return max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per_copy, AF_REP_BATCH_SLOTS // max(1, int(run.A["n_slots"]) + run.nl))), caps
+    per_copy += n_selections * (40 * max(1, n) + 16 * max(1, run.nl) + 16)
+    return max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per_copy, AF_REP_BATCH_SLOTS // max(1, int(run.A["n_slots"]) + run.nl),
+                      SEL_MAX_SELECTIONS // max(1, n_selections))), caps
 
 
 def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed, bits,
@@ -3200,7 +3272,7 @@ def scan_called_host(text, v, threshold: int, repeats) -> bool:
 
 
 def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed,
-               bits, threshold, repeats, check0, indel: dict = None):
+               bits, threshold, repeats, check0, indel: dict = None, depth: dict = None):
     """The _SpikedCopies of the run at one target, one per seed of `part_seeds`, each built behind the other into one device batch and
     the batch called with one plan - _spike_rep_call's way - but the rows stay in HBM: smc_scan_detect gives a verdict per (copy,
     listed locus), and only the rows it leaves to the host come down, one by one, to be printed and cut the existing way.  run.group:
@@ -3211,15 +3283,85 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
     af_run_variants' records of run.group - they stand where `listed` does -, want: per copy and variant the counts call's (N, V1))):
     every build leaves its extras list in HBM and makes no table (BuildExtras); smc_scan_detect_keys resolves the key's allele id per
     copy from them; replicate 0's (N, V1) on the copy must be the counts call's; and the table of a row that comes down is made from
-    its copy's extras, the texts through copy_allele_key on the copy, which is alive until this call returns."""
+    its copy's extras, the texts through copy_allele_key on the copy, which is alive until this call returns.
+    `depth` (--spikeScanDepth: dict(fracs, params, thresholds: per fraction the cell's VcParams and truncated-PI cut, var, var_ins:
+    af_run_variants' records of run.group, want: per fraction, copy and variant the counts call's (N', V1'))): behind the full-depth
+    batch ONE select_copies call makes the copies' selections at every fraction, each copy with its own seed; per fraction the B
+    selections are built behind each other into one batch and called with one plan at the cell's params, the verdicts at the cell's
+    cut - with `indel` the selections' records at the batched stride, the CIGAR words and pairs at the copies' -; replicate 0's (N',
+    V1') by smc_allele_carriers on its selection must be the counts call's.
+    -> (called, per fraction the same, the verdicts the host decided over all of them, 1 + the fractions built), or NARROW."""
     from . import vc
     from .engine import DevBuf
     A, lo, nl, chrom = run.A, run.lo, run.nl, run.chrom
     B, G = len(part_seeds), len(run.group)
     flag, entry = ("--spikeScan", "smc_scan_detect") if indel is None else ("--spikeScanIndel", "smc_scan_detect_keys")
     copies = _SpikedCopies(eng, run, svar, part_seeds, thr, P, *((indel["ins"], indel.get("caps")) if indel is not None else ()))
-    runs, extras, xbufs = copies.runs, None, []
-    d = d_rows = plan = None
+    runs, extras, xbufs, sels = copies.runs, None, [], None
+
+    def decide(kept_runs, Pb, cut, where, key_of, what):
+        """`kept_runs` built into one batch and called with one plan at params `Pb`; the verdicts at the cut `cut` -> (called, the
+        verdicts the host decided), or NARROW.  where: scan_detect_keys' `copies` of these builds; key_of(c): allele_key of build c."""
+        d = d_rows = plan = None
+        try:
+            built = _build_copies(eng, run, B, kept_runs, Pb, bits, flag, fasta, max_depth, sampler, sampler_seed, extras)
+            if built == NARROW:
+                return NARROW
+            d = built
+            plan = eng.make_plan(d.loci())
+            d_rows = plan.run_into_devbuf([d.words, d.uaux[0]], Pb)
+            if indel is None:
+                rec, todo = scan_detect(eng, d_rows, B, nl, listed, cut)         # (its downloads wait for the plan's kernels)
+                table_of = lambda c, a: d.tables[c * nl + a]
+            else:
+                rec, todo, _ = scan_detect_keys(
+                    eng, d_rows, B, nl, indel["var"], indel["var_ins"], where,
+                    dict(x=xbufs[0].data_ptr(), cnt=xbufs[1].data_ptr(), x_stride=5 * xcap, cnt_stride=2, xcap=xcap), cut)
+                lists, keys = {}, {}
+
+                def table_of(c, a):
+                    if c not in lists:
+                        n_x = min(int(extras[c].n), xcap)
+                        lists[c] = extras[c].x.download(np.uint32, 5 * n_x).reshape(n_x, 5) if n_x else np.zeros((0, 5), np.uint32)
+                        keys[c] = key_of(c)
+                    return extras_table(lists[c], a, keys[c], chrom, lo, fasta)
+            verdict = (rec["mt_verdict"] >> 30).astype(np.int64)
+            called = verdict == abi.SCAN_CALLED
+            theirs = set(int(x) for x in todo)
+            if theirs != set(int(x) for x in np.flatnonzero(verdict.reshape(-1) == abi.SCAN_HOST)):
+                raise RuntimeError("%s: %s:%d-%d%s: the list of the records for the host is not that of the HOST verdicts" %
+                                   (flag, chrom, lo + 1, lo + nl, what))
+            mine = sorted(theirs | (set(check0 * G + g for g in range(G)) if check0 is not None else set()))
+            if mine:
+                at = [int(listed["offset"][i % G]) for i in mine]
+                got = np.empty(len(mine), abi.ROW_DTYPE)
+                for n, (i, a) in enumerate(zip(mine, at)):
+                    d_rows.download(abi.ROW_DTYPE, 1, ((i // G) * nl + a) * abi.ROW_DTYPE.itemsize, out=got[n:n + 1])
+                view = vc.LocusView([chrom] * len(mine), [lo + 1 + a for a in at], [run.run_ref[a] if a < len(run.run_ref) else "" for a in at],
+                                    [table_of(i // G, a) for i, a in zip(mine, at)])
+                text = vc._strings(got, view, Pb, fasta)
+                for i, line in zip(mine, text):
+                    v = variants[run.group[i % G]]
+                    if line.startswith(vc.EXC_PREFIX):
+                        raise RuntimeError("%s: %s:%d%s: the row of seed %d could not be printed:\n%s" %
+                                           (flag, v.chrom, v.pos, what, int(part_seeds[i // G]), line))
+                    host = scan_called_host(line, v, cut, repeats)
+                    if i in theirs:
+                        called[i // G, i % G] = host
+                    elif host != bool(called[i // G, i % G]):
+                        who = "replicate 0 of" if indel is None else "seed %d at" % int(part_seeds[i // G])
+                        raise RuntimeError("%s: %s %s:%d %s>%s%s: %s says %s (PI %.17g, threshold %d), the row as "
+                                           "the run would print and cut it says %s:\n%s" %
+                                           (flag, who, v.chrom, v.pos, v.ref, v.alt, what, entry,
+                                            "CALLED" if called[i // G, i % G] else "NOT", float(rec[i // G, i % G]["pi"]),
+                                            cut, "called" if host else "not called", line))
+            return called, len(theirs)
+        finally:
+            if plan is not None:
+                plan.close()
+            for b in (d_rows, d):
+                if b is not None:
+                    b.free()
     try:
         if indel is not None and copies.totals[:, 2].any():
             raise _lib.SmcError("smc_spike_indels_reps: a copy of %s:%d-%d did not fit spike_indel_caps' bounds" % (chrom, lo + 1, lo + nl))
@@ -3233,67 +3375,43 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
         # (every alignment is there: the decoder's allele keys hold, as in the main pass's spike branch; a record the indel rewrite
         # relocated has its texts in the copy - no table is made of those builds here)
         kept = (_KeptRun(runs[c], A, None, A, run.bam.allele_key, run.bam.barcode_name, lambda n: run.idents) for c in range(B))
-        built = _build_copies(eng, run, B, kept, P, bits, flag, fasta, max_depth, sampler, sampler_seed, extras)
-        if built == NARROW:
-            return NARROW
-        d = built
-        plan = eng.make_plan(d.loci())
-        d_rows = plan.run_into_devbuf([d.words, d.uaux[0]], P)
-        if indel is None:
-            rec, todo = scan_detect(eng, d_rows, B, nl, listed, threshold)       # (its downloads wait for the plan's kernels)
-            table_of = lambda c, a: d.tables[c * nl + a]
-        else:
-            rec, todo, _ = scan_detect_keys(
-                eng, d_rows, B, nl, indel["var"], indel["var_ins"], copies.addresses(),
-                dict(x=xbufs[0].data_ptr(), cnt=xbufs[1].data_ptr(), x_stride=5 * xcap, cnt_stride=2, xcap=xcap), threshold)
-            lists, keys = {}, {}
-
-            def table_of(c, a):
-                if c not in lists:
-                    n_x = min(int(extras[c].n), xcap)
-                    lists[c] = extras[c].x.download(np.uint32, 5 * n_x).reshape(n_x, 5) if n_x else np.zeros((0, 5), np.uint32)
-                    keys[c] = copy_allele_key(runs[c], A, run.bam.allele_key)
-                return extras_table(lists[c], a, keys[c], chrom, lo, fasta)
-        verdict = (rec["mt_verdict"] >> 30).astype(np.int64)
-        called = verdict == abi.SCAN_CALLED
-        theirs = set(int(x) for x in todo)
-        if theirs != set(int(x) for x in np.flatnonzero(verdict.reshape(-1) == abi.SCAN_HOST)):
-            raise RuntimeError("%s: %s:%d-%d: the list of the records for the host is not that of the HOST verdicts" % (flag, chrom, lo + 1, lo + nl))
-        mine = sorted(theirs | (set(check0 * G + g for g in range(G)) if check0 is not None else set()))
-        if mine:
-            at = [int(listed["offset"][i % G]) for i in mine]
-            got = np.empty(len(mine), abi.ROW_DTYPE)
-            for n, (i, a) in enumerate(zip(mine, at)):
-                d_rows.download(abi.ROW_DTYPE, 1, ((i // G) * nl + a) * abi.ROW_DTYPE.itemsize, out=got[n:n + 1])
-            view = vc.LocusView([chrom] * len(mine), [lo + 1 + a for a in at], [run.run_ref[a] if a < len(run.run_ref) else "" for a in at],
-                                [table_of(i // G, a) for i, a in zip(mine, at)])
-            text = vc._strings(got, view, P, fasta)
-            for i, line in zip(mine, text):
-                v = variants[run.group[i % G]]
-                if line.startswith(vc.EXC_PREFIX):
-                    raise RuntimeError("%s: %s:%d: the row of seed %d could not be printed:\n%s" % (flag, v.chrom, v.pos, int(part_seeds[i // G]), line))
-                host = scan_called_host(line, v, threshold, repeats)
-                if i in theirs:
-                    called[i // G, i % G] = host
-                elif host != bool(called[i // G, i % G]):
-                    who = "replicate 0 of" if indel is None else "seed %d at" % int(part_seeds[i // G])
-                    raise RuntimeError("%s: %s %s:%d %s>%s: %s says %s (PI %.17g, threshold %d), the row as "
-                                       "the run would print and cut it says %s:\n%s" %
-                                       (flag, who, v.chrom, v.pos, v.ref, v.alt, entry,
-                                        "CALLED" if called[i // G, i % G] else "NOT", float(rec[i // G, i % G]["pi"]),
-                                        threshold, "called" if host else "not called", line))
-        return called, len(theirs)
+        full = decide(kept, P, threshold, copies.addresses() if indel is not None else None,
+                      lambda c: copy_allele_key(runs[c], A, run.bam.allele_key), "")
+        if full == NARROW or depth is None:
+            return full
+        sels = select_copies(eng, runs, A, lo, run.idents, part_seeds, depth["fracs"])
+        of_cell, n_host = [], full[1]
+        for f, frac in enumerate(depth["fracs"]):
+            what = " x fraction %g" % frac
+            if check0 is not None:
+                sel, counts, _ = sels.of[f][check0]
+                copies.check_carriers(check0, sel, counts, depth["want"][f][check0], depth["var"], depth["var_ins"], variants,
+                                      "--spikeScanDepth", what)
+            kept = [_KeptRun(*sels.of[f][c], A, run.bam.allele_key, run.bam.barcode_name, lambda n: run.idents,
+                             copy=runs[c] if indel is not None else None) for c in range(B)]
+            where = None
+            if indel is not None:
+                # (the records of this fraction's selections at the batched stride; n_aln bounds the index an extras entry holds: no
+                # build walks more than its kept records, and the largest kept count stays inside every selection's own stretch)
+                where = dict(copies.addresses(), aln=sels.bufs[0].data_ptr() + f * B * sels.strides[0],
+                             strides=(sels.strides[0],) + tuple(copies.strides[1:]), n_aln=max(k.run.n_aln for k in kept))
+            cell = decide(iter(kept), depth["params"][f], depth["thresholds"][f], where, lambda c: kept[c].allele_key, what)
+            if cell == NARROW:
+                return NARROW
+            of_cell.append(cell[0])
+            n_host += cell[1]
+        return full[0], of_cell, n_host, 1 + len(of_cell)
     finally:
-        if plan is not None:
-            plan.close()
-        for b in [d_rows, d] + xbufs:
-            if b is not None:
-                b.free()
+        for b in xbufs:
+            b.free()
+        if sels is not None:
+            sels.free()
         copies.free()
 
 
 def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n_reps: int, eng, threshold: int, repeats,
-               sampler: str = "reference", sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, indel: bool = False):
+               sampler: str = "reference", sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, indel: bool = False,
+               depth: dict = None):
     """The stage of --spikeScan.  variants: the scan's SNV at every scanned locus (tools.spike_scan_lists.scan_variants); passes: [(k,
     the indices of pass k)] (scan_passes).  A pass is the run --spikeAF <targets> --spikeVariants <its list> --spikeReps n_reps --dsSeed
     seed: replicate j has seed (seed + j) mod 2^64, and the draws, the rewrite, NM and the thresholds are that run's.
@@ -3309,6 +3427,12 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     _spike_single_counters, the counts come from one smc_spike_indel_counts call, the copies from smc_spike_indels_reps under the same
     room rule, and the verdicts from smc_scan_detect_keys (_scan_call's `indel`).  ValueError before anything is spiked: a run with a
     record at which the rewrite's 16-bit limits could bind (_refuse_indel_limits).
+    `depth` (--spikeScanDepth: dict(fracs, params, thresholds: per fraction f the VcParams of its cells - mtDepth max(1,
+    py2_round(f x mtDepth)) - and their truncated-PI cut)): a pass is then the run with --spikeDepth <fracs> (--spikeIndelDepth) beside
+    it.  One smc_spike_depth_counts (smc_spike_indel_counts) call per pass and run gives the cells' (N', V0', S', READS', V1'); behind
+    every full-depth batch ONE select_copies call makes its copies' selections at all fractions, and every fraction's are built and
+    called as one batch at the cell's params (_scan_call's `depth`).  The result gets depth_counts: uint32 [V, R, T, F, 5],
+    depth_called: bool [V, T, F, R], and the passes' dicts "selects": the select_copies calls.
     -> dict(seeds, base: per variant (N, V0), counts: uint32 [V, R, T, 3] = (S, READS, V1), called: bool [V, T, R], passes: per pass
     of `passes` dict(variants, copies, builds, host, seconds), times: dict(stage, runs, decode))."""
     import time
@@ -3331,6 +3455,11 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     spikes = [SpikeSet([variants[i] for i in members], indels=indel) for _, members in passes]
     base, counts, called = [None] * V, np.zeros((V, R, T, 3), np.uint32), np.zeros((V, T, R), bool)
     stats = [dict(variants=0, copies=0, builds=0, host=0, seconds=0.0) for _ in passes]
+    if depth is not None:
+        F = len(depth["fracs"])
+        depth = dict(depth, counts=np.zeros((V, R, T, F, 5), np.uint32), called=np.zeros((V, T, F, R), bool))
+        for st in stats:
+            st["selects"] = 0
     times = {"decode": 0.0, "runs": 0}
     order = sorted(range(V), key=lambda k: (variants[k].chrom, variants[k].pos))
     spans = _listed_spans(variants, order)
@@ -3350,23 +3479,29 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
             for p in in_run:
                 t0 = time.perf_counter()
                 run.group = [k for k in inside if pass_at[k] == p]
-                room, caps = _copy_room(run, spikes[p].chrom_variants(chrom, 0.5)[0] if indel else None, indel)
+                room, caps = _copy_room(run, spikes[p].chrom_variants(chrom, 0.5)[0] if indel else None, indel,
+                                        len(depth["fracs"]) if depth is not None else 0)
                 _scan_pass(eng, run, spikes[p], [int(local[k]) for k in run.group], variants, seeds, thr, P, fasta, max_depth, sampler,
-                           sampler_seed, threshold, repeats, room, base, counts, called, stats[p], caps)
+                           sampler_seed, threshold, repeats, room, base, counts, called, stats[p], caps, depth)
                 stats[p]["variants"] += len(run.group)
                 stats[p]["seconds"] += time.perf_counter() - t0
         finally:
             run.free()
         spans.send(len(inside))
     times["stage"] = time.perf_counter() - t_start
-    return dict(seeds=seeds, base=base, counts=counts, called=called, passes=stats, times=times)
+    out = dict(seeds=seeds, base=base, counts=counts, called=called, passes=stats, times=times)
+    if depth is not None:
+        out.update(depth_counts=depth["counts"], depth_called=depth["called"])
+    return out
 
 
 def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr, P, fasta, max_depth, sampler, sampler_seed, threshold,
-               repeats, room, base, counts, called, stat, caps=None):
+               repeats, room, base, counts, called, stat, caps=None, depth: dict = None):
     """spike_scan's work for one pass in one run: run.group are the pass's variants there (indices into `variants`), members[g] the
     place of run.group[g] in the pass's list (`spikes`).  base, counts, called and stat are filled.  `caps` (--spikeScanIndel:
-    spike_indel_caps of the pass's list on the run): the indel branch."""
+    spike_indel_caps of the pass's list on the run): the indel branch.  `depth` (--spikeScanDepth: spike_scan's dict with "counts" and
+    "called"): the cells' counters of the pass from ONE smc_spike_depth_counts (indel: smc_spike_indel_counts) call, and per batch of
+    copies the cells' verdicts (_scan_call's `depth`); both are filled."""
     A, up, lo, chrom = run.A, run.up, run.lo, run.chrom
     idents, (nm, n_indel) = run.idents, run.mism
     group = run.group
@@ -3376,32 +3511,46 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
                                                             cov, cnt0, caps is not None)
     for g, k in enumerate(group):
         base[k] = (int(cov[g].sum()), int(car[g].sum()))
-    mine = (spike_rep_counts if caps is None else spike_indel_counts)(eng, [spikes.lead_pos[m] for m in members], covers, counters, seeds,
-                                                                     thr)       # [G, R, T, 3]
+    lead = [spikes.lead_pos[m] for m in members]
+    mine = (spike_rep_counts if caps is None else spike_indel_counts)(eng, lead, covers, counters, seeds, thr)       # [G, R, T, 3]
+    cells = None
+    if depth is not None:
+        cells = (spike_depth_counts if caps is None else spike_indel_counts)(eng, lead, covers, counters, seeds, thr,
+                                                                             [frac_threshold(f) for f in depth["fracs"]])   # [G, R, T, F, 5]
     at_of = {m: n for n, m in enumerate(sorder)}
     var_at = [at_of[m] for m in members]
     listed = np.zeros(len(group), abi.SCAN_LOCUS_DTYPE)
     for g, k in enumerate(group):
         counts[k] = mine[g]
+        if cells is not None:
+            depth["counts"][k] = cells[g]
         # (--spikeScanIndel: a key has no fixed id - smc_scan_detect_keys takes `var`, and of `listed` only the offsets are read)
         listed[g] = (variants[k].pos - 1 - lo, SCAN_ALT_ID[variants[k].alt] if caps is None else 0)
-    R = len(seeds)
+    R, F = len(seeds), len(depth["fracs"]) if depth is not None else 0
     for t in range(len(thr)):
         for b in range(0, R, room):
             js = list(range(b, min(R, b + room)))
             want = [[int(mine[g, j, t, 1]) for g in range(len(group))] for j in js]
             args = (eng, run, svar, var_at, listed, [seeds[j] for j in js], thr[t], want, P, fasta, variants, max_depth, sampler, sampler_seed)
             tail = (threshold, repeats, js.index(0) if 0 in js else None)
-            if caps is not None:
-                tail += (dict(ins=spikes.ins[chrom], caps=caps, var=var, var_ins=ins,
-                              want=[[(len(covers[g]), int(mine[g, j, t, 2])) for g in range(len(group))] for j in js]),)
-            yes, n_host = _narrow_retry(eng, P, lambda bits: _scan_call(*args, bits, *tail))
+            tail += (dict(ins=spikes.ins[chrom], caps=caps, var=var, var_ins=ins,
+                          want=[[(len(covers[g]), int(mine[g, j, t, 2])) for g in range(len(group))] for j in js]) if caps is not None else None,)
+            if depth is not None:
+                tail += (dict(fracs=depth["fracs"], params=depth["params"], thresholds=depth["thresholds"], var=var, var_ins=ins,
+                              want=[[[(int(cells[g, j, t, f, 0]), int(cells[g, j, t, f, 4])) for g in range(len(group))] for j in js]
+                                    for f in range(F)]),)
+            got = _narrow_retry(eng, P, lambda bits: _scan_call(*args, bits, *tail))
+            yes, n_host, builds = (got[0], got[2], got[3]) if depth is not None else (got[0], got[1], 1)
             for c, j in enumerate(js):
                 for g, k in enumerate(group):
                     called[k, t, j] = yes[c, g]
+                    for f in range(F):
+                        depth["called"][k, t, f, j] = got[1][f][c, g]
             stat["copies"] += len(js)
-            stat["builds"] += len(js)
+            stat["builds"] += len(js) * builds
             stat["host"] += n_host
+            if depth is not None:
+                stat["selects"] = stat.get("selects", 0) + 1
 
 
 def _fnv64(text: str) -> int:

@@ -690,13 +690,16 @@ def scan(args):
     down-sampling flag beside it, a target outside (0, 1) or listed twice, more than MAX_TARGETS, R outside REPS_MIN .. REPS_MAX or no
     integer, a stride below 1 or no integer, an unknown ALT rule.
     --spikeScanIndel adds "indel": ("del" or "dup", the length) to the dict.  SystemExit: the flag without --spikeScan or beside
-    --spikeScanAlt, a rule that is neither del<d> nor dup<s> with a length in 1 .. 255, a stride below the footprint's."""
+    --spikeScanAlt, a rule that is neither del<d> nor dup<s> with a length in 1 .. 255, a stride below the footprint's.
+    --spikeScanDepth adds "fracs": the barcode fractions of the scan's depth axis.  SystemExit: the flag without --spikeScan, text that
+    is no list of numbers, a fraction outside (0, 1] or listed twice, more than MAX_CELLS targets x fractions."""
     from .tools import spike_scan_lists as lists
     text, r, stride, alt = (getattr(args, f, None) for f in SCAN_FLAGS)
     indel = getattr(args, "spikeScanIndel", None)
+    fracs = getattr(args, "spikeScanDepth", None)
     given = lambda x: x not in (None, "", False)
     if not given(text):
-        for flag, value in zip(SCAN_FLAGS[1:] + ("spikeScanIndel",), (r, stride, alt, indel)):
+        for flag, value in zip(SCAN_FLAGS[1:] + ("spikeScanIndel", "spikeScanDepth"), (r, stride, alt, indel, fracs)):
             if given(value):
                 raise SystemExit("--%s belongs to --spikeScan: it needs --spikeScan" % flag)
         return None
@@ -732,6 +735,19 @@ def scan(args):
             lists.check_indel_stride(out["indel"], stride)
         except ValueError as e:
             raise SystemExit(str(e))
+    if given(fracs):
+        try:
+            fr = [float(x) for x in str(fracs).split(",") if x.strip()]
+        except ValueError:
+            raise SystemExit("--spikeScanDepth: comma-separated fractions in (0, 1] expected, got %r" % (fracs,))
+        if not fr or any(not (0.0 < f <= 1.0) for f in fr):
+            raise SystemExit("--spikeScanDepth: every fraction must lie in (0, 1], got %r" % (fracs,))
+        if len(set("%g" % f for f in fr)) != len(fr):
+            raise SystemExit("--spikeScanDepth: a fraction is listed twice (the cells' files would share a name), got %r" % (fracs,))
+        if len(ts) * len(fr) > MAX_CELLS:
+            raise SystemExit("--spikeScanDepth: %d targets x %d fractions = %d cells, at most %d" % (len(ts), len(fr), len(ts) * len(fr),
+                                                                                                   MAX_CELLS))
+        out["fracs"] = fr
     return out
 
 
@@ -781,3 +797,92 @@ def write_scan(out_prefix: str, loci, variants, targets, entries, lods=None) -> 
     with open(out_prefix + ".spikeScan.t95.bedgraph", "w") as fh:
         for chrom, pos, i in loci:
             fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "1" if i is None or t95s[i] == dsaf.NA else t95s[i]))
+
+
+# ---- --spikeScanDepth: the scan's pages per barcode depth
+SCAN_DEPTH_SENSITIVITY_HEADER = tuple(c for c in DEPTH_SENSITIVITY_HEADER if c not in ("PI_MEAN", "PI_MIN"))
+SCAN_NEED_HEADER = ("CHROM", "POS", "REF", "ALT", "TARGET", "N", "F95", "MTDEPTH95", "N95")
+
+
+def scan_depth_mt(mt_depth: int, frac: float) -> int:
+    """The mtDepth of a cell at fraction `frac`: what --dsMT f (and --spikeDepth f) gets from the run's mtDepth."""
+    from .py2compat import py2_round
+    return max(1, int(py2_round(frac * mt_depth)))
+
+
+def scan_depth_sensitivity_line(v, target, frac, mt_depth, per) -> str:
+    """depth_sensitivity_line() without PI_MEAN and PI_MIN (the scan keeps no row); N_MEAN stays."""
+    f = depth_sensitivity_line(v, target, frac, mt_depth, per).split("\t")
+    drop = {DEPTH_SENSITIVITY_HEADER.index(c) for c in ("PI_MEAN", "PI_MIN")}
+    return "\t".join(x for n, x in enumerate(f) if n not in drop)
+
+
+def f95(depths, rates):
+    """dsaf.t95's rule on the depth axis: the smallest of `depths` (the listed fractions and 1 = full) whose rate is at least 0.95
+    together with every larger depth's, or None when full depth fails -> the index into `depths`, or None."""
+    best = dsaf.t95(depths, rates)
+    return None if best is None else next(n for n, d in enumerate(depths) if d == best)
+
+
+def need_line(v, target, n: int, depths, mt_depths, rates, n_means) -> str:
+    """One line of the need page: variant `v` at `target` with N covering barcodes at full depth; depths / mt_depths / rates / n_means:
+    per depth of the axis (the listed fractions, then 1 = full) its mtDepth, detection rate and mean covering barcodes."""
+    k = f95(depths, rates)
+    return "\t".join([v.chrom, "%d" % v.pos, v.ref, v.alt, dsaf.target_text(target), "%d" % n] +
+                     ([dsaf.NA] * 3 if k is None else ["%g" % depths[k], "%d" % mt_depths[k], dsaf.frac_text(n_means[k])]))
+
+
+def write_scan_depth(out_prefix: str, loci, variants, targets, fracs, mt_depth: int, full_entries, entries) -> None:
+    """The pages of --spikeScanDepth.  loci, variants, targets: write_scan's; full_entries[(i, t)]: the full-depth replicates of variant
+    i at targets[t] (write_scan's entries); entries[(i, t, f)]: those of the cell at fracs[f] (scan_entry with the cell's counters).
+      <outPrefix>.spikeScan.depth.sensitivity.txt   a line per scanned locus, target and fraction (scan_depth_sensitivity_line)
+      <outPrefix>.spikeScan.depth.curve.txt         depth_curve_line per scanned locus: full, then every fraction
+      <outPrefix>.spikeScan<t>.dsMT<f>.rate.bedgraph  chrom, pos - 1, pos, RATE of the cell - the page's text - per scanned locus
+      <outPrefix>.spikeScan.dsMT<f>.t95.bedgraph    chrom, pos - 1, pos, T95 at that depth; 1 where it is NA and at a skipped locus
+      <outPrefix>.spikeScan.depth.need.txt          need_line per scanned locus and target
+      <outPrefix>.spikeScan<t>.f95.bedgraph         chrom, pos - 1, pos, F95 of the target; 2 - above the axis - where it is NA and at
+                                                    a skipped locus"""
+    T, F = len(targets), len(fracs)
+    mts = [scan_depth_mt(mt_depth, f) for f in fracs]
+    depths = list(fracs) + ([] if any(f == 1.0 for f in fracs) else [1.0])
+    depth_mts = mts + ([] if len(depths) == F else [mt_depth])
+    i_rate = SCAN_DEPTH_SENSITIVITY_HEADER.index("RATE")
+    i_t95 = len(DEPTH_CURVE_HEADER) + T
+    rates = {}                                   # (t, f) -> per variant the page's RATE text
+    t95s = [[] for _ in range(F)]
+    f95s = [[] for _ in range(T)]
+    with open(out_prefix + ".spikeScan.depth.sensitivity.txt", "w") as fs, open(out_prefix + ".spikeScan.depth.curve.txt", "w") as fc, \
+            open(out_prefix + ".spikeScan.depth.need.txt", "w") as fn:
+        fs.write("\t".join(SCAN_DEPTH_SENSITIVITY_HEADER) + "\n")
+        fc.write("\t".join(depth_curve_header(targets)) + "\n")
+        fn.write("\t".join(SCAN_NEED_HEADER) + "\n")
+        for i, v in enumerate(variants):
+            for t, target in enumerate(targets):
+                for f, frac in enumerate(fracs):
+                    line = scan_depth_sensitivity_line(v, target, frac, mts[f], entries[(i, t, f)])
+                    rates.setdefault((t, f), []).append(line.split("\t")[i_rate])
+                    fs.write(line + "\n")
+                # (the axis: the listed fractions; full depth stands for 1 where 1 is not listed)
+                per = [entries[(i, t, f)] for f in range(F)] + ([] if len(depths) == F else [full_entries[(i, t)]])
+                line = need_line(v, target, full_entries[(i, t)][0][0]["N"], depths, depth_mts,
+                                 [float(_called(v, p)) / len(p) for p in per], [_n_mean(p) for p in per])
+                f95s[t].append(line.split("\t")[SCAN_NEED_HEADER.index("F95")])
+                fn.write(line + "\n")
+            fc.write(depth_curve_line(v, None, [mt_depth] * T, targets, [full_entries[(i, t)] for t in range(T)]) + "\n")
+            for f, frac in enumerate(fracs):
+                line = depth_curve_line(v, frac, [mts[f]] * T, targets, [entries[(i, t, f)] for t in range(T)])
+                t95s[f].append(line.split("\t")[i_t95])
+                fc.write(line + "\n")
+    for t, target in enumerate(targets):
+        for f, frac in enumerate(fracs):
+            with open("%s.spikeScan%g.dsMT%g.rate.bedgraph" % (out_prefix, target, frac), "w") as fh:
+                for chrom, pos, i in loci:
+                    if i is not None:
+                        fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), rates[(t, f)][i]))
+        with open("%s.spikeScan%g.f95.bedgraph" % (out_prefix, target), "w") as fh:
+            for chrom, pos, i in loci:
+                fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "2" if i is None or f95s[t][i] == dsaf.NA else f95s[t][i]))
+    for f, frac in enumerate(fracs):
+        with open("%s.spikeScan.dsMT%g.t95.bedgraph" % (out_prefix, frac), "w") as fh:
+            for chrom, pos, i in loci:
+                fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "1" if i is None or t95s[f][i] == dsaf.NA else t95s[f][i]))

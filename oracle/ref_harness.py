@@ -44,7 +44,11 @@ class _Capture(object):
         self.round2 = []     # arguments of round(x, 2) in call order -> PI_A, PI_T, PI_G, PI_C, PI_alt
         self.fisher = []     # (table, oddsratio, pvalue)
         self.calprob = []    # per-UMI posterior dicts, in bcKeys order
-        self.final = []      # finalDict.items() as handed to sorted() (smCounter.py:534)
+        self.final = []      # the argument of the LAST sorted() call if its items are tuples, else [] - the sorted() calls of
+                             # isHPorLowComp (:156, lists of counts) empty it again, so it holds finalDict.items() (:534) only for
+                             # loci that do not reach filterVariants.  tie_ambiguous is computed from it as it is: the stored goldens
+                             # carry that value.
+        self.final_items = []  # finalDict.items() as handed to sorted() at :534, in the emulated py2 dict's order; never emptied
         self.sampled = False # random.sample ran (smCounter.py:497-498)
 
 
@@ -59,6 +63,7 @@ def _py2_sorted(iterable, key=None, reverse=False):
         order = py2compat.py2_dict_order([k for k, _ in items])
         rank = {k: i for i, k in enumerate(order)}
         items.sort(key=lambda kv: rank[kv[0]])
+        CAP.final_items = [(k, float(v)) for k, v in items]
     return builtins.sorted(items, key=key, reverse=reverse)
 
 
@@ -188,7 +193,8 @@ def run_reference(pb, params, chroms, use_wrapper=True):
     """Call the reference's vc_wrapper() per locus.  `chroms`: {name: sequence} fake FASTA.
 
     Returns a list of dicts: row (the TAB-joined string vc() returns), pi_raw (unrounded
-    PI_A, PI_T, PI_G, PI_C, PI_alt; empty for zero-coverage rows), fisher (captured calls).
+    PI_A, PI_T, PI_G, PI_C, PI_alt; empty for zero-coverage rows), fisher (captured calls), final (the (key, PI) items of
+    finalDict in the order the emulated py2 dict hands them to sorted() at :534 - what a PI tie falls back on).
     """
     global _MOD
     if _MOD is None:
@@ -210,6 +216,7 @@ def run_reference(pb, params, chroms, use_wrapper=True):
                      params.maxMT, params.primerDist, fa)
         res.append(dict(row=row, pi_raw=list(CAP.round2), fisher=list(CAP.fisher),
                         n_umi_used=len(CAP.calprob), tie_ambiguous=_tie_ambiguous(CAP.final),
+                        final=[[k, v] for k, v in CAP.final_items],
                         sampled=bool(CAP.sampled)))
     return res
 

@@ -1049,6 +1049,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BLOCK == 
                         const double x = 1.0 - mypost;
                         mypred = x > 0.0 ? neg_log10_unit(x) : 16.0;
                     }
+                    // A barcode of ONE allele (a variant's - the reference's own were scored from the per-count table before they
+                    // could get here) takes the table's two values as well (lane 0 the allele, lane 1 the padded keys): equal
+                    // barcodes of the reference and of another allele then give bit-equal prediction indices, and an exact tie
+                    // between the two at smCounter.py:534 stays one (the route above is ~1e-13 away from the table's).
+                    if (n_exist == 1 && nf < P.simple_to && jc < 2) mypred = g_simple[2 * nf + jc];
                     double predv[4], mx = -1.0;
                     predv[0] = dpp_f64<0x00>(mypred); predv[1] = dpp_f64<0x55>(mypred);
                     predv[2] = dpp_f64<0xAA>(mypred); predv[3] = dpp_f64<0xFF>(mypred);

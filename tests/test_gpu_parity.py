@@ -38,8 +38,10 @@ def test_golden_rows_vs_oracle_and_reference(engine0, path):
         assert flagged.tolist() == [False, True, True, True]
         assert ((got["status"] & abi.ST_UNDERFLOW) != 0).tolist() == ((want["status"] & abi.ST_UNDERFLOW) != 0).tolist()
     for l, (t, e) in enumerate(zip(text, expected)):
-        if e["tie_ambiguous"] or l in ties or fragile[l] or flagged[l]:
+        if e["tie_ambiguous"] or fragile[l] or flagged[l]:
             continue        # unpinned by the reference algorithm itself (see abi.compare_rows)
+        if l in ties and t.split("\t")[3] != e["row"].split("\t")[3]:
+            continue        # two PI-tied alleles in another order than the restatement's AND another ALT than the reference's
         assert t == e["row"], "locus %d differs from the reference's own output" % l
         if e["pi_raw"]:
             d = max(max(abs(e["pi_raw"][k] - got["pi"][l][k]) for k in range(4)),
@@ -235,12 +237,13 @@ def test_general_path_with_and_without_the_reference_fragment_shortcut(monkeypat
 def test_one_allele_barcodes_of_the_major_other_allele(monkeypatch):
     """Deep loci (> 24576 reads) guess their major other allele from 64 sampled reads and score the barcodes whose live fragments
     all show it from the per-count table, like the reference allele's (calProb's posteriors of a one-allele barcode depend on the
-    fragment count only).  With the shortcut (default) and without (SMC_NO_ALT=1): every integer column equal, PI far inside the
-    tolerance - on the example run's shape (58 k reads, 30 % of the loci with a variant: the shortcut is taken) and on a deep
-    shape without variants; both against the CPU restatement.  Shallow loci are not touched by it at all."""
+    fragment count only).  With the shortcut (default) and without (SMC_NO_ALT=1): the SAME BYTES - the general path gives a
+    one-allele barcode the table's values too (an exact tie between the reference and another base must stay one,
+    tests/test_gpu_decision.py), so the shortcut only saves the walk - on the example run's shape (58 k reads, 30 % of the loci
+    with a variant), on a deep shape without variants and on shallow loci; all against the CPU restatement."""
     from smcounter_amd import engine
     eng = engine.Engine(0)
-    for name, n, taken in (("EX", 40, True), ("X9", 24, None), ("C3", 300, False)):
+    for name, n in (("EX", 40), ("X9", 24), ("C3", 300)):
         cfg = synth.CONFIGS[name]
         P = synth.params_for(cfg)
         db = synth.generate_native(cfg, 0, n, P)
@@ -248,10 +251,7 @@ def test_one_allele_barcodes_of_the_major_other_allele(monkeypatch):
         monkeypatch.setenv("SMC_NO_ALT", "1")
         full = eng.call_batch_host(db, P)
         monkeypatch.delenv("SMC_NO_ALT")
-        if taken is True:
-            assert alt.tobytes() != full.tobytes(), name          # (the shortcut was taken)
-        elif taken is False:
-            assert alt.tobytes() == full.tobytes(), name
+        assert alt.tobytes() == full.tobytes(), name
         assert abi.compare_rows(alt, full, 1e-9, 1e-12) == [], name
         want, fragile = oracle_lib.call_batch(db, abi.c_params(P), abi.ROW_DTYPE, return_fragile=True)
         assert abi.compare_rows(alt, want, PI_TOL, P_TOL, fragile) == [], name

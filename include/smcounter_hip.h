@@ -436,6 +436,29 @@ int smc_select_alignments_copies(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t
                                  const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0, const uint64_t* d_ident, int64_t n_ids,
                                  const uint64_t* seeds, const double* fracs, int32_t n_fracs, smc_dev_aln* d_aln_out, uint32_t* d_orig_index,
                                  smc_dev_locus* d_loc_out, uint32_t* d_summary, void* stream);
+/* (ABI 11, additive: one entry more, the version number unchanged) The READ-level selections of n_copies copies of a run under n_masks
+ * keep masks each in one call - what n_copies x n_masks smc_select_alignments_keyed calls at SMC_SEL_KEY_READ give, without their
+ * launches, allocations and downloads.  Copy c's records stand at d_aln + c x aln_stride_bytes (0: the copies share the records; else
+ * a positive multiple of 4).  The keep mask of (copy c, mask m) stands at d_masks + c x mask_copy_stride_words + m x mask_words
+ * (uint32 words; a stride of 0: every copy uses the same masks) and holds a bit per run-wide read-name id, n_ids of them - the layout
+ * smc_read_groups_masks writes for one seed, the seeds of a run behind each other.  The masks of a copy need not be nested.
+ * Selection s = m x n_copies + c, masks outer - smc_select_alignments_copies' layout:
+ *   d_aln_out + s x n_aln, d_orig_index + s x n_aln   the kept records in file order and their indices in the copy
+ *   d_loc_out + s x n_loci                            the n_loci descriptors
+ *   d_summary + 4 x s                                 kept alignments, deepest n, total slots (the fourth word is not written)
+ * For every (c, m) the first `kept` records - with bc_gid and pair_gid renumbered by first kept appearance -, their indices, all
+ * descriptors and the three summary words are byte for byte what smc_select_alignments_keyed(key = SMC_SEL_KEY_READ, n_bc, n_pair,
+ * d_keep_mask = that mask, d_ident = NULL, n_ids) writes for copy c's records; nothing is written behind the kept records.
+ * SMC_E_INPUT, nothing launched: n_copies or n_masks below 1, more than SMC_SEL_MAX_SELECTIONS selections, a negative record stride or
+ * one that is no multiple of 4, a negative mask stride, mask_words below ceil(n_ids / 32), negative n_bc / n_pair / n_ids, NULL
+ * d_masks, a NULL output.  Asynchronous on `stream`; the scratch is the context's, once per selection (4 bytes per locus, 16 per 1024
+ * alignments and 8 per barcode id and read-name id each), shared with smc_select_alignments: calls of one context are to be ordered
+ * on one stream. */
+int smc_select_alignments_reads_copies(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t aln_stride_bytes, int32_t n_copies, int64_t n_aln,
+                                       const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0, int64_t n_bc, int64_t n_pair,
+                                       const uint32_t* d_masks, int64_t mask_words, int64_t mask_copy_stride_words, int32_t n_masks,
+                                       int64_t n_ids, smc_dev_aln* d_aln_out, uint32_t* d_orig_index, smc_dev_locus* d_loc_out,
+                                       uint32_t* d_summary, void* stream);
 /* (ABI 11) The read-level philox sampler of --dsRpb (--dsRpbSampler philox): a file-wide table of read names and barcodes that stays
  * in HBM for the whole run (csrc/k_read_groups.inc).  Grouping as ds.reads.withinMT.py:37-58: the unit is the full read name, its
  * barcode field -2 of the stripped name; per barcode the names counted; one / multi = barcodes with one / two or more names,

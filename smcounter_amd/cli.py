@@ -295,6 +295,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "smallest depth with a rate of 0.95 at it and above), <outPrefix>.spikeScan<t>.dsMT<f>.rate.bedgraph, "
                         ".spikeScan.dsMT<f>.t95.bedgraph and .spikeScan<t>.f95.bedgraph (2 where full depth fails); targets x "
                         "fractions at most %d.  With --lod these pages carry no LOD column.  Needs --spikeScan" % GRID_MAX_CELLS)
+    p.add_argument("--spikeScanRpb", default=None,
+                   help="r1,r2,...: --spikeScan (and --spikeScanIndel) also at these reads-per-barcode targets, each > 0 and none listed "
+                        "twice.  A pass is then by definition its run with --spikeRpb <targets> (--spikeIndelRpb) beside --spikeReps: "
+                        "the same draws and philox read sampler, a cell called at the scan's mtDepth with --rpb r.  The copies of a batch "
+                        "are selected at every target by one smc_select_alignments_reads_copies call.  Writes "
+                        "<outPrefix>.spikeScan.rpb.sensitivity.txt, .spikeScan.rpb.curve.txt, .spikeScan.rpb.need.txt (R95: the smallest "
+                        "target with a rate of 0.95 at it and above, `full` when only the file's own reads reach it), "
+                        "<outPrefix>.spikeScan<t>.dsRpb<r>.rate.bedgraph, .spikeScan.dsRpb<r>.t95.bedgraph and .spikeScan<t>.r95.bedgraph "
+                        "(twice the largest of --rpb and the targets where full depth fails); targets x reads-per-barcode targets at most "
+                        "%d.  With --lod these pages carry no LOD column.  Needs --spikeScan; not with --spikeScanDepth" % GRID_MAX_CELLS)
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -768,10 +778,15 @@ def _spike_scan(args, plan, ref, eng, params):
     if "fracs" in scan:
         cells = [dataclasses.replace(params, mtDepth=_spike.scan_depth_mt(params.mtDepth, f)) for f in scan["fracs"]]
         depth = dict(fracs=scan["fracs"], params=cells, thresholds=[writers.pi_threshold(c.mtDepth, args.threshold) for c in cells])
+    rpb = None
+    if "rpbs" in scan:
+        # (a cell is called at the scan's mtDepth with --rpb r: the cut is the scan's own)
+        rpb = dict(targets=scan["rpbs"], params=[dataclasses.replace(params, rpb=r) for r in scan["rpbs"]],
+                   thresholds=[threshold] * len(scan["rpbs"]))
     try:
         out = devplanes.spike_scan(args.bamFile, ref, scan["variants"], scan["passes"], scan["targets"], params, int(args.dsSeed), scan["reps"],
                                    eng, threshold, repeats, sampler=getattr(args, "sampler", "reference"),
-                                   sampler_seed=getattr(args, "samplerSeed", 0), indel="indel" in scan, depth=depth)
+                                   sampler_seed=getattr(args, "samplerSeed", 0), indel="indel" in scan, depth=depth, rpb=rpb)
     except (ValueError, bamio.BamError) as e:
         raise SystemExit(str(e))
     for (k, _), st in zip(scan["passes"], out["passes"]):
@@ -1304,7 +1319,8 @@ def _scan_reports(args, plan, shard):
     print("--spikeScan: %d loci x %d targets x %d replicates in %d passes: %d runs decoded once each (%.3f s), %d copies built and "
           "called, %d of %d verdicts decided by the host, stage %.3f s" %
           (len(variants), len(targets), R, len(scan["passes"]), tm["runs"], tm["decode"], sum(st["builds"] for st in out["passes"]),
-           sum(st["host"] for st in out["passes"]), len(variants) * len(targets) * R * (1 + len(scan.get("fracs", ()))), tm["stage"]))
+           sum(st["host"] for st in out["passes"]), len(variants) * len(targets) * R * (1 + len(scan.get("fracs", scan.get("rpbs", ())))),
+           tm["stage"]))
     if "fracs" in scan:
         fracs = scan["fracs"]
         cells = {}
@@ -1317,6 +1333,22 @@ def _scan_reports(args, plan, shard):
         _spike.write_scan_depth(args.outPrefix, scan["loci"], variants, targets, fracs, plan.outputs[0].params.mtDepth, entries, cells)
         print("--spikeScanDepth: fractions %s: %d cells per pass, %d select_copies calls" %
               (",".join("%g" % f for f in fracs), len(targets) * len(fracs), sum(st["selects"] for st in out["passes"])))
+    if "rpbs" in scan:
+        rpbs = scan["rpbs"]
+        cells = {}
+        for i, v in enumerate(variants):
+            for t in range(len(targets)):
+                for r in range(len(rpbs)):
+                    cells[(i, t, r)] = [_spike.scan_entry(v, dict(N=int(n), V0=int(v0), S=int(s), READS=int(reads), V1=int(v1)),
+                                                          bool(out["rpb_called"][i, t, r, j]))
+                                        for j, (n, v0, s, reads, v1) in enumerate(out["rpb_counts"][i, :, t, r].tolist())]
+        params = plan.outputs[0].params
+        _spike.write_scan_rpb(args.outPrefix, scan["loci"], variants, targets, rpbs, params.mtDepth, params.rpb, entries, cells)
+        print("--spikeScanRpb: reads-per-barcode targets %s: %d cells per pass, %d select_copies_reads calls" %
+              (",".join("%g" % r for r in rpbs), len(targets) * len(rpbs), sum(st["selects"] for st in out["passes"])))
+        for r, rule in zip(rpbs, out["rpb_rules"]):
+            print("--spikeScanRpb %g: sampler philox, seed %d, probKeep %.6g, threshold %d, %d of %d read names kept (mtDepth %d)" %
+                  (r, rule["seed"], rule["prob_keep"], rule["thr"], rule["n_kept"], rule["n_names"], params.mtDepth))
 
 
 def _run(args, plan, loc_list, t0):

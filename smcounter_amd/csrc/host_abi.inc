@@ -979,6 +979,87 @@ int smc_select_alignments_copies(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t
     return SMC_OK;
 }
 
+// (ABI 11, additive) the read-level selections of n_copies copies of a run under n_masks keep masks each: the ten stages of
+// smc_select_alignments_keyed at SMC_SEL_KEY_READ with the selection as a grid dimension (k_select_aln.inc), the scratch once per
+// selection.  Nothing waits.
+int smc_select_alignments_reads_copies(smc_ctx* ctx, const smc_dev_aln* d_aln, int64_t aln_stride_bytes, int32_t n_copies, int64_t n_aln,
+                                       const smc_dev_locus* d_loc, int64_t n_loci, int32_t start0, int64_t n_bc, int64_t n_pair,
+                                       const uint32_t* d_masks, int64_t mask_words, int64_t mask_copy_stride_words, int32_t n_masks,
+                                       int64_t n_ids, smc_dev_aln* d_aln_out, uint32_t* d_orig_index, smc_dev_locus* d_loc_out,
+                                       uint32_t* d_summary, void* stream) {
+    const std::string who = "smc_select_alignments_reads_copies";
+    if (!ctx) return fail(SMC_E_ARG, who + ": NULL context");
+    if (n_aln < 0 || n_loci < 0 || n_aln >= (int64_t)0xFFFFF000 || n_loci >= (int64_t)0x7FFFFFFF || n_ids > (int64_t)0xFFFFFFFF ||
+        n_bc + n_pair >= (int64_t)0xFFFFFFFF || (n_aln && !d_aln))
+        return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_copies < 1 || n_masks < 1 || (int64_t)n_copies * (int64_t)n_masks > SMC_SEL_MAX_SELECTIONS)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies x " + std::to_string(n_masks) + " masks, 1 .. " +
+                                 std::to_string(SMC_SEL_MAX_SELECTIONS) + " selections expected");
+    if (aln_stride_bytes < 0 || (aln_stride_bytes & 3))
+        return fail(SMC_E_INPUT, who + ": a record stride of " + std::to_string(aln_stride_bytes) + " bytes (0 or a positive multiple of 4 expected)");
+    if (n_bc < 0 || n_pair < 0 || n_ids < 0)
+        return fail(SMC_E_INPUT, who + ": negative id counts (" + std::to_string(n_bc) + " barcodes, " + std::to_string(n_pair) + " read names, " +
+                                 std::to_string(n_ids) + " mask ids)");
+    if (mask_copy_stride_words < 0 || mask_words < (n_ids + 31) / 32)
+        return fail(SMC_E_INPUT, who + ": masks of " + std::to_string(mask_words) + " words at a copy stride of " +
+                                 std::to_string(mask_copy_stride_words) + " for " + std::to_string(n_ids) + " ids");
+    if (!d_masks) return fail(SMC_E_INPUT, who + ": NULL masks");
+    if (!d_aln_out || !d_orig_index || !d_loc_out || !d_summary) return fail(SMC_E_INPUT, who + ": NULL output");
+    (void)d_loc;                          // (as the single call: the input windows are not needed)
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t n_blk = (uint32_t)((n_aln + SEL_ITEMS - 1) / SEL_ITEMS), nl = (uint32_t)n_loci;
+    const uint32_t C = (uint32_t)n_copies, M = (uint32_t)n_masks, S = C * M;
+    const size_t n_idw = (size_t)(n_bc + n_pair);
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_off = carve(4 * ((size_t)n_blk + 1) * S), o_max = carve(4 * ((size_t)n_blk + 1) * S), o_diff = carve(4 * ((size_t)nl + 1) * S);
+    const size_t o_rcnt = carve(8 * ((size_t)n_blk + 1) * S), o_rsum = carve(8 * (size_t)S), o_first = carve(4 * n_idw * S), o_map = carve(4 * n_idw * S);
+    if (int rc = grow_scratch(ctx->sel_scratch, ctx->sel_bytes, off, off + off / 8, who.c_str(), &st)) return rc;
+    char* sc = (char*)ctx->sel_scratch;
+    uint32_t* blk_off = (uint32_t*)(sc + o_off);
+    int32_t* blk_max = (int32_t*)(sc + o_max);
+    int32_t* diff = (int32_t*)(sc + o_diff);
+    // the two record stages: a launch per group of SEL_CP_FRACS masks (a bit of a register each; one launch for a usual batch)
+    auto records = [&](bool scatter) {
+        for (uint32_t m0 = 0; m0 < M; m0 += SEL_CP_FRACS) {
+            SelReadCopies K;
+            K.masks = d_masks; K.mask_words = (unsigned long long)mask_words; K.copy_stride = (unsigned long long)mask_copy_stride_words;
+            K.n_ids = (uint32_t)n_ids; K.m0 = m0; K.n_m = std::min<uint32_t>(SEL_CP_FRACS, M - m0); K.n_copies = C;
+            if (!scatter)
+                hipLaunchKernelGGL(k_selr_count, dim3(n_blk, C), dim3(SEL_BLOCK), 0, st, (const char*)d_aln, (unsigned long long)aln_stride_bytes,
+                                   (uint32_t)n_aln, K, n_blk, blk_off);
+            else
+                hipLaunchKernelGGL(k_selr_scatter, dim3(n_blk, C), dim3(SEL_BLOCK), 0, st, (const char*)d_aln, (unsigned long long)aln_stride_bytes,
+                                   (uint32_t)n_aln, K, n_blk, (const uint32_t*)blk_off, start0, nl, d_aln_out, d_orig_index, diff, blk_max);
+        }
+    };
+    if (n_blk) records(false);
+    hipLaunchKernelGGL(k_selc_offsets, dim3(S), dim3(SEL_SCAN), 0, st, blk_off, n_blk, diff, nl + 1u, d_summary);
+    if (n_blk) records(true);
+    hipLaunchKernelGGL(k_selc_loci, dim3(S), dim3(SEL_SCAN), 0, st, blk_max, n_blk, (const int32_t*)diff, nl, d_loc_out, d_summary);
+    if (nl) hipLaunchKernelGGL(k_selc_windows, dim3((nl + SEL_BLOCK / WAVE - 1) / (SEL_BLOCK / WAVE), S), dim3(SEL_BLOCK), 0, st,
+                               (const smc_dev_aln*)d_aln_out, (uint32_t)n_aln, (const uint32_t*)blk_off, (const int32_t*)blk_max, n_blk, start0,
+                               nl, d_loc_out);
+    if (n_blk) {
+        // the kept ids of every selection renumbered by first kept appearance: the single call's five stages, the selection on blockIdx.y
+        SelIds I;
+        I.first = (uint32_t*)(sc + o_first); I.map = (uint32_t*)(sc + o_map); I.n_bc = (uint32_t)n_bc; I.n_pair = (uint32_t)n_pair;
+        uint32_t* rcnt = (uint32_t*)(sc + o_rcnt);
+        uint32_t* rsum = (uint32_t*)(sc + o_rsum);
+        const smc_dev_aln* kept = d_aln_out;
+        const uint32_t* sum = d_summary;
+        if (n_idw) HIPCHK(hipMemsetAsync(I.first, 0xFF, 4 * n_idw * S, st));
+        hipLaunchKernelGGL(k_selr_first, dim3(n_blk, S), dim3(SEL_BLOCK), 0, st, kept, (uint32_t)n_aln, sum, I);
+        hipLaunchKernelGGL(k_selr_rcount, dim3(n_blk, S), dim3(SEL_BLOCK), 0, st, kept, (uint32_t)n_aln, sum, I, n_blk, rcnt);
+        hipLaunchKernelGGL(k_selr_offsets, dim3(2 * S), dim3(SEL_SCAN), 0, st, rcnt, n_blk, rsum);
+        hipLaunchKernelGGL(k_selr_rank, dim3(n_blk, S), dim3(SEL_BLOCK), 0, st, kept, (uint32_t)n_aln, sum, I, n_blk, (const uint32_t*)rcnt);
+        hipLaunchKernelGGL(k_selr_regid, dim3(n_blk, S), dim3(SEL_BLOCK), 0, st, d_aln_out, (uint32_t)n_aln, sum, I);
+    }
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
 // ---- (ABI 11) the read-level philox sampler's file-wide table (k_read_groups.inc)
 struct smc_read_groups {
     smc_ctx* ctx = nullptr;

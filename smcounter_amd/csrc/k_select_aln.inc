@@ -276,7 +276,7 @@ __device__ __forceinline__ uint32_t sel_slot(const SelIds& I, const smc_dev_aln&
     return which == 0 ? (a.bc_gid < I.n_bc ? a.bc_gid : 0xFFFFFFFFu) : (a.pair_gid < I.n_pair ? I.n_bc + a.pair_gid : 0xFFFFFFFFu);
 }
 
-__global__ __launch_bounds__(SEL_BLOCK) void k_sel_first(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, SelIds I) {
+__device__ __forceinline__ void sel_first_body(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, const SelIds& I) {
     const uint32_t kept = summary[0], base = blockIdx.x * (uint32_t)SEL_ITEMS;
     for (int r = 0; r < SEL_ROUNDS; ++r) {
         const uint32_t k = base + (uint32_t)r * SEL_BLOCK + threadIdx.x;
@@ -289,9 +289,13 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_sel_first(const smc_dev_aln* __re
     }
 }
 
+__global__ __launch_bounds__(SEL_BLOCK) void k_sel_first(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, SelIds I) {
+    sel_first_body(out, summary, I);
+}
+
 // per block: the kept alignments that are the first of their barcode (cnt[b]) / of their read name (cnt[n_blk + 1 + b])
-__global__ __launch_bounds__(SEL_BLOCK) void k_sel_rcount(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, SelIds I,
-                                                          uint32_t n_blk, uint32_t* __restrict__ cnt) {
+__device__ __forceinline__ void sel_rcount_body(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, const SelIds& I,
+                                                uint32_t n_blk, uint32_t* __restrict__ cnt) {
     __shared__ uint32_t wsum[2][SEL_BLOCK / WAVE];
     const uint32_t kept = summary[0], base = blockIdx.x * (uint32_t)SEL_ITEMS;
     uint32_t mine[2] = {0u, 0u};
@@ -316,10 +320,15 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_sel_rcount(const smc_dev_aln* __r
     }
 }
 
+__global__ __launch_bounds__(SEL_BLOCK) void k_sel_rcount(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, SelIds I,
+                                                          uint32_t n_blk, uint32_t* __restrict__ cnt) {
+    sel_rcount_body(out, summary, I, n_blk, cnt);
+}
+
 // per block (block offsets: the exclusive scans of k_sel_rcount's counts): the first kept alignment of every id gives it its new id
 // (ballot ranks within a round, the rounds in order - as k_sel_scatter ranks the kept alignments)
-__global__ __launch_bounds__(SEL_BLOCK) void k_sel_rank(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, SelIds I,
-                                                        uint32_t n_blk, const uint32_t* __restrict__ off) {
+__device__ __forceinline__ void sel_rank_body(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, const SelIds& I,
+                                              uint32_t n_blk, const uint32_t* __restrict__ off) {
     __shared__ uint32_t wcnt[2][SEL_BLOCK / WAVE];
     const uint32_t t = threadIdx.x, wv = t / WAVE, lane = t & (WAVE - 1), kept = summary[0], base = blockIdx.x * (uint32_t)SEL_ITEMS;
     uint32_t dst[2] = {off[blockIdx.x], off[n_blk + 1 + blockIdx.x]};
@@ -349,7 +358,12 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_sel_rank(const smc_dev_aln* __res
     }
 }
 
-__global__ __launch_bounds__(SEL_BLOCK) void k_sel_regid(smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, SelIds I) {
+__global__ __launch_bounds__(SEL_BLOCK) void k_sel_rank(const smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, SelIds I,
+                                                        uint32_t n_blk, const uint32_t* __restrict__ off) {
+    sel_rank_body(out, summary, I, n_blk, off);
+}
+
+__device__ __forceinline__ void sel_regid_body(smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, const SelIds& I) {
     const uint32_t kept = summary[0], base = blockIdx.x * (uint32_t)SEL_ITEMS;
     for (int r = 0; r < SEL_ROUNDS; ++r) {
         const uint32_t k = base + (uint32_t)r * SEL_BLOCK + threadIdx.x;
@@ -359,6 +373,10 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_sel_regid(smc_dev_aln* __restrict
         if (sb != 0xFFFFFFFFu) out[k].bc_gid = I.map[sb];
         if (sp != 0xFFFFFFFFu) out[k].pair_gid = I.map[sp];
     }
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_sel_regid(smc_dev_aln* __restrict__ out, const uint32_t* __restrict__ summary, SelIds I) {
+    sel_regid_body(out, summary, I);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -397,25 +415,47 @@ __device__ __forceinline__ bool selc_draw(const smc_dev_aln* __restrict__ aln, u
     return true;
 }
 
-__global__ __launch_bounds__(SEL_BLOCK) void k_selc_count(const char* __restrict__ aln_base, unsigned long long aln_stride, uint32_t n_aln,
-                                                          const unsigned long long* __restrict__ ident, uint32_t n_ids, SelCopies K,
-                                                          uint32_t n_blk, uint32_t* __restrict__ blk_cnt_all) {
+// The keep rule of a batch's two record stages: per (alignment, copy) one word made once (`load`: false when the record cannot be
+// kept at all), tested per selection j of the launch (`keep`).  SelcPhilox: the barcode's draw against the nested thresholds;
+// SelcBits (smc_select_alignments_reads_copies, below): bit j of the word = the read name's bit in mask m0 + j of the copy.
+struct SelcPhilox {
+    const unsigned long long* __restrict__ ident;
+    uint32_t n_ids;
+    unsigned long long seed;
+    const SelCopies& K;
+    __device__ __forceinline__ bool load(const smc_dev_aln* __restrict__ aln, uint32_t i, uint32_t n_aln, uint32_t& v) const {
+        return selc_draw(aln, i, n_aln, ident, n_ids, seed, v);
+    }
+    __device__ __forceinline__ bool keep(bool ok, uint32_t v, uint32_t j) const { return ok && (unsigned long long)v < K.thr[j]; }
+};
+
+// (n_j selections j0 .. j0 + n_j - 1 of copy c, of a call of n_copies copies: selection s = j x n_copies + c)
+template <typename P>
+__device__ __forceinline__ void selc_count_body(const smc_dev_aln* __restrict__ aln, uint32_t n_aln, const P& rule, uint32_t c, uint32_t j0,
+                                                uint32_t n_j, uint32_t n_copies, uint32_t n_blk, uint32_t* __restrict__ blk_cnt_all) {
     __shared__ uint32_t cnt[SEL_CP_FRACS];
-    const uint32_t t = threadIdx.x, c = K.c0 + blockIdx.y, base = blockIdx.x * (uint32_t)SEL_ITEMS;
-    const smc_dev_aln* aln = (const smc_dev_aln*)(aln_base + (size_t)c * aln_stride);
+    const uint32_t t = threadIdx.x, base = blockIdx.x * (uint32_t)SEL_ITEMS;
     if (t < SEL_CP_FRACS) cnt[t] = 0u;
     __syncthreads();
 #pragma unroll 1
     for (int r = 0; r < SEL_ROUNDS; ++r) {
-        uint32_t draw;
-        const bool ok = selc_draw(aln, base + (uint32_t)r * SEL_BLOCK + t, n_aln, ident, n_ids, K.seed[blockIdx.y], draw);
-        for (uint32_t f = 0; f < K.n_f; ++f) {
-            const unsigned long long m = __ballot(ok && (unsigned long long)draw < K.thr[f]);
-            if ((t & (WAVE - 1)) == 0 && m) atomicAdd(&cnt[f], (uint32_t)__popcll(m));
+        uint32_t v;
+        const bool ok = rule.load(aln, base + (uint32_t)r * SEL_BLOCK + t, n_aln, v);
+        for (uint32_t j = 0; j < n_j; ++j) {
+            const unsigned long long m = __ballot(rule.keep(ok, v, j));
+            if ((t & (WAVE - 1)) == 0 && m) atomicAdd(&cnt[j], (uint32_t)__popcll(m));
         }
     }
     __syncthreads();
-    if (t < K.n_f) blk_cnt_all[((size_t)(K.f0 + t) * K.n_copies + c) * (n_blk + 1u) + blockIdx.x] = cnt[t];
+    if (t < n_j) blk_cnt_all[((size_t)(j0 + t) * n_copies + c) * (n_blk + 1u) + blockIdx.x] = cnt[t];
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_selc_count(const char* __restrict__ aln_base, unsigned long long aln_stride, uint32_t n_aln,
+                                                          const unsigned long long* __restrict__ ident, uint32_t n_ids, SelCopies K,
+                                                          uint32_t n_blk, uint32_t* __restrict__ blk_cnt_all) {
+    const uint32_t c = K.c0 + blockIdx.y;
+    const SelcPhilox rule{ident, n_ids, K.seed[blockIdx.y], K};
+    selc_count_body((const smc_dev_aln*)(aln_base + (size_t)c * aln_stride), n_aln, rule, c, K.f0, K.n_f, K.n_copies, n_blk, blk_cnt_all);
 }
 
 __global__ __launch_bounds__(SEL_SCAN) void k_selc_offsets(uint32_t* __restrict__ blk_cnt_all, uint32_t n_blk, int32_t* __restrict__ diff_all,
@@ -424,26 +464,25 @@ __global__ __launch_bounds__(SEL_SCAN) void k_selc_offsets(uint32_t* __restrict_
     sel_offsets_body(blk_cnt_all + s * (n_blk + 1u), n_blk, diff_all + s * n_diff, n_diff, summary + 4 * s);
 }
 
-__global__ __launch_bounds__(SEL_BLOCK) void k_selc_scatter(const char* __restrict__ aln_base, unsigned long long aln_stride, uint32_t n_aln,
-                                                            const unsigned long long* __restrict__ ident, uint32_t n_ids, SelCopies K,
-                                                            uint32_t n_blk, const uint32_t* __restrict__ blk_off_all, int32_t start0,
-                                                            uint32_t n_loci, smc_dev_aln* __restrict__ out_all, uint32_t* __restrict__ orig_all,
-                                                            int32_t* __restrict__ diff_all, int32_t* __restrict__ blk_maxend_all) {
+template <typename P>
+__device__ __forceinline__ void selc_scatter_body(const smc_dev_aln* __restrict__ aln, uint32_t n_aln, const P& rule, uint32_t c, uint32_t j0,
+                                                  uint32_t n_j, uint32_t n_copies, uint32_t n_blk, const uint32_t* __restrict__ blk_off_all,
+                                                  int32_t start0, uint32_t n_loci, smc_dev_aln* __restrict__ out_all,
+                                                  uint32_t* __restrict__ orig_all, int32_t* __restrict__ diff_all,
+                                                  int32_t* __restrict__ blk_maxend_all) {
     __shared__ int32_t win[SEL_WIN];
     __shared__ uint32_t wcnt[SEL_BLOCK / WAVE];
     __shared__ int32_t wmax[SEL_BLOCK / WAVE];
-    const uint32_t t = threadIdx.x, wv = t / WAVE, lane = t & (WAVE - 1), c = K.c0 + blockIdx.y, base = blockIdx.x * (uint32_t)SEL_ITEMS;
-    const smc_dev_aln* aln = (const smc_dev_aln*)(aln_base + (size_t)c * aln_stride);
-    uint32_t draw[SEL_ROUNDS];
+    const uint32_t t = threadIdx.x, wv = t / WAVE, lane = t & (WAVE - 1), base = blockIdx.x * (uint32_t)SEL_ITEMS;
+    uint32_t v[SEL_ROUNDS];
     bool ok[SEL_ROUNDS];
 #pragma unroll
-    for (int r = 0; r < SEL_ROUNDS; ++r) ok[r] = selc_draw(aln, base + (uint32_t)r * SEL_BLOCK + t, n_aln, ident, n_ids, K.seed[blockIdx.y], draw[r]);
+    for (int r = 0; r < SEL_ROUNDS; ++r) ok[r] = rule.load(aln, base + (uint32_t)r * SEL_BLOCK + t, n_aln, v[r]);
     // (the block's alignments are sorted by position: the window starts at the first one's)
     const int32_t wbase = max(aln[base].pos, start0) - start0;
 #pragma unroll 1
-    for (uint32_t f = 0; f < K.n_f; ++f) {
-        const size_t s = (size_t)(K.f0 + f) * K.n_copies + c;
-        const unsigned long long thr = K.thr[f];
+    for (uint32_t j = 0; j < n_j; ++j) {
+        const size_t s = (size_t)(j0 + j) * n_copies + c;
         smc_dev_aln* out = out_all + s * n_aln;
         uint32_t* orig_index = orig_all + s * n_aln;
         int32_t* diff = diff_all + s * ((size_t)n_loci + 1u);
@@ -458,7 +497,7 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_selc_scatter(const char* __restri
 #pragma unroll
         for (int r = 0; r < SEL_ROUNDS; ++r) {
             const uint32_t i = base + (uint32_t)r * SEL_BLOCK + t;
-            const bool keep = ok[r] && (unsigned long long)draw[r] < thr;
+            const bool keep = rule.keep(ok[r], v[r], j);
             const unsigned long long m = __ballot(keep);
             const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
             if (lane == 0) wcnt[wv] = (uint32_t)__popcll(m);
@@ -485,11 +524,22 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_selc_scatter(const char* __restri
             blk_maxend_all[s * (n_blk + 1u) + blockIdx.x] = m;
         }
         for (uint32_t k = t; k < SEL_WIN; k += SEL_BLOCK) {
-            const int32_t v = win[k];
-            if (v && wbase + (int32_t)k <= (int32_t)n_loci) atomicAdd(&diff[wbase + (int32_t)k], v);
+            const int32_t x = win[k];
+            if (x && wbase + (int32_t)k <= (int32_t)n_loci) atomicAdd(&diff[wbase + (int32_t)k], x);
         }
-        __syncthreads();                                   // (win and wmax are rewritten by the next fraction)
+        __syncthreads();                                   // (win and wmax are rewritten by the next selection)
     }
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_selc_scatter(const char* __restrict__ aln_base, unsigned long long aln_stride, uint32_t n_aln,
+                                                            const unsigned long long* __restrict__ ident, uint32_t n_ids, SelCopies K,
+                                                            uint32_t n_blk, const uint32_t* __restrict__ blk_off_all, int32_t start0,
+                                                            uint32_t n_loci, smc_dev_aln* __restrict__ out_all, uint32_t* __restrict__ orig_all,
+                                                            int32_t* __restrict__ diff_all, int32_t* __restrict__ blk_maxend_all) {
+    const uint32_t c = K.c0 + blockIdx.y;
+    const SelcPhilox rule{ident, n_ids, K.seed[blockIdx.y], K};
+    selc_scatter_body((const smc_dev_aln*)(aln_base + (size_t)c * aln_stride), n_aln, rule, c, K.f0, K.n_f, K.n_copies, n_blk, blk_off_all,
+                      start0, n_loci, out_all, orig_all, diff_all, blk_maxend_all);
 }
 
 __global__ __launch_bounds__(SEL_SCAN) void k_selc_loci(int32_t* __restrict__ blk_maxend_all, uint32_t n_blk, const int32_t* __restrict__ diff_all,
@@ -504,4 +554,95 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_selc_windows(const smc_dev_aln* _
     const size_t s = blockIdx.y;
     sel_windows_body(out_all + s * n_aln, blk_off_all + s * (n_blk + 1u), blk_runmax_all + s * (n_blk + 1u), n_blk, start0, n_loci,
                      loc_out + s * n_loci);
+}
+
+// ------------------------------------------------------------------------------------------
+// the read-level selections of several copies of a run under several keep masks in one call (smc_select_alignments_reads_copies)
+// ------------------------------------------------------------------------------------------
+// --spikeScanRpb selects every spiked copy of a run at every reads-per-barcode target: the read-level rule of
+// smc_select_alignments_keyed (SMC_SEL_KEY_READ) with a keep mask per (copy, target) - ReadGroups.masks writes them; the sets of a
+// copy are NOT nested - and the renumbering of the kept ids per selection.  Selection s = mask x n_copies + copy.  The five selection
+// stages are k_selc_*'s: the record stages with the SelcBits rule (a record's pair_gid tested against the launch's masks of its copy
+// once, the bits kept in a register), k_selc_offsets / k_selc_loci / k_selc_windows as they are.  The five renumbering stages are
+// k_sel_first / k_sel_rcount / k_sel_offsets / k_sel_rank / k_sel_regid's bodies with the selection on blockIdx.y: each reads its own
+// summary[4 s]; first / map hold n_bc + n_pair words per selection, the counts 2 x (n_blk + 1) per selection.
+struct SelReadCopies {
+    const uint32_t* masks;                    // mask (copy c, mask m) at masks + c * copy_stride + m * mask_words (words)
+    unsigned long long mask_words, copy_stride;
+    uint32_t n_ids;                           // read-name ids at or beyond this are not kept
+    uint32_t m0, n_m;                         // the launch's masks m0 .. m0 + n_m - 1 (n_m <= SEL_CP_FRACS: a bit each)
+    uint32_t n_copies;                        // of the whole call
+};
+
+struct SelcBits {
+    const uint32_t* __restrict__ masks;       // the copy's mask m0
+    unsigned long long mask_words;
+    uint32_t n_m, n_ids;
+    __device__ __forceinline__ bool load(const smc_dev_aln* __restrict__ aln, uint32_t i, uint32_t n_aln, uint32_t& v) const {
+        v = 0u;
+        if (i >= n_aln) return false;
+        const uint32_t g = aln[i].pair_gid;
+        if (g >= n_ids) return false;
+        for (uint32_t j = 0; j < n_m; ++j) v |= ((masks[(size_t)j * mask_words + (g >> 5)] >> (g & 31u)) & 1u) << j;
+        return v != 0u;
+    }
+    __device__ __forceinline__ bool keep(bool, uint32_t v, uint32_t j) const { return ((v >> j) & 1u) != 0u; }
+};
+
+__device__ __forceinline__ SelcBits selr_rule(const SelReadCopies& K, uint32_t c) {
+    return SelcBits{K.masks + (size_t)c * K.copy_stride + (size_t)K.m0 * K.mask_words, K.mask_words, K.n_m, K.n_ids};
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_selr_count(const char* __restrict__ aln_base, unsigned long long aln_stride, uint32_t n_aln,
+                                                          SelReadCopies K, uint32_t n_blk, uint32_t* __restrict__ blk_cnt_all) {
+    const uint32_t c = blockIdx.y;
+    selc_count_body((const smc_dev_aln*)(aln_base + (size_t)c * aln_stride), n_aln, selr_rule(K, c), c, K.m0, K.n_m, K.n_copies, n_blk, blk_cnt_all);
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_selr_scatter(const char* __restrict__ aln_base, unsigned long long aln_stride, uint32_t n_aln,
+                                                            SelReadCopies K, uint32_t n_blk, const uint32_t* __restrict__ blk_off_all,
+                                                            int32_t start0, uint32_t n_loci, smc_dev_aln* __restrict__ out_all,
+                                                            uint32_t* __restrict__ orig_all, int32_t* __restrict__ diff_all,
+                                                            int32_t* __restrict__ blk_maxend_all) {
+    const uint32_t c = blockIdx.y;
+    selc_scatter_body((const smc_dev_aln*)(aln_base + (size_t)c * aln_stride), n_aln, selr_rule(K, c), c, K.m0, K.n_m, K.n_copies, n_blk,
+                      blk_off_all, start0, n_loci, out_all, orig_all, diff_all, blk_maxend_all);
+}
+
+// the renumbering's arrays of selection s = blockIdx.y
+__device__ __forceinline__ SelIds selr_ids(const SelIds& I) {
+    const size_t o = (size_t)blockIdx.y * ((size_t)I.n_bc + I.n_pair);
+    return SelIds{I.first + o, I.map + o, I.n_bc, I.n_pair};
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_selr_first(const smc_dev_aln* __restrict__ out_all, uint32_t n_aln,
+                                                          const uint32_t* __restrict__ summary, SelIds I) {
+    const size_t s = blockIdx.y;
+    sel_first_body(out_all + s * n_aln, summary + 4 * s, selr_ids(I));
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_selr_rcount(const smc_dev_aln* __restrict__ out_all, uint32_t n_aln,
+                                                           const uint32_t* __restrict__ summary, SelIds I, uint32_t n_blk,
+                                                           uint32_t* __restrict__ cnt_all) {
+    const size_t s = blockIdx.y;
+    sel_rcount_body(out_all + s * n_aln, summary + 4 * s, selr_ids(I), n_blk, cnt_all + s * 2u * (n_blk + 1u));
+}
+
+// a workgroup per (selection, barcodes / read names): the exclusive scan of its n_blk + 1 counts; the totals into rsum (not read)
+__global__ __launch_bounds__(SEL_SCAN) void k_selr_offsets(uint32_t* __restrict__ cnt_all, uint32_t n_blk, uint32_t* __restrict__ rsum) {
+    const size_t j = blockIdx.x;
+    sel_offsets_body(cnt_all + j * (n_blk + 1u), n_blk, (int32_t*)nullptr, 0u, rsum + j);
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_selr_rank(const smc_dev_aln* __restrict__ out_all, uint32_t n_aln,
+                                                         const uint32_t* __restrict__ summary, SelIds I, uint32_t n_blk,
+                                                         const uint32_t* __restrict__ off_all) {
+    const size_t s = blockIdx.y;
+    sel_rank_body(out_all + s * n_aln, summary + 4 * s, selr_ids(I), n_blk, off_all + s * 2u * (n_blk + 1u));
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_selr_regid(smc_dev_aln* __restrict__ out_all, uint32_t n_aln,
+                                                          const uint32_t* __restrict__ summary, SelIds I) {
+    const size_t s = blockIdx.y;
+    sel_regid_body(out_all + s * n_aln, summary + 4 * s, selr_ids(I));
 }

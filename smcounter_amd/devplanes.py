@@ -1299,34 +1299,29 @@ class CopySelections(object):
         self.bufs = []
 
 
-def select_copies(eng, runs, A, lo: int, idents, seeds, fracs) -> CopySelections:
-    """smc_select_alignments_copies: the philox selections of the B copies `runs` of one run (RunOnDevices of equal n_aln whose records
-    stand at a constant stride - _SpikedCopies.runs - or are the same array; A: the run's counts) at every fraction of `fracs`, copy c
-    drawn with seeds[c] -> CopySelections.  Every selection is what select_run(eng, runs[c], A, lo, idents=idents, frac=fracs[f],
-    seed=seeds[c]) gives; one call and ONE download (the summaries) in place of B x F of each."""
-    from .engine import DevBuf
-    B, F = len(runs), len(fracs)
-    if B < 1 or F < 1 or B * F > SEL_MAX_SELECTIONS or len(seeds) != B:
-        raise ValueError("select_copies: %d copies (%d seeds) x %d fractions; 1 .. %d selections" % (B, len(seeds), F, SEL_MAX_SELECTIONS))
-    n, nl, S = runs[0].n_aln, int(A["nl"]), B * F
-    base = runs[0].aln.data_ptr()
-    stride = runs[1].aln.data_ptr() - base if B > 1 else 0
+def _copies_at_one_stride(who, runs):
+    """-> (n_aln, base address, byte stride) of copies whose records stand at a constant stride or are the same array."""
+    n, base = runs[0].n_aln, runs[0].aln.data_ptr()
+    stride = runs[1].aln.data_ptr() - base if len(runs) > 1 else 0
     if any(r.n_aln != n or r.aln.data_ptr() != base + c * stride for c, r in enumerate(runs)):
-        raise ValueError("select_copies: the copies' records do not stand at one stride, or differ in length")
-    idents = np.ascontiguousarray(idents, np.uint64)[:int(A["n_bc"])]
-    seeds = np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], np.uint64)
-    fr = np.ascontiguousarray(fracs, np.float64)
+        raise ValueError("%s: the copies' records do not stand at one stride, or differ in length" % who)
+    return n, base, int(stride)
+
+
+def _copy_selections(eng, runs, A, n_outer, launch) -> CopySelections:
+    """The outputs of a batched selection call of n_outer x len(runs) selections (s = outer x copies + copy): the four buffers, the
+    call itself (`launch(records, orig_index, descriptors, summary)`), ONE download - the summaries - and select_run's triple per
+    selection as views."""
+    from .engine import DevBuf
+    B, n, nl = len(runs), runs[0].n_aln, int(A["nl"])
+    S = B * n_outer
     sa, so, sl = 36 * n, 4 * n, 16 * nl
     bufs = [DevBuf(eng, max(1, sa) * S + 256), DevBuf(eng, max(1, so) * S + 256), DevBuf(eng, max(1, sl) * S + 256), DevBuf(eng, 16 * S + 256)]
-    d_id = DevBuf(eng, 8 * max(1, len(idents)) + 256).upload(idents if len(idents) else np.zeros(1, np.uint64))
     try:
-        _lib.check(eng.L.smc_select_alignments_copies(eng.ctx, base, int(stride), B, n, None, nl, int(lo), d_id.data_ptr(), len(idents),
-                                                      seeds.ctypes.data, fr.ctypes.data, F, bufs[0].data_ptr(), bufs[1].data_ptr(),
-                                                      bufs[2].data_ptr(), bufs[3].data_ptr(), ctypes.c_void_p(0)),
-                   "smc_select_alignments_copies")
-        summary = bufs[3].download(np.uint32, 4 * S).reshape(F, B, 4)[:, :, :3].copy()     # (the default stream: behind the kernels)
+        launch(*(b.data_ptr() for b in bufs))
+        summary = bufs[3].download(np.uint32, 4 * S).reshape(n_outer, B, 4)[:, :, :3].copy()     # (the default stream: behind the kernels)
         of = []
-        for f in range(F):
+        for f in range(n_outer):
             of.append([])
             for c, up in enumerate(runs):
                 s = f * B + c
@@ -1343,9 +1338,52 @@ def select_copies(eng, runs, A, lo: int, idents, seeds, fracs) -> CopySelections
         for b in bufs:
             b.free()
         raise
+    return CopySelections(bufs, of, summary, (sa, so, sl))
+
+
+def select_copies(eng, runs, A, lo: int, idents, seeds, fracs) -> CopySelections:
+    """smc_select_alignments_copies: the philox selections of the B copies `runs` of one run (RunOnDevices of equal n_aln whose records
+    stand at a constant stride - _SpikedCopies.runs - or are the same array; A: the run's counts) at every fraction of `fracs`, copy c
+    drawn with seeds[c] -> CopySelections.  Every selection is what select_run(eng, runs[c], A, lo, idents=idents, frac=fracs[f],
+    seed=seeds[c]) gives; one call and ONE download (the summaries) in place of B x F of each."""
+    from .engine import DevBuf
+    B, F = len(runs), len(fracs)
+    if B < 1 or F < 1 or B * F > SEL_MAX_SELECTIONS or len(seeds) != B:
+        raise ValueError("select_copies: %d copies (%d seeds) x %d fractions; 1 .. %d selections" % (B, len(seeds), F, SEL_MAX_SELECTIONS))
+    n, base, stride = _copies_at_one_stride("select_copies", runs)
+    nl = int(A["nl"])
+    idents = np.ascontiguousarray(idents, np.uint64)[:int(A["n_bc"])]
+    seeds = np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], np.uint64)
+    fr = np.ascontiguousarray(fracs, np.float64)
+    d_id = DevBuf(eng, 8 * max(1, len(idents)) + 256).upload(idents if len(idents) else np.zeros(1, np.uint64))
+
+    def launch(*outs):
+        _lib.check(eng.L.smc_select_alignments_copies(eng.ctx, base, stride, B, n, None, nl, int(lo), d_id.data_ptr(), len(idents),
+                                                      seeds.ctypes.data, fr.ctypes.data, F, *outs, ctypes.c_void_p(0)),
+                   "smc_select_alignments_copies")
+    try:
+        return _copy_selections(eng, runs, A, F, launch)
     finally:
         d_id.free()
-    return CopySelections(bufs, of, summary, (sa, so, sl))
+
+
+def select_copies_reads(eng, runs, A, lo: int, d_masks, n_words: int, copy_stride_words: int, n_masks: int) -> CopySelections:
+    """smc_select_alignments_reads_copies: the READ-level selections of the B copies `runs` (as select_copies takes them) under n_masks
+    keep masks each, already in HBM: mask (c, m) at d_masks + 4 x (c x copy_stride_words + m x n_words) bytes, a bit per run-wide
+    read-name id (ReadGroups.masks' layout; a copy stride of 0: one set for all) -> CopySelections, of[m][c].  Every selection is what
+    select_run(eng, runs[c], A, lo, level="read", d_mask=that mask) gives, ids renumbered; one call and ONE download."""
+    B, M = len(runs), int(n_masks)
+    if B < 1 or M < 1 or B * M > SEL_MAX_SELECTIONS:
+        raise ValueError("select_copies_reads: %d copies x %d masks; 1 .. %d selections" % (B, M, SEL_MAX_SELECTIONS))
+    n, base, stride = _copies_at_one_stride("select_copies_reads", runs)
+    nl = int(A["nl"])
+
+    def launch(*outs):
+        _lib.check(eng.L.smc_select_alignments_reads_copies(eng.ctx, base, stride, B, n, None, nl, int(lo), int(A["n_bc"]), int(A["n_pair"]),
+                                                            int(d_masks), int(n_words), int(copy_stride_words), M, int(A["n_pair"]), *outs,
+                                                            ctypes.c_void_p(0)),
+                   "smc_select_alignments_reads_copies")
+    return _copy_selections(eng, runs, A, M, launch)
 
 
 # ---- in-run dilution of listed variants (--dsAF): tools.ds_allele_fraction's drop of the barcodes that carry a listed allele
@@ -2943,15 +2981,18 @@ class _SpikedCopies(object):
             b.free()
 
 
-def _copy_room(run: AfRun, svar, four: bool, n_selections: int = 0):
+def _copy_room(run: AfRun, svar, four: bool, n_selections: int = 0, by_read: bool = False):
     """How many spiked copies of the kept run one rewrite call makes: as many as fit SPIKE_REP_BATCH_BYTES - a copy is its records and
     pair pool or, with `four` counters, records, both pools at their capacities and the call's scratch of 8 bytes per alignment -,
     AF_REP_BATCH_SLOTS read slots and SMC_SPIKE_MAX_COPIES, and at least one -> (copies, spike_indel_caps of `svar` on the run or None).
     `n_selections` (--spikeScanDepth: the fractions): a copy also has that many selections alive beside it (select_copies: records,
-    orig_index and descriptors at their capacities), and copies x selections stays within SEL_MAX_SELECTIONS."""
+    orig_index and descriptors at their capacities), and copies x selections stays within SEL_MAX_SELECTIONS.  `by_read`
+    (--spikeScanRpb: the selections are select_copies_reads', one per reads-per-barcode target): each also has the renumbering's
+    scratch, 8 bytes per barcode id and read-name id."""
     n, caps = run.up.n_aln, spike_indel_caps(run.A, svar) if four else None
     per_copy = sum(spike_indel_copy_strides(n, *caps)) + 8 * n if four else sum(spike_copy_strides(n, len(run.A["bq"]) // 2))
-    per_copy += n_selections * (40 * max(1, n) + 16 * max(1, run.nl) + 16)
+    per_copy += n_selections * (40 * max(1, n) + 16 * max(1, run.nl) + 16 +
+                                (8 * (int(run.A["n_bc"]) + int(run.A["n_pair"])) if by_read else 0))
     return max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per_copy, AF_REP_BATCH_SLOTS // max(1, int(run.A["n_slots"]) + run.nl),
                       SEL_MAX_SELECTIONS // max(1, n_selections))), caps
 
@@ -3272,7 +3313,7 @@ def scan_called_host(text, v, threshold: int, repeats) -> bool:
 
 
 def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed,
-               bits, threshold, repeats, check0, indel: dict = None, depth: dict = None):
+               bits, threshold, repeats, check0, indel: dict = None, depth: dict = None, rpb: dict = None):
     """The _SpikedCopies of the run at one target, one per seed of `part_seeds`, each built behind the other into one device batch and
     the batch called with one plan - _spike_rep_call's way - but the rows stay in HBM: smc_scan_detect gives a verdict per (copy,
     listed locus), and only the rows it leaves to the host come down, one by one, to be printed and cut the existing way.  run.group:
@@ -3290,7 +3331,11 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
     selections are built behind each other into one batch and called with one plan at the cell's params, the verdicts at the cell's
     cut - with `indel` the selections' records at the batched stride, the CIGAR words and pairs at the copies' -; replicate 0's (N',
     V1') by smc_allele_carriers on its selection must be the counts call's.
-    -> (called, per fraction the same, the verdicts the host decided over all of them, 1 + the fractions built), or NARROW."""
+    -> (called, per fraction the same, the verdicts the host decided over all of them, 1 + the fractions built), or NARROW.
+    `rpb` (--spikeScanRpb: dict(targets, params, thresholds: per reads-per-barcode target the cell's VcParams and cut, var, var_ins,
+    want: as `depth`'s per target r, masks: the device address of the first copy's first keep mask, n_words: words per mask,
+    copy_stride: words from a copy's masks to the next one's)): the same with ONE select_copies_reads call in place of select_copies
+    - whole read names kept by the copy's seed's masks, the kept ids renumbered -, the builds told so (_KeptRun's by_read)."""
     from . import vc
     from .engine import DevBuf
     A, lo, nl, chrom = run.A, run.lo, run.nl, run.chrom
@@ -3377,25 +3422,29 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
         kept = (_KeptRun(runs[c], A, None, A, run.bam.allele_key, run.bam.barcode_name, lambda n: run.idents) for c in range(B))
         full = decide(kept, P, threshold, copies.addresses() if indel is not None else None,
                       lambda c: copy_allele_key(runs[c], A, run.bam.allele_key), "")
-        if full == NARROW or depth is None:
+        cells = depth or rpb
+        if full == NARROW or cells is None:
             return full
-        sels = select_copies(eng, runs, A, lo, run.idents, part_seeds, depth["fracs"])
+        if rpb is not None:
+            sels = select_copies_reads(eng, runs, A, lo, rpb["masks"], rpb["n_words"], rpb["copy_stride"], len(rpb["targets"]))
+            axis, cell_flag = [" x --spikeScanRpb %g" % r for r in rpb["targets"]], "--spikeScanRpb"
+        else:
+            sels = select_copies(eng, runs, A, lo, run.idents, part_seeds, depth["fracs"])
+            axis, cell_flag = [" x fraction %g" % f for f in depth["fracs"]], "--spikeScanDepth"
         of_cell, n_host = [], full[1]
-        for f, frac in enumerate(depth["fracs"]):
-            what = " x fraction %g" % frac
+        for f, what in enumerate(axis):
             if check0 is not None:
                 sel, counts, _ = sels.of[f][check0]
-                copies.check_carriers(check0, sel, counts, depth["want"][f][check0], depth["var"], depth["var_ins"], variants,
-                                      "--spikeScanDepth", what)
+                copies.check_carriers(check0, sel, counts, cells["want"][f][check0], cells["var"], cells["var_ins"], variants, cell_flag, what)
             kept = [_KeptRun(*sels.of[f][c], A, run.bam.allele_key, run.bam.barcode_name, lambda n: run.idents,
-                             copy=runs[c] if indel is not None else None) for c in range(B)]
+                             copy=runs[c] if indel is not None else None, by_read=rpb is not None) for c in range(B)]
             where = None
             if indel is not None:
-                # (the records of this fraction's selections at the batched stride; n_aln bounds the index an extras entry holds: no
+                # (the records of this cell's selections at the batched stride; n_aln bounds the index an extras entry holds: no
                 # build walks more than its kept records, and the largest kept count stays inside every selection's own stretch)
                 where = dict(copies.addresses(), aln=sels.bufs[0].data_ptr() + f * B * sels.strides[0],
                              strides=(sels.strides[0],) + tuple(copies.strides[1:]), n_aln=max(k.run.n_aln for k in kept))
-            cell = decide(iter(kept), depth["params"][f], depth["thresholds"][f], where, lambda c: kept[c].allele_key, what)
+            cell = decide(iter(kept), cells["params"][f], cells["thresholds"][f], where, lambda c: kept[c].allele_key, what)
             if cell == NARROW:
                 return NARROW
             of_cell.append(cell[0])
@@ -3411,7 +3460,7 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
 
 def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n_reps: int, eng, threshold: int, repeats,
                sampler: str = "reference", sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, indel: bool = False,
-               depth: dict = None):
+               depth: dict = None, rpb: dict = None):
     """The stage of --spikeScan.  variants: the scan's SNV at every scanned locus (tools.spike_scan_lists.scan_variants); passes: [(k,
     the indices of pass k)] (scan_passes).  A pass is the run --spikeAF <targets> --spikeVariants <its list> --spikeReps n_reps --dsSeed
     seed: replicate j has seed (seed + j) mod 2^64, and the draws, the rewrite, NM and the thresholds are that run's.
@@ -3433,6 +3482,15 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     every full-depth batch ONE select_copies call makes its copies' selections at all fractions, and every fraction's are built and
     called as one batch at the cell's params (_scan_call's `depth`).  The result gets depth_counts: uint32 [V, R, T, F, 5],
     depth_called: bool [V, T, F, R], and the passes' dicts "selects": the select_copies calls.
+    `rpb` (--spikeScanRpb: dict(targets, params, thresholds: per reads-per-barcode target r the VcParams of its cells - the scan's with
+    rpb = r - and their cut); not with `depth`): a pass is then the run with --spikeRpb <targets> (--spikeIndelRpb) beside it.  Once
+    per file philox_read_rules builds the table of read names and gives probKeep and the threshold per r; once per decoded run come
+    the read-name identities (pair_idents_or_refuse), the barcodes' first names (run_first_names) and the keep masks of all R seeds x
+    Rr targets in ONE buffer - R ReadGroups.masks launches, seed j's masks at j x Rr; per pass and run one spike_rpb_counts call gives
+    the cells' (N', V0', S', READS', V1'); behind every full-depth batch ONE select_copies_reads call makes its copies' selections at
+    all r, and every r's are built and called as one batch (_scan_call's `rpb`).  The result gets rpb_counts: uint32 [V, R, T, Rr, 5],
+    rpb_called: bool [V, T, Rr, R], rpb_rules: per r dict(seed, prob_keep, thr, n_kept, n_names), and the passes' dicts "selects".
+    ValueError / BamError naming --spikeScanRpb: what --dsRpbSampler philox refuses.
     -> dict(seeds, base: per variant (N, V0), counts: uint32 [V, R, T, 3] = (S, READS, V1), called: bool [V, T, R], passes: per pass
     of `passes` dict(variants, copies, builds, host, seconds), times: dict(stage, runs, decode))."""
     import time
@@ -3455,53 +3513,104 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     spikes = [SpikeSet([variants[i] for i in members], indels=indel) for _, members in passes]
     base, counts, called = [None] * V, np.zeros((V, R, T, 3), np.uint32), np.zeros((V, T, R), bool)
     stats = [dict(variants=0, copies=0, builds=0, host=0, seconds=0.0) for _ in passes]
+    if depth is not None and rpb is not None:
+        raise ValueError("--spikeScanRpb: the grid of barcode fractions x reads-per-barcode targets is not built")
     if depth is not None:
         F = len(depth["fracs"])
         depth = dict(depth, counts=np.zeros((V, R, T, F, 5), np.uint32), called=np.zeros((V, T, F, R), bool))
-        for st in stats:
-            st["selects"] = 0
+    read_rules = None
+    if rpb is not None:
+        F = len(rpb["targets"])
+        # (the file-wide table of the UNSPIKED file serves every pass, cell and replicate: spiking changes no name, barcode or record count)
+        read_rules = philox_read_rules(path, list(rpb["targets"]), [P] * F, seed, eng, nthreads=nthreads, flag="--spikeScanRpb")
+        rpb = dict(rpb, counts=np.zeros((V, R, T, F, 5), np.uint32), called=np.zeros((V, T, F, R), bool), read_thr=[r.thr for r in read_rules])
+    for st in stats if (depth or rpb) is not None else ():
+        st["selects"] = 0
     times = {"decode": 0.0, "runs": 0}
     order = sorted(range(V), key=lambda k: (variants[k].chrom, variants[k].pos))
     spans = _listed_spans(variants, order)
-    for chrom, lo, hi, span in spans:
-        t0 = time.perf_counter()
-        run = AfRun(chrom, lo, hi, [], 0)
-        try:
-            nl = run.load(path, fasta, eng, P, max_reads, nthreads, mism=True)
-            if nl < 1:
-                raise bamio.BamError("--spikeScan: the run %s:%d-%d could not be decoded" % (chrom, lo + 1, hi))
-            inside = [k for k in span if variants[k].pos - 1 - lo < nl]
-            times["decode"] += time.perf_counter() - t0
-            times["runs"] += 1
-            in_run = sorted({int(pass_at[k]) for k in inside})
-            for p in in_run if indel else ():
-                _refuse_indel_limits(run.A, spikes[p].chrom_variants(chrom, 0.5)[0], "--spikeScanIndel", chrom)
-            for p in in_run:
-                t0 = time.perf_counter()
-                run.group = [k for k in inside if pass_at[k] == p]
-                room, caps = _copy_room(run, spikes[p].chrom_variants(chrom, 0.5)[0] if indel else None, indel,
-                                        len(depth["fracs"]) if depth is not None else 0)
-                _scan_pass(eng, run, spikes[p], [int(local[k]) for k in run.group], variants, seeds, thr, P, fasta, max_depth, sampler,
-                           sampler_seed, threshold, repeats, room, base, counts, called, stats[p], caps, depth)
-                stats[p]["variants"] += len(run.group)
-                stats[p]["seconds"] += time.perf_counter() - t0
-        finally:
-            run.free()
-        spans.send(len(inside))
+    try:
+        for chrom, lo, hi, span in spans:
+            t0 = time.perf_counter()
+            run = AfRun(chrom, lo, hi, [], 0)
+            try:
+                nl = run.load(path, fasta, eng, P, max_reads, nthreads, mism=True)
+                if nl < 1:
+                    raise bamio.BamError("--spikeScan: the run %s:%d-%d could not be decoded" % (chrom, lo + 1, hi))
+                inside = [k for k in span if variants[k].pos - 1 - lo < nl]
+                times["decode"] += time.perf_counter() - t0
+                times["runs"] += 1
+                in_run = sorted({int(pass_at[k]) for k in inside})
+                for p in in_run if indel else ():
+                    _refuse_indel_limits(run.A, spikes[p].chrom_variants(chrom, 0.5)[0], "--spikeScanIndel", chrom)
+                if rpb is not None:
+                    rpb.update(_scan_read_masks(eng, run, read_rules, seeds))
+                for p in in_run:
+                    t0 = time.perf_counter()
+                    run.group = [k for k in inside if pass_at[k] == p]
+                    room, caps = _copy_room(run, spikes[p].chrom_variants(chrom, 0.5)[0] if indel else None, indel,
+                                            len((depth or rpb)["params"]) if (depth or rpb) is not None else 0, rpb is not None)
+                    _scan_pass(eng, run, spikes[p], [int(local[k]) for k in run.group], variants, seeds, thr, P, fasta, max_depth, sampler,
+                               sampler_seed, threshold, repeats, room, base, counts, called, stats[p], caps, depth, rpb)
+                    stats[p]["variants"] += len(run.group)
+                    stats[p]["seconds"] += time.perf_counter() - t0
+            finally:
+                if rpb is not None and rpb.get("masks") is not None:
+                    rpb.pop("masks").free()
+                run.free()
+            spans.send(len(inside))
+    finally:
+        close_rules(read_rules)
     times["stage"] = time.perf_counter() - t_start
     out = dict(seeds=seeds, base=base, counts=counts, called=called, passes=stats, times=times)
     if depth is not None:
         out.update(depth_counts=depth["counts"], depth_called=depth["called"])
+    if rpb is not None:
+        out.update(rpb_counts=rpb["counts"], rpb_called=rpb["called"],
+                   rpb_rules=[dict(seed=r.seed, prob_keep=r.prob_keep, thr=r.thr, n_kept=r.n_kept, n_names=r.n_names) for r in read_rules])
     return out
 
 
+def _scan_read_masks(eng, run: AfRun, read_rules, seeds) -> dict:
+    """(--spikeScanRpb) What the passes of one decoded run share on the read axis: the identity of every read-name id (BamError naming
+    the flag: an id that stands for two names), whether a name is its barcode's first, and the keep masks of every seed and
+    reads-per-barcode target in ONE device buffer - seed j's len(read_rules) masks at j x len(read_rules) x n_words words, the layout
+    smc_select_alignments_reads_copies takes for a batch of consecutive seeds; one ReadGroups.masks launch per seed.
+    -> dict(p_idents, first, masks, n_words); the caller frees `masks`."""
+    from .engine import DevBuf
+    groups, Rr = read_rules[0].groups, len(read_rules)
+    p_idents = pair_idents_or_refuse(run.bam, run.A, "--spikeScanRpb", run.chrom, run.lo, run.nl)
+    first = run_first_names(eng, groups, p_idents, run.chrom, run.lo, run.nl)
+    n = len(p_idents)
+    n_words = (n + 31) // 32
+    d_id = DevBuf(eng, 8 * max(1, n) + 256).upload(np.ascontiguousarray(p_idents, np.uint64) if n else np.zeros(1, np.uint64))
+    buf = DevBuf(eng, 4 * max(1, n_words * Rr * len(seeds)) + 256)
+    try:
+        for j, s in enumerate(seeds):
+            groups.masks(d_id.data_ptr(), n, int(s), [r.thr for r in read_rules], buf.data_ptr() + 4 * n_words * Rr * j)
+        st = groups.status()
+    except BaseException:
+        buf.free()
+        raise
+    finally:
+        d_id.free()
+    if st & RG_MISS:
+        buf.free()
+        raise bamio.BamError("--spikeScanRpb: the run %s:%d-%d has a read name the file-wide table does not hold (status %#x)"
+                             % (run.chrom, run.lo + 1, run.lo + run.nl, st))
+    return dict(p_idents=p_idents, first=first, masks=buf, n_words=n_words)
+
+
 def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr, P, fasta, max_depth, sampler, sampler_seed, threshold,
-               repeats, room, base, counts, called, stat, caps=None, depth: dict = None):
+               repeats, room, base, counts, called, stat, caps=None, depth: dict = None, rpb: dict = None):
     """spike_scan's work for one pass in one run: run.group are the pass's variants there (indices into `variants`), members[g] the
     place of run.group[g] in the pass's list (`spikes`).  base, counts, called and stat are filled.  `caps` (--spikeScanIndel:
     spike_indel_caps of the pass's list on the run): the indel branch.  `depth` (--spikeScanDepth: spike_scan's dict with "counts" and
     "called"): the cells' counters of the pass from ONE smc_spike_depth_counts (indel: smc_spike_indel_counts) call, and per batch of
-    copies the cells' verdicts (_scan_call's `depth`); both are filled."""
+    copies the cells' verdicts (_scan_call's `depth`); both are filled.  `rpb` (--spikeScanRpb: spike_scan's dict with "counts",
+    "called" and the run's "p_idents", "first", "masks", "n_words"): the same on the read axis - smc_spike_read_bits
+    (smc_spike_indel_read_bits) on the pass's variants, spike_rpb_records per variant and ONE spike_rpb_counts call for the cells'
+    counters; a batch's mask base is that of its first seed."""
     A, up, lo, chrom = run.A, run.up, run.lo, run.chrom
     idents, (nm, n_indel) = run.idents, run.mism
     group = run.group
@@ -3519,14 +3628,21 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
                                                                              [frac_threshold(f) for f in depth["fracs"]])   # [G, R, T, F, 5]
     at_of = {m: n for n, m in enumerate(sorder)}
     var_at = [at_of[m] for m in members]
+    axis = depth or rpb                         # (the cells' dict: one axis at most)
+    if rpb is not None:
+        read_bits = spike_read_bits(eng, up, A, lo, var) if caps is None else \
+            spike_indel_read_bits(eng, up, A, lo, svar[var_at], spikes.ins[chrom])
+        records = [spike_rpb_records(A, read_bits[g], np.flatnonzero(cov[g][:len(idents)]), rpb["p_idents"], rpb["first"])
+                   for g in range(len(group))]
+        cells = spike_rpb_counts(eng, lead, covers, records, seeds, thr, rpb["read_thr"], four=caps is not None)   # [G, R, T, Rr, 5]
     listed = np.zeros(len(group), abi.SCAN_LOCUS_DTYPE)
     for g, k in enumerate(group):
         counts[k] = mine[g]
         if cells is not None:
-            depth["counts"][k] = cells[g]
+            axis["counts"][k] = cells[g]
         # (--spikeScanIndel: a key has no fixed id - smc_scan_detect_keys takes `var`, and of `listed` only the offsets are read)
         listed[g] = (variants[k].pos - 1 - lo, SCAN_ALT_ID[variants[k].alt] if caps is None else 0)
-    R, F = len(seeds), len(depth["fracs"]) if depth is not None else 0
+    R, F = len(seeds), len(depth["fracs"]) if depth is not None else len(rpb["targets"]) if rpb is not None else 0
     for t in range(len(thr)):
         for b in range(0, R, room):
             js = list(range(b, min(R, b + room)))
@@ -3535,21 +3651,26 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
             tail = (threshold, repeats, js.index(0) if 0 in js else None)
             tail += (dict(ins=spikes.ins[chrom], caps=caps, var=var, var_ins=ins,
                           want=[[(len(covers[g]), int(mine[g, j, t, 2])) for g in range(len(group))] for j in js]) if caps is not None else None,)
-            if depth is not None:
-                tail += (dict(fracs=depth["fracs"], params=depth["params"], thresholds=depth["thresholds"], var=var, var_ins=ins,
-                              want=[[[(int(cells[g, j, t, f, 0]), int(cells[g, j, t, f, 4])) for g in range(len(group))] for j in js]
-                                    for f in range(F)]),)
+            if axis is not None:
+                want = [[[(int(cells[g, j, t, f, 0]), int(cells[g, j, t, f, 4])) for g in range(len(group))] for j in js] for f in range(F)]
+                if depth is not None:
+                    tail += (dict(fracs=depth["fracs"], params=depth["params"], thresholds=depth["thresholds"], var=var, var_ins=ins, want=want),)
+                else:
+                    # (the masks of seed j stand at j x Rr masks: the batch's seeds are consecutive)
+                    tail += (None, dict(targets=rpb["targets"], params=rpb["params"], thresholds=rpb["thresholds"], var=var, var_ins=ins,
+                                        want=want, masks=rpb["masks"].data_ptr() + 4 * rpb["n_words"] * F * js[0], n_words=rpb["n_words"],
+                                        copy_stride=rpb["n_words"] * F),)
             got = _narrow_retry(eng, P, lambda bits: _scan_call(*args, bits, *tail))
-            yes, n_host, builds = (got[0], got[2], got[3]) if depth is not None else (got[0], got[1], 1)
+            yes, n_host, builds = (got[0], got[2], got[3]) if axis is not None else (got[0], got[1], 1)
             for c, j in enumerate(js):
                 for g, k in enumerate(group):
                     called[k, t, j] = yes[c, g]
                     for f in range(F):
-                        depth["called"][k, t, f, j] = got[1][f][c, g]
+                        axis["called"][k, t, f, j] = got[1][f][c, g]
             stat["copies"] += len(js)
             stat["builds"] += len(js) * builds
             stat["host"] += n_host
-            if depth is not None:
+            if axis is not None:
                 stat["selects"] = stat.get("selects", 0) + 1
 
 

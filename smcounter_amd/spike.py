@@ -692,14 +692,18 @@ def scan(args):
     --spikeScanIndel adds "indel": ("del" or "dup", the length) to the dict.  SystemExit: the flag without --spikeScan or beside
     --spikeScanAlt, a rule that is neither del<d> nor dup<s> with a length in 1 .. 255, a stride below the footprint's.
     --spikeScanDepth adds "fracs": the barcode fractions of the scan's depth axis.  SystemExit: the flag without --spikeScan, text that
-    is no list of numbers, a fraction outside (0, 1] or listed twice, more than MAX_CELLS targets x fractions."""
+    is no list of numbers, a fraction outside (0, 1] or listed twice, more than MAX_CELLS targets x fractions.
+    --spikeScanRpb adds "rpbs": the reads-per-barcode targets of the scan's read axis.  SystemExit: the flag without --spikeScan or
+    beside --spikeScanDepth (the t x f x r grid is not built), text that is no list of numbers, a target <= 0 or listed twice, more
+    than MAX_CELLS targets x reads-per-barcode targets."""
     from .tools import spike_scan_lists as lists
     text, r, stride, alt = (getattr(args, f, None) for f in SCAN_FLAGS)
     indel = getattr(args, "spikeScanIndel", None)
     fracs = getattr(args, "spikeScanDepth", None)
+    rpbs = getattr(args, "spikeScanRpb", None)
     given = lambda x: x not in (None, "", False)
     if not given(text):
-        for flag, value in zip(SCAN_FLAGS[1:] + ("spikeScanIndel", "spikeScanDepth"), (r, stride, alt, indel, fracs)):
+        for flag, value in zip(SCAN_FLAGS[1:] + ("spikeScanIndel", "spikeScanDepth", "spikeScanRpb"), (r, stride, alt, indel, fracs, rpbs)):
             if given(value):
                 raise SystemExit("--%s belongs to --spikeScan: it needs --spikeScan" % flag)
         return None
@@ -748,6 +752,12 @@ def scan(args):
             raise SystemExit("--spikeScanDepth: %d targets x %d fractions = %d cells, at most %d" % (len(ts), len(fr), len(ts) * len(fr),
                                                                                                    MAX_CELLS))
         out["fracs"] = fr
+    if given(rpbs):
+        if given(fracs):
+            raise SystemExit("--spikeScanRpb cannot be combined with --spikeScanDepth in one run: the grid of targets x barcode fractions x "
+                             "reads-per-barcode targets is not built")
+        # (the targets' texts and limits are --spikeRpb's: the scan's targets stand where the --spikeAF targets do)
+        out["rpbs"] = _rpb_cells(rpbs, [(t, 0, "") for t in ts], "spikeScanRpb")[0]
     return out
 
 
@@ -886,3 +896,84 @@ def write_scan_depth(out_prefix: str, loci, variants, targets, fracs, mt_depth: 
         with open("%s.spikeScan.dsMT%g.t95.bedgraph" % (out_prefix, frac), "w") as fh:
             for chrom, pos, i in loci:
                 fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "1" if i is None or t95s[f][i] == dsaf.NA else t95s[f][i]))
+
+
+# ---- --spikeScanRpb: the scan's pages per reads-per-barcode target
+SCAN_RPB_SENSITIVITY_HEADER = tuple(c for c in cell_sensitivity_header(RPB_AXIS) if c not in ("PI_MEAN", "PI_MIN"))
+SCAN_RPB_NEED_HEADER = ("CHROM", "POS", "REF", "ALT", "TARGET", "N", "R95", "N95")
+
+
+def r95(rpbs, rates, full_rate):
+    """dsaf.t95's rule on the reads-per-barcode axis - the listed targets ascending, full depth on top: the smallest entry whose rate is
+    at least 0.95 together with every larger entry's -> the index into `rpbs`, dsaf.FULL when only full depth passes, None when full
+    depth fails."""
+    top = float("inf")
+    best = dsaf.t95(list(rpbs) + [top], list(rates) + [full_rate])
+    return None if best is None else dsaf.FULL if best == top else next(n for n, r in enumerate(rpbs) if r == best)
+
+
+def rpb_need_line(v, target, n: int, rpbs, rates, n_means, full_rate, full_n_mean) -> str:
+    """One line of the reads-per-barcode need page: variant `v` at `target` with N covering barcodes at full depth; rates / n_means: per
+    listed reads-per-barcode target its detection rate and mean covering barcodes; full_rate / full_n_mean: those of full depth."""
+    k = r95(rpbs, rates, full_rate)
+    return "\t".join([v.chrom, "%d" % v.pos, v.ref, v.alt, dsaf.target_text(target), "%d" % n] +
+                     ([dsaf.NA] * 2 if k is None else [dsaf.FULL, dsaf.frac_text(full_n_mean)] if k == dsaf.FULL else
+                      ["%g" % rpbs[k], dsaf.frac_text(n_means[k])]))
+
+
+def write_scan_rpb(out_prefix: str, loci, variants, targets, rpbs, mt_depth: int, run_rpb: float, full_entries, entries) -> None:
+    """The pages of --spikeScanRpb.  loci, variants, targets, full_entries: write_scan_depth's; entries[(i, t, r)]: the replicates of the
+    cell at rpbs[r] (scan_entry with the cell's counters); mt_depth, run_rpb: the run's --mtDepth (every cell is called at it) and --rpb.
+      <outPrefix>.spikeScan.rpb.sensitivity.txt     a line per scanned locus, target and r: the pass's .spikeAF.rpb.sensitivity.txt line
+                                                    without PI_MEAN and PI_MIN (scan_depth_sensitivity_line)
+      <outPrefix>.spikeScan.rpb.curve.txt           depth_curve_line per scanned locus: full, then every r
+      <outPrefix>.spikeScan<t>.dsRpb<r>.rate.bedgraph  chrom, pos - 1, pos, RATE of the cell - the page's text - per scanned locus
+      <outPrefix>.spikeScan.dsRpb<r>.t95.bedgraph   chrom, pos - 1, pos, T95 at that r; 1 where it is NA and at a skipped locus
+      <outPrefix>.spikeScan.rpb.need.txt            rpb_need_line per scanned locus and target
+      <outPrefix>.spikeScan<t>.r95.bedgraph         chrom, pos - 1, pos, R95 of the target as a number: `full` as run_rpb; twice the
+                                                    larger of run_rpb and the largest listed r - above the axis - where it is NA and
+                                                    at a skipped locus"""
+    T, Rr = len(targets), len(rpbs)
+    i_rate = SCAN_RPB_SENSITIVITY_HEADER.index("RATE")
+    i_t95 = len(DEPTH_CURVE_HEADER) + T
+    i_r95 = SCAN_RPB_NEED_HEADER.index("R95")
+    above = "%g" % (2.0 * max([float(run_rpb)] + [float(r) for r in rpbs]))
+    rates = {}                                   # (t, r) -> per variant the page's RATE text
+    t95s = [[] for _ in range(Rr)]
+    r95s = [[] for _ in range(T)]
+    rate = lambda v, per: float(_called(v, per)) / len(per)
+    with open(out_prefix + ".spikeScan.rpb.sensitivity.txt", "w") as fs, open(out_prefix + ".spikeScan.rpb.curve.txt", "w") as fc, \
+            open(out_prefix + ".spikeScan.rpb.need.txt", "w") as fn:
+        fs.write("\t".join(SCAN_RPB_SENSITIVITY_HEADER) + "\n")
+        fc.write("\t".join(depth_curve_header(targets, False, RPB_AXIS)) + "\n")
+        fn.write("\t".join(SCAN_RPB_NEED_HEADER) + "\n")
+        for i, v in enumerate(variants):
+            for t, target in enumerate(targets):
+                for r, rpb in enumerate(rpbs):
+                    line = scan_depth_sensitivity_line(v, target, rpb, mt_depth, entries[(i, t, r)])
+                    rates.setdefault((t, r), []).append(line.split("\t")[i_rate])
+                    fs.write(line + "\n")
+                per, full = [entries[(i, t, r)] for r in range(Rr)], full_entries[(i, t)]
+                line = rpb_need_line(v, target, full[0][0]["N"], rpbs, [rate(v, p) for p in per], [_n_mean(p) for p in per], rate(v, full),
+                                     _n_mean(full))
+                r95s[t].append(line.split("\t")[i_r95])
+                fn.write(line + "\n")
+            fc.write(depth_curve_line(v, None, [mt_depth] * T, targets, [full_entries[(i, t)] for t in range(T)]) + "\n")
+            for r, rpb in enumerate(rpbs):
+                line = depth_curve_line(v, rpb, [mt_depth] * T, targets, [entries[(i, t, r)] for t in range(T)])
+                t95s[r].append(line.split("\t")[i_t95])
+                fc.write(line + "\n")
+    for t, target in enumerate(targets):
+        for r, rpb in enumerate(rpbs):
+            with open("%s.spikeScan%g.dsRpb%g.rate.bedgraph" % (out_prefix, target, rpb), "w") as fh:
+                for chrom, pos, i in loci:
+                    if i is not None:
+                        fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), rates[(t, r)][i]))
+        with open("%s.spikeScan%g.r95.bedgraph" % (out_prefix, target), "w") as fh:
+            for chrom, pos, i in loci:
+                text = above if i is None or r95s[t][i] == dsaf.NA else "%g" % run_rpb if r95s[t][i] == dsaf.FULL else r95s[t][i]
+                fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), text))
+    for r, rpb in enumerate(rpbs):
+        with open("%s.spikeScan.dsRpb%g.t95.bedgraph" % (out_prefix, rpb), "w") as fh:
+            for chrom, pos, i in loci:
+                fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "1" if i is None or t95s[r][i] == dsaf.NA else t95s[r][i]))

@@ -994,6 +994,35 @@ int smc_scan_detect_keys(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, 
                          int64_t cap_pairs, const uint32_t* d_x, int64_t x_stride, const uint32_t* d_xcount, int64_t xcount_stride,
                          int64_t xcap, double thr, uint32_t* d_alt_id, smc_scan_verdict* d_out, uint32_t* d_host_list, uint32_t* d_n_host,
                          void* stream);
+/* (ABI 11, additive: one entry more, the version number unchanged) --spikeScanFilter: the FILTER column of every listed locus's row
+ * as a word of bits, per copy of a called batch whose rows stay in HBM - called right behind smc_scan_detect / smc_scan_detect_keys
+ * on the same d_rows; the verdict records are neither read nor written.
+ *   d_rows, n_copies, n_loci   as smc_scan_detect takes them.
+ *   d_offsets / offsets_host[n_listed]  the listed loci within a copy (below n_loci).
+ *   d_gate / gate_host[n_listed]        per listed variant SMC_F_HP and / or SMC_F_LOWC: what hpregion.is_hp_or_lowcomp says of the
+ *                              PLANTED variant (chromosome, position, REF, ALT, genome) - they apply where cand[0].vmf_lt_099.
+ *   d_always / always_host[n_listed]    the repeat names of the position from the run's BEDs (postfilter._apply_one's first-hit rule):
+ *                              SMC_F_REPT, SMC_F_REPS, SMC_F_SL, SMC_F_OTHER_REPEAT, and SMC_F_LOWC for RepeatMasker's Low_complexity.
+ *   d_out[c * n_listed + g]    from cand[0] of copy c's row at the locus alone:
+ *     bits 0 - 9   flt_applied ? (flt & 0x3FF) | (vmf_lt_099 ? gate : 0) : 0        (rows.filter_string)
+ *     bits 0 - 13  additionally `always` where pi > 4.995 + 1e-6: int(float(py2 round(PI, 2))) >= 5 outside the band
+ *     bit 31       SMC_SCAN_FLT_HOST: the host has to print the row - a status that is not 0, a bi-allelic row, a pi that is NaN or
+ *                  within 4.995 +- 1e-6, a flt_applied that is neither 0 nor 1.
+ *   A word means the row's FILTER only where the detect call's verdict is SMC_SCAN_CALLED (cand[0] is the planted variant there, and
+ *   it is never DEL).  Nothing but d_out is written.
+ * Enqueued on `stream`; nothing waits; no launch for n_listed = 0 or n_copies = 0.  SMC_E_INPUT, nothing launched: a NULL array with
+ * n_listed > 0, an offset that is not below n_loci, a gate word outside SMC_F_HP | SMC_F_LOWC, an always word outside SMC_F_LOWC and
+ * bits 10 - 13, n_copies above 65535, n_copies * n_listed or n_copies * n_loci of 2^31 or more. */
+#define SMC_F_REPT 0x0400u          /* the four names only postfilter adds: never in smc_cand.flt */
+#define SMC_F_REPS 0x0800u
+#define SMC_F_SL 0x1000u
+#define SMC_F_OTHER_REPEAT 0x2000u
+#define SMC_SCAN_FLT_DEVICE_MASK 0x3FFu
+#define SMC_SCAN_FLT_NAMES_MASK 0x3FFFu
+#define SMC_SCAN_FLT_HOST 0x80000000u
+int smc_scan_filter(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64_t n_loci, const uint32_t* d_offsets,
+                    const uint32_t* offsets_host, const uint32_t* d_gate, const uint32_t* gate_host, const uint32_t* d_always,
+                    const uint32_t* always_host, int32_t n_listed, uint32_t* d_out, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

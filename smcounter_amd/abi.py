@@ -61,6 +61,11 @@ assert SCAN_LOCUS_DTYPE.itemsize == 8 and SCAN_VERDICT_DTYPE.itemsize == 16
 SCAN_NOT, SCAN_CALLED, SCAN_HOST, SCAN_MT_MASK = 0, 1, 2, 0x3FFFFFFF
 # (smc_scan_detect_keys) what d_alt_id holds where no extras entry of the copy shows the listed key / where the host has to look
 SCAN_ID_NONE, SCAN_ID_HOST = 0xFFFFFFFF, 0xFFFFFFFE
+# (smc_scan_filter) the four names only postfilter adds, behind the ten SMC_F_* bits; the 14 names of a FILTER column in the order of
+# their bits; the bit that leaves a row's FILTER to the host
+F_REPT, F_REPS, F_SL, F_OTHER_REPEAT = 0x400, 0x800, 0x1000, 0x2000
+SCAN_FILTER_NAMES = FILTER_NAMES + ((F_REPT, "RepT"), (F_REPS, "RepS"), (F_SL, "SL"), (F_OTHER_REPEAT, "Other_Repeat"))
+SCAN_FLT_DEVICE_MASK, SCAN_FLT_NAMES_MASK, SCAN_FLT_HOST = 0x3FF, 0x3FFF, 0x80000000
 
 
 def c_params(p: VcParams) -> SmcParams:

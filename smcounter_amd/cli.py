@@ -305,6 +305,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "<outPrefix>.spikeScan<t>.dsRpb<r>.rate.bedgraph, .spikeScan.dsRpb<r>.t95.bedgraph and .spikeScan<t>.r95.bedgraph "
                         "(twice the largest of --rpb and the targets where full depth fails); targets x reads-per-barcode targets at most "
                         "%d.  With --lod these pages carry no LOD column.  Needs --spikeScan; not with --spikeScanDepth" % GRID_MAX_CELLS)
+    p.add_argument("--spikeScanFilter", action="store_true", default=False,
+                   help="--spikeScan's rates over the replicates that are called AND whose FILTER is PASS, and which flags took the "
+                        "others away: behind every verdict the GPU decides the FILTER column of the row (smc_scan_filter: the device's "
+                        "eight flags, HP / LowC and the repeat names of the planted variant from two words made once per listed variant) "
+                        "- by definition the FILTER and CALLED columns of the pass's own .spikeAF.replicates.txt.  Writes "
+                        "<outPrefix>.spikeScan.filter.txt (REPS, CALLED, PASS, RATE_PASS with its interval and a count per FILTER name), "
+                        ".spikeScan.filter.curve.txt (RATE_PASS at every target and T95_PASS), <outPrefix>.spikeScan<t>.passrate.bedgraph "
+                        "and .spikeScan.t95pass.bedgraph; with --spikeScanDepth / --spikeScanRpb also .spikeScan.depth.filter.txt / "
+                        ".spikeScan.rpb.filter.txt.  Every other file of the scan stays as it is.  Needs --spikeScan")
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -786,7 +795,8 @@ def _spike_scan(args, plan, ref, eng, params):
     try:
         out = devplanes.spike_scan(args.bamFile, ref, scan["variants"], scan["passes"], scan["targets"], params, int(args.dsSeed), scan["reps"],
                                    eng, threshold, repeats, sampler=getattr(args, "sampler", "reference"),
-                                   sampler_seed=getattr(args, "samplerSeed", 0), indel="indel" in scan, depth=depth, rpb=rpb)
+                                   sampler_seed=getattr(args, "samplerSeed", 0), indel="indel" in scan, depth=depth, rpb=rpb,
+                                   **(dict(flt=True) if "filter" in scan else {}))
     except (ValueError, bamio.BamError) as e:
         raise SystemExit(str(e))
     for (k, _), st in zip(scan["passes"], out["passes"]):
@@ -1349,6 +1359,31 @@ def _scan_reports(args, plan, shard):
         for r, rule in zip(rpbs, out["rpb_rules"]):
             print("--spikeScanRpb %g: sampler philox, seed %d, probKeep %.6g, threshold %d, %d of %d read names kept (mtDepth %d)" %
                   (r, rule["seed"], rule["prob_keep"], rule["thr"], rule["n_kept"], rule["n_names"], params.mtDepth))
+    if "filter" in scan:
+        _scan_filter_reports(args, plan, shard)
+
+
+def _scan_filter_reports(args, plan, shard):
+    """--spikeScanFilter: the filter pages from the stage's verdicts and FILTER words, and the closing line of the run log."""
+    from . import spike as _spike
+    scan, out = plan.scan, shard.scan
+    variants, targets = scan["variants"], scan["targets"]
+    mt_depth = plan.outputs[0].params.mtDepth
+    _spike.write_scan_filter(args.outPrefix, scan["loci"], variants, targets, [n for n, _ in out["base"]], out["called"], out["filter"])
+    held = [(out["called"], out["filter"])]
+    if "fracs" in scan:
+        _spike.write_scan_filter_cells(args.outPrefix, variants, targets, scan["fracs"], [_spike.scan_depth_mt(mt_depth, f) for f in scan["fracs"]],
+                                       out["depth_called"], out["depth_filter"])
+        held.append((out["depth_called"], out["depth_filter"]))
+    if "rpbs" in scan:
+        _spike.write_scan_filter_cells(args.outPrefix, variants, targets, scan["rpbs"], [mt_depth] * len(scan["rpbs"]), out["rpb_called"],
+                                       out["rpb_filter"], _spike.RPB_AXIS)
+        held.append((out["rpb_called"], out["rpb_filter"]))
+    n_called = sum(int(c.sum()) for c, _ in held)
+    n_pass = sum(int((c & (w == 0)).sum()) for c, w in held)
+    totals = [sum(int((c & ((w & bit) != 0)).sum()) for c, w in held) for bit, _ in abi.SCAN_FILTER_NAMES]
+    print("--spikeScanFilter: %d of %d called records PASS, the FILTER of %d decided by the host; %s" %
+          (n_pass, n_called, out["filter_host"], ", ".join("%s %d" % (name, n) for (_, name), n in zip(abi.SCAN_FILTER_NAMES, totals))))
 
 
 def _run(args, plan, loc_list, t0):

@@ -161,3 +161,37 @@ __global__ __launch_bounds__(SCD_BLOCK) void k_sdk_detect(const smc_row* __restr
         if (v == SMC_SCAN_HOST) host_list[atomicAdd(n_host, 1u)] = idx;       // (at most n_copies * n_listed appends: the list's size)
     }
 }
+
+// ------------------------------------------------------------------------------------------
+// --spikeScanFilter: the FILTER column of a listed locus's row as a word of bits (smc_scan_filter)
+// ------------------------------------------------------------------------------------------
+// What the user of a run acts on is a .cut row whose FILTER is PASS.  Of the 14 names the column can hold, eight are decided by
+// k_filter_loci and stand in cand.flt; HP and LowC need the genome (rows.filter_string), the repeat names the run's BEDs
+// (postfilter._apply_one) - but for the variant a pass PLANTED at the locus those depend on chromosome, position, REF, ALT and the
+// files alone: constants of the listed variant, made once on the host as two words
+//     gate     SMC_F_HP and / or SMC_F_LOWC of hpregion.is_hp_or_lowcomp - they apply where filterVariants ran and cand.vmf_lt_099;
+//     always   the repeat names of the position (bits 10 .. 13, and SMC_F_LOWC for RepeatMasker's Low_complexity) - they apply where
+//              int(float(py2 round(PI, 2))) >= 5, filterVariants or not: PI > 4.995 outside a band of 1e-6 that py2's round decides.
+//   k_scan_filter  a lane per (copy = blockIdx.y, listed locus), from cand[0] alone: the word with one vector store, bit 31
+//                  (SMC_SCAN_FLT_HOST) where the host has to print the row - a status that is not 0, a bi-allelic row (the candidate
+//                  printed is chosen with the genome in hand), PI NaN or inside the band, flt_applied neither 0 nor 1.
+// The host reads a word only where the detect call's verdict is CALLED (cand[0] is the planted variant there).  Nothing but `out`
+// is written; the verdict records are neither read nor written.  Once per called batch, G x B lanes.
+__global__ __launch_bounds__(SCD_BLOCK) void k_scan_filter(const smc_row* __restrict__ rows, uint32_t n_loci,
+                                                           const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ gate,
+                                                           const uint32_t* __restrict__ always, uint32_t n_listed, double lo, double hi,
+                                                           uint32_t* __restrict__ out) {
+    const uint32_t c = blockIdx.y;
+    for (uint32_t g = blockIdx.x * SCD_BLOCK + threadIdx.x; g < n_listed; g += gridDim.x * SCD_BLOCK) {
+        const smc_row* const r = rows + ((size_t)c * n_loci + offsets[g]);    // (the host checked the offset < n_loci on its copy)
+        const int32_t status = r->status, bi = r->biallelic;
+        const int32_t applied = r->cand[0].flt_applied, below = r->cand[0].vmf_lt_099;
+        const uint32_t flt = r->cand[0].flt;
+        const double pi = r->cand[0].pi;
+        uint32_t w = 0;
+        if (applied != 0) w = (flt & SMC_SCAN_FLT_DEVICE_MASK) | (below != 0 ? gate[g] : 0u);
+        if (pi > hi) w |= always[g];
+        if (status != 0 || bi != 0 || !(pi < lo || pi > hi) || (applied != 0 && applied != 1)) w |= SMC_SCAN_FLT_HOST;
+        out[(size_t)c * n_listed + g] = w;
+    }
+}

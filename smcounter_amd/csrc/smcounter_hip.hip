@@ -83,7 +83,7 @@
 #include "k_spike_indel.inc"   // --spikeIndels: listed insertions / deletions planted in a copy of a run: count, scan, scatter of the relocated records
 #include "k_spike_cells.inc"   // --spikeReps, --spikeDepth, --spikePhase: the achieved counts per variant or phase set, replicate and cell, without a copy
 #include "k_spike_rpb.inc"     // --spikeRpb: a flag byte per record and listed SNV; the achieved counts per variant, replicate and cell (target x read threshold)
-#include "k_scan_detect.inc"   // --spikeScan: one verdict per (copy, listed locus) of a called batch, the rows staying in HBM
+#include "k_scan_detect.inc"   // --spikeScan: one verdict per (copy, listed locus) of a called batch, the rows staying in HBM; --spikeScanFilter: its FILTER word
                                // (--spikeScanIndel: the same for allele keys, their ids resolved per copy from the builds' extras)
 #include "k_lod.inc"           // --lod: the limit of detection per barcode depth (one lane per depth, Brent root search in FP64)
 #include "k_plan.inc"          // launch plan of a batch whose descriptors are in HBM (classify + fill)

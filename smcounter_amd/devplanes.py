@@ -3304,6 +3304,34 @@ def scan_detect_keys(eng, d_rows, n_copies: int, n_loci: int, var, ins, copies: 
     return rec.reshape(B, G), todo, ids.reshape(B, G)
 
 
+def scan_filter(eng, d_rows, n_copies: int, n_loci: int, offsets, gate_bits, always_bits):
+    """smc_scan_filter over the rows of a called batch in HBM -> uint32 [n_copies, G]: per copy and listed locus the FILTER column of
+    the row as bits (abi.SCAN_FILTER_NAMES), abi.SCAN_FLT_HOST where the host has to print the row - it says something where the detect
+    call's verdict is CALLED.  offsets: the listed loci within a copy; gate_bits, always_bits: spike.scan_filter_words' of the listed
+    variants.  One upload of 12 bytes per listed locus, one launch, 4 bytes per record down."""
+    from .engine import DevBuf
+    B, G = int(n_copies), len(offsets)
+    host = np.ascontiguousarray(np.stack([np.asarray(a, np.uint32).reshape(G) for a in (offsets, gate_bits, always_bits)]))
+    n = B * G
+    if not B and d_rows is None:                # (no copy, no rows: nothing to ask)
+        return np.zeros((0, G), np.uint32)
+    bufs = [DevBuf(eng, host.nbytes + 256).upload(host.view(np.uint8).reshape(-1) if G else np.zeros(4, np.uint8)), DevBuf(eng, 4 * max(1, n) + 256)]
+    try:
+        at = bufs[0].data_ptr()
+        _lib.check(eng.L.smc_scan_filter(eng.ctx, d_rows.data_ptr() if d_rows is not None else None, B, int(n_loci), at, host[0].ctypes.data,
+                                         at + 4 * G, host[1].ctypes.data, at + 8 * G, host[2].ctypes.data, G, bufs[1].data_ptr(),
+                                         ctypes.c_void_p(0)), "smc_scan_filter")
+        out = bufs[1].download(np.uint32, n) if n else np.zeros(0, np.uint32)      # (the default stream: behind the kernel)
+    finally:
+        for b in bufs:
+            b.free()
+    return out.reshape(B, G)
+
+
+def _filter_names(word: int) -> str:
+    return ";".join(name for bit, name in abi.SCAN_FILTER_NAMES if word & bit) or "PASS"
+
+
 def scan_called_host(text, v, threshold: int, repeats) -> bool:
     """Was `v` called in the raw row `text`, the way the replicate pages decide it: the row through the repeat filters and the .cut
     rule (dsaf.replicate_entry), then REF and ALT compared (spike._called)."""
@@ -3313,7 +3341,7 @@ def scan_called_host(text, v, threshold: int, repeats) -> bool:
 
 
 def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed,
-               bits, threshold, repeats, check0, indel: dict = None, depth: dict = None, rpb: dict = None):
+               bits, threshold, repeats, check0, indel: dict = None, depth: dict = None, rpb: dict = None, flt: dict = None):
     """The _SpikedCopies of the run at one target, one per seed of `part_seeds`, each built behind the other into one device batch and
     the batch called with one plan - _spike_rep_call's way - but the rows stay in HBM: smc_scan_detect gives a verdict per (copy,
     listed locus), and only the rows it leaves to the host come down, one by one, to be printed and cut the existing way.  run.group:
@@ -3335,8 +3363,14 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
     `rpb` (--spikeScanRpb: dict(targets, params, thresholds: per reads-per-barcode target the cell's VcParams and cut, var, var_ins,
     want: as `depth`'s per target r, masks: the device address of the first copy's first keep mask, n_words: words per mask,
     copy_stride: words from a copy's masks to the next one's)): the same with ONE select_copies_reads call in place of select_copies
-    - whole read names kept by the copy's seed's masks, the kept ids renumbered -, the builds told so (_KeptRun's by_read)."""
-    from . import vc
+    - whole read names kept by the copy's seed's masks, the kept ids renumbered -, the builds told so (_KeptRun's by_read).
+    `flt` (--spikeScanFilter: dict(gate, always: spike.scan_filter_words' of run.group)): behind every detect call smc_scan_filter
+    gives the FILTER word per (copy, listed locus) from the same rows.  A CALLED record whose word has abi.SCAN_FLT_HOST joins the rows
+    that come down, and so gets its FILTER from the printed row, as a HOST verdict the host calls does; replicate 0's CALLED rows come
+    down anyway, and the names of the printed row must be the device word's.  flt["out"] is filled: per batch decided - full depth,
+    then the cells in order - (uint32 [copies, listed]: the 14 name bits, meaningful where called, the records whose FILTER the host
+    decided)."""
+    from . import dsaf, spike as _spike, vc
     from .engine import DevBuf
     A, lo, nl, chrom = run.A, run.lo, run.nl, run.chrom
     B, G = len(part_seeds), len(run.group)
@@ -3372,11 +3406,15 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
                     return extras_table(lists[c], a, keys[c], chrom, lo, fasta)
             verdict = (rec["mt_verdict"] >> 30).astype(np.int64)
             called = verdict == abi.SCAN_CALLED
+            words, fhost, n_fhost = None, set(), 0
+            if flt is not None:
+                words = scan_filter(eng, d_rows, B, nl, listed["offset"], flt["gate"], flt["always"])
+                fhost = set(int(x) for x in np.flatnonzero((called & ((words & abi.SCAN_FLT_HOST) != 0)).reshape(-1)))
             theirs = set(int(x) for x in todo)
             if theirs != set(int(x) for x in np.flatnonzero(verdict.reshape(-1) == abi.SCAN_HOST)):
                 raise RuntimeError("%s: %s:%d-%d%s: the list of the records for the host is not that of the HOST verdicts" %
                                    (flag, chrom, lo + 1, lo + nl, what))
-            mine = sorted(theirs | (set(check0 * G + g for g in range(G)) if check0 is not None else set()))
+            mine = sorted(theirs | fhost | (set(check0 * G + g for g in range(G)) if check0 is not None else set()))
             if mine:
                 at = [int(listed["offset"][i % G]) for i in mine]
                 got = np.empty(len(mine), abi.ROW_DTYPE)
@@ -3400,6 +3438,18 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
                                            (flag, who, v.chrom, v.pos, v.ref, v.alt, what, entry,
                                             "CALLED" if called[i // G, i % G] else "NOT", float(rec[i // G, i % G]["pi"]),
                                             cut, "called" if host else "not called", line))
+                    if flt is not None and host:
+                        seen = _spike.scan_filter_of_text(dsaf.replicate_entry(line, cut, *repeats)[0][-1])
+                        if i in theirs or i in fhost:
+                            words[i // G, i % G] = seen
+                            n_fhost += 1
+                        elif seen != int(words[i // G, i % G]) & abi.SCAN_FLT_NAMES_MASK:
+                            raise RuntimeError("--spikeScanFilter: seed %d at %s:%d %s>%s%s: smc_scan_filter says %#x (%s), the row as the "
+                                               "run would print it says %#x (%s):\n%s" %
+                                               (int(part_seeds[i // G]), v.chrom, v.pos, v.ref, v.alt, what, int(words[i // G, i % G]),
+                                                _filter_names(int(words[i // G, i % G])), seen, _filter_names(seen), line))
+            if flt is not None:
+                flt["out"].append((words & np.uint32(abi.SCAN_FLT_NAMES_MASK), n_fhost))
             return called, len(theirs)
         finally:
             if plan is not None:
@@ -3407,6 +3457,8 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
             for b in (d_rows, d):
                 if b is not None:
                     b.free()
+    if flt is not None:
+        flt["out"] = []                         # (a narrower retry starts over)
     try:
         if indel is not None and copies.totals[:, 2].any():
             raise _lib.SmcError("smc_spike_indels_reps: a copy of %s:%d-%d did not fit spike_indel_caps' bounds" % (chrom, lo + 1, lo + nl))
@@ -3460,7 +3512,7 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
 
 def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n_reps: int, eng, threshold: int, repeats,
                sampler: str = "reference", sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, indel: bool = False,
-               depth: dict = None, rpb: dict = None):
+               depth: dict = None, rpb: dict = None, flt: bool = False):
     """The stage of --spikeScan.  variants: the scan's SNV at every scanned locus (tools.spike_scan_lists.scan_variants); passes: [(k,
     the indices of pass k)] (scan_passes).  A pass is the run --spikeAF <targets> --spikeVariants <its list> --spikeReps n_reps --dsSeed
     seed: replicate j has seed (seed + j) mod 2^64, and the draws, the rewrite, NM and the thresholds are that run's.
@@ -3491,6 +3543,10 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     all r, and every r's are built and called as one batch (_scan_call's `rpb`).  The result gets rpb_counts: uint32 [V, R, T, Rr, 5],
     rpb_called: bool [V, T, Rr, R], rpb_rules: per r dict(seed, prob_keep, thr, n_kept, n_names), and the passes' dicts "selects".
     ValueError / BamError naming --spikeScanRpb: what --dsRpbSampler philox refuses.
+    `flt` (--spikeScanFilter): the two words of every variant are made once (spike.scan_filter_words: params.hpLen, `fasta`, `repeats`),
+    and behind every detect call smc_scan_filter decides the FILTER column per (copy, listed locus) on the same rows (_scan_call's
+    `flt`).  The result gets filter: uint32 [V, T, R] - the 14 name bits of abi.SCAN_FILTER_NAMES where `called` -, with an axis
+    depth_filter / rpb_filter: uint32 [V, T, F, R], and filter_host: the called records whose FILTER the host decided.
     -> dict(seeds, base: per variant (N, V0), counts: uint32 [V, R, T, 3] = (S, READS, V1), called: bool [V, T, R], passes: per pass
     of `passes` dict(variants, copies, builds, host, seconds), times: dict(stage, runs, decode))."""
     import time
@@ -3526,6 +3582,13 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
         rpb = dict(rpb, counts=np.zeros((V, R, T, F, 5), np.uint32), called=np.zeros((V, T, F, R), bool), read_thr=[r.thr for r in read_rules])
     for st in stats if (depth or rpb) is not None else ():
         st["selects"] = 0
+    if flt:
+        from . import spike as _spike
+        gate, always = _spike.scan_filter_words(variants, P.hpLen, fasta, *repeats)
+        flt = dict(gate=gate, always=always, words=np.zeros((V, T, R), np.uint32), host=0,
+                   cell_words=np.zeros((V, T, F, R), np.uint32) if (depth or rpb) is not None else np.zeros((V, T, 0, R), np.uint32))
+    else:
+        flt = None
     times = {"decode": 0.0, "runs": 0}
     order = sorted(range(V), key=lambda k: (variants[k].chrom, variants[k].pos))
     spans = _listed_spans(variants, order)
@@ -3551,7 +3614,7 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
                     room, caps = _copy_room(run, spikes[p].chrom_variants(chrom, 0.5)[0] if indel else None, indel,
                                             len((depth or rpb)["params"]) if (depth or rpb) is not None else 0, rpb is not None)
                     _scan_pass(eng, run, spikes[p], [int(local[k]) for k in run.group], variants, seeds, thr, P, fasta, max_depth, sampler,
-                               sampler_seed, threshold, repeats, room, base, counts, called, stats[p], caps, depth, rpb)
+                               sampler_seed, threshold, repeats, room, base, counts, called, stats[p], caps, depth, rpb, flt)
                     stats[p]["variants"] += len(run.group)
                     stats[p]["seconds"] += time.perf_counter() - t0
             finally:
@@ -3568,6 +3631,10 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     if rpb is not None:
         out.update(rpb_counts=rpb["counts"], rpb_called=rpb["called"],
                    rpb_rules=[dict(seed=r.seed, prob_keep=r.prob_keep, thr=r.thr, n_kept=r.n_kept, n_names=r.n_names) for r in read_rules])
+    if flt is not None:
+        out.update(filter=flt["words"], filter_host=flt["host"])
+        if (depth or rpb) is not None:
+            out["depth_filter" if depth is not None else "rpb_filter"] = flt["cell_words"]
     return out
 
 
@@ -3602,7 +3669,7 @@ def _scan_read_masks(eng, run: AfRun, read_rules, seeds) -> dict:
 
 
 def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr, P, fasta, max_depth, sampler, sampler_seed, threshold,
-               repeats, room, base, counts, called, stat, caps=None, depth: dict = None, rpb: dict = None):
+               repeats, room, base, counts, called, stat, caps=None, depth: dict = None, rpb: dict = None, flt: dict = None):
     """spike_scan's work for one pass in one run: run.group are the pass's variants there (indices into `variants`), members[g] the
     place of run.group[g] in the pass's list (`spikes`).  base, counts, called and stat are filled.  `caps` (--spikeScanIndel:
     spike_indel_caps of the pass's list on the run): the indel branch.  `depth` (--spikeScanDepth: spike_scan's dict with "counts" and
@@ -3610,7 +3677,8 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
     copies the cells' verdicts (_scan_call's `depth`); both are filled.  `rpb` (--spikeScanRpb: spike_scan's dict with "counts",
     "called" and the run's "p_idents", "first", "masks", "n_words"): the same on the read axis - smc_spike_read_bits
     (smc_spike_indel_read_bits) on the pass's variants, spike_rpb_records per variant and ONE spike_rpb_counts call for the cells'
-    counters; a batch's mask base is that of its first seed."""
+    counters; a batch's mask base is that of its first seed.  `flt` (--spikeScanFilter: spike_scan's dict with "gate", "always",
+    "words", "cell_words" and "host"): per batch the FILTER words of the copies (_scan_call's `flt`); the last three are filled."""
     A, up, lo, chrom = run.A, run.up, run.lo, run.chrom
     idents, (nm, n_indel) = run.idents, run.mism
     group = run.group
@@ -3660,13 +3728,20 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
                     tail += (None, dict(targets=rpb["targets"], params=rpb["params"], thresholds=rpb["thresholds"], var=var, var_ins=ins,
                                         want=want, masks=rpb["masks"].data_ptr() + 4 * rpb["n_words"] * F * js[0], n_words=rpb["n_words"],
                                         copy_stride=rpb["n_words"] * F),)
-            got = _narrow_retry(eng, P, lambda bits: _scan_call(*args, bits, *tail))
+            fl = dict(gate=flt["gate"][group], always=flt["always"][group]) if flt is not None else None
+            got = _narrow_retry(eng, P, lambda bits: _scan_call(*args, bits, *tail, flt=fl))
             yes, n_host, builds = (got[0], got[2], got[3]) if axis is not None else (got[0], got[1], 1)
             for c, j in enumerate(js):
                 for g, k in enumerate(group):
                     called[k, t, j] = yes[c, g]
                     for f in range(F):
                         axis["called"][k, t, f, j] = got[1][f][c, g]
+                    if flt is not None:
+                        flt["words"][k, t, j] = fl["out"][0][0][c, g]
+                        for f in range(F):
+                            flt["cell_words"][k, t, f, j] = fl["out"][1 + f][0][c, g]
+            if flt is not None:
+                flt["host"] += sum(n for _, n in fl["out"])
             stat["copies"] += len(js)
             stat["builds"] += len(js) * builds
             stat["host"] += n_host

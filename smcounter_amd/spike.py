@@ -41,11 +41,18 @@ the called rows on the GPU (smc_scan_detect).
 and refuses the flag; tools.spike_scan_lists.scan_indels is the rule); the files and their writers are --spikeScan's, REF and ALT the
 indel's texts at its anchor, the verdicts from smc_scan_detect_keys.
 
+--spikeScanFilter: the scan's rates over the replicates that are called AND whose FILTER is PASS, and which of the 14 FILTER names
+took the others away (scan reads the switch).  The two words per listed variant smc_scan_filter takes (scan_filter_words), its host
+twin (scan_filter_host), a printed FILTER column as the same word (scan_filter_of_text), and the pages
+<outPrefix>.spikeScan.filter.txt, .filter.curve.txt, .spikeScan<t>.passrate.bedgraph and .spikeScan.t95pass.bedgraph
+(write_scan_filter) and, per axis, .spikeScan.depth.filter.txt / .spikeScan.rpb.filter.txt (write_scan_filter_cells).
+
 The semantics are tools/spike_variants.py's (DESIGN.md "--spikeAF"); the rewrite on the GPU is csrc/k_spike.inc (smc_spike_alleles),
 the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the main pass are devplanes.spike_rules / spike_run.
 """
 from __future__ import annotations
 
+from . import abi as _abi
 from . import dsaf
 from .tools import ds_allele_fraction as af
 from .tools import spike_variants as sv
@@ -695,15 +702,18 @@ def scan(args):
     is no list of numbers, a fraction outside (0, 1] or listed twice, more than MAX_CELLS targets x fractions.
     --spikeScanRpb adds "rpbs": the reads-per-barcode targets of the scan's read axis.  SystemExit: the flag without --spikeScan or
     beside --spikeScanDepth (the t x f x r grid is not built), text that is no list of numbers, a target <= 0 or listed twice, more
-    than MAX_CELLS targets x reads-per-barcode targets."""
+    than MAX_CELLS targets x reads-per-barcode targets.
+    --spikeScanFilter (a switch) adds "filter": True.  SystemExit: the switch without --spikeScan."""
     from .tools import spike_scan_lists as lists
     text, r, stride, alt = (getattr(args, f, None) for f in SCAN_FLAGS)
     indel = getattr(args, "spikeScanIndel", None)
     fracs = getattr(args, "spikeScanDepth", None)
     rpbs = getattr(args, "spikeScanRpb", None)
+    flt = getattr(args, "spikeScanFilter", None)
     given = lambda x: x not in (None, "", False)
     if not given(text):
-        for flag, value in zip(SCAN_FLAGS[1:] + ("spikeScanIndel", "spikeScanDepth", "spikeScanRpb"), (r, stride, alt, indel, fracs, rpbs)):
+        for flag, value in zip(SCAN_FLAGS[1:] + ("spikeScanIndel", "spikeScanDepth", "spikeScanRpb", "spikeScanFilter"),
+                               (r, stride, alt, indel, fracs, rpbs, flt)):
             if given(value):
                 raise SystemExit("--%s belongs to --spikeScan: it needs --spikeScan" % flag)
         return None
@@ -758,6 +768,8 @@ def scan(args):
                              "reads-per-barcode targets is not built")
         # (the targets' texts and limits are --spikeRpb's: the scan's targets stand where the --spikeAF targets do)
         out["rpbs"] = _rpb_cells(rpbs, [(t, 0, "") for t in ts], "spikeScanRpb")[0]
+    if given(flt):
+        out["filter"] = True
     return out
 
 
@@ -977,3 +989,144 @@ def write_scan_rpb(out_prefix: str, loci, variants, targets, rpbs, mt_depth: int
         with open("%s.spikeScan.dsRpb%g.t95.bedgraph" % (out_prefix, rpb), "w") as fh:
             for chrom, pos, i in loci:
                 fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "1" if i is None or t95s[r][i] == dsaf.NA else t95s[r][i]))
+
+
+# ---- --spikeScanFilter: the scan's rates over the replicates that are called AND PASS, and a tally per FILTER name
+SCAN_FILTER_NAMES = tuple(name for _, name in _abi.SCAN_FILTER_NAMES)
+SCAN_FILTER_HEADER = ("CHROM", "POS", "REF", "ALT", "TARGET", "REPS", "CALLED", "PASS", "RATE_PASS", "LO95", "HI95") + SCAN_FILTER_NAMES
+_FILTER_BIT = {name: bit for bit, name in _abi.SCAN_FILTER_NAMES}
+# (postfilter.load_repeat_regions' flag texts: RepeatMasker's Low_complexity is the LowC the low-complexity window gives)
+_REPEAT_BIT = {"RepT": _abi.F_REPT, "RepS": _abi.F_REPS, "SL": _abi.F_SL, "Other_Repeat": _abi.F_OTHER_REPEAT, "LowC": _abi.F_LOWC}
+SCAN_FILTER_PI_EDGE = 4.995     # round(PI, 2) >= 5 above it; py2's round decides within +- 1e-6 (smc_scan_filter's band)
+
+
+def _repeat_bits(regions, chrom: str, pos: int) -> int:
+    """The names the FIRST interval of `regions` with lo < pos <= hi holds (postfilter._apply_one's rule), as bits."""
+    for lo, hi, flag in regions.get(chrom, ()):
+        if lo < pos <= hi:
+            bits = 0
+            for name in flag.split(";"):
+                if name:
+                    bits |= _REPEAT_BIT[name]
+            return bits
+    return 0
+
+
+def scan_filter_words(variants, hp_len: int, refprov, trf, rm):
+    """The two words per listed variant smc_scan_filter takes -> (gate, always), uint32 [len(variants)] each.  gate: F_HP and / or
+    F_LOWC of hpregion.is_hp_or_lowcomp on the variant's REF and ALT - rows.filter_string sets them where cand.vmf_lt_099; always:
+    the names postfilter.apply_repeat_filters appends at the position from the run's `trf` / `rm` regions
+    (postfilter.load_repeat_regions), RepeatMasker's LowC as F_LOWC.  Constants of the variant: nothing of a row is read."""
+    import numpy as np
+    from .hpregion import is_hp_or_lowcomp
+    gate, always = np.zeros(len(variants), np.uint32), np.zeros(len(variants), np.uint32)
+    for i, v in enumerate(variants):
+        homop, lowcomp = is_hp_or_lowcomp(v.chrom, str(int(v.pos)), hp_len, v.ref, v.alt, refprov)
+        gate[i] = (_abi.F_HP if homop else 0) | (_abi.F_LOWC if lowcomp else 0)
+        always[i] = _repeat_bits(trf, v.chrom, int(v.pos)) | _repeat_bits(rm, v.chrom, int(v.pos))
+    return gate, always
+
+
+def scan_filter_host(row, gate: int, always: int) -> int:
+    """k_scan_filter's word for one abi.ROW_DTYPE record, on the host: the same comparisons on the same doubles."""
+    c0 = row["cand"][0]
+    applied, pi = int(c0["flt_applied"]), float(c0["pi"])
+    lo, hi = SCAN_FILTER_PI_EDGE - 1e-6, SCAN_FILTER_PI_EDGE + 1e-6
+    w = 0
+    if applied != 0:
+        w = (int(c0["flt"]) & _abi.SCAN_FLT_DEVICE_MASK) | (int(gate) if int(c0["vmf_lt_099"]) != 0 else 0)
+    if pi > hi:
+        w |= int(always)
+    if int(row["status"]) != 0 or int(row["biallelic"]) != 0 or not (pi < lo or pi > hi) or applied not in (0, 1):
+        w |= _abi.SCAN_FLT_HOST
+    return w
+
+
+def scan_filter_of_text(text: str) -> int:
+    """A printed FILTER column (after postfilter.apply_repeat_filters: PASS, or names joined by ';') as the word of its names' bits - a
+    name counts once.  ValueError: a name that is none of the 14 (Zero_Coverage: no called row holds it)."""
+    if text == "PASS":
+        return 0
+    w = 0
+    for name in text.split(";"):
+        if name not in _FILTER_BIT:
+            raise ValueError("FILTER %r holds %r, none of %s" % (text, name, " ".join(SCAN_FILTER_NAMES)))
+        w |= _FILTER_BIT[name]
+    return w
+
+
+def scan_filter_tally(called, words):
+    """-> (replicates called, those whose word is 0 = PASS, per name of SCAN_FILTER_NAMES the called replicates whose word holds it)."""
+    hit = [int(w) & _abi.SCAN_FLT_NAMES_MASK for c, w in zip(called, words) if c]
+    return len(hit), sum(1 for w in hit if w == 0), [sum(1 for w in hit if w & bit) for bit, _ in _abi.SCAN_FILTER_NAMES]
+
+
+def scan_filter_line(v, target, called, words) -> str:
+    """One line of the filter page: variant `v` at `target`; called[j] / words[j]: replicate j's verdict and, where it is called, its
+    FILTER word.  RATE_PASS = PASS / REPS with its Wilson interval (dsaf.wilson, as the sensitivity pages'), then the tally."""
+    n = len(called)
+    n_called, n_pass, tally = scan_filter_tally(called, words)
+    lo, hi = dsaf.wilson(n_pass, n)
+    return "\t".join([v.chrom, "%d" % v.pos, v.ref, v.alt, dsaf.target_text(target), "%d" % n, "%d" % n_called, "%d" % n_pass,
+                      dsaf.frac_text(float(n_pass) / n), dsaf.frac_text(lo), dsaf.frac_text(hi)] + ["%d" % x for x in tally])
+
+
+def scan_filter_curve_header(targets):
+    return CURVE_HEADER + tuple("RATE_PASS@%g" % t for t in sorted(targets)) + ("T95_PASS",)
+
+
+def scan_filter_curve_line(v, n: int, targets, rates) -> str:
+    """curve_line() on the PASS rates: rates[t] of targets[t]; T95_PASS by dsaf.t95's rule."""
+    best = dsaf.t95(targets, rates)
+    return "\t".join([v.chrom, "%d" % v.pos, v.ref, v.alt, "%d" % n] +
+                     [dsaf.frac_text(rates[t]) for t in sorted(range(len(targets)), key=lambda t: targets[t])] +
+                     [dsaf.NA if best is None else "%g" % best])
+
+
+def write_scan_filter(out_prefix: str, loci, variants, targets, ns, called, words) -> None:
+    """The pages of --spikeScanFilter.  loci, variants, targets: write_scan's; ns[i]: variant i's covering barcodes; called[i][t] /
+    words[i][t]: per replicate the verdict and the FILTER word of variant i at targets[t].
+      <outPrefix>.spikeScan.filter.txt            scan_filter_line per scanned locus and target
+      <outPrefix>.spikeScan.filter.curve.txt      scan_filter_curve_line per scanned locus
+      <outPrefix>.spikeScan<t>.passrate.bedgraph  chrom, pos - 1, pos, RATE_PASS of that target - the page's text - per scanned locus
+      <outPrefix>.spikeScan.t95pass.bedgraph      chrom, pos - 1, pos, T95_PASS; 1 where it is NA and at a skipped locus"""
+    T = len(targets)
+    rates, t95s = [[] for _ in range(T)], []
+    i_rate, i_t95 = SCAN_FILTER_HEADER.index("RATE_PASS"), len(CURVE_HEADER) + T
+    with open(out_prefix + ".spikeScan.filter.txt", "w") as fs, open(out_prefix + ".spikeScan.filter.curve.txt", "w") as fc:
+        fs.write("\t".join(SCAN_FILTER_HEADER) + "\n")
+        fc.write("\t".join(scan_filter_curve_header(targets)) + "\n")
+        for i, v in enumerate(variants):
+            mine = []
+            for t, target in enumerate(targets):
+                line = scan_filter_line(v, target, called[i][t], words[i][t])
+                rates[t].append(line.split("\t")[i_rate])
+                mine.append(float(scan_filter_tally(called[i][t], words[i][t])[1]) / len(called[i][t]))
+                fs.write(line + "\n")
+            line = scan_filter_curve_line(v, int(ns[i]), targets, mine)
+            t95s.append(line.split("\t")[i_t95])
+            fc.write(line + "\n")
+    for t, target in enumerate(targets):
+        with open("%s.spikeScan%g.passrate.bedgraph" % (out_prefix, target), "w") as fh:
+            for chrom, pos, i in loci:
+                if i is not None:
+                    fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), rates[t][i]))
+    with open(out_prefix + ".spikeScan.t95pass.bedgraph", "w") as fh:
+        for chrom, pos, i in loci:
+            fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "1" if i is None or t95s[i] == dsaf.NA else t95s[i]))
+
+
+def scan_filter_cells_header(axis=DEPTH_AXIS):
+    return SCAN_FILTER_HEADER[:5] + (axis[1], "MTDEPTH") + SCAN_FILTER_HEADER[5:]
+
+
+def write_scan_filter_cells(out_prefix: str, variants, targets, values, mt_depths, called, words, axis=DEPTH_AXIS) -> None:
+    """<outPrefix>.spikeScan.depth.filter.txt (axis RPB_AXIS: .spikeScan.rpb.filter.txt): scan_filter_line per scanned locus, target
+    and cell with the axis column and MTDEPTH behind TARGET.  values / mt_depths: the cells' fractions (reads-per-barcode targets)
+    and mtDepths; called[i][t][f] / words[i][t][f]: per replicate."""
+    with open("%s.spikeScan.%s.filter.txt" % (out_prefix, axis[0]), "w") as fh:
+        fh.write("\t".join(scan_filter_cells_header(axis)) + "\n")
+        for i, v in enumerate(variants):
+            for t, target in enumerate(targets):
+                for f, value in enumerate(values):
+                    fh.write("\t".join(_cell_fields(scan_filter_line(v, target, called[i][t][f], words[i][t][f]), value, mt_depths[f])) + "\n")

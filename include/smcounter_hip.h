@@ -1112,6 +1112,45 @@ int smc_build_planes_w16(smc_ctx* ctx, const smc_params* params, const smc_build
                          uint16_t* words16, uint32_t* umi_start, uint32_t* u_gid, uint32_t* u_finc, smc_locus* loci,
                          uint32_t* xlist, uint32_t xcap, uint32_t* counters, void* stream);
 
+/* Build only LISTED loci of a run, for several copies of it, in one call (--spikeScanBuild listed): for B copies and G listed loci
+ * (run offsets `offsets[g]`, strictly ascending, HOST memory) what smc_build_planes / smc_build_planes_w16 write for those loci -
+ * the read words, the umi_start / u_gid / u_finc stretch, the descriptor, the extras entries, the status bits: byte for byte - as a
+ * dense batch of B x G loci, copy-major: locus g of copy c is batch locus c * G + g.
+ * `d_copies` (DEVICE memory): per copy where its records, CIGAR pool, (letter, quality) pool and smc_dev_locus array lie and
+ * its counts - the copies of smc_spike_alleles_reps / smc_spike_indels_reps and the selections of smc_select_alignments_copies /
+ * _reads_copies all fit it.  `flags` & SMC_LISTED_SHARED_ORDER: the copies have the same spans, barcode ids and pair ids (spiked
+ * copies of one run: spiking changes bases, CIGARs and NM only) - the barcode-major order of a locus is then made once, from copy
+ * 0 (and a declined copy 0 declines them all).  `flags` & SMC_LISTED_DENSE_LOCUS: the locus field of an extras entry holds g, the
+ * locus's place in a copy of the dense batch, not the run offset - what smc_scan_detect_keys needs when it is told that a copy has
+ * n_listed rows and its listed variants' `locus` fields are 0 .. n_listed - 1.
+ * `caps[g]` (HOST memory; a multiple of 4, below 2^24): the slots listed locus g gets in every copy - at least the 4-aligned depth
+ * of the locus in any copy (align4 of loc[offsets[g]].n of the unselected, unspiked run: spiking changes no span, a selection
+ * only drops records).  With S the sum of the capacities: the words of batch locus c * G + g start at slot slot_base + c * S +
+ * (caps[0] + .. + caps[g - 1]), its umi_start / u_gid / u_finc entries at umi_base + c * (S + G) + (caps[0] + .. + caps[g - 1]) + g
+ * (n_umi + 1 of them); loci[B * G] holds the batch-relative read_off4 / umi_off.  `word_bits` 16 or 32 (`words` is then uint16 or
+ * uint32; 16: params->min_bq in 0 .. 63).  Copy c's extras entries go to xlist + 5 * xcap * c - five words as smc_build_planes'
+ * with the locus field holding the RUN offset offsets[g] (or g: SMC_LISTED_DENSE_LOCUS), in the order of the listed loci and of the allele ids - and
+ * counters[2 c] = their number, counters[2 c + 1] = the copy's status bits: smc_build_planes' (1 a locus's reads differ from its
+ * copy's loc[].n or exceed caps[g], 2 more than xcap extras, 4 base quality > 126, 8 more than 64 alleles, 32 no room in 16-bit
+ * words) and SMC_LISTED_UNFLAGGED: the copy has an alignment flagged neither READ1 nor READ2 - it is declined (such reads need
+ * the whole builder's look-back rule) and nothing but its counters is written.  The raw-field planes are the whole builder's.
+ * A listed locus may be as deep as smc_build_max_depth().  No atomic operation orders an output: two calls leave the same bytes.
+ * Everything is checked before anything is enqueued; asynchronous on `stream`.  (ABI 11, additive.) */
+#define SMC_LISTED_MAX_LOCI 64
+#define SMC_LISTED_MAX_COPIES 1024
+#define SMC_LISTED_UNFLAGGED 64u
+#define SMC_LISTED_SHARED_ORDER 1
+#define SMC_LISTED_DENSE_LOCUS 2
+typedef struct smc_listed_copy {       /* 48 bytes */
+    const smc_dev_aln* aln; const uint32_t* cig; const uint8_t* bq; const smc_dev_locus* loc;
+    int32_t n_aln, n_bc, n_pair, reserved;
+} smc_listed_copy;
+int smc_build_listed(smc_ctx* ctx, const smc_params* params, const smc_listed_copy* d_copies, int32_t n_copies, int32_t flags,
+                     int32_t start0, int32_t n_loci, const uint8_t* d_refseq, const uint32_t* offsets, const uint32_t* caps,
+                     int32_t n_listed, int32_t word_bits, uint32_t slot_base, uint32_t umi_base, void* words, uint32_t* umi_start,
+                     uint32_t* u_gid, uint32_t* u_finc, smc_locus* loci, uint32_t* xlist, uint32_t xcap, uint32_t* counters,
+                     void* stream);
+
 /* The context keeps the device blocks of destroyed plans for the next plan (at most 64 blocks / 8 GB; the oldest goes first).
  * smc_pool_trim waits for the plans' last runs and returns every pooled block to the runtime. */
 int smc_pool_trim(smc_ctx* ctx);

@@ -314,6 +314,14 @@ def build_parser() -> argparse.ArgumentParser:
                         ".spikeScan.filter.curve.txt (RATE_PASS at every target and T95_PASS), <outPrefix>.spikeScan<t>.passrate.bedgraph "
                         "and .spikeScan.t95pass.bedgraph; with --spikeScanDepth / --spikeScanRpb also .spikeScan.depth.filter.txt / "
                         ".spikeScan.rpb.filter.txt.  Every other file of the scan stays as it is.  Needs --spikeScan")
+    p.add_argument("--spikeScanBuild", default=None,
+                   help="whole (default) or listed: how --spikeScan builds its spiked copies.  whole: every copy is a build of its whole "
+                        "decoded run, however few of its loci the pass lists.  listed: one smc_build_listed call builds the listed loci "
+                        "alone, for all copies of a batch at once, as a dense batch of copies x listed loci - byte for byte the whole "
+                        "build's planes of those loci, so every file of the scan is the whole run's.  A batch holds as many copies as "
+                        "their listed slots allow.  A run the listed builder declines (an alignment flagged neither READ1 nor READ2) is "
+                        "built the whole way and counted in the pass's log line; the listed rows of replicate 0 are also made the whole "
+                        "way and must be equal.  Beside every other flag of the scan, --spikeScanIndel among them.  Needs --spikeScan")
     p.add_argument("--lod", action="store_true", default=False,
                    help="the theoretical limit of detection of every locus, as the reference's mt_depths_lod.R computes it from the "
                         "barcode depth (the smallest allele fraction whose variant barcodes reach ceiling((14 + 0.012 x mtDepth) / 3.5) "
@@ -796,12 +804,17 @@ def _spike_scan(args, plan, ref, eng, params):
         out = devplanes.spike_scan(args.bamFile, ref, scan["variants"], scan["passes"], scan["targets"], params, int(args.dsSeed), scan["reps"],
                                    eng, threshold, repeats, sampler=getattr(args, "sampler", "reference"),
                                    sampler_seed=getattr(args, "samplerSeed", 0), indel="indel" in scan, depth=depth, rpb=rpb,
-                                   **(dict(flt=True) if "filter" in scan else {}))
+                                   **(dict(flt=True) if "filter" in scan else {}),
+                                   **(dict(build="listed") if _spike.scan_build(scan) == "listed" else {}))
     except (ValueError, bamio.BamError) as e:
         raise SystemExit(str(e))
+    listed = _spike.scan_build(scan) == "listed"
     for (k, _), st in zip(scan["passes"], out["passes"]):
-        print("--spikeScan pass %d: %d variants, %d copies, %d builds, %d verdicts decided by the host, %.3f s" %
-              (k, st["variants"], st["copies"], st["builds"], st["host"], st["seconds"]))
+        print("--spikeScan pass %d: %d variants, %d copies, %d builds, %s%d verdicts decided by the host, %.3f s" %
+              (k, st["variants"], st["copies"], st["builds"], "%d of them whole, " % st["whole"] if listed else "", st["host"], st["seconds"]))
+    if listed:
+        print("--spikeScanBuild listed: %d listed builds, %d whole fallbacks, %d replicate-0 row checks" %
+              tuple(sum(st[k] for st in out["passes"]) for k in ("listed", "whole", "checks")))
     return out
 
 

@@ -43,6 +43,10 @@ struct smc_ctx {
     // scratch of smc_spike_indels (per alignment the relocated sizes, per workgroup their sums), grown on demand
     void* spi_scratch = nullptr;
     size_t spi_bytes = 0;
+    // scratch of smc_build_listed (the loci's sort buffers, orders and head marks, per-locus status and extras), grown on demand
+    void* bl_scratch = nullptr;
+    size_t bl_bytes = 0;
+    hipEvent_t bl_done_ev = nullptr;          // behind the last kernel of the last smc_build_listed (one scratch: as bp_done_ev)
     // scratch of the checking entries smc_fisher_tables / smc_lfact_values (arguments, then results), grown on demand
     void* chk_scratch = nullptr;
     size_t chk_bytes = 0;
@@ -491,6 +495,7 @@ void smc_destroy(smc_ctx* c) {
     (void)hipFree(c->lod_scratch);
     (void)hipFree(c->af_scratch);
     (void)hipFree(c->spi_scratch);
+    (void)hipFree(c->bl_scratch);
     (void)hipFree(c->chk_scratch);
     {
         std::vector<smc_ctx::VmmBlock> left;
@@ -505,6 +510,7 @@ void smc_destroy(smc_ctx* c) {
     for (void* h : c->spec_host_free) (void)hipHostFree(h);
     if (c->plan_fill_ev) (void)hipEventDestroy(c->plan_fill_ev);
     if (c->bp_done_ev) (void)hipEventDestroy(c->bp_done_ev);
+    if (c->bl_done_ev) (void)hipEventDestroy(c->bl_done_ev);
     for (auto& sg : c->seg_stage) { if (sg.host) (void)hipHostFree(sg.host); if (sg.ev) (void)hipEventDestroy(sg.ev); }
     for (auto e : c->bp_ev0) (void)hipEventDestroy(e);
     for (auto e : c->bp_ev1) (void)hipEventDestroy(e);
@@ -2674,6 +2680,84 @@ static int build_planes_impl(smc_ctx* ctx, const smc_params* prm, const smc_buil
     HIPCHK(hipGetLastError());
     if (!ctx->bp_done_ev) HIPCHK(hipEventCreateWithFlags(&ctx->bp_done_ev, hipEventDisableTiming));
     HIPCHK(hipEventRecord(ctx->bp_done_ev, st));
+    return SMC_OK;
+}
+
+// (--spikeScanBuild listed) the listed loci of B copies of a run as a dense batch: everything checked on the host before anything is
+// enqueued, then five launches for the whole batch (k_build_listed.inc)
+int smc_build_listed(smc_ctx* ctx, const smc_params* prm, const smc_listed_copy* d_copies, int32_t n_copies, int32_t flags,
+                     int32_t start0, int32_t n_loci, const uint8_t* d_refseq, const uint32_t* offsets, const uint32_t* caps,
+                     int32_t n_listed, int32_t word_bits, uint32_t slot_base, uint32_t umi_base, void* words, uint32_t* umi_start,
+                     uint32_t* u_gid, uint32_t* u_finc, smc_locus* loci, uint32_t* xlist, uint32_t xcap, uint32_t* counters,
+                     void* stream) {
+    const std::string who = "smc_build_listed";
+    static_assert(sizeof(smc_listed_copy) == 48, "smc_build_listed's copy record");
+    static_assert(SMC_LISTED_MAX_LOCI == BL_MAX_LOCI && SMC_LISTED_MAX_COPIES == BL_MAX_COPIES && SMC_LISTED_UNFLAGGED == BL_ST_UNFLAGGED, "smc_build_listed's limits");
+    if (!ctx || !prm) return fail(SMC_E_ARG, who + ": NULL argument");
+    if (n_copies < 0 || n_copies > SMC_LISTED_MAX_COPIES)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies, 0 .. " + std::to_string(SMC_LISTED_MAX_COPIES) + " expected");
+    if (n_listed < 0 || n_listed > SMC_LISTED_MAX_LOCI)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_listed) + " listed loci, 0 .. " + std::to_string(SMC_LISTED_MAX_LOCI) + " expected");
+    if (word_bits != 16 && word_bits != 32) return fail(SMC_E_INPUT, who + ": read words of " + std::to_string(word_bits) + " bits, 16 or 32 expected");
+    if (word_bits == 16 && (prm->min_bq < 0 || prm->min_bq > 63))
+        return fail(SMC_E_INPUT, who + ": minBQ " + std::to_string(prm->min_bq) + " has no room in a 16-bit read word (0 .. 63)");
+    if (n_loci < 0) return fail(SMC_E_INPUT, who + ": a run of " + std::to_string(n_loci) + " loci");
+    if (flags & ~(SMC_LISTED_SHARED_ORDER | SMC_LISTED_DENSE_LOCUS)) return fail(SMC_E_INPUT, who + ": flags " + std::to_string(flags) + ", bits 0 and 1 expected");
+    const bool shared_order = (flags & SMC_LISTED_SHARED_ORDER) != 0;
+    if (!n_copies) return SMC_OK;
+    if (!d_copies || !counters) return fail(SMC_E_ARG, who + ": NULL device pointer");
+    if (n_listed && (!offsets || !caps)) return fail(SMC_E_ARG, who + ": NULL argument with " + std::to_string(n_listed) + " listed loci");
+    if (n_listed && (!d_refseq || !words || !umi_start || !u_gid || !u_finc || !loci || !xlist)) return fail(SMC_E_ARG, who + ": NULL device pointer");
+    if (slot_base & 3u) return fail(SMC_E_INPUT, who + ": slot_base " + std::to_string(slot_base) + " is not on a 4-read boundary");
+    BlArgs A{};
+    uint64_t stride = 0;
+    uint32_t cap_max = 0;
+    for (int32_t g = 0; g < n_listed; ++g) {
+        if ((int64_t)offsets[g] >= (int64_t)n_loci)
+            return fail(SMC_E_INPUT, who + ": listed locus " + std::to_string(g) + " names offset " + std::to_string(offsets[g]) + " of " + std::to_string(n_loci));
+        if (g && offsets[g] <= offsets[g - 1]) return fail(SMC_E_INPUT, who + ": the listed offsets do not ascend at entry " + std::to_string(g));
+        if ((caps[g] & 3u) || caps[g] > (uint32_t)smc_build_max_depth() + 1u)
+            return fail(SMC_E_INPUT, who + ": listed locus " + std::to_string(g) + " has a capacity of " + std::to_string(caps[g]) +
+                                     " slots (a multiple of 4, at most " + std::to_string(smc_build_max_depth() + 1) + ")");
+        A.off[g] = offsets[g]; A.capoff[g] = (uint32_t)stride;
+        stride += caps[g];
+        cap_max = std::max(cap_max, caps[g]);
+    }
+    A.capoff[n_listed] = (uint32_t)stride;
+    const uint64_t G = (uint64_t)n_listed, B = (uint64_t)n_copies;
+    if ((uint64_t)slot_base + B * stride >= (1ull << 32) || (uint64_t)umi_base + B * (stride + G) + 1ull >= (1ull << 32))
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies of " + std::to_string(stride) + " slots: 2^32 slots or more");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t Bo = shared_order ? 1ull : B;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_k0 = carve(8 * Bo * stride), o_k1 = carve(8 * Bo * stride), o_v0 = carve(4 * Bo * stride), o_v1 = carve(4 * Bo * stride);
+    const size_t o_ord = carve(4 * Bo * stride), o_hi = carve(4 * Bo * stride), o_meta = carve(16 * Bo * G);
+    const size_t o_cstat = carve(4 * B), o_st = carve(4 * B * G), o_nx = carve(4 * B * G), o_xtmp = carve(20 * (size_t)BL_XMAX * B * G);
+    if (int rc = grow_scratch(ctx->bl_scratch, ctx->bl_bytes, off, off + off / 8, who.c_str(), &st)) return rc;
+    if (ctx->bl_done_ev) HIPCHK(hipStreamWaitEvent(st, ctx->bl_done_ev, 0));
+    char* sc = (char*)ctx->bl_scratch;
+    A.copies = d_copies; A.refseq = d_refseq;
+    A.n_copies = n_copies; A.n_listed = n_listed; A.shared = shared_order ? 1 : 0; A.dense = (flags & SMC_LISTED_DENSE_LOCUS) ? 1 : 0; A.start0 = start0;
+    A.min_bq = prm->min_bq; A.min_mq = prm->min_mq; A.primer_dist = prm->primer_dist; A.ds = prm->ds;
+    A.fp = (uint32_t)smc_param_fingerprint(prm->min_bq, prm->min_mq, prm->mismatch_thr, prm->primer_dist) << SMC_LF_FP_SHIFT;
+    A.w16 = word_bits == 16 ? 1u : 0u; A.slot_base = slot_base; A.umi_base = umi_base; A.stride = (uint32_t)stride;
+    A.words = words; A.umi_start = umi_start; A.u_gid = u_gid; A.u_finc = u_finc; A.loci = loci; A.xlist = xlist; A.xcap = xcap; A.counters = counters;
+    A.key[0] = (unsigned long long*)(sc + o_k0); A.key[1] = (unsigned long long*)(sc + o_k1);
+    A.val[0] = (uint32_t*)(sc + o_v0); A.val[1] = (uint32_t*)(sc + o_v1);
+    A.order = (uint32_t*)(sc + o_ord); A.hinfo = (uint32_t*)(sc + o_hi); A.meta = (uint32_t*)(sc + o_meta);
+    A.cstat = (uint32_t*)(sc + o_cstat); A.st = (uint32_t*)(sc + o_st); A.nx = (uint32_t*)(sc + o_nx); A.xtmp = (uint32_t*)(sc + o_xtmp);
+    hipLaunchKernelGGL(k_bl_check, dim3((unsigned)n_copies), dim3(256), 0, st, A);
+    if (n_listed) {
+        hipLaunchKernelGGL(k_bl_sort, dim3((unsigned)n_listed, (unsigned)Bo), dim3(64 * BL_SORT_WAVES), 0, st, A);
+        if (cap_max) hipLaunchKernelGGL(k_bl_words, dim3((cap_max + 255u) / 256u, (unsigned)n_listed, (unsigned)n_copies), dim3(256), 0, st, A);
+        hipLaunchKernelGGL(k_bl_finish, dim3((unsigned)n_listed, (unsigned)n_copies), dim3(256), 0, st, A);
+    }
+    hipLaunchKernelGGL(k_bl_gather, dim3((unsigned)n_copies), dim3(64), 0, st, A);
+    HIPCHK(hipGetLastError());
+    if (!ctx->bl_done_ev) HIPCHK(hipEventCreateWithFlags(&ctx->bl_done_ev, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ctx->bl_done_ev, st));
     return SMC_OK;
 }
 

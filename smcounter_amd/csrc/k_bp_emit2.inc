@@ -771,6 +771,9 @@ __global__ __launch_bounds__(64) void k_bp_emit2(BpArgs A, const BpRow* __restri
                         }
                         if (!found) atomicOr(A.status, BP_ST_NOPAIR);
                     }
+                    // (bl_read of k_build_listed.inc restates the lines from here to the word for a flagged alignment - gap / site /
+                    // quality, kind, the end distances, incCond, the class, the word: an edit here is an edit there, and
+                    // tests/test_gpu_build_listed.py holds the two to the same bytes)
                     const BpRes r = bp2_resolve(A.cig + kcig, n_cig, pos, p, l_seq);
                     const bool gap = (r.isdel && r.indel == 0) || r.qpos < 0;
                     uint32_t site = 0, bq = 0;

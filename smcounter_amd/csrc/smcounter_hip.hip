@@ -38,6 +38,8 @@
 //                        cell (spike target x barcode fraction), from the covering barcodes' counters alone: no spiked copy is made.
 //   k_spike_rpb.inc      --spikeRpb: the same counts per cell (spike target x reads-per-barcode target), made per READ - thinning reads
 //                        moves a barcode's counters - from a flag byte per covering record and one read draw per record and replicate.
+//   k_build_listed.inc   --spikeScanBuild listed: the planes of a few LISTED loci of many copies of a run in one call, byte for byte the
+//                        whole builder's at those loci (the exact path of k_bp_emit2's walk per read, a one-workgroup sort per locus).
 //   k_lod.inc            the limit-of-detection table of --lod: per barcode depth the root R's uniroot finds (mt_depths_lod.R), FP64.
 //
 // Data layout (include/smcounter_hip.h): ONE uint32 per pileup read (allele, quality, fragment start, read
@@ -85,6 +87,7 @@
 #include "k_spike_rpb.inc"     // --spikeRpb: a flag byte per record and listed SNV; the achieved counts per variant, replicate and cell (target x read threshold)
 #include "k_scan_detect.inc"   // --spikeScan: one verdict per (copy, listed locus) of a called batch, the rows staying in HBM; --spikeScanFilter: its FILTER word
                                // (--spikeScanIndel: the same for allele keys, their ids resolved per copy from the builds' extras)
+#include "k_build_listed.inc"  // --spikeScanBuild listed: the listed loci of B copies of a run as a dense batch, one call (smc_build_listed)
 #include "k_lod.inc"           // --lod: the limit of detection per barcode depth (one lane per depth, Brent root search in FP64)
 #include "k_plan.inc"          // launch plan of a batch whose descriptors are in HBM (classify + fill)
 #include "host_abi.inc"        // the C ABI of include/smcounter_hip.h

@@ -639,6 +639,69 @@ def _run_depth_masks(eng, table, idents):
     return buf, n_words
 
 
+def _build_status(cnt, xcap, w16, chrom, lo, nl):
+    """What a build's two counters (extras entries, status bits) say -> True: use it; NARROW: an allele id beyond 15 or a quality beyond
+    63 with 16-bit read words - the caller builds with 32-bit words; None: the device builder does not take the run.  PileupError: a
+    base quality > 126."""
+    if int(cnt[1]) != 0 or int(cnt[0]) > xcap:
+        if w16 and (int(cnt[1]) & ~BUILD_ST_NARROW) == 0 and int(cnt[0]) <= xcap:
+            return NARROW                     # (an allele id beyond 15 or a quality beyond 63: the caller builds with 32-bit words)
+        if int(cnt[1]) & 4:
+            from .features import PileupError
+            raise PileupError("base quality > 126 at %s:%d-%d" % (chrom, lo + 1, lo + nl))
+        return None
+    return True
+
+
+def _philox_marks_over_cap(eng, L, cp, params, d_loci, lc, positions, words, w16, uaux, sampler, sampler_seed, n_bc, barcode_idents, barcode_name):
+    """(sampler "philox") smc_philox_marks over the built loci `d_loci` (their descriptors on the host: `lc`; their 1-based positions:
+    `positions`) where one is over the barcode cap -> the descriptors as the call leaves them, or `lc`."""
+    n = len(lc)
+    if not (sampler == "philox" and params.ds > 0 and bool((lc["n_umi"] > params.ds).any())):
+        return lc
+    from .engine import DevBuf
+    # the NON-parity down-sampling of the loci over the barcode cap, on the device (smc_philox_marks: Philox4x32-10 keyed by
+    # position): marks in umi_start + SMC_LF_SAMPLED in the descriptors, where the reference-exact sampling leaves its own
+    d_pos = DevBuf(eng, 8 * n + 256).upload(np.ascontiguousarray(positions, np.int64))
+    d_st = DevBuf(eng, 256).upload(np.zeros(4, np.uint32))
+    # (what identifies a barcode is a hash of its TEXT, by the run-wide id the builder left in u_gid at these loci: the sample does
+    # not depend on where the runs and batches of the file were cut)
+    idents = barcode_idents(n_bc) if barcode_idents is not None else \
+        np.array([_fnv64(barcode_name(g)) for g in range(int(n_bc))], np.uint64)
+    d_id = DevBuf(eng, 8 * max(1, len(idents)) + 256).upload(idents)
+    _lib.check(L.smc_philox_marks(eng.ctx, ctypes.byref(cp), d_loci.data_ptr(), n, d_pos.data_ptr(), words.data_ptr(),
+                                  16 if w16 else 32, uaux[0].data_ptr(), d_id.data_ptr(), uaux[1].data_ptr(),
+                                  ctypes.c_uint64(int(sampler_seed) & 0xFFFFFFFFFFFFFFFF), d_st.data_ptr(), ctypes.c_void_p(0)), "smc_philox_marks")
+    lc = d_loci.download(LOCUS_DTYPE, n)
+    d_pos.free(); d_st.free(); d_id.free()
+    return lc
+
+
+def _py2_sample_over_cap(params, lc, pos_text, uaux, barcode_name) -> None:
+    """The reference's down-sampling (smCounter.py:496-498) on the loci of `lc` over the barcode cap that no sampler has marked: barcode
+    texts by first included read, the dropped ones marked in umi_start (uaux[0]), SMC_LF_SAMPLED set in `lc`.  pos_text(l): the
+    locus's 1-based position as text (the sample's seed)."""
+    over = np.nonzero((lc["n_umi"] > params.ds) & ((lc["flags"] & LF_SAMPLED) == 0))[0] if params.ds > 0 else []
+    if len(over):
+        from .py2compat import py2_downsample_barcodes
+        for l in over.tolist():
+            o, nu = int(lc["umi_off"][l]), int(lc["n_umi"][l])
+            us = uaux[0].download(np.uint32, nu, 4 * o)
+            gid = uaux[1].download(np.uint32, nu, 4 * o)
+            finc = uaux[2].download(np.uint32, nu, 4 * o)
+            keys = np.nonzero(finc != 0xFFFFFFFF)[0]
+            keys = keys[np.argsort(finc[keys], kind="stable")]
+            if len(keys) <= params.ds:
+                continue
+            names = [barcode_name(int(gid[u])) for u in keys]
+            kept = set(py2_downsample_barcodes(pos_text(l), names, params.ds))
+            for u, name in zip(keys.tolist(), names):
+                if name not in kept:
+                    us[u] |= USTART_DROPPED
+            uaux[0].upload(us, 4 * o)
+            lc["flags"][l] |= LF_SAMPLED
+
+
 def build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, planes, uaux, slot_base, umi_base, cap, max_depth,
               allele_key, barcode_name, stream_sync=True, sampler: str = "reference", sampler_seed: int = 0, barcode_idents=None,
               uploaded=None, extras: "BuildExtras" = None):
@@ -697,29 +760,13 @@ def build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, planes, uaux, sl
     t3 = time.perf_counter()
     if T is not None:
         T["upload+launch"] += t2 - t1; T["kernel (sync)"] += t3 - t2
-    if int(cnt[1]) != 0 or int(cnt[0]) > xcap:
-        if w16 and (int(cnt[1]) & ~BUILD_ST_NARROW) == 0 and int(cnt[0]) <= xcap:
-            return NARROW                     # (an allele id beyond 15 or a quality beyond 63: the caller builds with 32-bit words)
-        if int(cnt[1]) & 4:
-            from .features import PileupError
-            raise PileupError("base quality > 126 at %s:%d-%d" % (chrom, lo + 1, lo + nl))
-        return None
+    st = _build_status(cnt, xcap, w16, chrom, lo, nl)
+    if st is not True:
+        return st
     lc = d_loci.download(LOCUS_DTYPE, nl)
-    if sampler == "philox" and params.ds > 0 and bool((lc["n_umi"] > params.ds).any()):
-        # the NON-parity down-sampling of the loci over the barcode cap, on the device (smc_philox_marks: Philox4x32-10 keyed by
-        # position): marks in umi_start + SMC_LF_SAMPLED in the descriptors, where the reference-exact sampling below leaves its own
-        d_pos = DevBuf(eng, 8 * nl + 256).upload(np.arange(lo + 1, lo + 1 + nl, dtype=np.int64))
-        d_st = DevBuf(eng, 256).upload(np.zeros(4, np.uint32))
-        # (what identifies a barcode is a hash of its TEXT, by the run-wide id the builder left in u_gid at these loci: the sample does
-        # not depend on where the runs and batches of the file were cut)
-        idents = barcode_idents(A["n_bc"]) if barcode_idents is not None else \
-            np.array([_fnv64(barcode_name(g)) for g in range(int(A["n_bc"]))], np.uint64)
-        d_id = DevBuf(eng, 8 * max(1, len(idents)) + 256).upload(idents)
-        _lib.check(L.smc_philox_marks(eng.ctx, ctypes.byref(cp), d_loci.data_ptr(), nl, d_pos.data_ptr(), planes[0].data_ptr(),
-                                      16 if w16 else 32, uaux[0].data_ptr(), d_id.data_ptr(), uaux[1].data_ptr(),
-                                      ctypes.c_uint64(int(sampler_seed) & 0xFFFFFFFFFFFFFFFF), d_st.data_ptr(), ctypes.c_void_p(0)), "smc_philox_marks")
-        lc = d_loci.download(LOCUS_DTYPE, nl)
-        d_pos.free(); d_st.free(); d_id.free()
+    if sampler == "philox":                   # (the positions are made only where the call may need them)
+        lc = _philox_marks_over_cap(eng, L, cp, params, d_loci, lc, np.arange(lo + 1, lo + 1 + nl, dtype=np.int64), planes[0], w16, uaux, sampler,
+                                    sampler_seed, A["n_bc"], barcode_idents, barcode_name)
     if own is not None:
         own.free()
     for b in (d_loci,) + ((d_cnt,) if extras is None else ()):
@@ -733,26 +780,8 @@ def build_run(A, L, eng, cp, params, chrom, lo, fasta, run_ref, planes, uaux, sl
         if nx:
             _extras_into_tables(tables, d_x.download(np.uint32, 5 * nx).reshape(nx, 5), allele_key, chrom, lo, fasta)
         d_x.free()
-    # the reference's down-sampling (smCounter.py:496-498) on loci over the barcode cap: barcode texts by first included read
-    over = np.nonzero((lc["n_umi"] > params.ds) & ((lc["flags"] & LF_SAMPLED) == 0))[0] if params.ds > 0 else []
-    if len(over):
-        from .py2compat import py2_downsample_barcodes
-        for l in over.tolist():
-            o, nu = int(lc["umi_off"][l]), int(lc["n_umi"][l])
-            us = uaux[0].download(np.uint32, nu, 4 * o)
-            gid = uaux[1].download(np.uint32, nu, 4 * o)
-            finc = uaux[2].download(np.uint32, nu, 4 * o)
-            keys = np.nonzero(finc != 0xFFFFFFFF)[0]
-            keys = keys[np.argsort(finc[keys], kind="stable")]
-            if len(keys) <= params.ds:
-                continue
-            names = [barcode_name(int(gid[u])) for u in keys]
-            kept = set(py2_downsample_barcodes(str(lo + l + 1), names, params.ds))
-            for u, name in zip(keys.tolist(), names):
-                if name not in kept:
-                    us[u] |= USTART_DROPPED
-            uaux[0].upload(us, 4 * o)
-            lc["flags"][l] |= LF_SAMPLED
+    if params.ds > 0:
+        _py2_sample_over_cap(params, lc, lambda l: str(lo + l + 1), uaux, barcode_name)
     return nl, ns, lc, tables
 
 
@@ -2386,6 +2415,164 @@ def _build_copies(eng, run: AfRun, n_copies: int, kept_runs, P, bits, flag, fast
         raise
 
 
+BUILD_ST_UNFLAGGED = 64         # SMC_LISTED_UNFLAGGED: smc_build_listed declined a copy (an alignment flagged neither READ1 nor READ2)
+LISTED_MAX_LOCI, LISTED_MAX_COPIES = 64, 1024      # SMC_LISTED_MAX_LOCI, SMC_LISTED_MAX_COPIES
+LISTED_SHARED_ORDER, LISTED_DENSE_LOCUS = 1, 2     # smc_build_listed's flags
+LISTED_XMAX = 58                                   # BL_XMAX: the alleles beyond the six fixed ones a listed locus holds
+LISTED_COPY_DTYPE = np.dtype([("aln", "<u8"), ("cig", "<u8"), ("bq", "<u8"), ("loc", "<u8"), ("n_aln", "<i4"), ("n_bc", "<i4"),
+                              ("n_pair", "<i4"), ("reserved", "<i4")])     # smc_listed_copy
+assert LISTED_COPY_DTYPE.itemsize == 48
+
+
+def listed_takes(run, n_listed: int) -> bool:
+    """Can the listed builder take `n_listed` loci of the kept run `run` at all?  Not a run with an alignment flagged neither READ1 nor
+    READ2 (every copy of it would be declined), and no more loci than one call lists."""
+    return 1 <= n_listed <= LISTED_MAX_LOCI and not (int(run.A["status"]) & 1)
+
+
+def listed_layout(loc_host, offsets, n_copies: int) -> dict:
+    """Where smc_build_listed puts the dense batch of n_copies x len(offsets) loci: the slot capacity of listed locus g is align4 of
+    loc_host[offsets[g]].n - the depth in the unselected, unspiked run: spiking changes no span, a selection only drops records.
+    -> dict(caps: uint32 [G], stride: the slots of a copy, n_slots, n_ustart: the batch's, slot(c, g) / ustart(c, g): first slot /
+    first umi_start entry of locus g of copy c behind the batch's bases, index(c, g): its place among the batch's loci and rows)."""
+    offsets = [int(a) for a in offsets]
+    if any(b <= a for a, b in zip(offsets, offsets[1:])) or (offsets and (offsets[0] < 0 or offsets[-1] >= len(loc_host))):
+        raise ValueError("listed_layout: the offsets %r do not ascend within the run's %d loci" % (offsets, len(loc_host)))
+    caps = np.array([(int(loc_host["n"][a]) + 3) & ~3 for a in offsets], np.uint32)
+    capoff = [0] + [int(x) for x in np.cumsum(caps.astype(np.int64))]
+    S, G = capoff[-1], len(offsets)
+    return dict(caps=caps, stride=S, n_slots=n_copies * S, n_ustart=n_copies * (S + G) + 1,
+                slot=lambda c, g: c * S + capoff[g], ustart=lambda c, g: c * (S + G) + capoff[g] + g, index=lambda c, g: c * G + g)
+
+
+def _build_listed(eng, run: "AfRun", kept_list, at, P, bits, sampler, sampler_seed, shared: bool, dense: bool = False):
+    """smc_build_listed: the loci at run offsets `at` (ascending) of every _KeptRun of `kept_list` - spiked copies of the kept run `run`
+    (`shared`: one barcode-major order serves them all) or selections of them - as ONE dense _DsBatch of copies x listed loci, locus g
+    of copy c at c x len(at) + g, with the cell's params `P`: one call, ONE download of the copies' counters, one of the descriptors
+    and - where a copy has extras entries - one of all the copies' extras stretches.  The copies stay the caller's (nothing is freed
+    here).  `dense` (--spikeScanIndel): the device entries' locus field holds g (SMC_LISTED_DENSE_LOCUS), and the extras stretches and
+    their counts stay in HBM for smc_scan_detect_keys - the answer's third member, which the caller frees.
+    -> (the batch - the caller frees it -, per copy its extras entries [n, 5] with the RUN offset in the locus field, None or
+    dict(x, cnt: the DevBufs, xcap)), NARROW (no room in 16-bit read words), or None: the listed builder declines (an alignment flagged
+    neither READ1 nor READ2, a depth beyond the unselected run's, more alleles than it holds) - the caller builds the whole way."""
+    from .engine import DevBuf
+    lo, nl, B, G = run.lo, run.nl, len(kept_list), len(at)
+    if not listed_takes(run, G) or not 1 <= B <= LISTED_MAX_COPIES or any(k.counts["status"] != 0 for k in kept_list):
+        return None
+    lay = listed_layout(run.up.loc_host, at, B)
+    cap = lay["n_ustart"] + 64
+    xcap = LISTED_XMAX * G                     # (every allele beyond the six fixed ones of every listed locus: the list cannot overflow)
+    desc = np.zeros(B, LISTED_COPY_DTYPE)
+    for c, k in enumerate(kept_list):
+        r = k.run
+        desc[c] = (r.aln.data_ptr(), r.cig.data_ptr(), r.bq.data_ptr(), r.loc.data_ptr(), r.n_aln, int(k.counts["n_bc"]), int(k.counts["n_pair"]), 0)
+    offs = np.array(list(at) + [0], np.uint32)
+    cp = abi.c_params(P)
+    d = _DsBatch(eng, cap, bits, False)
+    bufs = [DevBuf(eng, desc.nbytes + 256).upload(desc), DevBuf(eng, LOCUS_DTYPE.itemsize * B * G + 256), DevBuf(eng, 20 * xcap * B + 256),
+            DevBuf(eng, 8 * B + 256)]
+    d_desc, d_loci, d_x, d_cnt = bufs
+    keep = None
+    try:
+        _lib.check(eng.L.smc_build_listed(eng.ctx, ctypes.byref(cp), d_desc.data_ptr(), B, (LISTED_SHARED_ORDER if shared else 0) | (LISTED_DENSE_LOCUS if dense else 0),
+                                          lo, nl, run.up.ref.data_ptr(), offs.ctypes.data, lay["caps"].ctypes.data, G, bits, 0, 0, d.words.data_ptr(),
+                                          d.uaux[0].data_ptr(), d.uaux[1].data_ptr(), d.uaux[2].data_ptr(), d_loci.data_ptr(), d_x.data_ptr(), xcap,
+                                          d_cnt.data_ptr(), ctypes.c_void_p(0)), "smc_build_listed")
+        cnt = d_cnt.download(np.uint32, 2 * B).reshape(B, 2)
+        verdict = True
+        for c in range(B):
+            st = _build_status(cnt[c], xcap, bits == 16, run.chrom, lo, nl)
+            if st is None:
+                verdict = None
+                break
+            if st == NARROW:
+                verdict = NARROW
+        if verdict is not True:
+            d.free()
+            return verdict
+        lc = d_loci.download(LOCUS_DTYPE, B * G)
+        pos = np.array([lo + 1 + a for a in at], np.int64)
+        if any(k.by_read for k in kept_list):       # (renumbered barcodes: a copy's identities are its own)
+            for c, k in enumerate(kept_list):
+                lc[c * G:(c + 1) * G] = _philox_marks_over_cap(eng, eng.L, cp, P, _BufView(d_loci, LOCUS_DTYPE.itemsize * G * c), lc[c * G:(c + 1) * G], pos,
+                                                               d.words, bits == 16, d.uaux, sampler, sampler_seed, k.counts["n_bc"], k.barcode_idents,
+                                                               k.barcode_name)
+        else:                                       # (the run's ids in every copy: one call over the B x G loci)
+            k = kept_list[0]
+            lc = _philox_marks_over_cap(eng, eng.L, cp, P, d_loci, lc, np.tile(pos, B), d.words, bits == 16, d.uaux, sampler, sampler_seed,
+                                        run.A["n_bc"], k.barcode_idents, k.barcode_name)
+        for c, k in enumerate(kept_list):
+            _py2_sample_over_cap(P, lc[c * G:(c + 1) * G], lambda g: str(lo + int(at[g]) + 1), d.uaux, k.barcode_name)
+        xl = [np.zeros((0, 5), np.uint32)] * B
+        if cnt[:, 0].any():
+            # (all B stretches in one copy, 1160 x G bytes each: the scan's batches hold at most SPIKE_MAX_COPIES = 64 copies, so 74 KB x G
+            # - 148 KB at the two loci a default pass lists, 4.75 MB at the 64 a call takes; the entry's own limit of 1024 copies would
+            # make it 76 MB, and a caller with such batches should bring the stretches down by the largest count instead)
+            allx = d_x.download(np.uint32, 5 * xcap * B).reshape(B, xcap, 5)
+            xl = [allx[c, :int(cnt[c, 0])].copy() for c in range(B)]
+            if dense:
+                for x in xl:
+                    x[:, 0] = np.asarray(at, np.uint32)[x[:, 0]]
+        d.LC, d.slots, d.tables = [lc], lay["n_slots"], None
+        if dense:
+            keep = dict(x=d_x, cnt=d_cnt, xcap=xcap)
+        return d, xl, keep
+    except BaseException:
+        d.free()
+        raise
+    finally:
+        for b in bufs:
+            if keep is None or (b is not d_x and b is not d_cnt):
+                b.free()
+
+
+def _check_listed_rows(eng, run: "AfRun", held, c0: int, d_rows, listed, P, bits, flag, fasta, max_depth, sampler, sampler_seed, variants, what):
+    """(--spikeScanBuild listed) The self-check of a listed batch whose called rows are `d_rows`: copy c0 - replicate 0 - is also built
+    the whole way (_build_copies on that one _KeptRun, which frees it: its place in `held` is taken by a stand-in that keeps its
+    allele_key; 32-bit read words and no table, whatever the batch has) and called with a plan of its own; the smc_row bytes of every
+    listed locus must be the listed build's.  RuntimeError naming the locus otherwise."""
+    from .engine import DevBuf
+    G, nl, size = len(listed), run.nl, abi.ROW_DTYPE.itemsize
+    k0 = held[c0]
+    if k0.d_orig is not None:
+        k0.orig_index()                         # (its allele_key outlives the selection's arrays)
+    held[c0] = _FreedKept(k0.allele_key)
+    # (32-bit read words whatever the batch's: an unlisted locus of the run may have no room in 16-bit ones, and a row does not depend on
+    # the width - nothing to retry, and the run's word width stays the main pass's business)
+    # (no table is made of this build - rows are compared, not printed: its extras list stays in a region of its own)
+    xcap = build_xcap(nl)
+    xb = [DevBuf(eng, 20 * xcap + 256), DevBuf(eng, 256)]
+    plan = rows = w = None
+    try:
+        w = _build_copies(eng, run, 1, iter([k0]), P, 32, flag, fasta, max_depth, sampler, sampler_seed, extras=[BuildExtras(xb[0], xb[1])])
+        plan = eng.make_plan(w.loci())
+        rows = plan.run_into_devbuf([w.words, w.uaux[0]], P)
+        for g in range(G):
+            a = int(listed["offset"][g])
+            mine = d_rows.download(abi.ROW_DTYPE, 1, (c0 * G + g) * size)
+            theirs = rows.download(abi.ROW_DTYPE, 1, a * size)
+            if mine.tobytes() != theirs.tobytes():
+                raise RuntimeError("--spikeScanBuild listed: replicate 0 at %s:%d%s: the row of the listed build is not the whole build's "
+                                   "(fields %s)" % (run.chrom, run.lo + 1 + a, what,
+                                                    ", ".join(f for f in abi.ROW_DTYPE.names if mine[f].tobytes() != theirs[f].tobytes())))
+    finally:
+        if plan is not None:
+            plan.close()
+        for b in [rows, w] + xb:
+            if b is not None:
+                b.free()
+
+
+class _FreedKept(object):
+    """What stands in `held` for a _KeptRun the self-check's whole build has freed: its allele_key, and nothing left to free."""
+
+    def __init__(self, allele_key):
+        self.allele_key = allele_key
+
+    def free(self):
+        pass
+
+
 def _listed_rows(d: _DsBatch, out_rows, run: AfRun, at, n_copies: int, P, fasta):
     """The raw row strings of the loci at offsets `at` of the run in every one of the `n_copies` builds of batch `d`, whose called rows
     `out_rows` are -> per copy the listed loci's text, in the order of `at`."""
@@ -2981,19 +3168,20 @@ class _SpikedCopies(object):
             b.free()
 
 
-def _copy_room(run: AfRun, svar, four: bool, n_selections: int = 0, by_read: bool = False):
+def _copy_room(run: AfRun, svar, four: bool, n_selections: int = 0, by_read: bool = False, listed_slots: int = 0):
     """How many spiked copies of the kept run one rewrite call makes: as many as fit SPIKE_REP_BATCH_BYTES - a copy is its records and
     pair pool or, with `four` counters, records, both pools at their capacities and the call's scratch of 8 bytes per alignment -,
     AF_REP_BATCH_SLOTS read slots and SMC_SPIKE_MAX_COPIES, and at least one -> (copies, spike_indel_caps of `svar` on the run or None).
     `n_selections` (--spikeScanDepth: the fractions): a copy also has that many selections alive beside it (select_copies: records,
     orig_index and descriptors at their capacities), and copies x selections stays within SEL_MAX_SELECTIONS.  `by_read`
     (--spikeScanRpb: the selections are select_copies_reads', one per reads-per-barcode target): each also has the renumbering's
-    scratch, 8 bytes per barcode id and read-name id."""
+    scratch, 8 bytes per barcode id and read-name id.  `listed_slots` (--spikeScanBuild listed: the slots and umi_start entries of a
+    copy's listed loci, listed_layout's stride + G): a copy takes those read slots of the batch, not the whole run's."""
     n, caps = run.up.n_aln, spike_indel_caps(run.A, svar) if four else None
     per_copy = sum(spike_indel_copy_strides(n, *caps)) + 8 * n if four else sum(spike_copy_strides(n, len(run.A["bq"]) // 2))
     per_copy += n_selections * (40 * max(1, n) + 16 * max(1, run.nl) + 16 +
                                 (8 * (int(run.A["n_bc"]) + int(run.A["n_pair"])) if by_read else 0))
-    return max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per_copy, AF_REP_BATCH_SLOTS // max(1, int(run.A["n_slots"]) + run.nl),
+    return max(1, min(SPIKE_MAX_COPIES, SPIKE_REP_BATCH_BYTES // per_copy, AF_REP_BATCH_SLOTS // max(1, listed_slots or int(run.A["n_slots"]) + run.nl),
                       SEL_MAX_SELECTIONS // max(1, n_selections))), caps
 
 
@@ -3341,7 +3529,7 @@ def scan_called_host(text, v, threshold: int, repeats) -> bool:
 
 
 def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed,
-               bits, threshold, repeats, check0, indel: dict = None, depth: dict = None, rpb: dict = None, flt: dict = None):
+               bits, threshold, repeats, check0, indel: dict = None, depth: dict = None, rpb: dict = None, flt: dict = None, build: dict = None):
     """The _SpikedCopies of the run at one target, one per seed of `part_seeds`, each built behind the other into one device batch and
     the batch called with one plan - _spike_rep_call's way - but the rows stay in HBM: smc_scan_detect gives a verdict per (copy,
     listed locus), and only the rows it leaves to the host come down, one by one, to be printed and cut the existing way.  run.group:
@@ -3369,7 +3557,13 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
     that come down, and so gets its FILTER from the printed row, as a HOST verdict the host calls does; replicate 0's CALLED rows come
     down anyway, and the names of the printed row must be the device word's.  flt["out"] is filled: per batch decided - full depth,
     then the cells in order - (uint32 [copies, listed]: the 14 name bits, meaningful where called, the records whose FILTER the host
-    decided)."""
+    decided).
+    `build` (--spikeScanBuild listed: a dict whose "listed", "whole" and "checks" are counted up): every batch is ONE _build_listed call
+    - a dense batch of copies x listed loci, row c x G + g, every table from the copy's extras entries - in place of a whole build per
+    copy (with `indel` the entry writes g into its extras entries' locus field, the stretches stay in HBM and smc_scan_detect_keys gets
+    n_loci = G and variant records whose locus is g); a batch the listed builder declines is built the whole way and counted under
+    "whole"; the listed
+    rows of replicate 0 are also made by a whole build of that one copy, and a row that differs in a byte ends the run."""
     from . import dsaf, spike as _spike, vc
     from .engine import DevBuf
     A, lo, nl, chrom = run.A, run.lo, run.nl, run.chrom
@@ -3378,18 +3572,58 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
     copies = _SpikedCopies(eng, run, svar, part_seeds, thr, P, *((indel["ins"], indel.get("caps")) if indel is not None else ()))
     runs, extras, xbufs, sels = copies.runs, None, [], None
 
-    def decide(kept_runs, Pb, cut, where, key_of, what):
+    def decide(kept_runs, Pb, cut, where, key_of, what, shared=False):
         """`kept_runs` built into one batch and called with one plan at params `Pb`; the verdicts at the cut `cut` -> (called, the
-        verdicts the host decided), or NARROW.  where: scan_detect_keys' `copies` of these builds; key_of(c): allele_key of build c."""
+        verdicts the host decided), or NARROW.  where: scan_detect_keys' `copies` of these builds; key_of(c): allele_key of build c;
+        shared: the builds are spiked copies of one run (one barcode-major order serves a listed build of them)."""
         d = d_rows = plan = None
+        held, xl, n_rows, spots = [], None, nl, listed          # held: the _KeptRuns a listed build leaves to this call to free
+        xkeep = None                                            # (a listed build of `indel`: its extras stretches and counts, in HBM)
         try:
-            built = _build_copies(eng, run, B, kept_runs, Pb, bits, flag, fasta, max_depth, sampler, sampler_seed, extras)
-            if built == NARROW:
-                return NARROW
-            d = built
+            if build is not None:
+                held = list(kept_runs)
+                got = _build_listed(eng, run, held, [int(a) for a in listed["offset"]], Pb, bits, sampler, sampler_seed, shared, dense=indel is not None)
+                if got == NARROW:
+                    return NARROW
+                if got is None:
+                    kept_runs, held = iter(held), []            # (declined: the whole way, which frees each behind its build)
+                else:
+                    d, xl, xkeep = got
+                    build["listed"] += B
+                    n_rows, spots = G, listed.copy()
+                    spots["offset"] = np.arange(G)
+            if d is None:
+                built = _build_copies(eng, run, B, kept_runs, Pb, bits, flag, fasta, max_depth, sampler, sampler_seed, extras)
+                if built == NARROW:
+                    return NARROW
+                d = built
+                if build is not None:
+                    build["whole"] += B
             plan = eng.make_plan(d.loci())
             d_rows = plan.run_into_devbuf([d.words, d.uaux[0]], Pb)
-            if indel is None:
+            row_at = (lambda i, a: i) if xl is not None else (lambda i, a: (i // G) * nl + a)
+            if xl is not None:
+                keys_of = {}
+                if check0 is not None:
+                    if indel is not None:
+                        keys_of[check0] = key_of(check0)         # (a selection's key asks for its orig_index: before the check frees it)
+                    _check_listed_rows(eng, run, held, check0, d_rows, listed, Pb, bits, flag, fasta, max_depth, sampler, sampler_seed, variants, what)
+                    build["checks"] += G
+
+                def table_of(c, a):
+                    if c not in keys_of:                        # (with `indel` a relocated record's texts come from the copy: key_of)
+                        keys_of[c] = held[c].allele_key if indel is None else key_of(c)
+                    return extras_table(xl[c], a, keys_of[c], chrom, lo, fasta)
+                if indel is None:
+                    rec, todo = scan_detect(eng, d_rows, B, G, spots, cut)
+                else:
+                    # (a copy has G rows: the variant records name the dense locus, as the entries of the listed build do)
+                    var = np.array(indel["var"], abi.AF_VARIANT_DTYPE)
+                    var["locus"] = np.arange(G)
+                    rec, todo, _ = scan_detect_keys(
+                        eng, d_rows, B, G, var, indel["var_ins"], where,
+                        dict(x=xkeep["x"].data_ptr(), cnt=xkeep["cnt"].data_ptr(), x_stride=5 * xkeep["xcap"], cnt_stride=2, xcap=xkeep["xcap"]), cut)
+            elif indel is None:
                 rec, todo = scan_detect(eng, d_rows, B, nl, listed, cut)         # (its downloads wait for the plan's kernels)
                 table_of = lambda c, a: d.tables[c * nl + a]
             else:
@@ -3408,7 +3642,7 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
             called = verdict == abi.SCAN_CALLED
             words, fhost, n_fhost = None, set(), 0
             if flt is not None:
-                words = scan_filter(eng, d_rows, B, nl, listed["offset"], flt["gate"], flt["always"])
+                words = scan_filter(eng, d_rows, B, n_rows, spots["offset"], flt["gate"], flt["always"])
                 fhost = set(int(x) for x in np.flatnonzero((called & ((words & abi.SCAN_FLT_HOST) != 0)).reshape(-1)))
             theirs = set(int(x) for x in todo)
             if theirs != set(int(x) for x in np.flatnonzero(verdict.reshape(-1) == abi.SCAN_HOST)):
@@ -3419,7 +3653,7 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
                 at = [int(listed["offset"][i % G]) for i in mine]
                 got = np.empty(len(mine), abi.ROW_DTYPE)
                 for n, (i, a) in enumerate(zip(mine, at)):
-                    d_rows.download(abi.ROW_DTYPE, 1, ((i // G) * nl + a) * abi.ROW_DTYPE.itemsize, out=got[n:n + 1])
+                    d_rows.download(abi.ROW_DTYPE, 1, row_at(i, a) * abi.ROW_DTYPE.itemsize, out=got[n:n + 1])
                 view = vc.LocusView([chrom] * len(mine), [lo + 1 + a for a in at], [run.run_ref[a] if a < len(run.run_ref) else "" for a in at],
                                     [table_of(i // G, a) for i, a in zip(mine, at)])
                 text = vc._strings(got, view, Pb, fasta)
@@ -3454,9 +3688,11 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
         finally:
             if plan is not None:
                 plan.close()
-            for b in (d_rows, d):
+            for b in (d_rows, d) + ((xkeep["x"], xkeep["cnt"]) if xkeep is not None else ()):
                 if b is not None:
                     b.free()
+            for k in held:
+                k.free()
     if flt is not None:
         flt["out"] = []                         # (a narrower retry starts over)
     try:
@@ -3473,7 +3709,7 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
         # relocated has its texts in the copy - no table is made of those builds here)
         kept = (_KeptRun(runs[c], A, None, A, run.bam.allele_key, run.bam.barcode_name, lambda n: run.idents) for c in range(B))
         full = decide(kept, P, threshold, copies.addresses() if indel is not None else None,
-                      lambda c: copy_allele_key(runs[c], A, run.bam.allele_key), "")
+                      lambda c: copy_allele_key(runs[c], A, run.bam.allele_key), "", shared=True)
         cells = depth or rpb
         if full == NARROW or cells is None:
             return full
@@ -3512,7 +3748,7 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
 
 def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n_reps: int, eng, threshold: int, repeats,
                sampler: str = "reference", sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, indel: bool = False,
-               depth: dict = None, rpb: dict = None, flt: bool = False):
+               depth: dict = None, rpb: dict = None, flt: bool = False, build: str = "whole"):
     """The stage of --spikeScan.  variants: the scan's SNV at every scanned locus (tools.spike_scan_lists.scan_variants); passes: [(k,
     the indices of pass k)] (scan_passes).  A pass is the run --spikeAF <targets> --spikeVariants <its list> --spikeReps n_reps --dsSeed
     seed: replicate j has seed (seed + j) mod 2^64, and the draws, the rewrite, NM and the thresholds are that run's.
@@ -3547,6 +3783,9 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     and behind every detect call smc_scan_filter decides the FILTER column per (copy, listed locus) on the same rows (_scan_call's
     `flt`).  The result gets filter: uint32 [V, T, R] - the 14 name bits of abi.SCAN_FILTER_NAMES where `called` -, with an axis
     depth_filter / rpb_filter: uint32 [V, T, F, R], and filter_host: the called records whose FILTER the host decided.
+    `build` "listed" (--spikeScanBuild): every batch of copies is one smc_build_listed call over the pass's loci of the run
+    (_scan_call's `build`), a batch holds as many copies as their listed slots allow (_copy_room), and the passes' dicts get "listed"
+    and "whole" - the builds made either way - and "checks": the replicate-0 rows compared with a whole build's.
     -> dict(seeds, base: per variant (N, V0), counts: uint32 [V, R, T, 3] = (S, READS, V1), called: bool [V, T, R], passes: per pass
     of `passes` dict(variants, copies, builds, host, seconds), times: dict(stage, runs, decode))."""
     import time
@@ -3569,6 +3808,11 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     spikes = [SpikeSet([variants[i] for i in members], indels=indel) for _, members in passes]
     base, counts, called = [None] * V, np.zeros((V, R, T, 3), np.uint32), np.zeros((V, T, R), bool)
     stats = [dict(variants=0, copies=0, builds=0, host=0, seconds=0.0) for _ in passes]
+    if build not in ("whole", "listed"):
+        raise ValueError("--spikeScanBuild: whole or listed expected, got %r" % (build,))
+    listed_build = build == "listed"
+    for st in stats if listed_build else ():
+        st.update(listed=0, whole=0, checks=0)
     if depth is not None and rpb is not None:
         raise ValueError("--spikeScanRpb: the grid of barcode fractions x reads-per-barcode targets is not built")
     if depth is not None:
@@ -3611,10 +3855,13 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
                 for p in in_run:
                     t0 = time.perf_counter()
                     run.group = [k for k in inside if pass_at[k] == p]
+                    slots = 0
+                    if listed_build and listed_takes(run, len(run.group)):     # (else every batch is whole builds: whole-run slots)
+                        slots = listed_layout(run.up.loc_host, [variants[k].pos - 1 - lo for k in run.group], 1)["n_ustart"]
                     room, caps = _copy_room(run, spikes[p].chrom_variants(chrom, 0.5)[0] if indel else None, indel,
-                                            len((depth or rpb)["params"]) if (depth or rpb) is not None else 0, rpb is not None)
+                                            len((depth or rpb)["params"]) if (depth or rpb) is not None else 0, rpb is not None, slots)
                     _scan_pass(eng, run, spikes[p], [int(local[k]) for k in run.group], variants, seeds, thr, P, fasta, max_depth, sampler,
-                               sampler_seed, threshold, repeats, room, base, counts, called, stats[p], caps, depth, rpb, flt)
+                               sampler_seed, threshold, repeats, room, base, counts, called, stats[p], caps, depth, rpb, flt, listed_build)
                     stats[p]["variants"] += len(run.group)
                     stats[p]["seconds"] += time.perf_counter() - t0
             finally:
@@ -3669,7 +3916,7 @@ def _scan_read_masks(eng, run: AfRun, read_rules, seeds) -> dict:
 
 
 def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr, P, fasta, max_depth, sampler, sampler_seed, threshold,
-               repeats, room, base, counts, called, stat, caps=None, depth: dict = None, rpb: dict = None, flt: dict = None):
+               repeats, room, base, counts, called, stat, caps=None, depth: dict = None, rpb: dict = None, flt: dict = None, listed_build: bool = False):
     """spike_scan's work for one pass in one run: run.group are the pass's variants there (indices into `variants`), members[g] the
     place of run.group[g] in the pass's list (`spikes`).  base, counts, called and stat are filled.  `caps` (--spikeScanIndel:
     spike_indel_caps of the pass's list on the run): the indel branch.  `depth` (--spikeScanDepth: spike_scan's dict with "counts" and
@@ -3678,7 +3925,8 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
     "called" and the run's "p_idents", "first", "masks", "n_words"): the same on the read axis - smc_spike_read_bits
     (smc_spike_indel_read_bits) on the pass's variants, spike_rpb_records per variant and ONE spike_rpb_counts call for the cells'
     counters; a batch's mask base is that of its first seed.  `flt` (--spikeScanFilter: spike_scan's dict with "gate", "always",
-    "words", "cell_words" and "host"): per batch the FILTER words of the copies (_scan_call's `flt`); the last three are filled."""
+    "words", "cell_words" and "host"): per batch the FILTER words of the copies (_scan_call's `flt`); the last three are filled.
+    `listed_build` (--spikeScanBuild listed): _scan_call's `build` is `stat`, whose "listed", "whole" and "checks" count up."""
     A, up, lo, chrom = run.A, run.up, run.lo, run.chrom
     idents, (nm, n_indel) = run.idents, run.mism
     group = run.group
@@ -3729,7 +3977,15 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
                                         want=want, masks=rpb["masks"].data_ptr() + 4 * rpb["n_words"] * F * js[0], n_words=rpb["n_words"],
                                         copy_stride=rpb["n_words"] * F),)
             fl = dict(gate=flt["gate"][group], always=flt["always"][group]) if flt is not None else None
-            got = _narrow_retry(eng, P, lambda bits: _scan_call(*args, bits, *tail, flt=fl))
+            if listed_build:
+                before = {k: stat[k] for k in ("listed", "whole", "checks")}
+
+                def call(bits):
+                    stat.update(before)         # (a narrower retry starts over)
+                    return _scan_call(*args, bits, *tail, flt=fl, build=stat)
+            else:
+                call = lambda bits: _scan_call(*args, bits, *tail, flt=fl)
+            got = _narrow_retry(eng, P, call)
             yes, n_host, builds = (got[0], got[2], got[3]) if axis is not None else (got[0], got[1], 1)
             for c, j in enumerate(js):
                 for g, k in enumerate(group):

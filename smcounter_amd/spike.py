@@ -52,6 +52,8 @@ the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the 
 """
 from __future__ import annotations
 
+import re
+
 from . import abi as _abi
 from . import dsaf
 from .tools import ds_allele_fraction as af
@@ -676,6 +678,7 @@ SCAN_FLAGS = ("spikeScan", "spikeScanReps", "spikeScanStride", "spikeScanAlt")
 SCAN_NOT_WITH = ("spikeAF", "spikeVariants", "spikeMtDepth", "spikeReps", "spikePhase", "spikeIndels", "spikeIndelReps", "spikeIndelDepth",
                  "spikeIndelPhase", "spikeDepth", "spikeRpb", "spikeIndelRpb", "spikePhaseRpb")
 SCAN_NOT_WITH_DS = DS_FLAGS + ("dsMtDepth", "dsRpbMtDepth", "dsAFVariants", "dsAFMtDepth")
+SCAN_BUILDS = ("whole", "listed")      # --spikeScanBuild: every copy a whole build of its run (the default), or smc_build_listed
 SCAN_SENSITIVITY_HEADER = tuple(c for c in SENSITIVITY_HEADER if c not in ("PI_MEAN", "PI_MIN"))
 
 
@@ -703,20 +706,25 @@ def scan(args):
     --spikeScanRpb adds "rpbs": the reads-per-barcode targets of the scan's read axis.  SystemExit: the flag without --spikeScan or
     beside --spikeScanDepth (the t x f x r grid is not built), text that is no list of numbers, a target <= 0 or listed twice, more
     than MAX_CELLS targets x reads-per-barcode targets.
-    --spikeScanFilter (a switch) adds "filter": True.  SystemExit: the switch without --spikeScan."""
+    --spikeScanFilter (a switch) adds "filter": True.  SystemExit: the switch without --spikeScan.
+    --spikeScanBuild listed adds "build": "listed" (`whole`, the default, adds nothing: scan_build reads it).  SystemExit: the flag
+    without --spikeScan, a value that is neither whole nor listed."""
     from .tools import spike_scan_lists as lists
     text, r, stride, alt = (getattr(args, f, None) for f in SCAN_FLAGS)
     indel = getattr(args, "spikeScanIndel", None)
     fracs = getattr(args, "spikeScanDepth", None)
     rpbs = getattr(args, "spikeScanRpb", None)
     flt = getattr(args, "spikeScanFilter", None)
+    build = getattr(args, "spikeScanBuild", None)
     given = lambda x: x not in (None, "", False)
     if not given(text):
-        for flag, value in zip(SCAN_FLAGS[1:] + ("spikeScanIndel", "spikeScanDepth", "spikeScanRpb", "spikeScanFilter"),
-                               (r, stride, alt, indel, fracs, rpbs, flt)):
+        for flag, value in zip(SCAN_FLAGS[1:] + ("spikeScanIndel", "spikeScanDepth", "spikeScanRpb", "spikeScanFilter", "spikeScanBuild"),
+                               (r, stride, alt, indel, fracs, rpbs, flt, build)):
             if given(value):
                 raise SystemExit("--%s belongs to --spikeScan: it needs --spikeScan" % flag)
         return None
+    if given(build) and str(build) not in SCAN_BUILDS:
+        raise SystemExit("--spikeScanBuild: %s expected, got %r" % (" or ".join(SCAN_BUILDS), build))
     if given(indel) and given(alt):
         raise SystemExit("--spikeScanIndel cannot be combined with --spikeScanAlt: the scan plants an insertion or a deletion OR an SNV at "
                          "every locus, not both")
@@ -770,7 +778,29 @@ def scan(args):
         out["rpbs"] = _rpb_cells(rpbs, [(t, 0, "") for t in ts], "spikeScanRpb")[0]
     if given(flt):
         out["filter"] = True
+    if given(build) and str(build) != SCAN_BUILDS[0]:
+        out["build"] = str(build)
     return out
+
+
+SCAN_PASS_LINE = re.compile(r"^--spikeScan pass (\d+): (\d+) variants, (\d+) copies, (\d+) builds, (?:(\d+) of them whole, )?(\d+) verdicts decided "
+                            r"by the host, ([0-9.]+) s$")
+
+
+def scan_pass_line(line: str):
+    """A pass line of the run log -> dict(k, variants, copies, builds, whole, host, seconds), or None for any other line; `whole` - the
+    builds made by the whole-run builder - is None where the line has no such field (--spikeScanBuild whole)."""
+    m = SCAN_PASS_LINE.match(line.rstrip("\n"))
+    if m is None:
+        return None
+    k, variants, copies, builds, whole, host, seconds = m.groups()
+    return dict(k=int(k), variants=int(variants), copies=int(copies), builds=int(builds), whole=None if whole is None else int(whole),
+                host=int(host), seconds=float(seconds))
+
+
+def scan_build(plan) -> str:
+    """How the scan `plan` (scan()'s dict) builds its spiked copies: SCAN_BUILDS[0] unless --spikeScanBuild said otherwise."""
+    return plan.get("build", SCAN_BUILDS[0])
 
 
 def scan_entry(v, r, called: bool):

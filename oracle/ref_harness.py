@@ -12,7 +12,8 @@ here.  This harness
         str    -> 12-significant-digit float printing,
         sorted -> stable sort preceded by py2 dict key order (ties in PI, smCounter.py:534),
   4. wraps scipy.stats.fisher_exact and round to capture the Fisher p-values and the unrounded
-     prediction indices of every call.
+     prediction indices of every call,
+  5. reads vc()'s per-allele tallies out of its frame when it returns (capture_pileup).
 Nothing from the reference is copied into the repo: this file reads it by path at run time and
 only the generated input/output vectors (tests/golden/) are committed.
 """
@@ -50,6 +51,7 @@ class _Capture(object):
                              # carry that value.
         self.final_items = []  # finalDict.items() as handed to sorted() at :534, in the emulated py2 dict's order; never emptied
         self.sampled = False # random.sample ran (smCounter.py:497-498)
+        self.pileup = None   # vc()'s own per-allele tallies when it returned (capture_pileup below), as plain dicts and lists
 
 
 CAP = _Capture()
@@ -131,6 +133,38 @@ def load_reference():
     return mod
 
 
+# what vc() has tallied per allele key when its pileup loop is over (smCounter.py:280-300, :316-479)
+PILEUP_COUNTS = ("alleleCnt", "r1Cnt", "r2Cnt", "forwardCnt", "reverseCnt", "lowQReads", "bqSum")
+PILEUP_LISTS = ("r1BcEndPos", "r2BcEndPos", "r2PrimerEndPos")
+
+
+@contextlib.contextmanager
+def capture_pileup(mod):
+    """While the block runs, a profile hook watches for the `return` event of the reference's vc() frame - a plain return or an
+    exception on its way out - and copies the tallies its locals hold then into CAP.pileup: the PILEUP_COUNTS and PILEUP_LISTS
+    dictionaries per allele key, allBcDict (barcode -> read ids) and cvg.  The hook reads the frame at run time; it is installed
+    only around the call and the previous one is put back whatever happens."""
+    code = mod.vc.__code__
+
+    def hook(frame, event, arg):
+        if event == "return" and frame.f_code is code:
+            loc = frame.f_locals
+            if "lowQReads" not in loc:             # (left before the tallies existed)
+                return
+            out = {name: {builtins.str(k): int(v) for k, v in loc[name].items()} for name in PILEUP_COUNTS}
+            out.update({name: {builtins.str(k): [int(x) for x in v] for k, v in loc[name].items()} for name in PILEUP_LISTS})
+            out["allBcDict"] = {builtins.str(k): [builtins.str(x) for x in v] for k, v in loc["allBcDict"].items()}
+            out["cvg"] = int(loc["cvg"])
+            CAP.pileup = out
+
+    prev = sys.getprofile()
+    sys.setprofile(hook)
+    try:
+        yield
+    finally:
+        sys.setprofile(prev)
+
+
 def locus_to_stub_reads(pb, l):
     """PileupBatch locus -> the dicts stub_pysam serves as pileup reads."""
     s = pb.locus_slice(l)
@@ -194,7 +228,8 @@ def run_reference(pb, params, chroms, use_wrapper=True):
 
     Returns a list of dicts: row (the TAB-joined string vc() returns), pi_raw (unrounded
     PI_A, PI_T, PI_G, PI_C, PI_alt; empty for zero-coverage rows), fisher (captured calls), final (the (key, PI) items of
-    finalDict in the order the emulated py2 dict hands them to sorted() at :534 - what a PI tie falls back on).
+    finalDict in the order the emulated py2 dict hands them to sorted() at :534 - what a PI tie falls back on), pileup (CAP.pileup:
+    vc()'s per-allele tallies, capture_pileup above).
     """
     global _MOD
     if _MOD is None:
@@ -210,14 +245,14 @@ def run_reference(pb, params, chroms, use_wrapper=True):
     fn = mod.vc_wrapper if use_wrapper else mod.vc
     for l in range(pb.n_loci):
         CAP.reset()
-        with contextlib.redirect_stdout(io.StringIO()):
+        with contextlib.redirect_stdout(io.StringIO()), capture_pileup(mod):
             row = fn(bam, pb.chrom[l], builtins.str(int(pb.pos[l])), params.minBQ, params.minMQ,
                      params.mtDepth, params.rpb, params.hpLen, params.mismatchThr, params.mtDrop,
                      params.maxMT, params.primerDist, fa)
         res.append(dict(row=row, pi_raw=list(CAP.round2), fisher=list(CAP.fisher),
                         n_umi_used=len(CAP.calprob), tie_ambiguous=_tie_ambiguous(CAP.final),
                         final=[[k, v] for k, v in CAP.final_items],
-                        sampled=bool(CAP.sampled)))
+                        sampled=bool(CAP.sampled), pileup=CAP.pileup))
     return res
 
 

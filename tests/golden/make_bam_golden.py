@@ -37,13 +37,9 @@ from smcounter_amd import bamio, fasta  # noqa: E402
 from smcounter_amd.params import VcParams  # noqa: E402
 
 
-def reference_rows(bam_path, fa_path, loci, params):
-    """The reference's vc_wrapper() per locus, its pysam served from the BAM's records."""
-    import builtins
-    import contextlib
-    import io
-    mod = ref_harness._MOD or ref_harness.load_reference()
-    ref_harness._MOD = mod
+def pileup_table(bam_path, fa_path, loci):
+    """What the stub pysam serves for `loci`: per locus the covering records in file order with their pileup columns, and the
+    chromosomes' sequences."""
     bam = bamio.BamFile(bam_path)
     fa = fasta.FastaFile(fa_path)
     table, chroms = {}, {}
@@ -66,17 +62,30 @@ def reference_rows(bam_path, fa_path, loci, params):
                 chroms[chrom] = fa.fetch(chrom, 0, fa.get_reference_length(chrom))
             except Exception:
                 chroms[chrom] = ""
+    return table, chroms
+
+
+def reference_rows(bam_path, fa_path, loci, params, served=None):
+    """The reference's vc_wrapper() per locus, its pysam served from the BAM's records (`served`: pileup_table's answer, for a
+    caller that asks for several parameter sets).  Per locus the row, what make_golden keeps of a call, and `pileup`: vc()'s
+    per-allele tallies (ref_harness.capture_pileup)."""
+    import builtins
+    import contextlib
+    import io
+    mod = ref_harness._MOD or ref_harness.load_reference()
+    ref_harness._MOD = mod
+    table, chroms = served if served is not None else pileup_table(bam_path, fa_path, loci)
     stub_pysam.register_bam("golden.bam", table)
     stub_pysam.register_fasta("golden.fa", chroms)
     out = []
     for chrom, pos in loci:
         ref_harness.CAP.reset()
-        with contextlib.redirect_stdout(io.StringIO()):
+        with contextlib.redirect_stdout(io.StringIO()), ref_harness.capture_pileup(mod):
             row = mod.vc_wrapper("golden.bam", chrom, builtins.str(int(pos)), params.minBQ, params.minMQ, params.mtDepth, params.rpb,
                                  params.hpLen, params.mismatchThr, params.mtDrop, params.maxMT, params.primerDist, "golden.fa")
         assert not row.startswith("Exception thrown!"), row
         out.append(dict(row=row, pi_raw=list(ref_harness.CAP.round2), tie_ambiguous=ref_harness._tie_ambiguous(ref_harness.CAP.final),
-                        sampled=bool(ref_harness.CAP.sampled), depth=len(table[(chrom, int(pos))])))
+                        sampled=bool(ref_harness.CAP.sampled), depth=len(table[(chrom, int(pos))]), pileup=ref_harness.CAP.pileup))
     return out
 
 
@@ -91,7 +100,7 @@ def emit(name, refs, seqs, recs, loci, params):
     recs.sort(key=lambda r: (r["tid"], r["pos"]))
     bamio.write_bam(bam, refs, recs, block=60000)
     bamio.write_bai(bam)
-    exp = reference_rows(bam, fa_path, loci, params)
+    exp = [{k: v for k, v in e.items() if k != "pileup"} for e in reference_rows(bam, fa_path, loci, params)]   # (the tallies: tests/golden/geometry/)
     meta = dict(loci=loci, params=dataclasses.asdict(params), expected=exp)
     np.savez_compressed(os.path.join(HERE, name + ".npz"), bam=np.frombuffer(open(bam, "rb").read(), np.uint8),
                         bai=np.frombuffer(open(bam + ".bai", "rb").read(), np.uint8),

@@ -864,6 +864,36 @@ int smc_spike_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32
                          const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
                          int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
                          int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out, void* stream);
+/* (ABI 11, additive: two entries more, the version number unchanged) --spikeGrid: the cells (spike target t, barcode fraction f,
+ * reads-per-barcode target r) of the --spikeAF spike-in.  Cell (t, f, r) of replicate j is the spike-in at t drawn with seeds[j], of
+ * which the records stay that smc_read_groups_masks_grid keeps with the same seed in cell (f, r): the barcode's draw (smc_select_
+ * alignments' philox rule, domain "dsMT") is below bc_thr[f], and the record's name is its barcode's first, file-wide, or its read
+ * draw (smc_spike_rpb_counts') is below the cell's read threshold.  probKeep of (f, r) is made from the barcodes kept at f, which move
+ * with the seed, so every replicate has read thresholds of its own:
+ *   smc_read_groups_counts_frac_seeds  smc_read_groups_counts_frac for n_seeds seeds (HOST memory, at most SMC_AF_REP_MAX_REPS) in one
+ *            launch: host counts[j][f][4] uint64 = (barcodes, one, multi, multi_names) of the barcodes seeds[j] keeps at bc_thr[f] - the
+ *            four counters probKeep is made from.  Null stream; the table must be finished.  Unlike _counts_frac, which uses the
+ *            table's own scratch, every call allocates and frees a device buffer for the seeds and the counters (R reaches 1000) and
+ *            copies both ways blocking: meant for one call per run, not for a loop.
+ *   smc_spike_grid_counts  smc_spike_rpb_counts' arguments, with `bc_thr`: HOST memory, n_fracs words in [0, 2^32] (2^32 keeps every
+ *            barcode), and the read thresholds d_rd_thr[n_reps][n_fracs][n_read_thr] uint64 in DEVICE memory, rd_thr_host the same
+ *            words on the host (checked there; each in [0, 2^32]).  With (reads_q, alt_q, single_q) of a barcode over the records
+ *            kept at the pair q = (f, r) - flag bit 0 set, or the read draw below d_rd_thr[j][f][r] -, hit as there and
+ *            there = the barcode's draw < bc_thr[f] && reads_q > 0:
+ *            d_out[v][j][t][f][r][5] uint32 = smc_spike_rpb_counts' five counters with that `there`.  One spike draw and one barcode
+ *            draw per (b, v, j), one read draw per (record, j).  With n_fracs = 1, bc_thr[0] = 2^32 and the same thresholds in every
+ *            replicate the words are smc_spike_rpb_counts'; with n_read_thr = 1 and a threshold of 2^32 they are smc_spike_depth_
+ *            counts' on the per-barcode sums of the flag bits.  d_out is zeroed by the call; integer atomics only: two calls give
+ *            the same words.  Enqueued on `stream`; nothing waits.
+ * SMC_E_INPUT, nothing launched and nothing zeroed: what smc_spike_rpb_counts refuses, n_fracs or n_read_thr below 1, n_targets *
+ * n_fracs * n_read_thr above SMC_AF_DEPTH_MAX_CELLS, a threshold above 2^32 on any axis. */
+int smc_read_groups_counts_frac_seeds(smc_read_groups* g, const uint64_t* seeds, int32_t n_seeds, const uint64_t* bc_thr, int32_t n_frac,
+                                      uint64_t* counts);
+int smc_spike_grid_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_off, const uint32_t* cov_off_host,
+                          const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
+                          int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
+                          int32_t n_targets, const uint64_t* bc_thr, int32_t n_fracs, const uint64_t* d_rd_thr, const uint64_t* rd_thr_host,
+                          int32_t n_read_thr, uint32_t* d_out, void* stream);
 /* (ABI 11, additive: two entries more, the version number unchanged) --spikeIndelRpb: the cells (spike target t, reads-per-barcode
  * target r) of the --spikeIndels spike-in.  The cell, the two draws and the kept records are smc_spike_rpb_counts'; what a record
  * contributes is FOUR bits, because for an insertion or a deletion the records that show the key when the barcode is hit (alt1) and the

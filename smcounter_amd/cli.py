@@ -233,6 +233,23 @@ def build_parser() -> argparse.ArgumentParser:
                         "seed (dsSeed + j) mod 2^64: <outPrefix>.spikeAF.rpb.replicates.txt, .spikeAF.rpb.sensitivity.txt and "
                         ".spikeAF.rpb.curve.txt (per variant and r the detection rate at every target and T95).  SNV lists only; not "
                         "with --spikeDepth, --spikePhase or the --spikeIndel* flags.  Needs --spikeAF" % GRID_MAX_CELLS)
+    p.add_argument("--spikeGrid", action="store_true", default=False,
+                   help="a switch: --spikeDepth f1,.. and --spikeRpb r1,.. beside it give the two axes of a GRID.  For every --spikeAF "
+                        "target t, fraction f and reads-per-barcode target r the run is also called on the CELL (t, f, r): the spike-in "
+                        "at t, of which a record stays when the --dsGrid philox rule keeps it at (f, r) with the same --dsSeed (three "
+                        "independent draws: the spike-in's, the barcode's, the read name's; probKeep of (f, r) over the barcodes kept at "
+                        "f) - the .dsMT<f>.dsRpb<r> output of a --dsMT f --dsRpb r --dsGrid --dsSampler philox --dsRpbSampler philox "
+                        "run on the BAM tools/spike_variants.py --af t writes, at the mtDepth max(1, round(f x mtDepth)) of (t, f) and "
+                        "--rpb r; written to <outPrefix>.spikeAF<t>.dsMT<f>.dsRpb<r>.smCounter.{all,cut}.txt and .cut.vcf (with --lod: "
+                        "its LOD files and summary line), and, one line per variant and cell, <outPrefix>.spikeAF.grid.detection.txt.  "
+                        "The depth-only and reads-only cells either axis flag writes alone are NOT written: f = 1 gives the reads-only "
+                        "column, a depth-only row is a --spikeDepth run.  With --spikeReps replicate j draws all three streams with seed "
+                        "(dsSeed + j) mod 2^64 - its read thresholds are its own, probKeep moving with the barcodes it keeps: "
+                        "<outPrefix>.spikeAF.grid.replicates.txt, .spikeAF.grid.sensitivity.txt and .spikeAF.grid.budget.txt (per "
+                        "variant and target the cells by COST - the kept share of the file's read names - ascending, with the detection "
+                        "rate and CHEAPEST95 on the cheapest cell whose rate reaches 0.95).  At most %d cells; SNV lists only; not with "
+                        "--spikePhase, the --spikeIndel* flags, --spikePhaseRpb or --spikeScan*.  Without the switch --spikeDepth beside "
+                        "--spikeRpb stays refused.  Needs --spikeAF, --spikeDepth and --spikeRpb" % GRID_MAX_CELLS)
     p.add_argument("--spikeIndelRpb", default=None,
                    help="--spikeRpb on the --spikeIndels spike-in: comma-separated reads-per-barcode targets r > 0; --spikeVariants may "
                         "hold SNVs, insertions and deletions (the rules of --spikeIndels).  Cell (t, r) is the .dsRpb<r> output of a "
@@ -500,7 +517,7 @@ class _Plan:
     spike: dict = None          # (--spikeAF) once the rules are made: "variants", and "res", the pre-pass's numbers per target
     spike_reps: int = None      # (--spikeReps) R; plan.spike then holds "keep", what the pre-pass kept (None once the stage has taken it)
     spike_depth: dict = None    # (--spikeDepth) "fracs", the cells' "params", and once the rules are made "rules" and "counts" [V][T x F]
-    spike_rpb: dict = None      # (--spikeRpb, --spikeIndelRpb, --spikePhaseRpb: then also "flag") "targets", the cells' "params", and once the rules are made "rules" and "counts" [V][T x Rr]
+    spike_rpb: dict = None      # (--spikeRpb, --spikeIndelRpb, --spikePhaseRpb: then also "flag") "targets", the cells' "params", and once the rules are made "rules" and "counts" [V][T x Rr]; --spikeGrid: also "fracs" and "reps", the cells are (t, f, r) and the counts [V][T x F x Rr]
     spike_indel_counters: bool = False   # (--spikeIndelReps, --spikeIndelDepth, --spikeIndelPhase, --spikeIndelRpb, --spikePhaseRpb) the spike-ins are --spikeIndels', four counters per covering barcode
     scan: dict = None           # (--spikeScan) spike.scan's dict; once the rules are made also "variants", "loci" and "passes"
     spike_phase: bool = False   # (--spikePhase, --spikeIndelPhase, --spikePhaseRpb) plan.spike then holds "phase": None, or devplanes.spike_rules' dict of the sets of two members or more
@@ -947,9 +964,15 @@ def _main(args) -> int:
     phase_rpbs, phase_rpb_cells = _spike.phase_rpb_cells(args, spike_targets)
     indel_phase = _spike.indel_phase(args, spike_targets)
     indel_reps, indel_depth = _spike.indel_flags(args, spike_targets)
-    spike_fracs, spike_cells = _spike.depth_cells(args, spike_targets, "spikeIndelDepth" if indel_depth is not None else "spikeDepth")
-    _spike.indels(args, spike_targets)
-    spike_rpbs, spike_rpb_cells = _spike.rpb_cells(args, spike_targets)
+    # (--spikeGrid: the two axis flags give the grid's axes - the cells take the place of both flags' own)
+    grid_fracs, grid_rpbs, grid_cells = _spike.grid_cells(args, spike_targets)
+    if grid_fracs is not None:
+        _spike.indels(args, spike_targets)
+        spike_fracs, spike_cells, spike_rpbs, spike_rpb_cells = None, [], grid_rpbs, [(k, t, r, d, p) for k, t, (_, r), d, p in grid_cells]
+    else:
+        spike_fracs, spike_cells = _spike.depth_cells(args, spike_targets, "spikeIndelDepth" if indel_depth is not None else "spikeDepth")
+        _spike.indels(args, spike_targets)
+        spike_rpbs, spike_rpb_cells = _spike.rpb_cells(args, spike_targets)
     indel_rpb = False
     if spike_rpbs is None:
         # (--spikeIndelRpb: the same cells and outputs, the spike-ins --spikeIndels')
@@ -977,6 +1000,11 @@ def _main(args) -> int:
         plan.spike_rpb = dict(targets=spike_rpbs, params=[o.params for o in plan.outputs if o.kind == "spikeRpb"])
         if phase_rpbs is not None:
             plan.spike_rpb["flag"] = "--spikePhaseRpb"
+        if grid_fracs is not None:
+            # (--spikeGrid: the cells are --spikeRpb's with a fraction each; the pre-pass makes every replicate's thresholds up front)
+            for o, (_, _, (f, _), _, _) in zip((o for o in plan.outputs if o.kind == "spikeRpb"), grid_cells):
+                o.frac = f
+            plan.spike_rpb.update(flag="--spikeGrid", fracs=grid_fracs, reps=plan.spike_reps)
     plan.scan = scan
     if af_fracs is not None:
         plan.depth = dict(fracs=af_fracs, params=[o.params for o in plan.outputs if o.kind == "dsAFDepth"])
@@ -1012,8 +1040,9 @@ def _main(args) -> int:
     for rule in plan.rules:
         if rule.level == "read":               # (a target or a cell)
             if rule.spike_rpb_cell:
-                print("%s %s: sampler %s, seed %d, probKeep %.6g, threshold %d, %d of %d read names kept (mtDepth %d)" %
-                      (rule.flag, rule.label, rule.sampler, rule.seed, rule.prob_keep, rule.thr, rule.n_kept, rule.n_names, rule.params.mtDepth))
+                print("%s %s: sampler %s, seed %d, probKeep %.6g, %sthreshold %d, %d of %d read names kept (mtDepth %d)" %
+                      (rule.flag, rule.label, rule.sampler, rule.seed, rule.prob_keep, "barcode threshold %d, read " % rule.bc_thr if rule.grid else "",
+                       rule.thr, rule.n_kept, rule.n_names, rule.params.mtDepth))
                 continue
             print("%s: sampler %s, seed %d, probKeep %.6g, %d of %d read names kept (mtDepth %d)" %
                   ("--dsGrid " + rule.label if rule.grid else "--dsRpb %g" % rule.target, rule.sampler, rule.seed, rule.prob_keep,
@@ -1228,7 +1257,8 @@ def _af_reports(args, plan, shard, loc_list, repeats):
 def _spike_cells(plan, lods, kind="spikeDepth"):
     """(--spikeDepth; `kind` "spikeRpb": --spikeRpb) per cell (target index, target, fraction or reads-per-barcode target, mtDepth,
     output prefix, that output's LODs or None), as spike's depth pages take them; the cells' outputs lie behind the targets'."""
-    return [(o.af_index, o.af, o.frac if kind == "spikeDepth" else o.target, o.params.mtDepth, o.prefix,
+    grid = kind == "spikeRpb" and plan.spike_rpb is not None and plan.spike_rpb.get("fracs") is not None
+    return [(o.af_index, o.af, o.frac if kind == "spikeDepth" else (o.frac, o.target) if grid else o.target, o.params.mtDepth, o.prefix,
              lods[k]["lods"] if lods is not None else None) for k, o in enumerate(plan.outputs) if o.kind == kind]
 
 
@@ -1260,6 +1290,9 @@ def _spike_reports(args, plan, shard, loc_index, repeats):
             continue
         # (--spikeDepth, --spikeRpb: the same three pages over the cells; their rows stand behind the targets' in the stage's)
         depth = kind == "spikeDepth"
+        grid = not depth and info.get("fracs") is not None      # (--spikeGrid: the cells (t, f, r); the budget in the curve's place)
+        if grid:
+            axis = _spike.GRID_AXIS
         cells, T, dc = _spike_cells(plan, lods, kind), len(outs), reps["depth_counts" if depth else "rpb_counts"]
         cell_entries = {}
         for i, v in enumerate(variants):
@@ -1270,10 +1303,18 @@ def _spike_reports(args, plan, shard, loc_index, repeats):
                     row, cut = dsaf.replicate_entry(reps["rows"].get((i, T + c, j)), thr_c, *repeats)
                     per.append((dict(zip(("N", "V0", "S", "READS", "V1"), (int(x) for x in dc[i, j].reshape(-1, 5)[c]))), row, cut))
                 cell_entries[(i, c)] = per
-                print("--spikeReps: %s:%d %s>%s at %g x %s %g: called %d of %d" % (v.chrom, v.pos, v.ref, v.alt, o.af, "fraction" if depth else "target",
-                                                                                   o.frac if depth else o.target, _spike._called(v, per), R))
+                if grid and per[0][0] != info["counts"][i][c]:
+                    raise RuntimeError("--spikeGrid: %s:%d in %s: replicate 0 holds %r, the run's own cell %r" %
+                                       (v.chrom, v.pos, o.prefix, per[0][0], info["counts"][i][c]))
+                print("--spikeReps: %s:%d %s>%s at %g x %s%s %g: called %d of %d" % (v.chrom, v.pos, v.ref, v.alt, o.af, "fraction %g x " % o.frac if grid else "",
+                                                                                     "fraction" if depth else "target",
+                                                                                     o.frac if depth else o.target, _spike._called(v, per), R))
         _spike.write_depth_replicates(args.outPrefix, variants, cells, reps["seeds"], cell_entries, axis)
         _spike.write_depth_sensitivity(args.outPrefix, variants, cells, cell_entries, loc_index, axis)
+        if grid:
+            kept = [o.rule.n_kept for o in plan.outputs if o.kind == kind]
+            _spike.write_budget(args.outPrefix, variants, [c + (n,) for c, n in zip(cells, kept)], info["file_names"], cell_entries)
+            continue
         full = [(o.params.mtDepth, lods[1 + t]["lods"] if lods is not None else None) for t, o in enumerate(outs)]
         _spike.write_depth_curve(args.outPrefix, variants, targets, info["fracs"] if depth else info["targets"], full, cells, entries, cell_entries,
                                  loc_index, axis)
@@ -1445,7 +1486,8 @@ def _run(args, plan, loc_list, t0):
             _spike.write_depth_detection(args.outPrefix, plan.spike["variants"], _spike_cells(plan, lods), plan.spike_depth["counts"], loc_index)
         if plan.spike_rpb is not None:
             _spike.write_depth_detection(args.outPrefix, plan.spike["variants"], _spike_cells(plan, lods, "spikeRpb"),
-                                         plan.spike_rpb["counts"], loc_index, _spike.RPB_AXIS)
+                                         plan.spike_rpb["counts"], loc_index,
+                                         _spike.GRID_AXIS if plan.spike_rpb.get("fracs") is not None else _spike.RPB_AXIS)
         phase = plan.spike.get("phase")
         if phase is not None:
             # (--spikePhase: every set in the full-depth output - nothing spiked there -, in every target's and in every cell's)

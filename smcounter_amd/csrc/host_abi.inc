@@ -1836,36 +1836,16 @@ int smc_scan_detect_keys(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, 
     return SMC_OK;
 }
 
-// (--spikeRpb, --spikeIndelRpb, --spikePhaseRpb) what the three counts entries check, on the host copies and before anything is
-// enqueued, then the counters zeroed and k_spr_counts.  A row is a listed variant: (N', V0', S', READS', V1') per replicate and cell
-// (spike target x read threshold) from the records of its covering barcodes, segment e the records of barcode e - with `four` the
-// instance that reads alt1 and touch from flag bits 2 and 3, else the one in which bit 2 is both.  Or with `sets` a phase set of
-// set_m_host[g] members: (N_ALL', V0_ALL', S_ALL', V1_ALL') from the records of every (joint barcode, member); the segment bases are
-// the running sums of (joint barcodes x members), so no lane reads an offset beyond the n_seg + 1 there are.
-static int spr_cell_counts(const std::string& who, bool four, bool sets, smc_ctx* ctx, const uint64_t* d_ident, const uint32_t* d_off,
-                           const uint32_t* off_host, const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_seg_base,
-                           const uint32_t* seg_base_host, const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name,
-                           const uint8_t* d_rec_flag, int64_t n_rec, const uint32_t* d_pos1, int32_t n_rows, const uint64_t* d_seeds,
-                           int32_t n_reps, const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr,
-                           uint32_t* d_out, void* stream) {
-    const std::string rows = sets ? " sets" : " variants", row = sets ? "set " : "variant ";
-    const size_t n_counters = sets ? SPP_COUNTERS : SPC_COUNTERS;
-    SpkThr T;
-    if (int rc = spk_axes(who, ctx, n_rec < 0, rows, n_rows, d_seeds, n_reps, thr, n_targets, true, " read thresholds", read_thr, n_read_thr, T)) return rc;
-    RgThr Q;
-    memset(&Q, 0, sizeof Q);
-    for (int32_t r = 0; r < n_read_thr; ++r) {
-        if (read_thr[r] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": read threshold " + std::to_string(r) + " is above 2^32");
-        if (r < SMC_RG_MAX_TARGETS) Q.t[r] = read_thr[r];         // (more of them pass the cells' limit only without a target: nothing is launched)
-    }
-    if ((double)n_rows * (double)n_reps * (double)n_targets * (double)n_read_thr * (double)n_counters >= (double)0xFFFFFF00u)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_rows) + rows + " x " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) +
-                                 " targets x " + std::to_string(n_read_thr) + " read thresholds: too many counters for one call");
-    if (n_rec >= (int64_t)0xFFFFFF00) return fail(SMC_E_INPUT, who + ": too many covering records for one call");
-    if (!n_rows || !n_reps || !n_targets) return SMC_OK;
+// What spr_cell_counts and smc_spike_grid_counts check of the rows and their record segments, on the host copies -> `widest`: the most
+// barcodes a row has.
+static int spr_check_segments(const std::string& who, bool sets, const uint64_t* d_ident, const uint32_t* d_off, const uint32_t* off_host,
+                              const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_seg_base, const uint32_t* seg_base_host,
+                              const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
+                              int64_t n_rec, const uint32_t* d_pos1, int32_t n_rows, const uint32_t* d_out, uint32_t& widest) {
+    const std::string row = sets ? "set " : "variant ";
     if (!off_host || !d_off || !d_pos1 || !d_out || (sets && (!set_m_host || !d_set_m || !seg_base_host || !d_seg_base)))
         return fail(SMC_E_ARG, who + ": NULL argument");
-    uint32_t widest = 0;
+    widest = 0;
     uint64_t n_seg = 0;
     for (int32_t g = 0; g < n_rows; ++g) {
         const uint32_t m = sets ? set_m_host[g] : 1u;
@@ -1891,6 +1871,39 @@ static int spr_cell_counts(const std::string& who, bool four, bool sets, smc_ctx
             return fail(SMC_E_INPUT, who + ": the record offsets end at " + std::to_string(rec_off_host[n_seg]) + ", beyond the " + std::to_string(n_rec) + " records");
         if (n_rec && (!d_rec_name || !d_rec_flag)) return fail(SMC_E_ARG, who + ": NULL records");
     }
+    return SMC_OK;
+}
+
+// (--spikeRpb, --spikeIndelRpb, --spikePhaseRpb) what the three counts entries check, on the host copies and before anything is
+// enqueued, then the counters zeroed and k_spr_counts.  A row is a listed variant: (N', V0', S', READS', V1') per replicate and cell
+// (spike target x read threshold) from the records of its covering barcodes, segment e the records of barcode e - with `four` the
+// instance that reads alt1 and touch from flag bits 2 and 3, else the one in which bit 2 is both.  Or with `sets` a phase set of
+// set_m_host[g] members: (N_ALL', V0_ALL', S_ALL', V1_ALL') from the records of every (joint barcode, member); the segment bases are
+// the running sums of (joint barcodes x members), so no lane reads an offset beyond the n_seg + 1 there are.
+static int spr_cell_counts(const std::string& who, bool four, bool sets, smc_ctx* ctx, const uint64_t* d_ident, const uint32_t* d_off,
+                           const uint32_t* off_host, const uint32_t* d_set_m, const uint32_t* set_m_host, const uint32_t* d_seg_base,
+                           const uint32_t* seg_base_host, const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name,
+                           const uint8_t* d_rec_flag, int64_t n_rec, const uint32_t* d_pos1, int32_t n_rows, const uint64_t* d_seeds,
+                           int32_t n_reps, const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr,
+                           uint32_t* d_out, void* stream) {
+    const std::string rows = sets ? " sets" : " variants";
+    const size_t n_counters = sets ? SPP_COUNTERS : SPC_COUNTERS;
+    SpkThr T;
+    if (int rc = spk_axes(who, ctx, n_rec < 0, rows, n_rows, d_seeds, n_reps, thr, n_targets, true, " read thresholds", read_thr, n_read_thr, T)) return rc;
+    RgThr Q;
+    memset(&Q, 0, sizeof Q);
+    for (int32_t r = 0; r < n_read_thr; ++r) {
+        if (read_thr[r] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": read threshold " + std::to_string(r) + " is above 2^32");
+        if (r < SMC_RG_MAX_TARGETS) Q.t[r] = read_thr[r];         // (more of them pass the cells' limit only without a target: nothing is launched)
+    }
+    if ((double)n_rows * (double)n_reps * (double)n_targets * (double)n_read_thr * (double)n_counters >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_rows) + rows + " x " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) +
+                                 " targets x " + std::to_string(n_read_thr) + " read thresholds: too many counters for one call");
+    if (n_rec >= (int64_t)0xFFFFFF00) return fail(SMC_E_INPUT, who + ": too many covering records for one call");
+    if (!n_rows || !n_reps || !n_targets) return SMC_OK;
+    uint32_t widest = 0;
+    if (int rc = spr_check_segments(who, sets, d_ident, d_off, off_host, d_set_m, set_m_host, d_seg_base, seg_base_host, d_rec_off, rec_off_host,
+                                    d_rec_name, d_rec_flag, n_rec, d_pos1, n_rows, d_out, widest)) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     const hipStream_t st = (hipStream_t)stream;
     const size_t n_out = n_counters * (size_t)n_rows * (size_t)n_reps * (size_t)n_targets * (size_t)n_read_thr;
@@ -1917,6 +1930,55 @@ int smc_spike_rpb_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32
     return spr_cell_counts("smc_spike_rpb_counts", false, false, ctx, d_cov_ident, d_cov_off, cov_off_host, nullptr, nullptr, nullptr, nullptr,
                            d_rec_off, rec_off_host, d_rec_name, d_rec_flag, n_rec, d_pos1, n_var, d_seeds, n_reps, thr, n_targets, read_thr,
                            n_read_thr, d_out, stream);
+}
+
+// (--spikeGrid) smc_spike_rpb_counts' numbers per cell (spike target x barcode fraction x read threshold): the barcode rule's
+// thresholds by value, the read thresholds per replicate in device memory (rd_thr_host: the same words on the host, for the checks).
+// A pair (fraction, read threshold) takes the place of smc_spike_rpb_counts' read threshold; k_spg_counts for 8 pairs or for 32.
+int smc_spike_grid_counts(smc_ctx* ctx, const uint64_t* d_cov_ident, const uint32_t* d_cov_off, const uint32_t* cov_off_host,
+                          const uint32_t* d_rec_off, const uint32_t* rec_off_host, const uint64_t* d_rec_name, const uint8_t* d_rec_flag,
+                          int64_t n_rec, const uint32_t* d_pos1, int32_t n_var, const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr,
+                          int32_t n_targets, const uint64_t* bc_thr, int32_t n_fracs, const uint64_t* d_rd_thr, const uint64_t* rd_thr_host,
+                          int32_t n_read_thr, uint32_t* d_out, void* stream) {
+    const std::string who = "smc_spike_grid_counts";
+    if (n_fracs < 0 || n_read_thr < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_fracs < 1) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_fracs) + " fractions, at least 1 expected");
+    if (n_read_thr < 1) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_read_thr) + " read thresholds, at least 1 expected");
+    const int64_t n_pairs = (int64_t)n_fracs * (int64_t)n_read_thr;
+    SpkThr T;
+    if (int rc = spk_axes(who, ctx, n_rec < 0, " variants", n_var, d_seeds, n_reps, thr, n_targets, true, " fraction x read-threshold pairs", bc_thr,
+                          (int32_t)std::min<int64_t>(n_pairs, INT32_MAX), T)) return rc;
+    AfdThr D;
+    memset(&D, 0, sizeof D);
+    for (int32_t f = 0; f < n_fracs; ++f) {
+        if (bc_thr[f] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": depth threshold " + std::to_string(f) + " is above 2^32");
+        if (f < SMC_AF_DEPTH_MAX_CELLS) D.f[f] = bc_thr[f];          // (more of them pass the cells' limit only without a target: nothing is launched)
+    }
+    if ((double)n_var * (double)n_reps * (double)n_targets * (double)n_pairs * (double)SPC_COUNTERS >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_var) + " variants x " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) +
+                                 " targets x " + std::to_string(n_fracs) + " fractions x " + std::to_string(n_read_thr) + " read thresholds: too many counters for one call");
+    if (n_rec >= (int64_t)0xFFFFFF00) return fail(SMC_E_INPUT, who + ": too many covering records for one call");
+    if (!n_var || !n_reps || !n_targets) return SMC_OK;
+    if (!d_rd_thr || !rd_thr_host) return fail(SMC_E_ARG, who + ": NULL argument");
+    for (int64_t k = 0; k < (int64_t)n_reps * n_pairs; ++k)         // (n_pairs <= SMC_AF_DEPTH_MAX_CELLS here: a target there is)
+        if (rd_thr_host[k] > (1ull << 32))
+            return fail(SMC_E_INPUT, who + ": read threshold " + std::to_string(k % n_pairs) + " of replicate " + std::to_string(k / n_pairs) + " is above 2^32");
+    uint32_t widest = 0;
+    if (int rc = spr_check_segments(who, false, d_cov_ident, d_cov_off, cov_off_host, nullptr, nullptr, nullptr, nullptr, d_rec_off, rec_off_host,
+                                    d_rec_name, d_rec_flag, n_rec, d_pos1, n_var, d_out, widest)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t n_out = (size_t)SPC_COUNTERS * (size_t)n_var * (size_t)n_reps * (size_t)n_targets * (size_t)n_pairs;
+    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
+    const auto kernel = n_pairs <= 8 ? k_spg_counts<8> : k_spg_counts<SMC_AF_DEPTH_MAX_CELLS>;
+    if (widest)
+        hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<uint32_t>((widest + SPB_BLOCK - 1) / SPB_BLOCK, 256u), (unsigned)n_var,
+                                        (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPB_BLOCK), 0, st,
+                           (const unsigned long long*)d_cov_ident, d_cov_off, d_rec_off, (const unsigned long long*)d_rec_name, d_rec_flag,
+                           (uint32_t)n_rec, d_pos1, T, (int)n_targets, D, (int)n_fracs, (int)n_read_thr, (const unsigned long long*)d_rd_thr,
+                           (const unsigned long long*)d_seeds, (int)n_reps, d_out);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
 }
 
 // (--spikeIndelRpb) the same from FOUR bits per record: flag bit 2 = alt1, bit 3 = touch (smc_spike_indel_read_bits' bits 2 and 3)
@@ -2130,6 +2192,35 @@ int smc_read_groups_counts_frac(smc_read_groups* g, uint64_t seed, const uint64_
         c[6] = (int64_t)a[RG_F_BARCODES];                                  // first names: one per barcode
         c[7] = 0;
     }
+    return SMC_OK;
+}
+
+// (--spikeGrid) smc_read_groups_counts_frac's four counters for n_seeds seeds in ONE launch: counts[(j * n_frac + f) * 4 + k], k =
+// barcodes, one, multi, multi_names of the barcodes seeds[j] keeps at bc_thr[f].  The seeds and the counters live in one allocation of
+// the call's own (R can be 1000: more than the table's scratch holds).
+int smc_read_groups_counts_frac_seeds(smc_read_groups* g, const uint64_t* seeds, int32_t n_seeds, const uint64_t* bc_thr, int32_t n_frac,
+                                      uint64_t* counts) {
+    const std::string who = "smc_read_groups_counts_frac_seeds";
+    if (!g || n_seeds < 0 || (n_seeds && !seeds) || (n_seeds && n_frac > 0 && !counts)) return fail(SMC_E_ARG, who + ": bad argument");
+    if (!g->finished) return fail(SMC_E_ARG, who + ": the table is not finished");
+    if (n_seeds > SMC_AF_REP_MAX_REPS) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_seeds) + " seeds, at most " + std::to_string(SMC_AF_REP_MAX_REPS));
+    RgThr F;
+    { const int rc = rg_thresholds(bc_thr, n_frac, F); if (rc) return rc; }
+    if (!n_frac || !n_seeds) return SMC_OK;
+    HIPCHK(hipSetDevice(g->ctx->device));
+    const size_t n_out = (size_t)n_seeds * (size_t)n_frac * RG_F_N;
+    unsigned long long* d = nullptr;
+    HIPCHK(hipMalloc((void**)&d, 8 * ((size_t)n_seeds + n_out)));
+    hipError_t e = hipMemcpy(d, seeds, 8 * (size_t)n_seeds, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(d + n_seeds, 0, 8 * n_out, 0);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_rg_reduce_frac_seeds, dim3(std::min(rg_grid(g->G.b_mask + 1), RG_RED_GRID), (unsigned)std::min<int32_t>(n_seeds, 64)),
+                           dim3(RG_BLOCK), 0, 0, g->G, d, (int)n_seeds, F, (int)n_frac, d + n_seeds);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(counts, d + n_seeds, 8 * n_out, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIPCHK(e);
     return SMC_OK;
 }
 

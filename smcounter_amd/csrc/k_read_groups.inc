@@ -22,7 +22,7 @@
 //   k_rg_masks    per run: a wave of 64 read-name ids looks up its names and writes two mask words per target (the bit layout
 //                 smc_select_alignments_keyed takes at SMC_SEL_KEY_READ)
 //   k_rg_kept     per name slot: the kept names of every target, for the run log
-// and, for --dsGrid (below): k_rg_reduce_frac, k_rg_masks_grid, k_rg_kept_grid.
+// and, for --dsGrid (below): k_rg_reduce_frac, k_rg_masks_grid, k_rg_kept_grid; for --spikeGrid: k_rg_reduce_frac_seeds.
 // Every probe loop ends after `capacity` steps: a full table sets RG_FULL and the record is dropped (not met: load <= 0.5).
 #define RG_BLOCK 256
 #define RG_DOMAIN 0x64735250u               // counter word 2 of the read draw ("dsRP"); SEL_DOMAIN "dsMT" is the barcode draw's
@@ -255,9 +255,10 @@ struct RgGridThr {
     unsigned long long rd[SMC_RG_MAX_TARGETS];   // per cell: floor(probKeep * 2^32) in [0, 2^32]
 };
 
-__global__ __launch_bounds__(RG_BLOCK) void k_rg_reduce_frac(RgTable G, unsigned long long seed, RgThr F, int n_frac,
-                                                             unsigned long long* __restrict__ out) {
-    __shared__ unsigned long long acc[SMC_RG_MAX_TARGETS * RG_F_N];
+// (the body of k_rg_reduce_frac and k_rg_reduce_frac_seeds: one seed's counters over the workgroup's share of the barcode slots;
+// `acc`: SMC_RG_MAX_TARGETS * RG_F_N words of LDS; every thread of the workgroup calls it, it begins and ends with a barrier)
+__device__ __forceinline__ void rg_reduce_frac_seed(const RgTable& G, unsigned long long seed, const RgThr& F, int n_frac,
+                                                    unsigned long long* __restrict__ acc, unsigned long long* __restrict__ out) {
     for (int k = threadIdx.x; k < n_frac * RG_F_N; k += RG_BLOCK) acc[k] = 0ull;
     __syncthreads();
     const unsigned long long n = G.b_mask + 1, stride = (unsigned long long)gridDim.x * RG_BLOCK;
@@ -292,6 +293,22 @@ __global__ __launch_bounds__(RG_BLOCK) void k_rg_reduce_frac(RgTable G, unsigned
     __syncthreads();
     for (int k = threadIdx.x; k < n_frac * RG_F_N; k += RG_BLOCK)
         if (acc[k]) atomicAdd(&out[k], acc[k]);
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(RG_BLOCK) void k_rg_reduce_frac(RgTable G, unsigned long long seed, RgThr F, int n_frac,
+                                                             unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long acc[SMC_RG_MAX_TARGETS * RG_F_N];
+    rg_reduce_frac_seed(G, seed, F, n_frac, acc, out);
+}
+
+// (--spikeGrid) k_rg_reduce_frac with the replicate as a grid dimension: blockIdx.y strides over the n_seeds seeds,
+// out[(j * n_frac + f) * RG_F_N + k] the counters of seed j (zeroed before the launch) - one launch where --spikeReps R would make R
+__global__ __launch_bounds__(RG_BLOCK) void k_rg_reduce_frac_seeds(RgTable G, const unsigned long long* __restrict__ seeds, int n_seeds, RgThr F,
+                                                                   int n_frac, unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long acc[SMC_RG_MAX_TARGETS * RG_F_N];
+    for (int j = blockIdx.y; j < n_seeds; j += gridDim.y)
+        rg_reduce_frac_seed(G, seeds[j], F, n_frac, acc, out + (size_t)j * n_frac * RG_F_N);
 }
 
 // masks[c * n_words + (g >> 5)] bit (g & 31): read-name id g is kept in cell c (k_rg_masks' layout, a mask per cell)

@@ -1,4 +1,5 @@
-// Included by smcounter_hip.hip (after k_spike_cells.inc: SPC_COUNTERS, spd_hits and the spike draw's domain; after k_read_groups.inc:
+// Included by smcounter_hip.hip (after k_spike_cells.inc: SPC_COUNTERS, spd_hits, the spike draw's domain and, for k_spg_counts at the
+// end of this file, what k_spike_cells itself takes from k_af_depth.inc and k_select_aln.inc: afd_keep_depth, sel_draw; after k_read_groups.inc:
 // rg_draw, the read draw k_rg_masks makes; after k_allele_carriers.inc: af_shows; after k_spike_indel.inc: spi_walk, spi_first).
 // ------------------------------------------------------------------------------------------
 // --spikeRpb: what every cell (spike target t, reads-per-barcode target r) of R replicate spike-ins achieves per listed SNV, counted
@@ -245,3 +246,102 @@ __global__ __launch_bounds__(SPB_BLOCK) void k_spr_counts(const unsigned long lo
 }
 static_assert(SMC_RG_MAX_TARGETS == SMC_AF_DEPTH_MAX_CELLS && SPP_COUNTERS <= SPC_COUNTERS && SPC_COUNTERS * SMC_AF_DEPTH_MAX_CELLS <= SPB_BLOCK,
               "k_spr_counts: a bit per read threshold, a lane per cell and counter");
+
+// ------------------------------------------------------------------------------------------
+// --spikeGrid (smc_spike_grid_counts): the cells (spike target t, barcode fraction f, reads-per-barcode target r)
+// ------------------------------------------------------------------------------------------
+// Cell (t, f, r) of replicate j is the spike-in at t, then --dsGrid's philox rule at (f, r), all three streams keyed by s_j: a record
+// stays when its barcode's sel_draw is below bc_thr[f] AND it is a first name or its rg_draw is below the cell's read threshold.
+// Under a grid the read threshold is no constant of the file: probKeep of (f, r) is made from the barcodes kept at f, which move with
+// the seed - so the thresholds come per replicate, rd_thr[(j * n_frac + f) * n_rr + r] in device memory, and k_spr_counts, whose
+// thresholds are one by-value set for every replicate, cannot serve.  A PAIR q = f * n_rr + r takes the place of k_spr_counts' r: one
+// rg_draw per record and replicate, its compares against the replicate's n_frac * n_rr thresholds one bit set, (reads_q, alt_q,
+// single_q) per pair in registers (unrolled loops only; MAXQ = 8 and 32 as there).  The barcode rule drops whole barcodes, so it is
+// ONE sel_draw per (barcode, replicate), a bit set over f, applied behind the record walk:
+//   there = kept_f && reads_q > 0      N' = there      V0' = there && 2 alt_q > reads_q      S' = there && hit_t
+//   READS' = single_q over there && hit_t             V1' = there && (hit_t ? 2 single_q > reads_q : 2 alt_q > reads_q)
+// reduced exactly as k_spr_counts reduces.  With one fraction of 2^32 and every replicate's thresholds equal the words are
+// k_spr_counts<., false, false>'s; with one read threshold of 2^32 they are k_spike_cells' on the per-barcode sums of the flag bits.
+// out[((((g * n_reps + j) * n_tgt + t) * n_frac + f) * n_rr + r) * 5 + k] (zeroed before the launch); n_tgt * n_frac * n_rr <=
+// SMC_AF_DEPTH_MAX_CELLS, n_frac * n_rr <= MAXQ (the host picks the instance).
+template <int MAXQ>
+__global__ __launch_bounds__(SPB_BLOCK) void k_spg_counts(const unsigned long long* __restrict__ ident, const uint32_t* __restrict__ off,
+                                                          const uint32_t* __restrict__ rec_off, const unsigned long long* __restrict__ rec_name,
+                                                          const uint8_t* __restrict__ rec_flag, uint32_t n_rec,
+                                                          const uint32_t* __restrict__ pos1, SpkThr T, int n_tgt, AfdThr D, int n_frac, int n_rr,
+                                                          const unsigned long long* __restrict__ rd_thr,
+                                                          const unsigned long long* __restrict__ seeds, int n_reps, uint32_t* __restrict__ out) {
+    __shared__ uint32_t part[SPB_BLOCK / WAVE][SMC_AF_DEPTH_MAX_CELLS][SPC_COUNTERS];
+    __shared__ unsigned long long Q[SMC_AF_DEPTH_MAX_CELLS];                            // the replicate's thresholds, one per pair
+    const uint32_t g = blockIdx.y;
+    const uint32_t e0 = off[g], e1 = off[g + 1], pos = pos1[g];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    const int n_q = n_frac * n_rr, n_cells = n_tgt * n_q;
+    const uint32_t every = n_q >= 32 ? 0xFFFFFFFFu : (1u << n_q) - 1u;
+    const uint32_t stride = gridDim.x * SPB_BLOCK;
+    for (uint32_t base = e0 + blockIdx.x * SPB_BLOCK; base < e1; base += stride) {     // (whole workgroups: the barriers below)
+        const uint32_t e = base + threadIdx.x;
+        const bool in_row = e < e1;
+        const unsigned long long id = in_row ? ident[e] : 0ull;
+        uint32_t r0 = 0, r1 = 0;                                                       // (a lane beyond the row: no records, N' = 0 everywhere)
+        if (in_row) spr_segment(rec_off, e, n_rec, r0, r1);
+        for (int j = blockIdx.z; j < n_reps; j += gridDim.z) {
+            const unsigned long long seed = seeds[j];
+            // (the replicate's own thresholds, fetched ONCE into LDS - not per record; the barrier behind the last reduction, or the one
+            // below, stands between a lane's reads of the previous replicate's and these stores)
+            if ((int)threadIdx.x < n_q) Q[threadIdx.x] = rd_thr[(size_t)j * n_q + threadIdx.x];
+            __syncthreads();
+            uint32_t x[4];
+            smc_philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), SPK_DOMAIN, pos, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+            const uint32_t k_hit = spd_hits(T, x[0], n_tgt);
+            const uint32_t k_d = in_row ? afd_keep_depth(D, sel_draw(id, seed), n_frac) : 0u;
+            uint32_t reads[MAXQ], alt[MAXQ], sgl[MAXQ];
+#pragma unroll
+            for (int q = 0; q < MAXQ; ++q) reads[q] = alt[q] = sgl[q] = 0u;
+            for (uint32_t i = r0; i < r1; ++i) {
+                const uint32_t fl = rec_flag[i];
+                uint32_t kept = every;
+                if (!(fl & SPB_FIRST)) {
+                    const uint32_t u = rg_draw(rec_name[i], seed);
+                    kept = 0u;
+                    for (int q = 0; q < n_q; ++q) kept |= (uint32_t)((unsigned long long)u < Q[q]) << q;
+                }
+                const uint32_t is_alt = (fl >> 1) & 1u, is_sgl = (fl >> 2) & 1u;
+#pragma unroll
+                for (int q = 0; q < MAXQ; ++q) {
+                    const uint32_t k = (kept >> q) & 1u;
+                    reads[q] += k; alt[q] += k & is_alt; sgl[q] += k & is_sgl;
+                }
+            }
+            int f = 0, r = 0;                                                          // (pair q = f * n_rr + r, stepped: no division)
+#pragma unroll
+            for (int q = 0; q < MAXQ; ++q) {
+                if (q < n_q) {                                                         // (uniform)
+                    const bool there = ((k_d >> f) & 1u) != 0u && reads[q] > 0u;
+                    const bool car0 = 2ull * alt[q] > (unsigned long long)reads[q];
+                    const bool car1 = 2ull * sgl[q] > (unsigned long long)reads[q];
+                    const unsigned long long m_n = __ballot(there), m_v0 = __ballot(there && car0);
+                    for (int t = 0; t < n_tgt; ++t) {
+                        const bool hit = ((k_hit >> t) & 1u) != 0u;
+                        const unsigned long long m_s = __ballot(there && hit), m_v1 = __ballot(there && (hit ? car1 : car0));
+                        const int rd = wave_add((int)((there && hit) ? sgl[q] : 0u));    // (fewer than 2^32 - 256 records: no wrap that matters)
+                        if (lane == 0) {
+                            uint32_t* const p = part[wave][t * n_q + q];
+                            p[0] = (uint32_t)__popcll(m_n); p[1] = (uint32_t)__popcll(m_v0); p[2] = (uint32_t)__popcll(m_s);
+                            p[3] = (uint32_t)rd; p[4] = (uint32_t)__popcll(m_v1);
+                        }
+                    }
+                    if (++r == n_rr) { r = 0; ++f; }
+                }
+            }
+            __syncthreads();
+            if ((int)threadIdx.x < SPC_COUNTERS * n_cells) {                           // (5 * 32 = 160 < SPB_BLOCK)
+                const int c = threadIdx.x / SPC_COUNTERS, k = threadIdx.x % SPC_COUNTERS;
+                uint32_t sum = 0;
+                for (int w = 0; w < SPB_BLOCK / WAVE; ++w) sum += part[w][c][k];
+                if (sum) atomicAdd(&out[(((size_t)g * n_reps + j) * n_cells + c) * SPC_COUNTERS + k], sum);
+            }
+            __syncthreads();
+        }
+    }
+}

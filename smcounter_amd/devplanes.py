@@ -897,6 +897,7 @@ class DsRule:
     # (--spikeRpb) a cell: `spike` and `af` of its target beside level "read", `target` r, `prob_keep`, `groups` (the file-wide table of
     # the UNSPIKED file: spiking changes no name) and `thr`: the spiked copy of the target, then the philox read selection at r with the
     # same `seed`
+    # (--spikeGrid) a cell: the same with `grid`, `frac` f and `bc_thr` - --dsGrid's composed philox rule at (f, r) over the spiked copy
     spike: object = None
 
     @property
@@ -926,6 +927,8 @@ class DsRule:
 
     @property
     def label(self) -> str:
+        if self.spike_rpb_cell and self.grid:
+            return "spiked allele fraction %g x fraction %g x target %g" % (self.af, self.frac, self.target)
         if self.spike_rpb_cell:
             return "spiked allele fraction %g x target %g" % (self.af, self.target)
         if self.spike_cell:
@@ -1109,6 +1112,16 @@ class ReadGroups(object):
         _lib.check(self.L.smc_read_groups_counts_frac(self._h, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), t.ctypes.data, len(t),
                                                       c.ctypes.data), "smc_read_groups_counts_frac")
         return [dict(zip(self.COUNTS[1:], (int(v) for v in row[1:7]))) for row in c[:len(t)]]
+
+    def counts_frac_seeds(self, seeds, bc_thr) -> np.ndarray:
+        """(--spikeGrid) counts_frac for every seed in one launch -> uint64 [len(seeds), len(bc_thr), 4] = (barcodes, one, multi,
+        multi_names) of the barcodes seeds[j] keeps at bc_thr[f]."""
+        t = self._thr(bc_thr, "--dsMT fractions")
+        s = np.ascontiguousarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], np.uint64)
+        c = np.zeros((len(s), len(t), 4), np.uint64)
+        _lib.check(self.L.smc_read_groups_counts_frac_seeds(self._h, s.ctypes.data, len(s), t.ctypes.data, len(t), c.ctypes.data),
+                   "smc_read_groups_counts_frac_seeds")
+        return c
 
     def masks_grid(self, d_idents, n_ids: int, seed: int, bc_thr, rd_thr, d_masks):
         """(--dsGrid) masks() with a mask per cell: barcode threshold bc_thr[c] and read threshold rd_thr[c]."""
@@ -1955,7 +1968,11 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
     phase["rpb_counts"], per set and cell dict(N_ALL, V0_ALL, S_ALL, V1_ALL) over the reads the cell keeps.  They are counted a second
     way as well: the read selections hand back smc_allele_carriers' cover and carrier bits as identities, and per set and cell the AND
     over the members - on the selection of the spiked copy of t for N_ALL' and V1_ALL', on that of the run itself for V0_ALL' - must
-    give the same numbers, else RuntimeError naming set and cell.  The refusals and DsRule.flag name --spikePhaseRpb."""
+    give the same numbers, else RuntimeError naming set and cell.  The refusals and DsRule.flag name --spikePhaseRpb.
+    `rpb` with "fracs" and "flag" "--spikeGrid" (--spikeGrid: SNV lists only; "reps": R or None; "params" of the T x F x Rr cells,
+    targets outer, then fractions, then r): a read rule per PAIR (f, r) over the same table (_spike_grid_rules: every replicate's
+    thresholds up front in rpb["rep_thr"] [R, F, Rr], the run's own rules from philox_grid_rules); the masks are masks_grid's, the
+    counts come from one smc_spike_grid_counts call, "counts" and "rules" run over the T x F x Rr cells; the second count is the same."""
     from .tools import ds_allele_fraction as af
     from .tools import spike_variants as sv
     af.unique_idents(bamio.placed_barcodes(path), path)
@@ -1964,6 +1981,9 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
         # (--spikeIndelRpb - `indel_counters` - lifts the indel part; an indel in the list without it is --spikeRpb's to refuse)
         # (--spikePhaseRpb - rpb["flag"], with `indel_counters` - lifts the phase part as well)
         phase_rpb = indel_counters and rpb.get("flag") == "--spikePhaseRpb"
+        grid = rpb.get("fracs") is not None
+        if grid and (depth is not None or phase is not None or indel_counters or any(v.kind != af.SNV for v in variants)):
+            raise ValueError("--spikeGrid: phase sets or indel spike-ins on the grid are not built")
         if depth is not None or (phase is not None and not phase_rpb) or (not indel_counters and any(v.kind != af.SNV for v in variants)):
             raise ValueError("--spikeRpb: cells of barcode depths, phase sets or indel spike-ins are not built")
         # (the file-wide table of the UNSPIKED file serves every cell and replicate: spiking changes no name, barcode or record count -
@@ -1971,6 +1991,8 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
         read_rules = philox_read_rules(path, list(rpb["targets"]), [params_list[0]] * len(rpb["targets"]), seed, eng, nthreads=nthreads,
                                        flag=rpb.get("flag") or ("--spikeIndelRpb" if indel_counters else "--spikeRpb"))
         try:
+            if grid:
+                read_rules = _spike_grid_rules(path, rpb, params_list[0], seed, read_rules)
             return _spike_rules(path=path, fasta=fasta, variants=variants, targets=targets, params_list=params_list, seed=seed, eng=eng,
                                 nthreads=nthreads, max_reads=max_reads, keep=keep, keep_bytes=keep_bytes, depth=depth, phase=phase,
                                 indel_counters=indel_counters, rpb=rpb, read_rules=read_rules)
@@ -1982,6 +2004,23 @@ def spike_rules(path: str, fasta, variants, targets, params_list, seed: int, eng
                         indel_counters=indel_counters, rpb=None, read_rules=None)
 
 
+def _spike_grid_rules(path, rpb, P, seed, read_rules):
+    """(--spikeGrid) The F x Rr read rules of the grid (fractions outer), over the table of philox_read_rules' `read_rules`.  First the
+    thresholds of EVERY replicate (rpb["reps"], None: the run alone) from one counts_frac_seeds launch - a (replicate, fraction) that
+    keeps no barcode of two or more names ends the run here, before any file is written -, kept in rpb["rep_thr"] / rpb["rep_prob"]
+    for the replicate stage; then philox_grid_rules' rules of the run's own seed, whose thresholds must be replicate 0's.
+    rpb["file_names"]: the file's distinct read names (the budget page's denominator)."""
+    from . import dsaf
+    groups = read_rules[0].groups
+    rpb["rep_thr"], rpb["rep_prob"] = grid_read_thresholds(groups, dsaf.rep_seeds(seed, rpb.get("reps") or 1), rpb["fracs"], rpb["targets"])
+    cells = [(f, r) for f in rpb["fracs"] for r in rpb["targets"]]
+    rules = philox_grid_rules(path, cells, [P] * len(cells), seed, groups)
+    if [int(r.thr) for r in rules] != [int(x) for x in rpb["rep_thr"][0].reshape(-1)]:
+        raise RuntimeError("--spikeGrid: the thresholds of replicate 0 are not the run's own cells'")
+    rpb["file_names"] = int(groups.counts["names"])
+    return rules
+
+
 def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthreads, max_reads, keep, keep_bytes, depth, phase,
                  indel_counters, rpb, read_rules):
     """spike_rules' body; `read_rules` (--spikeRpb): philox_read_rules' rules of the reads-per-barcode targets, whose table the caller
@@ -1991,6 +2030,9 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
     spikes = SpikeSet(variants, indels=indel_counters)
     spikes.rpb_flag = (rpb or {}).get("flag")          # (--spikePhaseRpb: the flag DsRule.flag names for the cells)
     rpb_flag = (rpb or {}).get("flag") or ("--spikeIndelRpb" if indel_counters else "--spikeRpb")
+    grid = rpb is not None and rpb.get("fracs") is not None      # (--spikeGrid: a read rule per pair (f, r), fractions outer)
+    cell_text = (lambda r: "fraction %g x target %g" % (read_rules[r].frac, read_rules[r].target)) if grid else \
+        (lambda r: "target %g" % rpb["targets"][r])
     P = params_list[0]
     rows = [[None] * len(variants) for _ in targets]
     psets = list(phase["sets"]) if phase is not None else []
@@ -2076,9 +2118,9 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
                                 if who is not None:
                                     rbits[(k, r)][1][t] = who[x]
                                 if second_rpb[(k, t, r)][0] != int(n_r[x]):
-                                    raise RuntimeError("%s: %s:%d at %g x target %g: the read selection keeps %d covering barcodes of "
+                                    raise RuntimeError("%s: %s:%d at %g x %s: the read selection keeps %d covering barcodes of "
                                                        "the run and %d of its spiked copy" % (rpb_flag, variants[k].chrom, variants[k].pos, target,
-                                                                                             rpb["targets"][r], second_rpb[(k, t, r)][0], int(n_r[x])))
+                                                                                             cell_text(r), second_rpb[(k, t, r)][0], int(n_r[x])))
                                 second_rpb[(k, t, r)][2] = int(car_r[x])
                         for f, frac in enumerate(fracs):
                             sel, sel_counts, d_orig = select_run(eng, spiked, A, lo, idents=idents, frac=frac, seed=seed)
@@ -2161,13 +2203,19 @@ def _spike_rules(*, path, fasta, variants, targets, params_list, seed, eng, nthr
     if rpb is not None:
         try:
             rthr = [r.thr for r in read_rules]
-            got = spike_rpb_counts(eng, spikes.lead_pos, covers, records, [int(seed) & 0xFFFFFFFFFFFFFFFF], [sv.threshold(t) for t in targets],
-                                   rthr, four=indel_counters)[:, 0]
+            if grid:
+                # (one call over the pairs (f, r): [V, 1, T, F, Rr, 5] -> [V, T, F x Rr, 5], the order of the read rules)
+                got = spike_grid_counts(eng, spikes.lead_pos, covers, records, [int(seed) & 0xFFFFFFFFFFFFFFFF], [sv.threshold(t) for t in targets],
+                                        [frac_threshold(f) for f in rpb["fracs"]], rpb["rep_thr"][:1])[:, 0]
+                got = got.reshape(got.shape[0], got.shape[1], -1, 5)
+            else:
+                got = spike_rpb_counts(eng, spikes.lead_pos, covers, records, [int(seed) & 0xFFFFFFFFFFFFFFFF], [sv.threshold(t) for t in targets],
+                                       rthr, four=indel_counters)[:, 0]
             for (k, t, r), mine in second_rpb.items():
                 if [int(got[k, t, r, c]) for c in (0, 1, 4)] != mine:
                     v = variants[k]
-                    raise RuntimeError("%s: %s:%d at %g x target %g: the counts call says (N, V0, V1) = %r, the selection of the "
-                                       "spiked copy %r" % (rpb_flag, v.chrom, v.pos, targets[t], rpb["targets"][r],
+                    raise RuntimeError("%s: %s:%d at %g x %s: the counts call says (N, V0, V1) = %r, the selection of the "
+                                       "spiked copy %r" % (rpb_flag, v.chrom, v.pos, targets[t], cell_text(r),
                                                            [int(got[k, t, r, c]) for c in (0, 1, 4)], mine))
         except BaseException:
             if keep is not None:
@@ -2889,6 +2937,61 @@ def spike_rpb_counts(eng, positions, covers, records, seeds, thresholds, read_th
                                                     d_out, ctypes.c_void_p(0)))
 
 
+def spike_grid_counts(eng, positions, covers, records, seeds, thresholds, frac_thresholds, read_thresholds) -> np.ndarray:
+    """smc_spike_grid_counts -> uint32 [V, R, T, F, Rr, 5] = (N', V0', S', READS', V1') of every variant, replicate and cell (spike
+    target x barcode fraction x reads-per-barcode target).  positions, covers, records, seeds, thresholds: spike_rpb_counts';
+    frac_thresholds: frac_threshold(f) per fraction; read_thresholds: uint64 [R, F, Rr], read_threshold(probKeep) of every replicate's
+    own (fraction, target) - grid_read_thresholds makes them."""
+    n_var = len(covers)
+    off = np.zeros(n_var + 1, np.uint32)
+    off[1:] = np.cumsum([len(c) for c in covers])
+    ident = np.concatenate([np.asarray(c, np.uint64) for c in covers]) if n_var else np.zeros(0, np.uint64)
+    rec_off, name, flag = _spike_rpb_flat(records, [len(c) for c in covers],
+                                          lambda v: "spike_grid_counts: variant %d: %d covering barcodes" % (v, len(covers[v])))
+    pos = np.array([int(p) & 0xFFFFFFFF for p in positions], np.uint32)
+    seeds = np.ascontiguousarray(seeds, np.uint64)
+    thr, bthr = np.ascontiguousarray(thresholds, np.uint64), np.ascontiguousarray(frac_thresholds, np.uint64)
+    rthr = np.ascontiguousarray(read_thresholds, np.uint64)
+    if rthr.ndim != 3 or rthr.shape[:2] != (len(seeds), len(bthr)):
+        raise ValueError("spike_grid_counts: read thresholds of shape %r for %d replicates x %d fractions" % (rthr.shape, len(seeds), len(bthr)))
+    n_rr = int(rthr.shape[2])
+    return _spike_counts_call(
+        eng, "smc_spike_grid_counts", [ident, off, rec_off, name, flag, pos, seeds, rthr.reshape(-1)],
+        (n_var, len(seeds), len(thr), len(bthr), n_rr, 5),
+        lambda d, d_out: eng.L.smc_spike_grid_counts(eng.ctx, d[0], d[1], off.ctypes.data, d[2], rec_off.ctypes.data, d[3], d[4], len(name),
+                                                     d[5], n_var, d[6], len(seeds), thr.ctypes.data, len(thr), bthr.ctypes.data, len(bthr),
+                                                     d[7], rthr.ctypes.data, n_rr, d_out, ctypes.c_void_p(0)))
+
+
+def grid_prob_keep(c, r: float):
+    """ds.reads.withinMT.py:58's probKeep at target r from the counters of the barcodes a fraction keeps (dict or sequence of one,
+    multi, multi_names), as philox_grid_rules computes it; None where no kept barcode has two or more names (it divides by zero)."""
+    one, multi, multi_names = (c["one"], c["multi"], c["multi_names"]) if isinstance(c, dict) else c
+    if multi_names == multi:
+        return None
+    return 1.0 * (float(r) - 1.0) * (one + multi) / (multi_names - multi)
+
+
+def grid_read_thresholds(groups: ReadGroups, seeds, fractions, rpb_targets, flag: str = "--spikeGrid"):
+    """(--spikeGrid) The read thresholds of every (replicate, fraction, target): ONE counts_frac_seeds launch gives the counters of the
+    barcodes each seed keeps at each fraction, probKeep and read_threshold follow on the host exactly as philox_grid_rules makes them
+    for one seed -> (uint64 [R, F, Rr] thresholds, float64 [R, F, Rr] probKeep).  ValueError: a (replicate, fraction) at which no kept
+    barcode has two or more read names - it names the replicate, its seed and the fraction."""
+    seeds = [int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]
+    c = groups.counts_frac_seeds(seeds, [frac_threshold(f) for f in fractions])
+    thr = np.zeros((len(seeds), len(fractions), len(rpb_targets)), np.uint64)
+    prob = np.zeros(thr.shape, np.float64)
+    for j, s in enumerate(seeds):
+        for k, f in enumerate(fractions):
+            for q, r in enumerate(rpb_targets):
+                p = grid_prob_keep(tuple(int(x) for x in c[j, k, 1:4]), r)
+                if p is None:
+                    raise ValueError("%s: replicate %d (seed %d), fraction %g: no barcode kept there has more than one read name, so "
+                                     "ds.reads.withinMT.py's probKeep (:58) is not defined (it divides by zero)" % (flag, j, s, f))
+                prob[j, k, q], thr[j, k, q] = p, read_threshold(p)
+    return thr, prob
+
+
 def _spike_joint_index(s, covers):
     """Phase set `s` -> (uint64 [n]: the identities of the barcodes that cover EVERY member, ascending; per member, in the set's order,
     int64 [n]: where each of them stands in covers[member])."""
@@ -3200,9 +3303,11 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
     address of its first keep mask - ReadGroups.masks with the copy's seed, one mask per target -, n_words: words per mask)): every
     copy is also selected per r by read name (select_run, level "read") and built; a cell's selections share one batch and one plan
     -> (the copies' rows, per cell the same), or NARROW.  With `indel` (--spikeIndelRpb) want_cells holds the cells' (N', V1') per
-    reads-per-barcode target, and `read_cells` their "targets" for the message."""
+    reads-per-barcode target, and `read_cells` their "labels" for the message.  With "want_cells" and no `indel` (--spikeGrid: a
+    cell per pair (f, r), the masks masks_grid's) every selection's (N', V1') is held against it the same way."""
     A, lo, B = run.A, run.lo, len(part_seeds)
-    if indel is not None:
+    grid_want = read_cells.get("want_cells") if read_cells and indel is None else None
+    if indel is not None or grid_want is not None:
         af_var, af_ins = af_run_variants([variants[k] for k in run.group], run.chrom, lo, fasta)
     flag = (read_cells.get("flag") or ("--spikeIndelRpb" if indel is not None else "--spikeRpb")) if read_cells else \
         "--spikeDepth" if cells else "--spikeReps"
@@ -3215,8 +3320,10 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
         barcode id of the selection -, key (variant, copy, read)."""
         for c, copy in enumerate(copies.runs):
             if read is not None:
-                picked = select_run(eng, copy, A, lo, d_mask=read_cells["masks"][c] + 4 * read_cells["n_words"] * read, level="read")
-                cell, what = read, " x target %g" % read_cells["targets"][read]
+                # (--spikeGrid: the batch's selections were made by one call; else one select_run per copy and target)
+                picked = sels.of[read][c] if sels is not None else \
+                    select_run(eng, copy, A, lo, d_mask=read_cells["masks"][c] + 4 * read_cells["n_words"] * read, level="read")
+                cell, what = read, " x " + read_cells["labels"][read]
             elif frac is None:
                 picked, cell, what = (copy, A, None), None, ""
             else:
@@ -3236,12 +3343,19 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
                 except BaseException:
                     kept.free()
                     raise
+            elif grid_want is not None and read is not None:
+                try:
+                    copies.check_carriers(c, kept.run, kept.counts, grid_want[read][c], af_var, af_ins, variants, flag, what)
+                except BaseException:
+                    kept.free()
+                    raise
             yield kept
 
     def batch_rows(Pb, frac, read=None):
         """kept_copies built into one batch and called with one plan at params `Pb`."""
         return _copy_rows(eng, run, variants, B, kept_copies(frac, read), Pb, bits, flag, fasta, max_depth, sampler, sampler_seed)
     cell_at = {frac: f for f, (frac, _) in enumerate(cells)}
+    sels = None
     try:
         copies.check_reads(var_at, want_reads, variants, "--spikeReps")      # (the message names --spikeReps whichever flag is in force)
         full = batch_rows(P, None)
@@ -3252,13 +3366,47 @@ def _spike_rep_call(eng, run: AfRun, svar, var_at, part_seeds, thr: int, want_re
             of_cell.append(batch_rows(Pc, frac))
             if of_cell[-1] == NARROW:
                 return NARROW
+        if read_cells and read_cells.get("copy_stride") is not None:
+            # (--spikeGrid: the B copies at all F x Rr pairs by ONE smc_select_alignments_reads_copies call and one download)
+            sels = select_copies_reads(eng, copies.runs, A, lo, read_cells["masks"][0], read_cells["n_words"], read_cells["copy_stride"],
+                                       len(read_cells["params"]))
         for r, Pc in enumerate(read_cells["params"] if read_cells else ()):
             of_cell.append(batch_rows(Pc, None, r))
             if of_cell[-1] == NARROW:
                 return NARROW
         return full, of_cell
     finally:
+        if sels is not None:
+            sels.free()
         copies.free()
+
+
+def _grid_seed_masks(eng, read_rules, seeds, rep_thr, p_idents, chrom, lo, nl):
+    """(--spikeGrid) The keep masks of every seed and pair (f, r) over a run's read-name identities in ONE device buffer - seed j's
+    len(read_rules) masks at j x len(read_rules) x n_words words, the layout smc_select_alignments_reads_copies takes for a batch of
+    consecutive seeds; one ReadGroups.masks_grid launch per seed, with that seed's own read thresholds rep_thr[j] ([F, Rr]).
+    -> (the buffer, words per mask); the caller frees the buffer."""
+    from .engine import DevBuf
+    groups, Q = read_rules[0].groups, len(read_rules)
+    n = len(p_idents)
+    n_words = (n + 31) // 32
+    d_id = DevBuf(eng, 8 * max(1, n) + 256).upload(np.ascontiguousarray(p_idents, np.uint64) if n else np.zeros(1, np.uint64))
+    buf = DevBuf(eng, 4 * max(1, n_words * Q * len(seeds)) + 256)
+    try:
+        for j, s in enumerate(seeds):
+            groups.masks_grid(d_id.data_ptr(), n, int(s), [r.bc_thr for r in read_rules], [int(t) for t in np.asarray(rep_thr[j]).reshape(-1)],
+                              buf.data_ptr() + 4 * n_words * Q * j)
+        st = groups.status()
+    except BaseException:
+        buf.free()
+        raise
+    finally:
+        d_id.free()
+    if st & RG_MISS:
+        buf.free()
+        raise bamio.BamError("--spikeGrid: the run %s:%d-%d has a read name the file-wide table does not hold (status %#x)"
+                             % (chrom, lo + 1, lo + nl, st))
+    return buf, n_words
 
 
 def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int, n_reps: int, eng, keep: dict, sampler: str = "reference",
@@ -3286,7 +3434,10 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
     (N, V1), and every cell's (N', V1') on its selection, must equal the counts calls'.
     `rpb` with `phase` (--spikePhaseRpb: phase["joint_records"] from the pre-pass): one smc_spike_phase_rpb_counts call with all R
     seeds gives "phase_rpb_counts", uint32 [G, R, T, Rr, 4]; per copy and cell the AND over a set's members of the selection's cover and
-    carrier bits must give its (N_ALL', V1_ALL') (_check_joint_bits)."""
+    carrier bits must give its (N_ALL', V1_ALL') (_check_joint_bits).
+    `rpb` with "fracs" (--spikeGrid): one smc_spike_grid_counts call with all R seeds and THEIR thresholds (rpb["rep_thr"]) gives
+    "rpb_counts", uint32 [V, R, T, F x Rr, 5]; the masks of replicate j are masks_grid's with its seed and its thresholds; every copy
+    is selected and built per pair (f, r), and each selection's (N', V1') must equal the counts call's."""
     import time
     from . import dsaf
     from .tools import spike_variants as sv
@@ -3319,9 +3470,16 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
                 phase_depth_counts = joint_counts(eng, lead, phase["joint"], seeds, thr, [frac_threshold(f) for f in depth["fracs"]])
         rpb_counts, read_rules = None, []
         if rpb is not None:
-            F = len(rpb["targets"])
+            grid = rpb.get("fracs") is not None
+            F = len(rpb["rules"]) // T                             # (the cells of one target: Rr, or with --spikeGrid F x Rr)
             read_rules = rpb["rules"][:F]
-            rpb_counts = spike_rpb_counts(eng, spikes.lead_pos, keep["covers"], keep["records"], seeds, thr, [r.thr for r in read_rules], four=four)
+            if grid:
+                # (--spikeGrid: every replicate's own thresholds, made by the pre-pass; [V, R, T, F, Rr, 5] -> [V, R, T, F x Rr, 5])
+                rpb_counts = spike_grid_counts(eng, spikes.lead_pos, keep["covers"], keep["records"], seeds, thr,
+                                               [frac_threshold(f) for f in rpb["fracs"]], rpb["rep_thr"])
+                rpb_counts = rpb_counts.reshape(rpb_counts.shape[:3] + (-1, 5))
+            else:
+                rpb_counts = spike_rpb_counts(eng, spikes.lead_pos, keep["covers"], keep["records"], seeds, thr, [r.thr for r in read_rules], four=four)
             if phase is not None and phase.get("joint_records"):
                 # (--spikePhaseRpb: one call with all R seeds over the (joint barcode, member) records of the pre-pass)
                 phase_rpb_counts = spike_phase_rpb_counts(eng, [spikes.lead_pos[s.members[0]] for s in phase["sets"]],
@@ -3340,11 +3498,16 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
                 times["decode again"] += time.perf_counter() - t0
             svar, sorder = spikes.chrom_variants(run.chrom, targets[0])
             var_at = [sorder.index(k) for k in run.group]
-            room, _ = _copy_room(run, svar, four)
+            # (--spikeGrid: a batch's copies are selected at all F x Rr pairs by one call - their selections live beside them)
+            room, _ = _copy_room(run, svar, four, F, True) if rpb is not None and grid else _copy_room(run, svar, four)
             t0 = time.perf_counter()
-            seed_masks = {}
+            seed_masks, grid_masks = {}, None
             try:
-                if rpb is not None:
+                if rpb is not None and grid:
+                    p_idents = pair_idents_or_refuse(run.bam, run.A, read_rules[0].flag, run.chrom, run.lo, run.nl)
+                    grid_masks, n_words = _grid_seed_masks(eng, read_rules, seeds, rpb["rep_thr"], p_idents, run.chrom, run.lo, run.nl)
+                    seed_masks = {j: (_BufView(grid_masks, 4 * n_words * F * j), n_words, None) for j in range(n_reps)}
+                elif rpb is not None:
                     # (the keep masks of every reads-per-barcode target, per seed: one launch each over the run's read-name identities)
                     p_idents = pair_idents_or_refuse(run.bam, run.A, read_rules[0].flag, run.chrom, run.lo, run.nl)
                     for j in range(n_reps):
@@ -3362,6 +3525,8 @@ def spike_replicates(path: str, fasta, variants, targets, params_list, seed: int
             finally:
                 for buf, _, _ in seed_masks.values():
                     buf.free()
+                if grid_masks is not None:
+                    grid_masks.free()
             times["calls"] += time.perf_counter() - t0
             run.free()
     finally:
@@ -3394,8 +3559,8 @@ def _spike_rep_targets(*, eng, run, svar, var_at, seeds, thr, counts, depth_coun
     """spike_replicates' calls for one kept run: per target as many replicates per _spike_rep_call as `room` allows; `rows` and `times`
     are filled.  seed_masks[j] (--spikeRpb): _run_read_masks' of replicate j."""
     T = len(params_list)
-    F = len(depth["fracs"]) if depth is not None else len(rpb["targets"]) if rpb is not None else 0
-    cell_counts = depth_counts if depth is not None else rpb_counts      # (the cells' [V, R, T, F or Rr, 5])
+    F = len(depth["fracs"]) if depth is not None else len(rpb["rules"]) // T if rpb is not None else 0
+    cell_counts = depth_counts if depth is not None else rpb_counts      # (the cells' [V, R, T, F or Rr, 5]; --spikeGrid: [V, R, T, F x Rr, 5])
     for t in range(T):
         P = params_list[t]
         cells = [(depth["fracs"][f], depth["params"][t * F + f]) for f in range(F)] if depth is not None else []
@@ -3413,7 +3578,14 @@ def _spike_rep_targets(*, eng, run, svar, var_at, seeds, thr, counts, depth_coun
             read_cells = None
             if rpb is not None:
                 read_cells = dict(params=rpb["params"][t * F:(t + 1) * F], masks=[seed_masks[j][0].data_ptr() for j in js],
-                                  n_words=seed_masks[js[0]][1], targets=list(rpb["targets"]), flag=rpb.get("flag"))
+                                  n_words=seed_masks[js[0]][1], flag=rpb.get("flag"),
+                                  labels=[("fraction %g x " % r.frac if r.grid else "") + "target %g" % r.target for r in rpb["rules"][:F]])
+                if rpb.get("fracs") is not None:
+                    # (--spikeGrid: every copy's cell is held against the counts call's (N', V1'), as the indel cells are)
+                    read_cells["want_cells"] = [[[(int(cell_counts[k, j, t, f, 0]), int(cell_counts[k, j, t, f, 4])) for k in run.group]
+                                                 for j in js] for f in range(F)]
+                    # (the masks of the batch's consecutive seeds stand at one stride: one selection call for all copies and pairs)
+                    read_cells["copy_stride"] = F * seed_masks[js[0]][1]
             def call(bits):
                 times["rewrites"] += 1                                 # (a call that answers NARROW has spiked its copies too)
                 return _spike_rep_call(*args, bits, cells, indel, read_cells)

@@ -325,21 +325,32 @@ def write_curve(out_prefix: str, variants, targets, entries, lods=None) -> None:
 
 # ---- --spikeDepth (and, with another axis, --spikeRpb)
 # the cells' second axis on the pages below: (the pages' infix, the axis column's name); the column's text is "%g" of the cell's value
+# (--spikeGrid: two columns, and a cell's value is the pair (f, r))
 DEPTH_AXIS = ("depth", "FRACTION")
 RPB_AXIS = ("rpb", "RPB")
+GRID_AXIS = ("grid", ("FRACTION", "RPB"))
+
+
+def _axis_columns(axis):
+    return axis[1] if isinstance(axis[1], tuple) else (axis[1],)
+
+
+def _axis_text(value):
+    """The axis columns' text of a cell: "%g" of its value, or of each number of a pair."""
+    return ["%g" % x for x in value] if isinstance(value, tuple) else ["%g" % value]
 
 
 def cell_detection_header(axis=DEPTH_AXIS):
-    return DETECTION_HEADER[:5] + (axis[1], "MTDEPTH") + DETECTION_HEADER[5:]
+    return DETECTION_HEADER[:5] + _axis_columns(axis) + ("MTDEPTH",) + DETECTION_HEADER[5:]
 
 
 def cell_replicates_header(axis=DEPTH_AXIS):
-    h = cell_detection_header(axis)
-    return h[:7] + ("REP", "SEED") + h[7:]
+    h, n = cell_detection_header(axis), 6 + len(_axis_columns(axis))
+    return h[:n] + ("REP", "SEED") + h[n:]
 
 
 def cell_sensitivity_header(axis=DEPTH_AXIS):
-    return SENSITIVITY_HEADER[:5] + (axis[1], "MTDEPTH") + SENSITIVITY_HEADER[5:] + ("N_MEAN",)
+    return SENSITIVITY_HEADER[:5] + _axis_columns(axis) + ("MTDEPTH",) + SENSITIVITY_HEADER[5:] + ("N_MEAN",)
 
 
 DEPTH_DETECTION_HEADER = cell_detection_header()
@@ -373,9 +384,9 @@ def depth_cells(args, spike_targets, flag: str = "spikeDepth"):
     return fr, [(k, t, f, max(1, int(py2_round(f * d))), "%s.dsMT%g" % (p, f)) for k, (t, d, p) in enumerate(spike_targets) for f in fr]
 
 
-def _cell_fields(line: str, frac: float, mt_depth: int):
+def _cell_fields(line: str, frac, mt_depth: int):
     f = line.split("\t")
-    return f[:5] + ["%g" % frac, "%d" % mt_depth] + f[5:]
+    return f[:5] + _axis_text(frac) + ["%d" % mt_depth] + f[5:]
 
 
 def depth_detection_line(v, target, frac, mt_depth, r, row, cut, lod=None) -> str:
@@ -386,7 +397,8 @@ def depth_detection_line(v, target, frac, mt_depth, r, row, cut, lod=None) -> st
 
 def depth_replicate_line(v, target, frac, mt_depth, rep: int, seed: int, r, row, cut) -> str:
     f = _cell_fields(detection_line(v, target, r, row, cut), frac, mt_depth)
-    return "\t".join(f[:7] + ["%d" % rep, "%d" % seed] + f[7:])
+    n = 6 + len(_axis_text(frac))
+    return "\t".join(f[:n] + ["%d" % rep, "%d" % seed] + f[n:])
 
 
 def _n_mean(per) -> float:
@@ -515,6 +527,76 @@ def _rpb_cells(text, spike_targets, flag: str):
         raise SystemExit("--%s: %d targets x %d reads-per-barcode targets = %d cells, at most %d" %
                          (flag, len(spike_targets), len(rs), len(spike_targets) * len(rs), MAX_CELLS))
     return rs, [(k, t, r, d, "%s.dsRpb%g" % (p, r)) for k, (t, d, p) in enumerate(spike_targets) for r in rs]
+
+
+# ---- --spikeGrid
+GRID_NOT_WITH = ("spikePhase", "spikeIndels", "spikeIndelReps", "spikeIndelDepth", "spikeIndelRpb", "spikeIndelPhase", "spikePhaseRpb")
+BUDGET_HEADER = ("CHROM", "POS", "REF", "ALT", "TARGET", "FRACTION", "RPB", "MTDEPTH", "KEPT_NAMES", "COST", "N_MEAN", "REPS", "CALLED", "RATE",
+                 "LO95", "HI95", "CHEAPEST95")
+
+
+def grid_cells(args, spike_targets):
+    """--spikeGrid -> (fractions, reads-per-barcode targets, [(target index, t, (f, r), mtDepth of the cell, output prefix)] for every
+    --spikeAF target t, --spikeDepth fraction f and --spikeRpb target r - targets outer, then fractions, then r), or (None, None, [])
+    without the switch.  A cell is called at depth_cells' mtDepth of (t, f) and at --rpb r.  SystemExit: without --spikeAF or one of
+    the two axis flags, beside a flag of GRID_NOT_WITH or a --spikeScan* flag (not built), what --spikeDepth and --spikeRpb refuse of
+    their lists, beyond MAX_CELLS cells."""
+    if not getattr(args, "spikeGrid", False):
+        return None, None, []
+    if not spike_targets:
+        raise SystemExit("--spikeGrid calls the --spikeAF spike-ins on the --spikeDepth x --spikeRpb grid: it needs --spikeAF")
+    for flag in ("spikeDepth", "spikeRpb"):
+        if getattr(args, flag, None) in (None, ""):
+            raise SystemExit("--spikeGrid calls every --spikeDepth fraction with every --spikeRpb target: it needs both --spikeDepth and "
+                             "--spikeRpb (--%s is missing)" % flag)
+    for flag in GRID_NOT_WITH + tuple(f for f in sorted(vars(args)) if f.startswith("spikeScan")):
+        if getattr(args, flag, None) not in (None, "", False):
+            raise SystemExit("--spikeGrid cannot be combined with --%s in one run (the combination is not built)" % flag)
+    fracs, depth = depth_cells(args, spike_targets)
+    rpbs, _ = _rpb_cells(args.spikeRpb, spike_targets, "spikeRpb")
+    if len(spike_targets) * len(fracs) * len(rpbs) > MAX_CELLS:
+        raise SystemExit("--spikeGrid: %d targets x %d fractions x %d reads-per-barcode targets = %d cells, at most %d" %
+                         (len(spike_targets), len(fracs), len(rpbs), len(spike_targets) * len(fracs) * len(rpbs), MAX_CELLS))
+    return fracs, rpbs, [(k, t, (f, r), d, "%s.dsRpb%g" % (p, r)) for k, t, f, d, p in depth for r in rpbs]
+
+
+def budget_order(costs):
+    """The budget page's order of a variant's cells at one target: by cost ascending, ties in the listed order -> indices."""
+    return sorted(range(len(costs)), key=lambda c: (costs[c], c))
+
+
+def budget_lines(v, target, cells, file_names: int, per_cell):
+    """The budget page's lines of variant `v` at `target`: cells[c] = ((f, r), mtDepth, kept names of the cell file-wide), per_cell[c]
+    the cell's replicates as sensitivity_line() takes them.  COST = kept names over the file's distinct read names; the lines by
+    COST ascending (ties in the listed order); CHEAPEST95 is 1 on the first line whose RATE is at least 0.95."""
+    costs = [float(kept) / file_names if file_names else 0.0 for _, _, kept in cells]
+    out, found = [], False
+    for c in budget_order(costs):
+        (f, r), depth, kept = cells[c]
+        per = per_cell[c]
+        n, called = len(per), _called(v, per_cell[c])
+        lo, hi = dsaf.wilson(called, n)
+        rate = float(called) / n
+        first = rate >= 0.95 and not found
+        found = found or first
+        out.append("\t".join([v.chrom, "%d" % v.pos, v.ref, v.alt, dsaf.target_text(target), "%g" % f, "%g" % r, "%d" % depth, "%d" % kept,
+                              dsaf.frac_text(costs[c]), dsaf.frac_text(_n_mean(per)), "%d" % n, "%d" % called, dsaf.frac_text(rate),
+                              dsaf.frac_text(lo), dsaf.frac_text(hi), "%d" % first]))
+    return out
+
+
+def write_budget(out_prefix: str, variants, cells, file_names: int, entries) -> None:
+    """<outPrefix>.spikeAF.grid.budget.txt: per listed variant and target a line per cell of that target, cheapest first.  `cells`:
+    per cell (target index, target, (f, r), mtDepth, output prefix, LODs or None, kept names) - the grid pages' tuples with the cell's
+    kept read names file-wide behind; entries[(v, cell)]: the replicates."""
+    with open(out_prefix + ".spikeAF.grid.budget.txt", "w") as fh:
+        fh.write("\t".join(BUDGET_HEADER) + "\n")
+        for i, v in enumerate(variants):
+            for k in dict.fromkeys(c[0] for c in cells):
+                mine = [c for c, cell in enumerate(cells) if cell[0] == k]
+                for line in budget_lines(v, cells[mine[0]][1], [(cells[c][2], cells[c][3], cells[c][6]) for c in mine], file_names,
+                                         [entries[(i, c)] for c in mine]):
+                    fh.write(line + "\n")
 
 
 # ---- --spikeIndelRpb

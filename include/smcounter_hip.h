@@ -1130,6 +1130,12 @@ int smc_build_max_depth(void);
  * returns that launch's mean duration over the last min(runs, slots) calls. */
 int smc_build_set_timing(smc_ctx* ctx, int slots);
 int smc_build_kernel_ms(smc_ctx* ctx, float* avg_ms, int32_t* n_samples);
+/* Checks and measurements: the rows the walks of the context's LAST smc_build_planes / _w16 call took from each sorted list (a list
+ * per tile of 64 loci; per segment of several tiles in a deep run built without per-tile lists), after that build has finished.
+ * A tile's list is its window of the file, loc[first].w0 .. loc[last].w1, without the alignments that end at or before the tile's
+ * first position where one workgroup sorts it (k_bp_sort_seg); every window row elsewhere.  -> *n_lists, and the first
+ * min(cap, *n_lists) counts in live[]. */
+int smc_build_live_rows(smc_ctx* ctx, uint32_t* live, int32_t cap, int32_t* n_lists);
 int smc_build_planes(smc_ctx* ctx, const smc_params* params, const smc_build_in* in, uint32_t slot_base, uint32_t umi_base,
                      uint32_t* words, uint32_t* meta, uint32_t* umi, uint32_t* frag, uint32_t* dist, uint32_t* umi_start,
                      uint32_t* u_gid, uint32_t* u_finc, smc_locus* loci, uint32_t* xlist, uint32_t xcap, uint32_t* counters, void* stream);

@@ -16,7 +16,7 @@ SYMBOLS = ("smc_abi_version", "smc_last_error", "smc_row_size", "smc_locus_size"
            "smc_read_groups_counts_frac", "smc_read_groups_masks_grid", "smc_read_groups_kept_grid", "smc_lod_table", "smc_fisher_tables", "smc_lfact_values", "smc_allele_carriers", "smc_af_rep_masks", "smc_af_rep_counts", "smc_af_depth_masks", "smc_af_depth_counts", "smc_spike_alleles", "smc_spike_indels", "smc_spike_alleles_reps", "smc_spike_rep_counts", "smc_spike_depth_counts", "smc_spike_phase_counts", "smc_spike_indels_reps", "smc_spike_indel_touch", "smc_spike_indel_counts", "smc_spike_indel_phase_counts", "smc_spike_read_bits", "smc_spike_rpb_counts", "smc_spike_indel_read_bits", "smc_spike_indel_rpb_counts", "smc_spike_phase_rpb_counts", "smc_read_groups_counts_frac_seeds", "smc_spike_grid_counts", "smc_scan_detect", "smc_scan_detect_keys", "smc_scan_filter", "smc_plan_destroy", "smc_plan_info",
            "smc_plan_run", "smc_plan_run_words", "smc_plan_run_words16", "smc_pack_words", "smc_plan_set_timing", "smc_plan_kernel_ms", "smc_call_batch_host", "smc_event_create", "smc_event_record",
            "smc_event_elapsed_ms", "smc_event_destroy", "smc_class_table", "smc_wire_row_size", "smc_pack_rows", "smc_unpack_rows",
-           "smc_build_planes", "smc_build_planes_w16", "smc_build_listed", "smc_build_max_depth", "smc_build_set_timing", "smc_build_kernel_ms", "smc_mem_alloc", "smc_mem_alloc_best", "smc_mem_write_probe", "smc_mem_free", "smc_mem_h2d", "smc_mem_d2h",
+           "smc_build_planes", "smc_build_planes_w16", "smc_build_listed", "smc_build_max_depth", "smc_build_set_timing", "smc_build_kernel_ms", "smc_build_live_rows", "smc_mem_alloc", "smc_mem_alloc_best", "smc_mem_write_probe", "smc_mem_free", "smc_mem_h2d", "smc_mem_d2h",
            "smc_mem_alloc_host", "smc_mem_free_host", "smc_pool_trim",
            "smc_device_sync")
 
@@ -151,6 +151,7 @@ def load(with_torch: bool = True):
     L.smc_build_max_depth.restype = ctypes.c_int
     L.smc_build_set_timing.argtypes = [vp, ctypes.c_int]
     L.smc_build_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)]
+    L.smc_build_live_rows.argtypes = [vp, vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
     L.smc_build_planes.argtypes = [vp, ctypes.POINTER(abi.SmcParams), ctypes.POINTER(abi.SmcBuildIn), ctypes.c_uint32,
                                    ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint32, vp, vp]
     L.smc_build_planes_w16.argtypes = [vp, ctypes.POINTER(abi.SmcParams), ctypes.POINTER(abi.SmcBuildIn), ctypes.c_uint32,

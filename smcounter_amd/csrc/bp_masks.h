@@ -18,3 +18,15 @@ BP_HD uint32_t bp_heads(uint32_t C, uint32_t S, bool carried) {
     if (carried) H &= ~G0;
     return H;
 }
+// ---- the live rows of a tile's list.  A tile's window of the file begins at the first alignment that ends behind its first
+// locus's position; every later, shorter alignment that ends at or before the TILE's first position is in the window too and covers
+// none of the tile's loci (its coverage mask is empty in both walks): the one-workgroup sort leaves such a row out of the list.
+// (tests/test_bp_live_rows_host.py compiles both helpers for the host.)
+BP_HD bool bp_row_dead(int end /* exclusive */, int p_first /* position of the tile's first locus */) { return end <= p_first; }
+// rows [j0, j1) of the q-th part of `part` rows of a list that starts at entry `off` and holds n_live rows (j0 >= j1: no row - a
+// part the host's upper bound w1 - w0 made room for and the live rows do not reach)
+BP_HD void bp_part_rows(uint32_t off, uint32_t n_live, uint32_t q, uint32_t part, uint32_t& j0, uint32_t& j1) {
+    const uint32_t end = off + n_live;
+    j0 = off + q * part;
+    j1 = end < j0 + part ? end : j0 + part;                                      // (a run's lists hold fewer than 2^31 entries: no wrap)
+}

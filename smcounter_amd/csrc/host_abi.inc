@@ -57,6 +57,8 @@ struct smc_ctx {
     int seg_next = 0;
     std::vector<hipEvent_t> bp_ev0, bp_ev1;   // optional timing of the plane-writing walk (smc_build_set_timing)
     int64_t bp_timed = 0;
+    size_t bp_nlive_off = 0;                  // the last build's per-list live row counts in bp_scratch, and how many lists (smc_build_live_rows)
+    int32_t bp_nlive_n = 0;
     // device blocks of destroyed plans, kept for the next plan (a plan per batch allocates and frees half a dozen lists: every
     // hipFree synchronises the device - 0.3 ms between two steps of the from_alignments run); size class -> blocks
     std::vector<std::pair<size_t, void*>> plan_pool;
@@ -2590,8 +2592,9 @@ static int build_planes_impl(smc_ctx* ctx, const smc_params* prm, const smc_buil
     // scratch, carved in 256-byte steps
     size_t off = 0;
     auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_seg = carve(sizeof(BpSeg) * (size_t)n_seg);
-    const size_t o_wseg = carve(tile_lists ? sizeof(BpSeg) * (size_t)n_tiles : 0), o_sorted2 = carve(tile_lists ? 4 * (size_t)ntot_w : 0),
+    // (behind each segment table its segments' live row counts, BpArgs.n_live: one copy brings both)
+    const size_t o_seg = carve((sizeof(BpSeg) + 4) * (size_t)n_seg);
+    const size_t o_wseg = carve(tile_lists ? (sizeof(BpSeg) + 4) * (size_t)n_tiles : 0), o_sorted2 = carve(tile_lists ? 4 * (size_t)ntot_w : 0),
                  o_tc = carve(tile_lists ? 4 * (size_t)n_tiles * (size_t)nch : 0);
     const size_t o_k0 = carve(8 * (size_t)ntot), o_k1 = carve(8 * (size_t)ntot), o_v0 = carve(4 * (size_t)ntot), o_v1 = carve(4 * (size_t)ntot);
     const size_t o_hist = carve(4 * 256 * (size_t)total_blk), o_dtot = carve(4 * 256 * (size_t)n_seg);
@@ -2605,6 +2608,7 @@ static int build_planes_impl(smc_ctx* ctx, const smc_params* prm, const smc_buil
     // (the list of general CIGARs in BP_NCUR parts: workgroup b appends to part b % BP_NCUR - at most its 256 alignments)
     const uint32_t glist_stride = 256u * ((n_rblk + BP_NCUR - 1) / BP_NCUR) + 64u;
     const size_t o_glist = carve(4 * (size_t)glist_stride * BP_NCUR), o_k8 = carve(8 * (size_t)std::max<int64_t>(1, n_aln));
+    const size_t o_kend = carve(4 * (size_t)std::max<int64_t>(1, n_aln));
     const size_t o_zero = off;                                                // [o_zero, o_zend): cleared before every run
     const size_t o_xcnt = carve(4 * (size_t)n_loci), o_tcnt = carve(4 * ((size_t)n_tiles + 1)), o_tcur = carve(4 * (size_t)n_tiles), o_xn = carve(4);
     const size_t o_zend = off;
@@ -2632,7 +2636,11 @@ static int build_planes_impl(smc_ctx* ctx, const smc_params* prm, const smc_buil
     A.words = words; A.w16 = w16 ? 1u : 0u; A.meta = meta; A.umi = umi; A.frag = frag; A.dist = dist; A.umi_start = umi_start; A.u_gid = u_gid; A.u_finc = u_finc;
     A.loci = loci;
     BpSeg* d_seg = (BpSeg*)(sc + o_seg);
-    A.seg = d_seg;
+    uint32_t* d_nlive = (uint32_t*)(d_seg + n_seg);
+    A.seg = d_seg; A.n_live = d_nlive;
+    // the sort of a one-tile segment drops the window rows that end before the tile (k_bp_sort_seg); SMC_BP_KEEP_DEAD_ROWS keeps
+    // them - the planes are the same bytes either way (a dead row's coverage mask is empty in both walks)
+    const bool live_rows = tiles_per_seg == 1 && !exp_env("SMC_BP_KEEP_DEAD_ROWS");
     A.cnt = (uint32_t*)(sc + o_cnt); A.cntp = (uint32_t*)(sc + o_cntp); A.pstate = (uint32_t*)(sc + o_pstate);
     A.xraw = (uint32_t*)(sc + o_xraw); A.xraw_cap = xraw_cap; A.xraw_n = (uint32_t*)(sc + o_xn);
     A.xcnt = (uint32_t*)(sc + o_xcnt); A.tcnt = (uint32_t*)(sc + o_tcnt); A.tcur = (uint32_t*)(sc + o_tcur); A.gidx = (uint32_t*)(sc + o_gidx); A.gidx2 = (uint32_t*)(sc + o_gidx2);
@@ -2645,15 +2653,16 @@ static int build_planes_impl(smc_ctx* ctx, const smc_params* prm, const smc_buil
         ctx->seg_next = (ctx->seg_next + 1) % 4;
         if (SG.used) HIPCHK(hipEventSynchronize(SG.ev));                      // (four builds ago: long done)
         const size_t n_stage = (size_t)n_seg + (tile_lists ? (size_t)n_tiles : 0);
-        if (SG.cap < sizeof(BpSeg) * n_stage) {
+        if (SG.cap < (sizeof(BpSeg) + 4) * n_stage) {
             if (SG.host) (void)hipHostFree(SG.host);
             SG.host = nullptr; SG.cap = 0;
-            const size_t want = std::max<size_t>(4096, sizeof(BpSeg) * n_stage * 2);
+            const size_t want = std::max<size_t>(4096, (sizeof(BpSeg) + 4) * n_stage * 2);
             HIPCHK(hipHostMalloc(&SG.host, want, hipHostMallocDefault));
             SG.cap = want;
         }
         if (!SG.ev) HIPCHK(hipEventCreateWithFlags(&SG.ev, hipEventDisableTiming));
         BpSeg* hs = (BpSeg*)SG.host;
+        uint32_t* hn = (uint32_t*)(hs + n_seg);                               // every row of the window: the sort writes the live count where it filters
         uint32_t off_run = 0, part_run = 0, blk_run = 0, cpart_run = 0;
         for (int sgi = 0; sgi < n_seg; ++sgi) {
             BpSeg S{};
@@ -2667,11 +2676,12 @@ static int build_planes_impl(smc_ctx* ctx, const smc_params* prm, const smc_buil
             S.n_blk = bp_seg_blocks(cnt, max_blk);
             S.off = off_run; S.part_base = part_run; S.blk_base = blk_run; S.cpart_base = cpart_run;
             off_run += cnt; part_run += S.ppt * S.n_tiles; blk_run += S.n_blk; cpart_run += S.cppt * S.n_tiles;
-            hs[(size_t)sgi] = S;
+            hs[(size_t)sgi] = S; hn[(size_t)sgi] = cnt;
         }
-        HIPCHK(hipMemcpyAsync(d_seg, hs, sizeof(BpSeg) * (size_t)n_seg, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_seg, hs, (sizeof(BpSeg) + 4) * (size_t)n_seg, hipMemcpyHostToDevice, st));
         if (tile_lists) {                                                     // the walks' table: a segment per tile, its own window and list
-            BpSeg* hw = hs + n_seg;
+            BpSeg* hw = (BpSeg*)(hn + n_seg);
+            uint32_t* hwn = (uint32_t*)(hw + n_tiles);                        // (a deep run's tile lists keep every window row)
             uint32_t woff = 0, wpart = 0, wcpart = 0;
             for (int t = 0; t < n_tiles; ++t) {
                 BpSeg S{};
@@ -2681,24 +2691,26 @@ static int build_planes_impl(smc_ctx* ctx, const smc_params* prm, const smc_buil
                 S.n_tiles = 1u; S.ppt = (cnt + BP_SUB - 1) / BP_SUB; S.cppt = (cnt + part - 1) / part; S.n_blk = 0u;
                 S.off = woff; S.part_base = wpart; S.blk_base = 0u; S.cpart_base = wcpart;
                 woff += cnt; wpart += S.ppt; wcpart += S.cppt;
-                hw[(size_t)t] = S;
+                hw[(size_t)t] = S; hwn[(size_t)t] = cnt;
             }
-            HIPCHK(hipMemcpyAsync(d_wseg, hw, sizeof(BpSeg) * (size_t)n_tiles, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_wseg, hw, (sizeof(BpSeg) + 4) * (size_t)n_tiles, hipMemcpyHostToDevice, st));
         }
         HIPCHK(hipEventRecord(SG.ev, st));
         SG.used = true;
     } else
-        hipLaunchKernelGGL(k_bp_segtab, dim3(1), dim3(1024), 0, st, in->loc, n_loci, n_seg, seg_loci, part, max_blk, d_seg);
+        hipLaunchKernelGGL(k_bp_segtab, dim3(1), dim3(1024), 0, st, in->loc, n_loci, n_seg, seg_loci, part, max_blk, d_seg, d_nlive);
     HIPCHK(hipGetLastError());
     const bool raw = meta || umi || frag || dist;
     BpRow* d_rows = (BpRow*)(sc + o_rows);
     uint8_t* d_lin = (uint8_t*)(sc + o_lin);
     uint2* d_k8 = (uint2*)(sc + o_k8);
+    int32_t* d_kend = (int32_t*)(sc + o_kend);
+    uint32_t* const sort_nlive = live_rows ? d_nlive : nullptr;
     uint32_t* d_bsum = (uint32_t*)(sc + o_bsum);
     uint32_t* d_glist = (uint32_t*)(sc + o_glist);
     if (total_parts) {      // the row records first: they do not depend on the order, and leave the sort its keys as a compact array
         hipLaunchKernelGGL(k_bp_zero_words, dim3(8), dim3(256), 0, st, d_bsum, 32u * BP_NCUR);   // (its cursors: pool pairs handed out, general CIGARs listed)
-        hipLaunchKernelGGL(k_bp_rows_write, dim3(n_rblk), dim3(256), 0, st, A, (uint32_t)n_aln, d_bsum, d_glist, glist_stride, d_rows, (uint32_t)lin_cap, raw ? 1 : 0, d_k8,
+        hipLaunchKernelGGL(k_bp_rows_write, dim3(n_rblk), dim3(256), 0, st, A, (uint32_t)n_aln, d_bsum, d_glist, glist_stride, d_rows, (uint32_t)lin_cap, raw ? 1 : 0, d_k8, d_kend,
                            (uint32_t*)(sc + o_zero), (uint32_t)((o_zend - o_zero) / 4), counters);
     }
     unsigned long long* kb[2] = {(unsigned long long*)(sc + o_k0), (unsigned long long*)(sc + o_k1)};
@@ -2718,10 +2730,10 @@ static int build_planes_impl(smc_ctx* ctx, const smc_params* prm, const smc_buil
         for (int s = 0; s < n_seg; ++s) any_le |= seg_cnt[(size_t)s] > 0 && seg_cnt[(size_t)s] <= BP_SORT_LDS_MAX;
         if (any_le || !big)
             hipLaunchKernelGGL((k_bp_sort_seg<BP_SORT_REG, BP_SORT_WAVES_SMALL, false>), dim3((unsigned)n_seg), dim3(64 * BP_SORT_WAVES_SMALL), 0, st, d_seg, d_k8, pair_bits, passes, kb[0], kb[1], vb[0], vb[1],
-                               0u, big ? (uint32_t)BP_SORT_LDS_MAX : (uint32_t)BP_LSORT_MAX);
+                               0u, big ? (uint32_t)BP_SORT_LDS_MAX : (uint32_t)BP_LSORT_MAX, d_kend, in->start0, sort_nlive);
         if (big)
             hipLaunchKernelGGL((k_bp_sort_seg<BP_SORT_REG_BIG, BP_SORT_WAVES, true>), dim3((unsigned)n_seg), dim3(64 * BP_SORT_WAVES), 0, st, d_seg, d_k8, pair_bits, passes, kb[0], kb[1], vb[0], vb[1],
-                               (uint32_t)BP_SORT_LDS_MAX, (uint32_t)BP_LSORT_MAX);
+                               (uint32_t)BP_SORT_LDS_MAX, (uint32_t)BP_LSORT_MAX, d_kend, in->start0, sort_nlive);
     }
     if (total_blk) {
         for (int ps = 0; ps < passes; ++ps) {
@@ -2742,7 +2754,7 @@ static int build_planes_impl(smc_ctx* ctx, const smc_params* prm, const smc_buil
         const unsigned tgrid = (unsigned)((size_t)n_tiles * (size_t)nch);
         hipLaunchKernelGGL(k_bp_tile_count, dim3(tgrid), dim3(256), 0, st, d_seg, tiles_per_seg, d_wseg, n_tiles, nch, A.sorted, d_tc);
         hipLaunchKernelGGL(k_bp_tile_scatter, dim3(tgrid), dim3(256), 0, st, d_seg, tiles_per_seg, d_wseg, n_tiles, nch, A.sorted, d_tc, d_sorted2);
-        A.sorted = d_sorted2; A.seg = d_wseg; A.n_seg = n_tiles; A.seg_tiles = 1;
+        A.sorted = d_sorted2; A.seg = d_wseg; A.n_live = (const uint32_t*)(d_wseg + n_tiles); A.n_seg = n_tiles; A.seg_tiles = 1;
     }
     if (total_parts) {
         int64_t lin_grid = 2048;                                              // (workgroups of 16 teams of 16 lanes, a team per general CIGAR at a time)
@@ -2769,6 +2781,7 @@ static int build_planes_impl(smc_ctx* ctx, const smc_params* prm, const smc_buil
         hipLaunchKernelGGL(k_bp_xfix, dim3((unsigned)n_tiles), dim3(64 * BP_XF_WAVES), 0, st, A);
     }
     HIPCHK(hipGetLastError());
+    ctx->bp_nlive_off = (size_t)((const char*)A.n_live - sc); ctx->bp_nlive_n = A.n_seg;
     if (!ctx->bp_done_ev) HIPCHK(hipEventCreateWithFlags(&ctx->bp_done_ev, hipEventDisableTiming));
     HIPCHK(hipEventRecord(ctx->bp_done_ev, st));
     return SMC_OK;
@@ -2849,6 +2862,17 @@ int smc_build_listed(smc_ctx* ctx, const smc_params* prm, const smc_listed_copy*
     HIPCHK(hipGetLastError());
     if (!ctx->bl_done_ev) HIPCHK(hipEventCreateWithFlags(&ctx->bl_done_ev, hipEventDisableTiming));
     HIPCHK(hipEventRecord(ctx->bl_done_ev, st));
+    return SMC_OK;
+}
+
+int smc_build_live_rows(smc_ctx* ctx, uint32_t* live, int32_t cap, int32_t* n_lists) {
+    if (!ctx || !n_lists || cap < 0 || (cap > 0 && !live)) return fail(SMC_E_ARG, "smc_build_live_rows: bad argument");
+    if (!ctx->bp_scratch || !ctx->bp_done_ev || ctx->bp_nlive_n <= 0) return fail(SMC_E_ARG, "smc_build_live_rows: no build on this context yet");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipEventSynchronize(ctx->bp_done_ev));
+    *n_lists = ctx->bp_nlive_n;
+    const int32_t n = std::min(cap, ctx->bp_nlive_n);
+    if (n > 0) HIPCHK(hipMemcpy(live, (const char*)ctx->bp_scratch + ctx->bp_nlive_off, 4 * (size_t)n, hipMemcpyDeviceToHost));
     return SMC_OK;
 }
 

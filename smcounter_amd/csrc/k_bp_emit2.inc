@@ -118,7 +118,8 @@ __global__ __launch_bounds__(256) void k_bp_rows_write(BpArgs A, uint32_t n_aln,
                                                        region of the second pool handed out, word 2 general CIGARs in its part of the list; zero before the
                                                        launch */, uint32_t* __restrict__ glist, uint32_t glist_stride,
                                                        BpRow* __restrict__ rows, uint32_t lin_cap, int raw, uint2* __restrict__ k8,
-                                                       uint32_t* __restrict__ zero, uint32_t zero_words, uint32_t* __restrict__ counters) {
+                                                       int32_t* __restrict__ k_end /* the alignment's end position, contiguous like k8: the sort drops
+                                                       the rows that end before its tile by it */, uint32_t* __restrict__ zero, uint32_t zero_words, uint32_t* __restrict__ counters) {
     // Round 6: ONE launch where there were three (k_bp_rows_need -> k_bp_scan -> this kernel: each alignment's record and CIGAR read
     // twice, a one-workgroup prefix between them).  Where a general CIGAR's copy lies in the second pool and where it stands in the
     // list of k_bp_lin need not follow the file's order: a workgroup takes the pairs its alignments need and its places in the list
@@ -189,6 +190,7 @@ __global__ __launch_bounds__(256) void k_bp_rows_write(BpArgs A, uint32_t n_aln,
         R.wbase = simple ? kseq + (aux & 0xFFFFu) - (uint32_t)kpos : off - (uint32_t)kpos;
         R.bc = rec[7]; R.pair = rec[8];
         k8[a] = make_uint2(R.bc, R.pair);                                         // (what the sort reads: its keys, contiguous)
+        k_end[a] = kend;
         uint4* o = (uint4*)(rows + a);
         o[0] = make_uint4((uint32_t)R.pos, R.len, R.wbase, R.hi);
         o[1] = make_uint4((uint32_t)R.cA, (uint32_t)R.cP, R.bc, R.pair);

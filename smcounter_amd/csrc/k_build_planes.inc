@@ -90,6 +90,8 @@ struct BpArgs {
     uint32_t *meta, *umi, *frag, *dist, *umi_start, *u_gid, *u_finc;   // meta, umi, frag, dist: the raw-field planes (optional: checks)
     smc_locus* loci;
     const BpSeg* seg;
+    const uint32_t* n_live;                               // [segment of `seg`]: entries of its sorted list - w1 - w0, or fewer where the sort has dropped
+                                                          // the rows that end before the tile (k_bp_sort_seg); the walks stop there (bp_wave)
     const uint32_t* sorted;                               // alignment indices, segment by segment, each in (barcode, fragment, file) order
     uint32_t* cnt;                                        // [wavefront of k_bp_count][3][64]: reads / fragment heads / barcode heads per locus in its A.part rows
     uint32_t* cntp;                                       // [wavefront of BP_SUB rows][64]: the same three counts of that stretch alone, a byte each
@@ -111,6 +113,8 @@ __device__ __forceinline__ void bp_patch_allele(const BpArgs& A, uint32_t sp, ui
         *b = (uint8_t)((*b & 0xF0u) | id);
     } else ((uint8_t*)A.words)[4ull * sp] = (uint8_t)id;
 }
+#include "bp_masks.h"   // bp_heads: the rows that start a run at a locus; bp_row_dead / bp_part_rows: the live rows of a tile's list (plain C++:
+                        // also compiled and tested on the host)
 __device__ __forceinline__ uint32_t bp_lanes_below(unsigned long long m) {
     return (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
@@ -168,7 +172,7 @@ __host__ __device__ static inline uint32_t bp_seg_blocks(uint32_t cnt, uint32_t 
     return t < max_blk ? t : max_blk;
 }
 __global__ __launch_bounds__(1024) void k_bp_segtab(const smc_dev_locus* __restrict__ loc, int n_loci, int n_seg, int seg_loci, uint32_t part, uint32_t max_blk,
-                                                    BpSeg* __restrict__ seg) {
+                                                    BpSeg* __restrict__ seg, uint32_t* __restrict__ n_live) {
     __shared__ uint32_t ws[4][16];
     __shared__ uint32_t carry[4];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -205,7 +209,7 @@ __global__ __launch_bounds__(1024) void k_bp_segtab(const smc_dev_locus* __restr
             for (int w = 0; w < wid; ++w) pre += ws[c][w];
             ex[c] += pre;
         }
-        if (s < n_seg) { S.off = ex[0]; S.part_base = ex[1]; S.blk_base = ex[2]; S.cpart_base = ex[3]; seg[s] = S; }
+        if (s < n_seg) { S.off = ex[0]; S.part_base = ex[1]; S.blk_base = ex[2]; S.cpart_base = ex[3]; seg[s] = S; n_live[s] = v[0]; }   // (every row, until the sort says otherwise)
         __syncthreads();
         if (tid < 4) { uint32_t t = 0; for (int w = 0; w < 16; ++w) t += ws[tid][w]; carry[tid] += t; }
         __syncthreads();
@@ -371,7 +375,14 @@ struct BpReg16 {
 };
 template <int REG /* entries per thread of the register + LDS path: BP_SORT_REG or BP_SORT_REG_BIG */, int WAVES /* wavefronts of the workgroup */, bool BIG>
 __global__ __launch_bounds__(64 * WAVES) void k_bp_sort_seg(const BpSeg* __restrict__ seg, const uint2* __restrict__ k8 /* (barcode, pair) per alignment */, int pair_bits, int passes,
-                                                      unsigned long long* k0, unsigned long long* k1, uint32_t* v0, uint32_t* v1, uint32_t only_above, uint32_t only_upto) {
+                                                      unsigned long long* k0, unsigned long long* k1, uint32_t* v0, uint32_t* v1, uint32_t only_above, uint32_t only_upto,
+                                                      const int32_t* __restrict__ kend /* end position per alignment, beside k8 */, int start0,
+                                                      uint32_t* __restrict__ n_live /* nullptr: every window row stays (segments of several tiles, or the switch) */) {
+    // The live rows (a segment that is ONE tile: n_live given).  An entry whose alignment ends at or before the tile's first position
+    // (bp_row_dead) is handled like the positions behind e1 of a partial last iteration from the start: not in the key range, no digit
+    // count, no rank, not written.  The first pass therefore leaves the nl live entries at [0, nl) in their old relative order - the
+    // sort stays stable -, the later passes run on those alone, and n_live[segment] = nl is where the walks end the list.  A segment
+    // this kernel returns early on keeps the full count the segment table came with.
     constexpr int LDS_MAX = 64 * WAVES * REG;
     if (!BIG && (seg[blockIdx.x].w1 - seg[blockIdx.x].w0) > only_upto) return;
     __shared__ uint32_t whist[WAVES][256];
@@ -382,26 +393,65 @@ __global__ __launch_bounds__(64 * WAVES) void k_bp_sort_seg(const BpSeg* __restr
     if (n == 0u || n > BP_LSORT_MAX || (BIG ? n <= only_above : false)) return;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const uint32_t chunk = ((n + (uint32_t)WAVES - 1u) / (uint32_t)WAVES + 63u) & ~63u;
-    const uint32_t e0 = min(n, (uint32_t)wid * chunk), e1 = min(n, e0 + chunk);
+    uint32_t e0 = min(n, (uint32_t)wid * chunk), e1 = min(n, e0 + chunk);       // the wavefront's entries: of the window in the first pass, of the live rows after it
     unsigned long long* kb[2] = {k0 + S.off, k1 + S.off};
     uint32_t* vb[2] = {v0 + S.off, v1 + S.off};
-    __shared__ uint32_t rng[4];                                                 // smallest / largest barcode id, smallest / largest pair id
-    if (tid == 0) { rng[0] = 0xFFFFFFFFu; rng[1] = 0u; rng[2] = 0xFFFFFFFFu; rng[3] = 0u; }
+    const bool filter = n_live != nullptr;                                      // (wave-uniform: a kernel argument)
+    const int p_first = start0 + (int)blockIdx.x * BP_TILE;                     // (filter: the segment is tile blockIdx.x)
+    auto live = [&](uint32_t e) -> bool { return !filter || !bp_row_dead(kend[S.w0 + e], p_first); };   // e: an entry of the window
+    __shared__ uint32_t rng[5];                                                 // smallest / largest barcode id, smallest / largest pair id, live rows
+    if (tid == 0) { rng[0] = 0xFFFFFFFFu; rng[1] = 0u; rng[2] = 0xFFFFFFFFu; rng[3] = 0u; rng[4] = 0u; }
     __syncthreads();
+    // (the register + LDS path below takes a wavefront's whole share in REG entries per lane: its keys and end positions are then
+    // fetched ONCE, here, every load asked for before the first is waited for - the index of a lane behind e1 is clamped, so no load
+    // stands behind a branch - and stay in the registers the path sorts them in)
+    const bool in_regs = n <= (uint32_t)LDS_MAX && chunk <= 64u * REG;           // (wave-uniform)
+    BpReg16 key, val;       // (REG <= 16 registers each; until the ranges are known: barcode and pair id as fetched)
+    uint32_t vm = 0u;       // bit it: the thread's entry `it` takes part in the pass (first pass: in the window and live; then: below f1)
+#pragma unroll
+    for (int it = 0; it < 16; ++it) { key.at(it) = 0u; val.at(it) = 0u; }
     {
-        uint32_t b_lo = 0xFFFFFFFFu, b_hi = 0u, p_lo = 0xFFFFFFFFu, p_hi = 0u;
-        for (uint32_t e = e0 + (uint32_t)lane; e < e1; e += 64u) {
+        uint32_t b_lo = 0xFFFFFFFFu, b_hi = 0u, p_lo = 0xFFFFFFFFu, p_hi = 0u, nlv = 0u;
+        if (in_regs) {
+            if (e0 < e1) {
+                int ke[REG];
+#pragma unroll
+                for (int it = 0; it < REG; ++it) {
+                    const uint32_t a = S.w0 + min(e0 + 64u * (uint32_t)it + (uint32_t)lane, e1 - 1u);
+                    const uint2 kv = k8[a];
+                    key.at(it) = kv.x; val.at(it) = kv.y;
+                    ke[it] = filter ? kend[a] : 0x7FFFFFFF;
+                }
+#pragma unroll
+                for (int it = 0; it < REG; ++it) {
+                    const bool ok = e0 + 64u * (uint32_t)it + (uint32_t)lane < e1 && !bp_row_dead(ke[it], p_first);
+                    vm |= ok ? 1u << it : 0u;
+                    b_lo = min(b_lo, ok ? key.at(it) : 0xFFFFFFFFu); b_hi = max(b_hi, ok ? key.at(it) : 0u);
+                    p_lo = min(p_lo, ok ? val.at(it) : 0xFFFFFFFFu); p_hi = max(p_hi, ok ? val.at(it) : 0u);
+                }
+                nlv = (uint32_t)__popc(vm);
+            }
+        } else for (uint32_t e = e0 + (uint32_t)lane; e < e1; e += 64u) {
             const uint2 kv = k8[S.w0 + e];
+            if (!live(e)) continue;
             const uint32_t b = kv.x, q = kv.y;
             b_lo = min(b_lo, b); b_hi = max(b_hi, b); p_lo = min(p_lo, q); p_hi = max(p_hi, q);
+            ++nlv;
         }
         for (int o = 32; o; o >>= 1) {
             b_lo = min(b_lo, (uint32_t)__shfl_xor((int)b_lo, o)); b_hi = max(b_hi, (uint32_t)__shfl_xor((int)b_hi, o));
             p_lo = min(p_lo, (uint32_t)__shfl_xor((int)p_lo, o)); p_hi = max(p_hi, (uint32_t)__shfl_xor((int)p_hi, o));
+            nlv += (uint32_t)__shfl_xor((int)nlv, o);
         }
-        if (lane == 0 && e0 < e1) { atomicMin(&rng[0], b_lo); atomicMax(&rng[1], b_hi); atomicMin(&rng[2], p_lo); atomicMax(&rng[3], p_hi); }
+        if (lane == 0 && nlv) { atomicMin(&rng[0], b_lo); atomicMax(&rng[1], b_hi); atomicMin(&rng[2], p_lo); atomicMax(&rng[3], p_hi); atomicAdd(&rng[4], nlv); }
     }
     __syncthreads();
+    const uint32_t nl = rng[4];                                                 // (= n without the filter)
+    if (filter && tid == 0) n_live[blockIdx.x] = nl;
+    if (nl == 0u) return;                                                       // (every row of the window ends before the tile)
+    // the wavefronts' shares of the live rows, once the first pass has put them at [0, nl)
+    const uint32_t chunk2 = ((nl + (uint32_t)WAVES - 1u) / (uint32_t)WAVES + 63u) & ~63u;
+    const uint32_t f0 = min(nl, (uint32_t)wid * chunk2), f1 = min(nl, f0 + chunk2);
     const uint32_t bc_min = rng[0], pair_min = rng[2];
     const int pb = 32 - __builtin_clz((rng[3] - pair_min) | 1u), bb = 32 - __builtin_clz((rng[1] - bc_min) | 1u);
     int my_passes = (pb + bb + 7) / 8;
@@ -410,22 +460,17 @@ __global__ __launch_bounds__(64 * WAVES) void k_bp_sort_seg(const BpSeg* __restr
     // ---- a segment of up to BP_SORT_LDS_MAX entries with keys of up to 32 bits (a tile of a panel at 3000x: 4,500 entries, 21 bits):
     // every thread keeps its (up to five) entries in registers from pass to pass and the workgroup exchanges them through LDS -
     // no trip through global memory between passes, only the last pass's alignment indices leave
-    if (n <= (uint32_t)LDS_MAX && pb + bb <= 32 && chunk <= 64u * REG) {
+    if (in_regs && pb + bb <= 32) {
         // (an entry's value on its way through LDS is its index in the segment's window, 16 bits: with 32-bit values the 6-entry
         // instantiation claimed 68 KB and ONE workgroup ran per CU - 15 wavefronts resident on average by the counters)
         __shared__ uint32_t lk[LDS_MAX];
         __shared__ uint16_t lv[LDS_MAX];
         static_assert(LDS_MAX <= 65536, "lv holds window indices in 16 bits");
-        BpReg16 key, val;   // (REG <= 16 registers each)
 #pragma unroll
-        for (int it = 0; it < REG; ++it) {
-            const uint32_t e = e0 + 64u * (uint32_t)it + (uint32_t)lane;
-            key.at(it) = 0u; val.at(it) = 0u;
-            if (e < e1) {
-                val.at(it) = e;
-                const uint2 kv = k8[S.w0 + e];
-                key.at(it) = (kv.x - bc_min) << pb | (kv.y - pair_min);
-            }
+        for (int it = 0; it < REG; ++it) {                                      // (barcode, pair) as fetched -> the narrowed key; the value: the entry's index in the window
+            const bool ok = (vm >> it) & 1u;
+            key.at(it) = ok ? (key.at(it) - bc_min) << pb | (val.at(it) - pair_min) : 0u;
+            val.at(it) = ok ? e0 + 64u * (uint32_t)it + (uint32_t)lane : 0u;
         }
         // (where the walks read the sorted list.  Typed as global: picked from an array of two pointers it is a generic one to the
         // compiler, its stores flat_ ones - and a flat store also counts as an LDS operation in flight, so every wait for the
@@ -443,7 +488,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_bp_sort_seg(const BpSeg* __restr
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int it = 0; it < REG; ++it)
-                if (e0 + 64u * (uint32_t)it + (uint32_t)lane < e1) atomicAdd(&whist[wid][(key.at(it) >> shift) & dmask], 1u);
+                if ((vm >> it) & 1u) atomicAdd(&whist[wid][(key.at(it) >> shift) & dmask], 1u);
             __syncthreads();
             if (tid < 256) {
                 uint32_t run = 0;
@@ -466,7 +511,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_bp_sort_seg(const BpSeg* __restr
 #pragma unroll
             for (int it = 0; it < REG; ++it) {                          // (in entry order: the sort is stable)
                 if (e0 + 64u * (uint32_t)it >= e1) break;                       // (wave-uniform)
-                const bool valid = e0 + 64u * (uint32_t)it + (uint32_t)lane < e1;
+                const bool valid = (vm >> it) & 1u;
                 const uint32_t dgt = valid ? (key.at(it) >> shift) & dmask : 0u;
                 uint32_t rank, np;
                 bp_match(dgt, valid, dbits, rank, np);
@@ -482,10 +527,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_bp_sort_seg(const BpSeg* __restr
             }
             if (last) break;
             __syncthreads();
+            e0 = f0; e1 = f1; vm = 0u;                                          // (the live rows, dealt to the wavefronts again)
 #pragma unroll
             for (int it = 0; it < REG; ++it) {
                 const uint32_t e = e0 + 64u * (uint32_t)it + (uint32_t)lane;
-                if (e < e1) { key.at(it) = lk[e]; val.at(it) = lv[e]; }
+                if (e < e1) { vm |= 1u << it; key.at(it) = lk[e]; val.at(it) = lv[e]; }
             }
             __syncthreads();
         }
@@ -498,20 +544,21 @@ __global__ __launch_bounds__(64 * WAVES) void k_bp_sort_seg(const BpSeg* __restr
         const uint32_t* vin = vb[ps & 1];
         unsigned long long* kout = kb[(ps & 1) ^ 1];
         uint32_t* vout = vb[(ps & 1) ^ 1];
-        auto fetch = [&](uint32_t e, unsigned long long& key, uint32_t& val) {
+        auto fetch = [&](uint32_t e, unsigned long long& key, uint32_t& val) -> bool {   // -> the entry takes part (first pass: it is live)
             if (ps == 0) {
+                if (!live(e)) return false;
                 val = S.w0 + e;
                 const uint2 kv = k8[val];
                 key = ((unsigned long long)(kv.x - bc_min) << pb) | (unsigned long long)(kv.y - pair_min);
             } else { key = kin[e]; val = vin[e]; }
+            return true;
         };
 #pragma unroll
         for (int k = 0; k < 4; ++k) whist[wid][lane + 64 * k] = 0u;
         __builtin_amdgcn_wave_barrier();
         for (uint32_t e = e0 + (uint32_t)lane; e < e1; e += 64u) {
-            unsigned long long key; uint32_t val;
-            fetch(e, key, val);
-            atomicAdd(&whist[wid][(uint32_t)(key >> shift) & 255u], 1u);
+            unsigned long long key = 0; uint32_t val = 0;
+            if (fetch(e, key, val)) atomicAdd(&whist[wid][(uint32_t)(key >> shift) & 255u], 1u);
         }
         __syncthreads();
         if (tid < 256) {
@@ -534,10 +581,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_bp_sort_seg(const BpSeg* __restr
         __syncthreads();
         for (uint32_t eb = e0; eb < e1; eb += 64u) {
             const uint32_t e = eb + (uint32_t)lane;
-            const bool valid = e < e1;
+            bool valid = e < e1;
             unsigned long long key = 0; uint32_t val = 0;
-            if (valid) fetch(e, key, val);
-            const uint32_t dgt = (uint32_t)(key >> shift) & 255u;
+            if (valid) valid = fetch(e, key, val);
+            const uint32_t dgt = valid ? (uint32_t)(key >> shift) & 255u : 0u;
             uint32_t rank, np;
             bp_match(dgt, valid, 8, rank, np);
             const uint32_t wo = valid ? whist[wid][dgt] : 0u;
@@ -547,6 +594,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_bp_sort_seg(const BpSeg* __restr
             if (valid) { const uint32_t d = dbase[dgt] + wo + rank; kout[d] = key; vout[d] = val; }
         }
         __syncthreads();                                                        // (stores drained: the next pass reads them)
+        e0 = f0; e1 = f1;                                                       // (the live rows, dealt to the wavefronts again)
     }
 }
 
@@ -571,9 +619,8 @@ __device__ __forceinline__ BpWave bp_wave(const BpArgs& A, int lane, uint32_t w)
     W.p = A.start0 + W.l; W.p_first = A.start0 + l_first; W.p_last = A.start0 + l_last;
     W.a_lo = A.loc[l_first].w0; W.a_hi = A.loc[l_last].w1;                        // the tile's window of the file
     W.seg_off = SG.off;
-    const uint32_t seg_end = SG.off + (SG.w1 - SG.w0);
-    W.j0 = SG.off + q * part;
-    W.j1 = min(seg_end, W.j0 + part);
+    // (the list's end is its LIVE end - grids, ppt and cppt are the host's upper bounds from w1 - w0: a wavefront behind it has j0 >= j1)
+    bp_part_rows(SG.off, A.n_live[s], q, part, W.j0, W.j1);
     W.sub0 = SG.part_base + tis * SG.ppt + q * (part / (uint32_t)BP_SUB);        // the first BP_SUB-row wavefront of this one's rows
     {   // (the walk that writes) which of k_bp_count's wavefronts counted this stretch, and how many stretches of that one lie before it
         const uint32_t per = (uint32_t)A.part / (uint32_t)BP_SUB;
@@ -611,7 +658,6 @@ __device__ __forceinline__ uint32_t bp_scan_xor(uint32_t v) {                   
     v ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);     // row_bcast:31 into rows 2 and 3
     return v;
 }
-#include "bp_masks.h"   // bp_heads: the rows that start a run at a locus (plain C++: also compiled and tested on the host)
 #define BP_MASK_LDS (66 + 32 + 32)   // words: the start / end marks per tile position (+ the one behind the tile), barcode and pair of each row
 struct BpCols { uint32_t C, NF, NB; };
 // the batch's rows (lanes with in_b: row rr, tile-relative span [lo, hi), barcode, pair) -> the lane's columns; advances last_bc / last_pair

@@ -990,6 +990,23 @@ typedef struct smc_scan_verdict {      /* 16 bytes */
 int smc_scan_detect(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64_t n_loci, const smc_scan_locus* d_listed,
                     const smc_scan_locus* listed_host, int32_t n_listed, double thr, smc_scan_verdict* d_out, uint32_t* d_host_list,
                     uint32_t* d_n_host, void* stream);
+/* (ABI 11, additive: one entry more, the version number unchanged) --spikeScanMnv: smc_scan_detect when the listed records are the
+ * members of phase sets, and an MNV is called when every member is.  d_rows .. n_listed, thr: smc_scan_detect's.
+ *   d_set_off / set_off_host[n_sets + 1]  the sets tile the listed records in order: set s holds the records set_off[s] ..
+ *                              set_off[s + 1] - 1; set_off[0] = 0, set_off[n_sets] = n_listed, every size in 1 ..
+ *                              SMC_SPIKE_PHASE_MAX_MEMBERS.
+ *   d_out[c * n_listed + g]    byte for byte the record smc_scan_detect writes.
+ *   d_joint[c * n_sets + s]    one word: bits 31..30 the joint verdict - SMC_SCAN_NOT when any member is NOT, else SMC_SCAN_HOST when any
+ *                              member is HOST, else SMC_SCAN_CALLED; bit m of byte 0 / 1 / 2: member m of the set is CALLED / HOST / NOT.
+ *   d_host_list[0 .. *d_n_host)  the indices c * n_listed + g of the HOST member records of the sets whose JOINT verdict is HOST - a HOST
+ *                              member beside a NOT member decides nothing -, each once, in no fixed order (room for n_copies *
+ *                              n_listed words); *d_n_host is zeroed by the call.  Nothing else is written.
+ * Enqueued on `stream`, one launch; nothing waits.  SMC_E_INPUT, nothing launched: what smc_scan_detect refuses; offsets that do not
+ * tile the records; a set of 0 members or of more than SMC_SPIKE_PHASE_MAX_MEMBERS; n_copies * n_sets of 2^31 or more. */
+int smc_scan_detect_sets(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64_t n_loci, const smc_scan_locus* d_listed,
+                         const smc_scan_locus* listed_host, int32_t n_listed, const uint32_t* d_set_off, const uint32_t* set_off_host,
+                         int32_t n_sets, double thr, smc_scan_verdict* d_out, uint32_t* d_joint, uint32_t* d_host_list, uint32_t* d_n_host,
+                         void* stream);
 /* (ABI 11, additive: one entry more, the version number unchanged) --spikeScanIndel: smc_scan_detect for lists whose members are
  * allele KEYS.  An insertion's or a deletion's allele id is numbered per locus and per build (6 and up, in the order the builder met
  * the keys), so the id to compare cand[0].allele with is resolved per copy from that build's extras list.

@@ -59,6 +59,31 @@ SCAN_LOCUS_DTYPE = np.dtype([("offset", "<u4"), ("alt", "<u4")])
 SCAN_VERDICT_DTYPE = np.dtype([("pi", "<f8"), ("vmt", "<i4"), ("mt_verdict", "<u4")])
 assert SCAN_LOCUS_DTYPE.itemsize == 8 and SCAN_VERDICT_DTYPE.itemsize == 16
 SCAN_NOT, SCAN_CALLED, SCAN_HOST, SCAN_MT_MASK = 0, 1, 2, 0x3FFFFFFF
+# (smc_scan_detect_sets) a joint word: the joint verdict in bits 31..30, the members CALLED / HOST / NOT by bit in bytes 0 / 1 / 2
+SCAN_JOINT_CALLED_SHIFT, SCAN_JOINT_HOST_SHIFT, SCAN_JOINT_NOT_SHIFT = 0, 8, 16
+
+
+def scan_joint_rule(verdicts, set_off):
+    """smc_scan_detect_sets' joint rule in numpy.  verdicts: int [B, G], the member verdicts (SCAN_NOT / SCAN_CALLED / SCAN_HOST);
+    set_off: [n_sets + 1], the sets' tiling of the G records -> (uint32 [B, n_sets]: the joint words, the indices c * G + g of the HOST
+    members of the sets whose joint verdict is HOST, ascending)."""
+    verdicts = np.asarray(verdicts, np.int64)
+    B, G = verdicts.shape
+    off = np.asarray(set_off, np.int64)
+    words, listed = np.zeros((B, len(off) - 1), np.uint32), []
+    for c in range(B):
+        for s in range(len(off) - 1):
+            w = 0
+            for m, g in enumerate(range(int(off[s]), int(off[s + 1]))):
+                v = int(verdicts[c, g])
+                w |= 1 << (m + (SCAN_JOINT_CALLED_SHIFT if v == SCAN_CALLED else SCAN_JOINT_HOST_SHIFT if v == SCAN_HOST else SCAN_JOINT_NOT_SHIFT))
+            jv = SCAN_NOT if w & 0xFF0000 else SCAN_HOST if w & 0xFF00 else SCAN_CALLED
+            words[c, s] = (jv << 30) | w
+            if jv == SCAN_HOST:
+                listed += [c * G + g for g in range(int(off[s]), int(off[s + 1])) if int(verdicts[c, g]) == SCAN_HOST]
+    return words, np.array(sorted(listed), np.uint32)
+
+
 # (smc_scan_detect_keys) what d_alt_id holds where no extras entry of the copy shows the listed key / where the host has to look
 SCAN_ID_NONE, SCAN_ID_HOST = 0xFFFFFFFF, 0xFFFFFFFE
 # (smc_scan_filter) the four names only postfilter adds, behind the ten SMC_F_* bits; the 14 names of a FILTER column in the order of

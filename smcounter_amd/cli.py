@@ -331,6 +331,17 @@ def build_parser() -> argparse.ArgumentParser:
                         ".spikeScan.filter.curve.txt (RATE_PASS at every target and T95_PASS), <outPrefix>.spikeScan<t>.passrate.bedgraph "
                         "and .spikeScan.t95pass.bedgraph; with --spikeScanDepth / --spikeScanRpb also .spikeScan.depth.filter.txt / "
                         ".spikeScan.rpb.filter.txt.  Every other file of the scan stays as it is.  Needs --spikeScan")
+    p.add_argument("--spikeScanMnv", default=None,
+                   help="L in 2 .. 8: --spikeScan with an MNV of L adjacent letters instead of the SNV: at every locus P of --bedTarget REF = "
+                        "genome[P .. P+L-1], ALT = --spikeScanAlt's rule applied to every letter, planted as ONE phase set of L member SNVs "
+                        "named chrom:P (a barcode is spiked at all members or at none).  A locus is skipped when a position of P .. P+L-1 is "
+                        "no locus of the target or its letter is not A, C, G or T.  A pass is by definition the run --spikeAF <targets> "
+                        "--spikeVariants <the pass's list> --spikeReps R --spikePhase --dsSeed s (tools/spike_scan_lists.py --mnv writes the "
+                        "lists); --spikeScanStride >= L.  The GPU decides per copy and set whether every member was called "
+                        "(smc_scan_detect_sets).  Writes <outPrefix>.spikeScan.mnv.sensitivity.txt (the sets' lines of "
+                        ".spikeAF.phase.sensitivity.txt), .spikeScan.mnv.curve.txt, <outPrefix>.spikeScan<t>.mnv.rate.bedgraph and "
+                        ".spikeScan.mnv.t95.bedgraph in place of the SNV scan's pages; no LOD column with --lod.  Needs --spikeScan; beside "
+                        "--spikeScanBuild; not with --spikeScanIndel, --spikeScanDepth, --spikeScanRpb or --spikeScanFilter (not built)")
     p.add_argument("--spikeScanBuild", default=None,
                    help="whole (default) or listed: how --spikeScan builds its spiked copies.  whole: every copy is a build of its whole "
                         "decoded run, however few of its loci the pass lists.  listed: one smc_build_listed call builds the listed loci "
@@ -822,7 +833,8 @@ def _spike_scan(args, plan, ref, eng, params):
                                    eng, threshold, repeats, sampler=getattr(args, "sampler", "reference"),
                                    sampler_seed=getattr(args, "samplerSeed", 0), indel="indel" in scan, depth=depth, rpb=rpb,
                                    **(dict(flt=True) if "filter" in scan else {}),
-                                   **(dict(build="listed") if _spike.scan_build(scan) == "listed" else {}))
+                                   **(dict(build="listed") if _spike.scan_build(scan) == "listed" else {}),
+                                   **(dict(mnv=scan["mnv"]) if "mnv" in scan else {}))
     except (ValueError, bamio.BamError) as e:
         raise SystemExit(str(e))
     listed = _spike.scan_build(scan) == "listed"
@@ -1105,27 +1117,41 @@ def _make_rules(args, plan, loc_list):
         from .tools import ds_allele_fraction as af, spike_scan_lists as lists
         try:
             af.unique_idents(bamio.placed_barcodes(args.bamFile), args.bamFile)
-            if "indel" in plan.scan:
+            if "mnv" in plan.scan:
+                # (`variants`: the member SNVs with their sets; a pass holds indices of sets, `leaders` stand where the variants do below)
+                variants, leaders, skipped = lists.scan_mnvs(loc_list, fasta.FastaFile(args.refGenome), plan.scan["mnv"], plan.scan["alt"])
+                passes = lists.mnv_passes(variants, plan.scan["stride"])
+            elif "indel" in plan.scan:
                 variants, skipped = lists.scan_indels(loc_list, fasta.FastaFile(args.refGenome), plan.scan["indel"])
             else:
                 variants, skipped = lists.scan_variants(loc_list, fasta.FastaFile(args.refGenome), plan.scan["alt"])
-            passes = lists.scan_passes(variants, plan.scan["stride"])
+            if "mnv" not in plan.scan:
+                passes = lists.scan_passes(variants, plan.scan["stride"])
         except (ValueError, OSError, bamio.BamError) as e:
             raise SystemExit(str(e))
         for k, members in passes:
             # (the rewrite takes a pass's whole list of a chromosome: smc_spike_alleles_reps' limit, and smc_spike_indels_reps')
-            chrom, n = collections.Counter(variants[i].chrom for i in members).most_common(1)[0]
+            if "mnv" in plan.scan:              # (the rewrite's records are the member SNVs)
+                chrom, n = collections.Counter(variants.sets[i].chrom for i in members).most_common(1)[0]
+                n *= plan.scan["mnv"]
+            else:
+                chrom, n = collections.Counter(variants[i].chrom for i in members).most_common(1)[0]
             if n > SCAN_MAX_PASS_VARIANTS:
                 raise SystemExit("--spikeScan: pass %d holds %d loci of %s, at most %d (a larger --spikeScanStride makes more and smaller "
                                  "passes)" % (k, n, chrom, SCAN_MAX_PASS_VARIANTS))
-        index = {(v.chrom, v.pos): i for i, v in enumerate(variants)}
+        index = {cp: i for i, cp in enumerate(leaders)} if "mnv" in plan.scan else {(v.chrom, v.pos): i for i, v in enumerate(variants)}
         seen, loci = set(), []
         for c, q in loc_list:
             if (c, int(q)) not in seen:
                 seen.add((c, int(q)))
                 loci.append((c, int(q), index.get((c, int(q)))))
         plan.scan.update(variants=variants, skipped=skipped, passes=passes, loci=loci, loc_list=loc_list)
-        if "indel" in plan.scan:
+        if "mnv" in plan.scan:
+            print("--spikeScan: %d loci in %d passes of stride %d (--spikeScanMnv %d, %s), %d skipped for a position of the footprint that is "
+                  "no locus of the target or whose letter is not A, C, G or T; %d replicates x %d targets" %
+                  (len(leaders), len(passes), plan.scan["stride"], plan.scan["mnv"], plan.scan["alt"], len(skipped), plan.scan["reps"],
+                   len(plan.scan["targets"])))
+        elif "indel" in plan.scan:
             print("--spikeScan: %d loci in %d passes of stride %d (--spikeScanIndel %s%d), %d skipped for a letter inside the footprint "
                   "that is not A, C, G or T or lies past the chromosome's end; %d replicates x %d targets" %
                   ((len(variants), len(passes), plan.scan["stride"]) + plan.scan["indel"] + (len(skipped), plan.scan["reps"],
@@ -1365,6 +1391,8 @@ def _scan_reports(args, plan, shard):
     from . import spike as _spike
     scan, out = plan.scan, shard.scan
     variants, targets, R = scan["variants"], scan["targets"], scan["reps"]
+    if "mnv" in scan:
+        return _scan_mnv_reports(args, plan, shard)
     entries = {}
     for i, v in enumerate(variants):
         n, v0 = out["base"][i]
@@ -1415,6 +1443,27 @@ def _scan_reports(args, plan, shard):
                   (r, rule["seed"], rule["prob_keep"], rule["thr"], rule["n_kept"], rule["n_names"], params.mtDepth))
     if "filter" in scan:
         _scan_filter_reports(args, plan, shard)
+
+
+def _scan_mnv_reports(args, plan, shard):
+    """--spikeScanMnv: the two pages and the bedgraphs from the stage's joint verdicts and counts, and the closing lines of the run log."""
+    from . import spike as _spike
+    scan, out = plan.scan, shard.scan
+    variants, targets, R = scan["variants"], scan["targets"], scan["reps"]
+    sets = variants.sets
+    entries = {}
+    for i in range(len(sets)):
+        for t in range(len(targets)):
+            entries[(i, t)] = [(dict(zip(_spike.PHASE_NAMES, (int(x) for x in out["joint_counts"][i, j, t]))), int(out["joint_called"][i, t, j]))
+                               for j in range(R)]
+    _spike.write_scan_mnv(args.outPrefix, scan["loci"], variants, sets, targets, plan.outputs[0].params.mtDepth, entries)
+    tm = out["times"]
+    print("--spikeScan: %d loci x %d targets x %d replicates in %d passes: %d runs decoded once each (%.3f s), %d copies built and "
+          "called, %d of %d verdicts decided by the host, stage %.3f s" %
+          (len(sets), len(targets), R, len(scan["passes"]), tm["runs"], tm["decode"], sum(st["builds"] for st in out["passes"]),
+           sum(st["host"] for st in out["passes"]), len(variants) * len(targets) * R, tm["stage"]))
+    print("--spikeScanMnv %d: %d sets scanned, %d loci skipped, %d of %d joint verdicts decided by the host" %
+          (scan["mnv"], len(sets), len(scan["skipped"]), out["joint_host"], len(sets) * len(targets) * R))
 
 
 def _scan_filter_reports(args, plan, shard):

@@ -1735,6 +1735,51 @@ int smc_scan_detect(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64
     return SMC_OK;
 }
 
+// (--spikeScanMnv) smc_scan_detect with the listed records tiled by phase sets: smc_scan_detect's checks and those of the offsets on
+// the host copies before anything is enqueued, then the cursor zeroed and one launch (none for an empty list or no copy)
+int smc_scan_detect_sets(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64_t n_loci, const smc_scan_locus* d_listed,
+                         const smc_scan_locus* listed_host, int32_t n_listed, const uint32_t* d_set_off, const uint32_t* set_off_host,
+                         int32_t n_sets, double thr, smc_scan_verdict* d_out, uint32_t* d_joint, uint32_t* d_host_list, uint32_t* d_n_host,
+                         void* stream) {
+    const std::string who = "smc_scan_detect_sets";
+    if (!ctx || n_copies < 0 || n_loci < 0 || n_listed < 0 || n_sets < 0 || !d_n_host || !set_off_host) return fail(SMC_E_ARG, who + ": bad argument");
+    if (n_listed && !listed_host) return fail(SMC_E_ARG, who + ": NULL argument");
+    if (!std::isfinite(thr)) return fail(SMC_E_INPUT, who + ": a threshold that is not finite");
+    if (n_copies > 65535) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies, at most 65535");
+    if ((int64_t)n_copies * (int64_t)n_listed >= (1ll << 31) || (int64_t)n_copies * n_loci >= (1ll << 31) ||
+        (int64_t)n_copies * (int64_t)n_sets >= (1ll << 31))
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies of " + std::to_string(n_loci) + " loci, " +
+                                 std::to_string(n_listed) + " listed in " + std::to_string(n_sets) + " sets: 2^31 records, rows or sets, or more");
+    for (int32_t g = 0; g < n_listed; ++g) {
+        if ((int64_t)listed_host[g].offset >= n_loci)
+            return fail(SMC_E_INPUT, who + ": listed locus " + std::to_string(g) + " names offset " + std::to_string(listed_host[g].offset) +
+                                     " of " + std::to_string(n_loci));
+        if (listed_host[g].alt > 3u)
+            return fail(SMC_E_INPUT, who + ": listed locus " + std::to_string(g) + " has allele id " + std::to_string(listed_host[g].alt) +
+                                     ", one of 0 .. 3 expected");
+    }
+    if (set_off_host[0] != 0u || (int64_t)set_off_host[n_sets] != (int64_t)n_listed)
+        return fail(SMC_E_INPUT, who + ": the sets' offsets run from " + std::to_string(set_off_host[0]) + " to " + std::to_string(set_off_host[n_sets]) +
+                                 ", they must tile the " + std::to_string(n_listed) + " listed records");
+    for (int32_t s = 0; s < n_sets; ++s) {
+        const int64_t m = (int64_t)set_off_host[s + 1] - (int64_t)set_off_host[s];
+        if (m < 1 || m > SMC_SPIKE_PHASE_MAX_MEMBERS)
+            return fail(SMC_E_INPUT, who + ": set " + std::to_string(s) + " has " + std::to_string(m) + " members, 1 .. " +
+                                     std::to_string(SMC_SPIKE_PHASE_MAX_MEMBERS) + " expected");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemsetAsync(d_n_host, 0, sizeof(uint32_t), (hipStream_t)stream));
+    if (!n_listed || !n_copies) return SMC_OK;
+    if (!d_rows || !d_listed || !d_set_off || !d_out || !d_joint || !d_host_list) return fail(SMC_E_ARG, who + ": NULL argument");
+    const double edge = thr - 0.005;
+    const int64_t per_block = SCD_BLOCK / SCD_SET_LANES;
+    hipLaunchKernelGGL(k_scan_detect_sets, dim3((unsigned)std::min<int64_t>(((int64_t)n_sets + per_block - 1) / per_block, 1024), (unsigned)n_copies),
+                       dim3(SCD_BLOCK), 0, (hipStream_t)stream, d_rows, (uint32_t)n_loci, d_listed, (uint32_t)n_listed, d_set_off, (uint32_t)n_sets,
+                       edge - 1e-6, edge + 1e-6, d_out, d_joint, d_host_list, d_n_host);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
 // (--spikeScanFilter) the FILTER word per (copy, listed locus) of a called batch: everything checked on the host copies before
 // anything is enqueued, then one launch (none for an empty list or no copy)
 int smc_scan_filter(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64_t n_loci, const uint32_t* d_offsets,

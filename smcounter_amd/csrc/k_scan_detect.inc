@@ -23,29 +23,84 @@
 // lane), which at a few thousand lanes is nothing beside the batch's build.
 #define SCD_BLOCK 256
 
+// The member rule, shared by k_scan_detect and k_scan_detect_sets: the record of (copy c, listed locus L) and its verdict.
+__device__ __forceinline__ uint32_t scd_member(const smc_row* __restrict__ rows, uint32_t n_loci, uint32_t c, const smc_scan_locus L,
+                                               double lo, double hi, smc_scan_verdict& rec) {
+    const smc_row* const r = rows + ((size_t)c * n_loci + L.offset);          // (the host checked offset < n_loci on its copy)
+    const int32_t status = r->status, bi = r->biallelic, used = r->used_mt;
+    const int32_t allele = r->cand[0].allele, vmt = r->cand[0].vmt;
+    const double pi = r->cand[0].pi;
+    uint32_t v = SMC_SCAN_HOST;
+    if (status == 0 && bi == 0) {
+        if (allele != (int32_t)L.alt || pi < lo) v = SMC_SCAN_NOT;
+        else if (pi > hi) v = SMC_SCAN_CALLED;
+    }
+    rec.pi = pi;
+    rec.vmt = vmt;
+    rec.mt_verdict = (v << 30) | (uint32_t)min(max(used, 0), (int32_t)SMC_SCAN_MT_MASK);
+    return v;
+}
+
 __global__ __launch_bounds__(SCD_BLOCK) void k_scan_detect(const smc_row* __restrict__ rows, uint32_t n_loci,
                                                            const smc_scan_locus* __restrict__ listed, uint32_t n_listed, double lo, double hi,
                                                            smc_scan_verdict* __restrict__ out, uint32_t* __restrict__ host_list,
                                                            uint32_t* __restrict__ n_host) {
     const uint32_t c = blockIdx.y;
     for (uint32_t g = blockIdx.x * SCD_BLOCK + threadIdx.x; g < n_listed; g += gridDim.x * SCD_BLOCK) {
-        const smc_scan_locus L = listed[g];
-        const smc_row* const r = rows + ((size_t)c * n_loci + L.offset);      // (the host checked offset < n_loci on its copy)
-        const int32_t status = r->status, bi = r->biallelic, used = r->used_mt;
-        const int32_t allele = r->cand[0].allele, vmt = r->cand[0].vmt;
-        const double pi = r->cand[0].pi;
-        uint32_t v = SMC_SCAN_HOST;
-        if (status == 0 && bi == 0) {
-            if (allele != (int32_t)L.alt || pi < lo) v = SMC_SCAN_NOT;
-            else if (pi > hi) v = SMC_SCAN_CALLED;
-        }
         const uint32_t idx = c * n_listed + g;
         smc_scan_verdict rec;
-        rec.pi = pi;
-        rec.vmt = vmt;
-        rec.mt_verdict = (v << 30) | (uint32_t)min(max(used, 0), (int32_t)SMC_SCAN_MT_MASK);
+        const uint32_t v = scd_member(rows, n_loci, c, listed[g], lo, hi, rec);
         out[idx] = rec;
         if (v == SMC_SCAN_HOST) host_list[atomicAdd(n_host, 1u)] = idx;       // (at most n_copies * n_listed appends: the list's size)
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// --spikeScanMnv: the verdicts of phase SETS - an MNV is called when every member SNV is (smc_scan_detect_sets)
+// ------------------------------------------------------------------------------------------
+// The listed records are tiled by sets: set s holds the records set_off[s] .. set_off[s + 1] - 1, one to SMC_SPIKE_PHASE_MAX_MEMBERS
+// (= 8) of them - the host checked both on its copy.
+//   k_scan_detect_sets  a group of eight neighbouring lanes per (copy = blockIdx.y, set): lane m of the group takes member m with
+//                  scd_member - so the up to eight scattered row gathers of a set are in flight together, not behind one another in
+//                  one lane - and writes its 16-byte record exactly as k_scan_detect does.  Each lane makes a word with its bit m in
+//                  byte 0 (CALLED), 1 (HOST) or 2 (NOT); three xor-shuffles OR the eight words (a group never straddles a wavefront:
+//                  eight divides 64, and every lane of the wavefront runs every round - the loop's bound is the workgroup's).  The
+//                  joint verdict - NOT when any member is NOT, else HOST when any is HOST, else CALLED - goes into bits 31..30 above
+//                  the three bytes, written by lane 0 of the group with one vector store.  The HOST members append their record's
+//                  index to the list ONLY when the joint verdict is HOST: beside a NOT member a HOST member decides nothing.
+// Nothing else is written.  The list's ORDER is that of the atomics; its CONTENT is fixed.
+#define SCD_SET_LANES 8
+
+__global__ __launch_bounds__(SCD_BLOCK) void k_scan_detect_sets(const smc_row* __restrict__ rows, uint32_t n_loci,
+                                                                const smc_scan_locus* __restrict__ listed, uint32_t n_listed,
+                                                                const uint32_t* __restrict__ set_off, uint32_t n_sets, double lo, double hi,
+                                                                smc_scan_verdict* __restrict__ out, uint32_t* __restrict__ joint,
+                                                                uint32_t* __restrict__ host_list, uint32_t* __restrict__ n_host) {
+    const uint32_t c = blockIdx.y, m = threadIdx.x & (SCD_SET_LANES - 1);
+    const uint32_t per_block = SCD_BLOCK / SCD_SET_LANES;
+    for (uint32_t s0 = blockIdx.x * per_block; s0 < n_sets; s0 += gridDim.x * per_block) {       // (uniform over the workgroup)
+        const uint32_t s = s0 + threadIdx.x / SCD_SET_LANES;
+        uint32_t w = 0, v = SMC_SCAN_NOT, idx = 0;
+        bool mine = false;
+        if (s < n_sets) {
+            const uint32_t first = set_off[s], size = set_off[s + 1] - first;
+            mine = m < size;
+            if (mine) {
+                const uint32_t g = first + m;                                  // (below n_listed: the offsets tile the records)
+                idx = c * n_listed + g;
+                smc_scan_verdict rec;
+                v = scd_member(rows, n_loci, c, listed[g], lo, hi, rec);
+                out[idx] = rec;
+                w = 1u << (m + (v == SMC_SCAN_CALLED ? 0u : v == SMC_SCAN_HOST ? 8u : 16u));
+            }
+        }
+        w |= __shfl_xor(w, 1);
+        w |= __shfl_xor(w, 2);
+        w |= __shfl_xor(w, 4);
+        const uint32_t jv = (w & 0xFF0000u) ? SMC_SCAN_NOT : (w & 0xFF00u) ? SMC_SCAN_HOST : SMC_SCAN_CALLED;
+        if (s < n_sets && m == 0) joint[c * n_sets + s] = (jv << 30) | w;
+        if (mine && v == SMC_SCAN_HOST && jv == SMC_SCAN_HOST)
+            host_list[atomicAdd(n_host, 1u)] = idx;                            // (at most n_copies * n_listed appends: the list's size)
     }
 }
 

@@ -1472,6 +1472,34 @@ def _listed_spans(variants, order):
         yield                                          # (what send() returns; the loop's next step resumes here)
 
 
+def _set_spans(variants, sets, order):
+    """_listed_spans for phase sets (--spikeScanMnv): a set is never split over two decoded runs.  `order`: the indexes into `sets` by
+    chromosome and leader position; from the first set not yet taken those of its chromosome whose LAST member stands less than
+    AF_RUN_LOCI positions behind that set's leader -> a generator of (chrom, lo, hi, the span's set indexes), hi the last member's
+    position.  The caller answers each with send(n), the sets its run holds whole (sets_inside) - one cut short: the rest, whole
+    sets, starts the next."""
+    first = lambda i: variants[sets[i].members[0]].pos
+    last = lambda i: max(variants[k].pos for k in sets[i].members)
+    i = 0
+    while i < len(order):
+        c0, p0, j = sets[order[i]].chrom, first(order[i]), i
+        while j + 1 < len(order) and sets[order[j + 1]].chrom == c0 and last(order[j + 1]) - p0 < AF_RUN_LOCI:
+            j += 1
+        i += yield c0, p0 - 1, max(last(k) for k in order[i:j + 1]), order[i:j + 1]
+        yield                                          # (what send() returns; the loop's next step resumes here)
+
+
+def sets_inside(variants, sets, span, lo: int, nl: int):
+    """The leading sets of `span` (_set_spans') that a run of `nl` loci from 0-based `lo` holds WHOLE: it ends in front of the first
+    set with a member beyond the run - that set and everything behind it is deferred, so the sets are handed out in order."""
+    out = []
+    for i in span:
+        if any(variants[k].pos - 1 - lo >= nl for k in sets[i].members):
+            break
+        out.append(i)
+    return out
+
+
 def allele_carriers_run(eng, up: RunOnDevice, A, lo: int, var: np.ndarray, ins: np.ndarray, counts: bool = False):
     """smc_allele_carriers over the run `up` (A: its counts) -> (covers, carries: bool [n_var, n_bc] by run-wide barcode id; the
     (reads, alt) counters uint32 [n_var, n_bc, 2] when `counts`, else None)."""
@@ -3631,6 +3659,55 @@ def scan_detect(eng, d_rows, n_copies: int, n_loci: int, listed, threshold):
     return rec.reshape(B, G), todo
 
 
+def scan_detect_sets(eng, d_rows, n_copies: int, n_loci: int, listed, set_off, threshold, records_of=None):
+    """smc_scan_detect_sets over the rows of a called batch in HBM -> (uint32 [n_copies, n_sets]: the joint words (abi.scan_joint_rule),
+    the indices copy x G + listed record of the HOST members of the sets whose joint verdict is HOST, ascending, and the member records
+    abi.SCAN_VERDICT_DTYPE [len(records_of), G] of the copies `records_of` - all of them with None).  listed: abi.SCAN_LOCUS_DTYPE [G];
+    set_off: uint32 [n_sets + 1], the sets' tiling of the listed records.  What comes down: 4 bytes per (copy, set), the list, and 16
+    bytes per listed record of the copies asked for."""
+    from .engine import DevBuf
+    listed = np.ascontiguousarray(listed, abi.SCAN_LOCUS_DTYPE)
+    set_off = np.ascontiguousarray(set_off, np.uint32)
+    B, G, S = int(n_copies), len(listed), len(set_off) - 1
+    n = B * G
+    want = list(range(B)) if records_of is None else [int(c) for c in records_of]
+    bufs = [DevBuf(eng, listed.nbytes + 256).upload(listed.view(np.uint8).reshape(-1) if G else np.zeros(4, np.uint8)),
+            _up8(eng, set_off), DevBuf(eng, 16 * max(1, n) + 256), DevBuf(eng, 4 * max(1, B * S) + 256), DevBuf(eng, 4 * max(1, n) + 256),
+            DevBuf(eng, 256)]
+    try:
+        _lib.check(eng.L.smc_scan_detect_sets(eng.ctx, d_rows.data_ptr() if d_rows is not None else None, B, int(n_loci), bufs[0].data_ptr(),
+                                              listed.ctypes.data, G, bufs[1].data_ptr(), set_off.ctypes.data, S, float(threshold),
+                                              bufs[2].data_ptr(), bufs[3].data_ptr(), bufs[4].data_ptr(), bufs[5].data_ptr(),
+                                              ctypes.c_void_p(0)), "smc_scan_detect_sets")
+        n_host = int(bufs[5].download(np.uint32, 1)[0])              # (the default stream: behind the kernel)
+        if n_host > n:
+            raise _lib.SmcError("smc_scan_detect_sets: %d records for the host out of %d" % (n_host, n))
+        joint = bufs[3].download(np.uint32, B * S) if B * S and G else np.zeros(B * S, np.uint32)
+        rec = np.zeros((len(want), G), abi.SCAN_VERDICT_DTYPE)
+        for i, c in enumerate(want if G else ()):
+            if not 0 <= c < B:
+                raise ValueError("scan_detect_sets: the records of copy %d of %d" % (c, B))
+            bufs[2].download(abi.SCAN_VERDICT_DTYPE, G, 16 * c * G, out=rec[i])
+        todo = np.sort(bufs[4].download(np.uint32, n_host)) if n_host else np.zeros(0, np.uint32)
+    finally:
+        for b in bufs:
+            b.free()
+    return joint.reshape(B, S), todo, rec
+
+
+def scan_joint_members(words, set_off) -> np.ndarray:
+    """The member verdicts that smc_scan_detect_sets' joint words hold -> int64 [B, G]: member m of set s is CALLED / HOST / NOT by bit
+    m of byte 0 / 1 / 2 of words[c, s]."""
+    words = np.asarray(words, np.uint32)
+    off = np.asarray(set_off, np.int64)
+    out = np.zeros((words.shape[0], int(off[-1]) if len(off) else 0), np.int64)
+    for s in range(len(off) - 1):
+        for m in range(int(off[s + 1] - off[s])):
+            w = words[:, s].astype(np.int64) >> m
+            out[:, off[s] + m] = np.where(w & 1, abi.SCAN_CALLED, np.where((w >> abi.SCAN_JOINT_HOST_SHIFT) & 1, abi.SCAN_HOST, abi.SCAN_NOT))
+    return out
+
+
 def scan_detect_keys(eng, d_rows, n_copies: int, n_loci: int, var, ins, copies: dict, extras: dict, threshold):
     """smc_scan_detect_keys over the rows of a called batch in HBM -> scan_detect's pair and the resolved ids, uint32 [n_copies, G]
     (abi.SCAN_ID_NONE: no extras entry of the copy shows the key; abi.SCAN_ID_HOST: the host has to look).  var, ins:
@@ -3701,7 +3778,8 @@ def scan_called_host(text, v, threshold: int, repeats) -> bool:
 
 
 def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want_reads, P, fasta, variants, max_depth, sampler, sampler_seed,
-               bits, threshold, repeats, check0, indel: dict = None, depth: dict = None, rpb: dict = None, flt: dict = None, build: dict = None):
+               bits, threshold, repeats, check0, indel: dict = None, depth: dict = None, rpb: dict = None, flt: dict = None, build: dict = None,
+               mnv: dict = None):
     """The _SpikedCopies of the run at one target, one per seed of `part_seeds`, each built behind the other into one device batch and
     the batch called with one plan - _spike_rep_call's way - but the rows stay in HBM: smc_scan_detect gives a verdict per (copy,
     listed locus), and only the rows it leaves to the host come down, one by one, to be printed and cut the existing way.  run.group:
@@ -3735,12 +3813,22 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
     copy (with `indel` the entry writes g into its extras entries' locus field, the stretches stay in HBM and smc_scan_detect_keys gets
     n_loci = G and variant records whose locus is g); a batch the listed builder declines is built the whole way and counted under
     "whole"; the listed
-    rows of replicate 0 are also made by a whole build of that one copy, and a row that differs in a byte ends the run."""
+    rows of replicate 0 are also made by a whole build of that one copy, and a row that differs in a byte ends the run.
+    `mnv` (--spikeScanMnv: dict(set_off: the tiling of run.group by phase sets, var, var_ins: af_run_variants' records of run.group,
+    want: per copy and member the counts call's (N, V1), want_joint: per copy and set smc_spike_phase_counts' (N_ALL, V1_ALL)); not
+    with `indel`, `depth`, `rpb` or `flt`): the verdicts come from smc_scan_detect_sets - the joint words, the list and replicate 0's
+    member records come down, the member verdicts of the other copies are read from the words' bits.  Only the HOST members of sets
+    whose joint verdict is HOST are decided by the host; replicate 0's member rows come down anyway, are decided the host way and
+    held against the device's member verdicts, and the joint verdict against their AND; replicate 0's (N, V1) per member and (N_ALL,
+    V1_ALL) per set are counted a second time, by smc_allele_carriers' cover and carrier bits on the spiked copy and their AND over
+    the members.  mnv["out"] is filled: (bool [copies, sets]: the MNV was called, the joint verdicts the host decided)."""
     from . import dsaf, spike as _spike, vc
     from .engine import DevBuf
     A, lo, nl, chrom = run.A, run.lo, run.nl, run.chrom
     B, G = len(part_seeds), len(run.group)
     flag, entry = ("--spikeScan", "smc_scan_detect") if indel is None else ("--spikeScanIndel", "smc_scan_detect_keys")
+    if mnv is not None:
+        flag, entry = "--spikeScanMnv", "smc_scan_detect_sets"
     copies = _SpikedCopies(eng, run, svar, part_seeds, thr, P, *((indel["ins"], indel.get("caps")) if indel is not None else ()))
     runs, extras, xbufs, sels = copies.runs, None, [], None
 
@@ -3786,7 +3874,9 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
                     if c not in keys_of:                        # (with `indel` a relocated record's texts come from the copy: key_of)
                         keys_of[c] = held[c].allele_key if indel is None else key_of(c)
                     return extras_table(xl[c], a, keys_of[c], chrom, lo, fasta)
-                if indel is None:
+                if mnv is not None:
+                    words_j, todo, rec0 = scan_detect_sets(eng, d_rows, B, G, spots, mnv["set_off"], cut, [] if check0 is None else [check0])
+                elif indel is None:
                     rec, todo = scan_detect(eng, d_rows, B, G, spots, cut)
                 else:
                     # (a copy has G rows: the variant records name the dense locus, as the entries of the listed build do)
@@ -3795,6 +3885,9 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
                     rec, todo, _ = scan_detect_keys(
                         eng, d_rows, B, G, var, indel["var_ins"], where,
                         dict(x=xkeep["x"].data_ptr(), cnt=xkeep["cnt"].data_ptr(), x_stride=5 * xkeep["xcap"], cnt_stride=2, xcap=xkeep["xcap"]), cut)
+            elif mnv is not None:
+                words_j, todo, rec0 = scan_detect_sets(eng, d_rows, B, nl, listed, mnv["set_off"], cut, [] if check0 is None else [check0])
+                table_of = lambda c, a: d.tables[c * nl + a]
             elif indel is None:
                 rec, todo = scan_detect(eng, d_rows, B, nl, listed, cut)         # (its downloads wait for the plan's kernels)
                 table_of = lambda c, a: d.tables[c * nl + a]
@@ -3810,14 +3903,29 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
                         lists[c] = extras[c].x.download(np.uint32, 5 * n_x).reshape(n_x, 5) if n_x else np.zeros((0, 5), np.uint32)
                         keys[c] = key_of(c)
                     return extras_table(lists[c], a, keys[c], chrom, lo, fasta)
-            verdict = (rec["mt_verdict"] >> 30).astype(np.int64)
+            if mnv is not None:
+                # (the member verdicts of every copy from the joint words' bits; the records of replicate 0 alone came down)
+                verdict = scan_joint_members(words_j, mnv["set_off"])
+                rec = np.zeros((B, G), abi.SCAN_VERDICT_DTYPE)
+                rec["mt_verdict"] = verdict.astype(np.uint32) << 30
+                if check0 is not None:
+                    if not np.array_equal(rec0[0]["mt_verdict"] >> 30, verdict[check0]):
+                        raise RuntimeError("%s: %s:%d-%d%s: the joint words' member bits are not the member records' verdicts" %
+                                           (flag, chrom, lo + 1, lo + nl, what))
+                    rec[check0] = rec0[0]
+                want_list = abi.scan_joint_rule(verdict, mnv["set_off"])
+                if not np.array_equal(want_list[0], words_j):
+                    raise RuntimeError("%s: %s:%d-%d%s: a joint word is not the joint rule of its member bits" % (flag, chrom, lo + 1, lo + nl, what))
+            else:
+                verdict = (rec["mt_verdict"] >> 30).astype(np.int64)
             called = verdict == abi.SCAN_CALLED
             words, fhost, n_fhost = None, set(), 0
             if flt is not None:
                 words = scan_filter(eng, d_rows, B, n_rows, spots["offset"], flt["gate"], flt["always"])
                 fhost = set(int(x) for x in np.flatnonzero((called & ((words & abi.SCAN_FLT_HOST) != 0)).reshape(-1)))
             theirs = set(int(x) for x in todo)
-            if theirs != set(int(x) for x in np.flatnonzero(verdict.reshape(-1) == abi.SCAN_HOST)):
+            if theirs != (set(int(x) for x in want_list[1]) if mnv is not None else
+                          set(int(x) for x in np.flatnonzero(verdict.reshape(-1) == abi.SCAN_HOST))):
                 raise RuntimeError("%s: %s:%d-%d%s: the list of the records for the host is not that of the HOST verdicts" %
                                    (flag, chrom, lo + 1, lo + nl, what))
             mine = sorted(theirs | fhost | (set(check0 * G + g for g in range(G)) if check0 is not None else set()))
@@ -3835,8 +3943,8 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
                         raise RuntimeError("%s: %s:%d%s: the row of seed %d could not be printed:\n%s" %
                                            (flag, v.chrom, v.pos, what, int(part_seeds[i // G]), line))
                     host = scan_called_host(line, v, cut, repeats)
-                    if i in theirs:
-                        called[i // G, i % G] = host
+                    if i in theirs or (mnv is not None and verdict[i // G, i % G] == abi.SCAN_HOST):
+                        called[i // G, i % G] = host        # (mnv: replicate 0's HOST member beside a NOT one - not listed, decided anyway)
                     elif host != bool(called[i // G, i % G]):
                         who = "replicate 0 of" if indel is None else "seed %d at" % int(part_seeds[i // G])
                         raise RuntimeError("%s: %s %s:%d %s>%s%s: %s says %s (PI %.17g, threshold %d), the row as "
@@ -3856,6 +3964,16 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
                                                 _filter_names(int(words[i // G, i % G])), seen, _filter_names(seen), line))
             if flt is not None:
                 flt["out"].append((words & np.uint32(abi.SCAN_FLT_NAMES_MASK), n_fhost))
+            if mnv is not None:
+                # (every member of replicate 0 was decided the host way above: `called` holds the host's answers there, so the AND over
+                # a set's members is the host's joint verdict - the device's NOT must agree with it)
+                off = np.asarray(mnv["set_off"], np.int64)
+                jv = (words_j >> 30).astype(np.int64)
+                all_called = np.logical_and.reduceat(called, off[:-1], axis=1) if G else np.zeros((B, 0), bool)
+                if check0 is not None and bool((all_called[check0] & (jv[check0] == abi.SCAN_NOT)).any()):
+                    raise RuntimeError("%s: replicate 0 at %s:%d-%d%s: a set whose members the host all calls has the joint verdict NOT" %
+                                       (flag, chrom, lo + 1, lo + nl, what))
+                mnv["out"] = (all_called & (jv != abi.SCAN_NOT), int((jv == abi.SCAN_HOST).sum()))
             return called, len(theirs)
         finally:
             if plan is not None:
@@ -3871,6 +3989,15 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
         if indel is not None and copies.totals[:, 2].any():
             raise _lib.SmcError("smc_spike_indels_reps: a copy of %s:%d-%d did not fit spike_indel_caps' bounds" % (chrom, lo + 1, lo + nl))
         copies.check_reads(var_at, want_reads, variants, flag)
+        if mnv is not None and check0 is not None:
+            cov1, car1 = copies.check_carriers(check0, runs[check0], A, mnv["want"][check0], mnv["var"], mnv["var_ins"], variants, flag)
+            for s_, (a, b) in enumerate(zip(mnv["set_off"][:-1], mnv["set_off"][1:])):
+                mine = (int(cov1[a:b].all(axis=0).sum()), int(car1[a:b].all(axis=0).sum()))
+                if mine != tuple(int(x) for x in mnv["want_joint"][check0][s_]):
+                    v = variants[run.group[int(a)]]
+                    raise RuntimeError("%s: seed %d, the set at %s:%d: the AND of the copy's cover and carrier bits holds (N_ALL, V1_ALL) = "
+                                       "%r, the counts call says %r" % (flag, int(part_seeds[check0]), v.chrom, v.pos, mine,
+                                                                        tuple(int(x) for x in mnv["want_joint"][check0][s_])))
         if indel is not None:
             if check0 is not None:
                 copies.check_carriers(check0, runs[check0], A, indel["want"][check0], indel["var"], indel["var_ins"], variants, flag)
@@ -3920,7 +4047,7 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
 
 def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n_reps: int, eng, threshold: int, repeats,
                sampler: str = "reference", sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, indel: bool = False,
-               depth: dict = None, rpb: dict = None, flt: bool = False, build: str = "whole"):
+               depth: dict = None, rpb: dict = None, flt: bool = False, build: str = "whole", mnv: int = 0):
     """The stage of --spikeScan.  variants: the scan's SNV at every scanned locus (tools.spike_scan_lists.scan_variants); passes: [(k,
     the indices of pass k)] (scan_passes).  A pass is the run --spikeAF <targets> --spikeVariants <its list> --spikeReps n_reps --dsSeed
     seed: replicate j has seed (seed + j) mod 2^64, and the draws, the rewrite, NM and the thresholds are that run's.
@@ -3958,6 +4085,13 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     `build` "listed" (--spikeScanBuild): every batch of copies is one smc_build_listed call over the pass's loci of the run
     (_scan_call's `build`), a batch holds as many copies as their listed slots allow (_copy_room), and the passes' dicts get "listed"
     and "whole" - the builds made either way - and "checks": the replicate-0 rows compared with a whole build's.
+    `mnv` L (--spikeScanMnv): `variants` are tools.spike_scan_lists.scan_mnvs' member SNVs with their phase sets of L, `passes` hold
+    indices of SETS (mnv_passes); a pass is the run --spikeAF <targets> --spikeVariants <its list of MNV lines> --spikeReps n_reps
+    --spikePhase: its SpikeSet is built from the pass's PhasedVariants, so every member is drawn with its leader's position.  The runs
+    are cut so that no set is split over two of them (_set_spans, sets_inside).  The result gets joint_counts: uint32 [sets, R, T, 4] =
+    (N_ALL, V0_ALL, S_ALL, V1_ALL), joint_called: bool [sets, T, R] and joint_host: the joint verdicts the host decided; base and
+    counts are per member, `called` holds the member verdicts only as far as a joint verdict needed them.  ValueError: beside `indel`,
+    `depth`, `rpb` or `flt` (not built).
     -> dict(seeds, base: per variant (N, V0), counts: uint32 [V, R, T, 3] = (S, READS, V1), called: bool [V, T, R], passes: per pass
     of `passes` dict(variants, copies, builds, host, seconds), times: dict(stage, runs, decode))."""
     import time
@@ -3967,6 +4101,8 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     T, R, V = len(targets), int(n_reps), len(variants)
     if T > SPIKE_MAX_TARGETS:
         raise ValueError("--spikeScan: %d targets, at most %d" % (T, SPIKE_MAX_TARGETS))
+    if mnv and (indel or depth is not None or rpb is not None or flt):
+        raise ValueError("--spikeScanMnv: indel members and the depth, reads-per-barcode and filter axes of an MNV scan are not built")
     seeds = dsaf.rep_seeds(seed, R)
     thr = [sv.threshold(t) for t in targets]
     P = params
@@ -3974,10 +4110,24 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     max_depth = eng.L.smc_build_max_depth()
     pass_at = np.full(V, -1, np.int64)          # variant -> its pass's index in `passes`
     local = np.zeros(V, np.int64)               # ... and its place in that pass's list
-    for p, (_, members) in enumerate(passes):
-        pass_at[members] = p
-        local[members] = np.arange(len(members))
-    spikes = [SpikeSet([variants[i] for i in members], indels=indel) for _, members in passes]
+    if mnv:
+        from .tools import spike_scan_lists as lists
+        sets = variants.sets
+        set_of = np.zeros(V, np.int64)          # member -> its set
+        for i, ps in enumerate(sets):
+            set_of[list(ps.members)] = i
+        for p, (_, members) in enumerate(passes):
+            for r, i in enumerate(members):     # (mnv_pass_variants lays a pass's list out set by set)
+                pass_at[list(sets[i].members)] = p
+                local[list(sets[i].members)] = r * mnv + np.arange(mnv)
+        spikes = [SpikeSet(lists.mnv_pass_variants(variants, members)) for _, members in passes]
+        mnv = dict(L=int(mnv), set_of=set_of, counts=np.zeros((len(sets), R, T, 4), np.uint32), called=np.zeros((len(sets), T, R), bool), host=0)
+    else:
+        mnv = None
+        for p, (_, members) in enumerate(passes):
+            pass_at[members] = p
+            local[members] = np.arange(len(members))
+        spikes = [SpikeSet([variants[i] for i in members], indels=indel) for _, members in passes]
     base, counts, called = [None] * V, np.zeros((V, R, T, 3), np.uint32), np.zeros((V, T, R), bool)
     stats = [dict(variants=0, copies=0, builds=0, host=0, seconds=0.0) for _ in passes]
     if build not in ("whole", "listed"):
@@ -4006,8 +4156,11 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     else:
         flt = None
     times = {"decode": 0.0, "runs": 0}
-    order = sorted(range(V), key=lambda k: (variants[k].chrom, variants[k].pos))
-    spans = _listed_spans(variants, order)
+    if mnv is not None:
+        spans = _set_spans(variants, sets, sorted(range(len(sets)), key=lambda i: (sets[i].chrom, variants[sets[i].members[0]].pos)))
+    else:
+        order = sorted(range(V), key=lambda k: (variants[k].chrom, variants[k].pos))
+        spans = _listed_spans(variants, order)
     try:
         for chrom, lo, hi, span in spans:
             t0 = time.perf_counter()
@@ -4016,7 +4169,14 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
                 nl = run.load(path, fasta, eng, P, max_reads, nthreads, mism=True)
                 if nl < 1:
                     raise bamio.BamError("--spikeScan: the run %s:%d-%d could not be decoded" % (chrom, lo + 1, hi))
-                inside = [k for k in span if variants[k].pos - 1 - lo < nl]
+                if mnv is not None:
+                    taken = sets_inside(variants, sets, span, lo, nl)          # (whole sets only; `span` holds sets here)
+                    if not taken:
+                        raise bamio.BamError("--spikeScanMnv: the run %s:%d-%d came back with %d loci, fewer than the MNV's %d" %
+                                             (chrom, lo + 1, hi, nl, mnv["L"]))
+                    inside = [k for i in taken for k in sets[i].members]
+                else:
+                    inside = [k for k in span if variants[k].pos - 1 - lo < nl]
                 times["decode"] += time.perf_counter() - t0
                 times["runs"] += 1
                 in_run = sorted({int(pass_at[k]) for k in inside})
@@ -4033,14 +4193,15 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
                     room, caps = _copy_room(run, spikes[p].chrom_variants(chrom, 0.5)[0] if indel else None, indel,
                                             len((depth or rpb)["params"]) if (depth or rpb) is not None else 0, rpb is not None, slots)
                     _scan_pass(eng, run, spikes[p], [int(local[k]) for k in run.group], variants, seeds, thr, P, fasta, max_depth, sampler,
-                               sampler_seed, threshold, repeats, room, base, counts, called, stats[p], caps, depth, rpb, flt, listed_build)
+                               sampler_seed, threshold, repeats, room, base, counts, called, stats[p], caps, depth, rpb, flt, listed_build,
+                               **(dict(mnv=mnv) if mnv is not None else {}))
                     stats[p]["variants"] += len(run.group)
                     stats[p]["seconds"] += time.perf_counter() - t0
             finally:
                 if rpb is not None and rpb.get("masks") is not None:
                     rpb.pop("masks").free()
                 run.free()
-            spans.send(len(inside))
+            spans.send(len(inside) if mnv is None else len(taken))
     finally:
         close_rules(read_rules)
     times["stage"] = time.perf_counter() - t_start
@@ -4050,6 +4211,8 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     if rpb is not None:
         out.update(rpb_counts=rpb["counts"], rpb_called=rpb["called"],
                    rpb_rules=[dict(seed=r.seed, prob_keep=r.prob_keep, thr=r.thr, n_kept=r.n_kept, n_names=r.n_names) for r in read_rules])
+    if mnv is not None:
+        out.update(joint_counts=mnv["counts"], joint_called=mnv["called"], joint_host=mnv["host"])
     if flt is not None:
         out.update(filter=flt["words"], filter_host=flt["host"])
         if (depth or rpb) is not None:
@@ -4088,7 +4251,8 @@ def _scan_read_masks(eng, run: AfRun, read_rules, seeds) -> dict:
 
 
 def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr, P, fasta, max_depth, sampler, sampler_seed, threshold,
-               repeats, room, base, counts, called, stat, caps=None, depth: dict = None, rpb: dict = None, flt: dict = None, listed_build: bool = False):
+               repeats, room, base, counts, called, stat, caps=None, depth: dict = None, rpb: dict = None, flt: dict = None, listed_build: bool = False,
+               mnv: dict = None):
     """spike_scan's work for one pass in one run: run.group are the pass's variants there (indices into `variants`), members[g] the
     place of run.group[g] in the pass's list (`spikes`).  base, counts, called and stat are filled.  `caps` (--spikeScanIndel:
     spike_indel_caps of the pass's list on the run): the indel branch.  `depth` (--spikeScanDepth: spike_scan's dict with "counts" and
@@ -4098,7 +4262,11 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
     (smc_spike_indel_read_bits) on the pass's variants, spike_rpb_records per variant and ONE spike_rpb_counts call for the cells'
     counters; a batch's mask base is that of its first seed.  `flt` (--spikeScanFilter: spike_scan's dict with "gate", "always",
     "words", "cell_words" and "host"): per batch the FILTER words of the copies (_scan_call's `flt`); the last three are filled.
-    `listed_build` (--spikeScanBuild listed): _scan_call's `build` is `stat`, whose "listed", "whole" and "checks" count up."""
+    `listed_build` (--spikeScanBuild listed): _scan_call's `build` is `stat`, whose "listed", "whole" and "checks" count up.
+    `mnv` (--spikeScanMnv: spike_scan's dict with "L", "set_of", "counts", "called" and "host"): run.group holds the members of whole
+    phase sets of L, set by set; the joint barcodes of every set come from spike_joint and (N_ALL, V0_ALL, S_ALL, V1_ALL) of every set,
+    replicate and target from ONE smc_spike_phase_counts call; per batch the joint verdicts (_scan_call's `mnv`).  `called` holds the
+    member verdicts as far as a joint verdict needed them."""
     A, up, lo, chrom = run.A, run.up, run.lo, run.chrom
     idents, (nm, n_indel) = run.idents, run.mism
     group = run.group
@@ -4131,6 +4299,15 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
         # (--spikeScanIndel: a key has no fixed id - smc_scan_detect_keys takes `var`, and of `listed` only the offsets are read)
         listed[g] = (variants[k].pos - 1 - lo, SCAN_ALT_ID[variants[k].alt] if caps is None else 0)
     R, F = len(seeds), len(depth["fracs"]) if depth is not None else len(rpb["targets"]) if rpb is not None else 0
+    if mnv is not None:
+        from .tools import spike_variants as sv
+        set_off = np.arange(0, len(group) + 1, mnv["L"], dtype=np.uint32)
+        first = [int(a) for a in set_off[:-1]]
+        joint = spike_joint([sv.PhaseSet("", chrom, tuple(range(a, a + mnv["L"]))) for a in first], covers, counters)
+        joint_counts = spike_phase_counts(eng, [lead[a] for a in first], joint, seeds, thr, [1 << 32])[:, :, :, 0]     # [sets, R, T, 4]
+        set_ids = [int(mnv["set_of"][group[a]]) for a in first]
+        for s_, i in enumerate(set_ids):
+            mnv["counts"][i] = joint_counts[s_]
     for t in range(len(thr)):
         for b in range(0, R, room):
             js = list(range(b, min(R, b + room)))
@@ -4149,15 +4326,27 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
                                         want=want, masks=rpb["masks"].data_ptr() + 4 * rpb["n_words"] * F * js[0], n_words=rpb["n_words"],
                                         copy_stride=rpb["n_words"] * F),)
             fl = dict(gate=flt["gate"][group], always=flt["always"][group]) if flt is not None else None
+            more = {}
+            if mnv is not None:
+                more["mnv"] = dict(set_off=set_off, var=var, var_ins=ins,
+                                   want=[[(len(covers[g]), int(mine[g, j, t, 2])) for g in range(len(group))] for j in js],
+                                   want_joint=[[(int(joint_counts[s_, j, t, 0]), int(joint_counts[s_, j, t, 3])) for s_ in range(len(first))]
+                                               for j in js])
             if listed_build:
                 before = {k: stat[k] for k in ("listed", "whole", "checks")}
 
                 def call(bits):
                     stat.update(before)         # (a narrower retry starts over)
-                    return _scan_call(*args, bits, *tail, flt=fl, build=stat)
+                    return _scan_call(*args, bits, *tail, flt=fl, build=stat, **more)
             else:
-                call = lambda bits: _scan_call(*args, bits, *tail, flt=fl)
+                call = lambda bits: _scan_call(*args, bits, *tail, flt=fl, **more)
             got = _narrow_retry(eng, P, call)
+            if mnv is not None:
+                yes_all, n_joint_host = more["mnv"]["out"]
+                for c, j in enumerate(js):
+                    for s_, i in enumerate(set_ids):
+                        mnv["called"][i, t, j] = yes_all[c, s_]
+                mnv["host"] += n_joint_host
             yes, n_host, builds = (got[0], got[2], got[3]) if axis is not None else (got[0], got[1], 1)
             for c, j in enumerate(js):
                 for g, k in enumerate(group):

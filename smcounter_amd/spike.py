@@ -790,7 +790,10 @@ def scan(args):
     than MAX_CELLS targets x reads-per-barcode targets.
     --spikeScanFilter (a switch) adds "filter": True.  SystemExit: the switch without --spikeScan.
     --spikeScanBuild listed adds "build": "listed" (`whole`, the default, adds nothing: scan_build reads it).  SystemExit: the flag
-    without --spikeScan, a value that is neither whole nor listed."""
+    without --spikeScan, a value that is neither whole nor listed.
+    --spikeScanMnv L adds "mnv": L, the letters of the MNV planted at every locus in place of the SNV.  SystemExit: the flag without
+    --spikeScan, L no integer in 2 .. 8, a stride below L, the flag beside --spikeScanIndel, or beside --spikeScanDepth, --spikeScanRpb
+    or --spikeScanFilter (not built)."""
     from .tools import spike_scan_lists as lists
     text, r, stride, alt = (getattr(args, f, None) for f in SCAN_FLAGS)
     indel = getattr(args, "spikeScanIndel", None)
@@ -798,10 +801,12 @@ def scan(args):
     rpbs = getattr(args, "spikeScanRpb", None)
     flt = getattr(args, "spikeScanFilter", None)
     build = getattr(args, "spikeScanBuild", None)
+    mnv = getattr(args, "spikeScanMnv", None)
     given = lambda x: x not in (None, "", False)
     if not given(text):
-        for flag, value in zip(SCAN_FLAGS[1:] + ("spikeScanIndel", "spikeScanDepth", "spikeScanRpb", "spikeScanFilter", "spikeScanBuild"),
-                               (r, stride, alt, indel, fracs, rpbs, flt, build)):
+        for flag, value in zip(SCAN_FLAGS[1:] + ("spikeScanIndel", "spikeScanDepth", "spikeScanRpb", "spikeScanFilter", "spikeScanBuild",
+                                                 "spikeScanMnv"),
+                               (r, stride, alt, indel, fracs, rpbs, flt, build, mnv)):
             if given(value):
                 raise SystemExit("--%s belongs to --spikeScan: it needs --spikeScan" % flag)
         return None
@@ -810,6 +815,14 @@ def scan(args):
     if given(indel) and given(alt):
         raise SystemExit("--spikeScanIndel cannot be combined with --spikeScanAlt: the scan plants an insertion or a deletion OR an SNV at "
                          "every locus, not both")
+    if given(mnv):
+        if given(indel):
+            raise SystemExit("--spikeScanMnv cannot be combined with --spikeScanIndel: the scan plants an MNV OR an insertion or a deletion "
+                             "at every locus (indel members in a scan are not built)")
+        for flag, value in (("spikeScanDepth", fracs), ("spikeScanRpb", rpbs), ("spikeScanFilter", flt)):
+            if given(value):
+                raise SystemExit("--spikeScanMnv cannot be combined with --%s: the %s axis of an MNV scan is not built" %
+                                 (flag, {"spikeScanDepth": "depth", "spikeScanRpb": "reads-per-barcode", "spikeScanFilter": "filter"}[flag]))
     for flag in SCAN_NOT_WITH:
         if given(getattr(args, flag, None)):
             raise SystemExit("--spikeScan cannot be combined with --%s in one run: the scan plants its own SNV at every locus of "
@@ -833,6 +846,12 @@ def scan(args):
     if alt not in lists.ALT_RULES:
         raise SystemExit("--spikeScanAlt: one of %s expected, got %r" % (", ".join(sorted(lists.ALT_RULES)), alt))
     out = dict(targets=ts, reps=r, stride=stride, alt=alt)
+    if given(mnv):
+        try:
+            out["mnv"] = lists.parse_mnv(mnv)
+            lists.check_mnv_stride(out["mnv"], stride)
+        except ValueError as e:
+            raise SystemExit(str(e))
     if given(indel):
         try:
             out["indel"] = lists.parse_indel_rule(indel)
@@ -929,6 +948,58 @@ def write_scan(out_prefix: str, loci, variants, targets, entries, lods=None) -> 
                 if i is not None:
                     fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), rates[t][i]))
     with open(out_prefix + ".spikeScan.t95.bedgraph", "w") as fh:
+        for chrom, pos, i in loci:
+            fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "1" if i is None or t95s[i] == dsaf.NA else t95s[i]))
+
+
+# ---- --spikeScanMnv: the scan's pages when an MNV - one phase set of L member SNVs - is planted at every locus
+SCAN_MNV_CURVE_HEADER = ("CHROM", "POS", "REF", "ALT", "N_ALL")
+
+
+def scan_mnv_curve_header(targets):
+    return SCAN_MNV_CURVE_HEADER + curve_header(targets)[len(CURVE_HEADER):]
+
+
+def scan_mnv_variant(pset, variants):
+    """The MNV of set `pset` as one variant at the leader's position: REF and ALT the members' letters."""
+    vs = [variants[k] for k in pset.members]
+    ref, alt = "".join(v.ref for v in vs), "".join(v.alt for v in vs)
+    return af.Variant(vs[0].chrom, vs[0].pos, ref, alt, alt, af.SNV)
+
+
+def write_scan_mnv(out_prefix: str, loci, variants, sets, targets, mt_depth: int, entries) -> None:
+    """The pages of --spikeScanMnv.  `loci`: every locus of the target in order as (chrom, pos, index into `sets` or None for a skipped
+    locus); `variants`: the member SNVs `sets` index; entries[(i, t)]: the replicates of set i at targets[t] as phase_sensitivity_line
+    takes them - (dict(N_ALL, V0_ALL, S_ALL, V1_ALL), CALLED_ALL).
+      <outPrefix>.spikeScan.mnv.sensitivity.txt   PHASE_SENSITIVITY_HEADER, then per scanned leader and target the line the set has at
+                                                  that target, FRACTION `full`, in .spikeAF.phase.sensitivity.txt of the pass's own run
+      <outPrefix>.spikeScan.mnv.curve.txt         CHROM POS REF ALT N_ALL, RATE@<t> ascending, T95: curve_line over the joint verdicts,
+                                                  REF and ALT the L letters, N_ALL the joint barcodes at full depth
+      <outPrefix>.spikeScan<t>.mnv.rate.bedgraph  chrom, pos - 1, pos, RATE of that target - the page's text - at the leader's position
+      <outPrefix>.spikeScan.mnv.t95.bedgraph      chrom, pos - 1, pos, T95 - 1 where it is NA and at a skipped locus, as write_scan
+    No LOD column with --lod: a theoretical limit is a one-locus number."""
+    T = len(targets)
+    rates, t95s = [[] for _ in range(T)], []
+    i_rate, i_t95 = PHASE_SENSITIVITY_HEADER.index("RATE"), len(SCAN_MNV_CURVE_HEADER) + T
+    with open(out_prefix + ".spikeScan.mnv.sensitivity.txt", "w") as fs, open(out_prefix + ".spikeScan.mnv.curve.txt", "w") as fc:
+        fs.write("\t".join(PHASE_SENSITIVITY_HEADER) + "\n")
+        fc.write("\t".join(scan_mnv_curve_header(targets)) + "\n")
+        for i, pset in enumerate(sets):
+            v = scan_mnv_variant(pset, variants)
+            for t, target in enumerate(targets):
+                line = phase_sensitivity_line(pset, variants, target, None, mt_depth, entries[(i, t)])
+                rates[t].append(line.split("\t")[i_rate])
+                fs.write(line + "\n")
+            line = curve_line(v, entries[(i, 0)][0][0]["N_ALL"], targets,
+                              [[scan_entry(v, r, bool(called)) for r, called in entries[(i, t)]] for t in range(T)])
+            t95s.append(line.split("\t")[i_t95])
+            fc.write(line + "\n")
+    for t, target in enumerate(targets):
+        with open("%s.spikeScan%g.mnv.rate.bedgraph" % (out_prefix, target), "w") as fh:
+            for chrom, pos, i in loci:
+                if i is not None:
+                    fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), rates[t][i]))
+    with open(out_prefix + ".spikeScan.mnv.t95.bedgraph", "w") as fh:
         for chrom, pos, i in loci:
             fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "1" if i is None or t95s[i] == dsaf.NA else t95s[i]))
 

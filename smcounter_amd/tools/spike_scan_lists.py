@@ -24,6 +24,16 @@ deletion, S >= 2 for a duplication (indel_min_stride).  A pass is then the run
     --spikeAF <targets> --spikeVariants <outPrefix>.pass<k>.txt --spikeIndelReps R --dsSeed s
 
 and every list written parses under spike_variants.parse_variants(..., indels=True).
+
+--spikeScanMnv L (--mnv here), L in 2 .. 8, plants one MNV of L adjacent letters at every locus P: REF = genome[P .. P+L-1], ALT = the
+--alt rule applied to every letter, one phase set of L member SNVs named chrom:P with P as leader.  A locus is skipped when a position
+of P .. P+L-1 is no locus of the target on that chromosome or its letter is not A, C, G or T.  Pass k holds the leaders with pos mod S
+== k, the footprints of a pass must be disjoint: S >= L (mnv_min_stride).  The lists hold 4-column MNV lines `chrom pos REF ALT`, a
+pass is the run
+
+    --spikeAF <targets> --spikeVariants <outPrefix>.pass<k>.txt --spikeReps R --spikePhase --dsSeed s
+
+and every list written parses under spike_variants.parse_variants(..., phased=True) into sets of exactly L members.
 """
 from __future__ import annotations
 
@@ -121,6 +131,97 @@ def scan_indels(loc_list, fasta, rule):
     return out, skipped
 
 
+MNV_MIN, MNV_MAX = 2, 8       # letters of --spikeScanMnv's MNV (spike_variants.PHASE_MAX_MEMBERS)
+
+
+def parse_mnv(text, flag: str = "--spikeScanMnv") -> int:
+    """L, the letters of the scan's MNV.  ValueError: no integer in MNV_MIN .. MNV_MAX."""
+    try:
+        n = text if isinstance(text, int) and not isinstance(text, bool) else int(str(text).strip())
+    except ValueError:
+        n = None
+    if n is None or not MNV_MIN <= n <= MNV_MAX:
+        raise ValueError("%s: an integer in %d .. %d expected (the letters of the MNV), got %r" % (flag, MNV_MIN, MNV_MAX, text))
+    return n
+
+
+def mnv_min_stride(L: int) -> int:
+    """The smallest stride at which the footprints P .. P+L-1 of a pass are disjoint: L."""
+    return int(L)
+
+
+def check_mnv_stride(L: int, stride: int, flag: str = "--spikeScanStride") -> None:
+    """ValueError: a stride below mnv_min_stride - two MNVs of a pass would share a position."""
+    if int(stride) < mnv_min_stride(L):
+        raise ValueError("%s: a stride of %d with an MNV of %d letters: the footprints of a pass would overlap, the smallest stride "
+                         "allowed is %d" % (flag, int(stride), int(L), mnv_min_stride(L)))
+
+
+def scan_mnvs(loc_list, fasta, L: int, alt: str = DEFAULT_ALT):
+    """scan_variants for --spikeScanMnv: one MNV of L adjacent letters at every locus P - REF = genome[P .. P+L-1], ALT the rule of
+    `alt` applied to every letter - as ONE phase set of L member SNVs named chrom:P, P the leader.
+    -> (spike_variants.PhasedVariants: the member SNVs set by set, in the locus order of the leaders - set i holds the members
+    i*L .. i*L+L-1, so a position stands once per set that covers it -, the leaders (chrom, P) in that order, the (chrom, pos) skipped:
+    a position of P .. P+L-1 that is no locus of `loc_list` on that chromosome, or whose letter is not A, C, G or T).  A locus listed
+    twice counts once; `loc_list` may be out of position order.  ValueError: an unknown rule, L outside MNV_MIN .. MNV_MAX."""
+    from . import spike_variants as sv
+    rule = ALT_RULES.get(alt)
+    if rule is None:
+        raise ValueError("--spikeScanAlt: one of %s expected, got %r" % (", ".join(sorted(ALT_RULES)), alt))
+    L = parse_mnv(L)
+    singles, _ = scan_variants(loc_list, fasta, alt)           # (every locus with a letter of the rule, each once, in locus order)
+    letter = {(v.chrom, v.pos): v for v in singles}
+    members, sets, leaders, skipped, seen = [], [], [], [], set()
+    for chrom, pos in loc_list:
+        pos = int(pos)
+        if (chrom, pos) in seen:
+            continue
+        seen.add((chrom, pos))
+        vs = [letter.get((chrom, pos + x)) for x in range(L)]
+        if any(v is None for v in vs):
+            skipped.append((chrom, pos))
+            continue
+        sets.append(sv.PhaseSet("%s:%d" % (chrom, pos), chrom, tuple(range(len(members), len(members) + L))))
+        leaders.append((chrom, pos))
+        members += vs
+    return sv.PhasedVariants(members, sets), leaders, skipped
+
+
+def mnv_passes(mnvs, stride: int):
+    """scan_passes for scan_mnvs' variants -> [(k, the indices of the SETS of pass k, in the order given)]: pass k holds the leaders
+    with pos mod stride == k."""
+    return scan_passes([mnvs[s.members[0]] for s in mnvs.sets], stride)
+
+
+def mnv_pass_variants(mnvs, set_indices):
+    """The sets `set_indices` of scan_mnvs' variants as a list of their own - what parse_variants(phased=True) reads from the pass's
+    file: a PhasedVariants of their members, set by set."""
+    from . import spike_variants as sv
+    members, sets = [], []
+    for i in set_indices:
+        s = mnvs.sets[i]
+        sets.append(sv.PhaseSet(s.name, s.chrom, tuple(range(len(members), len(members) + len(s.members)))))
+        members += [mnvs[k] for k in s.members]
+    return sv.PhasedVariants(members, sets)
+
+
+def write_mnv_lists(out_prefix: str, mnvs, passes, n_skipped: int):
+    """write_lists for MNVs: a pass file holds one 4-column MNV line `chrom pos REF ALT` per set, REF and ALT the members' letters."""
+    names = []
+    for k, members in passes:
+        names.append("%s.pass%d.txt" % (out_prefix, k))
+        with open(names[-1], "w") as fh:
+            for i in members:
+                vs = [mnvs[m] for m in mnvs.sets[i].members]
+                fh.write("%s\t%d\t%s\t%s\n" % (vs[0].chrom, vs[0].pos, "".join(v.ref for v in vs), "".join(v.alt for v in vs)))
+    with open(out_prefix + ".passes.txt", "w") as fh:
+        fh.write("#k\tvariants\tfile\n")
+        for (k, members), name in zip(passes, names):
+            fh.write("%d\t%d\t%s\n" % (k, len(members), name))
+        fh.write("#skipped\t%d\n" % n_skipped)
+    return names
+
+
 def scan_passes(variants, stride: int):
     """-> [(k, the indices into `variants` of pass k, in the order given)] for every k in 0 .. stride - 1 that holds a locus."""
     stride = int(stride)
@@ -154,6 +255,22 @@ def main(args):
         os.chdir(args.runPath)
     from .. import bedops, fasta as _fasta
     indel = getattr(args, "indel", None)
+    mnv = getattr(args, "mnv", None)
+    if mnv not in (None, ""):
+        if indel not in (None, ""):
+            raise SystemExit("--mnv cannot be combined with --indel: the scan plants an MNV OR an indel at every locus")
+        try:
+            L = parse_mnv(mnv, "--mnv")
+            check_mnv_stride(L, args.stride, "--stride")
+            loc_list, fa = bedops.expand_loci(args.bedTarget), _fasta.FastaFile(args.refGenome)
+            mnvs, _, skipped = scan_mnvs(loc_list, fa, L, args.alt)
+            passes = mnv_passes(mnvs, args.stride)
+        except (ValueError, OSError) as e:
+            raise SystemExit(str(e))
+        names = write_mnv_lists(args.outPrefix, mnvs, passes, len(skipped))
+        print("%d MNVs of %d letters in %d passes of stride %d (%s), %d loci skipped for a position of the footprint that is no locus of "
+              "the target or whose letter is not A, C, G or T" % (len(mnvs.sets), L, len(passes), args.stride, args.alt, len(skipped)))
+        return names
     try:
         loc_list, fa = bedops.expand_loci(args.bedTarget), _fasta.FastaFile(args.refGenome)
         if indel in (None, ""):
@@ -185,6 +302,8 @@ def build_parser():
                         "T>G) or complement (A>T, T>A, C>G, G>C)")
     parser.add_argument("--indel", default=None, help="del<d> or dup<s>, d, s in 1 .. 255: the lists of --spikeScanIndel - a deletion of the "
                         "d letters behind every locus, or a tandem duplication of the next s - for --spikeIndelReps; --alt is not read")
+    parser.add_argument("--mnv", default=None, help="L in 2 .. 8: the lists of --spikeScanMnv - one MNV of L adjacent letters at every "
+                        "locus, --alt applied to every letter, as 4-column MNV lines for --spikeReps --spikePhase; needs --stride >= L")
     parser.add_argument("--outPrefix", default=None, required=True, help="prefix of the files written")
     return parser
 

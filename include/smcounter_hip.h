@@ -1070,6 +1070,24 @@ int smc_scan_detect_keys(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, 
 int smc_scan_filter(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64_t n_loci, const uint32_t* d_offsets,
                     const uint32_t* offsets_host, const uint32_t* d_gate, const uint32_t* gate_host, const uint32_t* d_always,
                     const uint32_t* always_host, int32_t n_listed, uint32_t* d_out, void* stream);
+/* (ABI 11, additive: one entry more, the version number unchanged) --spikeScanMnvFilter: smc_scan_filter when the listed loci are the
+ * members of phase sets, and an MNV is PASS when every member's row is - called right behind smc_scan_detect_sets on the same d_rows.
+ *   d_rows .. n_listed         smc_scan_filter's; d_set_off / set_off_host[n_sets + 1]: smc_scan_detect_sets'.
+ *   d_members[c * n_listed + g]  word for word what smc_scan_filter writes to its d_out.
+ *   d_joint_flt[c * n_sets + s]  one word per (copy, set):
+ *     bits 0 - 13  the OR over the members of their name bits (SMC_SCAN_FLT_NAMES_MASK)
+ *     bit 16 + m   member m's word has at least one name bit: member m is not PASS
+ *     bit 31       SMC_SCAN_FLT_HOST: some member's word has it
+ *   A word means the set's FILTER only where smc_scan_detect_sets' joint verdict is SMC_SCAN_CALLED.  Nothing else is written.
+ * Enqueued on `stream`, one launch of a few thousand lanes (launch latency, not a hot loop); nothing waits; no launch for n_listed = 0
+ * or n_copies = 0.  SMC_E_INPUT, nothing launched: what smc_scan_filter refuses; a NULL set_off_host (whatever n_listed is: it has
+ * n_sets + 1 entries), a NULL d_set_off, d_members or d_joint_flt with n_listed > 0; offsets that do not tile the listed loci; a set of
+ * 0 members or of more than SMC_SPIKE_PHASE_MAX_MEMBERS; n_copies * n_sets of 2^31 or more. */
+#define SMC_SCAN_FLT_MEMBER_SHIFT 16
+int smc_scan_filter_sets(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64_t n_loci, const uint32_t* d_offsets,
+                         const uint32_t* offsets_host, const uint32_t* d_gate, const uint32_t* gate_host, const uint32_t* d_always,
+                         const uint32_t* always_host, int32_t n_listed, const uint32_t* d_set_off, const uint32_t* set_off_host,
+                         int32_t n_sets, uint32_t* d_members, uint32_t* d_joint_flt, void* stream);
 /* number of kernel launches one smc_plan_run issues, and bytes of device scratch it holds */
 int smc_plan_info(const smc_plan* plan, int32_t* n_launches, int64_t* scratch_bytes);
 

@@ -91,6 +91,28 @@ SCAN_ID_NONE, SCAN_ID_HOST = 0xFFFFFFFF, 0xFFFFFFFE
 F_REPT, F_REPS, F_SL, F_OTHER_REPEAT = 0x400, 0x800, 0x1000, 0x2000
 SCAN_FILTER_NAMES = FILTER_NAMES + ((F_REPT, "RepT"), (F_REPS, "RepS"), (F_SL, "SL"), (F_OTHER_REPEAT, "Other_Repeat"))
 SCAN_FLT_DEVICE_MASK, SCAN_FLT_NAMES_MASK, SCAN_FLT_HOST = 0x3FF, 0x3FFF, 0x80000000
+# (smc_scan_filter_sets) a joint FILTER word: the OR of the members' name bits, bit 16 + m where member m is not PASS, bit 31 where a
+# member's word has it
+SCAN_FLT_MEMBER_SHIFT = 16
+
+
+def scan_filter_joint_rule(member_words, set_off):
+    """smc_scan_filter_sets' joint rule in numpy.  member_words: uint32 [B, G], smc_scan_filter's words of the members; set_off:
+    [n_sets + 1], the sets' tiling of the G members -> uint32 [B, n_sets]: the joint words."""
+    member_words = np.asarray(member_words, np.uint32)
+    B, G = member_words.shape
+    off = np.asarray(set_off, np.int64)
+    words = np.zeros((B, len(off) - 1), np.uint32)
+    for c in range(B):
+        for s in range(len(off) - 1):
+            w = 0
+            for m, g in enumerate(range(int(off[s]), int(off[s + 1]))):
+                mw = int(member_words[c, g])
+                w |= mw & (SCAN_FLT_NAMES_MASK | SCAN_FLT_HOST)
+                if mw & SCAN_FLT_NAMES_MASK:
+                    w |= 1 << (SCAN_FLT_MEMBER_SHIFT + m)
+            words[c, s] = w
+    return words
 
 
 def c_params(p: VcParams) -> SmcParams:

@@ -341,7 +341,30 @@ def build_parser() -> argparse.ArgumentParser:
                         "(smc_scan_detect_sets).  Writes <outPrefix>.spikeScan.mnv.sensitivity.txt (the sets' lines of "
                         ".spikeAF.phase.sensitivity.txt), .spikeScan.mnv.curve.txt, <outPrefix>.spikeScan<t>.mnv.rate.bedgraph and "
                         ".spikeScan.mnv.t95.bedgraph in place of the SNV scan's pages; no LOD column with --lod.  Needs --spikeScan; beside "
-                        "--spikeScanBuild; not with --spikeScanIndel, --spikeScanDepth, --spikeScanRpb or --spikeScanFilter (not built)")
+                        "--spikeScanBuild, --spikeScanMnvFilter and --spikeScanMnvDepth; not with --spikeScanIndel, --spikeScanDepth, --spikeScanRpb or "
+                        "--spikeScanFilter (not built)")
+    p.add_argument("--spikeScanMnvFilter", action="store_true", default=False,
+                   help="--spikeScanMnv's rates over the replicates in which every member SNV is called AND every member's FILTER is "
+                        "PASS, and which flags took the others away - by definition the FILTER and CALLED columns of the members' lines "
+                        "in the pass's own .spikeAF.replicates.txt.  Behind every joint verdict the GPU decides the joint FILTER word of "
+                        "the set on the same rows (smc_scan_filter_sets: the OR of the members' names, and which members are not PASS; "
+                        "4 bytes per copy and set come down).  Writes <outPrefix>.spikeScan.mnv.filter.txt (REPS, CALLED_ALL, PASS_ALL, "
+                        "RATE_PASS with its interval, and per FILTER name the called replicates in which a member holds it), "
+                        ".spikeScan.mnv.filter.curve.txt (RATE_PASS at every target and T95_PASS), "
+                        "<outPrefix>.spikeScan<t>.mnv.passrate.bedgraph and .spikeScan.mnv.t95pass.bedgraph.  Every other file of the MNV "
+                        "scan stays as it is.  Needs --spikeScanMnv")
+    p.add_argument("--spikeScanMnvDepth", default=None,
+                   help="f1,f2,...: --spikeScanMnv also at these barcode fractions, each in (0, 1] and none listed twice: only barcodes that "
+                        "cover ALL members carry an MNV, so N_ALL falls faster than N at amplicon ends.  A pass is then by definition its "
+                        "run with --spikeDepth <fractions> beside --spikeReps --spikePhase: cell (t, f) is called at max(1, round(f x "
+                        "mtDepth)) with its own threshold, and the set's cell line of that run's .spikeAF.phase.sensitivity.txt is the "
+                        "definition.  The joint counts of every cell come from the one smc_spike_phase_counts call per pass, the copies of a "
+                        "batch are selected at every fraction by one smc_select_alignments_copies call.  Writes "
+                        "<outPrefix>.spikeScan.mnv.depth.sensitivity.txt, .spikeScan.mnv.depth.curve.txt, .spikeScan.mnv.depth.need.txt "
+                        "(F95 over the joint rates, N95 the mean N_ALL there), <outPrefix>.spikeScan<t>.dsMT<f>.mnv.rate.bedgraph, "
+                        ".spikeScan.dsMT<f>.mnv.t95.bedgraph and .spikeScan<t>.mnv.f95.bedgraph (2 where full depth fails); with "
+                        "--spikeScanMnvFilter also .spikeScan.mnv.depth.filter.txt; targets x fractions at most %d; no LOD column with "
+                        "--lod.  Needs --spikeScanMnv" % GRID_MAX_CELLS)
     p.add_argument("--spikeScanBuild", default=None,
                    help="whole (default) or listed: how --spikeScan builds its spiked copies.  whole: every copy is a build of its whole "
                         "decoded run, however few of its loci the pass lists.  listed: one smc_build_listed call builds the listed loci "
@@ -823,6 +846,10 @@ def _spike_scan(args, plan, ref, eng, params):
     if "fracs" in scan:
         cells = [dataclasses.replace(params, mtDepth=_spike.scan_depth_mt(params.mtDepth, f)) for f in scan["fracs"]]
         depth = dict(fracs=scan["fracs"], params=cells, thresholds=[writers.pi_threshold(c.mtDepth, args.threshold) for c in cells])
+    mnv_axes = dict(flt=True) if "mnv_filter" in scan else {}
+    if "mnv_fracs" in scan:
+        cells = [dataclasses.replace(params, mtDepth=_spike.scan_depth_mt(params.mtDepth, f)) for f in scan["mnv_fracs"]]
+        mnv_axes["depth"] = dict(fracs=scan["mnv_fracs"], params=cells, thresholds=[writers.pi_threshold(c.mtDepth, args.threshold) for c in cells])
     rpb = None
     if "rpbs" in scan:
         # (a cell is called at the scan's mtDepth with --rpb r: the cut is the scan's own)
@@ -834,7 +861,8 @@ def _spike_scan(args, plan, ref, eng, params):
                                    sampler_seed=getattr(args, "samplerSeed", 0), indel="indel" in scan, depth=depth, rpb=rpb,
                                    **(dict(flt=True) if "filter" in scan else {}),
                                    **(dict(build="listed") if _spike.scan_build(scan) == "listed" else {}),
-                                   **(dict(mnv=scan["mnv"]) if "mnv" in scan else {}))
+                                   **(dict(mnv=scan["mnv"]) if "mnv" in scan else {}),
+                                   **(dict(mnv_axes=mnv_axes) if mnv_axes else {}))
     except (ValueError, bamio.BamError) as e:
         raise SystemExit(str(e))
     listed = _spike.scan_build(scan) == "listed"
@@ -1462,8 +1490,31 @@ def _scan_mnv_reports(args, plan, shard):
           "called, %d of %d verdicts decided by the host, stage %.3f s" %
           (len(sets), len(targets), R, len(scan["passes"]), tm["runs"], tm["decode"], sum(st["builds"] for st in out["passes"]),
            sum(st["host"] for st in out["passes"]), len(variants) * len(targets) * R, tm["stage"]))
-    print("--spikeScanMnv %d: %d sets scanned, %d loci skipped, %d of %d joint verdicts decided by the host" %
-          (scan["mnv"], len(sets), len(scan["skipped"]), out["joint_host"], len(sets) * len(targets) * R))
+    closing = "--spikeScanMnv %d: %d sets scanned, %d loci skipped, %d of %d joint verdicts decided by the host" % \
+        (scan["mnv"], len(sets), len(scan["skipped"]), out["joint_host"], len(sets) * len(targets) * R * (1 + len(scan.get("mnv_fracs", ()))))
+    mt_depth, fracs = plan.outputs[0].params.mtDepth, scan.get("mnv_fracs")
+    if fracs is not None:
+        cells = {(i, t, f): [(dict(zip(_spike.PHASE_NAMES, (int(x) for x in out["joint_depth_counts"][i, j, t, f]))),
+                              int(out["joint_depth_called"][i, t, f, j])) for j in range(R)]
+                 for i in range(len(sets)) for t in range(len(targets)) for f in range(len(fracs))}
+        _spike.write_scan_mnv_depth(args.outPrefix, scan["loci"], variants, sets, targets, fracs, mt_depth, entries, cells)
+    if "mnv_filter" in scan:
+        _spike.write_scan_mnv_filter(args.outPrefix, scan["loci"], variants, sets, targets, [int(out["joint_counts"][i, 0, 0, 0]) for i in range(len(sets))],
+                                     out["joint_called"], out["joint_filter"])
+        held = [(out["joint_called"], out["joint_filter"] & np.uint32(abi.SCAN_FLT_NAMES_MASK))]
+        if fracs is not None:
+            _spike.write_scan_filter_cells(args.outPrefix, [_spike.scan_mnv_variant(ps, variants) for ps in sets], targets, fracs,
+                                           [_spike.scan_depth_mt(mt_depth, f) for f in fracs], out["joint_depth_called"], out["joint_depth_filter"],
+                                           mnv=True)
+            held.append((out["joint_depth_called"], out["joint_depth_filter"] & np.uint32(abi.SCAN_FLT_NAMES_MASK)))
+        closing += "; --spikeScanMnvFilter: %d of %d called sets PASS, the FILTER of %d decided by the host; %s" % \
+            (sum(int((c & (w == 0)).sum()) for c, w in held), sum(int(c.sum()) for c, _ in held), out["joint_filter_host"],
+             ", ".join("%s %d" % (name, sum(int((c & ((w & bit) != 0)).sum()) for c, w in held)) for bit, name in abi.SCAN_FILTER_NAMES))
+    if fracs is not None:
+        closing += "; --spikeScanMnvDepth: fractions %s: %d cells per pass, %d builds (S x R x T x (1 + F)), %d select_copies calls" % \
+            (",".join("%g" % f for f in fracs), len(targets) * len(fracs), sum(st["builds"] for st in out["passes"]),
+             sum(st["selects"] for st in out["passes"]))
+    print(closing)
 
 
 def _scan_filter_reports(args, plan, shard):

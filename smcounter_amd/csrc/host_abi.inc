@@ -1815,6 +1815,55 @@ int smc_scan_filter(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64
     return SMC_OK;
 }
 
+// (--spikeScanMnvFilter) smc_scan_filter with the listed loci tiled by phase sets: smc_scan_filter's checks and smc_scan_detect_sets'
+// of the offsets on the host copies before anything is enqueued, then one launch (none for an empty list or no copy)
+int smc_scan_filter_sets(smc_ctx* ctx, const smc_row* d_rows, int32_t n_copies, int64_t n_loci, const uint32_t* d_offsets,
+                         const uint32_t* offsets_host, const uint32_t* d_gate, const uint32_t* gate_host, const uint32_t* d_always,
+                         const uint32_t* always_host, int32_t n_listed, const uint32_t* d_set_off, const uint32_t* set_off_host,
+                         int32_t n_sets, uint32_t* d_members, uint32_t* d_joint_flt, void* stream) {
+    const std::string who = "smc_scan_filter_sets";
+    if (!ctx || n_copies < 0 || n_loci < 0 || n_listed < 0 || n_sets < 0) return fail(SMC_E_ARG, who + ": bad argument");
+    if (!set_off_host) return fail(SMC_E_INPUT, who + ": NULL argument: the sets' offsets");
+    if (n_listed && (!d_rows || !d_offsets || !offsets_host || !d_gate || !gate_host || !d_always || !always_host || !d_set_off ||
+                     !d_members || !d_joint_flt))
+        return fail(SMC_E_INPUT, who + ": NULL argument with " + std::to_string(n_listed) + " listed loci");
+    if (n_copies > 65535) return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies, at most 65535");
+    if ((int64_t)n_copies * (int64_t)n_listed >= (1ll << 31) || (int64_t)n_copies * n_loci >= (1ll << 31) ||
+        (int64_t)n_copies * (int64_t)n_sets >= (1ll << 31))
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_copies) + " copies of " + std::to_string(n_loci) + " loci, " +
+                                 std::to_string(n_listed) + " listed in " + std::to_string(n_sets) + " sets: 2^31 words, rows or sets, or more");
+    const uint32_t gate_ok = SMC_F_HP | SMC_F_LOWC, always_ok = SMC_F_LOWC | SMC_F_REPT | SMC_F_REPS | SMC_F_SL | SMC_F_OTHER_REPEAT;
+    for (int32_t g = 0; g < n_listed; ++g) {
+        if ((int64_t)offsets_host[g] >= n_loci)
+            return fail(SMC_E_INPUT, who + ": listed locus " + std::to_string(g) + " names offset " + std::to_string(offsets_host[g]) +
+                                     " of " + std::to_string(n_loci));
+        if (gate_host[g] & ~gate_ok)
+            return fail(SMC_E_INPUT, who + ": listed locus " + std::to_string(g) + " has gate bits " + std::to_string(gate_host[g]) +
+                                     ", HP and LowC expected");
+        if (always_host[g] & ~always_ok)
+            return fail(SMC_E_INPUT, who + ": listed locus " + std::to_string(g) + " has always bits " + std::to_string(always_host[g]) +
+                                     ", LowC and the repeat names expected");
+    }
+    if (set_off_host[0] != 0u || (int64_t)set_off_host[n_sets] != (int64_t)n_listed)
+        return fail(SMC_E_INPUT, who + ": the sets' offsets run from " + std::to_string(set_off_host[0]) + " to " + std::to_string(set_off_host[n_sets]) +
+                                 ", they must tile the " + std::to_string(n_listed) + " listed loci");
+    for (int32_t s = 0; s < n_sets; ++s) {
+        const int64_t m = (int64_t)set_off_host[s + 1] - (int64_t)set_off_host[s];
+        if (m < 1 || m > SMC_SPIKE_PHASE_MAX_MEMBERS)
+            return fail(SMC_E_INPUT, who + ": set " + std::to_string(s) + " has " + std::to_string(m) + " members, 1 .. " +
+                                     std::to_string(SMC_SPIKE_PHASE_MAX_MEMBERS) + " expected");
+    }
+    if (!n_listed || !n_copies) return SMC_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    const double edge = 4.995;
+    const int64_t per_block = SCD_BLOCK / SCD_SET_LANES;
+    hipLaunchKernelGGL(k_scan_filter_sets, dim3((unsigned)std::min<int64_t>(((int64_t)n_sets + per_block - 1) / per_block, 1024), (unsigned)n_copies),
+                       dim3(SCD_BLOCK), 0, (hipStream_t)stream, d_rows, (uint32_t)n_loci, d_offsets, d_gate, d_always, (uint32_t)n_listed,
+                       d_set_off, (uint32_t)n_sets, edge - 1e-6, edge + 1e-6, d_members, d_joint_flt);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+
 // (--spikeScanIndel) smc_scan_detect for lists whose members are allele keys: the same checks, and those of the listed records, of the
 // strides and of the pool, on the host copies before anything is enqueued; then the cursor zeroed and three launches (none for an
 // empty list or no copy)

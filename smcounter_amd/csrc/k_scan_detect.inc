@@ -232,21 +232,64 @@ __global__ __launch_bounds__(SCD_BLOCK) void k_sdk_detect(const smc_row* __restr
 //                  printed is chosen with the genome in hand), PI NaN or inside the band, flt_applied neither 0 nor 1.
 // The host reads a word only where the detect call's verdict is CALLED (cand[0] is the planted variant there).  Nothing but `out`
 // is written; the verdict records are neither read nor written.  Once per called batch, G x B lanes.
+// The member rule, shared by k_scan_filter and k_scan_filter_sets: the word of (copy c, listed locus g).
+__device__ __forceinline__ uint32_t scf_member(const smc_row* __restrict__ rows, uint32_t n_loci, uint32_t c, uint32_t offset, uint32_t gate,
+                                               uint32_t always, double lo, double hi) {
+    const smc_row* const r = rows + ((size_t)c * n_loci + offset);            // (the host checked the offset < n_loci on its copy)
+    const int32_t status = r->status, bi = r->biallelic;
+    const int32_t applied = r->cand[0].flt_applied, below = r->cand[0].vmf_lt_099;
+    const uint32_t flt = r->cand[0].flt;
+    const double pi = r->cand[0].pi;
+    uint32_t w = 0;
+    if (applied != 0) w = (flt & SMC_SCAN_FLT_DEVICE_MASK) | (below != 0 ? gate : 0u);
+    if (pi > hi) w |= always;
+    if (status != 0 || bi != 0 || !(pi < lo || pi > hi) || (applied != 0 && applied != 1)) w |= SMC_SCAN_FLT_HOST;
+    return w;
+}
+
 __global__ __launch_bounds__(SCD_BLOCK) void k_scan_filter(const smc_row* __restrict__ rows, uint32_t n_loci,
                                                            const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ gate,
                                                            const uint32_t* __restrict__ always, uint32_t n_listed, double lo, double hi,
                                                            uint32_t* __restrict__ out) {
     const uint32_t c = blockIdx.y;
-    for (uint32_t g = blockIdx.x * SCD_BLOCK + threadIdx.x; g < n_listed; g += gridDim.x * SCD_BLOCK) {
-        const smc_row* const r = rows + ((size_t)c * n_loci + offsets[g]);    // (the host checked the offset < n_loci on its copy)
-        const int32_t status = r->status, bi = r->biallelic;
-        const int32_t applied = r->cand[0].flt_applied, below = r->cand[0].vmf_lt_099;
-        const uint32_t flt = r->cand[0].flt;
-        const double pi = r->cand[0].pi;
+    for (uint32_t g = blockIdx.x * SCD_BLOCK + threadIdx.x; g < n_listed; g += gridDim.x * SCD_BLOCK)
+        out[(size_t)c * n_listed + g] = scf_member(rows, n_loci, c, offsets[g], gate[g], always[g], lo, hi);
+}
+
+// ------------------------------------------------------------------------------------------
+// --spikeScanMnvFilter: the FILTER of phase SETS - an MNV is PASS when every member SNV's row is (smc_scan_filter_sets)
+// ------------------------------------------------------------------------------------------
+// The listed loci are tiled by sets as k_scan_detect_sets takes them (the host checked the offsets on its copy).
+//   k_scan_filter_sets  k_scan_detect_sets' geometry: a group of SCD_SET_LANES neighbouring lanes per (copy = blockIdx.y, set), lane m
+//                  takes member m with scf_member - the set's scattered row gathers are in flight together - and writes its word
+//                  exactly as k_scan_filter does.  Each lane makes a word of its name bits, its bit 31, and bit 16 + m where it has a
+//                  name bit (member m is not PASS); three xor-shuffles OR the eight words (the loop's bound is the workgroup's: every
+//                  lane of the wavefront runs every round), and lane 0 of the group writes the joint word with one vector store.
+// No atomics and no list: the host finds the sets it has to print from the joint words' bit 31 themselves.  Nothing but the two
+// outputs is written.  Once per called batch, 8 x sets x B lanes: launch latency, not a hot loop - what it buys is that four bytes per
+// (copy, set) come down and not four per member, and that the joint rule has one home.
+__global__ __launch_bounds__(SCD_BLOCK) void k_scan_filter_sets(const smc_row* __restrict__ rows, uint32_t n_loci,
+                                                                const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ gate,
+                                                                const uint32_t* __restrict__ always, uint32_t n_listed,
+                                                                const uint32_t* __restrict__ set_off, uint32_t n_sets, double lo, double hi,
+                                                                uint32_t* __restrict__ members, uint32_t* __restrict__ joint) {
+    const uint32_t c = blockIdx.y, m = threadIdx.x & (SCD_SET_LANES - 1);
+    const uint32_t per_block = SCD_BLOCK / SCD_SET_LANES;
+    for (uint32_t s0 = blockIdx.x * per_block; s0 < n_sets; s0 += gridDim.x * per_block) {       // (uniform over the workgroup)
+        const uint32_t s = s0 + threadIdx.x / SCD_SET_LANES;
         uint32_t w = 0;
-        if (applied != 0) w = (flt & SMC_SCAN_FLT_DEVICE_MASK) | (below != 0 ? gate[g] : 0u);
-        if (pi > hi) w |= always[g];
-        if (status != 0 || bi != 0 || !(pi < lo || pi > hi) || (applied != 0 && applied != 1)) w |= SMC_SCAN_FLT_HOST;
-        out[(size_t)c * n_listed + g] = w;
+        if (s < n_sets) {
+            const uint32_t first = set_off[s], size = set_off[s + 1] - first;
+            if (m < size) {
+                const uint32_t g = first + m;                                  // (below n_listed: the offsets tile the listed loci)
+                const uint32_t mw = scf_member(rows, n_loci, c, offsets[g], gate[g], always[g], lo, hi);
+                members[(size_t)c * n_listed + g] = mw;
+                w = (mw & (SMC_SCAN_FLT_NAMES_MASK | SMC_SCAN_FLT_HOST)) | ((mw & SMC_SCAN_FLT_NAMES_MASK) ? 1u << (SMC_SCAN_FLT_MEMBER_SHIFT + m) : 0u);
+            }
+        }
+        w |= __shfl_xor(w, 1);
+        w |= __shfl_xor(w, 2);
+        w |= __shfl_xor(w, 4);
+        if (s < n_sets && m == 0) joint[(size_t)c * n_sets + s] = w;
     }
 }

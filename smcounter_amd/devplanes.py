@@ -3765,6 +3765,59 @@ def scan_filter(eng, d_rows, n_copies: int, n_loci: int, offsets, gate_bits, alw
     return out.reshape(B, G)
 
 
+class ScanFilterSets:
+    """What scan_filter_sets uploads, kept on the device for several calls: the listed loci's offsets, gate and always words and the
+    sets' offsets - constants of a pass's variants in a run.  free() when done."""
+
+    def __init__(self, eng, offsets, gate_bits, always_bits, set_off):
+        from .engine import DevBuf
+        G = len(offsets)
+        self.host = np.ascontiguousarray(np.stack([np.asarray(a, np.uint32).reshape(G) for a in (offsets, gate_bits, always_bits)]))
+        self.set_off = np.ascontiguousarray(set_off, np.uint32)
+        self.bufs = [DevBuf(eng, self.host.nbytes + 256).upload(self.host.view(np.uint8).reshape(-1) if G else np.zeros(4, np.uint8)),
+                     _up8(eng, self.set_off)]
+
+    def free(self):
+        for b in self.bufs:
+            b.free()
+        self.bufs = []
+
+
+def scan_filter_sets(eng, d_rows, n_copies: int, n_loci: int, offsets, gate_bits, always_bits, set_off, members_of=None, consts=None):
+    """smc_scan_filter_sets over the rows of a called batch in HBM -> (uint32 [n_copies, n_sets]: the joint FILTER words
+    (abi.scan_filter_joint_rule), uint32 [len(members_of), G]: scan_filter's member words of the copies `members_of` - all of them with
+    None).  offsets, gate_bits, always_bits: scan_filter's; set_off: uint32 [n_sets + 1], the sets' tiling of the listed loci.  One
+    launch; 4 bytes per (copy, set) come down, and 4 per member of the copies asked for - the other member words stay in HBM.
+    `consts` (a ScanFilterSets of the same four arrays): they are on the device already - nothing is uploaded."""
+    from .engine import DevBuf
+    B, G = int(n_copies), len(offsets)
+    mine = consts if consts is not None else ScanFilterSets(eng, offsets, gate_bits, always_bits, set_off)
+    host, set_off = mine.host, mine.set_off
+    if host.shape[1] != G:
+        raise ValueError("scan_filter_sets: the constants hold %d listed loci, the call names %d" % (host.shape[1], G))
+    S, n = len(set_off) - 1, B * G
+    want = list(range(B)) if members_of is None else [int(c) for c in members_of]
+    bufs = list(mine.bufs) + [DevBuf(eng, 4 * max(1, n) + 256), DevBuf(eng, 4 * max(1, B * S) + 256)]
+    try:
+        at = bufs[0].data_ptr()
+        _lib.check(eng.L.smc_scan_filter_sets(eng.ctx, d_rows.data_ptr() if d_rows is not None else None, B, int(n_loci), at,
+                                              host[0].ctypes.data, at + 4 * G, host[1].ctypes.data, at + 8 * G, host[2].ctypes.data, G,
+                                              bufs[1].data_ptr(), set_off.ctypes.data, S, bufs[2].data_ptr(), bufs[3].data_ptr(),
+                                              ctypes.c_void_p(0)), "smc_scan_filter_sets")
+        joint = bufs[3].download(np.uint32, B * S) if B * S and G else np.zeros(B * S, np.uint32)    # (the default stream: behind the kernel)
+        mem = np.zeros((len(want), G), np.uint32)
+        for i, c in enumerate(want if G else ()):
+            if not 0 <= c < B:
+                raise ValueError("scan_filter_sets: the member words of copy %d of %d" % (c, B))
+            bufs[2].download(np.uint32, G, 4 * c * G, out=mem[i])
+    finally:
+        for b in bufs[2:]:
+            b.free()
+        if consts is None:
+            mine.free()
+    return joint.reshape(B, S), mem
+
+
 def _filter_names(word: int) -> str:
     return ";".join(name for bit, name in abi.SCAN_FILTER_NAMES if word & bit) or "PASS"
 
@@ -3816,12 +3869,25 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
     rows of replicate 0 are also made by a whole build of that one copy, and a row that differs in a byte ends the run.
     `mnv` (--spikeScanMnv: dict(set_off: the tiling of run.group by phase sets, var, var_ins: af_run_variants' records of run.group,
     want: per copy and member the counts call's (N, V1), want_joint: per copy and set smc_spike_phase_counts' (N_ALL, V1_ALL)); not
-    with `indel`, `depth`, `rpb` or `flt`): the verdicts come from smc_scan_detect_sets - the joint words, the list and replicate 0's
+    with `indel`, `rpb` or `flt`): the verdicts come from smc_scan_detect_sets - the joint words, the list and replicate 0's
     member records come down, the member verdicts of the other copies are read from the words' bits.  Only the HOST members of sets
     whose joint verdict is HOST are decided by the host; replicate 0's member rows come down anyway, are decided the host way and
     held against the device's member verdicts, and the joint verdict against their AND; replicate 0's (N, V1) per member and (N_ALL,
     V1_ALL) per set are counted a second time, by smc_allele_carriers' cover and carrier bits on the spiked copy and their AND over
-    the members.  mnv["out"] is filled: (bool [copies, sets]: the MNV was called, the joint verdicts the host decided)."""
+    the members.  mnv["out"] is filled: (bool [copies, sets]: the MNV was called, the joint verdicts the host decided).
+    `mnv` with "gate" and "always" (--spikeScanMnvFilter: spike.scan_filter_words' of run.group): behind every smc_scan_detect_sets call
+    smc_scan_filter_sets gives the joint FILTER word per (copy, set) from the same rows; the member words stay in HBM but replicate
+    0's.  The host reads a joint word only where the set ends CALLED.  Every member row of a set whose joint verdict is HOST, and of a
+    set the device calls whose joint FILTER word has abi.SCAN_FLT_HOST, comes down and is printed the existing way; where such a set
+    ends CALLED its joint word is made from the printed rows' FILTER columns (spike.scan_filter_of_text, abi.scan_filter_joint_rule).
+    Replicate 0: the names of each printed row of a called member must be the device's member word, and the joint words
+    abi.scan_filter_joint_rule of the member words.  mnv["flt_out"] is filled: (uint32 [copies, sets]: the joint words without bit 31,
+    meaningful where the set is called, the called sets whose FILTER the host decided).
+    `mnv` beside `depth` (--spikeScanMnvDepth; mnv["want_joint_cells"]: per fraction, copy and set the counts call's (N_ALL', V1_ALL')):
+    `depth`'s cells with the joint verdicts per cell - the ONE select_copies call, every fraction's selections one batch, decided at the
+    cell's params and cut by smc_scan_detect_sets (and smc_scan_filter_sets); replicate 0's (N_ALL', V1_ALL') of every cell is counted
+    a second time, the AND over the members of smc_allele_carriers' bits on its selection.  mnv["out"] and mnv["flt_out"] are LISTS:
+    full depth first, then the cells in order."""
     from . import dsaf, spike as _spike, vc
     from .engine import DevBuf
     A, lo, nl, chrom = run.A, run.lo, run.nl, run.chrom
@@ -3831,6 +3897,7 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
         flag, entry = "--spikeScanMnv", "smc_scan_detect_sets"
     copies = _SpikedCopies(eng, run, svar, part_seeds, thr, P, *((indel["ins"], indel.get("caps")) if indel is not None else ()))
     runs, extras, xbufs, sels = copies.runs, None, [], None
+    fconsts = {}                                # (--spikeScanMnvFilter: scan_filter_sets' constants on the device, by layout)
 
     def decide(kept_runs, Pb, cut, where, key_of, what, shared=False):
         """`kept_runs` built into one batch and called with one plan at params `Pb`; the verdicts at the cut `cut` -> (called, the
@@ -3923,6 +3990,25 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
             if flt is not None:
                 words = scan_filter(eng, d_rows, B, n_rows, spots["offset"], flt["gate"], flt["always"])
                 fhost = set(int(x) for x in np.flatnonzero((called & ((words & abi.SCAN_FLT_HOST) != 0)).reshape(-1)))
+            jflt = mnv is not None and mnv.get("gate") is not None       # (--spikeScanMnvFilter)
+            fsets, seen_of = [], {}
+            if jflt:
+                off = np.asarray(mnv["set_off"], np.int64)
+                # (the offsets, the two words per member and the sets' offsets go up once per layout - the run's offsets, or 0 .. G-1
+                # of a listed build - and serve full depth and every cell)
+                if (xl is not None) not in fconsts:
+                    fconsts[xl is not None] = ScanFilterSets(eng, spots["offset"], mnv["gate"], mnv["always"], mnv["set_off"])
+                words_f, mem0 = scan_filter_sets(eng, d_rows, B, n_rows, spots["offset"], mnv["gate"], mnv["always"], mnv["set_off"],
+                                                 [] if check0 is None else [check0], consts=fconsts[xl is not None])
+                if check0 is not None and not np.array_equal(abi.scan_filter_joint_rule(mem0, mnv["set_off"])[0], words_f[check0]):
+                    raise RuntimeError("--spikeScanMnvFilter: replicate 0 at %s:%d-%d%s: a joint FILTER word is not the joint rule of its "
+                                       "member words" % (chrom, lo + 1, lo + nl, what))
+                # (the sets whose FILTER the host may have to decide: every member row comes down - a set the host has to call, and a
+                # set the device calls whose joint FILTER word has bit 31)
+                jv_f = (words_j >> 30).astype(np.int64)
+                fsets = [(int(c), int(s_)) for c, s_ in zip(*np.nonzero((jv_f == abi.SCAN_HOST) |
+                                                                       ((jv_f == abi.SCAN_CALLED) & ((words_f & abi.SCAN_FLT_HOST) != 0))))]
+                fhost = set(c * G + g for c, s_ in fsets for g in range(int(off[s_]), int(off[s_ + 1])))
             theirs = set(int(x) for x in todo)
             if theirs != (set(int(x) for x in want_list[1]) if mnv is not None else
                           set(int(x) for x in np.flatnonzero(verdict.reshape(-1) == abi.SCAN_HOST))):
@@ -3946,12 +4032,23 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
                     if i in theirs or (mnv is not None and verdict[i // G, i % G] == abi.SCAN_HOST):
                         called[i // G, i % G] = host        # (mnv: replicate 0's HOST member beside a NOT one - not listed, decided anyway)
                     elif host != bool(called[i // G, i % G]):
-                        who = "replicate 0 of" if indel is None else "seed %d at" % int(part_seeds[i // G])
+                        # (only replicate 0's rows come down here beside the host's own - unless the keys of `indel` or the joint
+                        # FILTER words bring rows of other copies down: then the message names the copy's seed)
+                        who = "replicate 0 of" if indel is None and not jflt else "seed %d at" % int(part_seeds[i // G])
                         raise RuntimeError("%s: %s %s:%d %s>%s%s: %s says %s (PI %.17g, threshold %d), the row as "
                                            "the run would print and cut it says %s:\n%s" %
                                            (flag, who, v.chrom, v.pos, v.ref, v.alt, what, entry,
                                             "CALLED" if called[i // G, i % G] else "NOT", float(rec[i // G, i % G]["pi"]),
                                             cut, "called" if host else "not called", line))
+                    if jflt and host:
+                        seen_of[i] = _spike.scan_filter_of_text(dsaf.replicate_entry(line, cut, *repeats)[0][-1])
+                        # (replicate 0: the names of a called member's printed row are the device's member word, unless that has bit 31)
+                        if check0 is not None and i // G == check0 and not int(mem0[0, i % G]) & abi.SCAN_FLT_HOST and \
+                                seen_of[i] != int(mem0[0, i % G]) & abi.SCAN_FLT_NAMES_MASK:
+                            raise RuntimeError("--spikeScanMnvFilter: seed %d at %s:%d %s>%s%s: smc_scan_filter_sets says %#x (%s), the row "
+                                               "as the run would print it says %#x (%s):\n%s" %
+                                               (int(part_seeds[i // G]), v.chrom, v.pos, v.ref, v.alt, what, int(mem0[0, i % G]),
+                                                _filter_names(int(mem0[0, i % G])), seen_of[i], _filter_names(seen_of[i]), line))
                     if flt is not None and host:
                         seen = _spike.scan_filter_of_text(dsaf.replicate_entry(line, cut, *repeats)[0][-1])
                         if i in theirs or i in fhost:
@@ -3973,7 +4070,16 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
                 if check0 is not None and bool((all_called[check0] & (jv[check0] == abi.SCAN_NOT)).any()):
                     raise RuntimeError("%s: replicate 0 at %s:%d-%d%s: a set whose members the host all calls has the joint verdict NOT" %
                                        (flag, chrom, lo + 1, lo + nl, what))
-                mnv["out"] = (all_called & (jv != abi.SCAN_NOT), int((jv == abi.SCAN_HOST).sum()))
+                mnv["out"].append((all_called & (jv != abi.SCAN_NOT), int((jv == abi.SCAN_HOST).sum())))
+                if jflt:
+                    # (a called set whose FILTER the host decides: its joint word from the printed rows' FILTER columns)
+                    n_jhost = 0
+                    for c, s_ in fsets:
+                        if mnv["out"][-1][0][c, s_]:
+                            mine_w = [[seen_of[c * G + g] for g in range(int(off[s_]), int(off[s_ + 1]))]]
+                            words_f[c, s_] = abi.scan_filter_joint_rule(mine_w, [0, len(mine_w[0])])[0, 0]
+                            n_jhost += 1
+                    mnv["flt_out"].append((words_f & np.uint32(~abi.SCAN_FLT_HOST & 0xFFFFFFFF), n_jhost))
             return called, len(theirs)
         finally:
             if plan is not None:
@@ -3985,6 +4091,8 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
                 k.free()
     if flt is not None:
         flt["out"] = []                         # (a narrower retry starts over)
+    if mnv is not None:
+        mnv["out"], mnv["flt_out"] = [], []     # (per batch decided: full depth first, then the cells in order)
     try:
         if indel is not None and copies.totals[:, 2].any():
             raise _lib.SmcError("smc_spike_indels_reps: a copy of %s:%d-%d did not fit spike_indel_caps' bounds" % (chrom, lo + 1, lo + nl))
@@ -4017,12 +4125,21 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
             axis, cell_flag = [" x --spikeScanRpb %g" % r for r in rpb["targets"]], "--spikeScanRpb"
         else:
             sels = select_copies(eng, runs, A, lo, run.idents, part_seeds, depth["fracs"])
-            axis, cell_flag = [" x fraction %g" % f for f in depth["fracs"]], "--spikeScanDepth"
+            axis, cell_flag = [" x fraction %g" % f for f in depth["fracs"]], "--spikeScanDepth" if mnv is None else "--spikeScanMnvDepth"
         of_cell, n_host = [], full[1]
         for f, what in enumerate(axis):
             if check0 is not None:
                 sel, counts, _ = sels.of[f][check0]
-                copies.check_carriers(check0, sel, counts, cells["want"][f][check0], cells["var"], cells["var_ins"], variants, cell_flag, what)
+                cov1, car1 = copies.check_carriers(check0, sel, counts, cells["want"][f][check0], cells["var"], cells["var_ins"], variants,
+                                                   cell_flag, what)
+                for s_, (a, b) in enumerate(zip(mnv["set_off"][:-1], mnv["set_off"][1:]) if mnv is not None else ()):
+                    mine = (int(cov1[a:b].all(axis=0).sum()), int(car1[a:b].all(axis=0).sum()))
+                    if mine != tuple(int(x) for x in mnv["want_joint_cells"][f][check0][s_]):
+                        v = variants[run.group[int(a)]]
+                        raise RuntimeError("%s: seed %d, the set at %s:%d%s: the AND of the selection's cover and carrier bits holds (N_ALL', "
+                                           "V1_ALL') = %r, the counts call says %r" %
+                                           (cell_flag, int(part_seeds[check0]), v.chrom, v.pos, what, mine,
+                                            tuple(int(x) for x in mnv["want_joint_cells"][f][check0][s_])))
             kept = [_KeptRun(*sels.of[f][c], A, run.bam.allele_key, run.bam.barcode_name, lambda n: run.idents,
                              copy=runs[c] if indel is not None else None, by_read=rpb is not None) for c in range(B)]
             where = None
@@ -4038,7 +4155,7 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
             n_host += cell[1]
         return full[0], of_cell, n_host, 1 + len(of_cell)
     finally:
-        for b in xbufs:
+        for b in xbufs + list(fconsts.values()):
             b.free()
         if sels is not None:
             sels.free()
@@ -4047,7 +4164,7 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
 
 def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n_reps: int, eng, threshold: int, repeats,
                sampler: str = "reference", sampler_seed: int = 0, nthreads: int = 0, max_reads: int = 128_000_000, indel: bool = False,
-               depth: dict = None, rpb: dict = None, flt: bool = False, build: str = "whole", mnv: int = 0):
+               depth: dict = None, rpb: dict = None, flt: bool = False, build: str = "whole", mnv: int = 0, mnv_axes: dict = None):
     """The stage of --spikeScan.  variants: the scan's SNV at every scanned locus (tools.spike_scan_lists.scan_variants); passes: [(k,
     the indices of pass k)] (scan_passes).  A pass is the run --spikeAF <targets> --spikeVariants <its list> --spikeReps n_reps --dsSeed
     seed: replicate j has seed (seed + j) mod 2^64, and the draws, the rewrite, NM and the thresholds are that run's.
@@ -4092,6 +4209,15 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     (N_ALL, V0_ALL, S_ALL, V1_ALL), joint_called: bool [sets, T, R] and joint_host: the joint verdicts the host decided; base and
     counts are per member, `called` holds the member verdicts only as far as a joint verdict needed them.  ValueError: beside `indel`,
     `depth`, `rpb` or `flt` (not built).
+    `mnv_axes` (--spikeScanMnvFilter: dict(flt=True); only with `mnv`): the two words of every member SNV are made once
+    (spike.scan_filter_words), and behind every smc_scan_detect_sets call smc_scan_filter_sets decides the joint FILTER word per (copy,
+    set) on the same rows (_scan_call's `mnv` with "gate").  The result gets joint_filter: uint32 [sets, T, R] - the OR of the members'
+    14 name bits, bit abi.SCAN_FLT_MEMBER_SHIFT + m where member m is not PASS, where joint_called - and joint_filter_host: the called
+    sets whose FILTER the host decided.  `mnv_axes["depth"]` (--spikeScanMnvDepth: the dict `depth=` takes): a pass is then the run
+    with --spikeDepth <fracs> beside --spikeReps --spikePhase; the stage runs `depth`'s cells with the joint verdicts per cell, the joint
+    counts of every (set, replicate, target, fraction) from the ONE smc_spike_phase_counts call per pass and run.  The result gets
+    joint_depth_counts: uint32 [sets, R, T, F, 4], joint_depth_called: bool [sets, T, F, R], with flt joint_depth_filter: uint32 [sets,
+    T, F, R], and depth's own depth_counts / depth_called per member.  ValueError: without `mnv`; any other key.
     -> dict(seeds, base: per variant (N, V0), counts: uint32 [V, R, T, 3] = (S, READS, V1), called: bool [V, T, R], passes: per pass
     of `passes` dict(variants, copies, builds, host, seconds), times: dict(stage, runs, decode))."""
     import time
@@ -4103,6 +4229,13 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
         raise ValueError("--spikeScan: %d targets, at most %d" % (T, SPIKE_MAX_TARGETS))
     if mnv and (indel or depth is not None or rpb is not None or flt):
         raise ValueError("--spikeScanMnv: indel members and the depth, reads-per-barcode and filter axes of an MNV scan are not built")
+    mnv_axes = dict(mnv_axes or {})
+    if mnv_axes and not mnv:
+        raise ValueError("--spikeScanMnvFilter: the axes of an MNV scan need --spikeScanMnv")
+    if set(mnv_axes) - {"flt", "depth"}:
+        raise ValueError("--spikeScanMnv: the reads-per-barcode axis of an MNV scan is not built")
+    if mnv_axes.get("depth") is not None:
+        depth = mnv_axes["depth"]               # (the cells are --spikeScanDepth's: one select_copies call, a batch per fraction)
     seeds = dsaf.rep_seeds(seed, R)
     thr = [sv.threshold(t) for t in targets]
     P = params
@@ -4122,6 +4255,15 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
                 local[list(sets[i].members)] = r * mnv + np.arange(mnv)
         spikes = [SpikeSet(lists.mnv_pass_variants(variants, members)) for _, members in passes]
         mnv = dict(L=int(mnv), set_of=set_of, counts=np.zeros((len(sets), R, T, 4), np.uint32), called=np.zeros((len(sets), T, R), bool), host=0)
+        if mnv_axes.get("flt"):
+            from . import spike as _spike
+            gate, always = _spike.scan_filter_words(variants, params.hpLen, fasta, *repeats)
+            mnv["flt"] = dict(gate=gate, always=always, words=np.zeros((len(sets), T, R), np.uint32), host=0)
+        if depth is not None:
+            Fm = len(depth["fracs"])
+            mnv.update(cell_counts=np.zeros((len(sets), R, T, Fm, 4), np.uint32), cell_called=np.zeros((len(sets), T, Fm, R), bool))
+            if mnv.get("flt"):
+                mnv["flt"]["cell_words"] = np.zeros((len(sets), T, Fm, R), np.uint32)
     else:
         mnv = None
         for p, (_, members) in enumerate(passes):
@@ -4213,6 +4355,12 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
                    rpb_rules=[dict(seed=r.seed, prob_keep=r.prob_keep, thr=r.thr, n_kept=r.n_kept, n_names=r.n_names) for r in read_rules])
     if mnv is not None:
         out.update(joint_counts=mnv["counts"], joint_called=mnv["called"], joint_host=mnv["host"])
+        if mnv.get("flt"):
+            out.update(joint_filter=mnv["flt"]["words"], joint_filter_host=mnv["flt"]["host"])
+        if depth is not None:
+            out.update(joint_depth_counts=mnv["cell_counts"], joint_depth_called=mnv["cell_called"])
+            if mnv.get("flt"):
+                out["joint_depth_filter"] = mnv["flt"]["cell_words"]
     if flt is not None:
         out.update(filter=flt["words"], filter_host=flt["host"])
         if (depth or rpb) is not None:
@@ -4266,7 +4414,10 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
     `mnv` (--spikeScanMnv: spike_scan's dict with "L", "set_of", "counts", "called" and "host"): run.group holds the members of whole
     phase sets of L, set by set; the joint barcodes of every set come from spike_joint and (N_ALL, V0_ALL, S_ALL, V1_ALL) of every set,
     replicate and target from ONE smc_spike_phase_counts call; per batch the joint verdicts (_scan_call's `mnv`).  `called` holds the
-    member verdicts as far as a joint verdict needed them."""
+    member verdicts as far as a joint verdict needed them.  With mnv["flt"] (--spikeScanMnvFilter: dict(gate, always, words, host)) per
+    batch the joint FILTER words of the copies (_scan_call's `mnv` with "gate"); "words", "cell_words" and "host" are filled.  With
+    `depth` beside it (--spikeScanMnvDepth) the ONE smc_spike_phase_counts call also takes the fractions' thresholds and gives (N_ALL',
+    V0_ALL', S_ALL', V1_ALL') of every cell: mnv["cell_counts"] and mnv["cell_called"] are filled."""
     A, up, lo, chrom = run.A, run.up, run.lo, run.chrom
     idents, (nm, n_indel) = run.idents, run.mism
     group = run.group
@@ -4304,10 +4455,15 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
         set_off = np.arange(0, len(group) + 1, mnv["L"], dtype=np.uint32)
         first = [int(a) for a in set_off[:-1]]
         joint = spike_joint([sv.PhaseSet("", chrom, tuple(range(a, a + mnv["L"]))) for a in first], covers, counters)
-        joint_counts = spike_phase_counts(eng, [lead[a] for a in first], joint, seeds, thr, [1 << 32])[:, :, :, 0]     # [sets, R, T, 4]
+        # (ONE call: full depth - the threshold 2^32 keeps every barcode - and behind it the cells of --spikeScanMnvDepth)
+        joint_all = spike_phase_counts(eng, [lead[a] for a in first], joint, seeds, thr,
+                                       [1 << 32] + ([frac_threshold(f) for f in depth["fracs"]] if depth is not None else []))
+        joint_counts, joint_cells = joint_all[:, :, :, 0], joint_all[:, :, :, 1:]      # [sets, R, T, 4], [sets, R, T, F, 4]
         set_ids = [int(mnv["set_of"][group[a]]) for a in first]
         for s_, i in enumerate(set_ids):
             mnv["counts"][i] = joint_counts[s_]
+            if depth is not None:
+                mnv["cell_counts"][i] = joint_cells[s_]
     for t in range(len(thr)):
         for b in range(0, R, room):
             js = list(range(b, min(R, b + room)))
@@ -4328,10 +4484,13 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
             fl = dict(gate=flt["gate"][group], always=flt["always"][group]) if flt is not None else None
             more = {}
             if mnv is not None:
-                more["mnv"] = dict(set_off=set_off, var=var, var_ins=ins,
+                more["mnv"] = dict(**(dict(gate=mnv["flt"]["gate"][group], always=mnv["flt"]["always"][group]) if mnv.get("flt") else {}),
+                                   set_off=set_off, var=var, var_ins=ins,
                                    want=[[(len(covers[g]), int(mine[g, j, t, 2])) for g in range(len(group))] for j in js],
                                    want_joint=[[(int(joint_counts[s_, j, t, 0]), int(joint_counts[s_, j, t, 3])) for s_ in range(len(first))]
-                                               for j in js])
+                                               for j in js],
+                                   want_joint_cells=[[[(int(joint_cells[s_, j, t, f, 0]), int(joint_cells[s_, j, t, f, 3]))
+                                                       for s_ in range(len(first))] for j in js] for f in range(F)])
             if listed_build:
                 before = {k: stat[k] for k in ("listed", "whole", "checks")}
 
@@ -4342,11 +4501,19 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
                 call = lambda bits: _scan_call(*args, bits, *tail, flt=fl, **more)
             got = _narrow_retry(eng, P, call)
             if mnv is not None:
-                yes_all, n_joint_host = more["mnv"]["out"]
+                outs, fouts = more["mnv"]["out"], more["mnv"]["flt_out"]
                 for c, j in enumerate(js):
                     for s_, i in enumerate(set_ids):
-                        mnv["called"][i, t, j] = yes_all[c, s_]
-                mnv["host"] += n_joint_host
+                        mnv["called"][i, t, j] = outs[0][0][c, s_]
+                        for f in range(F):
+                            mnv["cell_called"][i, t, f, j] = outs[1 + f][0][c, s_]
+                        if mnv.get("flt"):
+                            mnv["flt"]["words"][i, t, j] = fouts[0][0][c, s_]
+                            for f in range(F):
+                                mnv["flt"]["cell_words"][i, t, f, j] = fouts[1 + f][0][c, s_]
+                mnv["host"] += sum(n for _, n in outs)
+                if mnv.get("flt"):
+                    mnv["flt"]["host"] += sum(n for _, n in fouts)
             yes, n_host, builds = (got[0], got[2], got[3]) if axis is not None else (got[0], got[1], 1)
             for c, j in enumerate(js):
                 for g, k in enumerate(group):

@@ -47,6 +47,11 @@ twin (scan_filter_host), a printed FILTER column as the same word (scan_filter_o
 <outPrefix>.spikeScan.filter.txt, .filter.curve.txt, .spikeScan<t>.passrate.bedgraph and .spikeScan.t95pass.bedgraph
 (write_scan_filter) and, per axis, .spikeScan.depth.filter.txt / .spikeScan.rpb.filter.txt (write_scan_filter_cells).
 
+--spikeScanMnvFilter: the same for the MNV scan (scan reads the switch) - a set is PASS in a replicate when every member is called and
+every member's FILTER is PASS; the joint words are smc_scan_filter_sets' (abi.scan_filter_joint_rule), the pages
+<outPrefix>.spikeScan.mnv.filter.txt, .mnv.filter.curve.txt, .spikeScan<t>.mnv.passrate.bedgraph and .spikeScan.mnv.t95pass.bedgraph
+(write_scan_mnv_filter: write_scan_filter on the sets' MNVs).
+
 The semantics are tools/spike_variants.py's (DESIGN.md "--spikeAF"); the rewrite on the GPU is csrc/k_spike.inc (smc_spike_alleles),
 the pre-pass that counts N, V0 and V1 and the rule that spikes every run of the main pass are devplanes.spike_rules / spike_run.
 """
@@ -776,6 +781,22 @@ def _scan_int(text, flag: str, lo: int, hi, what: str) -> int:
     return n
 
 
+def _scan_fracs(text, flag: str, n_targets: int):
+    """The barcode fractions of --spikeScanDepth / --spikeScanMnvDepth.  SystemExit naming `flag`: text that is no list of numbers, a
+    fraction outside (0, 1] or listed twice, more than MAX_CELLS targets x fractions."""
+    try:
+        fr = [float(x) for x in str(text).split(",") if x.strip()]
+    except ValueError:
+        raise SystemExit("--%s: comma-separated fractions in (0, 1] expected, got %r" % (flag, text))
+    if not fr or any(not (0.0 < f <= 1.0) for f in fr):
+        raise SystemExit("--%s: every fraction must lie in (0, 1], got %r" % (flag, text))
+    if len(set("%g" % f for f in fr)) != len(fr):
+        raise SystemExit("--%s: a fraction is listed twice (the cells' files would share a name), got %r" % (flag, text))
+    if n_targets * len(fr) > MAX_CELLS:
+        raise SystemExit("--%s: %d targets x %d fractions = %d cells, at most %d" % (flag, n_targets, len(fr), n_targets * len(fr), MAX_CELLS))
+    return fr
+
+
 def scan(args):
     """--spikeScan / --spikeScanReps / --spikeScanStride / --spikeScanAlt -> dict(targets, reps, stride, alt), or None without
     --spikeScan.  SystemExit: a helper flag without --spikeScan, --spikeScan without --spikeScanReps, any other --spike* flag or a
@@ -793,7 +814,12 @@ def scan(args):
     without --spikeScan, a value that is neither whole nor listed.
     --spikeScanMnv L adds "mnv": L, the letters of the MNV planted at every locus in place of the SNV.  SystemExit: the flag without
     --spikeScan, L no integer in 2 .. 8, a stride below L, the flag beside --spikeScanIndel, or beside --spikeScanDepth, --spikeScanRpb
-    or --spikeScanFilter (not built)."""
+    or --spikeScanFilter (not built).
+    --spikeScanMnvFilter (a switch) adds "mnv_filter": True, the filter axis of the MNV scan.  SystemExit: the switch without
+    --spikeScan or without --spikeScanMnv; beside --spikeScanDepth, --spikeScanRpb, --spikeScanFilter or --spikeScanIndel the refusals
+    of --spikeScanMnv above fire first.
+    --spikeScanMnvDepth adds "mnv_fracs": the barcode fractions of the MNV scan's depth axis.  SystemExit: as the switch's, and what
+    --spikeScanDepth refuses of its text, named after this flag."""
     from .tools import spike_scan_lists as lists
     text, r, stride, alt = (getattr(args, f, None) for f in SCAN_FLAGS)
     indel = getattr(args, "spikeScanIndel", None)
@@ -802,11 +828,13 @@ def scan(args):
     flt = getattr(args, "spikeScanFilter", None)
     build = getattr(args, "spikeScanBuild", None)
     mnv = getattr(args, "spikeScanMnv", None)
+    mnv_flt = getattr(args, "spikeScanMnvFilter", None)
+    mnv_fracs = getattr(args, "spikeScanMnvDepth", None)
     given = lambda x: x not in (None, "", False)
     if not given(text):
         for flag, value in zip(SCAN_FLAGS[1:] + ("spikeScanIndel", "spikeScanDepth", "spikeScanRpb", "spikeScanFilter", "spikeScanBuild",
-                                                 "spikeScanMnv"),
-                               (r, stride, alt, indel, fracs, rpbs, flt, build, mnv)):
+                                                 "spikeScanMnv", "spikeScanMnvFilter", "spikeScanMnvDepth"),
+                               (r, stride, alt, indel, fracs, rpbs, flt, build, mnv, mnv_flt, mnv_fracs)):
             if given(value):
                 raise SystemExit("--%s belongs to --spikeScan: it needs --spikeScan" % flag)
         return None
@@ -823,6 +851,9 @@ def scan(args):
             if given(value):
                 raise SystemExit("--spikeScanMnv cannot be combined with --%s: the %s axis of an MNV scan is not built" %
                                  (flag, {"spikeScanDepth": "depth", "spikeScanRpb": "reads-per-barcode", "spikeScanFilter": "filter"}[flag]))
+    for flag, value in (("spikeScanMnvFilter", mnv_flt), ("spikeScanMnvDepth", mnv_fracs)):
+        if given(value) and not given(mnv):
+            raise SystemExit("--%s belongs to --spikeScanMnv: it needs --spikeScanMnv" % flag)
     for flag in SCAN_NOT_WITH:
         if given(getattr(args, flag, None)):
             raise SystemExit("--spikeScan cannot be combined with --%s in one run: the scan plants its own SNV at every locus of "
@@ -852,6 +883,8 @@ def scan(args):
             lists.check_mnv_stride(out["mnv"], stride)
         except ValueError as e:
             raise SystemExit(str(e))
+    if given(mnv_flt):
+        out["mnv_filter"] = True
     if given(indel):
         try:
             out["indel"] = lists.parse_indel_rule(indel)
@@ -859,18 +892,9 @@ def scan(args):
         except ValueError as e:
             raise SystemExit(str(e))
     if given(fracs):
-        try:
-            fr = [float(x) for x in str(fracs).split(",") if x.strip()]
-        except ValueError:
-            raise SystemExit("--spikeScanDepth: comma-separated fractions in (0, 1] expected, got %r" % (fracs,))
-        if not fr or any(not (0.0 < f <= 1.0) for f in fr):
-            raise SystemExit("--spikeScanDepth: every fraction must lie in (0, 1], got %r" % (fracs,))
-        if len(set("%g" % f for f in fr)) != len(fr):
-            raise SystemExit("--spikeScanDepth: a fraction is listed twice (the cells' files would share a name), got %r" % (fracs,))
-        if len(ts) * len(fr) > MAX_CELLS:
-            raise SystemExit("--spikeScanDepth: %d targets x %d fractions = %d cells, at most %d" % (len(ts), len(fr), len(ts) * len(fr),
-                                                                                                   MAX_CELLS))
-        out["fracs"] = fr
+        out["fracs"] = _scan_fracs(fracs, "spikeScanDepth", len(ts))
+    if given(mnv_fracs):
+        out["mnv_fracs"] = _scan_fracs(mnv_fracs, "spikeScanMnvDepth", len(ts))
     if given(rpbs):
         if given(fracs):
             raise SystemExit("--spikeScanRpb cannot be combined with --spikeScanDepth in one run: the grid of targets x barcode fractions x "
@@ -1037,7 +1061,7 @@ def need_line(v, target, n: int, depths, mt_depths, rates, n_means) -> str:
                      ([dsaf.NA] * 3 if k is None else ["%g" % depths[k], "%d" % mt_depths[k], dsaf.frac_text(n_means[k])]))
 
 
-def write_scan_depth(out_prefix: str, loci, variants, targets, fracs, mt_depth: int, full_entries, entries) -> None:
+def write_scan_depth(out_prefix: str, loci, variants, targets, fracs, mt_depth: int, full_entries, entries, mnv=None) -> None:
     """The pages of --spikeScanDepth.  loci, variants, targets: write_scan's; full_entries[(i, t)]: the full-depth replicates of variant
     i at targets[t] (write_scan's entries); entries[(i, t, f)]: those of the cell at fracs[f] (scan_entry with the cell's counters).
       <outPrefix>.spikeScan.depth.sensitivity.txt   a line per scanned locus, target and fraction (scan_depth_sensitivity_line)
@@ -1046,25 +1070,30 @@ def write_scan_depth(out_prefix: str, loci, variants, targets, fracs, mt_depth: 
       <outPrefix>.spikeScan.dsMT<f>.t95.bedgraph    chrom, pos - 1, pos, T95 at that depth; 1 where it is NA and at a skipped locus
       <outPrefix>.spikeScan.depth.need.txt          need_line per scanned locus and target
       <outPrefix>.spikeScan<t>.f95.bedgraph         chrom, pos - 1, pos, F95 of the target; 2 - above the axis - where it is NA and at
-                                                    a skipped locus"""
+                                                    a skipped locus
+    `mnv` (write_scan_mnv_depth: per variant and cell the line of its sensitivity page): the same pages of an MNV scan - `.mnv` in
+    every name, PHASE_SENSITIVITY_HEADER on the sensitivity page, N_ALL for N on the need page."""
     T, F = len(targets), len(fracs)
+    stem = "" if mnv is None else ".mnv"
     mts = [scan_depth_mt(mt_depth, f) for f in fracs]
     depths = list(fracs) + ([] if any(f == 1.0 for f in fracs) else [1.0])
     depth_mts = mts + ([] if len(depths) == F else [mt_depth])
-    i_rate = SCAN_DEPTH_SENSITIVITY_HEADER.index("RATE")
+    head = SCAN_DEPTH_SENSITIVITY_HEADER if mnv is None else PHASE_SENSITIVITY_HEADER
+    i_rate = head.index("RATE")
     i_t95 = len(DEPTH_CURVE_HEADER) + T
     rates = {}                                   # (t, f) -> per variant the page's RATE text
     t95s = [[] for _ in range(F)]
     f95s = [[] for _ in range(T)]
-    with open(out_prefix + ".spikeScan.depth.sensitivity.txt", "w") as fs, open(out_prefix + ".spikeScan.depth.curve.txt", "w") as fc, \
-            open(out_prefix + ".spikeScan.depth.need.txt", "w") as fn:
-        fs.write("\t".join(SCAN_DEPTH_SENSITIVITY_HEADER) + "\n")
+    with open("%s.spikeScan%s.depth.sensitivity.txt" % (out_prefix, stem), "w") as fs, \
+            open("%s.spikeScan%s.depth.curve.txt" % (out_prefix, stem), "w") as fc, \
+            open("%s.spikeScan%s.depth.need.txt" % (out_prefix, stem), "w") as fn:
+        fs.write("\t".join(head) + "\n")
         fc.write("\t".join(depth_curve_header(targets)) + "\n")
-        fn.write("\t".join(SCAN_NEED_HEADER) + "\n")
+        fn.write("\t".join(SCAN_NEED_HEADER if mnv is None else SCAN_MNV_NEED_HEADER) + "\n")
         for i, v in enumerate(variants):
             for t, target in enumerate(targets):
                 for f, frac in enumerate(fracs):
-                    line = scan_depth_sensitivity_line(v, target, frac, mts[f], entries[(i, t, f)])
+                    line = scan_depth_sensitivity_line(v, target, frac, mts[f], entries[(i, t, f)]) if mnv is None else mnv[(i, t, f)]
                     rates.setdefault((t, f), []).append(line.split("\t")[i_rate])
                     fs.write(line + "\n")
                 # (the axis: the listed fractions; full depth stands for 1 where 1 is not listed)
@@ -1080,17 +1109,42 @@ def write_scan_depth(out_prefix: str, loci, variants, targets, fracs, mt_depth: 
                 fc.write(line + "\n")
     for t, target in enumerate(targets):
         for f, frac in enumerate(fracs):
-            with open("%s.spikeScan%g.dsMT%g.rate.bedgraph" % (out_prefix, target, frac), "w") as fh:
+            with open("%s.spikeScan%g.dsMT%g%s.rate.bedgraph" % (out_prefix, target, frac, stem), "w") as fh:
                 for chrom, pos, i in loci:
                     if i is not None:
                         fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), rates[(t, f)][i]))
-        with open("%s.spikeScan%g.f95.bedgraph" % (out_prefix, target), "w") as fh:
+        with open("%s.spikeScan%g%s.f95.bedgraph" % (out_prefix, target, stem), "w") as fh:
             for chrom, pos, i in loci:
                 fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "2" if i is None or f95s[t][i] == dsaf.NA else f95s[t][i]))
     for f, frac in enumerate(fracs):
-        with open("%s.spikeScan.dsMT%g.t95.bedgraph" % (out_prefix, frac), "w") as fh:
+        with open("%s.spikeScan.dsMT%g%s.t95.bedgraph" % (out_prefix, frac, stem), "w") as fh:
             for chrom, pos, i in loci:
                 fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "1" if i is None or t95s[f][i] == dsaf.NA else t95s[f][i]))
+
+
+# ---- --spikeScanMnvDepth: the MNV scan's pages per barcode depth
+SCAN_MNV_NEED_HEADER = tuple("N_ALL" if c == "N" else c for c in SCAN_NEED_HEADER)
+
+
+def write_scan_mnv_depth(out_prefix: str, loci, variants, sets, targets, fracs, mt_depth: int, full_entries, entries) -> None:
+    """The pages of --spikeScanMnvDepth.  loci, variants, sets, targets: write_scan_mnv's; full_entries[(i, t)]: the full-depth
+    replicates of set i at targets[t] as phase_sensitivity_line takes them - (dict(N_ALL, V0_ALL, S_ALL, V1_ALL), CALLED_ALL);
+    entries[(i, t, f)]: those of the cell at fracs[f].
+      <outPrefix>.spikeScan.mnv.depth.sensitivity.txt   PHASE_SENSITIVITY_HEADER, then per scanned leader, target and fraction the
+                                                        set's cell line in .spikeAF.phase.sensitivity.txt of the pass's own run
+      <outPrefix>.spikeScan.mnv.depth.curve.txt         .spikeScan.depth.curve.txt's columns per leader - `full`, then every fraction -,
+                                                        REF and ALT the L letters, N_MEAN the mean N_ALL of the cell
+      <outPrefix>.spikeScan<t>.dsMT<f>.mnv.rate.bedgraph, .spikeScan.dsMT<f>.mnv.t95.bedgraph   as --spikeScanDepth's, over the joint rates
+      <outPrefix>.spikeScan.mnv.depth.need.txt          SCAN_NEED_HEADER with N_ALL for N: F95 / MTDEPTH95 / N95 by need_line's rule over
+                                                        the joint rates, N95 the mean N_ALL there
+      <outPrefix>.spikeScan<t>.mnv.f95.bedgraph         F95 of the target; 2 where it is NA and at a skipped locus
+    write_scan_depth with the joint counts standing where a variant's do."""
+    mnvs = [scan_mnv_variant(pset, variants) for pset in sets]
+    as_scan = lambda v, per: [scan_entry(v, dict(N=r["N_ALL"], V0=r["V0_ALL"], S=r["S_ALL"], READS=0, V1=r["V1_ALL"]), bool(c)) for r, c in per]
+    mts = [scan_depth_mt(mt_depth, f) for f in fracs]
+    lines = {(i, t, f): phase_sensitivity_line(sets[i], variants, targets[t], fracs[f], mts[f], per) for (i, t, f), per in entries.items()}
+    write_scan_depth(out_prefix, loci, mnvs, targets, fracs, mt_depth, {(i, t): as_scan(mnvs[i], per) for (i, t), per in full_entries.items()},
+                     {(i, t, f): as_scan(mnvs[i], per) for (i, t, f), per in entries.items()}, mnv=lines)
 
 
 # ---- --spikeScanRpb: the scan's pages per reads-per-barcode target
@@ -1254,8 +1308,8 @@ def scan_filter_line(v, target, called, words) -> str:
                       dsaf.frac_text(float(n_pass) / n), dsaf.frac_text(lo), dsaf.frac_text(hi)] + ["%d" % x for x in tally])
 
 
-def scan_filter_curve_header(targets):
-    return CURVE_HEADER + tuple("RATE_PASS@%g" % t for t in sorted(targets)) + ("T95_PASS",)
+def scan_filter_curve_header(targets, first=CURVE_HEADER):
+    return first + tuple("RATE_PASS@%g" % t for t in sorted(targets)) + ("T95_PASS",)
 
 
 def scan_filter_curve_line(v, n: int, targets, rates) -> str:
@@ -1266,19 +1320,22 @@ def scan_filter_curve_line(v, n: int, targets, rates) -> str:
                      [dsaf.NA if best is None else "%g" % best])
 
 
-def write_scan_filter(out_prefix: str, loci, variants, targets, ns, called, words) -> None:
+def write_scan_filter(out_prefix: str, loci, variants, targets, ns, called, words, mnv: bool = False) -> None:
     """The pages of --spikeScanFilter.  loci, variants, targets: write_scan's; ns[i]: variant i's covering barcodes; called[i][t] /
     words[i][t]: per replicate the verdict and the FILTER word of variant i at targets[t].
       <outPrefix>.spikeScan.filter.txt            scan_filter_line per scanned locus and target
       <outPrefix>.spikeScan.filter.curve.txt      scan_filter_curve_line per scanned locus
       <outPrefix>.spikeScan<t>.passrate.bedgraph  chrom, pos - 1, pos, RATE_PASS of that target - the page's text - per scanned locus
-      <outPrefix>.spikeScan.t95pass.bedgraph      chrom, pos - 1, pos, T95_PASS; 1 where it is NA and at a skipped locus"""
+      <outPrefix>.spikeScan.t95pass.bedgraph      chrom, pos - 1, pos, T95_PASS; 1 where it is NA and at a skipped locus
+    `mnv` (write_scan_mnv_filter): the same pages of an MNV scan - `.mnv` in every name (.spikeScan.mnv.filter.txt, ...), the headers
+    SCAN_MNV_FILTER_HEADER and SCAN_MNV_CURVE_HEADER's."""
     T = len(targets)
     rates, t95s = [[] for _ in range(T)], []
-    i_rate, i_t95 = SCAN_FILTER_HEADER.index("RATE_PASS"), len(CURVE_HEADER) + T
-    with open(out_prefix + ".spikeScan.filter.txt", "w") as fs, open(out_prefix + ".spikeScan.filter.curve.txt", "w") as fc:
-        fs.write("\t".join(SCAN_FILTER_HEADER) + "\n")
-        fc.write("\t".join(scan_filter_curve_header(targets)) + "\n")
+    stem, head, first = (".mnv", SCAN_MNV_FILTER_HEADER, SCAN_MNV_CURVE_HEADER) if mnv else ("", SCAN_FILTER_HEADER, CURVE_HEADER)
+    i_rate, i_t95 = head.index("RATE_PASS"), len(first) + T
+    with open("%s.spikeScan%s.filter.txt" % (out_prefix, stem), "w") as fs, open("%s.spikeScan%s.filter.curve.txt" % (out_prefix, stem), "w") as fc:
+        fs.write("\t".join(head) + "\n")
+        fc.write("\t".join(scan_filter_curve_header(targets, first)) + "\n")
         for i, v in enumerate(variants):
             mine = []
             for t, target in enumerate(targets):
@@ -1290,25 +1347,42 @@ def write_scan_filter(out_prefix: str, loci, variants, targets, ns, called, word
             t95s.append(line.split("\t")[i_t95])
             fc.write(line + "\n")
     for t, target in enumerate(targets):
-        with open("%s.spikeScan%g.passrate.bedgraph" % (out_prefix, target), "w") as fh:
+        with open("%s.spikeScan%g%s.passrate.bedgraph" % (out_prefix, target, stem), "w") as fh:
             for chrom, pos, i in loci:
                 if i is not None:
                     fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), rates[t][i]))
-    with open(out_prefix + ".spikeScan.t95pass.bedgraph", "w") as fh:
+    with open("%s.spikeScan%s.t95pass.bedgraph" % (out_prefix, stem), "w") as fh:
         for chrom, pos, i in loci:
             fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "1" if i is None or t95s[i] == dsaf.NA else t95s[i]))
 
 
-def scan_filter_cells_header(axis=DEPTH_AXIS):
-    return SCAN_FILTER_HEADER[:5] + (axis[1], "MTDEPTH") + SCAN_FILTER_HEADER[5:]
+# ---- --spikeScanMnvFilter: the filter pages of an MNV scan - a set is PASS when every member is called and every member's FILTER is PASS
+SCAN_MNV_FILTER_HEADER = tuple({"CALLED": "CALLED_ALL", "PASS": "PASS_ALL"}.get(c, c) for c in SCAN_FILTER_HEADER)
 
 
-def write_scan_filter_cells(out_prefix: str, variants, targets, values, mt_depths, called, words, axis=DEPTH_AXIS) -> None:
+def write_scan_mnv_filter(out_prefix: str, loci, variants, sets, targets, n_alls, called, words) -> None:
+    """The pages of --spikeScanMnvFilter.  loci, variants, sets: write_scan_mnv's; n_alls[i]: set i's joint barcodes at full depth;
+    called[i][t] / words[i][t]: per replicate the joint verdict of set i at targets[t] and, where it is called, the joint FILTER word
+    (abi.scan_filter_joint_rule: the OR of the members' names - a name counts once per replicate).
+      <outPrefix>.spikeScan.mnv.filter.txt            CHROM POS REF ALT as .spikeScan.mnv.curve.txt has them, TARGET REPS CALLED_ALL
+                                                      PASS_ALL RATE_PASS LO95 HI95 and the 14 names: scan_filter_line on the joint words
+      <outPrefix>.spikeScan.mnv.filter.curve.txt      CHROM POS REF ALT N_ALL, RATE_PASS@<t> ascending, T95_PASS
+      <outPrefix>.spikeScan<t>.mnv.passrate.bedgraph  RATE_PASS of that target at the leader's position
+      <outPrefix>.spikeScan.mnv.t95pass.bedgraph      T95_PASS; 1 where it is NA and at a skipped locus"""
+    write_scan_filter(out_prefix, loci, [scan_mnv_variant(pset, variants) for pset in sets], targets, n_alls, called, words, mnv=True)
+
+
+def scan_filter_cells_header(axis=DEPTH_AXIS, head=SCAN_FILTER_HEADER):
+    return head[:5] + (axis[1], "MTDEPTH") + head[5:]
+
+
+def write_scan_filter_cells(out_prefix: str, variants, targets, values, mt_depths, called, words, axis=DEPTH_AXIS, mnv: bool = False) -> None:
     """<outPrefix>.spikeScan.depth.filter.txt (axis RPB_AXIS: .spikeScan.rpb.filter.txt): scan_filter_line per scanned locus, target
     and cell with the axis column and MTDEPTH behind TARGET.  values / mt_depths: the cells' fractions (reads-per-barcode targets)
-    and mtDepths; called[i][t][f] / words[i][t][f]: per replicate."""
-    with open("%s.spikeScan.%s.filter.txt" % (out_prefix, axis[0]), "w") as fh:
-        fh.write("\t".join(scan_filter_cells_header(axis)) + "\n")
+    and mtDepths; called[i][t][f] / words[i][t][f]: per replicate.  `mnv`: <outPrefix>.spikeScan.mnv.depth.filter.txt of an MNV scan -
+    `variants` the sets' MNVs (scan_mnv_variant), the joint verdicts and words, CALLED_ALL and PASS_ALL in the header."""
+    with open("%s.spikeScan%s.%s.filter.txt" % (out_prefix, ".mnv" if mnv else "", axis[0]), "w") as fh:
+        fh.write("\t".join(scan_filter_cells_header(axis, SCAN_MNV_FILTER_HEADER if mnv else SCAN_FILTER_HEADER)) + "\n")
         for i, v in enumerate(variants):
             for t, target in enumerate(targets):
                 for f, value in enumerate(values):

@@ -960,6 +960,35 @@ int smc_spike_phase_rpb_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, cons
                                int64_t n_rec, const uint32_t* d_pos1, int32_t n_sets, const uint64_t* d_seeds, int32_t n_reps,
                                const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr, int32_t n_read_thr, uint32_t* d_out,
                                void* stream);
+/* (ABI 11, additive: one entry more, the version number unchanged) --spikeScanMnvRpb: smc_spike_phase_rpb_counts' words without a
+ * record CSR made on the host - for a scan, where every locus of the panel is a set.  The segments of a (joint barcode, member) come
+ * from what is in HBM already: the run in BARCODE-MAJOR order, made once per decoded run, and smc_spike_read_bits' bytes.
+ * Per run, n_aln entries each, stable by bc_gid (file order inside a barcode): d_bm_aln uint32 the alignment's index in the run,
+ * d_bm_name uint64 the read-name identity of its pair_gid, d_bm_first uint8 1 when that name is its barcode's first, file-wide;
+ * d_bc_start / bc_start_host[n_bc + 1]: where each barcode's records begin (ascending, ending at n_aln); d_idents[n_bc]: the
+ * barcode identities smc_spike_alleles takes.
+ * Per call: d_bits[n_var][n_aln]: smc_spike_read_bits' output as it is (bit 0 covers, bit 1 alt0, bit 2 single = an SNV's alt1; bit
+ * 3 is not read).  The rows: d_row_off / row_off_host[n_rows + 1] over d_row_var / row_var_host - indices of bit rows, a row's
+ * members in order, 1 .. SMC_SPIKE_PHASE_MAX_MEMBERS of them (a row of one member is a listed variant).  The joint barcodes of every
+ * row: d_joint_off / joint_off_host[n_rows + 1] over d_joint_gid, run-wide barcode ids in any order (the host ANDs
+ * smc_allele_carriers' cover rows of the members).  d_pos1[n_rows], d_seeds, `thr`, `read_thr`: smc_spike_phase_rpb_counts'.
+ * A lane of row g takes joint barcode b and walks records [bc_start[b], bc_start[b + 1]) once per member m; the record of alignment
+ * i is member m's when d_bits[row_var[m] * n_aln + i] has bit 0.  A d_bm_aln that is not below n_aln, and a joint id that is not
+ * below n_bc, read nothing.  d_out[row][j][t][r][4] uint32 = (N_ALL', V0_ALL', S_ALL', V1_ALL') under smc_spike_phase_rpb_counts'
+ * definitions - one spike draw per (barcode, row, replicate) with the row's pos1, a record kept at r when its first-name flag is set
+ * or its read draw is below read_thr[r], (reads, alt0, alt1) per member over the kept records, the members ANDed - and by the same
+ * kernel body.  d_out is zeroed by the call; integer atomics only: two calls give the same words.
+ * Enqueued on `stream`; nothing waits.  SMC_E_INPUT, nothing launched and nothing zeroed, all on the host copies: row or joint
+ * offsets that decrease, a row with members outside 1 .. SMC_SPIKE_PHASE_MAX_MEMBERS, a row_var not below n_var, a bc_start that
+ * decreases or does not end at n_aln, more than SMC_AF_MAX_VARIANTS rows, a threshold above 2^32 on either axis, n_read_thr below 1,
+ * n_targets * n_read_thr above SMC_AF_DEPTH_MAX_CELLS, n_reps above SMC_AF_REP_MAX_REPS, an output of 2^32 - 256 words or more. */
+int smc_scan_phase_rpb_counts(smc_ctx* ctx, const uint32_t* d_bm_aln, const uint64_t* d_bm_name, const uint8_t* d_bm_first, int64_t n_aln,
+                              const uint32_t* d_bc_start, const uint32_t* bc_start_host, const uint64_t* d_idents, int64_t n_bc,
+                              const uint8_t* d_bits, int32_t n_var, const uint32_t* d_row_off, const uint32_t* row_off_host,
+                              const uint32_t* d_row_var, const uint32_t* row_var_host, const uint32_t* d_joint_off,
+                              const uint32_t* joint_off_host, const uint32_t* d_joint_gid, const uint32_t* d_pos1, int32_t n_rows,
+                              const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr,
+                              int32_t n_read_thr, uint32_t* d_out, void* stream);
 
 /* (ABI 11, additive: one entry more, the version number unchanged) --spikeScan: one verdict per (copy, listed locus) of a called
  * batch whose rows stay in HBM.  d_rows: n_copies x n_loci rows as a plan wrote them, copy c's locus l at c * n_loci + l.  d_listed /

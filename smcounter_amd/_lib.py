@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("SMC_HIP_LIB") or os.path.join(HERE, "libsmcounter_hip
 SYMBOLS = ("smc_abi_version", "smc_last_error", "smc_row_size", "smc_locus_size", "smc_device_count",
            "smc_create", "smc_destroy", "smc_plan_create", "smc_plan_create_dev", "smc_plan_create_dev_spec", "smc_plan_spec_ok", "smc_plan_spec_counts", "smc_plan_hint_reset", "smc_philox_marks", "smc_philox4x32_10_host", "smc_select_alignments", "smc_select_alignments_keyed", "smc_select_alignments_copies", "smc_select_alignments_reads_copies", "smc_read_groups_create", "smc_read_groups_add", "smc_read_groups_finish",
            "smc_read_groups_masks", "smc_read_groups_kept", "smc_read_groups_status", "smc_read_groups_destroy",
-           "smc_read_groups_counts_frac", "smc_read_groups_masks_grid", "smc_read_groups_kept_grid", "smc_lod_table", "smc_fisher_tables", "smc_lfact_values", "smc_allele_carriers", "smc_af_rep_masks", "smc_af_rep_counts", "smc_af_depth_masks", "smc_af_depth_counts", "smc_spike_alleles", "smc_spike_indels", "smc_spike_alleles_reps", "smc_spike_rep_counts", "smc_spike_depth_counts", "smc_spike_phase_counts", "smc_spike_indels_reps", "smc_spike_indel_touch", "smc_spike_indel_counts", "smc_spike_indel_phase_counts", "smc_spike_read_bits", "smc_spike_rpb_counts", "smc_spike_indel_read_bits", "smc_spike_indel_rpb_counts", "smc_spike_phase_rpb_counts", "smc_read_groups_counts_frac_seeds", "smc_spike_grid_counts", "smc_scan_detect", "smc_scan_detect_sets", "smc_scan_detect_keys", "smc_scan_filter", "smc_scan_filter_sets", "smc_plan_destroy", "smc_plan_info",
+           "smc_read_groups_counts_frac", "smc_read_groups_masks_grid", "smc_read_groups_kept_grid", "smc_lod_table", "smc_fisher_tables", "smc_lfact_values", "smc_allele_carriers", "smc_af_rep_masks", "smc_af_rep_counts", "smc_af_depth_masks", "smc_af_depth_counts", "smc_spike_alleles", "smc_spike_indels", "smc_spike_alleles_reps", "smc_spike_rep_counts", "smc_spike_depth_counts", "smc_spike_phase_counts", "smc_spike_indels_reps", "smc_spike_indel_touch", "smc_spike_indel_counts", "smc_spike_indel_phase_counts", "smc_spike_read_bits", "smc_spike_rpb_counts", "smc_spike_indel_read_bits", "smc_spike_indel_rpb_counts", "smc_spike_phase_rpb_counts", "smc_scan_phase_rpb_counts", "smc_read_groups_counts_frac_seeds", "smc_spike_grid_counts", "smc_scan_detect", "smc_scan_detect_sets", "smc_scan_detect_keys", "smc_scan_filter", "smc_scan_filter_sets", "smc_plan_destroy", "smc_plan_info",
            "smc_plan_run", "smc_plan_run_words", "smc_plan_run_words16", "smc_pack_words", "smc_plan_set_timing", "smc_plan_kernel_ms", "smc_call_batch_host", "smc_event_create", "smc_event_record",
            "smc_event_elapsed_ms", "smc_event_destroy", "smc_class_table", "smc_wire_row_size", "smc_pack_rows", "smc_unpack_rows",
            "smc_build_planes", "smc_build_planes_w16", "smc_build_listed", "smc_build_max_depth", "smc_build_set_timing", "smc_build_kernel_ms", "smc_build_live_rows", "smc_mem_alloc", "smc_mem_alloc_best", "smc_mem_write_probe", "smc_mem_free", "smc_mem_h2d", "smc_mem_d2h",
@@ -116,6 +116,8 @@ def load(with_torch: bool = True):
     L.smc_spike_indel_read_bits.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, i32, vp, vp, i32, vp, i64, vp, vp]
     L.smc_spike_indel_rpb_counts.argtypes = L.smc_spike_rpb_counts.argtypes
     L.smc_spike_phase_rpb_counts.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp]
+    L.smc_scan_phase_rpb_counts.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, i32,
+                                            vp, vp]
     L.smc_scan_detect.argtypes = [vp, vp, i32, i64, vp, vp, i32, ctypes.c_double, vp, vp, vp, vp]
     L.smc_scan_detect_sets.argtypes = [vp, vp, i32, i64, vp, vp, i32, vp, vp, i32, ctypes.c_double, vp, vp, vp, vp, vp]
     L.smc_scan_detect_keys.argtypes = [vp, vp, i32, i64, vp, vp, i32, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, vp, i64, vp, i64, i64,

@@ -115,6 +115,81 @@ def scan_filter_joint_rule(member_words, set_off):
     return words
 
 
+SPIKE_DRAW_DOMAIN, READ_DRAW_DOMAIN = 0x73704146, 0x64735250      # counter word 2 of the spike draw ("spAF") and of the read draw ("dsRP")
+
+
+def philox_word0(idents, domain: int, word3: int, seed: int) -> np.ndarray:
+    """Word 0 of Philox4x32-10(counter = (ident lo, ident hi, domain, word3), key = (seed lo, seed hi)) per identity, in numpy."""
+    idents = np.asarray(idents, np.uint64)
+    m32, n = np.uint64(0xFFFFFFFF), len(idents)
+    c = [idents & m32, idents >> np.uint64(32), np.full(n, int(domain), np.uint64), np.full(n, int(word3) & 0xFFFFFFFF, np.uint64)]
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & m32]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c[0].astype(np.uint64)
+
+
+def scan_phase_rpb_counts_rule(bm_aln, bm_name, bm_first, bc_start, idents, bits, row_off, row_var, joint_off, joint_gid, pos1, seeds, thr,
+                               read_thr, detail: list = None) -> np.ndarray:
+    """smc_scan_phase_rpb_counts in numpy, on the entry's own arrays -> uint32 [rows, R, T, Rr, 4] = (N_ALL', V0_ALL', S_ALL', V1_ALL').
+    bm_aln, bm_name, bm_first, bc_start: the run in barcode-major order; idents: the barcodes' identities; bits: uint8 [n_var, n_aln],
+    smc_spike_read_bits' bytes; row_off over row_var: a row's members (indices of bit rows); joint_off over joint_gid: a row's joint
+    barcodes (run-wide ids); pos1: the rows' draw positions; seeds, thr, read_thr: the replicates' seeds and the thresholds of both axes.
+    detail: a list that gets, per row, int64 [R, n joint barcodes, M, Rr, 3] = (reads, alt0, alt1) of every barcode at every member
+    over the records kept at r - what the verdicts are made of."""
+    bm_aln, bm_name = np.asarray(bm_aln, np.int64), np.asarray(bm_name, np.uint64)
+    bm_first, bc_start = np.asarray(bm_first, np.uint8) != 0, np.asarray(bc_start, np.int64)
+    idents, bits = np.asarray(idents, np.uint64), np.asarray(bits, np.uint8)
+    n_aln, n_bc = len(bm_aln), len(idents)
+    bits = bits.reshape(-1, n_aln) if n_aln else bits.reshape(len(bits), 0)
+    row_off, joint_off = np.asarray(row_off, np.int64), np.asarray(joint_off, np.int64)
+    row_var, joint_gid = np.asarray(row_var, np.int64), np.asarray(joint_gid, np.int64)
+    rthr = np.array([int(q) for q in read_thr], np.uint64)
+    n_rows, R, T, Rr = len(row_off) - 1, len(seeds), len(thr), len(rthr)
+    out = np.zeros((n_rows, R, T, Rr, 4), np.uint32)
+    for g in range(n_rows):
+        gids = joint_gid[joint_off[g]:joint_off[g + 1]]
+        members = row_var[row_off[g]:row_off[g + 1]]
+        n, M = len(gids), len(members)
+        ok = gids < n_bc                                            # (an id that is not below n_bc reads nothing)
+        safe = np.where(ok, gids, 0)
+        ids = np.where(ok, idents[safe] if n_bc else 0, 0).astype(np.uint64)
+        r0 = np.where(ok, np.minimum(bc_start[safe], n_aln), 0)
+        r1 = np.where(ok, np.minimum(bc_start[safe + 1], n_aln), 0) if n_bc else r0
+        length = np.maximum(r1 - r0, 0)
+        lane = np.repeat(np.arange(n), length)                      # every record of every joint barcode, barcode after barcode
+        k = np.repeat(r0 - (np.cumsum(length) - length), length) + np.arange(int(length.sum()))
+        a = bm_aln[k]
+        inside = a < n_aln
+        lane, k, a = lane[inside], k[inside], a[inside]
+        cnt = np.zeros((R, n, M, Rr, 3), np.int64)
+        for j, s in enumerate(seeds):
+            kept = bm_first[k][:, None] | (philox_word0(bm_name[k], READ_DRAW_DOMAIN, 0, s)[:, None] < rthr[None, :])       # [records, Rr]
+            for m, v in enumerate(members):
+                byte = bits[v][a]
+                mine = (byte & 1) != 0
+                for q, bit in enumerate((1, 2, 4)):
+                    w = kept[mine] & ((byte[mine] & bit) != 0)[:, None]
+                    np.add.at(cnt[j, :, m, :, q], lane[mine], w.astype(np.int64))
+            c = cnt[j]
+            there = (c[..., 0] > 0).all(axis=1)                     # [n, Rr]
+            car0 = (2 * c[..., 1] > c[..., 0]).all(axis=1)
+            car1 = (2 * c[..., 2] > c[..., 0]).all(axis=1)
+            u = philox_word0(ids, SPIKE_DRAW_DOMAIN, int(pos1[g]), s)
+            for t, h in enumerate(thr):
+                hit = (u < np.uint64(int(h)))[:, None]
+                out[g, j, t, :, 0] = there.sum(axis=0)
+                out[g, j, t, :, 1] = (there & car0).sum(axis=0)
+                out[g, j, t, :, 2] = (there & hit).sum(axis=0)
+                out[g, j, t, :, 3] = (there & np.where(hit, car1, car0)).sum(axis=0)
+        if detail is not None:
+            detail.append(cnt)
+    return out
+
+
 def c_params(p: VcParams) -> SmcParams:
     return SmcParams(p.minBQ, p.minMQ, p.mtDrop, p.primerDist, p.ds, 0, p.smt, float(p.mismatchThr))
 

@@ -341,7 +341,7 @@ def build_parser() -> argparse.ArgumentParser:
                         "(smc_scan_detect_sets).  Writes <outPrefix>.spikeScan.mnv.sensitivity.txt (the sets' lines of "
                         ".spikeAF.phase.sensitivity.txt), .spikeScan.mnv.curve.txt, <outPrefix>.spikeScan<t>.mnv.rate.bedgraph and "
                         ".spikeScan.mnv.t95.bedgraph in place of the SNV scan's pages; no LOD column with --lod.  Needs --spikeScan; beside "
-                        "--spikeScanBuild, --spikeScanMnvFilter and --spikeScanMnvDepth; not with --spikeScanIndel, --spikeScanDepth, --spikeScanRpb or "
+                        "--spikeScanBuild, --spikeScanMnvFilter, --spikeScanMnvDepth and --spikeScanMnvRpb; not with --spikeScanIndel, --spikeScanDepth, --spikeScanRpb or "
                         "--spikeScanFilter (not built)")
     p.add_argument("--spikeScanMnvFilter", action="store_true", default=False,
                    help="--spikeScanMnv's rates over the replicates in which every member SNV is called AND every member's FILTER is "
@@ -365,6 +365,20 @@ def build_parser() -> argparse.ArgumentParser:
                         ".spikeScan.dsMT<f>.mnv.t95.bedgraph and .spikeScan<t>.mnv.f95.bedgraph (2 where full depth fails); with "
                         "--spikeScanMnvFilter also .spikeScan.mnv.depth.filter.txt; targets x fractions at most %d; no LOD column with "
                         "--lod.  Needs --spikeScanMnv" % GRID_MAX_CELLS)
+    p.add_argument("--spikeScanMnvRpb", default=None,
+                   help="r1,r2,...: --spikeScanMnv also at these reads-per-barcode targets, each > 0 and none listed twice: thinning reads "
+                        "can take a barcode out of one member's pileup, or flip its majority at one member only, so the joint numbers are "
+                        "counted per record.  A pass is then by definition its run --spikeAF <targets> --spikeVariants <the pass's list> "
+                        "--spikeIndelReps R --spikePhaseRpb <r...> --dsSeed s: the same draws and philox read sampler, a cell called at the "
+                        "scan's mtDepth with --rpb r, and the set's cell line of that run's .spikeAF.rpb.phase.sensitivity.txt is the "
+                        "definition.  The joint counts of every cell come from one smc_scan_phase_rpb_counts call per pass and run over "
+                        "the run in barcode-major order - no per-variant record lists on the host -, the copies of a batch are selected at "
+                        "every target by one smc_select_alignments_reads_copies call.  Writes <outPrefix>.spikeScan.mnv.rpb.sensitivity.txt, "
+                        ".spikeScan.mnv.rpb.curve.txt, .spikeScan.mnv.rpb.need.txt (R95 over the joint rates, N95 the mean N_ALL there), "
+                        "<outPrefix>.spikeScan<t>.dsRpb<r>.mnv.rate.bedgraph, .spikeScan.dsRpb<r>.mnv.t95.bedgraph and "
+                        ".spikeScan<t>.mnv.r95.bedgraph; with --spikeScanMnvFilter also .spikeScan.mnv.rpb.filter.txt; targets x "
+                        "reads-per-barcode targets at most %d; no LOD column with --lod.  Needs --spikeScanMnv; not with "
+                        "--spikeScanMnvDepth" % GRID_MAX_CELLS)
     p.add_argument("--spikeScanBuild", default=None,
                    help="whole (default) or listed: how --spikeScan builds its spiked copies.  whole: every copy is a build of its whole "
                         "decoded run, however few of its loci the pass lists.  listed: one smc_build_listed call builds the listed loci "
@@ -850,6 +864,10 @@ def _spike_scan(args, plan, ref, eng, params):
     if "mnv_fracs" in scan:
         cells = [dataclasses.replace(params, mtDepth=_spike.scan_depth_mt(params.mtDepth, f)) for f in scan["mnv_fracs"]]
         mnv_axes["depth"] = dict(fracs=scan["mnv_fracs"], params=cells, thresholds=[writers.pi_threshold(c.mtDepth, args.threshold) for c in cells])
+    if "mnv_rpbs" in scan:
+        # (a cell is called at the scan's mtDepth with --rpb r: the cut is the scan's own)
+        mnv_axes["reads"] = dict(targets=scan["mnv_rpbs"], params=[dataclasses.replace(params, rpb=r) for r in scan["mnv_rpbs"]],
+                                 thresholds=[threshold] * len(scan["mnv_rpbs"]))
     rpb = None
     if "rpbs" in scan:
         # (a cell is called at the scan's mtDepth with --rpb r: the cut is the scan's own)
@@ -1491,8 +1509,14 @@ def _scan_mnv_reports(args, plan, shard):
           (len(sets), len(targets), R, len(scan["passes"]), tm["runs"], tm["decode"], sum(st["builds"] for st in out["passes"]),
            sum(st["host"] for st in out["passes"]), len(variants) * len(targets) * R, tm["stage"]))
     closing = "--spikeScanMnv %d: %d sets scanned, %d loci skipped, %d of %d joint verdicts decided by the host" % \
-        (scan["mnv"], len(sets), len(scan["skipped"]), out["joint_host"], len(sets) * len(targets) * R * (1 + len(scan.get("mnv_fracs", ()))))
-    mt_depth, fracs = plan.outputs[0].params.mtDepth, scan.get("mnv_fracs")
+        (scan["mnv"], len(sets), len(scan["skipped"]), out["joint_host"],
+         len(sets) * len(targets) * R * (1 + len(scan.get("mnv_fracs", scan.get("mnv_rpbs", ())))))
+    mt_depth, fracs, rpbs = plan.outputs[0].params.mtDepth, scan.get("mnv_fracs"), scan.get("mnv_rpbs")
+    if rpbs is not None:
+        cells = {(i, t, r): [(dict(zip(_spike.PHASE_NAMES, (int(x) for x in out["joint_rpb_counts"][i, j, t, r]))),
+                              int(out["joint_rpb_called"][i, t, r, j])) for j in range(R)]
+                 for i in range(len(sets)) for t in range(len(targets)) for r in range(len(rpbs))}
+        _spike.write_scan_mnv_rpb(args.outPrefix, scan["loci"], variants, sets, targets, rpbs, mt_depth, plan.outputs[0].params.rpb, entries, cells)
     if fracs is not None:
         cells = {(i, t, f): [(dict(zip(_spike.PHASE_NAMES, (int(x) for x in out["joint_depth_counts"][i, j, t, f]))),
                               int(out["joint_depth_called"][i, t, f, j])) for j in range(R)]
@@ -1507,6 +1531,10 @@ def _scan_mnv_reports(args, plan, shard):
                                            [_spike.scan_depth_mt(mt_depth, f) for f in fracs], out["joint_depth_called"], out["joint_depth_filter"],
                                            mnv=True)
             held.append((out["joint_depth_called"], out["joint_depth_filter"] & np.uint32(abi.SCAN_FLT_NAMES_MASK)))
+        if rpbs is not None:
+            _spike.write_scan_filter_cells(args.outPrefix, [_spike.scan_mnv_variant(ps, variants) for ps in sets], targets, rpbs,
+                                           [mt_depth] * len(rpbs), out["joint_rpb_called"], out["joint_rpb_filter"], _spike.RPB_AXIS, mnv=True)
+            held.append((out["joint_rpb_called"], out["joint_rpb_filter"] & np.uint32(abi.SCAN_FLT_NAMES_MASK)))
         closing += "; --spikeScanMnvFilter: %d of %d called sets PASS, the FILTER of %d decided by the host; %s" % \
             (sum(int((c & (w == 0)).sum()) for c, w in held), sum(int(c.sum()) for c, _ in held), out["joint_filter_host"],
              ", ".join("%s %d" % (name, sum(int((c & ((w & bit) != 0)).sum()) for c, w in held)) for bit, name in abi.SCAN_FILTER_NAMES))
@@ -1514,7 +1542,14 @@ def _scan_mnv_reports(args, plan, shard):
         closing += "; --spikeScanMnvDepth: fractions %s: %d cells per pass, %d builds (S x R x T x (1 + F)), %d select_copies calls" % \
             (",".join("%g" % f for f in fracs), len(targets) * len(fracs), sum(st["builds"] for st in out["passes"]),
              sum(st["selects"] for st in out["passes"]))
+    if rpbs is not None:
+        closing += "; --spikeScanMnvRpb: reads-per-barcode targets %s: %d cells per pass, %d builds (S x R x T x (1 + Rr)), " \
+                   "%d select_copies_reads calls" % (",".join("%g" % r for r in rpbs), len(targets) * len(rpbs),
+                                                     sum(st["builds"] for st in out["passes"]), sum(st["selects"] for st in out["passes"]))
     print(closing)
+    for r, rule in zip(rpbs or (), out.get("rpb_rules", ())):
+        print("--spikeScanMnvRpb %g: sampler philox, seed %d, probKeep %.6g, threshold %d, %d of %d read names kept (mtDepth %d)" %
+              (r, rule["seed"], rule["prob_keep"], rule["thr"], rule["n_kept"], rule["n_names"], mt_depth))
 
 
 def _scan_filter_reports(args, plan, shard):

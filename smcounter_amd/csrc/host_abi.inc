@@ -1970,6 +1970,22 @@ static int spr_check_segments(const std::string& who, bool sets, const uint64_t*
     return SMC_OK;
 }
 
+// (the counts entries over records) the two axes of the cells - spk_axes' checks, the read thresholds into `Q`, the counters' limit
+static int spr_cells(const std::string& who, const smc_ctx* ctx, bool bad, const std::string& rows, size_t n_counters, int32_t n_rows,
+                     const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr,
+                     int32_t n_read_thr, SpkThr& T, RgThr& Q) {
+    if (int rc = spk_axes(who, ctx, bad, rows, n_rows, d_seeds, n_reps, thr, n_targets, true, " read thresholds", read_thr, n_read_thr, T)) return rc;
+    memset(&Q, 0, sizeof Q);
+    for (int32_t r = 0; r < n_read_thr; ++r) {
+        if (read_thr[r] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": read threshold " + std::to_string(r) + " is above 2^32");
+        if (r < SMC_RG_MAX_TARGETS) Q.t[r] = read_thr[r];         // (more of them pass the cells' limit only without a target: nothing is launched)
+    }
+    if ((double)n_rows * (double)n_reps * (double)n_targets * (double)n_read_thr * (double)n_counters >= (double)0xFFFFFF00u)
+        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_rows) + rows + " x " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) +
+                                 " targets x " + std::to_string(n_read_thr) + " read thresholds: too many counters for one call");
+    return SMC_OK;
+}
+
 // (--spikeRpb, --spikeIndelRpb, --spikePhaseRpb) what the three counts entries check, on the host copies and before anything is
 // enqueued, then the counters zeroed and k_spr_counts.  A row is a listed variant: (N', V0', S', READS', V1') per replicate and cell
 // (spike target x read threshold) from the records of its covering barcodes, segment e the records of barcode e - with `four` the
@@ -1985,16 +2001,8 @@ static int spr_cell_counts(const std::string& who, bool four, bool sets, smc_ctx
     const std::string rows = sets ? " sets" : " variants";
     const size_t n_counters = sets ? SPP_COUNTERS : SPC_COUNTERS;
     SpkThr T;
-    if (int rc = spk_axes(who, ctx, n_rec < 0, rows, n_rows, d_seeds, n_reps, thr, n_targets, true, " read thresholds", read_thr, n_read_thr, T)) return rc;
     RgThr Q;
-    memset(&Q, 0, sizeof Q);
-    for (int32_t r = 0; r < n_read_thr; ++r) {
-        if (read_thr[r] > (1ull << 32)) return fail(SMC_E_INPUT, who + ": read threshold " + std::to_string(r) + " is above 2^32");
-        if (r < SMC_RG_MAX_TARGETS) Q.t[r] = read_thr[r];         // (more of them pass the cells' limit only without a target: nothing is launched)
-    }
-    if ((double)n_rows * (double)n_reps * (double)n_targets * (double)n_read_thr * (double)n_counters >= (double)0xFFFFFF00u)
-        return fail(SMC_E_INPUT, who + ": " + std::to_string(n_rows) + rows + " x " + std::to_string(n_reps) + " replicates x " + std::to_string(n_targets) +
-                                 " targets x " + std::to_string(n_read_thr) + " read thresholds: too many counters for one call");
+    if (int rc = spr_cells(who, ctx, n_rec < 0, rows, n_counters, n_rows, d_seeds, n_reps, thr, n_targets, read_thr, n_read_thr, T, Q)) return rc;
     if (n_rec >= (int64_t)0xFFFFFF00) return fail(SMC_E_INPUT, who + ": too many covering records for one call");
     if (!n_rows || !n_reps || !n_targets) return SMC_OK;
     uint32_t widest = 0;
@@ -2098,6 +2106,63 @@ int smc_spike_phase_rpb_counts(smc_ctx* ctx, const uint64_t* d_joint_ident, cons
     return spr_cell_counts("smc_spike_phase_rpb_counts", false, true, ctx, d_joint_ident, d_joint_off, joint_off_host, d_set_m, set_m_host,
                            d_seg_base, seg_base_host, d_rec_off, rec_off_host, d_rec_name, d_rec_flag, n_rec, d_pos1, n_sets, d_seeds, n_reps,
                            thr, n_targets, read_thr, n_read_thr, d_out, stream);
+}
+
+// (--spikeScanMnvRpb) smc_spike_phase_rpb_counts' words from the run in barcode-major order and the read bits in HBM: no record CSR.
+// Everything is checked on the host copies before anything is enqueued; what only the device holds (d_bm_aln, d_joint_gid) is bounded
+// by the kernel itself.
+int smc_scan_phase_rpb_counts(smc_ctx* ctx, const uint32_t* d_bm_aln, const uint64_t* d_bm_name, const uint8_t* d_bm_first, int64_t n_aln,
+                              const uint32_t* d_bc_start, const uint32_t* bc_start_host, const uint64_t* d_idents, int64_t n_bc,
+                              const uint8_t* d_bits, int32_t n_var, const uint32_t* d_row_off, const uint32_t* row_off_host,
+                              const uint32_t* d_row_var, const uint32_t* row_var_host, const uint32_t* d_joint_off,
+                              const uint32_t* joint_off_host, const uint32_t* d_joint_gid, const uint32_t* d_pos1, int32_t n_rows,
+                              const uint64_t* d_seeds, int32_t n_reps, const uint64_t* thr, int32_t n_targets, const uint64_t* read_thr,
+                              int32_t n_read_thr, uint32_t* d_out, void* stream) {
+    const std::string who = "smc_scan_phase_rpb_counts";
+    SpkThr T;
+    RgThr Q;
+    if (int rc = spr_cells(who, ctx, n_aln < 0 || n_bc < 0 || n_var < 0, " rows", SPP_COUNTERS, n_rows, d_seeds, n_reps, thr, n_targets, read_thr,
+                           n_read_thr, T, Q)) return rc;
+    if (n_aln >= (int64_t)0xFFFFFF00 || n_bc >= (int64_t)0xFFFFFF00) return fail(SMC_E_INPUT, who + ": run too large for one call");
+    if (!n_rows || !n_reps || !n_targets) return SMC_OK;
+    if (!row_off_host || !d_row_off || !joint_off_host || !d_joint_off || !d_pos1 || !d_out || !bc_start_host || !d_bc_start)
+        return fail(SMC_E_ARG, who + ": NULL argument");
+    uint32_t widest = 0;
+    for (int32_t g = 0; g < n_rows; ++g) {
+        if (row_off_host[g + 1] < row_off_host[g]) return fail(SMC_E_INPUT, who + ": the row offsets decrease at row " + std::to_string(g));
+        const uint32_t m = row_off_host[g + 1] - row_off_host[g];
+        if (m < 1 || m > SMC_SPIKE_PHASE_MAX_MEMBERS)
+            return fail(SMC_E_INPUT, who + ": row " + std::to_string(g) + " has " + std::to_string(m) + " members, 1 .. " +
+                                     std::to_string(SMC_SPIKE_PHASE_MAX_MEMBERS) + " expected");
+        if (joint_off_host[g + 1] < joint_off_host[g]) return fail(SMC_E_INPUT, who + ": the joint offsets decrease at row " + std::to_string(g));
+        widest = std::max(widest, joint_off_host[g + 1] - joint_off_host[g]);
+    }
+    if (!row_var_host || !d_row_var) return fail(SMC_E_ARG, who + ": NULL members");
+    for (uint32_t k = row_off_host[0]; k < row_off_host[n_rows]; ++k)
+        if ((int64_t)row_var_host[k] >= (int64_t)n_var)
+            return fail(SMC_E_INPUT, who + ": member " + std::to_string(k) + " names bit row " + std::to_string(row_var_host[k]) + " of " + std::to_string(n_var));
+    for (int64_t b = 0; b < n_bc; ++b)
+        if (bc_start_host[b + 1] < bc_start_host[b]) return fail(SMC_E_INPUT, who + ": the barcode starts decrease at barcode " + std::to_string(b));
+    if ((int64_t)bc_start_host[n_bc] != n_aln)
+        return fail(SMC_E_INPUT, who + ": the barcode starts end at " + std::to_string(bc_start_host[n_bc]) + ", not at the " + std::to_string(n_aln) + " alignments");
+    if (widest && (!d_joint_gid || (n_bc && !d_idents) || (n_aln && (!d_bm_aln || !d_bm_name || !d_bm_first || !d_bits))))
+        return fail(SMC_E_ARG, who + ": NULL run");
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t n_out = (size_t)SPP_COUNTERS * (size_t)n_rows * (size_t)n_reps * (size_t)n_targets * (size_t)n_read_thr;
+    hipLaunchKernelGGL(k_bp_zero_words, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 4096)), dim3(256), 0, st, d_out, (uint32_t)n_out);
+    SprRun src;
+    memset(&src, 0, sizeof src);
+    src.bm_aln = d_bm_aln; src.bm_name = (const unsigned long long*)d_bm_name; src.bm_first = d_bm_first; src.bc_start = d_bc_start;
+    src.idents = (const unsigned long long*)d_idents; src.bits = d_bits; src.row_off = d_row_off; src.row_var = d_row_var;
+    src.joint_gid = d_joint_gid; src.n_aln = (uint32_t)n_aln; src.n_bc = (uint32_t)n_bc;
+    const auto kernel = n_read_thr <= 8 ? k_spr_run_counts<8> : k_spr_run_counts<SMC_RG_MAX_TARGETS>;     // (as spr_cell_counts chooses)
+    if (widest)
+        hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<uint32_t>((widest + SPB_BLOCK - 1) / SPB_BLOCK, 256u), (unsigned)n_rows,
+                                        (unsigned)std::min<int32_t>(n_reps, 64)), dim3(SPB_BLOCK), 0, st,
+                           src, d_joint_off, d_pos1, T, (int)n_targets, Q, (int)n_read_thr, (const unsigned long long*)d_seeds, (int)n_reps, d_out);
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
 }
 
 // (--spikeIndelRpb) per listed variant of a run - an SNV, an insertion, a deletion - and alignment one byte: covers / shows the key /

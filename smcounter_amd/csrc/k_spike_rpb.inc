@@ -46,6 +46,12 @@
 //                 READS', so flag bit 3 is not read and there is no <MAXR, true, true>.  A record that spans several members is a
 //                 record of each of their segments, and its read draw is made once per member.  Without SETS a row is a listed
 //                 variant - a set of one member whose segments are its covering barcodes - and its bit sets are never formed.
+// --spikeScanMnvRpb (smc_scan_phase_rpb_counts): the same joint numbers for a SCAN, where every locus of the panel is a set and a
+// per-variant record CSR made on the host would be loci x members x depth records sorted and gathered pass after pass.
+//   k_spr_run_counts  the SETS body of k_spr_counts (spr_counts, one body for both kernels) over a second record source, SprRun: the
+//                 run in barcode-major order, made once per decoded run, and k_spr_bits' bytes left in HBM.  A lane walks ALL records
+//                 of its joint barcode once per member and keeps those whose byte at the member has bit 0; names and first flags
+//                 come pre-gathered in walk order, so the walk streams and its one scattered load is the byte.
 #define SPB_BLOCK 256
 #define SPB_COVERS 1u
 #define SPB_ALT 2u
@@ -141,28 +147,98 @@ __device__ __forceinline__ void spr_segment(const uint32_t* __restrict__ rec_off
 }
 
 #define SPP_COUNTERS 4
+// WHERE THE RECORDS OF A (BARCODE, MEMBER) COME FROM - the one thing in which the entries of spr_counts differ.  A source answers,
+// per lane: row(g) -> the row's members; barcode(e) -> the identity of entry e of the row's barcodes; segment(e, m, r0, r1) -> the
+// records the lane walks for member m (PER_MEMBER: they differ by member, else they are fetched once per barcode); member(m) before
+// the walk of member m; flag(i, fl) -> whether record i is one of the member's, and its flag byte (bit 0 first name, bits 1 .. 3);
+// name(i) -> its read-name identity, asked for only where the draw is made.
+//   SprCsr<SETS>  a record CSR the host made (smc_spike_rpb_counts, smc_spike_indel_rpb_counts, smc_spike_phase_rpb_counts): row g's
+//                 barcodes are [off[g], off[g + 1]) of `ident`; segment s: records [rec_off[s], rec_off[s + 1]) of rec_name / rec_flag,
+//                 clamped to n_rec.  A listed variant is a set of ONE member whose segments are its covering barcodes (segment e for
+//                 barcode e: set_m and seg_base are not read); with SETS row g has set_m[g] members (1 .. SMC_SPIKE_PHASE_MAX_MEMBERS:
+//                 the host checked) and its segments start at seg_base[g].  Every record of a segment is the member's.
+//   SprRun        (smc_scan_phase_rpb_counts) no CSR: the run in barcode-major order and smc_spike_read_bits' bytes, both in HBM.
+//                 Entry e is the run-wide barcode id joint_gid[e]; the lane walks ALL records of that barcode, [bc_start[b],
+//                 bc_start[b + 1]) of bm_aln / bm_name / bm_first (streamed, clamped to n_aln), once per member, and record k is member
+//                 m's when bit 0 (covers) of bits[row_var[m] * n_aln + bm_aln[k]] is set - the one scattered load of the walk, a byte;
+//                 bits 1 and 2 of that byte are the flag's.  A record of another amplicon has a byte of 0 and is passed over.  An id
+//                 that is not below n_bc, or an alignment index that is not below n_aln, reads nothing.
+template <bool SETS>
+struct SprCsr {
+    static constexpr bool PER_MEMBER = SETS;
+    const unsigned long long* __restrict__ ident;
+    const uint32_t* __restrict__ off;
+    const uint32_t* __restrict__ set_m;
+    const uint32_t* __restrict__ seg_base;
+    const uint32_t* __restrict__ rec_off;
+    const unsigned long long* __restrict__ rec_name;
+    const uint8_t* __restrict__ rec_flag;
+    uint32_t n_rec;
+    uint32_t e0, n_mem, s_base;
+    __device__ __forceinline__ uint32_t row(uint32_t g) {
+        e0 = off[g]; n_mem = SETS ? set_m[g] : 1u; s_base = SETS ? seg_base[g] : 0u;
+        return n_mem;
+    }
+    __device__ __forceinline__ unsigned long long barcode(uint32_t e) { return ident[e]; }
+    __device__ __forceinline__ void segment(uint32_t e, uint32_t m, uint32_t& r0, uint32_t& r1) const {
+        spr_segment(rec_off, SETS ? s_base + (e - e0) * n_mem + m : e, n_rec, r0, r1);
+    }
+    __device__ __forceinline__ void member(uint32_t) {}
+    __device__ __forceinline__ bool flag(uint32_t i, uint32_t& fl) const { fl = rec_flag[i]; return true; }
+    __device__ __forceinline__ unsigned long long name(uint32_t i) const { return rec_name[i]; }
+};
+
+struct SprRun {
+    static constexpr bool PER_MEMBER = false;
+    const uint32_t* __restrict__ bm_aln;
+    const unsigned long long* __restrict__ bm_name;
+    const uint8_t* __restrict__ bm_first;
+    const uint32_t* __restrict__ bc_start;
+    const unsigned long long* __restrict__ idents;
+    const uint8_t* __restrict__ bits;
+    const uint32_t* __restrict__ row_off;
+    const uint32_t* __restrict__ row_var;
+    const uint32_t* __restrict__ joint_gid;
+    uint32_t n_aln, n_bc;
+    uint32_t v0, b;
+    const uint8_t* __restrict__ mine;
+    __device__ __forceinline__ uint32_t row(uint32_t g) { v0 = row_off[g]; return row_off[g + 1] - v0; }
+    __device__ __forceinline__ unsigned long long barcode(uint32_t e) {
+        b = joint_gid[e];
+        return b < n_bc ? idents[b] : 0ull;
+    }
+    __device__ __forceinline__ void segment(uint32_t, uint32_t, uint32_t& r0, uint32_t& r1) const {
+        r0 = r1 = 0u;
+        if (b < n_bc) { r0 = min(bc_start[b], n_aln); r1 = min(bc_start[b + 1], n_aln); }
+    }
+    __device__ __forceinline__ void member(uint32_t m) { mine = bits + (size_t)row_var[v0 + m] * n_aln; }      // (uniform: the host checked row_var)
+    __device__ __forceinline__ bool flag(uint32_t i, uint32_t& fl) const {
+        const uint32_t a = bm_aln[i];
+        if (a >= n_aln) return false;
+        const uint32_t byte = mine[a];
+        fl = (byte & (SPB_ALT | SPB_SINGLE)) | (bm_first[i] ? SPB_FIRST : 0u);
+        return (byte & SPB_COVERS) != 0u;
+    }
+    __device__ __forceinline__ unsigned long long name(uint32_t i) const { return bm_name[i]; }
+};
+
 // Without SETS  out[(((g * n_reps + j) * n_tgt + t) * n_rr + r) * 5 + k] += counter k of (N', V0', S', READS', V1'),
 // with SETS     out[(((g * n_reps + j) * n_tgt + t) * n_rr + r) * 4 + k] += counter k of (N_ALL', V0_ALL', S_ALL', V1_ALL')
-// (zeroed before the launch); n_tgt * n_rr <= SMC_AF_DEPTH_MAX_CELLS, n_rr <= MAXR (the host picks the instance).  Row g: barcodes
-// [off[g], off[g + 1]) of `ident`; segment s: records [rec_off[s], rec_off[s + 1]) of rec_name / rec_flag, clamped to n_rec.  A listed
-// variant is a set of ONE member whose segments are its covering barcodes (segment e for barcode e: set_m and seg_base are not read);
-// with SETS row g has set_m[g] members (1 .. SMC_SPIKE_PHASE_MAX_MEMBERS: the host checked) and its segments start at seg_base[g].
+// (zeroed before the launch); n_tgt * n_rr <= SMC_AF_DEPTH_MAX_CELLS, n_rr <= MAXR (the host picks the instance).  Row g: entries
+// [off[g], off[g + 1]) of the source's barcodes; its records: the source's (above).
 // FOUR (smc_spike_indel_rpb_counts): flag bit 2 is alt1 and bit 3 touch, a per-r counter each; without it bit 2 is both (`single`) and
 // bit 3 is not read - a set has no READS', so it never reads it.
-template <int MAXR, bool FOUR, bool SETS>
-__global__ __launch_bounds__(SPB_BLOCK) void k_spr_counts(const unsigned long long* __restrict__ ident, const uint32_t* __restrict__ off,
-                                                          const uint32_t* __restrict__ set_m, const uint32_t* __restrict__ seg_base,
-                                                          const uint32_t* __restrict__ rec_off, const unsigned long long* __restrict__ rec_name,
-                                                          const uint8_t* __restrict__ rec_flag, uint32_t n_rec,
-                                                          const uint32_t* __restrict__ pos1, SpkThr T, int n_tgt, RgThr Q, int n_rr,
-                                                          const unsigned long long* __restrict__ seeds, int n_reps, uint32_t* __restrict__ out) {
-    static_assert(!(FOUR && SETS), "k_spr_counts: a set never reads flag bit 3");
+template <int MAXR, bool FOUR, bool SETS, class SRC>
+__device__ __forceinline__ void spr_counts(SRC src, const uint32_t* __restrict__ off, const uint32_t* __restrict__ pos1, SpkThr T, int n_tgt,
+                                           RgThr Q, int n_rr, const unsigned long long* __restrict__ seeds, int n_reps,
+                                           uint32_t* __restrict__ out) {
+    static_assert(!(FOUR && SETS), "spr_counts: a set never reads flag bit 3");
     constexpr int NC = SETS ? SPP_COUNTERS : SPC_COUNTERS;
     constexpr int TAIL = SETS ? 1 : MAXR;                  // (the cells' tail unrolled over the per-r arrays; a set's reads bit r of three words: a loop)
     __shared__ uint32_t part[SPB_BLOCK / WAVE][SMC_AF_DEPTH_MAX_CELLS][NC];
     const uint32_t g = blockIdx.y;
     const uint32_t e0 = off[g], e1 = off[g + 1], pos = pos1[g];
-    const uint32_t n_mem = SETS ? set_m[g] : 1u, s_base = SETS ? seg_base[g] : 0u;
+    const uint32_t n_mem = src.row(g);
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const int n_cells = n_tgt * n_rr;
     const uint32_t every = n_rr >= 32 ? 0xFFFFFFFFu : (1u << n_rr) - 1u;
@@ -170,10 +246,9 @@ __global__ __launch_bounds__(SPB_BLOCK) void k_spr_counts(const unsigned long lo
     for (uint32_t base = e0 + blockIdx.x * SPB_BLOCK; base < e1; base += stride) {     // (whole workgroups: the barriers below)
         const uint32_t e = base + threadIdx.x;
         const bool in_row = e < e1;
-        const unsigned long long id = in_row ? ident[e] : 0ull;
-        const uint32_t s0 = s_base + (e - e0) * n_mem;                                 // (SETS, read only in_row)
+        const unsigned long long id = in_row ? src.barcode(e) : 0ull;
         uint32_t r0 = 0, r1 = 0;                                                       // (a lane beyond the row: no records, N' = 0 everywhere)
-        if (!SETS && in_row) spr_segment(rec_off, e, n_rec, r0, r1);                   // (the variant's one segment, the same for every replicate)
+        if (!SRC::PER_MEMBER && in_row) src.segment(e, 0u, r0, r1);                    // (one segment for every member and replicate)
         for (int j = blockIdx.z; j < n_reps; j += gridDim.z) {
             const unsigned long long seed = seeds[j];
             uint32_t x[4];
@@ -182,14 +257,16 @@ __global__ __launch_bounds__(SPB_BLOCK) void k_spr_counts(const unsigned long lo
             uint32_t reads[MAXR], alt[MAXR], sgl[MAXR], tch[FOUR ? MAXR : 1];
             uint32_t all_there = in_row ? every : 0u, all_c0 = every, all_c1 = every;  // (SETS; a lane beyond the row: N_ALL' = 0 everywhere)
             for (uint32_t m = 0; m < n_mem; ++m) {                                     // (uniform bound; once without SETS)
-                if (SETS && in_row) spr_segment(rec_off, s0 + m, n_rec, r0, r1);
+                if (SRC::PER_MEMBER && in_row) src.segment(e, m, r0, r1);
+                src.member(m);
 #pragma unroll
                 for (int r = 0; r < MAXR; ++r) { reads[r] = alt[r] = sgl[r] = 0u; if (FOUR) tch[r] = 0u; }
                 for (uint32_t i = r0; i < r1; ++i) {
-                    const uint32_t fl = rec_flag[i];
+                    uint32_t fl;
+                    if (!src.flag(i, fl)) continue;
                     uint32_t kept = every;
                     if (!(fl & SPB_FIRST)) {
-                        const uint32_t u = rg_draw(rec_name[i], seed);
+                        const uint32_t u = rg_draw(src.name(i), seed);
                         kept = 0u;
                         for (int r = 0; r < n_rr; ++r) kept |= (uint32_t)((unsigned long long)u < Q.t[r]) << r;
                     }
@@ -244,8 +321,32 @@ __global__ __launch_bounds__(SPB_BLOCK) void k_spr_counts(const unsigned long lo
         }
     }
 }
+
+// spr_counts over a record CSR of the host's
+template <int MAXR, bool FOUR, bool SETS>
+__global__ __launch_bounds__(SPB_BLOCK) void k_spr_counts(const unsigned long long* __restrict__ ident, const uint32_t* __restrict__ off,
+                                                          const uint32_t* __restrict__ set_m, const uint32_t* __restrict__ seg_base,
+                                                          const uint32_t* __restrict__ rec_off, const unsigned long long* __restrict__ rec_name,
+                                                          const uint8_t* __restrict__ rec_flag, uint32_t n_rec,
+                                                          const uint32_t* __restrict__ pos1, SpkThr T, int n_tgt, RgThr Q, int n_rr,
+                                                          const unsigned long long* __restrict__ seeds, int n_reps, uint32_t* __restrict__ out) {
+    SprCsr<SETS> src;
+    src.ident = ident; src.off = off; src.set_m = set_m; src.seg_base = seg_base; src.rec_off = rec_off; src.rec_name = rec_name;
+    src.rec_flag = rec_flag; src.n_rec = n_rec;
+    spr_counts<MAXR, FOUR, SETS>(src, off, pos1, T, n_tgt, Q, n_rr, seeds, n_reps, out);
+}
+
+// spr_counts over the run in barcode-major order and the read bits in HBM (smc_scan_phase_rpb_counts): always the sets' four counters,
+// a row of one member a listed variant
+template <int MAXR>
+__global__ __launch_bounds__(SPB_BLOCK) void k_spr_run_counts(SprRun src, const uint32_t* __restrict__ joint_off, const uint32_t* __restrict__ pos1,
+                                                              SpkThr T, int n_tgt, RgThr Q, int n_rr,
+                                                              const unsigned long long* __restrict__ seeds, int n_reps,
+                                                              uint32_t* __restrict__ out) {
+    spr_counts<MAXR, false, true>(src, joint_off, pos1, T, n_tgt, Q, n_rr, seeds, n_reps, out);
+}
 static_assert(SMC_RG_MAX_TARGETS == SMC_AF_DEPTH_MAX_CELLS && SPP_COUNTERS <= SPC_COUNTERS && SPC_COUNTERS * SMC_AF_DEPTH_MAX_CELLS <= SPB_BLOCK,
-              "k_spr_counts: a bit per read threshold, a lane per cell and counter");
+              "spr_counts: a bit per read threshold, a lane per cell and counter");
 
 // ------------------------------------------------------------------------------------------
 // --spikeGrid (smc_spike_grid_counts): the cells (spike target t, barcode fraction f, reads-per-barcode target r)

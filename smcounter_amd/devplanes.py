@@ -2857,20 +2857,34 @@ SPB_ALT1, SPB_TOUCH = 4, 8                                   # smc_spike_indel_r
 def spike_read_bits(eng, up: RunOnDevice, A, lo: int, var: np.ndarray) -> np.ndarray:
     """smc_spike_read_bits over the run `up` (A: its host arrays) -> uint8 [n_var, n_aln]: per listed SNV (af_run_variants' records) and
     alignment bit 0 = the record covers the position, bit 1 = it shows ALT as it is, bit 2 = its allele key there is a single letter."""
-    from .engine import DevBuf
     n_var, n = len(var), up.n_aln
     if not n_var or not n:
         return np.zeros((n_var, n), np.uint8)
+    d_out = spike_read_bits_dev(eng, up, A, lo, var)
+    try:
+        return d_out.download(np.uint8, n_var * n).reshape(n_var, n)                      # (the default stream: behind the kernel)
+    finally:
+        d_out.free()
+
+
+def spike_read_bits_dev(eng, up: RunOnDevice, A, lo: int, var: np.ndarray):
+    """spike_read_bits that leaves the bytes in HBM -> the DevBuf of n_var x n_aln bytes (the caller frees it); enqueued on the default
+    stream, nothing waits.  What smc_scan_phase_rpb_counts takes as d_bits."""
+    from .engine import DevBuf
+    n_var, n = len(var), up.n_aln
     var = np.ascontiguousarray(var, abi.AF_VARIANT_DTYPE)
-    d_var = DevBuf(eng, var.nbytes + 256).upload(var.view(np.uint8).reshape(-1))
+    d_var = DevBuf(eng, var.nbytes + 256).upload(var.view(np.uint8).reshape(-1) if n_var else np.zeros(4, np.uint8))
     d_out = DevBuf(eng, n_var * n + 256)
     try:
         _lib.check(eng.L.smc_spike_read_bits(eng.ctx, up.aln.data_ptr(), n, up.cig.data_ptr(), len(A["cig"]), up.bq.data_ptr(), len(A["bq"]) // 2,
                                              up.loc.data_ptr(), int(A["nl"]), int(lo), d_var.data_ptr(), var.ctypes.data, n_var,
                                              d_out.data_ptr(), ctypes.c_void_p(0)), "smc_spike_read_bits")
-        return d_out.download(np.uint8, n_var * n).reshape(n_var, n)                      # (the default stream: behind the kernel)
+        return d_out                            # (d_var goes back to the spare list: whatever takes it next is behind the kernel on this stream)
+    except BaseException:
+        d_out.free()
+        raise
     finally:
-        d_var.free(); d_out.free()
+        d_var.free()
 
 
 def spike_indel_read_bits(eng, up: RunOnDevice, A, lo: int, var: np.ndarray, ins: np.ndarray) -> np.ndarray:
@@ -3140,6 +3154,95 @@ def spike_phase_rpb_counts(eng, lead_positions, set_members, joint_records, seed
                                                           seg_base.ctypes.data, d[4], rec_off.ctypes.data, d[5], d[6], len(name), d[7], G,
                                                           d[8], len(seeds), thr.ctypes.data, len(thr), rthr.ctypes.data, len(rthr), d_out,
                                                           ctypes.c_void_p(0)))
+
+
+SCAN_RPB_MAX_CELLS = 32           # SMC_AF_DEPTH_MAX_CELLS: spike targets x read thresholds of one counts call
+SCAN_BITS_BUDGET = 256 << 20      # bytes of read bits (bit rows x alignments) one smc_scan_phase_rpb_counts call of the stage keeps in HBM
+
+
+def run_barcode_major(A, p_idents, first) -> dict:
+    """The run `A` in barcode-major order, as smc_scan_phase_rpb_counts takes it: ONE stable argsort of bc_gid, so a barcode's records
+    stay in file order.  p_idents: the identity of every read-name id of the run; first: bool per read-name id, the name is its
+    barcode's first, file-wide -> dict(bm_aln uint32 [n_aln]: the alignment's index in the run, bm_name uint64: the identity of its
+    read name, bm_first uint8: 1 where that name is a first one, bc_start uint32 [n_bc + 1]: where each barcode's records begin)."""
+    aln, n_bc = A["aln"], int(A["n_bc"])
+    bc = aln["bc_gid"].astype(np.int64)
+    if len(bc) and int(bc.max()) >= n_bc:
+        raise ValueError("run_barcode_major: a record of barcode %d in a run of %d barcodes" % (int(bc.max()), n_bc))
+    order = np.argsort(bc, kind="stable")
+    pair = aln["pair_gid"][order]
+    bc_start = np.zeros(n_bc + 1, np.uint32)
+    bc_start[1:] = np.cumsum(np.bincount(bc, minlength=n_bc))
+    return dict(bm_aln=order.astype(np.uint32), bm_name=np.ascontiguousarray(np.asarray(p_idents, np.uint64)[pair]),
+                bm_first=np.asarray(first, bool)[pair].astype(np.uint8), bc_start=bc_start)
+
+
+class RunOrder(object):
+    """run_barcode_major's arrays and the barcodes' identities on the device, for every smc_scan_phase_rpb_counts call over one
+    decoded run; `host`: the arrays as they went up (bc_start is the entry's host copy).  free() when the run goes."""
+
+    def __init__(self, eng, order: dict, idents):
+        self.host = dict(order, idents=np.ascontiguousarray(idents, np.uint64))
+        self.n_aln, self.n_bc = len(order["bm_aln"]), len(order["bc_start"]) - 1
+        if len(self.host["idents"]) < self.n_bc:
+            raise ValueError("RunOrder: %d identities for %d barcodes" % (len(self.host["idents"]), self.n_bc))
+        self.bufs = []
+        try:
+            for k in ("bm_aln", "bm_name", "bm_first", "bc_start", "idents"):
+                self.bufs.append(_up8(eng, np.ascontiguousarray(self.host[k])))
+        except BaseException:
+            self.free()
+            raise
+
+    def free(self):
+        for b in self.bufs:
+            b.free()
+        self.bufs = []
+
+
+def scan_set_chunks(n_sets: int, members: int, n_aln: int, budget: int = None):
+    """[(first set, end)]: a pass's sets cut so that the read bits of a chunk - `members` bit rows per set, n_aln bytes each - stay under
+    `budget` bytes (SCAN_BITS_BUDGET unless given; one set at the least)."""
+    per = max(1, int(SCAN_BITS_BUDGET if budget is None else budget) // max(1, int(members) * max(1, int(n_aln))))
+    return [(a, min(n_sets, a + per)) for a in range(0, n_sets, per)]
+
+
+def scan_phase_rpb_counts(eng, run_order: RunOrder, d_bits, n_var: int, rows, joint_gids, lead_positions, seeds, thresholds,
+                          read_thresholds) -> np.ndarray:
+    """smc_scan_phase_rpb_counts -> uint32 [rows, R, T, Rr, 4] = (N_ALL', V0_ALL', S_ALL', V1_ALL') of every row, replicate and cell,
+    spike_phase_rpb_counts' words without a record CSR.  run_order: the decoded run's RunOrder; d_bits: spike_read_bits_dev's buffer of
+    n_var x n_aln bytes, left in HBM; rows[g]: the indices of the bit rows of row g's members, in order (one index: a listed variant);
+    joint_gids[g]: the run-wide ids of the barcodes that cover every member of row g, in any order; lead_positions[g]: the 1-based
+    position row g is drawn with; seeds, thresholds, read_thresholds: spike_rpb_counts'."""
+    G = len(rows)
+    if len(joint_gids) != G or len(lead_positions) != G:
+        raise ValueError("scan_phase_rpb_counts: %d rows, %d joint lists, %d positions" % (G, len(joint_gids), len(lead_positions)))
+    row_off, joint_off = np.zeros(G + 1, np.uint32), np.zeros(G + 1, np.uint32)
+    row_off[1:] = np.cumsum([len(r) for r in rows])
+    joint_off[1:] = np.cumsum([len(j) for j in joint_gids])
+    cat = lambda xs: np.concatenate([np.asarray(x, np.uint32).reshape(-1) for x in xs]) if G else np.zeros(0, np.uint32)
+    row_var, joint_gid = np.ascontiguousarray(cat(rows)), np.ascontiguousarray(cat(joint_gids))
+    pos = np.array([int(p) & 0xFFFFFFFF for p in lead_positions], np.uint32)
+    seeds = np.ascontiguousarray(seeds, np.uint64)
+    thr, rthr = np.ascontiguousarray(thresholds, np.uint64), np.ascontiguousarray(read_thresholds, np.uint64)
+    o, bc_start = run_order.bufs, run_order.host["bc_start"]
+    return _spike_counts_call(
+        eng, "smc_scan_phase_rpb_counts", [row_off, row_var, joint_off, joint_gid, pos, seeds], (G, len(seeds), len(thr), len(rthr), 4),
+        lambda d, d_out: eng.L.smc_scan_phase_rpb_counts(eng.ctx, o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), run_order.n_aln,
+                                                         o[3].data_ptr(), bc_start.ctypes.data, o[4].data_ptr(), run_order.n_bc,
+                                                         d_bits.data_ptr(), int(n_var), d[0], row_off.ctypes.data, d[1], row_var.ctypes.data,
+                                                         d[2], joint_off.ctypes.data, d[3], d[4], G, d[5], len(seeds), thr.ctypes.data,
+                                                         len(thr), rthr.ctypes.data, len(rthr), d_out, ctypes.c_void_p(0)))
+
+
+def scan_phase_rpb_counts_rule(run_order, bits, rows, joint_gids, lead_positions, seeds, thresholds, read_thresholds, detail=None):
+    """abi.scan_phase_rpb_counts_rule on scan_phase_rpb_counts' arguments (run_order: a RunOrder or its host dict; bits: uint8 [n_var,
+    n_aln] on the host)."""
+    h = run_order.host if isinstance(run_order, RunOrder) else run_order
+    row_off, joint_off = np.cumsum([0] + [len(r) for r in rows]), np.cumsum([0] + [len(j) for j in joint_gids])
+    cat = lambda xs: np.concatenate([np.asarray(x, np.int64).reshape(-1) for x in xs]) if len(xs) else np.zeros(0, np.int64)
+    return abi.scan_phase_rpb_counts_rule(h["bm_aln"], h["bm_name"], h["bm_first"], h["bc_start"], h["idents"], bits, row_off, cat(rows),
+                                          joint_off, cat(joint_gids), lead_positions, seeds, thresholds, read_thresholds, detail)
 
 
 def spike_copy_strides(n_aln: int, n_pairs: int):
@@ -3887,7 +3990,9 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
     `depth`'s cells with the joint verdicts per cell - the ONE select_copies call, every fraction's selections one batch, decided at the
     cell's params and cut by smc_scan_detect_sets (and smc_scan_filter_sets); replicate 0's (N_ALL', V1_ALL') of every cell is counted
     a second time, the AND over the members of smc_allele_carriers' bits on its selection.  mnv["out"] and mnv["flt_out"] are LISTS:
-    full depth first, then the cells in order."""
+    full depth first, then the cells in order.
+    `mnv` beside `rpb` (--spikeScanMnvRpb; mnv["want_joint_cells"]: per r, copy and set smc_scan_phase_rpb_counts' (N_ALL', V1_ALL')):
+    `rpb`'s cells with the joint verdicts per cell in the same way - the ONE select_copies_reads call, every r's selections one batch."""
     from . import dsaf, spike as _spike, vc
     from .engine import DevBuf
     A, lo, nl, chrom = run.A, run.lo, run.nl, run.chrom
@@ -4122,7 +4227,8 @@ def _scan_call(eng, run: AfRun, svar, var_at, listed, part_seeds, thr: int, want
             return full
         if rpb is not None:
             sels = select_copies_reads(eng, runs, A, lo, rpb["masks"], rpb["n_words"], rpb["copy_stride"], len(rpb["targets"]))
-            axis, cell_flag = [" x --spikeScanRpb %g" % r for r in rpb["targets"]], "--spikeScanRpb"
+            cell_flag = "--spikeScanRpb" if mnv is None else "--spikeScanMnvRpb"
+            axis = [" x %s %g" % (cell_flag, r) for r in rpb["targets"]]
         else:
             sels = select_copies(eng, runs, A, lo, run.idents, part_seeds, depth["fracs"])
             axis, cell_flag = [" x fraction %g" % f for f in depth["fracs"]], "--spikeScanDepth" if mnv is None else "--spikeScanMnvDepth"
@@ -4217,7 +4323,14 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     with --spikeDepth <fracs> beside --spikeReps --spikePhase; the stage runs `depth`'s cells with the joint verdicts per cell, the joint
     counts of every (set, replicate, target, fraction) from the ONE smc_spike_phase_counts call per pass and run.  The result gets
     joint_depth_counts: uint32 [sets, R, T, F, 4], joint_depth_called: bool [sets, T, F, R], with flt joint_depth_filter: uint32 [sets,
-    T, F, R], and depth's own depth_counts / depth_called per member.  ValueError: without `mnv`; any other key.
+    T, F, R], and depth's own depth_counts / depth_called per member.  `mnv_axes["reads"]` (--spikeScanMnvRpb: the dict `rpb=` takes;
+    not beside "depth" - the grid is not built): a pass is then the run --spikeIndelReps n_reps --spikePhaseRpb <r...> on its MNV lines;
+    the stage runs `rpb`'s cells with the joint verdicts per cell - philox_read_rules once per file, _scan_read_masks once per decoded
+    run (with the run's barcode-major order on the device), per pass, run and chunk of sets ONE smc_scan_phase_rpb_counts call for the
+    joint and the members' counts of every r (_scan_joint_rpb, which also holds the first pass of every run against the host's record
+    lists), ONE select_copies_reads call per full-depth batch.  The result gets joint_rpb_counts: uint32 [sets, R, T, Rr, 4],
+    joint_rpb_called: bool [sets, T, Rr, R], rpb_rules, and with flt joint_rpb_filter: uint32 [sets, T, Rr, R].  ValueError: without
+    `mnv`; any other key ("rpb" among them, as before).
     -> dict(seeds, base: per variant (N, V0), counts: uint32 [V, R, T, 3] = (S, READS, V1), called: bool [V, T, R], passes: per pass
     of `passes` dict(variants, copies, builds, host, seconds), times: dict(stage, runs, decode))."""
     import time
@@ -4232,10 +4345,15 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     mnv_axes = dict(mnv_axes or {})
     if mnv_axes and not mnv:
         raise ValueError("--spikeScanMnvFilter: the axes of an MNV scan need --spikeScanMnv")
-    if set(mnv_axes) - {"flt", "depth"}:
+    if set(mnv_axes) - {"flt", "depth", "reads"}:
         raise ValueError("--spikeScanMnv: the reads-per-barcode axis of an MNV scan is not built")
+    if mnv_axes.get("depth") is not None and mnv_axes.get("reads") is not None:
+        raise ValueError("--spikeScanMnvRpb: the grid of barcode fractions x reads-per-barcode targets is not built")
     if mnv_axes.get("depth") is not None:
         depth = mnv_axes["depth"]               # (the cells are --spikeScanDepth's: one select_copies call, a batch per fraction)
+    if mnv_axes.get("reads") is not None:
+        rpb = mnv_axes["reads"]                 # (the cells are --spikeScanRpb's: one select_copies_reads call, a batch per r)
+    rpb_flag = "--spikeScanMnvRpb" if mnv else "--spikeScanRpb"
     seeds = dsaf.rep_seeds(seed, R)
     thr = [sv.threshold(t) for t in targets]
     P = params
@@ -4259,8 +4377,8 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
             from . import spike as _spike
             gate, always = _spike.scan_filter_words(variants, params.hpLen, fasta, *repeats)
             mnv["flt"] = dict(gate=gate, always=always, words=np.zeros((len(sets), T, R), np.uint32), host=0)
-        if depth is not None:
-            Fm = len(depth["fracs"])
+        if (depth or rpb) is not None:
+            Fm = len(depth["fracs"]) if depth is not None else len(rpb["targets"])
             mnv.update(cell_counts=np.zeros((len(sets), R, T, Fm, 4), np.uint32), cell_called=np.zeros((len(sets), T, Fm, R), bool))
             if mnv.get("flt"):
                 mnv["flt"]["cell_words"] = np.zeros((len(sets), T, Fm, R), np.uint32)
@@ -4286,8 +4404,10 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     if rpb is not None:
         F = len(rpb["targets"])
         # (the file-wide table of the UNSPIKED file serves every pass, cell and replicate: spiking changes no name, barcode or record count)
-        read_rules = philox_read_rules(path, list(rpb["targets"]), [P] * F, seed, eng, nthreads=nthreads, flag="--spikeScanRpb")
-        rpb = dict(rpb, counts=np.zeros((V, R, T, F, 5), np.uint32), called=np.zeros((V, T, F, R), bool), read_thr=[r.thr for r in read_rules])
+        read_rules = philox_read_rules(path, list(rpb["targets"]), [P] * F, seed, eng, nthreads=nthreads, flag=rpb_flag)
+        # (under `mnv` a member's cells have no READS': the four columns of a row of one member)
+        rpb = dict(rpb, counts=np.zeros((V, R, T, F, 5 if mnv is None else 4), np.uint32), called=np.zeros((V, T, F, R), bool),
+                   read_thr=[r.thr for r in read_rules])
     for st in stats if (depth or rpb) is not None else ():
         st["selects"] = 0
     if flt:
@@ -4325,7 +4445,8 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
                 for p in in_run if indel else ():
                     _refuse_indel_limits(run.A, spikes[p].chrom_variants(chrom, 0.5)[0], "--spikeScanIndel", chrom)
                 if rpb is not None:
-                    rpb.update(_scan_read_masks(eng, run, read_rules, seeds))
+                    rpb.update(_scan_read_masks(eng, run, read_rules, seeds, rpb_flag, order=mnv is not None))
+                    rpb["check_host"] = True    # (--spikeScanMnvRpb: the first pass of the run also counts the existing way)
                 for p in in_run:
                     t0 = time.perf_counter()
                     run.group = [k for k in inside if pass_at[k] == p]
@@ -4342,6 +4463,8 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
             finally:
                 if rpb is not None and rpb.get("masks") is not None:
                     rpb.pop("masks").free()
+                if rpb is not None and rpb.get("order") is not None:
+                    rpb.pop("order").free()
                 run.free()
             spans.send(len(inside) if mnv is None else len(taken))
     finally:
@@ -4351,8 +4474,9 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     if depth is not None:
         out.update(depth_counts=depth["counts"], depth_called=depth["called"])
     if rpb is not None:
-        out.update(rpb_counts=rpb["counts"], rpb_called=rpb["called"],
-                   rpb_rules=[dict(seed=r.seed, prob_keep=r.prob_keep, thr=r.thr, n_kept=r.n_kept, n_names=r.n_names) for r in read_rules])
+        if mnv is None:
+            out.update(rpb_counts=rpb["counts"], rpb_called=rpb["called"])
+        out.update(rpb_rules=[dict(seed=r.seed, prob_keep=r.prob_keep, thr=r.thr, n_kept=r.n_kept, n_names=r.n_names) for r in read_rules])
     if mnv is not None:
         out.update(joint_counts=mnv["counts"], joint_called=mnv["called"], joint_host=mnv["host"])
         if mnv.get("flt"):
@@ -4361,6 +4485,10 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
             out.update(joint_depth_counts=mnv["cell_counts"], joint_depth_called=mnv["cell_called"])
             if mnv.get("flt"):
                 out["joint_depth_filter"] = mnv["flt"]["cell_words"]
+        if rpb is not None:
+            out.update(joint_rpb_counts=mnv["cell_counts"], joint_rpb_called=mnv["cell_called"])
+            if mnv.get("flt"):
+                out["joint_rpb_filter"] = mnv["flt"]["cell_words"]
     if flt is not None:
         out.update(filter=flt["words"], filter_host=flt["host"])
         if (depth or rpb) is not None:
@@ -4368,15 +4496,17 @@ def spike_scan(path: str, fasta, variants, passes, targets, params, seed: int, n
     return out
 
 
-def _scan_read_masks(eng, run: AfRun, read_rules, seeds) -> dict:
+def _scan_read_masks(eng, run: AfRun, read_rules, seeds, flag: str = "--spikeScanRpb", order: bool = False) -> dict:
     """(--spikeScanRpb) What the passes of one decoded run share on the read axis: the identity of every read-name id (BamError naming
     the flag: an id that stands for two names), whether a name is its barcode's first, and the keep masks of every seed and
     reads-per-barcode target in ONE device buffer - seed j's len(read_rules) masks at j x len(read_rules) x n_words words, the layout
     smc_select_alignments_reads_copies takes for a batch of consecutive seeds; one ReadGroups.masks launch per seed.
-    -> dict(p_idents, first, masks, n_words); the caller frees `masks`."""
+    -> dict(p_idents, first, masks, n_words); the caller frees `masks`.  `order` (--spikeScanMnvRpb): the dict also gets "order", the
+    run's RunOrder - the run in barcode-major order from A["aln"], p_idents and first, ONE stable argsort, on the device for every
+    smc_scan_phase_rpb_counts call over the run; the caller frees it with the masks."""
     from .engine import DevBuf
     groups, Rr = read_rules[0].groups, len(read_rules)
-    p_idents = pair_idents_or_refuse(run.bam, run.A, "--spikeScanRpb", run.chrom, run.lo, run.nl)
+    p_idents = pair_idents_or_refuse(run.bam, run.A, flag, run.chrom, run.lo, run.nl)
     first = run_first_names(eng, groups, p_idents, run.chrom, run.lo, run.nl)
     n = len(p_idents)
     n_words = (n + 31) // 32
@@ -4393,9 +4523,67 @@ def _scan_read_masks(eng, run: AfRun, read_rules, seeds) -> dict:
         d_id.free()
     if st & RG_MISS:
         buf.free()
-        raise bamio.BamError("--spikeScanRpb: the run %s:%d-%d has a read name the file-wide table does not hold (status %#x)"
-                             % (run.chrom, run.lo + 1, run.lo + run.nl, st))
-    return dict(p_idents=p_idents, first=first, masks=buf, n_words=n_words)
+        raise bamio.BamError("%s: the run %s:%d-%d has a read name the file-wide table does not hold (status %#x)"
+                             % (flag, run.chrom, run.lo + 1, run.lo + run.nl, st))
+    out = dict(p_idents=p_idents, first=first, masks=buf, n_words=n_words)
+    if order:
+        try:
+            out["order"] = RunOrder(eng, run_barcode_major(run.A, p_idents, first), run.idents)
+        except BaseException:
+            buf.free()
+            raise
+    return out
+
+
+def _scan_joint_rpb(eng, run: AfRun, rpb: dict, var, cov, covers, lead, first, L: int, seeds, thr, joint_counts, variants):
+    """(--spikeScanMnvRpb) _scan_pass' cells of the read axis for a pass of MNV sets in one run: per chunk of sets (scan_set_chunks: the
+    bit rows stay under SCAN_BITS_BUDGET) smc_spike_read_bits leaves the members' bytes in HBM and ONE smc_scan_phase_rpb_counts call
+    over the run's barcode-major order (rpb["order"]) counts every r - the chunk's sets as rows, then every member as a row of one.
+    var, cov, covers, lead: the pass's members in the run, their records, cover rows, covering identities and draw positions; first:
+    where each set begins in them -> (uint32 [sets, R, T, Rr, 4] joint, uint32 [members, R, T, Rr, 4] per member).
+    Where the cells' limit leaves room the threshold 2^32 rides along as one more r, and its joint words must be `joint_counts`, the
+    full-depth numbers of smc_spike_phase_counts.  rpb["check_host"] (the first pass of a decoded run; taken out here): the joint words
+    are also made the existing way - the bytes downloaded, spike_rpb_records, spike_joint_records, smc_spike_phase_rpb_counts - and a
+    word that differs ends the run."""
+    from .tools import spike_variants as sv
+    A, up, lo, chrom, n_ids = run.A, run.up, run.lo, run.chrom, len(run.idents)
+    order, rthr = rpb["order"], list(rpb["read_thr"])
+    Rr, n_sets = len(rthr), len(first)
+    ride = len(thr) * (Rr + 1) <= SCAN_RPB_MAX_CELLS              # (full depth as one more read threshold)
+    call_thr = rthr + ([1 << 32] if ride else [])
+    joint = np.zeros((n_sets, len(seeds), len(thr), len(call_thr), 4), np.uint32)
+    cells = np.zeros((len(var), len(seeds), len(thr), len(call_thr), 4), np.uint32)
+    cover = np.asarray(cov)[:, :n_ids] != 0
+    for a, b in scan_set_chunks(n_sets, L, up.n_aln):
+        rows_v = list(range(first[a], first[b - 1] + L))        # the chunk's members: bit row k of the chunk is member rows_v[k]
+        d_bits = spike_read_bits_dev(eng, up, A, lo, var[rows_v])
+        try:
+            rows = [list(range((s_ - a) * L, (s_ - a + 1) * L)) for s_ in range(a, b)] + [[k] for k in range(len(rows_v))]
+            gids = [np.flatnonzero(cover[first[s_]:first[s_] + L].all(axis=0)).astype(np.uint32) for s_ in range(a, b)] + \
+                   [np.flatnonzero(cover[g]).astype(np.uint32) for g in rows_v]
+            pos = [lead[first[s_]] for s_ in range(a, b)] + [lead[g] for g in rows_v]
+            got = scan_phase_rpb_counts(eng, order, d_bits, len(rows_v), rows, gids, pos, seeds, thr, call_thr)
+            if rpb.pop("check_host", False):
+                bits = d_bits.download(np.uint8, len(rows_v) * up.n_aln).reshape(len(rows_v), up.n_aln)
+                records = [spike_rpb_records(A, bits[k], np.flatnonzero(cover[g]), rpb["p_idents"], rpb["first"]) for k, g in enumerate(rows_v)]
+                sets = [sv.PhaseSet("", chrom, tuple(r)) for r in rows[:b - a]]
+                theirs = spike_phase_rpb_counts(eng, pos[:b - a], [L] * (b - a), spike_joint_records(sets, [covers[g] for g in rows_v], records),
+                                                seeds, thr, call_thr)
+                if not np.array_equal(theirs, got[:b - a]):
+                    s_ = a + int(np.argwhere(theirs != got[:b - a])[0][0])
+                    v = variants[run.group[first[s_]]]
+                    raise RuntimeError("--spikeScanMnvRpb: the set at %s:%d: smc_scan_phase_rpb_counts and smc_spike_phase_rpb_counts on the "
+                                       "host's records disagree: %r against %r" % (v.chrom, v.pos, got[s_ - a].tolist(), theirs[s_ - a].tolist()))
+        finally:
+            d_bits.free()
+        joint[a:b] = got[:b - a]
+        cells[rows_v] = got[b - a:]
+    if ride and not np.array_equal(joint[:, :, :, Rr], joint_counts):
+        s_ = int(np.argwhere(joint[:, :, :, Rr] != joint_counts)[0][0])
+        v = variants[run.group[first[s_]]]
+        raise RuntimeError("--spikeScanMnvRpb: the set at %s:%d: at the read threshold 2^32 smc_scan_phase_rpb_counts gives %r, "
+                           "smc_spike_phase_counts %r" % (v.chrom, v.pos, joint[s_, :, :, Rr].tolist(), np.asarray(joint_counts)[s_].tolist()))
+    return joint[:, :, :, :Rr], cells[:, :, :, :Rr]
 
 
 def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr, P, fasta, max_depth, sampler, sampler_seed, threshold,
@@ -4436,7 +4624,7 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
     at_of = {m: n for n, m in enumerate(sorder)}
     var_at = [at_of[m] for m in members]
     axis = depth or rpb                         # (the cells' dict: one axis at most)
-    if rpb is not None:
+    if rpb is not None and mnv is None:
         read_bits = spike_read_bits(eng, up, A, lo, var) if caps is None else \
             spike_indel_read_bits(eng, up, A, lo, svar[var_at], spikes.ins[chrom])
         records = [spike_rpb_records(A, read_bits[g], np.flatnonzero(cov[g][:len(idents)]), rpb["p_idents"], rpb["first"])
@@ -4459,10 +4647,15 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
         joint_all = spike_phase_counts(eng, [lead[a] for a in first], joint, seeds, thr,
                                        [1 << 32] + ([frac_threshold(f) for f in depth["fracs"]] if depth is not None else []))
         joint_counts, joint_cells = joint_all[:, :, :, 0], joint_all[:, :, :, 1:]      # [sets, R, T, 4], [sets, R, T, F, 4]
+        if rpb is not None:
+            # (--spikeScanMnvRpb: the cells of the read axis, the sets' joint numbers and the members' own, counted per record on the device)
+            joint_cells, cells = _scan_joint_rpb(eng, run, rpb, var, cov, covers, lead, first, mnv["L"], seeds, thr, joint_counts, variants)
+            for g, k in enumerate(group):
+                rpb["counts"][k] = cells[g]
         set_ids = [int(mnv["set_of"][group[a]]) for a in first]
         for s_, i in enumerate(set_ids):
             mnv["counts"][i] = joint_counts[s_]
-            if depth is not None:
+            if axis is not None:
                 mnv["cell_counts"][i] = joint_cells[s_]
     for t in range(len(thr)):
         for b in range(0, R, room):
@@ -4473,7 +4666,8 @@ def _scan_pass(eng, run: AfRun, spikes: SpikeSet, members, variants, seeds, thr,
             tail += (dict(ins=spikes.ins[chrom], caps=caps, var=var, var_ins=ins,
                           want=[[(len(covers[g]), int(mine[g, j, t, 2])) for g in range(len(group))] for j in js]) if caps is not None else None,)
             if axis is not None:
-                want = [[[(int(cells[g, j, t, f, 0]), int(cells[g, j, t, f, 4])) for g in range(len(group))] for j in js] for f in range(F)]
+                # (N' and V1': the first and the last column, of the five of a listed variant or the four of a member under --spikeScanMnvRpb)
+                want = [[[(int(cells[g, j, t, f, 0]), int(cells[g, j, t, f, -1])) for g in range(len(group))] for j in js] for f in range(F)]
                 if depth is not None:
                     tail += (dict(fracs=depth["fracs"], params=depth["params"], thresholds=depth["thresholds"], var=var, var_ins=ins, want=want),)
                 else:

@@ -819,7 +819,9 @@ def scan(args):
     --spikeScan or without --spikeScanMnv; beside --spikeScanDepth, --spikeScanRpb, --spikeScanFilter or --spikeScanIndel the refusals
     of --spikeScanMnv above fire first.
     --spikeScanMnvDepth adds "mnv_fracs": the barcode fractions of the MNV scan's depth axis.  SystemExit: as the switch's, and what
-    --spikeScanDepth refuses of its text, named after this flag."""
+    --spikeScanDepth refuses of its text, named after this flag.
+    --spikeScanMnvRpb adds "mnv_rpbs": the reads-per-barcode targets of the MNV scan's read axis.  SystemExit: as the switch's, the flag
+    beside --spikeScanMnvDepth (the t x f x r grid is not built), and what --spikeScanRpb refuses of its text, named after this flag."""
     from .tools import spike_scan_lists as lists
     text, r, stride, alt = (getattr(args, f, None) for f in SCAN_FLAGS)
     indel = getattr(args, "spikeScanIndel", None)
@@ -830,11 +832,12 @@ def scan(args):
     mnv = getattr(args, "spikeScanMnv", None)
     mnv_flt = getattr(args, "spikeScanMnvFilter", None)
     mnv_fracs = getattr(args, "spikeScanMnvDepth", None)
+    mnv_rpbs = getattr(args, "spikeScanMnvRpb", None)
     given = lambda x: x not in (None, "", False)
     if not given(text):
         for flag, value in zip(SCAN_FLAGS[1:] + ("spikeScanIndel", "spikeScanDepth", "spikeScanRpb", "spikeScanFilter", "spikeScanBuild",
-                                                 "spikeScanMnv", "spikeScanMnvFilter", "spikeScanMnvDepth"),
-                               (r, stride, alt, indel, fracs, rpbs, flt, build, mnv, mnv_flt, mnv_fracs)):
+                                                 "spikeScanMnv", "spikeScanMnvFilter", "spikeScanMnvDepth", "spikeScanMnvRpb"),
+                               (r, stride, alt, indel, fracs, rpbs, flt, build, mnv, mnv_flt, mnv_fracs, mnv_rpbs)):
             if given(value):
                 raise SystemExit("--%s belongs to --spikeScan: it needs --spikeScan" % flag)
         return None
@@ -851,7 +854,7 @@ def scan(args):
             if given(value):
                 raise SystemExit("--spikeScanMnv cannot be combined with --%s: the %s axis of an MNV scan is not built" %
                                  (flag, {"spikeScanDepth": "depth", "spikeScanRpb": "reads-per-barcode", "spikeScanFilter": "filter"}[flag]))
-    for flag, value in (("spikeScanMnvFilter", mnv_flt), ("spikeScanMnvDepth", mnv_fracs)):
+    for flag, value in (("spikeScanMnvFilter", mnv_flt), ("spikeScanMnvDepth", mnv_fracs), ("spikeScanMnvRpb", mnv_rpbs)):
         if given(value) and not given(mnv):
             raise SystemExit("--%s belongs to --spikeScanMnv: it needs --spikeScanMnv" % flag)
     for flag in SCAN_NOT_WITH:
@@ -895,6 +898,11 @@ def scan(args):
         out["fracs"] = _scan_fracs(fracs, "spikeScanDepth", len(ts))
     if given(mnv_fracs):
         out["mnv_fracs"] = _scan_fracs(mnv_fracs, "spikeScanMnvDepth", len(ts))
+    if given(mnv_rpbs):
+        if given(mnv_fracs):
+            raise SystemExit("--spikeScanMnvRpb cannot be combined with --spikeScanMnvDepth in one run: the grid of targets x barcode "
+                             "fractions x reads-per-barcode targets is not built")
+        out["mnv_rpbs"] = _rpb_cells(mnv_rpbs, [(t, 0, "") for t in ts], "spikeScanMnvRpb")[0]
     if given(rpbs):
         if given(fracs):
             raise SystemExit("--spikeScanRpb cannot be combined with --spikeScanDepth in one run: the grid of targets x barcode fractions x "
@@ -1170,7 +1178,7 @@ def rpb_need_line(v, target, n: int, rpbs, rates, n_means, full_rate, full_n_mea
                       ["%g" % rpbs[k], dsaf.frac_text(n_means[k])]))
 
 
-def write_scan_rpb(out_prefix: str, loci, variants, targets, rpbs, mt_depth: int, run_rpb: float, full_entries, entries) -> None:
+def write_scan_rpb(out_prefix: str, loci, variants, targets, rpbs, mt_depth: int, run_rpb: float, full_entries, entries, mnv=None) -> None:
     """The pages of --spikeScanRpb.  loci, variants, targets, full_entries: write_scan_depth's; entries[(i, t, r)]: the replicates of the
     cell at rpbs[r] (scan_entry with the cell's counters); mt_depth, run_rpb: the run's --mtDepth (every cell is called at it) and --rpb.
       <outPrefix>.spikeScan.rpb.sensitivity.txt     a line per scanned locus, target and r: the pass's .spikeAF.rpb.sensitivity.txt line
@@ -1181,9 +1189,13 @@ def write_scan_rpb(out_prefix: str, loci, variants, targets, rpbs, mt_depth: int
       <outPrefix>.spikeScan.rpb.need.txt            rpb_need_line per scanned locus and target
       <outPrefix>.spikeScan<t>.r95.bedgraph         chrom, pos - 1, pos, R95 of the target as a number: `full` as run_rpb; twice the
                                                     larger of run_rpb and the largest listed r - above the axis - where it is NA and
-                                                    at a skipped locus"""
+                                                    at a skipped locus
+    `mnv` (write_scan_mnv_rpb: per variant and cell the line of its sensitivity page): the same pages of an MNV scan - `.mnv` in every
+    name, phase_sensitivity_header(RPB_AXIS) on the sensitivity page, N_ALL for N on the need page."""
     T, Rr = len(targets), len(rpbs)
-    i_rate = SCAN_RPB_SENSITIVITY_HEADER.index("RATE")
+    stem = "" if mnv is None else ".mnv"
+    head = SCAN_RPB_SENSITIVITY_HEADER if mnv is None else phase_sensitivity_header(RPB_AXIS)
+    i_rate = head.index("RATE")
     i_t95 = len(DEPTH_CURVE_HEADER) + T
     i_r95 = SCAN_RPB_NEED_HEADER.index("R95")
     above = "%g" % (2.0 * max([float(run_rpb)] + [float(r) for r in rpbs]))
@@ -1191,15 +1203,15 @@ def write_scan_rpb(out_prefix: str, loci, variants, targets, rpbs, mt_depth: int
     t95s = [[] for _ in range(Rr)]
     r95s = [[] for _ in range(T)]
     rate = lambda v, per: float(_called(v, per)) / len(per)
-    with open(out_prefix + ".spikeScan.rpb.sensitivity.txt", "w") as fs, open(out_prefix + ".spikeScan.rpb.curve.txt", "w") as fc, \
-            open(out_prefix + ".spikeScan.rpb.need.txt", "w") as fn:
-        fs.write("\t".join(SCAN_RPB_SENSITIVITY_HEADER) + "\n")
+    with open("%s.spikeScan%s.rpb.sensitivity.txt" % (out_prefix, stem), "w") as fs, \
+            open("%s.spikeScan%s.rpb.curve.txt" % (out_prefix, stem), "w") as fc, open("%s.spikeScan%s.rpb.need.txt" % (out_prefix, stem), "w") as fn:
+        fs.write("\t".join(head) + "\n")
         fc.write("\t".join(depth_curve_header(targets, False, RPB_AXIS)) + "\n")
-        fn.write("\t".join(SCAN_RPB_NEED_HEADER) + "\n")
+        fn.write("\t".join(SCAN_RPB_NEED_HEADER if mnv is None else SCAN_MNV_RPB_NEED_HEADER) + "\n")
         for i, v in enumerate(variants):
             for t, target in enumerate(targets):
                 for r, rpb in enumerate(rpbs):
-                    line = scan_depth_sensitivity_line(v, target, rpb, mt_depth, entries[(i, t, r)])
+                    line = scan_depth_sensitivity_line(v, target, rpb, mt_depth, entries[(i, t, r)]) if mnv is None else mnv[(i, t, r)]
                     rates.setdefault((t, r), []).append(line.split("\t")[i_rate])
                     fs.write(line + "\n")
                 per, full = [entries[(i, t, r)] for r in range(Rr)], full_entries[(i, t)]
@@ -1214,18 +1226,41 @@ def write_scan_rpb(out_prefix: str, loci, variants, targets, rpbs, mt_depth: int
                 fc.write(line + "\n")
     for t, target in enumerate(targets):
         for r, rpb in enumerate(rpbs):
-            with open("%s.spikeScan%g.dsRpb%g.rate.bedgraph" % (out_prefix, target, rpb), "w") as fh:
+            with open("%s.spikeScan%g.dsRpb%g%s.rate.bedgraph" % (out_prefix, target, rpb, stem), "w") as fh:
                 for chrom, pos, i in loci:
                     if i is not None:
                         fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), rates[(t, r)][i]))
-        with open("%s.spikeScan%g.r95.bedgraph" % (out_prefix, target), "w") as fh:
+        with open("%s.spikeScan%g%s.r95.bedgraph" % (out_prefix, target, stem), "w") as fh:
             for chrom, pos, i in loci:
                 text = above if i is None or r95s[t][i] == dsaf.NA else "%g" % run_rpb if r95s[t][i] == dsaf.FULL else r95s[t][i]
                 fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), text))
     for r, rpb in enumerate(rpbs):
-        with open("%s.spikeScan.dsRpb%g.t95.bedgraph" % (out_prefix, rpb), "w") as fh:
+        with open("%s.spikeScan.dsRpb%g%s.t95.bedgraph" % (out_prefix, rpb, stem), "w") as fh:
             for chrom, pos, i in loci:
                 fh.write("%s\t%d\t%d\t%s\n" % (chrom, int(pos) - 1, int(pos), "1" if i is None or t95s[r][i] == dsaf.NA else t95s[r][i]))
+
+
+# ---- --spikeScanMnvRpb: the MNV scan's pages per reads-per-barcode target
+SCAN_MNV_RPB_NEED_HEADER = tuple("N_ALL" if c == "N" else c for c in SCAN_RPB_NEED_HEADER)
+
+
+def write_scan_mnv_rpb(out_prefix: str, loci, variants, sets, targets, rpbs, mt_depth: int, run_rpb: float, full_entries, entries) -> None:
+    """The pages of --spikeScanMnvRpb.  loci, variants, sets, targets, full_entries: write_scan_mnv_depth's; entries[(i, t, r)]: the
+    replicates of the cell at rpbs[r], (dict(N_ALL, V0_ALL, S_ALL, V1_ALL), CALLED_ALL); mt_depth, run_rpb: write_scan_rpb's.
+      <outPrefix>.spikeScan.mnv.rpb.sensitivity.txt   phase_sensitivity_header(RPB_AXIS), then per scanned leader, target and r the set's
+                                                      cell line in .spikeAF.rpb.phase.sensitivity.txt of the pass's own run
+      <outPrefix>.spikeScan.mnv.rpb.curve.txt         .spikeScan.rpb.curve.txt's columns per leader - `full`, then every r -, REF and ALT
+                                                      the L letters, N_MEAN the mean N_ALL' of the cell
+      <outPrefix>.spikeScan<t>.dsRpb<r>.mnv.rate.bedgraph, .spikeScan.dsRpb<r>.mnv.t95.bedgraph   as --spikeScanRpb's, over the joint rates
+      <outPrefix>.spikeScan.mnv.rpb.need.txt          SCAN_RPB_NEED_HEADER with N_ALL for N: R95 / N95 by rpb_need_line's rule over the
+                                                      joint rates, N95 the mean N_ALL' there
+      <outPrefix>.spikeScan<t>.mnv.r95.bedgraph       R95 of the target, with the fill values of .spikeScan<t>.r95.bedgraph
+    write_scan_rpb with the joint counts standing where a variant's do."""
+    mnvs = [scan_mnv_variant(pset, variants) for pset in sets]
+    as_scan = lambda v, per: [scan_entry(v, dict(N=r["N_ALL"], V0=r["V0_ALL"], S=r["S_ALL"], READS=0, V1=r["V1_ALL"]), bool(c)) for r, c in per]
+    lines = {(i, t, r): phase_sensitivity_line(sets[i], variants, targets[t], rpbs[r], mt_depth, per) for (i, t, r), per in entries.items()}
+    write_scan_rpb(out_prefix, loci, mnvs, targets, rpbs, mt_depth, run_rpb, {(i, t): as_scan(mnvs[i], per) for (i, t), per in full_entries.items()},
+                   {(i, t, r): as_scan(mnvs[i], per) for (i, t, r), per in entries.items()}, mnv=lines)
 
 
 # ---- --spikeScanFilter: the scan's rates over the replicates that are called AND PASS, and a tally per FILTER name
